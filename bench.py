@@ -10,8 +10,15 @@ firstmm = configs[4]).  With --gpus N the tasks of a meta-batch are sharded over
 uneven shards when N does not divide task_num) and the meta-gradient is summed by one RCCL all-reduce per
 step.  Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up, times --steps steps and prints the headline line (`value`, `ms_per_step`, `dtype`, `config`, ...).
+--full adds every secondary measurement after the timed steps: roofline / MFMA / step bound over serialised steps, one-stream and
+deferred-read-back steps, the flagged schedules, end to end with a fresh extraction per step, the extraction roofline, the evaluation
+leg, the `box` calibration, the all-reduce alone and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed
+(accuracies, query losses, meta-gradient, updated parameters) as DIR/<name>.npy; the inputs are seeded, so two builds compare 1:1.
+
     python bench.py --gpus 1 --steps 5 --warmup 2
-    python bench.py --gpus 8 --steps 5 --warmup 2          (starts its own 8 ranks: re-executes itself under torch.distributed.run)
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full --dump-outputs out_dir
+    python bench.py --gpus 8 --steps 5 --warmup 2          (starts its own 8 ranks: runs torch.distributed.run as a child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 \
         bench.py --gpus 8 --steps 5 --warmup 2
 """
@@ -19,6 +26,7 @@ import argparse
 import ctypes as C
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -409,6 +417,20 @@ def launch_probe(a, rank, world, local):
                           'local_ranks': [int(g[1]) for g in got], 'tasks_per_rank': [int(g[2]) for g in got]}), flush=True)
 
 
+def dump_outputs(out_dir, maml, accs):
+    """--dump-outputs: what a caller of the timed step holds after the last one -- the accuracies Meta.forward returned, the per-step query
+    losses it recorded (last_stats), the meta-gradient it left in .grad and the parameters after the Adam step -- as <out_dir>/<name>.npy."""
+    import torch
+    params = list(maml.net.parameters())
+    arrays = {'accs': np.asarray(accs, np.float64),
+              'losses_q': np.asarray(maml.last_stats['losses_q'], np.float64),
+              'meta_grad': torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params]).float().cpu().numpy(),
+              'params': torch.cat([p.detach().reshape(-1) for p in params]).float().cpu().numpy()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), x)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -427,12 +449,15 @@ def main():
     ap.add_argument('--e2e_steps', type=int, default=10, help='N=1 only: extra steps with a FRESH extraction per step (prefetched on a second thread), reported under "end_to_end"; 0 = skip')
     ap.add_argument('--defer', type=int, default=0, help='1: Meta.forward_deferred, accuracies of step k read after step k+1 is queued')
     ap.add_argument('--roofline_steps', type=int, default=2, help='extra serialised steps after the timed region for the per-kernel roofline')
+    ap.add_argument('--full', action='store_true', help='also run every secondary measurement after the timed steps (see the module docstring); '
+                                                        '--no_cpu_baseline, --no_eval, --extra_steps, --e2e_steps and --roofline_steps act only with it')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed as DIR/<name>.npy')
     a = ap.parse_args()
 
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
-        # plain `python bench.py --gpus N`: become the launcher -- one rank per GPU under torch.distributed.run on this node, rendezvous on
-        # 127.0.0.1 at a free port; rank 0 of the relaunched job prints the one JSON line (exec: this process IS the launcher from here on)
-        os.execv(sys.executable, relaunch_command(a.gpus, sys.argv[1:]))
+        # plain `python bench.py --gpus N`: start the launcher -- one rank per GPU under torch.distributed.run on this node, rendezvous on
+        # 127.0.0.1 at a free port; rank 0 of that job prints the one JSON line.  A child process, before anything here has touched a GPU.
+        raise SystemExit(subprocess.call(relaunch_command(a.gpus, sys.argv[1:])))
 
     import torch
     import torch.distributed as dist
@@ -550,6 +575,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
     ms_per_step = dt / a.steps * 1e3
+    if a.dump_outputs and rank == 0:        # before anything below steps the model again
+        dump_outputs(a.dump_outputs, maml, accs)
     # ---- per-kernel roofline of the aggregate: in the timed region the support chain and the query evaluations share
     # the GPU on two streams, which stretches every kernel; the kernel-alone duration is measured on extra steps with
     # serialize=1 (same inputs, same launches, one stream) -- the rocprofv3 summary under profiles/ uses the same mode.
@@ -561,7 +588,7 @@ def main():
     ser_steps = a.steps if a.serialize else 0
     one_stream_ms = None
     deferred_ms = None
-    if not a.serialize and not a.defer and a.roofline_steps > 0:
+    if a.full and not a.serialize and not a.defer and a.roofline_steps > 0:
         # the same steps with the accuracies of step k read after step k + 1 is queued (Meta.forward_deferred -- what train.py does between its report
         # steps): the host prologue of a step then runs while the GPU still works on the previous one.  `value` keeps the reference's calling
         # convention (Meta.forward returns the accuracies of every step).
@@ -577,7 +604,7 @@ def main():
             pend.pop(0).accs()
         torch.cuda.synchronize()
         deferred_ms = (time.perf_counter() - te) / nd * 1e3
-    if not a.serialize and a.roofline_steps > 0:            # every rank takes part: Meta.forward all-reduces when N > 1
+    if a.full and not a.serialize and a.roofline_steps > 0:     # every rank takes part: Meta.forward all-reduces when N > 1
         # the same step on ONE stream (no events): what the two queues buy -- kernels of the support chain and of the query evaluations side by side,
         # the stream aggregate's workgroups inside the CUs a persistent GEMM workgroup of the other queue occupies
         maml.serialize = 1
@@ -613,7 +640,7 @@ def main():
         ser_steps = a.roofline_steps
     lib.gm_profile_enable(0)
     box = None
-    if rank == 0 and not os.environ.get('GMETA_NO_BOX'):
+    if a.full and rank == 0 and not os.environ.get('GMETA_NO_BOX'):
         try:
             box = box_calibration(lib, _lib, batches[0][2][0].view_of)
         except Exception as e:         # a calibration aid, never the product path
@@ -621,7 +648,7 @@ def main():
     # ---- secondary numbers: the flagged schedules that produce identical results without the structural zeros /
     # loop-invariant recomputation (never the headline `value`)
     extra = {}
-    if world == 1 and a.extra_steps > 0 and not (a.sparse_bwd or a.hoist_z1 or a.serialize or a.cone):
+    if a.full and world == 1 and a.extra_steps > 0 and not (a.sparse_bwd or a.hoist_z1 or a.serialize or a.cone):
         _skip = set(os.environ.get('GMETA_BENCH_SKIP', '').split(','))
         for name, kw in (('sparse_bwd', dict(sparse_bwd=1)), ('sparse_bwd+hoist_z1', dict(sparse_bwd=1, hoist_z1=1)),
                          ('cone', dict(sparse_bwd=0, hoist_z1=0, cone=1)), ('cone+hoist_z1', dict(cone=1, hoist_z1=1))):
@@ -741,7 +768,7 @@ def main():
             lv[side] = {'batch_rows': int(x.rows), 'batch_edges': int(x.edges), 'level_rows': list(nr), 'level_edges': list(ne)}
         extra['cone']['receptive_field'] = lv
     # ---- evaluation leg (BASELINE configs[3]: "x10 eval tasks"): Meta.finetunning over eval_tasks tasks in one batched call
-    if n_eval > 0 and not (a.sparse_bwd or a.hoist_z1 or a.serialize or a.cone):
+    if a.full and n_eval > 0 and not (a.sparse_bwd or a.hoist_z1 or a.serialize or a.cone):
         base = T * (a.n_batches + a.e2e_steps + 2)
         ev = db.get_batch(list(range(base, base + n_eval)))
         maml.finetunning_batch(ev[0], ev[1], ev[2], ev[3])
@@ -757,7 +784,7 @@ def main():
 
     # ---- end to end ("report also with extraction included"): every step extracts its own meta-batch
     e2e = None
-    if world == 1 and a.e2e_steps > 0:
+    if a.full and world == 1 and a.e2e_steps > 0:
         # e2e_steps + 2 distinct meta-batches, walked n_e times in a row like the epochs of train.py (the task tables are fixed at construction,
         # sdp.py:150-292; their per-task host arrays are memoised after the first visit, as the reference memoises its subgraphs)
         lists = [list(range((a.n_batches + k) * T, (a.n_batches + k + 1) * T)) for k in range(a.e2e_steps + 2)]
@@ -789,7 +816,7 @@ def main():
     # ---- extraction kernels against the HBM roofline (SURVEY 8(d) "k-hop expansion, induce: HBM bandwidth"): one more extraction of the first
     # meta-batch with HIP events around k_nodes / k_fill / the finalisation (gm_profile_read categories 8-10), bytes from the actual batch
     extraction = None
-    if world == 1 and not (a.serialize or a.cone or a.sparse_bwd or a.hoist_z1):
+    if a.full and world == 1 and not (a.serialize or a.cone or a.sparse_bwd or a.hoist_z1):
         idx0 = list(range(lo, hi))
         torch.cuda.synchronize()
         reps = 3
@@ -831,7 +858,6 @@ def main():
                       'note': 'latency-bound integer work: one workgroup per subgraph, adjacency lists walked through dependent loads; the induced '
                               'subgraphs are built in two phases (count, then fill) so the lists are walked twice against the one pass priced here'}
         del bx
-    # ---- the one collective of a sharded meta-step, timed on its own (same buffer size, same stream): what the step's value already contains
     allreduce = None
     rank_report = None
     if use_dist:
@@ -841,6 +867,8 @@ def main():
         dist.all_gather(got, mine)
         rank_report = {'ranks_reporting': [int(g[0]) for g in got], 'devices': [int(g[1]) for g in got], 'tasks_per_rank': [int(g[2]) for g in got],
                        'rows_per_rank': [int(g[3]) for g in got], 'backend': dist.get_backend()}
+    if use_dist and a.full:
+        # the one collective of a sharded meta-step, timed on its own (same buffer size, same stream): what the step's value already contains
         P_ = sum(p.numel() for p in maml.net.parameters())
         buf = torch.zeros(P_ + 2 * (cfg['update_step'] + 1) + 1, dtype=torch.float32, device='cuda')
         for _ in range(5):
@@ -904,7 +932,7 @@ def main():
                                     'full (reference-equivalent: every forward/backward dense over all subgraph rows)'),
                        'fused_aggregate_gemm': bool(fused),
                        'last_layer_stores': 'every row of the last GraphConv is computed (and its relu bits written where a backward pass follows); the activation is stored at the centre rows the head gathers '
-                                            '(extra.store_every_row: the same step with GM_CENTRE_STORE=0)',
+                                            '(--full, extra.store_every_row: the same step with GM_CENTRE_STORE=0)',
                        'streams': 1 if a.serialize else 2,
                        'readback': 'deferred by one step (Meta.forward_deferred)' if a.defer else 'every step (Meta.forward returns the accuracies)',
                        'parallelism': 'tasks sharded over %d rank(s) (rank 0: %d of %d), one all-reduce of the meta-gradient per step' % (world, hi - lo, T),
@@ -932,6 +960,8 @@ def main():
                                         'DISTINCT source rows read once -- counted on the device per batch).  GM_FUSE_AGG=0 gives the all-full-launch sample of the earlier rounds.')
                                        if fused else 'full launches only (fused aggregate+GEMM off or not applicable to this schedule)'},
         }
+        if not (a.full or a.serialize):     # its numbers come from serialised steps: the timed region's own (--serialize 1) or those --full adds
+            del out['roofline']
         if mm[1][0] + mm[4][0] + mm[6][0] > 0:
             # Every launch is priced on the matrix pipe it ran on: the exact-fp32 kernels (v_mfma_f32_32x32x2_f32) against the 157.3 TFLOP/s dense
             # fp32 matrix peak, the split-bf16 kernels -- which issue SIX bf16 MFMA flops per flop of the fp32 product -- against 2.5 PFLOP/s bf16.
@@ -1004,7 +1034,7 @@ def main():
             out['end_to_end'] = e2e
         if extra:
             out['extra'] = {'note': 'flagged exact schedules (same accs/meta-gradient, golden-tested) and the evaluation leg; not the headline value', **extra}
-        if not a.no_cpu_baseline and world == 1:           # rank 0 at N=1 only
+        if a.full and not a.no_cpu_baseline and world == 1:    # rank 0 at N=1 only
             try:
                 out['cpu_baseline'] = cpu_baseline(db, data, cfg, config, batches[0])
             except Exception as e:   # the baseline is a reported number, never the product path

@@ -2,7 +2,7 @@
 # round-6 baseline on one box: default bench line, host timing of a batch build, 4-task shard with grid caps
 cd "$(dirname "$0")/.."
 O=gpurun_out/r06_base; mkdir -p $O
-python bench.py > $O/bench_arxiv.json 2> $O/bench_arxiv.err
+python bench.py --full > $O/bench_arxiv.json 2> $O/bench_arxiv.err
 tail -c 3000 $O/bench_arxiv.json
 GM_TIMING=1 python tools/extract_prof.py > $O/extract_prof.txt 2>&1
 for g in 0 224 192 160 128; do for rep in 1 2; do

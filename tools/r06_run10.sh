@@ -3,10 +3,10 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/r06_run10; mkdir -p $O
 timeout 1200 python -m pytest tests -m gpu -x -q > $O/pytest.txt 2>&1; tail -4 $O/pytest.txt
 for c in firstmm tissue syn0; do
-  timeout 600 python bench.py --config $c --no_cpu_baseline > $O/bench_$c.json 2> $O/bench_$c.err
+  timeout 600 python bench.py --full --config $c --no_cpu_baseline > $O/bench_$c.json 2> $O/bench_$c.err
 done
-timeout 600 python bench.py --task_num 4 --no_cpu_baseline > $O/bench_t4_shard.json 2> $O/bench_t4.err
-timeout 900 python bench.py --no_cpu_baseline > $O/bench_arxiv.json 2> $O/bench_arxiv.err
+timeout 600 python bench.py --full --task_num 4 --no_cpu_baseline > $O/bench_t4_shard.json 2> $O/bench_t4.err
+timeout 900 python bench.py --full --no_cpu_baseline > $O/bench_arxiv.json 2> $O/bench_arxiv.err
 python - <<'PY'
 import json
 for c in ['firstmm','tissue','syn0','t4_shard','arxiv']:

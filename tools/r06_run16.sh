@@ -1,7 +1,7 @@
 #!/bin/bash
 cd "$(dirname "$0")/.."
 O=gpurun_out/r06_run16; mkdir -p $O
-S=$(date +%s.%N); python bench.py > $O/bench_default.json 2> $O/bench_default.err; E=$(date +%s.%N); echo "bench.py default wall: $(echo "$E - $S" | bc) s"
+S=$(date +%s.%N); python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; E=$(date +%s.%N); echo "bench.py default wall: $(echo "$E - $S" | bc) s"
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r06_run16/bench_default.json').read().strip().splitlines()[-1])

@@ -10,7 +10,7 @@ timeout 600 rocprofv3 --kernel-trace --stats -d $out/p$L -o x -- python tools/bu
 python tools/prof_summary.py "$(db $out/p$L)" > $out/build_L${L}_kernel_stats.txt
 grep "^build" $out/build_L$L.log; head -22 $out/build_L${L}_kernel_stats.txt | cut -c1-130; tail -1 $out/build_L${L}_kernel_stats.txt
 rm -rf $out/p$L
-timeout 600 python bench.py > $out/bench.txt 2>&1; tail -1 $out/bench.txt | python -c "
+timeout 600 python bench.py --full > $out/bench.txt 2>&1; tail -1 $out/bench.txt | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 print(d['value'], d['ms_per_step'], d['roofline']['frac'])

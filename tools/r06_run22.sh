@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/r06_run22; mkdir -p $out
 timeout 2400 python -m pytest tests -m gpu -x -q > $out/tests.txt 2>&1; tail -4 $out/tests.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-timeout 900 python bench.py > $out/bench.txt 2>&1; tail -1 $out/bench.txt > $out/bench.json; python - <<'PY'
+timeout 900 python bench.py --full > $out/bench.txt 2>&1; tail -1 $out/bench.txt > $out/bench.json; python - <<'PY'
 import json
 d = json.load(open('gpurun_out/r06_run22/bench.json'))
 print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['box']['split_gemm']['fp32_equivalent_tflops'], d['box']['hbm_copy']['GBps'])

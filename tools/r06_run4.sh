@@ -4,7 +4,7 @@ O=gpurun_out/r06_run4; mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest.txt 2>&1; tail -5 $O/pytest.txt
 GM_TIMING=1 python tools/extract_prof.py > $O/extract_prof.txt 2>&1
 grep -v "gm timing" $O/extract_prof.txt | sed -n 2,2p
-python bench.py --no_cpu_baseline > $O/bench_arxiv.json 2> $O/bench_arxiv.err
+python bench.py --full --no_cpu_baseline > $O/bench_arxiv.json 2> $O/bench_arxiv.err
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r06_run4/bench_arxiv.json').read().strip().splitlines()[-1])
