@@ -374,8 +374,8 @@ __global__ __launch_bounds__(AGG_BLOCK) void k_agg_win(AggK a) {
 // 65536 / 2 -> these rules: 4-task arxiv shard 4.31 -> 4.17 ms, task_num 32 24.43 -> 24.25, Tissue shape 3.65 -> 3.36.
 int gm_agg_window(int64_t rows, int64_t edges) {
     const bool dense = edges > 8 * rows;
-    const int min_waves = gm_knob().agg_min_waves > 0 ? gm_knob().agg_min_waves : (dense ? 16384 : 32768);
-    const int min_win = gm_knob().agg_min_win > 0 ? gm_knob().agg_min_win : (dense ? 4 : 2);
+    const int min_waves = dense ? 16384 : 32768;
+    const int min_win = dense ? 4 : 2;
     int win = 64;
     while (win > min_win && rows / win < min_waves) win >>= 1;
     return win;
@@ -429,15 +429,14 @@ int gm_agg_schedule_flat(gm_batch* b, int64_t rows, int win, const int32_t* pos,
 
 int gm_agg_schedule(gm_batch* b, int64_t rows, int win, const int32_t* heavy_host, const int32_t* heavy_deg_host, int n_heavy, gm_agg_sched* out, hipStream_t s, gm_stager* sg) {
     *out = gm_agg_sched{};
-    const int on = gm_knob().agg_sched, part_env = gm_knob().agg_hub_part;      // part_env 0: one block per hub row
-    if (!on || n_heavy <= 0 || rows <= 0) return GM_OK;                  // no hub rows: the plain window launch
-    // edges per hub part: a multiple of 16, at most 32 parts for the widest row
+    if (n_heavy <= 0 || rows <= 0) return GM_OK;                  // no hub rows: the plain window launch
+    // edges per hub part: 128, or more (a multiple of 16) so that the widest row has at most 32 parts
     int hub_part = 0;
     std::vector<int32_t> tab;                                           // [part_off: n_heavy+1][part_hub: parts][counters: n_heavy]
-    if (part_env > 0 && heavy_deg_host) {
+    if (heavy_deg_host) {
         int maxdeg = 0;
         for (int k = 0; k < n_heavy; ++k) maxdeg = std::max(maxdeg, heavy_deg_host[k]);
-        hub_part = std::max((part_env + 15) / 16 * 16, ((maxdeg + 31) / 32 + 15) / 16 * 16);
+        hub_part = std::max(128, ((maxdeg + 31) / 32 + 15) / 16 * 16);
         tab.assign(n_heavy + 1, 0);
         for (int k = 0; k < n_heavy; ++k) tab[k + 1] = tab[k] + std::max(1, (heavy_deg_host[k] + hub_part / 2) / hub_part);      // nearest: a row is split from 1.5 parts upwards
         const int parts = tab[n_heavy];
@@ -471,10 +470,6 @@ static void launch_win(const AggK& a0, hipStream_t s) {
     int grid = a.nblocks;
     if (a.sched) grid = GM_NXCD * a.sched_len;
     else if (a.n_heavy > 0) hipLaunchKernelGGL((k_agg_heavy<LPR, NCH>), dim3(a.n_heavy), dim3(AGG_HEAVY_BLOCK), 0, s, a);
-    const int unr = gm_knob().agg_unr;
-#define GM_AGG_CASE(U_, M_) if (unr == U_ * 10 + M_) { hipLaunchKernelGGL((k_agg_win<LPR, NCH, U_, M_>), dim3(grid), dim3(AGG_BLOCK), 0, s, a); return; }
-    GM_AGG_CASE(1, 2) GM_AGG_CASE(1, 4) GM_AGG_CASE(2, 2) GM_AGG_CASE(2, 4) GM_AGG_CASE(4, 2) GM_AGG_CASE(4, 4) GM_AGG_CASE(3, 4) GM_AGG_CASE(2, 6) GM_AGG_CASE(2, 8) GM_AGG_CASE(1, 8)
-#undef GM_AGG_CASE
     hipLaunchKernelGGL((k_agg_win<LPR, NCH, 2, 4>), dim3(grid), dim3(AGG_BLOCK), 0, s, a);
 }
 
@@ -486,14 +481,10 @@ static void launch_one(const AggK& a0, hipStream_t s) {
     hipLaunchKernelGGL((k_agg<VEC, LPR>), dim3(a.nblocks), dim3(AGG_BLOCK), 0, s, a);
 }
 
-// Non-temporal stores of the output: 0 never, 2 always, 1 (default) from 128 MB of output upwards -- a small output stays in the caches for
-// the GEMM that reads it next (Tissue shape -1.3 %, FirstMM shape -1 %); at 146 MB (the support batch at task_num 32, the query batch of a
+// Non-temporal stores of the output from 128 MB of output upwards -- a small output stays in the caches for the GEMM that reads it next
+// (Tissue shape -1.3 %, FirstMM shape -1 % against non-temporal stores at every size); at 146 MB (the support batch at task_num 32, the query batch of a
 // 4-task shard) the two are within noise of each other, at 572k rows ordinary stores lose 1.5 %.
-static int agg_nt(int64_t rows, int width) {
-    const int k = gm_knob().agg_nt;
-    return k == 1 ? (rows * (int64_t)width * 4 >= ((int64_t)128 << 20) ? 1 : 0) : (k ? 1 : 0);
-}
-static int agg_variant() { return gm_knob().agg_variant; }
+static int agg_nt(int64_t rows, int width) { return rows * (int64_t)width * 4 >= ((int64_t)128 << 20) ? 1 : 0; }
 
 int gm_launch_aggregate(const gm_agg_args& g, hipStream_t s) {
     if (g.rows <= 0) return GM_OK;
@@ -507,7 +498,7 @@ int gm_launch_aggregate(const gm_agg_args& g, hipStream_t s) {
     const bool bias_ok = !g.bias || ((((uintptr_t)g.bias & 15) == 0) && (g.bias_stride % 4 == 0));
     const bool mask_ok = !g.mask_h || (((uintptr_t)g.mask_h & 15) == 0);
     GM_REQUIRE(!(g.mask_b || g.relu_bits) || vec4, GM_EINVAL, "aggregate: packed relu masks need width %% 4 == 0 and 16-byte aligned operands");
-    const bool win = vec4 && bias_ok && mask_ok && (g.width == 64 || g.width == 128 || g.width == 256 || g.width == 512) && agg_variant() != 1;
+    const bool win = vec4 && bias_ok && mask_ok && (g.width == 64 || g.width == 128 || g.width == 256 || g.width == 512);
     GM_REQUIRE(!g.rowlist || win, GM_EINVAL, "aggregate: a row list needs the window kernel");
     if (!win) { a.heavy = nullptr; a.n_heavy = 0; a.sched = nullptr; a.hub = nullptr; }      // the generic kernel walks every row itself
     if (win && gm_knob().agg_stream && gm_stream_ok(g)) return gm_launch_stream(g, a.nt, s);      // LDS-DMA stream kernel (row segments + hub parts in one launch)

@@ -30,6 +30,8 @@
 typedef int as_i4 __attribute__((ext_vector_type(4)));
 
 #define AS_WAVES 4                      // waves per workgroup: one per SIMD
+#define AS_WAVE_COST 96                 // edges + rows per wave of a launch (gm_stream_wgs)
+#define AS_DEPTH_KIB 12                 // KiB of gathers in flight per wave: R ring slots of LPR * 16 bytes (12 beat 8)
 
 // ---- scalar-cache loads.  SMEM returns out of order and the compiler does not count asm loads: every use sits behind an explicit lgkmcnt(0).
 // Addresses are formed in full by scalar arithmetic (no register offset operand).
@@ -322,15 +324,12 @@ __global__ void k_stream_segs(const int32_t* sptr, int64_t rows, int n_seg, int2
     seg[k] = make_int2(first_row(k), first_row(k + 1));
 }
 
-// Workgroups of a stream launch over a table of `cost` (edges + rows): a multiple of the XCD count.  Waves get SHORT runs (~GM_AGG_STREAM_COST cost units each, about
+// Workgroups of a stream launch over a table of `cost` (edges + rows): a multiple of the XCD count.  Waves get SHORT runs (~AS_WAVE_COST cost units each, about
 // 30 rows and their edges): the workgroups resident on an XCD at one time then sweep a few dozen consecutive subgraphs, and the second gather of a source row -- by
 // another row of its subgraph -- still finds it in that XCD's L2 (1.14 M-row launch at width 256: 534 us with 768 long-lived workgroups, 437 us with 6,144;
 // window kernel 494-518).  Too short and a wave's start-up (descriptor chunk + first round trip) dominates (142 k-row launch: best at ~1,500 workgroups).
 int gm_stream_wgs(int64_t cost) {
-    const int per_cu = gm_knob().agg_stream_wgs;
-    if (per_cu > 0) return std::max(2 * GM_NXCD, gm_num_cus() * per_cu / GM_NXCD * GM_NXCD);
-    const int64_t per_wave = std::max(16, gm_knob().agg_stream_cost);
-    const int64_t wgs = (cost / per_wave + AS_WAVES - 1) / AS_WAVES;
+    const int64_t wgs = (cost / AS_WAVE_COST + AS_WAVES - 1) / AS_WAVES;
     return (int)std::min<int64_t>(65536, std::max<int64_t>(gm_num_cus() * 3 / GM_NXCD * GM_NXCD, (wgs + GM_NXCD - 1) / GM_NXCD * GM_NXCD));
 }
 
@@ -426,7 +425,6 @@ static void launch_stream(const AggS& a, int nwg, hipStream_t s) {
 // The stream launch of a full aggregate over the batch the tables belong to; false: not eligible (the caller takes the window kernel)
 bool gm_stream_ok(const gm_agg_args& g) {
     if (!g.stream || g.s_out || g.bias || g.mask_h || g.mask_b || g.relu || g.relu_bits) return false;
-    if (g.stream_feat && !gm_knob().agg_stream_gather) return false;
     if (g.rowlist || g.skip_on) return false;                                  // partial launches stay on the window kernel (measured: profiles/r05_experiments_not_shipped.txt C.1)
     // The stream kernel takes every per-edge quantity from the batch's stream tables: the launch described by `g` must BE that aggregate -- same
     // orientation, rows, per-edge weights and (layer 1) per-edge feature rows -- or the window kernel, which reads g's own arrays, computes it
@@ -449,11 +447,11 @@ int gm_launch_stream(const gm_agg_args& g, int nt, hipStream_t s) {
     { static const int pr = getenv("GM_AGG_STREAM_PRIO") ? atoi(getenv("GM_AGG_STREAM_PRIO")) : 0; a.prio = pr; }
     if (g_stream_dbg && 2 * b->stream_nwg[o] <= g_stream_dbg_n) a.dbg = g_stream_dbg;
 #endif
-    const int depth = gm_knob().agg_stream_depth, nwg = b->stream_nwg[o];
-    // (ring depths: 8 / 12 KiB of gathers in flight per wave; beyond ~15 KiB per wave the workgroup's LDS would pass 64 KiB -- the reach of M0's 16-bit DMA base)
-    if (g.width == 256) { if (depth == 8) launch_stream<64, 8>(a, nwg, s); else launch_stream<64, 12>(a, nwg, s); }
-    else if (g.width == 128) { if (depth == 8) launch_stream<32, 16>(a, nwg, s); else launch_stream<32, 24>(a, nwg, s); }
-    else { if (depth == 8) launch_stream<16, 32>(a, nwg, s); else launch_stream<16, 48>(a, nwg, s); }
+    const int nwg = b->stream_nwg[o];
+    // (ring depth: AS_DEPTH_KIB of gathers in flight per wave; beyond ~15 KiB per wave the workgroup's LDS would pass 64 KiB -- the reach of M0's 16-bit DMA base)
+    if (g.width == 256) launch_stream<64, AS_DEPTH_KIB>(a, nwg, s);
+    else if (g.width == 128) launch_stream<32, 2 * AS_DEPTH_KIB>(a, nwg, s);
+    else launch_stream<16, 4 * AS_DEPTH_KIB>(a, nwg, s);
     GM_HIP(hipGetLastError());
     return GM_OK;
 }

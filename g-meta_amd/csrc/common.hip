@@ -336,33 +336,11 @@ const gm_knobs& gm_knob() {
     std::call_once(g_knobs_once, [] {
         gm_knobs& k = g_knobs;
         auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
-        k.agg_min_waves = env("GM_AGG_MIN_WAVES", 0);                   // 0: by batch density (gm_agg_window)
-        k.agg_min_win = std::max(0, env("GM_AGG_MIN_WIN", 0));          // 0: by batch density
-        k.agg_sched = env("GM_AGG_SCHED", 1);
-        k.agg_hub_part = env("GM_AGG_HUB_PART", 128);                  // 0: one block per hub row
-        k.agg_unr = env("GM_AGG_UNR", 24);
-        k.agg_nt = env("GM_AGG_NT", 1);
-        k.agg_variant = env("GM_AGG_VARIANT", 0);                      // 1 = force the generic row-per-group kernel (debug)
-        k.agg_edge_tables = env("GM_AGG_EDGE_TABLES", 1);
-        k.heavy_deg = env("GM_HEAVY_DEG", 0);                          // 0 = by batch density (gm_heavy_deg_for)
-        k.extract_global_bitmap = env("GM_EXTRACT_GLOBAL_BITMAP", 0);
-        k.feat_pad = env("GM_FEAT_PAD", 1);
         k.timing = env("GM_TIMING", 0);
         const char* gm = getenv("GM_GEMM_MODE");
         k.gemm_mode = (gm && (!strcmp(gm, "split") || !strcmp(gm, "1"))) ? 1 : (gm && (!strcmp(gm, "f32") || !strcmp(gm, "0"))) ? 0 : -1;
         k.gemm_split_min_tiles = env("GM_GEMM_SPLIT_MIN_TILES", -1);
-        k.gemm_split_grid = env("GM_GEMM_SPLIT_GRID", 0);
-        k.gemm_fused_rounds = std::max(0, env("GM_GEMM_FUSED_ROUNDS", 0));          // 0: by launch size (gemm.hip)
-        k.gemm_plain_rounds = std::max(1, env("GM_GEMM_PLAIN_ROUNDS", 1));
         k.centre_store = env("GM_CENTRE_STORE", 2);
-        k.gemm_half_tiles = env("GM_GEMM_HALF_TILES", 1);
-        k.gemm_bn = env("GM_GEMM_BN", 256);
-        k.gemm_mid_tiles = env("GM_GEMM_MID_TILES", 1536);
-        k.gemm_glds = env("GM_GEMM_GLDS", 1);
-        k.gemm_nt = env("GM_GEMM_NT", 1);
-        k.gemm_small = env("GM_GEMM_SMALL", 1);
-        k.wgrad_split = env("GM_WGRAD_SPLIT", 1);
-        k.dz_glds = env("GM_DZ_GLDS", 1);
         k.fuse_agg = env("GM_FUSE_AGG", 1);
         k.fuse_diff = env("GM_FUSE_DIFF", 2);
         k.extract_pref16 = env("GM_EXTRACT_PREF16", 1);
@@ -371,18 +349,11 @@ const gm_knobs& gm_knob() {
         k.query_streams = env("GM_QUERY_STREAMS", 0);
         k.agg_mid_list = env("GM_AGG_MID_LIST", 1);
         k.agg_mid_win = env("GM_AGG_MID_WIN", 0);
-        k.side_stream_priority = env("GM_SIDE_STREAM_PRIORITY", 1);
-        k.wgrad_round_bias = env("GM_WGRAD_ROUND_BIAS", 25);
         k.split_pieces = env("GM_SPLIT_PIECES", 3);                   // 3: every operand carries its full 24 significand bits (the reference multiplies in fp32, learner.py:36,47); 2 = opt-in fast mode
         k.split16_min_rows = env("GM_SPLIT16_MIN_ROWS", 65536);
-        k.cu_mask_support = env("GM_CU_MASK_SUPPORT", 0);
         k.wgrad_split_min_chunks = env("GM_WGRAD_SPLIT_MIN_CHUNKS", -1);
         k.agg_stream = env("GM_AGG_STREAM", 1);
         k.agg_stream_min_rows = env("GM_AGG_STREAM_MIN_ROWS", 100000);
-        k.agg_stream_wgs = env("GM_AGG_STREAM_WGS", 0);
-        k.agg_stream_cost = env("GM_AGG_STREAM_COST", 96);
-        k.agg_stream_gather = env("GM_AGG_STREAM_GATHER", 1);
-        k.agg_stream_depth = env("GM_AGG_STREAM_DEPTH", 12);
     });
     return k;
 }
@@ -395,12 +366,9 @@ extern "C" int32_t gm_tuning_epoch(void) { return g_tuning_epoch.load(std::memor
 static int gm_knobs::* gm_find_knob(const char* name) {
     (void)gm_knob();
     static const struct { const char* name; int gm_knobs::*field; } tab[] = {
-        {"GM_AGG_MIN_WAVES", &gm_knobs::agg_min_waves}, {"GM_AGG_MIN_WIN", &gm_knobs::agg_min_win}, {"GM_AGG_UNR", &gm_knobs::agg_unr}, {"GM_AGG_NT", &gm_knobs::agg_nt},
-        {"GM_AGG_VARIANT", &gm_knobs::agg_variant}, {"GM_GEMM_SPLIT_MIN_TILES", &gm_knobs::gemm_split_min_tiles}, {"GM_GEMM_SPLIT_GRID", &gm_knobs::gemm_split_grid},
-        {"GM_GEMM_FUSED_ROUNDS", &gm_knobs::gemm_fused_rounds}, {"GM_GEMM_PLAIN_ROUNDS", &gm_knobs::gemm_plain_rounds}, {"GM_CENTRE_STORE", &gm_knobs::centre_store}, {"GM_GEMM_HALF_TILES", &gm_knobs::gemm_half_tiles},
-        {"GM_GEMM_BN", &gm_knobs::gemm_bn}, {"GM_GEMM_MID_TILES", &gm_knobs::gemm_mid_tiles}, {"GM_GEMM_GLDS", &gm_knobs::gemm_glds}, {"GM_GEMM_NT", &gm_knobs::gemm_nt},
-        {"GM_GEMM_SMALL", &gm_knobs::gemm_small}, {"GM_WGRAD_SPLIT", &gm_knobs::wgrad_split}, {"GM_DZ_GLDS", &gm_knobs::dz_glds}, {"GM_HEAD_STAGE", &gm_knobs::head_stage}, {"GM_HEAD_THREADS", &gm_knobs::head_threads}, {"GM_QUERY_STREAMS", &gm_knobs::query_streams}, {"GM_AGG_MID_LIST", &gm_knobs::agg_mid_list}, {"GM_AGG_MID_WIN", &gm_knobs::agg_mid_win}, {"GM_AGG_STREAM", &gm_knobs::agg_stream}, {"GM_AGG_STREAM_DEPTH", &gm_knobs::agg_stream_depth}, {"GM_AGG_STREAM_MIN_ROWS", &gm_knobs::agg_stream_min_rows},
-        {"GM_SPLIT16_MIN_ROWS", &gm_knobs::split16_min_rows}, {"GM_WGRAD_SPLIT_MIN_CHUNKS", &gm_knobs::wgrad_split_min_chunks}, {"GM_WGRAD_ROUND_BIAS", &gm_knobs::wgrad_round_bias}, {"GM_TIMING", &gm_knobs::timing},
+        {"GM_GEMM_SPLIT_MIN_TILES", &gm_knobs::gemm_split_min_tiles}, {"GM_CENTRE_STORE", &gm_knobs::centre_store},
+        {"GM_HEAD_STAGE", &gm_knobs::head_stage}, {"GM_HEAD_THREADS", &gm_knobs::head_threads}, {"GM_QUERY_STREAMS", &gm_knobs::query_streams}, {"GM_AGG_MID_LIST", &gm_knobs::agg_mid_list}, {"GM_AGG_MID_WIN", &gm_knobs::agg_mid_win}, {"GM_AGG_STREAM", &gm_knobs::agg_stream}, {"GM_AGG_STREAM_MIN_ROWS", &gm_knobs::agg_stream_min_rows},
+        {"GM_SPLIT16_MIN_ROWS", &gm_knobs::split16_min_rows}, {"GM_WGRAD_SPLIT_MIN_CHUNKS", &gm_knobs::wgrad_split_min_chunks}, {"GM_TIMING", &gm_knobs::timing},
         {"GM_FUSE_DIFF", &gm_knobs::fuse_diff}, {"GM_EXTRACT_PREF16", &gm_knobs::extract_pref16},
     };
     for (const auto& e : tab)
@@ -420,13 +388,12 @@ extern "C" int32_t gm_get_tuning(const char* name) {
     return f ? g_knobs.*f : 0;
 }
 
-int gm_heavy_deg() { return gm_knob().heavy_deg > 0 ? std::max(2, gm_knob().heavy_deg) : 64; }
+int gm_heavy_deg() { return 64; }
 // Rows with more in-edges than this leave the wave windows for whole workgroups (hub parts).  A window row walks its edges four loads at a
 // time, so a 60-edge row is a ~30-us serial chain -- the fixed cost of every launch over SPARSE induced subgraphs (arxiv shape: mean
 // in-degree 2, a few hundred rows above 32), where 32 is better (4-task shard 4.73 -> 4.64 ms, roofline 0.50 -> 0.515 at task_num 32).
 // Dense subgraphs (Tissue shape: mean in-degree 24) would turn a quarter of their rows into workgroups: they keep 64 (32 costs +8 %).
 int gm_heavy_deg_for(int64_t rows, int64_t edges) {
-    if (gm_knob().heavy_deg > 0) return std::max(2, gm_knob().heavy_deg);
     return edges <= 8 * rows ? 32 : 64;
 }
 
@@ -445,17 +412,6 @@ int gm_num_cus() {
     cus[dev] = n;
     return n;
 }
-
-static std::map<hipStream_t, int> g_stream_cus;
-int gm_stream_cus(hipStream_t s) {
-    {
-        std::lock_guard<std::mutex> lk(g_dev_mu);
-        auto it = g_stream_cus.find(s);
-        if (it != g_stream_cus.end()) return it->second;
-    }
-    return gm_num_cus();
-}
-void gm_stream_set_cus(hipStream_t s, int cus) { std::lock_guard<std::mutex> lk(g_dev_mu); g_stream_cus[s] = cus; }
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize = 160 KiB) once per (device, kernel)
 int gm_func_full_lds(const void* fn) {

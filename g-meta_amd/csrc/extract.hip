@@ -906,8 +906,7 @@ static int finalize_launch(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
     int32_t* d_cdeg = (int32_t*)scratch + o_cdeg;
     int2* d_first[2] = {(int2*)((int32_t*)scratch + o_first), (int2*)((int32_t*)scratch + o_first) + first};
     for (int o = 0; o < 2; ++o) GM_TRY(gm_balloc(b, &b->d_heavy[o], 2 * (size_t)cap, s));
-    const int edge_tables = gm_knob().agg_edge_tables;
-    if (b->edges > 0 && edge_tables) {
+    if (b->edges > 0) {
         GM_TRY(gm_balloc(b, &b->d_enorm[0], (size_t)b->edges, s)); GM_TRY(gm_balloc(b, &b->d_enorm[1], (size_t)b->edges, s)); GM_TRY(gm_balloc(b, &b->d_efeat, (size_t)b->edges, s));
         hipLaunchKernelGGL(k_edge_tables, dim3((int)std::min<int64_t>(4096, (b->edges + 255) / 256)), dim3(256), 0, s, b->d_indices, b->d_indices_t, (int64_t)b->edges,
                            b->d_norm, b->d_feat_row, b->d_enorm[0], b->d_enorm[1], b->d_efeat);
@@ -1100,9 +1099,8 @@ static int extract_impl(const gm_store_t* store, const gm_seed_t* seeds, int n_p
     if (!given) cap = std::min<int64_t>(store->max_nodes, (int64_t)sample_nodes + 2);
     const int Wmax = (int)((store->max_nodes + 31) >> 5);
     size_t lds_a = sizeof(uint32_t) * (2 * (size_t)Wmax + EX_BLOCK + 256 + 16);
-    const int force_global = gm_knob().extract_global_bitmap;
     // parent graphs beyond ~650k nodes do not fit the LDS bitmap pair: fall back to a per-workgroup slab in HBM
-    const bool gpath = force_global || lds_a > 160 * 1024;
+    const bool gpath = lds_a > 160 * 1024;
     if (gpath) lds_a = sizeof(uint32_t) * (EX_BLOCK + 256 + 16);
     // 16-bit prefix words wherever a subgraph stays below 65,536 nodes (GM_EXTRACT_PREF16=0: 32-bit as before); the BFS keeps its `expanded` bitmap from three hops on
     const bool p16 = !gpath && cap < 65536 && gm_knob().extract_pref16;

@@ -551,15 +551,13 @@ static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
         const bool f16 = a.np == 2;
         GM_REQUIRE(!f16 || (a.a_bound.amax && a.b_bound.amax), GM_EINVAL, "gemm: the two-piece split kernel needs bounds for both operands");
         k.a_bound = f16 ? a.a_bound : gm_no_bound(); k.b_bound = f16 ? a.b_bound : gm_no_bound(); k.amax_out = a.amax_out;
-        // persistent: one workgroup per CU (it fills the CU's register file, so nothing else co-resides).  GM_GEMM_SPLIT_GRID caps the
-        // grid below the CU count, which leaves whole CUs to the kernels of the other stream (experiment knob).
-        const int cus = gm_stream_cus(s);                                 // the stream's CU mask, if it has one
-        int grid_cap = gm_knob().gemm_split_grid;
-        if (grid_cap <= 0 && a.n_tiles > 2 * cus && a.n_tiles <= 6 * cus && cus >= 128) grid_cap = cus - 2 * GM_NXCD;
+        // persistent: one workgroup per CU (it fills the CU's register file, so nothing else co-resides).  Launches of 2-6 tiles per CU cap the
+        // grid two CUs per XCD below the CU count, which leaves those CUs to the kernels of the other stream.
+        const int cus = gm_num_cus();
+        const int grid_cap = a.n_tiles > 2 * cus && a.n_tiles <= 6 * cus && cus >= 128 ? cus - 2 * GM_NXCD : cus;
         // (round 6, measured on the 4-task arxiv shard -- the per-GPU share of an 8-GPU meta-batch, 1,101 query tiles: two CUs per XCD left to the
         // other queue's small kernels, 4.07-4.16 -> 4.00-4.02 ms per meta-step; from ~8 tiles per CU upwards the cap only costs: task_num 8 / 16 even,
         // task_num 32 24.8 -> 25.0 ms; CU-masked streams lose at every split at this size too: profiles/r06_t4_sweep.txt)
-        if (grid_cap <= 0 || grid_cap > cus) grid_cap = cus;
         if (a.fuse2) {
             // fused aggregate + GEMM: A addresses the aggregate's input rows, rows of other degrees come finished from a.zside
             GM_REQUIRE(a.K / 16 >= PF_DA && a.zside && (a.ldz % 4 == 0) && (((uintptr_t)a.zside & 15) == 0), GM_EINVAL, "gemm: fused aggregate needs K >= %d and an aligned side buffer", 16 * PF_DA);
@@ -573,7 +571,7 @@ static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
             // for the 4-task shard, where the support chain is the critical path; 8 and more lose to the per-workgroup prologue).
             // With the two-piece kernels (shorter tiles) the optimum moved from 4 to 3, and to 2 for the launches of 16 and more tiles per CU:
             // 4-task shard 4.36 -> 4.25 ms, task_num 32 24.86 -> 24.50 (three runs each, same box).
-            const int mult_f = gm_knob().gemm_fused_rounds > 0 ? gm_knob().gemm_fused_rounds : (a.n_tiles >= 16 * grid_cap ? 2 : 3);
+            const int mult_f = a.n_tiles >= 16 * grid_cap ? 2 : 3;
             const dim3 grid(std::min(a.n_tiles, mult_f * grid_cap));
             if (a.N == 128 && f16) hipLaunchKernelGGL((k_gemm_split_p<true, 1, 2, 2>), grid, dim3(1024), 0, s, k);
             else if (a.N == 128) hipLaunchKernelGGL((k_gemm_split_p<true, 1, 2, 3>), grid, dim3(1024), 0, s, k);
@@ -581,11 +579,10 @@ static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
             else hipLaunchKernelGGL((k_gemm_split_p<true, 2, 4, 3>), grid, dim3(1024), 0, s, k);
         } else {
             // a launch that would leave more than half of the CUs without a tile walks 64-row half tiles: half the MFMA chain per workgroup
-            const int half_on = gm_knob().gemm_half_tiles;
-            const dim3 grid_r(std::min(a.n_tiles, gm_knob().gemm_plain_rounds * grid_cap));
+            const dim3 grid_r(std::min(a.n_tiles, grid_cap));
             if (a.N == 128 && f16) hipLaunchKernelGGL((k_gemm_split_p<false, 1, 2, 2>), grid_r, dim3(1024), 0, s, k);
             else if (a.N == 128) hipLaunchKernelGGL((k_gemm_split_p<false, 1, 2, 3>), grid_r, dim3(1024), 0, s, k);
-            else if (half_on && 2 * a.n_tiles <= grid_cap) {
+            else if (2 * a.n_tiles <= grid_cap) {
                 if (f16) hipLaunchKernelGGL((k_gemm_split_p<false, 1, 4, 2>), dim3(2 * a.n_tiles), dim3(1024), 0, s, k);
                 else hipLaunchKernelGGL((k_gemm_split_p<false, 1, 4, 3>), dim3(2 * a.n_tiles), dim3(1024), 0, s, k);
             } else if (f16) hipLaunchKernelGGL((k_gemm_split_p<false, 2, 4, 2>), grid_r, dim3(1024), 0, s, k);
@@ -611,17 +608,13 @@ static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
     } while (0)
     // column-tile width: the widest (A read once) unless that leaves CUs idle -- small batches are latency-bound, so
     // trade A re-reads (L2 hits, same XCD) for parallelism
-    const int bn_cap = gm_knob().gemm_bn;
     int bn = a.N > 128 ? 256 : a.N > 64 ? 128 : 64;
-    if (bn > bn_cap) bn = bn_cap;
     while (bn > 64 && (int64_t)a.n_tiles * ((a.N + bn - 1) / bn) < 512) bn >>= 1;
-    const int mid_tiles = gm_knob().gemm_mid_tiles;           // below this many row tiles a 256-wide tile grid is only a few rounds deep: halve the tile (shorter tail)
-    if (bn == 256 && a.n_tiles < mid_tiles) bn = 128;
+    if (bn == 256 && a.n_tiles < 1536) bn = 128;             // below this many row tiles a 256-wide tile grid is only a few rounds deep: halve the tile (shorter tail)
     g.n_col_tiles = (a.N + bn - 1) / bn;
-    const int use_glds = gm_knob().gemm_glds;
     const bool bias_al = !a.bias || ((((uintptr_t)a.bias & 15) == 0) && (a.bias_stride % 4 == 0));
-    g.nt_store = gm_knob().gemm_nt;
-    const bool dma = use_glds && vec && !a.transB && !a.mask_b && g.c_vec && bias_al && a.K % BK == 0 && a.K >= 2 * BK && a.N % bn == 0;
+    g.nt_store = 1;
+    const bool dma = vec && !a.transB && !a.mask_b && g.c_vec && bias_al && a.K % BK == 0 && a.K >= 2 * BK && a.N % bn == 0;
     if (a.zero_out) {               // honoured on every path: in the DMA kernels' epilogue (needs the whole row range of ldc covered), else a memset
         if (dma && a.N == a.ldc) g.zero_out = a.zero_out;
         else GM_HIP(hipMemsetAsync(a.zero_out, 0, sizeof(float) * (size_t)a.rows * a.ldc, s));
@@ -631,8 +624,8 @@ static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
         if (bn == 256) hipLaunchKernelGGL((k_gemm_glds<4>), grid, dim3(512), 0, s, g);
         else if (bn == 128) hipLaunchKernelGGL((k_gemm_glds<2>), grid, dim3(256), 0, s, g);
         else {
-            const int small = gm_knob().gemm_small;            // 1 (default): 8 x (32 x 32) waves per 128 x 64 tile when the launch leaves CUs mostly empty
-            if (small && (int64_t)g.n_tiles * g.n_col_tiles <= 4 * gm_num_cus()) hipLaunchKernelGGL(k_gemm_glds_small, grid, dim3(512), 0, s, g);
+            // 8 x (32 x 32) waves per 128 x 64 tile when the launch leaves CUs mostly empty
+            if ((int64_t)g.n_tiles * g.n_col_tiles <= 4 * gm_num_cus()) hipLaunchKernelGGL(k_gemm_glds_small, grid, dim3(512), 0, s, g);
             else hipLaunchKernelGGL((k_gemm_glds<1>), grid, dim3(128), 0, s, g);
         }
         GM_HIP(hipGetLastError());
@@ -1364,7 +1357,7 @@ static bool wgrad_fast_ok(const gm_wgrad_args& a) {
 }
 // exact 3-way bf16 split of both operands, fp32 accumulation (k_wgrad_split): the same arithmetic as the split GEMM
 static bool wgrad_split_shape_ok(int n_chunks, int K, int N) {
-    return n_chunks > 0 && gm_knob().wgrad_split && gm_gemm_mode() == 1 && n_chunks >= (gm_knob().wgrad_split_min_chunks >= 0 ? gm_knob().wgrad_split_min_chunks : gm_num_cus() / 4) &&
+    return n_chunks > 0 && gm_gemm_mode() == 1 && n_chunks >= (gm_knob().wgrad_split_min_chunks >= 0 ? gm_knob().wgrad_split_min_chunks : gm_num_cus() / 4) &&
            (K == 128 || K == 256) && (N == 128 || N == 256);
 }
 static bool wgrad_takes_split(const gm_wgrad_args& a) { return wgrad_fast_ok(a) && wgrad_split_shape_ok(a.n_chunks, a.K, a.N); }

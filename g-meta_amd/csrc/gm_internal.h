@@ -191,15 +191,12 @@ void gm_batch_mark_use(const gm_batch* b, hipStream_t st);
 // ---- tuning / debug knobs: every GM_* environment variable is read ONCE, under std::call_once, into this
 // struct (the prefetch thread and the training thread both enter the library); per-device quantities are derived at the call site.
 struct gm_knobs {
-    int agg_min_waves, agg_min_win, agg_sched, agg_hub_part, agg_unr, agg_nt, agg_variant, agg_edge_tables, heavy_deg;
-    int extract_global_bitmap, feat_pad, timing;
+    int timing;
     int extract_pref16;            // GM_EXTRACT_PREF16: 16-bit per-word prefix counts in the extraction kernels' LDS (1, default): four resident workgroups per CU instead of three at the arxiv parent size
     int gemm_mode;                 // 0 exact fp32, 1 split-bf16, -1 not set (library default)
     int gemm_split_min_tiles;      // -1: a quarter of the current device's CUs
-    int gemm_split_grid;           // 0: the current device's CU count
     int centre_store;              // GM_CENTRE_STORE: the last layer's update stores only the centre rows of its activation -- in every pass (2, default), in the forward-only passes (1) -- or every row (0)
-    int gemm_fused_rounds, gemm_plain_rounds, gemm_half_tiles, gemm_bn, gemm_mid_tiles, gemm_glds, gemm_nt, gemm_small, wgrad_split, dz_glds;
-    int fuse_agg, head_stage, side_stream_priority;
+    int fuse_agg, head_stage;
     int fuse_diff;                 // GM_FUSE_DIFF: the differentiated passes of the dense schedule take the fused aggregate + GEMM too, their weight gradients form Z's rows from the source table: 2 (default) everywhere except a support batch whose full launches take the stream aggregate, 1 everywhere, 0 never
     int agg_mid_win;               // GM_AGG_MID_WIN: rows per wave window over that list (0 = by its length)
     int agg_mid_list;              // GM_AGG_MID_LIST: the partial aggregate launch of a fused pass walks a compact list of its window rows (1, default) or every row (0)
@@ -207,14 +204,8 @@ struct gm_knobs {
     int head_threads;              // GM_HEAD_THREADS: workgroup size of k_head_loss: 256 or 512; anything else (default 0) = 1024
     int split16_min_rows;          // GM_SPLIT16_MIN_ROWS: support + query rows from which gm_meta_step takes the two-piece kernels (smaller steps are launch-bound: no gain)
     int split_pieces;              // GM_SPLIT_PIECES: pieces per operand of the split kernels inside gm_meta_step: 3 = exact bf16 triple, all 24 operand bits (default); 2 = opt-in fp16 pair under recorded bounds
-    int wgrad_round_bias;          // weight-gradient chunking: percent of row-slot efficiency another round of chunks must gain over fewer, longer chunks
     int wgrad_split_min_chunks;    // GM_WGRAD_SPLIT_MIN_CHUNKS: smallest launch (row chunks) that takes the split weight-gradient kernel; -1: a quarter of the CUs
-    int cu_mask_support;           // CUs per XCD reserved for the support chain's stream (0: no CU masks)
     int agg_stream;                // GM_AGG_STREAM: eligible full aggregate launches take the LDS-DMA stream kernel (agg_stream.hip)
-    int agg_stream_wgs;            // GM_AGG_STREAM_WGS: its workgroups per CU (0 = by the batch's size: agg_stream_cost)
-    int agg_stream_cost;           // GM_AGG_STREAM_COST: edges + rows per wave of a stream launch
-    int agg_stream_gather;         // GM_AGG_STREAM_GATHER: the layer-1 launches (sources = rows of the store's feature table) take the stream kernel too
-    int agg_stream_depth;          // GM_AGG_STREAM_DEPTH: KiB of gathers in flight per wave (8 / 12)
     int agg_stream_min_rows;       // GM_AGG_STREAM_MIN_ROWS: smallest batch (rows) that builds stream tables; dense batches (more than 8 edges per row) never do
 };
 const gm_knobs& gm_knob();
@@ -303,7 +294,7 @@ struct gm_agg_args {
     float* out;                // [rows, width]
     int64_t rows;
     int width;
-    const int32_t* heavy;      // optional list of rows with more than GM_HEAVY_DEG edges (processed by a whole workgroup)
+    const int32_t* heavy;      // optional list of rows with more than heavy_deg edges (processed by a whole workgroup)
     int n_heavy;
     int heavy_deg;
     const int32_t* sched;      // optional block schedule (gm_agg_schedule): hub rows ride in the window launch
@@ -345,7 +336,7 @@ struct gm_stager;
 // gm_agg_schedule call (empty: one block per hub row)
 int gm_agg_schedule_flat(gm_batch* b, int64_t rows, int win, const int32_t* pos, int n_heavy, const std::vector<int32_t>& tab, int32_t** d_sched, int32_t* len, hipStream_t s, gm_stager* sg);
 int gm_agg_schedule(gm_batch* b, int64_t rows, int win, const int32_t* heavy_host, const int32_t* heavy_deg_host, int n_heavy, gm_agg_sched* out, hipStream_t s, gm_stager* sg);
-int gm_heavy_deg();   // rows with more edges than this are aggregated by a whole workgroup (env GM_HEAVY_DEG; default by density, see gm_heavy_deg_for)
+int gm_heavy_deg();   // rows with more edges than this are aggregated by a whole workgroup (64; a batch's own threshold is by density, see gm_heavy_deg_for)
 int gm_heavy_deg_for(int64_t rows, int64_t edges);
 int gm_launch_aggregate(const gm_agg_args& a, hipStream_t s);
 
@@ -438,11 +429,8 @@ bool gm_wgrad_gather_ok(int n_chunks, int K, int N);
 // 280 chunks cost two rounds for the work of 1.1 -- and be small: every chunk adds a partial to write and re-read.
 // Chunks never straddle two sets (per-task weights).  Returns a multiple of 32.
 int gm_num_cus();                         // compute units of the current device (cached per device)
-// CUs a stream may use: the device's, unless the stream was created with a CU mask (gm_meta_step's CU-partitioned streams register theirs).
-// Persistent kernels size their grid with this.
-int gm_stream_cus(hipStream_t s);
-void gm_stream_set_cus(hipStream_t s, int cus);
 int gm_func_full_lds(const void* fn);     // allow 160 KiB of dynamic LDS for a kernel, once per (device, kernel)
+#define GM_WGRAD_EXTRA_ROUND_PCT 25   // percent of row-slot efficiency another round of chunks must gain over fewer, longer chunks
 static inline int gm_wgrad_chunk_rows(const std::vector<int32_t>& set_off, int n_cu = gm_num_cus()) {
     const int sets = (int)set_off.size() - 1;
     int64_t total = 0; int mx = 1;
@@ -458,7 +446,7 @@ static inline int gm_wgrad_chunk_rows(const std::vector<int32_t>& set_off, int n
         const int cr = std::max(128, 32 * lo);
         const int64_t c = chunks_at(cr);
         const double eff = (double)total / ((double)((c + n_cu - 1) / n_cu) * n_cu * cr);   // useful rows / rows the rounds have room for
-        if (eff > best_eff + 0.01 * gm_knob().wgrad_round_bias) { best_eff = eff; best = cr; }
+        if (eff > best_eff + 0.01 * GM_WGRAD_EXTRA_ROUND_PCT) { best_eff = eff; best = cr; }
     }
     return best;
 }

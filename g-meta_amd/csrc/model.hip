@@ -912,9 +912,8 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
             if (l > 0) {
                 gm_gemm_args g{}; g.A = dQ; g.lda = fo; g.C = T; g.ldc = fi; g.K = fo; g.N = fi;
                 g.row_scale = b->d_norm; g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows;
-                const int dz_glds = gm_knob().dz_glds;
                 const bool use_split = c.Wsplit && gm_gemm_split_ok(b->n_tiles, fo, fi);
-                const bool use_wt = !use_split && dz_glds && c.WTl[l] && fi % 64 == 0 && fo % 16 == 0;
+                const bool use_wt = !use_split && c.WTl[l] && fi % 64 == 0 && fo % 16 == 0;
                 if (use_split) {
                     // B = W^T with W stored [fi][fo]: the planes are W's own rows (no transpose), K = fo, N = fi
                     gm_bound ab = gm_no_bound(), bb;
@@ -1337,44 +1336,27 @@ static gm_model_t internal_model(const gm_model_t* m, const gm_store* store, int
     return mp;
 }
 
+// The query stream carries bulk, throughput-bound work; the caller's stream carries the latency-critical support chain.  A lower
+// priority (a) lets support kernels win CUs when both have work and (b) gives the stream a hardware queue of its own: HIP multiplexes
+// same-priority streams onto a small pool of HW queues (GPU_MAX_HW_QUEUES, default 4), and once RCCL/torch have created their streams an
+// ordinary stream created here was observed to alias the caller's queue, silently serialising the whole step.
+static int low_priority_stream(hipStream_t* st) {
+    int lo = 0, hi = 0;
+    if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) {
+        GM_HIP(hipStreamCreateWithPriority(st, hipStreamNonBlocking, lo));      // `lo` = least priority
+    } else {
+        (void)hipGetLastError();
+        GM_HIP(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+    }
+    return GM_OK;
+}
+
 struct MetaStreams {
     hipStream_t side = nullptr, side2 = nullptr;      // query streams (side2: GM_QUERY_STREAMS = 2)
-    hipStream_t main = nullptr;      // CU-partitioned mode only (GM_CU_MASK_SUPPORT): the support chain's own stream, masked to its CUs
     std::vector<hipEvent_t> ev;
     int ensure(int n) {
-        const int per_xcd = gm_knob().cu_mask_support;
-        if (!side && per_xcd > 0 && per_xcd * GM_NXCD < gm_num_cus()) {
-            // CU-partitioned streams: the support chain owns `per_xcd` CUs of every XCD, the query evaluations the rest, so that kernels of
-            // the two chains CO-RESIDE on the chip instead of time-slicing it (a persistent 1024-thread GEMM workgroup needs a completely
-            // empty CU, which it never gets while the other queue keeps feeding small workgroups).  Mask bit i = CU i / 8 of XCD i % 8
-            // (the driver deals queue mask bits round-robin over the XCDs), so [0, 8 s) is s CUs on each XCD.
-            const int cus = gm_num_cus(), ns = per_xcd * GM_NXCD, words = (cus + 31) / 32;
-            std::vector<uint32_t> ms(words, 0u), mq(words, 0u);
-            for (int i = 0; i < cus; ++i) (i < ns ? ms : mq)[i >> 5] |= 1u << (i & 31);
-            GM_HIP(hipExtStreamCreateWithCUMask(&main, (uint32_t)words, ms.data()));
-            GM_HIP(hipExtStreamCreateWithCUMask(&side, (uint32_t)words, mq.data()));
-            gm_stream_set_cus(main, ns); gm_stream_set_cus(side, cus - ns);
-        }
-        if (!side) {
-            // The query stream carries bulk, throughput-bound work; the caller's stream carries the latency-critical
-            // support chain.  A lower priority (a) lets support kernels win CUs when both have work and (b) gives this
-            // stream a hardware queue of its own: HIP multiplexes same-priority streams onto a small pool of HW queues
-            // (GPU_MAX_HW_QUEUES, default 4), and once RCCL/torch have created their streams an ordinary stream created
-            // here was observed to alias the caller's queue, silently serialising the whole step.
-            int lo = 0, hi = 0;
-            const int use_prio = gm_knob().side_stream_priority;
-            if (use_prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) {
-                GM_HIP(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, lo));      // `lo` = least priority
-            } else {
-                (void)hipGetLastError();
-                GM_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-            }
-        }
-        if (!side2 && !main) {
-            int lo = 0, hi = 0;
-            if (gm_knob().side_stream_priority && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) GM_HIP(hipStreamCreateWithPriority(&side2, hipStreamNonBlocking, lo));
-            else { (void)hipGetLastError(); GM_HIP(hipStreamCreateWithFlags(&side2, hipStreamNonBlocking)); }
-        }
+        if (!side) GM_TRY(low_priority_stream(&side));
+        if (!side2) GM_TRY(low_priority_stream(&side2));
         while ((int)ev.size() < n) { hipEvent_t e; GM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ev.push_back(e); }
         return GM_OK;
     }
@@ -1619,16 +1601,13 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
     const bool two_q = p.nq_ctx == 2 && !hp->serialize && ms.side2;
     hipStream_t sq2 = two_q ? ms.side2 : sq;
     if (two_q) GM_TRY(gm_batch_hub_alt(qry, st));          // private hub counters / partial rows for the second query stream
-    hipStream_t const st0 = st;                            // the caller's stream: inputs arrive on it, the output leaves on it
-    if (!hp->serialize && ms.main) st = ms.main;           // CU-partitioned mode: the support chain runs on its own masked stream
     int ev = 0;
     auto signal = [&](hipStream_t from) -> hipEvent_t { hipEvent_t e = ms.ev[ev++]; (void)hipEventRecord(e, from); return e; };
     auto wait = [&](hipStream_t who, hipEvent_t e) { (void)hipStreamWaitEvent(who, e, 0); };
     {
-        hipEvent_t e_in = signal(st0);                     // inputs (theta, class tables, batches) are ready
+        hipEvent_t e_in = signal(st);                      // inputs (theta, class tables, batches) are ready
         wait(sq, e_in);
         if (two_q) wait(sq2, e_in);
-        if (st != st0) wait(st, e_in);
     }
 
     auto fw = [&](int k) -> float* { return p.fw + (int64_t)(k - 1) * p.TP; };       // fw_k, k = 1..K
@@ -1702,10 +1681,8 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
             have_grad = true;
         }
     }
-    wait(st0, signal(sq));                                 // join
-    if (two_q) wait(st0, signal(sq2));
-    if (st != st0) wait(st0, signal(st));
-    st = st0;
+    wait(st, signal(sq));                                  // join
+    if (two_q) wait(st, signal(sq2));
     const int64_t tot = Lu.P + 2 * K1 + 1 + (int64_t)T * K1;
     hipLaunchKernelGGL(k_finalize, dim3((int)std::min<int64_t>(1024, (tot + 255) / 256)), dim3(256), 0, st,
                        have_grad ? p.gq : nullptr, p.gp, Pp, Lu.P, T, p.lq, p.aq, K1, out, cut, shift, p.viol);

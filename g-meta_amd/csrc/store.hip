@@ -66,12 +66,9 @@ extern "C" int gm_store_create(int32_t n_graphs, const int64_t* n_nodes, const i
     UP(s->d_out_ptr, out_ptr, int64_t)
     UP(s->d_out_idx, out_idx, int32_t)
 #undef UP
-    {
-        const int pad_on = gm_knob().feat_pad;
-        // 1 (default): pad only widths the vector kernels cannot take as they are (not a multiple of 4: 50, 5, ...); 2: always; 0: never.
-        // Aligned widths keep their native stride: padding is exact (zeros) but changes which kernels run, i.e. the fp summation order.
-        s->feat_ld = (pad_on == 2 || (pad_on == 1 && feat_dim % 4 != 0)) ? gm_pad_feat(feat_dim) : feat_dim;
-    }
+    // pad only widths the vector kernels cannot take as they are (not a multiple of 4: 50, 5, ...).  Aligned widths keep their native stride:
+    // padding is exact (zeros) but changes which kernels run, i.e. the fp summation order.
+    s->feat_ld = feat_dim % 4 != 0 ? gm_pad_feat(feat_dim) : feat_dim;
     const size_t feat_bytes = (size_t)s->total_nodes * s->feat_ld * sizeof(float);
     if (rc == GM_OK) rc = gm_dev_alloc((void**)&s->d_feat, feat_bytes, st);
     if (rc == GM_OK && s->feat_ld != feat_dim && hipMemset(s->d_feat, 0, feat_bytes) != hipSuccess) { gm_set_error("gm_store_create: feature memset failed"); rc = GM_EHIP; }

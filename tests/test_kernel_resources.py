@@ -64,11 +64,12 @@ def objs():
     return build
 
 
-def test_stream_aggregate_allocates_at_most_32_vgprs(objs):
+def test_stream_aggregate_of_every_width_allocates_at_most_32_vgprs(objs):
     with tempfile.TemporaryDirectory() as tmp:
         regs = _kernel_vgprs(_device_elf(os.path.join(objs, 'agg_stream.o'), tmp))
     stream = {k: v for k, v in regs.items() if 'k_agg_stream' in k}
-    assert len(stream) >= 4
+    # every width the stream launch takes has its instantiation (k_agg_stream<LPR = width / 4, ring slots>)
+    assert {re.match(r'_Z12k_agg_streamILi(\d+)E', k).group(1) for k in stream} == {'16', '32', '64'}, stream
     assert all(v <= 32 for v in stream.values()), stream
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the aggregate kernel on the arxiv-shape query batch (one rank's share of a meta-batch).
-    GM_AGG_VARIANT=k python tools/agg_bench.py [width] [tasks]"""
+    python tools/agg_bench.py [width] [tasks]"""
 import ctypes as C
 import os
 import sys
@@ -41,7 +41,7 @@ for transposed in (0, 1):
         for _ in range(n):
             _lib.check(lib.gm_aggregate(Q.handle, transposed, gather, None if gather else _lib.ptr(x), width, p, None, _lib.ptr(out), _lib.stream_ptr()))
         torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / n
-    print('variant %s width %d transposed %d: %.3f ms  %.0f GB/s algorithmic (%.1f%% of 8 TB/s)' % (os.environ.get('GM_AGG_VARIANT', '0'), width, transposed,
+    print('width %d transposed %d: %.3f ms  %.0f GB/s algorithmic (%.1f%% of 8 TB/s)' % (width, transposed,
           dt * 1e3, bytes_ / dt / 1e9, 100 * bytes_ / dt / 8e12))
 # calibration: plain copy of the same bytes
 torch.cuda.synchronize(); t0 = time.perf_counter()

@@ -2,7 +2,7 @@
 """A/B of the aggregate kernels on real batches of the arxiv shape: window kernel (k_agg_win, hub rows in its schedule) vs the LDS-DMA stream kernel
 (agg_stream.hip).  For the support and the query batch of a meta-batch, widths 256 / 128 and the layer-1 gather: output compared bitwise, time per
 launch, algorithmic GB/s (SURVEY 8(d) B_agg).
-    GM_AGG_STREAM=1 [GM_AGG_STREAM_WGS=k] [GM_AGG_STREAM_DEPTH=8|12|16] python tools/agg_stream_bench.py [tasks]"""
+    GM_AGG_STREAM=1 python tools/agg_stream_bench.py [tasks]"""
 import ctypes as C
 import os
 import sys

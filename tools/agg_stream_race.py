@@ -68,7 +68,7 @@ for mode, mname in ((1, 'stream kernel'), (0, 'window kernel')):
                     ptr, idx = (np.asarray(a) for a in S.csr()[:2])
                     nrm = np.maximum(deg, 1).astype(np.float32) ** np.float32(-0.5)
                     xh = xs.cpu().numpy(); d_all = (out - ref).cpu().numpy()
-                    part = int(os.environ.get('GM_AGG_HUB_PART', 128))
+                    part = 128                                  # edges per hub part (gm_agg_schedule)
                     for r in rows[:4]:
                         d = d_all[r]; e0, e1 = ptr[r], ptr[r + 1]
                         P = max(1, (e1 - e0) // part)

@@ -3,7 +3,7 @@
 101 KiB of LDS per CU) runs over the arxiv-shape query batch on one stream; while it runs, aggregate launches over the support batch are queued on a
 second stream.  Reported: each kernel alone, then together -- the GEMM's duration with the aggregates beside it, how many aggregate launches completed
 inside the GEMM's span, and the wall time of the pair against the sum of the parts.
-    GM_AGG_STREAM=1 [GM_AGG_STREAM_WGS=k] python tools/coreside_probe.py [tasks]"""
+    GM_AGG_STREAM=1 python tools/coreside_probe.py [tasks]"""
 import ctypes as C
 import os
 import sys

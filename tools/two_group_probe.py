@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""Probe: one 32-task gm_meta_step against G concurrent gm_meta_steps over task groups (own streams and workspaces) at the arxiv shape.
-GM_GEMM_SPLIT_GRID caps the persistent GEMM's grid so that the groups' kernels can share the chip."""
+"""Probe: one 32-task gm_meta_step against G concurrent gm_meta_steps over task groups (own streams and workspaces) at the arxiv shape."""
 import copy, os, sys, time, random
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
