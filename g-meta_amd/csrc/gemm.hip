@@ -1356,15 +1356,22 @@ static bool wgrad_fast_ok(const gm_wgrad_args& a) {
            (((uintptr_t)a.A & 15) == 0) && (((uintptr_t)a.G & 15) == 0);
 }
 // exact 3-way bf16 split of both operands, fp32 accumulation (k_wgrad_split): the same arithmetic as the split GEMM
+static bool wgrad_split_dims_ok(int K, int N) { return (K == 128 || K == 256) && (N == 128 || N == 256); }
 static bool wgrad_split_shape_ok(int n_chunks, int K, int N) {
     return n_chunks > 0 && gm_gemm_mode() == 1 && n_chunks >= (gm_knob().wgrad_split_min_chunks >= 0 ? gm_knob().wgrad_split_min_chunks : gm_num_cus() / 4) &&
-           (K == 128 || K == 256) && (N == 128 || N == 256);
+           wgrad_split_dims_ok(K, N);
 }
-static bool wgrad_takes_split(const gm_wgrad_args& a) { return wgrad_fast_ok(a) && wgrad_split_shape_ok(a.n_chunks, a.K, a.N); }
+static bool wgrad_takes_split(const gm_wgrad_args& a) {
+    if (a.pick == GM_WGRAD_PICK_EXACT) return false;
+    if (a.pick == GM_WGRAD_PICK_SPLIT) return wgrad_fast_ok(a) && wgrad_split_dims_ok(a.K, a.N);
+    return wgrad_fast_ok(a) && wgrad_split_shape_ok(a.n_chunks, a.K, a.N);
+}
 // Would a weight gradient over `n_chunks` row chunks with these widths run on the split kernel -- the one that can form its A operand from the per-row
 // source table (gm_wgrad_args::fuse2)?  The forward of a differentiated pass asks before it leaves Z_l unwritten (model.hip).
 bool gm_wgrad_gather_ok(int n_chunks, int K, int N) { return wgrad_split_shape_ok(n_chunks, K, N); }
 int gm_launch_wgrad(const gm_wgrad_args& a, hipStream_t s) {
+    GM_REQUIRE(a.pick != GM_WGRAD_PICK_SPLIT || wgrad_takes_split(a), GM_EINVAL,
+               "wgrad: the split kernel needs K, N in {128, 256}, no Gb / row indirection and 16-byte aligned operands (K=%d N=%d)", a.K, a.N);
     const int cat = wgrad_takes_split(a) ? ((a.np == 2 && a.a_bound.amax && a.g_bound.amax) ? GM_PROF_WGRAD_SPLIT16 : GM_PROF_WGRAD_SPLIT) : GM_PROF_WGRAD;
     gm_prof_begin(cat, s, 2 * a.rows * a.K * a.N);
     gm_prof_note(GM_PROF_WGRAD_BYTES, 4 * a.rows * ((int64_t)a.K + a.N));

@@ -419,7 +419,12 @@ struct gm_wgrad_args {
     const void* fuse2; const float* gx; int64_t ldgx;
     gm_wgrad_hold* hold; int hold_this; // optional: hold this call's reduction back (hold_this = 1; its `partial` must then stay untouched) /
                                         // flush the held ones with this call's reduction (hold_this = 0)
+    int pick;                           // kernel family: 0 = the library's choice (gm_gemm_mode, GM_WGRAD_SPLIT_MIN_CHUNKS); GM_WGRAD_PICK_EXACT /
+                                        // GM_WGRAD_PICK_SPLIT force one (GM_EINVAL where the split kernel cannot take the call).  Set only by the
+                                        // numerics-test export gm_dense_wgrad; the product path leaves it 0
 };
+#define GM_WGRAD_PICK_EXACT 1           // k_wgrad_fast / k_wgrad, whatever the launch size and gm_gemm_mode()
+#define GM_WGRAD_PICK_SPLIT 2           // k_wgrad_split, whatever the launch size and gm_gemm_mode()
 #define GM_WGRAD_ROWS 1024
 int gm_launch_wgrad(const gm_wgrad_args& a, hipStream_t s);
 bool gm_wgrad_gather_ok(int n_chunks, int K, int N);

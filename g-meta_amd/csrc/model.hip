@@ -1787,3 +1787,58 @@ extern "C" int gm_dense_update(const gm_batch_t* b, const float* x, int32_t K, c
     gm_batch_mark_use(b, st);
     return rc;
 }
+
+// ================================================================================ weight gradient, exported for numerics tests
+extern "C" int gm_dense_wgrad(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, const float* g, int64_t ldg, int32_t N, const float* s,
+                              const float* gb, int64_t ldgb, float* dW, int64_t dw_stride, float* db, int64_t db_stride, int32_t mode,
+                              const float* cur, float* next, int64_t p_stride, float lr, float* wt, uint16_t* pl_fwd, uint16_t* pl_dz, void* stream) {
+    GM_REQUIRE(b && x && g && dW && K >= 1 && N >= 1 && ldx >= K && ldg >= N && (!gb || ldgb >= N) && mode >= -1 && mode <= 2, GM_EINVAL,
+               "dense_wgrad: bad arguments");
+    // the generic kernel's bias sums hold 2048 columns (bsum[2] x 1024 threads), and gm_make_layout stops there too
+    GM_REQUIRE(K <= 2048 && N <= 2048, GM_ERANGE, "dense_wgrad: K=%d N=%d: at most 2048 columns per operand", K, N);
+    const int sets = b->sets;
+    const int64_t KN = (int64_t)K * N;
+    GM_REQUIRE(sets == 1 || (dw_stride >= KN && (!db || db_stride >= N)), GM_EINVAL, "dense_wgrad: per-set outputs overlap");
+    GM_REQUIRE(!next || (cur && db && (sets == 1 || p_stride >= KN + N)), GM_EINVAL, "dense_wgrad: the SGD step needs cur, db and a stride of at least (K+1)*N");
+    GM_REQUIRE((!wt && !pl_fwd && !pl_dz) || next, GM_EINVAL, "dense_wgrad: wt and the planes are outputs of the SGD step");
+    GM_REQUIRE((!pl_fwd && !pl_dz) || (K % 32 == 0 && N % 32 == 0), GM_EINVAL, "dense_wgrad: weight planes need K and N multiples of 32");
+    hipStream_t st = (hipStream_t)stream;
+    gm_wgrad_args w{};
+    w.A = x; w.lda = ldx; w.K = K; w.G = g; w.ldg = ldg; w.N = N; w.Gb = gb; w.ldgb = ldgb; w.a_scale = s;
+    w.chunks = b->d_chunks; w.n_chunks = b->n_chunks; w.set_chunk_off = b->d_set_chunk_off; w.sets = sets; w.rows = b->rows;
+    w.dW = dW; w.dw_stride = dw_stride; w.db = db; w.db_stride = db_stride;
+    if (next) {
+        w.sgd_cur = cur; w.sgd_cur_stride = p_stride; w.sgd_next = next; w.sgd_next_stride = p_stride; w.sgd_lr = lr; w.w_off = 0; w.b_off = KN;
+        w.wt_next = wt; w.pl_fwd = pl_fwd; w.pl_dz = pl_dz;
+    }
+    w.pick = mode == 0 ? GM_WGRAD_PICK_EXACT : mode > 0 ? GM_WGRAD_PICK_SPLIT : 0;
+    unsigned* slots = nullptr;
+    int rc = gm_alloc(&w.partial, (size_t)std::max(1, b->n_chunks) * (size_t)(KN + N), st);
+    if (rc == GM_OK && mode == 2) {
+        // two fp16 pieces per operand: per-set bounds of x (slots [0, sets)) and of g (slots [sets, 2 sets)), taken over each set's rows (with
+        // the padding between them), and ONE bound of |s| over all rows (slot 2 sets) as the gain of x's: |s x| <= max_t |x| * max |s|
+        rc = gm_alloc(&slots, (size_t)(2 * sets + 1) * GM_BOUND_PAD, st);
+        if (rc == GM_OK && hipMemsetAsync(slots, 0, sizeof(unsigned) * (2 * sets + 1) * GM_BOUND_PAD, st) != hipSuccess) { gm_set_error("dense_wgrad: memset failed"); rc = GM_EHIP; }
+        for (int t0 = 0; rc == GM_OK && t0 < sets; t0 += 8) {
+            const int segs = std::min(8, sets - t0);
+            int64_t xo[8], xn[8], go[8], gn[8];
+            for (int i = 0; i < segs; ++i) {
+                const int64_t r0 = b->h_set_row_off[t0 + i], nr = b->h_set_row_off[t0 + i + 1] - r0;
+                xo[i] = r0 * ldx; xn[i] = nr > 0 ? (nr - 1) * ldx + K : 0;
+                go[i] = r0 * ldg; gn[i] = nr > 0 ? (nr - 1) * ldg + N : 0;
+            }
+            rc = gm_amax_segs(x, xo, xn, segs, slots + (int64_t)t0 * GM_BOUND_PAD, GM_BOUND_PAD, st);
+            if (rc == GM_OK) rc = gm_amax_segs(g, go, gn, segs, slots + (int64_t)(sets + t0) * GM_BOUND_PAD, GM_BOUND_PAD, st);
+        }
+        if (rc == GM_OK && s) rc = gm_amax(s, 0, 0, b->rows, 1, slots + (int64_t)2 * sets * GM_BOUND_PAD, 0, st);
+        w.np = 2;
+        w.a_bound = gm_no_bound(); w.a_bound.amax = slots; w.a_bound.stride = GM_BOUND_PAD;
+        if (s) w.a_bound.gain = reinterpret_cast<const float*>(slots + (int64_t)2 * sets * GM_BOUND_PAD);     // (an amax slot holds fp32 bits)
+        w.g_bound = gm_no_bound(); w.g_bound.amax = slots + (int64_t)sets * GM_BOUND_PAD; w.g_bound.stride = GM_BOUND_PAD;
+    }
+    if (rc == GM_OK) rc = gm_launch_wgrad(w, st);
+    if (w.partial) gm_dev_free(w.partial, st);
+    if (slots) gm_dev_free(slots, st);
+    gm_batch_mark_use(b, st);
+    return rc;
+}

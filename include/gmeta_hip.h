@@ -175,6 +175,19 @@ int gm_gcn_backward(const gm_batch_t* b, const gm_model_t* m, const float* param
  * 2: split-fp16 kernel (two pieces; the bounds of x and of every W_t are taken by the call itself). */
 int gm_dense_update(const gm_batch_t* b, const float* x, int32_t K, const float* W, int64_t w_stride, int32_t N, float* out, int32_t mode,
                     void* stream);
+/* The weight gradient of the same layer (learner.py backward of `torch.matmul(feat, weight)` + bias) over the batch's weight-gradient row chunks,
+ * per set t:  dW_t[K, N] = sum over the set's rows r of (s[r] x[r, :])^T g[r, :]  and  db_t[N] = sum_r gb[r, :].  Exported for numerics tests of the
+ * weight-gradient kernels.  x: device [rows, ldx] (K used), g: [rows, ldg] (N used); s: row scale [rows] or NULL (1); gb: [rows, ldgb] or NULL (g).
+ * dW_t = dW + t * dw_stride, db_t = db + t * db_stride (db may be NULL).  mode -1: what the library would pick (gm_set_gemm_mode + launch size;
+ * three pieces), 0: exact fp32 (k_wgrad_fast or k_wgrad, by shape and alignment), 1: split-bf16 kernel (three pieces), 2: split-fp16 kernel (two
+ * pieces; per-set bounds of x and g and one bound of |s| are taken by the call itself).  Modes 1 and 2 need K, N in {128, 256}, no gb and 16-byte
+ * aligned x, g with ldx, ldg multiples of 4 (else GM_EINVAL); K or N above 2048: GM_ERANGE.  Optional fused inner SGD step (next != NULL):
+ * parameter vectors cur_t / next_t = cur / next + t * p_stride laid out as W [K, N] then b [N]:  next_t = cur_t - lr * (dW_t, db_t);  wt (or NULL):
+ * next_t's W transposed, [set][N][K];  pl_fwd / pl_dz (or NULL; K, N multiples of 32): next_t's W as three bf16 planes in the layouts of the
+ * split GEMM's operands, [set][3][K/8][N][8] and [set][3][N/8][K][8]. */
+int gm_dense_wgrad(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, const float* g, int64_t ldg, int32_t N, const float* s,
+                   const float* gb, int64_t ldgb, float* dW, int64_t dw_stride, float* db, int64_t db_stride, int32_t mode,
+                   const float* cur, float* next, int64_t p_stride, float lr, float* wt, uint16_t* pl_fwd, uint16_t* pl_dz, void* stream);
 
 /* ---- Prototypical losses (meta.py:28-54 proto_loss_spt, 56-79 proto_loss_qry), per set.
  * y: HOST int32 [subs] labels.  Outputs (device): loss[sets], acc[sets], protos[sets, c_task, n_out]

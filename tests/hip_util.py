@@ -1,6 +1,7 @@
 """GPU-side helpers shared by the -m gpu tests and __graft_entry__.smoke(): drive the HIP path
 (through the Python host mirror, i.e. through the C ABI) on a golden fixture."""
 import argparse
+import random
 
 import numpy as np
 import torch
@@ -59,3 +60,17 @@ def hip_meta_step(fx, replay=True, hoist=0, sparse_bwd=0, cone=0, fused_adam_ker
            'spt_parent': S.parent().astype(np.int64), 'qry_parent': Q.parent().astype(np.int64), 'stats': m.last_stats,
            'S': S, 'Q': Q, 'meta': m, 'store': store}
     return res
+
+
+def arxiv_query_batch(T=8):
+    """The query mega-batch of a synthetic arxiv meta-batch with T tasks (~286k rows at T = 8, one set per task) and its store: the
+    full-size launch shape of the numerics tests of the GEMM and weight-gradient kernels."""
+    from gmeta_amd import synth
+    np.random.seed(222); random.seed(222); torch.manual_seed(222)
+    args, cfg = synth.make_args('arxiv', task_num=T)
+    data = synth.make_dataset(cfg)
+    store = gmeta_amd.GraphStore(data['graphs'], data['feats'])
+    db = gmeta_amd.Subgraphs(None, 'train', data['info'], n_way=3, k_shot=3, k_query=24, batchsz=T, args=args, adjs=store, h=2,
+                             tables=data['tables'], verbose=False)
+    batch = db.get_batch(list(range(T)))
+    return batch[2][0].view_of, store

@@ -4,8 +4,6 @@ bf16 pieces, six MFMA products, fp32 accumulation -- the default for large N = 2
 MFMA kernel and as a plain PyTorch fp32 matmul; and the same for the split-fp16 kernel gm_meta_step uses where magnitude bounds are recorded
 (two fp16 pieces per operand under power-of-two scales, three products), including operands whose magnitudes span many octaves inside one
 bound (the low pieces then sit in fp16's subnormal range: the matrix cores must not flush them)."""
-import random
-
 import numpy as np
 import pytest
 import torch
@@ -15,17 +13,8 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope='module')
 def qbatch():
-    import gmeta_amd
-    from gmeta_amd import synth
-    np.random.seed(222); random.seed(222); torch.manual_seed(222)
-    T = 8
-    args, cfg = synth.make_args('arxiv', task_num=T)
-    data = synth.make_dataset(cfg)
-    store = gmeta_amd.GraphStore(data['graphs'], data['feats'])
-    db = gmeta_amd.Subgraphs(None, 'train', data['info'], n_way=3, k_shot=3, k_query=24, batchsz=T, args=args, adjs=store, h=2,
-                             tables=data['tables'], verbose=False)
-    batch = db.get_batch(list(range(T)))
-    return batch[2][0].view_of, store
+    from hip_util import arxiv_query_batch
+    return arxiv_query_batch(8)
 
 
 @pytest.mark.parametrize('K,N', [(256, 256), (128, 256), (128, 128), (64, 128)])
