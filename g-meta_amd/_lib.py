@@ -49,6 +49,7 @@ PROTOTYPES = {
     'gm_gcn_forward': (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]),
     'gm_gcn_backward': (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp]),
     'gm_dense_update': (C.c_int, [vp, vp, i32, vp, i64, i32, vp, i32, vp]),
+    'gm_dense_gemm': (C.c_int, [vp, vp, i64, i32, vp, i64, i32, i32, vp, i64, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i32, vp, vp]),
     'gm_dense_wgrad': (C.c_int, [vp, vp, i64, i32, vp, i64, i32, vp, vp, i64, vp, i64, vp, i64, i32, vp, vp, i64, C.c_float, vp, vp, vp, vp]),
     'gm_proto_loss_spt': (C.c_int, [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     'gm_proto_loss_qry': (C.c_int, [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),

@@ -539,11 +539,15 @@ int gm_launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
     return rc;
 }
 static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
+    // host-side record of the instantiation about to be launched (numerics tests only)
+#define GM_LAUNCHED(ID) do { if (a.launched) *a.launched = (ID); } while (0)
     if (a.Bsplit) {
         // fp32-accurate product on the bf16 matrix cores (exact 3-way operand split, 6 MFMA products, fp32 accumulation)
         const bool ok = (a.N == 256 || a.N == 128) && a.K % 16 == 0 && a.K >= 32 && !a.mask_h && !a.mask_b && (a.lda % 4 == 0) && (((uintptr_t)a.A & 15) == 0) &&
                         (a.ldc % 4 == 0) && (((uintptr_t)a.C & 15) == 0) && (!a.bias || a.bias_stride % 4 == 0);
         GM_REQUIRE(ok, GM_EINVAL, "gemm: launch not eligible for the split-bf16 kernel (N=%d K=%d)", a.N, a.K);
+        // the epilogue zero-fills columns [0, N) of its rows only: a zero_out of wider rows would be left partly unwritten
+        GM_REQUIRE(!a.zero_out || a.ldc == a.N, GM_EINVAL, "gemm: the split kernels zero-fill a [rows, N] buffer only (ldc=%lld N=%d)", (long long)a.ldc, a.N);
         SplitGemmK k{};
         k.A = a.A; k.lda = a.lda; k.Bt = a.Bsplit; k.bt_stride = a.bsplit_stride; k.C = a.C; k.ldc = a.ldc; k.K = a.K; k.N = a.N;
         k.row_scale = a.row_scale_keep ? a.row_scale_keep : a.row_scale; k.keep_signed = a.row_scale_keep ? 1 : 0; k.bias = a.bias; k.bias_stride = a.bias_stride; k.relu = a.relu; k.relu_bits = a.relu_bits;
@@ -573,20 +577,20 @@ static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
             // 4-task shard 4.36 -> 4.25 ms, task_num 32 24.86 -> 24.50 (three runs each, same box).
             const int mult_f = a.n_tiles >= 16 * grid_cap ? 2 : 3;
             const dim3 grid(std::min(a.n_tiles, mult_f * grid_cap));
-            if (a.N == 128 && f16) hipLaunchKernelGGL((k_gemm_split_p<true, 1, 2, 2>), grid, dim3(1024), 0, s, k);
-            else if (a.N == 128) hipLaunchKernelGGL((k_gemm_split_p<true, 1, 2, 3>), grid, dim3(1024), 0, s, k);
-            else if (f16) hipLaunchKernelGGL((k_gemm_split_p<true, 2, 4, 2>), grid, dim3(1024), 0, s, k);
-            else hipLaunchKernelGGL((k_gemm_split_p<true, 2, 4, 3>), grid, dim3(1024), 0, s, k);
+            if (a.N == 128 && f16) { GM_LAUNCHED(GM_GEMM_ID_SPLIT(true, 1, 2, 2)); hipLaunchKernelGGL((k_gemm_split_p<true, 1, 2, 2>), grid, dim3(1024), 0, s, k); }
+            else if (a.N == 128) { GM_LAUNCHED(GM_GEMM_ID_SPLIT(true, 1, 2, 3)); hipLaunchKernelGGL((k_gemm_split_p<true, 1, 2, 3>), grid, dim3(1024), 0, s, k); }
+            else if (f16) { GM_LAUNCHED(GM_GEMM_ID_SPLIT(true, 2, 4, 2)); hipLaunchKernelGGL((k_gemm_split_p<true, 2, 4, 2>), grid, dim3(1024), 0, s, k); }
+            else { GM_LAUNCHED(GM_GEMM_ID_SPLIT(true, 2, 4, 3)); hipLaunchKernelGGL((k_gemm_split_p<true, 2, 4, 3>), grid, dim3(1024), 0, s, k); }
         } else {
             // a launch that would leave more than half of the CUs without a tile walks 64-row half tiles: half the MFMA chain per workgroup
             const dim3 grid_r(std::min(a.n_tiles, grid_cap));
-            if (a.N == 128 && f16) hipLaunchKernelGGL((k_gemm_split_p<false, 1, 2, 2>), grid_r, dim3(1024), 0, s, k);
-            else if (a.N == 128) hipLaunchKernelGGL((k_gemm_split_p<false, 1, 2, 3>), grid_r, dim3(1024), 0, s, k);
+            if (a.N == 128 && f16) { GM_LAUNCHED(GM_GEMM_ID_SPLIT(false, 1, 2, 2)); hipLaunchKernelGGL((k_gemm_split_p<false, 1, 2, 2>), grid_r, dim3(1024), 0, s, k); }
+            else if (a.N == 128) { GM_LAUNCHED(GM_GEMM_ID_SPLIT(false, 1, 2, 3)); hipLaunchKernelGGL((k_gemm_split_p<false, 1, 2, 3>), grid_r, dim3(1024), 0, s, k); }
             else if (2 * a.n_tiles <= grid_cap) {
-                if (f16) hipLaunchKernelGGL((k_gemm_split_p<false, 1, 4, 2>), dim3(2 * a.n_tiles), dim3(1024), 0, s, k);
-                else hipLaunchKernelGGL((k_gemm_split_p<false, 1, 4, 3>), dim3(2 * a.n_tiles), dim3(1024), 0, s, k);
-            } else if (f16) hipLaunchKernelGGL((k_gemm_split_p<false, 2, 4, 2>), grid_r, dim3(1024), 0, s, k);
-            else hipLaunchKernelGGL((k_gemm_split_p<false, 2, 4, 3>), grid_r, dim3(1024), 0, s, k);
+                if (f16) { GM_LAUNCHED(GM_GEMM_ID_SPLIT(false, 1, 4, 2)); hipLaunchKernelGGL((k_gemm_split_p<false, 1, 4, 2>), dim3(2 * a.n_tiles), dim3(1024), 0, s, k); }
+                else { GM_LAUNCHED(GM_GEMM_ID_SPLIT(false, 1, 4, 3)); hipLaunchKernelGGL((k_gemm_split_p<false, 1, 4, 3>), dim3(2 * a.n_tiles), dim3(1024), 0, s, k); }
+            } else if (f16) { GM_LAUNCHED(GM_GEMM_ID_SPLIT(false, 2, 4, 2)); hipLaunchKernelGGL((k_gemm_split_p<false, 2, 4, 2>), grid_r, dim3(1024), 0, s, k); }
+            else { GM_LAUNCHED(GM_GEMM_ID_SPLIT(false, 2, 4, 3)); hipLaunchKernelGGL((k_gemm_split_p<false, 2, 4, 3>), grid_r, dim3(1024), 0, s, k); }
         }
         GM_HIP(hipGetLastError());
         return GM_OK;
@@ -601,6 +605,7 @@ static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
 #define GM_LAUNCH_GEMM(WC_, THREADS_)                                                                                         \
     do {                                                                                                                      \
         const dim3 grid(g.n_tiles * g.n_col_tiles), blk(THREADS_);                                                            \
+        GM_LAUNCHED(GM_GEMM_ID_NN(WC_, vec, a.transB ? 1 : 0));                                                               \
         if (vec && a.transB) hipLaunchKernelGGL((k_gemm_nn<WC_, true, true>), grid, blk, 0, s, g);                             \
         else if (vec) hipLaunchKernelGGL((k_gemm_nn<WC_, true, false>), grid, blk, 0, s, g);                                   \
         else if (a.transB) hipLaunchKernelGGL((k_gemm_nn<WC_, false, true>), grid, blk, 0, s, g);                              \
@@ -621,12 +626,12 @@ static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
     }
     if (dma) {
         const dim3 grid(g.n_tiles * g.n_col_tiles);
-        if (bn == 256) hipLaunchKernelGGL((k_gemm_glds<4>), grid, dim3(512), 0, s, g);
-        else if (bn == 128) hipLaunchKernelGGL((k_gemm_glds<2>), grid, dim3(256), 0, s, g);
+        if (bn == 256) { GM_LAUNCHED(GM_GEMM_ID_GLDS4); hipLaunchKernelGGL((k_gemm_glds<4>), grid, dim3(512), 0, s, g); }
+        else if (bn == 128) { GM_LAUNCHED(GM_GEMM_ID_GLDS2); hipLaunchKernelGGL((k_gemm_glds<2>), grid, dim3(256), 0, s, g); }
         else {
             // 8 x (32 x 32) waves per 128 x 64 tile when the launch leaves CUs mostly empty
-            if ((int64_t)g.n_tiles * g.n_col_tiles <= 4 * gm_num_cus()) hipLaunchKernelGGL(k_gemm_glds_small, grid, dim3(512), 0, s, g);
-            else hipLaunchKernelGGL((k_gemm_glds<1>), grid, dim3(128), 0, s, g);
+            if ((int64_t)g.n_tiles * g.n_col_tiles <= 4 * gm_num_cus()) { GM_LAUNCHED(GM_GEMM_ID_GLDS_SMALL); hipLaunchKernelGGL(k_gemm_glds_small, grid, dim3(512), 0, s, g); }
+            else { GM_LAUNCHED(GM_GEMM_ID_GLDS1); hipLaunchKernelGGL((k_gemm_glds<1>), grid, dim3(128), 0, s, g); }
         }
         GM_HIP(hipGetLastError());
         return GM_OK;
@@ -635,6 +640,7 @@ static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
     else if (bn == 128) GM_LAUNCH_GEMM(2, 256);
     else GM_LAUNCH_GEMM(1, 128);
 #undef GM_LAUNCH_GEMM
+#undef GM_LAUNCHED
     GM_HIP(hipGetLastError());
     return GM_OK;
 }

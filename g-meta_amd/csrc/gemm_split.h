@@ -421,6 +421,9 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
             if (sa_c == nchunks) {
                 sa_c = 0; ++sa_ti;
                 as_cur = as_next; inv_cur = inv_next;
+                // the loads run PF_DA - 1 chunks ahead: with fewer chunks per tile than that (K = 32), la_tile has already moved as_next to a
+                // LATER tile, whose set may have another A bound -- take this tile's own (the short-K path reads its constants per tile anyway)
+                if constexpr (NP == 2) { if (!fast_consts) as_cur = a_scale_of(tile_of(b + sa_ti * G).set); }
                 if constexpr (GATHER) {                                                // the loads of this tile were issued with w_next's table entries
 #pragma unroll
                     for (int p = 0; p < A_PER; ++p) { w_cur[p][0] = w_next[p][0]; w_cur[p][1] = w_next[p][1]; }

@@ -367,7 +367,16 @@ struct gm_gemm_args {
     const int32_t* tiles;               // device [n_tiles*3]: set, row0, nrows  (nrows <= BM)
     int n_tiles;
     int64_t rows;                       // total rows covered by the tiles (profiling: flops = 2*rows*K*N)
+    int* launched;                      // optional: receives the GM_GEMM_ID_* of the instantiation launched (host side).  Set only by the
+                                        // numerics-test export gm_dense_gemm; the product path leaves it NULL
 };
+// gm_gemm_args::launched
+#define GM_GEMM_ID_GLDS4 1              // k_gemm_glds<4>
+#define GM_GEMM_ID_GLDS2 2              // k_gemm_glds<2>
+#define GM_GEMM_ID_GLDS1 3              // k_gemm_glds<1>
+#define GM_GEMM_ID_GLDS_SMALL 4         // k_gemm_glds_small
+#define GM_GEMM_ID_NN(WC, VEC, TB) (10 + 4 * ((WC) == 4 ? 2 : (WC) == 2 ? 1 : 0) + 2 * (VEC) + (TB))     // k_gemm_nn<WC, VEC, TB>: 10 .. 21
+#define GM_GEMM_ID_SPLIT(GATHER, MI, WC, NP) (30 + 10 * (GATHER) + ((MI) == 2 ? 0 : (WC) == 4 ? 2 : 4) + ((NP) == 2))   // k_gemm_split_p: 30 .. 35, 40 .. 45
 #define GM_GEMM_BM 128
 int gm_launch_gemm_nn(const gm_gemm_args& a, hipStream_t s);
 // fp32 GEMM on the bf16 matrix cores by exact 3-way operand splitting (gemm_split.h): eligibility of a launch and the weight planes.

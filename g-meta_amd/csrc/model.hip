@@ -1788,6 +1788,59 @@ extern "C" int gm_dense_update(const gm_batch_t* b, const float* x, int32_t K, c
     return rc;
 }
 
+// The same product with every field of gm_gemm_args that the forward and dZ GEMMs set: the epilogue options, a transposed W, strides, the
+// choice of kernel family, and the instantiation that ran
+extern "C" int gm_dense_gemm(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, const float* W, int64_t w_stride, int32_t trans_w, int32_t N,
+                             float* out, int64_t ldc, const float* s, const float* s_keep, const float* bias, int64_t bias_stride, int32_t relu,
+                             uint8_t* relu_bits, const float* mask_h, const uint8_t* mask_b, float* zero_out, uint32_t* amax_out, int32_t mode,
+                             int32_t* launched, void* stream) {
+    GM_REQUIRE(b && x && W && out && K >= 1 && N >= 1 && ldx >= K && ldc >= N && mode >= -1 && mode <= 2 && !(mask_h && mask_b), GM_EINVAL,
+               "dense_gemm: bad arguments");
+    GM_REQUIRE(!amax_out || mode == 2, GM_EINVAL, "dense_gemm: amax_out is an output of the two-piece kernels (mode 2)");
+    hipStream_t st = (hipStream_t)stream;
+    const int sets = b->sets;
+    gm_gemm_args g{};
+    g.A = x; g.lda = ldx; g.B = W; g.b_stride = w_stride; g.transB = trans_w ? 1 : 0; g.C = out; g.ldc = ldc; g.K = K; g.N = N;
+    g.row_scale = s; g.row_scale_keep = s_keep; g.n_keep = b->rows; g.bias = bias; g.bias_stride = bias_stride; g.relu = relu ? 1 : 0;
+    g.relu_bits = relu_bits; g.mask_h = mask_h; g.mask_b = mask_b; g.zero_out = zero_out;
+    g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows; g.launched = launched;
+    uint16_t* planes = nullptr; unsigned* slots = nullptr;
+    int rc = GM_OK;
+    if (mode == 1 || mode == 2 || (mode < 0 && gm_gemm_split_ok(b->n_tiles, K, N))) {
+        GM_REQUIRE(!mask_h && !mask_b, GM_EINVAL, "dense_gemm: the split kernels take no relu' mask");
+        GM_REQUIRE((N == 256 || N == 128) && K % 16 == 0 && K >= 32, GM_EINVAL, "dense_gemm: the split kernels need N = 128 or 256 and K a multiple of 16 (>= 32)");
+        const int wsets = w_stride ? sets : 1;
+        rc = gm_alloc(&planes, (size_t)wsets * 3 * K * N, st);
+        gm_bound wb = gm_no_bound();
+        if (rc == GM_OK && mode == 2) {
+            // two fp16 pieces per operand: per-set bounds of x (slots [0, sets)), taken over each set's rows as gm_dense_wgrad does, and one per
+            // weight matrix (slots [sets, sets + wsets))
+            rc = gm_alloc(&slots, (size_t)(sets + wsets) * GM_BOUND_PAD, st);
+            if (rc == GM_OK && hipMemsetAsync(slots, 0, sizeof(unsigned) * (sets + wsets) * GM_BOUND_PAD, st) != hipSuccess) { gm_set_error("dense_gemm: memset failed"); rc = GM_EHIP; }
+            for (int t0 = 0; rc == GM_OK && t0 < sets; t0 += 8) {
+                const int segs = std::min(8, sets - t0);
+                int64_t xo[8], xn[8];
+                for (int i = 0; i < segs; ++i) {
+                    const int64_t r0 = b->h_set_row_off[t0 + i], nr = b->h_set_row_off[t0 + i + 1] - r0;
+                    xo[i] = r0 * ldx; xn[i] = nr > 0 ? (nr - 1) * ldx + K : 0;
+                }
+                rc = gm_amax_segs(x, xo, xn, segs, slots + (int64_t)t0 * GM_BOUND_PAD, GM_BOUND_PAD, st);
+            }
+            if (rc == GM_OK) rc = gm_amax(W, w_stride, 0, (int64_t)K * N, wsets, slots + (int64_t)sets * GM_BOUND_PAD, GM_BOUND_PAD, st);
+            wb.amax = slots + (int64_t)sets * GM_BOUND_PAD; wb.stride = w_stride ? GM_BOUND_PAD : 0;
+            g.np = 2; g.a_bound = gm_no_bound(); g.a_bound.amax = slots; g.a_bound.stride = GM_BOUND_PAD; g.b_bound = wb; g.amax_out = amax_out;
+        }
+        // trans_w: W stored [N, K] -- the planes are its own rows (as the dZ product's)
+        if (rc == GM_OK) rc = gm_split_weights(W, w_stride, 0, K, N, trans_w ? 1 : 0, wsets, planes, st, mode == 2 ? 2 : 3, wb);
+        g.Bsplit = planes; g.bsplit_stride = w_stride ? (int64_t)3 * K * N : 0;
+    }
+    if (rc == GM_OK) rc = gm_launch_gemm_nn(g, st);
+    if (planes) gm_dev_free(planes, st);
+    if (slots) gm_dev_free(slots, st);
+    gm_batch_mark_use(b, st);
+    return rc;
+}
+
 // ================================================================================ weight gradient, exported for numerics tests
 extern "C" int gm_dense_wgrad(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, const float* g, int64_t ldg, int32_t N, const float* s,
                               const float* gb, int64_t ldgb, float* dW, int64_t dw_stride, float* db, int64_t db_stride, int32_t mode,

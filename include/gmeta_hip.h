@@ -175,6 +175,24 @@ int gm_gcn_backward(const gm_batch_t* b, const gm_model_t* m, const float* param
  * 2: split-fp16 kernel (two pieces; the bounds of x and of every W_t are taken by the call itself). */
 int gm_dense_update(const gm_batch_t* b, const float* x, int32_t K, const float* W, int64_t w_stride, int32_t N, float* out, int32_t mode,
                     void* stream);
+/* The same product with the epilogue of the forward and dZ GEMMs, exported for numerics tests of every kernel gm_dense_update can reach:
+ *   out[r, :N] = epi(s[r] * (x[r, :K] @ B_t) + bias_t)   for the rows r of set t,
+ * B_t = W_t ([K, N] row-major), or W_t^T when trans_w (W_t stored [N, K], as in dZ = dQ W^T);  W_t = W + t * w_stride (0: one matrix for every
+ * set);  x: device [rows, ldx];  out: [rows, ldc], columns [N, ldc) untouched.  s: row scale [rows] or NULL (1); s_keep (split kernels only,
+ * or NULL): the row scale again with the sign bit set on rows that are computed and not stored (the exact kernels use s and store every row);
+ * bias_t = bias + t * bias_stride [N] or NULL;  relu: max(v, 0), NaN kept.  relu_bits (or NULL): packed relu' bits of the stored value, byte
+ * (r * ldc + c) / 4, bit c % 4;  mask_h [rows, ldc] (or NULL): zero where mask_h <= 0;  mask_b (or NULL): the same as packed bits.
+ * zero_out (or NULL): a [rows, ldc] buffer filled with zeros (the split kernels need ldc == N).  amax_out (mode 2 only, or NULL): per-set slots
+ * t * 64 (zeroed by the caller) that receive the fp32 bits of the largest |out| the kernel stores for set t.
+ * mode -1: the library's choice (gm_set_gemm_mode + launch size; three pieces), 0: exact-fp32 kernels (by shape and alignment), 1: split-bf16
+ * kernel (three pieces), 2: split-fp16 kernel (two pieces; per-set bounds of x's rows and of every W_t are taken by the call itself).
+ * GM_EINVAL: a split kernel with mask_h / mask_b, N not 128 or 256, K not a multiple of 16 or below 32, or zero_out with ldc != N;
+ * relu_bits / mask_b where the C stores are not 16-byte vectors.  launched (or NULL) receives the id of the kernel instantiation that ran
+ * (GM_GEMM_ID_* in the library's internal header). */
+int gm_dense_gemm(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, const float* W, int64_t w_stride, int32_t trans_w, int32_t N,
+                  float* out, int64_t ldc, const float* s, const float* s_keep, const float* bias, int64_t bias_stride, int32_t relu,
+                  uint8_t* relu_bits, const float* mask_h, const uint8_t* mask_b, float* zero_out, uint32_t* amax_out, int32_t mode,
+                  int32_t* launched, void* stream);
 /* The weight gradient of the same layer (learner.py backward of `torch.matmul(feat, weight)` + bias) over the batch's weight-gradient row chunks,
  * per set t:  dW_t[K, N] = sum over the set's rows r of (s[r] x[r, :])^T g[r, :]  and  db_t[N] = sum_r gb[r, :].  Exported for numerics tests of the
  * weight-gradient kernels.  x: device [rows, ldx] (K used), g: [rows, ldg] (N used); s: row scale [rows] or NULL (1); gb: [rows, ldgb] or NULL (g).

@@ -74,3 +74,62 @@ def arxiv_query_batch(T=8):
                              tables=data['tables'], verbose=False)
     batch = db.get_batch(list(range(T)))
     return batch[2][0].view_of, store
+
+
+def n_cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def chunk_count(set_rows, n_cu):
+    """Weight-gradient chunks of a batch with these set sizes: a restatement of gm_wgrad_chunk_rows (gm_internal.h)."""
+    total, mx = sum(set_rows), max(1, max(set_rows))
+
+    def chunks_at(cr):
+        return sum((n + cr - 1) // cr for n in set_rows)
+    best, best_eff = 128, -1.0
+    for rounds in (1, 2, 3, 4, 6, 8):
+        cap = n_cu * rounds
+        lo, hi = 1, (mx + 31) // 32
+        if chunks_at(32 * hi) > cap:
+            continue
+        while lo < hi:
+            mid = (lo + hi) // 2
+            if chunks_at(32 * mid) <= cap:
+                hi = mid
+            else:
+                lo = mid + 1
+        cr = max(128, 32 * lo)
+        c = chunks_at(cr)
+        eff = total / (((c + n_cu - 1) // n_cu) * n_cu * cr)
+        if eff > best_eff + 0.25:
+            best_eff, best = eff, cr
+    return chunks_at(best)
+
+
+class Batch:
+    """A SubgraphBatch with what the numerics tests need: set row offsets, the batch's own norm (device pointer + a copy), its weight-gradient
+    chunk count and GEMM tile count."""
+
+    def __init__(self, B):
+        self.B, self.T, self.rows = B, B.sets, B.rows
+        self.so = [int(v) for v in B.sub_off[B.set_sub_off]]
+        self.set_rows = [self.so[t + 1] - self.so[t] for t in range(self.T)]
+        self.norm_ptr = B.device_ptr(_lib.F_NORM)
+        self.norm = torch.from_numpy(B._read(_lib.F_NORM, B.rows, np.float32).copy()).cuda()
+        self.n_chunks = chunk_count(self.set_rows, n_cus())
+        self.n_tiles = sum((n + 127) // 128 for n in self.set_rows)          # GEMM row tiles of at most 128 rows, per set (gm_batch_finalize)
+
+
+def synthetic_batch(set_rows, seed):
+    """One subgraph per set with exactly set_rows[t] nodes of one random 1,100-node graph (SubgraphBatch.from_nodes)."""
+    rng = np.random.default_rng(seed)
+    n = 1100
+    src, dst = rng.integers(0, n, 6 * n), rng.integers(0, n, 6 * n)
+    store = gmeta_amd.GraphStore([(n, src.astype(np.int64), dst.astype(np.int64))], [rng.standard_normal((n, 8)).astype(np.float32)])
+    lists = [np.sort(rng.choice(n, r, replace=False)).astype(np.int32) for r in set_rows]
+    seeds = np.array([(0, int(l[0]), -1) for l in lists], np.int32)
+    B = SubgraphBatch.from_nodes(store, seeds, np.arange(len(set_rows) + 1), lists, False)
+    b = Batch(B)
+    b.store = store
+    assert b.set_rows == list(set_rows)
+    return b
