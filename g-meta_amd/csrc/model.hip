@@ -482,6 +482,61 @@ __global__ void k_protos_to_dlogits(const float* dprotos, const int32_t* rows, c
     }
 }
 
+// Scoring of query subgraphs against their set's prototypes (gm_proto_predict): one wave per subgraph, as k_head_fwd, so a set may hold any number of
+// subgraphs.  Per subgraph the same operations in the same order as k_head_loss's: the head of head_fwd_sub, a_c = -sqdist to every prototype, then
+// proto_set's log-softmax (a - m) - log(sum_c exp(a_c - m)) in class order and its FIRST maximum (class 0 when every entry is NaN or all round equal).
+// LDS per wave: the set's prototypes [c_task, D] and a_c [c_task].  logits: [subs, D] (written, then read back by the same block); logp: [subs, c_task],
+// -inf at and above the set's class count; pred: [subs].
+__global__ __launch_bounds__(256) void k_head_predict(HeadK k, const float* protos, int c_task, const int32_t* n_cls, float* logits, float* logp, int32_t* pred) {
+    extern __shared__ __attribute__((aligned(16))) float sm_generic[];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, s = blockIdx.x * 4 + w, D = k.C;
+    lds_float* pw = (lds_float*)sm_generic + w * c_task * (D + 1);
+    lds_float* aw = pw + c_task * D;
+    const bool live = s < k.subs;
+    const int set = live ? k.sub_set[s] : 0;
+    const int nt = live ? n_cls[set] : 0;
+    if (live) {
+        for (int id = lane; id < nt * D; id += 64) pw[id] = protos[(int64_t)set * c_task * D + id];
+        head_fwd_sub<MemG>(k, s, lane, logits, nullptr, 0, nullptr, 0);
+    }
+    __syncthreads();          // workgroup-scope fence: the logits written above are visible to the whole block, as in k_head_loss
+    const float* x = logits + (int64_t)s * D;
+    for (int c = lane; c < nt; c += 64) aw[c] = -sqdist(x, pw + c * D, D);
+    __syncthreads();
+    if (!live) return;
+    float m = -INFINITY;
+    for (int c = 0; c < nt; ++c) m = fmaxf(m, aw[c]);
+    float se = 0.f;
+    for (int c = 0; c < nt; ++c) se += expf(aw[c] - m);
+    const float lg = logf(se);
+    float* lp = logp + (int64_t)s * c_task;
+    for (int c = lane; c < c_task; c += 64) lp[c] = c < nt ? (aw[c] - m) - lg : -INFINITY;
+    if (lane == 0) {
+        float bl = -INFINITY; int best = 0;
+        for (int c = 0; c < nt; ++c) { const float v = (aw[c] - m) - lg; if (v > bl) { bl = v; best = c; } }
+        pred[s] = best;
+    }
+}
+
+// gm_meta_adapt's outputs in the caller's layouts: fw_out[t] = fw[t] without the `shift` zero rows at `cut` (k_finalize's unpadding), and the
+// prototypes [T, Ct, D] (set t's first tab[3t + 1] classes) restrided to [T, c_task, D] with zero rows at and above the set's class count
+__global__ void k_adapt_out(const float* fw, int64_t fw_in_stride, int64_t P, int64_t cut, int64_t shift, float* fw_out, int64_t fw_stride,
+                            const float* protos, int Ct, const int32_t* tab, int c_task, int D, float* protos_out) {
+    const int t = blockIdx.y;
+    const int64_t step = (int64_t)gridDim.x * blockDim.x, i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    for (int64_t i = i0; i < P; i += step) fw_out[t * fw_stride + i] = fw[t * fw_in_stride + (i < cut ? i : i + shift)];
+    const int nt = tab[t * 3 + 1];
+    for (int64_t id = i0; id < (int64_t)c_task * D; id += step)
+        protos_out[(int64_t)t * c_task * D + id] = id < (int64_t)nt * D ? protos[(int64_t)t * Ct * D + id] : 0.f;
+}
+
+// k_pad_params for one parameter vector per set: out[t] (stride ostride) = src[t] (stride sstride) with `shift` zeros inserted at `cut`
+__global__ void k_pad_params_sets(const float* src, int64_t sstride, int64_t P, int64_t cut, int64_t shift, float* out, int64_t ostride) {
+    const int t = blockIdx.y;
+    for (int64_t id = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; id < P + shift; id += (int64_t)gridDim.x * blockDim.x)
+        out[t * ostride + id] = id < cut ? src[t * sstride + id] : (id < cut + shift ? 0.f : src[t * sstride + id - shift]);
+}
+
 // Row-sparse backward, expansion through the transposed aggregate: for every in-edge e = (u -> centre k)
 //   G1[e,:] = norm[u] * relu'(H1[u,:]) * T2[k,:]      (dQ_{L-1} restricted to the rows that can be non-zero)
 __global__ void k_expand_edges(const float* T2, const float* H1, int F, const int32_t* e_row, const int32_t* e_par, const float* e_norm,
@@ -1413,6 +1468,27 @@ struct MetaPlan {
     unsigned* bound_ws; int64_t bound_words;      // gm_bound.h slots of this step ([S passes | Q passes | weights]), zeroed by ONE memset; NULL: three-piece kernels
 };
 
+// split-bf16 planes of every fast-weight vector fw_1..fw_K (= fw + (k-1) * TP; dense schedule, layers the split GEMM can take): forward planes
+// for every such layer, dZ planes for layers >= 1; ~1 MB per task and inner step at 128/256/256
+static void plan_planes(PlaneDir& pd, const gm_layout& L, int T, int K, float* fw, int64_t TP, bool dense, Carver& cv) {
+    pd = PlaneDir{};
+    if (gm_gemm_mode() == 1 && dense && K < 64) {
+        int64_t per_k = 0;
+        for (int l = 0; l < L.n_gcn; ++l) {
+            const int fi = L.dims[l], fo = L.dims[l + 1];
+            pd.off[l][0] = pd.off[l][1] = -1;
+            if (fi > fo) continue;                                           // multiply-first layers keep the on-the-fly path
+            const int64_t sz = (int64_t)T * 3 * fi * fo;
+            if ((fo == 256 || fo == 128) && fi % 16 == 0 && fi >= 32) { pd.off[l][0] = per_k; per_k += sz; }                 // X @ W: K = fi, N = fo
+            if (l > 0 && (fi == 256 || fi == 128) && fo % 16 == 0 && fo >= 32) { pd.off[l][1] = per_k; per_k += sz; }        // dQ @ W^T: K = fo, N = fi
+        }
+        if (per_k > 0) {
+            pd.base = cv.take<uint16_t>(per_k * K); pd.per_k = per_k; pd.fw0 = fw; pd.TP = TP; pd.K = K;
+            if (!pd.base) pd.base = reinterpret_cast<uint16_t*>(1);      // sizing pass (no workspace yet): keep the layout decisions identical
+        }
+    }
+}
+
 static int meta_plan(MetaPlan& p, const gm_batch* spt, const gm_batch* qry, const gm_model_t* m, const gm_hparams_t* hp, void* ws, int64_t ws_bytes,
                      int Ct, int ns, int nq, int64_t* need) {
     GM_TRY(gm_make_layout(m, &p.L));
@@ -1451,24 +1527,7 @@ static int meta_plan(MetaPlan& p, const gm_batch* spt, const gm_batch* qry, cons
     p.logit_q2 = p.nq_ctx == 2 ? cv.take<float>((int64_t)qry->subs * C) : nullptr;
     gcn_carve(p.S, cv); gcn_carve(p.Q, cv);
     if (p.nq_ctx == 2) { gcn_carve(p.Q2, cv); p.Q2.hub_set = 1; }
-    // split-bf16 planes of every fast-weight vector (dense schedule, layers the split GEMM can take): forward planes for every such
-    // layer, dZ planes for layers >= 1; ~1 MB per task and inner step at 128/256/256
-    p.pd = PlaneDir{};
-    if (gm_gemm_mode() == 1 && !p.S.cone && p.K < 64) {
-        int64_t per_k = 0;
-        for (int l = 0; l < p.L.n_gcn; ++l) {
-            const int fi = p.L.dims[l], fo = p.L.dims[l + 1];
-            p.pd.off[l][0] = p.pd.off[l][1] = -1;
-            if (fi > fo) continue;                                           // multiply-first layers keep the on-the-fly path
-            const int64_t sz = (int64_t)p.T * 3 * fi * fo;
-            if ((fo == 256 || fo == 128) && fi % 16 == 0 && fi >= 32) { p.pd.off[l][0] = per_k; per_k += sz; }                 // X @ W: K = fi, N = fo
-            if (l > 0 && (fi == 256 || fi == 128) && fo % 16 == 0 && fo >= 32) { p.pd.off[l][1] = per_k; per_k += sz; }        // dQ @ W^T: K = fo, N = fi
-        }
-        if (per_k > 0) {
-            p.pd.base = cv.take<uint16_t>(per_k * p.K); p.pd.per_k = per_k; p.pd.fw0 = p.fw; p.pd.TP = TP; p.pd.K = p.K;
-            if (!p.pd.base) p.pd.base = reinterpret_cast<uint16_t*>(1);      // sizing pass (no workspace yet): keep the layout decisions identical
-        }
-    }
+    plan_planes(p.pd, p.L, p.T, p.K, p.fw, TP, !p.S.cone, cv);
     // two-piece fp16 split kernels: when the weight planes are kept, every GCN layer is aggregate-first and the dense schedule runs
     p.bound_ws = nullptr; p.bound_words = 0; p.viol = nullptr;
     bool agg_first = true;
@@ -1688,6 +1747,192 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
                        have_grad ? p.gq : nullptr, p.gp, Pp, Lu.P, T, p.lq, p.aq, K1, out, cut, shift, p.viol);
     GM_HIP(hipGetLastError());
     gm_batch_mark_use(spt, st); gm_batch_mark_use(qry, st);
+    return GM_OK;
+}
+
+// ================================================================================ adaptation and prediction (beyond the reference)
+// gm_meta_adapt is the support chain of gm_meta_step alone (the same launches on the same context layout: forward -> k_head_loss -> backward with
+// the fused SGD, K times); gm_proto_predict is one query forward at per-set parameters followed by k_head_predict.  Both use the three-piece split
+// kernels (no bound slots).
+struct AdaptPlan {
+    gm_layout L; int T, K; int64_t Pp, TP, proto_sz;
+    GcnCtx S;
+    PlaneDir pd;
+    float *theta_p, *fw, *g, *logit_s, *dlog_s, *protos, *ls, *as_;
+    int32_t *rows_s, *tab_s;                  // class tables, one block [rows_s (spt->subs) | tab_s (3T)]
+};
+
+static int adapt_plan(AdaptPlan& p, const gm_batch* spt, const gm_model_t* m, const gm_hparams_t* hp, void* ws, int64_t ws_bytes, int64_t* need) {
+    GM_TRY(gm_make_layout(m, &p.L));
+    p.T = spt->sets; p.K = hp->update_step; p.Pp = (p.L.P + 63) / 64 * 64;
+    p.S = GcnCtx{}; p.S.is_support = true; p.S.b = spt; p.S.L = p.L;
+    if (hp->cone) {
+        const gm_cone* cs = nullptr;
+        GM_TRY(gm_batch_cone(spt, p.L.n_gcn, spt->stream, &cs));
+        if (cs->ok) p.S.cone = cs;
+    }
+    Carver cv(ws, ws_bytes);
+    const int C = p.L.n_out, K1 = p.K + 1;
+    p.TP = (int64_t)p.T * p.Pp; p.proto_sz = (int64_t)p.T * 256 * C;
+    p.theta_p = cv.take<float>(p.Pp);
+    p.fw = cv.take<float>(p.TP * p.K); p.g = cv.take<float>(p.TP);
+    p.logit_s = cv.take<float>((int64_t)spt->subs * C); p.dlog_s = cv.take<float>((int64_t)spt->subs * C);
+    p.protos = cv.take<float>(p.proto_sz);                      // every step overwrites them: the last support step's are the result
+    p.ls = cv.take<float>((int64_t)p.T * K1); p.as_ = cv.take<float>((int64_t)p.T * K1);
+    p.rows_s = cv.take<int32_t>((int64_t)spt->subs + 3 * (int64_t)p.T);
+    p.tab_s = p.rows_s ? p.rows_s + spt->subs : nullptr;
+    gcn_carve(p.S, cv);
+    plan_planes(p.pd, p.L, p.T, p.K, p.fw, p.TP, !p.S.cone, cv);
+    if (need) *need = cv.used + 256;
+    GM_REQUIRE(cv.ok(), GM_ENOMEM, "meta_adapt: workspace too small (%lld < %lld)", (long long)ws_bytes, (long long)cv.used);
+    return GM_OK;
+}
+
+extern "C" int64_t gm_adapt_ws_bytes(const gm_batch_t* spt, const gm_model_t* m, const gm_hparams_t* hp) {
+    if (!spt || !m || !hp || hp->update_step < 0) return -1;
+    AdaptPlan p; int64_t need = 0, cut, shift;
+    const gm_model_t mp = internal_model(m, spt->store, &cut, &shift);
+    if (adapt_plan(p, spt, &mp, hp, nullptr, 0, &need) != GM_OK) return -1;
+    return need;
+}
+
+extern "C" int gm_meta_adapt(const gm_batch_t* spt, const int32_t* y_spt, const gm_model_t* m, const gm_hparams_t* hp, const float* theta, float* fw_out,
+                             int64_t fw_stride, float* protos_out, int32_t c_task, void* ws, int64_t ws_bytes, void* stream) {
+    GM_REQUIRE(spt && y_spt && m && hp && theta && fw_out && protos_out && ws, GM_EINVAL, "meta_adapt: NULL argument");
+    const int K = hp->update_step;
+    GM_REQUIRE(K >= 0, GM_EINVAL, "meta_adapt: update_step must be >= 0 (got %d)", K);
+    GM_REQUIRE(!hp->need_meta_grad, GM_EINVAL, "meta_adapt: need_meta_grad must be 0 (adaptation computes no meta-gradient)");
+    GM_REQUIRE(hp->k_spt >= 1, GM_EINVAL, "meta_adapt: k_spt must be >= 1");
+    GM_REQUIRE(((uintptr_t)theta & 15) == 0, GM_EINVAL, "meta_adapt: theta must be 16-byte aligned");
+    gm_layout Lu;                                          // the caller's parameter layout (theta, fw_out)
+    GM_TRY(gm_make_layout(m, &Lu));
+    GM_REQUIRE(fw_stride >= Lu.P, GM_EINVAL, "meta_adapt: fw_stride %lld < P=%lld", (long long)fw_stride, (long long)Lu.P);
+    hipStream_t st = (hipStream_t)stream;
+    ClassTables cs;
+    GM_TRY(class_tables(spt, y_spt, hp->k_spt, cs));
+    GM_REQUIRE(c_task >= cs.Ct, GM_EINVAL, "meta_adapt: c_task=%d but a support set has %d classes", c_task, cs.Ct);
+    const int Ct = cs.Ct, ns = cs.n;
+    AdaptPlan p;
+    int64_t cut = 0, shift = 0;
+    const gm_model_t mp = internal_model(m, spt->store, &cut, &shift);
+    GM_TRY(adapt_plan(p, spt, &mp, hp, ws, ws_bytes, nullptr));
+    const gm_layout& L = p.L; const int T = p.T, C = L.n_out, K1 = K + 1; const int64_t Pp = p.Pp;
+    p.S.pd = p.pd.base ? &p.pd : nullptr;
+    if (shift) {
+        hipLaunchKernelGGL(k_pad_params, dim3((int)std::min<int64_t>(512, (L.P + 255) / 256)), dim3(256), 0, st, theta, Lu.P, cut, shift, p.theta_p);
+        GM_HIP(hipGetLastError());
+        theta = p.theta_p;
+    }
+    {   // support class tables -> pinned staging -> one asynchronous copy
+        const size_t n_tab = (size_t)spt->subs + 3 * (size_t)T;
+        void* h = nullptr; int slot = 0;
+        StageRing& ring = stage_ring();
+        GM_TRY(ring.acquire(4 * n_tab, &h, &slot));
+        int32_t* hp32 = (int32_t*)h;
+        memset(hp32, 0, 4 * n_tab);
+        memcpy(hp32, cs.rows.data(), 4 * cs.rows.size());
+        memcpy(hp32 + spt->subs, cs.tab.data(), 4 * cs.tab.size());
+        GM_HIP(hipMemcpyAsync(p.rows_s, h, 4 * n_tab, hipMemcpyHostToDevice, st));
+        GM_TRY(ring.release_after(slot, st));
+    }
+    auto fw = [&](int k) -> float* { return p.fw + (int64_t)(k - 1) * p.TP; };       // fw_k, k = 1..K
+    const int hoist = hp->hoist_z1, sparse = hp->sparse_bwd;
+    const int fwd_mode = (sparse && sparse_bwd_ok(p.L)) ? 0 : 2;
+    // gm_meta_step's spt_step / spt_step_bwd (meta.py:122-126,145-151); K = 0: the forward and the prototypes only
+    for (int k = 0; k < std::max(K, 1); ++k) {
+        const float* w = k ? fw(k) : theta;
+        const int64_t wstride = k ? Pp : 0;
+        const bool bwd = K > 0;
+        GM_TRY(gcn_forward(p.S, w, wstride, p.logit_s, st, hoist, 1, fwd_mode));
+        if (bwd) p.S.sgd = SgdK{w, wstride, fw(k + 1), Pp, hp->update_lr};
+        ProtoK pk{p.logit_s, C, p.rows_s, Ct, ns, 0, nullptr, p.protos, p.ls, p.as_, K1, k, bwd ? p.dlog_s : nullptr, nullptr, 0, p.tab_s, cs.uniform ? 1 : 0};
+        GM_TRY(head_loss(p.S, w, wstride, p.logit_s, pk, bwd ? 1 : 0, p.g, Pp, sparse, st));
+        if (bwd) {
+            GM_TRY(gcn_backward(p.S, w, wstride, p.dlog_s, p.g, Pp, st, sparse, 1));
+            p.S.sgd = SgdK{nullptr, 0, nullptr, 0, 0.f};
+        }
+    }
+    const int64_t big = std::max<int64_t>(Lu.P, (int64_t)c_task * C);
+    hipLaunchKernelGGL(k_adapt_out, dim3((int)std::min<int64_t>(256, (big + 255) / 256), T), dim3(256), 0, st, K ? fw(K) : theta, K ? Pp : 0, Lu.P, cut, shift,
+                       fw_out, fw_stride, p.protos, Ct, p.tab_s, c_task, C, protos_out);
+    GM_HIP(hipGetLastError());
+    gm_batch_mark_use(spt, st);
+    return GM_OK;
+}
+
+struct PredictPlan {
+    gm_layout L; int64_t Pp;
+    GcnCtx Q;
+    float *params_p, *logits;
+    int32_t* n_cls;
+};
+
+static int predict_plan(PredictPlan& p, const gm_batch* qry, const gm_model_t* m, const gm_hparams_t* hp, bool own_logits, void* ws, int64_t ws_bytes, int64_t* need) {
+    GM_TRY(gm_make_layout(m, &p.L));
+    p.Pp = (p.L.P + 63) / 64 * 64;
+    p.Q = GcnCtx{}; p.Q.b = qry; p.Q.L = p.L;
+    if (hp->cone) {
+        const gm_cone* cq = nullptr;
+        GM_TRY(gm_batch_cone(qry, p.L.n_gcn, qry->stream, &cq));
+        if (cq->ok) p.Q.cone = cq;
+    }
+    Carver cv(ws, ws_bytes);
+    p.params_p = cv.take<float>((int64_t)qry->sets * p.Pp);
+    p.logits = own_logits ? cv.take<float>((int64_t)qry->subs * p.L.n_out) : nullptr;
+    p.n_cls = cv.take<int32_t>(qry->sets);
+    gcn_carve(p.Q, cv);
+    if (need) *need = cv.used + 256;
+    GM_REQUIRE(cv.ok(), GM_ENOMEM, "proto_predict: workspace too small (%lld < %lld)", (long long)ws_bytes, (long long)cv.used);
+    return GM_OK;
+}
+
+extern "C" int64_t gm_predict_ws_bytes(const gm_batch_t* qry, const gm_model_t* m, const gm_hparams_t* hp) {
+    if (!qry || !m || !hp) return -1;
+    PredictPlan p; int64_t need = 0, cut, shift;
+    const gm_model_t mp = internal_model(m, qry->store, &cut, &shift);
+    if (predict_plan(p, qry, &mp, hp, true, nullptr, 0, &need) != GM_OK) return -1;
+    return need;
+}
+
+extern "C" int gm_proto_predict(const gm_batch_t* qry, const gm_model_t* m, const gm_hparams_t* hp, const float* params, int64_t param_stride,
+                                const float* protos, const int32_t* n_classes, int32_t c_task, float* logits_out, float* logp_out, int32_t* pred_out,
+                                void* ws, int64_t ws_bytes, void* stream) {
+    GM_REQUIRE(qry && m && hp && params && protos && n_classes && logp_out && pred_out && ws, GM_EINVAL, "proto_predict: NULL argument");
+    gm_layout Lu;
+    GM_TRY(gm_make_layout(m, &Lu));
+    GM_REQUIRE(param_stride >= Lu.P, GM_EINVAL, "proto_predict: param_stride %lld < P=%lld", (long long)param_stride, (long long)Lu.P);
+    GM_REQUIRE(c_task >= 1 && c_task <= 256, GM_EINVAL, "proto_predict: c_task=%d outside [1, 256]", c_task);
+    for (int t = 0; t < qry->sets; ++t)
+        GM_REQUIRE(n_classes[t] >= 1 && n_classes[t] <= c_task, GM_EINVAL, "proto_predict: set %d has %d classes, outside [1, c_task=%d]", t, n_classes[t], c_task);
+    const size_t lds = sizeof(float) * 4 * (size_t)c_task * (Lu.n_out + 1);
+    GM_REQUIRE(lds <= 160 * 1024, GM_ERANGE, "proto_predict: %d classes x %d logits per set is outside the scoring kernel's range", c_task, Lu.n_out);
+    hipStream_t st = (hipStream_t)stream;
+    PredictPlan p;
+    int64_t cut = 0, shift = 0;
+    const gm_model_t mp = internal_model(m, qry->store, &cut, &shift);
+    GM_TRY(predict_plan(p, qry, &mp, hp, logits_out == nullptr, ws, ws_bytes, nullptr));
+    const int T = qry->sets;
+    float* logits = logits_out ? logits_out : p.logits;
+    if (T > 0) {
+        hipLaunchKernelGGL(k_pad_params_sets, dim3((int)std::min<int64_t>(256, (p.L.P + 255) / 256), T), dim3(256), 0, st, params, param_stride, Lu.P, cut, shift,
+                           p.params_p, p.Pp);
+        GM_HIP(hipGetLastError());
+        void* h = nullptr; int slot = 0;
+        StageRing& ring = stage_ring();
+        GM_TRY(ring.acquire(4 * (size_t)T, &h, &slot));
+        memcpy(h, n_classes, 4 * (size_t)T);
+        GM_HIP(hipMemcpyAsync(p.n_cls, h, 4 * (size_t)T, hipMemcpyHostToDevice, st));
+        GM_TRY(ring.release_after(slot, st));
+    }
+    if (qry->subs > 0) {
+        // gm_meta_step's query evaluation nobody differentiates (fwd_only = 1: the fused aggregate + GEMM where eligible), then the scoring kernel
+        GM_TRY(gcn_forward(p.Q, p.params_p, p.Pp, logits, st, hp->hoist_z1, 1, 1));
+        HeadK hk = make_head(p.Q, p.params_p, p.Pp);
+        if (lds > 64 * 1024) GM_TRY(gm_func_full_lds((const void*)k_head_predict));
+        hipLaunchKernelGGL(k_head_predict, dim3((qry->subs + 3) / 4), dim3(256), lds, st, hk, protos, (int)c_task, p.n_cls, logits, logp_out, pred_out);
+        GM_HIP(hipGetLastError());
+    }
+    gm_batch_mark_use(qry, st);
     return GM_OK;
 }
 

@@ -378,6 +378,43 @@ class Meta(nn.Module):
             accs = self.finetunning_ProtoMAML(x_spt, y_spt, x_qry, y_qry, c_spt, c_qry, n_spt, n_qry, g_spt, g_qry, feat)
         return accs
 
+    # ---- beyond the reference: label new subgraphs with an adapted model (Adapted / Prediction below)
+    def adapt(self, x_spt, y_spt, K=None):
+        """Fine-tune a copy of theta on every task's support set (the inner loop of finetunning_ProtoMAML, meta.py:181-229, without its query
+        sets): K (default update_step_test) SGD steps of the prototypical loss.  theta, its .grad and the Adam state are left untouched."""
+        _lib.require_gpu()
+        lib = _lib.lib()
+        K = self.update_step_test if K is None else int(K)
+        if K < 0:
+            raise ValueError('K must be >= 0 (got %d)' % K)
+        theta = self._flat_theta()
+        dev = theta.device
+        if dev.type != 'cuda':
+            raise RuntimeError('Meta parameters must live on the GPU (call .to("cuda")); there is no CPU fallback')
+        S = _as_batch(x_spt)
+        ys = _labels(list(y_spt))
+        if len(ys) != S.subs:
+            raise ValueError('label count does not match the number of support subgraphs')
+        off = S.set_sub_off
+        classes = [np.unique(ys[int(off[t]):int(off[t + 1])]) for t in range(S.sets)]
+        c_task = max(len(c) for c in classes)
+        model = self.net.model
+        P = int(lib.gm_model_param_count(C.byref(model)))
+        hp = _lib.HParams(float(self.update_lr), K, int(self.k_spt), 0, int(self.hoist_z1), int(self.serialize), int(self.sparse_bwd), int(self.cone))
+        ws_bytes = int(lib.gm_adapt_ws_bytes(S.handle, C.byref(model), C.byref(hp)))
+        if ws_bytes < 0:
+            _lib.check(-1, 'gm_adapt_ws_bytes')
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        fw = torch.empty(S.sets, P, dtype=torch.float32, device=dev)
+        protos = torch.empty(S.sets, c_task, model.n_out, dtype=torch.float32, device=dev)
+        _lib.check(lib.gm_meta_adapt(S.handle, _lib.ptr(ys), C.byref(model), C.byref(hp), _lib.ptr(theta), _lib.ptr(fw), P, _lib.ptr(protos), int(c_task),
+                                     _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), 'gm_meta_adapt')
+        return Adapted(self, S.store, fw, protos, classes, K)
+
+    def predict(self, x_spt, y_spt, x_qry, K=None, tasks=None, logits=False):
+        """adapt(x_spt, y_spt, K) followed by predict(x_qry, tasks)."""
+        return self.adapt(x_spt, y_spt, K).predict(x_qry, tasks, logits)
+
 
 def _labels(ys):
     """The per-task label arrays of a meta-batch as one contiguous int32 vector (torch CPU tensors or numpy arrays)."""
@@ -468,3 +505,78 @@ class _Deferred:
         self._buf = None
         self._rerun = None
         return self._accs
+
+
+# ---- adaptation and prediction (beyond the reference: finetunning_ProtoMAML, meta.py:175-234, only scores labelled query sets)
+def _as_batch(x):
+    """A list of SubgraphBatch views (one per set) or one multi-set SubgraphBatch -> one SubgraphBatch."""
+    if isinstance(x, SubgraphBatch):
+        return x
+    x = list(x)
+    for b in x:
+        if not isinstance(b, SubgraphBatch):
+            raise TypeError('expected gmeta_amd.SubgraphBatch objects (from gmeta_amd.Subgraphs)')
+    if not x:
+        raise ValueError('no subgraph batch given')
+    return SubgraphBatch.concat(x)
+
+
+class Prediction:
+    """Labels of query subgraphs, per query set i (scored against task tasks[i] of the adaptation): log_probs[i] [n_q, n_t] (log-softmax of
+    -|z - prototype|^2 over the task's sorted support classes), pred[i] (class indices, the first maximum), labels[i] = classes[pred[i]] and, when
+    requested, logits[i] [n_q, n_out]; classes[i] = the task's sorted support labels (the columns of log_probs[i])."""
+
+    def __init__(self, log_probs, pred, labels, logits, classes, tasks):
+        self.log_probs, self.pred, self.labels, self.logits, self.classes, self.tasks = log_probs, pred, labels, logits, classes, tasks
+
+
+class Adapted:
+    """Result of Meta.adapt: per task t, fast_weights[t] (device [P], Classifier.vars order) = fw_K, prototypes[t] (device [c_task, n_out]) = the
+    support prototypes at fw_{max(K-1, 0)} (what finetunning scores step K against) and classes[t] (the sorted support labels)."""
+
+    def __init__(self, meta, store, fast_weights, prototypes, classes, K):
+        self._meta, self.store = meta, store
+        self.fast_weights, self.prototypes, self.classes, self.K = fast_weights, prototypes, classes, K
+
+    def predict(self, x_qry, tasks=None, logits=False):
+        """Label the query subgraphs of x_qry (a list of per-set SubgraphBatch views or one multi-set batch; no labels needed, sets of any size).
+        Query set i is scored against task tasks[i] (default: set i against task i).  Can be called any number of times."""
+        _lib.require_gpu()
+        lib = _lib.lib()
+        Q = _as_batch(x_qry)
+        T = len(self.classes)
+        tasks = list(range(T)) if tasks is None else [int(t) for t in tasks]
+        if len(tasks) != Q.sets:
+            raise ValueError('tasks has %d entries but the query batch holds %d sets' % (len(tasks), Q.sets))
+        if any(t < 0 or t >= T for t in tasks):
+            raise ValueError('tasks must index the %d adapted tasks' % T)
+        if Q.store is not self.store:
+            raise ValueError('the query batch comes from another store (GraphStore) than the support batch')
+        dev = self.fast_weights.device
+        model = self._meta.net.model
+        hp = _lib.HParams(float(self._meta.update_lr), int(self.K), int(self._meta.k_spt), 0, int(self._meta.hoist_z1), int(self._meta.serialize),
+                          int(self._meta.sparse_bwd), int(self._meta.cone))
+        idx = torch.tensor(tasks, dtype=torch.int64, device=dev)
+        params = self.fast_weights.index_select(0, idx).contiguous()
+        protos = self.prototypes.index_select(0, idx).contiguous()
+        ncls = np.ascontiguousarray([len(self.classes[t]) for t in tasks], np.int32)
+        c_task, n_out = self.prototypes.shape[1], self.prototypes.shape[2]
+        logp = torch.empty(Q.subs, c_task, dtype=torch.float32, device=dev)
+        pred = torch.empty(Q.subs, dtype=torch.int32, device=dev)
+        lg = torch.empty(Q.subs, n_out, dtype=torch.float32, device=dev) if logits else None
+        ws_bytes = int(lib.gm_predict_ws_bytes(Q.handle, C.byref(model), C.byref(hp)))
+        if ws_bytes < 0:
+            _lib.check(-1, 'gm_predict_ws_bytes')
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.gm_proto_predict(Q.handle, C.byref(model), C.byref(hp), _lib.ptr(params), params.shape[1], _lib.ptr(protos), _lib.ptr(ncls),
+                                        int(c_task), _lib.ptr(lg), _lib.ptr(logp), _lib.ptr(pred), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   'gm_proto_predict')
+        off = Q.set_sub_off
+        logp_h, pred_h = logp.cpu().numpy(), pred.cpu().numpy().astype(np.int64)
+        lg_h = lg.cpu().numpy() if logits else None
+        out_lp, out_p, out_l, out_z = [], [], [], []
+        for i, t in enumerate(tasks):
+            a, b, n = int(off[i]), int(off[i + 1]), len(self.classes[t])
+            out_lp.append(logp_h[a:b, :n]); out_p.append(pred_h[a:b]); out_l.append(self.classes[t][pred_h[a:b]])
+            out_z.append(lg_h[a:b] if logits else None)
+        return Prediction(out_lp, out_p, out_l, out_z if logits else None, [self.classes[t] for t in tasks], tasks)

@@ -554,6 +554,14 @@ class Subgraphs(Dataset):
         ys, yq = self._labels(arrs[0][2], arrs[0][3])
         return self._tuple(bs, bq, ys, yq)
 
+    def query_batch(self, names_per_task):
+        """Unlabelled query subgraphs for Meta.predict / Adapted.predict: one SubgraphBatch with one set per entry of names_per_task (names 'g_i',
+        or 'g_i_j' for pairs), extracted like the tasks' own subgraphs (this dataset's h, sample_nodes, sampling seed and link mode)."""
+        seeds = [self._seeds(list(names)) for names in names_per_task]
+        off = np.cumsum([0] + [len(s) for s in seeds])
+        return SubgraphBatch.extract(self.G, np.concatenate(seeds) if seeds else np.zeros((0, 3), np.int32), off, self.h, self.sample_nodes, self.rng_seed,
+                                     self.link_pred_mode)
+
     def get_batch(self, indices):
         """MI355X-first counterpart of DataLoader(..., collate_fn=collate): the subgraphs of ALL tasks of a
         meta-batch are extracted by two launches (support / query); returns the collated 10-tuple of lists."""

@@ -238,6 +238,25 @@ int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const int32_t* y_
                  const gm_model_t* m, const gm_hparams_t* hp, const float* theta, float* out, int64_t out_floats,
                  void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- Adaptation and prediction (beyond the reference, whose finetunning_ProtoMAML only scores labelled query sets).
+ * gm_meta_adapt: the support chain of gm_meta_step alone, for every set (task) of spt: fw_0 = theta, fw_{k+1} = fw_k - update_lr * grad L_spt(fw_k)
+ * for k < K = hp->update_step (K >= 0; hp->need_meta_grad must be 0; hoist_z1, sparse_bwd and cone are honoured; one stream).  y_spt: HOST int32
+ * labels per subgraph; theta: device [P], 16-byte aligned.  fw_out: device [sets, fw_stride] (fw_stride >= P) <- fw_K in the caller's layout;
+ * protos_out: device [sets, c_task, n_out] <- the prototypes of the support pass at fw_{max(K-1, 0)} -- the ones finetunning scores step K against
+ * (meta.py:136-139,152-154) -- of set t's sorted classes, zero rows at and above its class count.  GM_EINVAL if c_task is below a set's class count.
+ * gm_proto_predict: the query forward of every set s of qry at params + s * param_stride (caller's layout, param_stride >= P; gm_meta_step's
+ * forward-only query pass), then per subgraph q of set s: a_qc = -|z_q - protos[s, c]|^2 over the first n_classes[s] (HOST int32 [sets], 1..c_task)
+ * classes, logp_out[q, :] (device [subs, c_task]) = log_softmax(a_q), -inf at and above n_classes[s], pred_out[q] (device int32 [subs]) = its first
+ * maximum (class 0 when all are NaN or equal); logits_out (device [subs, n_out] or NULL) <- z_q.  No labels: sets may have any size.
+ * Both are stream-ordered (no host synchronisation) and always run the three-piece split kernels. */
+int64_t gm_adapt_ws_bytes(const gm_batch_t* spt, const gm_model_t* m, const gm_hparams_t* hp);
+int gm_meta_adapt(const gm_batch_t* spt, const int32_t* y_spt, const gm_model_t* m, const gm_hparams_t* hp, const float* theta, float* fw_out,
+                  int64_t fw_stride, float* protos_out, int32_t c_task, void* ws, int64_t ws_bytes, void* stream);
+int64_t gm_predict_ws_bytes(const gm_batch_t* qry, const gm_model_t* m, const gm_hparams_t* hp);
+int gm_proto_predict(const gm_batch_t* qry, const gm_model_t* m, const gm_hparams_t* hp, const float* params, int64_t param_stride,
+                     const float* protos, const int32_t* n_classes, int32_t c_task, float* logits_out, float* logp_out, int32_t* pred_out,
+                     void* ws, int64_t ws_bytes, void* stream);
+
 /* After the (optional) all-reduce of out[0 .. P + 2*(K+1)] over the ranks: the mean meta-gradient and the NaN guard of
  * meta.py:161-163, on the device.  head: device, the reduced block; grad: device fp32 [P] <- head[0..P) / task count;
  * found_inf: device fp32 [1] <- 1.0 if losses_q[K] / task count is NaN else 0.0 (a fused Adam skips its step on 1.0, which

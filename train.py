@@ -58,6 +58,8 @@ def parse(argv=None):
     ap.add_argument('--hoist_z1', type=int, default=0, help='1: aggregate the layer-1 input once per meta-step instead of in every forward')
     ap.add_argument('--sparse_bwd', type=int, default=0, help='1: backward only over the rows whose gradient is structurally non-zero')
     ap.add_argument('--cone', type=int, default=0, help='1: evaluate each layer only on the rows that can reach a centre (forward and backward)')
+    ap.add_argument('--predict_out', default=None, type=str,
+                    help='after the final test evaluation, label the query subgraphs of the test tasks with the early-stopped model and write them to this .npz')
     return ap.parse_args(argv)
 
 
@@ -149,7 +151,33 @@ def main(args):
         print('Test acc:', str(accs[-1])[:5])
         print('Early Stopped Test acc:', str(accs_max[-1])[:5])
         print('Total Time:', str(time.time() - s_start)[:5])
+    if args.predict_out and rank == 0:
+        write_predictions(args.predict_out, model_max, db_test, info)
     return {'test_acc': float(accs[-1]), 'early_stopped_test_acc': float(accs_max[-1]), 'val_best': float(max_acc)}
+
+
+def write_predictions(path, model, db, info):
+    """Meta.predict on every task of `db` (same tasks and K_test as the final evaluation).  The .npz holds, flattened over the tasks with
+    per-task offsets `task_off`: `names` (query subgraph names), `true` / `pred` (label values of the dataset's label.pkl) and `log_probs`
+    [n, c_max] (column c of task t = label value classes[class_off[t] + c]; -inf past the task's class count)."""
+    tasks = list(range(len(db)))
+    x = db.get_batch(tasks)
+    pr = model.predict(x[0], x[1], x[2])
+    names, true, pred, logp, classes, off, coff = [], [], [], [], [], [0], [0]
+    c_max = max(lp.shape[1] for lp in pr.log_probs)
+    for t in tasks:
+        spt_names, qry_names = db._task_names(t)
+        raw = {int(r): info[n] for r, n in zip(np.asarray(x[1][t]).reshape(-1), spt_names)}      # per-task rank (Disjoint relabelling) -> label value
+        names += qry_names
+        true += [info[n] for n in qry_names]
+        pred += [raw[int(c)] for c in pr.labels[t]]
+        lp = np.full((len(qry_names), c_max), -np.inf, np.float32)
+        lp[:, :pr.log_probs[t].shape[1]] = pr.log_probs[t]
+        logp.append(lp)
+        classes += [raw[int(c)] for c in pr.classes[t]]
+        off.append(len(names)); coff.append(len(classes))
+    np.savez(path, names=np.asarray(names), true=np.asarray(true), pred=np.asarray(pred), log_probs=np.concatenate(logp),
+             classes=np.asarray(classes), task_off=np.asarray(off, np.int64), class_off=np.asarray(coff, np.int64))
 
 
 if __name__ == '__main__':
