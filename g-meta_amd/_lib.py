@@ -53,6 +53,8 @@ PROTOTYPES = {
     'gm_dense_wgrad': (C.c_int, [vp, vp, i64, i32, vp, i64, i32, vp, vp, i64, vp, i64, vp, i64, i32, vp, vp, i64, C.c_float, vp, vp, vp, vp]),
     'gm_proto_loss_spt': (C.c_int, [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     'gm_proto_loss_qry': (C.c_int, [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+    'gm_set_ragged_classes': (None, [i32]),
+    'gm_get_ragged_classes': (i32, []),
     'gm_meta_ws_bytes': (i64, [vp, vp, vp, vp]),
     'gm_meta_out_floats': (i64, [vp, vp, vp]),
     'gm_meta_step': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp]),

@@ -223,6 +223,9 @@ struct ProtoK {
                                           // layout, like the per-task proto_loss calls of meta.py:118-157); prototypes are strided by Ct
     int uniform;                          // every set has Ct classes of n rows at offset set * Ct * n (the usual case): the kernels take the layout from the arguments
 };                                        // instead of a dependent load of `tab` ahead of the class rows
+// Ragged-task mode only: a launch may hold sets whose classes have unequal row counts (the kernels' RGK instantiations).  Such a set t has tab[3t + 2] =
+// -(its scored rows) and its block of `rows` is [class starts (Ct_t + 1, relative to the class rows) | class rows]; balanced sets of the same launch keep the
+// [off, Ct, n] form and the balanced code.  ProtoK::n of such a launch is rounded up so that Ct * n also covers the scored rows of every ragged set (LDS carve).
 
 template <typename XP>
 __device__ __forceinline__ float sqdist(XP x, const lds_float* p, int D) {
@@ -237,11 +240,28 @@ __device__ __forceinline__ float sqdist(XP x, const lds_float* p, int D) {
 // result) carry nothing but LDS reads that can be issued ahead.  The kernel is one workgroup per task and pure latency.
 // logits / dlogits / rows: the arrays the set is scored on -- k's global ones (MemG; rows already offset to the set) or the fused kernel's LDS copies (MemL).
 #define PROTO_A_MAX 8192
-template <int NT, typename M>
+// class of scored row q of a ragged set: the last class that starts at or before q (a class without rows -- a query set may have some -- starts where the
+// next one does, and is never the answer)
+template <typename CI>
+__device__ __forceinline__ int ragged_class(CI coff, int Ct, int q) {
+    int lo = 0, hi = Ct - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (coff[mid] <= q) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// RG: the set is ragged (see ProtoK): `rows` is its block [class starts | class rows], a row's class and a class's row count come from the class starts
+// (in LDS when the caller staged the block).  The LDS carve, the arithmetic and the summation orders are the balanced variant's.
+template <int NT, typename M, bool RG = false>
 __device__ __forceinline__ void proto_set(const ProtoK& k, int set, int tid, lds_float* sm, typename M::CF logits, typename M::F dlogits, typename M::CI rows,
                                           bool have_proto = false, float proto_pre = 0.f) {      // have_proto: protos_in[set][tid] was loaded by the caller (tid < Ct * D)
-    const int Ct = k.uniform ? k.Ct : k.tab[set * 3 + 1], n = k.uniform ? k.n : k.tab[set * 3 + 2];
-    const int Q = Ct * n, D = k.D, rb = k.row_base;
+    const int Ct = (k.uniform && !RG) ? k.Ct : k.tab[set * 3 + 1], n = RG ? 0 : (k.uniform ? k.n : k.tab[set * 3 + 2]);
+    const int Q = RG ? -k.tab[set * 3 + 2] : Ct * n, D = k.D, rb = k.row_base;
+    typename M::CI coff = rows;         // RG: class c scores rows[coff[c] .. coff[c + 1])
+    if constexpr (RG) rows += Ct + 1;
+    auto cls = [&](int q) -> int { if constexpr (RG) return ragged_class(coff, Ct, q); else return q / n; };
+    auto own = [&](int q, int c) -> bool { if constexpr (RG) return q >= coff[c] && q < coff[c + 1]; else return c == q / n; };
     lds_float* protos = sm;             // [Ct*D]   (LDS sized for the largest set)
     lds_float* lse = sm + k.Ct * D;     // [Q]
     lds_float* red = lse + k.Ct * k.n;  // [2 * NT]
@@ -252,9 +272,16 @@ __device__ __forceinline__ void proto_set(const ProtoK& k, int set, int tid, lds
         float p;
         if (k.mode == 0) {
             p = 0.f;
+            if constexpr (RG) {
+                const int r0 = coff[c], r1 = coff[c + 1];
 #pragma unroll 4
-            for (int r = 0; r < n; ++r) p += logits[(rows[c * n + r] - rb) * D + d];
-            p /= (float)n;                                                          // .mean(0) (meta.py:41)
+                for (int r = r0; r < r1; ++r) p += logits[(rows[r] - rb) * D + d];
+                p /= (float)(r1 - r0);
+            } else {
+#pragma unroll 4
+                for (int r = 0; r < n; ++r) p += logits[(rows[c * n + r] - rb) * D + d];
+                p /= (float)n;                                                      // .mean(0) (meta.py:41)
+            }
             if (k.protos_out) k.protos_out[(int64_t)set * k.Ct * D + id] = p;
         } else {
             p = (have_proto && id == tid) ? proto_pre : k.protos_in[(int64_t)set * k.Ct * D + id];
@@ -272,7 +299,7 @@ __device__ __forceinline__ void proto_set(const ProtoK& k, int set, int tid, lds
     float lpart = 0.f, apart = 0.f;
     for (int q = tid; q < Q; q += NT) {
         typename M::CF x = logits + (rows[q] - rb) * D;
-        const int tgt = q / n;
+        const int tgt = cls(q);
         float m = -INFINITY, at = 0.f;
         for (int c = 0; c < Ct; ++c) {
             const float a = useA ? A[q * Ct + c] : -sqdist(x, protos + c * D, D);
@@ -312,14 +339,14 @@ __device__ __forceinline__ void proto_set(const ProtoK& k, int set, int tid, lds
     if (useA) {
         for (int id = tid; id < Q * Ct; id += NT) {
             const int q = id / Ct, c = id - q * Ct;
-            A[id] = (expf(A[id] - lse[q]) - (c == q / n ? 1.f : 0.f)) * invQ;
+            A[id] = (expf(A[id] - lse[q]) - (own(q, c) ? 1.f : 0.f)) * invQ;
         }
         block_sync<M>();
     }
     for (int id = tid; id < Q * D; id += NT) {
         const int q = id / D, d = id - q * D;
         typename M::CF x = logits + (rows[q] - rb) * D;
-        const int tgt = q / n;
+        const int tgt = (RG && useA) ? 0 : cls(q);      // (only the branch without the A table needs it)
         float s = 0.f;
         for (int c = 0; c < Ct; ++c) {
             const float g = useA ? A[q * Ct + c] : (expf(-sqdist(x, protos + c * D, D) - lse[q]) - (c == tgt ? 1.f : 0.f)) * invQ;
@@ -338,29 +365,41 @@ __device__ __forceinline__ void proto_set(const ProtoK& k, int set, int tid, lds
         } else {
             for (int q = 0; q < Q; ++q) {
                 typename M::CF x = logits + (rows[q] - rb) * D;
-                const float g = (expf(-sqdist(x, protos + c * D, D) - lse[q]) - (c == q / n ? 1.f : 0.f)) * invQ;
+                const float g = (expf(-sqdist(x, protos + c * D, D) - lse[q]) - (own(q, c) ? 1.f : 0.f)) * invQ;
                 s += g * 2.f * (x[d] - pd);
             }
         }
         if (k.mode == 0) {
+            if constexpr (RG) {
+                const int r0 = coff[c], r1 = coff[c + 1];
 #pragma unroll 4
-            for (int r = 0; r < n; ++r) dlogits[(rows[c * n + r] - rb) * D + d] += s / (float)n;
+                for (int r = r0; r < r1; ++r) dlogits[(rows[r] - rb) * D + d] += s / (float)(r1 - r0);
+            } else {
+#pragma unroll 4
+                for (int r = 0; r < n; ++r) dlogits[(rows[c * n + r] - rb) * D + d] += s / (float)n;
+            }
         } else if (k.dprotos) {
             k.dprotos[(int64_t)set * k.Ct * D + id] = s;
         }
     }
 }
 
+template <bool RGK>      // RGK: the launch holds ragged sets (see ProtoK)
 __global__ __launch_bounds__(256) void k_proto(ProtoK k) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int set = blockIdx.x;
+    if constexpr (RGK) {
+        if (k.tab[set * 3 + 2] < 0) { proto_set<256, MemG, true>(k, set, threadIdx.x, (lds_float*)sm, k.logits, k.dlogits, k.rows + k.tab[set * 3]); return; }
+    }
     proto_set<256, MemG>(k, set, threadIdx.x, (lds_float*)sm, k.logits, k.dlogits, k.rows + (k.uniform ? set * k.Ct * k.n : k.tab[set * 3]));
 }
 
 // Head forward + prototypical loss (+ head backward and the SGD of the head's own parameters) of one set per block: the
 // five launches between the last GCN layer of a forward and the first weight gradient of its backward, in one.
 #define HL_THREADS 1024     // largest workgroup of k_head_loss (LDS sizing)
-template <int NT>
+// RGK: the launch holds ragged sets (ragged-task mode, see ProtoK): a kernel of its own, so that the kernel every other launch runs is the one it always ran
+// (with both variants in one kernel the balanced path measured 0.9 us per launch slower at the FirstMM shape)
+template <int NT, bool RGK = false>
 __global__ __launch_bounds__(NT) void k_head_loss(HeadK hk, float* logits, ProtoK pk, int do_bwd, float* dparams, int64_t dstride, float* dQ,
                                                           float* Gc, SgdK u, int stage, int proto_floats, int copy_out, unsigned long long* dbg) {
     extern __shared__ __attribute__((aligned(16))) float sm_generic[];
@@ -378,6 +417,7 @@ __global__ __launch_bounds__(NT) void k_head_loss(HeadK hk, float* logits, Proto
         if (tid < hk.C) pre_b = u.cur[(int64_t)set * u.cur_stride + hk.bl_off + tid];
     }
     // ... and so do the prototypes a query loss is scored against (mode 1; uniform class layout: the set's are at set * Ct * D)
+    const bool ragged = RGK && pk.tab[set * 3 + 2] < 0;
     const bool have_proto = stage && pk.mode == 1 && pk.uniform && pk.Ct * D <= NT;
     float proto_pre = 0.f;
     if (have_proto && tid < pk.Ct * D) proto_pre = pk.protos_in[(int64_t)set * pk.Ct * D + tid];
@@ -387,7 +427,8 @@ __global__ __launch_bounds__(NT) void k_head_loss(HeadK hk, float* logits, Proto
         for (int s = s0 + (tid >> 6); s < s1; s += NT / 64) head_fwd_sub<MemG>(hk, s, tid & 63, logits, nullptr, 0, nullptr, 0);
         __syncthreads();          // workgroup-scope fence: the logits / zeros written above are visible to the whole block
         HL_STAMP(3);
-        proto_set<NT, MemG>(pk, set, tid, sm, logits, pk.dlogits, pk.rows + (pk.uniform ? set * pk.Ct * pk.n : pk.tab[set * 3]));
+        if constexpr (RGK) { if (ragged) proto_set<NT, MemG, true>(pk, set, tid, sm, logits, pk.dlogits, pk.rows + pk.tab[set * 3]); }
+        if (!ragged) proto_set<NT, MemG>(pk, set, tid, sm, logits, pk.dlogits, pk.rows + (pk.uniform ? set * pk.Ct * pk.n : pk.tab[set * 3]));
         HL_STAMP(4);
         if (!do_bwd) return;
         __syncthreads();
@@ -402,13 +443,14 @@ __global__ __launch_bounds__(NT) void k_head_loss(HeadK hk, float* logits, Proto
     lds_float* lg_s = wl_s + hk.C * hk.hc + hk.C;                           // [S, D] logits
     lds_float* dl_s = lg_s + S * D;                                         // [S, D] dlogits
     lds_int* crow = (lds_int*)(dl_s + S * D);                               // [S * nc] row of every centre
-    lds_int* rows_l = crow + S * hk.nc;                                     // [Ct * n] the set's class rows (subgraph ids)
+    lds_int* rows_l = crow + S * hk.nc;                                     // [Ct * n] the set's class rows (subgraph ids); ragged set: [class starts | class rows]
     const float* P = hk.params + (int64_t)set * hk.pstride;
     const int nq = S * hk.nc;
     // first round trip, everything that needs no other load: centre rows (two dependent loads each), class rows, head weights
     for (int q = tid; q < nq; q += NT) crow[q] = (int)centre_row(hk, s0 + q / hk.nc, q % hk.nc);
     {
-        const int off = pk.uniform ? set * pk.Ct * pk.n : pk.tab[set * 3], Qs = pk.uniform ? pk.Ct * pk.n : pk.tab[set * 3 + 1] * pk.tab[set * 3 + 2];
+        const int off = pk.uniform ? set * pk.Ct * pk.n : pk.tab[set * 3];
+        const int Qs = pk.uniform ? pk.Ct * pk.n : (ragged ? pk.tab[set * 3 + 1] + 1 - pk.tab[set * 3 + 2] : pk.tab[set * 3 + 1] * pk.tab[set * 3 + 2]);
         for (int q = tid; q < Qs; q += NT) rows_l[q] = pk.rows[off + q];
     }
     for (int id = tid; id < hk.C * hk.hc; id += NT) wl_s[id] = P[hk.wl_off + id];
@@ -455,7 +497,8 @@ __global__ __launch_bounds__(NT) void k_head_loss(HeadK hk, float* logits, Proto
     HL_STAMP(3);
     ProtoK pl = pk;
     pl.row_base = s0;                                   // the LDS copies hold the set's subgraphs only
-    proto_set<NT, MemL>(pl, set, tid, sm, lg_s, dl, rows_l, have_proto, proto_pre);
+    if constexpr (RGK) { if (ragged) proto_set<NT, MemL, true>(pl, set, tid, sm, lg_s, dl, rows_l); }
+    if (!ragged) proto_set<NT, MemL>(pl, set, tid, sm, lg_s, dl, rows_l, have_proto, proto_pre);
     HL_STAMP(4);
     if (copy_out) {  // the global copies (the public gm_proto_loss_* shape; nobody inside gm_meta_step reads them): logits always, dlogits when requested
         block_sync<MemL>();
@@ -1211,13 +1254,75 @@ extern "C" int gm_gcn_backward(const gm_batch_t* b, const gm_model_t* m, const f
 // own class layout -- the reference calls proto_loss_* once per task (meta.py:118-157), so a Shared dataset whose graphs
 // carry different label sets, or evaluation tasks of different shapes, are fine.
 struct ClassTables {
-    std::vector<int32_t> rows;          // concatenated per set: [Ct_t][n_t] subgraph ids
-    std::vector<int32_t> tab;           // [sets*3]: offset into rows, Ct_t, n_t
-    int Ct = 0, n = 0;                  // maxima over the sets (LDS sizing, prototype stride)
+    std::vector<int32_t> rows;          // concatenated per set: [Ct_t][n_t] subgraph ids; a ragged set: [class starts (Ct_t + 1) | class rows]
+    std::vector<int32_t> tab;           // [sets*3]: offset into rows, Ct_t, n_t; a ragged set: -(scored rows) in place of n_t
+    int Ct = 0, n = 0;                  // maxima over the sets (LDS sizing, prototype stride); n: over the balanced sets
     bool uniform = false;               // every set: Ct classes x n rows, stored at set * Ct * n
+    int qmax = 0;                       // largest scored-row count of a ragged set; 0 = every set is balanced.  Else n is rounded up so that Ct * n >= qmax
+    std::vector<int32_t> labels;        // ragged mode: the sorted class labels of every set, concatenated (tab[3t + 1] each)
 };
-static int class_tables(const gm_batch* b, const int32_t* y, int limit, ClassTables& ct) {
-    ct.rows.clear(); ct.tab.assign((size_t)b->sets * 3, 0); ct.Ct = 0; ct.n = 0;
+
+// Ragged-task mode (gm_set_ragged_classes, include/gmeta_hip.h): per calling thread, like gm_last_error and the profile counters
+static thread_local int g_ragged = 0;
+extern "C" void gm_set_ragged_classes(int32_t on) { g_ragged = on ? 1 : 0; }
+extern "C" int32_t gm_get_ragged_classes(void) { return g_ragged; }
+
+// Class tables in ragged-task mode.  support == NULL: the classes of a set are its own sorted labels, each with its first min(limit, count) rows
+// (limit = 0: all).  support != NULL (the query side of a task): the classes are the support set's, a class may have no rows, and a label outside
+// them is an error.  A set whose classes all score the same number of rows gets the balanced table entry -- and with it the balanced code path.
+static int class_tables_ragged(const gm_batch* b, const int32_t* y, int limit, const ClassTables* support, ClassTables& ct) {
+    ct.rows.clear(); ct.labels.clear(); ct.tab.assign((size_t)b->sets * 3, 0); ct.Ct = 0; ct.n = 0; ct.qmax = 0;
+    size_t lab_off = 0;
+    for (int t = 0; t < b->sets; ++t) {
+        std::map<int32_t, std::vector<int32_t>> by;
+        if (support) {
+            const int nc = support->tab[t * 3 + 1];
+            for (int c = 0; c < nc; ++c) by[support->labels[lab_off + c]];
+            lab_off += nc;
+            GM_REQUIRE(b->h_set_sub_off[t + 1] > b->h_set_sub_off[t], GM_EINVAL, "proto loss: task %d has no query rows", t);
+            for (int s = b->h_set_sub_off[t]; s < b->h_set_sub_off[t + 1]; ++s) {
+                auto it = by.find(y[s]);
+                GM_REQUIRE(it != by.end(), GM_EINVAL, "proto loss: task %d has a query row of label %d, which is not among its support classes", t, y[s]);
+                it->second.push_back(s);
+            }
+        } else {
+            for (int s = b->h_set_sub_off[t]; s < b->h_set_sub_off[t + 1]; ++s) by[y[s]].push_back(s);
+            GM_REQUIRE(!by.empty(), GM_EINVAL, "proto loss: set %d is empty", t);
+        }
+        const int nc = (int)by.size();
+        GM_REQUIRE(nc <= 256, GM_ERANGE, "proto loss: set %d has %d classes, outside the kernel's range (256)", t, nc);
+        int64_t q = 0; int first = -1; bool balanced = true;
+        for (auto& kv : by) {
+            const int c = limit > 0 ? std::min(limit, (int)kv.second.size()) : (int)kv.second.size();
+            kv.second.resize(c);
+            if (first < 0) first = c;
+            balanced = balanced && c == first;
+            q += c;
+            ct.labels.push_back(kv.first);
+        }
+        GM_REQUIRE(q <= 8192, GM_ERANGE, "proto loss: set %d scores %lld rows, outside the kernel's range (8192)", t, (long long)q);
+        ct.tab[t * 3] = (int32_t)ct.rows.size(); ct.tab[t * 3 + 1] = nc;
+        ct.Ct = std::max(ct.Ct, nc);
+        if (balanced) {
+            ct.tab[t * 3 + 2] = first; ct.n = std::max(ct.n, first);
+        } else {
+            ct.tab[t * 3 + 2] = -(int32_t)q; ct.qmax = std::max(ct.qmax, (int)q);
+            int32_t at = 0;
+            for (auto& kv : by) { ct.rows.push_back(at); at += (int32_t)kv.second.size(); }
+            ct.rows.push_back(at);
+        }
+        for (auto& kv : by) ct.rows.insert(ct.rows.end(), kv.second.begin(), kv.second.end());
+    }
+    GM_REQUIRE((int64_t)ct.Ct * ct.n <= 8192, GM_ERANGE, "proto loss: %d classes x %d rows per set is outside the kernel's range", ct.Ct, ct.n);
+    ct.uniform = ct.qmax == 0;
+    for (int t = 0; t < b->sets; ++t) ct.uniform = ct.uniform && ct.tab[t * 3] == t * ct.Ct * ct.n && ct.tab[t * 3 + 1] == ct.Ct && ct.tab[t * 3 + 2] == ct.n;
+    if (ct.qmax) ct.n = std::max(ct.n, (ct.qmax + ct.Ct - 1) / ct.Ct);      // the kernels carve lse / A for Ct * n rows
+    return GM_OK;
+}
+
+static int class_tables(const gm_batch* b, const int32_t* y, int limit, ClassTables& ct, const ClassTables* support = nullptr) {
+    if (g_ragged) return class_tables_ragged(b, y, limit, support, ct);
+    ct.rows.clear(); ct.tab.assign((size_t)b->sets * 3, 0); ct.Ct = 0; ct.n = 0; ct.qmax = 0;
     for (int t = 0; t < b->sets; ++t) {
         std::map<int32_t, std::vector<int32_t>> by;
         for (int s = b->h_set_sub_off[t]; s < b->h_set_sub_off[t + 1]; ++s) by[y[s]].push_back(s);
@@ -1247,9 +1352,11 @@ static size_t proto_lds(int Ct, int n, int D, int nt = 256) {
     return sizeof(float) * ((size_t)Ct * D + (size_t)Ct * n + 2 * (size_t)nt + (a <= PROTO_A_MAX ? a : 0));
 }
 
-static int launch_proto(const gm_batch* b, ProtoK k, hipStream_t st) {
-    GM_TRY(gm_func_full_lds((const void*)k_proto));
-    hipLaunchKernelGGL(k_proto, dim3(b->sets), dim3(256), proto_lds(k.Ct, k.n, k.D), st, k);
+static int launch_proto_ragged(const gm_batch* b, const ProtoK& k, hipStream_t st);
+static int launch_proto(const gm_batch* b, ProtoK k, bool ragged, hipStream_t st) {
+    if (ragged) return launch_proto_ragged(b, k, st);
+    GM_TRY(gm_func_full_lds((const void*)k_proto<false>));
+    hipLaunchKernelGGL(k_proto<false>, dim3(b->sets), dim3(256), proto_lds(k.Ct, k.n, k.D), st, k);
     GM_HIP(hipGetLastError());
     return GM_OK;
 }
@@ -1280,7 +1387,7 @@ extern "C" int gm_proto_loss_spt(const gm_batch_t* b, const float* logits, int32
     if (dlogits && hipMemsetAsync(dlogits, 0, sizeof(float) * b->subs * n_out, st) != hipSuccess) { gm_set_error("proto_loss_spt: memset failed"); rc = GM_EHIP; }
     if (rc == GM_OK) {
         ProtoK k{logits, n_out, d_rows, ct.Ct, ct.n, 0, nullptr, protos, loss, acc, 1, 0, dlogits, nullptr, 0, d_rows + ct.rows.size()};
-        rc = launch_proto(b, k, st);
+        rc = launch_proto(b, k, ct.qmax != 0, st);
     }
     if (hipStreamSynchronize(st) != hipSuccess && rc == GM_OK) { gm_set_error("proto_loss_spt: kernel failed"); rc = GM_EHIP; }
     gm_dev_free(d_rows, st);
@@ -1295,15 +1402,18 @@ extern "C" int gm_proto_loss_qry(const gm_batch_t* b, const float* logits, int32
     GM_TRY(class_tables(b, y, 0, ct));
     // prototypes are indexed by sorted-class position with stride c_task: EVERY set must carry exactly c_task query classes (a set with
     // fewer would be scored against another class's prototype); gm_meta_step checks support vs query class counts per task itself
+    // (ragged-task mode: a set may carry fewer -- its classes are its own sorted labels, scored against its first prototypes)
     for (int t = 0; t < b->sets; ++t)
-        GM_REQUIRE(ct.tab[t * 3 + 1] == c_task, GM_EINVAL, "proto_loss_qry: set %d has %d query classes but the prototypes hold %d per set", t, ct.tab[t * 3 + 1], c_task);
+        GM_REQUIRE(g_ragged ? ct.tab[t * 3 + 1] <= c_task : ct.tab[t * 3 + 1] == c_task, GM_EINVAL,
+                   "proto_loss_qry: set %d has %d query classes but the prototypes hold %d per set", t, ct.tab[t * 3 + 1], c_task);
+    GM_REQUIRE(c_task <= 256 && (int64_t)c_task * ct.n <= 16384, GM_ERANGE, "proto_loss_qry: c_task=%d with %d rows per class is outside the kernel's range", c_task, ct.n);
     int32_t* d_rows = nullptr;
     GM_TRY(upload_tables(ct, &d_rows, st));
     int rc = GM_OK;
     if (dlogits && hipMemsetAsync(dlogits, 0, sizeof(float) * b->subs * n_out, st) != hipSuccess) { gm_set_error("proto_loss_qry: memset failed"); rc = GM_EHIP; }
     if (rc == GM_OK) {
-        ProtoK k{logits, n_out, d_rows, ct.Ct, ct.n, 1, protos, nullptr, loss, acc, 1, 0, dlogits, dprotos, 0, d_rows + ct.rows.size()};
-        rc = launch_proto(b, k, st);
+        ProtoK k{logits, n_out, d_rows, c_task, ct.n, 1, protos, nullptr, loss, acc, 1, 0, dlogits, dprotos, 0, d_rows + ct.rows.size()};      // (prototype stride c_task)
+        rc = launch_proto(b, k, ct.qmax != 0, st);
     }
     if (hipStreamSynchronize(st) != hipSuccess && rc == GM_OK) { gm_set_error("proto_loss_qry: kernel failed"); rc = GM_EHIP; }
     gm_dev_free(d_rows, st);
@@ -1324,11 +1434,13 @@ extern "C" int gm_head_loss_debug(int32_t enable, unsigned long long* out) {
 static unsigned long long* const g_head_dbg = nullptr;      // the product library carries no probe state
 #endif
 
+static int launch_head_loss_ragged(int nt, int sets, size_t lds, hipStream_t st, const HeadK& hk, float* logits, const ProtoK& pk, int bwd, float* dparams, int64_t dstride,
+                                   float* dQ, float* Gc, const SgdK& sg, int stage_h, int proto_floats);
 // Head forward + loss (+ head backward) in one launch (k_head_loss) after a gcn_forward(..., skip_head = 1).  With
 // bwd != 0 the matching gcn_backward(..., skip_head = 1) continues from dQ_L / the compact G2 written here; c.sgd (if
 // set) makes the head's own parameters take their SGD step in the same launch.
 static int head_loss(GcnCtx& c, const float* params, int64_t pstride, float* logits, const ProtoK& pk, int bwd, float* dparams, int64_t dstride, int sparse,
-                     hipStream_t st) {
+                     hipStream_t st, bool ragged = false) {      // ragged: the class tables hold ragged sets (see ProtoK)
     const gm_batch* b = c.b; const gm_layout& L = c.L;
     float* dQ = nullptr; float* Gc = nullptr;
     if (bwd) {
@@ -1345,7 +1457,7 @@ static int head_loss(GcnCtx& c, const float* params, int64_t pstride, float* log
     int max_subs = 0;
     for (int t = 0; t < b->sets; ++t) max_subs = std::max(max_subs, b->h_set_sub_off[t + 1] - b->h_set_sub_off[t]);
     const size_t hs_bytes = sizeof(float) * ((size_t)max_subs * b->centres * L.dims[L.n_gcn] + (size_t)L.n_out * (L.hc + 1) + 2 * (size_t)max_subs * L.n_out +
-                                             (size_t)max_subs * b->centres + (size_t)pk.Ct * pk.n) + 16;      // + the centre-row scratch + the class rows
+                                             (size_t)max_subs * b->centres + (size_t)pk.Ct * pk.n + (ragged ? (size_t)pk.Ct + 1 : 0)) + 16;      // + the centre-row scratch + the class rows (a ragged set's follow its class starts)
     const int stage_on = gm_knob().head_stage;
     const int stage_h = stage_on && proto_bytes + hs_bytes <= 150 * 1024;
     const size_t lds = proto_bytes + (stage_h ? hs_bytes : 0);
@@ -1356,13 +1468,15 @@ static int head_loss(GcnCtx& c, const float* params, int64_t pstride, float* log
     if (nt != 256 && nt != 512) nt = 1024;
     const SgdK sg = bwd ? c.sgd : SgdK{nullptr, 0, nullptr, 0, 0.f};
     gm_prof_begin(GM_PROF_HEAD, st, b->subs);
-    if (nt == 256) { GM_TRY(gm_func_full_lds((const void*)k_head_loss<256>)); hipLaunchKernelGGL(k_head_loss<256>, dim3(b->sets), dim3(256), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, (int)(proto_bytes / sizeof(float)), 0, g_head_dbg); }
-    else if (nt == 512) { GM_TRY(gm_func_full_lds((const void*)k_head_loss<512>)); hipLaunchKernelGGL(k_head_loss<512>, dim3(b->sets), dim3(512), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, (int)(proto_bytes / sizeof(float)), 0, g_head_dbg); }
-    else { GM_TRY(gm_func_full_lds((const void*)k_head_loss<1024>)); hipLaunchKernelGGL(k_head_loss<1024>, dim3(b->sets), dim3(1024), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, (int)(proto_bytes / sizeof(float)), 0, g_head_dbg); }
+    if (!ragged) {      // (first: the kernels every launch without ragged sets runs stay where they were in the code object)
+        if (nt == 256) { GM_TRY(gm_func_full_lds((const void*)k_head_loss<256>)); hipLaunchKernelGGL(k_head_loss<256>, dim3(b->sets), dim3(256), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, (int)(proto_bytes / sizeof(float)), 0, g_head_dbg); }
+        else if (nt == 512) { GM_TRY(gm_func_full_lds((const void*)k_head_loss<512>)); hipLaunchKernelGGL(k_head_loss<512>, dim3(b->sets), dim3(512), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, (int)(proto_bytes / sizeof(float)), 0, g_head_dbg); }
+        else { GM_TRY(gm_func_full_lds((const void*)k_head_loss<1024>)); hipLaunchKernelGGL(k_head_loss<1024>, dim3(b->sets), dim3(1024), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, (int)(proto_bytes / sizeof(float)), 0, g_head_dbg); }
+    } else GM_TRY(launch_head_loss_ragged(nt, b->sets, lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, (int)(proto_bytes / sizeof(float))));
 #ifdef GM_PROBES
     {   // tools/head_loss_probe.py: the same launch again -- it is idempotent -- to see what a warm instruction cache / warm L2 is worth
         static const int twice = getenv("GM_HEAD_TWICE") ? atoi(getenv("GM_HEAD_TWICE")) : 0;
-        if (twice && nt != 256 && nt != 512)
+        if (twice && nt != 256 && nt != 512 && !ragged)
             hipLaunchKernelGGL(k_head_loss<1024>, dim3(b->sets), dim3(1024), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, (int)(proto_bytes / sizeof(float)), 0, g_head_dbg);
     }
 #endif
@@ -1370,6 +1484,41 @@ static int head_loss(GcnCtx& c, const float* params, int64_t pstride, float* log
     gm_prof_end(GM_PROF_HEAD, st);
     if (bwd && dQ && hk.dq_amax) c.dqv = true;
     return GM_OK;
+}
+
+// ================================================================================ ragged-task mode: kernels of launches that hold ragged sets
+// Instantiated and defined HERE, behind everything a launch without ragged sets runs: those kernels keep the place in the code object they had before the mode existed
+// (k_head_loss is pure latency; with the ragged instantiations emitted ahead of it, the same instructions measured 0.1-0.3 us per launch slower at the FirstMM shape).
+static int launch_proto_ragged(const gm_batch* b, const ProtoK& k, hipStream_t st) {
+    GM_TRY(gm_func_full_lds((const void*)k_proto<true>));
+    hipLaunchKernelGGL(k_proto<true>, dim3(b->sets), dim3(256), proto_lds(k.Ct, k.n, k.D), st, k);
+    GM_HIP(hipGetLastError());
+    return GM_OK;
+}
+static int launch_head_loss_ragged(int nt, int sets, size_t lds, hipStream_t st, const HeadK& hk, float* logits, const ProtoK& pk, int bwd, float* dparams, int64_t dstride,
+                                   float* dQ, float* Gc, const SgdK& sg, int stage_h, int proto_floats) {
+    if (nt == 256) { GM_TRY(gm_func_full_lds((const void*)k_head_loss<256, true>)); hipLaunchKernelGGL((k_head_loss<256, true>), dim3(sets), dim3(256), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, proto_floats, 0, g_head_dbg); }
+    else if (nt == 512) { GM_TRY(gm_func_full_lds((const void*)k_head_loss<512, true>)); hipLaunchKernelGGL((k_head_loss<512, true>), dim3(sets), dim3(512), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, proto_floats, 0, g_head_dbg); }
+    else { GM_TRY(gm_func_full_lds((const void*)k_head_loss<1024, true>)); hipLaunchKernelGGL((k_head_loss<1024, true>), dim3(sets), dim3(1024), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, proto_floats, 0, g_head_dbg); }
+    return GM_OK;
+}
+// k_protos_to_dlogits for a launch with ragged sets ([class starts | class rows], see ProtoK): prototype_c = mean of the class's own row count
+__global__ void k_protos_to_dlogits_ragged(const float* dprotos, const int32_t* rows, const int32_t* tab, int CtMax, int D, float* dlogits) {
+    const int set = blockIdx.x, Ct = tab[set * 3 + 1], n = tab[set * 3 + 2];
+    rows += tab[set * 3];
+    if (n < 0) {
+        const int32_t* coff = rows;
+        rows += Ct + 1;
+        for (int id = threadIdx.x; id < -n * D; id += blockDim.x) {
+            const int q = id / D, d = id - q * D, c = ragged_class(coff, Ct, q);
+            dlogits[(int64_t)rows[q] * D + d] = dprotos[((int64_t)set * CtMax + c) * D + d] / (float)(coff[c + 1] - coff[c]);
+        }
+        return;
+    }
+    for (int id = threadIdx.x; id < Ct * n * D; id += blockDim.x) {
+        const int q = id / D, d = id - q * D, c = q / n;
+        dlogits[(int64_t)rows[q] * D + d] = dprotos[((int64_t)set * CtMax + c) * D + d] / (float)n;
+    }
 }
 
 // ================================================================================ the fused meta-step
@@ -1465,6 +1614,8 @@ struct MetaPlan {
     unsigned* viol;                               // the step's violation word (gm_bound.h), zeroed with the bound slots; NULL without two-piece kernels
     int Ct, ns, nq;
     int uni_s = 0, uni_q = 0;                     // class layouts uniform over the tasks (ProtoK::uniform)
+    int qmax_s = 0, qmax_q = 0;                   // ragged-task mode: largest scored-row count of a ragged set (0: none, the usual kernels)
+    int64_t cap_s, cap_q;                         // ints held by rows_s / rows_q
     unsigned* bound_ws; int64_t bound_words;      // gm_bound.h slots of this step ([S passes | Q passes | weights]), zeroed by ONE memset; NULL: three-piece kernels
 };
 
@@ -1511,9 +1662,12 @@ static int meta_plan(MetaPlan& p, const gm_batch* spt, const gm_batch* qry, cons
     p.ls = cv.take<float>((int64_t)p.T * K1); p.as_ = cv.take<float>((int64_t)p.T * K1);
     p.lq = cv.take<float>((int64_t)p.T * K1); p.aq = cv.take<float>((int64_t)p.T * K1);
     {   // rows of a set never exceed its subgraphs: [rows_s (spt->subs) | rows_q (qry->subs) | tab_s (3T) | tab_q (3T)]
-        int32_t* blk = cv.take<int32_t>((int64_t)spt->subs + qry->subs + 8 * (int64_t)p.T);
-        p.rows_s = blk; p.rows_q = blk ? blk + spt->subs : nullptr;
-        p.tab_s = blk ? p.rows_q + qry->subs : nullptr; p.tab_q = blk ? p.tab_s + 3 * p.T : nullptr;
+        // ragged-task mode: a ragged set's rows follow its class starts, one more than it has classes -- on either side at most the support set's subgraphs + 1
+        const int64_t starts = g_ragged ? (int64_t)spt->subs + p.T : 0;
+        p.cap_s = spt->subs + starts; p.cap_q = qry->subs + starts;
+        int32_t* blk = cv.take<int32_t>(p.cap_s + p.cap_q + 8 * (int64_t)p.T);
+        p.rows_s = blk; p.rows_q = blk ? blk + p.cap_s : nullptr;
+        p.tab_s = blk ? p.rows_q + p.cap_q : nullptr; p.tab_q = blk ? p.tab_s + 3 * p.T : nullptr;
         p.featb_s = blk ? reinterpret_cast<unsigned*>(p.tab_q + 3 * p.T) : nullptr; p.featb_q = blk ? p.featb_s + p.T : nullptr;
     }
     // Two query streams (GM_QUERY_STREAMS=2, off by default): evaluations k and k + 1 are independent of each other (each needs only fw_k and the
@@ -1581,7 +1735,7 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
     gm_phase_timer tm("meta_step");
     ClassTables cs, cq;
     GM_TRY(class_tables(spt, y_spt, hp->k_spt, cs));
-    GM_TRY(class_tables(qry, y_qry, 0, cq));
+    GM_TRY(class_tables(qry, y_qry, 0, cq, &cs));      // (ragged-task mode: the query rows are filed under the support classes, which their labels must be among)
     for (int t = 0; t < spt->sets; ++t)
         GM_REQUIRE(cs.tab[t * 3 + 1] == cq.tab[t * 3 + 1], GM_EINVAL, "meta_step: task %d has %d support classes but %d query classes", t, cs.tab[t * 3 + 1], cq.tab[t * 3 + 1]);
     const int Ct = cs.Ct, ns = cs.n, nq = cq.n;
@@ -1593,6 +1747,8 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
     GM_TRY(meta_plan(p, spt, qry, &mp, hp, ws, ws_bytes, Ct, ns, nq, nullptr));
     const gm_layout& L = p.L; const int T = p.T, C = L.n_out, K1 = K + 1; const int64_t Pp = p.Pp;
     p.uni_s = cs.uniform ? 1 : 0; p.uni_q = cq.uniform ? 1 : 0;
+    p.qmax_s = cs.qmax; p.qmax_q = cq.qmax;
+    GM_REQUIRE((int64_t)cs.rows.size() <= p.cap_s && (int64_t)cq.rows.size() <= p.cap_q, GM_EINVAL, "meta_step: class tables outgrew the workspace plan");
     p.S.pd = p.Q.pd = p.Q2.pd = p.pd.base ? &p.pd : nullptr;
     if (shift) {
         hipLaunchKernelGGL(k_pad_params, dim3((int)std::min<int64_t>(512, (L.P + 255) / 256)), dim3(256), 0, st, theta, Lu.P, cut, shift, p.theta_p);
@@ -1600,16 +1756,16 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
         theta = p.theta_p;
     }
     {   // class tables -> pinned staging -> ONE asynchronous copy (no host synchronisation in the meta-step)
-        const size_t n_tab = (size_t)spt->subs + qry->subs + 8 * (size_t)T;
+        const size_t n_rows = (size_t)(p.cap_s + p.cap_q), n_tab = n_rows + 8 * (size_t)T;
         void* h = nullptr; int slot = 0;
         StageRing& ring = stage_ring();
         GM_TRY(ring.acquire(4 * n_tab, &h, &slot));
         int32_t* hp32 = (int32_t*)h;
         memset(hp32, 0, 4 * n_tab);
         memcpy(hp32, cs.rows.data(), 4 * cs.rows.size());
-        memcpy(hp32 + spt->subs, cq.rows.data(), 4 * cq.rows.size());
-        memcpy(hp32 + spt->subs + qry->subs, cs.tab.data(), 4 * cs.tab.size());
-        memcpy(hp32 + spt->subs + qry->subs + 3 * (size_t)T, cq.tab.data(), 4 * cq.tab.size());
+        memcpy(hp32 + p.cap_s, cq.rows.data(), 4 * cq.rows.size());
+        memcpy(hp32 + n_rows, cs.tab.data(), 4 * cs.tab.size());
+        memcpy(hp32 + n_rows + 3 * (size_t)T, cq.tab.data(), 4 * cq.tab.size());
         if (p.bound_ws) {
             // two-piece kernels: the layer-1 operand of task t is bounded by the largest feature of the graphs its subgraphs come from.  A step
             // that touches a LOOSE table (gm_store::h_feat_mean: largest entry more than 2^14 above the typical one, or not finite) runs
@@ -1618,7 +1774,7 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
             bool loose = false;
             int k = 0;
             for (const gm_batch* bb : {spt, qry}) {
-                float* fb = reinterpret_cast<float*>(hp32 + spt->subs + qry->subs + 6 * (size_t)T) + (size_t)(k++) * T;
+                float* fb = reinterpret_cast<float*>(hp32 + n_rows + 6 * (size_t)T) + (size_t)(k++) * T;
                 for (int t = 0; t < T; ++t) {
                     float mx = 0.f;
                     for (int sg = bb->h_set_sub_off[t]; sg < bb->h_set_sub_off[t + 1]; ++sg) {
@@ -1679,7 +1835,7 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
         GM_TRY(gcn_forward(p.S, w, wstride, p.logit_s, st, hoist, 1, (sparse && sparse_bwd_ok(p.L)) ? 0 : 2));
         p.S.sgd = SgdK{w, wstride, w_next, Pp, hp->update_lr};
         ProtoK pk{p.logit_s, C, p.rows_s, Ct, ns, 0, nullptr, protos(k), p.ls, p.as_, K1, k, p.dlog_s, nullptr, 0, p.tab_s, p.uni_s};
-        GM_TRY(head_loss(p.S, w, wstride, p.logit_s, pk, 1, p.g, Pp, sparse, st));
+        GM_TRY(head_loss(p.S, w, wstride, p.logit_s, pk, 1, p.g, Pp, sparse, st, p.qmax_s != 0));
         return GM_OK;
     };
     auto spt_step_bwd = [&](const float* w, int64_t wstride) -> int {
@@ -1700,7 +1856,7 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
     };
     auto qry_loss = [&](int j, const float* w, int64_t wstride, int col, int kproto, bool grad) -> int {
         ProtoK pk{q_log(j), C, p.rows_q, Ct, nq, 1, protos(kproto), nullptr, p.lq, p.aq, K1, col, grad ? p.dlog_q : nullptr, grad ? p.dprotos : nullptr, 0, p.tab_q, p.uni_q};
-        return head_loss(q_ctx(j), w, wstride, q_log(j), pk, grad ? 1 : 0, p.gq, Pp, sparse, q_str(j));
+        return head_loss(q_ctx(j), w, wstride, q_log(j), pk, grad ? 1 : 0, p.gq, Pp, sparse, q_str(j), p.qmax_q != 0);
     };
     // ---- support step 0 (meta.py:122-126) on st ; query evaluations 0 and 1 (meta.py:129-141) on sq.  Host enqueue order matters at the
     // start of a step (the GPU is idle and a launch costs the host ~5 us): the first query forward needs nothing but theta and is the head
@@ -1735,7 +1891,8 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
             GM_TRY(gcn_backward(q_ctx(j), fw(k + 1), Pp, p.dlog_q, p.gq, Pp, q_str(j), sparse, 1));
             wait(st, e_dp);
             GM_HIP(hipMemsetAsync(p.dlog_s, 0, sizeof(float) * spt->subs * C, st));
-            hipLaunchKernelGGL(k_protos_to_dlogits, dim3(T), dim3(256), 0, st, p.dprotos, p.rows_s, p.tab_s, Ct, C, p.dlog_s);
+            if (p.qmax_s) hipLaunchKernelGGL(k_protos_to_dlogits_ragged, dim3(T), dim3(256), 0, st, p.dprotos, p.rows_s, p.tab_s, Ct, C, p.dlog_s);
+            else hipLaunchKernelGGL(k_protos_to_dlogits, dim3(T), dim3(256), 0, st, p.dprotos, p.rows_s, p.tab_s, Ct, C, p.dlog_s);
             GM_TRY(gcn_backward(p.S, fw(k), Pp, p.dlog_s, p.gp, Pp, st, sparse));
             have_grad = true;
         }
@@ -1759,7 +1916,8 @@ struct AdaptPlan {
     GcnCtx S;
     PlaneDir pd;
     float *theta_p, *fw, *g, *logit_s, *dlog_s, *protos, *ls, *as_;
-    int32_t *rows_s, *tab_s;                  // class tables, one block [rows_s (spt->subs) | tab_s (3T)]
+    int32_t *rows_s, *tab_s;                  // class tables, one block [rows_s (cap_s) | tab_s (3T)]
+    int64_t cap_s;                            // spt->subs; ragged-task mode: + the class starts of ragged sets (at most spt->subs + T)
 };
 
 static int adapt_plan(AdaptPlan& p, const gm_batch* spt, const gm_model_t* m, const gm_hparams_t* hp, void* ws, int64_t ws_bytes, int64_t* need) {
@@ -1779,8 +1937,9 @@ static int adapt_plan(AdaptPlan& p, const gm_batch* spt, const gm_model_t* m, co
     p.logit_s = cv.take<float>((int64_t)spt->subs * C); p.dlog_s = cv.take<float>((int64_t)spt->subs * C);
     p.protos = cv.take<float>(p.proto_sz);                      // every step overwrites them: the last support step's are the result
     p.ls = cv.take<float>((int64_t)p.T * K1); p.as_ = cv.take<float>((int64_t)p.T * K1);
-    p.rows_s = cv.take<int32_t>((int64_t)spt->subs + 3 * (int64_t)p.T);
-    p.tab_s = p.rows_s ? p.rows_s + spt->subs : nullptr;
+    p.cap_s = spt->subs + (g_ragged ? (int64_t)spt->subs + p.T : 0);
+    p.rows_s = cv.take<int32_t>(p.cap_s + 3 * (int64_t)p.T);
+    p.tab_s = p.rows_s ? p.rows_s + p.cap_s : nullptr;
     gcn_carve(p.S, cv);
     plan_planes(p.pd, p.L, p.T, p.K, p.fw, p.TP, !p.S.cone, cv);
     if (need) *need = cv.used + 256;
@@ -1824,14 +1983,14 @@ extern "C" int gm_meta_adapt(const gm_batch_t* spt, const int32_t* y_spt, const 
         theta = p.theta_p;
     }
     {   // support class tables -> pinned staging -> one asynchronous copy
-        const size_t n_tab = (size_t)spt->subs + 3 * (size_t)T;
+        const size_t n_tab = (size_t)p.cap_s + 3 * (size_t)T;
         void* h = nullptr; int slot = 0;
         StageRing& ring = stage_ring();
         GM_TRY(ring.acquire(4 * n_tab, &h, &slot));
         int32_t* hp32 = (int32_t*)h;
         memset(hp32, 0, 4 * n_tab);
         memcpy(hp32, cs.rows.data(), 4 * cs.rows.size());
-        memcpy(hp32 + spt->subs, cs.tab.data(), 4 * cs.tab.size());
+        memcpy(hp32 + p.cap_s, cs.tab.data(), 4 * cs.tab.size());
         GM_HIP(hipMemcpyAsync(p.rows_s, h, 4 * n_tab, hipMemcpyHostToDevice, st));
         GM_TRY(ring.release_after(slot, st));
     }
@@ -1846,7 +2005,7 @@ extern "C" int gm_meta_adapt(const gm_batch_t* spt, const int32_t* y_spt, const 
         GM_TRY(gcn_forward(p.S, w, wstride, p.logit_s, st, hoist, 1, fwd_mode));
         if (bwd) p.S.sgd = SgdK{w, wstride, fw(k + 1), Pp, hp->update_lr};
         ProtoK pk{p.logit_s, C, p.rows_s, Ct, ns, 0, nullptr, p.protos, p.ls, p.as_, K1, k, bwd ? p.dlog_s : nullptr, nullptr, 0, p.tab_s, cs.uniform ? 1 : 0};
-        GM_TRY(head_loss(p.S, w, wstride, p.logit_s, pk, bwd ? 1 : 0, p.g, Pp, sparse, st));
+        GM_TRY(head_loss(p.S, w, wstride, p.logit_s, pk, bwd ? 1 : 0, p.g, Pp, sparse, st, cs.qmax != 0));
         if (bwd) {
             GM_TRY(gcn_backward(p.S, w, wstride, p.dlog_s, p.g, Pp, st, sparse, 1));
             p.S.sgd = SgdK{nullptr, 0, nullptr, 0, 0.f};

@@ -42,6 +42,7 @@ class Meta(nn.Module):
         self.serialize = int(getattr(args, 'serialize', 0))     # 1: one stream (per-kernel timing)
         self.sparse_bwd = int(getattr(args, 'sparse_bwd', 0))   # 1: exact row-sparse backward (flagged schedule)
         self.cone = int(getattr(args, 'cone', 0))               # 1: receptive-field schedule, forward and backward (flagged)
+        self.ragged = int(getattr(args, 'ragged', 0))           # 1: ragged-task mode (include/gmeta_hip.h): classes may have unequal / short row counts
         self.last_stats = {}
         self.fused_adam_kernel = True                           # False: gm_meta_finish + torch's own fused Adam launches (the rule is the same)
         self._ws = None
@@ -230,20 +231,24 @@ class Meta(nn.Module):
         # objects are recycled; a dead or different partner recomputes) -- two FFI calls (one of them a full planning pass) less on the host
         # path between the read-back of one step and the first launch of the next
         key = (S.rows, Q.rows, S.subs, Q.subs, S.sets, Q.sets, P, int(K), int(need_grad), int(self.hoist_z1), int(self.serialize), int(self.sparse_bwd),
-               int(self.cone), int(lib.gm_get_gemm_mode()), int(lib.gm_get_split_pieces()), int(lib.gm_tuning_epoch()))
-        sizes = getattr(S, '_meta_sizes', None)
-        if sizes is None or sizes[0] != key or sizes[1]() is not Q:
-            n_out = int(lib.gm_meta_out_floats(S.handle, C.byref(model), C.byref(hp)))
-            ws_bytes = int(lib.gm_meta_ws_bytes(S.handle, Q.handle, C.byref(model), C.byref(hp)))
-            if ws_bytes < 0 or n_out < 0:
-                _lib.check(-1, 'gm_meta_ws_bytes')
-            S._meta_sizes = (key, weakref.ref(Q), n_out, ws_bytes)
-        else:
-            n_out, ws_bytes = sizes[2], sizes[3]
-        ws = self._workspace(ws_bytes, dev)
-        out = torch.empty(n_out, dtype=torch.float32, device=dev)
-        _lib.check(lib.gm_meta_step(S.handle, Q.handle, _lib.ptr(ys), _lib.ptr(yq), C.byref(model), C.byref(hp), _lib.ptr(theta),
-                                    _lib.ptr(out), out.numel(), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), 'gm_meta_step')
+               int(self.cone), int(lib.gm_get_gemm_mode()), int(lib.gm_get_split_pieces()), int(lib.gm_tuning_epoch()), int(self.ragged))
+        was = _set_ragged(lib, self.ragged)                   # the calling thread's switch: the sizes and the step below depend on it
+        try:
+            sizes = getattr(S, '_meta_sizes', None)
+            if sizes is None or sizes[0] != key or sizes[1]() is not Q:
+                n_out = int(lib.gm_meta_out_floats(S.handle, C.byref(model), C.byref(hp)))
+                ws_bytes = int(lib.gm_meta_ws_bytes(S.handle, Q.handle, C.byref(model), C.byref(hp)))
+                if ws_bytes < 0 or n_out < 0:
+                    _lib.check(-1, 'gm_meta_ws_bytes')
+                S._meta_sizes = (key, weakref.ref(Q), n_out, ws_bytes)
+            else:
+                n_out, ws_bytes = sizes[2], sizes[3]
+            ws = self._workspace(ws_bytes, dev)
+            out = torch.empty(n_out, dtype=torch.float32, device=dev)
+            _lib.check(lib.gm_meta_step(S.handle, Q.handle, _lib.ptr(ys), _lib.ptr(yq), C.byref(model), C.byref(hp), _lib.ptr(theta),
+                                        _lib.ptr(out), out.numel(), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), 'gm_meta_step')
+        finally:
+            _set_ragged(lib, was)
         self._keep = (S, Q)             # keep concatenated batches alive until the stream has consumed them
         return out, P, T
 
@@ -401,19 +406,31 @@ class Meta(nn.Module):
         model = self.net.model
         P = int(lib.gm_model_param_count(C.byref(model)))
         hp = _lib.HParams(float(self.update_lr), K, int(self.k_spt), 0, int(self.hoist_z1), int(self.serialize), int(self.sparse_bwd), int(self.cone))
-        ws_bytes = int(lib.gm_adapt_ws_bytes(S.handle, C.byref(model), C.byref(hp)))
-        if ws_bytes < 0:
-            _lib.check(-1, 'gm_adapt_ws_bytes')
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        fw = torch.empty(S.sets, P, dtype=torch.float32, device=dev)
-        protos = torch.empty(S.sets, c_task, model.n_out, dtype=torch.float32, device=dev)
-        _lib.check(lib.gm_meta_adapt(S.handle, _lib.ptr(ys), C.byref(model), C.byref(hp), _lib.ptr(theta), _lib.ptr(fw), P, _lib.ptr(protos), int(c_task),
-                                     _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), 'gm_meta_adapt')
+        was = _set_ragged(lib, self.ragged)
+        try:
+            ws_bytes = int(lib.gm_adapt_ws_bytes(S.handle, C.byref(model), C.byref(hp)))
+            if ws_bytes < 0:
+                _lib.check(-1, 'gm_adapt_ws_bytes')
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            fw = torch.empty(S.sets, P, dtype=torch.float32, device=dev)
+            protos = torch.empty(S.sets, c_task, model.n_out, dtype=torch.float32, device=dev)
+            _lib.check(lib.gm_meta_adapt(S.handle, _lib.ptr(ys), C.byref(model), C.byref(hp), _lib.ptr(theta), _lib.ptr(fw), P, _lib.ptr(protos), int(c_task),
+                                         _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), 'gm_meta_adapt')
+        finally:
+            _set_ragged(lib, was)
         return Adapted(self, S.store, fw, protos, classes, K)
 
     def predict(self, x_spt, y_spt, x_qry, K=None, tasks=None, logits=False):
         """adapt(x_spt, y_spt, K) followed by predict(x_qry, tasks)."""
         return self.adapt(x_spt, y_spt, K).predict(x_qry, tasks, logits)
+
+
+def _set_ragged(lib, on):
+    """Set the calling thread's ragged-task switch (gm_set_ragged_classes); returns the value it had, for the caller's `finally`."""
+    was = int(lib.gm_get_ragged_classes())
+    if was != int(on):
+        lib.gm_set_ragged_classes(int(on))
+    return was
 
 
 def _labels(ys):

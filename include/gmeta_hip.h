@@ -211,11 +211,30 @@ int gm_dense_wgrad(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, 
  * y: HOST int32 [subs] labels.  Outputs (device): loss[sets], acc[sets], protos[sets, c_task, n_out]
  * (c_task = the LARGEST number of classes of any set; every set keeps its own class layout -- classes, rows per class --
  * like the per-task calls of meta.py:118-157; set t uses the first classes_t rows of its [c_task, n_out] block),
- * dlogits[subs, n_out] (may be NULL), dprotos[sets, c_task, n_out] (qry only, may be NULL). */
+ * dlogits[subs, n_out] (may be NULL), dprotos[sets, c_task, n_out] (qry only, may be NULL).
+ * Every class of a set must score the same number of rows, and hold at least n_support of them on the support side (GM_EINVAL otherwise:
+ * torch.stack at meta.py:42,65), unless the calling thread has switched on
+ *
+ * RAGGED-TASK MODE, gm_set_ragged_classes(1): off by default, per calling thread (like gm_last_error and the profile counters), honoured by
+ * gm_proto_loss_spt / _qry, gm_meta_step and gm_meta_adapt.  Per task t:
+ *   - classes C_t = the sorted unique SUPPORT labels; class c contributes its first min(n_support, count) support rows in batch order, n_c >= 1 of
+ *     them; prototype p_c = the mean of the head outputs of those rows;
+ *   - support loss / accuracy: over all sum_c n_c contributing rows, mean(-log_softmax(-|z - p|^2)[own class]) and the share of rows whose FIRST
+ *     maximum of the fp32 log-probabilities is their own class;
+ *   - query loss / accuracy: the same two means over ALL query rows of the task, each scored against the class its label has in C_t, rows visited
+ *     class by class in sorted class order and in batch order inside a class (the fp32 summation order).  A support class may have no query rows; a
+ *     query label outside C_t, or a task without query rows, is GM_EINVAL (the message names the task and the label);
+ *   - these are SAMPLE means (`.view(-1).mean()`, meta.py:51,76) -- on a balanced task the reference's numbers; there is no class-balanced weighting;
+ *   - backward: dL/dz of the query role is (softmax - onehot) / Q_t; the prototype role spreads dL/dp_c over the class's n_c support rows as / n_c;
+ *   - limits: at most 256 classes and at most 8192 scored rows per set, else GM_ERANGE.
+ * A set whose classes all score the same number of rows runs the same code as with the mode off, bit for bit.  The stand-alone gm_proto_loss_qry has
+ * no support labels: there a set's classes are its own sorted labels, at most c_task of them, scored against the set's first prototypes. */
 int gm_proto_loss_spt(const gm_batch_t* b, const float* logits, int32_t n_out, const int32_t* y, int32_t n_support,
                       float* loss, float* acc, float* protos, float* dlogits, void* stream);
 int gm_proto_loss_qry(const gm_batch_t* b, const float* logits, int32_t n_out, const int32_t* y, const float* protos,
                       int32_t c_task, float* loss, float* acc, float* dlogits, float* dprotos, void* stream);
+void gm_set_ragged_classes(int32_t on);     /* 1 / 0: ragged-task mode of the calling thread (above); workspace sizes depend on it */
+int32_t gm_get_ragged_classes(void);
 
 /* ---- The fused hot path: Meta.forward_ProtoMAML (meta.py:101-173) when need_meta_grad = 1,
  * Meta.finetunning_ProtoMAML (meta.py:175-234) when 0, for ALL sets (tasks) of spt/qry at once.

@@ -58,6 +58,8 @@ def parse(argv=None):
     ap.add_argument('--hoist_z1', type=int, default=0, help='1: aggregate the layer-1 input once per meta-step instead of in every forward')
     ap.add_argument('--sparse_bwd', type=int, default=0, help='1: backward only over the rows whose gradient is structurally non-zero')
     ap.add_argument('--cone', type=int, default=0, help='1: evaluate each layer only on the rows that can reach a centre (forward and backward)')
+    ap.add_argument('--ragged', type=int, default=0, choices=[0, 1],
+                    help='1: tasks with short or imbalanced classes are trained and evaluated on (sample means over the rows that are there) instead of raising')
     ap.add_argument('--predict_out', default=None, type=str,
                     help='after the final test evaluation, label the query subgraphs of the test tasks with the early-stopped model and write them to this .npz')
     return ap.parse_args(argv)
