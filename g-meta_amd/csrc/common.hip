@@ -341,6 +341,7 @@ const gm_knobs& gm_knob() {
         k.gemm_mode = (gm && (!strcmp(gm, "split") || !strcmp(gm, "1"))) ? 1 : (gm && (!strcmp(gm, "f32") || !strcmp(gm, "0"))) ? 0 : -1;
         k.gemm_split_min_tiles = env("GM_GEMM_SPLIT_MIN_TILES", -1);
         k.centre_store = env("GM_CENTRE_STORE", 2);
+        k.dead_rows = env("GM_DEAD_ROWS", 1);
         k.fuse_agg = env("GM_FUSE_AGG", 1);
         k.fuse_diff = env("GM_FUSE_DIFF", 2);
         k.extract_pref16 = env("GM_EXTRACT_PREF16", 1);
@@ -366,7 +367,7 @@ extern "C" int32_t gm_tuning_epoch(void) { return g_tuning_epoch.load(std::memor
 static int gm_knobs::* gm_find_knob(const char* name) {
     (void)gm_knob();
     static const struct { const char* name; int gm_knobs::*field; } tab[] = {
-        {"GM_GEMM_SPLIT_MIN_TILES", &gm_knobs::gemm_split_min_tiles}, {"GM_CENTRE_STORE", &gm_knobs::centre_store},
+        {"GM_GEMM_SPLIT_MIN_TILES", &gm_knobs::gemm_split_min_tiles}, {"GM_CENTRE_STORE", &gm_knobs::centre_store}, {"GM_DEAD_ROWS", &gm_knobs::dead_rows},
         {"GM_HEAD_STAGE", &gm_knobs::head_stage}, {"GM_HEAD_THREADS", &gm_knobs::head_threads}, {"GM_QUERY_STREAMS", &gm_knobs::query_streams}, {"GM_AGG_MID_LIST", &gm_knobs::agg_mid_list}, {"GM_AGG_MID_WIN", &gm_knobs::agg_mid_win}, {"GM_AGG_STREAM", &gm_knobs::agg_stream}, {"GM_AGG_STREAM_MIN_ROWS", &gm_knobs::agg_stream_min_rows},
         {"GM_SPLIT16_MIN_ROWS", &gm_knobs::split16_min_rows}, {"GM_WGRAD_SPLIT_MIN_CHUNKS", &gm_knobs::wgrad_split_min_chunks}, {"GM_TIMING", &gm_knobs::timing},
         {"GM_FUSE_DIFF", &gm_knobs::fuse_diff}, {"GM_EXTRACT_PREF16", &gm_knobs::extract_pref16},

@@ -554,10 +554,12 @@ __global__ void k_edge_tables(const int32_t* indices, const int32_t* indices_t, 
 // ONE pass over the rows for everything the finalisation derives from the row bounds (round 6; four launches before): hub-row lists of both orientations (atomic append; the host orders them), the fused launch's per-row source table with its
 // row / edge counts (gm_batch::d_fuse2 / d_fuse2_feat, unfused_rows / unfused_edges), and the keep-flag row scale gm_batch::d_norm_c with the sign bit set on
 // every row (k_centre_rows clears it on the centre rows afterwards).  Hub rows: in-degree (o = 0) / out-degree (o = 1) above `thr`.
+// Same pass: gm_batch::d_norm_src (the norm, sign bit set on the rows without an out-edge: nobody's source) with the count of the other rows as a third
+// per-workgroup partial, and the all-zero entries of gm_batch::d_dq_tab (k_centre_rows writes the centre rows' afterwards).
 __global__ void k_row_tables(const int32_t* indptr, const int32_t* indices, const int32_t* indptr_t, int64_t rows, const float* norm, const int32_t* feat_row,
                              int4* f2, int4* f2_feat, unsigned long long* counts, int32_t* heavy0, int32_t* heavy1, int32_t* hcnt, int cap, int thr, float* norm_c,
-                             int2* first0, int2* first1, int n_first) {
-    unsigned long long nr = 0, ne = 0;
+                             int2* first0, int2* first1, int n_first, float* norm_src, int4* dq_tab) {
+    unsigned long long nr = 0, ne = 0, ns = 0;
     for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
         const int p = indptr[r], d = indptr[r + 1] - p, dt = indptr_t[r + 1] - indptr_t[r];
         // [rows: cap][degrees: cap]; the first n_first (row, degree) pairs also go to the round trip's scratch (one download for everything the host waits for)
@@ -579,6 +581,9 @@ __global__ void k_row_tables(const int32_t* indptr, const int32_t* indices, cons
         }
         const float nrm = norm[r];
         norm_c[r] = __uint_as_float(__float_as_uint(nrm) | 0x80000000u);
+        norm_src[r] = dt > 0 ? nrm : __uint_as_float(__float_as_uint(nrm) | 0x80000000u);
+        if (dt > 0) ++ns;
+        dq_tab[r] = make_int4(GM_FUSE_ZERO, GM_FUSE_ZERO, 0, 0);
         const int self = (int)r | GM_FUSE_SELF;
         int4 t = make_int4(self, self, __float_as_int(1.f), 0), tf = t;
         if (d == 0) { t = make_int4(GM_FUSE_ZERO, GM_FUSE_ZERO, __float_as_int(1.f), 0); tf = t; }
@@ -592,14 +597,15 @@ __global__ void k_row_tables(const int32_t* indptr, const int32_t* indices, cons
     }
     // one pair of partials per WORKGROUP (wave shuffles, then the four wave partials through LDS): as atomics the two counters are a single contended
     // address each -- per thread 92k atomics took longer than the table itself, per wave the 16k of the 1.14 M-row batch still cost ~100 us
-    __shared__ unsigned long long part[2][4];
+    __shared__ unsigned long long part[3][4];
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { nr += __shfl_down(nr, off, 64); ne += __shfl_down(ne, off, 64); }
-    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = nr; part[1][threadIdx.x >> 6] = ne; }
+    for (int off = 32; off >= 1; off >>= 1) { nr += __shfl_down(nr, off, 64); ne += __shfl_down(ne, off, 64); ns += __shfl_down(ns, off, 64); }
+    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = nr; part[1][threadIdx.x >> 6] = ne; part[2][threadIdx.x >> 6] = ns; }
     __syncthreads();
     if (threadIdx.x == 0) {         // per-workgroup partials, summed by the host after the round trip (no same-address atomics at all: 2 x 2,048 of them were a third of this kernel)
-        counts[2 * blockIdx.x] = part[0][0] + part[0][1] + part[0][2] + part[0][3];
-        counts[2 * blockIdx.x + 1] = part[1][0] + part[1][1] + part[1][2] + part[1][3];
+        counts[3 * blockIdx.x] = part[0][0] + part[0][1] + part[0][2] + part[0][3];
+        counts[3 * blockIdx.x + 1] = part[1][0] + part[1][1] + part[1][2] + part[1][3];
+        counts[3 * blockIdx.x + 2] = part[2][0] + part[2][1] + part[2][2] + part[2][3];
     }
 }
 // distinct sources of the rows with more than maxdeg in-edges: mark, then count
@@ -677,13 +683,14 @@ __global__ __launch_bounds__(MID_BLOCK) void k_mid_scatter(const int32_t* indptr
 // centre rows, their norms and in-degrees (row-sparse backward tables)
 // (norm_c != NULL: also clears the keep-flag scale's sign bit on the centre rows -- after k_row_tables set it on every row)
 __global__ void k_centre_rows(const int32_t* sub_off, const int32_t* centre, int nc, int n_c, const int32_t* indptr, const float* norm,
-                              int32_t* crow, float* cnorm, int32_t* cdeg, float* norm_c, int32_t* centre_copy) {
+                              int32_t* crow, float* cnorm, int32_t* cdeg, float* norm_c, int32_t* centre_copy, int4* dq_tab) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_c) return;
     const int row = sub_off[k / nc] + centre[k];
     centre_copy[k] = centre[k];
     crow[k] = row; cnorm[k] = norm[row]; cdeg[k] = indptr[row + 1] - indptr[row];
     if (norm_c) norm_c[row] = __uint_as_float(__float_as_uint(norm[row]) & 0x7fffffffu);
+    if (dq_tab) dq_tab[row] = make_int4(row | GM_FUSE_SELF, GM_FUSE_ZERO, __float_as_int(1.f), 0);      // (two centres on one row write the same entry)
 }
 __global__ void k_centre_edges(const int32_t* crow, const int32_t* eoff, int n_c, const int32_t* indptr, const int32_t* indices,
                                const float* norm, int32_t* e_row, int32_t* e_par, float* e_norm) {
@@ -892,11 +899,11 @@ static int finalize_launch(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
     b->heavy_deg = gm_heavy_deg_for(b->rows, b->edges);
     const int cap = (int)(b->edges / b->heavy_deg + 1);
     // scratch of the round trip in ONE allocation, ONE memset, ONE download (eight copies before):
-    // ints [4,6) hub-row counts | [8, 8 + n_c) centre in-degrees | n_c local centre ids | 2 x first (row, degree) pairs of the hub lists | k_row_tables' per-workgroup {rows, edges} partials (u64 pairs)
+    // ints [4,6) hub-row counts | [8, 8 + n_c) centre in-degrees | n_c local centre ids | 2 x first (row, degree) pairs of the hub lists | k_row_tables' per-workgroup {rows, edges, rows with an out-edge} partials (u64 triples)
     const int nc = b->centres; b->n_c = b->subs * nc;
     const int first = std::min(cap, GM_HEAVY_FIRST);
-    const int rt_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (b->rows + 255) / 256));        // k_row_tables' grid, one {rows, edges} partial pair per workgroup (512 .. 8,192 workgroups: the same 91 us on the query batch)
-    const size_t o_cdeg = 8, o_centre = o_cdeg + b->n_c, o_first = (o_centre + b->n_c + 1) / 2 * 2, o_part = o_first + 4 * (size_t)first, scr_ints = o_part + 4 * (size_t)rt_blocks;
+    const int rt_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (b->rows + 255) / 256));        // k_row_tables' grid, one {rows, edges, source rows} partial triple per workgroup (512 .. 8,192 workgroups: the same 91 us on the query batch)
+    const size_t o_cdeg = 8, o_centre = o_cdeg + b->n_c, o_first = (o_centre + b->n_c + 1) / 2 * 2, o_part = o_first + 4 * (size_t)first, scr_ints = o_part + 6 * (size_t)rt_blocks;
     char* scratch = nullptr;
     GM_TRY(gm_dev_alloc((void**)&scratch, 4 * scr_ints, s));
     fc.scratch = scratch; fc.s = s;
@@ -911,17 +918,17 @@ static int finalize_launch(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
         hipLaunchKernelGGL(k_edge_tables, dim3((int)std::min<int64_t>(4096, (b->edges + 255) / 256)), dim3(256), 0, s, b->d_indices, b->d_indices_t, (int64_t)b->edges,
                            b->d_norm, b->d_feat_row, b->d_enorm[0], b->d_enorm[1], b->d_efeat);
     }
-    GM_TRY(gm_balloc(b, &b->d_norm_c, b->rows, s));
+    GM_TRY(gm_balloc(b, &b->d_norm_c, b->rows, s)); GM_TRY(gm_balloc(b, &b->d_norm_src, b->rows, s));
     if (b->rows > 0) {
-        int4 *f0 = nullptr, *ff = nullptr;
-        GM_TRY(gm_balloc(b, &f0, (size_t)b->rows, s)); GM_TRY(gm_balloc(b, &ff, (size_t)b->rows, s));
-        b->d_fuse2 = f0; b->d_fuse2_feat = ff;
+        int4 *f0 = nullptr, *ff = nullptr, *fd = nullptr;
+        GM_TRY(gm_balloc(b, &f0, (size_t)b->rows, s)); GM_TRY(gm_balloc(b, &ff, (size_t)b->rows, s)); GM_TRY(gm_balloc(b, &fd, (size_t)b->rows, s));
+        b->d_fuse2 = f0; b->d_fuse2_feat = ff; b->d_dq_tab = fd;
         hipLaunchKernelGGL(k_row_tables, dim3(rt_blocks), dim3(256), 0, s, b->d_indptr, b->d_indices, b->d_indptr_t, (int64_t)b->rows,
-                           b->d_norm, b->d_feat_row, f0, ff, d_counts, b->d_heavy[0], b->d_heavy[1], d_cnt, cap, b->heavy_deg, b->d_norm_c, d_first[0], d_first[1], first);
+                           b->d_norm, b->d_feat_row, f0, ff, d_counts, b->d_heavy[0], b->d_heavy[1], d_cnt, cap, b->heavy_deg, b->d_norm_c, d_first[0], d_first[1], first, b->d_norm_src, fd);
     }
     GM_TRY(gm_balloc(b, &b->d_crow, b->n_c, s)); GM_TRY(gm_balloc(b, &b->d_cnorm, b->n_c, s));
     hipLaunchKernelGGL(k_centre_rows, dim3((b->n_c + 255) / 256), dim3(256), 0, s, b->d_sub_off, b->d_centre, nc, b->n_c, b->d_indptr, b->d_norm,
-                       b->d_crow, b->d_cnorm, d_cdeg, b->d_norm_c, (int32_t*)scratch + o_centre);
+                       b->d_crow, b->d_cnorm, d_cdeg, b->d_norm_c, (int32_t*)scratch + o_centre, (int4*)b->d_dq_tab);
     GM_HIP(hipGetLastError());
     // ---- the one round trip
     const int32_t* h_scr = sg.download((const int32_t*)scratch, scr_ints);
@@ -939,9 +946,9 @@ static int finalize_finish(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
     const int32_t* h_cnt = fc.h_cnt; const unsigned long long* h_counts = fc.h_counts; const int32_t* h_cdeg = fc.h_cdeg;
     gm_dev_free(fc.scratch, s); fc.scratch = nullptr;
     if (h_counts) {
-        unsigned long long nr = 0, ne = 0;
-        for (int k = 0; k < fc.n_count_pairs; ++k) { nr += h_counts[2 * k]; ne += h_counts[2 * k + 1]; }
-        b->unfused_rows = (int64_t)nr; b->unfused_edges = (int64_t)ne;
+        unsigned long long nr = 0, ne = 0, ns = 0;
+        for (int k = 0; k < fc.n_count_pairs; ++k) { nr += h_counts[3 * k]; ne += h_counts[3 * k + 1]; ns += h_counts[3 * k + 2]; }
+        b->unfused_rows = (int64_t)nr; b->unfused_edges = (int64_t)ne; b->n_src = (int64_t)ns;
     }
     b->h_centre.assign(fc.h_centre, fc.h_centre + b->n_c);
     b->sched_win = gm_agg_window(b->rows, b->edges);
@@ -1339,6 +1346,8 @@ static int field_ptr(const gm_batch_t* b, int32_t field, void** p, int64_t* byte
         case GM_F_CENTRE: *p = b->d_centre; *bytes = 4ll * b->subs * b->centres; break;
         case GM_F_NORM: *p = b->d_norm; *bytes = 4ll * b->rows; break;
         case GM_F_FEAT_ROW: *p = b->d_feat_row; *bytes = 4ll * b->rows; break;
+        case GM_F_NORM_SRC: *p = b->d_norm_src; *bytes = 4ll * b->rows; break;
+        case GM_F_NORM_CENTRE: *p = b->d_norm_c; *bytes = 4ll * b->rows; break;
         default: gm_set_error("unknown batch field %d", field); return GM_EINVAL;
     }
     return GM_OK;
@@ -1352,6 +1361,12 @@ extern "C" int gm_batch_read(const gm_batch_t* b, int32_t field, void* host_dst,
     if (field == GM_F_CENTRE && (int64_t)b->h_centre.size() * 4 == need) { memcpy(host_dst, b->h_centre.data(), (size_t)need); return GM_OK; }
     GM_HIP(hipMemcpyAsync(host_dst, p, (size_t)need, hipMemcpyDeviceToHost, b->stream));
     GM_HIP(hipStreamSynchronize(b->stream));
+    return GM_OK;
+}
+
+extern "C" int gm_batch_source_rows(const gm_batch_t* b, int64_t* n_rows) {
+    GM_REQUIRE(b && n_rows, GM_EINVAL, "batch_source_rows: NULL argument");
+    *n_rows = b->n_src;
     return GM_OK;
 }
 

@@ -947,7 +947,11 @@ __device__ const float gm_wgs_ones[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f}
 // lane j & 7 fetches row j's entry, forms its two addresses (src_addr), and v_readlane broadcasts them into the SGPR base pairs of the group's loads.
 // (Forming them inside the stage's MFMA sequence instead of in front of the loads measured the same; that variant's first build came out with phi
 // copies of in-flight registers at its loop head -- tools/check_inflight_regs.py / tests/test_kernel_resources.py now replay every build's ISA.)
-template <int KT, int NT, int NP = 3, bool GA = false>
+// DR = true (GM_DEAD_ROWS): G = dQ_L of a pass that never zero-filled it -- only the centre rows were written.  The row scales carry "never written" in their
+// sign bit (gm_batch::d_norm_c): A is scaled by the magnitude, a flagged row of G enters the planes and db as zeros by a SELECT (its bytes may hold anything,
+// NaN included).  The scale load then fetches the stage's 16 rows (lane j & 15: row j) instead of the A octet's 8 twice: A and G items of a wave may sit in
+// different octets.  Loads, their order and every wait are those of the DR = false kernels, which this parameter leaves as they were.
+template <int KT, int NT, int NP = 3, bool GA = false, bool DR = false>
 __global__ __launch_bounds__(WGS_THREADS) void k_wgrad_split(WgradK w) {
     constexpr int K = KT * 128, N = NT * 128, COLS = K + N;
     constexpr int NTK = KT, NTN = 2 * NT;                                           // 32 x 32 tiles per wave: (K / 32) / 4 x (N / 32) / 2
@@ -1059,7 +1063,8 @@ __global__ __launch_bounds__(WGS_THREADS) void k_wgrad_split(WgradK w) {
             }                                                                                                              \
         }                                                                                                                  \
         }                                                                                                                  \
-        const unsigned offs = scaled ? (unsigned)min((R0) + oct8[0] + (lane & 7), nrows - 1) * 4u : (unsigned)(lane & 7) * 4u; \
+        const unsigned offs = DR ? (unsigned)min((R0) + (lane & 15), nrows - 1) * 4u                                       \
+                                 : scaled ? (unsigned)min((R0) + oct8[0] + (lane & 7), nrows - 1) * 4u : (unsigned)(lane & 7) * 4u; \
         asm volatile("global_load_dword %0, %1, %2" : "=v"(ps[SL]) : "v"(offs), "s"(sscale) : "memory");                  \
     } while (0)
 #define WGS_TIE(SL, IT) "+v"(pf[SL][IT][0]), "+v"(pf[SL][IT][1]), "+v"(pf[SL][IT][2]), "+v"(pf[SL][IT][3]), "+v"(pf[SL][IT][4]), "+v"(pf[SL][IT][5]), "+v"(pf[SL][IT][6]), "+v"(pf[SL][IT][7])
@@ -1088,8 +1093,14 @@ __global__ __launch_bounds__(WGS_THREADS) void k_wgrad_split(WgradK w) {
                 if constexpr (GA) if (it == 0)                           /* the aggregate kernel's chain: fma(x1, w1, fma(x0, w0, 0)) */ \
                     v_ = __fmaf_rn(pf1[SL][j], __int_as_float(__builtin_amdgcn_readlane(tw[SL].y, j)),                     \
                                    __fmaf_rn(v_, __int_as_float(__builtin_amdgcn_readlane(tw[SL].x, j)), 0.f));            \
+                if constexpr (DR) {                                                                                        \
+                    const int sc_ = __builtin_amdgcn_readlane(__float_as_int(ps[SL]), oct8[it] + j);                       \
+                    if (it == 0) { v_ *= __int_as_float(sc_ & 0x7fffffff); x[j] = r < nrows ? v_ : 0.f; }                  \
+                    else x[j] = (r < nrows && sc_ >= 0) ? v_ : 0.f;                 /* ... and so do the rows nobody wrote */ \
+                } else {                                                                                                   \
                 if (it == 0) v_ *= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ps[SL]), j));                   \
                 x[j] = r < nrows ? v_ : 0.f;                                        /* rows past the chunk end contribute zeros */ \
+                }                                                                                                          \
                 if (it == 1) bsum += x[j];                                                                                 \
                 if constexpr (NP == 2) x[j] *= op_scale[it];                                                               \
             }                                                                                                              \
@@ -1197,10 +1208,16 @@ __global__ __launch_bounds__(WGS_THREADS) void k_wgrad_split(WgradK w) {
 }
 
 template <int KT, int NT>
-static int launch_wgrad_split(const WgradK& w, hipStream_t s, int np) {
+static int launch_wgrad_split(const WgradK& w, hipStream_t s, int np, bool dead_rows) {
     constexpr int K = KT * 128, N = NT * 128;
     const size_t lds = 2 * 32 * (size_t)np * (size_t)(K + N);
-    if (w.f2) {                                          // A formed from the per-row source table (three-piece kernels only: launch_wgrad checks)
+    if (dead_rows && w.f2) {                             // (three-piece kernels only: launch_wgrad checks)
+        GM_TRY(gm_func_full_lds((const void*)k_wgrad_split<KT, NT, 3, true, true>));
+        hipLaunchKernelGGL((k_wgrad_split<KT, NT, 3, true, true>), dim3(w.n_chunks), dim3(WGS_THREADS), lds, s, w);
+    } else if (dead_rows) {
+        GM_TRY(gm_func_full_lds((const void*)k_wgrad_split<KT, NT, 3, false, true>));
+        hipLaunchKernelGGL((k_wgrad_split<KT, NT, 3, false, true>), dim3(w.n_chunks), dim3(WGS_THREADS), lds, s, w);
+    } else if (w.f2) {                                          // A formed from the per-row source table (three-piece kernels only: launch_wgrad checks)
         GM_TRY(gm_func_full_lds((const void*)k_wgrad_split<KT, NT, 3, true>));
         hipLaunchKernelGGL((k_wgrad_split<KT, NT, 3, true>), dim3(w.n_chunks), dim3(WGS_THREADS), lds, s, w);
     } else if (np == 2) {
@@ -1420,14 +1437,18 @@ static int launch_wgrad(const gm_wgrad_args& a, hipStream_t s) {
     const bool fast_ok = wgrad_fast_ok(a);
     GM_REQUIRE(!a.fuse2 || (wgrad_takes_split(a) && a.gx && a.np != 2 && a.lda <= (int64_t)(1 << 20) && a.ldgx <= (int64_t)(1 << 20)), GM_EINVAL,
                "wgrad: a table-formed A operand needs the split kernel (K=%d N=%d chunks=%d)", a.K, a.N, a.n_chunks);
+    GM_REQUIRE(!a.g_keep || (wgrad_takes_split(a) && !(a.np == 2 && a.a_bound.amax && a.g_bound.amax)), GM_EINVAL,
+               "wgrad: flagged rows of G need the three-piece split kernel (K=%d N=%d chunks=%d)", a.K, a.N, a.n_chunks);
     if (wgrad_takes_split(a)) {
         const int np = (a.np == 2 && a.a_bound.amax && a.g_bound.amax) ? 2 : 3;
+        const bool dr = a.g_keep != nullptr;
+        if (dr) w.a_scale = a.g_keep;
         if (a.fuse2) { w.f2 = (const int4*)a.fuse2; w.gx = a.gx; w.ldgx = a.ldgx; w.zrow = gm_zero_row(s); GM_REQUIRE(w.zrow, GM_ENOMEM, "wgrad: no zero row"); }
         w.a_bound = a.a_bound; w.g_bound = a.g_bound;
-        if (a.K == 256 && a.N == 256) GM_TRY((launch_wgrad_split<2, 2>(w, s, np)));
-        else if (a.K == 128 && a.N == 256) GM_TRY((launch_wgrad_split<1, 2>(w, s, np)));
-        else if (a.K == 256 && a.N == 128) GM_TRY((launch_wgrad_split<2, 1>(w, s, np)));
-        else GM_TRY((launch_wgrad_split<1, 1>(w, s, np)));
+        if (a.K == 256 && a.N == 256) GM_TRY((launch_wgrad_split<2, 2>(w, s, np, dr)));
+        else if (a.K == 128 && a.N == 256) GM_TRY((launch_wgrad_split<1, 2>(w, s, np, dr)));
+        else if (a.K == 256 && a.N == 128) GM_TRY((launch_wgrad_split<2, 1>(w, s, np, dr)));
+        else GM_TRY((launch_wgrad_split<1, 1>(w, s, np, dr)));
         launched = true;
     }
     if (fast_ok && !launched) {

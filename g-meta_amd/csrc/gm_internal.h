@@ -162,7 +162,12 @@ struct gm_batch {
     float* d_cnorm = nullptr;          // [n_c]  norm[centre row]
     float* d_norm_c = nullptr;         // [rows] norm with the SIGN BIT SET on every row that is not a centre: row scale + "somebody reads this row" flag of the last layer's
                                        //        forward-only update (gm_gemm_args::row_scale_keep)
-    int32_t n_e1 = 0;                  // in-edges of centres, concatenated in centre order
+    // GM_DEAD_ROWS (k_row_tables, same pass): the same flag for the layers BELOW the last, whose activations are read through the edges only --
+    float* d_norm_src = nullptr;       // [rows] norm with the SIGN BIT SET on every row without an out-edge inside the batch (nobody's source: H_l of that row has no reader)
+    int64_t n_src = 0;                 //        rows WITH an out-edge (the rows those updates store)
+    void* d_dq_tab = nullptr;          // [rows] int4, laid out like d_fuse2: centre rows {row | GM_FUSE_SELF, GM_FUSE_ZERO, 1, 0}, every other row {GM_FUSE_ZERO, GM_FUSE_ZERO, 0, 0} --
+                                       //        the dZ GEMM of the last layer reads dQ_L through it (only its centre rows were ever written)
+    int32_t n_e1 = 0;                 // in-edges of centres, concatenated in centre order
     int32_t* d_e1_row = nullptr;       // [n_e1] source row of the edge
     int32_t* d_e1_par = nullptr;       // [n_e1] compact index of the centre it enters
     float* d_e1_norm = nullptr;        // [n_e1] norm[source row]
@@ -196,6 +201,7 @@ struct gm_knobs {
     int gemm_mode;                 // 0 exact fp32, 1 split-bf16, -1 not set (library default)
     int gemm_split_min_tiles;      // -1: a quarter of the current device's CUs
     int centre_store;              // GM_CENTRE_STORE: the last layer's update stores only the centre rows of its activation -- in every pass (2, default), in the forward-only passes (1) -- or every row (0)
+    int dead_rows;                 // GM_DEAD_ROWS: rows no later kernel reads are computed and not stored / not zero-filled (1, default; off with GM_CENTRE_STORE=0 too): H_l below the last layer at rows without an out-edge, dQ_L outside the centre rows
     int fuse_agg, head_stage;
     int fuse_diff;                 // GM_FUSE_DIFF: the differentiated passes of the dense schedule take the fused aggregate + GEMM too, their weight gradients form Z's rows from the source table: 2 (default) everywhere except a support batch whose full launches take the stream aggregate, 1 everywhere, 0 never
     int agg_mid_win;               // GM_AGG_MID_WIN: rows per wave window over that list (0 = by its length)
@@ -426,6 +432,9 @@ struct gm_wgrad_args {
     // from gx (row stride ldgx) through the per-row table fuse2 (gm_batch::d_fuse2 / d_fuse2_feat) in the aggregate's fma order, rows the table flags
     // GM_FUSE_SELF are read from A (the partial aggregate launch wrote them), GM_FUSE_ZERO rows are zero
     const void* fuse2; const float* gx; int64_t ldgx;
+    // optional (three-piece split kernel only, GM_EINVAL elsewhere): the row scale again, |value| = a_scale, with the SIGN BIT SET on rows of G that were never
+    // written (dQ_L outside the centre rows: gm_batch::d_norm_c) -- such a row enters dW and db as zeros, whatever its bytes hold
+    const float* g_keep;
     gm_wgrad_hold* hold; int hold_this; // optional: hold this call's reduction back (hold_this = 1; its `partial` must then stay untouched) /
                                         // flush the held ones with this call's reduction (hold_this = 0)
     int pick;                           // kernel family: 0 = the library's choice (gm_gemm_mode, GM_WGRAD_SPLIT_MIN_CHUNKS); GM_WGRAD_PICK_EXACT /

@@ -688,6 +688,8 @@ struct GcnCtx {
     PlaneDir* pd;                // non-NULL inside gm_meta_step
     bool is_support = false;     // gm_meta_step's support-chain context (the serial dependency of the step; the query contexts carry the bulk work)
     int dq_zeroed = 0;           // the last forward GEMM already zero-filled bufA (= dQ) for the head/loss launch that follows
+    int dq_centre = 0;           // GM_DEAD_ROWS: the last forward left bufA (= dQ) alone -- the head/loss launch assigns its centre rows and the two readers of dQ_L in the
+                                 // gcn_backward(skip_head = 1) that follows take every other row as zeros (dZ GEMM: gm_batch::d_dq_tab; weight gradient: gm_wgrad_args::g_keep)
     bool zfused[GM_MAX_GCN] = {};    // the last forward left Z[l] written at the rows of three or more sources only (fused aggregate + GEMM in a pass that IS
                                      // differentiated): the backward's weight gradient forms the other rows from the per-row source table (gm_wgrad_args::fuse2)
     float* Z[GM_MAX_GCN]; float* H[GM_MAX_GCN]; float* X0; float* bufA; float* bufB; float* partial;
@@ -843,6 +845,9 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
     GM_REQUIRE(L.dims[0] == b->store->feat_dim || L.dims[0] == b->store->feat_ld || c.x0_user, GM_EINVAL, "forward: dims[0]=%d but the store has %d features", L.dims[0], b->store->feat_dim);
     GM_REQUIRE((L.link != 0) == (b->centres == 2), GM_EINVAL, "forward: link_pred model needs a 2-centre batch and vice versa");
     const float* xin = c.x0_user;           // NULL = gather rows of the store through feat_row
+    c.dq_centre = 0;
+    // GM_DEAD_ROWS: rows nobody reads are computed and not stored (GM_CENTRE_STORE=0, "every row stored", switches it off too)
+    const bool dead_rows = gm_knob().dead_rows && gm_knob().centre_store != 0 && !c.centre;
     if (c.np == 2) {                        // a new pass: its own bound slots
         ++c.am_pass;
         GM_REQUIRE(c.am_pass < c.am_passes, GM_EINVAL, "forward: more passes than bound slots (%d)", c.am_passes);
@@ -923,6 +928,11 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
             // last layer: only the head reads H_L, and only its centre rows (h[to_fetch]; the backward pass takes relu' from the bits and the
             // weight gradient from Z_L): the other rows are computed, their relu' bits written, their values not stored
             if (l == L.n_gcn - 1 && !c.centre && b->d_norm_c && (gm_knob().centre_store >= 2 || (gm_knob().centre_store == 1 && fwd_only == 1))) { g.row_scale_keep = b->d_norm_c; g.n_keep = b->n_c; }
+            // a layer below the last: H_l is read through the edges only (the next layer's aggregate, the fused loaders, the table-formed weight gradient; the
+            // backward takes relu' from the bits) -- a row without an out-edge is nobody's source: computed, its relu' bits written, its value not stored
+            if (dead_rows && split_ok && l < L.n_gcn - 1 && (fwd_only == 1 || (fwd_only == 2 && c.M[l])) && L.dims[l + 1] <= L.dims[l + 2] && b->d_norm_src) {
+                g.row_scale_keep = b->d_norm_src; g.n_keep = b->n_src;
+            }
             if (split_ok) {
                 gm_bound ab = gm_no_bound(), bb;
                 const bool want16 = in_bound(c, l, ab);
@@ -934,7 +944,13 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
                 if (np == 2) { g.amax_out = c.amH(l); c.hv[l] = true; }        // (the two-piece kernels record it)
             }
             // fwd_only == 2: the head + loss + backward follow (gm_meta_step): the last layer's GEMM zero-fills dQ on its way out instead of a memset launch
-            if (fwd_only == 2 && l == L.n_gcn - 1 && fo == L.dims[L.n_gcn]) { g.zero_out = c.bufA; c.dq_zeroed = 1; }
+            // GM_DEAD_ROWS: ... or no fill at all, where both readers of dQ_L can take the rows the head/loss launch does not assign as zeros: the dZ GEMM on the
+            // fused kernel through gm_batch::d_dq_tab, the weight gradient on the three-piece split kernel (gm_wgrad_args::g_keep)
+            if (fwd_only == 2 && l == L.n_gcn - 1 && fo == L.dims[L.n_gcn]) {
+                const bool dz_ok = l == 0 || (gm_gemm_split_ok(b->n_tiles, fo, fi) && fo >= 64 && fo <= 4096 && b->d_dq_tab);
+                if (dead_rows && split_ok && g.np != 2 && c.np != 2 && b->d_norm_c && dz_ok && gm_wgrad_gather_ok(b->n_chunks, fi, fo)) c.dq_centre = 1;
+                else { g.zero_out = c.bufA; c.dq_zeroed = 1; }
+            }
             if (fuse) {
                 g.zside = c.Z[l]; g.ldz = fi;
                 if (gather) { g.A = b->store->d_feat; g.lda = b->store->feat_ld; g.fuse2 = b->d_fuse2_feat; }
@@ -963,6 +979,7 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
     const int Lg = L.n_gcn;
     float* dQ = c.bufA; float* T = c.bufB;
     c.hold.n = 0;
+    const bool dq_centre = skip_head && c.dq_centre;      // dQ_L holds its centre rows only (head_loss); without skip_head it is filled right here
     if (!skip_head) {
         GM_HIP(hipMemsetAsync(dQ, 0, sizeof(float) * b->rows * L.dims[Lg], st));
         HeadK k = make_head(c, params, pstride);
@@ -1002,6 +1019,7 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
             // Order: dZ GEMM (reads dQ and the CURRENT weights) -> weight gradient (reads dQ; its reduction writes the updated
             // weights and, for the next step's dZ GEMM, their transpose) -> transposed aggregate (overwrites dQ).
             w.A = c.Z[l]; w.lda = fi; w.G = dQ; w.ldg = fo;
+            if (dq_centre && l == Lg - 1) w.g_keep = b->d_norm_c;
             if (c.zfused[l]) {                 // the forward ran fused: Z[l] holds the rows of three or more sources, the table forms the others
                 const bool gather = l == 0 && !c.x0_user;
                 w.fuse2 = gather ? b->d_fuse2_feat : b->d_fuse2;
@@ -1022,6 +1040,9 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
                     g.np = np; g.a_bound = ab; g.b_bound = bb;
                     if (np == 2) { g.amax_out = c.amT(l); c.tv[l] = true; }
                     g.B = params + L.w_off[l]; g.b_stride = pstride; g.transB = 1;
+                    // dQ_L with its centre rows only: the fused kernel's loader reads them through the batch's table (fma(0, 0, fma(x, 1, 0)) = x) and zeros for
+                    // every other row -- the same tile, bit for bit, as the plain launch over a zero-filled dQ
+                    if (dq_centre && l == Lg - 1) { g.fuse2 = b->d_dq_tab; g.zside = dQ; g.ldz = fo; }
                 } else if (use_wt) {
                     // dZ = dQ @ W^T through the direct-to-LDS kernel on transposed weights: left there by the previous step's
                     // weight-gradient reduction (which wrote these very weights), else transposed now (T x 256 KB)
@@ -1033,6 +1054,7 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
                     }
                     g.B = c.WTl[l]; g.b_stride = pstride ? (int64_t)fi * fo : 0; g.transB = 0;
                 } else { g.B = params + L.w_off[l]; g.b_stride = pstride; g.transB = 1; }
+                GM_REQUIRE(!(dq_centre && l == Lg - 1) || g.fuse2, GM_EINVAL, "backward: dQ was left unfilled for a dZ GEMM that cannot read it through the table");
                 GM_TRY(gm_launch_gemm_nn(g, st));
                 if (use_wt && c.sgd.next) { w.wt_next = c.WTl[l]; }
             }
@@ -1449,6 +1471,7 @@ static int head_loss(GcnCtx& c, const float* params, int64_t pstride, float* log
         else {
             dQ = c.bufA;
             if (c.dq_zeroed) c.dq_zeroed = 0;
+            else if (c.dq_centre) {}          // nobody reads the rows this launch does not assign
             else GM_HIP(hipMemsetAsync(dQ, 0, sizeof(float) * b->rows * L.dims[L.n_gcn], st));
         }
     }
@@ -2241,6 +2264,43 @@ extern "C" int gm_dense_gemm(const gm_batch_t* b, const float* x, int64_t ldx, i
     if (rc == GM_OK) rc = gm_launch_gemm_nn(g, st);
     if (planes) gm_dev_free(planes, st);
     if (slots) gm_dev_free(slots, st);
+    gm_batch_mark_use(b, st);
+    return rc;
+}
+
+// The dZ product of the last layer over a dQ that holds its centre rows only, as gcn_backward launches it under GM_DEAD_ROWS (tests)
+extern "C" int gm_dense_dz_centre(const gm_batch_t* b, const float* dQ, int32_t K, const float* W, int64_t w_stride, int32_t N, float* T, void* stream) {
+    GM_REQUIRE(b && dQ && W && T && b->d_dq_tab, GM_EINVAL, "dense_dz_centre: bad arguments");
+    GM_REQUIRE((N == 256 || N == 128) && K % 16 == 0 && K >= 64, GM_EINVAL, "dense_dz_centre: the fused split kernel needs N = 128 or 256 and K a multiple of 16 (>= 64)");
+    hipStream_t st = (hipStream_t)stream;
+    const int wsets = w_stride ? b->sets : 1;
+    uint16_t* planes = nullptr;
+    GM_TRY(gm_alloc(&planes, (size_t)wsets * 3 * K * N, st));
+    gm_gemm_args g{};
+    g.A = dQ; g.lda = K; g.B = W; g.b_stride = w_stride; g.transB = 1; g.C = T; g.ldc = N; g.K = K; g.N = N;
+    g.row_scale = b->d_norm; g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows;
+    g.fuse2 = b->d_dq_tab; g.zside = dQ; g.ldz = K;
+    int rc = gm_split_weights(W, w_stride, 0, K, N, 1, wsets, planes, st, 3, gm_no_bound());
+    g.Bsplit = planes; g.bsplit_stride = w_stride ? (int64_t)3 * K * N : 0; g.np = 3;
+    if (rc == GM_OK) rc = gm_launch_gemm_nn(g, st);
+    gm_dev_free(planes, st);
+    gm_batch_mark_use(b, st);
+    return rc;
+}
+// ... and its weight gradient
+extern "C" int gm_dense_wgrad_centre(const gm_batch_t* b, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
+                                     int64_t db_stride, void* stream) {
+    GM_REQUIRE(b && x && dQ && dW && db && b->d_norm_c, GM_EINVAL, "dense_wgrad_centre: bad arguments");
+    const int64_t KN = (int64_t)Kx * N;
+    GM_REQUIRE(b->sets == 1 || (dw_stride >= KN && db_stride >= N), GM_EINVAL, "dense_wgrad_centre: per-set outputs overlap");
+    hipStream_t st = (hipStream_t)stream;
+    gm_wgrad_args w{};
+    w.A = x; w.lda = Kx; w.K = Kx; w.G = dQ; w.ldg = N; w.N = N; w.a_scale = b->d_norm; w.g_keep = b->d_norm_c;
+    w.chunks = b->d_chunks; w.n_chunks = b->n_chunks; w.set_chunk_off = b->d_set_chunk_off; w.sets = b->sets; w.rows = b->rows;
+    w.dW = dW; w.dw_stride = dw_stride; w.db = db; w.db_stride = db_stride; w.pick = GM_WGRAD_PICK_SPLIT;
+    int rc = gm_alloc(&w.partial, (size_t)std::max(1, b->n_chunks) * (size_t)(KN + N), st);
+    if (rc == GM_OK) rc = gm_launch_wgrad(w, st);
+    if (w.partial) gm_dev_free(w.partial, st);
     gm_batch_mark_use(b, st);
     return rc;
 }

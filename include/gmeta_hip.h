@@ -133,12 +133,17 @@ enum gm_field {
     GM_F_INDICES_T,     /* int32[edges]   destination ROW of every out-edge                                          */
     GM_F_CENTRE,        /* int32[subs*centres] local index of the centre(s) inside each subgraph (sdp.py:318-319)    */
     GM_F_NORM,          /* float[rows]    in_degree.clamp(1)^-0.5 (learner.py:29)                                    */
-    GM_F_FEAT_ROW       /* int32[rows]    row of the store's feature matrix for each batch row                       */
+    GM_F_FEAT_ROW,      /* int32[rows]    row of the store's feature matrix for each batch row                       */
+    GM_F_NORM_SRC,      /* float[rows]    GM_F_NORM with the sign bit set on every row without an out-edge inside the batch: no later
+                                          kernel reads that row of a hidden activation below the last layer (GM_DEAD_ROWS)       */
+    GM_F_NORM_CENTRE    /* float[rows]    GM_F_NORM with the sign bit set on every row that is not a centre                     */
 };
 /* Copies a field to host memory (synchronises `stream` internally). */
 int gm_batch_read(const gm_batch_t* b, int32_t field, void* host_dst, int64_t bytes);
 /* Device address of a field (valid until gm_batch_destroy). */
 int gm_batch_device_ptr(const gm_batch_t* b, int32_t field, void** dptr);
+/* Rows with at least one out-edge inside the batch: the rows of GM_F_NORM_SRC whose sign bit is clear. */
+int gm_batch_source_rows(const gm_batch_t* b, int64_t* n_rows);
 
 /* ---- Feature gather: replaces np.vstack([feat[g][ids] ...]) + H2D (meta.py:119-120,193-194).
  * x_out: device fp32 [rows, feat_dim]. */
@@ -193,6 +198,14 @@ int gm_dense_gemm(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, c
                   float* out, int64_t ldc, const float* s, const float* s_keep, const float* bias, int64_t bias_stride, int32_t relu,
                   uint8_t* relu_bits, const float* mask_h, const uint8_t* mask_b, float* zero_out, uint32_t* amax_out, int32_t mode,
                   int32_t* launched, void* stream);
+/* The last layer's dZ product and weight gradient where dQ holds its CENTRE rows only (GM_DEAD_ROWS: gm_meta_step no longer zero-fills the others;
+ * their bytes may be anything), exported for tests:  T[r, :N] = norm[r] * (dQ0[r, :K] @ W_t^T)  with W_t stored [N, K] and dQ0 = dQ on the batch's
+ * centre rows, 0 elsewhere -- through the fused split kernel and the batch's per-row table;  dW_t[Kx, N] = sum_r (norm[r] x[r, :Kx])^T dQ0[r, :N],
+ * db_t[N] = sum_r dQ0[r, :N] -- through the split weight-gradient kernel's flagged-row variant.  Three pieces; dims as for modes 1 of gm_dense_gemm /
+ * gm_dense_wgrad (K >= 64 here), GM_EINVAL otherwise. */
+int gm_dense_dz_centre(const gm_batch_t* b, const float* dQ, int32_t K, const float* W, int64_t w_stride, int32_t N, float* T, void* stream);
+int gm_dense_wgrad_centre(const gm_batch_t* b, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
+                          int64_t db_stride, void* stream);
 /* The weight gradient of the same layer (learner.py backward of `torch.matmul(feat, weight)` + bias) over the batch's weight-gradient row chunks,
  * per set t:  dW_t[K, N] = sum over the set's rows r of (s[r] x[r, :])^T g[r, :]  and  db_t[N] = sum_r gb[r, :].  Exported for numerics tests of the
  * weight-gradient kernels.  x: device [rows, ldx] (K used), g: [rows, ldg] (N used); s: row scale [rows] or NULL (1); gb: [rows, ldgb] or NULL (g).
