@@ -687,9 +687,10 @@ struct GcnCtx {
     const gm_batch* b; gm_layout L;
     PlaneDir* pd;                // non-NULL inside gm_meta_step
     bool is_support = false;     // gm_meta_step's support-chain context (the serial dependency of the step; the query contexts carry the bulk work)
-    int dq_zeroed = 0;           // the last forward GEMM already zero-filled bufA (= dQ) for the head/loss launch that follows
-    int dq_centre = 0;           // GM_DEAD_ROWS: the last forward left bufA (= dQ) alone -- the head/loss launch assigns its centre rows and the two readers of dQ_L in the
-                                 // gcn_backward(skip_head = 1) that follows take every other row as zeros (dZ GEMM: gm_batch::d_dq_tab; weight gradient: gm_wgrad_args::g_keep)
+    // How the last forward left bufA (= dQ) for the head/loss launch and the gcn_backward(skip_head = 1) that follow.  DQ_MEMSET: untouched, head_loss zero-fills
+    // it with a memset launch; DQ_ZEROED: the last forward GEMM zero-filled it on its way out; DQ_CENTRE (GM_DEAD_ROWS): left alone -- the head/loss launch assigns its
+    // centre rows and the two readers of dQ_L in the backward take every other row as zeros (dZ GEMM: gm_batch::d_dq_tab; weight gradient: gm_wgrad_args::g_keep)
+    enum DqFill { DQ_MEMSET, DQ_ZEROED, DQ_CENTRE } dq = DQ_MEMSET;
     bool zfused[GM_MAX_GCN] = {};    // the last forward left Z[l] written at the rows of three or more sources only (fused aggregate + GEMM in a pass that IS
                                      // differentiated): the backward's weight gradient forms the other rows from the per-row source table (gm_wgrad_args::fuse2)
     float* Z[GM_MAX_GCN]; float* H[GM_MAX_GCN]; float* X0; float* bufA; float* bufB; float* partial;
@@ -825,6 +826,44 @@ static HeadK make_head(const GcnCtx& c, const float* params, int64_t pstride) {
     for (int t = 0; t <= b->sets && k.subs_per_set; ++t) if (b->h_set_sub_off[t] != t * k.subs_per_set) k.subs_per_set = 0;
     return k;
 }
+static int launch_head_fwd(const GcnCtx& c, const float* params, int64_t pstride, float* logits, hipStream_t st) {
+    hipLaunchKernelGGL(k_head_fwd, dim3((c.b->subs + 3) / 4), dim3(256), 0, st, make_head(c, params, pstride), logits);
+    GM_HIP(hipGetLastError());
+    return GM_OK;
+}
+// dQ: the full-height dQ_L (zero-filled by the caller), or Gc: its centre rows as a compact matrix
+static int launch_head_bwd(GcnCtx& c, const float* params, int64_t pstride, const float* dlogits, float* dparams, int64_t dstride, float* dQ, float* Gc, hipStream_t st) {
+    const HeadK k = make_head(c, params, pstride);
+    hipLaunchKernelGGL(k_head_bwd, dim3(c.b->sets), dim3(256), 0, st, k, dlogits, dparams, dstride, dQ, Gc);
+    GM_HIP(hipGetLastError());
+    if (dQ && k.dq_amax) c.dqv = true;
+    return GM_OK;
+}
+
+// One aggregate launch under the launch accounting: `bytes` as SURVEY 8(d) prices it, `strict_bytes` its compulsory HBM part
+static int launch_agg(const gm_agg_args& a, int64_t bytes, int64_t strict_bytes, hipStream_t st) {
+    gm_prof_agg_begin(st, bytes); gm_prof_note(GM_PROF_AGG_STRICT, strict_bytes);
+    const int rc = gm_launch_aggregate(a, st);
+    gm_prof_agg_end(st);
+    return rc;
+}
+// The batch-wide aggregate of the dense schedule over orientation dir (0: A, the in-edges; 1: A^T): graph, hub rows, block schedule and the context's hub set
+static int batch_agg(const GcnCtx& c, int dir, hipStream_t st, gm_agg_args& a) {
+    const gm_batch* b = c.b;
+    a = gm_agg_args{};
+    if (dir == 0) { a.indptr = b->d_indptr; a.indices = b->d_indices; } else { a.indptr = b->d_indptr_t; a.indices = b->d_indices_t; }
+    a.heavy = b->d_heavy[dir]; a.n_heavy = b->n_heavy[dir]; a.heavy_deg = b->heavy_deg;
+    a.sched = b->d_sched[dir]; a.sched_len = b->sched_len[dir]; a.sched_win = b->sched_win;
+    GM_TRY(gm_agg_hub(a, b, dir, st, c.hub_set));
+    a.rows = b->rows;
+    return GM_OK;
+}
+
+// The dZ GEMM of layer l >= 1 (dQ_l @ W_l^T: K = fo, N = fi) runs on the split kernels ...
+static bool dz_split_ok(const GcnCtx& c, int l) { return c.Wsplit && gm_gemm_split_ok(c.b->n_tiles, c.L.dims[l + 1], c.L.dims[l]); }
+// ... and on their fused loader, which reads a dQ_l that holds its centre rows only through the batch's table (DQ_CENTRE).  gcn_forward leaves dQ_L
+// unfilled, and gcn_backward reads it that way, by this one predicate
+static bool dz_centre_ok(const GcnCtx& c, int l) { return dz_split_ok(c, l) && c.L.dims[l + 1] >= 64 && c.L.dims[l + 1] <= 4096 && c.b->d_dq_tab; }
 
 int gm_gather_rows(const gm_store* store, const int32_t* feat_row, int64_t n, int F, float* out, hipStream_t st);
 static int cone_forward(GcnCtx& c, const float* params, int64_t pstride, float* logits, hipStream_t st, int reuse_z1, int skip_head);
@@ -845,7 +884,7 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
     GM_REQUIRE(L.dims[0] == b->store->feat_dim || L.dims[0] == b->store->feat_ld || c.x0_user, GM_EINVAL, "forward: dims[0]=%d but the store has %d features", L.dims[0], b->store->feat_dim);
     GM_REQUIRE((L.link != 0) == (b->centres == 2), GM_EINVAL, "forward: link_pred model needs a 2-centre batch and vice versa");
     const float* xin = c.x0_user;           // NULL = gather rows of the store through feat_row
-    c.dq_centre = 0;
+    c.dq = GcnCtx::DQ_MEMSET;
     // GM_DEAD_ROWS: rows nobody reads are computed and not stored (GM_CENTRE_STORE=0, "every row stored", switches it off too)
     const bool dead_rows = gm_knob().dead_rows && gm_knob().centre_store != 0 && !c.centre;
     if (c.np == 2) {                        // a new pass: its own bound slots
@@ -863,12 +902,11 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
             gm_gemm_args g{}; g.A = A; g.lda = lda; g.B = params + L.w_off[l]; g.b_stride = pstride; g.C = c.Z[l]; g.ldc = fo; g.K = fi; g.N = fo;
             g.row_scale = b->d_norm; g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows;
             GM_TRY(gm_launch_gemm_nn(g, st));
-            gm_agg_args a{}; a.indptr = b->d_indptr; a.indices = b->d_indices; a.heavy = b->d_heavy[0]; a.n_heavy = b->n_heavy[0]; a.heavy_deg = b->heavy_deg; a.sched = b->d_sched[0]; a.sched_len = b->sched_len[0]; a.sched_win = b->sched_win; GM_TRY(gm_agg_hub(a, b, 0, st, c.hub_set)); a.x = c.Z[l]; a.ldx = fo; a.s_out = b->d_norm;
+            gm_agg_args a; GM_TRY(batch_agg(c, 0, st, a));
+            a.x = c.Z[l]; a.ldx = fo; a.s_out = b->d_norm;
             a.bias = params + L.b_off[l]; a.bias_stride = pstride; a.set_row_off = b->d_set_row_off; a.n_sets = b->sets; a.relu = 1;
-            a.out = c.H[l]; a.rows = b->rows; a.width = fo; a.relu_bits = c.M[l];
-            gm_prof_agg_begin(st, gm_aggregate_bytes(b, fo)); gm_prof_note(GM_PROF_AGG_STRICT, gm_aggregate_bytes(b, fo));
-            GM_TRY(gm_launch_aggregate(a, st));
-            gm_prof_agg_end(st);
+            a.out = c.H[l]; a.width = fo; a.relu_bits = c.M[l];
+            GM_TRY(launch_agg(a, gm_aggregate_bytes(b, fo), gm_aggregate_bytes(b, fo), st));
         } else {                            // learner.py:41-47: aggregate first, then multiply
             const bool split_ok = c.Wsplit && gm_gemm_split_ok(b->n_tiles, fi, fo) && ((uintptr_t)(params + L.b_off[l]) & 15) == 0 && pstride % 4 == 0;
             // ... and, round 6, the passes that ARE differentiated by the dense backward (fwd_only == 2: the support passes, the last query pass): their only
@@ -885,7 +923,8 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
                               2 * b->unfused_rows <= b->rows;
             c.zfused[l] = fuse && fwd_only == 2;
             if (!(l == 0 && reuse_z1 && c.z1_valid)) {
-                gm_agg_args a{}; a.indptr = b->d_indptr; a.indices = b->d_indices; a.heavy = b->d_heavy[0]; a.n_heavy = b->n_heavy[0]; a.heavy_deg = b->heavy_deg; a.sched = b->d_sched[0]; a.sched_len = b->sched_len[0]; a.sched_win = b->sched_win; GM_TRY(gm_agg_hub(a, b, 0, st, c.hub_set)); a.s_in = b->d_norm; a.e_w = b->d_enorm[0]; a.out = c.Z[l]; a.rows = b->rows; a.width = fi;
+                gm_agg_args a; GM_TRY(batch_agg(c, 0, st, a));
+                a.s_in = b->d_norm; a.e_w = b->d_enorm[0]; a.out = c.Z[l]; a.width = fi;
                 if (gather) { a.x = b->store->d_feat; a.x_row = b->d_feat_row; a.x_idx = b->d_efeat; a.ldx = b->store->feat_ld; }
                 else { a.x = xin; a.ldx = fi; }
                 if (fuse) {
@@ -905,20 +944,14 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
                     const int64_t pb = pb0 + 4 * src * (int64_t)fi;
                     // strict HBM pricing as for the full launches: a gather launch reads at most the whole (cache-resident) feature table
                     const int64_t pbs = pb0 + 4 * (gather ? std::min<int64_t>(src, b->store->total_nodes) : src) * (int64_t)fi;
-                    gm_prof_agg_begin(st, pb); gm_prof_note(GM_PROF_AGG_STRICT, pbs);
                     gm_prof_note(GM_PROF_AGG_BOUND, pb0 + 4 * std::min<int64_t>(b->unfused_edges, b->rows) * (int64_t)fi - pb);      // (difference to the exact count)
-                    GM_TRY(gm_launch_aggregate(a, st));
-                    gm_prof_agg_end(st);
+                    GM_TRY(launch_agg(a, pb, pbs, st));
                 } else {
                     if (a.e_w) GM_TRY(gm_agg_stream_args(a, b, 0, gather, st));      // full launches may take the LDS-DMA stream kernel (agg_stream.hip)
-                    gm_prof_agg_begin(st, gm_aggregate_bytes(b, fi));
-                    {   // compulsory HBM bytes: a gather launch reads rows of the (cache-resident) feature table, at most all of it
-                        int64_t strict = gm_aggregate_bytes(b, fi);
-                        if (gather) strict += 4 * b->rows - 4 * b->rows * (int64_t)fi + std::min<int64_t>(4 * b->rows * (int64_t)fi, 4 * b->store->total_nodes * (int64_t)fi);
-                        gm_prof_note(GM_PROF_AGG_STRICT, strict);
-                    }
-                    GM_TRY(gm_launch_aggregate(a, st));
-                    gm_prof_agg_end(st);
+                    // compulsory HBM bytes: a gather launch reads rows of the (cache-resident) feature table, at most all of it
+                    int64_t strict = gm_aggregate_bytes(b, fi);
+                    if (gather) strict += 4 * b->rows - 4 * b->rows * (int64_t)fi + std::min<int64_t>(4 * b->rows * (int64_t)fi, 4 * b->store->total_nodes * (int64_t)fi);
+                    GM_TRY(launch_agg(a, gm_aggregate_bytes(b, fi), strict, st));
                     if (l == 0) c.z1_valid = 1;
                 }
             }
@@ -947,9 +980,9 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
             // GM_DEAD_ROWS: ... or no fill at all, where both readers of dQ_L can take the rows the head/loss launch does not assign as zeros: the dZ GEMM on the
             // fused kernel through gm_batch::d_dq_tab, the weight gradient on the three-piece split kernel (gm_wgrad_args::g_keep)
             if (fwd_only == 2 && l == L.n_gcn - 1 && fo == L.dims[L.n_gcn]) {
-                const bool dz_ok = l == 0 || (gm_gemm_split_ok(b->n_tiles, fo, fi) && fo >= 64 && fo <= 4096 && b->d_dq_tab);
-                if (dead_rows && split_ok && g.np != 2 && c.np != 2 && b->d_norm_c && dz_ok && gm_wgrad_gather_ok(b->n_chunks, fi, fo)) c.dq_centre = 1;
-                else { g.zero_out = c.bufA; c.dq_zeroed = 1; }
+                const bool dz_ok = l == 0 || dz_centre_ok(c, l);
+                if (dead_rows && split_ok && g.np != 2 && c.np != 2 && b->d_norm_c && dz_ok && gm_wgrad_gather_ok(b->n_chunks, fi, fo)) c.dq = GcnCtx::DQ_CENTRE;
+                else { g.zero_out = c.bufA; c.dq = GcnCtx::DQ_ZEROED; }
             }
             if (fuse) {
                 g.zside = c.Z[l]; g.ldz = fi;
@@ -960,11 +993,7 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
         }
         xin = c.H[l];
     }
-    if (skip_head) return GM_OK;
-    HeadK k = make_head(c, params, pstride);
-    hipLaunchKernelGGL(k_head_fwd, dim3((b->subs + 3) / 4), dim3(256), 0, st, k, logits);
-    GM_HIP(hipGetLastError());
-    return GM_OK;
+    return skip_head ? GM_OK : launch_head_fwd(c, params, pstride, logits, st);
 }
 
 static int gcn_backward_sparse(GcnCtx& c, const float* params, int64_t pstride, const float* dlogits, float* dparams, int64_t dstride, hipStream_t st, int skip_head);
@@ -979,13 +1008,10 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
     const int Lg = L.n_gcn;
     float* dQ = c.bufA; float* T = c.bufB;
     c.hold.n = 0;
-    const bool dq_centre = skip_head && c.dq_centre;      // dQ_L holds its centre rows only (head_loss); without skip_head it is filled right here
+    const bool dq_centre = skip_head && c.dq == GcnCtx::DQ_CENTRE;      // dQ_L holds its centre rows only (head_loss); without skip_head it is filled right here
     if (!skip_head) {
         GM_HIP(hipMemsetAsync(dQ, 0, sizeof(float) * b->rows * L.dims[Lg], st));
-        HeadK k = make_head(c, params, pstride);
-        hipLaunchKernelGGL(k_head_bwd, dim3(b->sets), dim3(256), 0, st, k, dlogits, dparams, dstride, dQ, (float*)nullptr);
-        GM_HIP(hipGetLastError());
-        if (k.dq_amax) c.dqv = true;
+        GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, dQ, nullptr, st));
     }
     for (int l = Lg - 1; l >= 0; --l) {
         const int fi = L.dims[l], fo = L.dims[l + 1];
@@ -1003,10 +1029,9 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
         if (l > 0) w.partial = c.partial_l[l];
         if (fi > fo) {
             // dY = A^T (norm * dQ) ; dW = (norm*X)^T dY ; db = colsum(dQ) ; dQ_prev = relu'(H_prev) * norm * (dY W^T)
-            gm_agg_args a{}; a.indptr = b->d_indptr_t; a.indices = b->d_indices_t; a.heavy = b->d_heavy[1]; a.n_heavy = b->n_heavy[1]; a.heavy_deg = b->heavy_deg; a.sched = b->d_sched[1]; a.sched_len = b->sched_len[1]; a.sched_win = b->sched_win; GM_TRY(gm_agg_hub(a, b, 1, st, c.hub_set)); a.x = dQ; a.ldx = fo; a.s_in = b->d_norm; a.e_w = b->d_enorm[1]; a.out = T; a.rows = b->rows; a.width = fo;
-            gm_prof_agg_begin(st, gm_aggregate_bytes(b, fo)); gm_prof_note(GM_PROF_AGG_STRICT, gm_aggregate_bytes(b, fo));
-            GM_TRY(gm_launch_aggregate(a, st));
-            gm_prof_agg_end(st);
+            gm_agg_args a; GM_TRY(batch_agg(c, 1, st, a));
+            a.x = dQ; a.ldx = fo; a.s_in = b->d_norm; a.e_w = b->d_enorm[1]; a.out = T; a.width = fo;
+            GM_TRY(launch_agg(a, gm_aggregate_bytes(b, fo), gm_aggregate_bytes(b, fo), st));
             w.A = Xprev; w.lda = fi; w.G = T; w.ldg = fo; w.Gb = dQ; w.ldgb = fo;
             GM_TRY(gm_launch_wgrad(w, st));
             if (l > 0) {
@@ -1028,7 +1053,7 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
             if (l > 0) {
                 gm_gemm_args g{}; g.A = dQ; g.lda = fo; g.C = T; g.ldc = fi; g.K = fo; g.N = fi;
                 g.row_scale = b->d_norm; g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows;
-                const bool use_split = c.Wsplit && gm_gemm_split_ok(b->n_tiles, fo, fi);
+                const bool use_split = dz_split_ok(c, l);
                 const bool use_wt = !use_split && c.WTl[l] && fi % 64 == 0 && fo % 16 == 0;
                 if (use_split) {
                     // B = W^T with W stored [fi][fo]: the planes are W's own rows (no transpose), K = fo, N = fi
@@ -1041,8 +1066,9 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
                     if (np == 2) { g.amax_out = c.amT(l); c.tv[l] = true; }
                     g.B = params + L.w_off[l]; g.b_stride = pstride; g.transB = 1;
                     // dQ_L with its centre rows only: the fused kernel's loader reads them through the batch's table (fma(0, 0, fma(x, 1, 0)) = x) and zeros for
-                    // every other row -- the same tile, bit for bit, as the plain launch over a zero-filled dQ
-                    if (dq_centre && l == Lg - 1) { g.fuse2 = b->d_dq_tab; g.zside = dQ; g.ldz = fo; }
+                    // every other row -- the same tile, bit for bit, as the plain launch over a zero-filled dQ.  (dz_centre_ok is what gcn_forward chose
+                    // DQ_CENTRE by, so it holds here whenever dq_centre does: the two ends of one contract, and the GM_REQUIRE below is its guard)
+                    if (dq_centre && l == Lg - 1 && dz_centre_ok(c, l)) { g.fuse2 = b->d_dq_tab; g.zside = dQ; g.ldz = fo; }
                 } else if (use_wt) {
                     // dZ = dQ @ W^T through the direct-to-LDS kernel on transposed weights: left there by the previous step's
                     // weight-gradient reduction (which wrote these very weights), else transposed now (T x 256 KB)
@@ -1071,11 +1097,10 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
             if (kn) { c.pd->valid[kn][l][0] = w.pl_fwd != nullptr; c.pd->valid[kn][l][1] = w.pl_dz != nullptr; }
             if (w.wt_next) { c.wt_of[l] = c.sgd.next; c.wt_stride[l] = c.sgd.next_stride; }
             if (l > 0) {
-                gm_agg_args a{}; a.indptr = b->d_indptr_t; a.indices = b->d_indices_t; a.heavy = b->d_heavy[1]; a.n_heavy = b->n_heavy[1]; a.heavy_deg = b->heavy_deg; a.sched = b->d_sched[1]; a.sched_len = b->sched_len[1]; a.sched_win = b->sched_win; GM_TRY(gm_agg_hub(a, b, 1, st, c.hub_set)); a.x = T; a.ldx = fi; a.s_out = b->d_norm; a.mask_h = maskprev; a.mask_b = maskbits;
-                a.out = dQ; a.rows = b->rows; a.width = fi;
-                gm_prof_agg_begin(st, gm_aggregate_bytes(b, fi)); gm_prof_note(GM_PROF_AGG_STRICT, gm_aggregate_bytes(b, fi));
-                GM_TRY(gm_launch_aggregate(a, st));
-                gm_prof_agg_end(st);
+                gm_agg_args a; GM_TRY(batch_agg(c, 1, st, a));
+                a.x = T; a.ldx = fi; a.s_out = b->d_norm; a.mask_h = maskprev; a.mask_b = maskbits;
+                a.out = dQ; a.width = fi;
+                GM_TRY(launch_agg(a, gm_aggregate_bytes(b, fi), gm_aggregate_bytes(b, fi), st));
             }
         }
     }
@@ -1094,11 +1119,7 @@ static bool sparse_bwd_ok(const gm_layout& L) {
 static int gcn_backward_sparse(GcnCtx& c, const float* params, int64_t pstride, const float* dlogits, float* dparams, int64_t dstride, hipStream_t st, int skip_head) {
     const gm_layout& L = c.L; const gm_batch* b = c.b;
     const int Lg = L.n_gcn, fiL = L.dims[Lg - 1], foL = L.dims[Lg];
-    if (!skip_head) {
-        HeadK k = make_head(c, params, pstride);
-        hipLaunchKernelGGL(k_head_bwd, dim3(b->sets), dim3(256), 0, st, k, dlogits, dparams, dstride, (float*)nullptr, c.cG2);
-        GM_HIP(hipGetLastError());
-    }
+    if (!skip_head) GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, nullptr, c.cG2, st));
     // dW_L = sum_k norm[c_k] Z_L[c_k]^T G2[k] ; db_L = sum_k G2[k]
     gm_wgrad_args w{}; w.A = c.Z[Lg - 1]; w.lda = fiL; w.K = fiL; w.a_row = b->d_crow; w.a_scale = b->d_cnorm; w.G = c.cG2; w.ldg = foL; w.N = foL;
     w.rows = b->n_c; w.chunks = b->d_c_chunks; w.n_chunks = b->n_c_chunks; w.set_chunk_off = b->d_c_set_chunk_off; w.sets = b->sets; w.partial = c.partial_c;
@@ -1139,10 +1160,7 @@ static int64_t cone_agg_bytes(int64_t n_dst, int64_t n_src, int64_t nnz, int wid
 }
 static int cone_launch_agg(const gm_agg_args& a, int64_t n_src, int64_t nnz, hipStream_t st) {
     const int64_t by = cone_agg_bytes(a.rows, n_src, nnz, a.width);
-    gm_prof_agg_begin(st, by); gm_prof_note(GM_PROF_AGG_STRICT, by);
-    const int rc = gm_launch_aggregate(a, st);
-    gm_prof_agg_end(st);
-    return rc;
+    return launch_agg(a, by, by, st);
 }
 static gm_agg_args cone_agg(const gm_cone* cn, const gm_cone_level& up, int transposed) {
     gm_agg_args a{};
@@ -1184,22 +1202,14 @@ static int cone_forward(GcnCtx& c, const float* params, int64_t pstride, float* 
         }
         xin = c.H[l];
     }
-    if (skip_head) return GM_OK;
-    HeadK k = make_head(c, params, pstride);
-    hipLaunchKernelGGL(k_head_fwd, dim3((b->subs + 3) / 4), dim3(256), 0, st, k, logits);
-    GM_HIP(hipGetLastError());
-    return GM_OK;
+    return skip_head ? GM_OK : launch_head_fwd(c, params, pstride, logits, st);
 }
 
 static int cone_backward(GcnCtx& c, const float* params, int64_t pstride, const float* dlogits, float* dparams, int64_t dstride, hipStream_t st, int skip_head) {
     const gm_layout& L = c.L; const gm_batch* b = c.b; const gm_cone* cn = c.cone;
     const int Lg = L.n_gcn;
     float* dQ = c.bufA; float* T = c.bufB;
-    if (!skip_head) {
-        HeadK k = make_head(c, params, pstride);
-        hipLaunchKernelGGL(k_head_bwd, dim3(b->sets), dim3(256), 0, st, k, dlogits, dparams, dstride, (float*)nullptr, dQ);   // dQ_L on the centre rows
-        GM_HIP(hipGetLastError());
-    }
+    if (!skip_head) GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, nullptr, dQ, st));   // dQ_L on the centre rows
     for (int l = Lg - 1; l >= 0; --l) {
         const gm_cone_level& lo = cn->lv[l]; const gm_cone_level& up = cn->lv[l + 1];
         const int fi = L.dims[l], fo = L.dims[l + 1];
@@ -1374,14 +1384,15 @@ static size_t proto_lds(int Ct, int n, int D, int nt = 256) {
     return sizeof(float) * ((size_t)Ct * D + (size_t)Ct * n + 2 * (size_t)nt + (a <= PROTO_A_MAX ? a : 0));
 }
 
-static int launch_proto_ragged(const gm_batch* b, const ProtoK& k, hipStream_t st);
-static int launch_proto(const gm_batch* b, ProtoK k, bool ragged, hipStream_t st) {
-    if (ragged) return launch_proto_ragged(b, k, st);
-    GM_TRY(gm_func_full_lds((const void*)k_proto<false>));
-    hipLaunchKernelGGL(k_proto<false>, dim3(b->sets), dim3(256), proto_lds(k.Ct, k.n, k.D), st, k);
+template <bool RGK>
+static int launch_proto_t(const gm_batch* b, const ProtoK& k, hipStream_t st) {
+    GM_TRY(gm_func_full_lds((const void*)k_proto<RGK>));
+    hipLaunchKernelGGL(k_proto<RGK>, dim3(b->sets), dim3(256), proto_lds(k.Ct, k.n, k.D), st, k);
     GM_HIP(hipGetLastError());
     return GM_OK;
 }
+static int launch_proto_ragged(const gm_batch* b, const ProtoK& k, hipStream_t st);
+static int launch_proto(const gm_batch* b, const ProtoK& k, bool ragged, hipStream_t st) { return ragged ? launch_proto_ragged(b, k, st) : launch_proto_t<false>(b, k, st); }
 
 // rows + tab of a ClassTables on the device (one allocation: [rows | tab]); freed by the caller with gm_dev_free
 static int upload_tables(const ClassTables& ct, int32_t** d_out, hipStream_t st) {
@@ -1456,8 +1467,22 @@ extern "C" int gm_head_loss_debug(int32_t enable, unsigned long long* out) {
 static unsigned long long* const g_head_dbg = nullptr;      // the product library carries no probe state
 #endif
 
-static int launch_head_loss_ragged(int nt, int sets, size_t lds, hipStream_t st, const HeadK& hk, float* logits, const ProtoK& pk, int bwd, float* dparams, int64_t dstride,
-                                   float* dQ, float* Gc, const SgdK& sg, int stage_h, int proto_floats);
+// One k_head_loss launch: everything but the instantiation
+struct HeadLossLaunch {
+    int sets; size_t lds; HeadK hk; float* logits; ProtoK pk; int bwd; float* dparams; int64_t dstride; float* dQ; float* Gc; SgdK sg; int stage_h, proto_floats;
+};
+template <int NT, bool RGK>
+static int launch_head_loss_t(const HeadLossLaunch& a, hipStream_t st, bool again = false) {      // again: the probe's repeat of a launch just made -- the launch alone
+    const auto k_head_loss_nt = k_head_loss<NT, RGK>;
+    if (!again) GM_TRY(gm_func_full_lds((const void*)k_head_loss_nt));
+    hipLaunchKernelGGL(k_head_loss_nt, dim3(a.sets), dim3(NT), a.lds, st, a.hk, a.logits, a.pk, a.bwd, a.dparams, a.dstride, a.dQ, a.Gc, a.sg, a.stage_h, a.proto_floats, 0, g_head_dbg);
+    return GM_OK;
+}
+template <bool RGK>
+static int launch_head_loss(int nt, const HeadLossLaunch& a, hipStream_t st) {
+    return nt == 256 ? launch_head_loss_t<256, RGK>(a, st) : nt == 512 ? launch_head_loss_t<512, RGK>(a, st) : launch_head_loss_t<1024, RGK>(a, st);
+}
+static int launch_head_loss_ragged(int nt, const HeadLossLaunch& a, hipStream_t st);
 // Head forward + loss (+ head backward) in one launch (k_head_loss) after a gcn_forward(..., skip_head = 1).  With
 // bwd != 0 the matching gcn_backward(..., skip_head = 1) continues from dQ_L / the compact G2 written here; c.sgd (if
 // set) makes the head's own parameters take their SGD step in the same launch.
@@ -1470,9 +1495,7 @@ static int head_loss(GcnCtx& c, const float* params, int64_t pstride, float* log
         else if (sparse && sparse_bwd_ok(L)) Gc = c.cG2;
         else {
             dQ = c.bufA;
-            if (c.dq_zeroed) c.dq_zeroed = 0;
-            else if (c.dq_centre) {}          // nobody reads the rows this launch does not assign
-            else GM_HIP(hipMemsetAsync(dQ, 0, sizeof(float) * b->rows * L.dims[L.n_gcn], st));
+            if (c.dq == GcnCtx::DQ_MEMSET) GM_HIP(hipMemsetAsync(dQ, 0, sizeof(float) * b->rows * L.dims[L.n_gcn], st));      // (DQ_CENTRE: nobody reads the rows this launch does not assign)
         }
     }
     HeadK hk = make_head(c, params, pstride);
@@ -1489,19 +1512,14 @@ static int head_loss(GcnCtx& c, const float* params, int64_t pstride, float* log
     // meta-step, 4-task arxiv shard 4.59 -> 4.86; 512: 1.71 / 4.67).
     int nt = gm_knob().head_threads;
     if (nt != 256 && nt != 512) nt = 1024;
-    const SgdK sg = bwd ? c.sgd : SgdK{nullptr, 0, nullptr, 0, 0.f};
+    const HeadLossLaunch hl{b->sets, lds, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, bwd ? c.sgd : SgdK{nullptr, 0, nullptr, 0, 0.f}, stage_h, (int)(proto_bytes / sizeof(float))};
     gm_prof_begin(GM_PROF_HEAD, st, b->subs);
-    if (!ragged) {      // (first: the kernels every launch without ragged sets runs stay where they were in the code object)
-        if (nt == 256) { GM_TRY(gm_func_full_lds((const void*)k_head_loss<256>)); hipLaunchKernelGGL(k_head_loss<256>, dim3(b->sets), dim3(256), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, (int)(proto_bytes / sizeof(float)), 0, g_head_dbg); }
-        else if (nt == 512) { GM_TRY(gm_func_full_lds((const void*)k_head_loss<512>)); hipLaunchKernelGGL(k_head_loss<512>, dim3(b->sets), dim3(512), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, (int)(proto_bytes / sizeof(float)), 0, g_head_dbg); }
-        else { GM_TRY(gm_func_full_lds((const void*)k_head_loss<1024>)); hipLaunchKernelGGL(k_head_loss<1024>, dim3(b->sets), dim3(1024), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, (int)(proto_bytes / sizeof(float)), 0, g_head_dbg); }
-    } else GM_TRY(launch_head_loss_ragged(nt, b->sets, lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, (int)(proto_bytes / sizeof(float))));
+    if (!ragged) GM_TRY(launch_head_loss<false>(nt, hl, st));      // (first: the kernels every launch without ragged sets runs stay where they were in the code object)
+    else GM_TRY(launch_head_loss_ragged(nt, hl, st));
 #ifdef GM_PROBES
-    {   // tools/head_loss_probe.py: the same launch again -- it is idempotent -- to see what a warm instruction cache / warm L2 is worth
-        static const int twice = getenv("GM_HEAD_TWICE") ? atoi(getenv("GM_HEAD_TWICE")) : 0;
-        if (twice && nt != 256 && nt != 512 && !ragged)
-            hipLaunchKernelGGL(k_head_loss<1024>, dim3(b->sets), dim3(1024), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, (int)(proto_bytes / sizeof(float)), 0, g_head_dbg);
-    }
+    // tools/head_loss_probe.py: the same launch again -- it is idempotent -- to see what a warm instruction cache / warm L2 is worth
+    static const int twice = getenv("GM_HEAD_TWICE") ? atoi(getenv("GM_HEAD_TWICE")) : 0;
+    if (twice && nt == 1024 && !ragged) (void)launch_head_loss_t<1024, false>(hl, st, true);
 #endif
     GM_HIP(hipGetLastError());
     gm_prof_end(GM_PROF_HEAD, st);
@@ -1512,19 +1530,8 @@ static int head_loss(GcnCtx& c, const float* params, int64_t pstride, float* log
 // ================================================================================ ragged-task mode: kernels of launches that hold ragged sets
 // Instantiated and defined HERE, behind everything a launch without ragged sets runs: those kernels keep the place in the code object they had before the mode existed
 // (k_head_loss is pure latency; with the ragged instantiations emitted ahead of it, the same instructions measured 0.1-0.3 us per launch slower at the FirstMM shape).
-static int launch_proto_ragged(const gm_batch* b, const ProtoK& k, hipStream_t st) {
-    GM_TRY(gm_func_full_lds((const void*)k_proto<true>));
-    hipLaunchKernelGGL(k_proto<true>, dim3(b->sets), dim3(256), proto_lds(k.Ct, k.n, k.D), st, k);
-    GM_HIP(hipGetLastError());
-    return GM_OK;
-}
-static int launch_head_loss_ragged(int nt, int sets, size_t lds, hipStream_t st, const HeadK& hk, float* logits, const ProtoK& pk, int bwd, float* dparams, int64_t dstride,
-                                   float* dQ, float* Gc, const SgdK& sg, int stage_h, int proto_floats) {
-    if (nt == 256) { GM_TRY(gm_func_full_lds((const void*)k_head_loss<256, true>)); hipLaunchKernelGGL((k_head_loss<256, true>), dim3(sets), dim3(256), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, proto_floats, 0, g_head_dbg); }
-    else if (nt == 512) { GM_TRY(gm_func_full_lds((const void*)k_head_loss<512, true>)); hipLaunchKernelGGL((k_head_loss<512, true>), dim3(sets), dim3(512), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, proto_floats, 0, g_head_dbg); }
-    else { GM_TRY(gm_func_full_lds((const void*)k_head_loss<1024, true>)); hipLaunchKernelGGL((k_head_loss<1024, true>), dim3(sets), dim3(1024), lds, st, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, sg, stage_h, proto_floats, 0, g_head_dbg); }
-    return GM_OK;
-}
+static int launch_proto_ragged(const gm_batch* b, const ProtoK& k, hipStream_t st) { return launch_proto_t<true>(b, k, st); }
+static int launch_head_loss_ragged(int nt, const HeadLossLaunch& a, hipStream_t st) { return launch_head_loss<true>(nt, a, st); }
 // k_protos_to_dlogits for a launch with ragged sets ([class starts | class rows], see ProtoK): prototype_c = mean of the class's own row count
 __global__ void k_protos_to_dlogits_ragged(const float* dprotos, const int32_t* rows, const int32_t* tab, int CtMax, int D, float* dlogits) {
     const int set = blockIdx.x, Ct = tab[set * 3 + 1], n = tab[set * 3 + 2];
@@ -1623,22 +1630,39 @@ static StageRing& stage_ring() {
     if (hipGetDevice(&dev) != hipSuccess) (void)hipGetLastError();
     return m[dev];
 }
+// `bytes` of host data to dst without a host synchronisation: a ring slot, filled by fill(slot memory), ONE asynchronous copy on st
+template <class Fill>
+static int stage_to_device(void* dst, size_t bytes, hipStream_t st, Fill&& fill) {
+    void* h = nullptr; int slot = 0;
+    StageRing& ring = stage_ring();
+    GM_TRY(ring.acquire(bytes, &h, &slot));
+    fill(h);
+    GM_HIP(hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, st));
+    return ring.release_after(slot, st);
+}
 
-struct MetaPlan {
+// The support chain's part of a plan: gm_meta_step and gm_meta_adapt run the same launches on it (support_head / support_bwd below)
+struct SupportPlan {
     gm_layout L; int T, K; int64_t Pp;       // Pp = P padded to 64 floats: per-task weight vectors stay 16-B aligned
-    GcnCtx S, Q, Q2;                         // Q2: second query context (own activations) when two query streams are used
-    int nq_ctx;
-    float *logit_q2;
-    float *fw, *g, *gq, *gp, *logit_s, *logit_q, *dlog_s, *dlog_q, *protos, *dprotos, *ls, *as_, *lq, *aq, *theta_p;
+    GcnCtx S;
+    float *fw, *g, *logit_s, *dlog_s, *protos, *ls, *as_, *theta_p;
     PlaneDir pd;
     int64_t TP, proto_sz;               // fw holds K vectors-of-tasks fw_1..fw_K (distinct buffers: the support chain may run ahead)
-    int32_t *rows_s, *rows_q, *tab_s, *tab_q;     // class tables: one contiguous block [rows_s | rows_q | tab_s | tab_q | featb_s | featb_q]
+    int32_t *rows_s, *tab_s;            // support class tables
+    int64_t cap_s;                      // ints held by rows_s: spt->subs; ragged-task mode: + the class starts of ragged sets (at most spt->subs + T)
+    int Ct, ns, uni_s = 0;              // uni_s: class layout uniform over the tasks (ProtoK::uniform)
+    int qmax_s = 0;                     // ragged-task mode: largest scored-row count of a ragged set (0: none, the usual kernels)
+    float* fw_k(int k) const { return fw + (int64_t)(k - 1) * TP; }      // fw_k, k = 1..K
+};
+struct MetaPlan : SupportPlan {
+    GcnCtx Q, Q2;                            // Q2: second query context (own activations) when two query streams are used
+    int nq_ctx; float *logit_q2;
+    float *gq, *gp, *logit_q, *dlog_q, *dprotos, *lq, *aq;
+    int32_t *rows_q, *tab_q;                      // class tables: one contiguous block [rows_s | rows_q | tab_s | tab_q | featb_s | featb_q]
     unsigned *featb_s, *featb_q;                  // [T] each: per-task bound of the layer-1 operand (fp32 bit patterns; rides in the class-table copy)
     unsigned* viol;                               // the step's violation word (gm_bound.h), zeroed with the bound slots; NULL without two-piece kernels
-    int Ct, ns, nq;
-    int uni_s = 0, uni_q = 0;                     // class layouts uniform over the tasks (ProtoK::uniform)
-    int qmax_s = 0, qmax_q = 0;                   // ragged-task mode: largest scored-row count of a ragged set (0: none, the usual kernels)
-    int64_t cap_s, cap_q;                         // ints held by rows_s / rows_q
+    int nq, uni_q = 0, qmax_q = 0;                // as Ct / ns, uni_s, qmax_s of the support side
+    int64_t cap_q;                                // ints held by rows_q
     unsigned* bound_ws; int64_t bound_words;      // gm_bound.h slots of this step ([S passes | Q passes | weights]), zeroed by ONE memset; NULL: three-piece kernels
 };
 
@@ -1663,20 +1687,63 @@ static void plan_planes(PlaneDir& pd, const gm_layout& L, int T, int K, float* f
     }
 }
 
+// A fresh context on batch b; under hp->cone with the batch's receptive-field tables (built on first use, cached in the batch)
+static int plan_ctx(GcnCtx& c, const gm_batch* b, const gm_layout& L, const gm_hparams_t* hp) {
+    c = GcnCtx{}; c.b = b; c.L = L;
+    if (hp->cone) {
+        const gm_cone* cn = nullptr;
+        GM_TRY(gm_batch_cone(b, L.n_gcn, b->stream, &cn));
+        if (cn->ok) c.cone = cn;         // else: a self pair among the centres -> dense schedule
+    }
+    return GM_OK;
+}
+// What every plan starts with: the layout of the model the kernels run, Pp, the context of its (first) batch
+static int plan_prologue(const gm_model_t* m, const gm_hparams_t* hp, const gm_batch* b, gm_layout& L, int64_t& Pp, GcnCtx& c) {
+    GM_TRY(gm_make_layout(m, &L));
+    Pp = (L.P + 63) / 64 * 64;
+    return plan_ctx(c, b, L, hp);
+}
+static int support_prologue(SupportPlan& p, const gm_batch* spt, const gm_model_t* m, const gm_hparams_t* hp) {
+    GM_TRY(plan_prologue(m, hp, spt, p.L, p.Pp, p.S));
+    p.S.is_support = true;
+    p.T = spt->sets; p.K = hp->update_step; p.TP = (int64_t)p.T * p.Pp; p.proto_sz = (int64_t)p.T * 256 * p.L.n_out;
+    return GM_OK;
+}
+
+// theta in the caller's layout (P floats) -> the kernels' (internal_model) in p.theta_p; *theta moves there
+static int pad_theta(const SupportPlan& p, const float** theta, int64_t P, int64_t cut, int64_t shift, hipStream_t st) {
+    if (!shift) return GM_OK;
+    hipLaunchKernelGGL(k_pad_params, dim3((int)std::min<int64_t>(512, (p.L.P + 255) / 256)), dim3(256), 0, st, *theta, P, cut, shift, p.theta_p);
+    GM_HIP(hipGetLastError());
+    *theta = p.theta_p;
+    return GM_OK;
+}
+
+// One support step (meta.py:122-126,145-151) on st, in two halves -- gm_meta_step enqueues query work between them:
+//   support_head: forward -> [head + proto_loss_spt + head backward, one launch]; step k's losses go to column k, its prototypes to `protos`
+//   support_bwd:  backward, with the SGD step w_next = w - lr * grad written by the kernels that produce each gradient
+// w_next == NULL: the forward and the prototypes only, no support_bwd follows (gm_meta_adapt with K = 0).
+static int support_head(SupportPlan& p, const gm_hparams_t* hp, int k, const float* w, int64_t wstride, float* w_next, float* protos, hipStream_t st) {
+    const int bwd = w_next ? 1 : 0, sparse = hp->sparse_bwd;
+    GM_TRY(gcn_forward(p.S, w, wstride, p.logit_s, st, hp->hoist_z1, 1, (sparse && sparse_bwd_ok(p.L)) ? 0 : 2));
+    if (bwd) p.S.sgd = SgdK{w, wstride, w_next, p.Pp, hp->update_lr};
+    ProtoK pk{p.logit_s, p.L.n_out, p.rows_s, p.Ct, p.ns, 0, nullptr, protos, p.ls, p.as_, p.K + 1, k, bwd ? p.dlog_s : nullptr, nullptr, 0, p.tab_s, p.uni_s};
+    return head_loss(p.S, w, wstride, p.logit_s, pk, bwd, p.g, p.Pp, sparse, st, p.qmax_s != 0);
+}
+static int support_bwd(SupportPlan& p, const gm_hparams_t* hp, const float* w, int64_t wstride, hipStream_t st) {
+    GM_TRY(gcn_backward(p.S, w, wstride, p.dlog_s, p.g, p.Pp, st, hp->sparse_bwd, 1));
+    p.S.sgd = SgdK{nullptr, 0, nullptr, 0, 0.f};
+    return GM_OK;
+}
+
 static int meta_plan(MetaPlan& p, const gm_batch* spt, const gm_batch* qry, const gm_model_t* m, const gm_hparams_t* hp, void* ws, int64_t ws_bytes,
                      int Ct, int ns, int nq, int64_t* need) {
-    GM_TRY(gm_make_layout(m, &p.L));
-    p.T = spt->sets; p.K = hp->update_step; p.Pp = (p.L.P + 63) / 64 * 64;
-    p.S = GcnCtx{}; p.Q = GcnCtx{}; p.Q2 = GcnCtx{}; p.S.is_support = true; p.S.b = spt; p.Q.b = qry; p.Q2.b = qry; p.S.L = p.L; p.Q.L = p.L; p.Q2.L = p.L;
-    if (hp->cone) {                      // receptive-field tables: built on first use, cached in the batch
-        const gm_cone *cs = nullptr, *cq = nullptr;
-        GM_TRY(gm_batch_cone(spt, p.L.n_gcn, spt->stream, &cs));
-        GM_TRY(gm_batch_cone(qry, p.L.n_gcn, qry->stream, &cq));
-        if (cs->ok && cq->ok) { p.S.cone = cs; p.Q.cone = cq; p.Q2.cone = cq; }      // else: a self pair among the centres -> dense schedule
-    }
+    GM_TRY(support_prologue(p, spt, m, hp));
+    GM_TRY(plan_ctx(p.Q, qry, p.L, hp));
+    if (!p.S.cone || !p.Q.cone) p.S.cone = p.Q.cone = nullptr;      // one schedule for the whole step
+    p.Q2 = p.Q;
     Carver cv(ws, ws_bytes);
-    const int64_t TP = (int64_t)p.T * p.Pp; const int C = p.L.n_out; const int K1 = p.K + 1;
-    p.TP = TP; p.proto_sz = (int64_t)p.T * 256 * C;
+    const int64_t TP = p.TP; const int C = p.L.n_out; const int K1 = p.K + 1;
     p.theta_p = cv.take<float>(p.Pp);
     p.fw = cv.take<float>(TP * p.K); p.g = cv.take<float>(TP); p.gq = cv.take<float>(TP); p.gp = cv.take<float>(TP);
     p.logit_s = cv.take<float>((int64_t)spt->subs * C); p.logit_q = cv.take<float>((int64_t)qry->subs * C);
@@ -1773,16 +1840,10 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
     p.qmax_s = cs.qmax; p.qmax_q = cq.qmax;
     GM_REQUIRE((int64_t)cs.rows.size() <= p.cap_s && (int64_t)cq.rows.size() <= p.cap_q, GM_EINVAL, "meta_step: class tables outgrew the workspace plan");
     p.S.pd = p.Q.pd = p.Q2.pd = p.pd.base ? &p.pd : nullptr;
-    if (shift) {
-        hipLaunchKernelGGL(k_pad_params, dim3((int)std::min<int64_t>(512, (L.P + 255) / 256)), dim3(256), 0, st, theta, Lu.P, cut, shift, p.theta_p);
-        GM_HIP(hipGetLastError());
-        theta = p.theta_p;
-    }
-    {   // class tables -> pinned staging -> ONE asynchronous copy (no host synchronisation in the meta-step)
-        const size_t n_rows = (size_t)(p.cap_s + p.cap_q), n_tab = n_rows + 8 * (size_t)T;
-        void* h = nullptr; int slot = 0;
-        StageRing& ring = stage_ring();
-        GM_TRY(ring.acquire(4 * n_tab, &h, &slot));
+    GM_TRY(pad_theta(p, &theta, Lu.P, cut, shift, st));
+    // class tables -> pinned staging -> ONE asynchronous copy (no host synchronisation in the meta-step)
+    const size_t n_rows = (size_t)(p.cap_s + p.cap_q), n_tab = n_rows + 8 * (size_t)T;
+    GM_TRY(stage_to_device(p.rows_s, 4 * n_tab, st, [&](void* h) {
         int32_t* hp32 = (int32_t*)h;
         memset(hp32, 0, 4 * n_tab);
         memcpy(hp32, cs.rows.data(), 4 * cs.rows.size());
@@ -1814,9 +1875,7 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
                 p.pd.wam = nullptr; p.pd.viol = nullptr; p.viol = nullptr; p.bound_ws = nullptr;
             } else { p.S.feat_bound = p.featb_s; p.Q.feat_bound = p.Q2.feat_bound = p.featb_q; }
         }
-        GM_HIP(hipMemcpyAsync(p.rows_s, h, 4 * n_tab, hipMemcpyHostToDevice, st));
-        GM_TRY(ring.release_after(slot, st));
-    }
+    }));
     if (p.bound_ws) {
         GM_TRY(gm_batch_gains(spt, st)); GM_TRY(gm_batch_gains(qry, st));      // (computed once per batch, at its first two-piece step)
         // bound slots of this step: zero (the producers use atomicMax), then the maxima of theta's weight matrices (slot k = 0)
@@ -1848,24 +1907,8 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
         if (two_q) wait(sq2, e_in);
     }
 
-    auto fw = [&](int k) -> float* { return p.fw + (int64_t)(k - 1) * p.TP; };       // fw_k, k = 1..K
     auto protos = [&](int k) -> float* { return p.protos + (int64_t)k * p.proto_sz; };   // prototypes of support step k
     const int hoist = hp->hoist_z1, sparse = hp->sparse_bwd;
-    const SgdK no_sgd{nullptr, 0, nullptr, 0, 0.f};
-    // One support step (meta.py:122-126,145-151): forward -> [head + proto_loss_spt + head backward, one launch] -> backward,
-    // with the SGD step w_next = w - lr * grad written by the kernels that produce each gradient.
-    auto spt_step = [&](int k, const float* w, int64_t wstride, float* w_next) -> int {
-        GM_TRY(gcn_forward(p.S, w, wstride, p.logit_s, st, hoist, 1, (sparse && sparse_bwd_ok(p.L)) ? 0 : 2));
-        p.S.sgd = SgdK{w, wstride, w_next, Pp, hp->update_lr};
-        ProtoK pk{p.logit_s, C, p.rows_s, Ct, ns, 0, nullptr, protos(k), p.ls, p.as_, K1, k, p.dlog_s, nullptr, 0, p.tab_s, p.uni_s};
-        GM_TRY(head_loss(p.S, w, wstride, p.logit_s, pk, 1, p.g, Pp, sparse, st, p.qmax_s != 0));
-        return GM_OK;
-    };
-    auto spt_step_bwd = [&](const float* w, int64_t wstride) -> int {
-        GM_TRY(gcn_backward(p.S, w, wstride, p.dlog_s, p.g, Pp, st, sparse, 1));
-        p.S.sgd = no_sgd;
-        return GM_OK;
-    };
     // One query evaluation (meta.py:129-141,152-154): forward on sq, then head + proto_loss_qry (+ head backward when the
     // meta-gradient is wanted) once the prototypes / weights it needs are ready.
     // Evaluation j (j = 0: theta, j >= 1: fw_j) runs in query context j % 2 on that context's stream when two query streams are used.
@@ -1887,36 +1930,36 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
     // (Where the support chain is the longer one -- small query batches: the FirstMM shape lost 2.5 % -- its launches keep the lead.)
     const bool query_first = qry->rows >= 100000;
     if (query_first) GM_TRY(qry_fwd(0, theta, 0, 1));
-    GM_TRY(spt_step(0, theta, 0, fw(1)));
+    GM_TRY(support_head(p, hp, 0, theta, 0, p.fw_k(1), protos(0), st));
     hipEvent_t e_proto0 = signal(st);
     if (!query_first) GM_TRY(qry_fwd(0, theta, 0, 1));
     wait(q_str(0), e_proto0);
     GM_TRY(qry_loss(0, theta, 0, 0, 0, false));
-    GM_TRY(spt_step_bwd(theta, 0));
+    GM_TRY(support_bwd(p, hp, theta, 0, st));
     hipEvent_t e_fw = signal(st);                          // fw_1 ready (and, being later on st, the prototypes of step 0)
     wait(q_str(1), e_fw);
-    GM_TRY(qry_fwd(1, fw(1), Pp, 1));
-    GM_TRY(qry_loss(1, fw(1), Pp, 1, 0, false));
+    GM_TRY(qry_fwd(1, p.fw_k(1), Pp, 1));
+    GM_TRY(qry_loss(1, p.fw_k(1), Pp, 1, 0, false));
     bool have_grad = false;
     for (int k = 1; k < K; ++k) {            // meta.py:143-157
-        GM_TRY(spt_step(k, fw(k), Pp, fw(k + 1)));
-        GM_TRY(spt_step_bwd(fw(k), Pp));
+        GM_TRY(support_head(p, hp, k, p.fw_k(k), Pp, p.fw_k(k + 1), protos(k), st));
+        GM_TRY(support_bwd(p, hp, p.fw_k(k), Pp, st));
         e_fw = signal(st);                                 // fw_{k+1} and the prototypes of step k are ready
         const int j = k + 1;
         wait(q_str(j), e_fw);
         const bool last = hp->need_meta_grad && k == K - 1;
-        GM_TRY(qry_fwd(j, fw(k + 1), Pp, last ? ((sparse && sparse_bwd_ok(p.L)) ? 0 : 2) : 1));       // only the last evaluation is differentiated
-        GM_TRY(qry_loss(j, fw(k + 1), Pp, k + 1, k, last));
+        GM_TRY(qry_fwd(j, p.fw_k(k + 1), Pp, last ? ((sparse && sparse_bwd_ok(p.L)) ? 0 : 2) : 1));       // only the last evaluation is differentiated
+        GM_TRY(qry_loss(j, p.fw_k(k + 1), Pp, k + 1, k, last));
         if (last) {
             // first-order meta-gradient (no create_graph anywhere, meta.py:125,149): d L_q / d fw_K through the
             // query forward (on its query stream) plus d L_q / d fw_{K-1} through the prototypes of the last support forward (on st).
             hipEvent_t e_dp = signal(q_str(j));            // dprotos ready
-            GM_TRY(gcn_backward(q_ctx(j), fw(k + 1), Pp, p.dlog_q, p.gq, Pp, q_str(j), sparse, 1));
+            GM_TRY(gcn_backward(q_ctx(j), p.fw_k(k + 1), Pp, p.dlog_q, p.gq, Pp, q_str(j), sparse, 1));
             wait(st, e_dp);
             GM_HIP(hipMemsetAsync(p.dlog_s, 0, sizeof(float) * spt->subs * C, st));
             if (p.qmax_s) hipLaunchKernelGGL(k_protos_to_dlogits_ragged, dim3(T), dim3(256), 0, st, p.dprotos, p.rows_s, p.tab_s, Ct, C, p.dlog_s);
             else hipLaunchKernelGGL(k_protos_to_dlogits, dim3(T), dim3(256), 0, st, p.dprotos, p.rows_s, p.tab_s, Ct, C, p.dlog_s);
-            GM_TRY(gcn_backward(p.S, fw(k), Pp, p.dlog_s, p.gp, Pp, st, sparse));
+            GM_TRY(gcn_backward(p.S, p.fw_k(k), Pp, p.dlog_s, p.gp, Pp, st, sparse));
             have_grad = true;
         }
     }
@@ -1931,37 +1974,20 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
 }
 
 // ================================================================================ adaptation and prediction (beyond the reference)
-// gm_meta_adapt is the support chain of gm_meta_step alone (the same launches on the same context layout: forward -> k_head_loss -> backward with
+// gm_meta_adapt is the support chain of gm_meta_step alone (support_head / support_bwd on a SupportPlan of its own: forward -> k_head_loss -> backward with
 // the fused SGD, K times); gm_proto_predict is one query forward at per-set parameters followed by k_head_predict.  Both use the three-piece split
 // kernels (no bound slots).
-struct AdaptPlan {
-    gm_layout L; int T, K; int64_t Pp, TP, proto_sz;
-    GcnCtx S;
-    PlaneDir pd;
-    float *theta_p, *fw, *g, *logit_s, *dlog_s, *protos, *ls, *as_;
-    int32_t *rows_s, *tab_s;                  // class tables, one block [rows_s (cap_s) | tab_s (3T)]
-    int64_t cap_s;                            // spt->subs; ragged-task mode: + the class starts of ragged sets (at most spt->subs + T)
-};
-
-static int adapt_plan(AdaptPlan& p, const gm_batch* spt, const gm_model_t* m, const gm_hparams_t* hp, void* ws, int64_t ws_bytes, int64_t* need) {
-    GM_TRY(gm_make_layout(m, &p.L));
-    p.T = spt->sets; p.K = hp->update_step; p.Pp = (p.L.P + 63) / 64 * 64;
-    p.S = GcnCtx{}; p.S.is_support = true; p.S.b = spt; p.S.L = p.L;
-    if (hp->cone) {
-        const gm_cone* cs = nullptr;
-        GM_TRY(gm_batch_cone(spt, p.L.n_gcn, spt->stream, &cs));
-        if (cs->ok) p.S.cone = cs;
-    }
+static int adapt_plan(SupportPlan& p, const gm_batch* spt, const gm_model_t* m, const gm_hparams_t* hp, void* ws, int64_t ws_bytes, int64_t* need) {
+    GM_TRY(support_prologue(p, spt, m, hp));
     Carver cv(ws, ws_bytes);
     const int C = p.L.n_out, K1 = p.K + 1;
-    p.TP = (int64_t)p.T * p.Pp; p.proto_sz = (int64_t)p.T * 256 * C;
     p.theta_p = cv.take<float>(p.Pp);
     p.fw = cv.take<float>(p.TP * p.K); p.g = cv.take<float>(p.TP);
     p.logit_s = cv.take<float>((int64_t)spt->subs * C); p.dlog_s = cv.take<float>((int64_t)spt->subs * C);
     p.protos = cv.take<float>(p.proto_sz);                      // every step overwrites them: the last support step's are the result
     p.ls = cv.take<float>((int64_t)p.T * K1); p.as_ = cv.take<float>((int64_t)p.T * K1);
     p.cap_s = spt->subs + (g_ragged ? (int64_t)spt->subs + p.T : 0);
-    p.rows_s = cv.take<int32_t>(p.cap_s + 3 * (int64_t)p.T);
+    p.rows_s = cv.take<int32_t>(p.cap_s + 3 * (int64_t)p.T);      // one block [rows_s (cap_s) | tab_s (3T)]
     p.tab_s = p.rows_s ? p.rows_s + p.cap_s : nullptr;
     gcn_carve(p.S, cv);
     plan_planes(p.pd, p.L, p.T, p.K, p.fw, p.TP, !p.S.cone, cv);
@@ -1972,7 +1998,7 @@ static int adapt_plan(AdaptPlan& p, const gm_batch* spt, const gm_model_t* m, co
 
 extern "C" int64_t gm_adapt_ws_bytes(const gm_batch_t* spt, const gm_model_t* m, const gm_hparams_t* hp) {
     if (!spt || !m || !hp || hp->update_step < 0) return -1;
-    AdaptPlan p; int64_t need = 0, cut, shift;
+    SupportPlan p; int64_t need = 0, cut, shift;
     const gm_model_t mp = internal_model(m, spt->store, &cut, &shift);
     if (adapt_plan(p, spt, &mp, hp, nullptr, 0, &need) != GM_OK) return -1;
     return need;
@@ -1993,50 +2019,32 @@ extern "C" int gm_meta_adapt(const gm_batch_t* spt, const int32_t* y_spt, const 
     ClassTables cs;
     GM_TRY(class_tables(spt, y_spt, hp->k_spt, cs));
     GM_REQUIRE(c_task >= cs.Ct, GM_EINVAL, "meta_adapt: c_task=%d but a support set has %d classes", c_task, cs.Ct);
-    const int Ct = cs.Ct, ns = cs.n;
-    AdaptPlan p;
+    SupportPlan p;
     int64_t cut = 0, shift = 0;
     const gm_model_t mp = internal_model(m, spt->store, &cut, &shift);
     GM_TRY(adapt_plan(p, spt, &mp, hp, ws, ws_bytes, nullptr));
-    const gm_layout& L = p.L; const int T = p.T, C = L.n_out, K1 = K + 1; const int64_t Pp = p.Pp;
+    const int T = p.T, C = p.L.n_out; const int64_t Pp = p.Pp;
+    p.Ct = cs.Ct; p.ns = cs.n; p.uni_s = cs.uniform ? 1 : 0; p.qmax_s = cs.qmax;
     p.S.pd = p.pd.base ? &p.pd : nullptr;
-    if (shift) {
-        hipLaunchKernelGGL(k_pad_params, dim3((int)std::min<int64_t>(512, (L.P + 255) / 256)), dim3(256), 0, st, theta, Lu.P, cut, shift, p.theta_p);
-        GM_HIP(hipGetLastError());
-        theta = p.theta_p;
-    }
-    {   // support class tables -> pinned staging -> one asynchronous copy
-        const size_t n_tab = (size_t)p.cap_s + 3 * (size_t)T;
-        void* h = nullptr; int slot = 0;
-        StageRing& ring = stage_ring();
-        GM_TRY(ring.acquire(4 * n_tab, &h, &slot));
+    GM_TRY(pad_theta(p, &theta, Lu.P, cut, shift, st));
+    // support class tables -> pinned staging -> one asynchronous copy
+    const size_t n_tab = (size_t)p.cap_s + 3 * (size_t)T;
+    GM_TRY(stage_to_device(p.rows_s, 4 * n_tab, st, [&](void* h) {
         int32_t* hp32 = (int32_t*)h;
         memset(hp32, 0, 4 * n_tab);
         memcpy(hp32, cs.rows.data(), 4 * cs.rows.size());
         memcpy(hp32 + p.cap_s, cs.tab.data(), 4 * cs.tab.size());
-        GM_HIP(hipMemcpyAsync(p.rows_s, h, 4 * n_tab, hipMemcpyHostToDevice, st));
-        GM_TRY(ring.release_after(slot, st));
-    }
-    auto fw = [&](int k) -> float* { return p.fw + (int64_t)(k - 1) * p.TP; };       // fw_k, k = 1..K
-    const int hoist = hp->hoist_z1, sparse = hp->sparse_bwd;
-    const int fwd_mode = (sparse && sparse_bwd_ok(p.L)) ? 0 : 2;
-    // gm_meta_step's spt_step / spt_step_bwd (meta.py:122-126,145-151); K = 0: the forward and the prototypes only
+    }));
+    // gm_meta_step's support chain (meta.py:122-126,145-151); K = 0: the forward and the prototypes only
     for (int k = 0; k < std::max(K, 1); ++k) {
-        const float* w = k ? fw(k) : theta;
+        const float* w = k ? p.fw_k(k) : theta;
         const int64_t wstride = k ? Pp : 0;
-        const bool bwd = K > 0;
-        GM_TRY(gcn_forward(p.S, w, wstride, p.logit_s, st, hoist, 1, fwd_mode));
-        if (bwd) p.S.sgd = SgdK{w, wstride, fw(k + 1), Pp, hp->update_lr};
-        ProtoK pk{p.logit_s, C, p.rows_s, Ct, ns, 0, nullptr, p.protos, p.ls, p.as_, K1, k, bwd ? p.dlog_s : nullptr, nullptr, 0, p.tab_s, cs.uniform ? 1 : 0};
-        GM_TRY(head_loss(p.S, w, wstride, p.logit_s, pk, bwd ? 1 : 0, p.g, Pp, sparse, st, cs.qmax != 0));
-        if (bwd) {
-            GM_TRY(gcn_backward(p.S, w, wstride, p.dlog_s, p.g, Pp, st, sparse, 1));
-            p.S.sgd = SgdK{nullptr, 0, nullptr, 0, 0.f};
-        }
+        GM_TRY(support_head(p, hp, k, w, wstride, K > 0 ? p.fw_k(k + 1) : nullptr, p.protos, st));
+        if (K > 0) GM_TRY(support_bwd(p, hp, w, wstride, st));
     }
     const int64_t big = std::max<int64_t>(Lu.P, (int64_t)c_task * C);
-    hipLaunchKernelGGL(k_adapt_out, dim3((int)std::min<int64_t>(256, (big + 255) / 256), T), dim3(256), 0, st, K ? fw(K) : theta, K ? Pp : 0, Lu.P, cut, shift,
-                       fw_out, fw_stride, p.protos, Ct, p.tab_s, c_task, C, protos_out);
+    hipLaunchKernelGGL(k_adapt_out, dim3((int)std::min<int64_t>(256, (big + 255) / 256), T), dim3(256), 0, st, K ? p.fw_k(K) : theta, K ? Pp : 0, Lu.P, cut, shift,
+                       fw_out, fw_stride, p.protos, p.Ct, p.tab_s, c_task, C, protos_out);
     GM_HIP(hipGetLastError());
     gm_batch_mark_use(spt, st);
     return GM_OK;
@@ -2050,14 +2058,7 @@ struct PredictPlan {
 };
 
 static int predict_plan(PredictPlan& p, const gm_batch* qry, const gm_model_t* m, const gm_hparams_t* hp, bool own_logits, void* ws, int64_t ws_bytes, int64_t* need) {
-    GM_TRY(gm_make_layout(m, &p.L));
-    p.Pp = (p.L.P + 63) / 64 * 64;
-    p.Q = GcnCtx{}; p.Q.b = qry; p.Q.L = p.L;
-    if (hp->cone) {
-        const gm_cone* cq = nullptr;
-        GM_TRY(gm_batch_cone(qry, p.L.n_gcn, qry->stream, &cq));
-        if (cq->ok) p.Q.cone = cq;
-    }
+    GM_TRY(plan_prologue(m, hp, qry, p.L, p.Pp, p.Q));
     Carver cv(ws, ws_bytes);
     p.params_p = cv.take<float>((int64_t)qry->sets * p.Pp);
     p.logits = own_logits ? cv.take<float>((int64_t)qry->subs * p.L.n_out) : nullptr;
@@ -2099,12 +2100,7 @@ extern "C" int gm_proto_predict(const gm_batch_t* qry, const gm_model_t* m, cons
         hipLaunchKernelGGL(k_pad_params_sets, dim3((int)std::min<int64_t>(256, (p.L.P + 255) / 256), T), dim3(256), 0, st, params, param_stride, Lu.P, cut, shift,
                            p.params_p, p.Pp);
         GM_HIP(hipGetLastError());
-        void* h = nullptr; int slot = 0;
-        StageRing& ring = stage_ring();
-        GM_TRY(ring.acquire(4 * (size_t)T, &h, &slot));
-        memcpy(h, n_classes, 4 * (size_t)T);
-        GM_HIP(hipMemcpyAsync(p.n_cls, h, 4 * (size_t)T, hipMemcpyHostToDevice, st));
-        GM_TRY(ring.release_after(slot, st));
+        GM_TRY(stage_to_device(p.n_cls, 4 * (size_t)T, st, [&](void* h) { memcpy(h, n_classes, 4 * (size_t)T); }));
     }
     if (qry->subs > 0) {
         // gm_meta_step's query evaluation nobody differentiates (fwd_only = 1: the fused aggregate + GEMM where eligible), then the scoring kernel
@@ -2177,185 +2173,4 @@ extern "C" int gm_meta_finish_adam(const float* head, int64_t P, int32_t K1, flo
                        steps, (int)n_steps, lr, beta1, beta2, eps, found_inf, ticket);
     GM_HIP(hipGetLastError());
     return GM_OK;
-}
-
-// ================================================================================ dense update, exported for numerics tests
-extern "C" int gm_dense_update(const gm_batch_t* b, const float* x, int32_t K, const float* W, int64_t w_stride, int32_t N, float* out, int32_t mode,
-                               void* stream) {
-    GM_REQUIRE(b && x && W && out && K >= 1 && N >= 1, GM_EINVAL, "dense_update: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    gm_gemm_args g{};
-    g.A = x; g.lda = K; g.B = W; g.b_stride = w_stride; g.C = out; g.ldc = N; g.K = K; g.N = N;
-    g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows;
-    uint16_t* planes = nullptr; unsigned* slots = nullptr;
-    const bool split = mode == 1 || mode == 2 || (mode < 0 && gm_gemm_split_ok(b->n_tiles, K, N));
-    if (split) {
-        GM_REQUIRE((N == 256 || N == 128) && K % 16 == 0 && K >= 32, GM_EINVAL, "dense_update: the split kernels need N = 128 or 256 and K a multiple of 16 (>= 32)");
-        const int sets = w_stride ? b->sets : 1;
-        GM_TRY(gm_alloc(&planes, (size_t)sets * 3 * K * N, st));
-        int rc = GM_OK;
-        gm_bound wb = gm_no_bound();
-        if (mode == 2) {
-            // two fp16 pieces per operand: bounds taken here -- one for all of x (slot 0), one per weight matrix (slots 1..)
-            rc = gm_alloc(&slots, (size_t)(sets + 1) * GM_BOUND_PAD, st);
-            if (rc == GM_OK && hipMemsetAsync(slots, 0, sizeof(unsigned) * (sets + 1) * GM_BOUND_PAD, st) != hipSuccess) { gm_set_error("dense_update: memset failed"); rc = GM_EHIP; }
-            if (rc == GM_OK) rc = gm_amax(x, 0, 0, (int64_t)b->rows * K, 1, slots, 0, st);
-            if (rc == GM_OK) rc = gm_amax(W, w_stride, 0, (int64_t)K * N, sets, slots + GM_BOUND_PAD, GM_BOUND_PAD, st);
-            wb.amax = slots + GM_BOUND_PAD; wb.stride = w_stride ? GM_BOUND_PAD : 0;
-            g.np = 2; g.a_bound = gm_no_bound(); g.a_bound.amax = slots; g.b_bound = wb;
-        }
-        if (rc == GM_OK) rc = gm_split_weights(W, w_stride, 0, K, N, 0, sets, planes, st, mode == 2 ? 2 : 3, wb);
-        if (rc != GM_OK) { gm_dev_free(planes, st); if (slots) gm_dev_free(slots, st); return rc; }
-        g.Bsplit = planes; g.bsplit_stride = w_stride ? (int64_t)3 * K * N : 0;
-    }
-    const int rc = gm_launch_gemm_nn(g, st);
-    if (planes) gm_dev_free(planes, st);
-    if (slots) gm_dev_free(slots, st);
-    gm_batch_mark_use(b, st);
-    return rc;
-}
-
-// The same product with every field of gm_gemm_args that the forward and dZ GEMMs set: the epilogue options, a transposed W, strides, the
-// choice of kernel family, and the instantiation that ran
-extern "C" int gm_dense_gemm(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, const float* W, int64_t w_stride, int32_t trans_w, int32_t N,
-                             float* out, int64_t ldc, const float* s, const float* s_keep, const float* bias, int64_t bias_stride, int32_t relu,
-                             uint8_t* relu_bits, const float* mask_h, const uint8_t* mask_b, float* zero_out, uint32_t* amax_out, int32_t mode,
-                             int32_t* launched, void* stream) {
-    GM_REQUIRE(b && x && W && out && K >= 1 && N >= 1 && ldx >= K && ldc >= N && mode >= -1 && mode <= 2 && !(mask_h && mask_b), GM_EINVAL,
-               "dense_gemm: bad arguments");
-    GM_REQUIRE(!amax_out || mode == 2, GM_EINVAL, "dense_gemm: amax_out is an output of the two-piece kernels (mode 2)");
-    hipStream_t st = (hipStream_t)stream;
-    const int sets = b->sets;
-    gm_gemm_args g{};
-    g.A = x; g.lda = ldx; g.B = W; g.b_stride = w_stride; g.transB = trans_w ? 1 : 0; g.C = out; g.ldc = ldc; g.K = K; g.N = N;
-    g.row_scale = s; g.row_scale_keep = s_keep; g.n_keep = b->rows; g.bias = bias; g.bias_stride = bias_stride; g.relu = relu ? 1 : 0;
-    g.relu_bits = relu_bits; g.mask_h = mask_h; g.mask_b = mask_b; g.zero_out = zero_out;
-    g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows; g.launched = launched;
-    uint16_t* planes = nullptr; unsigned* slots = nullptr;
-    int rc = GM_OK;
-    if (mode == 1 || mode == 2 || (mode < 0 && gm_gemm_split_ok(b->n_tiles, K, N))) {
-        GM_REQUIRE(!mask_h && !mask_b, GM_EINVAL, "dense_gemm: the split kernels take no relu' mask");
-        GM_REQUIRE((N == 256 || N == 128) && K % 16 == 0 && K >= 32, GM_EINVAL, "dense_gemm: the split kernels need N = 128 or 256 and K a multiple of 16 (>= 32)");
-        const int wsets = w_stride ? sets : 1;
-        rc = gm_alloc(&planes, (size_t)wsets * 3 * K * N, st);
-        gm_bound wb = gm_no_bound();
-        if (rc == GM_OK && mode == 2) {
-            // two fp16 pieces per operand: per-set bounds of x (slots [0, sets)), taken over each set's rows as gm_dense_wgrad does, and one per
-            // weight matrix (slots [sets, sets + wsets))
-            rc = gm_alloc(&slots, (size_t)(sets + wsets) * GM_BOUND_PAD, st);
-            if (rc == GM_OK && hipMemsetAsync(slots, 0, sizeof(unsigned) * (sets + wsets) * GM_BOUND_PAD, st) != hipSuccess) { gm_set_error("dense_gemm: memset failed"); rc = GM_EHIP; }
-            for (int t0 = 0; rc == GM_OK && t0 < sets; t0 += 8) {
-                const int segs = std::min(8, sets - t0);
-                int64_t xo[8], xn[8];
-                for (int i = 0; i < segs; ++i) {
-                    const int64_t r0 = b->h_set_row_off[t0 + i], nr = b->h_set_row_off[t0 + i + 1] - r0;
-                    xo[i] = r0 * ldx; xn[i] = nr > 0 ? (nr - 1) * ldx + K : 0;
-                }
-                rc = gm_amax_segs(x, xo, xn, segs, slots + (int64_t)t0 * GM_BOUND_PAD, GM_BOUND_PAD, st);
-            }
-            if (rc == GM_OK) rc = gm_amax(W, w_stride, 0, (int64_t)K * N, wsets, slots + (int64_t)sets * GM_BOUND_PAD, GM_BOUND_PAD, st);
-            wb.amax = slots + (int64_t)sets * GM_BOUND_PAD; wb.stride = w_stride ? GM_BOUND_PAD : 0;
-            g.np = 2; g.a_bound = gm_no_bound(); g.a_bound.amax = slots; g.a_bound.stride = GM_BOUND_PAD; g.b_bound = wb; g.amax_out = amax_out;
-        }
-        // trans_w: W stored [N, K] -- the planes are its own rows (as the dZ product's)
-        if (rc == GM_OK) rc = gm_split_weights(W, w_stride, 0, K, N, trans_w ? 1 : 0, wsets, planes, st, mode == 2 ? 2 : 3, wb);
-        g.Bsplit = planes; g.bsplit_stride = w_stride ? (int64_t)3 * K * N : 0;
-    }
-    if (rc == GM_OK) rc = gm_launch_gemm_nn(g, st);
-    if (planes) gm_dev_free(planes, st);
-    if (slots) gm_dev_free(slots, st);
-    gm_batch_mark_use(b, st);
-    return rc;
-}
-
-// The dZ product of the last layer over a dQ that holds its centre rows only, as gcn_backward launches it under GM_DEAD_ROWS (tests)
-extern "C" int gm_dense_dz_centre(const gm_batch_t* b, const float* dQ, int32_t K, const float* W, int64_t w_stride, int32_t N, float* T, void* stream) {
-    GM_REQUIRE(b && dQ && W && T && b->d_dq_tab, GM_EINVAL, "dense_dz_centre: bad arguments");
-    GM_REQUIRE((N == 256 || N == 128) && K % 16 == 0 && K >= 64, GM_EINVAL, "dense_dz_centre: the fused split kernel needs N = 128 or 256 and K a multiple of 16 (>= 64)");
-    hipStream_t st = (hipStream_t)stream;
-    const int wsets = w_stride ? b->sets : 1;
-    uint16_t* planes = nullptr;
-    GM_TRY(gm_alloc(&planes, (size_t)wsets * 3 * K * N, st));
-    gm_gemm_args g{};
-    g.A = dQ; g.lda = K; g.B = W; g.b_stride = w_stride; g.transB = 1; g.C = T; g.ldc = N; g.K = K; g.N = N;
-    g.row_scale = b->d_norm; g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows;
-    g.fuse2 = b->d_dq_tab; g.zside = dQ; g.ldz = K;
-    int rc = gm_split_weights(W, w_stride, 0, K, N, 1, wsets, planes, st, 3, gm_no_bound());
-    g.Bsplit = planes; g.bsplit_stride = w_stride ? (int64_t)3 * K * N : 0; g.np = 3;
-    if (rc == GM_OK) rc = gm_launch_gemm_nn(g, st);
-    gm_dev_free(planes, st);
-    gm_batch_mark_use(b, st);
-    return rc;
-}
-// ... and its weight gradient
-extern "C" int gm_dense_wgrad_centre(const gm_batch_t* b, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
-                                     int64_t db_stride, void* stream) {
-    GM_REQUIRE(b && x && dQ && dW && db && b->d_norm_c, GM_EINVAL, "dense_wgrad_centre: bad arguments");
-    const int64_t KN = (int64_t)Kx * N;
-    GM_REQUIRE(b->sets == 1 || (dw_stride >= KN && db_stride >= N), GM_EINVAL, "dense_wgrad_centre: per-set outputs overlap");
-    hipStream_t st = (hipStream_t)stream;
-    gm_wgrad_args w{};
-    w.A = x; w.lda = Kx; w.K = Kx; w.G = dQ; w.ldg = N; w.N = N; w.a_scale = b->d_norm; w.g_keep = b->d_norm_c;
-    w.chunks = b->d_chunks; w.n_chunks = b->n_chunks; w.set_chunk_off = b->d_set_chunk_off; w.sets = b->sets; w.rows = b->rows;
-    w.dW = dW; w.dw_stride = dw_stride; w.db = db; w.db_stride = db_stride; w.pick = GM_WGRAD_PICK_SPLIT;
-    int rc = gm_alloc(&w.partial, (size_t)std::max(1, b->n_chunks) * (size_t)(KN + N), st);
-    if (rc == GM_OK) rc = gm_launch_wgrad(w, st);
-    if (w.partial) gm_dev_free(w.partial, st);
-    gm_batch_mark_use(b, st);
-    return rc;
-}
-
-// ================================================================================ weight gradient, exported for numerics tests
-extern "C" int gm_dense_wgrad(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, const float* g, int64_t ldg, int32_t N, const float* s,
-                              const float* gb, int64_t ldgb, float* dW, int64_t dw_stride, float* db, int64_t db_stride, int32_t mode,
-                              const float* cur, float* next, int64_t p_stride, float lr, float* wt, uint16_t* pl_fwd, uint16_t* pl_dz, void* stream) {
-    GM_REQUIRE(b && x && g && dW && K >= 1 && N >= 1 && ldx >= K && ldg >= N && (!gb || ldgb >= N) && mode >= -1 && mode <= 2, GM_EINVAL,
-               "dense_wgrad: bad arguments");
-    // the generic kernel's bias sums hold 2048 columns (bsum[2] x 1024 threads), and gm_make_layout stops there too
-    GM_REQUIRE(K <= 2048 && N <= 2048, GM_ERANGE, "dense_wgrad: K=%d N=%d: at most 2048 columns per operand", K, N);
-    const int sets = b->sets;
-    const int64_t KN = (int64_t)K * N;
-    GM_REQUIRE(sets == 1 || (dw_stride >= KN && (!db || db_stride >= N)), GM_EINVAL, "dense_wgrad: per-set outputs overlap");
-    GM_REQUIRE(!next || (cur && db && (sets == 1 || p_stride >= KN + N)), GM_EINVAL, "dense_wgrad: the SGD step needs cur, db and a stride of at least (K+1)*N");
-    GM_REQUIRE((!wt && !pl_fwd && !pl_dz) || next, GM_EINVAL, "dense_wgrad: wt and the planes are outputs of the SGD step");
-    GM_REQUIRE((!pl_fwd && !pl_dz) || (K % 32 == 0 && N % 32 == 0), GM_EINVAL, "dense_wgrad: weight planes need K and N multiples of 32");
-    hipStream_t st = (hipStream_t)stream;
-    gm_wgrad_args w{};
-    w.A = x; w.lda = ldx; w.K = K; w.G = g; w.ldg = ldg; w.N = N; w.Gb = gb; w.ldgb = ldgb; w.a_scale = s;
-    w.chunks = b->d_chunks; w.n_chunks = b->n_chunks; w.set_chunk_off = b->d_set_chunk_off; w.sets = sets; w.rows = b->rows;
-    w.dW = dW; w.dw_stride = dw_stride; w.db = db; w.db_stride = db_stride;
-    if (next) {
-        w.sgd_cur = cur; w.sgd_cur_stride = p_stride; w.sgd_next = next; w.sgd_next_stride = p_stride; w.sgd_lr = lr; w.w_off = 0; w.b_off = KN;
-        w.wt_next = wt; w.pl_fwd = pl_fwd; w.pl_dz = pl_dz;
-    }
-    w.pick = mode == 0 ? GM_WGRAD_PICK_EXACT : mode > 0 ? GM_WGRAD_PICK_SPLIT : 0;
-    unsigned* slots = nullptr;
-    int rc = gm_alloc(&w.partial, (size_t)std::max(1, b->n_chunks) * (size_t)(KN + N), st);
-    if (rc == GM_OK && mode == 2) {
-        // two fp16 pieces per operand: per-set bounds of x (slots [0, sets)) and of g (slots [sets, 2 sets)), taken over each set's rows (with
-        // the padding between them), and ONE bound of |s| over all rows (slot 2 sets) as the gain of x's: |s x| <= max_t |x| * max |s|
-        rc = gm_alloc(&slots, (size_t)(2 * sets + 1) * GM_BOUND_PAD, st);
-        if (rc == GM_OK && hipMemsetAsync(slots, 0, sizeof(unsigned) * (2 * sets + 1) * GM_BOUND_PAD, st) != hipSuccess) { gm_set_error("dense_wgrad: memset failed"); rc = GM_EHIP; }
-        for (int t0 = 0; rc == GM_OK && t0 < sets; t0 += 8) {
-            const int segs = std::min(8, sets - t0);
-            int64_t xo[8], xn[8], go[8], gn[8];
-            for (int i = 0; i < segs; ++i) {
-                const int64_t r0 = b->h_set_row_off[t0 + i], nr = b->h_set_row_off[t0 + i + 1] - r0;
-                xo[i] = r0 * ldx; xn[i] = nr > 0 ? (nr - 1) * ldx + K : 0;
-                go[i] = r0 * ldg; gn[i] = nr > 0 ? (nr - 1) * ldg + N : 0;
-            }
-            rc = gm_amax_segs(x, xo, xn, segs, slots + (int64_t)t0 * GM_BOUND_PAD, GM_BOUND_PAD, st);
-            if (rc == GM_OK) rc = gm_amax_segs(g, go, gn, segs, slots + (int64_t)(sets + t0) * GM_BOUND_PAD, GM_BOUND_PAD, st);
-        }
-        if (rc == GM_OK && s) rc = gm_amax(s, 0, 0, b->rows, 1, slots + (int64_t)2 * sets * GM_BOUND_PAD, 0, st);
-        w.np = 2;
-        w.a_bound = gm_no_bound(); w.a_bound.amax = slots; w.a_bound.stride = GM_BOUND_PAD;
-        if (s) w.a_bound.gain = reinterpret_cast<const float*>(slots + (int64_t)2 * sets * GM_BOUND_PAD);     // (an amax slot holds fp32 bits)
-        w.g_bound = gm_no_bound(); w.g_bound.amax = slots + (int64_t)sets * GM_BOUND_PAD; w.g_bound.stride = GM_BOUND_PAD;
-    }
-    if (rc == GM_OK) rc = gm_launch_wgrad(w, st);
-    if (w.partial) gm_dev_free(w.partial, st);
-    if (slots) gm_dev_free(slots, st);
-    gm_batch_mark_use(b, st);
-    return rc;
 }
