@@ -26,6 +26,17 @@ struct GemmK {
     float* zero_out;            // DMA kernels only: the epilogue also zero-fills this [rows, ldc] buffer (dQ of the backward pass that follows)
 };
 
+// The block's tile.  XCD-aware: hardware block b -> XCD b%8; make logical ids contiguous per XCD so that the column
+// tiles of one row tile (which share the A rows) and neighbouring row tiles share an L2.
+struct GemmTile { int set, row0, nrows, n0; };
+__device__ __forceinline__ GemmTile gemm_tile(const GemmK& g, int BN) {
+    const int nb = g.n_tiles * g.n_col_tiles, b = blockIdx.x;
+    const int q = nb / GM_NXCD, r = nb % GM_NXCD, xcd = b % GM_NXCD, idx = b / GM_NXCD;
+    const int lb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int tile = lb / g.n_col_tiles, ct = lb % g.n_col_tiles;
+    return GemmTile{g.tiles[tile * 3], g.tiles[tile * 3 + 1], g.tiles[tile * 3 + 2], ct * BN};
+}
+
 // Block tile 128 x (64*WC); 2 x WC waves, each wave a 64 x 64 sub-tile = 2 x 2 MFMA 32x32 blocks.
 template <int WC, bool VEC, bool TB>
 __global__ __launch_bounds__(128 * WC) void k_gemm_nn(GemmK g) {
@@ -33,14 +44,8 @@ __global__ __launch_bounds__(128 * WC) void k_gemm_nn(GemmK g) {
     constexpr int EP_LD = 68;                                      // epilogue staging: 32 rows x 64 cols (+4 pad) per wave
     constexpr int TILE_FLOATS = GM_GEMM_BM * AS_LD + BK * BS_LD, EPI_FLOATS = 2 * WC * 32 * EP_LD;
     __shared__ __attribute__((aligned(16))) float smem[2 * TILE_FLOATS > EPI_FLOATS ? 2 * TILE_FLOATS : EPI_FLOATS];
-    // XCD-aware: hardware block b -> XCD b%8; make logical ids contiguous per XCD so that the column
-    // tiles of one row tile (which share the A rows) and neighbouring row tiles share an L2.
-    const int nb = g.n_tiles * g.n_col_tiles, b = blockIdx.x;
-    const int q = nb / GM_NXCD, r = nb % GM_NXCD, xcd = b % GM_NXCD, idx = b / GM_NXCD;
-    const int lb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    const int tile = lb / g.n_col_tiles, ct = lb % g.n_col_tiles;
-    const int set = g.tiles[tile * 3], row0 = g.tiles[tile * 3 + 1], nrows = g.tiles[tile * 3 + 2];
-    const int n0 = ct * BN;
+    const GemmTile t = gemm_tile(g, BN);
+    const int set = t.set, row0 = t.row0, nrows = t.nrows, n0 = t.n0;
     const float* Bp = g.B + (int64_t)set * g.b_stride;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave / WC, wc = wave % WC;
@@ -215,24 +220,91 @@ __global__ __launch_bounds__(128 * WC) void k_gemm_nn(GemmK g) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Direct-to-LDS variant of the forward GEMM (C = epi(A W_t), W row-major [K,N], K % 16 == 0, N % (64*WC) == 0):
+// Direct-to-LDS variant of the forward GEMM (C = epi(A W_t), W row-major [K,N], K % 16 == 0, N % BN == 0):
 // tiles are DMA-ed HBM -> LDS with global_load_lds_dwordx4 (no staging registers), three LDS stages, and a COUNTED
 // s_waitcnt vmcnt so that the loads of chunks k+1 and k+2 stay in flight across the single barrier of chunk k.
 // LDS images are lane-linear (the DMA writes wave-uniform base + lane*16 B): A tile [128][16] floats unpadded (the
-// b128 fragment reads are 4-way bank conflicted -- irrelevant next to 64-cycle f32 MFMAs), B tile [16][64*WC].
-template <int WC>
-__global__ __launch_bounds__(128 * WC) void k_gemm_glds(GemmK g) {
-    constexpr int NW = 2 * WC, BN = 64 * WC;
+// b128 fragment reads are 4-way bank conflicted -- irrelevant next to 64-cycle f32 MFMAs), B tile [16][BN].
+
+// One 1-KiB DMA piece: 64 lanes x 16 B from gsrc (per lane) to LDS byte address dst (wave-uniform) + lane * 16.
+// Inline asm: with the builtin, hipcc cannot prove that the (dynamic) stage being filled does not alias the stage being read
+// and drains vmcnt(0) before the first ds_read, which serialises the pipeline.  An asm statement is outside its vmcnt
+// bookkeeping; completion is counted by hand in the main loop (cdna_hip_programming.md 5.7).
+__device__ __forceinline__ void gemm_dma_piece(const float* gsrc, unsigned dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
+}
+
+// Epilogue tail of the DMA kernels for the float4 at (row, col): scale + bias, ReLU, the relu' mask, the packed relu' bits, the
+// C store and the zero fill of zero_out.
+__device__ __forceinline__ void gemm_epilogue_store(const GemmK& g, int64_t row, int col, float4 v, float sc, float4 b4) {
+    v.x = v.x * sc + b4.x; v.y = v.y * sc + b4.y; v.z = v.z * sc + b4.z; v.w = v.w * sc + b4.w;
+    if (g.relu) { v.x = v.x < 0.f ? 0.f : v.x; v.y = v.y < 0.f ? 0.f : v.y; v.z = v.z < 0.f ? 0.f : v.z; v.w = v.w < 0.f ? 0.f : v.w; }   // NaN propagates like torch relu
+    if (g.mask_h) {
+        const float4 m = *reinterpret_cast<const float4*>(g.mask_h + row * g.ldc + col);
+        v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
+    }
+    if (g.relu_bits) g.relu_bits[(row * g.ldc + col) >> 2] = (uint8_t)((v.x > 0.f) | ((v.y > 0.f) << 1) | ((v.z > 0.f) << 2) | ((v.w > 0.f) << 3));
+    if (g.nt_store) {     // C is re-read by the NEXT kernel only (>> L2): keep L2 for the A rows and the weights
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        f4v vv = {v.x, v.y, v.z, v.w};
+        __builtin_nontemporal_store(vv, reinterpret_cast<f4v*>(g.C + row * g.ldc + col));
+    } else *reinterpret_cast<float4*>(g.C + row * g.ldc + col) = v;
+    if (g.zero_out) *reinterpret_cast<float4*>(g.zero_out + row * g.ldc + col) = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// One 16-k chunk of a wave's MI x MI blocks of 32 x 32 on v_mfma_f32_32x32x2_f32, from the LDS images As [128][16] and Bs [16][BN].
+// arow / bcol: the lane's row / column in the wave's first block.
+// A fragments: lane (li,kh) takes k = 8q + 4kh + r  (r = 0..3) of its row -> MFMA step 4q + r.  (k_gemm_nn keeps its own spelling of this
+// step: routed through this function its instantiations come out with other register allocations.)
+template <int MI, int BN>
+__device__ __forceinline__ void gemm_mfma_chunk(f32x16 (&acc)[MI][MI], const float* As, const float* Bs, int arow, int bcol, int kh) {
+    float4 af[MI][2];
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int qq = 0; qq < 2; ++qq) af[i][qq] = *reinterpret_cast<const float4*>(&As[(arow + i * 32) * BK + qq * 8 + kh * 4]);
+#pragma unroll
+    for (int qq = 0; qq < 2; ++qq) {
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int kk = qq * 8 + kh * 4 + rr;
+            float bv[MI];
+#pragma unroll
+            for (int j = 0; j < MI; ++j) bv[j] = Bs[kk * BN + bcol + j * 32];
+#pragma unroll
+            for (int i = 0; i < MI; ++i) {
+                const float a = rr == 0 ? af[i][qq].x : rr == 1 ? af[i][qq].y : rr == 2 ? af[i][qq].z : af[i][qq].w;
+#pragma unroll
+                for (int j = 0; j < MI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv[j], acc[i][j], 0, 0, 0);
+            }
+        }
+    }
+}
+
+// Block tile 128 x BN over a WR x WC grid of waves, each wave MI x MI MFMA 32x32 blocks: WR * MI * 32 == 128, BN = WC * MI * 32.
+//   <2, WC, 2>  two wave rows of 64 x 64 sub-tiles, BN = 64 * WC (GM_GEMM_ID_GLDS1 / 2 / 4)
+//   <4, 2, 1>   EIGHT waves of 32 x 32 on the 128 x 64 tile (GM_GEMM_ID_GLDS_SMALL).  A launch with a few hundred tiles (support batches of
+//               a 4-task shard, the Tissue / FirstMM shapes) puts about one workgroup on a CU, where <2, 1, 2> walks a chain of K/2 * 4
+//               dependent-issue MFMAs (64 cycles each) with one wave per SIMD and nothing to cover the per-chunk LDS latency: 34 us for a
+//               14-us chain.  Same tiles, same DMA pipeline, a quarter of the MFMA chain per wave.
+template <int WR, int WC, int MI>
+__global__ __launch_bounds__(64 * WR * WC) void k_gemm_glds(GemmK g) {
+    static_assert(WR * MI * 32 == GM_GEMM_BM, "the wave rows cover the 128-row tile");
+    constexpr int NW = WR * WC, BN = WC * MI * 32;
     constexpr int A_FLOATS = GM_GEMM_BM * BK, B_FLOATS = BK * BN, STAGE = A_FLOATS + B_FLOATS;
-    constexpr int EP_LD = 68, EPI_FLOATS = NW * 32 * EP_LD;
+    constexpr int EP_LD = MI * 32 + 4, EPI_FLOATS = NW * 32 * EP_LD;          // epilogue staging: 32 rows x MI * 32 cols (+4 pad) per wave
     constexpr int MAIN_FLOATS = 3 * STAGE > EPI_FLOATS ? 3 * STAGE : EPI_FLOATS;
-    __shared__ __attribute__((aligned(16))) float smem[MAIN_FLOATS + GM_GEMM_BM];      // + the tile's 128 row scales
-    const int nb = g.n_tiles * g.n_col_tiles, b = blockIdx.x;
-    const int q = nb / GM_NXCD, r = nb % GM_NXCD, xcd = b % GM_NXCD, idx = b / GM_NXCD;
-    const int lb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    const int tile = lb / g.n_col_tiles, ct = lb % g.n_col_tiles;
-    const int set = g.tiles[tile * 3], row0 = g.tiles[tile * 3 + 1], nrows = g.tiles[tile * 3 + 2];
-    const int n0 = ct * BN;
+    // DMA pieces of 1 KiB (64 lanes x 16 B).  A tile = 8 pieces (16 rows x 16 floats each), B tile = BK*BN*4/1024 pieces; PPW slots per wave
+    // and chunk.  Where the pieces do not divide over the waves (<4, 2, 1>: 12 over 8), the DUMMY slots left over re-read A piece 0 into a
+    // scratch KiB, so that every wave issues exactly PPW loads per chunk (the vmcnt wait is a fixed count).
+    constexpr int A_PIECES = A_FLOATS / 256, B_PIECES = B_FLOATS / 256, PIECES = A_PIECES + B_PIECES;
+    constexpr int PPW = (PIECES + NW - 1) / NW, DUMMY = NW * PPW - PIECES;
+    constexpr int SCALE_OFF = MAIN_FLOATS + (DUMMY ? 256 : 0);
+    __shared__ __attribute__((aligned(16))) float smem[SCALE_OFF + GM_GEMM_BM];        // + the tile's 128 row scales
+    const GemmTile t = gemm_tile(g, BN);
+    const int set = t.set, row0 = t.row0, nrows = t.nrows, n0 = t.n0;
     const float* Bp = g.B + (int64_t)set * g.b_stride;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // The epilogue's per-row scales (norm) are fetched now and parked in LDS: as dependent loads inside the epilogue they
@@ -241,19 +313,16 @@ __global__ __launch_bounds__(128 * WC) void k_gemm_glds(GemmK g) {
     if (tid < GM_GEMM_BM && g.row_scale) my_scale = g.row_scale[row0 + min(tid, nrows - 1)];
     const int wr = wave / WC, wc = wave % WC;
     const int li = lane & 31, kh = lane >> 5;
-    // DMA pieces of 1 KiB (64 lanes x 16 B).  A tile = 8 pieces (16 rows x 16 floats each), B tile = BK*BN*4/1024 pieces.
-    constexpr int A_PIECES = A_FLOATS / 256, B_PIECES = B_FLOATS / 256, PIECES = A_PIECES + B_PIECES;
-    constexpr int PPW = (PIECES + NW - 1) / NW;                         // pieces per wave per chunk
-    static_assert(PIECES % NW == 0, "tile pieces must divide evenly over the waves");
     // per-lane source pointers of this wave's pieces (advance by k0 / k0*N per chunk)
-    const float* src[PPW]; int dstoff[PPW]; int64_t kstep[PPW];
+    const float* src[PPW]; int dstoff[PPW]; int64_t kstep[PPW]; bool dummy[PPW];
 #pragma unroll
     for (int p = 0; p < PPW; ++p) {
         const int piece = wave * PPW + p;
-        if (piece < A_PIECES) {                                        // rows piece*16 .. +15, lane -> (row, k4)
-            const int rr = piece * 16 + (lane >> 2);
+        dummy[p] = DUMMY && piece >= PIECES;
+        if (piece < A_PIECES || dummy[p]) {                            // rows pc*16 .. +15, lane -> (row, k4)
+            const int pc = dummy[p] ? 0 : piece, rr = pc * 16 + (lane >> 2);
             src[p] = g.A + (int64_t)(row0 + min(rr, nrows - 1)) * g.lda + (lane & 3) * 4;
-            kstep[p] = BK; dstoff[p] = piece * 256;
+            kstep[p] = BK; dstoff[p] = pc * 256;
         } else {                                                       // B: piece -> 256 consecutive floats of the [16][BN] tile
             const int e = (piece - A_PIECES) * 256 + lane * 4;
             const int kk = e / BN, n = e % BN;
@@ -261,32 +330,25 @@ __global__ __launch_bounds__(128 * WC) void k_gemm_glds(GemmK g) {
             kstep[p] = (int64_t)BK * g.N; dstoff[p] = A_FLOATS + (piece - A_PIECES) * 256;
         }
     }
-    // The DMA is issued through inline asm: with the builtin, hipcc cannot prove that the (dynamic) stage being filled
-    // does not alias the stage being read and drains vmcnt(0) before the first ds_read, which serialises the pipeline.
-    // An asm statement is outside its vmcnt bookkeeping; completion is counted by hand below (cdna_hip_programming.md 5.7).
     const unsigned lds_base = (unsigned)(uintptr_t)((__attribute__((address_space(3))) float*)smem);
     auto issue = [&](int chunk) {
         const unsigned st = lds_base + (unsigned)((chunk % 3) * STAGE * 4);
 #pragma unroll
-        for (int p = 0; p < PPW; ++p) {
-            const float* gsrc = src[p] + chunk * kstep[p];
-            const unsigned dst = __builtin_amdgcn_readfirstlane(st + (unsigned)dstoff[p] * 4u);
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-        }
+        for (int p = 0; p < PPW; ++p)
+            gemm_dma_piece(src[p] + chunk * kstep[p],
+                           __builtin_amdgcn_readfirstlane(dummy[p] ? lds_base + (unsigned)MAIN_FLOATS * 4u : st + (unsigned)dstoff[p] * 4u));
     };
-    f32x16 acc[2][2];
+    f32x16 acc[MI][MI];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < MI; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < MI; ++j)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
     const int nchunks = g.K / BK;
     issue(0);
     if (nchunks > 1) issue(1);
-    if (tid < GM_GEMM_BM) smem[MAIN_FLOATS + tid] = my_scale;      // visible to everyone after the first barrier of the main loop
+    if (tid < GM_GEMM_BM) smem[SCALE_OFF + tid] = my_scale;        // visible to everyone after the first barrier of the main loop
     for (int c = 0; c < nchunks; ++c) {
         // this wave's pieces of chunk c have landed once at most the PPW pieces of chunk c+1 are still outstanding
         if (c + 1 < nchunks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
@@ -294,177 +356,31 @@ __global__ __launch_bounds__(128 * WC) void k_gemm_glds(GemmK g) {
         __builtin_amdgcn_s_barrier();                  // every wave's pieces of chunk c landed; everyone is done reading chunk c-1
         if (c + 2 < nchunks) issue(c + 2);             // into the stage chunk c-1 occupied
         const float* As = smem + (c % 3) * STAGE;
-        const float* Bs = As + A_FLOATS;
-        float4 af[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int qq = 0; qq < 2; ++qq)
-                af[i][qq] = *reinterpret_cast<const float4*>(&As[(wr * 64 + i * 32 + li) * BK + qq * 8 + kh * 4]);
-#pragma unroll
-        for (int qq = 0; qq < 2; ++qq) {
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int kk = qq * 8 + kh * 4 + rr;
-                const float b0 = Bs[kk * BN + wc * 64 + li], b1 = Bs[kk * BN + wc * 64 + 32 + li];
-                const float a0 = rr == 0 ? af[0][qq].x : rr == 1 ? af[0][qq].y : rr == 2 ? af[0][qq].z : af[0][qq].w;
-                const float a1 = rr == 0 ? af[1][qq].x : rr == 1 ? af[1][qq].y : rr == 2 ? af[1][qq].z : af[1][qq].w;
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-            }
-        }
+        gemm_mfma_chunk<MI, BN>(acc, As, As + A_FLOATS, wr * MI * 32 + li, wc * MI * 32 + li, kh);
     }
     __syncthreads();                                   // all MFMAs' LDS reads done before the epilogue reuses the stages
+    // epilogue: each wave's 32 x (MI * 32) block rows go through LDS and leave as float4 row segments (see k_gemm_nn)
+    constexpr int LPR = MI * 8, RPP = 64 / LPR;        // lanes per row, rows per pass
     const float* biasp = g.bias ? g.bias + (int64_t)set * g.bias_stride : nullptr;
     float* E = smem + wave * (32 * EP_LD);
-    const int er = lane >> 4, ec = (lane & 15) * 4;
-    const int col = n0 + wc * 64 + ec;
+    const int er = lane / LPR, ec = (lane % LPR) * 4;
+    const int col = n0 + wc * MI * 32 + ec;
     float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (biasp) b4 = *reinterpret_cast<const float4*>(biasp + col);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < MI; ++i) {
         if (i) __syncthreads();
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < MI; ++j)
 #pragma unroll
             for (int e = 0; e < 16; ++e) E[((e & 3) + 8 * (e >> 2) + 4 * kh) * EP_LD + j * 32 + li] = acc[i][j][e];
         __syncthreads();
 #pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int rl = wr * 64 + i * 32 + it * 4 + er;
+        for (int it = 0; it < 32 / RPP; ++it) {
+            const int rl = wr * MI * 32 + i * 32 + it * RPP + er;
             if (rl >= nrows) continue;
-            const int64_t row = row0 + rl;
-            const float sc = smem[MAIN_FLOATS + rl];
-            float4 v = *reinterpret_cast<const float4*>(&E[(it * 4 + er) * EP_LD + ec]);
-            v.x = v.x * sc + b4.x; v.y = v.y * sc + b4.y; v.z = v.z * sc + b4.z; v.w = v.w * sc + b4.w;
-            if (g.relu) { v.x = v.x < 0.f ? 0.f : v.x; v.y = v.y < 0.f ? 0.f : v.y; v.z = v.z < 0.f ? 0.f : v.z; v.w = v.w < 0.f ? 0.f : v.w; }
-            if (g.mask_h) {
-                const float4 m = *reinterpret_cast<const float4*>(g.mask_h + row * g.ldc + col);
-                v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
-            }
-            if (g.relu_bits) g.relu_bits[(row * g.ldc + col) >> 2] = (uint8_t)((v.x > 0.f) | ((v.y > 0.f) << 1) | ((v.z > 0.f) << 2) | ((v.w > 0.f) << 3));
-            if (g.nt_store) {     // C is re-read by the NEXT kernel only (>> L2): keep L2 for the A rows and the weights
-                typedef float f4v __attribute__((ext_vector_type(4)));
-                f4v vv = {v.x, v.y, v.z, v.w};
-                __builtin_nontemporal_store(vv, reinterpret_cast<f4v*>(g.C + row * g.ldc + col));
-            } else *reinterpret_cast<float4*>(g.C + row * g.ldc + col) = v;
-            if (g.zero_out) *reinterpret_cast<float4*>(g.zero_out + row * g.ldc + col) = make_float4(0.f, 0.f, 0.f, 0.f);
+            gemm_epilogue_store(g, row0 + rl, col, *reinterpret_cast<const float4*>(&E[(it * RPP + er) * EP_LD + ec]), smem[SCALE_OFF + rl], b4);
         }
-    }
-}
-
-// Small-launch variant of k_gemm_glds<1> (tile 128 x 64): EIGHT waves of 32 x 32 instead of two of 64 x 64.  A launch with
-// a few hundred tiles (support batches of a 4-task shard, the Tissue / FirstMM shapes) puts about one workgroup on a CU, where
-// the two-wave version walks a chain of K/2 * 4 dependent-issue MFMAs (64 cycles each) with one wave per SIMD and nothing to
-// cover the per-chunk LDS latency: 34 us for a 14-us chain.  Same tiles, same DMA pipeline, a quarter of the MFMA chain per wave.
-__global__ __launch_bounds__(512) void k_gemm_glds_small(GemmK g) {
-    constexpr int NW = 8, BN = 64;
-    constexpr int A_FLOATS = GM_GEMM_BM * BK, B_FLOATS = BK * BN, STAGE = A_FLOATS + B_FLOATS;         // 2048 + 1024 floats
-    constexpr int EP_LD = 36, EPI_FLOATS = NW * 32 * EP_LD;                                              // == 3 * STAGE
-    constexpr int MAIN_FLOATS = 3 * STAGE > EPI_FLOATS ? 3 * STAGE : EPI_FLOATS;
-    __shared__ __attribute__((aligned(16))) float smem[MAIN_FLOATS + 256 + GM_GEMM_BM];                 // + one dummy DMA piece + the row scales
-    const int nb = g.n_tiles * g.n_col_tiles, b = blockIdx.x;
-    const int q = nb / GM_NXCD, r = nb % GM_NXCD, xcd = b % GM_NXCD, idx = b / GM_NXCD;
-    const int lb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    const int tile = lb / g.n_col_tiles, ct = lb % g.n_col_tiles;
-    const int set = g.tiles[tile * 3], row0 = g.tiles[tile * 3 + 1], nrows = g.tiles[tile * 3 + 2];
-    const int n0 = ct * BN;
-    const float* Bp = g.B + (int64_t)set * g.b_stride;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    float my_scale = 1.f;
-    if (tid < GM_GEMM_BM && g.row_scale) my_scale = g.row_scale[row0 + min(tid, nrows - 1)];
-    const int wr = wave >> 1, wc = wave & 1;                               // 4 x 2 grid of 32 x 32 sub-tiles
-    const int li = lane & 31, kh = lane >> 5;
-    // 12 one-KiB DMA pieces per chunk (8 of A, 4 of B) over 8 waves: two slots per wave, the last four slots re-read A piece 0
-    // into a scratch KiB so that every wave issues exactly two loads per chunk (the vmcnt wait is a fixed count)
-    constexpr int A_PIECES = 8, PIECES = 12, PPW = 2;
-    const float* src[PPW]; int dstoff[PPW]; int64_t kstep[PPW]; bool dummy[PPW];
-#pragma unroll
-    for (int p = 0; p < PPW; ++p) {
-        const int piece = wave * PPW + p;
-        dummy[p] = piece >= PIECES;
-        if (piece < A_PIECES || dummy[p]) {
-            const int pc = dummy[p] ? 0 : piece, rr = pc * 16 + (lane >> 2);
-            src[p] = g.A + (int64_t)(row0 + min(rr, nrows - 1)) * g.lda + (lane & 3) * 4;
-            kstep[p] = BK; dstoff[p] = pc * 256;
-        } else {
-            const int e = (piece - A_PIECES) * 256 + lane * 4, kk = e / BN, n = e % BN;
-            src[p] = Bp + (int64_t)kk * g.N + n0 + n;
-            kstep[p] = (int64_t)BK * g.N; dstoff[p] = A_FLOATS + (piece - A_PIECES) * 256;
-        }
-    }
-    const unsigned lds_base = (unsigned)(uintptr_t)((__attribute__((address_space(3))) float*)smem);
-    auto issue = [&](int chunk) {
-        const unsigned st = lds_base + (unsigned)((chunk % 3) * STAGE * 4);
-#pragma unroll
-        for (int p = 0; p < PPW; ++p) {
-            const float* gsrc = src[p] + chunk * kstep[p];
-            const unsigned dst = __builtin_amdgcn_readfirstlane(dummy[p] ? lds_base + (unsigned)MAIN_FLOATS * 4u : st + (unsigned)dstoff[p] * 4u);
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-        }
-    };
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-    const int nchunks = g.K / BK;
-    issue(0);
-    if (nchunks > 1) issue(1);
-    if (tid < GM_GEMM_BM) smem[MAIN_FLOATS + 256 + tid] = my_scale;
-    for (int c = 0; c < nchunks; ++c) {
-        if (c + 1 < nchunks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (c + 2 < nchunks) issue(c + 2);
-        const float* As = smem + (c % 3) * STAGE;
-        const float* Bs = As + A_FLOATS;
-        float4 af[2];
-#pragma unroll
-        for (int qq = 0; qq < 2; ++qq) af[qq] = *reinterpret_cast<const float4*>(&As[(wr * 32 + li) * BK + qq * 8 + kh * 4]);
-#pragma unroll
-        for (int qq = 0; qq < 2; ++qq) {
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int kk = qq * 8 + kh * 4 + rr;
-                const float b0 = Bs[kk * BN + wc * 32 + li];
-                const float a0 = rr == 0 ? af[qq].x : rr == 1 ? af[qq].y : rr == 2 ? af[qq].z : af[qq].w;
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc, 0, 0, 0);
-            }
-        }
-    }
-    __syncthreads();
-    const float* biasp = g.bias ? g.bias + (int64_t)set * g.bias_stride : nullptr;
-    float* E = smem + wave * (32 * EP_LD);
-    const int er = lane >> 3, ec = (lane & 7) * 4;                          // 8 rows x 32 columns per pass
-    const int col = n0 + wc * 32 + ec;
-    float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (biasp) b4 = *reinterpret_cast<const float4*>(biasp + col);
-#pragma unroll
-    for (int e = 0; e < 16; ++e) E[((e & 3) + 8 * (e >> 2) + 4 * kh) * EP_LD + li] = acc[e];
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const int rl = wr * 32 + it * 8 + er;
-        if (rl >= nrows) continue;
-        const int64_t row = row0 + rl;
-        const float sc = smem[MAIN_FLOATS + 256 + rl];
-        float4 v = *reinterpret_cast<const float4*>(&E[(it * 8 + er) * EP_LD + ec]);
-        v.x = v.x * sc + b4.x; v.y = v.y * sc + b4.y; v.z = v.z * sc + b4.z; v.w = v.w * sc + b4.w;
-        if (g.relu) { v.x = v.x < 0.f ? 0.f : v.x; v.y = v.y < 0.f ? 0.f : v.y; v.z = v.z < 0.f ? 0.f : v.z; v.w = v.w < 0.f ? 0.f : v.w; }
-        if (g.mask_h) {
-            const float4 m = *reinterpret_cast<const float4*>(g.mask_h + row * g.ldc + col);
-            v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
-        }
-        if (g.relu_bits) g.relu_bits[(row * g.ldc + col) >> 2] = (uint8_t)((v.x > 0.f) | ((v.y > 0.f) << 1) | ((v.z > 0.f) << 2) | ((v.w > 0.f) << 3));
-        if (g.nt_store) {
-            typedef float f4v __attribute__((ext_vector_type(4)));
-            f4v vv = {v.x, v.y, v.z, v.w};
-            __builtin_nontemporal_store(vv, reinterpret_cast<f4v*>(g.C + row * g.ldc + col));
-        } else *reinterpret_cast<float4*>(g.C + row * g.ldc + col) = v;
-        if (g.zero_out) *reinterpret_cast<float4*>(g.zero_out + row * g.ldc + col) = make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
 
@@ -481,7 +397,6 @@ extern "C" int32_t gm_get_gemm_mode(void) { return gm_gemm_mode(); }
 static std::atomic<int> g_split_pieces{-1};     // gm_set_split_pieces override (-1: GM_SPLIT_PIECES / default 3)
 extern "C" void gm_set_split_pieces(int32_t pieces) { g_split_pieces.store(pieces == 3 ? 3 : (pieces == 2 ? 2 : -1), std::memory_order_relaxed); }
 extern "C" int32_t gm_get_split_pieces(void) { return gm_split_np(); }
-// The persistent kernel walks 128 x 256 tiles, one workgroup per CU: worth it from about one tile per CU upwards.
 const float* gm_zero_row(hipStream_t s) {
     static std::mutex mu;
     static float* rows[64] = {};
@@ -496,10 +411,12 @@ const float* gm_zero_row(hipStream_t s) {
     }
     return rows[dev];
 }
+// shapes the split kernels (k_gemm_split_p) take
+static bool split_dims_ok(int K, int N) { return (N == 256 || N == 128) && K % 16 == 0 && K >= 32; }
 bool gm_gemm_split_ok(int n_tiles, int K, int N) {
     // default: from a quarter of the (current device's) CUs busy upwards (measured on the 141-tile support batch of a 4-task shard: still ahead of the fp32 small-tile kernel)
     const int min_tiles = gm_knob().gemm_split_min_tiles >= 0 ? gm_knob().gemm_split_min_tiles : gm_num_cus() / 4;
-    return gm_gemm_mode() == 1 && (N == 256 || N == 128) && K % 16 == 0 && K >= 32 && n_tiles >= min_tiles;
+    return gm_gemm_mode() == 1 && split_dims_ok(K, N) && n_tiles >= min_tiles;
 }
 int gm_split_weights(const float* params, int64_t pstride, int64_t w_off, int K, int N, int trans, int sets, uint16_t* out, hipStream_t s, int np, gm_bound bound) {
     GM_REQUIRE(np == 3 || (np == 2 && bound.amax), GM_EINVAL, "split_weights: two-piece planes need a bound");
@@ -527,6 +444,36 @@ int gm_split_np() {
     return o > 0 ? o : (gm_knob().split_pieces == 2 ? 2 : 3);
 }
 
+// One kernel launch: records the instantiation's GM_GEMM_ID_* for the host (`launched`: numerics tests only), lifts the kernel's dynamic-LDS
+// limit where asked, launches.  The caller reads hipGetLastError.
+template <typename KArgs>
+static int launch_kernel(void (*kernel)(KArgs), dim3 grid, dim3 block, size_t lds, hipStream_t s, const KArgs& k, int* launched = nullptr, int id = 0,
+                         bool full_lds = false) {
+    if (launched) *launched = id;
+    if (full_lds) GM_TRY(gm_func_full_lds((const void*)kernel));
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, k);
+    return GM_OK;
+}
+// k_gemm_split_p<GATHER, ., ., NP>: N == 128 takes the 128 x 128 tile; a launch that would leave more than half of the CUs without a tile
+// walks 64-row half tiles (half the MFMA chain per workgroup; unfused launches only); everything else the 128 x 256 tile
+template <bool GATHER, int NP>
+static int launch_gemm_split(const gm_gemm_args& a, const SplitGemmK& k, int grid, bool half_tiles, hipStream_t s) {
+    const dim3 blk(1024);
+    if (a.N == 128) return launch_kernel(k_gemm_split_p<GATHER, 1, 2, NP>, dim3(grid), blk, 0, s, k, a.launched, GM_GEMM_ID_SPLIT(GATHER, 1, 2, NP));
+    if constexpr (!GATHER)
+        if (half_tiles) return launch_kernel(k_gemm_split_p<false, 1, 4, NP>, dim3(2 * a.n_tiles), blk, 0, s, k, a.launched, GM_GEMM_ID_SPLIT(false, 1, 4, NP));
+    return launch_kernel(k_gemm_split_p<GATHER, 2, 4, NP>, dim3(grid), blk, 0, s, k, a.launched, GM_GEMM_ID_SPLIT(GATHER, 2, 4, NP));
+}
+template <int WC>
+static int launch_gemm_exact(const gm_gemm_args& a, const GemmK& g, bool vec, hipStream_t s) {
+    const dim3 grid(g.n_tiles * g.n_col_tiles), blk(128 * WC);
+    const int id = GM_GEMM_ID_NN(WC, vec, a.transB ? 1 : 0);
+    if (vec && a.transB) return launch_kernel(k_gemm_nn<WC, true, true>, grid, blk, 0, s, g, a.launched, id);
+    if (vec) return launch_kernel(k_gemm_nn<WC, true, false>, grid, blk, 0, s, g, a.launched, id);
+    if (a.transB) return launch_kernel(k_gemm_nn<WC, false, true>, grid, blk, 0, s, g, a.launched, id);
+    return launch_kernel(k_gemm_nn<WC, false, false>, grid, blk, 0, s, g, a.launched, id);
+}
+
 static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s);
 int gm_launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
     if (a.n_tiles <= 0) return GM_OK;
@@ -539,11 +486,9 @@ int gm_launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
     return rc;
 }
 static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
-    // host-side record of the instantiation about to be launched (numerics tests only)
-#define GM_LAUNCHED(ID) do { if (a.launched) *a.launched = (ID); } while (0)
     if (a.Bsplit) {
         // fp32-accurate product on the bf16 matrix cores (exact 3-way operand split, 6 MFMA products, fp32 accumulation)
-        const bool ok = (a.N == 256 || a.N == 128) && a.K % 16 == 0 && a.K >= 32 && !a.mask_h && !a.mask_b && (a.lda % 4 == 0) && (((uintptr_t)a.A & 15) == 0) &&
+        const bool ok = split_dims_ok(a.K, a.N) && !a.mask_h && !a.mask_b && (a.lda % 4 == 0) && (((uintptr_t)a.A & 15) == 0) &&
                         (a.ldc % 4 == 0) && (((uintptr_t)a.C & 15) == 0) && (!a.bias || a.bias_stride % 4 == 0);
         GM_REQUIRE(ok, GM_EINVAL, "gemm: launch not eligible for the split-bf16 kernel (N=%d K=%d)", a.N, a.K);
         // the epilogue zero-fills columns [0, N) of its rows only: a zero_out of wider rows would be left partly unwritten
@@ -576,21 +521,12 @@ static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
             // With the two-piece kernels (shorter tiles) the optimum moved from 4 to 3, and to 2 for the launches of 16 and more tiles per CU:
             // 4-task shard 4.36 -> 4.25 ms, task_num 32 24.86 -> 24.50 (three runs each, same box).
             const int mult_f = a.n_tiles >= 16 * grid_cap ? 2 : 3;
-            const dim3 grid(std::min(a.n_tiles, mult_f * grid_cap));
-            if (a.N == 128 && f16) { GM_LAUNCHED(GM_GEMM_ID_SPLIT(true, 1, 2, 2)); hipLaunchKernelGGL((k_gemm_split_p<true, 1, 2, 2>), grid, dim3(1024), 0, s, k); }
-            else if (a.N == 128) { GM_LAUNCHED(GM_GEMM_ID_SPLIT(true, 1, 2, 3)); hipLaunchKernelGGL((k_gemm_split_p<true, 1, 2, 3>), grid, dim3(1024), 0, s, k); }
-            else if (f16) { GM_LAUNCHED(GM_GEMM_ID_SPLIT(true, 2, 4, 2)); hipLaunchKernelGGL((k_gemm_split_p<true, 2, 4, 2>), grid, dim3(1024), 0, s, k); }
-            else { GM_LAUNCHED(GM_GEMM_ID_SPLIT(true, 2, 4, 3)); hipLaunchKernelGGL((k_gemm_split_p<true, 2, 4, 3>), grid, dim3(1024), 0, s, k); }
+            const int grid = std::min(a.n_tiles, mult_f * grid_cap);
+            GM_TRY(f16 ? (launch_gemm_split<true, 2>(a, k, grid, false, s)) : (launch_gemm_split<true, 3>(a, k, grid, false, s)));
         } else {
-            // a launch that would leave more than half of the CUs without a tile walks 64-row half tiles: half the MFMA chain per workgroup
-            const dim3 grid_r(std::min(a.n_tiles, grid_cap));
-            if (a.N == 128 && f16) { GM_LAUNCHED(GM_GEMM_ID_SPLIT(false, 1, 2, 2)); hipLaunchKernelGGL((k_gemm_split_p<false, 1, 2, 2>), grid_r, dim3(1024), 0, s, k); }
-            else if (a.N == 128) { GM_LAUNCHED(GM_GEMM_ID_SPLIT(false, 1, 2, 3)); hipLaunchKernelGGL((k_gemm_split_p<false, 1, 2, 3>), grid_r, dim3(1024), 0, s, k); }
-            else if (2 * a.n_tiles <= grid_cap) {
-                if (f16) { GM_LAUNCHED(GM_GEMM_ID_SPLIT(false, 1, 4, 2)); hipLaunchKernelGGL((k_gemm_split_p<false, 1, 4, 2>), dim3(2 * a.n_tiles), dim3(1024), 0, s, k); }
-                else { GM_LAUNCHED(GM_GEMM_ID_SPLIT(false, 1, 4, 3)); hipLaunchKernelGGL((k_gemm_split_p<false, 1, 4, 3>), dim3(2 * a.n_tiles), dim3(1024), 0, s, k); }
-            } else if (f16) { GM_LAUNCHED(GM_GEMM_ID_SPLIT(false, 2, 4, 2)); hipLaunchKernelGGL((k_gemm_split_p<false, 2, 4, 2>), grid_r, dim3(1024), 0, s, k); }
-            else { GM_LAUNCHED(GM_GEMM_ID_SPLIT(false, 2, 4, 3)); hipLaunchKernelGGL((k_gemm_split_p<false, 2, 4, 3>), grid_r, dim3(1024), 0, s, k); }
+            const int grid = std::min(a.n_tiles, grid_cap);
+            const bool half_tiles = 2 * a.n_tiles <= grid_cap;
+            GM_TRY(f16 ? (launch_gemm_split<false, 2>(a, k, grid, half_tiles, s)) : (launch_gemm_split<false, 3>(a, k, grid, half_tiles, s)));
         }
         GM_HIP(hipGetLastError());
         return GM_OK;
@@ -602,15 +538,6 @@ static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
     g.c_vec = (a.N % 4 == 0) && (a.ldc % 4 == 0) && (((uintptr_t)a.C & 15) == 0) && (!a.mask_h || (((uintptr_t)a.mask_h & 15) == 0));
     const bool vec = g.a_vec && g.b_vec && a.K >= 4 && a.N >= 4;
     GM_REQUIRE(!(a.mask_b || a.relu_bits) || g.c_vec, GM_EINVAL, "gemm: packed relu masks need 16-byte aligned C with N %% 4 == 0");
-#define GM_LAUNCH_GEMM(WC_, THREADS_)                                                                                         \
-    do {                                                                                                                      \
-        const dim3 grid(g.n_tiles * g.n_col_tiles), blk(THREADS_);                                                            \
-        GM_LAUNCHED(GM_GEMM_ID_NN(WC_, vec, a.transB ? 1 : 0));                                                               \
-        if (vec && a.transB) hipLaunchKernelGGL((k_gemm_nn<WC_, true, true>), grid, blk, 0, s, g);                             \
-        else if (vec) hipLaunchKernelGGL((k_gemm_nn<WC_, true, false>), grid, blk, 0, s, g);                                   \
-        else if (a.transB) hipLaunchKernelGGL((k_gemm_nn<WC_, false, true>), grid, blk, 0, s, g);                              \
-        else hipLaunchKernelGGL((k_gemm_nn<WC_, false, false>), grid, blk, 0, s, g);                                           \
-    } while (0)
     // column-tile width: the widest (A read once) unless that leaves CUs idle -- small batches are latency-bound, so
     // trade A re-reads (L2 hits, same XCD) for parallelism
     int bn = a.N > 128 ? 256 : a.N > 64 ? 128 : 64;
@@ -626,21 +553,14 @@ static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
     }
     if (dma) {
         const dim3 grid(g.n_tiles * g.n_col_tiles);
-        if (bn == 256) { GM_LAUNCHED(GM_GEMM_ID_GLDS4); hipLaunchKernelGGL((k_gemm_glds<4>), grid, dim3(512), 0, s, g); }
-        else if (bn == 128) { GM_LAUNCHED(GM_GEMM_ID_GLDS2); hipLaunchKernelGGL((k_gemm_glds<2>), grid, dim3(256), 0, s, g); }
-        else {
-            // 8 x (32 x 32) waves per 128 x 64 tile when the launch leaves CUs mostly empty
-            if ((int64_t)g.n_tiles * g.n_col_tiles <= 4 * gm_num_cus()) { GM_LAUNCHED(GM_GEMM_ID_GLDS_SMALL); hipLaunchKernelGGL(k_gemm_glds_small, grid, dim3(512), 0, s, g); }
-            else { GM_LAUNCHED(GM_GEMM_ID_GLDS1); hipLaunchKernelGGL((k_gemm_glds<1>), grid, dim3(128), 0, s, g); }
-        }
-        GM_HIP(hipGetLastError());
-        return GM_OK;
-    }
-    if (bn == 256) GM_LAUNCH_GEMM(4, 512);
-    else if (bn == 128) GM_LAUNCH_GEMM(2, 256);
-    else GM_LAUNCH_GEMM(1, 128);
-#undef GM_LAUNCH_GEMM
-#undef GM_LAUNCHED
+        if (bn == 256) GM_TRY(launch_kernel(k_gemm_glds<2, 4, 2>, grid, dim3(512), 0, s, g, a.launched, GM_GEMM_ID_GLDS4));
+        else if (bn == 128) GM_TRY(launch_kernel(k_gemm_glds<2, 2, 2>, grid, dim3(256), 0, s, g, a.launched, GM_GEMM_ID_GLDS2));
+        // 8 x (32 x 32) waves per 128 x 64 tile when the launch leaves CUs mostly empty
+        else if ((int64_t)g.n_tiles * g.n_col_tiles <= 4 * gm_num_cus()) GM_TRY(launch_kernel(k_gemm_glds<4, 2, 1>, grid, dim3(512), 0, s, g, a.launched, GM_GEMM_ID_GLDS_SMALL));
+        else GM_TRY(launch_kernel(k_gemm_glds<2, 1, 2>, grid, dim3(128), 0, s, g, a.launched, GM_GEMM_ID_GLDS1));
+    } else if (bn == 256) GM_TRY(launch_gemm_exact<4>(a, g, vec, s));
+    else if (bn == 128) GM_TRY(launch_gemm_exact<2>(a, g, vec, s));
+    else GM_TRY(launch_gemm_exact<1>(a, g, vec, s));
     GM_HIP(hipGetLastError());
     return GM_OK;
 }
@@ -987,7 +907,6 @@ __global__ __launch_bounds__(WGS_THREADS) void k_wgrad_split(WgradK w) {
     constexpr int plane[2] = {A_PLANE, G_PLANE};
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
-        constexpr int dummy = 0; (void)dummy;
         const int W = it == 0 ? K : N;                                              // columns of this operand
         valid[it] = wave_u * 64 < 2 * W;                                            // (wave-uniform)
         const int oct = valid[it] ? (wave_u * 64) / W : 0, c = valid[it] ? tid - oct * W : 0;
@@ -1211,23 +1130,13 @@ template <int KT, int NT>
 static int launch_wgrad_split(const WgradK& w, hipStream_t s, int np, bool dead_rows) {
     constexpr int K = KT * 128, N = NT * 128;
     const size_t lds = 2 * 32 * (size_t)np * (size_t)(K + N);
-    if (dead_rows && w.f2) {                             // (three-piece kernels only: launch_wgrad checks)
-        GM_TRY(gm_func_full_lds((const void*)k_wgrad_split<KT, NT, 3, true, true>));
-        hipLaunchKernelGGL((k_wgrad_split<KT, NT, 3, true, true>), dim3(w.n_chunks), dim3(WGS_THREADS), lds, s, w);
-    } else if (dead_rows) {
-        GM_TRY(gm_func_full_lds((const void*)k_wgrad_split<KT, NT, 3, false, true>));
-        hipLaunchKernelGGL((k_wgrad_split<KT, NT, 3, false, true>), dim3(w.n_chunks), dim3(WGS_THREADS), lds, s, w);
-    } else if (w.f2) {                                          // A formed from the per-row source table (three-piece kernels only: launch_wgrad checks)
-        GM_TRY(gm_func_full_lds((const void*)k_wgrad_split<KT, NT, 3, true>));
-        hipLaunchKernelGGL((k_wgrad_split<KT, NT, 3, true>), dim3(w.n_chunks), dim3(WGS_THREADS), lds, s, w);
-    } else if (np == 2) {
-        GM_TRY(gm_func_full_lds((const void*)k_wgrad_split<KT, NT, 2>));
-        hipLaunchKernelGGL((k_wgrad_split<KT, NT, 2>), dim3(w.n_chunks), dim3(WGS_THREADS), lds, s, w);
-    } else {
-        GM_TRY(gm_func_full_lds((const void*)k_wgrad_split<KT, NT, 3>));
-        hipLaunchKernelGGL((k_wgrad_split<KT, NT, 3>), dim3(w.n_chunks), dim3(WGS_THREADS), lds, s, w);
-    }
-    return GM_OK;
+    auto go = [&](void (*kernel)(WgradK)) { return launch_kernel(kernel, dim3(w.n_chunks), dim3(WGS_THREADS), lds, s, w, nullptr, 0, true); };
+    // flagged rows of G and an A formed from the per-row source table: three-piece kernels only (launch_wgrad checks)
+    if (dead_rows && w.f2) return go(k_wgrad_split<KT, NT, 3, true, true>);
+    if (dead_rows) return go(k_wgrad_split<KT, NT, 3, false, true>);
+    if (w.f2) return go(k_wgrad_split<KT, NT, 3, true>);
+    if (np == 2) return go(k_wgrad_split<KT, NT, 2>);
+    return go(k_wgrad_split<KT, NT, 3>);
 }
 
 // out_t[j] = sum over the set's chunks of partial[c][j];  j < K*N -> dW, else db.
@@ -1236,55 +1145,74 @@ struct WgradSgd {
     int pl_np; gm_bound pl_bound;       // planes as two fp16 pieces under pl_bound (pl_np == 2) or three bf16 pieces
 };
 
-__device__ __forceinline__ void wgrad_reduce_body(const float* partial, const int32_t* set_chunk_off, int KN, int N, float* dW, int64_t dw_stride,
+// sum over the set's chunks [c0, c1) of partial[c][j]: 8 independent loads in flight; the summation order is fixed (deterministic), just not sequential
+__device__ __forceinline__ float wgrad_chunk_sum(const float* partial, int c0, int c1, int tot, int j) {
+    float s8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int c = c0;
+    for (; c + 8 <= c1; c += 8) {
+#pragma unroll
+        for (int u_ = 0; u_ < 8; ++u_) s8[u_] += partial[(int64_t)(c + u_) * tot + j];
+    }
+    for (int u_ = 0; c < c1; ++c, ++u_) s8[u_] += partial[(int64_t)c * tot + j];
+    return ((s8[0] + s8[1]) + (s8[2] + s8[3])) + ((s8[4] + s8[5]) + (s8[6] + s8[7]));
+}
+// the SGD step of W[k][n] (j = k N + n) with gradient s: the new weight, stored to the next fast weights and, transposed, to wt
+__device__ __forceinline__ float wgrad_weight_step(const WgradSgd& u, int set, int K, int N, int k, int n, float s) {
+    const int64_t j = (int64_t)k * N + n;
+    const float wn = u.cur[(int64_t)set * u.cur_stride + u.w_off + j] - u.lr * s;
+    u.next[(int64_t)set * u.next_stride + u.w_off + j] = wn;
+    if (u.wt) u.wt[(int64_t)set * K * N + (int64_t)n * K + k] = wn;
+    return wn;
+}
+// db[n] = s and the SGD step of the bias
+__device__ __forceinline__ void wgrad_bias_step(float* db, int64_t db_stride, const WgradSgd& u, int set, int n, float s) {
+    db[(int64_t)set * db_stride + n] = s;
+    if (u.next) u.next[(int64_t)set * u.next_stride + u.b_off + n] = u.cur[(int64_t)set * u.cur_stride + u.b_off + n] - u.lr * s;
+}
+// The new weight as the next step's GEMM operand pieces (bit patterns): three bf16 by exact truncation, or (pl_np == 2) two fp16 under the
+// set's scale, p[2] = 0
+__device__ __forceinline__ void wgrad_weight_pieces(const WgradSgd& u, int set, float wn, uint16_t (&p)[3]) {
+    if (u.pl_np == 2) {
+        const float xs = wn * gs_bound_scale_v(u.pl_bound, set);
+        if (u.pl_bound.viol && fabsf(xs) > 65504.f && fabsf(wn) < INFINITY) atomicOr(u.pl_bound.viol, GM_VIOL_WEIGHT);      // the fast weight outgrew the step's bound
+        const _Float16 h = (_Float16)xs, m = (_Float16)(xs - (float)h);
+        p[0] = __builtin_bit_cast(uint16_t, h); p[1] = __builtin_bit_cast(uint16_t, m); p[2] = 0;
+    } else {
+        const uint32_t bh = __float_as_uint(wn) & 0xffff0000u;
+        const float r1 = wn - __uint_as_float(bh);
+        const uint32_t bm = __float_as_uint(r1) & 0xffff0000u;
+        const uint32_t bl = __float_as_uint(r1 - __uint_as_float(bm));
+        p[0] = (uint16_t)(bh >> 16); p[1] = (uint16_t)(bm >> 16); p[2] = (uint16_t)(bl >> 16);
+    }
+}
+
+// Element per thread: the planes (if any) leave as scattered 2-byte stores.
+__device__ __forceinline__ void wgrad_reduce_body(const float* partial, const int32_t* set_chunk_off, int K, int N, float* dW, int64_t dw_stride,
                                                   float* db, int64_t db_stride, const WgradSgd& u, const int bx, const int gx) {
     const int set = blockIdx.y;
     const int c0 = set_chunk_off[set], c1 = set_chunk_off[set + 1];
-    const int tot = KN + N;
+    const int KN = K * N, tot = KN + N;
     for (int j = bx * blockDim.x + threadIdx.x; j < tot; j += gx * blockDim.x) {
-        // 8 independent loads in flight; the summation order is fixed (deterministic), just not sequential
-        float s8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        int c = c0;
-        for (; c + 8 <= c1; c += 8) {
-#pragma unroll
-            for (int u_ = 0; u_ < 8; ++u_) s8[u_] += partial[(int64_t)(c + u_) * tot + j];
-        }
-        for (int u_ = 0; c < c1; ++c, ++u_) s8[u_] += partial[(int64_t)c * tot + j];
-        const float s = ((s8[0] + s8[1]) + (s8[2] + s8[3])) + ((s8[4] + s8[5]) + (s8[6] + s8[7]));
+        const float s = wgrad_chunk_sum(partial, c0, c1, tot, j);
         if (j < KN) {
             dW[(int64_t)set * dw_stride + j] = s;
             if (u.next) {
-                const float wn = u.cur[(int64_t)set * u.cur_stride + u.w_off + j] - u.lr * s;
-                u.next[(int64_t)set * u.next_stride + u.w_off + j] = wn;
-                if (u.wt) { const int k = j / N, n = j - k * N; u.wt[(int64_t)set * KN + (int64_t)n * (KN / N) + k] = wn; }
-                if (u.pl_fwd || u.pl_dz) {          // exact 3-way bf16 split of the new weight, straight into the next step's GEMM operand planes
-                    const int K = KN / N, k = j / N, n = j - k * N;
-                    uint32_t bh, bm, bl = 0;
-                    if (u.pl_np == 2) {             // two fp16 pieces under the set's scale (bit patterns in the high halves, as below)
-                        const float xs = wn * gs_bound_scale_v(u.pl_bound, set);
-                        if (u.pl_bound.viol && fabsf(xs) > 65504.f && fabsf(wn) < INFINITY) atomicOr(u.pl_bound.viol, GM_VIOL_WEIGHT);
-                        const _Float16 h = (_Float16)xs, m = (_Float16)(xs - (float)h);
-                        bh = (uint32_t)__builtin_bit_cast(uint16_t, h) << 16; bm = (uint32_t)__builtin_bit_cast(uint16_t, m) << 16;
-                    } else {
-                        const uint32_t bx = __float_as_uint(wn); bh = bx & 0xffff0000u;
-                        const float r1 = wn - __uint_as_float(bh);
-                        bm = __float_as_uint(r1) & 0xffff0000u;
-                        bl = __float_as_uint(r1 - __uint_as_float(bm));
-                    }
+                const int k = j / N, n = j - k * N;
+                const float wn = wgrad_weight_step(u, set, K, N, k, n, s);
+                if (u.pl_fwd || u.pl_dz) {          // the pieces of the new weight, straight into the next step's GEMM operand planes
+                    uint16_t p[3];
+                    wgrad_weight_pieces(u, set, wn, p);
                     if (u.pl_fwd) {                 // B[k][n] = W[k][n]  ->  [k/8][n][8]
                         uint16_t* o = u.pl_fwd + (int64_t)set * 3 * KN + ((int64_t)(k >> 3) * N + n) * 8 + (k & 7);
-                        o[0] = (uint16_t)(bh >> 16); o[KN] = (uint16_t)(bm >> 16); if (u.pl_np != 2) o[2 * (int64_t)KN] = (uint16_t)(bl >> 16);
+                        o[0] = p[0]; o[KN] = p[1]; if (u.pl_np != 2) o[2 * (int64_t)KN] = p[2];
                     }
                     if (u.pl_dz) {                  // B[k'][n'] = W[n'][k'] (k' = n, n' = k)  ->  [n/8][k][8]
                         uint16_t* o = u.pl_dz + (int64_t)set * 3 * KN + ((int64_t)(n >> 3) * K + k) * 8 + (n & 7);
-                        o[0] = (uint16_t)(bh >> 16); o[KN] = (uint16_t)(bm >> 16); if (u.pl_np != 2) o[2 * (int64_t)KN] = (uint16_t)(bl >> 16);
+                        o[0] = p[0]; o[KN] = p[1]; if (u.pl_np != 2) o[2 * (int64_t)KN] = p[2];
                     }
                 }
             }
-        } else if (db) {
-            db[(int64_t)set * db_stride + (j - KN)] = s;
-            if (u.next) u.next[(int64_t)set * u.next_stride + u.b_off + (j - KN)] = u.cur[(int64_t)set * u.cur_stride + u.b_off + (j - KN)] - u.lr * s;
-        }
+        } else if (db) wgrad_bias_step(db, db_stride, u, set, j - KN, s);
     }
 }
 
@@ -1298,47 +1226,22 @@ __device__ __forceinline__ void wgrad_reduce_pl_body(const float* partial, const
     const int set = blockIdx.y, tid = threadIdx.x;
     const int c0 = set_chunk_off[set], c1 = set_chunk_off[set + 1];
     const int KN = K * N, tot = KN + N, npn = N / 32, n_patch = (K / 8) * npn;
-    auto sum_of = [&](int j) -> float {
-        float s8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        int c = c0;
-        for (; c + 8 <= c1; c += 8) {
-#pragma unroll
-            for (int u_ = 0; u_ < 8; ++u_) s8[u_] += partial[(int64_t)(c + u_) * tot + j];
-        }
-        for (int u_ = 0; c < c1; ++c, ++u_) s8[u_] += partial[(int64_t)c * tot + j];
-        return ((s8[0] + s8[1]) + (s8[2] + s8[3])) + ((s8[4] + s8[5]) + (s8[6] + s8[7]));      // same order as k_wgrad_reduce
-    };
     if (bx >= n_patch) {                                    // db (and the bias step)
         const int n = (bx - n_patch) * 256 + tid;
-        if (n < N && db) {
-            const float s = sum_of(KN + n);
-            db[(int64_t)set * db_stride + n] = s;
-            if (u.next) u.next[(int64_t)set * u.next_stride + u.b_off + n] = u.cur[(int64_t)set * u.cur_stride + u.b_off + n] - u.lr * s;
-        }
+        if (n < N && db) wgrad_bias_step(db, db_stride, u, set, n, wgrad_chunk_sum(partial, c0, c1, tot, KN + n));
         return;
     }
     const int kb = bx / npn, nb = bx - kb * npn, tk = tid >> 5, tn = tid & 31;
     const int k = kb * 8 + tk, n = nb * 32 + tn, j = k * N + n;
-    const float s = sum_of(j);
+    const float s = wgrad_chunk_sum(partial, c0, c1, tot, j);
     dW[(int64_t)set * dw_stride + j] = s;
     if (!u.next) return;                                    // (uniform)
-    const float wn = u.cur[(int64_t)set * u.cur_stride + u.w_off + j] - u.lr * s;
-    u.next[(int64_t)set * u.next_stride + u.w_off + j] = wn;
-    if (u.wt) u.wt[(int64_t)set * KN + (int64_t)n * K + k] = wn;
+    const float wn = wgrad_weight_step(u, set, K, N, k, n, s);
     if (!(u.pl_fwd || u.pl_dz)) return;                     // (uniform)
     const int np = u.pl_np == 2 ? 2 : 3;
-    if (np == 2) {                                          // two fp16 pieces under the set's scale
-        const float xs = wn * gs_bound_scale_v(u.pl_bound, set);
-        if (u.pl_bound.viol && fabsf(xs) > 65504.f && fabsf(wn) < INFINITY) atomicOr(u.pl_bound.viol, GM_VIOL_WEIGHT);      // the fast weight outgrew the step's bound
-        const _Float16 h = (_Float16)xs, m = (_Float16)(xs - (float)h);
-        pl[0][tk][tn] = __builtin_bit_cast(uint16_t, h); pl[1][tk][tn] = __builtin_bit_cast(uint16_t, m);
-    } else {
-        const uint32_t bits = __float_as_uint(wn), bh = bits & 0xffff0000u;
-        const float r1 = wn - __uint_as_float(bh);
-        const uint32_t bm = __float_as_uint(r1) & 0xffff0000u;
-        const uint32_t bl = __float_as_uint(r1 - __uint_as_float(bm));
-        pl[0][tk][tn] = (uint16_t)(bh >> 16); pl[1][tk][tn] = (uint16_t)(bm >> 16); pl[2][tk][tn] = (uint16_t)(bl >> 16);
-    }
+    uint16_t p3[3];
+    wgrad_weight_pieces(u, set, wn, p3);
+    pl[0][tk][tn] = p3[0]; pl[1][tk][tn] = p3[1]; if (np == 3) pl[2][tk][tn] = p3[2];
     __syncthreads();
     if (tid < 32 * np && u.pl_fwd) {                             // forward planes: unit (plane, n) = the patch's 8 k of column n
         const int p = tid >> 5, c = tid & 31;
@@ -1365,7 +1268,7 @@ struct RedK {
 __device__ __forceinline__ void wgrad_reduce_one(const RedK& r, const int bx) {
     if (bx >= r.gx) return;
     if (r.use_pl) wgrad_reduce_pl_body(r.partial, r.set_chunk_off, r.K, r.N, r.dW, r.dw_stride, r.db, r.db_stride, r.u, bx);
-    else wgrad_reduce_body(r.partial, r.set_chunk_off, r.K * r.N, r.N, r.dW, r.dw_stride, r.db, r.db_stride, r.u, bx, r.gx);
+    else wgrad_reduce_body(r.partial, r.set_chunk_off, r.K, r.N, r.dW, r.dw_stride, r.db, r.db_stride, r.u, bx, r.gx);
 }
 __global__ __launch_bounds__(256) void k_wgrad_reduce(RedK r) { wgrad_reduce_one(r, blockIdx.x); }
 // The reductions of SEVERAL layers in one launch (blockIdx.z = layer): the backward of gm_meta_step holds the reductions of the layers above
@@ -1392,10 +1295,13 @@ static bool wgrad_takes_split(const gm_wgrad_args& a) {
 // Would a weight gradient over `n_chunks` row chunks with these widths run on the split kernel -- the one that can form its A operand from the per-row
 // source table (gm_wgrad_args::fuse2)?  The forward of a differentiated pass asks before it leaves Z_l unwritten (model.hip).
 bool gm_wgrad_gather_ok(int n_chunks, int K, int N) { return wgrad_split_shape_ok(n_chunks, K, N); }
+// pieces per operand of the split weight gradient: two fp16 where both operands carry a bound, else three bf16
+static int wgrad_np(const gm_wgrad_args& a) { return (a.np == 2 && a.a_bound.amax && a.g_bound.amax) ? 2 : 3; }
 int gm_launch_wgrad(const gm_wgrad_args& a, hipStream_t s) {
-    GM_REQUIRE(a.pick != GM_WGRAD_PICK_SPLIT || wgrad_takes_split(a), GM_EINVAL,
+    const bool split = wgrad_takes_split(a);
+    GM_REQUIRE(a.pick != GM_WGRAD_PICK_SPLIT || split, GM_EINVAL,
                "wgrad: the split kernel needs K, N in {128, 256}, no Gb / row indirection and 16-byte aligned operands (K=%d N=%d)", a.K, a.N);
-    const int cat = wgrad_takes_split(a) ? ((a.np == 2 && a.a_bound.amax && a.g_bound.amax) ? GM_PROF_WGRAD_SPLIT16 : GM_PROF_WGRAD_SPLIT) : GM_PROF_WGRAD;
+    const int cat = split ? (wgrad_np(a) == 2 ? GM_PROF_WGRAD_SPLIT16 : GM_PROF_WGRAD_SPLIT) : GM_PROF_WGRAD;
     gm_prof_begin(cat, s, 2 * a.rows * a.K * a.N);
     gm_prof_note(GM_PROF_WGRAD_BYTES, 4 * a.rows * ((int64_t)a.K + a.N));
     const int rc = launch_wgrad(a, s);
@@ -1434,13 +1340,13 @@ static int launch_wgrad(const gm_wgrad_args& a, hipStream_t s) {
     w.a_scale = a.a_scale; w.chunks = a.chunks; w.n_chunks = a.n_chunks; w.partial = a.partial;
     w.TK = (a.K + 31) / 32; w.TN = (a.N + 31) / 32;
     bool launched = false;
-    const bool fast_ok = wgrad_fast_ok(a);
-    GM_REQUIRE(!a.fuse2 || (wgrad_takes_split(a) && a.gx && a.np != 2 && a.lda <= (int64_t)(1 << 20) && a.ldgx <= (int64_t)(1 << 20)), GM_EINVAL,
+    const bool fast_ok = wgrad_fast_ok(a), split = wgrad_takes_split(a);
+    GM_REQUIRE(!a.fuse2 || (split && a.gx && a.np != 2 && a.lda <= (int64_t)(1 << 20) && a.ldgx <= (int64_t)(1 << 20)), GM_EINVAL,
                "wgrad: a table-formed A operand needs the split kernel (K=%d N=%d chunks=%d)", a.K, a.N, a.n_chunks);
-    GM_REQUIRE(!a.g_keep || (wgrad_takes_split(a) && !(a.np == 2 && a.a_bound.amax && a.g_bound.amax)), GM_EINVAL,
+    GM_REQUIRE(!a.g_keep || (split && wgrad_np(a) != 2), GM_EINVAL,
                "wgrad: flagged rows of G need the three-piece split kernel (K=%d N=%d chunks=%d)", a.K, a.N, a.n_chunks);
-    if (wgrad_takes_split(a)) {
-        const int np = (a.np == 2 && a.a_bound.amax && a.g_bound.amax) ? 2 : 3;
+    if (split) {
+        const int np = wgrad_np(a);
         const bool dr = a.g_keep != nullptr;
         if (dr) w.a_scale = a.g_keep;
         if (a.fuse2) { w.f2 = (const int4*)a.fuse2; w.gx = a.gx; w.ldgx = a.ldgx; w.zrow = gm_zero_row(s); GM_REQUIRE(w.zrow, GM_ENOMEM, "wgrad: no zero row"); }

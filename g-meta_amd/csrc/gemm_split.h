@@ -62,8 +62,8 @@ struct SplitGemmK {
     const float* row_scale; const float* bias; int64_t bias_stride; const float* mask_h; int relu;
     const uint8_t* mask_b; uint8_t* relu_bits;
     const int32_t* tiles; int n_tiles; int n_col_tiles; int nt_store;
-    unsigned long long* dbg;                   // experiment: per-iteration timestamps of one workgroup (FC_TRACE)
-    int dephase;                               // k_gemm_split_h: s_sleep(127) count for the second-slot workgroups
+    unsigned long long* dbg;                   // unused; kept so the split kernels' argument layout stays as it is
+    int dephase;                               // unused; kept so the split kernels' argument layout stays as it is
     // k_gemm_split_p<true> (fused aggregate + GEMM): A / lda address the aggregate's INPUT rows, f2 is the per-row source table, rows
     // flagged GM_SPLIT_FUSE_SELF read their finished aggregate from zside (row stride ldz), rows without a source read zeros
     float* zero_out;                           // optional [rows, ldc]: the epilogue also zero-fills this buffer's tile (dQ of the backward pass that follows)

@@ -377,10 +377,10 @@ struct gm_gemm_args {
                                         // numerics-test export gm_dense_gemm; the product path leaves it NULL
 };
 // gm_gemm_args::launched
-#define GM_GEMM_ID_GLDS4 1              // k_gemm_glds<4>
-#define GM_GEMM_ID_GLDS2 2              // k_gemm_glds<2>
-#define GM_GEMM_ID_GLDS1 3              // k_gemm_glds<1>
-#define GM_GEMM_ID_GLDS_SMALL 4         // k_gemm_glds_small
+#define GM_GEMM_ID_GLDS4 1              // k_gemm_glds<2, 4, 2>
+#define GM_GEMM_ID_GLDS2 2              // k_gemm_glds<2, 2, 2>
+#define GM_GEMM_ID_GLDS1 3              // k_gemm_glds<2, 1, 2>
+#define GM_GEMM_ID_GLDS_SMALL 4         // k_gemm_glds<4, 2, 1>
 #define GM_GEMM_ID_NN(WC, VEC, TB) (10 + 4 * ((WC) == 4 ? 2 : (WC) == 2 ? 1 : 0) + 2 * (VEC) + (TB))     // k_gemm_nn<WC, VEC, TB>: 10 .. 21
 #define GM_GEMM_ID_SPLIT(GATHER, MI, WC, NP) (30 + 10 * (GATHER) + ((MI) == 2 ? 0 : (WC) == 4 ? 2 : 4) + ((NP) == 2))   // k_gemm_split_p: 30 .. 35, 40 .. 45
 #define GM_GEMM_BM 128

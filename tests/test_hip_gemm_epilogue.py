@@ -311,14 +311,23 @@ def check_run(case, r, rows, relu, mask=None, stored=None, exact_out=None, what=
 # (kernel, batch, K, N, Case options, run options).  The DMA kernels need K % 16 == 0, 16-byte aligned x / W / bias and N a multiple of the
 # column tile; anything else, a transposed W or mask_b takes k_gemm_nn<WC, VEC, TB>.  WC follows from the tile count and N (256 / 128 / 64-wide
 # column tiles), VEC from the alignment of x and W and K, N >= 4.
+# The DMA pipeline has three regimes, each run on every DMA instantiation: K = 32 (two chunks, no refill), K = 48 (three chunks, each LDS stage
+# used once), K >= 64 (stages reused); one row per instantiation has ldc > N (zero_out by memset instead of in the epilogue).
 EXACT_CASES = [
     ('glds<4>', 'arxiv', 64, 256, {}, {}),
     ('glds<4>', 'arxiv', 32, 256, {}, {'ldc': 260}),                       # zero_out by memset
+    ('glds<4>', 'arxiv', 48, 256, {}, {}),
     ('glds<2>', 'capped', 128, 256, {}, {}),
     ('glds<2>', 'capped', 48, 128, {'shared_w': True}, {'ldc': 132}),
+    ('glds<2>', 'capped', 32, 128, {}, {}),
+    ('glds<2>', 'capped', 64, 128, {}, {}),
     ('glds<1>', 'capped', 64, 64, {}, {}),
+    ('glds<1>', 'capped', 32, 64, {}, {'ldc': 68}),
+    ('glds<1>', 'capped', 48, 64, {'shared_w': True}, {}),
     ('glds_small', 'short', 256, 256, {}, {}),
     ('glds_small', 'short', 32, 64, {}, {'ldc': 68}),
+    ('glds_small', 'short', 48, 64, {}, {}),
+    ('glds_small', 'short', 64, 64, {'shared_w': True}, {}),
     ('nn<4,1,0>', 'arxiv', 64, 256, {'bias_off': True}, {}),
     ('nn<4,1,1>', 'arxiv', 64, 256, {'trans': True}, {}),
     ('nn<4,0,0>', 'arxiv', 64, 256, {'xoff': True}, {}),

@@ -1,6 +1,8 @@
-// Micro-benchmark + accuracy check of the split-bf16 fp32 GEMM (g-meta_amd/csrc/gemm_split.h) against an fp64 reference
-// and the plain fp32 fmaf chain, at the arxiv query-layer shape (rows x 256 x 256).
-//   hipcc --offload-arch=gfx950 -O3 -o tools/_build/gemm_split_bench tools/gemm_split_bench.hip && tools/_build/gemm_split_bench
+// Micro-benchmark + accuracy check of the split-bf16 fp32 GEMM (g-meta_amd/csrc/gemm_split.h: the persistent three-piece kernel the library ships,
+// 128 x 256 tiles) against an fp64 reference and the plain fp32 fmaf chain, at the arxiv query-layer shape (rows x 256 x 256).
+//   hipcc --offload-arch=gfx950 -O3 -o tools/_build/gemm_split_bench tools/gemm_split_bench.hip && tools/_build/gemm_split_bench [M [K [N]]]
+// Environment: GS_HALF=1 64-row half tiles (two workgroups per tile), GS_GRID=n grid cap (default 256), GS_NT=0 ordinary C stores,
+// GS_SLEEP_US=n "cool chip" mode.  Exit status 0 if the error against fp64 is within 20x the fmaf chain's, else 2.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -8,18 +10,16 @@
 #include <vector>
 #include <algorithm>
 #include <unistd.h>
-#include "gemm_split_experiments.h"     // includes g-meta_amd/csrc/gemm_split.h + the prototype kernels
+#include "../g-meta_amd/csrc/gemm_split.h"
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s failed: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
 
-template <int WC, int BK> static void run(SplitGemmK g, hipStream_t s) {
-    hipLaunchKernelGGL((k_gemm_split<WC, BK>), dim3(g.n_tiles * g.n_col_tiles), dim3(128 * WC), 0, s, g);
-}
-
 int main(int argc, char** argv) {
     const int M = argc > 1 ? atoi(argv[1]) : 1146880, K = argc > 2 ? atoi(argv[2]) : 256, N = argc > 3 ? atoi(argv[3]) : 256;
-    const int WC = argc > 4 ? atoi(argv[4]) : 4, BK = argc > 5 ? atoi(argv[5]) : 32;
-    printf("M=%d K=%d N=%d WC=%d BK=%d\n", M, K, N, WC, BK);
+    if (M <= 0 || K < 32 || K % 16 || N != 256) { printf("usage: gemm_split_bench [M [K [N]]]   K a multiple of 16, at least 32; N = 256 (the 256-wide tiles)\n"); return 1; }
+    const bool half = getenv("GS_HALF") != nullptr;
+    const int cap = getenv("GS_GRID") ? atoi(getenv("GS_GRID")) : 256;
+    printf("M=%d K=%d N=%d %s tiles, grid cap %d\n", M, K, N, half ? "half" : "full", cap);
     std::vector<float> A((size_t)M * K), W((size_t)K * N), bias(N);
     srand(1);
     auto rnd = []() { return (float)((rand() / (double)RAND_MAX) * 2.0 - 1.0); };
@@ -36,17 +36,10 @@ int main(int argc, char** argv) {
     hipLaunchKernelGGL(k_split_w, dim3((K + 31) / 32, (N + 31) / 32, 1), dim3(256), 0, 0, dW, 0, 0, K, N, 0, dBt, 3, gm_no_bound());
     SplitGemmK g{};
     g.A = dA; g.lda = K; g.Bt = dBt; g.bt_stride = 0; g.C = dC; g.ldc = N; g.K = K; g.N = N; g.bias = dBias; g.relu = 0;
-    unsigned long long* dDbg; CK(hipMalloc(&dDbg, 3 * 64 * 4 * 8)); CK(hipMemset(dDbg, 0, 3 * 64 * 4 * 8)); g.dbg = dDbg;
-    g.tiles = dT; g.n_tiles = (int)tiles.size() / 3; g.n_col_tiles = N / (64 * WC); g.nt_store = getenv("GS_NT") ? atoi(getenv("GS_NT")) : 1;
-    const bool fc = argc > 6 && atoi(argv[6]) == 1, pers = argc > 6 && atoi(argv[6]) == 2, halfk = argc > 6 && atoi(argv[6]) == 3, roll = argc > 6 && atoi(argv[6]) == 4;
-    g.dephase = getenv("GS_DEPHASE") ? atoi(getenv("GS_DEPHASE")) : 2;
+    g.tiles = dT; g.n_tiles = (int)tiles.size() / 3; g.n_col_tiles = 1; g.nt_store = getenv("GS_NT") ? atoi(getenv("GS_NT")) : 1;
     auto launch = [&]() {
-        if (roll) { static const int cap = getenv("GS_GRID") ? atoi(getenv("GS_GRID")) : 256; hipLaunchKernelGGL(k_gemm_split_r, dim3(std::min(g.n_tiles, cap)), dim3(1024), 0, 0, g); return; }
-        if (halfk) { hipLaunchKernelGGL(k_gemm_split_h, dim3(std::min(2 * g.n_tiles, 512)), dim3(512), 0, 0, g); return; }
-        if (pers) { static const int cap = getenv("GS_GRID") ? atoi(getenv("GS_GRID")) : 256; if (getenv("GS_HALF")) hipLaunchKernelGGL((k_gemm_split_p<false, 1>), dim3(std::min(2 * g.n_tiles, cap)), dim3(1024), 0, 0, g); else hipLaunchKernelGGL((k_gemm_split_p<false, 2>), dim3(std::min(g.n_tiles, cap)), dim3(1024), 0, 0, g); return; }
-        if (fc) { hipLaunchKernelGGL(k_gemm_split_fc, dim3(g.n_tiles * g.n_col_tiles), dim3(640 + 64 * FC_NB), 0, 0, g); return; }
-        if (BK == 32) { printf("BK=32 removed\n"); exit(1); }
-        else { if (WC == 4) run<4, 16>(g, 0); else if (WC == 2) run<2, 16>(g, 0); else run<1, 16>(g, 0); }
+        if (half) hipLaunchKernelGGL((k_gemm_split_p<false, 1>), dim3(std::min(2 * g.n_tiles, cap)), dim3(1024), 0, 0, g);
+        else hipLaunchKernelGGL((k_gemm_split_p<false, 2>), dim3(std::min(g.n_tiles, cap)), dim3(1024), 0, 0, g);
     };
     launch();
     CK(hipDeviceSynchronize());
@@ -74,18 +67,6 @@ int main(int argc, char** argv) {
     const double fl = 2.0 * M * K * N;
     printf("split-bf16 GEMM: %.3f ms  %.1f TFLOP/s (fp32-equivalent)  %.1f TFLOP/s of bf16 MFMA work  %.2f TB/s of A+C traffic\n", ms, fl / ms / 1e9,
            6 * fl / ms / 1e9, ((double)M * K * 4 + (double)M * N * 4) / ms / 1e9);
-#if defined(FC_TRACE)
-    {
-        std::vector<unsigned long long> d(3 * 64 * 4);
-        CK(hipMemcpy(d.data(), dDbg, d.size() * 8, hipMemcpyDeviceToHost));
-        const char* names[3] = {"compute", "A-feeder", "B-feeder"};
-        const unsigned long long t0 = d[0];
-        for (int r = 0; r < 3; ++r) {
-            printf("%s (ticks since compute chunk 0 start; s_memtime ticks = 100 MHz?)\n", names[r]);
-            for (int c = 0; c < 40; ++c) printf("  c%d: start %lld  issued %lld  ready %lld  after-barrier %lld\n", c, (long long)(d[(r * 64 + c) * 4] - t0), (long long)(d[(r * 64 + c) * 4 + 1] - t0), (long long)(d[(r * 64 + c) * 4 + 2] - t0), (long long)(d[(r * 64 + c) * 4 + 3] - t0));
-        }
-    }
-#endif
     std::vector<float> C((size_t)M * N);
     CK(hipMemcpy(C.data(), dC, C.size() * 4, hipMemcpyDeviceToHost));
     // accuracy on a sample of rows: vs fp64, next to the fp32 fmaf chain's own error
