@@ -8,6 +8,7 @@ LIB_PATH = os.environ.get('GMETA_HIP_LIB') or os.path.join(HERE, 'libgmeta_hip.s
 GM_MAX_GCN = 4
 (F_SUB_OFF, F_SET_SUB_OFF, F_PARENT, F_GRAPH, F_INDPTR, F_INDICES, F_INDPTR_T, F_INDICES_T, F_CENTRE, F_NORM,
  F_FEAT_ROW, F_NORM_SRC, F_NORM_CENTRE) = range(13)
+LINK_SYMMETRIC = 2      # GM_LINK_SYMMETRIC: the link_pred mode of gm_extract / gm_extract_pair with h hops around both endpoints
 
 
 class Seed(C.Structure):

@@ -154,11 +154,81 @@ __device__ __forceinline__ int wave_count(const int64_t a, const int64_t b, cons
     return c;
 }
 
+// The h-hop in-neighbour expansion (H = 1, 2, 3) rooted at `root`, into `seen`; called by the whole workgroup, complete (all bits visible) on return.
+// `xbm` (NEEDX) is the `expanded` bitmap: a set bit means "every in-neighbour of this node is already in `seen`".  That does not depend on the root,
+// so the two roots of a symmetric pair share it: what the first root expanded the second one skips.  `big` / `nbig`: the hub list of hop 2 (this
+// root's; *nbig is zero on entry).
+template <bool G, bool NEEDX>
+__device__ __forceinline__ void expand_root(const ExStore& S, const int64_t base, const int root, const int H, uint32_t* seen, uint32_t* xbm,
+                                            int* big, int* nbig, const int tid, const int lane, const int wave) {
+    const int64_t p0 = S.in_ptr[base + root], p1 = S.in_ptr[base + root + 1];
+    if (tid == 0) { bit_set(seen, root); if (NEEDX) bit_set(xbm, root); }
+    for (int64_t q = p0 + tid; q < p1; q += EX_BLOCK) bit_set(seen, S.in_idx[q]);          // hop 1 (sdp.py:301,305,308)
+    __syncthreads();
+    if (H >= 2) {                                                                         // hop 2 (sdp.py:302,309)
+        // eight frontier nodes per wave at a time; frontier hubs go to the list in `part` and get a whole wave each afterwards
+        const int grp = lane / EX_GL, gl = lane % EX_GL;
+        for (int64_t q0 = p0 + (int64_t)wave * EX_GROUPS; q0 < p1; q0 += (int64_t)EX_WAVES * EX_GROUPS) {
+            const int64_t q = q0 + grp;
+            int v = -1; int64_t a = 0, b = 0;
+            if (q < p1) {
+                v = S.in_idx[q];
+                int first = 1;
+                if constexpr (NEEDX) {
+                    first = 0;
+                    if (gl == 0) { const uint32_t bit = 1u << (v & 31); first = !(atomicOr(&xbm[v >> 5], bit) & bit); }
+                    first = __shfl(first, grp * EX_GL, 64);
+                }
+                if (first) { a = S.in_ptr[base + v]; b = S.in_ptr[base + v + 1]; }
+                if (b - a > EX_BIG_DEG) {
+                    int slot = EX_BLOCK;
+                    if (gl == 0) slot = atomicAdd(nbig, 1);
+                    slot = __shfl(slot, grp * EX_GL, 64);
+                    if (slot < EX_BLOCK) { if (gl == 0) big[slot] = v; b = a; }      // (list full: the group walks it itself)
+                }
+            }
+            for (int64_t r = a + gl; __any(r < b); r += EX_INFL * EX_GL) {
+                int u[EX_INFL];
+#pragma unroll
+                for (int k = 0; k < EX_INFL; ++k) u[k] = r + k * EX_GL < b ? S.in_idx[r + k * EX_GL] : -1;
+#pragma unroll
+                for (int k = 0; k < EX_INFL; ++k) if (u[k] >= 0) bit_set(seen, u[k]);
+            }
+        }
+        __syncthreads();
+        const int nb = min(*nbig, EX_BLOCK);
+        for (int k = wave; k < nb; k += EX_WAVES) wave_mark_preds(S, base, big[k], seen, lane);
+        __syncthreads();
+    }
+    if (H >= 3) {                                                                         // hop 3 (sdp.py:310)
+        for (int64_t q = p0 + wave; q < p1; q += EX_WAVES) {
+            const int v = S.in_idx[q];
+            const int64_t a = S.in_ptr[base + v], b = S.in_ptr[base + v + 1];
+            for (int64_t r = a; r < b; r += GM_WAVE) {
+                int u = -1, first = 0;
+                if (r + lane < b) {
+                    u = S.in_idx[r + lane];
+                    const uint32_t bit = 1u << (u & 31);
+                    first = !(atomicOr(&xbm[u >> 5], bit) & bit);
+                }
+                unsigned long long m = __ballot(first);
+                while (m) {
+                    const int src = __ffsll((long long)m) - 1;
+                    m &= m - 1;
+                    wave_mark_preds(S, base, __shfl(u, src, 64), seen, lane);
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // Phase A: node set (BFS or given), sampling, sorted node list, induced in/out degrees.
 // P16: 16-bit prefix words (LDS bitmaps, subgraphs below 65,536 nodes).  NEEDX: keep the `expanded` bitmap that de-duplicates frontier expansions -- needed from
 // the third hop on (a hop-2 node is reached through many hop-1 nodes); with two hops it only catches parallel edges of the centre, and without it the
 // region behind `seen` shrinks to the 16-bit prefix words.
-template <bool G, bool P16 = false, bool NEEDX = true>
+// SYM: pairs in GM_LINK_SYMMETRIC mode -- h hops around BOTH endpoints (link != 0 then); without it a pair is the reference's: i side two hops, j side one.
+template <bool G, bool P16 = false, bool NEEDX = true, bool SYM = false>
 __global__ __launch_bounds__(EX_BLOCK) void k_nodes(ExStore S, const gm_seed_t* seeds, int n_seeds, int h, int sample_n,
                                                     uint64_t rng_seed, int link, const int32_t* given, const int64_t* given_off,
                                                     int cap, int32_t* nodes_slab, int32_t* degi_slab, int32_t* dego_slab,
@@ -189,69 +259,14 @@ __global__ __launch_bounds__(EX_BLOCK) void k_nodes(ExStore S, const gm_seed_t* 
         for (int64_t k = a + tid; k < b; k += EX_BLOCK) bit_set(seen, given[k]);
         __syncthreads();
     } else {
-        const int H = link ? 2 : h;
-        const int64_t p0 = S.in_ptr[base + ci], p1 = S.in_ptr[base + ci + 1];
-        if (tid == 0) { bit_set(seen, ci); if (NEEDX) bit_set(xbm, ci); }
-        for (int64_t q = p0 + tid; q < p1; q += EX_BLOCK) bit_set(seen, S.in_idx[q]);          // hop 1 (sdp.py:301,305,308)
-        __syncthreads();
-        if (H >= 2) {                                                                         // hop 2 (sdp.py:302,309)
-            // eight frontier nodes per wave at a time; frontier hubs go to the list in `part` and get a whole wave each afterwards
-            const int grp = lane / EX_GL, gl = lane % EX_GL;
-            int* big = part; int* nbig = &sc[5];
-            for (int64_t q0 = p0 + (int64_t)wave * EX_GROUPS; q0 < p1; q0 += (int64_t)EX_WAVES * EX_GROUPS) {
-                const int64_t q = q0 + grp;
-                int v = -1; int64_t a = 0, b = 0;
-                if (q < p1) {
-                    v = S.in_idx[q];
-                    int first = 1;
-                    if constexpr (NEEDX) {
-                        first = 0;
-                        if (gl == 0) { const uint32_t bit = 1u << (v & 31); first = !(atomicOr(&xbm[v >> 5], bit) & bit); }
-                        first = __shfl(first, grp * EX_GL, 64);
-                    }
-                    if (first) { a = S.in_ptr[base + v]; b = S.in_ptr[base + v + 1]; }
-                    if (b - a > EX_BIG_DEG) {
-                        int slot = EX_BLOCK;
-                        if (gl == 0) slot = atomicAdd(nbig, 1);
-                        slot = __shfl(slot, grp * EX_GL, 64);
-                        if (slot < EX_BLOCK) { if (gl == 0) big[slot] = v; b = a; }      // (list full: the group walks it itself)
-                    }
-                }
-                for (int64_t r = a + gl; __any(r < b); r += EX_INFL * EX_GL) {
-                    int u[EX_INFL];
-#pragma unroll
-                    for (int k = 0; k < EX_INFL; ++k) u[k] = r + k * EX_GL < b ? S.in_idx[r + k * EX_GL] : -1;
-#pragma unroll
-                    for (int k = 0; k < EX_INFL; ++k) if (u[k] >= 0) bit_set(seen, u[k]);
-                }
-            }
+        const int H = SYM ? h : (link ? 2 : h);
+        int* big = part; int* nbig = &sc[5];
+        expand_root<G, NEEDX>(S, base, ci, H, seen, xbm, big, nbig, tid, lane, wave);
+        if constexpr (SYM) {                                                                  // j side: the same h hops
+            if (tid == 0) *nbig = 0;                                                          // (the hub list is per root; every wave is past its last read of it)
             __syncthreads();
-            const int nb = min(*nbig, EX_BLOCK);
-            for (int k = wave; k < nb; k += EX_WAVES) wave_mark_preds(S, base, big[k], seen, lane);
-            __syncthreads();
-        }
-        if (H >= 3) {                                                                         // hop 3 (sdp.py:310)
-            for (int64_t q = p0 + wave; q < p1; q += EX_WAVES) {
-                const int v = S.in_idx[q];
-                const int64_t a = S.in_ptr[base + v], b = S.in_ptr[base + v + 1];
-                for (int64_t r = a; r < b; r += GM_WAVE) {
-                    int u = -1, first = 0;
-                    if (r + lane < b) {
-                        u = S.in_idx[r + lane];
-                        const uint32_t bit = 1u << (u & 31);
-                        first = !(atomicOr(&xbm[u >> 5], bit) & bit);
-                    }
-                    unsigned long long m = __ballot(first);
-                    while (m) {
-                        const int src = __ffsll((long long)m) - 1;
-                        m &= m - 1;
-                        wave_mark_preds(S, base, __shfl(u, src, 64), seen, lane);
-                    }
-                }
-            }
-            __syncthreads();
-        }
-        if (link) {                                                                           // j side: 1 hop only (sdp.py:331-333)
+            expand_root<G, NEEDX>(S, base, cj, H, seen, xbm, big, nbig, tid, lane, wave);
+        } else if (link) {                                                                    // j side: 1 hop only (sdp.py:331-333)
             if (tid == 0) bit_set(seen, cj);
             const int64_t a = S.in_ptr[base + cj], b = S.in_ptr[base + cj + 1];
             for (int64_t q = a + tid; q < b; q += EX_BLOCK) bit_set(seen, S.in_idx[q]);
@@ -1079,7 +1094,13 @@ static int extract_impl(const gm_store_t* store, const gm_seed_t* seeds, int n_p
     const int32_t split = parts[0].n_seeds;                  // seeds [0, split): part 0
     const bool given = nodes_flat != nullptr;
     GM_REQUIRE(!given || n_parts == 1, GM_EINVAL, "extract: node lists are given per batch");
+    // `link` is a mode from here on: 0 node seeds, 1 pairs as the reference builds them (h ignored), GM_LINK_SYMMETRIC pairs with h hops around both
+    // endpoints.  Given node lists only need to know that there are two centres.  Past k_nodes everything asks "two centres?" (link != 0).
+    if (given) link = link ? 1 : 0;
+    const bool sym = link == GM_LINK_SYMMETRIC;
     if (!given) {
+        GM_REQUIRE(link == 0 || link == 1 || sym, GM_EINVAL, "extract: link_pred=%d is not a mode (0 node seeds, 1 reference pairs, %d symmetric pairs)", link, GM_LINK_SYMMETRIC);
+        GM_REQUIRE(!sym || (h >= 1 && h <= 3), GM_EINVAL, "extract: h=%d unsupported for symmetric pairs (h in {1,2,3} around both endpoints)", h);
         GM_REQUIRE(link || (h >= 1 && h <= 3), GM_EINVAL, "extract: h=%d unsupported (the reference defines h in {1,2,3}, sdp.py:300-311)", h);
         GM_REQUIRE(sample_nodes >= 1, GM_EINVAL, "extract: sample_nodes must be >= 1");
     }
@@ -1111,13 +1132,18 @@ static int extract_impl(const gm_store_t* store, const gm_seed_t* seeds, int n_p
     if (gpath) lds_a = sizeof(uint32_t) * (EX_BLOCK + 256 + 16);
     // 16-bit prefix words wherever a subgraph stays below 65,536 nodes (GM_EXTRACT_PREF16=0: 32-bit as before); the BFS keeps its `expanded` bitmap from three hops on
     const bool p16 = !gpath && cap < 65536 && gm_knob().extract_pref16;
-    const bool needx = !given && !link && h >= 3;
+    const bool needx = !given && link != 1 && h >= 3;          // (reference pairs stop at two hops whatever h says)
     const size_t Wp = p16 ? ((size_t)Wmax + 1) / 2 : (size_t)Wmax;              // words of the prefix region
     if (!gpath) lds_a = sizeof(uint32_t) * ((size_t)Wmax + ((p16 && !needx) ? Wp : (size_t)Wmax) + EX_BLOCK + 256 + 16);
     hipStream_t st = (hipStream_t)stream;
     GM_TRY(gm_func_full_lds((const void*)k_nodes<false>));
     GM_TRY(gm_func_full_lds((const void*)k_nodes<false, true, true>));
     GM_TRY(gm_func_full_lds((const void*)k_nodes<false, true, false>));
+    if (sym) {
+        GM_TRY(gm_func_full_lds((const void*)k_nodes<false, false, true, true>));
+        GM_TRY(gm_func_full_lds((const void*)k_nodes<false, true, true, true>));
+        GM_TRY(gm_func_full_lds((const void*)k_nodes<false, true, false, true>));
+    }
     GM_TRY(gm_func_full_lds((const void*)k_fill<false>));
     GM_TRY(gm_func_full_lds((const void*)k_fill<false, true>));
     ExStore S{store->d_node_off, store->d_in_ptr, store->d_in_idx, store->d_out_ptr, store->d_out_idx, store->symmetric ? 1 : 0};
@@ -1150,20 +1176,16 @@ static int extract_impl(const gm_store_t* store, const gm_seed_t* seeds, int n_p
         EX_TRY(sg.upload(d_given_off, nodes_off, sizeof(int64_t) * (n_seeds + 1)));
     }
     gm_prof_begin(GM_PROF_EX_NODES, st, n_seeds);
-    if (gpath) {
-        EX_TRY(gm_alloc(&d_gbits, (size_t)n_seeds * 2 * Wmax, st));
-        hipLaunchKernelGGL(k_nodes<true>, dim3(n_seeds), dim3(EX_BLOCK), lds_a, st, S, d_seeds, n_seeds, h, sample_nodes, rng_seed, link ? 1 : 0,
+    if (gpath) EX_TRY(gm_alloc(&d_gbits, (size_t)n_seeds * 2 * Wmax, st));
+    // four launch shapes (global bitmap; LDS with 16-bit prefix words without / with the `expanded` bitmap; LDS, 32-bit), each with its symmetric-pair twin
+    auto launch_nodes = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(n_seeds), dim3(EX_BLOCK), lds_a, st, S, d_seeds, n_seeds, h, sample_nodes, rng_seed, link ? 1 : 0,
                            d_given, d_given_off, (int)cap, d_nodes, d_degi, d_dego, d_nsub, d_esub, Wmax, d_gbits);
-    } else if (p16 && !needx) {
-        hipLaunchKernelGGL((k_nodes<false, true, false>), dim3(n_seeds), dim3(EX_BLOCK), lds_a, st, S, d_seeds, n_seeds, h, sample_nodes, rng_seed, link ? 1 : 0,
-                           d_given, d_given_off, (int)cap, d_nodes, d_degi, d_dego, d_nsub, d_esub, Wmax, (uint32_t*)nullptr);
-    } else if (p16) {
-        hipLaunchKernelGGL((k_nodes<false, true, true>), dim3(n_seeds), dim3(EX_BLOCK), lds_a, st, S, d_seeds, n_seeds, h, sample_nodes, rng_seed, link ? 1 : 0,
-                           d_given, d_given_off, (int)cap, d_nodes, d_degi, d_dego, d_nsub, d_esub, Wmax, (uint32_t*)nullptr);
-    } else {
-        hipLaunchKernelGGL(k_nodes<false>, dim3(n_seeds), dim3(EX_BLOCK), lds_a, st, S, d_seeds, n_seeds, h, sample_nodes, rng_seed, link ? 1 : 0,
-                           d_given, d_given_off, (int)cap, d_nodes, d_degi, d_dego, d_nsub, d_esub, Wmax, (uint32_t*)nullptr);
-    }
+    };
+    if (gpath) { if (sym) launch_nodes(k_nodes<true, false, true, true>); else launch_nodes(k_nodes<true>); }
+    else if (p16 && !needx) { if (sym) launch_nodes(k_nodes<false, true, false, true>); else launch_nodes(k_nodes<false, true, false>); }
+    else if (p16) { if (sym) launch_nodes(k_nodes<false, true, true, true>); else launch_nodes(k_nodes<false, true, true>); }
+    else { if (sym) launch_nodes(k_nodes<false, false, true, true>); else launch_nodes(k_nodes<false>); }
     gm_prof_end(GM_PROF_EX_NODES, st);
     EX_HIP(hipGetLastError());
     const int32_t* nsub = sg.download(d_nsub, (size_t)n_seeds); const int32_t* esub = sg.download(d_esub, (size_t)n_seeds);

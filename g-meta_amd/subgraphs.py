@@ -81,13 +81,19 @@ class SubgraphBatch:
         # gm_seed_t is three packed int32 (graph, i, j): a C-contiguous int32 [n, 3] array has the same layout
         return np.ascontiguousarray(np.asarray(seeds, np.int32).reshape(-1, 3))
 
+    @staticmethod
+    def _link_mode(link_pred):
+        """gm_extract's link_pred mode: False / 0 node seeds, True / 1 pairs as the reference builds them (h ignored), _lib.LINK_SYMMETRIC (2) pairs
+        with h hops around both endpoints.  Anything else is passed on and refused by the library."""
+        return int(link_pred or 0)
+
     @classmethod
     def extract(cls, store, seeds, set_offsets, h, sample_nodes, rng_seed, link_pred):
         arr = cls._seed_array(seeds)
         so = np.ascontiguousarray(set_offsets, np.int32)
         out = C.c_void_p()
         _lib.check(_lib.lib().gm_extract(store.handle, _lib.ptr(arr), len(arr), _lib.ptr(so), len(so) - 1, int(h), int(sample_nodes),
-                                         C.c_uint64(int(rng_seed) & (2 ** 64 - 1)), int(bool(link_pred)), _lib.stream_ptr(), C.byref(out)),
+                                         C.c_uint64(int(rng_seed) & (2 ** 64 - 1)), cls._link_mode(link_pred), _lib.stream_ptr(), C.byref(out)),
                    'gm_extract')
         b = cls(out, store)
         # what the host already knows is never read back from the device (a gm_batch_read synchronises the batch's stream)
@@ -102,7 +108,7 @@ class SubgraphBatch:
         sa, sb = np.ascontiguousarray(set_offsets_a, np.int32), np.ascontiguousarray(set_offsets_b, np.int32)
         oa, ob = C.c_void_p(), C.c_void_p()
         _lib.check(_lib.lib().gm_extract_pair(store.handle, _lib.ptr(aa), len(aa), _lib.ptr(sa), len(sa) - 1, _lib.ptr(ab), len(ab), _lib.ptr(sb), len(sb) - 1,
-                                              int(h), int(sample_nodes), C.c_uint64(int(rng_seed) & (2 ** 64 - 1)), int(bool(link_pred)), _lib.stream_ptr(),
+                                              int(h), int(sample_nodes), C.c_uint64(int(rng_seed) & (2 ** 64 - 1)), cls._link_mode(link_pred), _lib.stream_ptr(),
                                               C.byref(oa), C.byref(ob)), 'gm_extract_pair')
         out = []
         for h_, arr, so in ((oa, aa, sa), (ob, ab, sb)):
@@ -227,7 +233,7 @@ class Subgraphs(Dataset):
     (create_batch_*) follows sdp.py:150-292; `tables=` can replace the CSV files by in-memory
     {'train': (names, labels)} style dictionaries (names 'g_i' or 'g_i_j', labels as in the CSV)."""
 
-    def __init__(self, root, mode, subgraph2label, n_way, k_shot, k_query, batchsz, args, adjs, h, tables=None, verbose=True, sample_mode=None):
+    def __init__(self, root, mode, subgraph2label, n_way, k_shot, k_query, batchsz, args, adjs, h, tables=None, verbose=True, sample_mode=None, link_hops=None):
         self.batchsz, self.n_way, self.k_shot, self.k_query = batchsz, n_way, k_shot, k_query
         # 'device' (default): neighbourhoods above sample_nodes are thinned by the keyed permutation in gm_extract.
         # 'reference': the node sets the REFERENCE would draw for the same global-RNG history (sdp.py:312-314,337-339):
@@ -247,6 +253,19 @@ class Subgraphs(Dataset):
         self.subgraph2label = subgraph2label
         self.link_pred_mode = args.link_pred_mode == 'True'                   # string booleans (train.py:175)
         self.task_setup = args.task_setup
+        # 'reference' (default): a pair's subgraph is generate_subgraph_link_pred's -- 2 hops around i, 1 hop around j, h ignored (sdp.py:327-335).
+        # 'symmetric': the h-hop in-neighbourhood of BOTH endpoints (GM_LINK_SYMMETRIC), for every extraction of this dataset.
+        self.link_hops = link_hops or getattr(args, 'link_hops', 'reference')
+        if self.link_hops not in ('reference', 'symmetric'):
+            raise ValueError("link_hops must be 'reference' or 'symmetric'")
+        if self.link_hops == 'symmetric':
+            if not self.link_pred_mode:
+                raise ValueError("link_hops='symmetric' is a link prediction mode: it needs link_pred_mode='True'")
+            if self.sample_mode == 'reference':
+                raise ValueError("link_hops='symmetric' cannot be combined with sample_mode='reference': the reference has no such mode, so there is no "
+                                 "RNG history of it to replay")
+        # what every gm_extract / gm_extract_pair call of this dataset passes as its link_pred mode
+        self.link_mode = _lib.LINK_SYMMETRIC if self.link_hops == 'symmetric' else int(self.link_pred_mode)
         if not isinstance(adjs, GraphStore):
             raise TypeError('adjs must be a gmeta_amd.GraphStore (graphs + features resident in HBM)')
         self.G = adjs
@@ -510,7 +529,7 @@ class Subgraphs(Dataset):
 
     def _extract_on(self, stream, seeds, off):
         with torch.cuda.stream(stream):
-            b = SubgraphBatch.extract(self.G, seeds, off, self.h, self.sample_nodes, self.rng_seed, self.link_pred_mode)
+            b = SubgraphBatch.extract(self.G, seeds, off, self.h, self.sample_nodes, self.rng_seed, self.link_mode)
             ev = torch.cuda.Event()
             ev.record(stream)
         return b, ev
@@ -533,16 +552,16 @@ class Subgraphs(Dataset):
         # GMETA_EXTRACT_MODE=threads: two gm_extract calls, the support batch on a helper thread / stream; =serial: one after the other
         mode = os.environ.get('GMETA_EXTRACT_MODE', 'pair')
         if mode == 'pair':
-            S, Q = SubgraphBatch.extract_pair(self.G, seeds_s, off_s, seeds_q, off_q, self.h, self.sample_nodes, self.rng_seed, self.link_pred_mode)
+            S, Q = SubgraphBatch.extract_pair(self.G, seeds_s, off_s, seeds_q, off_q, self.h, self.sample_nodes, self.rng_seed, self.link_mode)
             return arrs, S, Q
         helper = self._helper() if (mode == 'threads' and len(seeds_q) >= 64) else None
         if helper is None:
-            S = SubgraphBatch.extract(self.G, seeds_s, off_s, self.h, self.sample_nodes, self.rng_seed, self.link_pred_mode)
-            Q = SubgraphBatch.extract(self.G, seeds_q, off_q, self.h, self.sample_nodes, self.rng_seed, self.link_pred_mode)
+            S = SubgraphBatch.extract(self.G, seeds_s, off_s, self.h, self.sample_nodes, self.rng_seed, self.link_mode)
+            Q = SubgraphBatch.extract(self.G, seeds_q, off_q, self.h, self.sample_nodes, self.rng_seed, self.link_mode)
             return arrs, S, Q
         fut = helper[0].submit(self._extract_on, helper[1], seeds_s, off_s)
         try:
-            Q = SubgraphBatch.extract(self.G, seeds_q, off_q, self.h, self.sample_nodes, self.rng_seed, self.link_pred_mode)
+            Q = SubgraphBatch.extract(self.G, seeds_q, off_q, self.h, self.sample_nodes, self.rng_seed, self.link_mode)
         finally:
             S, ev = fut.result()                                              # (also re-raises the helper's failure)
         torch.cuda.current_stream().wait_event(ev)
@@ -556,11 +575,11 @@ class Subgraphs(Dataset):
 
     def query_batch(self, names_per_task):
         """Unlabelled query subgraphs for Meta.predict / Adapted.predict: one SubgraphBatch with one set per entry of names_per_task (names 'g_i',
-        or 'g_i_j' for pairs), extracted like the tasks' own subgraphs (this dataset's h, sample_nodes, sampling seed and link mode)."""
+        or 'g_i_j' for pairs), extracted like the tasks' own subgraphs (this dataset's h, sample_nodes, sampling seed, link mode and link_hops)."""
         seeds = [self._seeds(list(names)) for names in names_per_task]
         off = np.cumsum([0] + [len(s) for s in seeds])
         return SubgraphBatch.extract(self.G, np.concatenate(seeds) if seeds else np.zeros((0, 3), np.int32), off, self.h, self.sample_nodes, self.rng_seed,
-                                     self.link_pred_mode)
+                                     self.link_mode)
 
     def get_batch(self, indices):
         """MI355X-first counterpart of DataLoader(..., collate_fn=collate): the subgraphs of ALL tasks of a

@@ -82,11 +82,20 @@ void gm_store_destroy(gm_store_t* s);
 /* ---- Extraction: replaces Subgraphs.generate_subgraph / generate_subgraph_link_pred
  * (sdp.py:295-346: h-hop in-neighbour expansion, node sampling, G.subgraph) and dgl.batch
  * (sdp.py:399-406) for n_sets sets at once.  seeds/set_offsets are host arrays; set s owns seeds
- * [set_offsets[s], set_offsets[s+1]).  h in {1,2,3} (ignored when link_pred: i side 2 hops,
- * j side 1 hop -- the reference's sdp.py:332 behaviour).  Nodes inside a subgraph are in
- * ASCENDING parent id.  If a neighbourhood has more than sample_nodes nodes, sample_nodes of them
- * are kept by a keyed permutation of (rng_seed, graph, i, j) and the centre(s) re-added
- * (sdp.py:312-314,337-339). */
+ * [set_offsets[s], set_offsets[s+1]).  Nodes inside a subgraph are in ASCENDING parent id.  If a
+ * neighbourhood has more than sample_nodes nodes, sample_nodes of them are kept by a keyed
+ * permutation of (rng_seed, graph, i, j) and the centre(s) re-added (sdp.py:312-314,337-339).
+ * link_pred is a MODE (gm_extract and gm_extract_pair; any other value is GM_EINVAL):
+ *   0                  node seeds (j = -1): the h-hop in-neighbourhood of i, h in {1,2,3}.
+ *   1                  pairs as the reference builds them: i side 2 hops, j side 1 hop, h IGNORED
+ *                      (generate_subgraph_link_pred with its sdp.py:332 slip).  Two centres per subgraph.
+ *   GM_LINK_SYMMETRIC  pairs, beyond the reference: {v : in-hop distance to i <= h} U {v : in-hop distance
+ *                      to j <= h}, h in {1,2,3} (GM_EINVAL otherwise).  Same sampling key, same
+ *                      threshold, both centres re-added; everything derived from the node set (node
+ *                      order, both CSR orientations, centre indices, norms, GM_F_*) as in mode 1.
+ * gm_batch_from_nodes takes the node sets as given and only asks whether there are two centres:
+ * any non-zero link_pred means pairs. */
+#define GM_LINK_SYMMETRIC 2
 int gm_extract(const gm_store_t* store, const gm_seed_t* seeds, int32_t n_seeds,
                const int32_t* set_offsets, int32_t n_sets, int32_t h, int32_t sample_nodes,
                uint64_t rng_seed, int32_t link_pred, void* stream, gm_batch_t** out);
