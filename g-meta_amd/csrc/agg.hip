@@ -570,10 +570,17 @@ extern "C" int gm_aggregate(const gm_batch_t* b, int32_t transposed, int32_t gat
     a.x_row = gather ? b->d_feat_row : nullptr;
     if (gather && !transposed) a.x_idx = b->d_efeat;
     if (s_in && s_in == b->d_norm) a.e_w = b->d_enorm[transposed ? 1 : 0];
+    if (b->weighted) {
+        // every term carries its edge's weight, and only the per-edge tables have a slot for it: the raw weights (no s_in) or weight x source norm (the batch's
+        // own norm: d_enorm).  A foreign s_in would be gathered per source, and a transposed feature gather has no per-edge row table to pair the weights with
+        GM_REQUIRE(!s_in || s_in == b->d_norm, GM_EINVAL, "aggregate: on a weighted batch s_in must be NULL or the batch's own GM_F_NORM (the per-source gather has no edge-weight slot)");
+        GM_REQUIRE(!(gather && transposed), GM_EINVAL, "aggregate: gather with transposed is not available on a weighted batch (no per-edge feature rows for the by-source CSR)");
+        if (!s_in) a.e_w = b->d_ew[transposed ? 1 : 0];
+    }
     a.ldx = gather ? b->store->feat_ld : width; a.s_in = s_in; a.s_out = s_out; a.out = out; a.rows = b->rows; a.width = width;
     a.heavy = b->d_heavy[transposed ? 1 : 0]; a.n_heavy = b->n_heavy[transposed ? 1 : 0]; a.heavy_deg = b->heavy_deg;
     a.sched = b->d_sched[transposed ? 1 : 0]; a.sched_len = b->sched_len[transposed ? 1 : 0]; a.sched_win = b->sched_win; GM_TRY(gm_agg_hub(a, b, transposed ? 1 : 0, (hipStream_t)stream));
-    if (a.e_w) GM_TRY(gm_agg_stream_args(a, b, transposed ? 1 : 0, gather != 0, (hipStream_t)stream));
+    if (a.e_w && a.e_w == b->d_enorm[transposed ? 1 : 0]) GM_TRY(gm_agg_stream_args(a, b, transposed ? 1 : 0, gather != 0, (hipStream_t)stream));
     gm_prof_agg_begin((hipStream_t)stream, gm_aggregate_bytes(b, width));
     int rc = gm_launch_aggregate(a, (hipStream_t)stream);
     gm_prof_agg_end((hipStream_t)stream);

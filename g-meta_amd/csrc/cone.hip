@@ -159,17 +159,29 @@ __global__ __launch_bounds__(SCAN_T) void k_level_rows(const int32_t* flags, int
 }
 // forward CSR of the upper level: every in-edge of an upper row, sources renamed to compact ids of the lower level
 // ... and the out-degree of every lower row into the upper level (integer atomics: the counts do not depend on their order), which sizes the backward CSR
+// Weighted batches: the level CSRs carry, per edge, the batch's weight and coefficient tables (gm_batch::d_ew / d_enorm / d_efeat of the same edge).  The extra
+// argument exists in the weighted instantiations alone; with the empty pack a kernel is the unweighted one, argument for argument.
+struct LevelW { const float* ew; const float* enorm; const int32_t* efeat; float* l_ew; float* l_enorm; int32_t* l_efeat; };      // (efeat / l_efeat: level 1 only, else NULL)
+template <typename... WArgs>
 __global__ __launch_bounds__(256) void k_fill_in(const int32_t* up_row, const int32_t* n_ptr, const int32_t* indptr, const int32_t* indices, const int32_t* pos_lo,
-                                                 const int32_t* cptr, int32_t* cidx, int32_t* deg_t) {
+                                                 const int32_t* cptr, int32_t* cidx, int32_t* deg_t, WArgs... w_args) {
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (q >= *n_ptr) return;
     const int r = up_row[q], e0 = indptr[r], n = indptr[r + 1] - e0, o = cptr[q];
-    for (int j = lane; j < n; j += 64) { const int u = pos_lo[indices[e0 + j]]; cidx[o + j] = u; atomicAdd(&deg_t[u], 1); }
+    for (int j = lane; j < n; j += 64) {
+        const int u = pos_lo[indices[e0 + j]]; cidx[o + j] = u; atomicAdd(&deg_t[u], 1);
+        if constexpr (sizeof...(WArgs) != 0) {
+            const LevelW& lw = (w_args, ...);
+            lw.l_ew[o + j] = lw.ew[e0 + j]; lw.l_enorm[o + j] = lw.enorm[e0 + j];
+            if (lw.l_efeat) lw.l_efeat[o + j] = lw.efeat[e0 + j];
+        }
+    }
 }
 // backward CSR: out-edges of a lower-level row that end in the upper level, in the batch's by-source order (order preserved with a ballot prefix:
 // deterministic); the row bounds tptr come from the scan of k_fill_in's counts.
+template <typename... WArgs>
 __global__ __launch_bounds__(256) void k_out_edges(const int32_t* lo_row, const int32_t* n_ptr, const int32_t* indptr_t, const int32_t* indices_t, const int32_t* pos_up,
-                                                   const int32_t* tptr, int32_t* tidx) {
+                                                   const int32_t* tptr, int32_t* tidx, WArgs... w_args) {
     // eight lanes per lower-level row, eight rows per wave (round 6: a whole wave per row before -- 940 k waves for the ~2 out-edges of a level-0 row of the
     // arxiv query batch, 59 us a launch)
     const int lane = threadIdx.x & 63, grp = lane >> 3, gl = lane & 7;
@@ -182,7 +194,14 @@ __global__ __launch_bounds__(256) void k_out_edges(const int32_t* lo_row, const 
         const int e = eb + gl;
         const int q = e < e1 ? pos_up[indices_t[e]] : -1;
         const unsigned m = (unsigned)(__ballot(q >= 0) >> (grp * 8)) & 0xffu;
-        if (q >= 0) tidx[base + __popc(m & ((1u << gl) - 1u))] = q;
+        if (q >= 0) {
+            tidx[base + __popc(m & ((1u << gl) - 1u))] = q;
+            if constexpr (sizeof...(WArgs) != 0) {
+                const LevelW& lw = (w_args, ...);
+                const int at = base + __popc(m & ((1u << gl) - 1u));
+                lw.l_ew[at] = lw.ew[e]; lw.l_enorm[at] = lw.enorm[e];
+            }
+        }
         base += __popc(m);
     }
 }
@@ -287,6 +306,10 @@ int ConeBuild::launch() {
                 v.d_indptr = cv.take<int32_t>(Bn[l] + 1); v.d_indices = cv.take<int32_t>(Be[l]);
                 v.d_indptr_t = cv.take<int32_t>(Bn[l - 1] + 1); v.d_indices_t = cv.take<int32_t>(Be[l]);
                 v.d_heavy[0] = cv.take<int32_t>(hcap(Be[l])); v.d_heavy[1] = cv.take<int32_t>(hcap(Be[l]));
+                if (b->weighted) {
+                    v.d_ew = cv.take<float>(Be[l]); v.d_enorm = cv.take<float>(Be[l]); v.d_ew_t = cv.take<float>(Be[l]); v.d_enorm_t = cv.take<float>(Be[l]);
+                    v.d_efeat = l == 1 ? cv.take<int32_t>(Be[l]) : nullptr;
+                }
             }
         }
     };
@@ -333,9 +356,13 @@ int ConeBuild::launch() {
         hipLaunchKernelGGL(k_set_off, dim3((sets + 256) / 256), dim3(256), 0, s, lo.d_row, cnt(l, 0), b->d_set_row_off, sets, rows, lo.d_set_off, soff_copy + (size_t)l * (sets + 1));
         dev_scan(deg, up.d_indptr, bu, 1, cnt(l + 1, 1), chain, s);                            // forward CSR bounds of level l + 1; nnz
         // forward CSR (by destination) and backward CSR (by source)
-        hipLaunchKernelGGL(k_fill_in, dim3((bu + 3) / 4), dim3(256), 0, s, up.d_row, cnt(l + 1, 0), b->d_indptr, b->d_indices, posB, up.d_indptr, up.d_indices, deg_t);
+        if (b->weighted) hipLaunchKernelGGL(k_fill_in<LevelW>, dim3((bu + 3) / 4), dim3(256), 0, s, up.d_row, cnt(l + 1, 0), b->d_indptr, b->d_indices, posB, up.d_indptr, up.d_indices, deg_t,
+                                            LevelW{b->d_ew[0], b->d_enorm[0], b->d_efeat, up.d_ew, up.d_enorm, up.d_efeat});
+        else hipLaunchKernelGGL(k_fill_in<>, dim3((bu + 3) / 4), dim3(256), 0, s, up.d_row, cnt(l + 1, 0), b->d_indptr, b->d_indices, posB, up.d_indptr, up.d_indices, deg_t);
         dev_scan(deg_t, up.d_indptr_t, bl, 1, cnt(l + 1, 2), chain, s);
-        hipLaunchKernelGGL(k_out_edges, dim3((bl + 31) / 32), dim3(256), 0, s, lo.d_row, cnt(l, 0), b->d_indptr_t, b->d_indices_t, posA, up.d_indptr_t, up.d_indices_t);
+        if (b->weighted) hipLaunchKernelGGL(k_out_edges<LevelW>, dim3((bl + 31) / 32), dim3(256), 0, s, lo.d_row, cnt(l, 0), b->d_indptr_t, b->d_indices_t, posA, up.d_indptr_t, up.d_indices_t,
+                                            LevelW{b->d_ew[1], b->d_enorm[1], nullptr, up.d_ew_t, up.d_enorm_t, nullptr});
+        else hipLaunchKernelGGL(k_out_edges<>, dim3((bl + 31) / 32), dim3(256), 0, s, lo.d_row, cnt(l, 0), b->d_indptr_t, b->d_indices_t, posA, up.d_indptr_t, up.d_indices_t);
         // hub rows of both CSRs, ascending
         for (int o = 0; o < 2; ++o) {
             const int bound = o ? bl : bu;

@@ -395,39 +395,57 @@ __device__ __forceinline__ void scan_degrees(const int32_t* deg, int ns, int32_t
 }
 
 // Ordered compaction of the neighbours of v that are inside the subgraph, remapped to batch rows (out2: optional second copy -- the
-// by-source CSR of a symmetric parent).
-template <bool G, typename PT>
+// by-source CSR of a symmetric parent).  WT (weighted stores): the edge's weight wsrc[q] goes to wout / wout2 at the slot its endpoint goes to in out / out2.
+template <bool G, typename PT, bool WT = false>
 __device__ __forceinline__ void wave_fill_row(const int64_t* ptr, const int32_t* idx, int64_t base, int v, const uint32_t* seen,
-                                              const PT* pref, int row0, int32_t* out, int32_t* out2, int pos, int lane) {
+                                              const PT* pref, int row0, int32_t* out, int32_t* out2, int pos, int lane,
+                                              const float* wsrc = nullptr, float* wout = nullptr, float* wout2 = nullptr) {
     const int64_t a = ptr[base + v], b = ptr[base + v + 1];
     const unsigned long long lt = (1ull << lane) - 1ull;
     for (int64_t q = a; q < b; q += EX_WINFL * GM_WAVE) {
         int u[EX_WINFL];
 #pragma unroll
         for (int k = 0; k < EX_WINFL; ++k) u[k] = q + k * GM_WAVE + lane < b ? idx[q + k * GM_WAVE + lane] : -1;
+        float wv[EX_WINFL];
+        if constexpr (WT) {
+#pragma unroll
+            for (int k = 0; k < EX_WINFL; ++k) wv[k] = q + k * GM_WAVE + lane < b ? wsrc[q + k * GM_WAVE + lane] : 0.f;
+        }
 #pragma unroll
         for (int k = 0; k < EX_WINFL; ++k) {                     // in list order
             const int hit = u[k] >= 0 && bit_test<G>(seen, u[k]);
             const unsigned long long m = __ballot(hit);
-            if (hit) { const int x = row0 + bit_rank<G, PT>(seen, pref, u[k]), p = pos + __popcll(m & lt); out[p] = x; if (out2) out2[p] = x; }
+            if (hit) {
+                const int x = row0 + bit_rank<G, PT>(seen, pref, u[k]), p = pos + __popcll(m & lt); out[p] = x; if (out2) out2[p] = x;
+                if constexpr (WT) { wout[p] = wv[k]; if (out2) wout2[p] = wv[k]; }
+            }
             pos += __popcll(m);
         }
     }
 }
 // The same for one node per group of eight lanes (all lanes of the wave call it; a group without a node passes a == b)
-template <bool G, typename PT>
+template <bool G, typename PT, bool WT = false>
 __device__ __forceinline__ void group_fill_row(const int64_t a, const int64_t b, const int32_t* idx, const uint32_t* seen, const PT* pref, int row0,
-                                               int32_t* out, int32_t* out2, int pos, int grp, int gl) {
+                                               int32_t* out, int32_t* out2, int pos, int grp, int gl,
+                                               const float* wsrc = nullptr, float* wout = nullptr, float* wout2 = nullptr) {
     const unsigned lt = (1u << gl) - 1u;
     for (int64_t q = a + gl; __any(q < b); q += EX_INFL * EX_GL) {
         int u[EX_INFL];
 #pragma unroll
         for (int k = 0; k < EX_INFL; ++k) u[k] = q + k * EX_GL < b ? idx[q + k * EX_GL] : -1;
+        float wv[EX_INFL];
+        if constexpr (WT) {
+#pragma unroll
+            for (int k = 0; k < EX_INFL; ++k) wv[k] = q + k * EX_GL < b ? wsrc[q + k * EX_GL] : 0.f;
+        }
 #pragma unroll
         for (int k = 0; k < EX_INFL; ++k) {                      // in list order: the k-th batch of eight neighbours after the (k-1)-th
             const int h = u[k] >= 0 && bit_test<G>(seen, u[k]);
             const unsigned bm = (unsigned)(__ballot(h) >> (grp * EX_GL)) & 0xffu;
-            if (h) { const int x = row0 + bit_rank<G, PT>(seen, pref, u[k]), p = pos + __popc(bm & lt); out[p] = x; if (out2) out2[p] = x; }
+            if (h) {
+                const int x = row0 + bit_rank<G, PT>(seen, pref, u[k]), p = pos + __popc(bm & lt); out[p] = x; if (out2) out2[p] = x;
+                if constexpr (WT) { wout[p] = wv[k]; if (out2) wout2[p] = wv[k]; }
+            }
             pos += __popc(bm);
         }
     }
@@ -441,10 +459,16 @@ struct FillOut {
     const int32_t* sub_off; const int32_t* sub_eoff; int32_t* parent; int32_t* feat_row; float* norm;
     int32_t* indptr; int32_t* indices; int32_t* indptr_t; int32_t* indices_t; int32_t* centre;
 };
-template <bool G, bool P16 = false>
+// Weighted stores (WT): the store's edge weights in both orientations and the two batches' gm_batch::d_ew -- written at the slots where the fill writes
+// indices / indices_t.  They ride in a LAST argument that only the weighted instantiations have, k_fill<G, P16, FillW>: with the empty pack the kernel is
+// k_fill<G, P16> argument for argument, and, WT being a compile-time flag, instruction for instruction (even an empty struct there would move the hidden
+// arguments a kernel reads blockDim from).
+struct FillW { const float* in_w; const float* out_w; float* ew0[2]; float* ew1[2]; };      // ew0 / ew1: d_ew of the batch o0 / o1 fills
+template <bool G, bool P16 = false, typename... WArgs>
 __global__ __launch_bounds__(EX_BLOCK) void k_fill(ExStore S, const gm_seed_t* seeds, int n_seeds, int link, int cap,
                                                    const int32_t* nodes_slab, const int32_t* degi_slab, const int32_t* dego_slab,
-                                                   FillOut o0, FillOut o1, int split, int Wmax, uint32_t* gbits, const int32_t* order) {
+                                                   FillOut o0, FillOut o1, int split, int Wmax, uint32_t* gbits, const int32_t* order, WArgs... w_args) {
+    constexpr bool WT = sizeof...(WArgs) != 0;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t* seen = G ? gbits + (size_t)blockIdx.x * 2 * Wmax : lds;
     static_assert(!(G && P16), "16-bit prefix words live in LDS");
@@ -501,6 +525,12 @@ __global__ __launch_bounds__(EX_BLOCK) void k_fill(ExStore S, const gm_seed_t* s
         if (tid == 0) *nbig = 0;
         __syncthreads();
         int32_t* ind2 = S.sym ? indices_t : nullptr;
+        float* ew = nullptr; float* ew_t = nullptr;
+        const float* in_w = nullptr; const float* out_w = nullptr;
+        if constexpr (WT) {
+            const FillW& fw = (w_args, ...);
+            in_w = fw.in_w; out_w = fw.out_w; ew = second ? fw.ew1[0] : fw.ew0[0]; ew_t = second ? fw.ew1[1] : fw.ew0[1];
+        }
         // node ids two batches ahead, row bounds and output offsets one batch ahead (see k_nodes)
         constexpr int RSTEP = EX_WAVES * EX_GROUPS;
         int r = wave * EX_GROUPS + grp;
@@ -529,16 +559,35 @@ __global__ __launch_bounds__(EX_BLOCK) void k_fill(ExStore S, const gm_seed_t* s
                     if (slot < EX_BLOCK) { if (gl == 0) big[slot] = r; ia = ib = oa = ob = 0; }      // (list full: the group walks it itself)
                 }
             }
-            group_fill_row<G, PT>(ia, ib, S.in_idx, seen, pref, row0, indices, ind2, pi, grp, gl);
-            if (!S.sym) group_fill_row<G, PT>(oa, ob, S.out_idx, seen, pref, row0, indices_t, nullptr, po, grp, gl);
+            if constexpr (WT) {
+                group_fill_row<G, PT, true>(ia, ib, S.in_idx, seen, pref, row0, indices, ind2, pi, grp, gl, in_w, ew, ew_t);
+                if (!S.sym) group_fill_row<G, PT, true>(oa, ob, S.out_idx, seen, pref, row0, indices_t, nullptr, po, grp, gl, out_w, ew_t, nullptr);
+            } else {
+                group_fill_row<G, PT>(ia, ib, S.in_idx, seen, pref, row0, indices, ind2, pi, grp, gl);
+                if (!S.sym) group_fill_row<G, PT>(oa, ob, S.out_idx, seen, pref, row0, indices_t, nullptr, po, grp, gl);
+            }
         }
         __syncthreads();
         const int nb = min(*nbig, EX_BLOCK);
         for (int k = wave; k < nb; k += EX_WAVES) {
             const int r = big[k], v = nodes[r];
-            wave_fill_row<G, PT>(S.in_ptr, S.in_idx, base, v, seen, pref, row0, indices, ind2, indptr[row0 + r], lane);
-            if (!S.sym) wave_fill_row<G, PT>(S.out_ptr, S.out_idx, base, v, seen, pref, row0, indices_t, nullptr, indptr_t[row0 + r], lane);
+            if constexpr (WT) {
+                wave_fill_row<G, PT, true>(S.in_ptr, S.in_idx, base, v, seen, pref, row0, indices, ind2, indptr[row0 + r], lane, in_w, ew, ew_t);
+                if (!S.sym) wave_fill_row<G, PT, true>(S.out_ptr, S.out_idx, base, v, seen, pref, row0, indices_t, nullptr, indptr_t[row0 + r], lane, out_w, ew_t, nullptr);
+            } else {
+                wave_fill_row<G, PT>(S.in_ptr, S.in_idx, base, v, seen, pref, row0, indices, ind2, indptr[row0 + r], lane);
+                if (!S.sym) wave_fill_row<G, PT>(S.out_ptr, S.out_idx, base, v, seen, pref, row0, indices_t, nullptr, indptr_t[row0 + r], lane);
+            }
         }
+    }
+}
+// Weighted batches: norm[r] = 1 / sqrt(d > 0 ? d : 1), d = the row's in-edge weights summed in edge order (k_fill knows only the count and wrote the
+// unweighted norm; this launch replaces it).  All weights 1: d is the count, an exact integer, and the quotient below is k_fill's own expression.
+__global__ void k_weighted_norm(const int32_t* indptr, const float* ew, int64_t rows, float* norm) {
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
+        float d = 0.f;
+        for (int e = indptr[r], e1 = indptr[r + 1]; e < e1; ++e) d += ew[e];
+        norm[r] = 1.0f / sqrtf(d > 0.f ? d : 1.0f);
     }
 }
 
@@ -566,14 +615,26 @@ __global__ void k_edge_tables(const int32_t* indices, const int32_t* indices_t, 
         enorm[e] = norm[u]; enorm_t[e] = norm[v]; efeat[e] = feat_row[u];
     }
 }
+// (weighted batches: the table carries the edge's weight too -- enorm[e] = w[e] * norm[u] is the aggregate's whole per-edge coefficient)
+__global__ void k_edge_tables_w(const int32_t* indices, const int32_t* indices_t, int64_t edges, const float* norm, const int32_t* feat_row,
+                                const float* ew, const float* ew_t, float* enorm, float* enorm_t, int32_t* efeat) {
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < edges; e += (int64_t)gridDim.x * blockDim.x) {
+        const int u = indices[e], v = indices_t[e];
+        enorm[e] = ew[e] * norm[u]; enorm_t[e] = ew_t[e] * norm[v]; efeat[e] = feat_row[u];
+    }
+}
 // ONE pass over the rows for everything the finalisation derives from the row bounds (round 6; four launches before): hub-row lists of both orientations (atomic append; the host orders them), the fused launch's per-row source table with its
 // row / edge counts (gm_batch::d_fuse2 / d_fuse2_feat, unfused_rows / unfused_edges), and the keep-flag row scale gm_batch::d_norm_c with the sign bit set on
 // every row (k_centre_rows clears it on the centre rows afterwards).  Hub rows: in-degree (o = 0) / out-degree (o = 1) above `thr`.
 // Same pass: gm_batch::d_norm_src (the norm, sign bit set on the rows without an out-edge: nobody's source) with the count of the other rows as a third
 // per-workgroup partial, and the all-zero entries of gm_batch::d_dq_tab (k_centre_rows writes the centre rows' afterwards).
+// WT (weighted batches): the source table's w0 / w1 are ew[e] * norm[u], the products k_edge_tables_w stores for the same edges.
+struct RowW { const float* ew; };      // gm_batch::d_ew[0]
+template <typename... WArgs>           // {}: the unweighted kernel, argument for argument; {RowW}: weighted batches
 __global__ void k_row_tables(const int32_t* indptr, const int32_t* indices, const int32_t* indptr_t, int64_t rows, const float* norm, const int32_t* feat_row,
                              int4* f2, int4* f2_feat, unsigned long long* counts, int32_t* heavy0, int32_t* heavy1, int32_t* hcnt, int cap, int thr, float* norm_c,
-                             int2* first0, int2* first1, int n_first, float* norm_src, int4* dq_tab) {
+                             int2* first0, int2* first1, int n_first, float* norm_src, int4* dq_tab, WArgs... w_args) {
+    constexpr bool WT = sizeof...(WArgs) != 0;
     unsigned long long nr = 0, ne = 0, ns = 0;
     for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
         const int p = indptr[r], d = indptr[r + 1] - p, dt = indptr_t[r + 1] - indptr_t[r];
@@ -604,7 +665,9 @@ __global__ void k_row_tables(const int32_t* indptr, const int32_t* indices, cons
         if (d == 0) { t = make_int4(GM_FUSE_ZERO, GM_FUSE_ZERO, __float_as_int(1.f), 0); tf = t; }
         else if (d <= GM_FUSE_MAXDEG) {
             const int u0 = indices[p], u1 = d >= 2 ? indices[p + 1] : u0;
-            const int w0 = __float_as_int(norm[u0]), w1 = d >= 2 ? __float_as_int(norm[u1]) : 0;
+            int w0, w1;
+            if constexpr (WT) { const float* ew = (w_args, ...).ew; w0 = __float_as_int(ew[p] * norm[u0]); w1 = d >= 2 ? __float_as_int(ew[p + 1] * norm[u1]) : 0; }
+            else { w0 = __float_as_int(norm[u0]); w1 = d >= 2 ? __float_as_int(norm[u1]) : 0; }
             t = make_int4(u0, u1, w0, w1); tf = make_int4(feat_row[u0], feat_row[u1], w0, w1);
         }
         if (d > GM_FUSE_MAXDEG) { ++nr; ne += (unsigned long long)d; }
@@ -707,12 +770,17 @@ __global__ void k_centre_rows(const int32_t* sub_off, const int32_t* centre, int
     if (norm_c) norm_c[row] = __uint_as_float(__float_as_uint(norm[row]) & 0x7fffffffu);
     if (dq_tab) dq_tab[row] = make_int4(row | GM_FUSE_SELF, GM_FUSE_ZERO, __float_as_int(1.f), 0);      // (two centres on one row write the same entry)
 }
+struct CentreW { const float* ew; float* e_coef; };      // weighted batches: gm_batch::d_ew[0] -> gm_batch::d_e1_coef = weight x source norm of every centre in-edge
+template <typename... WArgs>                              // {}: the unweighted kernel, argument for argument; {CentreW}: weighted batches
 __global__ void k_centre_edges(const int32_t* crow, const int32_t* eoff, int n_c, const int32_t* indptr, const int32_t* indices,
-                               const float* norm, int32_t* e_row, int32_t* e_par, float* e_norm) {
+                               const float* norm, int32_t* e_row, int32_t* e_par, float* e_norm, WArgs... w_args) {
     const int k = blockIdx.x;
     if (k >= n_c) return;
     const int p0 = indptr[crow[k]], n = eoff[k + 1] - eoff[k], o = eoff[k];
-    for (int j = threadIdx.x; j < n; j += blockDim.x) { const int u = indices[p0 + j]; e_row[o + j] = u; e_par[o + j] = k; e_norm[o + j] = norm[u]; }
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+        const int u = indices[p0 + j]; e_row[o + j] = u; e_par[o + j] = k; e_norm[o + j] = norm[u];
+        if constexpr (sizeof...(WArgs) != 0) { const CentreW& cw = (w_args, ...); cw.e_coef[o + j] = cw.ew[p0 + j] * norm[u]; }
+    }
 }
 __global__ void k_copy_add(int32_t* dst, const int32_t* src, int64_t n, int32_t add) {
     for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) dst[k] = src[k] + add;
@@ -930,7 +998,9 @@ static int finalize_launch(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
     for (int o = 0; o < 2; ++o) GM_TRY(gm_balloc(b, &b->d_heavy[o], 2 * (size_t)cap, s));
     if (b->edges > 0) {
         GM_TRY(gm_balloc(b, &b->d_enorm[0], (size_t)b->edges, s)); GM_TRY(gm_balloc(b, &b->d_enorm[1], (size_t)b->edges, s)); GM_TRY(gm_balloc(b, &b->d_efeat, (size_t)b->edges, s));
-        hipLaunchKernelGGL(k_edge_tables, dim3((int)std::min<int64_t>(4096, (b->edges + 255) / 256)), dim3(256), 0, s, b->d_indices, b->d_indices_t, (int64_t)b->edges,
+        if (b->weighted) hipLaunchKernelGGL(k_edge_tables_w, dim3((int)std::min<int64_t>(4096, (b->edges + 255) / 256)), dim3(256), 0, s, b->d_indices, b->d_indices_t, (int64_t)b->edges,
+                                            b->d_norm, b->d_feat_row, b->d_ew[0], b->d_ew[1], b->d_enorm[0], b->d_enorm[1], b->d_efeat);
+        else hipLaunchKernelGGL(k_edge_tables, dim3((int)std::min<int64_t>(4096, (b->edges + 255) / 256)), dim3(256), 0, s, b->d_indices, b->d_indices_t, (int64_t)b->edges,
                            b->d_norm, b->d_feat_row, b->d_enorm[0], b->d_enorm[1], b->d_efeat);
     }
     GM_TRY(gm_balloc(b, &b->d_norm_c, b->rows, s)); GM_TRY(gm_balloc(b, &b->d_norm_src, b->rows, s));
@@ -938,7 +1008,9 @@ static int finalize_launch(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
         int4 *f0 = nullptr, *ff = nullptr, *fd = nullptr;
         GM_TRY(gm_balloc(b, &f0, (size_t)b->rows, s)); GM_TRY(gm_balloc(b, &ff, (size_t)b->rows, s)); GM_TRY(gm_balloc(b, &fd, (size_t)b->rows, s));
         b->d_fuse2 = f0; b->d_fuse2_feat = ff; b->d_dq_tab = fd;
-        hipLaunchKernelGGL(k_row_tables, dim3(rt_blocks), dim3(256), 0, s, b->d_indptr, b->d_indices, b->d_indptr_t, (int64_t)b->rows,
+        if (b->weighted) hipLaunchKernelGGL(k_row_tables<RowW>, dim3(rt_blocks), dim3(256), 0, s, b->d_indptr, b->d_indices, b->d_indptr_t, (int64_t)b->rows, b->d_norm, b->d_feat_row, f0, ff,
+                                            d_counts, b->d_heavy[0], b->d_heavy[1], d_cnt, cap, b->heavy_deg, b->d_norm_c, d_first[0], d_first[1], first, b->d_norm_src, fd, RowW{b->d_ew[0]});
+        else hipLaunchKernelGGL(k_row_tables<>, dim3(rt_blocks), dim3(256), 0, s, b->d_indptr, b->d_indices, b->d_indptr_t, (int64_t)b->rows,
                            b->d_norm, b->d_feat_row, f0, ff, d_counts, b->d_heavy[0], b->d_heavy[1], d_cnt, cap, b->heavy_deg, b->d_norm_c, d_first[0], d_first[1], first, b->d_norm_src, fd);
     }
     GM_TRY(gm_balloc(b, &b->d_crow, b->n_c, s)); GM_TRY(gm_balloc(b, &b->d_cnorm, b->n_c, s));
@@ -1032,7 +1104,11 @@ static int finalize_finish(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
     GM_TRY(gm_alloc(&d_eoff, eoff.size(), s));
     GM_TRY(sg.upload(d_eoff, eoff));
     GM_TRY(gm_balloc(b, &b->d_e1_row, b->n_e1, s)); GM_TRY(gm_balloc(b, &b->d_e1_par, b->n_e1, s)); GM_TRY(gm_balloc(b, &b->d_e1_norm, b->n_e1, s));
-    hipLaunchKernelGGL(k_centre_edges, dim3(b->n_c), dim3(64), 0, s, b->d_crow, d_eoff, b->n_c, b->d_indptr, b->d_indices, b->d_norm,
+    if (b->weighted) {
+        GM_TRY(gm_balloc(b, &b->d_e1_coef, b->n_e1, s));
+        hipLaunchKernelGGL(k_centre_edges<CentreW>, dim3(b->n_c), dim3(64), 0, s, b->d_crow, d_eoff, b->n_c, b->d_indptr, b->d_indices, b->d_norm,
+                           b->d_e1_row, b->d_e1_par, b->d_e1_norm, CentreW{b->d_ew[0], b->d_e1_coef});
+    } else hipLaunchKernelGGL(k_centre_edges<>, dim3(b->n_c), dim3(64), 0, s, b->d_crow, d_eoff, b->n_c, b->d_indptr, b->d_indices, b->d_norm,
                        b->d_e1_row, b->d_e1_par, b->d_e1_norm);
     GM_HIP(hipGetLastError());
     std::vector<int32_t> ct, cc, ccoff(b->sets + 1, 0), ec, ecoff(b->sets + 1, 0), c_set_off(b->sets + 1), e_set_off(b->sets + 1);
@@ -1065,6 +1141,7 @@ static int batch_alloc(gm_batch* b, hipStream_t s) {
     GM_TRY(gm_balloc(b, &b->d_indptr, b->rows + 1, s)); GM_TRY(gm_balloc(b, &b->d_indices, b->edges, s));
     GM_TRY(gm_balloc(b, &b->d_indptr_t, b->rows + 1, s)); GM_TRY(gm_balloc(b, &b->d_indices_t, b->edges, s));
     GM_TRY(gm_balloc(b, &b->d_centre, (size_t)b->subs * b->centres, s)); GM_TRY(gm_balloc(b, &b->d_norm, b->rows, s));
+    if (b->weighted) { GM_TRY(gm_balloc(b, &b->d_ew[0], b->edges, s)); GM_TRY(gm_balloc(b, &b->d_ew[1], b->edges, s)); }
     return GM_OK;
 }
 
@@ -1146,6 +1223,11 @@ static int extract_impl(const gm_store_t* store, const gm_seed_t* seeds, int n_p
     }
     GM_TRY(gm_func_full_lds((const void*)k_fill<false>));
     GM_TRY(gm_func_full_lds((const void*)k_fill<false, true>));
+    const bool weighted = store->weighted;
+    if (weighted) {
+        GM_TRY(gm_func_full_lds((const void*)k_fill<false, false, FillW>));
+        GM_TRY(gm_func_full_lds((const void*)k_fill<false, true, FillW>));
+    }
     ExStore S{store->d_node_off, store->d_in_ptr, store->d_in_idx, store->d_out_ptr, store->d_out_idx, store->symmetric ? 1 : 0};
 
     gm_seed_t* d_seeds = nullptr; int32_t *d_nodes = nullptr, *d_degi = nullptr, *d_dego = nullptr, *d_nsub = nullptr, *d_esub = nullptr;
@@ -1201,7 +1283,7 @@ static int extract_impl(const gm_store_t* store, const gm_seed_t* seeds, int n_p
     FillOut fo[2] = {};
     for (int p = 0, k0 = 0; p < n_parts; k0 += parts[p].n_seeds, ++p) {
         gm_batch* b = bs[p]; const ExPart& q = parts[p];
-        b->store = store; b->subs = q.n_seeds; b->sets = q.n_sets; b->centres = link ? 2 : 1; b->stream = st;
+        b->store = store; b->subs = q.n_seeds; b->sets = q.n_sets; b->centres = link ? 2 : 1; b->stream = st; b->weighted = weighted;
         b->h_sub_off.assign(q.n_seeds + 1, 0); b->h_graph.resize(q.n_seeds);
         int64_t rows = 0, edges = 0;
         for (int k = 0; k < q.n_seeds; ++k) {
@@ -1243,7 +1325,18 @@ static int extract_impl(const gm_store_t* store, const gm_seed_t* seeds, int n_p
     }
     if (n_parts == 1) fo[1] = fo[0];
     gm_prof_begin(GM_PROF_EX_FILL, st, n_seeds);
-    if (gpath) {
+    if (weighted) {                       // the weighted instantiations: the same walk, the weights written beside the indices
+        const FillW fw{store->d_in_w, store->d_out_w, {bs[0]->d_ew[0], bs[0]->d_ew[1]}, {bs[n_parts - 1]->d_ew[0], bs[n_parts - 1]->d_ew[1]}};
+        const size_t lds_b = gpath ? sizeof(uint32_t) * (EX_BLOCK + 16) : sizeof(uint32_t) * ((size_t)Wmax + Wp + EX_BLOCK + 16);
+        auto launch_fill = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(n_seeds), dim3(EX_BLOCK), lds_b, st, S, d_seeds, n_seeds, link ? 1 : 0, (int)cap, d_nodes, d_degi, d_dego,
+                               fo[0], fo[1], (int)split, Wmax, d_gbits, d_order, fw);
+        };
+        if (gpath) launch_fill(k_fill<true, false, FillW>); else if (p16) launch_fill(k_fill<false, true, FillW>); else launch_fill(k_fill<false, false, FillW>);
+        for (int p = 0; p < n_parts; ++p)
+            if (bs[p]->rows > 0)
+                hipLaunchKernelGGL(k_weighted_norm, dim3((int)std::min<int64_t>(2048, (bs[p]->rows + 255) / 256)), dim3(256), 0, st, bs[p]->d_indptr, bs[p]->d_ew[0], (int64_t)bs[p]->rows, bs[p]->d_norm);
+    } else if (gpath) {
         hipLaunchKernelGGL(k_fill<true>, dim3(n_seeds), dim3(EX_BLOCK), sizeof(uint32_t) * (EX_BLOCK + 16), st, S, d_seeds, n_seeds, link ? 1 : 0, (int)cap,
                            d_nodes, d_degi, d_dego, fo[0], fo[1], (int)split, Wmax, d_gbits, d_order);
     } else {
@@ -1310,6 +1403,11 @@ extern "C" int gm_batch_concat(const gm_batch_t* const* parts, int32_t n_parts, 
     b->store = parts[0]->store; b->centres = parts[0]->centres; b->stream = st;
     int64_t rows = 0, edges = 0, subs = 0, sets = 0;
     for (int p = 0; p < n_parts; ++p) {
+        if (parts[p] && parts[p]->weighted != parts[0]->weighted) {
+            delete b; gm_set_error("concat: part %d is %s but part 0 is %s: weighted and unweighted batches cannot be concatenated", p,
+                                   parts[p]->weighted ? "weighted" : "unweighted", parts[0]->weighted ? "weighted" : "unweighted");
+            return GM_EINVAL;
+        }
         if (!parts[p] || parts[p]->store != b->store || parts[p]->centres != b->centres) {
             delete b; gm_set_error("concat: part %d has a different store or centre count", p); return GM_EINVAL;
         }
@@ -1318,6 +1416,7 @@ extern "C" int gm_batch_concat(const gm_batch_t* const* parts, int32_t n_parts, 
     if (rows > INT32_MAX - 2 || edges > INT32_MAX - 2) { delete b; gm_set_error("concat: batch exceeds 2^31 rows/edges"); return GM_ERANGE; }
     b->rows = rows; b->edges = edges; b->subs = (int32_t)subs; b->sets = (int32_t)sets;
     b->h_sub_off.assign(1, 0); b->h_set_sub_off.assign(1, 0); b->h_set_row_off.assign(1, 0);
+    b->weighted = parts[0]->weighted;
     int rc = batch_alloc(b, st);
     if (rc != GM_OK) { batch_free(b); delete b; return rc; }
     int64_t r0 = 0, e0 = 0; int32_t s0 = 0;
@@ -1333,6 +1432,7 @@ extern "C" int gm_batch_concat(const gm_batch_t* const* parts, int32_t n_parts, 
         cpy(b->d_indptr + r0, q->d_indptr, q->rows + (p == n_parts - 1 ? 1 : 0), (int32_t)e0);
         cpy(b->d_indptr_t + r0, q->d_indptr_t, q->rows + (p == n_parts - 1 ? 1 : 0), (int32_t)e0);
         cpy(b->d_indices + e0, q->d_indices, q->edges, (int32_t)r0); cpy(b->d_indices_t + e0, q->d_indices_t, q->edges, (int32_t)r0);
+        if (b->weighted) { cpy((int32_t*)b->d_ew[0] + e0, (const int32_t*)q->d_ew[0], q->edges, 0); cpy((int32_t*)b->d_ew[1] + e0, (const int32_t*)q->d_ew[1], q->edges, 0); }
         cpy(b->d_centre + (int64_t)s0 * b->centres, q->d_centre, (int64_t)q->subs * b->centres, 0);
         for (int k = 1; k <= q->subs; ++k) b->h_sub_off.push_back((int32_t)(r0 + q->h_sub_off[k]));
         for (int k = 1; k <= q->sets; ++k) { b->h_set_sub_off.push_back(s0 + q->h_set_sub_off[k]); b->h_set_row_off.push_back((int32_t)(r0 + q->h_set_row_off[k])); }
@@ -1370,6 +1470,9 @@ static int field_ptr(const gm_batch_t* b, int32_t field, void** p, int64_t* byte
         case GM_F_FEAT_ROW: *p = b->d_feat_row; *bytes = 4ll * b->rows; break;
         case GM_F_NORM_SRC: *p = b->d_norm_src; *bytes = 4ll * b->rows; break;
         case GM_F_NORM_CENTRE: *p = b->d_norm_c; *bytes = 4ll * b->rows; break;
+        case GM_F_EDGE_W: case GM_F_EDGE_W_T:
+            GM_REQUIRE(b->weighted, GM_EINVAL, "batch field %s: the batch is unweighted (its store was created without edge weights)", field == GM_F_EDGE_W ? "GM_F_EDGE_W" : "GM_F_EDGE_W_T");
+            *p = b->d_ew[field == GM_F_EDGE_W ? 0 : 1]; *bytes = 4ll * b->edges; break;
         default: gm_set_error("unknown batch field %d", field); return GM_EINVAL;
     }
     return GM_OK;
@@ -1385,6 +1488,8 @@ extern "C" int gm_batch_read(const gm_batch_t* b, int32_t field, void* host_dst,
     GM_HIP(hipStreamSynchronize(b->stream));
     return GM_OK;
 }
+
+extern "C" int32_t gm_batch_weighted(const gm_batch_t* b) { return b && b->weighted ? 1 : 0; }
 
 extern "C" int gm_batch_source_rows(const gm_batch_t* b, int64_t* n_rows) {
     GM_REQUIRE(b && n_rows, GM_EINVAL, "batch_source_rows: NULL argument");

@@ -50,6 +50,9 @@ struct gm_store {
     int64_t* d_out_ptr = nullptr;    // by-source CSR of the same edges (for the transposed induce)
     int32_t* d_out_idx = nullptr;    // destination node, LOCAL to its graph
     bool symmetric = false;          // out-CSR == in-CSR element for element (extract.hip: adjacency lists walked once)
+    bool weighted = false;           // created with edge weights (gm_store_create_weighted): every batch cut from it carries them
+    float* d_in_w = nullptr;         // [total_edges] weight of the edge, aligned with d_in_idx (weighted stores only)
+    float* d_out_w = nullptr;        // ... aligned with d_out_idx
     float* d_feat = nullptr;         // [total_nodes, feat_ld]
     unsigned* d_feat_amax = nullptr; // [1] bit pattern of max |feature| over the whole table
     // per graph (host): max |x| and mean |x| over the non-zero entries.  The two-piece fp16 kernels (opt-in, gm_bound.h) bound the layer-1 operand
@@ -71,6 +74,9 @@ struct gm_cone_level {
     int32_t* d_chunks = nullptr; int32_t* d_set_chunk_off = nullptr; int32_t n_chunks = 0;
     int32_t* d_indptr = nullptr; int32_t* d_indices = nullptr;       // [n+1], [nnz]: in-edges, sources = compact ids of level l-1
     int32_t* d_indptr_t = nullptr; int32_t* d_indices_t = nullptr;   // [n_{l-1}+1], [nnz]: the same edges by source, destinations = compact ids of level l
+    // weighted batches only (NULL otherwise), per edge: its weight and weight x norm of the row the aggregate reads -- aligned with d_indices (source = level l-1)
+    // and with d_indices_t (source = level l); level 1 also the feature row of the edge's source, what its weighted gather needs beside the coefficient
+    float* d_ew = nullptr; float* d_enorm = nullptr; float* d_ew_t = nullptr; float* d_enorm_t = nullptr; int32_t* d_efeat = nullptr;
     int32_t* d_heavy[2] = {nullptr, nullptr}; int32_t n_heavy[2] = {0, 0};
 };
 struct gm_cone {
@@ -102,6 +108,8 @@ struct gm_batch {
     int32_t* d_centre = nullptr;       // [subs*centres] local index
     std::vector<int32_t> h_centre;     // host copy, brought by the finalisation's round trip (gm_batch_read serves it without another one)
     float* d_norm = nullptr;           // [rows]
+    bool weighted = false;             // cut from a weighted store: d_ew holds the induced edge weights, d_norm the weighted in-degree's norm
+    float* d_ew[2] = {nullptr, nullptr};   // [edges] weight of every edge, aligned with d_indices / d_indices_t (weighted batches only)
     // derived launch tables (built by gm_batch_finalize)
     int32_t* d_sub_set = nullptr;      // [subs]  set of each subgraph
     int32_t* d_tiles = nullptr;        // [n_tiles*3]  GEMM row tiles: set, row0, nrows (<= GM_GEMM_BM)
@@ -128,7 +136,8 @@ struct gm_batch {
     // that moves an orientation's launches to another stream (public gm_aggregate / gm_gcn_* API) is ordered behind the previous stream's
     // launch by gm_batch_hub_order (an event wait, only when the stream changes).  Host-side bookkeeping, guarded by hub_mu.
     mutable hipStream_t hub_stream[4] = {nullptr, nullptr, nullptr, nullptr}; mutable bool hub_used[4] = {false, false, false, false}; mutable hipEvent_t hub_ev[4] = {nullptr, nullptr, nullptr, nullptr};      // [set * 2 + orientation]
-    // per-edge tables (gm_batch_finalize): the source's norm for both CSR orientations (enorm[o][e] = norm[indices_o[e]]) and the source's
+    // per-edge tables (gm_batch_finalize): the source's norm for both CSR orientations (enorm[o][e] = norm[indices_o[e]]; weighted batches:
+    // d_ew[o][e] * norm[indices_o[e]] -- this table and d_fuse2's w0 / w1 are where the weights meet the model's kernels) and the source's
     // feature row (efeat[e] = feat_row[indices[e]]): what the aggregate would otherwise fetch with a dependent 4-byte gather per edge
     float* d_enorm[2] = {nullptr, nullptr}; int32_t* d_efeat = nullptr;
     // row gains of the two aggregates (gm_bound.h): |out| <= gain * max |in| -- [0] forward: max_i sum_{u->i} norm[u]; [1] transposed with the
@@ -171,6 +180,7 @@ struct gm_batch {
     int32_t* d_e1_row = nullptr;       // [n_e1] source row of the edge
     int32_t* d_e1_par = nullptr;       // [n_e1] compact index of the centre it enters
     float* d_e1_norm = nullptr;        // [n_e1] norm[source row]
+    float* d_e1_coef = nullptr;        // [n_e1] weighted batches only: edge weight x norm[source row] (the transposed aggregate's coefficient; d_e1_norm stays the row scale)
     int32_t* d_c_tiles = nullptr; int32_t n_c_tiles = 0;          // GEMM tiles over centre rows (per set)
     int32_t* d_c_chunks = nullptr; int32_t* d_c_set_chunk_off = nullptr; int32_t n_c_chunks = 0;
     int32_t* d_e1_chunks = nullptr; int32_t* d_e1_set_chunk_off = nullptr; int32_t n_e1_chunks = 0;

@@ -856,6 +856,9 @@ static int batch_agg(const GcnCtx& c, int dir, hipStream_t st, gm_agg_args& a) {
     a.sched = b->d_sched[dir]; a.sched_len = b->sched_len[dir]; a.sched_win = b->sched_win;
     GM_TRY(gm_agg_hub(a, b, dir, st, c.hub_set));
     a.rows = b->rows;
+    // weighted batches: an aggregate without a source scale still carries the edges' weights (the callers that scale by the source's norm replace this
+    // with d_enorm, which holds weight x norm).  A pointer choice only: the kernels read e_w as they do on unweighted batches
+    if (b->weighted) a.e_w = b->d_ew[dir];
     return GM_OK;
 }
 
@@ -1134,7 +1137,7 @@ static int gcn_backward_sparse(GcnCtx& c, const float* params, int64_t pstride, 
     if (b->n_e1 > 0) {
         const int64_t tot = (int64_t)b->n_e1 * fiL;
         hipLaunchKernelGGL(k_expand_edges, dim3((int)std::min<int64_t>(2048, (tot + 255) / 256)), dim3(256), 0, st, c.cT2, c.H[0], fiL, b->d_e1_row, b->d_e1_par,
-                           b->d_e1_norm, b->n_e1, c.cG1);
+                           b->weighted ? b->d_e1_coef : b->d_e1_norm, b->n_e1, c.cG1);      // (weighted batches: the edge's weight rides in the coefficient)
         GM_HIP(hipGetLastError());
     }
     // dW_1 = sum_e norm[u_e] Z_1[u_e]^T G1[e] ; db_1 = sum_e G1[e]   (a set without any centre in-edge gets zeros: empty chunk range)
@@ -1166,6 +1169,7 @@ static gm_agg_args cone_agg(const gm_cone* cn, const gm_cone_level& up, int tran
     gm_agg_args a{};
     a.indptr = transposed ? up.d_indptr_t : up.d_indptr; a.indices = transposed ? up.d_indices_t : up.d_indices;
     a.heavy = up.d_heavy[transposed]; a.n_heavy = up.n_heavy[transposed]; a.heavy_deg = cn->heavy_deg;
+    a.e_w = transposed ? up.d_ew_t : up.d_ew;      // weighted batches (NULL otherwise): the edges' weights; launches that scale by the source's norm take d_enorm / d_enorm_t instead
     return a;
 }
 
@@ -1191,8 +1195,8 @@ static int cone_forward(GcnCtx& c, const float* params, int64_t pstride, float* 
         } else {
             if (!(l == 0 && reuse_z1 && c.z1_valid)) {
                 gm_agg_args a = cone_agg(cn, up, 0);
-                a.s_in = lo.d_norm; a.out = c.Z[l]; a.rows = up.n; a.width = fi; a.ldx = fi;
-                if (l == 0) { a.x = b->store->d_feat; a.x_row = lo.d_feat_row; a.ldx = b->store->feat_ld; } else a.x = xin;
+                a.s_in = lo.d_norm; a.e_w = up.d_enorm; a.out = c.Z[l]; a.rows = up.n; a.width = fi; a.ldx = fi;
+                if (l == 0) { a.x = b->store->d_feat; a.x_row = lo.d_feat_row; a.x_idx = up.d_efeat; a.ldx = b->store->feat_ld; } else a.x = xin;
                 GM_TRY(cone_launch_agg(a, lo.n, up.nnz, st));
                 if (l == 0) c.z1_valid = 1;
             }
@@ -1220,7 +1224,7 @@ static int cone_backward(GcnCtx& c, const float* params, int64_t pstride, const 
         if (fi > fo) {
             // dY = A^T (norm * dQ) on the source level ; dW = (norm*X)^T dY ; db = colsum(dQ) ; dQ_prev = relu'(H_prev) * norm * (dY W^T)
             gm_agg_args a = cone_agg(cn, up, 1);
-            a.x = dQ; a.ldx = fo; a.s_in = up.d_norm; a.out = T; a.rows = lo.n; a.width = fo;
+            a.x = dQ; a.ldx = fo; a.s_in = up.d_norm; a.e_w = up.d_enorm_t; a.out = T; a.rows = lo.n; a.width = fo;
             GM_TRY(cone_launch_agg(a, up.n, up.nnz, st));
             w.A = l > 0 ? c.H[l - 1] : c.X0; w.lda = fi; w.a_scale = lo.d_norm; w.G = T; w.ldg = fo; w.db = nullptr;
             w.rows = lo.n; w.chunks = lo.d_chunks; w.n_chunks = lo.n_chunks; w.set_chunk_off = lo.d_set_chunk_off;
@@ -1776,7 +1780,8 @@ static int meta_plan(MetaPlan& p, const gm_batch* spt, const gm_batch* qry, cons
     p.bound_ws = nullptr; p.bound_words = 0; p.viol = nullptr;
     bool agg_first = true;
     for (int l = 0; l < p.L.n_gcn; ++l) agg_first = agg_first && p.L.dims[l] <= p.L.dims[l + 1];
-    if (p.pd.base && gm_split_np() == 2 && agg_first && !hp->sparse_bwd && !p.S.cone && spt->store->d_feat_amax &&
+    // (never on weighted batches: the magnitude bounds -- k_gains, gm_bound.h -- assume edge scales <= 1; they keep the three-piece kernels, violation word 0)
+    if (p.pd.base && gm_split_np() == 2 && agg_first && !hp->sparse_bwd && !p.S.cone && spt->store->d_feat_amax && !spt->weighted && !qry->weighted &&
         spt->rows + qry->rows >= gm_knob().split16_min_rows) {
         const int per_pass = 2 * p.L.n_gcn + 1;
         const int64_t ws_s = (int64_t)p.K * per_pass * p.T * GM_BOUND_PAD, ws_q = (int64_t)K1 * per_pass * p.T * GM_BOUND_PAD, ws_w = (int64_t)p.L.n_gcn * GM_BOUND_PAD;
@@ -1816,6 +1821,7 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
                (long long)gm_meta_out_floats(spt, m, hp));
     GM_REQUIRE(spt->sets == qry->sets, GM_EINVAL, "meta_step: %d support sets but %d query sets", spt->sets, qry->sets);
     GM_REQUIRE(spt->store == qry->store, GM_EINVAL, "meta_step: support and query batches come from different stores");
+    GM_REQUIRE(spt->weighted == qry->weighted, GM_EINVAL, "meta_step: one of the support and query batches is weighted, the other is not");
     const int K = hp->update_step;
     GM_REQUIRE(K >= 1, GM_EINVAL, "meta_step: update_step must be >= 1");
     GM_REQUIRE(!hp->need_meta_grad || K >= 2, GM_EINVAL,

@@ -3,13 +3,15 @@
 #include <math.h>
 #include "gm_internal.h"
 
-extern "C" int gm_store_create(int32_t n_graphs, const int64_t* n_nodes, const int64_t* const* indptr,
-                               const int32_t* const* indices, const float* const* feat, int32_t feat_dim,
-                               gm_store_t** out) {
+// weights: NULL (every edge counts once) or one fp32 array per graph, aligned with indices[g] (gm_store_create_weighted)
+static int store_create(int32_t n_graphs, const int64_t* n_nodes, const int64_t* const* indptr, const int32_t* const* indices,
+                        const float* const* weights, const float* const* feat, int32_t feat_dim, gm_store_t** out) {
     GM_REQUIRE(out, GM_EINVAL, "gm_store_create: out is NULL");
     *out = nullptr;
     GM_REQUIRE(n_graphs >= 1 && n_nodes && indptr && indices && feat && feat_dim >= 1, GM_EINVAL,
                "gm_store_create: bad arguments");
+    if (weights)
+        for (int g = 0; g < n_graphs; ++g) GM_REQUIRE(weights[g] || indptr[g][n_nodes[g]] == 0, GM_EINVAL, "gm_store_create_weighted: graph %d has no weight array", g);
     gm_store* s = new gm_store();
     s->n_graphs = n_graphs; s->feat_dim = feat_dim;
     s->node_off.assign(n_graphs + 1, 0); s->edge_off.assign(n_graphs + 1, 0);
@@ -26,6 +28,8 @@ extern "C" int gm_store_create(int32_t n_graphs, const int64_t* n_nodes, const i
     // host staging: global in-CSR, derived out-CSR (stable counting sort: destinations ascending per source)
     std::vector<int64_t> in_ptr(s->total_nodes + 1), out_ptr(s->total_nodes + 1, 0);
     std::vector<int32_t> in_idx(s->total_edges ? s->total_edges : 1), out_idx(s->total_edges ? s->total_edges : 1);
+    std::vector<float> in_w, out_w;                                          // weighted stores only: the edge weights in both orientations
+    if (weights) { s->weighted = true; in_w.assign(in_idx.size(), 1.f); out_w.assign(in_idx.size(), 1.f); }
     for (int g = 0; g < n_graphs; ++g) {
         const int64_t n = n_nodes[g], no = s->node_off[g], eo = s->edge_off[g];
         for (int64_t v = 0; v < n; ++v) {
@@ -38,6 +42,16 @@ extern "C" int gm_store_create(int32_t n_graphs, const int64_t* n_nodes, const i
             if (u < 0 || u >= n) { delete s; gm_set_error("graph %d: edge source %d out of range", g, u); return GM_EINVAL; }
             in_idx[eo + e] = u;
             out_ptr[no + u + 1] += 1;
+            if (weights) {
+                const float w = weights[g][e];
+                if (!(w > 0.f) || !(w <= 3.4028234e38f)) {                    // NaN, inf, zero and negative weights
+                    int64_t v = 0;                                            // destination of edge e: the last row that starts at or before it
+                    { int64_t lo = 0, hi = n; while (hi - lo > 1) { const int64_t mid = (lo + hi) / 2; if (indptr[g][mid] <= e) lo = mid; else hi = mid; } v = lo; }
+                    delete s; gm_set_error("graph %d: edge %lld (%d -> %lld) has weight %g: edge weights must be finite and > 0", g, (long long)e, u, (long long)v, (double)w);
+                    return GM_EINVAL;
+                }
+                in_w[eo + e] = w;
+            }
         }
     }
     in_ptr[s->total_nodes] = s->total_edges;
@@ -47,10 +61,15 @@ extern "C" int gm_store_create(int32_t n_graphs, const int64_t* n_nodes, const i
         for (int g = 0; g < n_graphs; ++g) {
             const int64_t n = n_nodes[g], no = s->node_off[g];
             for (int64_t v = 0; v < n; ++v)
-                for (int64_t e = in_ptr[no + v]; e < in_ptr[no + v + 1]; ++e) out_idx[cur[no + in_idx[e]]++] = (int32_t)v;
+                for (int64_t e = in_ptr[no + v]; e < in_ptr[no + v + 1]; ++e) {
+                    const int64_t at = cur[no + in_idx[e]]++;
+                    out_idx[at] = (int32_t)v;
+                    if (weights) out_w[at] = in_w[e];                         // the same stable order: the weight travels with its edge
+                }
         }
     }
-    s->symmetric = s->total_edges > 0 && in_ptr == out_ptr && in_idx == out_idx && getenv("GM_EXTRACT_NO_SYM") == nullptr;
+    // (weighted: the single walk copies the in-edge's weight into the by-source CSR, so the two weight arrays must agree slot by slot as well)
+    s->symmetric = s->total_edges > 0 && in_ptr == out_ptr && in_idx == out_idx && in_w == out_w && getenv("GM_EXTRACT_NO_SYM") == nullptr;
     hipStream_t st = nullptr;
     int rc = GM_OK;
 #define UP(dptr, vec, T)                                                                              \
@@ -65,6 +84,10 @@ extern "C" int gm_store_create(int32_t n_graphs, const int64_t* n_nodes, const i
     UP(s->d_in_idx, in_idx, int32_t)
     UP(s->d_out_ptr, out_ptr, int64_t)
     UP(s->d_out_idx, out_idx, int32_t)
+    if (weights) {
+        UP(s->d_in_w, in_w, float)
+        UP(s->d_out_w, out_w, float)
+    }
 #undef UP
     // pad only widths the vector kernels cannot take as they are (not a multiple of 4: 50, 5, ...).  Aligned widths keep their native stride:
     // padding is exact (zeros) but changes which kernels run, i.e. the fp summation order.
@@ -98,10 +121,23 @@ extern "C" int gm_store_create(int32_t n_graphs, const int64_t* n_nodes, const i
     return GM_OK;
 }
 
+extern "C" int gm_store_create(int32_t n_graphs, const int64_t* n_nodes, const int64_t* const* indptr,
+                               const int32_t* const* indices, const float* const* feat, int32_t feat_dim,
+                               gm_store_t** out) {
+    return store_create(n_graphs, n_nodes, indptr, indices, nullptr, feat, feat_dim, out);
+}
+extern "C" int gm_store_create_weighted(int32_t n_graphs, const int64_t* n_nodes, const int64_t* const* indptr,
+                                        const int32_t* const* indices, const float* const* weights, const float* const* feat, int32_t feat_dim,
+                                        gm_store_t** out) {
+    return store_create(n_graphs, n_nodes, indptr, indices, weights, feat, feat_dim, out);
+}
+extern "C" int32_t gm_store_weighted(const gm_store_t* s) { return s && s->weighted ? 1 : 0; }
+
 extern "C" void gm_store_destroy(gm_store_t* s) {
     if (!s) return;
     (void)hipDeviceSynchronize();
     gm_dev_free(s->d_node_off, nullptr); gm_dev_free(s->d_in_ptr, nullptr); gm_dev_free(s->d_in_idx, nullptr);
     gm_dev_free(s->d_out_ptr, nullptr); gm_dev_free(s->d_out_idx, nullptr); gm_dev_free(s->d_feat, nullptr); gm_dev_free(s->d_feat_amax, nullptr);
+    gm_dev_free(s->d_in_w, nullptr); gm_dev_free(s->d_out_w, nullptr);
     delete s;
 }

@@ -5,6 +5,7 @@ The reference loads (train.py:41-53): `features.npy` (2-D array, or object array
 (dict name -> label) and `{train,val,test}.csv` (+ `_spt` / `_qry` variants for link prediction).
 This build reads the same files except the DGL pickle, which is replaced by `graph_csr.npz`:
     n_graphs, and per graph g:  g{g}_n, g{g}_src, g{g}_dst   (directed edge list, edge k: src -> dst)
+    and optionally g{g}_w (fp32, one weight per edge; beyond the reference): the graphs then load as (n, src, dst, w) and GraphStore builds a weighted store
 `convert_dgl_pickle` produces it wherever DGL is importable; `write_datadir` writes a complete directory
 (used by the synthetic generators and the tests)."""
 import os
@@ -24,7 +25,8 @@ def load_graphs(root):
     p = os.path.join(root, 'graph_csr.npz')
     if os.path.exists(p):
         z = np.load(p)
-        return [(int(z['g%d_n' % g]), z['g%d_src' % g], z['g%d_dst' % g]) for g in range(int(z['n_graphs']))]
+        return [(int(z['g%d_n' % g]), z['g%d_src' % g], z['g%d_dst' % g]) + ((z['g%d_w' % g],) if 'g%d_w' % g in z.files else ())
+                for g in range(int(z['n_graphs']))]
     pk = os.path.join(root, 'graph_dgl.pkl')
     if os.path.exists(pk):
         try:
@@ -50,10 +52,13 @@ def convert_dgl_pickle(root):
 
 def save_graphs(root, graphs):
     out = {'n_graphs': len(graphs)}
-    for g, (n, src, dst) in enumerate(graphs):
+    for g, gr in enumerate(graphs):
+        n, src, dst = gr[:3]
         out['g%d_n' % g] = n
         out['g%d_src' % g] = np.asarray(src, np.int32)
         out['g%d_dst' % g] = np.asarray(dst, np.int32)
+        if len(gr) == 4:                                   # optional edge weights
+            out['g%d_w' % g] = np.asarray(gr[3], np.float32)
     np.savez(os.path.join(root, 'graph_csr.npz'), **out)
 
 

@@ -7,37 +7,64 @@ import numpy as np
 from . import _lib
 
 
-def edges_to_in_csr(n, src, dst):
+def edges_to_in_csr(n, src, dst, w=None):
     """Directed multigraph edge list (edge k: src[k] -> dst[k]) -> in-edge CSR.  Within a row the
-    parent edge-id order is kept (DGL's in_edges order, sdp.py:301)."""
+    parent edge-id order is kept (DGL's in_edges order, sdp.py:301).  With edge weights `w` (one per edge) a third
+    array comes back: the weights in the CSR's order (the same stable sort carries them)."""
     src = np.asarray(src, np.int64).reshape(-1); dst = np.asarray(dst, np.int64).reshape(-1)
     if src.shape != dst.shape:
         raise ValueError('src and dst must have the same length')
+    if w is not None:
+        w = np.asarray(w, np.float32).reshape(-1)
+        if w.shape != src.shape:
+            raise ValueError('need one weight per edge (%d weights, %d edges)' % (len(w), len(src)))
     if len(src) and (src.min() < 0 or src.max() >= n or dst.min() < 0 or dst.max() >= n):
         raise ValueError('edge endpoint out of range')
     order = np.argsort(dst, kind='stable')
     indptr = np.zeros(n + 1, np.int64)
     np.add.at(indptr, dst + 1, 1)
+    if w is not None:
+        return np.cumsum(indptr), np.ascontiguousarray(src[order].astype(np.int32)), np.ascontiguousarray(w[order])
     return np.cumsum(indptr), np.ascontiguousarray(src[order].astype(np.int32))
 
 
 class GraphStore:
     """`graphs`: list of (n_nodes, src, dst) edge lists or (indptr, indices) in-CSR pairs;
-    `feats`: list of float arrays [n_nodes, F0] (one per graph)."""
+    `feats`: list of float arrays [n_nodes, F0] (one per graph).
+    Edge weights (beyond the reference; include/gmeta_hip.h, gm_store_create_weighted): (n_nodes, src, dst, w) 4-tuples, or `edge_weights` =
+    one array per graph aligned with the graph's edge list (3-tuples) or with its `indices` (CSR pairs).  Every graph carries weights or none
+    does; they must be finite and > 0.  `.weighted` says which kind the store is, `.host_weights` keeps the weights in `host_csr`'s order."""
 
-    def __init__(self, graphs, feats):
+    def __init__(self, graphs, feats, edge_weights=None):
         _lib.require_gpu()
         if len(graphs) != len(feats) or not graphs:
             raise ValueError('need one feature matrix per graph')
-        ptrs, idxs, ns = [], [], []
-        for g in graphs:
+        if edge_weights is not None and len(edge_weights) != len(graphs):
+            raise ValueError('edge_weights needs one array per graph')
+        ptrs, idxs, ns, wts = [], [], [], []
+        for k, g in enumerate(graphs):
+            w = None if edge_weights is None else edge_weights[k]
+            if len(g) == 4:
+                if w is not None:
+                    raise ValueError('graph %d has weights in its tuple and in edge_weights' % k)
+                g, w = g[:3], g[3]
             if len(g) == 3:
                 n, src, dst = g
-                ip, ix = edges_to_in_csr(int(n), src, dst)
+                if w is None:
+                    ip, ix = edges_to_in_csr(int(n), src, dst)
+                else:
+                    ip, ix, w = edges_to_in_csr(int(n), src, dst, w)
             else:
                 ip, ix = np.ascontiguousarray(g[0], np.int64), np.ascontiguousarray(g[1], np.int32)
                 n = len(ip) - 1
-            ptrs.append(ip); idxs.append(ix); ns.append(int(n))
+                if w is not None:
+                    w = np.ascontiguousarray(w, np.float32).reshape(-1)
+                    if len(w) != len(ix):
+                        raise ValueError('graph %d: %d weights for %d edges' % (k, len(w), len(ix)))
+            ptrs.append(ip); idxs.append(ix); ns.append(int(n)); wts.append(w)
+        if any(w is None for w in wts) and not all(w is None for w in wts):
+            raise ValueError('either every graph carries edge weights or none does')
+        self.weighted = wts[0] is not None
         F0 = int(np.asarray(feats[0]).shape[1])
         fl = []
         for n, f in zip(ns, feats):
@@ -51,20 +78,28 @@ class GraphStore:
         i_arr = (C.c_void_p * G)(*[a.ctypes.data for a in idxs])
         f_arr = (C.c_void_p * G)(*[a.ctypes.data for a in fl])
         h = C.c_void_p()
-        _lib.check(_lib.lib().gm_store_create(G, n_arr, p_arr, i_arr, f_arr, F0, C.byref(h)), 'gm_store_create')
+        if self.weighted:
+            w_arr = (C.c_void_p * G)(*[a.ctypes.data for a in wts])
+            _lib.check(_lib.lib().gm_store_create_weighted(G, n_arr, p_arr, i_arr, w_arr, f_arr, F0, C.byref(h)), 'gm_store_create_weighted')
+        else:
+            _lib.check(_lib.lib().gm_store_create(G, n_arr, p_arr, i_arr, f_arr, F0, C.byref(h)), 'gm_store_create')
         self.handle = h
         self.n_graphs, self.n_nodes, self.feat_dim = G, ns, F0
         self.n_edges = [int(p[-1]) for p in ptrs]
         self.host_csr = list(zip(ptrs, idxs))      # host copy of the in-edge CSR (Subgraphs(sample_mode='reference') walks it like sdp.py:301)
+        self.host_weights = wts if self.weighted else None      # per graph: the edge weights aligned with host_csr's indices
 
     def symmetric(self):
         """True when every out-edge list equals the in-edge list element for element (undirected graphs stored in both directions with
-        ascending rows): extraction then walks the adjacency lists once for both CSR orientations (csrc/extract.hip)."""
-        for ptr, ix in self.host_csr:
+        ascending rows): extraction then walks the adjacency lists once for both CSR orientations (csrc/extract.hip).  A weighted store must
+        also carry the same weight in both lists slot for slot (w_uv == w_vu): the one walk copies the in-edge's weight to both."""
+        for g, (ptr, ix) in enumerate(self.host_csr):
             n = len(ptr) - 1
             dst = np.repeat(np.arange(n, dtype=np.int64), np.diff(ptr))
             order = np.argsort(ix, kind='stable')                      # out-CSR: by source, destinations in in-CSR (= ascending destination) order
             if not (np.array_equal(np.bincount(ix, minlength=n), np.diff(ptr)) and np.array_equal(dst[order], ix.astype(np.int64))):
+                return False
+            if self.weighted and not np.array_equal(self.host_weights[g][order], self.host_weights[g]):
                 return False
         return True
 

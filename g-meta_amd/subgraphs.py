@@ -208,6 +208,15 @@ class SubgraphBatch:
         ix = self._read(_lib.F_INDICES_T if transposed else _lib.F_INDICES, self.edges, np.int32)
         return ip, ix
 
+    @property
+    def weighted(self):
+        """True for a batch cut from a weighted GraphStore (it carries the induced edge weights)."""
+        return bool(_lib.lib().gm_batch_weighted(self.handle))
+
+    def edge_weights(self, transposed=False):
+        """The induced edge weights, aligned with csr(transposed)[1] (weighted batches only: ValueError otherwise)."""
+        return self._read(_lib.F_EDGE_W_T if transposed else _lib.F_EDGE_W, self.edges, np.float32)
+
     def device_ptr(self, field):
         p = C.c_void_p()
         _lib.check(_lib.lib().gm_batch_device_ptr(self.handle, field, C.byref(p)))

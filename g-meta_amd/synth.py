@@ -139,8 +139,29 @@ def make_config(F0, hidden, h, n_out, link=False):
     return config
 
 
-def make_dataset(c, seed=222):
-    """Synthetic data of a CONFIGS entry: {'graphs', 'feats', 'info', 'tables'} (tables as Subgraphs(tables=...) takes them)."""
+def with_edge_weights(graphs, seed=222, lo=0.25, hi=4.0, symmetric=True):
+    """(n, src, dst) -> (n, src, dst, w) with log-uniform weights in [lo, hi] (tests and timing of weighted stores).  symmetric: an edge and its
+    reverse get the same weight (a function of the unordered endpoint pair), so an undirected graph stored in both directions stays symmetric."""
+    out = []
+    for g, (n, src, dst) in enumerate(graphs):
+        src = np.asarray(src, np.int64); dst = np.asarray(dst, np.int64)
+        if symmetric:
+            a, b = np.minimum(src, dst), np.maximum(src, dst)
+            key, inv = np.unique(a * int(n) + b, return_inverse=True)
+            u = np.random.default_rng([seed, g]).random(len(key))[inv]
+        else:
+            u = np.random.default_rng([seed, g]).random(len(src))
+        out.append((n, src, dst, np.exp(np.log(lo) + u * (np.log(hi) - np.log(lo))).astype(np.float32)))
+    return out
+
+
+def make_dataset(c, seed=222, edge_weights=False):
+    """Synthetic data of a CONFIGS entry: {'graphs', 'feats', 'info', 'tables'} (tables as Subgraphs(tables=...) takes them).
+    edge_weights: the graphs carry log-uniform weights in [0.25, 4] (with_edge_weights)."""
+    if edge_weights:
+        d = make_dataset(c, seed)
+        d['graphs'] = with_edge_weights(d['graphs'], seed)
+        return d
     kind = c.get('kind', 'single')
     if kind == 'single':
         d = node_dataset(c['n'], c['m'], c['F0'], c['classes'], seed)

@@ -65,6 +65,11 @@ typedef struct gm_hparams {
                               (L-l) in-hops upstream of a centre, forward and backward -- the same sums for every row
                               that matters, nothing for the rows that cannot influence logits or gradients.
                               Supersedes sparse_bwd; falls back to the dense schedule if a pair has i == j */
+    /* Batches of a WEIGHTED store (gm_store_create_weighted): every schedule CARRIES the weights, none falls back.  hoist_z1 needs nothing (the
+       hoisted aggregate is the dense schedule's own launch); sparse_bwd reads a per-edge coefficient (weight x source norm) for the centres'
+       in-edges beside their norms; cone copies the batch's per-edge weight / coefficient tables into its level CSRs.  With all weights 1.0
+       each schedule returns its unweighted floats bit for bit.  gm_set_split_pieces(2) is ignored on weighted batches (three pieces,
+       violation word 0): the two-piece magnitude bounds assume edge scales <= 1. */
 } gm_hparams_t;
 
 const char* gm_last_error(void);
@@ -77,6 +82,19 @@ int gm_version(void);
 int gm_store_create(int32_t n_graphs, const int64_t* n_nodes, const int64_t* const* indptr,
                     const int32_t* const* indices, const float* const* feat, int32_t feat_dim,
                     gm_store_t** out);
+/* The same with a strength on every edge (beyond the reference): weights[g] (host fp32, aligned with indices[g]) = w_uv of the edge u->v,
+ * finite and > 0 (GM_EINVAL otherwise; the message names the graph and the edge).  weights == NULL is gm_store_create.  Extraction stays
+ * purely topological (hops, the sampling threshold and keys, the node order never look at a weight); a batch cut from a weighted store carries
+ * the induced weights (GM_F_EDGE_W / GM_F_EDGE_W_T), and in fp32
+ *   d(v) = sum of w_uv over the in-edges of v inside its subgraph, in the row's edge order;   GM_F_NORM(v) = 1 / sqrtf(d(v) > 0 ? d(v) : 1);
+ *   GraphConv: relu(norm(v) * sum_{u->v} w_uv * norm(u) * x[u] W + b), both branch orders of learner.py:34-47; the backward uses the same
+ *   coefficients on the by-source CSR; weights are constants (no gradient).
+ * Integer weights equal the multigraph with the edge repeated w_uv times; all weights 1.0 give the unweighted floats bit for bit.
+ * gm_store_weighted / gm_batch_weighted: 1 for a store created with weights / a batch cut from one. */
+int gm_store_create_weighted(int32_t n_graphs, const int64_t* n_nodes, const int64_t* const* indptr,
+                             const int32_t* const* indices, const float* const* weights, const float* const* feat, int32_t feat_dim,
+                             gm_store_t** out);
+int32_t gm_store_weighted(const gm_store_t* s);
 void gm_store_destroy(gm_store_t* s);
 
 /* ---- Extraction: replaces Subgraphs.generate_subgraph / generate_subgraph_link_pred
@@ -112,7 +130,8 @@ int gm_extract_pair(const gm_store_t* store, const gm_seed_t* seeds_a, int32_t n
 int gm_batch_from_nodes(const gm_store_t* store, const gm_seed_t* seeds, int32_t n_seeds,
                         const int32_t* set_offsets, int32_t n_sets, const int32_t* nodes_flat,
                         const int64_t* nodes_off, int32_t link_pred, void* stream, gm_batch_t** out);
-/* dgl.batch over already-built batches (sets are appended in order).  Inputs stay valid. */
+/* dgl.batch over already-built batches (sets are appended in order).  Inputs stay valid.  Parts of one store are all weighted or all
+ * unweighted; a mix (hand-made handles) is GM_EINVAL. */
 int gm_batch_concat(const gm_batch_t* const* parts, int32_t n_parts, void* stream, gm_batch_t** out);
 /* Receptive-field tables for gm_hparams_t.cone with an n_gcn-layer model (built on `stream`, cached in the
  * batch; gm_meta_ws_bytes/gm_meta_step build them on first use otherwise).  level_rows/level_edges
@@ -141,12 +160,15 @@ enum gm_field {
     GM_F_INDPTR_T,      /* int32[rows+1]  by-source CSR (for the backward aggregate)                                 */
     GM_F_INDICES_T,     /* int32[edges]   destination ROW of every out-edge                                          */
     GM_F_CENTRE,        /* int32[subs*centres] local index of the centre(s) inside each subgraph (sdp.py:318-319)    */
-    GM_F_NORM,          /* float[rows]    in_degree.clamp(1)^-0.5 (learner.py:29)                                    */
+    GM_F_NORM,          /* float[rows]    in_degree.clamp(1)^-0.5 (learner.py:29); weighted batches: the weighted in-degree      */
     GM_F_FEAT_ROW,      /* int32[rows]    row of the store's feature matrix for each batch row                       */
     GM_F_NORM_SRC,      /* float[rows]    GM_F_NORM with the sign bit set on every row without an out-edge inside the batch: no later
                                           kernel reads that row of a hidden activation below the last layer (GM_DEAD_ROWS)       */
-    GM_F_NORM_CENTRE    /* float[rows]    GM_F_NORM with the sign bit set on every row that is not a centre                     */
+    GM_F_NORM_CENTRE,   /* float[rows]    GM_F_NORM with the sign bit set on every row that is not a centre                     */
+    GM_F_EDGE_W,        /* float[edges]   weight of every in-edge, aligned with GM_F_INDICES (weighted batches only: GM_EINVAL otherwise) */
+    GM_F_EDGE_W_T       /* float[edges]   the same weights in the order of GM_F_INDICES_T (weighted batches only)                       */
 };
+int32_t gm_batch_weighted(const gm_batch_t* b);
 /* Copies a field to host memory (synchronises `stream` internally). */
 int gm_batch_read(const gm_batch_t* b, int32_t field, void* host_dst, int64_t bytes);
 /* Device address of a field (valid until gm_batch_destroy). */
@@ -161,7 +183,9 @@ int gm_gather_features(const gm_batch_t* b, float* x_out, void* stream);
 /* ---- GCN building blocks (GraphConv.forward, learner.py:25-56), exported for tests/profiling.
  * out[v,:] = s_out[v] * sum_{u in row v} s_in[u] * x[u,:]   (s_in / s_out may be NULL = 1).
  * transposed != 0 runs on the by-source CSR (autograd backward of update_all).  If gather != 0,
- * x is ignored and rows are read from the store's features through GM_F_FEAT_ROW. */
+ * x is ignored and rows are read from the store's features through GM_F_FEAT_ROW.
+ * Weighted batches: every term also carries w_uv.  s_in == NULL sums w_uv * x[u]; s_in == the batch's own GM_F_NORM device pointer sums
+ * w_uv * norm[u] * x[u]; any other s_in is GM_EINVAL (the per-source gather has no weight slot), and so is gather with transposed. */
 int gm_aggregate(const gm_batch_t* b, int32_t transposed, int32_t gather, const float* x, int32_t width,
                  const float* s_in, const float* s_out, float* out, void* stream);
 int64_t gm_aggregate_bytes(const gm_batch_t* b, int32_t width); /* algorithmic HBM bytes of one call */

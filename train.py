@@ -92,6 +92,8 @@ def main(args):
     maml = gmeta_amd.Meta(args, config).to('cuda')
     if rank == 0:
         print('There are {} classes '.format(total_class))
+        if store.weighted:
+            print('The graphs carry edge weights (graph_csr.npz g*_w)')
         print('Total trainable tensors:', sum(int(np.prod(p.shape)) for p in maml.parameters() if p.requires_grad))
     mk = lambda mode, b: gmeta_amd.Subgraphs(root, mode, info, n_way=args.n_way, k_shot=args.k_spt, k_query=args.k_qry, batchsz=b,  # noqa: E731
                                              args=args, adjs=store, h=args.h, verbose=rank == 0)
