@@ -12,8 +12,8 @@ There is no CPU fallback: every compute entry point raises if the HIP library or
 """
 from . import _lib  # noqa: F401
 from .graphstore import GraphStore  # noqa: F401
-from .subgraphs import Subgraphs, SubgraphBatch, collate  # noqa: F401
+from .subgraphs import Subgraphs, SubgraphBatch, collate, hop_label_width, hop_labels_switch  # noqa: F401
 from .learner import Classifier  # noqa: F401
 from .meta import Meta  # noqa: F401
 
-__all__ = ['GraphStore', 'Subgraphs', 'SubgraphBatch', 'collate', 'Classifier', 'Meta']
+__all__ = ['GraphStore', 'Subgraphs', 'SubgraphBatch', 'collate', 'Classifier', 'Meta', 'hop_label_width', 'hop_labels_switch']

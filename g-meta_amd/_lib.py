@@ -7,7 +7,7 @@ LIB_PATH = os.environ.get('GMETA_HIP_LIB') or os.path.join(HERE, 'libgmeta_hip.s
 
 GM_MAX_GCN = 4
 (F_SUB_OFF, F_SET_SUB_OFF, F_PARENT, F_GRAPH, F_INDPTR, F_INDICES, F_INDPTR_T, F_INDICES_T, F_CENTRE, F_NORM,
- F_FEAT_ROW, F_NORM_SRC, F_NORM_CENTRE, F_EDGE_W, F_EDGE_W_T) = range(15)
+ F_FEAT_ROW, F_NORM_SRC, F_NORM_CENTRE, F_EDGE_W, F_EDGE_W_T, F_HOP) = range(16)
 LINK_SYMMETRIC = 2      # GM_LINK_SYMMETRIC: the link_pred mode of gm_extract / gm_extract_pair with h hops around both endpoints
 
 
@@ -36,6 +36,9 @@ PROTOTYPES = {
     'gm_extract': (C.c_int, [vp, vp, i32, vp, i32, i32, i32, u64, i32, vp, vp]),
     'gm_extract_pair': (C.c_int, [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, u64, i32, vp, vp, vp]),
     'gm_batch_from_nodes': (C.c_int, [vp, vp, i32, vp, i32, vp, vp, i32, vp, vp]),
+    'gm_set_hop_labels': (None, [i32]),
+    'gm_get_hop_labels': (i32, []),
+    'gm_batch_hop_labels': (i32, [vp]),
     'gm_batch_concat': (C.c_int, [vp, i32, vp, vp]),
     'gm_batch_destroy': (None, [vp]),
     'gm_batch_prepare_cone': (C.c_int, [vp, i32, vp]),

@@ -548,7 +548,7 @@ int gm_agg_stream_args(gm_agg_args& a, const gm_batch* b, int o, bool gather, hi
     }
     if (!b->d_sptr[o] || !b->d_sseg[o] || (gather && (o != 0 || !b->d_su_feat))) return GM_OK;
     a.stream = b; a.stream_o = o; a.stream_feat = gather ? 1 : 0;
-    a.stream_xrows = gather ? b->store->total_nodes : b->rows;
+    a.stream_xrows = gather ? b->feat_rows : b->rows;
     return GM_OK;
 }
 
@@ -562,11 +562,11 @@ extern "C" int gm_aggregate(const gm_batch_t* b, int32_t transposed, int32_t gat
                             const float* s_in, const float* s_out, float* out, void* stream) {
     GM_REQUIRE(b && out && width >= 1, GM_EINVAL, "aggregate: bad arguments");
     GM_REQUIRE(gather || x, GM_EINVAL, "aggregate: x is NULL and gather == 0");
-    GM_REQUIRE(!gather || width == b->store->feat_dim, GM_EINVAL, "aggregate: gather needs width == feat_dim");
+    GM_REQUIRE(!gather || width == b->feat_dim, GM_EINVAL, "aggregate: gather needs width == feat_dim");
     gm_agg_args a{};
     a.indptr = transposed ? b->d_indptr_t : b->d_indptr;
     a.indices = transposed ? b->d_indices_t : b->d_indices;
-    a.x = gather ? b->store->d_feat : x;
+    a.x = gather ? b->feat : x;
     a.x_row = gather ? b->d_feat_row : nullptr;
     if (gather && !transposed) a.x_idx = b->d_efeat;
     if (s_in && s_in == b->d_norm) a.e_w = b->d_enorm[transposed ? 1 : 0];
@@ -577,7 +577,7 @@ extern "C" int gm_aggregate(const gm_batch_t* b, int32_t transposed, int32_t gat
         GM_REQUIRE(!(gather && transposed), GM_EINVAL, "aggregate: gather with transposed is not available on a weighted batch (no per-edge feature rows for the by-source CSR)");
         if (!s_in) a.e_w = b->d_ew[transposed ? 1 : 0];
     }
-    a.ldx = gather ? b->store->feat_ld : width; a.s_in = s_in; a.s_out = s_out; a.out = out; a.rows = b->rows; a.width = width;
+    a.ldx = gather ? b->feat_ld : width; a.s_in = s_in; a.s_out = s_out; a.out = out; a.rows = b->rows; a.width = width;
     a.heavy = b->d_heavy[transposed ? 1 : 0]; a.n_heavy = b->n_heavy[transposed ? 1 : 0]; a.heavy_deg = b->heavy_deg;
     a.sched = b->d_sched[transposed ? 1 : 0]; a.sched_len = b->sched_len[transposed ? 1 : 0]; a.sched_win = b->sched_win; GM_TRY(gm_agg_hub(a, b, transposed ? 1 : 0, (hipStream_t)stream));
     if (a.e_w && a.e_w == b->d_enorm[transposed ? 1 : 0]) GM_TRY(gm_agg_stream_args(a, b, transposed ? 1 : 0, gather != 0, (hipStream_t)stream));

@@ -793,7 +793,102 @@ __global__ void k_gather_rows(const float* feat, int64_t ld, const int32_t* feat
     }
 }
 
+// ---- hop-distance node labels (gm_set_hop_labels, include/gmeta_hip.h): the labelling step of local-subgraph methods, beyond the reference
+// One workgroup per (subgraph, centre): level-synchronous BFS from the centre along the in-edges of the batch's own induced CSR, at most D levels.
+// label = distance where <= D, D + 1 for everything farther or unreachable (every row starts there).  A wave takes a frontier row, its lanes the
+// row's in-edges; the writers racing for a row within a level all write that level.  The distance bytes live in LDS while the subgraph fits
+// (sample_nodes + 2 rows: 1,002 by default), in the output array itself above that (workgroup-scope visibility: volatile accesses + the barrier).
+#define GM_HOP_LDS_ROWS 2048
+#define GM_HOP_BLOCK 256
+template <bool LDS>
+__device__ __forceinline__ void hop_bfs(int8_t* dist, int64_t stride, int n, int root, int r0, const int32_t* indptr, const int32_t* indices, int D) {
+    auto get = [&](int v) -> int { return LDS ? (int)dist[v] : (int)((volatile int8_t*)dist)[(int64_t)v * stride]; };
+    auto put = [&](int v, int d) { if (LDS) dist[v] = (int8_t)d; else ((volatile int8_t*)dist)[(int64_t)v * stride] = (int8_t)d; };
+    const int far = D + 1, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int v = threadIdx.x; v < n; v += GM_HOP_BLOCK) put(v, v == root ? 0 : far);
+    __syncthreads();
+    for (int level = 1; level <= D; ++level) {
+        for (int v = wave; v < n; v += GM_HOP_BLOCK / 64) {
+            if (get(v) != level - 1) continue;                        // (wave-uniform)
+            const int e1 = indptr[r0 + v + 1];
+            for (int e = indptr[r0 + v] + lane; e < e1; e += 64) {
+                const int u = indices[e] - r0;
+                if ((unsigned)u < (unsigned)n && get(u) == far) put(u, level);
+            }
+        }
+        __syncthreads();
+    }
+}
+__global__ __launch_bounds__(GM_HOP_BLOCK) void k_hop_labels(const int32_t* sub_off, const int32_t* centre, int nc, const int32_t* indptr, const int32_t* indices, int D,
+                                                             int8_t* hop) {
+    __shared__ int8_t dist_s[GM_HOP_LDS_ROWS];
+    const int k = blockIdx.x / nc, c = blockIdx.x - k * nc;
+    const int r0 = sub_off[k], n = sub_off[k + 1] - r0, root = centre[k * nc + c];
+    int8_t* out = hop + (int64_t)r0 * nc + c;                         // row v of the subgraph: out[v * nc]
+    if (n <= GM_HOP_LDS_ROWS) {
+        hop_bfs<true>(dist_s, 1, n, root, r0, indptr, indices, D);
+        for (int v = threadIdx.x; v < n; v += GM_HOP_BLOCK) out[(int64_t)v * nc] = dist_s[v];
+    } else hop_bfs<false>(out, nc, n, root, r0, indptr, indices, D);
+}
+// The labelled feature table of a batch: row r = [the store's feature row | one one-hot block of Lw columns per centre | zeros up to ldo] (ldo % 4 == 0),
+// 16-byte loads from the store where its leading dimension allows, 16-byte stores; the same pass writes the identity row table the layer-1 readers
+// address the table through.
+__global__ void k_label_features(const float* feat, int64_t ld, int F0, const int32_t* store_row, const int8_t* hop, int nc, int Lw, float* out, int ldo, int64_t rows,
+                                 int32_t* ident) {
+    const int groups = ldo >> 2;
+    const bool vec = (ld & 3) == 0;
+    const int64_t total = rows * groups;
+    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < total; k += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = k / groups; const int g = (int)(k - r * groups), c0 = 4 * g;
+        const float* x = feat + (int64_t)store_row[r] * ld;
+        float4 v;
+        if (vec && c0 + 4 <= F0) v = *reinterpret_cast<const float4*>(x + c0);
+        else {
+            float t[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = c0 + q;
+                if (c < F0) t[q] = x[c];
+                else { const int j = c - F0, blk = j / Lw; t[q] = (blk < nc && (int)hop[r * nc + blk] == j - blk * Lw) ? 1.f : 0.f; }
+            }
+            v = make_float4(t[0], t[1], t[2], t[3]);
+        }
+        *reinterpret_cast<float4*>(out + r * (int64_t)ldo + c0) = v;
+        if (g == 0) ident[r] = (int32_t)r;
+    }
+}
+
 // ------------------------------------------------------------------------------------------ host
+// Hop-label switch of the calling thread (gm_set_hop_labels): read where a batch is built
+static thread_local int g_hop_labels = 0;
+extern "C" void gm_set_hop_labels(int32_t D) {
+    if (D < 0 || D > 7) { gm_set_error("gm_set_hop_labels: D=%d ignored (0 = off, 1..7 = label cap)", D); return; }
+    g_hop_labels = D;
+}
+extern "C" int32_t gm_get_hop_labels(void) { return g_hop_labels; }
+extern "C" int32_t gm_batch_hop_labels(const gm_batch_t* b) { return b ? b->hop_D : 0; }
+static inline int hop_feat_dim(const gm_store* st, int centres, int D) { return st->feat_dim + centres * (D + 2); }
+// a new batch reads the store's feature table; with D > 0 the finalisation replaces it by the batch's own labelled table (label_batch)
+static void batch_features(gm_batch* b, int D) {
+    b->feat = b->store->d_feat; b->feat_ld = b->store->feat_ld; b->feat_dim = b->store->feat_dim; b->feat_rows = b->store->total_nodes; b->hop_D = D;
+}
+// Finalisation of a labelled batch, before the edge / row tables are derived (they then come out with identity feature rows): labels, the batch's
+// feature table, and the row tables swapped -- d_store_row keeps the store rows (GM_F_FEAT_ROW)
+static int label_batch(gm_batch* b, hipStream_t s) {
+    const int D = b->hop_D, nc = b->centres, Fd = hop_feat_dim(b->store, nc, D), ldo = gm_pad_feat(Fd);
+    float* tab = nullptr; int32_t* ident = nullptr;
+    GM_TRY(gm_balloc(b, &b->d_hop, (size_t)b->rows * nc, s)); GM_TRY(gm_balloc(b, &tab, (size_t)b->rows * ldo, s)); GM_TRY(gm_balloc(b, &ident, (size_t)b->rows, s));
+    if (b->rows > 0) {
+        hipLaunchKernelGGL(k_hop_labels, dim3(b->subs * nc), dim3(GM_HOP_BLOCK), 0, s, b->d_sub_off, b->d_centre, nc, b->d_indptr, b->d_indices, D, b->d_hop);
+        const int64_t total = b->rows * (ldo / 4);
+        hipLaunchKernelGGL(k_label_features, dim3((int)std::min<int64_t>(4096, (total + 255) / 256)), dim3(256), 0, s, b->store->d_feat, (int64_t)b->store->feat_ld,
+                           b->store->feat_dim, b->d_feat_row, b->d_hop, nc, D + 2, tab, ldo, (int64_t)b->rows, ident);
+        GM_HIP(hipGetLastError());
+    }
+    b->d_store_row = b->d_feat_row; b->d_feat_row = ident;
+    b->feat = tab; b->feat_ld = ldo; b->feat_dim = Fd; b->feat_rows = b->rows;
+    return GM_OK;
+}
 void gm_batch_mark_use(const gm_batch* b, hipStream_t st) {
     if (!b || st == b->stream) return;              // same stream: the frees are already ordered behind the consumer
     if (!b->used_ev && hipEventCreateWithFlags(&b->used_ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); b->used_ev = nullptr; return; }
@@ -852,7 +947,8 @@ int gm_balloc_bytes(gm_batch* b, void** p, size_t bytes, hipStream_t s) {
         // slab size: what the big arrays of this batch will need in total when the sizes are known (rows / edges; measured on the arxiv query batch:
         // 139 MB at 1.14 M rows / 2.1 M edges), plus room for the level arrays of a two-layer receptive-field build (12 + 4 bytes per row, 8 per edge:
         // cone.hip) so that a batch is ONE block of the slab cache; else 8 MiB steps
-        const size_t guess = (size_t)b->rows * 74 + (size_t)b->edges * 27 + ((size_t)2 << 20) + (size_t)b->rows * 20 + (size_t)b->edges * 8;
+        const size_t guess = (size_t)b->rows * 74 + (size_t)b->edges * 27 + ((size_t)2 << 20) + (size_t)b->rows * 20 + (size_t)b->edges * 8 +
+                             (b->hop_D ? (size_t)b->rows * (4 * (size_t)gm_pad_feat(b->store->feat_dim + b->centres * (b->hop_D + 2)) + 8) : 0);      // (+ a labelled batch's own feature table)
         gm_batch::slab sl{nullptr, 0, 0};
         GM_TRY(gm_slab_acquire(&sl.base, &sl.cap, std::max(bytes, b->slabs.empty() ? guess : std::max<size_t>(guess / 4, (size_t)8 << 20)), s));
         b->slabs.push_back(sl);
@@ -977,6 +1073,7 @@ static int finalize_launch(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
     b->n_tiles = (int32_t)(tiles.size() / 3); b->n_chunks = (int32_t)(chunks.size() / 3);
     GM_TRY(upload_tables(b, sg, s, {{&b->d_sub_set, &sub_set}, {&b->d_tiles, &tiles}, {&b->d_chunks, &chunks}, {&b->d_set_chunk_off, &set_chunk_off}}));
     tm.lap("tables");
+    if (b->hop_D > 0) GM_TRY(label_batch(b, s)); else b->d_store_row = b->d_feat_row;
     // ---- device side, nothing here waits for the host: hub-row lists of both orientations, per-edge tables, the fused launch's row table +
     // counts, centre rows with their in-degrees
     b->heavy_deg = gm_heavy_deg_for(b->rows, b->edges);
@@ -1284,6 +1381,7 @@ static int extract_impl(const gm_store_t* store, const gm_seed_t* seeds, int n_p
     for (int p = 0, k0 = 0; p < n_parts; k0 += parts[p].n_seeds, ++p) {
         gm_batch* b = bs[p]; const ExPart& q = parts[p];
         b->store = store; b->subs = q.n_seeds; b->sets = q.n_sets; b->centres = link ? 2 : 1; b->stream = st; b->weighted = weighted;
+        batch_features(b, g_hop_labels);
         b->h_sub_off.assign(q.n_seeds + 1, 0); b->h_graph.resize(q.n_seeds);
         int64_t rows = 0, edges = 0;
         for (int k = 0; k < q.n_seeds; ++k) {
@@ -1408,6 +1506,11 @@ extern "C" int gm_batch_concat(const gm_batch_t* const* parts, int32_t n_parts, 
                                    parts[p]->weighted ? "weighted" : "unweighted", parts[0]->weighted ? "weighted" : "unweighted");
             return GM_EINVAL;
         }
+        if (parts[p] && parts[p]->hop_D != parts[0]->hop_D) {
+            delete b; gm_set_error("concat: part %d has hop labels D=%d but part 0 has D=%d: parts must all be labelled with the same D, or all unlabelled", p,
+                                   parts[p]->hop_D, parts[0]->hop_D);
+            return GM_EINVAL;
+        }
         if (!parts[p] || parts[p]->store != b->store || parts[p]->centres != b->centres) {
             delete b; gm_set_error("concat: part %d has a different store or centre count", p); return GM_EINVAL;
         }
@@ -1417,6 +1520,7 @@ extern "C" int gm_batch_concat(const gm_batch_t* const* parts, int32_t n_parts, 
     b->rows = rows; b->edges = edges; b->subs = (int32_t)subs; b->sets = (int32_t)sets;
     b->h_sub_off.assign(1, 0); b->h_set_sub_off.assign(1, 0); b->h_set_row_off.assign(1, 0);
     b->weighted = parts[0]->weighted;
+    batch_features(b, parts[0]->hop_D);      // (labelled parts: the finalisation labels the concatenated subgraphs again -- the same labels, the concatenated table)
     int rc = batch_alloc(b, st);
     if (rc != GM_OK) { batch_free(b); delete b; return rc; }
     int64_t r0 = 0, e0 = 0; int32_t s0 = 0;
@@ -1427,7 +1531,7 @@ extern "C" int gm_batch_concat(const gm_batch_t* const* parts, int32_t n_parts, 
     };
     for (int p = 0; p < n_parts; ++p) {
         const gm_batch* q = parts[p];
-        cpy(b->d_parent + r0, q->d_parent, q->rows, 0); cpy(b->d_feat_row + r0, q->d_feat_row, q->rows, 0);
+        cpy(b->d_parent + r0, q->d_parent, q->rows, 0); cpy(b->d_feat_row + r0, q->d_store_row, q->rows, 0);
         cpy((int32_t*)b->d_norm + r0, (const int32_t*)q->d_norm, q->rows, 0);
         cpy(b->d_indptr + r0, q->d_indptr, q->rows + (p == n_parts - 1 ? 1 : 0), (int32_t)e0);
         cpy(b->d_indptr_t + r0, q->d_indptr_t, q->rows + (p == n_parts - 1 ? 1 : 0), (int32_t)e0);
@@ -1467,7 +1571,10 @@ static int field_ptr(const gm_batch_t* b, int32_t field, void** p, int64_t* byte
         case GM_F_INDICES_T: *p = b->d_indices_t; *bytes = 4ll * b->edges; break;
         case GM_F_CENTRE: *p = b->d_centre; *bytes = 4ll * b->subs * b->centres; break;
         case GM_F_NORM: *p = b->d_norm; *bytes = 4ll * b->rows; break;
-        case GM_F_FEAT_ROW: *p = b->d_feat_row; *bytes = 4ll * b->rows; break;
+        case GM_F_FEAT_ROW: *p = b->d_store_row; *bytes = 4ll * b->rows; break;
+        case GM_F_HOP:
+            GM_REQUIRE(b->hop_D > 0, GM_EINVAL, "batch field GM_F_HOP: the batch carries no hop labels (built with gm_set_hop_labels(0))");
+            *p = b->d_hop; *bytes = (int64_t)b->rows * b->centres; break;
         case GM_F_NORM_SRC: *p = b->d_norm_src; *bytes = 4ll * b->rows; break;
         case GM_F_NORM_CENTRE: *p = b->d_norm_c; *bytes = 4ll * b->rows; break;
         case GM_F_EDGE_W: case GM_F_EDGE_W_T:
@@ -1503,20 +1610,20 @@ extern "C" int gm_batch_device_ptr(const gm_batch_t* b, int32_t field, void** dp
     return field_ptr(b, field, dptr, &bytes);
 }
 
-int gm_gather_rows(const gm_store* store, const int32_t* feat_row, int64_t n, int F, float* out, hipStream_t st) {
-    if (n <= 0) return GM_OK;          // F: columns copied (feat_dim, or feat_ld for the padded internal model)
+int gm_gather_rows(const gm_batch* b, const int32_t* feat_row, int64_t n, int F, float* out, hipStream_t st) {
+    if (n <= 0) return GM_OK;          // F: columns copied (feat_dim, or feat_ld for the padded internal model); feat_row: rows of the batch's feature table
     const int blocks = (int)std::min<int64_t>(256 * 8, (n * F + 255) / 256);
-    hipLaunchKernelGGL(k_gather_rows, dim3(blocks), dim3(256), 0, st, store->d_feat, (int64_t)store->feat_ld, feat_row, out, n, F);
+    hipLaunchKernelGGL(k_gather_rows, dim3(blocks), dim3(256), 0, st, b->feat, (int64_t)b->feat_ld, feat_row, out, n, F);
     GM_HIP(hipGetLastError());
     return GM_OK;
 }
 
 extern "C" int gm_gather_features(const gm_batch_t* b, float* x_out, void* stream) {
     GM_REQUIRE(b && x_out, GM_EINVAL, "gather_features: NULL argument");
-    const int F = b->store->feat_dim;
+    const int F = b->feat_dim;
     const int64_t total = b->rows * F;
     const int blocks = (int)std::min<int64_t>(256 * 8, (total + 255) / 256);
-    hipLaunchKernelGGL(k_gather_rows, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b->store->d_feat, (int64_t)b->store->feat_ld, b->d_feat_row, x_out, b->rows, F);
+    hipLaunchKernelGGL(k_gather_rows, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b->feat, (int64_t)b->feat_ld, b->d_feat_row, x_out, b->rows, F);
     GM_HIP(hipGetLastError());
     return GM_OK;
 }

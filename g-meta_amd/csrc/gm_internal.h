@@ -100,7 +100,13 @@ struct gm_batch {
     int32_t* d_set_row_off = nullptr;  // [sets+1]
     int32_t* d_graph = nullptr;        // [subs]
     int32_t* d_parent = nullptr;       // [rows]
-    int32_t* d_feat_row = nullptr;     // [rows]
+    int32_t* d_feat_row = nullptr;     // [rows]  row of the feature table below (labelled batches: the identity)
+    // The feature table layer 1 gathers from: the store's (default), or -- hop-labelled batches, gm_set_hop_labels -- the batch's own
+    // [rows, feat_ld] table of store features + one-hot label columns + zero padding (k_label_features).  Every gather path reads these four.
+    const float* feat = nullptr; int64_t feat_ld = 0, feat_rows = 0; int32_t feat_dim = 0;
+    int32_t hop_D = 0;                 // label cap D of a labelled batch (0: unlabelled)
+    int8_t* d_hop = nullptr;           // [rows, centres] hop-distance labels (GM_F_HOP; labelled batches only)
+    int32_t* d_store_row = nullptr;    // [rows]  row of the STORE's feature matrix (GM_F_FEAT_ROW): d_feat_row itself on unlabelled batches
     int32_t* d_indptr = nullptr;       // [rows+1]
     int32_t* d_indices = nullptr;      // [edges]
     int32_t* d_indptr_t = nullptr;     // [rows+1]
@@ -284,6 +290,14 @@ struct gm_layout {
     int64_t w_off[GM_MAX_GCN], b_off[GM_MAX_GCN], wl_off, bl_off, P;
 };
 int gm_make_layout(const gm_model_t* m, gm_layout* L);
+// dims[0] of a model against the feature rows of a batch (the padded width is what the kernels' internal model carries)
+static inline int gm_check_feat_dim(const gm_batch* b, int dims0, const char* what) {
+    if (dims0 == b->feat_dim || dims0 == b->feat_ld) return GM_OK;
+    if (b->hop_D) gm_set_error("%s: dims[0]=%d but the batch has %d features (%d of the store + %d hop-label columns, gm_set_hop_labels(%d))", what, dims0, b->feat_dim,
+                               b->store->feat_dim, b->feat_dim - b->store->feat_dim, b->hop_D);
+    else gm_set_error("%s: dims[0]=%d but the store has %d features", what, dims0, b->feat_dim);
+    return GM_EINVAL;
+}
 static inline int gm_pad_feat(int F) { return F <= 32 ? 32 : (F + 63) / 64 * 64; }
 
 // ---- kernels launched across translation units

@@ -868,7 +868,7 @@ static bool dz_split_ok(const GcnCtx& c, int l) { return c.Wsplit && gm_gemm_spl
 // unfilled, and gcn_backward reads it that way, by this one predicate
 static bool dz_centre_ok(const GcnCtx& c, int l) { return dz_split_ok(c, l) && c.L.dims[l + 1] >= 64 && c.L.dims[l + 1] <= 4096 && c.b->d_dq_tab; }
 
-int gm_gather_rows(const gm_store* store, const int32_t* feat_row, int64_t n, int F, float* out, hipStream_t st);
+int gm_gather_rows(const gm_batch* b, const int32_t* feat_row, int64_t n, int F, float* out, hipStream_t st);
 static int cone_forward(GcnCtx& c, const float* params, int64_t pstride, float* logits, hipStream_t st, int reuse_z1, int skip_head);
 static int cone_backward(GcnCtx& c, const float* params, int64_t pstride, const float* dlogits, float* dparams, int64_t dstride, hipStream_t st, int skip_head);
 
@@ -884,7 +884,7 @@ extern "C" int32_t gm_get_fuse_agg(void) { const int o = g_fuse_agg_override.loa
 static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* logits, hipStream_t st, int reuse_z1, int skip_head = 0, int fwd_only = 0) {
     if (c.cone) return cone_forward(c, params, pstride, logits, st, reuse_z1, skip_head);
     const gm_layout& L = c.L; const gm_batch* b = c.b;
-    GM_REQUIRE(L.dims[0] == b->store->feat_dim || L.dims[0] == b->store->feat_ld || c.x0_user, GM_EINVAL, "forward: dims[0]=%d but the store has %d features", L.dims[0], b->store->feat_dim);
+    if (!c.x0_user) GM_TRY(gm_check_feat_dim(b, L.dims[0], "forward"));
     GM_REQUIRE((L.link != 0) == (b->centres == 2), GM_EINVAL, "forward: link_pred model needs a 2-centre batch and vice versa");
     const float* xin = c.x0_user;           // NULL = gather rows of the store through feat_row
     c.dq = GcnCtx::DQ_MEMSET;
@@ -901,7 +901,7 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
         const bool gather = (l == 0 && !c.x0_user);
         if (fi > fo) {                      // learner.py:34-40: multiply first, then aggregate
             const float* A = xin; int64_t lda = fi;
-            if (gather) { GM_TRY(gm_gather_rows(b->store, b->d_feat_row, b->rows, fi, c.X0, st)); A = c.X0; }
+            if (gather) { GM_TRY(gm_gather_rows(b, b->d_feat_row, b->rows, fi, c.X0, st)); A = c.X0; }
             gm_gemm_args g{}; g.A = A; g.lda = lda; g.B = params + L.w_off[l]; g.b_stride = pstride; g.C = c.Z[l]; g.ldc = fo; g.K = fi; g.N = fo;
             g.row_scale = b->d_norm; g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows;
             GM_TRY(gm_launch_gemm_nn(g, st));
@@ -920,7 +920,7 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
             const bool keeps_stream = gm_knob().fuse_diff == 2 && c.is_support && gm_knob().agg_stream && gm_stream_batch_ok(b, 0);
             const bool diff_ok = fwd_only == 2 && gm_knob().fuse_diff && !keeps_stream && c.np != 2 && !c.cone && gm_wgrad_gather_ok(b->n_chunks, fi, fo);
             const bool fuse = (fwd_only == 1 || diff_ok) && gm_get_fuse_agg() && split_ok && !(l == 0 && reuse_z1) && fi >= 64 && fi % 4 == 0 && b->d_fuse2 && b->d_enorm[0] &&
-                              (!gather || (b->store->feat_ld % 4 == 0 && b->store->feat_ld >= fi)) &&
+                              (!gather || (b->feat_ld % 4 == 0 && b->feat_ld >= fi)) &&
                               // worth it only where a good part of the rows has one or two sources: on dense batches (Tissue shape: ~30 in-edges per
                               // row) nearly every row still goes through the ordinary aggregate and the gather feeders only cost (3.30 -> 3.21 ms)
                               2 * b->unfused_rows <= b->rows;
@@ -928,7 +928,7 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
             if (!(l == 0 && reuse_z1 && c.z1_valid)) {
                 gm_agg_args a; GM_TRY(batch_agg(c, 0, st, a));
                 a.s_in = b->d_norm; a.e_w = b->d_enorm[0]; a.out = c.Z[l]; a.width = fi;
-                if (gather) { a.x = b->store->d_feat; a.x_row = b->d_feat_row; a.x_idx = b->d_efeat; a.ldx = b->store->feat_ld; }
+                if (gather) { a.x = b->feat; a.x_row = b->d_feat_row; a.x_idx = b->d_efeat; a.ldx = b->feat_ld; }
                 else { a.x = xin; a.ldx = fi; }
                 if (fuse) {
                     // only the rows the fused kernel does not form itself (more than GM_FUSE_MAXDEG sources): a partial launch
@@ -946,14 +946,14 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
                     const int64_t src = gm_prof_enabled() ? gm_batch_unfused_sources(b, st) : std::min<int64_t>(b->unfused_edges, b->rows);
                     const int64_t pb = pb0 + 4 * src * (int64_t)fi;
                     // strict HBM pricing as for the full launches: a gather launch reads at most the whole (cache-resident) feature table
-                    const int64_t pbs = pb0 + 4 * (gather ? std::min<int64_t>(src, b->store->total_nodes) : src) * (int64_t)fi;
+                    const int64_t pbs = pb0 + 4 * (gather ? std::min<int64_t>(src, b->feat_rows) : src) * (int64_t)fi;
                     gm_prof_note(GM_PROF_AGG_BOUND, pb0 + 4 * std::min<int64_t>(b->unfused_edges, b->rows) * (int64_t)fi - pb);      // (difference to the exact count)
                     GM_TRY(launch_agg(a, pb, pbs, st));
                 } else {
                     if (a.e_w) GM_TRY(gm_agg_stream_args(a, b, 0, gather, st));      // full launches may take the LDS-DMA stream kernel (agg_stream.hip)
                     // compulsory HBM bytes: a gather launch reads rows of the (cache-resident) feature table, at most all of it
                     int64_t strict = gm_aggregate_bytes(b, fi);
-                    if (gather) strict += 4 * b->rows - 4 * b->rows * (int64_t)fi + std::min<int64_t>(4 * b->rows * (int64_t)fi, 4 * b->store->total_nodes * (int64_t)fi);
+                    if (gather) strict += 4 * b->rows - 4 * b->rows * (int64_t)fi + std::min<int64_t>(4 * b->rows * (int64_t)fi, 4 * b->feat_rows * (int64_t)fi);
                     GM_TRY(launch_agg(a, gm_aggregate_bytes(b, fi), strict, st));
                     if (l == 0) c.z1_valid = 1;
                 }
@@ -989,7 +989,7 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
             }
             if (fuse) {
                 g.zside = c.Z[l]; g.ldz = fi;
-                if (gather) { g.A = b->store->d_feat; g.lda = b->store->feat_ld; g.fuse2 = b->d_fuse2_feat; }
+                if (gather) { g.A = b->feat; g.lda = b->feat_ld; g.fuse2 = b->d_fuse2_feat; }
                 else { g.A = xin; g.lda = fi; g.fuse2 = b->d_fuse2; }
             }
             GM_TRY(gm_launch_gemm_nn(g, st));
@@ -1051,7 +1051,7 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
             if (c.zfused[l]) {                 // the forward ran fused: Z[l] holds the rows of three or more sources, the table forms the others
                 const bool gather = l == 0 && !c.x0_user;
                 w.fuse2 = gather ? b->d_fuse2_feat : b->d_fuse2;
-                w.gx = gather ? b->store->d_feat : (l > 0 ? c.H[l - 1] : c.x0_user); w.ldgx = gather ? b->store->feat_ld : fi;
+                w.gx = gather ? b->feat : (l > 0 ? c.H[l - 1] : c.x0_user); w.ldgx = gather ? b->feat_ld : fi;
             }
             if (l > 0) {
                 gm_gemm_args g{}; g.A = dQ; g.lda = fo; g.C = T; g.ldc = fi; g.K = fo; g.N = fi;
@@ -1175,7 +1175,7 @@ static gm_agg_args cone_agg(const gm_cone* cn, const gm_cone_level& up, int tran
 
 static int cone_forward(GcnCtx& c, const float* params, int64_t pstride, float* logits, hipStream_t st, int reuse_z1, int skip_head) {
     const gm_layout& L = c.L; const gm_batch* b = c.b; const gm_cone* cn = c.cone;
-    GM_REQUIRE(L.dims[0] == b->store->feat_dim || L.dims[0] == b->store->feat_ld, GM_EINVAL, "forward: dims[0]=%d but the store has %d features", L.dims[0], b->store->feat_dim);
+    GM_TRY(gm_check_feat_dim(b, L.dims[0], "forward"));
     GM_REQUIRE((L.link != 0) == (b->centres == 2), GM_EINVAL, "forward: link_pred model needs a 2-centre batch and vice versa");
     GM_REQUIRE(!c.x0_user && !c.centre, GM_EINVAL, "forward: the cone schedule reads features and centres from the batch");
     const float* xin = nullptr;
@@ -1184,7 +1184,7 @@ static int cone_forward(GcnCtx& c, const float* params, int64_t pstride, float* 
         const int fi = L.dims[l], fo = L.dims[l + 1];
         if (fi > fo) {                      // multiply on the source level, then aggregate into the destination level
             const float* A = xin;
-            if (l == 0) { GM_TRY(gm_gather_rows(b->store, lo.d_feat_row, lo.n, fi, c.X0, st)); A = c.X0; }
+            if (l == 0) { GM_TRY(gm_gather_rows(b, lo.d_feat_row, lo.n, fi, c.X0, st)); A = c.X0; }
             gm_gemm_args g{}; g.A = A; g.lda = fi; g.B = params + L.w_off[l]; g.b_stride = pstride; g.C = c.Z[l]; g.ldc = fo; g.K = fi; g.N = fo;
             g.row_scale = lo.d_norm; g.tiles = lo.d_tiles; g.n_tiles = lo.n_tiles; g.rows = lo.n;
             GM_TRY(gm_launch_gemm_nn(g, st));
@@ -1196,7 +1196,7 @@ static int cone_forward(GcnCtx& c, const float* params, int64_t pstride, float* 
             if (!(l == 0 && reuse_z1 && c.z1_valid)) {
                 gm_agg_args a = cone_agg(cn, up, 0);
                 a.s_in = lo.d_norm; a.e_w = up.d_enorm; a.out = c.Z[l]; a.rows = up.n; a.width = fi; a.ldx = fi;
-                if (l == 0) { a.x = b->store->d_feat; a.x_row = lo.d_feat_row; a.x_idx = up.d_efeat; a.ldx = b->store->feat_ld; } else a.x = xin;
+                if (l == 0) { a.x = b->feat; a.x_row = lo.d_feat_row; a.x_idx = up.d_efeat; a.ldx = b->feat_ld; } else a.x = xin;
                 GM_TRY(cone_launch_agg(a, lo.n, up.nnz, st));
                 if (l == 0) c.z1_valid = 1;
             }
@@ -1565,11 +1565,12 @@ __global__ void k_pad_params(const float* theta, int64_t P, int64_t cut, int64_t
 // The model the kernels run: layer 1 reads the store's padded feature rows (gm_store::feat_ld columns, the extra ones zero), so W_1
 // gets matching zero rows -- same sums, but the layer takes the vectorised aggregate / DMA GEMM / fast weight-gradient kernels
 // whatever the dataset's feature width (50 and 5 in the reference's Tissue-PPI / FirstMM-DB configs).
-static gm_model_t internal_model(const gm_model_t* m, const gm_store* store, int64_t* cut, int64_t* shift) {
+// (a hop-labelled batch: its own table's width and leading dimension)
+static gm_model_t internal_model(const gm_model_t* m, const gm_batch* b, int64_t* cut, int64_t* shift) {
     gm_model_t mp = *m; *cut = 0; *shift = 0;
-    if (store->feat_ld != store->feat_dim && m->dims[0] == store->feat_dim) {
-        mp.dims[0] = store->feat_ld;
-        *cut = (int64_t)store->feat_dim * m->dims[1]; *shift = (int64_t)(store->feat_ld - store->feat_dim) * m->dims[1];
+    if (b->feat_ld != b->feat_dim && m->dims[0] == b->feat_dim) {
+        mp.dims[0] = (int32_t)b->feat_ld;
+        *cut = (int64_t)b->feat_dim * m->dims[1]; *shift = (int64_t)(b->feat_ld - b->feat_dim) * m->dims[1];
     }
     return mp;
 }
@@ -1704,6 +1705,7 @@ static int plan_ctx(GcnCtx& c, const gm_batch* b, const gm_layout& L, const gm_h
 // What every plan starts with: the layout of the model the kernels run, Pp, the context of its (first) batch
 static int plan_prologue(const gm_model_t* m, const gm_hparams_t* hp, const gm_batch* b, gm_layout& L, int64_t& Pp, GcnCtx& c) {
     GM_TRY(gm_make_layout(m, &L));
+    GM_TRY(gm_check_feat_dim(b, L.dims[0], "model"));      // (m: the internal model -- dims[0] is the caller's, or the padded width where the caller's matched)
     Pp = (L.P + 63) / 64 * 64;
     return plan_ctx(c, b, L, hp);
 }
@@ -1781,7 +1783,8 @@ static int meta_plan(MetaPlan& p, const gm_batch* spt, const gm_batch* qry, cons
     bool agg_first = true;
     for (int l = 0; l < p.L.n_gcn; ++l) agg_first = agg_first && p.L.dims[l] <= p.L.dims[l + 1];
     // (never on weighted batches: the magnitude bounds -- k_gains, gm_bound.h -- assume edge scales <= 1; they keep the three-piece kernels, violation word 0)
-    if (p.pd.base && gm_split_np() == 2 && agg_first && !hp->sparse_bwd && !p.S.cone && spt->store->d_feat_amax && !spt->weighted && !qry->weighted &&
+    // (nor on hop-labelled batches: the layer-1 operand bound -- the store's largest |feature| -- does not cover the 1.0 label entries)
+    if (p.pd.base && gm_split_np() == 2 && agg_first && !hp->sparse_bwd && !p.S.cone && spt->store->d_feat_amax && !spt->weighted && !qry->weighted && !spt->hop_D && !qry->hop_D &&
         spt->rows + qry->rows >= gm_knob().split16_min_rows) {
         const int per_pass = 2 * p.L.n_gcn + 1;
         const int64_t ws_s = (int64_t)p.K * per_pass * p.T * GM_BOUND_PAD, ws_q = (int64_t)K1 * per_pass * p.T * GM_BOUND_PAD, ws_w = (int64_t)p.L.n_gcn * GM_BOUND_PAD;
@@ -1803,7 +1806,7 @@ static int meta_plan(MetaPlan& p, const gm_batch* spt, const gm_batch* qry, cons
 extern "C" int64_t gm_meta_ws_bytes(const gm_batch_t* spt, const gm_batch_t* qry, const gm_model_t* m, const gm_hparams_t* hp) {
     if (!spt || !qry || !m || !hp) return -1;
     MetaPlan p; int64_t need = 0, cut, shift;
-    const gm_model_t mp = internal_model(m, spt->store, &cut, &shift);
+    const gm_model_t mp = internal_model(m, spt, &cut, &shift);
     if (meta_plan(p, spt, qry, &mp, hp, nullptr, 0, 1, 1, 1, &need) != GM_OK) return -1;
     return need;
 }
@@ -1822,6 +1825,7 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
     GM_REQUIRE(spt->sets == qry->sets, GM_EINVAL, "meta_step: %d support sets but %d query sets", spt->sets, qry->sets);
     GM_REQUIRE(spt->store == qry->store, GM_EINVAL, "meta_step: support and query batches come from different stores");
     GM_REQUIRE(spt->weighted == qry->weighted, GM_EINVAL, "meta_step: one of the support and query batches is weighted, the other is not");
+    GM_REQUIRE(spt->hop_D == qry->hop_D, GM_EINVAL, "meta_step: the support batch has hop labels D=%d but the query batch D=%d", spt->hop_D, qry->hop_D);
     const int K = hp->update_step;
     GM_REQUIRE(K >= 1, GM_EINVAL, "meta_step: update_step must be >= 1");
     GM_REQUIRE(!hp->need_meta_grad || K >= 2, GM_EINVAL,
@@ -1837,7 +1841,7 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
     const int Ct = cs.Ct, ns = cs.n, nq = cq.n;
     MetaPlan p;
     int64_t cut = 0, shift = 0;
-    const gm_model_t mp = internal_model(m, spt->store, &cut, &shift);
+    const gm_model_t mp = internal_model(m, spt, &cut, &shift);
     gm_layout Lu;                                          // the caller's parameter layout (theta, out)
     GM_TRY(gm_make_layout(m, &Lu));
     GM_TRY(meta_plan(p, spt, qry, &mp, hp, ws, ws_bytes, Ct, ns, nq, nullptr));
@@ -2005,7 +2009,7 @@ static int adapt_plan(SupportPlan& p, const gm_batch* spt, const gm_model_t* m, 
 extern "C" int64_t gm_adapt_ws_bytes(const gm_batch_t* spt, const gm_model_t* m, const gm_hparams_t* hp) {
     if (!spt || !m || !hp || hp->update_step < 0) return -1;
     SupportPlan p; int64_t need = 0, cut, shift;
-    const gm_model_t mp = internal_model(m, spt->store, &cut, &shift);
+    const gm_model_t mp = internal_model(m, spt, &cut, &shift);
     if (adapt_plan(p, spt, &mp, hp, nullptr, 0, &need) != GM_OK) return -1;
     return need;
 }
@@ -2027,7 +2031,7 @@ extern "C" int gm_meta_adapt(const gm_batch_t* spt, const int32_t* y_spt, const 
     GM_REQUIRE(c_task >= cs.Ct, GM_EINVAL, "meta_adapt: c_task=%d but a support set has %d classes", c_task, cs.Ct);
     SupportPlan p;
     int64_t cut = 0, shift = 0;
-    const gm_model_t mp = internal_model(m, spt->store, &cut, &shift);
+    const gm_model_t mp = internal_model(m, spt, &cut, &shift);
     GM_TRY(adapt_plan(p, spt, &mp, hp, ws, ws_bytes, nullptr));
     const int T = p.T, C = p.L.n_out; const int64_t Pp = p.Pp;
     p.Ct = cs.Ct; p.ns = cs.n; p.uni_s = cs.uniform ? 1 : 0; p.qmax_s = cs.qmax;
@@ -2078,7 +2082,7 @@ static int predict_plan(PredictPlan& p, const gm_batch* qry, const gm_model_t* m
 extern "C" int64_t gm_predict_ws_bytes(const gm_batch_t* qry, const gm_model_t* m, const gm_hparams_t* hp) {
     if (!qry || !m || !hp) return -1;
     PredictPlan p; int64_t need = 0, cut, shift;
-    const gm_model_t mp = internal_model(m, qry->store, &cut, &shift);
+    const gm_model_t mp = internal_model(m, qry, &cut, &shift);
     if (predict_plan(p, qry, &mp, hp, true, nullptr, 0, &need) != GM_OK) return -1;
     return need;
 }
@@ -2098,7 +2102,7 @@ extern "C" int gm_proto_predict(const gm_batch_t* qry, const gm_model_t* m, cons
     hipStream_t st = (hipStream_t)stream;
     PredictPlan p;
     int64_t cut = 0, shift = 0;
-    const gm_model_t mp = internal_model(m, qry->store, &cut, &shift);
+    const gm_model_t mp = internal_model(m, qry, &cut, &shift);
     GM_TRY(predict_plan(p, qry, &mp, hp, logits_out == nullptr, ws, ws_bytes, nullptr));
     const int T = qry->sets;
     float* logits = logits_out ? logits_out : p.logits;

@@ -3,6 +3,7 @@ h-hop extraction, sampling, induced-subgraph build and batching done by HIP kern
 (gm_extract, include/gmeta_hip.h) on HBM-resident CSR instead of DGL + Python loops."""
 import collections
 import concurrent.futures
+import contextlib
 import csv
 import ctypes as C
 import itertools
@@ -16,6 +17,31 @@ from torch.utils.data import Dataset
 
 from . import _lib
 from .graphstore import GraphStore
+
+
+def hop_label_width(D, link_pred):
+    """Columns the hop-distance labels add to a feature row (gm_set_hop_labels): D + 2 per centre -- distances 0..D and the 'farther or
+    unreachable' bucket -- one centre for node seeds, two for pairs.  A labelled model's dims[0] is the store's feature width plus this."""
+    D = int(D or 0)
+    if not 0 <= D <= 7:
+        raise ValueError('hop_labels must be 0 (off) or a label cap D in 1..7')
+    return 0 if D == 0 else (D + 2) * (2 if link_pred else 1)
+
+
+@contextlib.contextmanager
+def hop_labels_switch(D):
+    """The calling thread's hop-label switch (gm_set_hop_labels) set to D for the length of the block: batches built inside carry hop-distance
+    labels with cap D (0: none).  The switch is per thread: a block covers only the extraction calls made from its own thread."""
+    D = int(D or 0)
+    if not 0 <= D <= 7:
+        raise ValueError('hop_labels must be 0 (off) or a label cap D in 1..7')
+    lib = _lib.lib()
+    old = lib.gm_get_hop_labels()
+    lib.gm_set_hop_labels(D)
+    try:
+        yield
+    finally:
+        lib.gm_set_hop_labels(old)
 
 
 class _NodeIds(collections.abc.Sequence):
@@ -213,6 +239,21 @@ class SubgraphBatch:
         """True for a batch cut from a weighted GraphStore (it carries the induced edge weights)."""
         return bool(_lib.lib().gm_batch_weighted(self.handle))
 
+    @property
+    def hop_labels_cap(self):
+        """The label cap D of a hop-labelled batch, 0 for an unlabelled one (gm_batch_hop_labels)."""
+        return int(_lib.lib().gm_batch_hop_labels(self.handle))
+
+    @property
+    def hop_labels(self):
+        """Host int8 [rows, centres]: the hop-distance label of every row per centre (GM_F_HOP), read on first use; ValueError on an unlabelled batch."""
+        return self._read(_lib.F_HOP, self.rows * self.centres, np.int8).reshape(self.rows, self.centres)
+
+    @property
+    def feat_dim(self):
+        """Width of the batch's feature rows: the store's, plus the label columns on a hop-labelled batch (what a model's dims[0] must be)."""
+        return self.store.feat_dim + hop_label_width(self.hop_labels_cap, self.centres == 2)
+
     def edge_weights(self, transposed=False):
         """The induced edge weights, aligned with csr(transposed)[1] (weighted batches only: ValueError otherwise)."""
         return self._read(_lib.F_EDGE_W_T if transposed else _lib.F_EDGE_W, self.edges, np.float32)
@@ -242,7 +283,8 @@ class Subgraphs(Dataset):
     (create_batch_*) follows sdp.py:150-292; `tables=` can replace the CSV files by in-memory
     {'train': (names, labels)} style dictionaries (names 'g_i' or 'g_i_j', labels as in the CSV)."""
 
-    def __init__(self, root, mode, subgraph2label, n_way, k_shot, k_query, batchsz, args, adjs, h, tables=None, verbose=True, sample_mode=None, link_hops=None):
+    def __init__(self, root, mode, subgraph2label, n_way, k_shot, k_query, batchsz, args, adjs, h, tables=None, verbose=True, sample_mode=None, link_hops=None,
+                 hop_labels=None):
         self.batchsz, self.n_way, self.k_shot, self.k_query = batchsz, n_way, k_shot, k_query
         # 'device' (default): neighbourhoods above sample_nodes are thinned by the keyed permutation in gm_extract.
         # 'reference': the node sets the REFERENCE would draw for the same global-RNG history (sdp.py:312-314,337-339):
@@ -275,6 +317,9 @@ class Subgraphs(Dataset):
                                  "RNG history of it to replay")
         # what every gm_extract / gm_extract_pair call of this dataset passes as its link_pred mode
         self.link_mode = _lib.LINK_SYMMETRIC if self.link_hops == 'symmetric' else int(self.link_pred_mode)
+        # hop-distance node labels (gm_set_hop_labels): cap D in 1..7, appended to the feature rows of every batch this dataset extracts; 0 / None = off
+        self.hop_labels = int((hop_labels if hop_labels is not None else getattr(args, 'hop_labels', 0)) or 0)
+        hop_label_width(self.hop_labels, self.link_pred_mode)                 # (ValueError outside 0..7)
         if not isinstance(adjs, GraphStore):
             raise TypeError('adjs must be a gmeta_amd.GraphStore (graphs + features resident in HBM)')
         self.G = adjs
@@ -498,7 +543,8 @@ class Subgraphs(Dataset):
         names = [n for t in tasks for n in (list(t[1]) + list(t[3]))]
         # sizing pass: with a threshold of sample_nodes + 1 every neighbourhood the reference would sample comes back with more than
         # sample_nodes nodes (thinned or not) and every other one comes back exact -- without per-subgraph buffers of graph size
-        full = SubgraphBatch.extract(self.G, seeds, [0, len(seeds)], self.h, self.sample_nodes + 1, self.rng_seed, self.link_pred_mode)
+        with hop_labels_switch(0):              # (only its node lists are read)
+            full = SubgraphBatch.extract(self.G, seeds, [0, len(seeds)], self.h, self.sample_nodes + 1, self.rng_seed, self.link_pred_mode)
         off, par = full.sub_off, full.parent()
         lists = []
         for k, (name, (g, i, j)) in enumerate(zip(names, seeds.tolist())):
@@ -537,7 +583,7 @@ class Subgraphs(Dataset):
         return torch.cuda.Stream(priority=Subgraphs._PREFETCH_PRIORITY)
 
     def _extract_on(self, stream, seeds, off):
-        with torch.cuda.stream(stream):
+        with torch.cuda.stream(stream), hop_labels_switch(self.hop_labels):      # (the helper thread's own switch)
             b = SubgraphBatch.extract(self.G, seeds, off, self.h, self.sample_nodes, self.rng_seed, self.link_mode)
             ev = torch.cuda.Event()
             ev.record(stream)
@@ -550,6 +596,11 @@ class Subgraphs(Dataset):
         return np.concatenate([a[0] for a in arrs]), off_s, np.concatenate([a[1] for a in arrs]), off_q
 
     def _extract_tasks(self, indices, arrs=None, packed=None):
+        # every extraction of this dataset runs under its hop-label switch, set in the calling thread (the caller's, a builder thread of batches())
+        with hop_labels_switch(self.hop_labels):
+            return self._extract_tasks_switched(indices, arrs, packed)
+
+    def _extract_tasks_switched(self, indices, arrs=None, packed=None):
         if arrs is None:
             arrs = [self._task_arrays(i) for i in indices]
         if self.sample_mode == 'reference':
@@ -587,8 +638,9 @@ class Subgraphs(Dataset):
         or 'g_i_j' for pairs), extracted like the tasks' own subgraphs (this dataset's h, sample_nodes, sampling seed, link mode and link_hops)."""
         seeds = [self._seeds(list(names)) for names in names_per_task]
         off = np.cumsum([0] + [len(s) for s in seeds])
-        return SubgraphBatch.extract(self.G, np.concatenate(seeds) if seeds else np.zeros((0, 3), np.int32), off, self.h, self.sample_nodes, self.rng_seed,
-                                     self.link_mode)
+        with hop_labels_switch(self.hop_labels):
+            return SubgraphBatch.extract(self.G, np.concatenate(seeds) if seeds else np.zeros((0, 3), np.int32), off, self.h, self.sample_nodes, self.rng_seed,
+                                         self.link_mode)
 
     def get_batch(self, indices):
         """MI355X-first counterpart of DataLoader(..., collate_fn=collate): the subgraphs of ALL tasks of a

@@ -130,8 +130,27 @@ int gm_extract_pair(const gm_store_t* store, const gm_seed_t* seeds_a, int32_t n
 int gm_batch_from_nodes(const gm_store_t* store, const gm_seed_t* seeds, int32_t n_seeds,
                         const int32_t* set_offsets, int32_t n_sets, const int32_t* nodes_flat,
                         const int64_t* nodes_off, int32_t link_pred, void* stream, gm_batch_t** out);
+/* HOP-DISTANCE LABELS, gm_set_hop_labels(D): off (0) by default, per calling thread (like gm_set_ragged_classes), D in 1..7 (anything outside 0..7
+ * is ignored and leaves an error string); read by gm_extract, gm_extract_pair and gm_batch_from_nodes when they build a batch -- the labelling
+ * step of local-subgraph methods (SEAL, distance encoding), beyond the reference.  Per subgraph and per centre c (one for node seeds, two -- i, j --
+ * for pairs), with the BATCH's own induced in-edge CSR (GM_F_INDPTR / GM_F_INDICES, i.e. after sampling):
+ *   d_c(v)     = the least k >= 0 such that a directed path v -> ... -> c of k edges lies inside the subgraph (BFS from c along in-edges);
+ *   label_c(v) = d_c(v) if d_c(v) <= D, else D + 1 (farther rows and unreachable ones, e.g. where sampling cut the path);
+ *   distances are topological: edge weights, parallel edges and self loops do not change them;
+ *   Lw = D + 2 columns per centre;  x'(v) = [x(v) | onehot_Lw(label_i(v)) | onehot_Lw(label_j(v))] (second block: pairs only; a pair with
+ *   i == j gets two identical blocks), so a model for a labelled batch has dims[0] = feat_dim + centres * Lw.  Labels are constants (no gradient).
+ * GM_F_HOP exposes the labels; the batch owns its [rows, ld'] table of x' rows (ld' = the padded width, rows * ld' * 4 bytes of HBM per batch)
+ * and every layer-1 gather of every schedule reads it through identity row tables (it no longer reads the store's cache-resident table), while
+ * GM_F_FEAT_ROW keeps meaning the store row.  gm_gather_features returns x'.  A model whose dims[0] is not the batch's feature width is GM_EINVAL
+ * (the message names both).  gm_set_split_pieces(2) is ignored on labelled batches (three pieces, violation word 0): the layer-1 operand bound
+ * does not cover the 1.0 entries.  With the switch off every batch field, launch and output is what it was without the feature.
+ * gm_batch_hop_labels: the batch's D, or 0. */
+void gm_set_hop_labels(int32_t D);
+int32_t gm_get_hop_labels(void);
+int32_t gm_batch_hop_labels(const gm_batch_t* b);
 /* dgl.batch over already-built batches (sets are appended in order).  Inputs stay valid.  Parts of one store are all weighted or all
- * unweighted; a mix (hand-made handles) is GM_EINVAL. */
+ * unweighted; a mix (hand-made handles) is GM_EINVAL.  Parts are all hop-labelled with the same D, or all unlabelled (a mix: GM_EINVAL); the result's
+ * feature table is the concatenation of the parts'. */
 int gm_batch_concat(const gm_batch_t* const* parts, int32_t n_parts, void* stream, gm_batch_t** out);
 /* Receptive-field tables for gm_hparams_t.cone with an n_gcn-layer model (built on `stream`, cached in the
  * batch; gm_meta_ws_bytes/gm_meta_step build them on first use otherwise).  level_rows/level_edges
@@ -161,12 +180,13 @@ enum gm_field {
     GM_F_INDICES_T,     /* int32[edges]   destination ROW of every out-edge                                          */
     GM_F_CENTRE,        /* int32[subs*centres] local index of the centre(s) inside each subgraph (sdp.py:318-319)    */
     GM_F_NORM,          /* float[rows]    in_degree.clamp(1)^-0.5 (learner.py:29); weighted batches: the weighted in-degree      */
-    GM_F_FEAT_ROW,      /* int32[rows]    row of the store's feature matrix for each batch row                       */
+    GM_F_FEAT_ROW,      /* int32[rows]    row of the store's feature matrix for each batch row (also on hop-labelled batches) */
     GM_F_NORM_SRC,      /* float[rows]    GM_F_NORM with the sign bit set on every row without an out-edge inside the batch: no later
                                           kernel reads that row of a hidden activation below the last layer (GM_DEAD_ROWS)       */
     GM_F_NORM_CENTRE,   /* float[rows]    GM_F_NORM with the sign bit set on every row that is not a centre                     */
     GM_F_EDGE_W,        /* float[edges]   weight of every in-edge, aligned with GM_F_INDICES (weighted batches only: GM_EINVAL otherwise) */
-    GM_F_EDGE_W_T       /* float[edges]   the same weights in the order of GM_F_INDICES_T (weighted batches only)                       */
+    GM_F_EDGE_W_T = 14, /* float[edges]   the same weights in the order of GM_F_INDICES_T (weighted batches only)                       */
+    GM_F_HOP = 15       /* int8[rows*centres] hop-distance label of every row per centre, row-major [rows, centres] (hop-labelled batches only: GM_EINVAL otherwise) */
 };
 int32_t gm_batch_weighted(const gm_batch_t* b);
 /* Copies a field to host memory (synchronises `stream` internally). */
@@ -177,7 +197,7 @@ int gm_batch_device_ptr(const gm_batch_t* b, int32_t field, void** dptr);
 int gm_batch_source_rows(const gm_batch_t* b, int64_t* n_rows);
 
 /* ---- Feature gather: replaces np.vstack([feat[g][ids] ...]) + H2D (meta.py:119-120,193-194).
- * x_out: device fp32 [rows, feat_dim]. */
+ * x_out: device fp32 [rows, feat_dim]; hop-labelled batches: [rows, feat_dim + centres * (D + 2)], the labelled rows x'. */
 int gm_gather_features(const gm_batch_t* b, float* x_out, void* stream);
 
 /* ---- GCN building blocks (GraphConv.forward, learner.py:25-56), exported for tests/profiling.

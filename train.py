@@ -56,6 +56,9 @@ def parse(argv=None):
     ap.add_argument('--link_hops', default='reference', choices=['reference', 'symmetric'],
                     help="pair subgraphs (--link_pred_mode True): 'reference' = 2 hops around i and 1 hop around j whatever --h says, as the reference "
                          "builds them; 'symmetric' = --h hops around both endpoints")
+    ap.add_argument('--hop_labels', type=int, default=0,
+                    help='D in 1..7: append one-hot hop-distance labels (distance to the centre, to both endpoints of a pair; capped at D) to the '
+                         'features of every subgraph; 0 = off')
     ap.add_argument('--eval_tasks', type=int, default=100, help='validation / test tasks (the reference hard-codes 100, train.py:90-91)')
     # schedules of the MI355X build that return the same results faster (include/gmeta_hip.h, gm_hparams_t); 0 = as the reference computes
     ap.add_argument('--hoist_z1', type=int, default=0, help='1: aggregate the layer-1 input once per meta-step instead of in every forward')
@@ -82,7 +85,7 @@ def main(args):
     info = datadir.load_labels(root)
     total_class = len(np.unique(np.array(list(info.values()))))
     labels_num = args.n_way if args.task_setup == 'Disjoint' else total_class   # train.py:58-61
-    config = [('GraphConv', [feat[0].shape[1], args.hidden_dim])]
+    config = [('GraphConv', [feat[0].shape[1] + gmeta_amd.hop_label_width(args.hop_labels, args.link_pred_mode == 'True'), args.hidden_dim])]
     if args.h > 1:
         config = config + [('GraphConv', [args.hidden_dim, args.hidden_dim])] * (args.h - 1)
     config = config + [('Linear', [args.hidden_dim, labels_num])]
