@@ -65,6 +65,8 @@ PROTOTYPES = {
     'gm_proto_loss_qry': (C.c_int, [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
     'gm_set_ragged_classes': (None, [i32]),
     'gm_get_ragged_classes': (i32, []),
+    'gm_set_readout': (None, [i32]),
+    'gm_get_readout': (i32, []),
     'gm_meta_ws_bytes': (i64, [vp, vp, vp, vp]),
     'gm_meta_out_floats': (i64, [vp, vp, vp]),
     'gm_meta_step': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp]),
@@ -144,8 +146,52 @@ def ptr(t):
     return C.c_void_p(t.ctypes.data)
 
 
+READOUT_CENTRE, READOUT_MEAN = 0, 1      # GM_READOUT_*
+READOUTS = {'centre': READOUT_CENTRE, 'mean': READOUT_MEAN}
+
+
+def config_readout(config):
+    """The readout a config asks for: 'centre' (no entry, or ('Readout', ['centre'])) or 'mean' (('Readout', ['mean'])).  At most one entry, after the
+    Linear entry's GraphConv stack or anywhere else -- but before a trailing ('LinkPred', [True]), which learner.py:78-79 looks for at config[-1]."""
+    ent = [(k, p) for k, (n, p) in enumerate(config) if n == 'Readout']
+    if not ent:
+        return 'centre'
+    if len(ent) > 1:
+        raise ValueError("config holds %d 'Readout' entries; at most one" % len(ent))
+    k, p = ent[0]
+    if not isinstance(p, (list, tuple)) or len(p) != 1 or p[0] not in READOUTS:
+        raise ValueError("config entry ('Readout', %r): expected ['centre'] or ['mean']" % (p,))
+    if any(n == 'LinkPred' for n, _ in config) and config[-1][0] != 'LinkPred':
+        raise ValueError("the ('Readout', ...) entry must come before the trailing ('LinkPred', [True]) entry")
+    return p[0]
+
+
+class readout_switch:
+    """The calling thread's readout (gm_set_readout) set for the length of the block; the block restores what it found, after an exception too."""
+
+    def __init__(self, readout):
+        self.mode = READOUTS[readout] if isinstance(readout, str) else int(readout)
+
+    def __enter__(self):
+        l = lib()
+        self.was = int(l.gm_get_readout())
+        if self.was != self.mode:
+            l.gm_set_readout(self.mode)
+        return self
+
+    def __exit__(self, *exc):
+        if self.was != self.mode:
+            lib().gm_set_readout(self.was)
+        return False
+
+
 def make_model(config):
-    """train.py:67-75 config list -> gm_model_t.  Mirrors learner.py:78-97 parsing."""
+    """train.py:67-75 config list -> gm_model_t.  Mirrors learner.py:78-97 parsing.  The readout is not part of gm_model_t (a switch of the calling
+    thread, gm_set_readout): config_readout(config) names it."""
+    unknown = sorted({str(n) for n, _ in config if n not in ('GraphConv', 'Linear', 'LinkPred', 'Readout', 'Attention')})
+    if unknown:
+        raise ValueError('unknown config entries: %s' % ', '.join(unknown))
+    config_readout(config)
     gcn = [p for n, p in config if n == 'GraphConv']
     lin = [p for n, p in config if n == 'Linear']
     if any(n == 'Attention' for n, _ in config):

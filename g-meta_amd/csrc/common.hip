@@ -214,12 +214,21 @@ gm_stager::~gm_stager() {
     }
 }
 
+// Readout of the calling thread (gm_set_readout, include/gmeta_hip.h): read where a model layout is made, i.e. at every call that takes a gm_model_t
+static thread_local int g_readout = GM_READOUT_CENTRE;
+extern "C" void gm_set_readout(int32_t mode) {
+    if (mode != GM_READOUT_CENTRE && mode != GM_READOUT_MEAN) { gm_set_error("gm_set_readout: mode=%d ignored (0 = centre, 1 = mean)", mode); return; }
+    g_readout = mode;
+}
+extern "C" int32_t gm_get_readout(void) { return g_readout; }
+
 int gm_make_layout(const gm_model_t* m, gm_layout* L) {
     GM_REQUIRE(m && m->n_gcn >= 1 && m->n_gcn <= GM_MAX_GCN, GM_EINVAL, "model: n_gcn must be in [1,%d]", GM_MAX_GCN);
     GM_REQUIRE(m->n_out >= 1 && m->n_out <= 64, GM_ERANGE, "model: n_out=%d outside [1,64]", m->n_out);
     L->n_gcn = m->n_gcn;
     L->n_out = m->n_out;
     L->link = m->link_pred ? 1 : 0;
+    L->readout = g_readout;
     int64_t off = 0;
     for (int l = 0; l <= m->n_gcn; ++l) {
         GM_REQUIRE(m->dims[l] >= 1 && m->dims[l] <= 2048, GM_ERANGE, "model: dims[%d]=%d outside [1,2048]", l, m->dims[l]);
@@ -229,7 +238,7 @@ int gm_make_layout(const gm_model_t* m, gm_layout* L) {
         L->w_off[l] = off; off += (int64_t)m->dims[l] * m->dims[l + 1];
         L->b_off[l] = off; off += m->dims[l + 1];
     }
-    L->hc = m->dims[m->n_gcn] * (L->link ? 2 : 1);
+    L->hc = m->dims[m->n_gcn] * ((L->link && L->readout != GM_READOUT_MEAN) ? 2 : 1);      // mean: one pooled vector per subgraph, pairs too
     L->wl_off = off; off += (int64_t)m->n_out * L->hc;
     L->bl_off = off; off += m->n_out;
     L->P = off;

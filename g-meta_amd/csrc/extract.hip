@@ -962,6 +962,7 @@ static void batch_free(gm_batch* b) {
     gm_phase_timer tm("batch-free");
     hipStream_t s = b->stream;
     for (int o = 0; o < 4; ++o) if (b->hub_ev[o]) { (void)hipEventDestroy(b->hub_ev[o]); b->hub_ev[o] = nullptr; }
+    if (b->ro_ev) { (void)hipEventDestroy(b->ro_ev); b->ro_ev = nullptr; }
     if (b->used_ev) {
         if (hipStreamWaitEvent(s, b->used_ev, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipEventSynchronize(b->used_ev); }
         (void)hipEventDestroy(b->used_ev); b->used_ev = nullptr;

@@ -190,6 +190,11 @@ struct gm_batch {
     int32_t* d_c_tiles = nullptr; int32_t n_c_tiles = 0;          // GEMM tiles over centre rows (per set)
     int32_t* d_c_chunks = nullptr; int32_t* d_c_set_chunk_off = nullptr; int32_t n_c_chunks = 0;
     int32_t* d_e1_chunks = nullptr; int32_t* d_e1_set_chunk_off = nullptr; int32_t n_e1_chunks = 0;
+    // mean readout (gm_set_readout; model.hip: readout_tables), built at first use from h_sub_off: every subgraph cut into chunks of GM_RO_ROWS rows, one int4
+    // {row0, rows, subgraph, rows of the subgraph} per chunk, and one int4 {subgraph, first chunk, chunks, rows} per subgraph of more than one chunk
+    mutable int32_t* d_ro_chunks = nullptr; mutable int32_t* d_ro_multi = nullptr; mutable int32_t n_ro_chunks = 0, n_ro_multi = 0;
+    // the upload went to ro_stream and ro_ev was recorded behind it: a later caller on ANOTHER stream waits on it before its kernels read the tables
+    mutable hipStream_t ro_stream = nullptr; mutable hipEvent_t ro_ev = nullptr;
     mutable gm_cone* cone[GM_MAX_GCN + 1] = {};     // receptive-field tables per number of GCN layers (gm_hparams_t.cone)
     hipStream_t stream = nullptr;      // stream the arrays were produced on (and are freed on, stream-ordered)
     // The ~45 device arrays above are carved out of a few slabs (gm_balloc): a stream-ordered allocation or free costs the host 20-35 us, and a
@@ -287,6 +292,7 @@ struct gm_layout {
     int n_gcn;
     int dims[GM_MAX_GCN + 1];
     int n_out, link, hc;              // hc = width of the head input
+    int readout;                      // GM_READOUT_* of the calling thread when the layout was made (gm_set_readout): under MEAN hc = dims[n_gcn] whatever `link` says
     int64_t w_off[GM_MAX_GCN], b_off[GM_MAX_GCN], wl_off, bl_off, P;
 };
 int gm_make_layout(const gm_model_t* m, gm_layout* L);
@@ -516,7 +522,9 @@ static inline int gm_wgrad_chunk_rows(const std::vector<int32_t>& set_off, int n
 #define GM_PROF_GEMM_BYTES 13         // work-only shadow of EVERY grouped GEMM launch (categories 1, 4, 6): compulsory HBM bytes, A rows read once + the C rows it stores
 #define GM_PROF_WGRAD_BYTES 14        // ... of every weight-gradient launch (categories 2, 5, 7): the A and G rows read once
 #define GM_PROF_HEAD 15               // head + prototypical loss (+ head backward) launches: time; work = subgraphs
-#define GM_PROF_CATS 16
+#define GM_PROF_READOUT 16            // mean readout, forward (k_readout_mean + k_readout_mean_fin): work = algorithmic bytes 4 rows Hd + 4 subs Hd
+#define GM_PROF_READOUT_BWD 17        // mean readout, backward (k_readout_mean_bwd): work = algorithmic bytes 8 rows Hd + 4 subs Hd
+#define GM_PROF_CATS 18
 void gm_prof_begin(int cat, hipStream_t s, int64_t work);
 void gm_prof_end(int cat, hipStream_t s);
 void gm_prof_reset(int n_cats = GM_PROF_CATS);

@@ -701,6 +701,7 @@ struct GcnCtx {
     const float* wt_of[GM_MAX_GCN]; int64_t wt_stride[GM_MAX_GCN];      // the parameter vector (pointer, per-set stride) WTl[l] is the transpose of
     uint8_t* M[GM_MAX_GCN];      // packed relu' bits of H[l] (one byte per 4 columns): what the backward reads instead of H[l] (dense schedule)
     float* cG2; float* cT2; float* cG1; float* partial_c;      // compact matrices of the row-sparse backward
+    float* Pool; float* Gpool; float* ro_part;                 // mean readout (L.readout): pooled rows P [subs, Hd] (the head's compact input), their gradient G [subs, Hd], chunk partials
     const float* x0_user; const int32_t* centre; int z1_valid;
     int zw[GM_MAX_GCN];
     const gm_cone* cone;       // non-NULL: receptive-field schedule, every buffer is compact (gm_hparams_t.cone)
@@ -758,6 +759,13 @@ static int weight_planes(GcnCtx& c, const float* params, int64_t pstride, int l,
     return GM_OK;
 }
 
+// Mean readout (gm_set_readout; kernels and launchers at the end of this file): the batch's chunk tables, P = mean rows of H_L, dQ_L from G
+static bool mean_readout(const GcnCtx& c) { return c.L.readout == GM_READOUT_MEAN; }
+static int64_t readout_chunk_count(const gm_batch* b);
+static int readout_tables(const gm_batch* b, hipStream_t s);
+static int readout_fwd(const GcnCtx& c, hipStream_t st);
+static int readout_bwd(const GcnCtx& c, hipStream_t st);
+
 static void wgrad_sgd(gm_wgrad_args& w, const GcnCtx& c, int l) {
     w.sgd_cur = c.sgd.cur; w.sgd_cur_stride = c.sgd.cur_stride; w.sgd_next = c.sgd.next; w.sgd_next_stride = c.sgd.next_stride; w.sgd_lr = c.sgd.lr;
     w.w_off = c.L.w_off[l]; w.b_off = c.L.b_off[l];
@@ -804,6 +812,10 @@ static void gcn_carve(GcnCtx& c, Carver& cv) {
     c.cG2 = cv.take<float>((int64_t)c.b->n_c * maxd); c.cT2 = cv.take<float>((int64_t)c.b->n_c * maxd);
     c.cG1 = cv.take<float>((int64_t)c.b->n_e1 * maxd);
     c.partial_c = cv.take<float>((int64_t)std::max(c.b->n_c_chunks, c.b->n_e1_chunks) * maxkn);
+    if (mean_readout(c)) {
+        const int64_t pooled = (int64_t)c.b->subs * L.dims[L.n_gcn];
+        c.Pool = cv.take<float>(pooled); c.Gpool = cv.take<float>(pooled); c.ro_part = cv.take<float>(readout_chunk_count(c.b) * L.dims[L.n_gcn]);
+    }
 }
 
 extern "C" int64_t gm_gcn_ws_bytes(const gm_batch_t* b, const gm_model_t* m) {
@@ -821,6 +833,7 @@ static HeadK make_head(const GcnCtx& c, const float* params, int64_t pstride) {
     k.sub_off = b->d_sub_off; k.centre = c.centre ? c.centre : b->d_centre; k.nc = b->centres; k.sub_set = b->d_sub_set;
     k.set_sub_off = b->d_set_sub_off; k.params = params; k.pstride = pstride; k.wl_off = L.wl_off; k.bl_off = L.bl_off;
     k.hc = L.hc; k.C = L.n_out; k.subs = b->subs; k.compact = c.cone ? 1 : 0;
+    if (mean_readout(c)) { k.H = c.Pool; k.compact = 1; k.nc = 1; }      // the pooled rows, one per subgraph (pairs too): hc = Hd
     k.dq_amax = (c.np == 2 && c.am_pass >= 0) ? c.amdQ() : nullptr;
     k.subs_per_set = b->sets > 0 ? b->subs / b->sets : 0;
     for (int t = 0; t <= b->sets && k.subs_per_set; ++t) if (b->h_set_sub_off[t] != t * k.subs_per_set) k.subs_per_set = 0;
@@ -888,6 +901,8 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
     GM_REQUIRE((L.link != 0) == (b->centres == 2), GM_EINVAL, "forward: link_pred model needs a 2-centre batch and vice versa");
     const float* xin = c.x0_user;           // NULL = gather rows of the store through feat_row
     c.dq = GcnCtx::DQ_MEMSET;
+    const bool mean = mean_readout(c);      // every row of H_L is stored, dQ_L is written whole by the backward readout: no centre-row store, no dQ fill
+    if (mean) GM_TRY(readout_tables(b, st));
     // GM_DEAD_ROWS: rows nobody reads are computed and not stored (GM_CENTRE_STORE=0, "every row stored", switches it off too)
     const bool dead_rows = gm_knob().dead_rows && gm_knob().centre_store != 0 && !c.centre;
     if (c.np == 2) {                        // a new pass: its own bound slots
@@ -963,7 +978,7 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
             g.relu_bits = fwd_only == 1 ? nullptr : c.M[l];
             // last layer: only the head reads H_L, and only its centre rows (h[to_fetch]; the backward pass takes relu' from the bits and the
             // weight gradient from Z_L): the other rows are computed, their relu' bits written, their values not stored
-            if (l == L.n_gcn - 1 && !c.centre && b->d_norm_c && (gm_knob().centre_store >= 2 || (gm_knob().centre_store == 1 && fwd_only == 1))) { g.row_scale_keep = b->d_norm_c; g.n_keep = b->n_c; }
+            if (l == L.n_gcn - 1 && !mean && !c.centre && b->d_norm_c && (gm_knob().centre_store >= 2 || (gm_knob().centre_store == 1 && fwd_only == 1))) { g.row_scale_keep = b->d_norm_c; g.n_keep = b->n_c; }
             // a layer below the last: H_l is read through the edges only (the next layer's aggregate, the fused loaders, the table-formed weight gradient; the
             // backward takes relu' from the bits) -- a row without an out-edge is nobody's source: computed, its relu' bits written, its value not stored
             if (dead_rows && split_ok && l < L.n_gcn - 1 && (fwd_only == 1 || (fwd_only == 2 && c.M[l])) && L.dims[l + 1] <= L.dims[l + 2] && b->d_norm_src) {
@@ -982,7 +997,7 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
             // fwd_only == 2: the head + loss + backward follow (gm_meta_step): the last layer's GEMM zero-fills dQ on its way out instead of a memset launch
             // GM_DEAD_ROWS: ... or no fill at all, where both readers of dQ_L can take the rows the head/loss launch does not assign as zeros: the dZ GEMM on the
             // fused kernel through gm_batch::d_dq_tab, the weight gradient on the three-piece split kernel (gm_wgrad_args::g_keep)
-            if (fwd_only == 2 && l == L.n_gcn - 1 && fo == L.dims[L.n_gcn]) {
+            if (fwd_only == 2 && l == L.n_gcn - 1 && fo == L.dims[L.n_gcn] && !mean) {
                 const bool dz_ok = l == 0 || dz_centre_ok(c, l);
                 if (dead_rows && split_ok && g.np != 2 && c.np != 2 && b->d_norm_c && dz_ok && gm_wgrad_gather_ok(b->n_chunks, fi, fo)) c.dq = GcnCtx::DQ_CENTRE;
                 else { g.zero_out = c.bufA; c.dq = GcnCtx::DQ_ZEROED; }
@@ -996,6 +1011,7 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
         }
         xin = c.H[l];
     }
+    if (mean) GM_TRY(readout_fwd(c, st));
     return skip_head ? GM_OK : launch_head_fwd(c, params, pstride, logits, st);
 }
 
@@ -1012,7 +1028,10 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
     float* dQ = c.bufA; float* T = c.bufB;
     c.hold.n = 0;
     const bool dq_centre = skip_head && c.dq == GcnCtx::DQ_CENTRE;      // dQ_L holds its centre rows only (head_loss); without skip_head it is filled right here
-    if (!skip_head) {
+    if (!skip_head && mean_readout(c)) {      // G = dlogits Wl on the pooled rows, then every row of dQ_L from it
+        GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, nullptr, c.Gpool, st));
+        GM_TRY(readout_bwd(c, st));
+    } else if (!skip_head) {
         GM_HIP(hipMemsetAsync(dQ, 0, sizeof(float) * b->rows * L.dims[Lg], st));
         GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, dQ, nullptr, st));
     }
@@ -1111,7 +1130,7 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
 }
 
 static bool sparse_bwd_ok(const gm_layout& L) {
-    if (L.n_gcn > 2) return false;
+    if (L.n_gcn > 2 || L.readout == GM_READOUT_MEAN) return false;      // (mean readout: dQ_L is dense, every row reaches the head)
     for (int l = 0; l < L.n_gcn; ++l) if (L.dims[l] > L.dims[l + 1]) return false;      // aggregate-first layers only
     return true;
 }
@@ -1494,8 +1513,10 @@ static int head_loss(GcnCtx& c, const float* params, int64_t pstride, float* log
                      hipStream_t st, bool ragged = false) {      // ragged: the class tables hold ragged sets (see ProtoK)
     const gm_batch* b = c.b; const gm_layout& L = c.L;
     float* dQ = nullptr; float* Gc = nullptr;
+    const bool mean = mean_readout(c);
     if (bwd) {
-        if (c.cone) Gc = c.bufA;
+        if (mean) Gc = c.Gpool;      // the pooled rows' gradient; readout_bwd below turns it into dQ_L
+        else if (c.cone) Gc = c.bufA;
         else if (sparse && sparse_bwd_ok(L)) Gc = c.cG2;
         else {
             dQ = c.bufA;
@@ -1506,8 +1527,9 @@ static int head_loss(GcnCtx& c, const float* params, int64_t pstride, float* log
     const size_t proto_bytes = (proto_lds(pk.Ct, pk.n, pk.D, HL_THREADS) + 15) / 16 * 16;
     int max_subs = 0;
     for (int t = 0; t < b->sets; ++t) max_subs = std::max(max_subs, b->h_set_sub_off[t + 1] - b->h_set_sub_off[t]);
-    const size_t hs_bytes = sizeof(float) * ((size_t)max_subs * b->centres * L.dims[L.n_gcn] + (size_t)L.n_out * (L.hc + 1) + 2 * (size_t)max_subs * L.n_out +
-                                             (size_t)max_subs * b->centres + (size_t)pk.Ct * pk.n + (ragged ? (size_t)pk.Ct + 1 : 0)) + 16;      // + the centre-row scratch + the class rows (a ragged set's follow its class starts)
+    const int nc = mean ? 1 : b->centres;
+    const size_t hs_bytes = sizeof(float) * ((size_t)max_subs * nc * L.dims[L.n_gcn] + (size_t)L.n_out * (L.hc + 1) + 2 * (size_t)max_subs * L.n_out +
+                                             (size_t)max_subs * nc + (size_t)pk.Ct * pk.n + (ragged ? (size_t)pk.Ct + 1 : 0)) + 16;      // + the centre-row scratch + the class rows (a ragged set's follow its class starts)
     const int stage_on = gm_knob().head_stage;
     const int stage_h = stage_on && proto_bytes + hs_bytes <= 150 * 1024;
     const size_t lds = proto_bytes + (stage_h ? hs_bytes : 0);
@@ -1528,6 +1550,7 @@ static int head_loss(GcnCtx& c, const float* params, int64_t pstride, float* log
     GM_HIP(hipGetLastError());
     gm_prof_end(GM_PROF_HEAD, st);
     if (bwd && dQ && hk.dq_amax) c.dqv = true;
+    if (bwd && mean) GM_TRY(readout_bwd(c, st));
     return GM_OK;
 }
 
@@ -1695,7 +1718,7 @@ static void plan_planes(PlaneDir& pd, const gm_layout& L, int T, int K, float* f
 // A fresh context on batch b; under hp->cone with the batch's receptive-field tables (built on first use, cached in the batch)
 static int plan_ctx(GcnCtx& c, const gm_batch* b, const gm_layout& L, const gm_hparams_t* hp) {
     c = GcnCtx{}; c.b = b; c.L = L;
-    if (hp->cone) {
+    if (hp->cone && L.readout != GM_READOUT_MEAN) {      // (mean readout: every row reaches the head, the dense schedule runs)
         const gm_cone* cn = nullptr;
         GM_TRY(gm_batch_cone(b, L.n_gcn, b->stream, &cn));
         if (cn->ok) c.cone = cn;         // else: a self pair among the centres -> dense schedule
@@ -1784,7 +1807,8 @@ static int meta_plan(MetaPlan& p, const gm_batch* spt, const gm_batch* qry, cons
     for (int l = 0; l < p.L.n_gcn; ++l) agg_first = agg_first && p.L.dims[l] <= p.L.dims[l + 1];
     // (never on weighted batches: the magnitude bounds -- k_gains, gm_bound.h -- assume edge scales <= 1; they keep the three-piece kernels, violation word 0)
     // (nor on hop-labelled batches: the layer-1 operand bound -- the store's largest |feature| -- does not cover the 1.0 label entries)
-    if (p.pd.base && gm_split_np() == 2 && agg_first && !hp->sparse_bwd && !p.S.cone && spt->store->d_feat_amax && !spt->weighted && !qry->weighted && !spt->hop_D && !qry->hop_D &&
+    // (nor under the mean readout: dQ_L comes from the readout's backward kernel, which records no bound)
+    if (p.pd.base && gm_split_np() == 2 && agg_first && !hp->sparse_bwd && !p.S.cone && p.L.readout != GM_READOUT_MEAN && spt->store->d_feat_amax && !spt->weighted && !qry->weighted && !spt->hop_D && !qry->hop_D &&
         spt->rows + qry->rows >= gm_knob().split16_min_rows) {
         const int per_pass = 2 * p.L.n_gcn + 1;
         const int64_t ws_s = (int64_t)p.K * per_pass * p.T * GM_BOUND_PAD, ws_q = (int64_t)K1 * per_pass * p.T * GM_BOUND_PAD, ws_w = (int64_t)p.L.n_gcn * GM_BOUND_PAD;
@@ -1898,6 +1922,10 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
     gm_prof_reset(GM_PROF_STEP_CATS);
     gm_prof_reset_cat(GM_PROF_GEMM_SPLIT_BYTES); gm_prof_reset_cat(GM_PROF_AGG_BOUND);
     gm_prof_reset_cat(GM_PROF_GEMM_BYTES); gm_prof_reset_cat(GM_PROF_WGRAD_BYTES); gm_prof_reset_cat(GM_PROF_HEAD);
+    if (L.readout == GM_READOUT_MEAN) {      // the chunk tables of both batches, on st ahead of the event every stream of the step waits for
+        GM_TRY(readout_tables(spt, st)); GM_TRY(readout_tables(qry, st));
+        gm_prof_reset_cat(GM_PROF_READOUT); gm_prof_reset_cat(GM_PROF_READOUT_BWD);
+    }
     tm.lap("plan");
     // Two streams: `st` carries the support chain (the serial dependency through the fast weights: forward -> loss ->
     // backward -> SGD, K times), `sq` carries the K+1 query evaluations, each of which only needs fw_k and the
@@ -2181,6 +2209,182 @@ extern "C" int gm_meta_finish_adam(const float* head, int64_t P, int32_t K1, flo
     GM_REQUIRE(head && theta && exp_avg && exp_avg_sq && grad && steps && found_inf && ticket && P >= 1 && K1 >= 1 && n_steps >= 1, GM_EINVAL, "meta_finish_adam: bad arguments");
     hipLaunchKernelGGL(k_meta_finish_adam, dim3((int)std::min<int64_t>(256, (P + 511) / 512)), dim3(256), 0, (hipStream_t)stream, head, P, (int)K1, theta, exp_avg, exp_avg_sq, grad,
                        steps, (int)n_steps, lr, beta1, beta2, eps, found_inf, ticket);
+    GM_HIP(hipGetLastError());
+    return GM_OK;
+}
+
+// ================================================================================ mean readout (gm_set_readout(GM_READOUT_MEAN), include/gmeta_hip.h)
+// P[s, :] = (sum over the rows of subgraph s of H_L[r, :]) / n_s and its backward dQ_L[r, :] = H_L[r, :] > 0 ? G[s, :] / n_s : 0.  Subgraphs run from one row
+// to over a thousand, so the unit of work is a CHUNK of up to GM_RO_ROWS consecutive rows of one subgraph (host table, built once per batch from its
+// sub_off mirror): one workgroup per chunk.  The summation order is fixed by n_s and Hd alone: inside a chunk, row slot j (of RS = 256 / min(Hd / V, 256))
+// adds rows j, j + RS, ... in ascending order, the slots are added in ascending order; a subgraph of one chunk is divided and stored right there, the
+// chunks of a larger one go to `part` and are added in ascending order by k_readout_mean_fin.  No atomics.
+// Defined HERE, behind every kernel a call without the mode launches: those keep their place in the code object (see the ragged-task kernels above).
+#define GM_RO_ROWS 64
+#define GM_RO_NT 256
+template <int V> struct RoVec;
+template <> struct RoVec<1> {
+    float v;
+    __device__ __forceinline__ static RoVec zero() { return RoVec{0.f}; }
+    __device__ __forceinline__ static RoVec load(const float* p) { return RoVec{*p}; }
+    __device__ __forceinline__ void store(float* p) const { *p = v; }
+    __device__ __forceinline__ void add(const RoVec& o) { v += o.v; }
+    __device__ __forceinline__ void div(float d) { v /= d; }
+    __device__ __forceinline__ RoVec where_pos(const RoVec& g) const { return RoVec{v > 0.f ? g.v : 0.f}; }
+};
+template <> struct RoVec<4> {
+    float4 v;
+    __device__ __forceinline__ static RoVec zero() { return RoVec{make_float4(0.f, 0.f, 0.f, 0.f)}; }
+    __device__ __forceinline__ static RoVec load(const float* p) { return RoVec{*reinterpret_cast<const float4*>(p)}; }
+    __device__ __forceinline__ void store(float* p) const { *reinterpret_cast<float4*>(p) = v; }
+    __device__ __forceinline__ void add(const RoVec& o) { v.x += o.v.x; v.y += o.v.y; v.z += o.v.z; v.w += o.v.w; }
+    __device__ __forceinline__ void div(float d) { v.x /= d; v.y /= d; v.z /= d; v.w /= d; }
+    __device__ __forceinline__ RoVec where_pos(const RoVec& g) const {
+        return RoVec{make_float4(v.x > 0.f ? g.v.x : 0.f, v.y > 0.f ? g.v.y : 0.f, v.z > 0.f ? g.v.z : 0.f, v.w > 0.f ? g.v.w : 0.f)};
+    }
+};
+
+// V = 4: 16-byte loads / stores (Hd % 4 == 0, 16-byte aligned bases); V = 1: the scalar path.  chunks[k] = {row0, rows, subgraph, rows of the subgraph}
+template <int V>
+__global__ __launch_bounds__(GM_RO_NT) void k_readout_mean(const float* __restrict__ H, int Hd, const int4* __restrict__ chunks, float* __restrict__ P,
+                                                           float* __restrict__ part) {
+    __shared__ __attribute__((aligned(16))) float sm[GM_RO_NT * V];
+    typedef RoVec<V> Vec;
+    const int4 ch = chunks[blockIdx.x];
+    const int nr = ch.y, ns = ch.w;
+    const int nv = Hd / V, cpp = min(nv, GM_RO_NT), RS = GM_RO_NT / cpp;      // column vectors per row; of them per pass; row slots
+    const int tid = threadIdx.x, slot = tid / cpp, cl = tid - slot * cpp;
+    const bool single = ns <= GM_RO_ROWS;
+    float* out = single ? P + (int64_t)ch.z * Hd : part + (int64_t)blockIdx.x * Hd;
+    const float* base = H + (int64_t)ch.x * Hd;
+    for (int c0 = 0; c0 < nv; c0 += cpp) {
+        const int c = c0 + cl;
+        Vec acc = Vec::zero();
+        if (slot < RS && c < nv) {
+            const float* p = base + c * V;
+            int r = slot;
+            for (; r + 3 * RS < nr; r += 4 * RS) {      // four loads in flight, added in row order
+                const Vec a0 = Vec::load(p + (int64_t)r * Hd), a1 = Vec::load(p + (int64_t)(r + RS) * Hd), a2 = Vec::load(p + (int64_t)(r + 2 * RS) * Hd),
+                          a3 = Vec::load(p + (int64_t)(r + 3 * RS) * Hd);
+                acc.add(a0); acc.add(a1); acc.add(a2); acc.add(a3);
+            }
+            for (; r < nr; r += RS) acc.add(Vec::load(p + (int64_t)r * Hd));
+        }
+        acc.store(sm + tid * V);
+        __syncthreads();
+        if (slot == 0 && c < nv) {
+            Vec t = Vec::load(sm + cl * V);
+            for (int j = 1; j < RS; ++j) t.add(Vec::load(sm + (j * cpp + cl) * V));
+            if (single) t.div((float)ns);
+            t.store(out + c * V);
+        }
+        __syncthreads();
+    }
+}
+// multi[m] = {subgraph, first chunk, chunks, rows}: the partials of a subgraph of more than one chunk, in chunk order
+__global__ __launch_bounds__(GM_RO_NT) void k_readout_mean_fin(const float* __restrict__ part, int Hd, const int4* __restrict__ multi, float* __restrict__ P) {
+    const int4 m = multi[blockIdx.x];
+    const float* p = part + (int64_t)m.y * Hd;
+    for (int col = threadIdx.x; col < Hd; col += GM_RO_NT) {
+        float t = p[col];
+        for (int k = 1; k < m.z; ++k) t += p[(int64_t)k * Hd + col];
+        P[(int64_t)m.x * Hd + col] = t / (float)m.w;
+    }
+}
+// Every row of dQ is written (nothing zero-fills it first)
+template <int V>
+__global__ __launch_bounds__(GM_RO_NT) void k_readout_mean_bwd(const float* __restrict__ H, const float* __restrict__ G, int Hd, const int4* __restrict__ chunks,
+                                                               float* __restrict__ dQ) {
+    typedef RoVec<V> Vec;
+    const int4 ch = chunks[blockIdx.x];
+    const int nr = ch.y;
+    const int nv = Hd / V, cpp = min(nv, GM_RO_NT), RS = GM_RO_NT / cpp;
+    const int tid = threadIdx.x, slot = tid / cpp, cl = tid - slot * cpp;
+    if (slot >= RS) return;
+    for (int c = cl; c < nv; c += cpp) {
+        Vec g = Vec::load(G + (int64_t)ch.z * Hd + c * V);
+        g.div((float)ch.w);
+        const int64_t off = (int64_t)ch.x * Hd + c * V;
+        int r = slot;
+        for (; r + 3 * RS < nr; r += 4 * RS) {
+            const Vec a0 = Vec::load(H + off + (int64_t)r * Hd), a1 = Vec::load(H + off + (int64_t)(r + RS) * Hd), a2 = Vec::load(H + off + (int64_t)(r + 2 * RS) * Hd),
+                      a3 = Vec::load(H + off + (int64_t)(r + 3 * RS) * Hd);
+            a0.where_pos(g).store(dQ + off + (int64_t)r * Hd); a1.where_pos(g).store(dQ + off + (int64_t)(r + RS) * Hd);
+            a2.where_pos(g).store(dQ + off + (int64_t)(r + 2 * RS) * Hd); a3.where_pos(g).store(dQ + off + (int64_t)(r + 3 * RS) * Hd);
+        }
+        for (; r < nr; r += RS) Vec::load(H + off + (int64_t)r * Hd).where_pos(g).store(dQ + off + (int64_t)r * Hd);
+    }
+}
+
+static int64_t readout_chunk_count(const gm_batch* b) {
+    int64_t n = 0;
+    for (int s = 0; s < b->subs; ++s) n += (b->h_sub_off[s + 1] - b->h_sub_off[s] + GM_RO_ROWS - 1) / GM_RO_ROWS;
+    return n;
+}
+// The chunk tables of a batch, built at its first call under the mode (on s, ordered behind the batch's build) and kept in its slabs, like gm_batch_gains
+static int readout_tables(const gm_batch* cb, hipStream_t s) {
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    gm_batch* b = const_cast<gm_batch*>(cb);
+    if (b->d_ro_chunks) {
+        // built by an earlier call: a caller on another stream is ordered behind that call's upload (no event: the upload was synchronised)
+        if (s != b->ro_stream && b->ro_ev) GM_HIP(hipStreamWaitEvent(s, b->ro_ev, 0));
+        return GM_OK;
+    }
+    std::vector<int32_t> tab, multi;
+    for (int sg = 0; sg < b->subs; ++sg) {
+        const int r0 = b->h_sub_off[sg], ns = b->h_sub_off[sg + 1] - r0, first = (int)(tab.size() / 4);
+        GM_REQUIRE(ns >= 1, GM_EINVAL, "mean readout: subgraph %d has no rows", sg);
+        for (int r = 0; r < ns; r += GM_RO_ROWS) { const int32_t e[4] = {r0 + r, std::min(GM_RO_ROWS, ns - r), sg, ns}; tab.insert(tab.end(), e, e + 4); }
+        if (ns > GM_RO_ROWS) { const int32_t e[4] = {sg, first, (int)(tab.size() / 4) - first, ns}; multi.insert(multi.end(), e, e + 4); }
+    }
+    const int32_t n_chunks = (int32_t)(tab.size() / 4), n_multi = (int32_t)(multi.size() / 4);
+    tab.insert(tab.end(), multi.begin(), multi.end());
+    int32_t* d = nullptr;
+    GM_TRY(gm_balloc(b, &d, tab.size() + 4, b->stream));                                   // (the batch's slabs: freed with it, on its own stream)
+    if (s != b->stream) { hipEvent_t e; GM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); GM_HIP(hipEventRecord(e, b->stream)); GM_HIP(hipStreamWaitEvent(s, e, 0)); GM_HIP(hipEventDestroy(e)); }
+    { gm_stager stg(s); GM_TRY(stg.upload(d, tab)); }
+    // later callers may come on other streams (two threads sharing the batch; the query streams of a step wait for st anyway): an event behind the upload
+    // for them to wait on -- where none can be made, the upload is finished before anybody learns of the tables
+    if (hipEventCreateWithFlags(&b->ro_ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(b->ro_ev, s) != hipSuccess) {
+        (void)hipGetLastError();
+        if (b->ro_ev) { (void)hipEventDestroy(b->ro_ev); b->ro_ev = nullptr; }
+        GM_HIP(hipStreamSynchronize(s));
+    }
+    b->ro_stream = s;
+    b->n_ro_chunks = n_chunks; b->n_ro_multi = n_multi; b->d_ro_multi = d + 4 * (size_t)n_chunks; b->d_ro_chunks = d;
+    gm_batch_mark_use(b, s);
+    return GM_OK;
+}
+static bool readout_vec_ok(const GcnCtx& c, const float* a, const float* b2, const float* c2) {
+    return c.L.dims[c.L.n_gcn] % 4 == 0 && (((uintptr_t)a | (uintptr_t)b2 | (uintptr_t)c2) & 15) == 0;
+}
+static int readout_fwd(const GcnCtx& c, hipStream_t st) {
+    const gm_batch* b = c.b; const int Hd = c.L.dims[c.L.n_gcn];
+    if (b->n_ro_chunks == 0) return GM_OK;
+    GM_REQUIRE(b->d_ro_chunks && c.Pool && c.ro_part, GM_EINVAL, "mean readout: the batch's chunk tables or the pooled buffers are missing");
+    const float* H = c.H[c.L.n_gcn - 1];
+    const int4* chunks = reinterpret_cast<const int4*>(b->d_ro_chunks);
+    gm_prof_begin(GM_PROF_READOUT, st, 4 * (int64_t)b->rows * Hd + 4 * (int64_t)b->subs * Hd);
+    if (readout_vec_ok(c, H, c.Pool, c.ro_part)) hipLaunchKernelGGL(k_readout_mean<4>, dim3(b->n_ro_chunks), dim3(GM_RO_NT), 0, st, H, Hd, chunks, c.Pool, c.ro_part);
+    else hipLaunchKernelGGL(k_readout_mean<1>, dim3(b->n_ro_chunks), dim3(GM_RO_NT), 0, st, H, Hd, chunks, c.Pool, c.ro_part);
+    if (b->n_ro_multi > 0)
+        hipLaunchKernelGGL(k_readout_mean_fin, dim3(b->n_ro_multi), dim3(GM_RO_NT), 0, st, (const float*)c.ro_part, Hd, reinterpret_cast<const int4*>(b->d_ro_multi), c.Pool);
+    gm_prof_end(GM_PROF_READOUT, st);
+    GM_HIP(hipGetLastError());
+    return GM_OK;
+}
+// dQ_L (c.bufA, every row) from G (c.Gpool, written by the head's backward) and H_L
+static int readout_bwd(const GcnCtx& c, hipStream_t st) {
+    const gm_batch* b = c.b; const int Hd = c.L.dims[c.L.n_gcn];
+    if (b->n_ro_chunks == 0) return GM_OK;
+    GM_REQUIRE(b->d_ro_chunks && c.Gpool, GM_EINVAL, "mean readout: the batch's chunk tables or the pooled buffers are missing");
+    const float* H = c.H[c.L.n_gcn - 1];
+    const int4* chunks = reinterpret_cast<const int4*>(b->d_ro_chunks);
+    gm_prof_begin(GM_PROF_READOUT_BWD, st, 8 * (int64_t)b->rows * Hd + 4 * (int64_t)b->subs * Hd);
+    if (readout_vec_ok(c, H, c.Gpool, c.bufA)) hipLaunchKernelGGL(k_readout_mean_bwd<4>, dim3(b->n_ro_chunks), dim3(GM_RO_NT), 0, st, H, (const float*)c.Gpool, Hd, chunks, c.bufA);
+    else hipLaunchKernelGGL(k_readout_mean_bwd<1>, dim3(b->n_ro_chunks), dim3(GM_RO_NT), 0, st, H, (const float*)c.Gpool, Hd, chunks, c.bufA);
+    gm_prof_end(GM_PROF_READOUT_BWD, st);
     GM_HIP(hipGetLastError());
     return GM_OK;
 }

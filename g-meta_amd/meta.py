@@ -206,7 +206,8 @@ class Meta(nn.Module):
         if dev.type != 'cuda':
             raise RuntimeError('Meta parameters must live on the GPU (call .to("cuda")); there is no CPU fallback')
         model = self.net.model
-        P = int(lib.gm_model_param_count(C.byref(model)))
+        with _lib.readout_switch(self.net.readout):
+            P = int(lib.gm_model_param_count(C.byref(model)))
         if len(x_spt) == 0:               # an empty task shard (more ranks than tasks in a trailing meta-batch): contributes zeros
             return torch.zeros(P + 2 * (K + 1) + 2, dtype=torch.float32, device=dev), P, 0
         for b in x_spt:
@@ -231,8 +232,9 @@ class Meta(nn.Module):
         # objects are recycled; a dead or different partner recomputes) -- two FFI calls (one of them a full planning pass) less on the host
         # path between the read-back of one step and the first launch of the next
         key = (S.rows, Q.rows, S.subs, Q.subs, S.sets, Q.sets, P, int(K), int(need_grad), int(self.hoist_z1), int(self.serialize), int(self.sparse_bwd),
-               int(self.cone), int(lib.gm_get_gemm_mode()), int(lib.gm_get_split_pieces()), int(lib.gm_tuning_epoch()), int(self.ragged))
-        was = _set_ragged(lib, self.ragged)                   # the calling thread's switch: the sizes and the step below depend on it
+               int(self.cone), int(lib.gm_get_gemm_mode()), int(lib.gm_get_split_pieces()), int(lib.gm_tuning_epoch()), int(self.ragged), self.net.readout)
+        was = _set_ragged(lib, self.ragged)                   # the calling thread's switches: the sizes and the step below depend on them
+        ro = _lib.readout_switch(self.net.readout).__enter__()
         try:
             sizes = getattr(S, '_meta_sizes', None)
             if sizes is None or sizes[0] != key or sizes[1]() is not Q:
@@ -248,6 +250,7 @@ class Meta(nn.Module):
             _lib.check(lib.gm_meta_step(S.handle, Q.handle, _lib.ptr(ys), _lib.ptr(yq), C.byref(model), C.byref(hp), _lib.ptr(theta),
                                         _lib.ptr(out), out.numel(), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), 'gm_meta_step')
         finally:
+            ro.__exit__()
             _set_ragged(lib, was)
         self._keep = (S, Q)             # keep concatenated batches alive until the stream has consumed them
         return out, P, T
@@ -404,10 +407,11 @@ class Meta(nn.Module):
         classes = [np.unique(ys[int(off[t]):int(off[t + 1])]) for t in range(S.sets)]
         c_task = max(len(c) for c in classes)
         model = self.net.model
-        P = int(lib.gm_model_param_count(C.byref(model)))
         hp = _lib.HParams(float(self.update_lr), K, int(self.k_spt), 0, int(self.hoist_z1), int(self.serialize), int(self.sparse_bwd), int(self.cone))
         was = _set_ragged(lib, self.ragged)
+        ro = _lib.readout_switch(self.net.readout).__enter__()
         try:
+            P = int(lib.gm_model_param_count(C.byref(model)))
             ws_bytes = int(lib.gm_adapt_ws_bytes(S.handle, C.byref(model), C.byref(hp)))
             if ws_bytes < 0:
                 _lib.check(-1, 'gm_adapt_ws_bytes')
@@ -417,6 +421,7 @@ class Meta(nn.Module):
             _lib.check(lib.gm_meta_adapt(S.handle, _lib.ptr(ys), C.byref(model), C.byref(hp), _lib.ptr(theta), _lib.ptr(fw), P, _lib.ptr(protos), int(c_task),
                                          _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), 'gm_meta_adapt')
         finally:
+            ro.__exit__()
             _set_ragged(lib, was)
         return Adapted(self, S.store, fw, protos, classes, K)
 
@@ -581,13 +586,14 @@ class Adapted:
         logp = torch.empty(Q.subs, c_task, dtype=torch.float32, device=dev)
         pred = torch.empty(Q.subs, dtype=torch.int32, device=dev)
         lg = torch.empty(Q.subs, n_out, dtype=torch.float32, device=dev) if logits else None
-        ws_bytes = int(lib.gm_predict_ws_bytes(Q.handle, C.byref(model), C.byref(hp)))
-        if ws_bytes < 0:
-            _lib.check(-1, 'gm_predict_ws_bytes')
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _lib.check(lib.gm_proto_predict(Q.handle, C.byref(model), C.byref(hp), _lib.ptr(params), params.shape[1], _lib.ptr(protos), _lib.ptr(ncls),
-                                        int(c_task), _lib.ptr(lg), _lib.ptr(logp), _lib.ptr(pred), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
-                   'gm_proto_predict')
+        with _lib.readout_switch(self._meta.net.readout):
+            ws_bytes = int(lib.gm_predict_ws_bytes(Q.handle, C.byref(model), C.byref(hp)))
+            if ws_bytes < 0:
+                _lib.check(-1, 'gm_predict_ws_bytes')
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.gm_proto_predict(Q.handle, C.byref(model), C.byref(hp), _lib.ptr(params), params.shape[1], _lib.ptr(protos), _lib.ptr(ncls),
+                                            int(c_task), _lib.ptr(lg), _lib.ptr(logp), _lib.ptr(pred), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                       'gm_proto_predict')
         off = Q.set_sub_off
         logp_h, pred_h = logp.cpu().numpy(), pred.cpu().numpy().astype(np.int64)
         lg_h = lg.cpu().numpy() if logits else None

@@ -302,6 +302,27 @@ int gm_proto_loss_qry(const gm_batch_t* b, const float* logits, int32_t n_out, c
 void gm_set_ragged_classes(int32_t on);     /* 1 / 0: ragged-task mode of the calling thread (above); workspace sizes depend on it */
 int32_t gm_get_ragged_classes(void);
 
+/* READOUT, gm_set_readout(mode): GM_READOUT_CENTRE (0, default: the head reads the centre row(s) of every subgraph, learner.py:159-170) or
+ * GM_READOUT_MEAN (1: the alternative the reference left commented out, `#h = dgl.mean_nodes(g, 'h')`, learner.py:160); per calling thread, like
+ * gm_set_ragged_classes and gm_set_hop_labels; any other value leaves the mode unchanged and sets gm_last_error.  Read at call time wherever a
+ * gm_model_t is interpreted: gm_model_param_count, every *_ws_bytes, gm_meta_out_floats, gm_gcn_forward / _backward, gm_meta_step, gm_meta_adapt,
+ * gm_proto_predict (call the size queries and the call they size under the same mode).  Under MEAN, per subgraph s with rows
+ * [sub_off[s], sub_off[s+1]), n_s >= 1 of them, and H_L the (post-relu) output of the last GraphConv:
+ *   forward   p_s = (sum_r H_L[r, :]) / n_s in fp32, in ONE fixed order that depends only on n_s and the model's width (rows in chunks of 64, a
+ *             chunk's rows in a fixed strided order, the chunks of a subgraph in ascending order; no float atomics): two runs from the same state
+ *             are bitwise identical;  logits_s = F.linear(p_s, W_lin, b_lin) with W_lin [n_out, dims[n_gcn]] -- for pair batches too: one pooled
+ *             vector, no cat, so the parameter vector is n_out * dims[n_gcn] floats shorter than the pair model's under CENTRE;
+ *   backward  dQ_L[r, :] = H_L[r, :] > 0 ? (dlogits_s W_lin) / n_s : 0 for EVERY row r of s;
+ *   centre_local / the batch's centres are accepted and not used; pooling is topological and unweighted (edge weights and hop labels change H_L,
+ *   not the pooling); ragged-task mode composes unchanged;
+ *   schedules: hoist_z1 is honoured; sparse_bwd and cone are ignored (every row reaches the head: the dense schedule runs, same floats);
+ *   gm_set_split_pieces(2) is ignored (three pieces, violation word 0).
+ * With the mode off every call runs the kernels and launches it ran before the mode existed. */
+#define GM_READOUT_CENTRE 0
+#define GM_READOUT_MEAN 1
+void gm_set_readout(int32_t mode);
+int32_t gm_get_readout(void);
+
 /* ---- The fused hot path: Meta.forward_ProtoMAML (meta.py:101-173) when need_meta_grad = 1,
  * Meta.finetunning_ProtoMAML (meta.py:175-234) when 0, for ALL sets (tasks) of spt/qry at once.
  * spt and qry must have the same number of sets; set t of each is task t.  y_spt / y_qry: HOST
@@ -401,7 +422,8 @@ int gm_profile_aggregate(double* total_ms, int64_t* launches, int64_t* algorithm
  * 12 = work-only: bytes by which the rounds-2/3 pricing of the partial aggregate launches (sources = min(edges, rows)) exceeds the exact count.
  * 11 = work-only shadow of categories 4 + 6: compulsory HBM bytes of the split GEMM launches, 4 rows (K + N) (A read once, C written once).
  * 13 / 14 = work-only: compulsory HBM bytes of EVERY grouped GEMM launch (A read once + the C rows stored) / of every weight-gradient launch
- * (A and G read once); 15 = the head + prototypical-loss launches (k_head_loss; work = subgraphs).  Under the receptive-field schedule
+ * (A and G read once); 15 = the head + prototypical-loss launches (k_head_loss; work = subgraphs); 16 / 17 = the mean readout's forward
+ * (k_readout_mean, k_readout_mean_fin) / backward (k_readout_mean_bwd) launches, work = algorithmic bytes 4 rows H + 4 subs H / 8 rows H + 4 subs H.  Under the receptive-field schedule
  * (gm_hparams_t.cone) category 0 is priced on the rows each level-to-level aggregate touches: destination-level row bounds and norms, the
  * edges between the two levels, every source-level row read once, every destination row written once. */
 int gm_profile_read(int32_t category, double* total_ms, int64_t* launches, int64_t* work);

@@ -59,6 +59,9 @@ def parse(argv=None):
     ap.add_argument('--hop_labels', type=int, default=0,
                     help='D in 1..7: append one-hot hop-distance labels (distance to the centre, to both endpoints of a pair; capped at D) to the '
                          'features of every subgraph; 0 = off')
+    ap.add_argument('--readout', default='centre', choices=['centre', 'mean'],
+                    help="what the head reads of every subgraph: 'centre' = the centre row (both endpoints' rows of a pair), as the reference; 'mean' = the mean "
+                         "over all of its rows (the dgl.mean_nodes line the reference left commented out), one pooled vector for pairs too")
     ap.add_argument('--eval_tasks', type=int, default=100, help='validation / test tasks (the reference hard-codes 100, train.py:90-91)')
     # schedules of the MI355X build that return the same results faster (include/gmeta_hip.h, gm_hparams_t); 0 = as the reference computes
     ap.add_argument('--hoist_z1', type=int, default=0, help='1: aggregate the layer-1 input once per meta-step instead of in every forward')
@@ -89,6 +92,8 @@ def main(args):
     if args.h > 1:
         config = config + [('GraphConv', [args.hidden_dim, args.hidden_dim])] * (args.h - 1)
     config = config + [('Linear', [args.hidden_dim, labels_num])]
+    if args.readout != 'centre':
+        config.append(('Readout', [args.readout]))
     if args.link_pred_mode == 'True':
         config.append(('LinkPred', [True]))
     store = gmeta_amd.GraphStore(graphs, feat)
