@@ -7,7 +7,7 @@ LIB_PATH = os.environ.get('GMETA_HIP_LIB') or os.path.join(HERE, 'libgmeta_hip.s
 
 GM_MAX_GCN = 4
 (F_SUB_OFF, F_SET_SUB_OFF, F_PARENT, F_GRAPH, F_INDPTR, F_INDICES, F_INDPTR_T, F_INDICES_T, F_CENTRE, F_NORM,
- F_FEAT_ROW, F_NORM_SRC, F_NORM_CENTRE, F_EDGE_W, F_EDGE_W_T, F_HOP) = range(16)
+ F_FEAT_ROW, F_NORM_SRC, F_NORM_CENTRE, F_EDGE_W, F_EDGE_W_T, F_HOP, F_NORM_E1, F_EDGE_CENTRE_T) = range(18)
 LINK_SYMMETRIC = 2      # GM_LINK_SYMMETRIC: the link_pred mode of gm_extract / gm_extract_pair with h hops around both endpoints
 
 
@@ -49,6 +49,7 @@ PROTOTYPES = {
     'gm_batch_read': (C.c_int, [vp, i32, vp, i64]),
     'gm_batch_device_ptr': (C.c_int, [vp, i32, vp]),
     'gm_batch_source_rows': (C.c_int, [vp, vp]),
+    'gm_batch_e1_source_rows': (C.c_int, [vp, vp]),
     'gm_gather_features': (C.c_int, [vp, vp, vp]),
     'gm_aggregate': (C.c_int, [vp, i32, i32, vp, i32, vp, vp, vp, vp]),
     'gm_aggregate_bytes': (i64, [vp, i32]),
@@ -60,6 +61,8 @@ PROTOTYPES = {
     'gm_dense_gemm': (C.c_int, [vp, vp, i64, i32, vp, i64, i32, i32, vp, i64, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i32, vp, vp]),
     'gm_dense_dz_centre': (C.c_int, [vp, vp, i32, vp, i64, i32, vp, vp]),
     'gm_dense_wgrad_centre': (C.c_int, [vp, vp, i32, vp, i32, vp, i64, vp, i64, vp]),
+    'gm_dense_agg_centre_t': (C.c_int, [vp, vp, i32, vp, vp, i32, vp]),
+    'gm_dense_wgrad_e1': (C.c_int, [vp, vp, i32, vp, i32, vp, i64, vp, i64, vp]),
     'gm_dense_wgrad': (C.c_int, [vp, vp, i64, i32, vp, i64, i32, vp, vp, i64, vp, i64, vp, i64, i32, vp, vp, i64, C.c_float, vp, vp, vp, vp]),
     'gm_proto_loss_spt': (C.c_int, [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     'gm_proto_loss_qry': (C.c_int, [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),

@@ -28,7 +28,17 @@ struct AggK {
     const float* e_w; const int32_t* x_idx;     // per-edge source scale / source row of x (see gm_agg_args)
     int skip_lo, skip_hi;                       // rows with skip_lo <= degree <= skip_hi are left to the fused aggregate+GEMM kernel (empty range: none)
     const int32_t* rowlist; int64_t n_list;     // optional: the windows walk this (ascending) row list instead of rows 0 .. rows
+    int keep_signed;                            // s_out's sign bit = nobody reads this row of `out`: computed, not stored; the scale is the magnitude.  Never read without the flag
 };
+// the row's output scale and whether the row is stored
+__device__ __forceinline__ float agg_out_scale(const AggK& a, const int64_t row, bool& keep) {
+    keep = true;
+    if (!a.s_out) return 1.f;
+    const float so = a.s_out[row];
+    if (!a.keep_signed) return so;
+    keep = !(__float_as_uint(so) >> 31);
+    return fabsf(so);
+}
 
 // edge e -> (row of x to read, its scale): from the per-edge tables when the launch has them, else through indices / s_in / x_row
 __device__ __forceinline__ void agg_edge(const AggK& a, const int e, int& u, float& w) {
@@ -67,7 +77,8 @@ __global__ __launch_bounds__(AGG_BLOCK) void k_agg(AggK a) {
     const int64_t row = (int64_t)lb * RPB + wave * RPW + sub;
     if (row >= a.rows) return;
     const int e0 = a.indptr[row], e1 = a.indptr[row + 1];
-    const float so = a.s_out ? a.s_out[row] : 1.0f;
+    bool keep;
+    const float so = agg_out_scale(a, row, keep);
     int set = 0;
     if (a.bias && a.bias_stride) {                      // set of this row (few sets: short binary search)
         int lo = 0, hi = a.n_sets;
@@ -107,7 +118,7 @@ __global__ __launch_bounds__(AGG_BLOCK) void k_agg(AggK a) {
             for (int k = 0; k < VEC; ++k) bits |= (vget(res, k) > 0.f ? 1u : 0u) << k;
             a.relu_bits[(row * a.width + c0) >> 2] = (uint8_t)bits;
         }
-        *reinterpret_cast<V*>(a.out + row * a.width + c0) = res;
+        if (keep) *reinterpret_cast<V*>(a.out + row * a.width + c0) = res;
     }
 }
 
@@ -139,9 +150,11 @@ __device__ __forceinline__ void agg_heavy_row(const AggK& a, const int g, float*
             float4 v[8][NCH]; float ww[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const int sl = gbase + j + i;
+                // slots past the end re-read the LAST edge's row with weight 0: a row some edge reads is one its producer stored (x may hold unwritten rows -- H_l at
+                // rows without an out-edge, T_L outside the centre rows -- and 0 x whatever such a row holds need not be 0)
+                const int sl = gbase + min(j + i, cnt - 1);
                 const int uu = __shfl(mu, sl, 64);
-                ww[i] = (j + i < cnt) ? __shfl(mw, sl, 64) : 0.f;
+                ww[i] = (j + i < cnt) ? __shfl(mw, gbase + j + i, 64) : 0.f;
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) v[i][c] = *reinterpret_cast<const float4*>(xl + (int64_t)uu * a.ldx + c * LPR * 4);
             }
@@ -200,7 +213,8 @@ __device__ __forceinline__ void agg_heavy_row(const AggK& a, const int g, float*
         }
     }
     if (gi != 0) return;
-    const float so = a.s_out ? a.s_out[row] : 1.f;
+    bool keep;
+    const float so = agg_out_scale(a, row, keep);
     const float* bp = nullptr;
     if (a.bias) {
         int set = 0;
@@ -224,7 +238,7 @@ __device__ __forceinline__ void agg_heavy_row(const AggK& a, const int g, float*
             v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
         }
         if (a.relu_bits) a.relu_bits[((int64_t)row * a.width + l * 4 + c * LPR * 4) >> 2] = (uint8_t)((v.x > 0.f) | ((v.y > 0.f) << 1) | ((v.z > 0.f) << 2) | ((v.w > 0.f) << 3));
-        *reinterpret_cast<float4*>(a.out + (int64_t)row * a.width + l * 4 + c * LPR * 4) = v;
+        if (keep) *reinterpret_cast<float4*>(a.out + (int64_t)row * a.width + l * 4 + c * LPR * 4) = v;
     }
 }
 template <int LPR, int NCH>
@@ -321,9 +335,9 @@ __global__ __launch_bounds__(AGG_BLOCK) void k_agg_win(AggK a) {
                     float4 v[MB][NCH]; float ww[MB];
 #pragma unroll
                     for (int i = 0; i < MB; ++i) {
-                        const int sl = g * LPR + ((j + i) & (LPR - 1));
+                        const int sl = g * LPR + min((j + i) & (LPR - 1), cnt - 1);      // out-of-range slots re-read the last edge's row (a row its producer stored) with weight 0
                         const int uu = __shfl(mu, sl, 64);
-                        ww[i] = (j + i < cnt) ? __shfl(mw, sl, 64) : 0.f;      // out-of-range slots re-read a valid row with weight 0
+                        ww[i] = (j + i < cnt) ? __shfl(mw, g * LPR + ((j + i) & (LPR - 1)), 64) : 0.f;
 #pragma unroll
                         for (int c = 0; c < NCH; ++c) v[i][c] = *reinterpret_cast<const float4*>(xl + (int64_t)uu * a.ldx + c * LPR * 4);
                     }
@@ -345,7 +359,7 @@ __global__ __launch_bounds__(AGG_BLOCK) void k_agg_win(AggK a) {
             }
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
-                const float s_ = rso[k];
+                const float s_ = a.keep_signed ? fabsf(rso[k]) : rso[k];
                 float4 v = make_float4(acc[k][c].x * s_, acc[k][c].y * s_, acc[k][c].z * s_, acc[k][c].w * s_);
                 if (bp) { const float4 bb = *reinterpret_cast<const float4*>(bp + c * LPR * 4); v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w; }
                 if (a.relu) { v.x = v.x < 0.f ? 0.f : v.x; v.y = v.y < 0.f ? 0.f : v.y; v.z = v.z < 0.f ? 0.f : v.z; v.w = v.w < 0.f ? 0.f : v.w; }
@@ -358,7 +372,8 @@ __global__ __launch_bounds__(AGG_BLOCK) void k_agg_win(AggK a) {
                 }
                 if (a.relu_bits) a.relu_bits[(row * a.width + l * 4 + c * LPR * 4) >> 2] = (uint8_t)((v.x > 0.f) | ((v.y > 0.f) << 1) | ((v.z > 0.f) << 2) | ((v.w > 0.f) << 3));
                 float4* dst = reinterpret_cast<float4*>(a.out + row * a.width + l * 4 + c * LPR * 4);
-                if (a.nt) {
+                if (a.keep_signed && (__float_as_uint(rso[k]) >> 31)) {      // nobody reads this row: computed, not stored
+                } else if (a.nt) {
                     typedef float f4v __attribute__((ext_vector_type(4)));
                     f4v vv = {v.x, v.y, v.z, v.w};
                     __builtin_nontemporal_store(vv, reinterpret_cast<f4v*>(dst));
@@ -492,7 +507,7 @@ int gm_launch_aggregate(const gm_agg_args& g, hipStream_t s) {
            g.set_row_off, g.n_sets, g.relu, g.out, g.rows, g.width, 0, g.mask_b, g.relu_bits, g.heavy, g.n_heavy, g.heavy_deg,
            g.sched, g.sched_len, agg_nt(g.rows, g.width), g.sched ? g.sched_win : 64,
            g.sched ? g.hub : nullptr, g.sched ? g.hub_scratch : nullptr, g.hub_part, GM_AGG_HUB_LD, g.e_w, g.x_idx, g.skip_on ? g.skip_lo : 1, g.skip_on ? g.skip_hi : 0,
-           g.rowlist, g.n_list};
+           g.rowlist, g.n_list, (g.keep_signed && g.s_out) ? 1 : 0};
     if (g.rowlist) a.win = g.list_win;
     const bool vec4 = (g.width % 4 == 0) && (g.ldx % 4 == 0) && (((uintptr_t)g.x & 15) == 0) && (((uintptr_t)g.out & 15) == 0);
     const bool bias_ok = !g.bias || ((((uintptr_t)g.bias & 15) == 0) && (g.bias_stride % 4 == 0));

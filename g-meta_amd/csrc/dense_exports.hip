@@ -117,15 +117,15 @@ extern "C" int gm_dense_dz_centre(const gm_batch_t* b, const float* dQ, int32_t 
     gm_batch_mark_use(b, st);
     return rc;
 }
-// ... and its weight gradient
-extern "C" int gm_dense_wgrad_centre(const gm_batch_t* b, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
-                                     int64_t db_stride, void* stream) {
-    GM_REQUIRE(b && x && dQ && dW && db && b->d_norm_c, GM_EINVAL, "dense_wgrad_centre: bad arguments");
+// ... and its weight gradient (keep: the flagged row scale that says which rows of dQ were written)
+static int dense_wgrad_keep(const gm_batch_t* b, const float* keep, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
+                            int64_t db_stride, void* stream) {
+    GM_REQUIRE(b && x && dQ && dW && db && keep, GM_EINVAL, "dense_wgrad_centre / _e1: bad arguments");
     const int64_t KN = (int64_t)Kx * N;
-    GM_REQUIRE(b->sets == 1 || (dw_stride >= KN && db_stride >= N), GM_EINVAL, "dense_wgrad_centre: per-set outputs overlap");
+    GM_REQUIRE(b->sets == 1 || (dw_stride >= KN && db_stride >= N), GM_EINVAL, "dense_wgrad_centre / _e1: per-set outputs overlap");
     hipStream_t st = (hipStream_t)stream;
     gm_wgrad_args w{};
-    w.A = x; w.lda = Kx; w.K = Kx; w.G = dQ; w.ldg = N; w.N = N; w.a_scale = b->d_norm; w.g_keep = b->d_norm_c;
+    w.A = x; w.lda = Kx; w.K = Kx; w.G = dQ; w.ldg = N; w.N = N; w.a_scale = b->d_norm; w.g_keep = keep;
     w.chunks = b->d_chunks; w.n_chunks = b->n_chunks; w.set_chunk_off = b->d_set_chunk_off; w.sets = b->sets; w.rows = b->rows;
     w.dW = dW; w.dw_stride = dw_stride; w.db = db; w.db_stride = db_stride; w.pick = GM_WGRAD_PICK_SPLIT;
     int rc = gm_alloc(&w.partial, (size_t)std::max(1, b->n_chunks) * (size_t)(KN + N), st);
@@ -133,6 +133,38 @@ extern "C" int gm_dense_wgrad_centre(const gm_batch_t* b, const float* x, int32_
     if (w.partial) gm_dev_free(w.partial, st);
     gm_batch_mark_use(b, st);
     return rc;
+}
+extern "C" int gm_dense_wgrad_centre(const gm_batch_t* b, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
+                                     int64_t db_stride, void* stream) {
+    return dense_wgrad_keep(b, b ? b->d_norm_c : nullptr, x, Kx, dQ, N, dW, dw_stride, db, db_stride, stream);
+}
+
+// GM_DEAD_ROWS=2 (tests): the last layer's transposed aggregate dQ_prev = relu' norm A^T T as gcn_backward launches it.  keep != 0: T read through the batch's
+// per-edge table (gm_batch::d_ect; T holds rows + 1 rows, the last one zeroed HERE) and only the rows gm_batch::d_norm_e1 keeps stored; keep == 0: the plain
+// launch, every row of T read and every row of `out` stored.  mask_b: packed relu' bits [rows * width / 4], or NULL
+extern "C" int gm_dense_agg_centre_t(const gm_batch_t* b, float* T, int32_t width, const uint8_t* mask_b, float* out, int32_t keep, void* stream) {
+    GM_REQUIRE(b && T && out && width >= 4 && width % 4 == 0, GM_EINVAL, "dense_agg_centre_t: bad arguments");
+    GM_REQUIRE(!keep || (b->d_ect && b->d_norm_e1), GM_EINVAL, "dense_agg_centre_t: the batch carries no centre-edge tables");
+    hipStream_t st = (hipStream_t)stream;
+    gm_agg_args a{};
+    a.indptr = b->d_indptr_t; a.indices = b->d_indices_t;
+    a.heavy = b->d_heavy[1]; a.n_heavy = b->n_heavy[1]; a.heavy_deg = b->heavy_deg;
+    a.sched = b->d_sched[1]; a.sched_len = b->sched_len[1]; a.sched_win = b->sched_win;
+    GM_TRY(gm_agg_hub(a, b, 1, st));
+    if (b->weighted) a.e_w = b->d_ew[1];
+    a.rows = b->rows; a.x = T; a.ldx = width; a.s_out = b->d_norm; a.mask_b = mask_b; a.out = out; a.width = width;
+    if (keep) {
+        GM_HIP(hipMemsetAsync(T + b->rows * (int64_t)width, 0, sizeof(float) * GM_ZERO_ROWS * width, st));
+        a.x_idx = b->d_ect; a.s_out = b->d_norm_e1; a.keep_signed = 1;
+    }
+    const int rc = gm_launch_aggregate(a, st);
+    gm_batch_mark_use(b, st);
+    return rc;
+}
+// ... and the weight gradient of the layer below over that dQ_prev: rows gm_batch::d_norm_e1 flags enter as zeros, whatever their bytes hold
+extern "C" int gm_dense_wgrad_e1(const gm_batch_t* b, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
+                                 int64_t db_stride, void* stream) {
+    return dense_wgrad_keep(b, b ? b->d_norm_e1 : nullptr, x, Kx, dQ, N, dW, dw_stride, db, db_stride, stream);
 }
 
 // ================================================================================ weight gradient, exported for numerics tests

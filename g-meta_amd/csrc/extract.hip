@@ -782,6 +782,31 @@ __global__ void k_centre_edges(const int32_t* crow, const int32_t* eoff, int n_c
         if constexpr (sizeof...(WArgs) != 0) { const CentreW& cw = (w_args, ...); cw.e_coef[o + j] = cw.ew[p0 + j] * norm[u]; }
     }
 }
+// GM_DEAD_ROWS=2 tables (gm_batch::d_ect / d_norm_e1).  First pass: every row's norm with the sign bit set, and every by-source edge's row of T -- its destination
+// where that is a centre (sign bit of norm_c clear), else a row of the zero block behind T.  Second pass, over the centres' in-edges: the sign bit cleared on
+// their source rows; the first clear of a row counts it.
+__global__ void k_e1_tables(const int32_t* indices_t, int64_t edges, const float* norm, const float* norm_c, int64_t rows, int32_t* ect, float* norm_e1, int32_t* n_rows) {
+    const int64_t n = edges > rows ? edges : rows;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *n_rows = 0;
+    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        if (k < rows) norm_e1[k] = __uint_as_float(__float_as_uint(norm[k]) | 0x80000000u);
+        if (k < edges) { const int v = indices_t[k]; ect[k] = (__float_as_uint(norm_c[v]) >> 31) ? (int32_t)(rows + (k & (GM_ZERO_ROWS - 1))) : v; }
+    }
+}
+__global__ void k_e1_rows(const int32_t* e_row, int n_e1, float* norm_e1, int32_t* n_rows) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_e1) return;
+    const unsigned old = atomicAnd(reinterpret_cast<unsigned*>(norm_e1) + e_row[k], 0x7fffffffu);
+    if (old >> 31) atomicAdd(n_rows, 1);
+}
+int64_t gm_batch_e1_rows(const gm_batch* b, hipStream_t s) {
+    if (b->n_e1_rows >= 0) return b->n_e1_rows;
+    const int64_t fallback = std::min<int64_t>(b->n_e1, b->rows);
+    if (!b->d_n_e1_rows) return fallback;
+    int32_t h = 0;
+    if (hipMemcpyAsync(&h, b->d_n_e1_rows, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return fallback; }
+    return b->n_e1_rows = h;
+}
 __global__ void k_copy_add(int32_t* dst, const int32_t* src, int64_t n, int32_t add) {
     for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) dst[k] = src[k] + add;
 }
@@ -947,7 +972,7 @@ int gm_balloc_bytes(gm_batch* b, void** p, size_t bytes, hipStream_t s) {
         // slab size: what the big arrays of this batch will need in total when the sizes are known (rows / edges; measured on the arxiv query batch:
         // 139 MB at 1.14 M rows / 2.1 M edges), plus room for the level arrays of a two-layer receptive-field build (12 + 4 bytes per row, 8 per edge:
         // cone.hip) so that a batch is ONE block of the slab cache; else 8 MiB steps
-        const size_t guess = (size_t)b->rows * 74 + (size_t)b->edges * 27 + ((size_t)2 << 20) + (size_t)b->rows * 20 + (size_t)b->edges * 8 +
+        const size_t guess = (size_t)b->rows * 78 + (size_t)b->edges * 31 + ((size_t)2 << 20) + (size_t)b->rows * 20 + (size_t)b->edges * 8 +
                              (b->hop_D ? (size_t)b->rows * (4 * (size_t)gm_pad_feat(b->store->feat_dim + b->centres * (b->hop_D + 2)) + 8) : 0);      // (+ a labelled batch's own feature table)
         gm_batch::slab sl{nullptr, 0, 0};
         GM_TRY(gm_slab_acquire(&sl.base, &sl.cap, std::max(bytes, b->slabs.empty() ? guess : std::max<size_t>(guess / 4, (size_t)8 << 20)), s));
@@ -1209,6 +1234,13 @@ static int finalize_finish(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
     } else hipLaunchKernelGGL(k_centre_edges<>, dim3(b->n_c), dim3(64), 0, s, b->d_crow, d_eoff, b->n_c, b->d_indptr, b->d_indices, b->d_norm,
                        b->d_e1_row, b->d_e1_par, b->d_e1_norm);
     GM_HIP(hipGetLastError());
+    if (b->rows > 0 && b->d_norm_c) {
+        GM_TRY(gm_balloc(b, &b->d_ect, (size_t)b->edges, s)); GM_TRY(gm_balloc(b, &b->d_norm_e1, (size_t)b->rows, s)); GM_TRY(gm_balloc(b, &b->d_n_e1_rows, 1, s));
+        hipLaunchKernelGGL(k_e1_tables, dim3((int)std::min<int64_t>(4096, (std::max<int64_t>(b->edges, b->rows) + 255) / 256)), dim3(256), 0, s, b->d_indices_t, (int64_t)b->edges,
+                           b->d_norm, b->d_norm_c, (int64_t)b->rows, b->d_ect, b->d_norm_e1, b->d_n_e1_rows);
+        if (b->n_e1 > 0) hipLaunchKernelGGL(k_e1_rows, dim3((b->n_e1 + 255) / 256), dim3(256), 0, s, b->d_e1_row, b->n_e1, b->d_norm_e1, b->d_n_e1_rows);
+        GM_HIP(hipGetLastError());
+    }
     std::vector<int32_t> ct, cc, ccoff(b->sets + 1, 0), ec, ecoff(b->sets + 1, 0), c_set_off(b->sets + 1), e_set_off(b->sets + 1);
     for (int t = 0; t <= b->sets; ++t) { c_set_off[t] = b->h_set_sub_off[t] * nc; e_set_off[t] = eoff[b->h_set_sub_off[t] * nc]; }
     const int ccr = gm_wgrad_chunk_rows(c_set_off), ecr = gm_wgrad_chunk_rows(e_set_off);
@@ -1578,6 +1610,8 @@ static int field_ptr(const gm_batch_t* b, int32_t field, void** p, int64_t* byte
             *p = b->d_hop; *bytes = (int64_t)b->rows * b->centres; break;
         case GM_F_NORM_SRC: *p = b->d_norm_src; *bytes = 4ll * b->rows; break;
         case GM_F_NORM_CENTRE: *p = b->d_norm_c; *bytes = 4ll * b->rows; break;
+        case GM_F_NORM_E1: *p = b->d_norm_e1; *bytes = 4ll * b->rows; break;
+        case GM_F_EDGE_CENTRE_T: *p = b->d_ect; *bytes = 4ll * b->edges; break;
         case GM_F_EDGE_W: case GM_F_EDGE_W_T:
             GM_REQUIRE(b->weighted, GM_EINVAL, "batch field %s: the batch is unweighted (its store was created without edge weights)", field == GM_F_EDGE_W ? "GM_F_EDGE_W" : "GM_F_EDGE_W_T");
             *p = b->d_ew[field == GM_F_EDGE_W ? 0 : 1]; *bytes = 4ll * b->edges; break;
@@ -1602,6 +1636,12 @@ extern "C" int32_t gm_batch_weighted(const gm_batch_t* b) { return b && b->weigh
 extern "C" int gm_batch_source_rows(const gm_batch_t* b, int64_t* n_rows) {
     GM_REQUIRE(b && n_rows, GM_EINVAL, "batch_source_rows: NULL argument");
     *n_rows = b->n_src;
+    return GM_OK;
+}
+
+extern "C" int gm_batch_e1_source_rows(const gm_batch_t* b, int64_t* n_rows) {
+    GM_REQUIRE(b && n_rows, GM_EINVAL, "batch_e1_source_rows: NULL argument");
+    *n_rows = gm_batch_e1_rows(b, b->stream);
     return GM_OK;
 }
 

@@ -185,6 +185,14 @@ struct gm_batch {
     int32_t n_e1 = 0;                 // in-edges of centres, concatenated in centre order
     int32_t* d_e1_row = nullptr;       // [n_e1] source row of the edge
     int32_t* d_e1_par = nullptr;       // [n_e1] compact index of the centre it enters
+    // GM_DEAD_ROWS=2 (k_e1_tables / k_e1_rows, after k_centre_edges): one level below d_norm_c / d_dq_tab.  T = norm (dQ_L W_L^T) is zero outside the centre rows, and
+    // dQ_{L-1} = relu' norm A^T T outside the sources of the centres' in-edges
+    int32_t* d_ect = nullptr;          // [edges] source row of T for every edge of the by-source CSR: indices_t[e] where that row is a centre, else a row of the zero
+                                       //        block behind T (rows + (e & (GM_ZERO_ROWS - 1))): gm_agg_args::x_idx of the last layer's transposed aggregate
+    float* d_norm_e1 = nullptr;        // [rows] norm with the SIGN BIT SET on every row that is not the source of an in-edge of a centre (gm_agg_args::s_out + keep_signed of that
+                                       //        launch, gm_wgrad_args::g_keep of the weight gradient below it)
+    int32_t* d_n_e1_rows = nullptr;    // [1]    rows with the bit clear, counted on the device (gm_batch_e1_rows reads it at first use)
+    mutable int64_t n_e1_rows = -1;
     float* d_e1_norm = nullptr;        // [n_e1] norm[source row]
     float* d_e1_coef = nullptr;        // [n_e1] weighted batches only: edge weight x norm[source row] (the transposed aggregate's coefficient; d_e1_norm stays the row scale)
     int32_t* d_c_tiles = nullptr; int32_t n_c_tiles = 0;          // GEMM tiles over centre rows (per set)
@@ -222,7 +230,8 @@ struct gm_knobs {
     int gemm_mode;                 // 0 exact fp32, 1 split-bf16, -1 not set (library default)
     int gemm_split_min_tiles;      // -1: a quarter of the current device's CUs
     int centre_store;              // GM_CENTRE_STORE: the last layer's update stores only the centre rows of its activation -- in every pass (2, default), in the forward-only passes (1) -- or every row (0)
-    int dead_rows;                 // GM_DEAD_ROWS: rows no later kernel reads are computed and not stored / not zero-filled (1, default; off with GM_CENTRE_STORE=0 too): H_l below the last layer at rows without an out-edge, dQ_L outside the centre rows
+    int dead_rows;                 // GM_DEAD_ROWS: rows no later kernel reads are computed and not stored / not zero-filled (off with GM_CENTRE_STORE=0 too): H_l below the last layer at rows without an out-edge, dQ_L outside the centre rows (1);
+                                   // and, one level down the dense backward, T_L outside the centre rows and dQ_{L-1} outside the sources of the centres' in-edges (2, default)
     int fuse_agg, head_stage;
     int fuse_diff;                 // GM_FUSE_DIFF: the differentiated passes of the dense schedule take the fused aggregate + GEMM too, their weight gradients form Z's rows from the source table: 2 (default) everywhere except a support batch whose full launches take the stream aggregate, 1 everywhere, 0 never
     int agg_mid_win;               // GM_AGG_MID_WIN: rows per wave window over that list (0 = by its length)
@@ -319,6 +328,7 @@ struct gm_agg_args {
     int64_t ldx;
     const float* s_in;         // optional per-source scale
     const float* s_out;        // optional per-destination scale
+    int keep_signed;           // s_out carries "nobody reads this row of `out`" in its sign bit (gm_batch::d_norm_e1): the scale is the magnitude, a flagged row is computed and not stored
     const float* mask_h;       // optional [rows, width]: zero the output where mask_h <= 0 (relu')
     const uint8_t* mask_b;     // same mask, packed: byte (row*width + col)/4 holds the relu' bits of 4 consecutive columns
     uint8_t* relu_bits;        // optional output: packed relu' bits of `out` (written with relu; width % 4 == 0)
@@ -350,6 +360,9 @@ int gm_stream_tables(gm_batch* b, int o, const int32_t* hubs_host, const int32_t
 #define GM_FUSE_SELF 0x40000000   // gm_batch::d_fuse2 entry: the source is the row's own, already aggregated, row
 #define GM_FUSE_ZERO 0x20000000   // ... the row has no source: an all-zero row
 const float* gm_zero_row(hipStream_t s);   // 4096 zero floats on the current device (allocated once)
+#ifndef GM_ZERO_ROWS
+#define GM_ZERO_ROWS 1            // rows of the zero block behind the dense backward's T (a power of two; gm_batch::d_ect spreads the dead sources over them)
+#endif
 #define GM_FUSE_MAXDEG 2
 #define GM_AGG_HUB_LD 512      // floats per partial hub row (the widest window-kernel width)
 struct gm_agg_sched { int32_t* d_sched = nullptr; int32_t len = 0; int32_t* d_hub = nullptr; float* d_hub_scratch = nullptr; int32_t hub_part = 0; int32_t hub_words = 0, parts = 0;
@@ -533,6 +546,8 @@ bool gm_prof_enabled();
 // distinct source rows of the in-edges of the rows with more than GM_FUSE_MAXDEG sources (what a partial aggregate launch reads): counted on the
 // device at first use (a bitmap over the batch rows; synchronises the stream) -- only the launch accounting of bench.py asks for it
 int64_t gm_batch_unfused_sources(const gm_batch* b, hipStream_t s);
+// distinct source rows of the centres' in-edges (the rows gm_batch::d_norm_e1 keeps): read back at first use (synchronises the stream) -- the launch accounting and the tests ask for it
+int64_t gm_batch_e1_rows(const gm_batch* b, hipStream_t s);
 void gm_prof_note(int cat, int64_t work);      // adds work to a category without timing events
 static inline void gm_prof_agg_begin(hipStream_t s, int64_t bytes) { gm_prof_begin(GM_PROF_AGG, s, bytes); }
 static inline void gm_prof_agg_end(hipStream_t s) { gm_prof_end(GM_PROF_AGG, s); }

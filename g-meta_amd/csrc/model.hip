@@ -691,6 +691,7 @@ struct GcnCtx {
     // it with a memset launch; DQ_ZEROED: the last forward GEMM zero-filled it on its way out; DQ_CENTRE (GM_DEAD_ROWS): left alone -- the head/loss launch assigns its
     // centre rows and the two readers of dQ_L in the backward take every other row as zeros (dZ GEMM: gm_batch::d_dq_tab; weight gradient: gm_wgrad_args::g_keep)
     enum DqFill { DQ_MEMSET, DQ_ZEROED, DQ_CENTRE } dq = DQ_MEMSET;
+    bool t_zero = false;         // GM_DEAD_ROWS=2: this call zeroed the block behind T_L (t_zero_fill), the last layer's backward may read T_L through gm_batch::d_ect
     bool zfused[GM_MAX_GCN] = {};    // the last forward left Z[l] written at the rows of three or more sources only (fused aggregate + GEMM in a pass that IS
                                      // differentiated): the backward's weight gradient forms the other rows from the per-row source table (gm_wgrad_args::fuse2)
     float* Z[GM_MAX_GCN]; float* H[GM_MAX_GCN]; float* X0; float* bufA; float* bufB; float* partial;
@@ -804,7 +805,7 @@ static void gcn_carve(GcnCtx& c, Carver& cv) {
     }
     c.X0 = (L.dims[0] > L.dims[1]) ? cv.take<float>(rows * L.dims[0]) : nullptr;
     c.bufA = cv.take<float>(rows * maxd);
-    c.bufB = cv.take<float>(rows * maxd);
+    c.bufB = cv.take<float>((rows + GM_ZERO_ROWS) * maxd);      // T of the dense backward + the zero block behind T_L (t_zero_rows)
     c.partial = cv.take<float>((int64_t)c.b->n_chunks * maxkn);
     for (int l = 1; l < L.n_gcn; ++l) c.partial_l[l] = cv.take<float>((int64_t)c.b->n_chunks * (L.dims[l] + 1) * L.dims[l + 1]);
     for (int l = 1; l < L.n_gcn; ++l) c.WTl[l] = cv.take<float>((int64_t)c.b->sets * L.dims[l] * L.dims[l + 1]);
@@ -880,6 +881,22 @@ static bool dz_split_ok(const GcnCtx& c, int l) { return c.Wsplit && gm_gemm_spl
 // ... and on their fused loader, which reads a dQ_l that holds its centre rows only through the batch's table (DQ_CENTRE).  gcn_forward leaves dQ_L
 // unfilled, and gcn_backward reads it that way, by this one predicate
 static bool dz_centre_ok(const GcnCtx& c, int l) { return dz_split_ok(c, l) && c.L.dims[l + 1] >= 64 && c.L.dims[l + 1] <= 4096 && c.b->d_dq_tab; }
+// GM_DEAD_ROWS=2: the zero block behind T_L = rows [rows, rows + GM_ZERO_ROWS) of bufB at T_L's width -- where gm_batch::d_ect sends every edge whose destination is
+// not a centre.  NULL where there is none: one GCN layer, the cone schedule, or a layer below the last whose T is wider than T_L and would run over the block.
+// Zeroed once per call that owns the workspace (t_zero_fill, where the context's last dZ GEMM can take the table-read launch at all): no launch writes a row of
+// T past `rows`.  GcnCtx::t_zero says that this call filled it -- gcn_backward reads T_L through d_ect only then
+static float* t_zero_rows(const GcnCtx& c) {
+    const gm_layout& L = c.L; const int Lg = L.n_gcn;
+    if (c.cone || Lg < 2 || !c.bufB || L.dims[Lg - 1] > L.dims[Lg]) return nullptr;
+    for (int l = 0; l < Lg - 1; ++l) if (std::min(L.dims[l], L.dims[l + 1]) > L.dims[Lg - 1]) return nullptr;
+    return c.bufB + c.b->rows * (int64_t)L.dims[Lg - 1];
+}
+static int t_zero_fill(GcnCtx& c, hipStream_t st) {
+    float* z = t_zero_rows(c);
+    c.t_zero = z && gm_knob().dead_rows >= 2 && gm_knob().centre_store != 0 && dz_centre_ok(c, c.L.n_gcn - 1) && c.b->d_ect && c.b->d_norm_e1;
+    if (c.t_zero) GM_HIP(hipMemsetAsync(z, 0, sizeof(float) * GM_ZERO_ROWS * c.L.dims[c.L.n_gcn - 1], st));
+    return GM_OK;
+}
 
 int gm_gather_rows(const gm_batch* b, const int32_t* feat_row, int64_t n, int F, float* out, hipStream_t st);
 static int cone_forward(GcnCtx& c, const float* params, int64_t pstride, float* logits, hipStream_t st, int reuse_z1, int skip_head);
@@ -1028,6 +1045,17 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
     float* dQ = c.bufA; float* T = c.bufB;
     c.hold.n = 0;
     const bool dq_centre = skip_head && c.dq == GcnCtx::DQ_CENTRE;      // dQ_L holds its centre rows only (head_loss); without skip_head it is filled right here
+    // GM_DEAD_ROWS=2: the same rule one level down.  Every row of T_L = norm (dQ_L W_L^T) outside the centre rows is an exact zero, and so is every row of dQ_{L-1} =
+    // relu' norm A^T T_L that is not the source of an in-edge of a centre.  Every row is still computed, no product and no sum is dropped:
+    //  * the dZ GEMM stores T_L's centre rows only (row_scale_keep = d_norm_c);
+    //  * the transposed aggregate reads T_L through gm_batch::d_ect, which sends an edge into any other row to the zero block behind T_L (t_zero_rows).  Bitwise the
+    //    dense pass: there the row read is +-0 (a +0-started sum of +-0 products, times a positive norm), and fma(+-0, w, acc) leaves the aggregate's +0-started
+    //    chain unchanged -- a +0 accumulator stays +0, any other value stays itself; the block's +0 does the same.  (A non-finite W_L makes the dense pass's zeros
+    //    NaN and not these: the forward over the same weights then gave a NaN loss, and the NaN guard discards the step -- DESIGN 4.3);
+    //  * where the layer below is the first, that aggregate stores only the rows of dQ_{L-1} that can be non-zero (s_out = d_norm_e1, keep_signed), and the first
+    //    layer's weight gradient selects zeros for the others (g_keep).  Deeper models keep dQ_{L-1} whole: it is the A operand of a plain-loader dZ GEMM.
+    const bool t_centre = dq_centre && c.t_zero && gm_knob().dead_rows >= 2;
+    const bool dq_e1 = t_centre && Lg == 2 && L.dims[0] <= L.dims[1] && c.np != 2 && gm_wgrad_gather_ok(b->n_chunks, L.dims[0], L.dims[1]);
     if (!skip_head && mean_readout(c)) {      // G = dlogits Wl on the pooled rows, then every row of dQ_L from it
         GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, nullptr, c.Gpool, st));
         GM_TRY(readout_bwd(c, st));
@@ -1067,6 +1095,7 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
             // weights and, for the next step's dZ GEMM, their transpose) -> transposed aggregate (overwrites dQ).
             w.A = c.Z[l]; w.lda = fi; w.G = dQ; w.ldg = fo;
             if (dq_centre && l == Lg - 1) w.g_keep = b->d_norm_c;
+            if (dq_e1 && l == Lg - 2) w.g_keep = b->d_norm_e1;      // dQ_{L-1} holds the sources of the centres' in-edges only; the other rows' bytes may be anything
             if (c.zfused[l]) {                 // the forward ran fused: Z[l] holds the rows of three or more sources, the table forms the others
                 const bool gather = l == 0 && !c.x0_user;
                 w.fuse2 = gather ? b->d_fuse2_feat : b->d_fuse2;
@@ -1091,6 +1120,7 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
                     // every other row -- the same tile, bit for bit, as the plain launch over a zero-filled dQ.  (dz_centre_ok is what gcn_forward chose
                     // DQ_CENTRE by, so it holds here whenever dq_centre does: the two ends of one contract, and the GM_REQUIRE below is its guard)
                     if (dq_centre && l == Lg - 1 && dz_centre_ok(c, l)) { g.fuse2 = b->d_dq_tab; g.zside = dQ; g.ldz = fo; }
+                    if (t_centre && l == Lg - 1) { g.row_scale_keep = b->d_norm_c; g.n_keep = b->n_c; }
                 } else if (use_wt) {
                     // dZ = dQ @ W^T through the direct-to-LDS kernel on transposed weights: left there by the previous step's
                     // weight-gradient reduction (which wrote these very weights), else transposed now (T x 256 KB)
@@ -1122,7 +1152,20 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
                 gm_agg_args a; GM_TRY(batch_agg(c, 1, st, a));
                 a.x = T; a.ldx = fi; a.s_out = b->d_norm; a.mask_h = maskprev; a.mask_b = maskbits;
                 a.out = dQ; a.width = fi;
-                GM_TRY(launch_agg(a, gm_aggregate_bytes(b, fi), gm_aggregate_bytes(b, fi), st));
+                int64_t by = gm_aggregate_bytes(b, fi);
+                if (t_centre && l == Lg - 1) {
+                    a.x_idx = b->d_ect;
+                    int64_t n_out = b->rows;
+                    if (dq_e1) {
+                        a.s_out = b->d_norm_e1; a.keep_signed = 1;
+                        // (the exact count when the launch accounting is on: read back once per batch; its bound otherwise -- nobody reads it then)
+                        n_out = gm_prof_enabled() ? gm_batch_e1_rows(b, st) : std::min<int64_t>(b->n_e1, b->rows);
+                    }
+                    // SURVEY 8(d)'s B_agg on what this launch touches: every indptr entry, the edge table, the row scales, the relu' bits of every row,
+                    // T_L's centre rows read once, the rows it stores written once
+                    by = 4 * (b->rows + 1) + 4 * b->edges + 4 * b->rows + (maskbits ? b->rows * (int64_t)fi / 4 : 0) + 4 * ((int64_t)b->n_c + n_out) * (int64_t)fi;
+                }
+                GM_TRY(launch_agg(a, by, by, st));
             }
         }
     }
@@ -1944,6 +1987,10 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
         wait(sq, e_in);
         if (two_q) wait(sq2, e_in);
     }
+    // the zero blocks behind T_L (GM_DEAD_ROWS=2), once per step: the caller's workspace is not preserved between calls.  On st BEHIND e_in -- the query streams
+    // start without them: the one query backward of the step follows a wait for an event st records later (e_fw), the support backwards run on st itself
+    GM_TRY(t_zero_fill(p.S, st)); GM_TRY(t_zero_fill(p.Q, st));
+    if (two_q) GM_TRY(t_zero_fill(p.Q2, st));
 
     auto protos = [&](int k) -> float* { return p.protos + (int64_t)k * p.proto_sz; };   // prototypes of support step k
     const int hoist = hp->hoist_z1, sparse = hp->sparse_bwd;
@@ -2065,6 +2112,7 @@ extern "C" int gm_meta_adapt(const gm_batch_t* spt, const int32_t* y_spt, const 
     p.Ct = cs.Ct; p.ns = cs.n; p.uni_s = cs.uniform ? 1 : 0; p.qmax_s = cs.qmax;
     p.S.pd = p.pd.base ? &p.pd : nullptr;
     GM_TRY(pad_theta(p, &theta, Lu.P, cut, shift, st));
+    GM_TRY(t_zero_fill(p.S, st));      // the zero block behind T_L (GM_DEAD_ROWS=2), once per call
     // support class tables -> pinned staging -> one asynchronous copy
     const size_t n_tab = (size_t)p.cap_s + 3 * (size_t)T;
     GM_TRY(stage_to_device(p.rows_s, 4 * n_tab, st, [&](void* h) {

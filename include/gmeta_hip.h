@@ -186,7 +186,11 @@ enum gm_field {
     GM_F_NORM_CENTRE,   /* float[rows]    GM_F_NORM with the sign bit set on every row that is not a centre                     */
     GM_F_EDGE_W,        /* float[edges]   weight of every in-edge, aligned with GM_F_INDICES (weighted batches only: GM_EINVAL otherwise) */
     GM_F_EDGE_W_T = 14, /* float[edges]   the same weights in the order of GM_F_INDICES_T (weighted batches only)                       */
-    GM_F_HOP = 15       /* int8[rows*centres] hop-distance label of every row per centre, row-major [rows, centres] (hop-labelled batches only: GM_EINVAL otherwise) */
+    GM_F_HOP = 15,      /* int8[rows*centres] hop-distance label of every row per centre, row-major [rows, centres] (hop-labelled batches only: GM_EINVAL otherwise) */
+    GM_F_NORM_E1 = 16,  /* float[rows]    GM_F_NORM with the sign bit set on every row that is not the source of an in-edge of a centre: the last
+                                          layer's backward leaves the gradient of the layer below zero there (GM_DEAD_ROWS=2)     */
+    GM_F_EDGE_CENTRE_T = 17 /* int32[edges] per edge of GM_F_INDICES_T: the destination row where it is a centre, else `rows` -- the zero row the
+                                          dense backward keeps behind its [rows, width] product T (GM_DEAD_ROWS=2)                 */
 };
 int32_t gm_batch_weighted(const gm_batch_t* b);
 /* Copies a field to host memory (synchronises `stream` internally). */
@@ -195,6 +199,8 @@ int gm_batch_read(const gm_batch_t* b, int32_t field, void* host_dst, int64_t by
 int gm_batch_device_ptr(const gm_batch_t* b, int32_t field, void** dptr);
 /* Rows with at least one out-edge inside the batch: the rows of GM_F_NORM_SRC whose sign bit is clear. */
 int gm_batch_source_rows(const gm_batch_t* b, int64_t* n_rows);
+/* Distinct source rows of the centres' in-edges: the rows of GM_F_NORM_E1 whose sign bit is clear (synchronises the batch's stream at first use). */
+int gm_batch_e1_source_rows(const gm_batch_t* b, int64_t* n_rows);
 
 /* ---- Feature gather: replaces np.vstack([feat[g][ids] ...]) + H2D (meta.py:119-120,193-194).
  * x_out: device fp32 [rows, feat_dim]; hop-labelled batches: [rows, feat_dim + centres * (D + 2)], the labelled rows x'. */
@@ -259,6 +265,14 @@ int gm_dense_gemm(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, c
 int gm_dense_dz_centre(const gm_batch_t* b, const float* dQ, int32_t K, const float* W, int64_t w_stride, int32_t N, float* T, void* stream);
 int gm_dense_wgrad_centre(const gm_batch_t* b, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
                           int64_t db_stride, void* stream);
+/* One level down (GM_DEAD_ROWS=2), exported for tests: the last layer's transposed aggregate  out[u, :] = mask[u, :] ? norm[u] * sum over the out-edges
+ * (u -> v) of w_uv T[v, :] : 0  as the dense backward launches it.  keep != 0: T is read through GM_F_EDGE_CENTRE_T -- its centre rows and one zero row
+ * behind it (T holds rows + 1 rows of `width` floats; the call zeroes the last one, the others outside the centre rows may hold anything) -- and only the
+ * rows GM_F_NORM_E1 keeps are stored, the other rows of `out` are left untouched; keep == 0: the plain launch over every row of T.  mask_b: packed relu'
+ * bits, byte (row * width + col) / 4, or NULL.  gm_dense_wgrad_e1 is gm_dense_wgrad_centre with GM_F_NORM_E1 as the flag. */
+int gm_dense_agg_centre_t(const gm_batch_t* b, float* T, int32_t width, const uint8_t* mask_b, float* out, int32_t keep, void* stream);
+int gm_dense_wgrad_e1(const gm_batch_t* b, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
+                      int64_t db_stride, void* stream);
 /* The weight gradient of the same layer (learner.py backward of `torch.matmul(feat, weight)` + bias) over the batch's weight-gradient row chunks,
  * per set t:  dW_t[K, N] = sum over the set's rows r of (s[r] x[r, :])^T g[r, :]  and  db_t[N] = sum_r gb[r, :].  Exported for numerics tests of the
  * weight-gradient kernels.  x: device [rows, ldx] (K used), g: [rows, ldg] (N used); s: row scale [rows] or NULL (1); gb: [rows, ldgb] or NULL (g).
