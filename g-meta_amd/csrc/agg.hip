@@ -473,7 +473,7 @@ int gm_agg_schedule(gm_batch* b, int64_t rows, int win, const int32_t* heavy_hos
 }
 
 template <int LPR, int NCH>
-static void launch_win(const AggK& a0, hipStream_t s) {
+static void launch_win(const AggK& a0, hipStream_t s, int* launched) {
     AggK a = a0;
     // rows per wave window: 64 at most, halved until the launch has ~64k waves (or 2 rows are left).  Small windows
     // keep the rows in flight on an XCD within reach of its 4-MiB L2 -- a source row is gathered by ~2 destination rows
@@ -486,14 +486,17 @@ static void launch_win(const AggK& a0, hipStream_t s) {
     if (a.sched) grid = GM_NXCD * a.sched_len;
     else if (a.n_heavy > 0) hipLaunchKernelGGL((k_agg_heavy<LPR, NCH>), dim3(a.n_heavy), dim3(AGG_HEAVY_BLOCK), 0, s, a);
     hipLaunchKernelGGL((k_agg_win<LPR, NCH, 2, 4>), dim3(grid), dim3(AGG_BLOCK), 0, s, a);
+    if (launched) *launched = GM_AGG_ID_WIN(LPR, NCH) + (a.sched ? GM_AGG_ID_WIN_SCHED + (a.hub ? GM_AGG_ID_WIN_SPLIT : 0) : a.n_heavy > 0 ? GM_AGG_ID_WIN_HEAVY : 0) +
+                                (a.rowlist ? GM_AGG_ID_WIN_LIST : 0);
 }
 
 template <int VEC, int LPR>
-static void launch_one(const AggK& a0, hipStream_t s) {
+static void launch_one(const AggK& a0, hipStream_t s, int* launched) {
     AggK a = a0;
     constexpr int RPB = (GM_WAVE / LPR) * (AGG_BLOCK / GM_WAVE);
     a.nblocks = (int)((a.rows + RPB - 1) / RPB);
     hipLaunchKernelGGL((k_agg<VEC, LPR>), dim3(a.nblocks), dim3(AGG_BLOCK), 0, s, a);
+    if (launched) *launched = GM_AGG_ID_ONE(VEC, LPR);
 }
 
 // Non-temporal stores of the output from 128 MB of output upwards -- a small output stays in the caches for the GEMM that reads it next
@@ -518,26 +521,26 @@ int gm_launch_aggregate(const gm_agg_args& g, hipStream_t s) {
     if (!win) { a.heavy = nullptr; a.n_heavy = 0; a.sched = nullptr; a.hub = nullptr; }      // the generic kernel walks every row itself
     if (win && gm_knob().agg_stream && gm_stream_ok(g)) return gm_launch_stream(g, a.nt, s);      // LDS-DMA stream kernel (row segments + hub parts in one launch)
     if (win) {
-        if (g.width == 64) launch_win<16, 1>(a, s);
-        else if (g.width == 128) launch_win<32, 1>(a, s);
-        else if (g.width == 256) launch_win<64, 1>(a, s);
-        else launch_win<64, 2>(a, s);
+        if (g.width == 64) launch_win<16, 1>(a, s, g.launched);
+        else if (g.width == 128) launch_win<32, 1>(a, s, g.launched);
+        else if (g.width == 256) launch_win<64, 1>(a, s, g.launched);
+        else launch_win<64, 2>(a, s, g.launched);
     } else if (vec4) {
         const int n4 = g.width / 4;
-        if (n4 > 32) launch_one<4, 64>(a, s);
-        else if (n4 > 16) launch_one<4, 32>(a, s);
-        else if (n4 > 8) launch_one<4, 16>(a, s);
-        else if (n4 > 4) launch_one<4, 8>(a, s);
-        else if (n4 > 2) launch_one<4, 4>(a, s);
-        else launch_one<4, 2>(a, s);
+        if (n4 > 32) launch_one<4, 64>(a, s, g.launched);
+        else if (n4 > 16) launch_one<4, 32>(a, s, g.launched);
+        else if (n4 > 8) launch_one<4, 16>(a, s, g.launched);
+        else if (n4 > 4) launch_one<4, 8>(a, s, g.launched);
+        else if (n4 > 2) launch_one<4, 4>(a, s, g.launched);
+        else launch_one<4, 2>(a, s, g.launched);
     } else {
         const int w = g.width;
-        if (w > 32) launch_one<1, 64>(a, s);
-        else if (w > 16) launch_one<1, 32>(a, s);
-        else if (w > 8) launch_one<1, 16>(a, s);
-        else if (w > 4) launch_one<1, 8>(a, s);
-        else if (w > 2) launch_one<1, 4>(a, s);
-        else launch_one<1, 2>(a, s);
+        if (w > 32) launch_one<1, 64>(a, s, g.launched);
+        else if (w > 16) launch_one<1, 32>(a, s, g.launched);
+        else if (w > 8) launch_one<1, 16>(a, s, g.launched);
+        else if (w > 4) launch_one<1, 8>(a, s, g.launched);
+        else if (w > 2) launch_one<1, 4>(a, s, g.launched);
+        else launch_one<1, 2>(a, s, g.launched);
     }
     GM_HIP(hipGetLastError());
     return GM_OK;

@@ -452,6 +452,7 @@ int gm_launch_stream(const gm_agg_args& g, int nt, hipStream_t s) {
     if (g.width == 256) launch_stream<64, AS_DEPTH_KIB>(a, nwg, s);
     else if (g.width == 128) launch_stream<32, 2 * AS_DEPTH_KIB>(a, nwg, s);
     else launch_stream<16, 4 * AS_DEPTH_KIB>(a, nwg, s);
+    if (g.launched) *g.launched = GM_AGG_ID_STREAM(g.width / 4, split);
     GM_HIP(hipGetLastError());
     return GM_OK;
 }

@@ -212,3 +212,94 @@ extern "C" int gm_dense_wgrad(const gm_batch_t* b, const float* x, int64_t ldx, 
     gm_batch_mark_use(b, st);
     return rc;
 }
+
+// ================================================================================ aggregate, exported for numerics tests
+// One launch of gm_launch_aggregate over one orientation of the batch with every field the production callers (gm_aggregate, batch_agg / gcn_forward,
+// gcn_backward) set, and the instantiation that ran (include/gmeta_hip.h)
+extern "C" int gm_dense_aggregate(const gm_batch_t* b, int32_t transposed, int32_t x_src, const float* x, int64_t ldx, int32_t width, int32_t scale_src,
+                                  const float* s_in, const float* s_out, int32_t keep_signed, const float* bias, int64_t bias_stride, int32_t relu,
+                                  uint8_t* relu_bits, const float* mask_h, const uint8_t* mask_b, int32_t hubs, const int32_t* rowlist, int64_t n_list,
+                                  int32_t list_win, int32_t list_sched, int32_t skip_lo, int32_t skip_hi, int32_t stream_ok, float* out, int32_t* launched,
+                                  void* stream) {
+    GM_REQUIRE(b && out && width >= 1 && x_src >= 0 && x_src <= 3 && scale_src >= 0 && scale_src <= 2 && hubs >= 0 && hubs <= 2, GM_EINVAL, "dense_aggregate: bad arguments");
+    GM_REQUIRE(!(mask_h && mask_b), GM_EINVAL, "dense_aggregate: mask_h together with mask_b");
+    GM_REQUIRE(!(rowlist && stream_ok), GM_EINVAL, "dense_aggregate: a row list together with the stream kernel");
+    GM_REQUIRE(!stream_ok || hubs == 2, GM_EINVAL, "dense_aggregate: the stream kernel takes the batch's hub tables (hubs == 2)");
+    const int o = transposed ? 1 : 0;
+    const bool gather = x_src == 1 || x_src == 2;
+    GM_REQUIRE(gather || (x && ldx >= width), GM_EINVAL, "dense_aggregate: a caller matrix needs x and ldx >= width");
+    GM_REQUIRE(!gather || width == b->feat_dim, GM_EINVAL, "dense_aggregate: a gather needs width == feat_dim (%d)", b->feat_dim);
+    GM_REQUIRE(x_src != 2 || (!transposed && b->d_efeat), GM_EINVAL, "dense_aggregate: the per-edge feature rows belong to the by-destination CSR");
+    GM_REQUIRE(x_src != 3 || (transposed && b->d_ect), GM_EINVAL, "dense_aggregate: the centre-edge table belongs to the by-source CSR of a batch that carries one");
+    GM_REQUIRE((scale_src == 1) == (s_in != nullptr), GM_EINVAL, "dense_aggregate: s_in goes with scale_src == 1 and only with it");
+    GM_REQUIRE(scale_src != 2 || b->d_enorm[o], GM_EINVAL, "dense_aggregate: the batch has no per-edge norm table");
+    GM_REQUIRE(!bias || !bias_stride || b->d_set_row_off, GM_EINVAL, "dense_aggregate: per-set bias without set row offsets");
+    GM_REQUIRE(!keep_signed || s_out, GM_EINVAL, "dense_aggregate: keep_signed needs s_out");
+    GM_REQUIRE(!relu_bits || relu, GM_EINVAL, "dense_aggregate: relu_bits are written with relu");
+    hipStream_t st = (hipStream_t)stream;
+    gm_agg_args a{};
+    a.indptr = transposed ? b->d_indptr_t : b->d_indptr;
+    a.indices = transposed ? b->d_indices_t : b->d_indices;
+    a.rows = b->rows; a.width = width; a.out = out; a.launched = launched;
+    if (gather) { a.x = b->feat; a.ldx = b->feat_ld; a.x_row = b->d_feat_row; if (x_src == 2) a.x_idx = b->d_efeat; }
+    else { a.x = x; a.ldx = ldx; if (x_src == 3) a.x_idx = b->d_ect; }
+    if (b->weighted) {
+        // as gm_aggregate: only the per-edge tables have a slot for the edges' weights
+        GM_REQUIRE(scale_src != 1, GM_EINVAL, "dense_aggregate: on a weighted batch the source scale is none or the batch's own table (the per-source gather has no edge-weight slot)");
+        // ... and a feature gather meets the weights only through the per-edge row table (gm_aggregate always takes it; the by-source CSR has none)
+        GM_REQUIRE(x_src != 1, GM_EINVAL, "dense_aggregate: on a weighted batch the feature gather goes through the per-edge row table (x_src 2; the per-source gather has no edge-weight slot)");
+        if (scale_src == 0) a.e_w = b->d_ew[o];
+    }
+    if (scale_src == 1) a.s_in = s_in;
+    if (scale_src == 2) { a.s_in = b->d_norm; a.e_w = b->d_enorm[o]; }
+    a.s_out = s_out; a.keep_signed = keep_signed ? 1 : 0;
+    a.bias = bias; a.bias_stride = bias_stride; a.set_row_off = b->d_set_row_off; a.n_sets = b->sets;
+    a.relu = relu ? 1 : 0; a.relu_bits = relu_bits; a.mask_h = mask_h; a.mask_b = mask_b;
+    if (hubs) { a.heavy = b->d_heavy[o]; a.n_heavy = b->n_heavy[o]; a.heavy_deg = b->heavy_deg; }
+    if (hubs == 2) { a.sched = b->d_sched[o]; a.sched_len = b->sched_len[o]; a.sched_win = b->sched_win; GM_TRY(gm_agg_hub(a, b, o, st)); }
+    if (skip_lo <= skip_hi) { a.skip_on = 1; a.skip_lo = skip_lo; a.skip_hi = skip_hi; }
+    if (rowlist) {
+        GM_REQUIRE(n_list >= 1 && n_list <= b->rows && list_win >= 2 && list_win <= 64 && (list_win & (list_win - 1)) == 0, GM_EINVAL,
+                   "dense_aggregate: a row list needs 1 .. rows entries and a window of 2, 4, .. 64 rows");
+        std::vector<int32_t> h((size_t)n_list);
+        GM_HIP(hipMemcpyAsync(h.data(), rowlist, sizeof(int32_t) * (size_t)n_list, hipMemcpyDeviceToHost, st));
+        GM_HIP(hipStreamSynchronize(st));
+        for (int64_t k = 0; k < n_list; ++k)
+            GM_REQUIRE(h[k] >= 0 && h[k] < b->rows && (k == 0 || h[k] > h[k - 1]), GM_EINVAL, "dense_aggregate: the row list is not ascending / out of range at entry %lld", (long long)k);
+        a.rowlist = rowlist; a.n_list = n_list; a.list_win = list_win;
+        if (list_sched) {
+            // the batch's block schedule over its own list of window rows (gcn_forward's partial launch of a fused pass)
+            GM_REQUIRE(hubs == 2 && !transposed && b->d_sched_mid && n_list == b->n_mid && list_win == b->mid_win, GM_EINVAL,
+                       "dense_aggregate: the list schedule goes with the batch's own list (%d rows, windows of %d) and its hub tables", b->n_mid, b->mid_win);
+            a.sched = b->d_sched_mid; a.sched_len = b->sched_len_mid; a.sched_win = b->mid_win;
+        } else { a.sched = nullptr; a.sched_len = 0; }
+    } else GM_REQUIRE(!list_sched, GM_EINVAL, "dense_aggregate: a list schedule without a row list");
+    if (stream_ok && a.e_w && a.e_w == b->d_enorm[o]) GM_TRY(gm_agg_stream_args(a, b, o, gather, st));
+    const int rc = gm_launch_aggregate(a, st);
+    gm_batch_mark_use(b, st);
+    return rc;
+}
+
+// What the tests of gm_dense_aggregate need to know about orientation o of a batch: info[16] = {hub threshold, hub rows, rows per scheduled window, edges
+// per hub part (0: unsplit), hub parts, scheduled (0 / 1), rows of the batch's window-row list, its window, list schedule (0 / 1), stream row segments (0 until the
+// orientation's first stream-eligible launch), stream workgroups, hub workgroups among them, weighted, feat_dim, feat_ld, 0}
+extern "C" int gm_dense_agg_info(const gm_batch_t* b, int32_t transposed, int64_t* info) {
+    GM_REQUIRE(b && info, GM_EINVAL, "dense_agg_info: bad arguments");
+    const int o = transposed ? 1 : 0;
+    const int64_t v[16] = {b->heavy_deg, b->n_heavy[o], b->sched_win, b->hub_part[o], b->hub_parts[o], b->d_sched[o] ? 1 : 0, b->d_mid ? b->n_mid : 0, b->mid_win,
+                           b->d_sched_mid ? 1 : 0, b->d_sseg[o] ? b->stream_nseg[o] : 0, b->stream_nwg[o], b->stream_hubwg[o], b->weighted ? 1 : 0, b->feat_dim, b->feat_ld, 0};
+    std::copy(v, v + 16, info);
+    return GM_OK;
+}
+// Device copies of the batch's derived tables (which: 0 per-edge source norm of orientation o [edges] float, 1 per-edge feature row [edges] int32, 2 window-row
+// list [info[6]] int32, 3 hub rows of orientation o [info[1]] int32): n elements -> dst (device)
+extern "C" int gm_dense_agg_table(const gm_batch_t* b, int32_t which, int32_t transposed, void* dst, int64_t n, void* stream) {
+    GM_REQUIRE(b && dst && n >= 0 && which >= 0 && which <= 3, GM_EINVAL, "dense_agg_table: bad arguments");
+    const int o = transposed ? 1 : 0;
+    const void* src = which == 0 ? (const void*)b->d_enorm[o] : which == 1 ? (const void*)b->d_efeat : which == 2 ? (const void*)b->d_mid : (const void*)b->d_heavy[o];
+    const int64_t have = which <= 1 ? b->edges : which == 2 ? b->n_mid : b->n_heavy[o];
+    GM_REQUIRE(src && n <= have, GM_EINVAL, "dense_agg_table: table %d holds %lld entries", which, (long long)(src ? have : 0));
+    if (n) GM_HIP(hipMemcpyAsync(dst, src, 4 * (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    gm_batch_mark_use(b, (hipStream_t)stream);
+    return GM_OK;
+}

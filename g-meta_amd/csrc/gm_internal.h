@@ -349,7 +349,17 @@ struct gm_agg_args {
     const int32_t* rowlist; int64_t n_list; int list_win;      // window kernel only: the wave windows walk rowlist[0 .. n_list) instead of every row (sched / sched_len then index list blocks)
     // optional: the batch / orientation whose stream tables this launch may use (gm_agg_stream_args): eligible launches take the LDS-DMA stream kernel (agg_stream.hip)
     const gm_batch* stream; int stream_o; int stream_feat; int64_t stream_xrows;
+    int* launched;             // optional: receives the GM_AGG_ID_* of the instantiation launched (host side; tests)
 };
+// gm_agg_args::launched
+#define GM_AGG_ID_LPR(LPR) ((LPR) == 64 ? 6 : (LPR) == 32 ? 5 : (LPR) == 16 ? 4 : (LPR) == 8 ? 3 : (LPR) == 4 ? 2 : 1)
+#define GM_AGG_ID_ONE(VEC, LPR) (100 + ((VEC) == 4 ? 10 : 0) + GM_AGG_ID_LPR(LPR))      // k_agg<VEC, LPR>: 101 .. 106, 111 .. 116
+#define GM_AGG_ID_WIN(LPR, NCH) (200 + 16 * ((NCH) == 2 ? 3 : GM_AGG_ID_LPR(LPR) - 4))  // k_agg_win<LPR, NCH, 2, 4>: 200, 216, 232, 248, plus the flags below
+#define GM_AGG_ID_WIN_SCHED 1           // hub rows ride in the window launch (block schedule)
+#define GM_AGG_ID_WIN_SPLIT 2           // ... split into parts (arrival ticket, part-order sum)
+#define GM_AGG_ID_WIN_HEAVY 4           // hub rows by a separate k_agg_heavy<LPR, NCH> launch
+#define GM_AGG_ID_WIN_LIST 8            // the windows walk a row list
+#define GM_AGG_ID_STREAM(LPR, SPLIT) (300 + 2 * (GM_AGG_ID_LPR(LPR) - 4) + ((SPLIT) ? 1 : 0))      // k_agg_stream<LPR, .>: 300 .. 305
 // fills the stream fields of `a` for orientation o of batch b (gather: the sources are rows of the store's feature table); a no-op without tables
 int gm_agg_stream_args(gm_agg_args& a, const gm_batch* b, int o, bool gather, hipStream_t s);      // (builds the orientation's tables at first use, on s)
 bool gm_stream_ok(const gm_agg_args& g);

@@ -257,6 +257,35 @@ int gm_dense_gemm(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, c
                   float* out, int64_t ldc, const float* s, const float* s_keep, const float* bias, int64_t bias_stride, int32_t relu,
                   uint8_t* relu_bits, const float* mask_h, const uint8_t* mask_b, float* zero_out, uint32_t* amax_out, int32_t mode,
                   int32_t* launched, void* stream);
+/* One aggregate launch over one orientation of the batch (0: the in-edge CSR, transposed: the by-source CSR) with every option the library's own callers
+ * set, exported for numerics tests of every aggregate kernel (agg.hip, agg_stream.hip):
+ *   out[v, :width] = epi(|s_out[v]| * sum over the edges e of row v of w_e * X[src_e, :] + bias_t)      for the rows v of set t.
+ * x_src: 0 X = x (device [rows, ldx]); 1 X = the batch's feature table through GM_F_FEAT_ROW per source; 2 the same through the per-edge row table (by-destination
+ *   CSR only); 3 X = x read through GM_F_EDGE_CENTRE_T (transposed only; x holds rows + 1 rows, the last one zero).  1 and 2 need width == the feature width.
+ * scale_src: 0 w_e = 1 (weighted batches: the edge's weight); 1 w_e = s_in[src_e], gathered per source (refused on weighted batches, as gm_aggregate does);
+ *   2 w_e from the batch's per-edge table of GM_F_NORM[src_e] (weighted batches: weight x norm).  s_in is given with scale_src == 1 only.
+ * s_out (or NULL): row scale; keep_signed: its sign bit marks rows that are computed and not stored, the scale is the magnitude.  bias_t = bias + t * bias_stride
+ *   (stride 0: one bias for every set) or NULL;  relu: max(v, 0), NaN kept;  relu_bits (or NULL, with relu): packed relu' bits of the stored value, byte
+ *   (v * width + c) / 4, bit c % 4;  mask_h [rows, width] (or NULL): zero where mask_h <= 0;  mask_b (or NULL): the same as packed bits.
+ * hubs: 0 no hub handling (every row by the row kernels); 1 the batch's hub-row list without a schedule (a separate hub launch); 2 its block schedule and hub parts.
+ * rowlist (device, ascending, n_list entries; or NULL): the windows walk these rows in windows of list_win rows (2, 4, .. 64); list_sched: with the batch's own
+ *   schedule over its list of window rows (the list must be that list).  skip_lo <= skip_hi: rows of those degrees are left unwritten (window kernel only).
+ * stream_ok: the launch may take the stream kernel where the library's own callers could (hubs == 2, scale_src == 2, no epilogue option).
+ * launched (or NULL) receives the id of the kernel instantiation that ran (GM_AGG_ID_* in the library's internal header).
+ * GM_EINVAL: mask_h together with mask_b; a row list together with stream_ok, off the window kernel, not ascending or out of range; a gather of another width
+ *   than the feature width; relu_bits / mask_b where the stores are not 16-byte vectors; on weighted batches scale_src 1 and x_src 1 (gm_aggregate's refusals: only
+ *   the per-edge tables have a slot for the weights). */
+int gm_dense_aggregate(const gm_batch_t* b, int32_t transposed, int32_t x_src, const float* x, int64_t ldx, int32_t width, int32_t scale_src,
+                       const float* s_in, const float* s_out, int32_t keep_signed, const float* bias, int64_t bias_stride, int32_t relu,
+                       uint8_t* relu_bits, const float* mask_h, const uint8_t* mask_b, int32_t hubs, const int32_t* rowlist, int64_t n_list,
+                       int32_t list_win, int32_t list_sched, int32_t skip_lo, int32_t skip_hi, int32_t stream_ok, float* out, int32_t* launched,
+                       void* stream);
+/* What those tests need to know about one orientation of a batch: info[16] = {hub threshold, hub rows, rows per scheduled window, edges per hub part (0: unsplit),
+ * hub parts, scheduled, rows of the batch's window-row list, its window, list schedule present, stream row segments (0 before the orientation's first
+ * stream-eligible launch), stream workgroups, hub workgroups among them, weighted, feature width, feature row stride, 0};  gm_dense_agg_table copies n entries of
+ * a derived table to dst (device): which 0 per-edge source norm (float), 1 per-edge feature row, 2 window-row list, 3 hub rows (int32). */
+int gm_dense_agg_info(const gm_batch_t* b, int32_t transposed, int64_t* info);
+int gm_dense_agg_table(const gm_batch_t* b, int32_t which, int32_t transposed, void* dst, int64_t n, void* stream);
 /* The last layer's dZ product and weight gradient where dQ holds its CENTRE rows only (GM_DEAD_ROWS: gm_meta_step no longer zero-fills the others;
  * their bytes may be anything), exported for tests:  T[r, :N] = norm[r] * (dQ0[r, :K] @ W_t^T)  with W_t stored [N, K] and dQ0 = dQ on the batch's
  * centre rows, 0 elsewhere -- through the fused split kernel and the batch's per-row table;  dW_t[Kx, N] = sum_r (norm[r] x[r, :Kx])^T dQ0[r, :N],
