@@ -86,7 +86,7 @@ void gm_dev_free(void* p, hipStream_t s) {
 // dropped.  With the release threshold raised the pool still hands ONE block of every build / drop cycle back to the OS inside hipFreeAsync and maps
 // a new one in the next build: 0.7 - 1.7 ms of host time per meta-batch at the arxiv shape, in whichever thread dropped the batch (ROCm 7.2; found
 // with GM_TIMING and tools/build_prof.py, reproduced in isolation by tools/pool_free_probe.py) -- the training thread's own loop, where a receptive-
-// field meta-step takes 2.2 ms.  A released slab carries an event recorded on the releasing stream (behind the batch's consumers: batch_free);
+// field meta-step takes 2.2 ms.  A released slab carries an event recorded on the releasing stream (behind the batch's consumers: gm_batch_destroy);
 // whoever takes it next waits for that event on ITS stream: the ordering the pool would give, without the unmapping.  The cache holds at most
 // GM_SLAB_CACHE_MB (default 4096) per process; what it holds at exit is left to the driver (a static destructor would run after HIP's teardown).
 struct SlabEntry { char* base; size_t cap; hipEvent_t ready; int dev; };

@@ -224,7 +224,7 @@ __global__ __launch_bounds__(SCAN_T) void k_heavy_rows(const int32_t* indptr, co
 // ------------------------------------------------------------------------------------------ host
 void gm_cone_free(gm_cone* c, hipStream_t s) {
     if (!c) return;
-    (void)s;                        // (the level arrays live in the batch's slabs: batch_free releases them)
+    (void)s;                        // (the level arrays live in the batch's slabs: gm_batch_destroy releases them)
     delete c;
 }
 

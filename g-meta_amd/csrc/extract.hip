@@ -7,6 +7,7 @@
 #include <initializer_list>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 #include <mutex>
 #include <type_traits>
 #include "gm_internal.h"
@@ -884,15 +885,8 @@ __global__ void k_label_features(const float* feat, int64_t ld, int F0, const in
 }
 
 // ------------------------------------------------------------------------------------------ host
-// Hop-label switch of the calling thread (gm_set_hop_labels): read where a batch is built
-static thread_local int g_hop_labels = 0;
-extern "C" void gm_set_hop_labels(int32_t D) {
-    if (D < 0 || D > 7) { gm_set_error("gm_set_hop_labels: D=%d ignored (0 = off, 1..7 = label cap)", D); return; }
-    g_hop_labels = D;
-}
-extern "C" int32_t gm_get_hop_labels(void) { return g_hop_labels; }
-extern "C" int32_t gm_batch_hop_labels(const gm_batch_t* b) { return b ? b->hop_D : 0; }
-static inline int hop_feat_dim(const gm_store* st, int centres, int D) { return st->feat_dim + centres * (D + 2); }
+// workgroups of 256 threads over n items, `cap` at most (the kernels stride over the rest)
+static inline int grid_for(int64_t n, int cap) { return (int)std::min<int64_t>(cap, (n + 255) / 256); }
 // a new batch reads the store's feature table; with D > 0 the finalisation replaces it by the batch's own labelled table (label_batch)
 static void batch_features(gm_batch* b, int D) {
     b->feat = b->store->d_feat; b->feat_ld = b->store->feat_ld; b->feat_dim = b->store->feat_dim; b->feat_rows = b->store->total_nodes; b->hop_D = D;
@@ -900,111 +894,19 @@ static void batch_features(gm_batch* b, int D) {
 // Finalisation of a labelled batch, before the edge / row tables are derived (they then come out with identity feature rows): labels, the batch's
 // feature table, and the row tables swapped -- d_store_row keeps the store rows (GM_F_FEAT_ROW)
 static int label_batch(gm_batch* b, hipStream_t s) {
-    const int D = b->hop_D, nc = b->centres, Fd = hop_feat_dim(b->store, nc, D), ldo = gm_pad_feat(Fd);
+    const int D = b->hop_D, nc = b->centres, Fd = gm_hop_feat_dim(b->store, nc, D), ldo = gm_pad_feat(Fd);
     float* tab = nullptr; int32_t* ident = nullptr;
     GM_TRY(gm_balloc(b, &b->d_hop, (size_t)b->rows * nc, s)); GM_TRY(gm_balloc(b, &tab, (size_t)b->rows * ldo, s)); GM_TRY(gm_balloc(b, &ident, (size_t)b->rows, s));
     if (b->rows > 0) {
         hipLaunchKernelGGL(k_hop_labels, dim3(b->subs * nc), dim3(GM_HOP_BLOCK), 0, s, b->d_sub_off, b->d_centre, nc, b->d_indptr, b->d_indices, D, b->d_hop);
-        const int64_t total = b->rows * (ldo / 4);
-        hipLaunchKernelGGL(k_label_features, dim3((int)std::min<int64_t>(4096, (total + 255) / 256)), dim3(256), 0, s, b->store->d_feat, (int64_t)b->store->feat_ld,
-                           b->store->feat_dim, b->d_feat_row, b->d_hop, nc, D + 2, tab, ldo, (int64_t)b->rows, ident);
+        hipLaunchKernelGGL(k_label_features, dim3(grid_for(b->rows * (ldo / 4), 4096)), dim3(256), 0, s, b->store->d_feat, (int64_t)b->store->feat_ld, b->store->feat_dim, b->d_feat_row, b->d_hop, nc, D + 2, tab, ldo, (int64_t)b->rows, ident);
         GM_HIP(hipGetLastError());
     }
     b->d_store_row = b->d_feat_row; b->d_feat_row = ident;
     b->feat = tab; b->feat_ld = ldo; b->feat_dim = Fd; b->feat_rows = b->rows;
     return GM_OK;
 }
-void gm_batch_mark_use(const gm_batch* b, hipStream_t st) {
-    if (!b || st == b->stream) return;              // same stream: the frees are already ordered behind the consumer
-    if (!b->used_ev && hipEventCreateWithFlags(&b->used_ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); b->used_ev = nullptr; return; }
-    if (hipEventRecord(b->used_ev, st) != hipSuccess) (void)hipGetLastError();
-}
 
-// Hub-part counters / partial rows of orientation o are about to be used by a launch on `s`: if the previous such launch went to ANOTHER
-// stream, order this one behind everything queued there so far (which includes that launch).  Costs nothing while a batch stays on one stream.
-int gm_batch_hub_order(const gm_batch* b, int o, hipStream_t s, int set) {
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    const int k = set * 2 + o;
-    if (b->hub_used[k] && b->hub_stream[k] != s) {
-        // The remembered stream may have been destroyed by its owner since: a failed record / wait must neither drop the ordering nor leave a
-        // sticky error for the next hipGetLastError() -- fall back to draining the device before the scratch is reused.
-        bool ordered = false;
-        if (b->hub_ev[k] || hipEventCreateWithFlags(&b->hub_ev[k], hipEventDisableTiming) == hipSuccess)
-            ordered = hipEventRecord(b->hub_ev[k], b->hub_stream[k]) == hipSuccess && hipStreamWaitEvent(s, b->hub_ev[k], 0) == hipSuccess;
-        if (!ordered) {
-            (void)hipGetLastError();
-            GM_HIP(hipDeviceSynchronize());
-        }
-    }
-    b->hub_used[k] = true; b->hub_stream[k] = s;
-    return GM_OK;
-}
-
-// Second set of hub-part arrival counters and partial rows: the part tables are copied (device to device, on `s`, behind the batch's build),
-// the counters start at zero like the first set's.
-int gm_batch_hub_alt(const gm_batch* cb, hipStream_t s) {
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    gm_batch* b = const_cast<gm_batch*>(cb);
-    bool waited = false;
-    for (int o = 0; o < 2; ++o) {
-        if (!b->d_hub[o] || b->d_hub2[o]) continue;
-        int32_t* h2 = nullptr; float* sc2 = nullptr;
-        GM_TRY(gm_balloc(b, &h2, (size_t)b->hub_words[o], b->stream));
-        GM_TRY(gm_balloc(b, &sc2, (size_t)b->hub_parts[o] * GM_AGG_HUB_LD, b->stream));
-        if (!waited && s != b->stream) { hipEvent_t e; GM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); GM_HIP(hipEventRecord(e, b->stream)); GM_HIP(hipStreamWaitEvent(s, e, 0)); GM_HIP(hipEventDestroy(e)); waited = true; }
-        GM_HIP(hipMemcpyAsync(h2, b->d_hub[o], sizeof(int32_t) * (size_t)b->hub_words[o], hipMemcpyDeviceToDevice, s));
-        // (the first set's counters are zero between launches -- the last arriver resets them -- but a launch of the first set may be in flight on
-        // another stream right now: zero the copy's counters explicitly)
-        const size_t n_heavy = (size_t)b->n_heavy[o], parts = (size_t)b->hub_parts[o];
-        GM_HIP(hipMemsetAsync(h2 + n_heavy + 1 + parts, 0, sizeof(int32_t) * n_heavy, s));
-        b->d_hub2[o] = h2; b->d_hub_scratch2[o] = sc2;
-    }
-    if (waited) gm_batch_mark_use(b, s);
-    return GM_OK;
-}
-
-int gm_balloc_bytes(gm_batch* b, void** p, size_t bytes, hipStream_t s) {
-    std::lock_guard<std::mutex> lk(b->slab_mu);          // (lazily built tables -- receptive-field levels, stream tables, gains -- may come from another thread than the build's)
-    bytes = (bytes + 255) / 256 * 256;
-    if (b->slabs.empty() || b->slabs.back().cap - b->slabs.back().used < bytes) {
-        // slab size: what the big arrays of this batch will need in total when the sizes are known (rows / edges; measured on the arxiv query batch:
-        // 139 MB at 1.14 M rows / 2.1 M edges), plus room for the level arrays of a two-layer receptive-field build (12 + 4 bytes per row, 8 per edge:
-        // cone.hip) so that a batch is ONE block of the slab cache; else 8 MiB steps
-        const size_t guess = (size_t)b->rows * 78 + (size_t)b->edges * 31 + ((size_t)2 << 20) + (size_t)b->rows * 20 + (size_t)b->edges * 8 +
-                             (b->hop_D ? (size_t)b->rows * (4 * (size_t)gm_pad_feat(b->store->feat_dim + b->centres * (b->hop_D + 2)) + 8) : 0);      // (+ a labelled batch's own feature table)
-        gm_batch::slab sl{nullptr, 0, 0};
-        GM_TRY(gm_slab_acquire(&sl.base, &sl.cap, std::max(bytes, b->slabs.empty() ? guess : std::max<size_t>(guess / 4, (size_t)8 << 20)), s));
-        b->slabs.push_back(sl);
-    }
-    gm_batch::slab& sl = b->slabs.back();
-    *p = sl.base + sl.used; sl.used += bytes;
-    return GM_OK;
-}
-
-static void batch_free(gm_batch* b) {
-    gm_phase_timer tm("batch-free");
-    hipStream_t s = b->stream;
-    for (int o = 0; o < 4; ++o) if (b->hub_ev[o]) { (void)hipEventDestroy(b->hub_ev[o]); b->hub_ev[o] = nullptr; }
-    if (b->ro_ev) { (void)hipEventDestroy(b->ro_ev); b->ro_ev = nullptr; }
-    if (b->used_ev) {
-        if (hipStreamWaitEvent(s, b->used_ev, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipEventSynchronize(b->used_ev); }
-        (void)hipEventDestroy(b->used_ev); b->used_ev = nullptr;
-    }
-    tm.lap("events");
-    for (auto& sl : b->slabs) {      // every array of the batch lives in these (gm_balloc)
-        gm_slab_release(sl.base, sl.cap, s);
-        if (gm_knob().timing) { char nm[64]; snprintf(nm, sizeof nm, "slab %zu MB (%zu used)", sl.cap >> 20, sl.used >> 20); tm.lap(nm); }
-    }
-    b->slabs.clear();
-    tm.lap("slabs");
-    for (int l = 0; l <= GM_MAX_GCN; ++l) { gm_cone_free(b->cone[l], s); b->cone[l] = nullptr; }
-    tm.lap("cones");
-}
-
-// Launch tables derived from the set layout: GEMM row tiles never straddle two sets (each set has its own
-// fast weights); weight-gradient chunks are sized by gm_wgrad_chunk_rows.
 // Row gains of the two aggregates (gm_bound.h): only the opt-in two-piece kernels read them, so they are computed at first use (on `s`,
 // ordered behind the batch's build) instead of in every batch finalisation (k_gains was the longest finalisation kernel: 0.2 ms on the 1.14 M-row
 // query batch).  At least 1: an isolated row still passes its own magnitude on wherever a kernel adds a self term.
@@ -1015,11 +917,10 @@ int gm_batch_gains(const gm_batch* cb, hipStream_t s) {
     if (b->d_gain) return GM_OK;
     float* g = nullptr;
     GM_TRY(gm_balloc(b, &g, (size_t)2, b->stream));                                        // (the batch's slabs: freed with it, on its own stream)
-    if (s != b->stream) { hipEvent_t e; GM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); GM_HIP(hipEventRecord(e, b->stream)); GM_HIP(hipStreamWaitEvent(s, e, 0)); GM_HIP(hipEventDestroy(e)); }
+    GM_TRY(gm_batch_wait_build(b, s));
     GM_HIP(hipMemsetD32Async((hipDeviceptr_t)g, 0x3f800000, 2, s));                        // 1.0f, 1.0f
     if (b->rows > 0) {
-        hipLaunchKernelGGL(k_gains, dim3((int)std::min<int64_t>(2048, (b->rows + 255) / 256)), dim3(256), 0, s, b->d_indptr, b->d_indices, b->d_indptr_t, b->d_norm,
-                           (int64_t)b->rows, reinterpret_cast<unsigned*>(g));
+        hipLaunchKernelGGL(k_gains, dim3(grid_for(b->rows, 2048)), dim3(256), 0, s, b->d_indptr, b->d_indices, b->d_indptr_t, b->d_norm, (int64_t)b->rows, reinterpret_cast<unsigned*>(g));
         GM_HIP(hipGetLastError());
     }
     b->d_gain = g;
@@ -1050,27 +951,30 @@ static void sort_rows_with_degrees(std::vector<int32_t>& row, std::vector<int32_
     }
     if (r0 != row.data()) { row.swap(row2); deg.swap(deg2); }
 }
+// Scratch of the finalisation's round trip: ONE allocation, ONE memset (its first 32 bytes), ONE download.  Offsets in ints, the same on the device and in
+// the downloaded copy: [4,6) hub-row counts | [8, 8 + n_c) centre in-degrees | n_c local centre ids | 2 x `first` (row, degree) pairs of the hub lists |
+// k_row_tables' per-workgroup {rows, edges, rows with an out-edge} partials (u64 triples)
+struct FinalScratch {
+    int first = 0, rt_blocks = 1;      // hub rows per orientation the first fetch carries; k_row_tables' grid (512 .. 8,192 workgroups: the same 91 us on the query batch)
+    size_t o_cnt = 4, o_cdeg = 8, o_centre = 0, o_first = 0, o_part = 0, ints = 0;
+    void plan(int64_t rows, int n_c, int cap) {
+        first = std::min(cap, GM_HEAVY_FIRST); rt_blocks = std::max(1, grid_for(rows, 2048));
+        o_centre = o_cdeg + (size_t)n_c; o_first = (o_centre + n_c + 1) / 2 * 2; o_part = o_first + 4 * (size_t)first; ints = o_part + 6 * (size_t)rt_blocks;
+    }
+    template <class I> I* pairs(I* base, int o) const { return base + o_first + 2 * (size_t)first * o; }      // hub list of orientation o
+};
 // The finalisation in two halves around its host round trip, so that a caller that builds TWO batches (gm_extract_pair) queues both batches' kernels,
 // waits once, and derives both batches' host-side tables while nothing is left to wait for.
 struct FinalizeCtx {
-    int cap = 0, first = 0, n_count_pairs = 0;
-    char* scratch = nullptr; hipStream_t s = nullptr;            // device side of the round trip (finalize_launch); released by finalize_finish or on the way out
-    const int32_t* h_cnt = nullptr; const int32_t* h_first[2] = {nullptr, nullptr};      // hub-row counts; the first (row, degree) pairs of both hub lists
-    const unsigned long long* h_counts = nullptr; const int32_t* h_cdeg = nullptr; const int32_t* h_centre = nullptr;
+    int cap = 0; FinalScratch lay;
+    int32_t* scratch = nullptr; hipStream_t s = nullptr;         // device side of the round trip (finalize_launch); released by finalize_finish or on the way out
+    const int32_t* h_scr = nullptr;                              // its downloaded copy
     FinalizeCtx() = default;
     FinalizeCtx(const FinalizeCtx&) = delete;
     FinalizeCtx& operator=(const FinalizeCtx&) = delete;
     ~FinalizeCtx() { if (scratch) gm_dev_free(scratch, s); }
 };
-static int finalize_launch(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCtx& fc);
-static int finalize_finish(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCtx& fc);
-int gm_batch_finalize(gm_batch* b, hipStream_t s, gm_stager& sg) {
-    FinalizeCtx fc;
-    GM_TRY(finalize_launch(b, s, sg, fc));
-    GM_HIP(hipStreamSynchronize(s));
-    return finalize_finish(b, s, sg, fc);
-}
-// several small host tables into ONE region of the batch's slabs (batch_free releases nothing else) with ONE copy through pinned staging; each part
+// several small host tables into ONE region of the batch's slabs (gm_batch_destroy releases nothing else) with ONE copy through pinned staging; each part
 // starts on a 256-byte boundary.  (One hipMemcpyAsync per table before: ~20 of the ~43 copies of a meta-batch build.)
 struct TabPart { int32_t** d; const std::vector<int32_t>* v; };
 static int upload_tables(gm_batch* b, gm_stager& sg, hipStream_t s, std::initializer_list<TabPart> parts) {
@@ -1084,18 +988,24 @@ static int upload_tables(gm_batch* b, gm_stager& sg, hipStream_t s, std::initial
     for (const TabPart& p : parts) { std::copy(p.v->begin(), p.v->end(), h.begin() + o); *p.d = base + o; o += pad(p.v->size()); }
     return sg.upload(base, h);
 }
+// the {set, start, length} spans that cut every set's range [off[t], off[t + 1]) into pieces of `step`: GEMM row tiles, weight-gradient chunks (neither
+// straddles two sets: each set has its own fast weights); set_first [sets + 1]: the first span of every set
+static std::vector<int32_t> set_spans(const std::vector<int32_t>& off, int step, std::vector<int32_t>* set_first = nullptr) {
+    std::vector<int32_t> v;
+    if (set_first) set_first->assign(1, 0);
+    for (int t = 0; t + 1 < (int)off.size(); ++t) {
+        for (int r = off[t]; r < off[t + 1]; r += step) { v.push_back(t); v.push_back(r); v.push_back(std::min(step, off[t + 1] - r)); }
+        if (set_first) set_first->push_back((int32_t)(v.size() / 3));
+    }
+    return v;
+}
+// Launch tables derived from the set layout (weight-gradient chunks are sized by gm_wgrad_chunk_rows), then the device side of the round trip
 static int finalize_launch(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCtx& fc) {
     gm_phase_timer tm("finalize-launch");
-    std::vector<int32_t> sub_set(b->subs), tiles, chunks, set_chunk_off(b->sets + 1, 0);
+    std::vector<int32_t> sub_set(b->subs), set_chunk_off;
     for (int t = 0; t < b->sets; ++t)
         for (int k = b->h_set_sub_off[t]; k < b->h_set_sub_off[t + 1]; ++k) sub_set[k] = t;
-    const int64_t cr = gm_wgrad_chunk_rows(b->h_set_row_off);
-    for (int t = 0; t < b->sets; ++t) {
-        const int r0 = b->h_set_row_off[t], r1 = b->h_set_row_off[t + 1];
-        for (int r = r0; r < r1; r += GM_GEMM_BM) { tiles.push_back(t); tiles.push_back(r); tiles.push_back(std::min(GM_GEMM_BM, r1 - r)); }
-        for (int r = r0; r < r1; r += (int)cr) { chunks.push_back(t); chunks.push_back(r); chunks.push_back(std::min<int>((int)cr, r1 - r)); }
-        set_chunk_off[t + 1] = (int32_t)(chunks.size() / 3);
-    }
+    const std::vector<int32_t> tiles = set_spans(b->h_set_row_off, GM_GEMM_BM), chunks = set_spans(b->h_set_row_off, gm_wgrad_chunk_rows(b->h_set_row_off), &set_chunk_off);
     b->n_tiles = (int32_t)(tiles.size() / 3); b->n_chunks = (int32_t)(chunks.size() / 3);
     GM_TRY(upload_tables(b, sg, s, {{&b->d_sub_set, &sub_set}, {&b->d_tiles, &tiles}, {&b->d_chunks, &chunks}, {&b->d_set_chunk_off, &set_chunk_off}}));
     tm.lap("tables");
@@ -1103,64 +1013,57 @@ static int finalize_launch(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
     // ---- device side, nothing here waits for the host: hub-row lists of both orientations, per-edge tables, the fused launch's row table +
     // counts, centre rows with their in-degrees
     b->heavy_deg = gm_heavy_deg_for(b->rows, b->edges);
-    const int cap = (int)(b->edges / b->heavy_deg + 1);
-    // scratch of the round trip in ONE allocation, ONE memset, ONE download (eight copies before):
-    // ints [4,6) hub-row counts | [8, 8 + n_c) centre in-degrees | n_c local centre ids | 2 x first (row, degree) pairs of the hub lists | k_row_tables' per-workgroup {rows, edges, rows with an out-edge} partials (u64 triples)
+    const int cap = fc.cap = (int)(b->edges / b->heavy_deg + 1);
     const int nc = b->centres; b->n_c = b->subs * nc;
-    const int first = std::min(cap, GM_HEAVY_FIRST);
-    const int rt_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (b->rows + 255) / 256));        // k_row_tables' grid, one {rows, edges, source rows} partial triple per workgroup (512 .. 8,192 workgroups: the same 91 us on the query batch)
-    const size_t o_cdeg = 8, o_centre = o_cdeg + b->n_c, o_first = (o_centre + b->n_c + 1) / 2 * 2, o_part = o_first + 4 * (size_t)first, scr_ints = o_part + 6 * (size_t)rt_blocks;
-    char* scratch = nullptr;
-    GM_TRY(gm_dev_alloc((void**)&scratch, 4 * scr_ints, s));
-    fc.scratch = scratch; fc.s = s;
-    GM_HIP(hipMemsetAsync(scratch, 0, 32, s));
-    unsigned long long* d_counts = (unsigned long long*)((int32_t*)scratch + o_part);
-    int32_t* d_cnt = (int32_t*)scratch + 4;
-    int32_t* d_cdeg = (int32_t*)scratch + o_cdeg;
-    int2* d_first[2] = {(int2*)((int32_t*)scratch + o_first), (int2*)((int32_t*)scratch + o_first) + first};
+    FinalScratch& lay = fc.lay;
+    lay.plan(b->rows, b->n_c, cap);
+    GM_TRY(gm_alloc(&fc.scratch, lay.ints, s));
+    fc.s = s;
+    int32_t* const scr = fc.scratch;
+    GM_HIP(hipMemsetAsync(scr, 0, 32, s));
     for (int o = 0; o < 2; ++o) GM_TRY(gm_balloc(b, &b->d_heavy[o], 2 * (size_t)cap, s));
+    // the weighted kernel of every pair takes the unweighted one's arguments and its weights (w: none on unweighted batches)
     if (b->edges > 0) {
         GM_TRY(gm_balloc(b, &b->d_enorm[0], (size_t)b->edges, s)); GM_TRY(gm_balloc(b, &b->d_enorm[1], (size_t)b->edges, s)); GM_TRY(gm_balloc(b, &b->d_efeat, (size_t)b->edges, s));
-        if (b->weighted) hipLaunchKernelGGL(k_edge_tables_w, dim3((int)std::min<int64_t>(4096, (b->edges + 255) / 256)), dim3(256), 0, s, b->d_indices, b->d_indices_t, (int64_t)b->edges,
-                                            b->d_norm, b->d_feat_row, b->d_ew[0], b->d_ew[1], b->d_enorm[0], b->d_enorm[1], b->d_efeat);
-        else hipLaunchKernelGGL(k_edge_tables, dim3((int)std::min<int64_t>(4096, (b->edges + 255) / 256)), dim3(256), 0, s, b->d_indices, b->d_indices_t, (int64_t)b->edges,
-                           b->d_norm, b->d_feat_row, b->d_enorm[0], b->d_enorm[1], b->d_efeat);
+        auto edge_tables = [&](auto kern, auto... w) {
+            hipLaunchKernelGGL(kern, dim3(grid_for(b->edges, 4096)), dim3(256), 0, s, b->d_indices, b->d_indices_t, (int64_t)b->edges, b->d_norm, b->d_feat_row, w..., b->d_enorm[0], b->d_enorm[1], b->d_efeat);
+        };
+        if (b->weighted) edge_tables(k_edge_tables_w, b->d_ew[0], b->d_ew[1]); else edge_tables(k_edge_tables);
     }
     GM_TRY(gm_balloc(b, &b->d_norm_c, b->rows, s)); GM_TRY(gm_balloc(b, &b->d_norm_src, b->rows, s));
     if (b->rows > 0) {
         int4 *f0 = nullptr, *ff = nullptr, *fd = nullptr;
         GM_TRY(gm_balloc(b, &f0, (size_t)b->rows, s)); GM_TRY(gm_balloc(b, &ff, (size_t)b->rows, s)); GM_TRY(gm_balloc(b, &fd, (size_t)b->rows, s));
         b->d_fuse2 = f0; b->d_fuse2_feat = ff; b->d_dq_tab = fd;
-        if (b->weighted) hipLaunchKernelGGL(k_row_tables<RowW>, dim3(rt_blocks), dim3(256), 0, s, b->d_indptr, b->d_indices, b->d_indptr_t, (int64_t)b->rows, b->d_norm, b->d_feat_row, f0, ff,
-                                            d_counts, b->d_heavy[0], b->d_heavy[1], d_cnt, cap, b->heavy_deg, b->d_norm_c, d_first[0], d_first[1], first, b->d_norm_src, fd, RowW{b->d_ew[0]});
-        else hipLaunchKernelGGL(k_row_tables<>, dim3(rt_blocks), dim3(256), 0, s, b->d_indptr, b->d_indices, b->d_indptr_t, (int64_t)b->rows,
-                           b->d_norm, b->d_feat_row, f0, ff, d_counts, b->d_heavy[0], b->d_heavy[1], d_cnt, cap, b->heavy_deg, b->d_norm_c, d_first[0], d_first[1], first, b->d_norm_src, fd);
+        auto row_tables = [&](auto kern, auto... w) {
+            hipLaunchKernelGGL(kern, dim3(lay.rt_blocks), dim3(256), 0, s, b->d_indptr, b->d_indices, b->d_indptr_t, (int64_t)b->rows, b->d_norm, b->d_feat_row, f0, ff,
+                               (unsigned long long*)(scr + lay.o_part), b->d_heavy[0], b->d_heavy[1], scr + lay.o_cnt, cap, b->heavy_deg, b->d_norm_c, (int2*)lay.pairs(scr, 0),
+                               (int2*)lay.pairs(scr, 1), lay.first, b->d_norm_src, fd, w...);
+        };
+        if (b->weighted) row_tables(k_row_tables<RowW>, RowW{b->d_ew[0]}); else row_tables(k_row_tables<>);
     }
     GM_TRY(gm_balloc(b, &b->d_crow, b->n_c, s)); GM_TRY(gm_balloc(b, &b->d_cnorm, b->n_c, s));
-    hipLaunchKernelGGL(k_centre_rows, dim3((b->n_c + 255) / 256), dim3(256), 0, s, b->d_sub_off, b->d_centre, nc, b->n_c, b->d_indptr, b->d_norm,
-                       b->d_crow, b->d_cnorm, d_cdeg, b->d_norm_c, (int32_t*)scratch + o_centre, (int4*)b->d_dq_tab);
+    hipLaunchKernelGGL(k_centre_rows, dim3((b->n_c + 255) / 256), dim3(256), 0, s, b->d_sub_off, b->d_centre, nc, b->n_c, b->d_indptr, b->d_norm, b->d_crow, b->d_cnorm, scr + lay.o_cdeg, b->d_norm_c, scr + lay.o_centre, (int4*)b->d_dq_tab);
     GM_HIP(hipGetLastError());
     // ---- the one round trip
-    const int32_t* h_scr = sg.download((const int32_t*)scratch, scr_ints);
-    GM_REQUIRE(h_scr, GM_ENOMEM, "finalize: pinned staging failed");
+    fc.h_scr = sg.download((const int32_t*)scr, lay.ints);
+    GM_REQUIRE(fc.h_scr, GM_ENOMEM, "finalize: pinned staging failed");
     tm.lap("launches");
-    fc.cap = cap; fc.first = first;
-    fc.h_cnt = h_scr + 4; fc.h_counts = b->rows > 0 ? (const unsigned long long*)(h_scr + o_part) : nullptr; fc.n_count_pairs = rt_blocks; fc.h_cdeg = h_scr + o_cdeg; fc.h_centre = h_scr + o_centre;
-    fc.h_first[0] = h_scr + o_first; fc.h_first[1] = h_scr + o_first + 2 * (size_t)first;
     return GM_OK;
 }
 static int finalize_finish(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCtx& fc) {      // (the stream has passed finalize_launch's downloads)
     gm_phase_timer tm("finalize-finish");
-    const int cap = fc.cap, first = fc.first, nc = b->centres;
-
-    const int32_t* h_cnt = fc.h_cnt; const unsigned long long* h_counts = fc.h_counts; const int32_t* h_cdeg = fc.h_cdeg;
+    const FinalScratch& lay = fc.lay;
+    const int cap = fc.cap, first = lay.first, nc = b->centres;
+    const int32_t* h_cnt = fc.h_scr + lay.o_cnt; const int32_t* h_cdeg = fc.h_scr + lay.o_cdeg; const int32_t* h_centre = fc.h_scr + lay.o_centre;
     gm_dev_free(fc.scratch, s); fc.scratch = nullptr;
-    if (h_counts) {
+    if (b->rows > 0) {
+        const unsigned long long* h_counts = (const unsigned long long*)(fc.h_scr + lay.o_part);
         unsigned long long nr = 0, ne = 0, ns = 0;
-        for (int k = 0; k < fc.n_count_pairs; ++k) { nr += h_counts[3 * k]; ne += h_counts[3 * k + 1]; ns += h_counts[3 * k + 2]; }
+        for (int k = 0; k < lay.rt_blocks; ++k) { nr += h_counts[3 * k]; ne += h_counts[3 * k + 1]; ns += h_counts[3 * k + 2]; }
         b->unfused_rows = (int64_t)nr; b->unfused_edges = (int64_t)ne; b->n_src = (int64_t)ns;
     }
-    b->h_centre.assign(fc.h_centre, fc.h_centre + b->n_c);
+    b->h_centre.assign(h_centre, h_centre + b->n_c);
     b->sched_win = gm_agg_window(b->rows, b->edges);
     std::vector<int32_t> heavy0, tab0;                       // forward orientation: sorted hub rows and their part table (for the list schedule below)
     for (int o = 0; o < 2; ++o) {
@@ -1168,7 +1071,7 @@ static int finalize_finish(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
         if (b->n_heavy[o] > 0) {         // deterministic order (atomic append order is not)
             const size_t nh = b->n_heavy[o];
             std::vector<int32_t> h(nh), hd(nh);
-            if ((int)nh <= first) { for (size_t k = 0; k < nh; ++k) { h[k] = fc.h_first[o][2 * k]; hd[k] = fc.h_first[o][2 * k + 1]; } }
+            if ((int)nh <= first) { const int32_t* pr = lay.pairs(fc.h_scr, o); for (size_t k = 0; k < nh; ++k) { h[k] = pr[2 * k]; hd[k] = pr[2 * k + 1]; } }
             else {                       // more hub rows than the first fetch carried: one more round trip for this orientation
                 const int32_t* a = sg.download(b->d_heavy[o], nh); const int32_t* d = sg.download(b->d_heavy[o] + cap, nh);
                 GM_REQUIRE(a && d, GM_ENOMEM, "finalize: pinned staging failed");
@@ -1227,41 +1130,34 @@ static int finalize_finish(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
     GM_TRY(gm_alloc(&d_eoff, eoff.size(), s));
     GM_TRY(sg.upload(d_eoff, eoff));
     GM_TRY(gm_balloc(b, &b->d_e1_row, b->n_e1, s)); GM_TRY(gm_balloc(b, &b->d_e1_par, b->n_e1, s)); GM_TRY(gm_balloc(b, &b->d_e1_norm, b->n_e1, s));
-    if (b->weighted) {
-        GM_TRY(gm_balloc(b, &b->d_e1_coef, b->n_e1, s));
-        hipLaunchKernelGGL(k_centre_edges<CentreW>, dim3(b->n_c), dim3(64), 0, s, b->d_crow, d_eoff, b->n_c, b->d_indptr, b->d_indices, b->d_norm,
-                           b->d_e1_row, b->d_e1_par, b->d_e1_norm, CentreW{b->d_ew[0], b->d_e1_coef});
-    } else hipLaunchKernelGGL(k_centre_edges<>, dim3(b->n_c), dim3(64), 0, s, b->d_crow, d_eoff, b->n_c, b->d_indptr, b->d_indices, b->d_norm,
-                       b->d_e1_row, b->d_e1_par, b->d_e1_norm);
+    if (b->weighted) GM_TRY(gm_balloc(b, &b->d_e1_coef, b->n_e1, s));
+    auto centre_edges = [&](auto kern, auto... w) {
+        hipLaunchKernelGGL(kern, dim3(b->n_c), dim3(64), 0, s, b->d_crow, d_eoff, b->n_c, b->d_indptr, b->d_indices, b->d_norm, b->d_e1_row, b->d_e1_par, b->d_e1_norm, w...);
+    };
+    if (b->weighted) centre_edges(k_centre_edges<CentreW>, CentreW{b->d_ew[0], b->d_e1_coef}); else centre_edges(k_centre_edges<>);
     GM_HIP(hipGetLastError());
     if (b->rows > 0 && b->d_norm_c) {
         GM_TRY(gm_balloc(b, &b->d_ect, (size_t)b->edges, s)); GM_TRY(gm_balloc(b, &b->d_norm_e1, (size_t)b->rows, s)); GM_TRY(gm_balloc(b, &b->d_n_e1_rows, 1, s));
-        hipLaunchKernelGGL(k_e1_tables, dim3((int)std::min<int64_t>(4096, (std::max<int64_t>(b->edges, b->rows) + 255) / 256)), dim3(256), 0, s, b->d_indices_t, (int64_t)b->edges,
-                           b->d_norm, b->d_norm_c, (int64_t)b->rows, b->d_ect, b->d_norm_e1, b->d_n_e1_rows);
+        hipLaunchKernelGGL(k_e1_tables, dim3(grid_for(std::max<int64_t>(b->edges, b->rows), 4096)), dim3(256), 0, s, b->d_indices_t, (int64_t)b->edges, b->d_norm, b->d_norm_c, (int64_t)b->rows, b->d_ect, b->d_norm_e1, b->d_n_e1_rows);
         if (b->n_e1 > 0) hipLaunchKernelGGL(k_e1_rows, dim3((b->n_e1 + 255) / 256), dim3(256), 0, s, b->d_e1_row, b->n_e1, b->d_norm_e1, b->d_n_e1_rows);
         GM_HIP(hipGetLastError());
     }
-    std::vector<int32_t> ct, cc, ccoff(b->sets + 1, 0), ec, ecoff(b->sets + 1, 0), c_set_off(b->sets + 1), e_set_off(b->sets + 1);
+    std::vector<int32_t> ccoff, ecoff, c_set_off(b->sets + 1), e_set_off(b->sets + 1);      // per set: its centres, and the in-edges of its centres
     for (int t = 0; t <= b->sets; ++t) { c_set_off[t] = b->h_set_sub_off[t] * nc; e_set_off[t] = eoff[b->h_set_sub_off[t] * nc]; }
-    const int ccr = gm_wgrad_chunk_rows(c_set_off), ecr = gm_wgrad_chunk_rows(e_set_off);
-    for (int t = 0; t < b->sets; ++t) {
-        const int k0 = b->h_set_sub_off[t] * nc, k1 = b->h_set_sub_off[t + 1] * nc;
-        for (int k = k0; k < k1; k += GM_GEMM_BM) { ct.push_back(t); ct.push_back(k); ct.push_back(std::min(GM_GEMM_BM, k1 - k)); }
-        for (int k = k0; k < k1; k += ccr) { cc.push_back(t); cc.push_back(k); cc.push_back(std::min(ccr, k1 - k)); }
-        ccoff[t + 1] = (int32_t)(cc.size() / 3);
-        for (int q = eoff[k0]; q < eoff[k1]; q += ecr) { ec.push_back(t); ec.push_back(q); ec.push_back(std::min(ecr, eoff[k1] - q)); }
-        ecoff[t + 1] = (int32_t)(ec.size() / 3);
-    }
+    const std::vector<int32_t> ct = set_spans(c_set_off, GM_GEMM_BM), cc = set_spans(c_set_off, gm_wgrad_chunk_rows(c_set_off), &ccoff), ec = set_spans(e_set_off, gm_wgrad_chunk_rows(e_set_off), &ecoff);
     b->n_c_tiles = (int32_t)(ct.size() / 3); b->n_c_chunks = (int32_t)(cc.size() / 3); b->n_e1_chunks = (int32_t)(ec.size() / 3);
     GM_TRY(upload_tables(b, sg, s, {{&b->d_c_tiles, &ct}, {&b->d_c_chunks, &cc}, {&b->d_c_set_chunk_off, &ccoff}, {&b->d_e1_chunks, &ec}, {&b->d_e1_set_chunk_off, &ecoff}}));
     gm_dev_free(d_eoff, s);
     return GM_OK;
 }
-
-extern "C" void gm_batch_destroy(gm_batch_t* b) {
-    if (!b) return;
-    batch_free(b);
-    delete b;
+// one batch, or the two of a joint build: every batch's kernels and downloads queued, ONE wait, then the host halves
+static int gm_batch_finalize(gm_batch* const* bs, int n, hipStream_t s, gm_stager& sg, gm_phase_timer* tm = nullptr) {
+    FinalizeCtx fc[2];
+    for (int p = 0; p < n; ++p) GM_TRY(finalize_launch(bs[p], s, sg, fc[p]));
+    GM_HIP(hipStreamSynchronize(s));
+    if (tm) tm->lap("finalize-wait");
+    for (int p = 0; p < n; ++p) GM_TRY(finalize_finish(bs[p], s, sg, fc[p]));
+    return GM_OK;
 }
 
 static int batch_alloc(gm_batch* b, hipStream_t s) {
@@ -1280,39 +1176,89 @@ static int upload_small(gm_batch* b, gm_stager& sg) {
     GM_TRY(sg.upload(b->d_set_row_off, b->h_set_row_off)); GM_TRY(sg.upload(b->d_graph, b->h_graph));
     return GM_OK;
 }
+// a batch under construction: dropped with everything it holds unless the builder releases it to its caller
+struct BatchDrop { void operator()(gm_batch* b) const { gm_batch_destroy(b); } };
+typedef std::unique_ptr<gm_batch, BatchDrop> BatchPtr;
 
 // One build of ONE batch (n_parts = 1) or of the two batches of a meta-batch together (n_parts = 2: seeds = [part 0 | part 1]; gm_extract_pair): the
 // node-set kernel runs over all subgraphs in one launch, so does the fill kernel (k_fill serves two batches), the two finalisations queue their kernels
 // back to back and share one host round trip.
 struct ExPart { const int32_t* set_offsets; int32_t n_sets; int32_t n_seeds; };
-static int extract_impl(const gm_store_t* store, const gm_seed_t* seeds, int n_parts, const ExPart* parts, int32_t h, int32_t sample_nodes, uint64_t rng_seed,
-                        int32_t link, const int32_t* nodes_flat, const int64_t* nodes_off, void* stream, gm_batch_t** outs) {
-    GM_REQUIRE(outs && (n_parts == 1 || n_parts == 2), GM_EINVAL, "extract: out is NULL");
-    for (int p = 0; p < n_parts; ++p) outs[p] = nullptr;
-    gm_phase_timer tm("extract");
+// What the two extraction kernels are launched with, decided once per build.  gpath: the bitmap pair of the store's largest graph does not fit the LDS
+// (beyond ~650k nodes) and lives in a per-workgroup slab of HBM.  p16: 16-bit prefix words wherever a subgraph stays below 65,536 nodes
+// (GM_EXTRACT_PREF16=0: 32-bit as before).  needx: the BFS keeps its `expanded` bitmap from three hops on (reference pairs stop at two whatever h says).
+struct ExPlan { bool gpath, p16, needx, sym; int Wmax; size_t Wp; int64_t cap; size_t lds_a, lds_b; };      // Wp: words of the prefix region; lds_a / lds_b: dynamic LDS of k_nodes / k_fill
+static ExPlan ex_plan(const gm_store* store, int64_t cap, bool given, int link, int h) {
+    ExPlan pl;
+    pl.cap = cap; pl.sym = link == GM_LINK_SYMMETRIC;
+    pl.Wmax = (int)((store->max_nodes + 31) >> 5);
+    const size_t W = (size_t)pl.Wmax;
+    pl.gpath = sizeof(uint32_t) * (2 * W + EX_BLOCK + 256 + 16) > 160 * 1024;
+    pl.p16 = !pl.gpath && cap < 65536 && gm_knob().extract_pref16;
+    pl.needx = !given && link != 1 && h >= 3;
+    pl.Wp = pl.p16 ? (W + 1) / 2 : W;
+    pl.lds_a = sizeof(uint32_t) * ((pl.gpath ? 0 : W + ((pl.p16 && !pl.needx) ? pl.Wp : W)) + EX_BLOCK + 256 + 16);
+    pl.lds_b = sizeof(uint32_t) * ((pl.gpath ? 0 : W + pl.Wp) + EX_BLOCK + 16);
+    return pl;
+}
+// The instantiations a plan takes: k_nodes in four shapes (LDS with 32-bit prefix words; LDS with 16-bit ones with / without the `expanded` bitmap; global
+// bitmap), each with its symmetric-pair twin; k_fill by bitmap home and prefix width, fill_w for weighted stores (the same walk, the weights written
+// beside the indices).  The LDS kernels may need more than the default dynamic LDS (gm_func_full_lds before their launch).
+struct ExKernels { decltype(&k_nodes<false>) nodes; decltype(&k_fill<false>) fill; decltype(&k_fill<false, false, FillW>) fill_w; };
+static ExKernels ex_kernels(const ExPlan& pl) {
+    ExKernels k;
+    if (!pl.gpath) {
+        if (!pl.sym) { if (!pl.p16) k.nodes = k_nodes<false>; else if (pl.needx) k.nodes = k_nodes<false, true, true>; else k.nodes = k_nodes<false, true, false>; }
+        else { if (!pl.p16) k.nodes = k_nodes<false, false, true, true>; else if (pl.needx) k.nodes = k_nodes<false, true, true, true>; else k.nodes = k_nodes<false, true, false, true>; }
+        if (!pl.p16) k.fill = k_fill<false>; else k.fill = k_fill<false, true>;
+        if (!pl.p16) k.fill_w = k_fill<false, false, FillW>; else k.fill_w = k_fill<false, true, FillW>;
+    } else {
+        if (pl.sym) k.nodes = k_nodes<true, false, true, true>; else k.nodes = k_nodes<true>;
+        k.fill_w = k_fill<true, false, FillW>; k.fill = k_fill<true>;
+    }
+    return k;
+}
+// One build: arguments, what the phases hand on, what it owns.  Leaving the scope frees the device scratch on the build's stream (behind every kernel that reads it), then drops the batches not released to the caller
+struct ExBuild {
+    const gm_store* store; const gm_seed_t* seeds; int n_parts; const ExPart* parts; int32_t n_seeds, split;      // seeds [0, split): part 0
+    int32_t h, sample_nodes, link; uint64_t rng_seed;            // link: 0 node seeds, 1 reference pairs (h ignored), GM_LINK_SYMMETRIC: h hops around both endpoints; past the plan everything asks "two centres?" (link != 0)
+    const int32_t* nodes_flat; const int64_t* nodes_off;         // given node lists (gm_batch_from_nodes), else NULL
+    hipStream_t st; ExPlan pl; ExKernels kern; ExStore S;
+    gm_stager sg;                                                // pinned staging: the build makes TWO host round trips (subgraph sizes, finalisation)
+    BatchPtr bs[2];
+    gm_seed_t* d_seeds = nullptr; int32_t *d_nodes = nullptr, *d_degi = nullptr, *d_dego = nullptr, *d_nsub = nullptr, *d_esub = nullptr;
+    int32_t* d_given = nullptr; int64_t* d_given_off = nullptr; uint32_t* d_gbits = nullptr;      // device copy of the given node lists; bitmap slabs of the global path
+    int32_t* d_eoff = nullptr; const int32_t* d_order = nullptr;                                  // the subgraphs' edge offsets per batch, and behind them k_fill's workgroup order (NULL: as seeded)
+    const int32_t* nsub = nullptr; const int32_t* esub = nullptr; FillOut fo[2] = {};             // nodes / edges of every subgraph, on the host after phase A; k_fill's outputs per batch
+    explicit ExBuild(hipStream_t s) : st(s), sg(s) {}
+    ~ExBuild() { for (void* p : {(void*)d_gbits, (void*)d_seeds, (void*)d_nodes, (void*)d_degi, (void*)d_dego, (void*)d_nsub, (void*)d_esub, (void*)d_given, (void*)d_given_off, (void*)d_eoff}) gm_dev_free(p, st); }
+};
+
+// Arguments and seeds; *cap_out: the rows a subgraph can have (the stride of the per-subgraph scratch)
+static int ex_validate(ExBuild& x, int64_t* cap_out) {
+    const gm_store* store = x.store; const gm_seed_t* seeds = x.seeds; const int32_t* nodes_flat = x.nodes_flat; const int64_t* nodes_off = x.nodes_off;
     GM_REQUIRE(store && seeds, GM_EINVAL, "extract: bad arguments");
-    int32_t n_seeds = 0;
-    for (int p = 0; p < n_parts; ++p) {
-        const ExPart& q = parts[p];
+    x.n_seeds = 0;
+    for (int p = 0; p < x.n_parts; ++p) {
+        const ExPart& q = x.parts[p];
         GM_REQUIRE(q.set_offsets && q.n_seeds >= 1 && q.n_sets >= 1, GM_EINVAL, "extract: bad arguments");
         GM_REQUIRE(q.set_offsets[0] == 0 && q.set_offsets[q.n_sets] == q.n_seeds, GM_EINVAL, "extract: set_offsets must span [0,n_seeds]");
-        n_seeds += q.n_seeds;
+        x.n_seeds += q.n_seeds;
     }
-    const int32_t split = parts[0].n_seeds;                  // seeds [0, split): part 0
+    x.split = x.parts[0].n_seeds;
     const bool given = nodes_flat != nullptr;
-    GM_REQUIRE(!given || n_parts == 1, GM_EINVAL, "extract: node lists are given per batch");
-    // `link` is a mode from here on: 0 node seeds, 1 pairs as the reference builds them (h ignored), GM_LINK_SYMMETRIC pairs with h hops around both
-    // endpoints.  Given node lists only need to know that there are two centres.  Past k_nodes everything asks "two centres?" (link != 0).
-    if (given) link = link ? 1 : 0;
-    const bool sym = link == GM_LINK_SYMMETRIC;
+    GM_REQUIRE(!given || x.n_parts == 1, GM_EINVAL, "extract: node lists are given per batch");
+    if (given) x.link = x.link ? 1 : 0;                      // given node lists only need to know that there are two centres
+    const int32_t link = x.link, h = x.h;
     if (!given) {
+        const bool sym = link == GM_LINK_SYMMETRIC;
         GM_REQUIRE(link == 0 || link == 1 || sym, GM_EINVAL, "extract: link_pred=%d is not a mode (0 node seeds, 1 reference pairs, %d symmetric pairs)", link, GM_LINK_SYMMETRIC);
         GM_REQUIRE(!sym || (h >= 1 && h <= 3), GM_EINVAL, "extract: h=%d unsupported for symmetric pairs (h in {1,2,3} around both endpoints)", h);
         GM_REQUIRE(link || (h >= 1 && h <= 3), GM_EINVAL, "extract: h=%d unsupported (the reference defines h in {1,2,3}, sdp.py:300-311)", h);
-        GM_REQUIRE(sample_nodes >= 1, GM_EINVAL, "extract: sample_nodes must be >= 1");
+        GM_REQUIRE(x.sample_nodes >= 1, GM_EINVAL, "extract: sample_nodes must be >= 1");
     }
     int64_t cap = 1;
-    for (int k = 0; k < n_seeds; ++k) {
+    for (int k = 0; k < x.n_seeds; ++k) {
         const gm_seed_t& sd = seeds[k];
         GM_REQUIRE(sd.graph >= 0 && sd.graph < store->n_graphs, GM_EINVAL, "extract: seed %d: graph %d out of range", k, sd.graph);
         const int64_t n = store->node_off[sd.graph + 1] - store->node_off[sd.graph];
@@ -1331,108 +1277,60 @@ static int extract_impl(const gm_store_t* store, const gm_seed_t* seeds, int n_p
             cap = std::max<int64_t>(cap, b - a);
         }
     }
-    if (!given) cap = std::min<int64_t>(store->max_nodes, (int64_t)sample_nodes + 2);
-    const int Wmax = (int)((store->max_nodes + 31) >> 5);
-    size_t lds_a = sizeof(uint32_t) * (2 * (size_t)Wmax + EX_BLOCK + 256 + 16);
-    // parent graphs beyond ~650k nodes do not fit the LDS bitmap pair: fall back to a per-workgroup slab in HBM
-    const bool gpath = lds_a > 160 * 1024;
-    if (gpath) lds_a = sizeof(uint32_t) * (EX_BLOCK + 256 + 16);
-    // 16-bit prefix words wherever a subgraph stays below 65,536 nodes (GM_EXTRACT_PREF16=0: 32-bit as before); the BFS keeps its `expanded` bitmap from three hops on
-    const bool p16 = !gpath && cap < 65536 && gm_knob().extract_pref16;
-    const bool needx = !given && link != 1 && h >= 3;          // (reference pairs stop at two hops whatever h says)
-    const size_t Wp = p16 ? ((size_t)Wmax + 1) / 2 : (size_t)Wmax;              // words of the prefix region
-    if (!gpath) lds_a = sizeof(uint32_t) * ((size_t)Wmax + ((p16 && !needx) ? Wp : (size_t)Wmax) + EX_BLOCK + 256 + 16);
-    hipStream_t st = (hipStream_t)stream;
-    GM_TRY(gm_func_full_lds((const void*)k_nodes<false>));
-    GM_TRY(gm_func_full_lds((const void*)k_nodes<false, true, true>));
-    GM_TRY(gm_func_full_lds((const void*)k_nodes<false, true, false>));
-    if (sym) {
-        GM_TRY(gm_func_full_lds((const void*)k_nodes<false, false, true, true>));
-        GM_TRY(gm_func_full_lds((const void*)k_nodes<false, true, true, true>));
-        GM_TRY(gm_func_full_lds((const void*)k_nodes<false, true, false, true>));
+    *cap_out = given ? cap : std::min<int64_t>(store->max_nodes, (int64_t)x.sample_nodes + 2);
+    return GM_OK;
+}
+// Phase A over all subgraphs, and the first round trip: the subgraphs' node and edge counts
+static int ex_nodes(ExBuild& x) {
+    const ExPlan& pl = x.pl; hipStream_t st = x.st; const int32_t n = x.n_seeds;
+    GM_TRY(gm_alloc(&x.d_seeds, n, st));
+    GM_TRY(gm_alloc(&x.d_nodes, (size_t)n * pl.cap, st)); GM_TRY(gm_alloc(&x.d_degi, (size_t)n * pl.cap, st)); GM_TRY(gm_alloc(&x.d_dego, (size_t)n * pl.cap, st));
+    GM_TRY(gm_alloc(&x.d_nsub, n, st)); GM_TRY(gm_alloc(&x.d_esub, n, st));
+    GM_TRY(x.sg.upload(x.d_seeds, x.seeds, sizeof(gm_seed_t) * n));
+    if (x.nodes_flat) {
+        const int64_t tot = x.nodes_off[n];
+        GM_TRY(gm_alloc(&x.d_given, tot, st)); GM_TRY(gm_alloc(&x.d_given_off, n + 1, st));
+        GM_TRY(x.sg.upload(x.d_given, x.nodes_flat, sizeof(int32_t) * tot));
+        GM_TRY(x.sg.upload(x.d_given_off, x.nodes_off, sizeof(int64_t) * (n + 1)));
     }
-    GM_TRY(gm_func_full_lds((const void*)k_fill<false>));
-    GM_TRY(gm_func_full_lds((const void*)k_fill<false, true>));
-    const bool weighted = store->weighted;
-    if (weighted) {
-        GM_TRY(gm_func_full_lds((const void*)k_fill<false, false, FillW>));
-        GM_TRY(gm_func_full_lds((const void*)k_fill<false, true, FillW>));
-    }
-    ExStore S{store->d_node_off, store->d_in_ptr, store->d_in_idx, store->d_out_ptr, store->d_out_idx, store->symmetric ? 1 : 0};
-
-    gm_seed_t* d_seeds = nullptr; int32_t *d_nodes = nullptr, *d_degi = nullptr, *d_dego = nullptr, *d_nsub = nullptr, *d_esub = nullptr;
-    int32_t* d_given = nullptr; int64_t* d_given_off = nullptr;
-    int32_t* d_eoff = nullptr;
-    uint32_t* d_gbits = nullptr;
-    gm_batch* bs[2] = {new gm_batch(), n_parts == 2 ? new gm_batch() : nullptr};
-    int rc = GM_OK;
-    auto cleanup = [&]() {
-        gm_dev_free(d_gbits, st);
-        gm_dev_free(d_seeds, st); gm_dev_free(d_nodes, st); gm_dev_free(d_degi, st); gm_dev_free(d_dego, st);
-        gm_dev_free(d_nsub, st); gm_dev_free(d_esub, st); gm_dev_free(d_given, st); gm_dev_free(d_given_off, st); gm_dev_free(d_eoff, st);
-    };
-    auto drop = [&]() { cleanup(); for (int p = 0; p < n_parts; ++p) { batch_free(bs[p]); delete bs[p]; } };
-#define EX_TRY(x) do { rc = (x); if (rc != GM_OK) { drop(); return rc; } } while (0)
-#define EX_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { gm_set_error("%s: %s", #x, hipGetErrorString(e_)); drop(); return GM_EHIP; } } while (0)
-    tm.lap("validate");
-    gm_stager sg(st);                          // pinned staging: the build makes TWO host round trips (subgraph sizes, finalisation)
-    EX_TRY(gm_alloc(&d_seeds, n_seeds, st));
-    EX_TRY(gm_alloc(&d_nodes, (size_t)n_seeds * cap, st)); EX_TRY(gm_alloc(&d_degi, (size_t)n_seeds * cap, st));
-    EX_TRY(gm_alloc(&d_dego, (size_t)n_seeds * cap, st));
-    EX_TRY(gm_alloc(&d_nsub, n_seeds, st)); EX_TRY(gm_alloc(&d_esub, n_seeds, st));
-    EX_TRY(sg.upload(d_seeds, seeds, sizeof(gm_seed_t) * n_seeds));
-    if (given) {
-        const int64_t tot = nodes_off[n_seeds];
-        EX_TRY(gm_alloc(&d_given, tot, st)); EX_TRY(gm_alloc(&d_given_off, n_seeds + 1, st));
-        EX_TRY(sg.upload(d_given, nodes_flat, sizeof(int32_t) * tot));
-        EX_TRY(sg.upload(d_given_off, nodes_off, sizeof(int64_t) * (n_seeds + 1)));
-    }
-    gm_prof_begin(GM_PROF_EX_NODES, st, n_seeds);
-    if (gpath) EX_TRY(gm_alloc(&d_gbits, (size_t)n_seeds * 2 * Wmax, st));
-    // four launch shapes (global bitmap; LDS with 16-bit prefix words without / with the `expanded` bitmap; LDS, 32-bit), each with its symmetric-pair twin
-    auto launch_nodes = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(n_seeds), dim3(EX_BLOCK), lds_a, st, S, d_seeds, n_seeds, h, sample_nodes, rng_seed, link ? 1 : 0,
-                           d_given, d_given_off, (int)cap, d_nodes, d_degi, d_dego, d_nsub, d_esub, Wmax, d_gbits);
-    };
-    if (gpath) { if (sym) launch_nodes(k_nodes<true, false, true, true>); else launch_nodes(k_nodes<true>); }
-    else if (p16 && !needx) { if (sym) launch_nodes(k_nodes<false, true, false, true>); else launch_nodes(k_nodes<false, true, false>); }
-    else if (p16) { if (sym) launch_nodes(k_nodes<false, true, true, true>); else launch_nodes(k_nodes<false, true, true>); }
-    else { if (sym) launch_nodes(k_nodes<false, false, true, true>); else launch_nodes(k_nodes<false>); }
+    if (!pl.gpath) GM_TRY(gm_func_full_lds((const void*)x.kern.nodes));
+    gm_prof_begin(GM_PROF_EX_NODES, st, n);
+    if (pl.gpath) GM_TRY(gm_alloc(&x.d_gbits, (size_t)n * 2 * pl.Wmax, st));
+    hipLaunchKernelGGL(x.kern.nodes, dim3(n), dim3(EX_BLOCK), pl.lds_a, st, x.S, x.d_seeds, n, x.h, x.sample_nodes, x.rng_seed, x.link ? 1 : 0,
+                       x.d_given, x.d_given_off, (int)pl.cap, x.d_nodes, x.d_degi, x.d_dego, x.d_nsub, x.d_esub, pl.Wmax, x.d_gbits);
     gm_prof_end(GM_PROF_EX_NODES, st);
-    EX_HIP(hipGetLastError());
-    const int32_t* nsub = sg.download(d_nsub, (size_t)n_seeds); const int32_t* esub = sg.download(d_esub, (size_t)n_seeds);
-    if (!nsub || !esub) { gm_set_error("extract: pinned staging failed"); drop(); return GM_ENOMEM; }
-    EX_HIP(hipStreamSynchronize(st));
-
-    tm.lap("k_nodes+sizes");
-    // per batch: host prefix sums, device arrays; the edge offsets of both batches share one upload ([part 0: n0 + 1 | part 1: n1 + 1])
+    GM_HIP(hipGetLastError());
+    x.nsub = x.sg.download(x.d_nsub, (size_t)n); x.esub = x.sg.download(x.d_esub, (size_t)n);
+    GM_REQUIRE(x.nsub && x.esub, GM_ENOMEM, "extract: pinned staging failed");
+    GM_HIP(hipStreamSynchronize(st));
+    return GM_OK;
+}
+// Per batch: host prefix sums, device arrays, k_fill's outputs; the edge offsets of both batches share one upload ([part 0: n0 + 1 | part 1: n1 + 1])
+static int ex_size_parts(ExBuild& x) {
+    const int32_t n_seeds = x.n_seeds; const int32_t* nsub = x.nsub; const int32_t* esub = x.esub;
     std::vector<int32_t> eoff;
-    eoff.reserve(2 * (size_t)n_seeds + n_parts);          // (+ k_fill's workgroup order below: no reallocation under eoff_p)
-    eoff.assign((size_t)n_seeds + n_parts, 0);
-    int32_t* eoff_p[2] = {eoff.data(), eoff.data() + split + 1};
-    FillOut fo[2] = {};
-    for (int p = 0, k0 = 0; p < n_parts; k0 += parts[p].n_seeds, ++p) {
-        gm_batch* b = bs[p]; const ExPart& q = parts[p];
-        b->store = store; b->subs = q.n_seeds; b->sets = q.n_sets; b->centres = link ? 2 : 1; b->stream = st; b->weighted = weighted;
-        batch_features(b, g_hop_labels);
+    eoff.reserve(2 * (size_t)n_seeds + x.n_parts);          // (+ k_fill's workgroup order below: no reallocation under eoff_p)
+    eoff.assign((size_t)n_seeds + x.n_parts, 0);
+    int32_t* eoff_p[2] = {eoff.data(), eoff.data() + x.split + 1};
+    for (int p = 0, k0 = 0; p < x.n_parts; k0 += x.parts[p].n_seeds, ++p) {
+        gm_batch* b = x.bs[p].get(); const ExPart& q = x.parts[p];
+        b->store = x.store; b->subs = q.n_seeds; b->sets = q.n_sets; b->centres = x.link ? 2 : 1; b->stream = x.st; b->weighted = x.store->weighted;
+        batch_features(b, gm_get_hop_labels());
         b->h_sub_off.assign(q.n_seeds + 1, 0); b->h_graph.resize(q.n_seeds);
         int64_t rows = 0, edges = 0;
         for (int k = 0; k < q.n_seeds; ++k) {
             const int gk = k0 + k;
-            if (nsub[gk] <= 0 || esub[gk] < 0) {
-                gm_set_error("extract: subgraph %d failed on device (nodes=%d, edges=%d, cap=%lld)", gk, nsub[gk], esub[gk], (long long)cap);
-                drop(); return GM_ERANGE;
-            }
+            GM_REQUIRE(nsub[gk] > 0 && esub[gk] >= 0, GM_ERANGE, "extract: subgraph %d failed on device (nodes=%d, edges=%d, cap=%lld)", gk, nsub[gk], esub[gk], (long long)x.pl.cap);
             rows += nsub[gk]; edges += esub[gk];
-            if (rows > INT32_MAX - 2 || edges > INT32_MAX - 2) { gm_set_error("extract: batch exceeds 2^31 rows/edges; split the meta-batch"); drop(); return GM_ERANGE; }
-            b->h_sub_off[k + 1] = (int32_t)rows; eoff_p[p][k + 1] = (int32_t)edges; b->h_graph[k] = seeds[gk].graph;
+            GM_REQUIRE(rows <= INT32_MAX - 2 && edges <= INT32_MAX - 2, GM_ERANGE, "extract: batch exceeds 2^31 rows/edges; split the meta-batch");
+            b->h_sub_off[k + 1] = (int32_t)rows; eoff_p[p][k + 1] = (int32_t)edges; b->h_graph[k] = x.seeds[gk].graph;
         }
         b->rows = rows; b->edges = edges;
         b->h_set_sub_off.assign(q.set_offsets, q.set_offsets + q.n_sets + 1);
         b->h_set_row_off.resize(q.n_sets + 1);
         for (int s = 0; s <= q.n_sets; ++s) b->h_set_row_off[s] = b->h_sub_off[q.set_offsets[s]];
-        EX_TRY(batch_alloc(b, st));
-        EX_TRY(upload_small(b, sg));
+        GM_TRY(batch_alloc(b, x.st));
+        GM_TRY(upload_small(b, x.sg));
     }
     // k_fill's workgroup order rides in the same upload: subgraphs by edge count, largest first (64 linear buckets: coarse is enough, and O(n))
     const size_t o_order = eoff.size();
@@ -1447,52 +1345,61 @@ static int extract_impl(const gm_store_t* store, const gm_seed_t* seeds, int n_p
         eoff.resize(o_order + n_seeds);
         for (int k = 0; k < n_seeds; ++k) eoff[o_order + cnt[bucket(esub[k])]++] = k;
     }
-    EX_TRY(gm_alloc(&d_eoff, eoff.size(), st));
-    EX_TRY(sg.upload(d_eoff, eoff));
-    const int32_t* d_order = lpt ? d_eoff + o_order : nullptr;
-    for (int p = 0; p < n_parts; ++p) {
-        gm_batch* b = bs[p];
-        fo[p] = FillOut{b->d_sub_off, d_eoff + (p ? split + 1 : 0), b->d_parent, b->d_feat_row, b->d_norm, b->d_indptr, b->d_indices, b->d_indptr_t, b->d_indices_t, b->d_centre};
+    GM_TRY(gm_alloc(&x.d_eoff, eoff.size(), x.st));
+    GM_TRY(x.sg.upload(x.d_eoff, eoff));
+    x.d_order = lpt ? x.d_eoff + o_order : nullptr;
+    for (int p = 0; p < x.n_parts; ++p) {
+        gm_batch* b = x.bs[p].get();
+        x.fo[p] = FillOut{b->d_sub_off, x.d_eoff + (p ? x.split + 1 : 0), b->d_parent, b->d_feat_row, b->d_norm, b->d_indptr, b->d_indices, b->d_indptr_t, b->d_indices_t, b->d_centre};
     }
-    if (n_parts == 1) fo[1] = fo[0];
-    gm_prof_begin(GM_PROF_EX_FILL, st, n_seeds);
-    if (weighted) {                       // the weighted instantiations: the same walk, the weights written beside the indices
-        const FillW fw{store->d_in_w, store->d_out_w, {bs[0]->d_ew[0], bs[0]->d_ew[1]}, {bs[n_parts - 1]->d_ew[0], bs[n_parts - 1]->d_ew[1]}};
-        const size_t lds_b = gpath ? sizeof(uint32_t) * (EX_BLOCK + 16) : sizeof(uint32_t) * ((size_t)Wmax + Wp + EX_BLOCK + 16);
-        auto launch_fill = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(n_seeds), dim3(EX_BLOCK), lds_b, st, S, d_seeds, n_seeds, link ? 1 : 0, (int)cap, d_nodes, d_degi, d_dego,
-                               fo[0], fo[1], (int)split, Wmax, d_gbits, d_order, fw);
-        };
-        if (gpath) launch_fill(k_fill<true, false, FillW>); else if (p16) launch_fill(k_fill<false, true, FillW>); else launch_fill(k_fill<false, false, FillW>);
-        for (int p = 0; p < n_parts; ++p)
-            if (bs[p]->rows > 0)
-                hipLaunchKernelGGL(k_weighted_norm, dim3((int)std::min<int64_t>(2048, (bs[p]->rows + 255) / 256)), dim3(256), 0, st, bs[p]->d_indptr, bs[p]->d_ew[0], (int64_t)bs[p]->rows, bs[p]->d_norm);
-    } else if (gpath) {
-        hipLaunchKernelGGL(k_fill<true>, dim3(n_seeds), dim3(EX_BLOCK), sizeof(uint32_t) * (EX_BLOCK + 16), st, S, d_seeds, n_seeds, link ? 1 : 0, (int)cap,
-                           d_nodes, d_degi, d_dego, fo[0], fo[1], (int)split, Wmax, d_gbits, d_order);
-    } else {
-        const size_t lds_b = sizeof(uint32_t) * ((size_t)Wmax + Wp + EX_BLOCK + 16);
-        if (p16) hipLaunchKernelGGL((k_fill<false, true>), dim3(n_seeds), dim3(EX_BLOCK), lds_b, st, S, d_seeds, n_seeds, link ? 1 : 0, (int)cap, d_nodes, d_degi, d_dego,
-                                    fo[0], fo[1], (int)split, Wmax, (uint32_t*)nullptr, d_order);
-        else hipLaunchKernelGGL(k_fill<false>, dim3(n_seeds), dim3(EX_BLOCK), lds_b, st, S, d_seeds, n_seeds, link ? 1 : 0, (int)cap, d_nodes, d_degi, d_dego,
-                                fo[0], fo[1], (int)split, Wmax, (uint32_t*)nullptr, d_order);
-    }
+    if (x.n_parts == 1) x.fo[1] = x.fo[0];
+    return GM_OK;
+}
+// Phase B over all subgraphs; weighted stores: the weights ride in k_fill's last argument, and the weighted in-degree's norm of every batch follows
+static int ex_fill(ExBuild& x) {
+    const ExPlan& pl = x.pl; hipStream_t st = x.st; const int32_t n = x.n_seeds;
+    const bool weighted = x.store->weighted;
+    if (!pl.gpath) GM_TRY(gm_func_full_lds(weighted ? (const void*)x.kern.fill_w : (const void*)x.kern.fill));
+    auto launch = [&](auto kern, auto... w) {
+        hipLaunchKernelGGL(kern, dim3(n), dim3(EX_BLOCK), pl.lds_b, st, x.S, x.d_seeds, n, x.link ? 1 : 0, (int)pl.cap, x.d_nodes, x.d_degi, x.d_dego, x.fo[0], x.fo[1], (int)x.split,
+                           pl.Wmax, x.d_gbits, x.d_order, w...);
+    };
+    gm_prof_begin(GM_PROF_EX_FILL, st, n);
+    if (weighted) {
+        gm_batch* b0 = x.bs[0].get(); gm_batch* b1 = x.bs[x.n_parts - 1].get();
+        launch(x.kern.fill_w, FillW{x.store->d_in_w, x.store->d_out_w, {b0->d_ew[0], b0->d_ew[1]}, {b1->d_ew[0], b1->d_ew[1]}});
+        for (int p = 0; p < x.n_parts; ++p)
+            if (gm_batch* b = x.bs[p].get(); b->rows > 0) hipLaunchKernelGGL(k_weighted_norm, dim3(grid_for(b->rows, 2048)), dim3(256), 0, st, b->d_indptr, b->d_ew[0], (int64_t)b->rows, b->d_norm);
+    } else launch(x.kern.fill);
     gm_prof_end(GM_PROF_EX_FILL, st);
-    EX_HIP(hipGetLastError());
+    GM_HIP(hipGetLastError());
+    return GM_OK;
+}
+static int extract_impl(const gm_store_t* store, const gm_seed_t* seeds, int n_parts, const ExPart* parts, int32_t h, int32_t sample_nodes, uint64_t rng_seed,
+                        int32_t link, const int32_t* nodes_flat, const int64_t* nodes_off, void* stream, gm_batch_t** outs) {
+    GM_REQUIRE(outs && (n_parts == 1 || n_parts == 2), GM_EINVAL, "extract: out is NULL");
+    for (int p = 0; p < n_parts; ++p) outs[p] = nullptr;
+    gm_phase_timer tm("extract");
+    ExBuild x((hipStream_t)stream);
+    x.store = store; x.seeds = seeds; x.n_parts = n_parts; x.parts = parts; x.h = h; x.sample_nodes = sample_nodes; x.link = link; x.rng_seed = rng_seed;
+    x.nodes_flat = nodes_flat; x.nodes_off = nodes_off;
+    int64_t cap = 1;
+    GM_TRY(ex_validate(x, &cap));
+    x.pl = ex_plan(store, cap, nodes_flat != nullptr, x.link, h); x.kern = ex_kernels(x.pl);
+    x.S = ExStore{store->d_node_off, store->d_in_ptr, store->d_in_idx, store->d_out_ptr, store->d_out_idx, store->symmetric ? 1 : 0};
+    for (int p = 0; p < n_parts; ++p) x.bs[p].reset(new gm_batch());
+    tm.lap("validate");
+    GM_TRY(ex_nodes(x));
+    tm.lap("k_nodes+sizes");
+    GM_TRY(ex_size_parts(x));
+    GM_TRY(ex_fill(x));
     tm.lap("alloc+k_fill");
-    // finalisation: both batches' kernels and downloads queued, ONE wait, then the host halves
-    gm_prof_begin(GM_PROF_EX_FINAL, st, 1);
-    FinalizeCtx fc[2];
-    for (int p = 0; p < n_parts; ++p) EX_TRY(finalize_launch(bs[p], st, sg, fc[p]));
-    EX_HIP(hipStreamSynchronize(st));
-    tm.lap("finalize-wait");
-    for (int p = 0; p < n_parts; ++p) EX_TRY(finalize_finish(bs[p], st, sg, fc[p]));
-    gm_prof_end(GM_PROF_EX_FINAL, st);
+    gm_batch* const bs[2] = {x.bs[0].get(), x.bs[1].get()};
+    gm_prof_begin(GM_PROF_EX_FINAL, x.st, 1);
+    GM_TRY(gm_batch_finalize(bs, n_parts, x.st, x.sg, &tm));
+    gm_prof_end(GM_PROF_EX_FINAL, x.st);
     tm.lap("finalize");
-    cleanup();
-#undef EX_TRY
-#undef EX_HIP
-    for (int p = 0; p < n_parts; ++p) outs[p] = bs[p];
+    for (int p = 0; p < n_parts; ++p) outs[p] = x.bs[p].release();
     return GM_OK;
 }
 
@@ -1530,37 +1437,29 @@ extern "C" int gm_batch_concat(const gm_batch_t* const* parts, int32_t n_parts, 
     *out = nullptr;
     GM_REQUIRE(parts && n_parts >= 1, GM_EINVAL, "concat: no parts");
     hipStream_t st = (hipStream_t)stream;
-    gm_batch* b = new gm_batch();
-    b->store = parts[0]->store; b->centres = parts[0]->centres; b->stream = st;
+    const gm_batch* p0 = parts[0];
     int64_t rows = 0, edges = 0, subs = 0, sets = 0;
     for (int p = 0; p < n_parts; ++p) {
-        if (parts[p] && parts[p]->weighted != parts[0]->weighted) {
-            delete b; gm_set_error("concat: part %d is %s but part 0 is %s: weighted and unweighted batches cannot be concatenated", p,
-                                   parts[p]->weighted ? "weighted" : "unweighted", parts[0]->weighted ? "weighted" : "unweighted");
-            return GM_EINVAL;
-        }
-        if (parts[p] && parts[p]->hop_D != parts[0]->hop_D) {
-            delete b; gm_set_error("concat: part %d has hop labels D=%d but part 0 has D=%d: parts must all be labelled with the same D, or all unlabelled", p,
-                                   parts[p]->hop_D, parts[0]->hop_D);
-            return GM_EINVAL;
-        }
-        if (!parts[p] || parts[p]->store != b->store || parts[p]->centres != b->centres) {
-            delete b; gm_set_error("concat: part %d has a different store or centre count", p); return GM_EINVAL;
-        }
-        rows += parts[p]->rows; edges += parts[p]->edges; subs += parts[p]->subs; sets += parts[p]->sets;
+        const gm_batch* q = parts[p];
+        GM_REQUIRE(!(q && p0) || q->weighted == p0->weighted, GM_EINVAL, "concat: part %d is %s but part 0 is %s: weighted and unweighted batches cannot be concatenated", p,
+                   q->weighted ? "weighted" : "unweighted", p0->weighted ? "weighted" : "unweighted");
+        GM_REQUIRE(!(q && p0) || q->hop_D == p0->hop_D, GM_EINVAL, "concat: part %d has hop labels D=%d but part 0 has D=%d: parts must all be labelled with the same D, or all unlabelled", p,
+                   q->hop_D, p0->hop_D);
+        GM_REQUIRE(q && p0 && q->store == p0->store && q->centres == p0->centres, GM_EINVAL, "concat: part %d has a different store or centre count", p);
+        rows += q->rows; edges += q->edges; subs += q->subs; sets += q->sets;
     }
-    if (rows > INT32_MAX - 2 || edges > INT32_MAX - 2) { delete b; gm_set_error("concat: batch exceeds 2^31 rows/edges"); return GM_ERANGE; }
+    GM_REQUIRE(rows <= INT32_MAX - 2 && edges <= INT32_MAX - 2, GM_ERANGE, "concat: batch exceeds 2^31 rows/edges");
+    BatchPtr held(new gm_batch());
+    gm_batch* b = held.get();
+    b->store = p0->store; b->centres = p0->centres; b->stream = st;
     b->rows = rows; b->edges = edges; b->subs = (int32_t)subs; b->sets = (int32_t)sets;
     b->h_sub_off.assign(1, 0); b->h_set_sub_off.assign(1, 0); b->h_set_row_off.assign(1, 0);
-    b->weighted = parts[0]->weighted;
-    batch_features(b, parts[0]->hop_D);      // (labelled parts: the finalisation labels the concatenated subgraphs again -- the same labels, the concatenated table)
-    int rc = batch_alloc(b, st);
-    if (rc != GM_OK) { batch_free(b); delete b; return rc; }
+    b->weighted = p0->weighted;
+    batch_features(b, p0->hop_D);      // (labelled parts: the finalisation labels the concatenated subgraphs again -- the same labels, the concatenated table)
+    GM_TRY(batch_alloc(b, st));
     int64_t r0 = 0, e0 = 0; int32_t s0 = 0;
     auto cpy = [&](int32_t* dst, const int32_t* src, int64_t n, int32_t add) {
-        if (n <= 0) return;
-        const int blocks = (int)std::min<int64_t>(1024, (n + 255) / 256);
-        hipLaunchKernelGGL(k_copy_add, dim3(blocks), dim3(256), 0, st, dst, src, n, add);
+        if (n > 0) hipLaunchKernelGGL(k_copy_add, dim3(grid_for(n, 1024)), dim3(256), 0, st, dst, src, n, add);
     };
     for (int p = 0; p < n_parts; ++p) {
         const gm_batch* q = parts[p];
@@ -1576,95 +1475,22 @@ extern "C" int gm_batch_concat(const gm_batch_t* const* parts, int32_t n_parts, 
         b->h_graph.insert(b->h_graph.end(), q->h_graph.begin(), q->h_graph.end());
         r0 += q->rows; e0 += q->edges; s0 += q->subs;
     }
-    if (hipGetLastError() != hipSuccess) { batch_free(b); delete b; gm_set_error("concat: copy kernel launch failed"); return GM_EHIP; }
+    GM_REQUIRE(hipGetLastError() == hipSuccess, GM_EHIP, "concat: copy kernel launch failed");
     gm_stager sg(st);
-    rc = upload_small(b, sg);
-    if (rc == GM_OK) rc = gm_batch_finalize(b, st, sg);
-    if (rc != GM_OK) { batch_free(b); delete b; return rc; }
-    *out = b;
+    GM_TRY(upload_small(b, sg));
+    GM_TRY(gm_batch_finalize(&b, 1, st, sg));
+    *out = held.release();
     return GM_OK;
-}
-
-extern "C" int gm_batch_dims(const gm_batch_t* b, int64_t* rows, int64_t* edges, int32_t* subs, int32_t* sets, int32_t* centres) {
-    GM_REQUIRE(b, GM_EINVAL, "batch_dims: NULL batch");
-    if (rows) *rows = b->rows; if (edges) *edges = b->edges; if (subs) *subs = b->subs; if (sets) *sets = b->sets;
-    if (centres) *centres = b->centres;
-    return GM_OK;
-}
-
-static int field_ptr(const gm_batch_t* b, int32_t field, void** p, int64_t* bytes) {
-    switch (field) {
-        case GM_F_SUB_OFF: *p = b->d_sub_off; *bytes = 4ll * (b->subs + 1); break;
-        case GM_F_SET_SUB_OFF: *p = b->d_set_sub_off; *bytes = 4ll * (b->sets + 1); break;
-        case GM_F_PARENT: *p = b->d_parent; *bytes = 4ll * b->rows; break;
-        case GM_F_GRAPH: *p = b->d_graph; *bytes = 4ll * b->subs; break;
-        case GM_F_INDPTR: *p = b->d_indptr; *bytes = 4ll * (b->rows + 1); break;
-        case GM_F_INDICES: *p = b->d_indices; *bytes = 4ll * b->edges; break;
-        case GM_F_INDPTR_T: *p = b->d_indptr_t; *bytes = 4ll * (b->rows + 1); break;
-        case GM_F_INDICES_T: *p = b->d_indices_t; *bytes = 4ll * b->edges; break;
-        case GM_F_CENTRE: *p = b->d_centre; *bytes = 4ll * b->subs * b->centres; break;
-        case GM_F_NORM: *p = b->d_norm; *bytes = 4ll * b->rows; break;
-        case GM_F_FEAT_ROW: *p = b->d_store_row; *bytes = 4ll * b->rows; break;
-        case GM_F_HOP:
-            GM_REQUIRE(b->hop_D > 0, GM_EINVAL, "batch field GM_F_HOP: the batch carries no hop labels (built with gm_set_hop_labels(0))");
-            *p = b->d_hop; *bytes = (int64_t)b->rows * b->centres; break;
-        case GM_F_NORM_SRC: *p = b->d_norm_src; *bytes = 4ll * b->rows; break;
-        case GM_F_NORM_CENTRE: *p = b->d_norm_c; *bytes = 4ll * b->rows; break;
-        case GM_F_NORM_E1: *p = b->d_norm_e1; *bytes = 4ll * b->rows; break;
-        case GM_F_EDGE_CENTRE_T: *p = b->d_ect; *bytes = 4ll * b->edges; break;
-        case GM_F_EDGE_W: case GM_F_EDGE_W_T:
-            GM_REQUIRE(b->weighted, GM_EINVAL, "batch field %s: the batch is unweighted (its store was created without edge weights)", field == GM_F_EDGE_W ? "GM_F_EDGE_W" : "GM_F_EDGE_W_T");
-            *p = b->d_ew[field == GM_F_EDGE_W ? 0 : 1]; *bytes = 4ll * b->edges; break;
-        default: gm_set_error("unknown batch field %d", field); return GM_EINVAL;
-    }
-    return GM_OK;
-}
-
-extern "C" int gm_batch_read(const gm_batch_t* b, int32_t field, void* host_dst, int64_t bytes) {
-    GM_REQUIRE(b && host_dst, GM_EINVAL, "batch_read: NULL argument");
-    void* p; int64_t need;
-    GM_TRY(field_ptr(b, field, &p, &need));
-    GM_REQUIRE(bytes >= need, GM_EINVAL, "batch_read: destination holds %lld bytes, field needs %lld", (long long)bytes, (long long)need);
-    if (field == GM_F_CENTRE && (int64_t)b->h_centre.size() * 4 == need) { memcpy(host_dst, b->h_centre.data(), (size_t)need); return GM_OK; }
-    GM_HIP(hipMemcpyAsync(host_dst, p, (size_t)need, hipMemcpyDeviceToHost, b->stream));
-    GM_HIP(hipStreamSynchronize(b->stream));
-    return GM_OK;
-}
-
-extern "C" int32_t gm_batch_weighted(const gm_batch_t* b) { return b && b->weighted ? 1 : 0; }
-
-extern "C" int gm_batch_source_rows(const gm_batch_t* b, int64_t* n_rows) {
-    GM_REQUIRE(b && n_rows, GM_EINVAL, "batch_source_rows: NULL argument");
-    *n_rows = b->n_src;
-    return GM_OK;
-}
-
-extern "C" int gm_batch_e1_source_rows(const gm_batch_t* b, int64_t* n_rows) {
-    GM_REQUIRE(b && n_rows, GM_EINVAL, "batch_e1_source_rows: NULL argument");
-    *n_rows = gm_batch_e1_rows(b, b->stream);
-    return GM_OK;
-}
-
-extern "C" int gm_batch_device_ptr(const gm_batch_t* b, int32_t field, void** dptr) {
-    GM_REQUIRE(b && dptr, GM_EINVAL, "batch_device_ptr: NULL argument");
-    int64_t bytes;
-    return field_ptr(b, field, dptr, &bytes);
 }
 
 int gm_gather_rows(const gm_batch* b, const int32_t* feat_row, int64_t n, int F, float* out, hipStream_t st) {
     if (n <= 0) return GM_OK;          // F: columns copied (feat_dim, or feat_ld for the padded internal model); feat_row: rows of the batch's feature table
-    const int blocks = (int)std::min<int64_t>(256 * 8, (n * F + 255) / 256);
-    hipLaunchKernelGGL(k_gather_rows, dim3(blocks), dim3(256), 0, st, b->feat, (int64_t)b->feat_ld, feat_row, out, n, F);
+    hipLaunchKernelGGL(k_gather_rows, dim3(grid_for(n * F, 256 * 8)), dim3(256), 0, st, b->feat, (int64_t)b->feat_ld, feat_row, out, n, F);
     GM_HIP(hipGetLastError());
     return GM_OK;
 }
 
 extern "C" int gm_gather_features(const gm_batch_t* b, float* x_out, void* stream) {
     GM_REQUIRE(b && x_out, GM_EINVAL, "gather_features: NULL argument");
-    const int F = b->feat_dim;
-    const int64_t total = b->rows * F;
-    const int blocks = (int)std::min<int64_t>(256 * 8, (total + 255) / 256);
-    hipLaunchKernelGGL(k_gather_rows, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b->feat, (int64_t)b->feat_ld, b->d_feat_row, x_out, b->rows, F);
-    GM_HIP(hipGetLastError());
-    return GM_OK;
+    return gm_gather_rows(b, b->d_feat_row, b->rows, b->feat_dim, x_out, (hipStream_t)stream);
 }

@@ -212,8 +212,6 @@ struct gm_batch {
     std::mutex slab_mu;
     mutable hipEvent_t used_ev = nullptr;   // last consumer on ANOTHER stream: the frees wait for it (gm_batch_mark_use)
 };
-struct gm_stager;
-int gm_batch_finalize(gm_batch* b, hipStream_t s, gm_stager& sg);
 int gm_batch_gains(const gm_batch* b, hipStream_t s);
 // n elements of T from the batch's slabs (256-byte aligned; lives until the batch is destroyed)
 int gm_balloc_bytes(gm_batch* b, void** p, size_t bytes, hipStream_t s);
@@ -221,6 +219,9 @@ template <class T> static inline int gm_balloc(gm_batch* b, T** p, size_t n, hip
 // A consumer that ran kernels over the batch on `st` calls this afterwards: gm_batch_destroy then orders its frees behind
 // that work instead of relying on the host having synchronised (deferred read-back, prefetch threads).
 void gm_batch_mark_use(const gm_batch* b, hipStream_t st);
+int gm_batch_wait_build(const gm_batch* b, hipStream_t s);      // orders s behind everything queued on the batch's build stream so far (nothing when s is that stream)
+// feature width of a batch labelled with cap D (gm_set_hop_labels): D + 2 one-hot columns per centre behind the store's features
+static inline int gm_hop_feat_dim(const gm_store* st, int centres, int D) { return st->feat_dim + centres * (D + 2); }
 
 // ---- tuning / debug knobs: every GM_* environment variable is read ONCE, under std::call_once, into this
 // struct (the prefetch thread and the training thread both enter the library); per-device quantities are derived at the call site.

@@ -2390,7 +2390,7 @@ static int readout_tables(const gm_batch* cb, hipStream_t s) {
     tab.insert(tab.end(), multi.begin(), multi.end());
     int32_t* d = nullptr;
     GM_TRY(gm_balloc(b, &d, tab.size() + 4, b->stream));                                   // (the batch's slabs: freed with it, on its own stream)
-    if (s != b->stream) { hipEvent_t e; GM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); GM_HIP(hipEventRecord(e, b->stream)); GM_HIP(hipStreamWaitEvent(s, e, 0)); GM_HIP(hipEventDestroy(e)); }
+    GM_TRY(gm_batch_wait_build(b, s));
     { gm_stager stg(s); GM_TRY(stg.upload(d, tab)); }
     // later callers may come on other streams (two threads sharing the batch; the query streams of a step wait for st anyway): an event behind the upload
     // for them to wait on -- where none can be made, the upload is finished before anybody learns of the tables
