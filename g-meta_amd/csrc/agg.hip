@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <mutex>
 #include "gm_internal.h"
+#include "agg_hub.h"
 
 #define AGG_BLOCK 256
 
@@ -30,14 +31,25 @@ struct AggK {
     const int32_t* rowlist; int64_t n_list;     // optional: the windows walk this (ascending) row list instead of rows 0 .. rows
     int keep_signed;                            // s_out's sign bit = nobody reads this row of `out`: computed, not stored; the scale is the magnitude.  Never read without the flag
 };
-// the row's output scale and whether the row is stored
-__device__ __forceinline__ float agg_out_scale(const AggK& a, const int64_t row, bool& keep) {
-    keep = true;
-    if (!a.s_out) return 1.f;
-    const float so = a.s_out[row];
-    if (!a.keep_signed) return so;
-    keep = !(__float_as_uint(so) >> 31);
-    return fabsf(so);
+// XCD-aware block mapping: hardware block b runs on XCD b % 8; each XCD gets a contiguous range of the nb logical blocks, so that one
+// subgraph's rows (and their gathers) stay in one L2.  First logical block of XCD x (x = GM_NXCD: nb) / logical block of hardware block b
+__host__ __device__ __forceinline__ int agg_xcd_first(const int nb, const int x) {
+    const int q = nb / GM_NXCD, r = nb % GM_NXCD;
+    return x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
+}
+__device__ __forceinline__ int agg_logical_block(const int nb, const int b) { return agg_xcd_first(nb, b % GM_NXCD) + b / GM_NXCD; }
+
+// the row's output scale from its raw s_out value (1 without s_out), and whether the row is stored
+__device__ __forceinline__ float agg_out_scale(const AggK& a, const float raw, bool& keep) {
+    keep = !(a.keep_signed && (__float_as_uint(raw) >> 31));
+    return a.keep_signed ? fabsf(raw) : raw;
+}
+// set of a row: which bias row it takes (few sets: short binary search)
+__device__ __forceinline__ int agg_bias_set(const AggK& a, const int64_t row) {
+    if (!a.bias || !a.bias_stride) return 0;
+    int lo = 0, hi = a.n_sets;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (a.set_row_off[mid] <= row) lo = mid; else hi = mid; }
+    return lo;
 }
 
 // edge e -> (row of x to read, its scale): from the per-edge tables when the launch has them, else through indices / s_in / x_row
@@ -67,24 +79,15 @@ __global__ __launch_bounds__(AGG_BLOCK) void k_agg(AggK a) {
     using V = typename VecT<VEC>::T;
     constexpr int RPW = GM_WAVE / LPR;                 // rows per wave
     constexpr int RPB = RPW * (AGG_BLOCK / GM_WAVE);   // rows per block
-    // XCD-aware mapping: hardware block b runs on XCD b % 8; give each XCD a contiguous range of row
-    // blocks so that one subgraph's rows (and its gathers) stay in one L2.
-    const int nb = a.nblocks, b = blockIdx.x;
-    const int q = nb / GM_NXCD, r = nb % GM_NXCD, xcd = b % GM_NXCD, idx = b / GM_NXCD;
-    const int lb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int lb = agg_logical_block(a.nblocks, blockIdx.x);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane / LPR, l = lane % LPR;
     const int64_t row = (int64_t)lb * RPB + wave * RPW + sub;
     if (row >= a.rows) return;
     const int e0 = a.indptr[row], e1 = a.indptr[row + 1];
     bool keep;
-    const float so = agg_out_scale(a, row, keep);
-    int set = 0;
-    if (a.bias && a.bias_stride) {                      // set of this row (few sets: short binary search)
-        int lo = 0, hi = a.n_sets;
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (a.set_row_off[mid] <= row) lo = mid; else hi = mid; }
-        set = lo;
-    }
+    const float so = agg_out_scale(a, a.s_out ? a.s_out[row] : 1.f, keep);
+    const int set = agg_bias_set(a, row);
     for (int c0 = l * VEC; c0 < a.width; c0 += LPR * VEC) {
         V acc0, acc1; vzero(acc0); vzero(acc1);
         int e = e0;
@@ -122,6 +125,62 @@ __global__ __launch_bounds__(AGG_BLOCK) void k_agg(AggK a) {
     }
 }
 
+// ---- the two pieces the 16-byte kernels (k_agg_win, the hub rows) share: a lane group of LPR lanes owns a row, lane l holds NCH float4 of it
+// (columns l * 4 + c * LPR * 4; xl = x + l * 4).
+// One gather batch over edges [eb, min(eb + VISIT, eend)) (VISIT <= LPR): the group's lanes (gbase: its first lane inside the wave) fetch the edges'
+// sources + scales with one coalesced load each, then MB row loads at a time are issued from registers and enter acc in ascending edge order, one
+// fma each.  Slots past the end re-read the LAST edge's row with weight 0: a row some edge reads is one its producer stored (x may hold unwritten
+// rows -- H_l at rows without an out-edge, T_L outside the centre rows -- and 0 x whatever such a row holds need not be 0).
+template <int LPR, int NCH, int VISIT, int MB>
+__device__ __forceinline__ void agg_gather_batch(const AggK& a, const float* xl, const int eb, const int eend, const int l, const int gbase, float4 (&acc)[NCH]) {
+    int mu = 0; float mw = 0.f;
+    if ((VISIT == LPR || l < VISIT) && eb + l < eend) agg_edge(a, eb + l, mu, mw);
+    const int cnt = min(VISIT, eend - eb);
+    for (int j = 0; j < cnt; j += MB) {
+        float4 v[MB][NCH]; float ww[MB];
+#pragma unroll
+        for (int i = 0; i < MB; ++i) {
+            const int uu = __shfl(mu, gbase + min(j + i, cnt - 1), 64);
+            ww[i] = (j + i < cnt) ? __shfl(mw, gbase + j + i, 64) : 0.f;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) v[i][c] = *reinterpret_cast<const float4*>(xl + (int64_t)uu * a.ldx + c * LPR * 4);
+        }
+#pragma unroll
+        for (int i = 0; i < MB; ++i)
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) vfma(acc[c], v[i][c], ww[i]);
+    }
+}
+// The row epilogue: out[row] = epi(so * acc), so = the row's raw s_out value (1 without s_out).  nt: non-temporal stores
+template <int LPR, int NCH>
+__device__ __forceinline__ void agg_store_row(const AggK& a, const int64_t row, const float so, const int l, const float4 (&acc)[NCH], const bool nt) {
+    bool keep;
+    const float s_ = agg_out_scale(a, so, keep);
+    const float* bp = a.bias ? a.bias + (int64_t)agg_bias_set(a, row) * a.bias_stride + l * 4 : nullptr;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const int64_t at = row * a.width + l * 4 + c * LPR * 4;
+        float4 v = make_float4(acc[c].x * s_, acc[c].y * s_, acc[c].z * s_, acc[c].w * s_);
+        if (bp) { const float4 bb = *reinterpret_cast<const float4*>(bp + c * LPR * 4); v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w; }
+        if (a.relu) { v.x = v.x < 0.f ? 0.f : v.x; v.y = v.y < 0.f ? 0.f : v.y; v.z = v.z < 0.f ? 0.f : v.z; v.w = v.w < 0.f ? 0.f : v.w; }      // NaN propagates like torch relu
+        if (a.mask_b) {
+            const unsigned m = a.mask_b[at >> 2];
+            v.x = (m & 1u) ? v.x : 0.f; v.y = (m & 2u) ? v.y : 0.f; v.z = (m & 4u) ? v.z : 0.f; v.w = (m & 8u) ? v.w : 0.f;
+        } else if (a.mask_h) {
+            const float4 m = *reinterpret_cast<const float4*>(a.mask_h + at);
+            v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
+        }
+        if (a.relu_bits) a.relu_bits[at >> 2] = (uint8_t)((v.x > 0.f) | ((v.y > 0.f) << 1) | ((v.z > 0.f) << 2) | ((v.w > 0.f) << 3));
+        float4* dst = reinterpret_cast<float4*>(a.out + at);
+        if (!keep) {                                    // nobody reads this row: computed, not stored
+        } else if (nt) {
+            typedef float f4v __attribute__((ext_vector_type(4)));
+            const f4v vv = {v.x, v.y, v.z, v.w};
+            __builtin_nontemporal_store(vv, reinterpret_cast<f4v*>(dst));
+        } else *dst = v;
+    }
+}
+
 // One 1024-thread workgroup per heavy row (in-degree > gm_heavy_deg(): hub nodes inside their own neighbourhood, up to
 // ~1000 edges): enough loads in flight on one CU (16 groups x 8 x 1 KiB) to stream the row instead of crawling through it.
 // The 1024/LPR lane groups take interleaved LPR-edge chunks (coalesced index loads, 8 row loads in flight each), the
@@ -142,28 +201,7 @@ __device__ __forceinline__ void agg_heavy_row(const AggK& a, const int g, float*
     float4 acc[NCH];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int eb = e0 + gi * PS; eb < e1; eb += NG * PS) {
-        int mu = 0; float mw = 0.f;
-        if (l < PS && eb + l < e1) agg_edge(a, eb + l, mu, mw);
-        const int cnt = min(PS, e1 - eb);
-        for (int j = 0; j < cnt; j += 8) {
-            float4 v[8][NCH]; float ww[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                // slots past the end re-read the LAST edge's row with weight 0: a row some edge reads is one its producer stored (x may hold unwritten rows -- H_l at
-                // rows without an out-edge, T_L outside the centre rows -- and 0 x whatever such a row holds need not be 0)
-                const int sl = gbase + min(j + i, cnt - 1);
-                const int uu = __shfl(mu, sl, 64);
-                ww[i] = (j + i < cnt) ? __shfl(mw, gbase + j + i, 64) : 0.f;
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) v[i][c] = *reinterpret_cast<const float4*>(xl + (int64_t)uu * a.ldx + c * LPR * 4);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) vfma(acc[c], v[i][c], ww[i]);
-        }
-    }
+    for (int eb = e0 + gi * PS; eb < e1; eb += NG * PS) agg_gather_batch<LPR, NCH, PS, 8>(a, xl, eb, e1, l, gbase, acc);
 #pragma unroll
     for (int c = 0; c < NCH; ++c) *reinterpret_cast<float4*>(&part[(gi * NCH + c) * LPR * 4 + l * 4]) = acc[c];
     __syncthreads();
@@ -176,30 +214,16 @@ __device__ __forceinline__ void agg_heavy_row(const AggK& a, const int g, float*
         }
     }
     if (P > 1) {
-        // Partial row -> scratch with write-through (sc1) 16-byte stores, drained by every wave; one relaxed agent-scope ticket;
-        // only the last block to arrive goes on: one lane's agent-scope acquire, then plain loads of the P partial rows, summed
-        // in part order.  Correct wherever the parts run (the schedule keeps them on one XCD only because that is faster).
-        typedef float f4v __attribute__((ext_vector_type(4)));
+        // partial row -> scratch, ticket, the last block to arrive sums the P partial rows in part order (agg_hub.h)
         if (gi == 0) {
 #pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                float* dst = a.hub_scratch + (int64_t)g * a.hub_ld + l * 4 + c * LPR * 4;
-                const f4v val = {s4[c].x, s4[c].y, s4[c].z, s4[c].w};
-                asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(dst), "v"(val) : "memory");
-            }
+            for (int c = 0; c < NCH; ++c) agg_hub_publish(a.hub_scratch + (int64_t)g * a.hub_ld + l * 4 + c * LPR * 4, s4[c]);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        agg_hub_drain();
         __syncthreads();                                   // also: every read of `part` above is done
         int* ctr = const_cast<int*>(a.hub) + a.n_heavy + 1 + a.hub[a.n_heavy] + h;
         int* flag = reinterpret_cast<int*>(part);
-        if (tid == 0) {
-            const int old = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (old == P - 1) {
-                __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next launch
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            }
-            *flag = (old == P - 1);
-        }
+        if (tid == 0) *flag = agg_hub_arrive(ctr, P);
         __syncthreads();
         if (!*flag || gi != 0) return;
         const float* sc = a.hub_scratch + (int64_t)a.hub[h] * a.hub_ld + l * 4;
@@ -212,34 +236,7 @@ __device__ __forceinline__ void agg_heavy_row(const AggK& a, const int g, float*
             }
         }
     }
-    if (gi != 0) return;
-    bool keep;
-    const float so = agg_out_scale(a, row, keep);
-    const float* bp = nullptr;
-    if (a.bias) {
-        int set = 0;
-        if (a.bias_stride) {
-            int lo = 0, hi = a.n_sets;
-            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (a.set_row_off[mid] <= row) lo = mid; else hi = mid; }
-            set = lo;
-        }
-        bp = a.bias + (int64_t)set * a.bias_stride + l * 4;
-    }
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        float4 v = make_float4(s4[c].x * so, s4[c].y * so, s4[c].z * so, s4[c].w * so);
-        if (bp) { const float4 bb = *reinterpret_cast<const float4*>(bp + c * LPR * 4); v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w; }
-        if (a.relu) { v.x = v.x < 0.f ? 0.f : v.x; v.y = v.y < 0.f ? 0.f : v.y; v.z = v.z < 0.f ? 0.f : v.z; v.w = v.w < 0.f ? 0.f : v.w; }
-        if (a.mask_b) {
-            const unsigned m = a.mask_b[((int64_t)row * a.width + l * 4 + c * LPR * 4) >> 2];
-            v.x = (m & 1u) ? v.x : 0.f; v.y = (m & 2u) ? v.y : 0.f; v.z = (m & 4u) ? v.z : 0.f; v.w = (m & 8u) ? v.w : 0.f;
-        } else if (a.mask_h) {
-            const float4 m = *reinterpret_cast<const float4*>(a.mask_h + (int64_t)row * a.width + l * 4 + c * LPR * 4);
-            v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
-        }
-        if (a.relu_bits) a.relu_bits[((int64_t)row * a.width + l * 4 + c * LPR * 4) >> 2] = (uint8_t)((v.x > 0.f) | ((v.y > 0.f) << 1) | ((v.z > 0.f) << 2) | ((v.w > 0.f) << 3));
-        if (keep) *reinterpret_cast<float4*>(a.out + (int64_t)row * a.width + l * 4 + c * LPR * 4) = v;
-    }
+    if (gi == 0) agg_store_row<LPR, NCH>(a, row, a.s_out ? a.s_out[row] : 1.f, l, s4, false);      // (hub rows: plain stores)
 }
 template <int LPR, int NCH>
 __global__ __launch_bounds__(AGG_HEAVY_BLOCK) void k_agg_heavy(AggK a) {
@@ -254,18 +251,17 @@ __global__ __launch_bounds__(AGG_HEAVY_BLOCK) void k_agg_heavy(AggK a) {
 // per row); then the row loads are issued from register-held addresses (broadcast by ds_bpermute), UNR rows at a
 // time, so up to 2*UNR independent 16-B loads per lane are in flight.  Edges beyond the second (p99 ~ 19) take a
 // conventional loop.  LPR = width/4 lanes own a row (width 256: the whole wave, 1 KiB per access).
-template <int LPR, int NCH, int UNR, int MB>
+template <int LPR, int NCH>
 __global__ __launch_bounds__(AGG_BLOCK) void k_agg_win(AggK a) {
     constexpr int G = GM_WAVE / LPR;           // rows processed side by side
-    const int nb = a.nblocks, b = blockIdx.x;
-    const int q = nb / GM_NXCD, r = nb % GM_NXCD, xcd = b % GM_NXCD, idx = b / GM_NXCD;
-    int lb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    constexpr int UNR = 2;
+    int lb = agg_logical_block(a.nblocks, blockIdx.x);
     if (a.sched) {
         // One launch for everything: the schedule interleaves a 256-thread block per hub row (in-degree > heavy_deg) with the
         // window blocks of the hub's own subgraph, on the XCD that owns them -- the hub gathers ~every row of its subgraph,
         // which the neighbouring window blocks are pulling through that XCD's L2 at that moment.  (As a separate launch the
         // hub rows re-read their subgraphs from HBM: 0.25 % of the rows caused ~40 % of the fetch traffic.)
-        const int e = a.sched[xcd * a.sched_len + idx];
+        const int e = a.sched[(blockIdx.x % GM_NXCD) * a.sched_len + blockIdx.x / GM_NXCD];
         if (e == -1) return;
         if (e < -1) {
             __shared__ __attribute__((aligned(16))) float part[AGG_BLOCK * 4 * NCH];
@@ -324,61 +320,10 @@ __global__ __launch_bounds__(AGG_BLOCK) void k_agg_win(AggK a) {
             if (rdg[k] < 0) continue;
             const int rr_ = t0 + k * G + g;
             const int64_t row = a.rowlist ? (int64_t)rrow[k] : R0 + rr_;
-            // rows with more than two in-edges (p99 ~ 19, hubs up to ~1000): the group's LPR lanes fetch the next LPR
-            // sources + scales with one coalesced load each, then 8 row loads at a time are issued from registers.
+            // rows with more than two in-edges (p99 ~ 19, hubs up to ~1000): LPR edges per batch, 4 row loads at a time
             const int eend = rp0[k] + rdg[k];
-            for (int eb = rp0[k] + 2; eb < eend; eb += LPR) {
-                int mu = 0; float mw = 0.f;
-                if (eb + l < eend) agg_edge(a, eb + l, mu, mw);
-                const int cnt = min(LPR, eend - eb);
-                for (int j = 0; j < cnt; j += MB) {
-                    float4 v[MB][NCH]; float ww[MB];
-#pragma unroll
-                    for (int i = 0; i < MB; ++i) {
-                        const int sl = g * LPR + min((j + i) & (LPR - 1), cnt - 1);      // out-of-range slots re-read the last edge's row (a row its producer stored) with weight 0
-                        const int uu = __shfl(mu, sl, 64);
-                        ww[i] = (j + i < cnt) ? __shfl(mw, g * LPR + ((j + i) & (LPR - 1)), 64) : 0.f;
-#pragma unroll
-                        for (int c = 0; c < NCH; ++c) v[i][c] = *reinterpret_cast<const float4*>(xl + (int64_t)uu * a.ldx + c * LPR * 4);
-                    }
-#pragma unroll
-                    for (int i = 0; i < MB; ++i)
-#pragma unroll
-                        for (int c = 0; c < NCH; ++c) vfma(acc[k][c], v[i][c], ww[i]);
-                }
-            }
-            const float* bp = nullptr;
-            if (a.bias) {
-                int set = 0;
-                if (a.bias_stride) {
-                    int lo = 0, hi = a.n_sets;
-                    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (a.set_row_off[mid] <= row) lo = mid; else hi = mid; }
-                    set = lo;
-                }
-                bp = a.bias + (int64_t)set * a.bias_stride + l * 4;
-            }
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                const float s_ = a.keep_signed ? fabsf(rso[k]) : rso[k];
-                float4 v = make_float4(acc[k][c].x * s_, acc[k][c].y * s_, acc[k][c].z * s_, acc[k][c].w * s_);
-                if (bp) { const float4 bb = *reinterpret_cast<const float4*>(bp + c * LPR * 4); v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w; }
-                if (a.relu) { v.x = v.x < 0.f ? 0.f : v.x; v.y = v.y < 0.f ? 0.f : v.y; v.z = v.z < 0.f ? 0.f : v.z; v.w = v.w < 0.f ? 0.f : v.w; }
-                if (a.mask_b) {
-                    const unsigned m = a.mask_b[(row * a.width + l * 4 + c * LPR * 4) >> 2];
-                    v.x = (m & 1u) ? v.x : 0.f; v.y = (m & 2u) ? v.y : 0.f; v.z = (m & 4u) ? v.z : 0.f; v.w = (m & 8u) ? v.w : 0.f;
-                } else if (a.mask_h) {
-                    const float4 m = *reinterpret_cast<const float4*>(a.mask_h + row * a.width + l * 4 + c * LPR * 4);
-                    v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
-                }
-                if (a.relu_bits) a.relu_bits[(row * a.width + l * 4 + c * LPR * 4) >> 2] = (uint8_t)((v.x > 0.f) | ((v.y > 0.f) << 1) | ((v.z > 0.f) << 2) | ((v.w > 0.f) << 3));
-                float4* dst = reinterpret_cast<float4*>(a.out + row * a.width + l * 4 + c * LPR * 4);
-                if (a.keep_signed && (__float_as_uint(rso[k]) >> 31)) {      // nobody reads this row: computed, not stored
-                } else if (a.nt) {
-                    typedef float f4v __attribute__((ext_vector_type(4)));
-                    f4v vv = {v.x, v.y, v.z, v.w};
-                    __builtin_nontemporal_store(vv, reinterpret_cast<f4v*>(dst));
-                } else *dst = v;
-            }
+            for (int eb = rp0[k] + 2; eb < eend; eb += LPR) agg_gather_batch<LPR, NCH, LPR, 4>(a, xl, eb, eend, l, g * LPR, acc[k]);
+            agg_store_row<LPR, NCH>(a, row, rso[k], l, acc[k], a.nt);
         }
     }
 }
@@ -401,17 +346,16 @@ int gm_agg_schedule_flat(gm_batch* b, int64_t rows, int win, const int32_t* pos,
     const bool split = !tab.empty();
     const int RPB = win * (AGG_BLOCK / GM_WAVE);
     const int nwb = std::max(1, (int)((rows + RPB - 1) / RPB));
-    const int q = nwb / GM_NXCD, r = nwb % GM_NXCD;
     // Two passes over the (ascending) hub rows instead of eight growing lists (this ran on the host between the build's kernels: 110 us per
     // orientation of the 1.14 M-row batch): the hub blocks of every XCD's window range are counted first, which gives the common list length,
     // then the flat [8][len] array is written in place -- runs of window blocks with the hub entries spliced in behind their block.
-    auto x_start = [&](int x) { return x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q; };
+    auto x_start = [&](int x) { return agg_xcd_first(nwb, x); };      // XCD x owns window blocks [x_start(x), x_start(x + 1))
     auto n_entries = [&](int k) { return split ? tab[k + 1] - tab[k] : 1; };
     int extra[GM_NXCD] = {}; int first[GM_NXCD + 1];
     {
         int hk = 0;
         for (int x = 0; x < GM_NXCD; ++x) {
-            const int end = x_start(x) + (x < r ? q + 1 : q);
+            const int end = x_start(x + 1);
             first[x] = hk;
             while (hk < n_heavy && pos[hk] / RPB < end) {
                 GM_REQUIRE(hk == 0 || pos[hk] >= pos[hk - 1], GM_EINVAL, "aggregate schedule: hub-row list is not ascending");
@@ -422,11 +366,11 @@ int gm_agg_schedule_flat(gm_batch* b, int64_t rows, int win, const int32_t* pos,
         GM_REQUIRE(hk == n_heavy, GM_EINVAL, "aggregate schedule: hub-row list is not ascending / out of range");
     }
     size_t len = 0;
-    for (int x = 0; x < GM_NXCD; ++x) len = std::max(len, (size_t)((x < r ? q + 1 : q) + extra[x]));
+    for (int x = 0; x < GM_NXCD; ++x) len = std::max(len, (size_t)(x_start(x + 1) - x_start(x) + extra[x]));
     std::vector<int32_t> flat(GM_NXCD * len);
     for (int x = 0; x < GM_NXCD; ++x) {
         int32_t* o = flat.data() + x * len; int32_t* const o_end = o + len;
-        int wb = x_start(x); const int end = wb + (x < r ? q + 1 : q);
+        int wb = x_start(x); const int end = x_start(x + 1);
         for (int hk = first[x]; hk < first[x + 1]; ++hk) {
             const int hb = pos[hk] / RPB;
             while (wb <= hb) *o++ = wb++;                                  // window blocks up to and including the hub row's
@@ -485,7 +429,7 @@ static void launch_win(const AggK& a0, hipStream_t s, int* launched) {
     int grid = a.nblocks;
     if (a.sched) grid = GM_NXCD * a.sched_len;
     else if (a.n_heavy > 0) hipLaunchKernelGGL((k_agg_heavy<LPR, NCH>), dim3(a.n_heavy), dim3(AGG_HEAVY_BLOCK), 0, s, a);
-    hipLaunchKernelGGL((k_agg_win<LPR, NCH, 2, 4>), dim3(grid), dim3(AGG_BLOCK), 0, s, a);
+    hipLaunchKernelGGL((k_agg_win<LPR, NCH>), dim3(grid), dim3(AGG_BLOCK), 0, s, a);
     if (launched) *launched = GM_AGG_ID_WIN(LPR, NCH) + (a.sched ? GM_AGG_ID_WIN_SCHED + (a.hub ? GM_AGG_ID_WIN_SPLIT : 0) : a.n_heavy > 0 ? GM_AGG_ID_WIN_HEAVY : 0) +
                                 (a.rowlist ? GM_AGG_ID_WIN_LIST : 0);
 }
@@ -498,6 +442,16 @@ static void launch_one(const AggK& a0, hipStream_t s, int* launched) {
     hipLaunchKernelGGL((k_agg<VEC, LPR>), dim3(a.nblocks), dim3(AGG_BLOCK), 0, s, a);
     if (launched) *launched = GM_AGG_ID_ONE(VEC, LPR);
 }
+// the generic kernel with the narrowest lane group (2 .. 64 lanes) that covers the `lanes` lanes a row needs (width / VEC), or the whole wave
+template <int VEC>
+static void launch_generic(const AggK& a, const int lanes, hipStream_t s, int* launched) {
+    if (lanes > 32) launch_one<VEC, 64>(a, s, launched);
+    else if (lanes > 16) launch_one<VEC, 32>(a, s, launched);
+    else if (lanes > 8) launch_one<VEC, 16>(a, s, launched);
+    else if (lanes > 4) launch_one<VEC, 8>(a, s, launched);
+    else if (lanes > 2) launch_one<VEC, 4>(a, s, launched);
+    else launch_one<VEC, 2>(a, s, launched);
+}
 
 // Non-temporal stores of the output from 128 MB of output upwards -- a small output stays in the caches for the GEMM that reads it next
 // (Tissue shape -1.3 %, FirstMM shape -1 % against non-temporal stores at every size); at 146 MB (the support batch at task_num 32, the query batch of a
@@ -506,12 +460,20 @@ static int agg_nt(int64_t rows, int width) { return rows * (int64_t)width * 4 >=
 
 int gm_launch_aggregate(const gm_agg_args& g, hipStream_t s) {
     if (g.rows <= 0) return GM_OK;
-    AggK a{g.indptr, g.indices, g.x, g.x_row, g.ldx, g.s_in, g.s_out, g.mask_h, g.bias, g.bias_stride,
-           g.set_row_off, g.n_sets, g.relu, g.out, g.rows, g.width, 0, g.mask_b, g.relu_bits, g.heavy, g.n_heavy, g.heavy_deg,
-           g.sched, g.sched_len, agg_nt(g.rows, g.width), g.sched ? g.sched_win : 64,
-           g.sched ? g.hub : nullptr, g.sched ? g.hub_scratch : nullptr, g.hub_part, GM_AGG_HUB_LD, g.e_w, g.x_idx, g.skip_on ? g.skip_lo : 1, g.skip_on ? g.skip_hi : 0,
-           g.rowlist, g.n_list, (g.keep_signed && g.s_out) ? 1 : 0};
-    if (g.rowlist) a.win = g.list_win;
+    AggK a{};
+    a.indptr = g.indptr; a.indices = g.indices; a.x = g.x; a.x_row = g.x_row; a.ldx = g.ldx;
+    a.s_in = g.s_in; a.s_out = g.s_out; a.mask_h = g.mask_h; a.bias = g.bias; a.bias_stride = g.bias_stride;
+    a.set_row_off = g.set_row_off; a.n_sets = g.n_sets; a.relu = g.relu; a.out = g.out; a.rows = g.rows; a.width = g.width;      // (nblocks: by the launcher)
+    a.mask_b = g.mask_b; a.relu_bits = g.relu_bits;
+    a.heavy = g.heavy; a.n_heavy = g.n_heavy; a.heavy_deg = g.heavy_deg;
+    a.sched = g.sched; a.sched_len = g.sched_len;
+    a.nt = agg_nt(g.rows, g.width);
+    a.win = g.rowlist ? g.list_win : g.sched ? g.sched_win : 64;
+    a.hub = g.sched ? g.hub : nullptr; a.hub_scratch = g.sched ? g.hub_scratch : nullptr; a.hub_part = g.hub_part; a.hub_ld = GM_AGG_HUB_LD;
+    a.e_w = g.e_w; a.x_idx = g.x_idx;
+    a.skip_lo = g.skip_on ? g.skip_lo : 1; a.skip_hi = g.skip_on ? g.skip_hi : 0;
+    a.rowlist = g.rowlist; a.n_list = g.n_list;
+    a.keep_signed = (g.keep_signed && g.s_out) ? 1 : 0;
     const bool vec4 = (g.width % 4 == 0) && (g.ldx % 4 == 0) && (((uintptr_t)g.x & 15) == 0) && (((uintptr_t)g.out & 15) == 0);
     const bool bias_ok = !g.bias || ((((uintptr_t)g.bias & 15) == 0) && (g.bias_stride % 4 == 0));
     const bool mask_ok = !g.mask_h || (((uintptr_t)g.mask_h & 15) == 0);
@@ -525,23 +487,8 @@ int gm_launch_aggregate(const gm_agg_args& g, hipStream_t s) {
         else if (g.width == 128) launch_win<32, 1>(a, s, g.launched);
         else if (g.width == 256) launch_win<64, 1>(a, s, g.launched);
         else launch_win<64, 2>(a, s, g.launched);
-    } else if (vec4) {
-        const int n4 = g.width / 4;
-        if (n4 > 32) launch_one<4, 64>(a, s, g.launched);
-        else if (n4 > 16) launch_one<4, 32>(a, s, g.launched);
-        else if (n4 > 8) launch_one<4, 16>(a, s, g.launched);
-        else if (n4 > 4) launch_one<4, 8>(a, s, g.launched);
-        else if (n4 > 2) launch_one<4, 4>(a, s, g.launched);
-        else launch_one<4, 2>(a, s, g.launched);
-    } else {
-        const int w = g.width;
-        if (w > 32) launch_one<1, 64>(a, s, g.launched);
-        else if (w > 16) launch_one<1, 32>(a, s, g.launched);
-        else if (w > 8) launch_one<1, 16>(a, s, g.launched);
-        else if (w > 4) launch_one<1, 8>(a, s, g.launched);
-        else if (w > 2) launch_one<1, 4>(a, s, g.launched);
-        else launch_one<1, 2>(a, s, g.launched);
-    }
+    } else if (vec4) launch_generic<4>(a, g.width / 4, s, g.launched);
+    else launch_generic<1>(a, g.width, s, g.launched);
     GM_HIP(hipGetLastError());
     return GM_OK;
 }

@@ -26,6 +26,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "gm_internal.h"
+#include "agg_hub.h"
 
 typedef int as_i4 __attribute__((ext_vector_type(4)));
 
@@ -243,25 +244,12 @@ __global__ __launch_bounds__(AS_WAVES * 64) void k_agg_stream(AggS a) {
         acc = make_float4(0.f, 0.f, 0.f, 0.f);
         run(a.hsu, a.hsw, eb, ee, std::false_type{});
         if (P == 1) { store_row((int64_t)row); continue; }
-        // partial row -> scratch with write-through (sc1) stores, drained; one relaxed agent-scope ticket; the last arriver does ONE agent-scope acquire
-        // and sums the P partial rows in part order (writers and reader share an L2: see above)
-        typedef float f4v __attribute__((ext_vector_type(4)));
-        if (act) {
-            float* dst = a.hub_scratch + (int64_t)g * a.hub_ld + lane * 4;
-            const f4v val = {acc.x, acc.y, acc.z, acc.w};
-            asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(dst), "v"(val) : "memory");
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // partial row -> scratch, ticket, the last arriver sums the P partial rows in part order (agg_hub.h; writers and reader share an L2: see above)
+        if (act) agg_hub_publish(a.hub_scratch + (int64_t)g * a.hub_ld + lane * 4, acc);
+        agg_hub_drain();
         int* ctr = const_cast<int*>(a.hub) + a.n_heavy + 1 + a.n_parts + h;
         int last = 0;
-        if (lane == 0) {
-            const int old = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (old == P - 1) {
-                __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next launch
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                last = 1;
-            }
-        }
+        if (lane == 0) last = agg_hub_arrive(ctr, P);
         last = __builtin_amdgcn_readfirstlane(last);
         if (!last) continue;
         acc = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -355,7 +355,7 @@ struct gm_agg_args {
 // gm_agg_args::launched
 #define GM_AGG_ID_LPR(LPR) ((LPR) == 64 ? 6 : (LPR) == 32 ? 5 : (LPR) == 16 ? 4 : (LPR) == 8 ? 3 : (LPR) == 4 ? 2 : 1)
 #define GM_AGG_ID_ONE(VEC, LPR) (100 + ((VEC) == 4 ? 10 : 0) + GM_AGG_ID_LPR(LPR))      // k_agg<VEC, LPR>: 101 .. 106, 111 .. 116
-#define GM_AGG_ID_WIN(LPR, NCH) (200 + 16 * ((NCH) == 2 ? 3 : GM_AGG_ID_LPR(LPR) - 4))  // k_agg_win<LPR, NCH, 2, 4>: 200, 216, 232, 248, plus the flags below
+#define GM_AGG_ID_WIN(LPR, NCH) (200 + 16 * ((NCH) == 2 ? 3 : GM_AGG_ID_LPR(LPR) - 4))  // k_agg_win<LPR, NCH>: 200, 216, 232, 248, plus the flags below
 #define GM_AGG_ID_WIN_SCHED 1           // hub rows ride in the window launch (block schedule)
 #define GM_AGG_ID_WIN_SPLIT 2           // ... split into parts (arrival ticket, part-order sum)
 #define GM_AGG_ID_WIN_HEAVY 4           // hub rows by a separate k_agg_heavy<LPR, NCH> launch
