@@ -9,6 +9,7 @@ GM_MAX_GCN = 4
 (F_SUB_OFF, F_SET_SUB_OFF, F_PARENT, F_GRAPH, F_INDPTR, F_INDICES, F_INDPTR_T, F_INDICES_T, F_CENTRE, F_NORM,
  F_FEAT_ROW, F_NORM_SRC, F_NORM_CENTRE, F_EDGE_W, F_EDGE_W_T, F_HOP, F_NORM_E1, F_EDGE_CENTRE_T) = range(18)
 LINK_SYMMETRIC = 2      # GM_LINK_SYMMETRIC: the link_pred mode of gm_extract / gm_extract_pair with h hops around both endpoints
+LINK_MASK_TARGET = 4    # GM_LINK_MASK_TARGET: flag OR-ed onto a pair mode -- the subgraph of (i, j) is built without the i-j edges themselves
 
 
 class Seed(C.Structure):
@@ -39,6 +40,7 @@ PROTOTYPES = {
     'gm_set_hop_labels': (None, [i32]),
     'gm_get_hop_labels': (i32, []),
     'gm_batch_hop_labels': (i32, [vp]),
+    'gm_batch_mask_target': (i32, [vp]),
     'gm_batch_concat': (C.c_int, [vp, i32, vp, vp]),
     'gm_batch_destroy': (None, [vp]),
     'gm_batch_prepare_cone': (C.c_int, [vp, i32, vp]),

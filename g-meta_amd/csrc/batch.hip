@@ -154,6 +154,7 @@ extern "C" int gm_batch_read(const gm_batch_t* b, int32_t field, void* host_dst,
 }
 
 extern "C" int32_t gm_batch_weighted(const gm_batch_t* b) { return b && b->weighted ? 1 : 0; }
+extern "C" int32_t gm_batch_mask_target(const gm_batch_t* b) { return b && b->mask_target ? 1 : 0; }
 extern "C" int gm_batch_source_rows(const gm_batch_t* b, int64_t* n_rows) {
     GM_REQUIRE(b && n_rows, GM_EINVAL, "batch_source_rows: NULL argument");
     *n_rows = b->n_src;

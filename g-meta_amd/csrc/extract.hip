@@ -113,16 +113,22 @@ __device__ __forceinline__ int group_sum(int v) {
     for (int o = EX_GL / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-// number of neighbours of v (list ptr/idx) inside the bitmap; the eight lanes of a group call it together (gl = lane within the group)
-template <bool G>
-__device__ __forceinline__ int group_count(const int64_t a, const int64_t b, const int32_t* idx, const uint32_t* seen, int gl) {
+// Target-link masking (GM_LINK_MASK_TARGET): a row drops ONE neighbour id, in its in-list and its out-list alike -- the other centre on the two centre
+// rows (all parallel copies; i == j: the centre's self loops), nothing (-1, no node id) on every other row.  The count pass (k_nodes) and the fill pass
+// (k_fill) take the id from this one function and apply it as `inside && u != excl` in all four walkers: indptr is the scan of the counted degrees and
+// the fill writes at those offsets.  MASK is a compile-time flag of the walkers; without it they are what they were before the flag existed.
+struct ExMask { int on; };      // the LAST argument of the masked instantiations of k_nodes / k_fill, which only they have (see FillW)
+__device__ __forceinline__ int mask_excl(int v, int ci, int cj) { return v == ci ? cj : (v == cj ? ci : -1); }
+// number of neighbours of v (list ptr/idx) inside the bitmap; the eight lanes of a group call it together (gl = lane within the group; excl: per group)
+template <bool G, bool MASK = false>
+__device__ __forceinline__ int group_count(const int64_t a, const int64_t b, const int32_t* idx, const uint32_t* seen, int gl, int excl = -1) {
     int c = 0;
     for (int64_t q = a + gl; __any(q < b); q += EX_INFL * EX_GL) {
         int u[EX_INFL];
 #pragma unroll
         for (int k = 0; k < EX_INFL; ++k) u[k] = q + k * EX_GL < b ? idx[q + k * EX_GL] : -1;
 #pragma unroll
-        for (int k = 0; k < EX_INFL; ++k) if (u[k] >= 0) c += bit_test<G>(seen, u[k]);
+        for (int k = 0; k < EX_INFL; ++k) if (u[k] >= 0 && (!MASK || u[k] != excl)) c += bit_test<G>(seen, u[k]);
     }
     return group_sum(c);
 }
@@ -141,16 +147,16 @@ __device__ __forceinline__ void wave_mark_preds(const ExStore& S, int64_t base, 
         for (int k = 0; k < EX_WINFL; ++k) if (u[k] >= 0) bit_set(seen, u[k]);
     }
 }
-// neighbours of a hub node (list [a, b) of idx) inside the bitmap, per lane (the caller adds the lanes up)
-template <bool G>
-__device__ __forceinline__ int wave_count(const int64_t a, const int64_t b, const int32_t* idx, const uint32_t* seen, int lane) {
+// neighbours of a hub node (list [a, b) of idx) inside the bitmap, per lane (the caller adds the lanes up; excl: wave-uniform)
+template <bool G, bool MASK = false>
+__device__ __forceinline__ int wave_count(const int64_t a, const int64_t b, const int32_t* idx, const uint32_t* seen, int lane, int excl = -1) {
     int c = 0;
     for (int64_t q = a + lane; q < b; q += EX_WINFL * GM_WAVE) {
         int u[EX_WINFL];
 #pragma unroll
         for (int k = 0; k < EX_WINFL; ++k) u[k] = q + k * GM_WAVE < b ? idx[q + k * GM_WAVE] : -1;
 #pragma unroll
-        for (int k = 0; k < EX_WINFL; ++k) if (u[k] >= 0) c += bit_test<G>(seen, u[k]);
+        for (int k = 0; k < EX_WINFL; ++k) if (u[k] >= 0 && (!MASK || u[k] != excl)) c += bit_test<G>(seen, u[k]);
     }
     return c;
 }
@@ -229,11 +235,14 @@ __device__ __forceinline__ void expand_root(const ExStore& S, const int64_t base
 // the third hop on (a hop-2 node is reached through many hop-1 nodes); with two hops it only catches parallel edges of the centre, and without it the
 // region behind `seen` shrinks to the 16-bit prefix words.
 // SYM: pairs in GM_LINK_SYMMETRIC mode -- h hops around BOTH endpoints (link != 0 then); without it a pair is the reference's: i side two hops, j side one.
-template <bool G, bool P16 = false, bool NEEDX = true, bool SYM = false>
+// MArgs: empty, or {ExMask} -- the induced degrees are those without the target link (the node set above them is the unmasked one: BFS, sampling and
+// node list do not look at the flag).  With the empty pack the kernel is k_nodes<G, P16, NEEDX, SYM> argument for argument.
+template <bool G, bool P16 = false, bool NEEDX = true, bool SYM = false, typename... MArgs>
 __global__ __launch_bounds__(EX_BLOCK) void k_nodes(ExStore S, const gm_seed_t* seeds, int n_seeds, int h, int sample_n,
                                                     uint64_t rng_seed, int link, const int32_t* given, const int64_t* given_off,
                                                     int cap, int32_t* nodes_slab, int32_t* degi_slab, int32_t* dego_slab,
-                                                    int32_t* n_sub, int32_t* e_sub, int Wmax, uint32_t* gbits) {
+                                                    int32_t* n_sub, int32_t* e_sub, int Wmax, uint32_t* gbits, MArgs... m_args) {
+    constexpr bool MASK = sizeof...(MArgs) != 0;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t* seen = G ? gbits + (size_t)blockIdx.x * 2 * Wmax : lds;
     static_assert(!(G && P16), "16-bit prefix words live in LDS");
@@ -350,6 +359,8 @@ __global__ __launch_bounds__(EX_BLOCK) void k_nodes(ExStore S, const gm_seed_t* 
         for (int r0 = wave * EX_GROUPS; r0 < ns; r0 += RSTEP, r += RSTEP) {
             int64_t ia = nia, ib = nib, oa = noa, ob = nob;
             const bool have = v1 >= 0;
+            int excl = -1;
+            if constexpr (MASK) excl = mask_excl(v1, ci, cj);      // (v1 < 0: a group without a row, and ci, cj >= 0)
             v1 = v2;
             v2 = r + 2 * RSTEP < ns ? nodes[r + 2 * RSTEP] : -1;
             nia = nib = noa = nob = 0;
@@ -363,8 +374,8 @@ __global__ __launch_bounds__(EX_BLOCK) void k_nodes(ExStore S, const gm_seed_t* 
                     if (slot < EX_BLOCK) { if (gl == 0) big[slot] = r; later = true; ia = ib = oa = ob = 0; }      // (list full: the group walks it itself)
                 }
             }
-            const int ci_ = group_count<G>(ia, ib, S.in_idx, seen, gl);
-            const int co_ = S.sym ? ci_ : group_count<G>(oa, ob, S.out_idx, seen, gl);
+            const int ci_ = group_count<G, MASK>(ia, ib, S.in_idx, seen, gl, excl);
+            const int co_ = S.sym ? ci_ : group_count<G, MASK>(oa, ob, S.out_idx, seen, gl, excl);
             if (have && gl == 0 && !later) { degi[r] = ci_; dego[r] = co_; ein += ci_; eout += co_; }
         }
         __syncthreads();
@@ -372,8 +383,10 @@ __global__ __launch_bounds__(EX_BLOCK) void k_nodes(ExStore S, const gm_seed_t* 
         for (int k = wave; k < nb; k += EX_WAVES) {
             const int r = big[k], v = nodes[r];
             int ci_ = 0, co_ = 0;
-            ci_ = wave_count<G>(S.in_ptr[base + v], S.in_ptr[base + v + 1], S.in_idx, seen, lane);
-            if (!S.sym) co_ = wave_count<G>(S.out_ptr[base + v], S.out_ptr[base + v + 1], S.out_idx, seen, lane);
+            int excl = -1;
+            if constexpr (MASK) excl = mask_excl(v, ci, cj);
+            ci_ = wave_count<G, MASK>(S.in_ptr[base + v], S.in_ptr[base + v + 1], S.in_idx, seen, lane, excl);
+            if (!S.sym) co_ = wave_count<G, MASK>(S.out_ptr[base + v], S.out_ptr[base + v + 1], S.out_idx, seen, lane, excl);
             ci_ = wave_sum(ci_); co_ = S.sym ? ci_ : wave_sum(co_);
             if (lane == 0) { degi[r] = ci_; dego[r] = co_; ein += ci_; eout += co_; }
         }
@@ -397,10 +410,11 @@ __device__ __forceinline__ void scan_degrees(const int32_t* deg, int ns, int32_t
 
 // Ordered compaction of the neighbours of v that are inside the subgraph, remapped to batch rows (out2: optional second copy -- the
 // by-source CSR of a symmetric parent).  WT (weighted stores): the edge's weight wsrc[q] goes to wout / wout2 at the slot its endpoint goes to in out / out2.
-template <bool G, typename PT, bool WT = false>
+// MASK: the neighbour id `excl` is left out (mask_excl; wave-uniform here, per group of eight lanes in group_fill_row) -- the predicate of the count walkers.
+template <bool G, typename PT, bool WT = false, bool MASK = false>
 __device__ __forceinline__ void wave_fill_row(const int64_t* ptr, const int32_t* idx, int64_t base, int v, const uint32_t* seen,
                                               const PT* pref, int row0, int32_t* out, int32_t* out2, int pos, int lane,
-                                              const float* wsrc = nullptr, float* wout = nullptr, float* wout2 = nullptr) {
+                                              const float* wsrc = nullptr, float* wout = nullptr, float* wout2 = nullptr, int excl = -1) {
     const int64_t a = ptr[base + v], b = ptr[base + v + 1];
     const unsigned long long lt = (1ull << lane) - 1ull;
     for (int64_t q = a; q < b; q += EX_WINFL * GM_WAVE) {
@@ -414,7 +428,7 @@ __device__ __forceinline__ void wave_fill_row(const int64_t* ptr, const int32_t*
         }
 #pragma unroll
         for (int k = 0; k < EX_WINFL; ++k) {                     // in list order
-            const int hit = u[k] >= 0 && bit_test<G>(seen, u[k]);
+            const int hit = u[k] >= 0 && (!MASK || u[k] != excl) && bit_test<G>(seen, u[k]);
             const unsigned long long m = __ballot(hit);
             if (hit) {
                 const int x = row0 + bit_rank<G, PT>(seen, pref, u[k]), p = pos + __popcll(m & lt); out[p] = x; if (out2) out2[p] = x;
@@ -425,10 +439,10 @@ __device__ __forceinline__ void wave_fill_row(const int64_t* ptr, const int32_t*
     }
 }
 // The same for one node per group of eight lanes (all lanes of the wave call it; a group without a node passes a == b)
-template <bool G, typename PT, bool WT = false>
+template <bool G, typename PT, bool WT = false, bool MASK = false>
 __device__ __forceinline__ void group_fill_row(const int64_t a, const int64_t b, const int32_t* idx, const uint32_t* seen, const PT* pref, int row0,
                                                int32_t* out, int32_t* out2, int pos, int grp, int gl,
-                                               const float* wsrc = nullptr, float* wout = nullptr, float* wout2 = nullptr) {
+                                               const float* wsrc = nullptr, float* wout = nullptr, float* wout2 = nullptr, int excl = -1) {
     const unsigned lt = (1u << gl) - 1u;
     for (int64_t q = a + gl; __any(q < b); q += EX_INFL * EX_GL) {
         int u[EX_INFL];
@@ -441,7 +455,7 @@ __device__ __forceinline__ void group_fill_row(const int64_t a, const int64_t b,
         }
 #pragma unroll
         for (int k = 0; k < EX_INFL; ++k) {                      // in list order: the k-th batch of eight neighbours after the (k-1)-th
-            const int h = u[k] >= 0 && bit_test<G>(seen, u[k]);
+            const int h = u[k] >= 0 && (!MASK || u[k] != excl) && bit_test<G>(seen, u[k]);
             const unsigned bm = (unsigned)(__ballot(h) >> (grp * EX_GL)) & 0xffu;
             if (h) {
                 const int x = row0 + bit_rank<G, PT>(seen, pref, u[k]), p = pos + __popc(bm & lt); out[p] = x; if (out2) out2[p] = x;
@@ -464,12 +478,15 @@ struct FillOut {
 // indices / indices_t.  They ride in a LAST argument that only the weighted instantiations have, k_fill<G, P16, FillW>: with the empty pack the kernel is
 // k_fill<G, P16> argument for argument, and, WT being a compile-time flag, instruction for instruction (even an empty struct there would move the hidden
 // arguments a kernel reads blockDim from).
+// Masked builds (GM_LINK_MASK_TARGET) add an ExMask to the pack, AHEAD of the FillW where there is one: k_fill<G, P16, ExMask> and k_fill<G, P16, ExMask, FillW>.
 struct FillW { const float* in_w; const float* out_w; float* ew0[2]; float* ew1[2]; };      // ew0 / ew1: d_ew of the batch o0 / o1 fills
+__device__ __forceinline__ const FillW& fill_w_of(const FillW& w) { return w; }
+__device__ __forceinline__ const FillW& fill_w_of(const ExMask&, const FillW& w) { return w; }
 template <bool G, bool P16 = false, typename... WArgs>
 __global__ __launch_bounds__(EX_BLOCK) void k_fill(ExStore S, const gm_seed_t* seeds, int n_seeds, int link, int cap,
                                                    const int32_t* nodes_slab, const int32_t* degi_slab, const int32_t* dego_slab,
                                                    FillOut o0, FillOut o1, int split, int Wmax, uint32_t* gbits, const int32_t* order, WArgs... w_args) {
-    constexpr bool WT = sizeof...(WArgs) != 0;
+    constexpr bool WT = (std::is_same<WArgs, FillW>::value || ...), MASK = (std::is_same<WArgs, ExMask>::value || ...);
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t* seen = G ? gbits + (size_t)blockIdx.x * 2 * Wmax : lds;
     static_assert(!(G && P16), "16-bit prefix words live in LDS");
@@ -526,10 +543,12 @@ __global__ __launch_bounds__(EX_BLOCK) void k_fill(ExStore S, const gm_seed_t* s
         if (tid == 0) *nbig = 0;
         __syncthreads();
         int32_t* ind2 = S.sym ? indices_t : nullptr;
+        [[maybe_unused]] int ci = -1, cj = -1, vrow = -1;      // masked builds only: the two centres, and the node of the row a group is about to walk
+        if constexpr (MASK) { ci = seeds[seed].i; cj = seeds[seed].j; }
         float* ew = nullptr; float* ew_t = nullptr;
         const float* in_w = nullptr; const float* out_w = nullptr;
         if constexpr (WT) {
-            const FillW& fw = (w_args, ...);
+            const FillW& fw = fill_w_of(w_args...);
             in_w = fw.in_w; out_w = fw.out_w; ew = second ? fw.ew1[0] : fw.ew0[0]; ew_t = second ? fw.ew1[1] : fw.ew0[1];
         }
         // node ids two batches ahead, row bounds and output offsets one batch ahead (see k_nodes)
@@ -545,6 +564,7 @@ __global__ __launch_bounds__(EX_BLOCK) void k_fill(ExStore S, const gm_seed_t* s
         for (int r0 = wave * EX_GROUPS; r0 < ns; r0 += RSTEP, r += RSTEP) {
             int64_t ia = nia, ib = nib, oa = noa, ob = nob; const int pi = npi, po = npo;
             const bool have = v1 >= 0;
+            if constexpr (MASK) vrow = v1;                         // (before the shift, as k_nodes; v1 < 0: a group without a row, and ci, cj >= 0)
             v1 = v2;
             v2 = r + 2 * RSTEP < ns ? nodes[r + 2 * RSTEP] : -1;
             nia = nib = noa = nob = 0; npi = npo = 0;
@@ -560,7 +580,16 @@ __global__ __launch_bounds__(EX_BLOCK) void k_fill(ExStore S, const gm_seed_t* s
                     if (slot < EX_BLOCK) { if (gl == 0) big[slot] = r; ia = ib = oa = ob = 0; }      // (list full: the group walks it itself)
                 }
             }
-            if constexpr (WT) {
+            if constexpr (MASK) {                                  // (everything the mask adds is an `if constexpr (MASK)` statement: without it the kernel is the one it was, token for token)
+                const int excl = mask_excl(vrow, ci, cj);
+                if constexpr (WT) {
+                    group_fill_row<G, PT, true, true>(ia, ib, S.in_idx, seen, pref, row0, indices, ind2, pi, grp, gl, in_w, ew, ew_t, excl);
+                    if (!S.sym) group_fill_row<G, PT, true, true>(oa, ob, S.out_idx, seen, pref, row0, indices_t, nullptr, po, grp, gl, out_w, ew_t, nullptr, excl);
+                } else {
+                    group_fill_row<G, PT, false, true>(ia, ib, S.in_idx, seen, pref, row0, indices, ind2, pi, grp, gl, nullptr, nullptr, nullptr, excl);
+                    if (!S.sym) group_fill_row<G, PT, false, true>(oa, ob, S.out_idx, seen, pref, row0, indices_t, nullptr, po, grp, gl, nullptr, nullptr, nullptr, excl);
+                }
+            } else if constexpr (WT) {
                 group_fill_row<G, PT, true>(ia, ib, S.in_idx, seen, pref, row0, indices, ind2, pi, grp, gl, in_w, ew, ew_t);
                 if (!S.sym) group_fill_row<G, PT, true>(oa, ob, S.out_idx, seen, pref, row0, indices_t, nullptr, po, grp, gl, out_w, ew_t, nullptr);
             } else {
@@ -572,7 +601,16 @@ __global__ __launch_bounds__(EX_BLOCK) void k_fill(ExStore S, const gm_seed_t* s
         const int nb = min(*nbig, EX_BLOCK);
         for (int k = wave; k < nb; k += EX_WAVES) {
             const int r = big[k], v = nodes[r];
-            if constexpr (WT) {
+            if constexpr (MASK) {
+                const int excl = mask_excl(v, ci, cj);
+                if constexpr (WT) {
+                    wave_fill_row<G, PT, true, true>(S.in_ptr, S.in_idx, base, v, seen, pref, row0, indices, ind2, indptr[row0 + r], lane, in_w, ew, ew_t, excl);
+                    if (!S.sym) wave_fill_row<G, PT, true, true>(S.out_ptr, S.out_idx, base, v, seen, pref, row0, indices_t, nullptr, indptr_t[row0 + r], lane, out_w, ew_t, nullptr, excl);
+                } else {
+                    wave_fill_row<G, PT, false, true>(S.in_ptr, S.in_idx, base, v, seen, pref, row0, indices, ind2, indptr[row0 + r], lane, nullptr, nullptr, nullptr, excl);
+                    if (!S.sym) wave_fill_row<G, PT, false, true>(S.out_ptr, S.out_idx, base, v, seen, pref, row0, indices_t, nullptr, indptr_t[row0 + r], lane, nullptr, nullptr, nullptr, excl);
+                }
+            } else if constexpr (WT) {
                 wave_fill_row<G, PT, true>(S.in_ptr, S.in_idx, base, v, seen, pref, row0, indices, ind2, indptr[row0 + r], lane, in_w, ew, ew_t);
                 if (!S.sym) wave_fill_row<G, PT, true>(S.out_ptr, S.out_idx, base, v, seen, pref, row0, indices_t, nullptr, indptr_t[row0 + r], lane, out_w, ew_t, nullptr);
             } else {
@@ -1204,9 +1242,15 @@ static ExPlan ex_plan(const gm_store* store, int64_t cap, bool given, int link, 
 // The instantiations a plan takes: k_nodes in four shapes (LDS with 32-bit prefix words; LDS with 16-bit ones with / without the `expanded` bitmap; global
 // bitmap), each with its symmetric-pair twin; k_fill by bitmap home and prefix width, fill_w for weighted stores (the same walk, the weights written
 // beside the indices).  The LDS kernels may need more than the default dynamic LDS (gm_func_full_lds before their launch).
-struct ExKernels { decltype(&k_nodes<false>) nodes; decltype(&k_fill<false>) fill; decltype(&k_fill<false, false, FillW>) fill_w; };
-static ExKernels ex_kernels(const ExPlan& pl) {
-    ExKernels k;
+// Masked builds (GM_LINK_MASK_TARGET) take nodes_m / fill_m / fill_wm: the same shapes with the ExMask argument (ex_kernels_masked, at the end of the file).
+struct ExKernels {
+    decltype(&k_nodes<false>) nodes; decltype(&k_fill<false>) fill; decltype(&k_fill<false, false, FillW>) fill_w;
+    decltype(&k_nodes<false, false, true, false, ExMask>) nodes_m; decltype(&k_fill<false, false, ExMask>) fill_m; decltype(&k_fill<false, false, ExMask, FillW>) fill_wm;
+};
+static void ex_kernels_masked(const ExPlan& pl, ExKernels& k);
+static ExKernels ex_kernels(const ExPlan& pl, bool mask) {
+    ExKernels k = {};
+    if (mask) { ex_kernels_masked(pl, k); return k; }
     if (!pl.gpath) {
         if (!pl.sym) { if (!pl.p16) k.nodes = k_nodes<false>; else if (pl.needx) k.nodes = k_nodes<false, true, true>; else k.nodes = k_nodes<false, true, false>; }
         else { if (!pl.p16) k.nodes = k_nodes<false, false, true, true>; else if (pl.needx) k.nodes = k_nodes<false, true, true, true>; else k.nodes = k_nodes<false, true, false, true>; }
@@ -1222,6 +1266,7 @@ static ExKernels ex_kernels(const ExPlan& pl) {
 struct ExBuild {
     const gm_store* store; const gm_seed_t* seeds; int n_parts; const ExPart* parts; int32_t n_seeds, split;      // seeds [0, split): part 0
     int32_t h, sample_nodes, link; uint64_t rng_seed;            // link: 0 node seeds, 1 reference pairs (h ignored), GM_LINK_SYMMETRIC: h hops around both endpoints; past the plan everything asks "two centres?" (link != 0)
+    bool mask = false;                                           // GM_LINK_MASK_TARGET: ex_validate takes the bit off `link`, which is the pair mode from there on
     const int32_t* nodes_flat; const int64_t* nodes_off;         // given node lists (gm_batch_from_nodes), else NULL
     hipStream_t st; ExPlan pl; ExKernels kern; ExStore S;
     gm_stager sg;                                                // pinned staging: the build makes TWO host round trips (subgraph sizes, finalisation)
@@ -1248,11 +1293,15 @@ static int ex_validate(ExBuild& x, int64_t* cap_out) {
     x.split = x.parts[0].n_seeds;
     const bool given = nodes_flat != nullptr;
     GM_REQUIRE(!given || x.n_parts == 1, GM_EINVAL, "extract: node lists are given per batch");
-    if (given) x.link = x.link ? 1 : 0;                      // given node lists only need to know that there are two centres
+    GM_REQUIRE(x.link != GM_LINK_MASK_TARGET, GM_EINVAL, "extract: link_pred=%d is GM_LINK_MASK_TARGET alone: node seeds have no target link to mask (OR the flag onto a pair mode: 1|%d or %d|%d)",
+               x.link, GM_LINK_MASK_TARGET, GM_LINK_SYMMETRIC, GM_LINK_MASK_TARGET);
+    x.mask = x.link > 0 && (x.link & GM_LINK_MASK_TARGET) != 0;
+    if (given) x.link = (x.link & ~GM_LINK_MASK_TARGET) ? 1 : 0;      // given node lists only need to know that there are two centres (and whether to mask)
+    else if (x.link >= 0 && x.link < 2 * GM_LINK_MASK_TARGET) x.link &= ~GM_LINK_MASK_TARGET;      // the pair mode (anything else fails below as it is)
     const int32_t link = x.link, h = x.h;
     if (!given) {
         const bool sym = link == GM_LINK_SYMMETRIC;
-        GM_REQUIRE(link == 0 || link == 1 || sym, GM_EINVAL, "extract: link_pred=%d is not a mode (0 node seeds, 1 reference pairs, %d symmetric pairs)", link, GM_LINK_SYMMETRIC);
+        GM_REQUIRE(link == 0 || link == 1 || sym, GM_EINVAL, "extract: link_pred=%d is not a mode (0 node seeds, 1 reference pairs, %d symmetric pairs; |%d on a pair mode masks the target link)", link | (x.mask ? GM_LINK_MASK_TARGET : 0), GM_LINK_SYMMETRIC, GM_LINK_MASK_TARGET);
         GM_REQUIRE(!sym || (h >= 1 && h <= 3), GM_EINVAL, "extract: h=%d unsupported for symmetric pairs (h in {1,2,3} around both endpoints)", h);
         GM_REQUIRE(link || (h >= 1 && h <= 3), GM_EINVAL, "extract: h=%d unsupported (the reference defines h in {1,2,3}, sdp.py:300-311)", h);
         GM_REQUIRE(x.sample_nodes >= 1, GM_EINVAL, "extract: sample_nodes must be >= 1");
@@ -1293,11 +1342,14 @@ static int ex_nodes(ExBuild& x) {
         GM_TRY(x.sg.upload(x.d_given, x.nodes_flat, sizeof(int32_t) * tot));
         GM_TRY(x.sg.upload(x.d_given_off, x.nodes_off, sizeof(int64_t) * (n + 1)));
     }
-    if (!pl.gpath) GM_TRY(gm_func_full_lds((const void*)x.kern.nodes));
+    if (!pl.gpath) GM_TRY(gm_func_full_lds(x.mask ? (const void*)x.kern.nodes_m : (const void*)x.kern.nodes));
     gm_prof_begin(GM_PROF_EX_NODES, st, n);
     if (pl.gpath) GM_TRY(gm_alloc(&x.d_gbits, (size_t)n * 2 * pl.Wmax, st));
-    hipLaunchKernelGGL(x.kern.nodes, dim3(n), dim3(EX_BLOCK), pl.lds_a, st, x.S, x.d_seeds, n, x.h, x.sample_nodes, x.rng_seed, x.link ? 1 : 0,
-                       x.d_given, x.d_given_off, (int)pl.cap, x.d_nodes, x.d_degi, x.d_dego, x.d_nsub, x.d_esub, pl.Wmax, x.d_gbits);
+    auto launch = [&](auto kern, auto... m) {
+        hipLaunchKernelGGL(kern, dim3(n), dim3(EX_BLOCK), pl.lds_a, st, x.S, x.d_seeds, n, x.h, x.sample_nodes, x.rng_seed, x.link ? 1 : 0,
+                           x.d_given, x.d_given_off, (int)pl.cap, x.d_nodes, x.d_degi, x.d_dego, x.d_nsub, x.d_esub, pl.Wmax, x.d_gbits, m...);
+    };
+    if (x.mask) launch(x.kern.nodes_m, ExMask{1}); else launch(x.kern.nodes);
     gm_prof_end(GM_PROF_EX_NODES, st);
     GM_HIP(hipGetLastError());
     x.nsub = x.sg.download(x.d_nsub, (size_t)n); x.esub = x.sg.download(x.d_esub, (size_t)n);
@@ -1314,7 +1366,7 @@ static int ex_size_parts(ExBuild& x) {
     int32_t* eoff_p[2] = {eoff.data(), eoff.data() + x.split + 1};
     for (int p = 0, k0 = 0; p < x.n_parts; k0 += x.parts[p].n_seeds, ++p) {
         gm_batch* b = x.bs[p].get(); const ExPart& q = x.parts[p];
-        b->store = x.store; b->subs = q.n_seeds; b->sets = q.n_sets; b->centres = x.link ? 2 : 1; b->stream = x.st; b->weighted = x.store->weighted;
+        b->store = x.store; b->subs = q.n_seeds; b->sets = q.n_sets; b->centres = x.link ? 2 : 1; b->stream = x.st; b->weighted = x.store->weighted; b->mask_target = x.mask;
         batch_features(b, gm_get_hop_labels());
         b->h_sub_off.assign(q.n_seeds + 1, 0); b->h_graph.resize(q.n_seeds);
         int64_t rows = 0, edges = 0;
@@ -1359,7 +1411,7 @@ static int ex_size_parts(ExBuild& x) {
 static int ex_fill(ExBuild& x) {
     const ExPlan& pl = x.pl; hipStream_t st = x.st; const int32_t n = x.n_seeds;
     const bool weighted = x.store->weighted;
-    if (!pl.gpath) GM_TRY(gm_func_full_lds(weighted ? (const void*)x.kern.fill_w : (const void*)x.kern.fill));
+    if (!pl.gpath) GM_TRY(gm_func_full_lds(x.mask ? (weighted ? (const void*)x.kern.fill_wm : (const void*)x.kern.fill_m) : (weighted ? (const void*)x.kern.fill_w : (const void*)x.kern.fill)));
     auto launch = [&](auto kern, auto... w) {
         hipLaunchKernelGGL(kern, dim3(n), dim3(EX_BLOCK), pl.lds_b, st, x.S, x.d_seeds, n, x.link ? 1 : 0, (int)pl.cap, x.d_nodes, x.d_degi, x.d_dego, x.fo[0], x.fo[1], (int)x.split,
                            pl.Wmax, x.d_gbits, x.d_order, w...);
@@ -1367,10 +1419,12 @@ static int ex_fill(ExBuild& x) {
     gm_prof_begin(GM_PROF_EX_FILL, st, n);
     if (weighted) {
         gm_batch* b0 = x.bs[0].get(); gm_batch* b1 = x.bs[x.n_parts - 1].get();
-        launch(x.kern.fill_w, FillW{x.store->d_in_w, x.store->d_out_w, {b0->d_ew[0], b0->d_ew[1]}, {b1->d_ew[0], b1->d_ew[1]}});
+        const FillW fw{x.store->d_in_w, x.store->d_out_w, {b0->d_ew[0], b0->d_ew[1]}, {b1->d_ew[0], b1->d_ew[1]}};
+        if (x.mask) launch(x.kern.fill_wm, ExMask{1}, fw); else launch(x.kern.fill_w, fw);
         for (int p = 0; p < x.n_parts; ++p)
             if (gm_batch* b = x.bs[p].get(); b->rows > 0) hipLaunchKernelGGL(k_weighted_norm, dim3(grid_for(b->rows, 2048)), dim3(256), 0, st, b->d_indptr, b->d_ew[0], (int64_t)b->rows, b->d_norm);
-    } else launch(x.kern.fill);
+    } else if (x.mask) launch(x.kern.fill_m, ExMask{1});
+    else launch(x.kern.fill);
     gm_prof_end(GM_PROF_EX_FILL, st);
     GM_HIP(hipGetLastError());
     return GM_OK;
@@ -1385,7 +1439,7 @@ static int extract_impl(const gm_store_t* store, const gm_seed_t* seeds, int n_p
     x.nodes_flat = nodes_flat; x.nodes_off = nodes_off;
     int64_t cap = 1;
     GM_TRY(ex_validate(x, &cap));
-    x.pl = ex_plan(store, cap, nodes_flat != nullptr, x.link, h); x.kern = ex_kernels(x.pl);
+    x.pl = ex_plan(store, cap, nodes_flat != nullptr, x.link, h); x.kern = ex_kernels(x.pl, x.mask);
     x.S = ExStore{store->d_node_off, store->d_in_ptr, store->d_in_idx, store->d_out_ptr, store->d_out_idx, store->symmetric ? 1 : 0};
     for (int p = 0; p < n_parts; ++p) x.bs[p].reset(new gm_batch());
     tm.lap("validate");
@@ -1445,6 +1499,8 @@ extern "C" int gm_batch_concat(const gm_batch_t* const* parts, int32_t n_parts, 
                    q->weighted ? "weighted" : "unweighted", p0->weighted ? "weighted" : "unweighted");
         GM_REQUIRE(!(q && p0) || q->hop_D == p0->hop_D, GM_EINVAL, "concat: part %d has hop labels D=%d but part 0 has D=%d: parts must all be labelled with the same D, or all unlabelled", p,
                    q->hop_D, p0->hop_D);
+        GM_REQUIRE(!(q && p0) || q->mask_target == p0->mask_target, GM_EINVAL, "concat: part %d is %s but part 0 is %s: parts must all be built with GM_LINK_MASK_TARGET, or all without", p,
+                   q->mask_target ? "target-masked" : "unmasked", p0->mask_target ? "target-masked" : "unmasked");
         GM_REQUIRE(q && p0 && q->store == p0->store && q->centres == p0->centres, GM_EINVAL, "concat: part %d has a different store or centre count", p);
         rows += q->rows; edges += q->edges; subs += q->subs; sets += q->sets;
     }
@@ -1454,7 +1510,7 @@ extern "C" int gm_batch_concat(const gm_batch_t* const* parts, int32_t n_parts, 
     b->store = p0->store; b->centres = p0->centres; b->stream = st;
     b->rows = rows; b->edges = edges; b->subs = (int32_t)subs; b->sets = (int32_t)sets;
     b->h_sub_off.assign(1, 0); b->h_set_sub_off.assign(1, 0); b->h_set_row_off.assign(1, 0);
-    b->weighted = p0->weighted;
+    b->weighted = p0->weighted; b->mask_target = p0->mask_target;
     batch_features(b, p0->hop_D);      // (labelled parts: the finalisation labels the concatenated subgraphs again -- the same labels, the concatenated table)
     GM_TRY(batch_alloc(b, st));
     int64_t r0 = 0, e0 = 0; int32_t s0 = 0;
@@ -1493,4 +1549,19 @@ int gm_gather_rows(const gm_batch* b, const int32_t* feat_row, int64_t n, int F,
 extern "C" int gm_gather_features(const gm_batch_t* b, float* x_out, void* stream) {
     GM_REQUIRE(b && x_out, GM_EINVAL, "gather_features: NULL argument");
     return gm_gather_rows(b, b->d_feat_row, b->rows, b->feat_dim, x_out, (hipStream_t)stream);
+}
+
+// ================================================================================ GM_LINK_MASK_TARGET: the masked instantiations of k_nodes / k_fill
+// Instantiated HERE, behind every kernel a build without the flag launches: those keep their place in the code object (see the ragged-task kernels of
+// model.hip).  Only the reachable shapes: reference pairs and given node lists never keep the `expanded` bitmap beside 16-bit prefix words.
+static void ex_kernels_masked(const ExPlan& pl, ExKernels& k) {
+    if (!pl.gpath) {
+        if (!pl.sym) { if (!pl.p16) k.nodes_m = k_nodes<false, false, true, false, ExMask>; else k.nodes_m = k_nodes<false, true, false, false, ExMask>; }
+        else { if (!pl.p16) k.nodes_m = k_nodes<false, false, true, true, ExMask>; else if (pl.needx) k.nodes_m = k_nodes<false, true, true, true, ExMask>; else k.nodes_m = k_nodes<false, true, false, true, ExMask>; }
+        if (!pl.p16) k.fill_m = k_fill<false, false, ExMask>; else k.fill_m = k_fill<false, true, ExMask>;
+        if (!pl.p16) k.fill_wm = k_fill<false, false, ExMask, FillW>; else k.fill_wm = k_fill<false, true, ExMask, FillW>;
+    } else {
+        if (pl.sym) k.nodes_m = k_nodes<true, false, true, true, ExMask>; else k.nodes_m = k_nodes<true, false, true, false, ExMask>;
+        k.fill_wm = k_fill<true, false, ExMask, FillW>; k.fill_m = k_fill<true, false, ExMask>;
+    }
 }

@@ -115,6 +115,7 @@ struct gm_batch {
     std::vector<int32_t> h_centre;     // host copy, brought by the finalisation's round trip (gm_batch_read serves it without another one)
     float* d_norm = nullptr;           // [rows]
     bool weighted = false;             // cut from a weighted store: d_ew holds the induced edge weights, d_norm the weighted in-degree's norm
+    bool mask_target = false;          // built with GM_LINK_MASK_TARGET: the CSR (and everything derived from it) holds no edge between a subgraph's two centres
     float* d_ew[2] = {nullptr, nullptr};   // [edges] weight of every edge, aligned with d_indices / d_indices_t (weighted batches only)
     // derived launch tables (built by gm_batch_finalize)
     int32_t* d_sub_set = nullptr;      // [subs]  set of each subgraph

@@ -110,11 +110,14 @@ class SubgraphBatch:
     @staticmethod
     def _link_mode(link_pred):
         """gm_extract's link_pred mode: False / 0 node seeds, True / 1 pairs as the reference builds them (h ignored), _lib.LINK_SYMMETRIC (2) pairs
-        with h hops around both endpoints.  Anything else is passed on and refused by the library."""
+        with h hops around both endpoints; _lib.LINK_MASK_TARGET (4) OR-ed onto a pair mode builds every subgraph without the edges between its two
+        centres.  Anything else is passed on and refused by the library."""
         return int(link_pred or 0)
 
     @classmethod
     def extract(cls, store, seeds, set_offsets, h, sample_nodes, rng_seed, link_pred):
+        """link_pred is gm_extract's MODE (_link_mode): target-link masking is the _lib.LINK_MASK_TARGET bit OR-ed onto a pair mode here and in
+        extract_pair -- but a KEYWORD of from_nodes (mask_target=True), whose link_pred is no mode: anything true there means pairs."""
         arr = cls._seed_array(seeds)
         so = np.ascontiguousarray(set_offsets, np.int32)
         out = C.c_void_p()
@@ -129,7 +132,8 @@ class SubgraphBatch:
 
     @classmethod
     def extract_pair(cls, store, seeds_a, set_offsets_a, seeds_b, set_offsets_b, h, sample_nodes, rng_seed, link_pred):
-        """The two batches extract() would return for (seeds_a, set_offsets_a) and (seeds_b, set_offsets_b), from one build (gm_extract_pair)."""
+        """The two batches extract() would return for (seeds_a, set_offsets_a) and (seeds_b, set_offsets_b), from one build (gm_extract_pair).  link_pred is
+        the mode, with the _lib.LINK_MASK_TARGET bit as in extract() (from_nodes takes the mask as a keyword instead)."""
         aa, ab = cls._seed_array(seeds_a), cls._seed_array(seeds_b)
         sa, sb = np.ascontiguousarray(set_offsets_a, np.int32), np.ascontiguousarray(set_offsets_b, np.int32)
         oa, ob = C.c_void_p(), C.c_void_p()
@@ -145,7 +149,12 @@ class SubgraphBatch:
         return out[0], out[1]
 
     @classmethod
-    def from_nodes(cls, store, seeds, set_offsets, node_lists, link_pred):
+    def from_nodes(cls, store, seeds, set_offsets, node_lists, link_pred, mask_target=False):
+        """link_pred: anything true means two centres, as before (here the value is no mode: 5 is "pairs", NOT "pairs, masked" -- unlike extract() and
+        extract_pair(), where the mask is the _lib.LINK_MASK_TARGET bit of the mode).  mask_target: gm_batch_from_nodes gets that bit -- the subgraphs
+        are induced without the edges between their two centres."""
+        if mask_target and not link_pred:
+            raise ValueError('mask_target masks the target link of a pair: node seeds have no target link')
         arr = cls._seed_array(seeds)
         so = np.ascontiguousarray(set_offsets, np.int32)
         lists = [np.unique(np.asarray(x, np.int32)) for x in node_lists]
@@ -153,7 +162,8 @@ class SubgraphBatch:
         off = np.ascontiguousarray(np.cumsum([0] + [len(x) for x in lists]), np.int64)
         out = C.c_void_p()
         _lib.check(_lib.lib().gm_batch_from_nodes(store.handle, _lib.ptr(arr), len(arr), _lib.ptr(so), len(so) - 1, _lib.ptr(flat), _lib.ptr(off),
-                                                  int(bool(link_pred)), _lib.stream_ptr(), C.byref(out)), 'gm_batch_from_nodes')
+                                                  int(bool(link_pred)) | (_lib.LINK_MASK_TARGET if mask_target else 0), _lib.stream_ptr(), C.byref(out)),
+                   'gm_batch_from_nodes')
         return cls(out, store)
 
     @classmethod
@@ -240,6 +250,11 @@ class SubgraphBatch:
         return bool(_lib.lib().gm_batch_weighted(self.handle))
 
     @property
+    def mask_target(self):
+        """True for a batch built with _lib.LINK_MASK_TARGET: no subgraph holds an edge between its two centres (gm_batch_mask_target)."""
+        return bool(_lib.lib().gm_batch_mask_target(self.handle))
+
+    @property
     def hop_labels_cap(self):
         """The label cap D of a hop-labelled batch, 0 for an unlabelled one (gm_batch_hop_labels)."""
         return int(_lib.lib().gm_batch_hop_labels(self.handle))
@@ -284,7 +299,7 @@ class Subgraphs(Dataset):
     {'train': (names, labels)} style dictionaries (names 'g_i' or 'g_i_j', labels as in the CSV)."""
 
     def __init__(self, root, mode, subgraph2label, n_way, k_shot, k_query, batchsz, args, adjs, h, tables=None, verbose=True, sample_mode=None, link_hops=None,
-                 hop_labels=None):
+                 hop_labels=None, mask_target=None):
         self.batchsz, self.n_way, self.k_shot, self.k_query = batchsz, n_way, k_shot, k_query
         # 'device' (default): neighbourhoods above sample_nodes are thinned by the keyed permutation in gm_extract.
         # 'reference': the node sets the REFERENCE would draw for the same global-RNG history (sdp.py:312-314,337-339):
@@ -317,6 +332,13 @@ class Subgraphs(Dataset):
                                  "RNG history of it to replay")
         # what every gm_extract / gm_extract_pair call of this dataset passes as its link_pred mode
         self.link_mode = _lib.LINK_SYMMETRIC if self.link_hops == 'symmetric' else int(self.link_pred_mode)
+        # target-link masking (GM_LINK_MASK_TARGET): every pair's subgraph is built without the edges between its two endpoints -- for graphs that hold the
+        # positive pairs as edges and the negative ones not (the reference's data layout hides the edge by injecting the negatives instead)
+        self.mask_target = bool(int((mask_target if mask_target is not None else getattr(args, 'mask_target', 0)) or 0))
+        if self.mask_target:
+            if not self.link_pred_mode:
+                raise ValueError("mask_target masks the target link of a pair: it needs link_pred_mode='True' (node seeds have no target link)")
+            self.link_mode |= _lib.LINK_MASK_TARGET
         # hop-distance node labels (gm_set_hop_labels): cap D in 1..7, appended to the feature rows of every batch this dataset extracts; 0 / None = off
         self.hop_labels = int((hop_labels if hop_labels is not None else getattr(args, 'hop_labels', 0)) or 0)
         hop_label_width(self.hop_labels, self.link_pred_mode)                 # (ValueError outside 0..7)
@@ -557,8 +579,8 @@ class Subgraphs(Dataset):
             ls += lists[pos:pos + len(t[0])]; pos += len(t[0])
             lq += lists[pos:pos + len(t[2])]; pos += len(t[2])
         off_s = np.cumsum([0] + [len(t[0]) for t in tasks]); off_q = np.cumsum([0] + [len(t[2]) for t in tasks])
-        S = SubgraphBatch.from_nodes(self.G, np.concatenate([t[0] for t in tasks]), off_s, ls, self.link_pred_mode)
-        Q = SubgraphBatch.from_nodes(self.G, np.concatenate([t[2] for t in tasks]), off_q, lq, self.link_pred_mode)
+        S = SubgraphBatch.from_nodes(self.G, np.concatenate([t[0] for t in tasks]), off_s, ls, self.link_pred_mode, self.mask_target)
+        Q = SubgraphBatch.from_nodes(self.G, np.concatenate([t[2] for t in tasks]), off_q, lq, self.link_pred_mode, self.mask_target)
         return S, Q
 
     # The support and the query batch of a meta-batch are independent builds (two gm_extract calls, each with two host round trips and ~0.1-0.3 ms

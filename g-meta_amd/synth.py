@@ -66,11 +66,13 @@ def multi_node_dataset(n_graphs, n, m, F0, n_classes, seed=222, label_sets=1):
             'tables': {'train': (names, sets[0]['labels'])}}
 
 
-def link_dataset(n_graphs, n, m, F0, seed=222, spt_frac=0.3):
+def link_dataset(n_graphs, n, m, F0, seed=222, spt_frac=0.3, inject_negatives=True):
     """Shared multi-graph link prediction (FirstMM-DB shape, SURVEY 8(d) SYN-FIRSTMM) laid out like data_process/link_process.py:
     positives stored once as u -> v with u < v (link_process.py:32-34,45-47), an equal number of negative pairs injected as edges
     (link_process.py:83-85, "following SEAL"), 30 % of each kind are support names and 70 % query names (link_process.py:13,37-41,
-    69-74); names 'g_i_j' (sdp.py:358-362), label 1 / 0."""
+    69-74); names 'g_i_j' (sdp.py:358-362), label 1 / 0.
+    inject_negatives=False: the same pairs, names and features, but the graphs hold the positive edges only -- the layout of a user's own graph, where
+    "there is an i-j edge" is the label itself and extraction has to mask the target link (Subgraphs(mask_target=True))."""
     rng = np.random.default_rng(seed)
     graphs, feats, info = [], [], {}
     tabs = {'train': ([], []), 'train_spt': ([], []), 'train_qry': ([], [])}
@@ -87,7 +89,7 @@ def link_dataset(n_graphs, n, m, F0, seed=222, spt_frac=0.3):
             if len(keep) == len(e):
                 break
         neg = np.array(keep, np.int64).reshape(-1, 2)
-        graphs.append((n, np.concatenate([e[:, 0], neg[:, 0]]), np.concatenate([e[:, 1], neg[:, 1]])))
+        graphs.append((n, np.concatenate([e[:, 0], neg[:, 0]]), np.concatenate([e[:, 1], neg[:, 1]])) if inject_negatives else (n, e[:, 0].copy(), e[:, 1].copy()))
         feats.append(rng.standard_normal((n, F0), dtype=np.float32))
         for arr, lab in ((e, 1), (neg, 0)):
             spt = np.zeros(len(arr), bool)

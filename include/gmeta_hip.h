@@ -112,8 +112,32 @@ void gm_store_destroy(gm_store_t* s);
  *                      threshold, both centres re-added; everything derived from the node set (node
  *                      order, both CSR orientations, centre indices, norms, GM_F_*) as in mode 1.
  * gm_batch_from_nodes takes the node sets as given and only asks whether there are two centres:
- * any non-zero link_pred means pairs. */
+ * any non-zero link_pred means pairs (bit 2, GM_LINK_MASK_TARGET, aside: it is read as the mask).
+ * GM_LINK_MASK_TARGET is a FLAG, OR-ed onto a pair mode (valid link_pred values: 0, 1, 2, 1|4, 2|4; the
+ * flag alone is GM_EINVAL -- node seeds have no target link), beyond the reference: the subgraph of a
+ * pair (i, j) is built WITHOUT the link it is asked about, as SEAL removes the target link from the
+ * enclosing subgraph (an existing i-j edge otherwise tells the head the answer: j is a source of row i,
+ * and label_j(i) == 1 under gm_set_hop_labels).  Under the flag, per subgraph with centres i, j:
+ *   node set   the one the unmasked mode gives: the expansion runs on the unmasked parent, same sampling
+ *              key (seed, g, i, j), same threshold, both centres re-added -- k hops first, then the link
+ *              removed.  (Remark: in both pair modes that is also the expansion on the masked graph --
+ *              whatever i reaches through j within h hops lies within h - 1 hops of j, and j's side is
+ *              expanded too.  The definition is "unmasked node set".)
+ *   edges      absent from the induced subgraph, in both CSR orientations (GM_F_INDPTR / GM_F_INDICES
+ *              and the _T pair): every parent edge i -> j and every edge j -> i, all parallel copies
+ *              included; for i == j every self loop i -> i.  No other edge changes, and the surviving
+ *              edges of a row keep the parent's order.
+ *   weights    the surviving edges carry their own weights at their new slots (GM_F_EDGE_W / _T).
+ *   norm       in_deg.clamp(1)^-1/2 of the MASKED degree; weighted batches: of the masked weighted
+ *              degree, summed in edge order.  A centre whose only in-edge was the target has norm 1.
+ *   derived    hop labels (for i != j, label_j(i) and label_i(j) are never 1) and every finalisation
+ *              table come from the masked CSR.
+ *   no-op      a pair with no edge between its endpoints yields the unmasked subgraph bit for bit.
+ * gm_batch_mask_target: 1 for a batch built under the flag, else 0; gm_batch_concat takes parts that are
+ * all masked or all unmasked and hands the flag on.  Without the flag every field, launch and output is
+ * what it was before the flag existed. */
 #define GM_LINK_SYMMETRIC 2
+#define GM_LINK_MASK_TARGET 4
 int gm_extract(const gm_store_t* store, const gm_seed_t* seeds, int32_t n_seeds,
                const int32_t* set_offsets, int32_t n_sets, int32_t h, int32_t sample_nodes,
                uint64_t rng_seed, int32_t link_pred, void* stream, gm_batch_t** out);
@@ -148,9 +172,11 @@ int gm_batch_from_nodes(const gm_store_t* store, const gm_seed_t* seeds, int32_t
 void gm_set_hop_labels(int32_t D);
 int32_t gm_get_hop_labels(void);
 int32_t gm_batch_hop_labels(const gm_batch_t* b);
+int32_t gm_batch_mask_target(const gm_batch_t* b);
 /* dgl.batch over already-built batches (sets are appended in order).  Inputs stay valid.  Parts of one store are all weighted or all
  * unweighted; a mix (hand-made handles) is GM_EINVAL.  Parts are all hop-labelled with the same D, or all unlabelled (a mix: GM_EINVAL); the result's
- * feature table is the concatenation of the parts'. */
+ * feature table is the concatenation of the parts'.  Parts are all built with GM_LINK_MASK_TARGET or all without (a mix: GM_EINVAL); the result
+ * carries the flag. */
 int gm_batch_concat(const gm_batch_t* const* parts, int32_t n_parts, void* stream, gm_batch_t** out);
 /* Receptive-field tables for gm_hparams_t.cone with an n_gcn-layer model (built on `stream`, cached in the
  * batch; gm_meta_ws_bytes/gm_meta_step build them on first use otherwise).  level_rows/level_edges

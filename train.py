@@ -59,6 +59,9 @@ def parse(argv=None):
     ap.add_argument('--hop_labels', type=int, default=0,
                     help='D in 1..7: append one-hot hop-distance labels (distance to the centre, to both endpoints of a pair; capped at D) to the '
                          'features of every subgraph; 0 = off')
+    ap.add_argument('--mask_target', type=int, default=0, choices=[0, 1],
+                    help='1 (--link_pred_mode True): build the subgraph of every pair without the edges between its two endpoints, as SEAL removes the target link; for '
+                         'graphs that hold the positive pairs as edges and no injected negative ones')
     ap.add_argument('--readout', default='centre', choices=['centre', 'mean'],
                     help="what the head reads of every subgraph: 'centre' = the centre row (both endpoints' rows of a pair), as the reference; 'mean' = the mean "
                          "over all of its rows (the dgl.mean_nodes line the reference left commented out), one pooled vector for pairs too")
