@@ -15,5 +15,6 @@ from .graphstore import GraphStore  # noqa: F401
 from .subgraphs import Subgraphs, SubgraphBatch, collate, hop_label_width, hop_labels_switch  # noqa: F401
 from .learner import Classifier  # noqa: F401
 from .meta import Meta  # noqa: F401
+from .negatives import link_tables_with_negatives  # noqa: F401
 
-__all__ = ['GraphStore', 'Subgraphs', 'SubgraphBatch', 'collate', 'Classifier', 'Meta', 'hop_label_width', 'hop_labels_switch']
+__all__ = ['GraphStore', 'Subgraphs', 'SubgraphBatch', 'collate', 'Classifier', 'Meta', 'hop_label_width', 'hop_labels_switch', 'link_tables_with_negatives']

@@ -364,6 +364,7 @@ const gm_knobs& gm_knob() {
         k.wgrad_split_min_chunks = env("GM_WGRAD_SPLIT_MIN_CHUNKS", -1);
         k.agg_stream = env("GM_AGG_STREAM", 1);
         k.agg_stream_min_rows = env("GM_AGG_STREAM_MIN_ROWS", 100000);
+        k.neg_round = env("GM_NEG_ROUND", 0);
     });
     return k;
 }
@@ -380,6 +381,7 @@ static int gm_knobs::* gm_find_knob(const char* name) {
         {"GM_HEAD_STAGE", &gm_knobs::head_stage}, {"GM_HEAD_THREADS", &gm_knobs::head_threads}, {"GM_QUERY_STREAMS", &gm_knobs::query_streams}, {"GM_AGG_MID_LIST", &gm_knobs::agg_mid_list}, {"GM_AGG_MID_WIN", &gm_knobs::agg_mid_win}, {"GM_AGG_STREAM", &gm_knobs::agg_stream}, {"GM_AGG_STREAM_MIN_ROWS", &gm_knobs::agg_stream_min_rows},
         {"GM_SPLIT16_MIN_ROWS", &gm_knobs::split16_min_rows}, {"GM_WGRAD_SPLIT_MIN_CHUNKS", &gm_knobs::wgrad_split_min_chunks}, {"GM_TIMING", &gm_knobs::timing},
         {"GM_FUSE_DIFF", &gm_knobs::fuse_diff}, {"GM_EXTRACT_PREF16", &gm_knobs::extract_pref16},
+        {"neg_round", &gm_knobs::neg_round}, {"GM_NEG_ROUND", &gm_knobs::neg_round},
     };
     for (const auto& e : tab)
         if (!strcmp(name, e.name)) return e.field;

@@ -245,6 +245,7 @@ struct gm_knobs {
     int wgrad_split_min_chunks;    // GM_WGRAD_SPLIT_MIN_CHUNKS: smallest launch (row chunks) that takes the split weight-gradient kernel; -1: a quarter of the CUs
     int agg_stream;                // GM_AGG_STREAM: eligible full aggregate launches take the LDS-DMA stream kernel (agg_stream.hip)
     int agg_stream_min_rows;       // GM_AGG_STREAM_MIN_ROWS: smallest batch (rows) that builds stream tables; dense batches (more than 8 edges per row) never do
+    int neg_round;                 // GM_NEG_ROUND, gm_set_tuning("neg_round"): candidates per round of gm_store_negative_pairs (negatives.hip); 0 (default) = by the call's n.  The result does not depend on it
 };
 const gm_knobs& gm_knob();
 

@@ -103,6 +103,49 @@ class GraphStore:
                 return False
         return True
 
+    def _pairs_of(self, g, pairs, what):
+        g = int(g)
+        if not 0 <= g < self.n_graphs:
+            raise ValueError('%s: graph %d of a store with %d graph(s)' % (what, g, self.n_graphs))
+        p = np.asarray(pairs, np.int64).reshape(-1, 2)
+        if len(p) and (p.min() < 0 or p.max() >= self.n_nodes[g]):
+            raise ValueError('%s: node id outside graph %d (%d nodes)' % (what, g, self.n_nodes[g]))
+        return g, p
+
+    def negative_pairs(self, g, n, seed=222, mode='uniform', exclude=None):
+        """`n` distinct node pairs (u < v) of graph `g` with no edge between them in either direction, drawn on the device: int64 [n, 2], in the order
+        include/gmeta_hip.h defines (gm_store_negative_pairs: a function of the graph, seed, mode, exclusion list and n alone; tests/negative_ref.py
+        restates it).  mode: 'uniform' (both endpoints uniform) or 'two_hop' (the second endpoint two out-steps from the first).  `exclude`: [m, 2]
+        pairs in any orientation that must not come back (e.g. positives taken out of the graph for validation).  ValueError when the draw budget
+        of 64 n + 4096 candidates holds fewer than n such pairs; the message names the count found."""
+        import torch
+        if mode not in _lib.NEG_MODES:
+            raise ValueError("mode must be 'uniform' or 'two_hop', not %r" % (mode,))
+        n = int(n)
+        g, ex = self._pairs_of(g, [] if exclude is None else exclude, 'negative_pairs(exclude=)')
+        keys = np.unique(np.minimum(ex[:, 0], ex[:, 1]) * self.n_nodes[g] + np.maximum(ex[:, 0], ex[:, 1]))      # canonical, keyed, sorted, unique
+        d_keys = torch.from_numpy(keys).cuda() if len(keys) else None
+        out = torch.empty((max(n, 1), 2), dtype=torch.int32, device='cuda')
+        found = C.c_int64(0)
+        _lib.check(_lib.lib().gm_store_negative_pairs(self.handle, g, n, int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.NEG_MODES[mode], _lib.ptr(d_keys), len(keys),
+                                                      _lib.ptr(out), C.byref(found), _lib.stream_ptr()), 'gm_store_negative_pairs')
+        if found.value < n:
+            raise ValueError('negative_pairs: graph %d holds only %d distinct non-adjacent %s pair(s) within the draw budget of %d candidates; %d asked for'
+                             % (g, found.value, mode, 64 * n + 4096, n))
+        return out[:n].cpu().numpy().astype(np.int64)
+
+    def has_edges(self, g, pairs):
+        """bool [m]: whether graph `g` holds an edge between the two nodes of each of the [m, 2] `pairs`, in either direction (gm_store_has_edges: the
+        negative sampler's own adjacency test)."""
+        import torch
+        g, p = self._pairs_of(g, pairs, 'has_edges')
+        if not len(p):
+            return np.zeros(0, bool)
+        d_p = torch.from_numpy(np.ascontiguousarray(p, np.int32)).cuda()
+        out = torch.empty(len(p), dtype=torch.uint8, device='cuda')
+        _lib.check(_lib.lib().gm_store_has_edges(self.handle, g, _lib.ptr(d_p), len(p), _lib.ptr(out), _lib.stream_ptr()), 'gm_store_has_edges')
+        return out.cpu().numpy().astype(bool)
+
     def close(self):
         if getattr(self, 'handle', None):
             _lib.lib().gm_store_destroy(self.handle)

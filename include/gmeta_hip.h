@@ -97,6 +97,38 @@ int gm_store_create_weighted(int32_t n_graphs, const int64_t* n_nodes, const int
 int32_t gm_store_weighted(const gm_store_t* s);
 void gm_store_destroy(gm_store_t* s);
 
+/* ---- NEGATIVE PAIRS for link prediction, drawn on the device (beyond the reference, which draws them on the host and stores them as false
+ * edges, data_process/link_process.py:83-85).  This comment is THE definition; tests/negative_ref.py restates it one candidate at a time and the
+ * device result equals it bit for bit.  Per parent graph g of a store with N >= 2 nodes, seed (u64) and mode m:
+ *   modes        GM_NEG_UNIFORM (0): both endpoints uniform over the nodes.  GM_NEG_TWO_HOP (1): a uniform, b two out-steps from a -- the hard
+ *                negatives that share a neighbour.
+ *   random words s = sample_salt(seed, g, 0x6E454721, m) (the salt of the extraction's keyed permutation: csrc/extract.hip, oracle.sample_salt);
+ *                r(k, c) = lowbias32(s + 4 k + c) in 32-bit wrap-around arithmetic, k = 0, 1, 2, ..., c in 0..3;
+ *                pick(r, n) = (uint64(r) * n) >> 32.
+ *   candidate k  uniform:  a = pick(r(k,0), N), b = pick(r(k,1), N).
+ *                two-hop, on the out-CSR rows with parallel copies kept (out[x] = destinations of x's out-edges, ascending):
+ *                a = pick(r(k,0), N);  w = out[a][pick(r(k,1), outdeg(a))];  b = out[w][pick(r(k,2), outdeg(w))];
+ *                the candidate is invalid if either out-degree is 0.
+ *                Canonical form: (u, v) = (min(a, b), max(a, b)).
+ *   valid        iff u != v, AND the graph holds no edge u -> v and no edge v -> u at any multiplicity (self loops elsewhere are irrelevant, edge
+ *                weights are ignored), AND the key u * N + v (int64) is not in the caller's exclusion list: d_exclude_keys, n_exclude sorted
+ *                unique int64 keys on the device (n_exclude = 0: none).
+ *   result       the first n DISTINCT valid pairs in ascending order of k -- a pair counts where its smallest k is -- written to d_out_pairs
+ *                (device int32 [n, 2], u < v) in that order.  The draw budget is 64 n + 4096 candidates: if it holds fewer than n distinct valid
+ *                pairs the call still returns GM_OK, *h_found (host) is the count found and only that many rows of d_out_pairs are written;
+ *                otherwise *h_found = n.
+ * The result is a function of (graph, seed, mode, exclusion list, n) alone: it does not depend on how the candidate stream is cut into rounds
+ * (gm_set_tuning("neg_round", R): candidates per round, 0 = the library's choice) nor on the stream.  The call runs on `stream`, takes its
+ * scratch from the stream-ordered pool, and returns after the stream has produced the pairs (it reads one counter per round).
+ * GM_EINVAL: a bad graph index, N < 2, n < 0, an unknown mode, or n above (2^31 - 1 - 4096) / 64 (the budget must fit int32 counters).
+ * gm_store_has_edges: the sampler's adjacency test for n given pairs (device int32 [n, 2], any orientation): d_out[k] = 1 where the graph holds
+ * an edge between the two nodes in either direction (for a pair (a, a): a self loop), else 0; 0 for a node id outside the graph. */
+#define GM_NEG_UNIFORM 0
+#define GM_NEG_TWO_HOP 1
+int32_t gm_store_negative_pairs(const gm_store_t* s, int32_t g, int64_t n, uint64_t seed, int32_t mode, const int64_t* d_exclude_keys,
+                                int64_t n_exclude, int32_t* d_out_pairs, int64_t* h_found, void* stream);
+int32_t gm_store_has_edges(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, uint8_t* d_out, void* stream);
+
 /* ---- Extraction: replaces Subgraphs.generate_subgraph / generate_subgraph_link_pred
  * (sdp.py:295-346: h-hop in-neighbour expansion, node sampling, G.subgraph) and dgl.batch
  * (sdp.py:399-406) for n_sets sets at once.  seeds/set_offsets are host arrays; set s owns seeds

@@ -62,6 +62,10 @@ def parse(argv=None):
     ap.add_argument('--mask_target', type=int, default=0, choices=[0, 1],
                     help='1 (--link_pred_mode True): build the subgraph of every pair without the edges between its two endpoints, as SEAL removes the target link; for '
                          'graphs that hold the positive pairs as edges and no injected negative ones')
+    ap.add_argument('--negatives', default='file', choices=['file', 'uniform', 'two_hop'],
+                    help="where the negative pairs of a link data set come from (--link_pred_mode True): 'file' = the CSV tables hold them, as the reference's do; "
+                         "'uniform' / 'two_hop' = the tables hold the positive pairs only and as many negatives are drawn on the GPU from each graph's non-edges "
+                         "(GraphStore.negative_pairs), the same on every rank; meant for --mask_target 1")
     ap.add_argument('--readout', default='centre', choices=['centre', 'mean'],
                     help="what the head reads of every subgraph: 'centre' = the centre row (both endpoints' rows of a pair), as the reference; 'mean' = the mean "
                          "over all of its rows (the dgl.mean_nodes line the reference left commented out), one pooled vector for pairs too")
@@ -89,6 +93,15 @@ def main(args):
     if args.task_setup == 'Shared' and args.task_mode == 'True':            # train.py:49-51
         root = os.path.join(root, 'task' + str(args.task_n)) + '/'
     info = datadir.load_labels(root)
+    store = gmeta_amd.GraphStore(graphs, feat)
+    tables = None
+    if args.negatives != 'file':
+        if args.link_pred_mode != 'True':
+            raise SystemExit('--negatives %s draws negative PAIRS: it needs --link_pred_mode True' % args.negatives)
+        from gmeta_amd.negatives import read_link_tables
+        tables, info = gmeta_amd.link_tables_with_negatives(store, read_link_tables(root), info, mode=args.negatives)      # fixed seed: every rank draws the same pairs
+        if rank == 0 and not args.mask_target:
+            print('--negatives %s without --mask_target 1: the target edges of the positive pairs are visible to the model' % args.negatives)
     total_class = len(np.unique(np.array(list(info.values()))))
     labels_num = args.n_way if args.task_setup == 'Disjoint' else total_class   # train.py:58-61
     config = [('GraphConv', [feat[0].shape[1] + gmeta_amd.hop_label_width(args.hop_labels, args.link_pred_mode == 'True'), args.hidden_dim])]
@@ -99,7 +112,6 @@ def main(args):
         config.append(('Readout', [args.readout]))
     if args.link_pred_mode == 'True':
         config.append(('LinkPred', [True]))
-    store = gmeta_amd.GraphStore(graphs, feat)
     maml = gmeta_amd.Meta(args, config).to('cuda')
     if rank == 0:
         print('There are {} classes '.format(total_class))
@@ -107,7 +119,7 @@ def main(args):
             print('The graphs carry edge weights (graph_csr.npz g*_w)')
         print('Total trainable tensors:', sum(int(np.prod(p.shape)) for p in maml.parameters() if p.requires_grad))
     mk = lambda mode, b: gmeta_amd.Subgraphs(root, mode, info, n_way=args.n_way, k_shot=args.k_spt, k_query=args.k_qry, batchsz=b,  # noqa: E731
-                                             args=args, adjs=store, h=args.h, verbose=rank == 0)
+                                             args=args, adjs=store, h=args.h, tables=tables, verbose=rank == 0)
     db_train, db_val, db_test = mk('train', args.batchsz), mk('val', args.eval_tasks), mk('test', args.eval_tasks)
     if world > args.task_num:
         raise SystemExit('task_num=%d cannot be sharded over %d ranks (every rank needs at least one task of a full meta-batch)' % (args.task_num, world))
