@@ -116,8 +116,8 @@ __device__ __forceinline__ int group_sum(int v) {
 // Target-link masking (GM_LINK_MASK_TARGET): a row drops ONE neighbour id, in its in-list and its out-list alike -- the other centre on the two centre
 // rows (all parallel copies; i == j: the centre's self loops), nothing (-1, no node id) on every other row.  The count pass (k_nodes) and the fill pass
 // (k_fill) take the id from this one function and apply it as `inside && u != excl` in all four walkers: indptr is the scan of the counted degrees and
-// the fill writes at those offsets.  MASK is a compile-time flag of the walkers; without it they are what they were before the flag existed.
-struct ExMask { int on; };      // the LAST argument of the masked instantiations of k_nodes / k_fill, which only they have (see FillW)
+// the fill writes at those offsets.  MASK is a template flag of the two kernels and of the walkers: it changes no signature, and without it the
+// comparison and `excl` are compiled out.
 __device__ __forceinline__ int mask_excl(int v, int ci, int cj) { return v == ci ? cj : (v == cj ? ci : -1); }
 // number of neighbours of v (list ptr/idx) inside the bitmap; the eight lanes of a group call it together (gl = lane within the group; excl: per group)
 template <bool G, bool MASK = false>
@@ -230,19 +230,68 @@ __device__ __forceinline__ void expand_root(const ExStore& S, const int64_t base
     }
 }
 
+// The walk over the ns rows of a subgraph (nodes[], ascending) that the count pass (k_nodes) and the fill pass (k_fill) share; called by the whole
+// workgroup.  Eight rows per wave at a time, one per group of eight lanes (grp, gl: a lane's group and its place in it, the caller's own values);
+// rows with more than EX_BIG_DEG neighbours in either list go to big[] (*nbig of them, zeroed here) and get a whole wave each after a barrier.
+// The walk of a batch of eight rows is a chain node id -> row bounds -> neighbour ids -> bitmap word.  The first two links are taken off the chain
+// (round 6): the node ids are fetched TWO batches ahead and the row bounds ONE batch ahead -- with OFFS also the rows' output offsets, off_i[r] and
+// off_o[r] -- so an iteration issues three independent groups of loads and waits one round trip instead of three.
+//   batch(have, later, r, v, ia, ib, oa, ob, pi, po): every lane of the wave, per batch.  have: the group has a row, r, of node v (else v = -1);
+//       later: it went to big[].  [ia, ib) / [oa, ob): its in- / out-list, empty without a row or with `later`; pi / po: the offsets (0 without OFFS).
+//   hub(r, v): every lane of a wave, per row of big[].  A symmetric parent (S.sym) has its out-lists left alone: oa == ob == 0.
+template <bool OFFS, typename Batch, typename Hub>
+__device__ __forceinline__ void walk_rows(const ExStore& S, const int64_t base, const int32_t* nodes, const int ns, const int32_t* off_i, const int32_t* off_o,
+                                          int* big, int* nbig, const int tid, const int wave, const int grp, const int gl, Batch batch, Hub hub) {
+    if (tid == 0) *nbig = 0;
+    __syncthreads();
+    constexpr int RSTEP = EX_WAVES * EX_GROUPS;
+    int r = wave * EX_GROUPS + grp;
+    int v1 = r < ns ? nodes[r] : -1;                                              // node of the NEXT batch
+    int v2 = r + RSTEP < ns ? nodes[r + RSTEP] : -1;                              // ... of the one after
+    int64_t nia = 0, nib = 0, noa = 0, nob = 0; int npi = 0, npo = 0;
+    if (v1 >= 0) {
+        nia = S.in_ptr[base + v1]; nib = S.in_ptr[base + v1 + 1]; if constexpr (OFFS) npi = off_i[r];
+        if (!S.sym) { noa = S.out_ptr[base + v1]; nob = S.out_ptr[base + v1 + 1]; if constexpr (OFFS) npo = off_o[r]; }
+    }
+    for (int r0 = wave * EX_GROUPS; r0 < ns; r0 += RSTEP, r += RSTEP) {
+        int64_t ia = nia, ib = nib, oa = noa, ob = nob; const int pi = npi, po = npo;
+        const int v = v1;
+        const bool have = v >= 0;
+        v1 = v2;
+        v2 = r + 2 * RSTEP < ns ? nodes[r + 2 * RSTEP] : -1;
+        nia = nib = noa = nob = 0; npi = npo = 0;
+        if (v1 >= 0) {
+            nia = S.in_ptr[base + v1]; nib = S.in_ptr[base + v1 + 1]; if constexpr (OFFS) npi = off_i[r + RSTEP];
+            if (!S.sym) { noa = S.out_ptr[base + v1]; nob = S.out_ptr[base + v1 + 1]; if constexpr (OFFS) npo = off_o[r + RSTEP]; }
+        }
+        bool later = false;
+        if (have) {
+            if (ib - ia > EX_BIG_DEG || ob - oa > EX_BIG_DEG) {
+                int slot = EX_BLOCK;
+                if (gl == 0) slot = atomicAdd(nbig, 1);
+                slot = __shfl(slot, grp * EX_GL, 64);
+                if (slot < EX_BLOCK) { if (gl == 0) big[slot] = r; later = true; ia = ib = oa = ob = 0; }      // (list full: the group walks it itself)
+            }
+        }
+        batch(have, later, r, v, ia, ib, oa, ob, pi, po);
+    }
+    __syncthreads();
+    const int nb = min(*nbig, EX_BLOCK);
+    for (int k = wave; k < nb; k += EX_WAVES) { const int r = big[k]; hub(r, nodes[r]); }
+}
+
 // Phase A: node set (BFS or given), sampling, sorted node list, induced in/out degrees.
 // P16: 16-bit prefix words (LDS bitmaps, subgraphs below 65,536 nodes).  NEEDX: keep the `expanded` bitmap that de-duplicates frontier expansions -- needed from
 // the third hop on (a hop-2 node is reached through many hop-1 nodes); with two hops it only catches parallel edges of the centre, and without it the
 // region behind `seen` shrinks to the 16-bit prefix words.
 // SYM: pairs in GM_LINK_SYMMETRIC mode -- h hops around BOTH endpoints (link != 0 then); without it a pair is the reference's: i side two hops, j side one.
-// MArgs: empty, or {ExMask} -- the induced degrees are those without the target link (the node set above them is the unmasked one: BFS, sampling and
-// node list do not look at the flag).  With the empty pack the kernel is k_nodes<G, P16, NEEDX, SYM> argument for argument.
-template <bool G, bool P16 = false, bool NEEDX = true, bool SYM = false, typename... MArgs>
+// MASK: the induced degrees are those without the target link (the node set above them is the unmasked one: BFS, sampling and node list do not look at
+// the flag).  Masked and unmasked instantiations take the same arguments.
+template <bool G, bool P16 = false, bool NEEDX = true, bool SYM = false, bool MASK = false>
 __global__ __launch_bounds__(EX_BLOCK) void k_nodes(ExStore S, const gm_seed_t* seeds, int n_seeds, int h, int sample_n,
                                                     uint64_t rng_seed, int link, const int32_t* given, const int64_t* given_off,
                                                     int cap, int32_t* nodes_slab, int32_t* degi_slab, int32_t* dego_slab,
-                                                    int32_t* n_sub, int32_t* e_sub, int Wmax, uint32_t* gbits, MArgs... m_args) {
-    constexpr bool MASK = sizeof...(MArgs) != 0;
+                                                    int32_t* n_sub, int32_t* e_sub, int Wmax, uint32_t* gbits) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t* seen = G ? gbits + (size_t)blockIdx.x * 2 * Wmax : lds;
     static_assert(!(G && P16), "16-bit prefix words live in LDS");
@@ -339,57 +388,28 @@ __global__ __launch_bounds__(EX_BLOCK) void k_nodes(ExStore S, const gm_seed_t* 
         while (bits) { const int b = __ffs(bits) - 1; bits &= bits - 1; nodes[r++] = w * 32 + b; }
     }
     __syncthreads();
-    // ---- induced in/out degree of every selected node (eight nodes per wave at a time, hubs by a whole wave afterwards)
+    // ---- induced in/out degree of every selected node (walk_rows: eight nodes per wave at a time, hubs by a whole wave afterwards)
     {
         const int grp = lane / EX_GL, gl = lane % EX_GL;
-        int* big = part; int* nbig = &sc[5];
-        if (tid == 0) *nbig = 0;
-        __syncthreads();
         int ein = 0, eout = 0;
         int32_t* degi = degi_slab + (int64_t)seed * cap; int32_t* dego = dego_slab + (int64_t)seed * cap;
-        // The walk of a batch of eight nodes is a chain node id -> row bounds -> neighbour ids -> bitmap word.  The first two links are taken off the
-        // chain (round 6): the node ids are fetched TWO batches ahead and the row bounds ONE batch ahead, so an iteration issues three independent
-        // groups of loads and waits one round trip instead of three.
-        constexpr int RSTEP = EX_WAVES * EX_GROUPS;
-        int r = wave * EX_GROUPS + grp;
-        int v1 = r < ns ? nodes[r] : -1;                                              // node of the NEXT batch
-        int v2 = r + RSTEP < ns ? nodes[r + RSTEP] : -1;                              // ... of the one after
-        int64_t nia = 0, nib = 0, noa = 0, nob = 0;
-        if (v1 >= 0) { nia = S.in_ptr[base + v1]; nib = S.in_ptr[base + v1 + 1]; if (!S.sym) { noa = S.out_ptr[base + v1]; nob = S.out_ptr[base + v1 + 1]; } }
-        for (int r0 = wave * EX_GROUPS; r0 < ns; r0 += RSTEP, r += RSTEP) {
-            int64_t ia = nia, ib = nib, oa = noa, ob = nob;
-            const bool have = v1 >= 0;
-            int excl = -1;
-            if constexpr (MASK) excl = mask_excl(v1, ci, cj);      // (v1 < 0: a group without a row, and ci, cj >= 0)
-            v1 = v2;
-            v2 = r + 2 * RSTEP < ns ? nodes[r + 2 * RSTEP] : -1;
-            nia = nib = noa = nob = 0;
-            if (v1 >= 0) { nia = S.in_ptr[base + v1]; nib = S.in_ptr[base + v1 + 1]; if (!S.sym) { noa = S.out_ptr[base + v1]; nob = S.out_ptr[base + v1 + 1]; } }
-            bool later = false;                                                          // a hub: its degrees come from the second pass
-            if (have) {
-                if (ib - ia > EX_BIG_DEG || ob - oa > EX_BIG_DEG) {
-                    int slot = EX_BLOCK;
-                    if (gl == 0) slot = atomicAdd(nbig, 1);
-                    slot = __shfl(slot, grp * EX_GL, 64);
-                    if (slot < EX_BLOCK) { if (gl == 0) big[slot] = r; later = true; ia = ib = oa = ob = 0; }      // (list full: the group walks it itself)
-                }
-            }
-            const int ci_ = group_count<G, MASK>(ia, ib, S.in_idx, seen, gl, excl);
-            const int co_ = S.sym ? ci_ : group_count<G, MASK>(oa, ob, S.out_idx, seen, gl, excl);
-            if (have && gl == 0 && !later) { degi[r] = ci_; dego[r] = co_; ein += ci_; eout += co_; }
-        }
-        __syncthreads();
-        const int nb = min(*nbig, EX_BLOCK);
-        for (int k = wave; k < nb; k += EX_WAVES) {
-            const int r = big[k], v = nodes[r];
-            int ci_ = 0, co_ = 0;
-            int excl = -1;
-            if constexpr (MASK) excl = mask_excl(v, ci, cj);
-            ci_ = wave_count<G, MASK>(S.in_ptr[base + v], S.in_ptr[base + v + 1], S.in_idx, seen, lane, excl);
-            if (!S.sym) co_ = wave_count<G, MASK>(S.out_ptr[base + v], S.out_ptr[base + v + 1], S.out_idx, seen, lane, excl);
-            ci_ = wave_sum(ci_); co_ = S.sym ? ci_ : wave_sum(co_);
-            if (lane == 0) { degi[r] = ci_; dego[r] = co_; ein += ci_; eout += co_; }
-        }
+        walk_rows<false>(S, base, nodes, ns, nullptr, nullptr, part, &sc[5], tid, wave, grp, gl,
+            [&](bool have, bool later, int r, int v, int64_t ia, int64_t ib, int64_t oa, int64_t ob, int, int) {
+                int excl = -1;
+                if constexpr (MASK) excl = mask_excl(v, ci, cj);      // (v < 0: a group without a row, and ci, cj >= 0)
+                const int ci_ = group_count<G, MASK>(ia, ib, S.in_idx, seen, gl, excl);
+                const int co_ = S.sym ? ci_ : group_count<G, MASK>(oa, ob, S.out_idx, seen, gl, excl);
+                if (have && gl == 0 && !later) { degi[r] = ci_; dego[r] = co_; ein += ci_; eout += co_; }      // (later: its degrees come from the second pass)
+            },
+            [&](int r, int v) {
+                int ci_ = 0, co_ = 0;
+                int excl = -1;
+                if constexpr (MASK) excl = mask_excl(v, ci, cj);
+                ci_ = wave_count<G, MASK>(S.in_ptr[base + v], S.in_ptr[base + v + 1], S.in_idx, seen, lane, excl);
+                if (!S.sym) co_ = wave_count<G, MASK>(S.out_ptr[base + v], S.out_ptr[base + v + 1], S.out_idx, seen, lane, excl);
+                ci_ = wave_sum(ci_); co_ = S.sym ? ci_ : wave_sum(co_);
+                if (lane == 0) { degi[r] = ci_; dego[r] = co_; ein += ci_; eout += co_; }
+            });
         if (ein | eout) { atomicAdd(&sc[3], ein); atomicAdd(&sc[4], eout); }
     }
     __syncthreads();
@@ -475,18 +495,15 @@ struct FillOut {
     int32_t* indptr; int32_t* indices; int32_t* indptr_t; int32_t* indices_t; int32_t* centre;
 };
 // Weighted stores (WT): the store's edge weights in both orientations and the two batches' gm_batch::d_ew -- written at the slots where the fill writes
-// indices / indices_t.  They ride in a LAST argument that only the weighted instantiations have, k_fill<G, P16, FillW>: with the empty pack the kernel is
-// k_fill<G, P16> argument for argument, and, WT being a compile-time flag, instruction for instruction (even an empty struct there would move the hidden
-// arguments a kernel reads blockDim from).
-// Masked builds (GM_LINK_MASK_TARGET) add an ExMask to the pack, AHEAD of the FillW where there is one: k_fill<G, P16, ExMask> and k_fill<G, P16, ExMask, FillW>.
+// indices / indices_t.  They ride in a LAST argument that only the weighted instantiations have, k_fill<G, P16, MASK, FillW>: with the empty pack the
+// kernel takes the arguments it took before there were weights (even an empty struct there would move the hidden arguments a kernel reads blockDim from).
+// MASK (GM_LINK_MASK_TARGET): the rows are filled without the target link, as k_nodes counted them.
 struct FillW { const float* in_w; const float* out_w; float* ew0[2]; float* ew1[2]; };      // ew0 / ew1: d_ew of the batch o0 / o1 fills
-__device__ __forceinline__ const FillW& fill_w_of(const FillW& w) { return w; }
-__device__ __forceinline__ const FillW& fill_w_of(const ExMask&, const FillW& w) { return w; }
-template <bool G, bool P16 = false, typename... WArgs>
+template <bool G, bool P16 = false, bool MASK = false, typename... WArgs>
 __global__ __launch_bounds__(EX_BLOCK) void k_fill(ExStore S, const gm_seed_t* seeds, int n_seeds, int link, int cap,
                                                    const int32_t* nodes_slab, const int32_t* degi_slab, const int32_t* dego_slab,
                                                    FillOut o0, FillOut o1, int split, int Wmax, uint32_t* gbits, const int32_t* order, WArgs... w_args) {
-    constexpr bool WT = (std::is_same<WArgs, FillW>::value || ...), MASK = (std::is_same<WArgs, ExMask>::value || ...);
+    constexpr bool WT = sizeof...(WArgs) != 0;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t* seen = G ? gbits + (size_t)blockIdx.x * 2 * Wmax : lds;
     static_assert(!(G && P16), "16-bit prefix words live in LDS");
@@ -535,89 +552,31 @@ __global__ __launch_bounds__(EX_BLOCK) void k_fill(ExStore S, const gm_seed_t* s
         centre[ls * nc] = bit_rank<G, PT>(seen, pref, seeds[seed].i);
         if (link) centre[ls * nc + 1] = bit_rank<G, PT>(seen, pref, seeds[seed].j);
     }
-    // eight rows per wave at a time (one per group of eight lanes); hub nodes by a whole wave afterwards.  A symmetric parent fills both
-    // orientations from the one walk.
+    // walk_rows: eight rows per wave at a time, hub nodes by a whole wave afterwards.  A symmetric parent fills both orientations from the one walk.
     {
         const int grp = lane / EX_GL, gl = lane % EX_GL;
-        int* big = part; int* nbig = &sc[2];
-        if (tid == 0) *nbig = 0;
-        __syncthreads();
         int32_t* ind2 = S.sym ? indices_t : nullptr;
-        [[maybe_unused]] int ci = -1, cj = -1, vrow = -1;      // masked builds only: the two centres, and the node of the row a group is about to walk
+        [[maybe_unused]] int ci = -1, cj = -1;      // masked builds only: the two centres
         if constexpr (MASK) { ci = seeds[seed].i; cj = seeds[seed].j; }
         float* ew = nullptr; float* ew_t = nullptr;
         const float* in_w = nullptr; const float* out_w = nullptr;
         if constexpr (WT) {
-            const FillW& fw = fill_w_of(w_args...);
+            const FillW& fw = (w_args, ...);
             in_w = fw.in_w; out_w = fw.out_w; ew = second ? fw.ew1[0] : fw.ew0[0]; ew_t = second ? fw.ew1[1] : fw.ew0[1];
         }
-        // node ids two batches ahead, row bounds and output offsets one batch ahead (see k_nodes)
-        constexpr int RSTEP = EX_WAVES * EX_GROUPS;
-        int r = wave * EX_GROUPS + grp;
-        int v1 = r < ns ? nodes[r] : -1;
-        int v2 = r + RSTEP < ns ? nodes[r + RSTEP] : -1;
-        int64_t nia = 0, nib = 0, noa = 0, nob = 0; int npi = 0, npo = 0;
-        if (v1 >= 0) {
-            nia = S.in_ptr[base + v1]; nib = S.in_ptr[base + v1 + 1]; npi = indptr[row0 + r];
-            if (!S.sym) { noa = S.out_ptr[base + v1]; nob = S.out_ptr[base + v1 + 1]; npo = indptr_t[row0 + r]; }
-        }
-        for (int r0 = wave * EX_GROUPS; r0 < ns; r0 += RSTEP, r += RSTEP) {
-            int64_t ia = nia, ib = nib, oa = noa, ob = nob; const int pi = npi, po = npo;
-            const bool have = v1 >= 0;
-            if constexpr (MASK) vrow = v1;                         // (before the shift, as k_nodes; v1 < 0: a group without a row, and ci, cj >= 0)
-            v1 = v2;
-            v2 = r + 2 * RSTEP < ns ? nodes[r + 2 * RSTEP] : -1;
-            nia = nib = noa = nob = 0; npi = npo = 0;
-            if (v1 >= 0) {
-                nia = S.in_ptr[base + v1]; nib = S.in_ptr[base + v1 + 1]; npi = indptr[row0 + r + RSTEP];
-                if (!S.sym) { noa = S.out_ptr[base + v1]; nob = S.out_ptr[base + v1 + 1]; npo = indptr_t[row0 + r + RSTEP]; }
-            }
-            if (have) {
-                if (ib - ia > EX_BIG_DEG || ob - oa > EX_BIG_DEG) {
-                    int slot = EX_BLOCK;
-                    if (gl == 0) slot = atomicAdd(nbig, 1);
-                    slot = __shfl(slot, grp * EX_GL, 64);
-                    if (slot < EX_BLOCK) { if (gl == 0) big[slot] = r; ia = ib = oa = ob = 0; }      // (list full: the group walks it itself)
-                }
-            }
-            if constexpr (MASK) {                                  // (everything the mask adds is an `if constexpr (MASK)` statement: without it the kernel is the one it was, token for token)
-                const int excl = mask_excl(vrow, ci, cj);
-                if constexpr (WT) {
-                    group_fill_row<G, PT, true, true>(ia, ib, S.in_idx, seen, pref, row0, indices, ind2, pi, grp, gl, in_w, ew, ew_t, excl);
-                    if (!S.sym) group_fill_row<G, PT, true, true>(oa, ob, S.out_idx, seen, pref, row0, indices_t, nullptr, po, grp, gl, out_w, ew_t, nullptr, excl);
-                } else {
-                    group_fill_row<G, PT, false, true>(ia, ib, S.in_idx, seen, pref, row0, indices, ind2, pi, grp, gl, nullptr, nullptr, nullptr, excl);
-                    if (!S.sym) group_fill_row<G, PT, false, true>(oa, ob, S.out_idx, seen, pref, row0, indices_t, nullptr, po, grp, gl, nullptr, nullptr, nullptr, excl);
-                }
-            } else if constexpr (WT) {
-                group_fill_row<G, PT, true>(ia, ib, S.in_idx, seen, pref, row0, indices, ind2, pi, grp, gl, in_w, ew, ew_t);
-                if (!S.sym) group_fill_row<G, PT, true>(oa, ob, S.out_idx, seen, pref, row0, indices_t, nullptr, po, grp, gl, out_w, ew_t, nullptr);
-            } else {
-                group_fill_row<G, PT>(ia, ib, S.in_idx, seen, pref, row0, indices, ind2, pi, grp, gl);
-                if (!S.sym) group_fill_row<G, PT>(oa, ob, S.out_idx, seen, pref, row0, indices_t, nullptr, po, grp, gl);
-            }
-        }
-        __syncthreads();
-        const int nb = min(*nbig, EX_BLOCK);
-        for (int k = wave; k < nb; k += EX_WAVES) {
-            const int r = big[k], v = nodes[r];
-            if constexpr (MASK) {
-                const int excl = mask_excl(v, ci, cj);
-                if constexpr (WT) {
-                    wave_fill_row<G, PT, true, true>(S.in_ptr, S.in_idx, base, v, seen, pref, row0, indices, ind2, indptr[row0 + r], lane, in_w, ew, ew_t, excl);
-                    if (!S.sym) wave_fill_row<G, PT, true, true>(S.out_ptr, S.out_idx, base, v, seen, pref, row0, indices_t, nullptr, indptr_t[row0 + r], lane, out_w, ew_t, nullptr, excl);
-                } else {
-                    wave_fill_row<G, PT, false, true>(S.in_ptr, S.in_idx, base, v, seen, pref, row0, indices, ind2, indptr[row0 + r], lane, nullptr, nullptr, nullptr, excl);
-                    if (!S.sym) wave_fill_row<G, PT, false, true>(S.out_ptr, S.out_idx, base, v, seen, pref, row0, indices_t, nullptr, indptr_t[row0 + r], lane, nullptr, nullptr, nullptr, excl);
-                }
-            } else if constexpr (WT) {
-                wave_fill_row<G, PT, true>(S.in_ptr, S.in_idx, base, v, seen, pref, row0, indices, ind2, indptr[row0 + r], lane, in_w, ew, ew_t);
-                if (!S.sym) wave_fill_row<G, PT, true>(S.out_ptr, S.out_idx, base, v, seen, pref, row0, indices_t, nullptr, indptr_t[row0 + r], lane, out_w, ew_t, nullptr);
-            } else {
-                wave_fill_row<G, PT>(S.in_ptr, S.in_idx, base, v, seen, pref, row0, indices, ind2, indptr[row0 + r], lane);
-                if (!S.sym) wave_fill_row<G, PT>(S.out_ptr, S.out_idx, base, v, seen, pref, row0, indices_t, nullptr, indptr_t[row0 + r], lane);
-            }
-        }
+        walk_rows<true>(S, base, nodes, ns, indptr + row0, indptr_t + row0, part, &sc[2], tid, wave, grp, gl,
+            [&](bool, bool, int, int v, int64_t ia, int64_t ib, int64_t oa, int64_t ob, int pi, int po) {
+                int excl = -1;
+                if constexpr (MASK) excl = mask_excl(v, ci, cj);      // (v < 0: a group without a row, and ci, cj >= 0)
+                group_fill_row<G, PT, WT, MASK>(ia, ib, S.in_idx, seen, pref, row0, indices, ind2, pi, grp, gl, in_w, ew, ew_t, excl);
+                if (!S.sym) group_fill_row<G, PT, WT, MASK>(oa, ob, S.out_idx, seen, pref, row0, indices_t, nullptr, po, grp, gl, out_w, ew_t, nullptr, excl);
+            },
+            [&](int r, int v) {
+                int excl = -1;
+                if constexpr (MASK) excl = mask_excl(v, ci, cj);
+                wave_fill_row<G, PT, WT, MASK>(S.in_ptr, S.in_idx, base, v, seen, pref, row0, indices, ind2, indptr[row0 + r], lane, in_w, ew, ew_t, excl);
+                if (!S.sym) wave_fill_row<G, PT, WT, MASK>(S.out_ptr, S.out_idx, base, v, seen, pref, row0, indices_t, nullptr, indptr_t[row0 + r], lane, out_w, ew_t, nullptr, excl);
+            });
     }
 }
 // Weighted batches: norm[r] = 1 / sqrt(d > 0 ? d : 1), d = the row's in-edge weights summed in edge order (k_fill knows only the count and wrote the
@@ -647,19 +606,16 @@ __global__ void k_gains(const int32_t* indptr, const int32_t* indices, const int
     if ((threadIdx.x & 63) == 0) { if (g0 > 0.f) atomicMax(gain, __float_as_uint(g0)); if (g1 > 0.f) atomicMax(gain + 1, __float_as_uint(g1)); }
 }
 
+// (weighted batches, WArgs = {EdgeW}: the table carries the edge's weight too -- enorm[e] = w[e] * norm[u] is the aggregate's whole per-edge coefficient)
+struct EdgeW { const float* ew; const float* ew_t; };      // gm_batch::d_ew
+template <typename... WArgs>
 __global__ void k_edge_tables(const int32_t* indices, const int32_t* indices_t, int64_t edges, const float* norm, const int32_t* feat_row,
-                              float* enorm, float* enorm_t, int32_t* efeat) {
+                              float* enorm, float* enorm_t, int32_t* efeat, WArgs... w_args) {
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < edges; e += (int64_t)gridDim.x * blockDim.x) {
         const int u = indices[e], v = indices_t[e];
-        enorm[e] = norm[u]; enorm_t[e] = norm[v]; efeat[e] = feat_row[u];
-    }
-}
-// (weighted batches: the table carries the edge's weight too -- enorm[e] = w[e] * norm[u] is the aggregate's whole per-edge coefficient)
-__global__ void k_edge_tables_w(const int32_t* indices, const int32_t* indices_t, int64_t edges, const float* norm, const int32_t* feat_row,
-                                const float* ew, const float* ew_t, float* enorm, float* enorm_t, int32_t* efeat) {
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < edges; e += (int64_t)gridDim.x * blockDim.x) {
-        const int u = indices[e], v = indices_t[e];
-        enorm[e] = ew[e] * norm[u]; enorm_t[e] = ew_t[e] * norm[v]; efeat[e] = feat_row[u];
+        if constexpr (sizeof...(WArgs) != 0) { const EdgeW& w = (w_args, ...); enorm[e] = w.ew[e] * norm[u]; enorm_t[e] = w.ew_t[e] * norm[v]; }
+        else { enorm[e] = norm[u]; enorm_t[e] = norm[v]; }
+        efeat[e] = feat_row[u];
     }
 }
 // ONE pass over the rows for everything the finalisation derives from the row bounds (round 6; four launches before): hub-row lists of both orientations (atomic append; the host orders them), the fused launch's per-row source table with its
@@ -667,7 +623,7 @@ __global__ void k_edge_tables_w(const int32_t* indices, const int32_t* indices_t
 // every row (k_centre_rows clears it on the centre rows afterwards).  Hub rows: in-degree (o = 0) / out-degree (o = 1) above `thr`.
 // Same pass: gm_batch::d_norm_src (the norm, sign bit set on the rows without an out-edge: nobody's source) with the count of the other rows as a third
 // per-workgroup partial, and the all-zero entries of gm_batch::d_dq_tab (k_centre_rows writes the centre rows' afterwards).
-// WT (weighted batches): the source table's w0 / w1 are ew[e] * norm[u], the products k_edge_tables_w stores for the same edges.
+// WT (weighted batches): the source table's w0 / w1 are ew[e] * norm[u], the products k_edge_tables<EdgeW> stores for the same edges.
 struct RowW { const float* ew; };      // gm_batch::d_ew[0]
 template <typename... WArgs>           // {}: the unweighted kernel, argument for argument; {RowW}: weighted batches
 __global__ void k_row_tables(const int32_t* indptr, const int32_t* indices, const int32_t* indptr_t, int64_t rows, const float* norm, const int32_t* feat_row,
@@ -1064,9 +1020,9 @@ static int finalize_launch(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
     if (b->edges > 0) {
         GM_TRY(gm_balloc(b, &b->d_enorm[0], (size_t)b->edges, s)); GM_TRY(gm_balloc(b, &b->d_enorm[1], (size_t)b->edges, s)); GM_TRY(gm_balloc(b, &b->d_efeat, (size_t)b->edges, s));
         auto edge_tables = [&](auto kern, auto... w) {
-            hipLaunchKernelGGL(kern, dim3(grid_for(b->edges, 4096)), dim3(256), 0, s, b->d_indices, b->d_indices_t, (int64_t)b->edges, b->d_norm, b->d_feat_row, w..., b->d_enorm[0], b->d_enorm[1], b->d_efeat);
+            hipLaunchKernelGGL(kern, dim3(grid_for(b->edges, 4096)), dim3(256), 0, s, b->d_indices, b->d_indices_t, (int64_t)b->edges, b->d_norm, b->d_feat_row, b->d_enorm[0], b->d_enorm[1], b->d_efeat, w...);
         };
-        if (b->weighted) edge_tables(k_edge_tables_w, b->d_ew[0], b->d_ew[1]); else edge_tables(k_edge_tables);
+        if (b->weighted) edge_tables(k_edge_tables<EdgeW>, EdgeW{b->d_ew[0], b->d_ew[1]}); else edge_tables(k_edge_tables<>);
     }
     GM_TRY(gm_balloc(b, &b->d_norm_c, b->rows, s)); GM_TRY(gm_balloc(b, &b->d_norm_src, b->rows, s));
     if (b->rows > 0) {
@@ -1242,26 +1198,24 @@ static ExPlan ex_plan(const gm_store* store, int64_t cap, bool given, int link, 
 // The instantiations a plan takes: k_nodes in four shapes (LDS with 32-bit prefix words; LDS with 16-bit ones with / without the `expanded` bitmap; global
 // bitmap), each with its symmetric-pair twin; k_fill by bitmap home and prefix width, fill_w for weighted stores (the same walk, the weights written
 // beside the indices).  The LDS kernels may need more than the default dynamic LDS (gm_func_full_lds before their launch).
-// Masked builds (GM_LINK_MASK_TARGET) take nodes_m / fill_m / fill_wm: the same shapes with the ExMask argument (ex_kernels_masked, at the end of the file).
-struct ExKernels {
-    decltype(&k_nodes<false>) nodes; decltype(&k_fill<false>) fill; decltype(&k_fill<false, false, FillW>) fill_w;
-    decltype(&k_nodes<false, false, true, false, ExMask>) nodes_m; decltype(&k_fill<false, false, ExMask>) fill_m; decltype(&k_fill<false, false, ExMask, FillW>) fill_wm;
-};
-static void ex_kernels_masked(const ExPlan& pl, ExKernels& k);
-static ExKernels ex_kernels(const ExPlan& pl, bool mask) {
+// Masked builds (GM_LINK_MASK_TARGET) take the same shapes with MASK set -- the same signatures, so the same three members.
+struct ExKernels { decltype(&k_nodes<false>) nodes; decltype(&k_fill<false>) fill; decltype(&k_fill<false, false, false, FillW>) fill_w; };
+template <bool MASK> static ExKernels ex_kernels_of(const ExPlan& pl) {
     ExKernels k = {};
-    if (mask) { ex_kernels_masked(pl, k); return k; }
     if (!pl.gpath) {
-        if (!pl.sym) { if (!pl.p16) k.nodes = k_nodes<false>; else if (pl.needx) k.nodes = k_nodes<false, true, true>; else k.nodes = k_nodes<false, true, false>; }
-        else { if (!pl.p16) k.nodes = k_nodes<false, false, true, true>; else if (pl.needx) k.nodes = k_nodes<false, true, true, true>; else k.nodes = k_nodes<false, true, false, true>; }
-        if (!pl.p16) k.fill = k_fill<false>; else k.fill = k_fill<false, true>;
-        if (!pl.p16) k.fill_w = k_fill<false, false, FillW>; else k.fill_w = k_fill<false, true, FillW>;
+        if (pl.sym) { if (!pl.p16) k.nodes = k_nodes<false, false, true, true, MASK>; else if (pl.needx) k.nodes = k_nodes<false, true, true, true, MASK>; else k.nodes = k_nodes<false, true, false, true, MASK>; }
+        else if (!pl.p16) k.nodes = k_nodes<false, false, true, false, MASK>;
+        else if constexpr (MASK) k.nodes = k_nodes<false, true, false, false, true>;      // (needx without sym is node seeds, which have no target link: that shape is not instantiated)
+        else if (pl.needx) k.nodes = k_nodes<false, true, true>; else k.nodes = k_nodes<false, true, false>;
+        if (!pl.p16) k.fill = k_fill<false, false, MASK>; else k.fill = k_fill<false, true, MASK>;
+        if (!pl.p16) k.fill_w = k_fill<false, false, MASK, FillW>; else k.fill_w = k_fill<false, true, MASK, FillW>;
     } else {
-        if (pl.sym) k.nodes = k_nodes<true, false, true, true>; else k.nodes = k_nodes<true>;
-        k.fill_w = k_fill<true, false, FillW>; k.fill = k_fill<true>;
+        if (pl.sym) k.nodes = k_nodes<true, false, true, true, MASK>; else k.nodes = k_nodes<true, false, true, false, MASK>;
+        k.fill_w = k_fill<true, false, MASK, FillW>; k.fill = k_fill<true, false, MASK>;
     }
     return k;
 }
+static ExKernels ex_kernels(const ExPlan& pl, bool mask) { return mask ? ex_kernels_of<true>(pl) : ex_kernels_of<false>(pl); }
 // One build: arguments, what the phases hand on, what it owns.  Leaving the scope frees the device scratch on the build's stream (behind every kernel that reads it), then drops the batches not released to the caller
 struct ExBuild {
     const gm_store* store; const gm_seed_t* seeds; int n_parts; const ExPart* parts; int32_t n_seeds, split;      // seeds [0, split): part 0
@@ -1342,14 +1296,11 @@ static int ex_nodes(ExBuild& x) {
         GM_TRY(x.sg.upload(x.d_given, x.nodes_flat, sizeof(int32_t) * tot));
         GM_TRY(x.sg.upload(x.d_given_off, x.nodes_off, sizeof(int64_t) * (n + 1)));
     }
-    if (!pl.gpath) GM_TRY(gm_func_full_lds(x.mask ? (const void*)x.kern.nodes_m : (const void*)x.kern.nodes));
+    if (!pl.gpath) GM_TRY(gm_func_full_lds((const void*)x.kern.nodes));
     gm_prof_begin(GM_PROF_EX_NODES, st, n);
     if (pl.gpath) GM_TRY(gm_alloc(&x.d_gbits, (size_t)n * 2 * pl.Wmax, st));
-    auto launch = [&](auto kern, auto... m) {
-        hipLaunchKernelGGL(kern, dim3(n), dim3(EX_BLOCK), pl.lds_a, st, x.S, x.d_seeds, n, x.h, x.sample_nodes, x.rng_seed, x.link ? 1 : 0,
-                           x.d_given, x.d_given_off, (int)pl.cap, x.d_nodes, x.d_degi, x.d_dego, x.d_nsub, x.d_esub, pl.Wmax, x.d_gbits, m...);
-    };
-    if (x.mask) launch(x.kern.nodes_m, ExMask{1}); else launch(x.kern.nodes);
+    hipLaunchKernelGGL(x.kern.nodes, dim3(n), dim3(EX_BLOCK), pl.lds_a, st, x.S, x.d_seeds, n, x.h, x.sample_nodes, x.rng_seed, x.link ? 1 : 0,
+                       x.d_given, x.d_given_off, (int)pl.cap, x.d_nodes, x.d_degi, x.d_dego, x.d_nsub, x.d_esub, pl.Wmax, x.d_gbits);
     gm_prof_end(GM_PROF_EX_NODES, st);
     GM_HIP(hipGetLastError());
     x.nsub = x.sg.download(x.d_nsub, (size_t)n); x.esub = x.sg.download(x.d_esub, (size_t)n);
@@ -1411,7 +1362,7 @@ static int ex_size_parts(ExBuild& x) {
 static int ex_fill(ExBuild& x) {
     const ExPlan& pl = x.pl; hipStream_t st = x.st; const int32_t n = x.n_seeds;
     const bool weighted = x.store->weighted;
-    if (!pl.gpath) GM_TRY(gm_func_full_lds(x.mask ? (weighted ? (const void*)x.kern.fill_wm : (const void*)x.kern.fill_m) : (weighted ? (const void*)x.kern.fill_w : (const void*)x.kern.fill)));
+    if (!pl.gpath) GM_TRY(gm_func_full_lds(weighted ? (const void*)x.kern.fill_w : (const void*)x.kern.fill));
     auto launch = [&](auto kern, auto... w) {
         hipLaunchKernelGGL(kern, dim3(n), dim3(EX_BLOCK), pl.lds_b, st, x.S, x.d_seeds, n, x.link ? 1 : 0, (int)pl.cap, x.d_nodes, x.d_degi, x.d_dego, x.fo[0], x.fo[1], (int)x.split,
                            pl.Wmax, x.d_gbits, x.d_order, w...);
@@ -1420,11 +1371,10 @@ static int ex_fill(ExBuild& x) {
     if (weighted) {
         gm_batch* b0 = x.bs[0].get(); gm_batch* b1 = x.bs[x.n_parts - 1].get();
         const FillW fw{x.store->d_in_w, x.store->d_out_w, {b0->d_ew[0], b0->d_ew[1]}, {b1->d_ew[0], b1->d_ew[1]}};
-        if (x.mask) launch(x.kern.fill_wm, ExMask{1}, fw); else launch(x.kern.fill_w, fw);
+        launch(x.kern.fill_w, fw);
         for (int p = 0; p < x.n_parts; ++p)
             if (gm_batch* b = x.bs[p].get(); b->rows > 0) hipLaunchKernelGGL(k_weighted_norm, dim3(grid_for(b->rows, 2048)), dim3(256), 0, st, b->d_indptr, b->d_ew[0], (int64_t)b->rows, b->d_norm);
-    } else if (x.mask) launch(x.kern.fill_m, ExMask{1});
-    else launch(x.kern.fill);
+    } else launch(x.kern.fill);
     gm_prof_end(GM_PROF_EX_FILL, st);
     GM_HIP(hipGetLastError());
     return GM_OK;
@@ -1549,19 +1499,4 @@ int gm_gather_rows(const gm_batch* b, const int32_t* feat_row, int64_t n, int F,
 extern "C" int gm_gather_features(const gm_batch_t* b, float* x_out, void* stream) {
     GM_REQUIRE(b && x_out, GM_EINVAL, "gather_features: NULL argument");
     return gm_gather_rows(b, b->d_feat_row, b->rows, b->feat_dim, x_out, (hipStream_t)stream);
-}
-
-// ================================================================================ GM_LINK_MASK_TARGET: the masked instantiations of k_nodes / k_fill
-// Instantiated HERE, behind every kernel a build without the flag launches: those keep their place in the code object (see the ragged-task kernels of
-// model.hip).  Only the reachable shapes: reference pairs and given node lists never keep the `expanded` bitmap beside 16-bit prefix words.
-static void ex_kernels_masked(const ExPlan& pl, ExKernels& k) {
-    if (!pl.gpath) {
-        if (!pl.sym) { if (!pl.p16) k.nodes_m = k_nodes<false, false, true, false, ExMask>; else k.nodes_m = k_nodes<false, true, false, false, ExMask>; }
-        else { if (!pl.p16) k.nodes_m = k_nodes<false, false, true, true, ExMask>; else if (pl.needx) k.nodes_m = k_nodes<false, true, true, true, ExMask>; else k.nodes_m = k_nodes<false, true, false, true, ExMask>; }
-        if (!pl.p16) k.fill_m = k_fill<false, false, ExMask>; else k.fill_m = k_fill<false, true, ExMask>;
-        if (!pl.p16) k.fill_wm = k_fill<false, false, ExMask, FillW>; else k.fill_wm = k_fill<false, true, ExMask, FillW>;
-    } else {
-        if (pl.sym) k.nodes_m = k_nodes<true, false, true, true, ExMask>; else k.nodes_m = k_nodes<true, false, true, false, ExMask>;
-        k.fill_wm = k_fill<true, false, ExMask, FillW>; k.fill_m = k_fill<true, false, ExMask>;
-    }
 }

@@ -1,7 +1,8 @@
 """GPU (-m gpu): the extraction kernels' two bitmap homes build the same batches.  Store A holds a small graph G, store B the same G followed by a
 700,000-node ring: B's largest graph is beyond what the LDS bitmap pair takes (~643k nodes), so every build on B runs the global-bitmap instantiations
 of k_nodes / k_fill and every build on A the LDS ones.  All seeds lie in graph 0: the two builds must agree in the dimensions and in every GM_F_* field,
-floats compared as bit patterns -- for node seeds, pairs, symmetric pairs, given node lists, the two-part build, hop labels and weighted stores.  The
+floats compared as bit patterns -- for node seeds, pairs, symmetric pairs, given node lists, the two-part build, hop labels, weighted stores and masked
+pairs on them (the *_pref32 cases: the LDS side with GM_EXTRACT_PREF16 = 0, the 32-bit-prefix instantiations of symmetric pairs and of the weighted fill).  The
 32-bit-prefix LDS kernels (GM_EXTRACT_PREF16=0, read once per process) are held against the default build from a fresh child process."""
 import os
 import subprocess
@@ -43,6 +44,16 @@ def _seeds(pairs):
     return np.stack([np.zeros(12, np.int64), i, j], 1)
 
 
+def _adjacent_seeds():
+    """_seeds(True) with the first eight pairs (the hubs among them) moved onto edges of G: a target-link mask has work to do"""
+    from gmeta_amd import synth
+    e = synth.pa_edges(N, 3, np.random.default_rng(11))                # G's edges, as _graphs draws them
+    s = _seeds(True)
+    for k in range(8):
+        s[k, 2] = np.concatenate([e[e[:, 0] == s[k, 1], 1], e[e[:, 1] == s[k, 1], 0]])[0]
+    return s
+
+
 def _fields(b):
     """dims and every GM_F_* field the batch carries, floats as their bit patterns"""
     from gmeta_amd import _lib as L
@@ -72,6 +83,20 @@ def _build(case, store):
     from gmeta_amd.subgraphs import SubgraphBatch, hop_labels_switch
     if case in ('nodes_h2', 'weighted'):
         return _node_case(store)
+    if case.endswith('_pref32'):
+        lib = _lib.lib()
+        prev = lib.gm_get_tuning(b'GM_EXTRACT_PREF16')
+        _lib.check(lib.gm_set_tuning(b'GM_EXTRACT_PREF16', 0), 'gm_set_tuning')
+        try:
+            return _build(case[:-len('_pref32')], store)
+        finally:
+            lib.gm_set_tuning(b'GM_EXTRACT_PREF16', prev)
+    if case == 'weighted_pairs':
+        return [SubgraphBatch.extract(store, _adjacent_seeds(), [0, 12], 2, SAMPLE, 222, True)]
+    if case == 'masked_weighted':
+        return [SubgraphBatch.extract(store, _adjacent_seeds(), [0, 12], 2, SAMPLE, 222, 1 | _lib.LINK_MASK_TARGET)]
+    if case == 'symmetric_h3':
+        return [SubgraphBatch.extract(store, _seeds(True), [0, 12], 3, SAMPLE, 222, _lib.LINK_SYMMETRIC)]
     if case == 'nodes_h3':
         return _node_case(store, 3)
     if case == 'pairs':
@@ -102,9 +127,10 @@ def stores():
     return get
 
 
-@pytest.mark.parametrize('case', ['nodes_h2', 'nodes_h3', 'pairs', 'symmetric_h2', 'from_nodes', 'extract_pair', 'hop_labels', 'weighted'])
+@pytest.mark.parametrize('case', ['nodes_h2', 'nodes_h3', 'pairs', 'symmetric_h2', 'symmetric_h3', 'from_nodes', 'extract_pair', 'hop_labels', 'weighted',
+                                  'symmetric_h2_pref32', 'weighted_pairs_pref32', 'masked_weighted', 'masked_weighted_pref32'])
 def test_global_bitmap_build_equals_lds_build(stores, case):
-    w = case == 'weighted'
+    w = 'weighted' in case
     got = [[_fields(b) for b in _build(case, stores(w, ring))] for ring in (False, True)]
     assert len(got[0]) == len(got[1])
     for x, y in zip(*got):
@@ -114,6 +140,10 @@ def test_global_bitmap_build_equals_lds_build(stores, case):
     if case in ('nodes_h2', 'nodes_h3', 'weighted'):
         sizes = np.diff(got[0][0]['f0'])                               # a thinned neighbourhood keeps sample_nodes nodes, and its centre
         assert (sizes >= SAMPLE).any() and (case == 'nodes_h3' or (sizes < SAMPLE).any()), sizes      # h = 2: two of the seeds reach 21 nodes, the others 100 and more
+    if case.startswith('masked_weighted'):                             # the same node sets, and the mask took edges away
+        from gmeta_amd import _lib
+        plain, par = _fields(_build('weighted_pairs', stores(True, False))[0]), 'f%d' % _lib.F_PARENT
+        assert np.array_equal(plain[par], got[0][0][par]) and got[0][0]['dims'][1] < plain['dims'][1]
 
 
 def _dump(path):
