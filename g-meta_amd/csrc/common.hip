@@ -365,6 +365,7 @@ const gm_knobs& gm_knob() {
         k.agg_stream = env("GM_AGG_STREAM", 1);
         k.agg_stream_min_rows = env("GM_AGG_STREAM_MIN_ROWS", 100000);
         k.neg_round = env("GM_NEG_ROUND", 0);
+        k.pair_lanes = env("GM_PAIR_LANES", 0);
     });
     return k;
 }
@@ -382,6 +383,7 @@ static int gm_knobs::* gm_find_knob(const char* name) {
         {"GM_SPLIT16_MIN_ROWS", &gm_knobs::split16_min_rows}, {"GM_WGRAD_SPLIT_MIN_CHUNKS", &gm_knobs::wgrad_split_min_chunks}, {"GM_TIMING", &gm_knobs::timing},
         {"GM_FUSE_DIFF", &gm_knobs::fuse_diff}, {"GM_EXTRACT_PREF16", &gm_knobs::extract_pref16},
         {"neg_round", &gm_knobs::neg_round}, {"GM_NEG_ROUND", &gm_knobs::neg_round},
+        {"pair_lanes", &gm_knobs::pair_lanes}, {"GM_PAIR_LANES", &gm_knobs::pair_lanes},
     };
     for (const auto& e : tab)
         if (!strcmp(name, e.name)) return e.field;

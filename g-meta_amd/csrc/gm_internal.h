@@ -60,6 +60,17 @@ struct gm_store {
     // entry 2^r below its bound keeps min(22, 39 - r) bits, so a table whose largest entry sits more than 2^14 above its typical one (or is
     // not finite / above 2^50) would lose precision silently
     std::vector<float> h_feat_amax, h_feat_mean;
+    // neighbour index of the pair scores (pair_scores.hip; definition: include/gmeta_hip.h): per node the ascending DISTINCT row of its in- and out-neighbours
+    // without itself, and the per-node terms.  Built at the first call that needs it, under nbr_mu, and complete on the device before nbr_ready is set:
+    // afterwards any stream reads it without an event.  Freed by gm_store_destroy.
+    mutable std::mutex nbr_mu;
+    mutable bool nbr_ready = false;
+    mutable int64_t* d_nbr_ptr = nullptr;     // [total_nodes + 1] offsets into d_nbr_idx, rows = global node ids
+    mutable int32_t* d_nbr_idx = nullptr;     // [<= 2 total_edges] neighbour, LOCAL to its graph, ascending inside a row
+    mutable int32_t* d_nbr_deg = nullptr;     // [total_nodes] deg = row length
+    mutable float* d_nbr_aa = nullptr;        // [total_nodes] 1 / ln(deg), deg >= 2, else 0
+    mutable float* d_nbr_ra = nullptr;        // [total_nodes] 1 / deg, deg >= 1, else 0
+    mutable std::vector<int64_t> nbr_off;     // [n_graphs + 1] host prefix of the row lengths per graph (mean distinct degree -> lanes per pair)
 };
 
 // Receptive-field tables (cone.hip): level l = rows whose layer-l activation reaches a centre.
@@ -246,6 +257,7 @@ struct gm_knobs {
     int agg_stream;                // GM_AGG_STREAM: eligible full aggregate launches take the LDS-DMA stream kernel (agg_stream.hip)
     int agg_stream_min_rows;       // GM_AGG_STREAM_MIN_ROWS: smallest batch (rows) that builds stream tables; dense batches (more than 8 edges per row) never do
     int neg_round;                 // GM_NEG_ROUND, gm_set_tuning("neg_round"): candidates per round of gm_store_negative_pairs (negatives.hip); 0 (default) = by the call's n.  The result does not depend on it
+    int pair_lanes;                // GM_PAIR_LANES, gm_set_tuning("pair_lanes"): lanes per pair of gm_store_pair_scores (pair_scores.hip): 16, 32 or 64; 0 (default) = by the graph's mean distinct degree
 };
 const gm_knobs& gm_knob();
 

@@ -146,6 +146,29 @@ class GraphStore:
         _lib.check(_lib.lib().gm_store_has_edges(self.handle, g, _lib.ptr(d_p), len(p), _lib.ptr(out), _lib.stream_ptr()), 'gm_store_has_edges')
         return out.cpu().numpy().astype(bool)
 
+    def pair_scores(self, g, pairs, mask_target=False):
+        """float32 [m, 5]: the neighbourhood heuristics of the [m, 2] node `pairs` of graph `g`, columns gmeta_amd.PAIR_SCORES = (cn, jaccard, adamic_adar,
+        resource_allocation, pref_attachment), computed on the device (gm_store_pair_scores; the definition is in include/gmeta_hip.h, tests/pair_score_ref.py
+        restates it).  Neighbourhoods are distinct nodes joined by an edge in either direction, self loops and weights aside; a pair may come in any
+        orientation.  mask_target=True scores an adjacent pair as if its own edge were absent (both degrees one less): pass it when the positive pairs are
+        edges of the graph, as with Subgraphs(mask_target=True)."""
+        import torch
+        g, p = self._pairs_of(g, pairs, 'pair_scores')
+        out = torch.empty((len(p), 5), dtype=torch.float32, device='cuda')
+        if len(p):
+            d_p = torch.from_numpy(np.ascontiguousarray(p, np.int32)).cuda()
+            _lib.check(_lib.lib().gm_store_pair_scores(self.handle, g, _lib.ptr(d_p), len(p), _lib.PAIR_MASK_TARGET if mask_target else 0, _lib.ptr(out),
+                                                       _lib.stream_ptr()), 'gm_store_pair_scores')
+        return out.cpu().numpy()
+
+    def neighbour_degrees(self, g):
+        """int32 [N]: the number of distinct neighbours (either direction, itself aside) of every node of graph `g` -- the degrees the pair scores use."""
+        import torch
+        g, _ = self._pairs_of(g, [], 'neighbour_degrees')
+        out = torch.empty(self.n_nodes[g], dtype=torch.int32, device='cuda')
+        _lib.check(_lib.lib().gm_store_neighbour_degrees(self.handle, g, _lib.ptr(out), _lib.stream_ptr()), 'gm_store_neighbour_degrees')
+        return out.cpu().numpy()
+
     def close(self):
         if getattr(self, 'handle', None):
             _lib.lib().gm_store_destroy(self.handle)

@@ -1,0 +1,45 @@
+"""Neighbourhood heuristics as a link-prediction baseline: the scores of GraphStore.pair_scores (gm_store_pair_scores; the definition is in
+include/gmeta_hip.h) turned into the ROC AUC a learned link predictor is held against.  The scores come from the device; the AUC is host work over
+one number per pair."""
+import numpy as np
+
+from .negatives import _pair
+
+PAIR_SCORES = ('cn', 'jaccard', 'adamic_adar', 'resource_allocation', 'pref_attachment')      # the columns of GraphStore.pair_scores, in order
+
+
+def link_auc(scores, labels):
+    """ROC AUC of `scores` against the 0 / 1 `labels` (numbers or the tables' strings) in the Mann-Whitney form: the positives' rank sum, tied scores
+    sharing the average of their ranks -- the probability that a positive outranks a negative, a tie counting one half.  ValueError unless both labels
+    occur, on any other label and on a score that is not finite."""
+    s = np.asarray(scores, np.float64).reshape(-1)
+    y = np.asarray(labels).reshape(-1).astype(np.int64)
+    if len(s) != len(y):
+        raise ValueError('link_auc: %d scores, %d labels' % (len(s), len(y)))
+    if not np.isin(y, (0, 1)).all():
+        raise ValueError('link_auc: labels must be 0 or 1')
+    n_pos = int(y.sum()); n_neg = len(y) - n_pos
+    if n_pos == 0 or n_neg == 0:
+        raise ValueError('link_auc needs both labels: %d positive(s), %d negative(s)' % (n_pos, n_neg))
+    if not np.isfinite(s).all():
+        raise ValueError('link_auc: a score is not finite')
+    _, inv, cnt = np.unique(s, return_inverse=True, return_counts=True)
+    rank = (np.cumsum(cnt) - (cnt - 1) / 2.0)[inv]                  # 1-based; a tie group shares the mean of the ranks it spans
+    return float((rank[y == 1].sum() - n_pos * (n_pos + 1) / 2.0) / (float(n_pos) * n_neg))
+
+
+def link_heuristic_scores(store, names, mask_target=False):
+    """float32 [len(names), 5]: GraphStore.pair_scores of the pairs named 'g_i_j', one call per graph, rows in the order of `names`."""
+    trip = np.asarray([_pair(nm) for nm in names], np.int64).reshape(-1, 3)
+    out = np.zeros((len(trip), len(PAIR_SCORES)), np.float32)
+    for g in np.unique(trip[:, 0]).tolist():
+        at = np.nonzero(trip[:, 0] == g)[0]
+        out[at] = store.pair_scores(g, trip[at, 1:], mask_target=mask_target)
+    return out
+
+
+def link_heuristic_auc(store, names, labels, mask_target=False):
+    """{score name: ROC AUC} of the five heuristics over the pairs `names` ('g_i_j') with the 0 / 1 `labels` of a link table, all graphs together.
+    mask_target as in GraphStore.pair_scores: pass True when the positive pairs are edges of the store's graphs."""
+    sc = link_heuristic_scores(store, names, mask_target)
+    return {nm: link_auc(sc[:, k], labels) for k, nm in enumerate(PAIR_SCORES)}

@@ -129,6 +129,36 @@ int32_t gm_store_negative_pairs(const gm_store_t* s, int32_t g, int64_t n, uint6
                                 int64_t n_exclude, int32_t* d_out_pairs, int64_t* h_found, void* stream);
 int32_t gm_store_has_edges(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, uint8_t* d_out, void* stream);
 
+/* ---- NEIGHBOURHOOD HEURISTIC SCORES of node pairs (beyond the reference): the numbers a learned link predictor is held against -- common neighbours,
+ * Jaccard, Adamic-Adar, resource allocation, preferential attachment -- for n pairs of one parent graph, on the device.  This comment is THE definition;
+ * tests/pair_score_ref.py restates it with Python sets and fp64 sums.  Per parent graph g of a store, with N nodes:
+ *   neighbourhood  G(x) = { z != x : the graph holds an edge x -> z or z -> x }: DISTINCT nodes -- parallel copies count once, self loops never count,
+ *                  edge weights are ignored.  deg(x) = |G(x)|.
+ *   node terms     w_aa(z) = 1 / ln(deg z) for deg z >= 2, else 0;  w_ra(z) = 1 / deg z for deg z >= 1, else 0: computed in double, rounded once to fp32.
+ *   pairs          d_pairs: device int32 [n, 2].  A pair (a, b) may come in any orientation and a == b is allowed; it is canonicalised to (min, max)
+ *                  first, so the result is bitwise the same for (a, b) and (b, a).
+ *   mask flag      GM_PAIR_MASK_TARGET (1) in `flags` scores the pair as if no edge joined a and b (it mirrors GM_LINK_MASK_TARGET): with the flag, when
+ *                  a != b and b in G(a), da = deg a - 1 and db = deg b - 1; otherwise -- and always without the flag -- da = deg a, db = deg b.
+ *   five scores    I = G(a) & G(b) (it never holds a or b when a != b; for a == b it is G(a)).  d_out: device fp32 [n, 5], columns
+ *                    0  cn                  = |I|
+ *                    1  jaccard             = |I| / U, 0 when U == 0;  a != b: U = da + db - |I|;  a == b: U = deg a
+ *                    2  adamic_adar         = sum of w_aa(z) over z in I
+ *                    3  resource_allocation = sum of w_ra(z) over z in I
+ *                    4  pref_attachment     = (float)((int64)da * db)
+ *   out of range   a node id outside the graph gives five zeros, as gm_store_has_edges gives 0.
+ *   exactness      cn and pref_attachment are exact (the integer, rounded once to fp32).  Columns 1-3 are fp32 quotients / sums; the order of a sum belongs
+ *                  to the launch configuration (lanes per pair: the library picks it per launch from the graph's mean distinct degree;
+ *                  gm_set_tuning("pair_lanes", L) with L in {16, 32, 64} forces one, 0 restores the library's choice).  For one configuration two runs
+ *                  are bitwise identical: no float atomics, nothing depends on arrival order.
+ * The scores read a neighbour index of the store -- per node the ascending distinct G row, deg, w_aa, w_ra; at most 2 |E| ints + 20 bytes per node --
+ * built once per store by the first call that needs it (on the host, under a lock, and complete on the device before that call goes on: later calls read
+ * it from any stream) and freed by gm_store_destroy.  Both calls run on `stream`; n == 0 is a no-op.
+ * gm_store_neighbour_degrees: deg(x) of every node of graph g, device int32 [N].
+ * GM_EINVAL: a bad graph index, n < 0, unknown flag bits, a pair_lanes value that is no instantiation. */
+#define GM_PAIR_MASK_TARGET 1
+int32_t gm_store_pair_scores(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, float* d_out, void* stream);
+int32_t gm_store_neighbour_degrees(const gm_store_t* s, int32_t g, int32_t* d_out, void* stream);
+
 /* ---- Extraction: replaces Subgraphs.generate_subgraph / generate_subgraph_link_pred
  * (sdp.py:295-346: h-hop in-neighbour expansion, node sampling, G.subgraph) and dgl.batch
  * (sdp.py:399-406) for n_sets sets at once.  seeds/set_offsets are host arrays; set s owns seeds

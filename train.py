@@ -66,6 +66,10 @@ def parse(argv=None):
                     help="where the negative pairs of a link data set come from (--link_pred_mode True): 'file' = the CSV tables hold them, as the reference's do; "
                          "'uniform' / 'two_hop' = the tables hold the positive pairs only and as many negatives are drawn on the GPU from each graph's non-edges "
                          "(GraphStore.negative_pairs), the same on every rank; meant for --mask_target 1")
+    ap.add_argument('--heuristics', type=int, default=0, choices=[0, 1],
+                    help='1 (--link_pred_mode True): after the test evaluation, print the ROC AUC of the five neighbourhood heuristics (common neighbours, Jaccard, '
+                         'Adamic-Adar, resource allocation, preferential attachment; GraphStore.pair_scores) over the pairs of the test table -- the baseline a '
+                         'learned link predictor is held against; follows --mask_target')
     ap.add_argument('--readout', default='centre', choices=['centre', 'mean'],
                     help="what the head reads of every subgraph: 'centre' = the centre row (both endpoints' rows of a pair), as the reference; 'mean' = the mean "
                          "over all of its rows (the dgl.mean_nodes line the reference left commented out), one pooled vector for pairs too")
@@ -94,6 +98,8 @@ def main(args):
         root = os.path.join(root, 'task' + str(args.task_n)) + '/'
     info = datadir.load_labels(root)
     store = gmeta_amd.GraphStore(graphs, feat)
+    if args.heuristics and args.link_pred_mode != 'True':
+        raise SystemExit('--heuristics 1 scores node PAIRS: it needs --link_pred_mode True')
     tables = None
     if args.negatives != 'file':
         if args.link_pred_mode != 'True':
@@ -183,7 +189,15 @@ def main(args):
         print('Total Time:', str(time.time() - s_start)[:5])
     if args.predict_out and rank == 0:
         write_predictions(args.predict_out, model_max, db_test, info)
-    return {'test_acc': float(accs[-1]), 'early_stopped_test_acc': float(accs_max[-1]), 'val_best': float(max_acc)}
+    res = {'test_acc': float(accs[-1]), 'early_stopped_test_acc': float(accs_max[-1]), 'val_best': float(max_acc)}
+    if args.heuristics:
+        # the test table as the run used it: completed by --negatives where that drew the negative pairs, else the CSV's own
+        from gmeta_amd.negatives import read_link_tables
+        names, labels = (tables if tables is not None else read_link_tables(root))['test']
+        res['heuristic_auc'] = gmeta_amd.link_heuristic_auc(store, names, labels, mask_target=bool(args.mask_target))
+        if rank == 0:
+            print('Heuristic test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['heuristic_auc'].items()))
+    return res
 
 
 def write_predictions(path, model, db, info):
