@@ -40,6 +40,7 @@ PROTOTYPES = {
     'gm_store_has_edges': (i32, [vp, i32, vp, i64, vp, vp]),
     'gm_store_pair_scores': (i32, [vp, i32, vp, i64, i32, vp, vp]),
     'gm_store_neighbour_degrees': (i32, [vp, i32, vp, vp]),
+    'gm_store_pair_candidates': (i32, [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp]),
     'gm_extract': (C.c_int, [vp, vp, i32, vp, i32, i32, i32, u64, i32, vp, vp]),
     'gm_extract_pair': (C.c_int, [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, u64, i32, vp, vp, vp]),
     'gm_batch_from_nodes': (C.c_int, [vp, vp, i32, vp, i32, vp, vp, i32, vp, vp]),

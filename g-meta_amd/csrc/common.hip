@@ -366,6 +366,8 @@ const gm_knobs& gm_knob() {
         k.agg_stream_min_rows = env("GM_AGG_STREAM_MIN_ROWS", 100000);
         k.neg_round = env("GM_NEG_ROUND", 0);
         k.pair_lanes = env("GM_PAIR_LANES", 0);
+        k.cand_round = env("GM_CAND_ROUND", 0);
+        k.cand_bitmap = env("GM_CAND_BITMAP", 0);
     });
     return k;
 }
@@ -384,6 +386,8 @@ static int gm_knobs::* gm_find_knob(const char* name) {
         {"GM_FUSE_DIFF", &gm_knobs::fuse_diff}, {"GM_EXTRACT_PREF16", &gm_knobs::extract_pref16},
         {"neg_round", &gm_knobs::neg_round}, {"GM_NEG_ROUND", &gm_knobs::neg_round},
         {"pair_lanes", &gm_knobs::pair_lanes}, {"GM_PAIR_LANES", &gm_knobs::pair_lanes},
+        {"cand_round", &gm_knobs::cand_round}, {"GM_CAND_ROUND", &gm_knobs::cand_round},
+        {"cand_bitmap", &gm_knobs::cand_bitmap}, {"GM_CAND_BITMAP", &gm_knobs::cand_bitmap},
     };
     for (const auto& e : tab)
         if (!strcmp(name, e.name)) return e.field;

@@ -258,8 +258,15 @@ struct gm_knobs {
     int agg_stream_min_rows;       // GM_AGG_STREAM_MIN_ROWS: smallest batch (rows) that builds stream tables; dense batches (more than 8 edges per row) never do
     int neg_round;                 // GM_NEG_ROUND, gm_set_tuning("neg_round"): candidates per round of gm_store_negative_pairs (negatives.hip); 0 (default) = by the call's n.  The result does not depend on it
     int pair_lanes;                // GM_PAIR_LANES, gm_set_tuning("pair_lanes"): lanes per pair of gm_store_pair_scores (pair_scores.hip): 16, 32 or 64; 0 (default) = by the graph's mean distinct degree
+    int cand_round;                // GM_CAND_ROUND, gm_set_tuning("cand_round"): pairs per round of gm_store_pair_candidates (candidates.hip); 0 (default) = the library's choice.  The result does not depend on it
+    int cand_bitmap;               // GM_CAND_BITMAP, gm_set_tuning("cand_bitmap"): home of that call's membership bitmap: 1 LDS, 2 a per-workgroup slab in HBM; 0 (default) = LDS wherever the graph fits.  The result does not depend on it
 };
 const gm_knobs& gm_knob();
+
+// ---- the neighbour index and the pair-score launch (pair_scores.hip), for the translation units that score pairs of their own (candidates.hip)
+int gm_nbr_index(const gm_store* s);                                                      // builds the index at first use (under gm_store::nbr_mu); complete on the device on return
+int gm_pair_lanes(const gm_store* s, int32_t g, const char* what, int* lpp);              // GM_EINVAL for a pair_lanes knob that is no instantiation; *lpp (optional; needs the index) = the lanes per pair in force
+int gm_pair_scores_launch(const gm_store* s, int32_t g, int lpp, const int32_t* d_pairs, int64_t n, int mask, float* d_out, hipStream_t st);      // k_pair_scores<lpp> over n pairs of graph g
 
 // ---- host phase timing for the setup paths (env GM_TIMING=1 prints to stderr)
 #include <chrono>

@@ -133,7 +133,7 @@ static int nbr_build(const gm_store* s) {
     return GM_OK;
 }
 
-static int nbr_index(const gm_store* s) {
+int gm_nbr_index(const gm_store* s) {
     std::lock_guard<std::mutex> lk(s->nbr_mu);
     if (s->nbr_ready) return GM_OK;
     GM_TRY(nbr_build(s));
@@ -155,23 +155,18 @@ static int pair_lanes_for(const gm_store* s, int32_t g) {
     return nnz <= 192 * N ? 16 : nnz <= 384 * N ? 32 : 64;
 }
 
-extern "C" int32_t gm_store_pair_scores(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, float* d_out, void* stream) {
-    const char* what = "gm_store_pair_scores";
-    GM_TRY(pair_graph_of(s, g, what));
-    GM_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX, GM_EINVAL, "%s: n = %lld", what, (long long)n);
-    GM_REQUIRE((flags & ~GM_PAIR_MASK_TARGET) == 0, GM_EINVAL, "%s: unknown flag bits 0x%x (GM_PAIR_MASK_TARGET = 1)", what, (unsigned)flags);
+int gm_pair_lanes(const gm_store* s, int32_t g, const char* what, int* lpp) {
     const int forced = gm_knob().pair_lanes;
     GM_REQUIRE(forced == 0 || forced == 16 || forced == 32 || forced == 64, GM_EINVAL,
                "%s: pair_lanes = %d; the kernel is built for 16, 32 and 64 lanes per pair (0: the library's choice)", what, forced);
-    if (n == 0) return GM_OK;
-    GM_REQUIRE(d_pairs && d_out, GM_EINVAL, "%s: NULL argument", what);
-    GM_TRY(nbr_index(s));
+    if (lpp) *lpp = forced ? forced : pair_lanes_for(s, g);
+    return GM_OK;
+}
+
+int gm_pair_scores_launch(const gm_store* s, int32_t g, int lpp, const int32_t* d_pairs, int64_t n, int mask, float* d_out, hipStream_t st) {
     const int64_t no = s->node_off[g];
     const pair_graph G = {s->d_nbr_ptr + no, s->d_nbr_idx, s->d_nbr_aa + no, s->d_nbr_ra + no, s->node_off[g + 1] - no};
-    const int lpp = forced ? forced : pair_lanes_for(s, g);
     const dim3 grid((unsigned)((n * lpp + GM_PAIR_THREADS - 1) / GM_PAIR_THREADS)), block(GM_PAIR_THREADS);      // n <= 2^31 - 1 pairs of at most 64 lanes: below 2^29 blocks
-    hipStream_t st = (hipStream_t)stream;
-    const int mask = flags & GM_PAIR_MASK_TARGET;
     if (lpp == 16) hipLaunchKernelGGL(k_pair_scores<16>, grid, block, 0, st, G, d_pairs, n, mask, d_out);
     else if (lpp == 32) hipLaunchKernelGGL(k_pair_scores<32>, grid, block, 0, st, G, d_pairs, n, mask, d_out);
     else hipLaunchKernelGGL(k_pair_scores<64>, grid, block, 0, st, G, d_pairs, n, mask, d_out);
@@ -179,11 +174,25 @@ extern "C" int32_t gm_store_pair_scores(const gm_store_t* s, int32_t g, const in
     return GM_OK;
 }
 
+extern "C" int32_t gm_store_pair_scores(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, float* d_out, void* stream) {
+    const char* what = "gm_store_pair_scores";
+    GM_TRY(pair_graph_of(s, g, what));
+    GM_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX, GM_EINVAL, "%s: n = %lld", what, (long long)n);
+    GM_REQUIRE((flags & ~GM_PAIR_MASK_TARGET) == 0, GM_EINVAL, "%s: unknown flag bits 0x%x (GM_PAIR_MASK_TARGET = 1)", what, (unsigned)flags);
+    GM_TRY(gm_pair_lanes(s, g, what, nullptr));
+    if (n == 0) return GM_OK;
+    GM_REQUIRE(d_pairs && d_out, GM_EINVAL, "%s: NULL argument", what);
+    GM_TRY(gm_nbr_index(s));
+    int lpp = 0;
+    GM_TRY(gm_pair_lanes(s, g, what, &lpp));                                             // (the library's choice reads the index's row lengths)
+    return gm_pair_scores_launch(s, g, lpp, d_pairs, n, flags & GM_PAIR_MASK_TARGET, d_out, (hipStream_t)stream);
+}
+
 extern "C" int32_t gm_store_neighbour_degrees(const gm_store_t* s, int32_t g, int32_t* d_out, void* stream) {
     const char* what = "gm_store_neighbour_degrees";
     GM_TRY(pair_graph_of(s, g, what));
     GM_REQUIRE(d_out, GM_EINVAL, "%s: d_out is NULL", what);
-    GM_TRY(nbr_index(s));
+    GM_TRY(gm_nbr_index(s));
     const int64_t no = s->node_off[g], N = s->node_off[g + 1] - no;
     GM_HIP(hipMemcpyAsync(d_out, s->d_nbr_deg + no, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return GM_OK;

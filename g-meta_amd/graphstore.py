@@ -169,6 +169,36 @@ class GraphStore:
         _lib.check(_lib.lib().gm_store_neighbour_degrees(self.handle, g, _lib.ptr(out), _lib.stream_ptr()), 'gm_store_neighbour_degrees')
         return out.cpu().numpy()
 
+    def link_candidates(self, g, nodes, k=10, score='adamic_adar'):
+        """Candidate partners of the `nodes` of graph `g` for a link predictor: per node the nodes at distance exactly two (not adjacent, at least one shared
+        neighbour; neighbourhoods as in pair_scores), ranked by the heuristic `score` (a name of gmeta_amd.PAIR_SCORES) descending, equal scores by ascending
+        node id, the best `k` (1..1024) kept -- enumerated, scored and selected on the device (gm_store_pair_candidates; the definition is in
+        include/gmeta_hip.h, tests/candidate_ref.py restates it).  -> (partners int64 [m, k], scores float32 [m, k], totals int64 [m]): row r holds the first
+        min(k, totals[r]) partners of nodes[r] and their scores, -1 / 0.0 behind them; totals[r] is the size of the whole candidate set.  The scores are those
+        pair_scores gives for the same pairs, bit for bit.  gmeta_amd.candidate_names turns the partners into the names Subgraphs.query_batch takes."""
+        from .heuristics import PAIR_SCORES
+        if score not in PAIR_SCORES:
+            raise ValueError('link_candidates: score must be one of %s, not %r' % (', '.join(PAIR_SCORES), score))
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError('link_candidates: k = %d; 1 .. 1024' % k)
+        import torch
+        g = int(g)
+        if not 0 <= g < self.n_graphs:
+            raise ValueError('link_candidates: graph %d of a store with %d graph(s)' % (g, self.n_graphs))
+        a = np.asarray(nodes, np.int64).reshape(-1)
+        if len(a) and (a.min() < 0 or a.max() >= self.n_nodes[g]):
+            raise ValueError('link_candidates: node id outside graph %d (%d nodes)' % (g, self.n_nodes[g]))
+        m = len(a)
+        part = torch.empty((m, k), dtype=torch.int32, device='cuda')
+        sc = torch.empty((m, k), dtype=torch.float32, device='cuda')
+        tot = torch.empty(m, dtype=torch.int32, device='cuda')
+        if m:
+            d_a = torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
+            _lib.check(_lib.lib().gm_store_pair_candidates(self.handle, g, _lib.ptr(d_a), m, k, PAIR_SCORES.index(score), _lib.ptr(part), _lib.ptr(sc), _lib.ptr(tot),
+                                                           _lib.stream_ptr()), 'gm_store_pair_candidates')
+        return part.cpu().numpy().astype(np.int64), sc.cpu().numpy(), tot.cpu().numpy().astype(np.int64)
+
     def close(self):
         if getattr(self, 'handle', None):
             _lib.lib().gm_store_destroy(self.handle)

@@ -43,3 +43,13 @@ def link_heuristic_auc(store, names, labels, mask_target=False):
     mask_target as in GraphStore.pair_scores: pass True when the positive pairs are edges of the store's graphs."""
     sc = link_heuristic_scores(store, names, mask_target)
     return {nm: link_auc(sc[:, k], labels) for k, nm in enumerate(PAIR_SCORES)}
+
+
+def candidate_names(g, nodes, partners):
+    """The partners GraphStore.link_candidates found for the `nodes` of graph `g`, as pair names: one list of 'g_a_w' per node, in ranking order, the -1
+    padding skipped -- the shape Subgraphs.query_batch takes (one set per source), whose batch Adapted.predict scores."""
+    a = np.asarray(nodes, np.int64).reshape(-1)
+    p = np.asarray(partners, np.int64)
+    if p.ndim != 2 or len(p) != len(a):
+        raise ValueError('candidate_names: %d nodes, partners of shape %s' % (len(a), p.shape))
+    return [['%d_%d_%d' % (int(g), x, w) for w in row.tolist() if w >= 0] for x, row in zip(a.tolist(), p)]

@@ -159,6 +159,33 @@ int32_t gm_store_has_edges(const gm_store_t* s, int32_t g, const int32_t* d_pair
 int32_t gm_store_pair_scores(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, float* d_out, void* stream);
 int32_t gm_store_neighbour_degrees(const gm_store_t* s, int32_t g, int32_t* d_out, void* stream);
 
+/* ---- CANDIDATE PARTNERS for link prediction (beyond the reference): which pairs to score at all.  For m source nodes of one parent graph, the non-adjacent
+ * nodes that share a neighbour with the source, ranked by one pair score, the best k of each -- on the device.  This comment is THE definition;
+ * tests/candidate_ref.py restates it with Python sets.  Per parent graph g of a store with N nodes:
+ *   neighbourhood  G(x) and deg are those of gm_store_pair_scores: DISTINCT nodes in either direction, self loops never count, weights are ignored.
+ *   candidate set  C(a) = { w : w != a, w not in G(a), G(a) & G(w) not empty }: the nodes at distance exactly 2 in the distinct-neighbour graph.
+ *                  d_nodes: device int32 [m] sources.  Duplicate sources are allowed, every row of the result is independent.  A source id outside [0, N)
+ *                  has C = {} (as gm_store_pair_scores gives five zeros for a node outside the graph).
+ *   score          column `col` (0..4, the order of gm_store_pair_scores: cn, jaccard, adamic_adar, resource_allocation, pref_attachment) of
+ *                  gm_store_pair_scores for the pair (a, w) with flags 0 (a candidate is never adjacent: the mask flag would change nothing), BITWISE equal to
+ *                  it under the lanes-per-pair configuration in force (the library's choice or gm_set_tuning("pair_lanes")).  Every candidate has cn >= 1
+ *                  and both degrees >= 1, so every score is a positive finite fp32.
+ *   ranking        descending score, among equal fp32 scores ascending node id w: the descending order of the integer key
+ *                  (uint64(score bits) << 32) | (0xFFFFFFFF - w).  Selection is integer work and the result is unique.
+ *   result         for k in 1..1024: d_out_nodes device int32 [m, k], d_out_scores device fp32 [m, k], d_out_total device int32 [m] = |C(a)|.  Row r holds
+ *                  the first min(k, total[r]) candidates of the ranking, in ranking order; the remaining entries are -1 in d_out_nodes and 0.0f in
+ *                  d_out_scores.  Nothing beyond row m - 1 is written.
+ * The result is a function of (graph, sources, k, col, lanes-per-pair configuration) alone: not of the stream, not of how the sources are cut into rounds
+ * (gm_set_tuning("cand_round", P): pairs per round, 0 = the library's choice; a source whose set alone exceeds P gets a round of its own), not of where the
+ * membership bitmap of the enumeration lives (gm_set_tuning("cand_bitmap", 0 | 1 | 2): the library's choice, LDS, a slab in HBM; forcing LDS on a graph
+ * of more than 262,144 nodes is GM_EINVAL).  Two runs agree bit for bit: no float atomics, nothing depends on arrival order.
+ * The call reads the neighbour index (built at first use, as for gm_store_pair_scores), runs on `stream`, takes its scratch from the stream-ordered pool,
+ * reads the set sizes back once to cut the rounds, and returns after the stream has produced the result.  m == 0 is a no-op.
+ * GM_EINVAL (the message names the value): a bad graph index, m < 0 or above INT32_MAX, k outside 1..1024, col outside 0..4, a NULL argument with m > 0,
+ * a pair_lanes value that is no instantiation, a bad cand_bitmap / cand_round.  GM_ERANGE: a round whose pair count passes 2^31 - 1. */
+int32_t gm_store_pair_candidates(const gm_store_t* s, int32_t g, const int32_t* d_nodes, int64_t m, int32_t k, int32_t col, int32_t* d_out_nodes,
+                                 float* d_out_scores, int32_t* d_out_total, void* stream);
+
 /* ---- Extraction: replaces Subgraphs.generate_subgraph / generate_subgraph_link_pred
  * (sdp.py:295-346: h-hop in-neighbour expansion, node sampling, G.subgraph) and dgl.batch
  * (sdp.py:399-406) for n_sets sets at once.  seeds/set_offsets are host arrays; set s owns seeds
