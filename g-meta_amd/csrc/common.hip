@@ -368,6 +368,8 @@ const gm_knobs& gm_knob() {
         k.pair_lanes = env("GM_PAIR_LANES", 0);
         k.cand_round = env("GM_CAND_ROUND", 0);
         k.cand_bitmap = env("GM_CAND_BITMAP", 0);
+        k.walk_chunk = env("GM_WALK_CHUNK", 0);
+        k.walk_lanes = env("GM_WALK_LANES", 0);
     });
     return k;
 }
@@ -388,6 +390,8 @@ static int gm_knobs::* gm_find_knob(const char* name) {
         {"pair_lanes", &gm_knobs::pair_lanes}, {"GM_PAIR_LANES", &gm_knobs::pair_lanes},
         {"cand_round", &gm_knobs::cand_round}, {"GM_CAND_ROUND", &gm_knobs::cand_round},
         {"cand_bitmap", &gm_knobs::cand_bitmap}, {"GM_CAND_BITMAP", &gm_knobs::cand_bitmap},
+        {"walk_chunk", &gm_knobs::walk_chunk}, {"GM_WALK_CHUNK", &gm_knobs::walk_chunk},
+        {"walk_lanes", &gm_knobs::walk_lanes}, {"GM_WALK_LANES", &gm_knobs::walk_lanes},
     };
     for (const auto& e : tab)
         if (!strcmp(name, e.name)) return e.field;

@@ -259,6 +259,8 @@ struct gm_knobs {
     int neg_round;                 // GM_NEG_ROUND, gm_set_tuning("neg_round"): candidates per round of gm_store_negative_pairs (negatives.hip); 0 (default) = by the call's n.  The result does not depend on it
     int pair_lanes;                // GM_PAIR_LANES, gm_set_tuning("pair_lanes"): lanes per pair of gm_store_pair_scores (pair_scores.hip): 16, 32 or 64; 0 (default) = by the graph's mean distinct degree
     int cand_round;                // GM_CAND_ROUND, gm_set_tuning("cand_round"): pairs per round of gm_store_pair_candidates (candidates.hip); 0 (default) = the library's choice.  The result does not depend on it
+    int walk_chunk;                // GM_WALK_CHUNK, gm_set_tuning("walk_chunk"): outer-row entries per work item of gm_store_pair_walks (pair_walks.hip); 0 (default) = the library's choice.  The result does not depend on it
+    int walk_lanes;                // GM_WALK_LANES, gm_set_tuning("walk_lanes"): lanes per work item of gm_store_pair_walks: 32 or 64; 0 (default) = by the graph's mean distinct degree and the length of the pair list.  The result does not depend on it
     int cand_bitmap;               // GM_CAND_BITMAP, gm_set_tuning("cand_bitmap"): home of that call's membership bitmap: 1 LDS, 2 a per-workgroup slab in HBM; 0 (default) = LDS wherever the graph fits.  The result does not depend on it
 };
 const gm_knobs& gm_knob();

@@ -161,6 +161,20 @@ class GraphStore:
                                                        _lib.stream_ptr()), 'gm_store_pair_scores')
         return out.cpu().numpy()
 
+    def pair_walks(self, g, pairs, mask_target=False):
+        """int64 [m, 3]: the numbers of walks of length 1, 2 and 3 between the two nodes of each of the [m, 2] `pairs` of graph `g` in the distinct-neighbour
+        graph of pair_scores, computed on the device (gm_store_pair_walks; the definition is in include/gmeta_hip.h, tests/path_walk_ref.py restates it).
+        Exact integers; a pair may come in any orientation.  mask_target=True counts the walks of an adjacent pair without its own edge.
+        gmeta_amd.local_path_index / katz_index turn the rows into scores."""
+        import torch
+        g, p = self._pairs_of(g, pairs, 'pair_walks')
+        out = torch.empty((len(p), 3), dtype=torch.int64, device='cuda')
+        if len(p):
+            d_p = torch.from_numpy(np.ascontiguousarray(p, np.int32)).cuda()
+            _lib.check(_lib.lib().gm_store_pair_walks(self.handle, g, _lib.ptr(d_p), len(p), _lib.PAIR_MASK_TARGET if mask_target else 0, _lib.ptr(out),
+                                                      _lib.stream_ptr()), 'gm_store_pair_walks')
+        return out.cpu().numpy()
+
     def neighbour_degrees(self, g):
         """int32 [N]: the number of distinct neighbours (either direction, itself aside) of every node of graph `g` -- the degrees the pair scores use."""
         import torch

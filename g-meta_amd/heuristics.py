@@ -1,11 +1,13 @@
 """Neighbourhood heuristics as a link-prediction baseline: the scores of GraphStore.pair_scores (gm_store_pair_scores; the definition is in
 include/gmeta_hip.h) turned into the ROC AUC a learned link predictor is held against.  The scores come from the device; the AUC is host work over
-one number per pair."""
+one number per pair.  The path scores one step further -- the local path index and the truncated Katz index -- are formed here, in float64, from the exact walk
+counts of GraphStore.pair_walks (gm_store_pair_walks)."""
 import numpy as np
 
 from .negatives import _pair
 
 PAIR_SCORES = ('cn', 'jaccard', 'adamic_adar', 'resource_allocation', 'pref_attachment')      # the columns of GraphStore.pair_scores, in order
+PATH_SCORES = ('local_path', 'katz')                                                          # the scores made of GraphStore.pair_walks' three columns
 
 
 def link_auc(scores, labels):
@@ -43,6 +45,36 @@ def link_heuristic_auc(store, names, labels, mask_target=False):
     mask_target as in GraphStore.pair_scores: pass True when the positive pairs are edges of the store's graphs."""
     sc = link_heuristic_scores(store, names, mask_target)
     return {nm: link_auc(sc[:, k], labels) for k, nm in enumerate(PAIR_SCORES)}
+
+
+def local_path_index(walks, eps=0.01):
+    """float64 [m]: w2 + eps * w3 of the int64 [m, 3] walk counts (w1, w2, w3) -- A^2 + eps A^3 at the pair."""
+    w = np.asarray(walks, np.int64).reshape(-1, 3).astype(np.float64)
+    return w[:, 1] + float(eps) * w[:, 2]
+
+
+def katz_index(walks, beta=0.005):
+    """float64 [m]: beta * w1 + beta^2 * w2 + beta^3 * w3 of the int64 [m, 3] walk counts -- the Katz index truncated after the walks of length three."""
+    w = np.asarray(walks, np.int64).reshape(-1, 3).astype(np.float64)
+    b = float(beta)
+    return b * w[:, 0] + b ** 2 * w[:, 1] + b ** 3 * w[:, 2]
+
+
+def link_path_scores(store, names, mask_target=False):
+    """int64 [len(names), 3]: GraphStore.pair_walks of the pairs named 'g_i_j', one call per graph, rows in the order of `names`."""
+    trip = np.asarray([_pair(nm) for nm in names], np.int64).reshape(-1, 3)
+    out = np.zeros((len(trip), 3), np.int64)
+    for g in np.unique(trip[:, 0]).tolist():
+        at = np.nonzero(trip[:, 0] == g)[0]
+        out[at] = store.pair_walks(g, trip[at, 1:], mask_target=mask_target)
+    return out
+
+
+def link_path_auc(store, names, labels, mask_target=False, eps=0.01, beta=0.005):
+    """{score name: ROC AUC} of the two path scores (PATH_SCORES) over the pairs `names` ('g_i_j') with the 0 / 1 `labels` of a link table, all graphs together;
+    mask_target as in link_heuristic_auc."""
+    w = link_path_scores(store, names, mask_target)
+    return {'local_path': link_auc(local_path_index(w, eps), labels), 'katz': link_auc(katz_index(w, beta), labels)}
 
 
 def candidate_names(g, nodes, partners):

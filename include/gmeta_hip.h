@@ -186,6 +186,35 @@ int32_t gm_store_neighbour_degrees(const gm_store_t* s, int32_t g, int32_t* d_ou
 int32_t gm_store_pair_candidates(const gm_store_t* s, int32_t g, const int32_t* d_nodes, int64_t m, int32_t k, int32_t col, int32_t* d_out_nodes,
                                  float* d_out_scores, int32_t* d_out_total, void* stream);
 
+/* ---- WALK COUNTS of node pairs (beyond the reference): the numbers of walks of length 1, 2 and 3 between the two nodes of n pairs of one parent graph, on the
+ * device -- what the heuristics one step beyond the common neighbours are made of: the local path index w2 + eps w3 and the truncated Katz index
+ * beta w1 + beta^2 w2 + beta^3 w3 (formed on the host from these integers: g-meta_amd/heuristics.py).  This comment is THE definition;
+ * tests/path_walk_ref.py restates it with Python sets.  Per parent graph g of a store, with N nodes:
+ *   neighbourhood  G(x) and deg are those of gm_store_pair_scores: DISTINCT nodes joined in either direction, self loops never count, parallel copies count
+ *                  once, weights are ignored.  S is the symmetric 0 / 1 matrix of G.
+ *   pairs          d_pairs: device int32 [n, 2].  Any orientation and a == b are allowed; a pair is canonicalised to (u, v) = (min, max) first, so (a, b) and
+ *                  (b, a) give the same row.
+ *   result         d_out: device int64 [n, 3], columns
+ *                    0  w1 = (S)[u, v]   = [v in G(u)]
+ *                    1  w2 = (S^2)[u, v] = sum over z in G(u) of [z in G(v)]: cn for u != v, deg u for u == v
+ *                    2  w3 = (S^3)[u, v] = sum over z in G(u) of |G(z) & G(v)|
+ *                  S^3 is symmetric: the value does not depend on which endpoint is expanded.
+ *   mask flag      GM_PAIR_MASK_TARGET (1) in `flags` counts the walks in S without the edge {u, v}: when u != v and v in G(u), w1 = 0, w2 is unchanged and w3
+ *                  loses deg u + deg v - 1 (deg v walks whose first step is u -> v, deg u whose last step is, u v u v in both; the middle step cannot be the
+ *                  edge alone).  Otherwise -- and always without the flag -- nothing changes.
+ *   out of range   a node id outside [0, N) gives three zeros.
+ *   exactness      integer work throughout; w3 <= deg u * deg v < 2^62.  The result is a function of (graph, pairs, flags) alone: the lanes per work item
+ *                  (gm_set_tuning("walk_lanes", L) with L in {32, 64} -- the widths that are built -- forces one, 0 restores the library's choice by the
+ *                  graph's mean distinct degree and the length of the pair list), the way a pair's work is cut (gm_set_tuning("walk_chunk", C): entries of the expanded endpoint's row per
+ *                  work item, 0 = the library's choice; a pair whose row is longer is summed by several items with 64-bit integer atomic adds onto its
+ *                  seeded row), the stream and the arrival order cannot change a bit of it.
+ *   writes         the rows of all n pairs, duplicates included (every row is seeded and summed on its own); nothing behind row n - 1.
+ * The call reads the neighbour index (built at first use, as for gm_store_pair_scores), runs on `stream`, takes its scratch from the stream-ordered pool and
+ * reads two counters back once to size the launch over the heavy pairs' items; the result is complete in stream order.  n == 0 is a no-op.
+ * GM_EINVAL (the message names the value): a bad graph index, n < 0 or above INT32_MAX, unknown flag bits, a NULL argument with n > 0, a negative walk_chunk,
+ * a walk_lanes value that is no instantiation.  GM_ERANGE: more than 2^30 work items in one call (a walk_chunk far too small for the pairs). */
+int32_t gm_store_pair_walks(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, int64_t* d_out, void* stream);
+
 /* ---- Extraction: replaces Subgraphs.generate_subgraph / generate_subgraph_link_pred
  * (sdp.py:295-346: h-hop in-neighbour expansion, node sampling, G.subgraph) and dgl.batch
  * (sdp.py:399-406) for n_sets sets at once.  seeds/set_offsets are host arrays; set s owns seeds

@@ -66,10 +66,11 @@ def parse(argv=None):
                     help="where the negative pairs of a link data set come from (--link_pred_mode True): 'file' = the CSV tables hold them, as the reference's do; "
                          "'uniform' / 'two_hop' = the tables hold the positive pairs only and as many negatives are drawn on the GPU from each graph's non-edges "
                          "(GraphStore.negative_pairs), the same on every rank; meant for --mask_target 1")
-    ap.add_argument('--heuristics', type=int, default=0, choices=[0, 1],
+    ap.add_argument('--heuristics', type=int, default=0, choices=[0, 1, 2],
                     help='1 (--link_pred_mode True): after the test evaluation, print the ROC AUC of the five neighbourhood heuristics (common neighbours, Jaccard, '
                          'Adamic-Adar, resource allocation, preferential attachment; GraphStore.pair_scores) over the pairs of the test table -- the baseline a '
-                         'learned link predictor is held against; follows --mask_target')
+                         'learned link predictor is held against; follows --mask_target.  2: that line and a second one with the two path scores over walks of up to '
+                         'three steps (local path index, truncated Katz index; GraphStore.pair_walks)')
     ap.add_argument('--readout', default='centre', choices=['centre', 'mean'],
                     help="what the head reads of every subgraph: 'centre' = the centre row (both endpoints' rows of a pair), as the reference; 'mean' = the mean "
                          "over all of its rows (the dgl.mean_nodes line the reference left commented out), one pooled vector for pairs too")
@@ -82,7 +83,10 @@ def parse(argv=None):
                     help='1: tasks with short or imbalanced classes are trained and evaluated on (sample means over the rows that are there) instead of raising')
     ap.add_argument('--predict_out', default=None, type=str,
                     help='after the final test evaluation, label the query subgraphs of the test tasks with the early-stopped model and write them to this .npz')
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.heuristics == 2 and a.link_pred_mode != 'True':      # refused before any data is read: node tasks have no pairs to score (--heuristics 1 keeps its check in main())
+        raise SystemExit('--heuristics 2 scores node PAIRS: it needs --link_pred_mode True')
+    return a
 
 
 def main(args):
@@ -99,7 +103,7 @@ def main(args):
     info = datadir.load_labels(root)
     store = gmeta_amd.GraphStore(graphs, feat)
     if args.heuristics and args.link_pred_mode != 'True':
-        raise SystemExit('--heuristics 1 scores node PAIRS: it needs --link_pred_mode True')
+        raise SystemExit('--heuristics %d scores node PAIRS: it needs --link_pred_mode True' % args.heuristics)
     tables = None
     if args.negatives != 'file':
         if args.link_pred_mode != 'True':
@@ -197,6 +201,10 @@ def main(args):
         res['heuristic_auc'] = gmeta_amd.link_heuristic_auc(store, names, labels, mask_target=bool(args.mask_target))
         if rank == 0:
             print('Heuristic test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['heuristic_auc'].items()))
+        if args.heuristics == 2:
+            res['path_auc'] = gmeta_amd.link_path_auc(store, names, labels, mask_target=bool(args.mask_target))
+            if rank == 0:
+                print('Path test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['path_auc'].items()))
     return res
 
 
