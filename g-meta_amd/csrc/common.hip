@@ -370,6 +370,8 @@ const gm_knobs& gm_knob() {
         k.cand_bitmap = env("GM_CAND_BITMAP", 0);
         k.walk_chunk = env("GM_WALK_CHUNK", 0);
         k.walk_lanes = env("GM_WALK_LANES", 0);
+        k.ppr_chunk = env("GM_PPR_CHUNK", 0);
+        k.ppr_cols = env("GM_PPR_COLS", 0);
     });
     return k;
 }
@@ -392,6 +394,8 @@ static int gm_knobs::* gm_find_knob(const char* name) {
         {"cand_bitmap", &gm_knobs::cand_bitmap}, {"GM_CAND_BITMAP", &gm_knobs::cand_bitmap},
         {"walk_chunk", &gm_knobs::walk_chunk}, {"GM_WALK_CHUNK", &gm_knobs::walk_chunk},
         {"walk_lanes", &gm_knobs::walk_lanes}, {"GM_WALK_LANES", &gm_knobs::walk_lanes},
+        {"ppr_chunk", &gm_knobs::ppr_chunk}, {"GM_PPR_CHUNK", &gm_knobs::ppr_chunk},
+        {"ppr_cols", &gm_knobs::ppr_cols}, {"GM_PPR_COLS", &gm_knobs::ppr_cols},
     };
     for (const auto& e : tab)
         if (!strcmp(name, e.name)) return e.field;

@@ -1,0 +1,430 @@
+// Rooted PageRank of sources and node pairs (gm_store_rooted_pagerank, gm_store_pair_pagerank: the one global score among the link-prediction baselines).
+// The DEFINITION is in include/gmeta_hip.h; tests/pagerank_ref.py restates it in float64.  This file is how it is computed, over the neighbour index of
+// pair_scores.hip (gm_nbr_index):
+//   columns     a column is a pair (s, x): the walk from s in the graph without the edge {s, x} (x = -1: the whole graph).  The host reads the sources or pairs
+//               back once, forms the DISTINCT columns in ascending (s, x) order and runs them in rounds of at most B (gm_set_tuning("ppr_cols")); with the mask
+//               flag only adjacent pairs get a column of their own (adjacency: k_ppr_adjacent, before the read-back).
+//   the state   Q[N, B] fp32, row-major: p_t[z] / deg' z, pre-scaled per column (a row without neighbours keeps p_t[z] itself), so that a step of the walk is
+//               one load and one add per neighbour.  Two buffers swap between iterations; the last iteration stores p itself.
+//   one row     a wave takes a row v and a slab of 64 columns: lanes are columns, the neighbour id is wave-uniform (scalar loads), and every neighbour costs one
+//               coalesced 256-byte row read of Q -- the gathered whole-row pattern.  GM_PPR_UNROLL row reads are in flight per lane; the adds follow in
+//               ascending neighbour order.  The mask is per lane: one excluded id on the two rows v in {s, x} (its term is replaced by +0, which changes no
+//               bit) and a degree one less when those two rows are scaled.
+//   hub rows    a row of more than C entries (gm_set_tuning("ppr_chunk")) is cut into segments of C: k_ppr_parts sums each segment into a partial buffer
+//               (a wave per segment and slab), k_ppr_hubs adds the partials in ascending segment order and finishes the row.  Plain vector stores.
+//   results     gm_store_rooted_pagerank: k_ppr_rows_out transposes p[N, B] into the rows of d_out through a 64 x 64 LDS tile (a column serves every duplicate
+//               of its source); gm_store_pair_pagerank: k_ppr_entries_out gathers the two wanted entries of every pair.
+// No float atomics, nothing depends on arrival order: a column's bits are a function of (graph, s, x, alpha, iters, C) alone.  Everything runs on the caller's
+// stream; scratch comes from the stream-ordered pool.
+#include <math.h>
+#include "gm_internal.h"
+
+#define GM_PPR_THREADS 256
+#define GM_PPR_WAVES (GM_PPR_THREADS / GM_WAVE)
+#define GM_PPR_UNROLL 8                   // row reads of Q in flight per lane
+#define GM_PPR_TILE 64                    // k_ppr_rows_out: nodes x output rows per workgroup
+#define GM_PPR_MAX_COLS 4096
+
+// one parent graph of a store inside the neighbour index (pair_scores.hip): rows by LOCAL node id, offsets global (into idx), neighbours local
+struct ppr_graph {
+    const int64_t* ptr;          // gm_store::d_nbr_ptr + node_off[g]   [N + 1]
+    const int32_t* idx;          // gm_store::d_nbr_idx
+    int64_t N;
+};
+
+// the columns of one round: source and excluded node per column (-1: no column / no excluded node), B a multiple of 64
+struct ppr_cols {
+    const int32_t* s; const int32_t* x;
+    int32_t B;
+};
+
+// the lane's column on the row v: its source and the id the row must skip (-1: none; >= 0 exactly when v is an endpoint of the column's removed edge)
+template <bool MASK>
+__device__ __forceinline__ void ppr_lane(const ppr_cols& K, int32_t c, int32_t v, int32_t* cs, int32_t* ex) {
+    *cs = K.s[c]; *ex = -1;
+    if (MASK) { const int32_t cx = K.x[c]; *ex = cx < 0 ? -1 : v == *cs ? cx : v == cx ? *cs : -1; }
+}
+
+// sum over row[0 .. len) of Q[z, c] in ascending order (Qc = Q + c); the excluded id's term is +0
+template <bool MASK>
+__device__ __forceinline__ float ppr_sum(const int32_t* __restrict__ row, int32_t len, const float* __restrict__ Qc, int64_t B, int32_t ex) {
+    float acc = 0.f;
+    int32_t i = 0;
+    for (; i + GM_PPR_UNROLL <= len; i += GM_PPR_UNROLL) {
+        int32_t z[GM_PPR_UNROLL]; float q[GM_PPR_UNROLL];
+#pragma unroll
+        for (int k = 0; k < GM_PPR_UNROLL; ++k) z[k] = row[i + k];
+#pragma unroll
+        for (int k = 0; k < GM_PPR_UNROLL; ++k) q[k] = Qc[(int64_t)z[k] * B];
+#pragma unroll
+        for (int k = 0; k < GM_PPR_UNROLL; ++k) acc = __fadd_rn(acc, MASK && z[k] == ex ? 0.f : q[k]);
+    }
+    for (; i < len; ++i) {
+        const int32_t z = row[i];
+        const float q = Qc[(int64_t)z * B];
+        acc = __fadd_rn(acc, MASK && z == ex ? 0.f : q);
+    }
+    return acc;
+}
+
+// p_{t+1}[v] of the lane's column from the row sum, stored pre-scaled for the next iteration (the last one stores p itself)
+__device__ __forceinline__ void ppr_store(float sum, int32_t deg, int32_t v, int32_t cs, int32_t ex, float a, float b, int last, const float* __restrict__ Qa,
+                                          float* __restrict__ Qb, int64_t at) {
+    const int32_t d = deg - (ex >= 0 ? 1 : 0);                                // deg' v
+    const float m = d > 0 ? sum : Qa[at];                                    // a node without neighbours keeps its mass (its Q entry is p itself)
+    const float p = __fadd_rn(v == cs ? a : 0.f, __fmul_rn(b, m));
+    Qb[at] = last || d == 0 ? p : __fmul_rn(p, __fdiv_rn(1.f, (float)d));
+}
+
+// p_0 = e_s, pre-scaled: one thread per column (Q is zero beforehand)
+__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_seed(ppr_graph G, ppr_cols K, float* __restrict__ Q) {
+    const int32_t c = (int32_t)(blockIdx.x * GM_PPR_THREADS + threadIdx.x);
+    if (c >= K.B) return;
+    const int32_t cs = K.s[c];
+    if (cs < 0 || cs >= G.N) return;
+    const int32_t d = (int32_t)(G.ptr[cs + 1] - G.ptr[cs]) - (K.x[c] >= 0 ? 1 : 0);
+    Q[(int64_t)cs * K.B + c] = d > 0 ? __fdiv_rn(1.f, (float)d) : 1.f;
+}
+
+// a wave per (row, slab of 64 columns); rows of more than C entries are left to k_ppr_parts / k_ppr_hubs
+template <bool MASK>
+__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_rows(ppr_graph G, ppr_cols K, int32_t slabs, int32_t C, float a, float b, int last,
+                                                             const float* __restrict__ Qa, float* __restrict__ Qb) {
+    const int64_t w = (int64_t)blockIdx.x * GM_PPR_WAVES + (threadIdx.x >> 6);
+    const int64_t row = w / slabs;
+    if (row >= G.N) return;
+    const int32_t v = __builtin_amdgcn_readfirstlane((int32_t)row);
+    const int32_t slab = __builtin_amdgcn_readfirstlane((int32_t)(w - row * slabs));
+    const int32_t c = slab * GM_WAVE + ((int32_t)threadIdx.x & (GM_WAVE - 1));
+    const int64_t r0 = G.ptr[v];
+    const int32_t deg = (int32_t)(G.ptr[v + 1] - r0);
+    if (deg > C) return;
+    int32_t cs, ex;
+    ppr_lane<MASK>(K, c, v, &cs, &ex);
+    const float sum = ppr_sum<MASK>(G.idx + r0, deg, Qa + c, K.B, ex);
+    ppr_store(sum, deg, v, cs, ex, a, b, last, Qa, Qb, (int64_t)v * K.B + c);
+}
+
+// a wave per (segment of a hub row, slab): part[item, c] = the segment's sum
+template <bool MASK>
+__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_parts(ppr_graph G, ppr_cols K, int32_t slabs, int32_t C, const int32_t* __restrict__ it_row,
+                                                              const int32_t* __restrict__ it_seg, int64_t n_items, const float* __restrict__ Qa, float* __restrict__ part) {
+    const int64_t w = (int64_t)blockIdx.x * GM_PPR_WAVES + (threadIdx.x >> 6);
+    const int64_t item = w / slabs;
+    if (item >= n_items) return;
+    const int32_t it = __builtin_amdgcn_readfirstlane((int32_t)item);
+    const int32_t slab = __builtin_amdgcn_readfirstlane((int32_t)(w - item * slabs));
+    const int32_t c = slab * GM_WAVE + ((int32_t)threadIdx.x & (GM_WAVE - 1));
+    const int32_t v = it_row[it];
+    const int64_t r0 = G.ptr[v], beg = (int64_t)it_seg[it] * C;
+    const int64_t left = G.ptr[v + 1] - r0 - beg;
+    const int32_t len = (int32_t)(left < C ? left : C);
+    int32_t cs, ex;
+    ppr_lane<MASK>(K, c, v, &cs, &ex);
+    part[(int64_t)it * K.B + c] = ppr_sum<MASK>(G.idx + r0 + beg, len, Qa + c, K.B, ex);
+}
+
+// a wave per (hub row, slab): its partials in ascending segment order, then the row as k_ppr_rows finishes it
+template <bool MASK>
+__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_hubs(ppr_graph G, ppr_cols K, int32_t slabs, const int32_t* __restrict__ hub_row,
+                                                             const int32_t* __restrict__ hub_first, int64_t n_hubs, float a, float b, int last,
+                                                             const float* __restrict__ part, const float* __restrict__ Qa, float* __restrict__ Qb) {
+    const int64_t w = (int64_t)blockIdx.x * GM_PPR_WAVES + (threadIdx.x >> 6);
+    const int64_t hub = w / slabs;
+    if (hub >= n_hubs) return;
+    const int32_t h = __builtin_amdgcn_readfirstlane((int32_t)hub);
+    const int32_t slab = __builtin_amdgcn_readfirstlane((int32_t)(w - hub * slabs));
+    const int32_t c = slab * GM_WAVE + ((int32_t)threadIdx.x & (GM_WAVE - 1));
+    const int32_t v = hub_row[h], first = hub_first[h], segs = hub_first[h + 1] - first;
+    const int32_t deg = (int32_t)(G.ptr[v + 1] - G.ptr[v]);
+    int32_t cs, ex;
+    ppr_lane<MASK>(K, c, v, &cs, &ex);
+    float sum = part[(int64_t)first * K.B + c];
+    for (int32_t k = 1; k < segs; ++k) sum = __fadd_rn(sum, part[(int64_t)(first + k) * K.B + c]);
+    ppr_store(sum, deg, v, cs, ex, a, b, last, Qa, Qb, (int64_t)v * K.B + c);
+}
+
+// gm_store_rooted_pagerank: out[row[r], v] = P[v, col[r] - c0] for the cnt output rows of a round (col < 0: a source outside the graph, a row of zeros), a
+// 64 x 64 tile per workgroup through LDS so that both sides move whole 256-byte pieces
+__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_rows_out(const float* __restrict__ P, int32_t B, int64_t c0, int64_t N, const int32_t* __restrict__ row, const int32_t* __restrict__ col,
+                                                                 int64_t cnt, int64_t v_tiles, float* __restrict__ out) {
+    __shared__ float tile[GM_PPR_TILE][GM_PPR_TILE + 1];
+    const int64_t v0 = ((int64_t)blockIdx.x % v_tiles) * GM_PPR_TILE, r0 = ((int64_t)blockIdx.x / v_tiles) * GM_PPR_TILE;
+    const int hi = (int)threadIdx.x >> 6, lo = (int)threadIdx.x & 63;
+    {
+        const int64_t r = r0 + lo;
+        const int64_t c = r < cnt ? (int64_t)col[r] - c0 : -1;                       // (a round's first column is c0; -1 stays negative)
+        for (int i = 0; i < GM_PPR_TILE; i += GM_PPR_WAVES) {
+            const int64_t v = v0 + i + hi;
+            tile[i + hi][lo] = c >= 0 && v < N ? P[v * B + c] : 0.f;
+        }
+    }
+    __syncthreads();
+    const int64_t v = v0 + lo;
+    for (int i = 0; i < GM_PPR_TILE; i += GM_PPR_WAVES) {
+        const int64_t r = r0 + i + hi;
+        if (r < cnt && v < N) out[(int64_t)row[r] * N + v] = tile[lo][i + hi];
+    }
+}
+
+// gm_store_pair_pagerank: out[dst[e]] = P[node[e], col[e] - c0] for the cnt entries of a round (col < 0: a node outside the graph, zero)
+__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_entries_out(const float* __restrict__ P, int32_t B, int64_t c0, const int64_t* __restrict__ dst, const int32_t* __restrict__ node,
+                                                                    const int32_t* __restrict__ col, int64_t cnt, float* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * GM_PPR_THREADS + threadIdx.x;
+    if (e >= cnt) return;
+    const int32_t c = col[e];
+    out[dst[e]] = c >= 0 ? P[(int64_t)node[e] * B + (c - c0)] : 0.f;
+}
+
+// adj[k] = 1 where the two nodes of pair k are distinct, inside the graph and neighbours (the pairs whose masked columns differ from the unmasked ones)
+__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_adjacent(ppr_graph G, const int32_t* __restrict__ pairs, int64_t n, uint8_t* __restrict__ adj) {
+    const int64_t k = (int64_t)blockIdx.x * GM_PPR_THREADS + threadIdx.x;
+    if (k >= n) return;
+    const int32_t a = pairs[2 * k], b = pairs[2 * k + 1];
+    bool hit = false;
+    if (a != b && a >= 0 && a < G.N && b >= 0 && b < G.N) {
+        const int32_t* __restrict__ row = G.idx + G.ptr[a];
+        int32_t lo = 0, hi = (int32_t)(G.ptr[a + 1] - G.ptr[a]);
+        while (lo < hi && !hit) {
+            const int32_t mid = lo + ((hi - lo) >> 1), z = row[mid];
+            hit = z == b;
+            if (z < b) lo = mid + 1; else hi = mid;
+        }
+    }
+    adj[k] = hit ? 1 : 0;
+}
+
+// device scratch of one call: handed back to the pool on the call's stream, whichever way the call ends
+struct ppr_scratch {
+    hipStream_t st;
+    std::vector<void*> p;
+    explicit ppr_scratch(hipStream_t s) : st(s) {}
+    ~ppr_scratch() { for (void* q : p) gm_dev_free(q, st); }
+    template <class T> int take(T** d, size_t n) {
+        GM_TRY(gm_alloc(d, n, st));
+        p.push_back((void*)*d);
+        return GM_OK;
+    }
+    template <class T> int put(T** d, const std::vector<T>& v, gm_stager& sg) {
+        GM_TRY(take(d, v.size()));
+        return sg.upload(*d, v);
+    }
+};
+
+// Columns per round and entries per hub segment, from the sweep at the arxiv shape (profiles/pair_pagerank.txt).  Wider rounds are faster as long as there are
+// columns to fill them (1,024 sources: 37.4 / 33.0 / 31.3 ms at 64 / 128 / 256 columns); a round is never wider than the call's columns.  The cut has to be ONE
+// value, whatever the round holds: the order of a row sum, hence the bits, belong to it.  Segments of 64 and 256 level everywhere; a round of one slab gains most
+// (64 sources: 2.5 ms against 3.9 uncut -- the longest row is the tail of every iteration), a round of four slabs, whose hub rows are spread over four waves
+// already, pays the two extra launches per iteration (256 sources: 7.96 ms against 7.48 uncut).  Segments of 1,024 lose on both sides.
+static int ppr_cols_for() { return 256; }
+static int32_t ppr_chunk_for() { return 256; }
+
+static unsigned ppr_grid(int64_t waves) { return (unsigned)((waves + GM_PPR_WAVES - 1) / GM_PPR_WAVES); }
+
+struct ppr_call {
+    float alpha; int32_t iters; hipStream_t st;
+    int B; int32_t C;             // the knobs in force
+    ppr_graph G;
+};
+
+// the checks both exports share; n == 0 leaves c->B == 0 (nothing to do)
+static int ppr_begin(const char* what, const char* cnt_name, const gm_store* s, int32_t g, int64_t n, int32_t flags, float alpha, int32_t iters, const void* d_in, const void* d_out,
+                     void* stream, ppr_call* c) {
+    GM_REQUIRE(s, GM_EINVAL, "%s: store is NULL", what);
+    GM_REQUIRE(g >= 0 && g < s->n_graphs, GM_EINVAL, "%s: graph %d of a store with %d graph(s)", what, g, s->n_graphs);
+    GM_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX, GM_EINVAL, "%s: %s = %lld", what, cnt_name, (long long)n);
+    GM_REQUIRE((flags & ~GM_PAIR_MASK_TARGET) == 0, GM_EINVAL, "%s: unknown flag bits 0x%x (GM_PAIR_MASK_TARGET = 1)", what, (unsigned)flags);
+    GM_REQUIRE(isfinite(alpha) && alpha > 0.f && alpha < 1.f, GM_EINVAL, "%s: alpha = %g; 0 < alpha < 1", what, (double)alpha);
+    GM_REQUIRE(iters >= 1 && iters <= 255, GM_EINVAL, "%s: iters = %d; 1 .. 255", what, iters);
+    const int cols = gm_knob().ppr_cols, chunk = gm_knob().ppr_chunk;
+    GM_REQUIRE(cols >= 0 && cols % GM_WAVE == 0 && cols <= GM_PPR_MAX_COLS, GM_EINVAL, "%s: ppr_cols = %d; a multiple of 64 up to %d (0: the library's choice)", what, cols,
+               GM_PPR_MAX_COLS);
+    GM_REQUIRE(chunk >= 0, GM_EINVAL, "%s: ppr_chunk = %d", what, chunk);
+    c->B = 0;
+    if (n == 0) return GM_OK;
+    GM_REQUIRE(d_in && d_out, GM_EINVAL, "%s: NULL argument", what);
+    GM_TRY(gm_nbr_index(s));
+    const int64_t no = s->node_off[g];
+    *c = {alpha, iters, (hipStream_t)stream, cols ? cols : ppr_cols_for(), chunk ? chunk : ppr_chunk_for(), {s->d_nbr_ptr + no, s->d_nbr_idx, s->node_off[g + 1] - no}};
+    return GM_OK;
+}
+
+// The walk of the columns (cs[k], cx[k]), ascending, in rounds of at most B: after a round's last iteration emit(c0, Br, P) reads P[N, Br] = p of the
+// columns c0 .. c0 + Br on the call's stream (Br == 0, P == NULL: a call without a single column).  h_ptr: the graph's row pointers on the host.
+template <class Emit>
+static int ppr_rounds(const char* what, const ppr_call& c, const int64_t* h_ptr, std::vector<int32_t> cs, std::vector<int32_t> cx, gm_stager& sg, Emit emit) {
+    const ppr_graph& G = c.G;
+    const int64_t N = G.N, ncols = (int64_t)cs.size(), ncp = (ncols + GM_WAVE - 1) / GM_WAVE * GM_WAVE;
+    cs.resize((size_t)ncp, -1); cx.resize((size_t)ncp, -1);
+    const int64_t Bmax = ncp < c.B ? ncp : c.B;
+    GM_REQUIRE(N * (Bmax / GM_WAVE + 1) <= (int64_t)INT32_MAX, GM_ERANGE, "%s: %lld nodes x %lld columns per round pass the launch's 2^31 waves", what, (long long)N, (long long)Bmax);
+    // the hub rows of the cut and their segments
+    std::vector<int32_t> hub_row, hub_first, it_row, it_seg;
+    for (int64_t v = 0; v < N; ++v) {
+        const int64_t deg = h_ptr[v + 1] - h_ptr[v];
+        if (deg <= c.C) continue;
+        hub_row.push_back((int32_t)v); hub_first.push_back((int32_t)it_row.size());
+        for (int64_t seg = 0; seg * c.C < deg; ++seg) { it_row.push_back((int32_t)v); it_seg.push_back((int32_t)seg); }
+        GM_REQUIRE(it_row.size() <= (size_t)(INT32_MAX / 2), GM_ERANGE, "%s: more than 2^30 hub segments at ppr_chunk = %d", what, (int)c.C);
+    }
+    hub_first.push_back((int32_t)it_row.size());
+    const int64_t n_hubs = (int64_t)hub_row.size(), n_items = (int64_t)it_row.size();
+
+    ppr_scratch sc(c.st);
+    float *Qa = nullptr, *Qb = nullptr, *part = nullptr;
+    int32_t *d_cs = nullptr, *d_cx = nullptr, *d_hub_row = nullptr, *d_hub_first = nullptr, *d_it_row = nullptr, *d_it_seg = nullptr;
+    if (ncols) {
+        GM_TRY(sc.take(&Qa, (size_t)(N * Bmax))); GM_TRY(sc.take(&Qb, (size_t)(N * Bmax)));
+        GM_TRY(sc.put(&d_cs, cs, sg)); GM_TRY(sc.put(&d_cx, cx, sg));
+        if (n_hubs) {
+            GM_TRY(sc.take(&part, (size_t)(n_items * Bmax)));
+            GM_TRY(sc.put(&d_hub_row, hub_row, sg)); GM_TRY(sc.put(&d_hub_first, hub_first, sg));
+            GM_TRY(sc.put(&d_it_row, it_row, sg)); GM_TRY(sc.put(&d_it_seg, it_seg, sg));
+        }
+    }
+    const float a = c.alpha, b = 1.0f - a;
+    const dim3 block(GM_PPR_THREADS);
+    for (int64_t c0 = 0; c0 == 0 || c0 < ncp; c0 += c.B) {
+        const int32_t Br = (int32_t)(ncp - c0 < c.B ? ncp - c0 : c.B);
+        const float* P = nullptr;
+        if (Br) {
+            const ppr_cols K = {d_cs + c0, d_cx + c0, Br};
+            const int32_t slabs = Br / GM_WAVE;
+            bool mask = false;
+            for (int32_t k = 0; k < Br && !mask; ++k) mask = cx[(size_t)(c0 + k)] >= 0;
+            GM_HIP(hipMemsetAsync(Qa, 0, (size_t)(N * Br) * sizeof(float), c.st));
+            hipLaunchKernelGGL(k_ppr_seed, dim3((unsigned)((Br + GM_PPR_THREADS - 1) / GM_PPR_THREADS)), block, 0, c.st, G, K, Qa);
+            float *src = Qa, *dst = Qb;
+            for (int32_t t = 0; t < c.iters; ++t) {
+                const int last = t == c.iters - 1;
+                const dim3 rows(ppr_grid(N * slabs)), parts(ppr_grid(n_items * slabs)), hubs(ppr_grid(n_hubs * slabs));
+                if (mask) hipLaunchKernelGGL(k_ppr_rows<true>, rows, block, 0, c.st, G, K, slabs, c.C, a, b, last, (const float*)src, dst);
+                else hipLaunchKernelGGL(k_ppr_rows<false>, rows, block, 0, c.st, G, K, slabs, c.C, a, b, last, (const float*)src, dst);
+                if (n_hubs) {
+                    if (mask) {
+                        hipLaunchKernelGGL(k_ppr_parts<true>, parts, block, 0, c.st, G, K, slabs, c.C, (const int32_t*)d_it_row, (const int32_t*)d_it_seg, n_items, (const float*)src, part);
+                        hipLaunchKernelGGL(k_ppr_hubs<true>, hubs, block, 0, c.st, G, K, slabs, (const int32_t*)d_hub_row, (const int32_t*)d_hub_first, n_hubs, a, b, last,
+                                           (const float*)part, (const float*)src, dst);
+                    } else {
+                        hipLaunchKernelGGL(k_ppr_parts<false>, parts, block, 0, c.st, G, K, slabs, c.C, (const int32_t*)d_it_row, (const int32_t*)d_it_seg, n_items, (const float*)src, part);
+                        hipLaunchKernelGGL(k_ppr_hubs<false>, hubs, block, 0, c.st, G, K, slabs, (const int32_t*)d_hub_row, (const int32_t*)d_hub_first, n_hubs, a, b, last,
+                                           (const float*)part, (const float*)src, dst);
+                    }
+                }
+                GM_HIP(hipGetLastError());
+                std::swap(src, dst);
+            }
+            P = src;
+        }
+        GM_TRY(emit(c0, Br, P));
+    }
+    return GM_OK;
+}
+
+// [lo, hi) of the ascending column numbers `col` that a round starting at column c0 serves: its own columns, and in the first round the -1s (no column)
+static void ppr_span(const std::vector<int32_t>& col, int64_t c0, int64_t Br, int64_t* lo, int64_t* hi) {
+    *lo = c0 == 0 ? 0 : std::lower_bound(col.begin(), col.end(), c0) - col.begin();
+    *hi = std::lower_bound(col.begin(), col.end(), c0 + Br) - col.begin();
+}
+
+extern "C" int32_t gm_store_rooted_pagerank(const gm_store_t* s, int32_t g, const int32_t* d_sources, int64_t m, float alpha, int32_t iters, float* d_out, void* stream) {
+    const char* what = "gm_store_rooted_pagerank";
+    ppr_call c;
+    GM_TRY(ppr_begin(what, "m", s, g, m, 0, alpha, iters, d_sources, d_out, stream, &c));
+    if (!c.B) return GM_OK;
+    const int64_t N = c.G.N;
+    gm_stager sg(c.st);
+    const int32_t* h_src = sg.download(d_sources, (size_t)m);
+    const int64_t* h_ptr = sg.download(c.G.ptr, (size_t)(N + 1));
+    GM_REQUIRE(h_src && h_ptr, GM_ENOMEM, "%s: pinned staging allocation failed", what);
+    GM_HIP(hipStreamSynchronize(c.st));
+    std::vector<int32_t> cs;
+    for (int64_t r = 0; r < m; ++r)
+        if (h_src[r] >= 0 && h_src[r] < N) cs.push_back(h_src[r]);
+    std::sort(cs.begin(), cs.end());
+    cs.erase(std::unique(cs.begin(), cs.end()), cs.end());
+    // the output rows in the order of their columns
+    std::vector<int32_t> row((size_t)m), col((size_t)m);
+    for (int64_t r = 0; r < m; ++r) row[(size_t)r] = (int32_t)r;
+    auto col_of = [&](int32_t r) { const int32_t x = h_src[r]; return x >= 0 && x < N ? (int32_t)(std::lower_bound(cs.begin(), cs.end(), x) - cs.begin()) : -1; };
+    std::stable_sort(row.begin(), row.end(), [&](int32_t p, int32_t q) { return col_of(p) < col_of(q); });
+    for (int64_t r = 0; r < m; ++r) col[(size_t)r] = col_of(row[(size_t)r]);
+    ppr_scratch sc(c.st);
+    int32_t *d_row = nullptr, *d_col = nullptr;
+    GM_TRY(sc.put(&d_row, row, sg)); GM_TRY(sc.put(&d_col, col, sg));
+    const int64_t v_tiles = (N + GM_PPR_TILE - 1) / GM_PPR_TILE;
+    std::vector<int32_t> cx(cs.size(), -1);
+    return ppr_rounds(what, c, h_ptr, cs, cx, sg, [&](int64_t c0, int32_t Br, const float* P) {
+        int64_t lo, hi;
+        ppr_span(col, c0, Br, &lo, &hi);
+        if (hi == lo) return (int)GM_OK;
+        const int64_t blocks = v_tiles * ((hi - lo + GM_PPR_TILE - 1) / GM_PPR_TILE);
+        GM_REQUIRE(blocks <= (int64_t)INT32_MAX, GM_ERANGE, "%s: %lld output tiles in one round", what, (long long)blocks);
+        hipLaunchKernelGGL(k_ppr_rows_out, dim3((unsigned)blocks), dim3(GM_PPR_THREADS), 0, c.st, P, Br, c0, N, (const int32_t*)d_row + lo, (const int32_t*)d_col + lo, hi - lo,
+                           v_tiles, d_out);
+        GM_HIP(hipGetLastError());
+        return (int)GM_OK;
+    });
+}
+
+extern "C" int32_t gm_store_pair_pagerank(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, float alpha, int32_t iters, float* d_out, void* stream) {
+    const char* what = "gm_store_pair_pagerank";
+    ppr_call c;
+    GM_TRY(ppr_begin(what, "n", s, g, n, flags, alpha, iters, d_pairs, d_out, stream, &c));
+    if (!c.B) return GM_OK;
+    const int64_t N = c.G.N;
+    const bool mask = (flags & GM_PAIR_MASK_TARGET) != 0;
+    ppr_scratch sc(c.st);
+    gm_stager sg(c.st);
+    uint8_t* d_adj = nullptr;
+    const uint8_t* h_adj = nullptr;
+    if (mask) {
+        GM_TRY(sc.take(&d_adj, (size_t)n));
+        hipLaunchKernelGGL(k_ppr_adjacent, dim3((unsigned)((n + GM_PPR_THREADS - 1) / GM_PPR_THREADS)), dim3(GM_PPR_THREADS), 0, c.st, c.G, d_pairs, n, d_adj);
+        GM_HIP(hipGetLastError());
+        h_adj = sg.download((const uint8_t*)d_adj, (size_t)n);
+    }
+    const int32_t* h_pairs = sg.download(d_pairs, (size_t)(2 * n));
+    const int64_t* h_ptr = sg.download(c.G.ptr, (size_t)(N + 1));
+    GM_REQUIRE(h_pairs && h_ptr && (!mask || h_adj), GM_ENOMEM, "%s: pinned staging allocation failed", what);
+    GM_HIP(hipStreamSynchronize(c.st));
+    // entry 2k: pi of the column (u, x)[v]; entry 2k + 1: pi of the column (v, x')[u]; x, x' = the other endpoint for a masked adjacent pair, else -1
+    auto key = [](int32_t src, int32_t x) { return ((int64_t)src << 32) | (uint32_t)(x + 1); };
+    std::vector<int64_t> want((size_t)(2 * n), -1), keys;
+    std::vector<int32_t> node((size_t)(2 * n), 0);
+    for (int64_t k = 0; k < n; ++k) {
+        const int32_t p = h_pairs[2 * k], q = h_pairs[2 * k + 1];
+        if (p < 0 || p >= N || q < 0 || q >= N) continue;
+        const int32_t u = p < q ? p : q, v = p < q ? q : p;
+        const bool cut = mask && h_adj[k];
+        want[(size_t)(2 * k)] = key(u, cut ? v : -1); node[(size_t)(2 * k)] = v;
+        want[(size_t)(2 * k + 1)] = key(v, cut ? u : -1); node[(size_t)(2 * k + 1)] = u;
+    }
+    for (const int64_t w : want)
+        if (w >= 0) keys.push_back(w);
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    GM_REQUIRE(keys.size() <= (size_t)INT32_MAX, GM_ERANGE, "%s: %lld distinct columns", what, (long long)keys.size());
+    std::vector<int32_t> cs(keys.size()), cx(keys.size());
+    for (size_t k = 0; k < keys.size(); ++k) { cs[k] = (int32_t)(keys[k] >> 32); cx[k] = (int32_t)(uint32_t)keys[k] - 1; }
+    // the entries in the order of their columns
+    std::vector<int32_t> ecol((size_t)(2 * n));
+    for (size_t e = 0; e < want.size(); ++e) ecol[e] = want[e] < 0 ? -1 : (int32_t)(std::lower_bound(keys.begin(), keys.end(), want[e]) - keys.begin());
+    std::vector<int64_t> dst((size_t)(2 * n));
+    for (size_t e = 0; e < dst.size(); ++e) dst[e] = (int64_t)e;
+    std::stable_sort(dst.begin(), dst.end(), [&](int64_t p, int64_t q) { return ecol[(size_t)p] < ecol[(size_t)q]; });
+    std::vector<int32_t> col((size_t)(2 * n)), nd((size_t)(2 * n));
+    for (size_t e = 0; e < dst.size(); ++e) { col[e] = ecol[(size_t)dst[e]]; nd[e] = node[(size_t)dst[e]]; }
+    int64_t* d_dst = nullptr;
+    int32_t *d_node = nullptr, *d_col = nullptr;
+    GM_TRY(sc.put(&d_dst, dst, sg)); GM_TRY(sc.put(&d_node, nd, sg)); GM_TRY(sc.put(&d_col, col, sg));
+    return ppr_rounds(what, c, h_ptr, cs, cx, sg, [&](int64_t c0, int32_t Br, const float* P) {
+        int64_t lo, hi;
+        ppr_span(col, c0, Br, &lo, &hi);
+        if (hi == lo) return (int)GM_OK;
+        hipLaunchKernelGGL(k_ppr_entries_out, dim3((unsigned)((hi - lo + GM_PPR_THREADS - 1) / GM_PPR_THREADS)), dim3(GM_PPR_THREADS), 0, c.st, P, Br, c0,
+                           (const int64_t*)d_dst + lo, (const int32_t*)d_node + lo, (const int32_t*)d_col + lo, hi - lo, d_out);
+        GM_HIP(hipGetLastError());
+        return (int)GM_OK;
+    });
+}

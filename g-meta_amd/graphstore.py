@@ -175,6 +175,49 @@ class GraphStore:
                                                       _lib.stream_ptr()), 'gm_store_pair_walks')
         return out.cpu().numpy()
 
+    @staticmethod
+    def _walk_of(alpha, iters, what):
+        alpha, iters = float(alpha), int(iters)
+        if not (np.isfinite(alpha) and 0.0 < float(np.float32(alpha)) < 1.0):
+            raise ValueError('%s: alpha = %r; 0 < alpha < 1' % (what, alpha))
+        if not 1 <= iters <= 255:
+            raise ValueError('%s: iters = %d; 1 .. 255' % (what, iters))
+        return alpha, iters
+
+    def rooted_pagerank(self, g, sources, alpha=0.15, iters=20):
+        """float32 [m, N]: row r is the rooted PageRank vector of sources[r] in graph `g` after `iters` steps of the walk that returns to its source with
+        probability `alpha`, over the distinct-neighbour graph of pair_scores, computed on the device (gm_store_rooted_pagerank; the definition is in
+        include/gmeta_hip.h, tests/pagerank_ref.py restates it).  A node without neighbours keeps its mass, so every row sums to 1 up to rounding.  Duplicate sources
+        are allowed."""
+        import torch
+        alpha, iters = self._walk_of(alpha, iters, 'rooted_pagerank')
+        g = int(g)
+        if not 0 <= g < self.n_graphs:
+            raise ValueError('rooted_pagerank: graph %d of a store with %d graph(s)' % (g, self.n_graphs))
+        a = np.asarray(sources, np.int64).reshape(-1)
+        if len(a) and (a.min() < 0 or a.max() >= self.n_nodes[g]):
+            raise ValueError('rooted_pagerank: node id outside graph %d (%d nodes)' % (g, self.n_nodes[g]))
+        out = torch.empty((len(a), self.n_nodes[g]), dtype=torch.float32, device='cuda')
+        if len(a):
+            d_a = torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
+            _lib.check(_lib.lib().gm_store_rooted_pagerank(self.handle, g, _lib.ptr(d_a), len(a), alpha, iters, _lib.ptr(out), _lib.stream_ptr()),
+                       'gm_store_rooted_pagerank')
+        return out.cpu().numpy()
+
+    def pair_pagerank(self, g, pairs, mask_target=False, alpha=0.15, iters=20):
+        """float32 [m, 2]: for each of the [m, 2] node `pairs` of graph `g`, canonicalised to (u, v) = (min, max), the rooted PageRank of v seen from u and of
+        u seen from v (rooted_pagerank's entries, bit for bit), computed on the device (gm_store_pair_pagerank).  mask_target=True walks an adjacent pair's
+        two columns in the graph without the pair's own edge.  gmeta_amd.rooted_pagerank_index turns the rows into the score."""
+        import torch
+        alpha, iters = self._walk_of(alpha, iters, 'pair_pagerank')
+        g, p = self._pairs_of(g, pairs, 'pair_pagerank')
+        out = torch.empty((len(p), 2), dtype=torch.float32, device='cuda')
+        if len(p):
+            d_p = torch.from_numpy(np.ascontiguousarray(p, np.int32)).cuda()
+            _lib.check(_lib.lib().gm_store_pair_pagerank(self.handle, g, _lib.ptr(d_p), len(p), _lib.PAIR_MASK_TARGET if mask_target else 0, alpha, iters,
+                                                         _lib.ptr(out), _lib.stream_ptr()), 'gm_store_pair_pagerank')
+        return out.cpu().numpy()
+
     def neighbour_degrees(self, g):
         """int32 [N]: the number of distinct neighbours (either direction, itself aside) of every node of graph `g` -- the degrees the pair scores use."""
         import torch

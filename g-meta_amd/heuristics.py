@@ -1,13 +1,15 @@
 """Neighbourhood heuristics as a link-prediction baseline: the scores of GraphStore.pair_scores (gm_store_pair_scores; the definition is in
 include/gmeta_hip.h) turned into the ROC AUC a learned link predictor is held against.  The scores come from the device; the AUC is host work over
 one number per pair.  The path scores one step further -- the local path index and the truncated Katz index -- are formed here, in float64, from the exact walk
-counts of GraphStore.pair_walks (gm_store_pair_walks)."""
+counts of GraphStore.pair_walks (gm_store_pair_walks).  The one global score, rooted PageRank, is the float64 sum of the two columns of
+GraphStore.pair_pagerank (gm_store_pair_pagerank)."""
 import numpy as np
 
 from .negatives import _pair
 
 PAIR_SCORES = ('cn', 'jaccard', 'adamic_adar', 'resource_allocation', 'pref_attachment')      # the columns of GraphStore.pair_scores, in order
 PATH_SCORES = ('local_path', 'katz')                                                          # the scores made of GraphStore.pair_walks' three columns
+PAGERANK_SCORES = ('rooted_pagerank',)                                                        # the score made of GraphStore.pair_pagerank's two columns
 
 
 def link_auc(scores, labels):
@@ -75,6 +77,28 @@ def link_path_auc(store, names, labels, mask_target=False, eps=0.01, beta=0.005)
     mask_target as in link_heuristic_auc."""
     w = link_path_scores(store, names, mask_target)
     return {'local_path': link_auc(local_path_index(w, eps), labels), 'katz': link_auc(katz_index(w, beta), labels)}
+
+
+def rooted_pagerank_index(cols):
+    """float64 [m]: pi_u(v) + pi_v(u) of the float32 [m, 2] columns of GraphStore.pair_pagerank -- the symmetric rooted PageRank score of a pair."""
+    c = np.asarray(cols, np.float32).reshape(-1, 2).astype(np.float64)
+    return c[:, 0] + c[:, 1]
+
+
+def link_pagerank_scores(store, names, mask_target=False, alpha=0.15, iters=20):
+    """float32 [len(names), 2]: GraphStore.pair_pagerank of the pairs named 'g_i_j', one call per graph, rows in the order of `names`."""
+    trip = np.asarray([_pair(nm) for nm in names], np.int64).reshape(-1, 3)
+    out = np.zeros((len(trip), 2), np.float32)
+    for g in np.unique(trip[:, 0]).tolist():
+        at = np.nonzero(trip[:, 0] == g)[0]
+        out[at] = store.pair_pagerank(g, trip[at, 1:], mask_target=mask_target, alpha=alpha, iters=iters)
+    return out
+
+
+def link_pagerank_auc(store, names, labels, mask_target=False, alpha=0.15, iters=20):
+    """{'rooted_pagerank': ROC AUC} (PAGERANK_SCORES) over the pairs `names` ('g_i_j') with the 0 / 1 `labels` of a link table, all graphs together;
+    mask_target as in link_heuristic_auc."""
+    return {'rooted_pagerank': link_auc(rooted_pagerank_index(link_pagerank_scores(store, names, mask_target, alpha, iters)), labels)}
 
 
 def candidate_names(g, nodes, partners):

@@ -215,6 +215,41 @@ int32_t gm_store_pair_candidates(const gm_store_t* s, int32_t g, const int32_t* 
  * a walk_lanes value that is no instantiation.  GM_ERANGE: more than 2^30 work items in one call (a walk_chunk far too small for the pairs). */
 int32_t gm_store_pair_walks(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, int64_t* d_out, void* stream);
 
+/* ---- ROOTED PAGERANK of sources and node pairs (beyond the reference): the one GLOBAL score among the baselines a link predictor is held against -- the
+ * stationary mass a walk from s that returns to s with probability alpha leaves on every node, after a fixed number of steps, on the device.  This comment is
+ * THE definition; tests/pagerank_ref.py restates it in float64.  Per parent graph g of a store, with N nodes:
+ *   neighbourhood  G(x) and deg are those of gm_store_pair_scores: DISTINCT nodes joined in either direction, self loops never count, parallel copies count
+ *                  once, weights are ignored.
+ *   column         a pair (s, x): s the source, x = -1 or a node whose edge {s, x} is removed.  The column's graph G' is G when x = -1, x == s or x not in
+ *                  G(s); otherwise G without that one edge: only the rows of s and x lose an entry, deg' s = deg s - 1, deg' x = deg x - 1.
+ *   walk           a = (float)alpha, b = 1.0f - a, in fp32.  p_0 = e_s; for t = 0 .. iters - 1:  p_{t+1}[v] = a [v == s] + b m_t[v], where
+ *                  m_t[v] = sum over z in G'(v) of p_t[z] / deg' z when deg' v > 0, and m_t[v] = p_t[v] when deg' v == 0: a node without neighbours keeps
+ *                  its mass.  So the walk keeps its mass -- sum_v p_{t+1}[v] = a + b sum_v p_t[v]: 1 up to the rounding of b and of the sums -- and an isolated source
+ *                  gives p = e_s for every t (in fp32 a + b rounds to 1.0f).  pi_(s,x) = p_iters, fp32.
+ *                  0 < alpha < 1, finite; iters in 1 .. 255.
+ *   gm_store_rooted_pagerank   d_sources: device int32 [m]; d_out: device fp32 [m, N], row r = pi_(sources[r], -1).  Duplicates are allowed, every row is
+ *                  written on its own; a source outside [0, N) gives a row of zeros.  Nothing behind row m - 1 is written.
+ *   gm_store_pair_pagerank     d_pairs: device int32 [n, 2], any orientation, a == b allowed; a pair is canonicalised to (u, v) = (min, max).  d_out: device
+ *                  fp32 [n, 2].  Without a flag column 0 = pi_(u,-1)[v], column 1 = pi_(v,-1)[u].  With GM_PAIR_MASK_TARGET (1) in `flags` column 0 =
+ *                  pi_(u,v)[v], column 1 = pi_(v,u)[u]: the score in the graph without the pair's own edge, as the other two pair calls mask it; a
+ *                  non-adjacent pair gives the bits of the unflagged call.  A node outside the graph gives two zeros.  The score pi_u(v) + pi_v(u) is formed
+ *                  on the host in float64 (g-meta_amd/heuristics.py), as the path scores are.
+ *   exactness      no float atomics, nothing depends on arrival order.  A row sum runs in ascending neighbour order; a row of more than C entries is summed
+ *                  in segments of C whose partial sums are added in ascending order (gm_set_tuning("ppr_chunk", C), 0 = the library's choice): the order of
+ *                  a row sum belongs to that configuration, as the order of a score sum belongs to pair_lanes.  For one value of ppr_chunk a row of either
+ *                  result is bit for bit a function of (graph, its own source or pair, flags, alpha, iters) alone: not of the other rows of the call, their
+ *                  order or their duplicates, not of how many columns a round holds (gm_set_tuning("ppr_cols", B), a multiple of 64 up to 4096, 0 = the
+ *                  library's choice), not of the stream; and the same from either export: gm_store_pair_pagerank without the flag gives the entries of
+ *                  gm_store_rooted_pagerank's rows, bitwise.
+ * Both calls read the neighbour index (built at first use, as for gm_store_pair_scores), run on `stream`, take their scratch -- two fp32 [N, B] states and
+ * the hub rows' partial sums -- from the stream-ordered pool, and read the sources or pairs (and the graph's row lengths) back once to form the distinct
+ * columns; the result is complete in stream order.  n == 0 / m == 0 is a no-op.
+ * GM_EINVAL (the message names the value): a bad graph index, n / m negative or above INT32_MAX, unknown flag bits, alpha outside (0, 1) or not finite, iters
+ * outside 1 .. 255, a NULL argument with work to do, a negative ppr_chunk, a ppr_cols that is no multiple of 64 or above 4096. */
+int32_t gm_store_rooted_pagerank(const gm_store_t* s, int32_t g, const int32_t* d_sources, int64_t m, float alpha, int32_t iters, float* d_out, void* stream);
+int32_t gm_store_pair_pagerank(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, float alpha, int32_t iters, float* d_out,
+                               void* stream);
+
 /* ---- Extraction: replaces Subgraphs.generate_subgraph / generate_subgraph_link_pred
  * (sdp.py:295-346: h-hop in-neighbour expansion, node sampling, G.subgraph) and dgl.batch
  * (sdp.py:399-406) for n_sets sets at once.  seeds/set_offsets are host arrays; set s owns seeds

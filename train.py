@@ -71,6 +71,9 @@ def parse(argv=None):
                          'Adamic-Adar, resource allocation, preferential attachment; GraphStore.pair_scores) over the pairs of the test table -- the baseline a '
                          'learned link predictor is held against; follows --mask_target.  2: that line and a second one with the two path scores over walks of up to '
                          'three steps (local path index, truncated Katz index; GraphStore.pair_walks)')
+    ap.add_argument('--pagerank', type=int, default=0, choices=[0, 1],
+                    help='1 (--link_pred_mode True): after the test evaluation and the --heuristics lines, print the ROC AUC of the rooted PageRank score (the one global '
+                         'baseline: GraphStore.pair_pagerank, alpha 0.15, 20 iterations) over the pairs of the test table; follows --mask_target, independent of --heuristics')
     ap.add_argument('--readout', default='centre', choices=['centre', 'mean'],
                     help="what the head reads of every subgraph: 'centre' = the centre row (both endpoints' rows of a pair), as the reference; 'mean' = the mean "
                          "over all of its rows (the dgl.mean_nodes line the reference left commented out), one pooled vector for pairs too")
@@ -86,6 +89,8 @@ def parse(argv=None):
     a = ap.parse_args(argv)
     if a.heuristics == 2 and a.link_pred_mode != 'True':      # refused before any data is read: node tasks have no pairs to score (--heuristics 1 keeps its check in main())
         raise SystemExit('--heuristics 2 scores node PAIRS: it needs --link_pred_mode True')
+    if a.pagerank and a.link_pred_mode != 'True':
+        raise SystemExit('--pagerank 1 scores node PAIRS: it needs --link_pred_mode True')
     return a
 
 
@@ -205,6 +210,12 @@ def main(args):
             res['path_auc'] = gmeta_amd.link_path_auc(store, names, labels, mask_target=bool(args.mask_target))
             if rank == 0:
                 print('Path test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['path_auc'].items()))
+    if args.pagerank:
+        from gmeta_amd.negatives import read_link_tables
+        names, labels = (tables if tables is not None else read_link_tables(root))['test']
+        res['pagerank_auc'] = gmeta_amd.link_pagerank_auc(store, names, labels, mask_target=bool(args.mask_target))
+        if rank == 0:
+            print('PageRank test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['pagerank_auc'].items()))
     return res
 
 
