@@ -18,7 +18,8 @@
 //               sorted order of unique keys does not.
 // Everything runs on the caller's stream; scratch comes from the stream-ordered pool and goes back to it on that stream.  No float arithmetic at all here,
 // no scratch memory in the kernels, integer atomics only where the result cannot depend on their order (bit sets, histogram counts).
-#include "gm_internal.h"
+#include "gm_nbr.h"
+#include "gm_devutil.h"      // wld / wst: the bitmap words in LDS (G = false) or in the workgroup's slab of HBM (G = true, agent-scope atomics: L1 is not coherent with the atomics that set the bits)
 
 #define GM_CAND_THREADS 256
 #define GM_CAND_WAVES (GM_CAND_THREADS / GM_WAVE)
@@ -29,23 +30,12 @@
 #define GM_CAND_COLS 5
 #define GM_CAND_ROUND_DEFAULT (1 << 22)   // pairs per round: 28 bytes of scratch each (the pair and its five scores)
 
-// one parent graph of a store inside the neighbour index (pair_scores.hip): rows by LOCAL node id, offsets global (into idx), neighbours local
+// the graph's view and the length of a membership bitmap over its nodes
 struct cand_graph {
-    const int64_t* ptr;          // gm_store::d_nbr_ptr + node_off[g]   [N + 1]
-    const int32_t* idx;          // gm_store::d_nbr_idx
-    int32_t N, words;            // words = ceil(N / 32)
+    gm_nbr_graph g;
+    int32_t words;               // ceil(N / 32); the host has checked N <= INT32_MAX
 };
 
-// Bitmap words in LDS (G = false) or in the workgroup's slab of HBM (G = true): there every access is an agent-scope relaxed atomic -- the bits are set
-// with L2 atomics and a CU's L1 is not coherent with those (extract.hip's wld / wst, restated: that translation unit keeps them static)
-template <bool G> __device__ __forceinline__ uint32_t cw_ld(const uint32_t* p) {
-    if (G) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return *p;
-}
-template <bool G> __device__ __forceinline__ void cw_st(uint32_t* p, uint32_t v) {
-    if (G) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
 template <bool G> __device__ __forceinline__ void cw_sync() {
     if (G) __threadfence();
     __syncthreads();
@@ -76,6 +66,8 @@ k_cand_walk(cand_graph Gr, const int32_t* __restrict__ nodes, int32_t m, uint32_
     __shared__ int part[GM_CAND_WAVES];
     const int tid = (int)threadIdx.x, lane = tid & (GM_WAVE - 1), wave = tid / GM_WAVE;
     const int grp = tid / GM_CAND_GROUP, gl = tid & (GM_CAND_GROUP - 1);
+    const gm_nbr_graph& Nb = Gr.g;
+    const int32_t N = (int32_t)Nb.N;
     const int words = Gr.words;
     uint32_t* bm = G ? slab + (int64_t)blockIdx.x * words : lds_bm;
     if (!G) {
@@ -86,27 +78,27 @@ k_cand_walk(cand_graph Gr, const int32_t* __restrict__ nodes, int32_t m, uint32_
     const int w0 = min(tid * wpt, words), w1 = min(w0 + wpt, words);
     for (int32_t r = (int32_t)blockIdx.x; r < m; r += (int32_t)gridDim.x) {
         const int32_t a = nodes[r];
-        if (a < 0 || a >= Gr.N) {                                               // a source outside the graph: C is empty (uniform over the workgroup)
+        if (a < 0 || a >= N) {                                                  // a source outside the graph: C is empty (uniform over the workgroup)
             if (!FILL && tid == 0) total[r] = 0;
             continue;
         }
-        const int64_t a0 = Gr.ptr[a];
-        const int32_t da = (int32_t)(Gr.ptr[a + 1] - a0);
-        const int32_t* __restrict__ row = Gr.idx + a0;
+        const int64_t a0 = Nb.ptr[a];
+        const int32_t da = (int32_t)(Nb.ptr[a + 1] - a0);
+        const int32_t* __restrict__ row = Nb.idx + a0;
         // short rows: one per group of eight lanes
         for (int32_t i = grp; i < da; i += GM_CAND_THREADS / GM_CAND_GROUP) {
             const int32_t z = row[i];
-            const int64_t z0 = Gr.ptr[z];
-            const int32_t dz = (int32_t)(Gr.ptr[z + 1] - z0);
+            const int64_t z0 = Nb.ptr[z];
+            const int32_t dz = (int32_t)(Nb.ptr[z + 1] - z0);
             if (dz > GM_CAND_LONG) continue;
-            for (int32_t j = gl; j < dz; j += GM_CAND_GROUP) { const int32_t w = Gr.idx[z0 + j]; atomicOr(&bm[w >> 5], 1u << (w & 31)); }
+            for (int32_t j = gl; j < dz; j += GM_CAND_GROUP) { const int32_t w = Nb.idx[z0 + j]; atomicOr(&bm[w >> 5], 1u << (w & 31)); }
         }
         // long rows: the waves take them in turn, 64 lanes a row
         int seen = 0;
         for (int32_t base = 0; base < da; base += GM_WAVE) {
             const int32_t i = base + lane;
             int64_t z0 = 0; int32_t dz = 0;
-            if (i < da) { const int32_t z = row[i]; z0 = Gr.ptr[z]; dz = (int32_t)(Gr.ptr[z + 1] - z0); }
+            if (i < da) { const int32_t z = row[i]; z0 = Nb.ptr[z]; dz = (int32_t)(Nb.ptr[z + 1] - z0); }
             unsigned long long ml = __ballot(dz > GM_CAND_LONG);
             while (ml) {
                 const int b = __ffsll((long long)ml) - 1;
@@ -114,7 +106,7 @@ k_cand_walk(cand_graph Gr, const int32_t* __restrict__ nodes, int32_t m, uint32_
                 if ((seen++ & (GM_CAND_WAVES - 1)) != wave) continue;
                 const int64_t s0 = __shfl(z0, b, GM_WAVE);
                 const int32_t ds = __shfl(dz, b, GM_WAVE);
-                for (int32_t j = lane; j < ds; j += GM_WAVE) { const int32_t w = Gr.idx[s0 + j]; atomicOr(&bm[w >> 5], 1u << (w & 31)); }
+                for (int32_t j = lane; j < ds; j += GM_WAVE) { const int32_t w = Nb.idx[s0 + j]; atomicOr(&bm[w >> 5], 1u << (w & 31)); }
             }
         }
         cw_sync<G>();
@@ -123,23 +115,23 @@ k_cand_walk(cand_graph Gr, const int32_t* __restrict__ nodes, int32_t m, uint32_
         if (tid == 0) atomicAnd(&bm[a >> 5], ~(1u << (a & 31)));
         cw_sync<G>();
         int c = 0;
-        for (int w = w0; w < w1; ++w) c += __popc(cw_ld<G>(&bm[w]));
+        for (int w = w0; w < w1; ++w) c += __popc(wld<G>(&bm[w]));
         int tot;
         const int inc = block_scan(c, part, &tot);
         if (!FILL) {
             if (tid == 0) total[r] = tot;
-            for (int w = w0; w < w1; ++w) cw_st<G>(&bm[w], 0u);
+            for (int w = w0; w < w1; ++w) wst<G>(&bm[w], 0u);
         } else {
             int64_t pos = (int64_t)off[r] + (inc - c);
             for (int w = w0; w < w1; ++w) {
-                uint32_t bits = cw_ld<G>(&bm[w]);
+                uint32_t bits = wld<G>(&bm[w]);
                 while (bits) {
                     const int b = __ffs((int)bits) - 1;
                     bits &= bits - 1u;
                     pairs[2 * pos] = a; pairs[2 * pos + 1] = w * 32 + b;
                     ++pos;
                 }
-                cw_st<G>(&bm[w], 0u);
+                wst<G>(&bm[w], 0u);
             }
         }
         cw_sync<G>();                                                           // the bitmap is zero before the next source sets a bit
@@ -221,14 +213,6 @@ k_cand_select(const int32_t* __restrict__ pairs, const float* __restrict__ score
     }
 }
 
-// device scratch of one call: handed back to the pool on the call's stream, whichever way the call ends
-struct cand_scratch {
-    hipStream_t st;
-    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-    explicit cand_scratch(hipStream_t s) : st(s) {}
-    ~cand_scratch() { for (void* q : p) gm_dev_free(q, st); }
-};
-
 template <bool FILL>
 static void cand_launch_walk(bool hbm, unsigned grid, size_t lds, hipStream_t st, const cand_graph& G, const int32_t* nodes, int32_t m, uint32_t* slab, const int32_t* off,
                              int32_t* total, int32_t* pairs) {
@@ -239,16 +223,14 @@ static void cand_launch_walk(bool hbm, unsigned grid, size_t lds, hipStream_t st
 extern "C" int32_t gm_store_pair_candidates(const gm_store_t* s, int32_t g, const int32_t* d_nodes, int64_t m, int32_t k, int32_t col, int32_t* d_out_nodes,
                                             float* d_out_scores, int32_t* d_out_total, void* stream) {
     const char* what = "gm_store_pair_candidates";
-    GM_REQUIRE(s, GM_EINVAL, "%s: store is NULL", what);
-    GM_REQUIRE(g >= 0 && g < s->n_graphs, GM_EINVAL, "%s: graph %d of a store with %d graph(s)", what, g, s->n_graphs);
-    GM_REQUIRE(m >= 0 && m <= (int64_t)INT32_MAX, GM_EINVAL, "%s: m = %lld", what, (long long)m);
+    GM_TRY(gm_store_call_check(what, s, g, "m", m));
     GM_REQUIRE(k >= 1 && k <= GM_CAND_MAX_K, GM_EINVAL, "%s: k = %d; 1 .. %d", what, k, GM_CAND_MAX_K);
     GM_REQUIRE(col >= 0 && col < GM_CAND_COLS, GM_EINVAL, "%s: col = %d; 0 .. 4 (cn, jaccard, adamic_adar, resource_allocation, pref_attachment)", what, col);
     GM_TRY(gm_pair_lanes(s, g, what, nullptr));
     const int home = gm_knob().cand_bitmap, budget_knob = gm_knob().cand_round;
     GM_REQUIRE(home >= 0 && home <= 2, GM_EINVAL, "%s: cand_bitmap = %d; 0 (the library's choice), 1 (LDS) or 2 (HBM slab)", what, home);
     GM_REQUIRE(budget_knob >= 0, GM_EINVAL, "%s: cand_round = %d", what, budget_knob);
-    const int64_t no = s->node_off[g], N = s->node_off[g + 1] - no;
+    const int64_t N = s->node_off[g + 1] - s->node_off[g];
     GM_REQUIRE(N <= (int64_t)INT32_MAX, GM_ERANGE, "%s: graph %d has %lld nodes", what, g, (long long)N);
     const int32_t words = (int32_t)((N + 31) / 32);
     GM_REQUIRE(!(home == 1 && words > GM_CAND_LDS_WORDS), GM_EINVAL, "%s: cand_bitmap = 1 (LDS) but graph %d has %lld nodes; the LDS bitmap holds %d at most", what, g,
@@ -262,15 +244,15 @@ extern "C" int32_t gm_store_pair_candidates(const gm_store_t* s, int32_t g, cons
     gm_phase_timer tm("pair candidates");
     const bool timed = gm_knob().timing != 0;
     const bool hbm = home == 2 || words > GM_CAND_LDS_WORDS;
-    const cand_graph G = {s->d_nbr_ptr + no, s->d_nbr_idx, (int32_t)N, words};
+    const cand_graph G = {gm_nbr_graph_of(s, g), words};
     const size_t lds = hbm ? 0 : (size_t)(words ? words : 1) * sizeof(uint32_t);
     const int64_t slabs = std::min<int64_t>(m, 2 * (int64_t)gm_num_cus());     // HBM home: a fixed grid strides the sources, one slab a workgroup
     const unsigned walk_grid = (unsigned)(hbm ? slabs : m);
 
-    cand_scratch sc(st);
+    gm_scratch sc(st);
     uint32_t* slab = nullptr;
     if (hbm) {
-        GM_TRY(gm_dev_alloc(&sc.p[0], (size_t)slabs * (size_t)words * sizeof(uint32_t), st)); slab = (uint32_t*)sc.p[0];
+        GM_TRY(sc.take(&slab, (size_t)slabs * (size_t)words));
         GM_HIP(hipMemsetAsync(slab, 0, (size_t)slabs * (size_t)words * sizeof(uint32_t), st));
     }
     // the count pass over every source; the host cuts the rounds by the exact set sizes
@@ -294,10 +276,10 @@ extern "C" int32_t gm_store_pair_candidates(const gm_store_t* s, int32_t g, cons
         max_pairs = std::max(max_pairs, sum); max_src = std::max(max_src, r1 - r0);
         r0 = r1;
     }
-    int32_t* pairs; float* scores; int32_t* off;
-    GM_TRY(gm_dev_alloc(&sc.p[1], (size_t)std::max<int64_t>(max_pairs, 1) * 2 * sizeof(int32_t), st)); pairs = (int32_t*)sc.p[1];
-    GM_TRY(gm_dev_alloc(&sc.p[2], (size_t)std::max<int64_t>(max_pairs, 1) * GM_CAND_COLS * sizeof(float), st)); scores = (float*)sc.p[2];
-    GM_TRY(gm_dev_alloc(&sc.p[3], (size_t)(max_src + 1) * sizeof(int32_t), st)); off = (int32_t*)sc.p[3];
+    int32_t* pairs = nullptr; float* scores = nullptr; int32_t* off = nullptr;
+    GM_TRY(sc.take(&pairs, (size_t)max_pairs * 2));
+    GM_TRY(sc.take(&scores, (size_t)max_pairs * GM_CAND_COLS));
+    GM_TRY(sc.take(&off, (size_t)(max_src + 1)));
 
     std::vector<int32_t> h_off;
     for (const round& R : rounds) {

@@ -11,38 +11,16 @@
 #include <mutex>
 #include <type_traits>
 #include "gm_internal.h"
+#include "gm_devutil.h"      // lowbias32, sample_salt; wld / wst: the bitmap words in LDS (G = false) or in the workgroup's slab of HBM (G = true)
 
 #define EX_BLOCK 512
 #define EX_WAVES (EX_BLOCK / GM_WAVE)
 
-__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ uint32_t sample_salt(uint64_t seed, int g, int i, int j) {
-    uint32_t s = lowbias32((uint32_t)(seed & 0xffffffffu) ^ 0x9E3779B9u);
-    s = lowbias32(s ^ (uint32_t)(seed >> 32));
-    s = lowbias32(s + (uint32_t)g * 0x85EBCA6Bu);
-    s = lowbias32(s ^ (uint32_t)i);
-    s = lowbias32(s + (uint32_t)(j + 1) * 0xC2B2AE35u);
-    return s;
-}
 __device__ __forceinline__ int lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-// Bitmap words live in LDS (G = false) or, for parent graphs too large for it, in a per-workgroup slab of global memory
-// (G = true).  In the global case every word access is an agent-scope relaxed atomic: the bits are set with L2 atomics, and a
-// CU's L1 is not coherent with those, so plain loads could return stale words.
-template <bool G> __device__ __forceinline__ uint32_t wld(const uint32_t* p) {
-    if (G) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return *p;
-}
-template <bool G> __device__ __forceinline__ void wst(uint32_t* p, uint32_t v) {
-    if (G) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
 }
 template <bool G> __device__ __forceinline__ bool bit_test(const uint32_t* bm, int v) { return (wld<G>(&bm[v >> 5]) >> (v & 31)) & 1u; }
 __device__ __forceinline__ void bit_set(uint32_t* bm, int v) { atomicOr(&bm[v >> 5], 1u << (v & 31)); }

@@ -60,7 +60,7 @@ struct gm_store {
     // entry 2^r below its bound keeps min(22, 39 - r) bits, so a table whose largest entry sits more than 2^14 above its typical one (or is
     // not finite / above 2^50) would lose precision silently
     std::vector<float> h_feat_amax, h_feat_mean;
-    // neighbour index of the pair scores (pair_scores.hip; definition: include/gmeta_hip.h): per node the ascending DISTINCT row of its in- and out-neighbours
+    // neighbour index of the link-prediction calls (nbr_index.hip; what the kernels see of it: gm_nbr.h; definition: include/gmeta_hip.h): per node the ascending DISTINCT row of its in- and out-neighbours
     // without itself, and the per-node terms.  Built at the first call that needs it, under nbr_mu, and complete on the device before nbr_ready is set:
     // afterwards any stream reads it without an event.  Freed by gm_store_destroy.
     mutable std::mutex nbr_mu;
@@ -267,10 +267,23 @@ struct gm_knobs {
 };
 const gm_knobs& gm_knob();
 
-// ---- the neighbour index and the pair-score launch (pair_scores.hip), for the translation units that score pairs of their own (candidates.hip)
+// ---- the neighbour index (nbr_index.hip; the device side is gm_nbr.h) and the pair-score launch (pair_scores.hip), for the translation units that read the one
+// and score pairs of their own through the other (candidates.hip)
 int gm_nbr_index(const gm_store* s);                                                      // builds the index at first use (under gm_store::nbr_mu); complete on the device on return
+void gm_nbr_release(const gm_store* s);                                                   // frees the index's five device arrays (a failed build, gm_store_destroy)
 int gm_pair_lanes(const gm_store* s, int32_t g, const char* what, int* lpp);              // GM_EINVAL for a pair_lanes knob that is no instantiation; *lpp (optional; needs the index) = the lanes per pair in force
 int gm_pair_scores_launch(const gm_store* s, int32_t g, int lpp, const int32_t* d_pairs, int64_t n, int mask, float* d_out, hipStream_t st);      // k_pair_scores<lpp> over n pairs of graph g
+
+// What every store-level link-prediction call checks first: the store, the graph and -- with cnt_name, the count's name in the call's signature -- the count
+// 0 .. INT32_MAX and the flag bits.  (gm_store_has_edges and gm_store_negative_pairs have count bounds of their own and pass no name.)
+static inline int gm_store_call_check(const char* what, const gm_store* s, int32_t g, const char* cnt_name = nullptr, int64_t n = 0, int32_t flags = 0) {
+    GM_REQUIRE(s, GM_EINVAL, "%s: store is NULL", what);
+    GM_REQUIRE(g >= 0 && g < s->n_graphs, GM_EINVAL, "%s: graph %d of a store with %d graph(s)", what, g, s->n_graphs);
+    if (!cnt_name) return GM_OK;
+    GM_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX, GM_EINVAL, "%s: %s = %lld", what, cnt_name, (long long)n);
+    GM_REQUIRE((flags & ~GM_PAIR_MASK_TARGET) == 0, GM_EINVAL, "%s: unknown flag bits 0x%x (GM_PAIR_MASK_TARGET = 1)", what, (unsigned)flags);
+    return GM_OK;
+}
 
 // ---- host phase timing for the setup paths (env GM_TIMING=1 prints to stderr)
 #include <chrono>
@@ -319,6 +332,25 @@ struct gm_stager {
         T* h = (T*)take((n ? n : 1) * sizeof(T));
         if (h && n && hipMemcpyAsync(h, dsrc, n * sizeof(T), hipMemcpyDeviceToHost, s) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         return h;
+    }
+};
+
+// ---- device scratch of one call: taken from the stream-ordered pool and handed back to it on the call's stream, whichever way the call ends
+struct gm_scratch {
+    hipStream_t st;
+    std::vector<void*> p;
+    explicit gm_scratch(hipStream_t s) : st(s) {}
+    ~gm_scratch() { for (void* q : p) gm_dev_free(q, st); }
+    gm_scratch(const gm_scratch&) = delete;
+    gm_scratch& operator=(const gm_scratch&) = delete;
+    template <class T> int take(T** d, size_t n) {
+        GM_TRY(gm_alloc(d, n, st));
+        p.push_back((void*)*d);
+        return GM_OK;
+    }
+    template <class T> int put(T** d, const std::vector<T>& v, gm_stager& sg) {
+        GM_TRY(take(d, v.size()));
+        return sg.upload(*d, v);
     }
 };
 

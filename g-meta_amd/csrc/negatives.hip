@@ -12,27 +12,12 @@
 //   output is a function of the definition alone: not of R, not of the schedule.  The host reads one counter per round and stops at n or at the budget.
 // Everything runs on the caller's stream; the table and the scratch come from the stream-ordered pool and go back to it on that stream.
 #include "gm_internal.h"
+#include "gm_devutil.h"      // lowbias32, sample_salt: extract.hip's hash and salt (oracle.lowbias32 / oracle.sample_salt)
 
 #define GM_NEG_SALT_TAG 0x6E454721      // the `i` of sample_salt(seed, g, i, mode) for this stream of random words
 #define GM_NEG_THREADS 256
 #define GM_NEG_MAX_ROUND (1 << 22)      // candidates per round at most (8 bytes of scratch each)
 #define GM_NEG_EMPTY 0xFFFFFFFFFFFFFFFFull
-
-// extract.hip's hash and salt (oracle.lowbias32 / oracle.sample_salt), restated: that translation unit keeps them static
-static __host__ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du;
-    x ^= x >> 15; x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-static uint32_t sample_salt(uint64_t seed, int g, int i, int j) {
-    uint32_t s = lowbias32((uint32_t)(seed & 0xffffffffu) ^ 0x9E3779B9u);
-    s = lowbias32(s ^ (uint32_t)(seed >> 32));
-    s = lowbias32(s + (uint32_t)g * 0x85EBCA6Bu);
-    s = lowbias32(s ^ (uint32_t)i);
-    s = lowbias32(s + (uint32_t)(j + 1) * 0xC2B2AE35u);
-    return s;
-}
 
 // one parent graph of a store: out-CSR rows by LOCAL node id, edge offsets global (into out_idx), destinations local
 struct neg_graph {
@@ -192,28 +177,15 @@ __global__ void __launch_bounds__(GM_NEG_THREADS) k_has_edges(neg_graph G, const
     out[i] = in && adjacent(G, a, b) ? 1 : 0;
 }
 
-// device scratch of one call: handed back to the pool on the call's stream, whichever way the call ends
-struct neg_scratch {
-    hipStream_t st;
-    void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    explicit neg_scratch(hipStream_t s) : st(s) {}
-    ~neg_scratch() { for (void* q : p) gm_dev_free(q, st); }
-};
-
-static int neg_graph_of(const gm_store* s, int32_t g, neg_graph* G, const char* what) {
-    GM_REQUIRE(s, GM_EINVAL, "%s: store is NULL", what);
-    GM_REQUIRE(g >= 0 && g < s->n_graphs, GM_EINVAL, "%s: graph %d of a store with %d graph(s)", what, g, s->n_graphs);
-    G->out_ptr = s->d_out_ptr + s->node_off[g]; G->out_idx = s->d_out_idx; G->N = s->node_off[g + 1] - s->node_off[g];
-    return GM_OK;
-}
+static neg_graph neg_graph_of(const gm_store* s, int32_t g) { return {s->d_out_ptr + s->node_off[g], s->d_out_idx, s->node_off[g + 1] - s->node_off[g]}; }
 
 extern "C" int32_t gm_store_negative_pairs(const gm_store_t* s, int32_t g, int64_t n, uint64_t seed, int32_t mode, const int64_t* d_exclude_keys, int64_t n_exclude,
                                            int32_t* d_out_pairs, int64_t* h_found, void* stream) {
     const char* what = "gm_store_negative_pairs";
     GM_REQUIRE(h_found, GM_EINVAL, "%s: h_found is NULL", what);
     *h_found = 0;
-    neg_graph G;
-    GM_TRY(neg_graph_of(s, g, &G, what));
+    GM_TRY(gm_store_call_check(what, s, g));
+    const neg_graph G = neg_graph_of(s, g);
     GM_REQUIRE(G.N >= 2, GM_EINVAL, "%s: graph %d has %lld node(s); a pair needs two", what, g, (long long)G.N);
     GM_REQUIRE(mode == GM_NEG_UNIFORM || mode == GM_NEG_TWO_HOP, GM_EINVAL, "%s: unknown mode %d (GM_NEG_UNIFORM = 0, GM_NEG_TWO_HOP = 1)", what, mode);
     GM_REQUIRE(n >= 0, GM_EINVAL, "%s: n = %lld", what, (long long)n);
@@ -232,13 +204,13 @@ extern "C" int32_t gm_store_negative_pairs(const gm_store_t* s, int32_t g, int64
     while (cap < 2 * (uint64_t)(n + R)) cap <<= 1;
     const int32_t nb = (int32_t)((R + GM_NEG_THREADS - 1) / GM_NEG_THREADS);
 
-    neg_scratch sc(st);
-    unsigned long long* tab_key; int32_t* tab_k; int2* cand; int32_t* blk; int32_t* state;
-    GM_TRY(gm_dev_alloc(&sc.p[0], cap * sizeof(unsigned long long), st)); tab_key = (unsigned long long*)sc.p[0];
-    GM_TRY(gm_dev_alloc(&sc.p[1], cap * sizeof(int32_t), st)); tab_k = (int32_t*)sc.p[1];
-    GM_TRY(gm_dev_alloc(&sc.p[2], (size_t)R * sizeof(int2), st)); cand = (int2*)sc.p[2];
-    GM_TRY(gm_dev_alloc(&sc.p[3], (size_t)nb * sizeof(int32_t), st)); blk = (int32_t*)sc.p[3];
-    GM_TRY(gm_dev_alloc(&sc.p[4], 2 * sizeof(int32_t), st)); state = (int32_t*)sc.p[4];
+    gm_scratch sc(st);
+    unsigned long long* tab_key = nullptr; int32_t* tab_k = nullptr; int2* cand = nullptr; int32_t* blk = nullptr; int32_t* state = nullptr;
+    GM_TRY(sc.take(&tab_key, cap));
+    GM_TRY(sc.take(&tab_k, cap));
+    GM_TRY(sc.take(&cand, (size_t)R));
+    GM_TRY(sc.take(&blk, (size_t)nb));
+    GM_TRY(sc.take(&state, 2));
     GM_HIP(hipMemsetAsync(tab_key, 0xFF, cap * sizeof(unsigned long long), st));
     GM_HIP(hipMemsetD32Async((hipDeviceptr_t)tab_k, INT32_MAX, cap, st));
     GM_HIP(hipMemsetAsync(state, 0, 2 * sizeof(int32_t), st));
@@ -266,8 +238,8 @@ extern "C" int32_t gm_store_negative_pairs(const gm_store_t* s, int32_t g, int64
 
 extern "C" int32_t gm_store_has_edges(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, uint8_t* d_out, void* stream) {
     const char* what = "gm_store_has_edges";
-    neg_graph G;
-    GM_TRY(neg_graph_of(s, g, &G, what));
+    GM_TRY(gm_store_call_check(what, s, g));
+    const neg_graph G = neg_graph_of(s, g);
     GM_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX * GM_NEG_THREADS, GM_EINVAL, "%s: n = %lld", what, (long long)n);
     if (n == 0) return GM_OK;
     GM_REQUIRE(d_pairs && d_out, GM_EINVAL, "%s: NULL argument", what);

@@ -1,6 +1,6 @@
 // Rooted PageRank of sources and node pairs (gm_store_rooted_pagerank, gm_store_pair_pagerank: the one global score among the link-prediction baselines).
-// The DEFINITION is in include/gmeta_hip.h; tests/pagerank_ref.py restates it in float64.  This file is how it is computed, over the neighbour index of
-// pair_scores.hip (gm_nbr_index):
+// The DEFINITION is in include/gmeta_hip.h; tests/pagerank_ref.py restates it in float64.  This file is how it is computed, over the neighbour index
+// (nbr_index.hip; gm_nbr.h):
 //   columns     a column is a pair (s, x): the walk from s in the graph without the edge {s, x} (x = -1: the whole graph).  The host reads the sources or pairs
 //               back once, forms the DISTINCT columns in ascending (s, x) order and runs them in rounds of at most B (gm_set_tuning("ppr_cols")); with the mask
 //               flag only adjacent pairs get a column of their own (adjacency: k_ppr_adjacent, before the read-back).
@@ -17,20 +17,13 @@
 // No float atomics, nothing depends on arrival order: a column's bits are a function of (graph, s, x, alpha, iters, C) alone.  Everything runs on the caller's
 // stream; scratch comes from the stream-ordered pool.
 #include <math.h>
-#include "gm_internal.h"
+#include "gm_nbr.h"
 
 #define GM_PPR_THREADS 256
 #define GM_PPR_WAVES (GM_PPR_THREADS / GM_WAVE)
 #define GM_PPR_UNROLL 8                   // row reads of Q in flight per lane
 #define GM_PPR_TILE 64                    // k_ppr_rows_out: nodes x output rows per workgroup
 #define GM_PPR_MAX_COLS 4096
-
-// one parent graph of a store inside the neighbour index (pair_scores.hip): rows by LOCAL node id, offsets global (into idx), neighbours local
-struct ppr_graph {
-    const int64_t* ptr;          // gm_store::d_nbr_ptr + node_off[g]   [N + 1]
-    const int32_t* idx;          // gm_store::d_nbr_idx
-    int64_t N;
-};
 
 // the columns of one round: source and excluded node per column (-1: no column / no excluded node), B a multiple of 64
 struct ppr_cols {
@@ -77,7 +70,7 @@ __device__ __forceinline__ void ppr_store(float sum, int32_t deg, int32_t v, int
 }
 
 // p_0 = e_s, pre-scaled: one thread per column (Q is zero beforehand)
-__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_seed(ppr_graph G, ppr_cols K, float* __restrict__ Q) {
+__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_seed(gm_nbr_graph G, ppr_cols K, float* __restrict__ Q) {
     const int32_t c = (int32_t)(blockIdx.x * GM_PPR_THREADS + threadIdx.x);
     if (c >= K.B) return;
     const int32_t cs = K.s[c];
@@ -88,7 +81,7 @@ __global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_seed(ppr_graph G, ppr_co
 
 // a wave per (row, slab of 64 columns); rows of more than C entries are left to k_ppr_parts / k_ppr_hubs
 template <bool MASK>
-__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_rows(ppr_graph G, ppr_cols K, int32_t slabs, int32_t C, float a, float b, int last,
+__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_rows(gm_nbr_graph G, ppr_cols K, int32_t slabs, int32_t C, float a, float b, int last,
                                                              const float* __restrict__ Qa, float* __restrict__ Qb) {
     const int64_t w = (int64_t)blockIdx.x * GM_PPR_WAVES + (threadIdx.x >> 6);
     const int64_t row = w / slabs;
@@ -107,7 +100,7 @@ __global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_rows(ppr_graph G, ppr_co
 
 // a wave per (segment of a hub row, slab): part[item, c] = the segment's sum
 template <bool MASK>
-__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_parts(ppr_graph G, ppr_cols K, int32_t slabs, int32_t C, const int32_t* __restrict__ it_row,
+__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_parts(gm_nbr_graph G, ppr_cols K, int32_t slabs, int32_t C, const int32_t* __restrict__ it_row,
                                                               const int32_t* __restrict__ it_seg, int64_t n_items, const float* __restrict__ Qa, float* __restrict__ part) {
     const int64_t w = (int64_t)blockIdx.x * GM_PPR_WAVES + (threadIdx.x >> 6);
     const int64_t item = w / slabs;
@@ -126,7 +119,7 @@ __global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_parts(ppr_graph G, ppr_c
 
 // a wave per (hub row, slab): its partials in ascending segment order, then the row as k_ppr_rows finishes it
 template <bool MASK>
-__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_hubs(ppr_graph G, ppr_cols K, int32_t slabs, const int32_t* __restrict__ hub_row,
+__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_hubs(gm_nbr_graph G, ppr_cols K, int32_t slabs, const int32_t* __restrict__ hub_row,
                                                              const int32_t* __restrict__ hub_first, int64_t n_hubs, float a, float b, int last,
                                                              const float* __restrict__ part, const float* __restrict__ Qa, float* __restrict__ Qb) {
     const int64_t w = (int64_t)blockIdx.x * GM_PPR_WAVES + (threadIdx.x >> 6);
@@ -177,39 +170,11 @@ __global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_entries_out(const float*
 }
 
 // adj[k] = 1 where the two nodes of pair k are distinct, inside the graph and neighbours (the pairs whose masked columns differ from the unmasked ones)
-__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_adjacent(ppr_graph G, const int32_t* __restrict__ pairs, int64_t n, uint8_t* __restrict__ adj) {
+__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_adjacent(gm_nbr_graph G, const int32_t* __restrict__ pairs, int64_t n, uint8_t* __restrict__ adj) {
     const int64_t k = (int64_t)blockIdx.x * GM_PPR_THREADS + threadIdx.x;
     if (k >= n) return;
-    const int32_t a = pairs[2 * k], b = pairs[2 * k + 1];
-    bool hit = false;
-    if (a != b && a >= 0 && a < G.N && b >= 0 && b < G.N) {
-        const int32_t* __restrict__ row = G.idx + G.ptr[a];
-        int32_t lo = 0, hi = (int32_t)(G.ptr[a + 1] - G.ptr[a]);
-        while (lo < hi && !hit) {
-            const int32_t mid = lo + ((hi - lo) >> 1), z = row[mid];
-            hit = z == b;
-            if (z < b) lo = mid + 1; else hi = mid;
-        }
-    }
-    adj[k] = hit ? 1 : 0;
+    adj[k] = gm_nbr_adjacent(G, pairs[2 * k], pairs[2 * k + 1]) ? 1 : 0;
 }
-
-// device scratch of one call: handed back to the pool on the call's stream, whichever way the call ends
-struct ppr_scratch {
-    hipStream_t st;
-    std::vector<void*> p;
-    explicit ppr_scratch(hipStream_t s) : st(s) {}
-    ~ppr_scratch() { for (void* q : p) gm_dev_free(q, st); }
-    template <class T> int take(T** d, size_t n) {
-        GM_TRY(gm_alloc(d, n, st));
-        p.push_back((void*)*d);
-        return GM_OK;
-    }
-    template <class T> int put(T** d, const std::vector<T>& v, gm_stager& sg) {
-        GM_TRY(take(d, v.size()));
-        return sg.upload(*d, v);
-    }
-};
 
 // Columns per round and entries per hub segment, from the sweep at the arxiv shape (profiles/pair_pagerank.txt).  Wider rounds are faster as long as there are
 // columns to fill them (1,024 sources: 37.4 / 33.0 / 31.3 ms at 64 / 128 / 256 columns); a round is never wider than the call's columns.  The cut has to be ONE
@@ -224,16 +189,13 @@ static unsigned ppr_grid(int64_t waves) { return (unsigned)((waves + GM_PPR_WAVE
 struct ppr_call {
     float alpha; int32_t iters; hipStream_t st;
     int B; int32_t C;             // the knobs in force
-    ppr_graph G;
+    gm_nbr_graph G;
 };
 
 // the checks both exports share; n == 0 leaves c->B == 0 (nothing to do)
 static int ppr_begin(const char* what, const char* cnt_name, const gm_store* s, int32_t g, int64_t n, int32_t flags, float alpha, int32_t iters, const void* d_in, const void* d_out,
                      void* stream, ppr_call* c) {
-    GM_REQUIRE(s, GM_EINVAL, "%s: store is NULL", what);
-    GM_REQUIRE(g >= 0 && g < s->n_graphs, GM_EINVAL, "%s: graph %d of a store with %d graph(s)", what, g, s->n_graphs);
-    GM_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX, GM_EINVAL, "%s: %s = %lld", what, cnt_name, (long long)n);
-    GM_REQUIRE((flags & ~GM_PAIR_MASK_TARGET) == 0, GM_EINVAL, "%s: unknown flag bits 0x%x (GM_PAIR_MASK_TARGET = 1)", what, (unsigned)flags);
+    GM_TRY(gm_store_call_check(what, s, g, cnt_name, n, flags));
     GM_REQUIRE(isfinite(alpha) && alpha > 0.f && alpha < 1.f, GM_EINVAL, "%s: alpha = %g; 0 < alpha < 1", what, (double)alpha);
     GM_REQUIRE(iters >= 1 && iters <= 255, GM_EINVAL, "%s: iters = %d; 1 .. 255", what, iters);
     const int cols = gm_knob().ppr_cols, chunk = gm_knob().ppr_chunk;
@@ -244,16 +206,34 @@ static int ppr_begin(const char* what, const char* cnt_name, const gm_store* s, 
     if (n == 0) return GM_OK;
     GM_REQUIRE(d_in && d_out, GM_EINVAL, "%s: NULL argument", what);
     GM_TRY(gm_nbr_index(s));
-    const int64_t no = s->node_off[g];
-    *c = {alpha, iters, (hipStream_t)stream, cols ? cols : ppr_cols_for(), chunk ? chunk : ppr_chunk_for(), {s->d_nbr_ptr + no, s->d_nbr_idx, s->node_off[g + 1] - no}};
+    *c = {alpha, iters, (hipStream_t)stream, cols ? cols : ppr_cols_for(), chunk ? chunk : ppr_chunk_for(), gm_nbr_graph_of(s, g)};
     return GM_OK;
+}
+
+// the hub rows of the cut and their segments, on the device
+struct ppr_hubs {
+    int64_t n_hubs = 0, n_items = 0;
+    int32_t *row = nullptr, *first = nullptr, *it_row = nullptr, *it_seg = nullptr;
+    float* part = nullptr;
+};
+
+// one iteration of a round's walk, src -> dst: the rows up to C entries, then the hub rows' segments and the hub rows
+template <bool MASK>
+static void ppr_iterate(const ppr_call& c, const ppr_cols& K, const ppr_hubs& H, int last, const float* src, float* dst) {
+    const int32_t slabs = K.B / GM_WAVE;
+    const float a = c.alpha, b = 1.0f - a;
+    const dim3 block(GM_PPR_THREADS), rows(ppr_grid(c.G.N * slabs)), parts(ppr_grid(H.n_items * slabs)), hubs(ppr_grid(H.n_hubs * slabs));
+    hipLaunchKernelGGL(k_ppr_rows<MASK>, rows, block, 0, c.st, c.G, K, slabs, c.C, a, b, last, src, dst);
+    if (!H.n_hubs) return;
+    hipLaunchKernelGGL(k_ppr_parts<MASK>, parts, block, 0, c.st, c.G, K, slabs, c.C, (const int32_t*)H.it_row, (const int32_t*)H.it_seg, H.n_items, src, H.part);
+    hipLaunchKernelGGL(k_ppr_hubs<MASK>, hubs, block, 0, c.st, c.G, K, slabs, (const int32_t*)H.row, (const int32_t*)H.first, H.n_hubs, a, b, last, (const float*)H.part, src, dst);
 }
 
 // The walk of the columns (cs[k], cx[k]), ascending, in rounds of at most B: after a round's last iteration emit(c0, Br, P) reads P[N, Br] = p of the
 // columns c0 .. c0 + Br on the call's stream (Br == 0, P == NULL: a call without a single column).  h_ptr: the graph's row pointers on the host.
 template <class Emit>
 static int ppr_rounds(const char* what, const ppr_call& c, const int64_t* h_ptr, std::vector<int32_t> cs, std::vector<int32_t> cx, gm_stager& sg, Emit emit) {
-    const ppr_graph& G = c.G;
+    const gm_nbr_graph& G = c.G;
     const int64_t N = G.N, ncols = (int64_t)cs.size(), ncp = (ncols + GM_WAVE - 1) / GM_WAVE * GM_WAVE;
     cs.resize((size_t)ncp, -1); cx.resize((size_t)ncp, -1);
     const int64_t Bmax = ncp < c.B ? ncp : c.B;
@@ -268,49 +248,33 @@ static int ppr_rounds(const char* what, const ppr_call& c, const int64_t* h_ptr,
         GM_REQUIRE(it_row.size() <= (size_t)(INT32_MAX / 2), GM_ERANGE, "%s: more than 2^30 hub segments at ppr_chunk = %d", what, (int)c.C);
     }
     hub_first.push_back((int32_t)it_row.size());
-    const int64_t n_hubs = (int64_t)hub_row.size(), n_items = (int64_t)it_row.size();
+    ppr_hubs H;
+    H.n_hubs = (int64_t)hub_row.size(); H.n_items = (int64_t)it_row.size();
 
-    ppr_scratch sc(c.st);
-    float *Qa = nullptr, *Qb = nullptr, *part = nullptr;
-    int32_t *d_cs = nullptr, *d_cx = nullptr, *d_hub_row = nullptr, *d_hub_first = nullptr, *d_it_row = nullptr, *d_it_seg = nullptr;
+    gm_scratch sc(c.st);
+    float *Qa = nullptr, *Qb = nullptr;
+    int32_t *d_cs = nullptr, *d_cx = nullptr;
     if (ncols) {
         GM_TRY(sc.take(&Qa, (size_t)(N * Bmax))); GM_TRY(sc.take(&Qb, (size_t)(N * Bmax)));
         GM_TRY(sc.put(&d_cs, cs, sg)); GM_TRY(sc.put(&d_cx, cx, sg));
-        if (n_hubs) {
-            GM_TRY(sc.take(&part, (size_t)(n_items * Bmax)));
-            GM_TRY(sc.put(&d_hub_row, hub_row, sg)); GM_TRY(sc.put(&d_hub_first, hub_first, sg));
-            GM_TRY(sc.put(&d_it_row, it_row, sg)); GM_TRY(sc.put(&d_it_seg, it_seg, sg));
+        if (H.n_hubs) {
+            GM_TRY(sc.take(&H.part, (size_t)(H.n_items * Bmax)));
+            GM_TRY(sc.put(&H.row, hub_row, sg)); GM_TRY(sc.put(&H.first, hub_first, sg));
+            GM_TRY(sc.put(&H.it_row, it_row, sg)); GM_TRY(sc.put(&H.it_seg, it_seg, sg));
         }
     }
-    const float a = c.alpha, b = 1.0f - a;
-    const dim3 block(GM_PPR_THREADS);
     for (int64_t c0 = 0; c0 == 0 || c0 < ncp; c0 += c.B) {
         const int32_t Br = (int32_t)(ncp - c0 < c.B ? ncp - c0 : c.B);
         const float* P = nullptr;
         if (Br) {
             const ppr_cols K = {d_cs + c0, d_cx + c0, Br};
-            const int32_t slabs = Br / GM_WAVE;
             bool mask = false;
             for (int32_t k = 0; k < Br && !mask; ++k) mask = cx[(size_t)(c0 + k)] >= 0;
             GM_HIP(hipMemsetAsync(Qa, 0, (size_t)(N * Br) * sizeof(float), c.st));
-            hipLaunchKernelGGL(k_ppr_seed, dim3((unsigned)((Br + GM_PPR_THREADS - 1) / GM_PPR_THREADS)), block, 0, c.st, G, K, Qa);
+            hipLaunchKernelGGL(k_ppr_seed, dim3((unsigned)((Br + GM_PPR_THREADS - 1) / GM_PPR_THREADS)), dim3(GM_PPR_THREADS), 0, c.st, G, K, Qa);
             float *src = Qa, *dst = Qb;
             for (int32_t t = 0; t < c.iters; ++t) {
-                const int last = t == c.iters - 1;
-                const dim3 rows(ppr_grid(N * slabs)), parts(ppr_grid(n_items * slabs)), hubs(ppr_grid(n_hubs * slabs));
-                if (mask) hipLaunchKernelGGL(k_ppr_rows<true>, rows, block, 0, c.st, G, K, slabs, c.C, a, b, last, (const float*)src, dst);
-                else hipLaunchKernelGGL(k_ppr_rows<false>, rows, block, 0, c.st, G, K, slabs, c.C, a, b, last, (const float*)src, dst);
-                if (n_hubs) {
-                    if (mask) {
-                        hipLaunchKernelGGL(k_ppr_parts<true>, parts, block, 0, c.st, G, K, slabs, c.C, (const int32_t*)d_it_row, (const int32_t*)d_it_seg, n_items, (const float*)src, part);
-                        hipLaunchKernelGGL(k_ppr_hubs<true>, hubs, block, 0, c.st, G, K, slabs, (const int32_t*)d_hub_row, (const int32_t*)d_hub_first, n_hubs, a, b, last,
-                                           (const float*)part, (const float*)src, dst);
-                    } else {
-                        hipLaunchKernelGGL(k_ppr_parts<false>, parts, block, 0, c.st, G, K, slabs, c.C, (const int32_t*)d_it_row, (const int32_t*)d_it_seg, n_items, (const float*)src, part);
-                        hipLaunchKernelGGL(k_ppr_hubs<false>, hubs, block, 0, c.st, G, K, slabs, (const int32_t*)d_hub_row, (const int32_t*)d_hub_first, n_hubs, a, b, last,
-                                           (const float*)part, (const float*)src, dst);
-                    }
-                }
+                (mask ? ppr_iterate<true> : ppr_iterate<false>)(c, K, H, t == c.iters - 1, src, dst);
                 GM_HIP(hipGetLastError());
                 std::swap(src, dst);
             }
@@ -327,6 +291,33 @@ static void ppr_span(const std::vector<int32_t>& col, int64_t c0, int64_t Br, in
     *hi = std::lower_bound(col.begin(), col.end(), c0 + Br) - col.begin();
 }
 
+// The columns a call walks and the order its output entries leave in.  want[e]: the column (source, excluded node) of output entry e as ppr_key packs it, -1:
+// no column (a node outside the graph).  -> cs / cx: the distinct columns in ascending (source, excluded) order; order: the entries stably by column number,
+// those without a column first; col[i]: the column number of entry order[i] (-1: none)
+struct ppr_plan {
+    std::vector<int32_t> cs, cx, col;
+    std::vector<int64_t> order;
+};
+static int64_t ppr_key(int32_t src, int32_t x) { return ((int64_t)src << 32) | (uint32_t)(x + 1); }
+static int ppr_plan_of(const char* what, const std::vector<int64_t>& want, ppr_plan* P) {
+    std::vector<int64_t> keys;
+    for (const int64_t w : want)
+        if (w >= 0) keys.push_back(w);
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    GM_REQUIRE(keys.size() <= (size_t)INT32_MAX, GM_ERANGE, "%s: %lld distinct columns", what, (long long)keys.size());
+    P->cs.resize(keys.size()); P->cx.resize(keys.size());
+    for (size_t k = 0; k < keys.size(); ++k) { P->cs[k] = (int32_t)(keys[k] >> 32); P->cx[k] = (int32_t)(uint32_t)keys[k] - 1; }
+    std::vector<int32_t> ecol(want.size());
+    for (size_t e = 0; e < want.size(); ++e) ecol[e] = want[e] < 0 ? -1 : (int32_t)(std::lower_bound(keys.begin(), keys.end(), want[e]) - keys.begin());
+    P->order.resize(want.size());
+    for (size_t e = 0; e < want.size(); ++e) P->order[e] = (int64_t)e;
+    std::stable_sort(P->order.begin(), P->order.end(), [&](int64_t p, int64_t q) { return ecol[(size_t)p] < ecol[(size_t)q]; });
+    P->col.resize(want.size());
+    for (size_t e = 0; e < want.size(); ++e) P->col[e] = ecol[(size_t)P->order[e]];
+    return GM_OK;
+}
+
 extern "C" int32_t gm_store_rooted_pagerank(const gm_store_t* s, int32_t g, const int32_t* d_sources, int64_t m, float alpha, int32_t iters, float* d_out, void* stream) {
     const char* what = "gm_store_rooted_pagerank";
     ppr_call c;
@@ -338,23 +329,19 @@ extern "C" int32_t gm_store_rooted_pagerank(const gm_store_t* s, int32_t g, cons
     const int64_t* h_ptr = sg.download(c.G.ptr, (size_t)(N + 1));
     GM_REQUIRE(h_src && h_ptr, GM_ENOMEM, "%s: pinned staging allocation failed", what);
     GM_HIP(hipStreamSynchronize(c.st));
-    std::vector<int32_t> cs;
+    // one entry per output row: the whole-graph column of its source
+    std::vector<int64_t> want((size_t)m, -1);
     for (int64_t r = 0; r < m; ++r)
-        if (h_src[r] >= 0 && h_src[r] < N) cs.push_back(h_src[r]);
-    std::sort(cs.begin(), cs.end());
-    cs.erase(std::unique(cs.begin(), cs.end()), cs.end());
-    // the output rows in the order of their columns
-    std::vector<int32_t> row((size_t)m), col((size_t)m);
-    for (int64_t r = 0; r < m; ++r) row[(size_t)r] = (int32_t)r;
-    auto col_of = [&](int32_t r) { const int32_t x = h_src[r]; return x >= 0 && x < N ? (int32_t)(std::lower_bound(cs.begin(), cs.end(), x) - cs.begin()) : -1; };
-    std::stable_sort(row.begin(), row.end(), [&](int32_t p, int32_t q) { return col_of(p) < col_of(q); });
-    for (int64_t r = 0; r < m; ++r) col[(size_t)r] = col_of(row[(size_t)r]);
-    ppr_scratch sc(c.st);
+        if (h_src[r] >= 0 && h_src[r] < N) want[(size_t)r] = ppr_key(h_src[r], -1);
+    ppr_plan pl;
+    GM_TRY(ppr_plan_of(what, want, &pl));
+    const std::vector<int32_t>& col = pl.col;
+    const std::vector<int32_t> row(pl.order.begin(), pl.order.end());      // (m <= INT32_MAX output rows)
+    gm_scratch sc(c.st);
     int32_t *d_row = nullptr, *d_col = nullptr;
     GM_TRY(sc.put(&d_row, row, sg)); GM_TRY(sc.put(&d_col, col, sg));
     const int64_t v_tiles = (N + GM_PPR_TILE - 1) / GM_PPR_TILE;
-    std::vector<int32_t> cx(cs.size(), -1);
-    return ppr_rounds(what, c, h_ptr, cs, cx, sg, [&](int64_t c0, int32_t Br, const float* P) {
+    return ppr_rounds(what, c, h_ptr, pl.cs, pl.cx, sg, [&](int64_t c0, int32_t Br, const float* P) {
         int64_t lo, hi;
         ppr_span(col, c0, Br, &lo, &hi);
         if (hi == lo) return (int)GM_OK;
@@ -374,7 +361,7 @@ extern "C" int32_t gm_store_pair_pagerank(const gm_store_t* s, int32_t g, const 
     if (!c.B) return GM_OK;
     const int64_t N = c.G.N;
     const bool mask = (flags & GM_PAIR_MASK_TARGET) != 0;
-    ppr_scratch sc(c.st);
+    gm_scratch sc(c.st);
     gm_stager sg(c.st);
     uint8_t* d_adj = nullptr;
     const uint8_t* h_adj = nullptr;
@@ -389,36 +376,26 @@ extern "C" int32_t gm_store_pair_pagerank(const gm_store_t* s, int32_t g, const 
     GM_REQUIRE(h_pairs && h_ptr && (!mask || h_adj), GM_ENOMEM, "%s: pinned staging allocation failed", what);
     GM_HIP(hipStreamSynchronize(c.st));
     // entry 2k: pi of the column (u, x)[v]; entry 2k + 1: pi of the column (v, x')[u]; x, x' = the other endpoint for a masked adjacent pair, else -1
-    auto key = [](int32_t src, int32_t x) { return ((int64_t)src << 32) | (uint32_t)(x + 1); };
-    std::vector<int64_t> want((size_t)(2 * n), -1), keys;
+    std::vector<int64_t> want((size_t)(2 * n), -1);
     std::vector<int32_t> node((size_t)(2 * n), 0);
     for (int64_t k = 0; k < n; ++k) {
         const int32_t p = h_pairs[2 * k], q = h_pairs[2 * k + 1];
         if (p < 0 || p >= N || q < 0 || q >= N) continue;
         const int32_t u = p < q ? p : q, v = p < q ? q : p;
         const bool cut = mask && h_adj[k];
-        want[(size_t)(2 * k)] = key(u, cut ? v : -1); node[(size_t)(2 * k)] = v;
-        want[(size_t)(2 * k + 1)] = key(v, cut ? u : -1); node[(size_t)(2 * k + 1)] = u;
+        want[(size_t)(2 * k)] = ppr_key(u, cut ? v : -1); node[(size_t)(2 * k)] = v;
+        want[(size_t)(2 * k + 1)] = ppr_key(v, cut ? u : -1); node[(size_t)(2 * k + 1)] = u;
     }
-    for (const int64_t w : want)
-        if (w >= 0) keys.push_back(w);
-    std::sort(keys.begin(), keys.end());
-    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-    GM_REQUIRE(keys.size() <= (size_t)INT32_MAX, GM_ERANGE, "%s: %lld distinct columns", what, (long long)keys.size());
-    std::vector<int32_t> cs(keys.size()), cx(keys.size());
-    for (size_t k = 0; k < keys.size(); ++k) { cs[k] = (int32_t)(keys[k] >> 32); cx[k] = (int32_t)(uint32_t)keys[k] - 1; }
-    // the entries in the order of their columns
-    std::vector<int32_t> ecol((size_t)(2 * n));
-    for (size_t e = 0; e < want.size(); ++e) ecol[e] = want[e] < 0 ? -1 : (int32_t)(std::lower_bound(keys.begin(), keys.end(), want[e]) - keys.begin());
-    std::vector<int64_t> dst((size_t)(2 * n));
-    for (size_t e = 0; e < dst.size(); ++e) dst[e] = (int64_t)e;
-    std::stable_sort(dst.begin(), dst.end(), [&](int64_t p, int64_t q) { return ecol[(size_t)p] < ecol[(size_t)q]; });
-    std::vector<int32_t> col((size_t)(2 * n)), nd((size_t)(2 * n));
-    for (size_t e = 0; e < dst.size(); ++e) { col[e] = ecol[(size_t)dst[e]]; nd[e] = node[(size_t)dst[e]]; }
+    ppr_plan pl;
+    GM_TRY(ppr_plan_of(what, want, &pl));
+    const std::vector<int32_t>& col = pl.col;
+    const std::vector<int64_t>& dst = pl.order;
+    std::vector<int32_t> nd((size_t)(2 * n));
+    for (size_t e = 0; e < dst.size(); ++e) nd[e] = node[(size_t)dst[e]];
     int64_t* d_dst = nullptr;
     int32_t *d_node = nullptr, *d_col = nullptr;
     GM_TRY(sc.put(&d_dst, dst, sg)); GM_TRY(sc.put(&d_node, nd, sg)); GM_TRY(sc.put(&d_col, col, sg));
-    return ppr_rounds(what, c, h_ptr, cs, cx, sg, [&](int64_t c0, int32_t Br, const float* P) {
+    return ppr_rounds(what, c, h_ptr, pl.cs, pl.cx, sg, [&](int64_t c0, int32_t Br, const float* P) {
         int64_t lo, hi;
         ppr_span(col, c0, Br, &lo, &hi);
         if (hi == lo) return (int)GM_OK;

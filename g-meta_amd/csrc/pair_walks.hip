@@ -1,12 +1,12 @@
 // Walk counts of node pairs (gm_store_pair_walks: the numbers of walks of length 1, 2 and 3 between the two nodes in the distinct-neighbour graph -- what the
 // local path index and the truncated Katz index are made of).  The DEFINITION is in include/gmeta_hip.h; tests/path_walk_ref.py restates it with Python sets.
-// This file is how it is computed, over the neighbour index of pair_scores.hip (gm_nbr_index):
+// This file is how it is computed, over the neighbour index (nbr_index.hip; gm_nbr.h):
 //   the work    w3(u, v) = sum over z in G(x) of |G(z) & G(t)|, x the endpoint with the shorter row (a tie: the smaller id), t the other: one row intersection
 //               per OUTER entry z.  A leaf pair is a few loads, a pair of hubs tens of thousands of intersections, so the outer row is cut into WORK ITEMS of
 //               at most C entries (gm_set_tuning("walk_chunk")) and no lane group walks more than C of them in a row.
 //   one item    walk_item<L>: a group of L lanes.  L outer entries at a time: every lane loads one z, its row bounds and searches z in G(t) (the w2 term), then
 //               the group takes the L inner rows in turn (bounds by shuffle) -- its lanes stride the SHORTER of G(z) and G(t) and binary-search the longer
-//               (nbr_has, as k_pair_scores does).  Lane partials meet in a butterfly over the group.
+//               (gm_nbr_common, as k_pair_scores does).  Lane partials meet in a butterfly over the group.
 //   light pairs k_pair_walks<L>: one group per pair.  A pair whose outer row holds at most C entries is one item: the group sums it and stores the row
 //               (w1, w2, w3 + mask correction) plainly.  A heavier pair gets its row SEEDED (w1, 0, mask correction: a negative start value) and its index appended
 //               to the call's heavy list through a counter; a second counter adds up the items.
@@ -15,7 +15,7 @@
 //               64-bit integer atomic add per column and item onto the seeded row).  Integer adds commute: list order, item order and arrival order cannot
 //               change a bit of the result.
 // No float arithmetic in this file, no LDS, no scratch memory.  Everything runs on the caller's stream; scratch comes from the stream-ordered pool.
-#include "gm_internal.h"
+#include "gm_nbr.h"
 
 #define GM_WALK_THREADS 256
 #define GM_WALK_COLS 3
@@ -23,50 +23,12 @@
 
 typedef unsigned long long walk_u64;
 
-// one parent graph of a store inside the neighbour index (pair_scores.hip): rows by LOCAL node id, offsets global (into idx), neighbours local
-struct walk_graph {
-    const int64_t* ptr;          // gm_store::d_nbr_ptr + node_off[g]   [N + 1]
-    const int32_t* idx;          // gm_store::d_nbr_idx
-    int64_t N;
-};
-
-// v in the ascending row[0 .. len)  (pair_scores.hip's search, restated: that translation unit keeps it to itself)
-__device__ __forceinline__ bool nbr_has(const int32_t* __restrict__ row, int32_t len, int32_t v) {
-    int32_t lo = 0, hi = len;
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        const int32_t x = row[mid];
-        if (x == v) return true;
-        if (x < v) lo = mid + 1; else hi = mid;
-    }
-    return false;
-}
-
-// a pair as the kernels see it: canonical (u, v), the expanded row X (the shorter; a tie takes the smaller id's) and the target row T
-struct walk_pair {
-    const int32_t* X; const int32_t* T;
-    int32_t dx, dt, u, v, du, dv;
-    bool in;                      // both ids inside the graph
-};
-__device__ __forceinline__ walk_pair walk_pair_of(const walk_graph& G, const int32_t* __restrict__ pairs, int64_t p) {
-    walk_pair w = {nullptr, nullptr, 0, 0, -1, -1, 0, 0, false};
-    const int32_t a = pairs[2 * p], b = pairs[2 * p + 1];
-    w.in = a >= 0 && a < G.N && b >= 0 && b < G.N;
-    if (!w.in) return w;
-    w.u = a < b ? a : b; w.v = a < b ? b : a;
-    const int64_t u0 = G.ptr[w.u], v0 = G.ptr[w.v];
-    w.du = (int32_t)(G.ptr[w.u + 1] - u0); w.dv = (int32_t)(G.ptr[w.v + 1] - v0);
-    const bool u_short = w.du <= w.dv;
-    w.X = G.idx + (u_short ? u0 : v0); w.T = G.idx + (u_short ? v0 : u0);
-    w.dx = u_short ? w.du : w.dv; w.dt = u_short ? w.dv : w.du;
-    return w;
-}
 __device__ __forceinline__ int64_t walk_items_of(int32_t dx, int32_t C) { return ((int64_t)dx + C - 1) / C; }
 
 // The outer entries X[zb .. ze) against the row T, by one group of L lanes (every lane of the group calls it with the same arguments): the lane's share of
 // sum [z in T] (*w2) and of sum |G(z) & T| (*w3).  The loops' bounds are the same in every lane of the group, so the shuffles find their source lanes active.
 template <int L>
-__device__ __forceinline__ void walk_item(const walk_graph& G, const int32_t* __restrict__ X, int64_t zb, int64_t ze, const int32_t* __restrict__ T, int32_t dt, int lane,
+__device__ __forceinline__ void walk_item(const gm_nbr_graph& G, const int32_t* __restrict__ X, int64_t zb, int64_t ze, const int32_t* __restrict__ T, int32_t dt, int lane,
                                           int32_t* w2, int64_t* w3) {
     int32_t c2 = 0; int64_t c3 = 0;
     for (int64_t base = zb; base < ze; base += L) {
@@ -75,21 +37,14 @@ __device__ __forceinline__ void walk_item(const walk_graph& G, const int32_t* __
         if (i < ze) {
             const int32_t z = X[i];
             z0 = G.ptr[z]; dz = (int32_t)(G.ptr[z + 1] - z0);
-            if (nbr_has(T, dt, z)) ++c2;
+            if (gm_nbr_has(T, dt, z)) ++c2;
         }
         const int cnt = (int)(ze - base < L ? ze - base : L);
         for (int k = 0; k < cnt; ++k) {
             const int64_t s0 = __shfl(z0, k, L);
             const int32_t ds = __shfl(dz, k, L);
             const int32_t* __restrict__ Z = G.idx + s0;
-            const bool z_short = ds <= dt;
-            const int32_t* __restrict__ S = z_short ? Z : T;
-            const int32_t* __restrict__ R = z_short ? T : Z;
-            const int32_t ns = z_short ? ds : dt, nr = z_short ? dt : ds;
-            int32_t c = 0;
-            for (int32_t j = lane; j < ns; j += L)
-                if (nbr_has(R, nr, S[j])) ++c;
-            c3 += c;
+            c3 += gm_nbr_common<L>(Z, ds, T, dt, lane, (int32_t)0, [](int32_t c, int32_t) { return c + 1; });
         }
     }
     *w2 = c2; *w3 = c3;
@@ -102,7 +57,7 @@ template <int L> __device__ __forceinline__ void walk_butterfly(int32_t& w2, int
 
 // cnt[0]: heavy pairs so far (slots of `heavy`), cnt[1]: their items.  out rows of every pair: the result (light) or the seed (heavy)
 template <int L>
-__global__ void __launch_bounds__(GM_WALK_THREADS) k_pair_walks(walk_graph G, const int32_t* __restrict__ pairs, int64_t n, int mask, int32_t C, int64_t* __restrict__ out,
+__global__ void __launch_bounds__(GM_WALK_THREADS) k_pair_walks(gm_nbr_graph G, const int32_t* __restrict__ pairs, int64_t n, int mask, int32_t C, int64_t* __restrict__ out,
                                                                  int32_t* __restrict__ heavy, walk_u64* cnt) {
     const int64_t p = ((int64_t)blockIdx.x * GM_WALK_THREADS + threadIdx.x) / L;      // the group's pair: a group is live or idle as a whole
     const int lane = (int)threadIdx.x & (L - 1);
@@ -110,9 +65,9 @@ __global__ void __launch_bounds__(GM_WALK_THREADS) k_pair_walks(walk_graph G, co
     int32_t w1 = 0, w2 = 0; int64_t w3 = 0, corr = 0;
     bool is_heavy = false; int64_t items = 0;
     if (live) {
-        const walk_pair w = walk_pair_of(G, pairs, p);
+        const gm_nbr_pair w = gm_nbr_pair_of(G, pairs, p);
         if (w.in) {
-            const bool adj = w.u != w.v && nbr_has(w.X, w.dx, w.du <= w.dv ? w.v : w.u);      // (v in u's row <=> u in v's row: the rows are symmetric)
+            const bool adj = gm_nbr_adjacent(w);
             if (adj && mask) corr = -((int64_t)w.du + w.dv - 1);                               // the walks of S^3 that use the edge {u, v}
             else w1 = adj ? 1 : 0;
             is_heavy = w.dx > C;
@@ -130,13 +85,13 @@ __global__ void __launch_bounds__(GM_WALK_THREADS) k_pair_walks(walk_graph G, co
 }
 
 // one group per heavy pair: its items (pair, chunk) at a base from cnt[2]
-__global__ void __launch_bounds__(GM_WALK_THREADS) k_walk_expand(walk_graph G, const int32_t* __restrict__ pairs, int32_t C, const int32_t* __restrict__ heavy, int64_t n_heavy,
+__global__ void __launch_bounds__(GM_WALK_THREADS) k_walk_expand(gm_nbr_graph G, const int32_t* __restrict__ pairs, int32_t C, const int32_t* __restrict__ heavy, int64_t n_heavy,
                                                                   int64_t n_items, walk_u64* cnt, int2* __restrict__ item) {
     const int64_t h = ((int64_t)blockIdx.x * GM_WALK_THREADS + threadIdx.x) / GM_WALK_EXPAND_LANES;
     const int lane = (int)threadIdx.x & (GM_WALK_EXPAND_LANES - 1);
     if (h >= n_heavy) return;
     const int32_t p = heavy[h];
-    const walk_pair w = walk_pair_of(G, pairs, p);
+    const gm_nbr_pair w = gm_nbr_pair_of(G, pairs, p);
     const int64_t items = walk_items_of(w.dx, C);
     walk_u64 base = 0;
     if (lane == 0) base = atomicAdd(&cnt[2], (walk_u64)items);
@@ -147,7 +102,7 @@ __global__ void __launch_bounds__(GM_WALK_THREADS) k_walk_expand(walk_graph G, c
 
 // one group per item: the on-chip sum of its outer entries, then one integer atomic add per column onto the pair's seeded row
 template <int L>
-__global__ void __launch_bounds__(GM_WALK_THREADS) k_walk_items(walk_graph G, const int32_t* __restrict__ pairs, int32_t C, const int2* __restrict__ item, int64_t n_items,
+__global__ void __launch_bounds__(GM_WALK_THREADS) k_walk_items(gm_nbr_graph G, const int32_t* __restrict__ pairs, int32_t C, const int2* __restrict__ item, int64_t n_items,
                                                                  int64_t* out) {
     const int64_t it = ((int64_t)blockIdx.x * GM_WALK_THREADS + threadIdx.x) / L;
     const int lane = (int)threadIdx.x & (L - 1);
@@ -156,7 +111,7 @@ __global__ void __launch_bounds__(GM_WALK_THREADS) k_walk_items(walk_graph G, co
     if (live) {
         const int2 e = item[it];
         p = e.x;
-        const walk_pair w = walk_pair_of(G, pairs, p);
+        const gm_nbr_pair w = gm_nbr_pair_of(G, pairs, p);
         const int64_t zb = (int64_t)e.y * C, ze = zb + C < w.dx ? zb + C : w.dx;
         walk_item<L>(G, w.X, zb, ze, w.T, w.dt, lane, &w2, &w3);
     }
@@ -165,14 +120,6 @@ __global__ void __launch_bounds__(GM_WALK_THREADS) k_walk_items(walk_graph G, co
     atomicAdd((walk_u64*)&out[GM_WALK_COLS * p + 1], (walk_u64)(int64_t)w2);
     atomicAdd((walk_u64*)&out[GM_WALK_COLS * p + 2], (walk_u64)w3);
 }
-
-// device scratch of one call: handed back to the pool on the call's stream, whichever way the call ends
-struct walk_scratch {
-    hipStream_t st;
-    void* p[3] = {nullptr, nullptr, nullptr};
-    explicit walk_scratch(hipStream_t s) : st(s) {}
-    ~walk_scratch() { for (void* q : p) gm_dev_free(q, st); }
-};
 
 // Lanes and outer entries per work item.  Measured on preferential-attachment graphs of mean distinct degree 2 to 554, edges + as many negatives
 // (profiles/pair_walks.txt).  A LONG pair list is throughput work: 32 lanes with items of 32 entries are fastest up to a mean distinct degree of 14 (a 16-lane
@@ -189,10 +136,7 @@ static unsigned walk_grid(int64_t groups, int lanes) { return (unsigned)((groups
 
 extern "C" int32_t gm_store_pair_walks(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, int64_t* d_out, void* stream) {
     const char* what = "gm_store_pair_walks";
-    GM_REQUIRE(s, GM_EINVAL, "%s: store is NULL", what);
-    GM_REQUIRE(g >= 0 && g < s->n_graphs, GM_EINVAL, "%s: graph %d of a store with %d graph(s)", what, g, s->n_graphs);
-    GM_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX, GM_EINVAL, "%s: n = %lld", what, (long long)n);
-    GM_REQUIRE((flags & ~GM_PAIR_MASK_TARGET) == 0, GM_EINVAL, "%s: unknown flag bits 0x%x (GM_PAIR_MASK_TARGET = 1)", what, (unsigned)flags);
+    GM_TRY(gm_store_call_check(what, s, g, "n", n, flags));
     const int chunk_knob = gm_knob().walk_chunk, forced = gm_knob().walk_lanes;
     GM_REQUIRE(chunk_knob >= 0, GM_EINVAL, "%s: walk_chunk = %d", what, chunk_knob);
     GM_REQUIRE(forced == 0 || forced == 32 || forced == 64, GM_EINVAL,
@@ -204,14 +148,12 @@ extern "C" int32_t gm_store_pair_walks(const gm_store_t* s, int32_t g, const int
     const int32_t C = chunk_knob > 0 ? chunk_knob : walk_chunk_for(n, L);
     const int mask = flags & GM_PAIR_MASK_TARGET;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t no = s->node_off[g];
-    const walk_graph G = {s->d_nbr_ptr + no, s->d_nbr_idx, s->node_off[g + 1] - no};
+    const gm_nbr_graph G = gm_nbr_graph_of(s, g);
 
-    walk_scratch sc(st);
-    GM_TRY(gm_dev_alloc(&sc.p[0], 3 * sizeof(walk_u64), st));
-    GM_TRY(gm_dev_alloc(&sc.p[1], (size_t)n * sizeof(int32_t), st));
-    walk_u64* cnt = (walk_u64*)sc.p[0];
-    int32_t* heavy = (int32_t*)sc.p[1];
+    gm_scratch sc(st);
+    walk_u64* cnt = nullptr; int32_t* heavy = nullptr; int2* item = nullptr;
+    GM_TRY(sc.take(&cnt, 3));
+    GM_TRY(sc.take(&heavy, (size_t)n));
     GM_HIP(hipMemsetAsync(cnt, 0, 3 * sizeof(walk_u64), st));
     {
         const dim3 grid(walk_grid(n, L)), block(GM_WALK_THREADS);             // n <= 2^31 - 1 pairs of at most 64 lanes: below 2^29 blocks
@@ -226,8 +168,7 @@ extern "C" int32_t gm_store_pair_walks(const gm_store_t* s, int32_t g, const int
     const int64_t n_heavy = (int64_t)h_cnt[0], n_items = (int64_t)h_cnt[1];
     if (n_heavy == 0) return GM_OK;
     GM_REQUIRE(n_items <= (int64_t)INT32_MAX / 2, GM_ERANGE, "%s: %lld work items at walk_chunk = %d; the item launch holds 2^30 at most", what, (long long)n_items, (int)C);
-    GM_TRY(gm_dev_alloc(&sc.p[2], (size_t)n_items * sizeof(int2), st));
-    int2* item = (int2*)sc.p[2];
+    GM_TRY(sc.take(&item, (size_t)n_items));
     hipLaunchKernelGGL(k_walk_expand, dim3(walk_grid(n_heavy, GM_WALK_EXPAND_LANES)), dim3(GM_WALK_THREADS), 0, st, G, d_pairs, C, (const int32_t*)heavy, n_heavy, n_items, cnt, item);
     GM_HIP(hipGetLastError());
     {

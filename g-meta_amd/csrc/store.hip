@@ -139,6 +139,6 @@ extern "C" void gm_store_destroy(gm_store_t* s) {
     gm_dev_free(s->d_node_off, nullptr); gm_dev_free(s->d_in_ptr, nullptr); gm_dev_free(s->d_in_idx, nullptr);
     gm_dev_free(s->d_out_ptr, nullptr); gm_dev_free(s->d_out_idx, nullptr); gm_dev_free(s->d_feat, nullptr); gm_dev_free(s->d_feat_amax, nullptr);
     gm_dev_free(s->d_in_w, nullptr); gm_dev_free(s->d_out_w, nullptr);
-    gm_dev_free(s->d_nbr_ptr, nullptr); gm_dev_free(s->d_nbr_idx, nullptr); gm_dev_free(s->d_nbr_deg, nullptr); gm_dev_free(s->d_nbr_aa, nullptr); gm_dev_free(s->d_nbr_ra, nullptr);      // the pair scores' neighbour index, if a call built it
+    gm_nbr_release(s);      // the neighbour index, if a call built it (nbr_index.hip)
     delete s;
 }

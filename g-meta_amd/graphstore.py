@@ -103,14 +103,28 @@ class GraphStore:
                 return False
         return True
 
-    def _pairs_of(self, g, pairs, what):
+    def _nodes_of(self, g, nodes, what, shape=(-1,)):
+        """(g, the node ids as an int64 array of `shape`) after the graph-range and node-range checks every link-prediction call starts with."""
         g = int(g)
         if not 0 <= g < self.n_graphs:
             raise ValueError('%s: graph %d of a store with %d graph(s)' % (what, g, self.n_graphs))
-        p = np.asarray(pairs, np.int64).reshape(-1, 2)
-        if len(p) and (p.min() < 0 or p.max() >= self.n_nodes[g]):
+        a = np.asarray(nodes, np.int64).reshape(shape)
+        if len(a) and (a.min() < 0 or a.max() >= self.n_nodes[g]):
             raise ValueError('%s: node id outside graph %d (%d nodes)' % (what, g, self.n_nodes[g]))
-        return g, p
+        return g, a
+
+    def _pairs_of(self, g, pairs, what):
+        return self._nodes_of(g, pairs, what, (-1, 2))
+
+    def _pair_call(self, name, g, p, shape, dtype, *tail):
+        """The export `name` over the [m, 2] pairs `p` of graph `g`: the pairs as int32 on the device, the result allocated there as `shape` of `dtype`, the
+        call (store, graph, pairs, m, *tail, result, stream; skipped for m == 0), the result brought back as a numpy array."""
+        import torch
+        out = torch.empty(shape, dtype=dtype, device='cuda')
+        if len(p):
+            d_p = torch.from_numpy(np.ascontiguousarray(p, np.int32)).cuda()
+            _lib.check(getattr(_lib.lib(), name)(self.handle, g, _lib.ptr(d_p), len(p), *tail, _lib.ptr(out), _lib.stream_ptr()), name)
+        return out.cpu().numpy()
 
     def negative_pairs(self, g, n, seed=222, mode='uniform', exclude=None):
         """`n` distinct node pairs (u < v) of graph `g` with no edge between them in either direction, drawn on the device: int64 [n, 2], in the order
@@ -139,12 +153,7 @@ class GraphStore:
         negative sampler's own adjacency test)."""
         import torch
         g, p = self._pairs_of(g, pairs, 'has_edges')
-        if not len(p):
-            return np.zeros(0, bool)
-        d_p = torch.from_numpy(np.ascontiguousarray(p, np.int32)).cuda()
-        out = torch.empty(len(p), dtype=torch.uint8, device='cuda')
-        _lib.check(_lib.lib().gm_store_has_edges(self.handle, g, _lib.ptr(d_p), len(p), _lib.ptr(out), _lib.stream_ptr()), 'gm_store_has_edges')
-        return out.cpu().numpy().astype(bool)
+        return self._pair_call('gm_store_has_edges', g, p, len(p), torch.uint8).astype(bool)
 
     def pair_scores(self, g, pairs, mask_target=False):
         """float32 [m, 5]: the neighbourhood heuristics of the [m, 2] node `pairs` of graph `g`, columns gmeta_amd.PAIR_SCORES = (cn, jaccard, adamic_adar,
@@ -154,12 +163,7 @@ class GraphStore:
         edges of the graph, as with Subgraphs(mask_target=True)."""
         import torch
         g, p = self._pairs_of(g, pairs, 'pair_scores')
-        out = torch.empty((len(p), 5), dtype=torch.float32, device='cuda')
-        if len(p):
-            d_p = torch.from_numpy(np.ascontiguousarray(p, np.int32)).cuda()
-            _lib.check(_lib.lib().gm_store_pair_scores(self.handle, g, _lib.ptr(d_p), len(p), _lib.PAIR_MASK_TARGET if mask_target else 0, _lib.ptr(out),
-                                                       _lib.stream_ptr()), 'gm_store_pair_scores')
-        return out.cpu().numpy()
+        return self._pair_call('gm_store_pair_scores', g, p, (len(p), 5), torch.float32, _lib.PAIR_MASK_TARGET if mask_target else 0)
 
     def pair_walks(self, g, pairs, mask_target=False):
         """int64 [m, 3]: the numbers of walks of length 1, 2 and 3 between the two nodes of each of the [m, 2] `pairs` of graph `g` in the distinct-neighbour
@@ -168,12 +172,7 @@ class GraphStore:
         gmeta_amd.local_path_index / katz_index turn the rows into scores."""
         import torch
         g, p = self._pairs_of(g, pairs, 'pair_walks')
-        out = torch.empty((len(p), 3), dtype=torch.int64, device='cuda')
-        if len(p):
-            d_p = torch.from_numpy(np.ascontiguousarray(p, np.int32)).cuda()
-            _lib.check(_lib.lib().gm_store_pair_walks(self.handle, g, _lib.ptr(d_p), len(p), _lib.PAIR_MASK_TARGET if mask_target else 0, _lib.ptr(out),
-                                                      _lib.stream_ptr()), 'gm_store_pair_walks')
-        return out.cpu().numpy()
+        return self._pair_call('gm_store_pair_walks', g, p, (len(p), 3), torch.int64, _lib.PAIR_MASK_TARGET if mask_target else 0)
 
     @staticmethod
     def _walk_of(alpha, iters, what):
@@ -191,12 +190,7 @@ class GraphStore:
         are allowed."""
         import torch
         alpha, iters = self._walk_of(alpha, iters, 'rooted_pagerank')
-        g = int(g)
-        if not 0 <= g < self.n_graphs:
-            raise ValueError('rooted_pagerank: graph %d of a store with %d graph(s)' % (g, self.n_graphs))
-        a = np.asarray(sources, np.int64).reshape(-1)
-        if len(a) and (a.min() < 0 or a.max() >= self.n_nodes[g]):
-            raise ValueError('rooted_pagerank: node id outside graph %d (%d nodes)' % (g, self.n_nodes[g]))
+        g, a = self._nodes_of(g, sources, 'rooted_pagerank')
         out = torch.empty((len(a), self.n_nodes[g]), dtype=torch.float32, device='cuda')
         if len(a):
             d_a = torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
@@ -211,12 +205,7 @@ class GraphStore:
         import torch
         alpha, iters = self._walk_of(alpha, iters, 'pair_pagerank')
         g, p = self._pairs_of(g, pairs, 'pair_pagerank')
-        out = torch.empty((len(p), 2), dtype=torch.float32, device='cuda')
-        if len(p):
-            d_p = torch.from_numpy(np.ascontiguousarray(p, np.int32)).cuda()
-            _lib.check(_lib.lib().gm_store_pair_pagerank(self.handle, g, _lib.ptr(d_p), len(p), _lib.PAIR_MASK_TARGET if mask_target else 0, alpha, iters,
-                                                         _lib.ptr(out), _lib.stream_ptr()), 'gm_store_pair_pagerank')
-        return out.cpu().numpy()
+        return self._pair_call('gm_store_pair_pagerank', g, p, (len(p), 2), torch.float32, _lib.PAIR_MASK_TARGET if mask_target else 0, alpha, iters)
 
     def neighbour_degrees(self, g):
         """int32 [N]: the number of distinct neighbours (either direction, itself aside) of every node of graph `g` -- the degrees the pair scores use."""
@@ -240,12 +229,7 @@ class GraphStore:
         if not 1 <= k <= 1024:
             raise ValueError('link_candidates: k = %d; 1 .. 1024' % k)
         import torch
-        g = int(g)
-        if not 0 <= g < self.n_graphs:
-            raise ValueError('link_candidates: graph %d of a store with %d graph(s)' % (g, self.n_graphs))
-        a = np.asarray(nodes, np.int64).reshape(-1)
-        if len(a) and (a.min() < 0 or a.max() >= self.n_nodes[g]):
-            raise ValueError('link_candidates: node id outside graph %d (%d nodes)' % (g, self.n_nodes[g]))
+        g, a = self._nodes_of(g, nodes, 'link_candidates')
         m = len(a)
         part = torch.empty((m, k), dtype=torch.int32, device='cuda')
         sc = torch.empty((m, k), dtype=torch.float32, device='cuda')

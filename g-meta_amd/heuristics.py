@@ -32,14 +32,19 @@ def link_auc(scores, labels):
     return float((rank[y == 1].sum() - n_pos * (n_pos + 1) / 2.0) / (float(n_pos) * n_neg))
 
 
-def link_heuristic_scores(store, names, mask_target=False):
-    """float32 [len(names), 5]: GraphStore.pair_scores of the pairs named 'g_i_j', one call per graph, rows in the order of `names`."""
+def _per_graph(store, names, width, dtype, call):
+    """`dtype` [len(names), width]: call(g, pairs) of the pairs named 'g_i_j', one call per graph, rows in the order of `names`."""
     trip = np.asarray([_pair(nm) for nm in names], np.int64).reshape(-1, 3)
-    out = np.zeros((len(trip), len(PAIR_SCORES)), np.float32)
+    out = np.zeros((len(trip), width), dtype)
     for g in np.unique(trip[:, 0]).tolist():
         at = np.nonzero(trip[:, 0] == g)[0]
-        out[at] = store.pair_scores(g, trip[at, 1:], mask_target=mask_target)
+        out[at] = call(g, trip[at, 1:])
     return out
+
+
+def link_heuristic_scores(store, names, mask_target=False):
+    """float32 [len(names), 5]: GraphStore.pair_scores of the pairs named 'g_i_j', one call per graph, rows in the order of `names`."""
+    return _per_graph(store, names, len(PAIR_SCORES), np.float32, lambda g, p: store.pair_scores(g, p, mask_target=mask_target))
 
 
 def link_heuristic_auc(store, names, labels, mask_target=False):
@@ -64,12 +69,7 @@ def katz_index(walks, beta=0.005):
 
 def link_path_scores(store, names, mask_target=False):
     """int64 [len(names), 3]: GraphStore.pair_walks of the pairs named 'g_i_j', one call per graph, rows in the order of `names`."""
-    trip = np.asarray([_pair(nm) for nm in names], np.int64).reshape(-1, 3)
-    out = np.zeros((len(trip), 3), np.int64)
-    for g in np.unique(trip[:, 0]).tolist():
-        at = np.nonzero(trip[:, 0] == g)[0]
-        out[at] = store.pair_walks(g, trip[at, 1:], mask_target=mask_target)
-    return out
+    return _per_graph(store, names, 3, np.int64, lambda g, p: store.pair_walks(g, p, mask_target=mask_target))
 
 
 def link_path_auc(store, names, labels, mask_target=False, eps=0.01, beta=0.005):
@@ -87,12 +87,7 @@ def rooted_pagerank_index(cols):
 
 def link_pagerank_scores(store, names, mask_target=False, alpha=0.15, iters=20):
     """float32 [len(names), 2]: GraphStore.pair_pagerank of the pairs named 'g_i_j', one call per graph, rows in the order of `names`."""
-    trip = np.asarray([_pair(nm) for nm in names], np.int64).reshape(-1, 3)
-    out = np.zeros((len(trip), 2), np.float32)
-    for g in np.unique(trip[:, 0]).tolist():
-        at = np.nonzero(trip[:, 0] == g)[0]
-        out[at] = store.pair_pagerank(g, trip[at, 1:], mask_target=mask_target, alpha=alpha, iters=iters)
-    return out
+    return _per_graph(store, names, 2, np.float32, lambda g, p: store.pair_pagerank(g, p, mask_target=mask_target, alpha=alpha, iters=iters))
 
 
 def link_pagerank_auc(store, names, labels, mask_target=False, alpha=0.15, iters=20):
