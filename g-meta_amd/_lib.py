@@ -42,6 +42,7 @@ PROTOTYPES = {
     'gm_store_pair_walks': (i32, [vp, i32, vp, i64, i32, vp, vp]),
     'gm_store_rooted_pagerank': (i32, [vp, i32, vp, i64, C.c_float, i32, vp, vp]),
     'gm_store_pair_pagerank': (i32, [vp, i32, vp, i64, i32, C.c_float, i32, vp, vp]),
+    'gm_store_pagerank_candidates': (i32, [vp, i32, vp, i64, i32, C.c_float, i32, vp, vp, vp, vp]),
     'gm_store_neighbour_degrees': (i32, [vp, i32, vp, vp]),
     'gm_store_pair_candidates': (i32, [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp]),
     'gm_extract': (C.c_int, [vp, vp, i32, vp, i32, i32, i32, u64, i32, vp, vp]),

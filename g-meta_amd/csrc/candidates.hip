@@ -15,18 +15,16 @@
 //               pair and score tables; keys are unique.  A segment longer than k gets a radix select of the k-th largest key, eight bits a pass from the
 //               top (a 256-bin LDS histogram of integer counts; it stops as soon as the chosen bin is wanted whole), then the survivors (at most 1,024) are
 //               sorted in LDS by a bitonic network and written with the padding.  Which slot a survivor lands in before the sort depends on arrival; the
-//               sorted order of unique keys does not.
+//               sorted order of unique keys does not.  The key, the workgroup scan and the sort with the padding are in gm_internal.h (gm_cand_*): the
+//               PageRank candidates (pagerank_candidates.hip) rank with the same code.
 // Everything runs on the caller's stream; scratch comes from the stream-ordered pool and goes back to it on that stream.  No float arithmetic at all here,
 // no scratch memory in the kernels, integer atomics only where the result cannot depend on their order (bit sets, histogram counts).
 #include "gm_nbr.h"
 #include "gm_devutil.h"      // wld / wst: the bitmap words in LDS (G = false) or in the workgroup's slab of HBM (G = true, agent-scope atomics: L1 is not coherent with the atomics that set the bits)
 
-#define GM_CAND_THREADS 256
-#define GM_CAND_WAVES (GM_CAND_THREADS / GM_WAVE)
 #define GM_CAND_GROUP 8                   // lanes per neighbour row of the walk
 #define GM_CAND_LONG 128                  // rows above this many entries are walked by a whole wave
 #define GM_CAND_LDS_WORDS 8192            // bitmap words in LDS at most: 32 KiB, N <= 262,144
-#define GM_CAND_MAX_K 1024
 #define GM_CAND_COLS 5
 #define GM_CAND_ROUND_DEFAULT (1 << 22)   // pairs per round: 28 bytes of scratch each (the pair and its five scores)
 
@@ -39,22 +37,6 @@ struct cand_graph {
 template <bool G> __device__ __forceinline__ void cw_sync() {
     if (G) __threadfence();
     __syncthreads();
-}
-
-// inclusive prefix of v over the workgroup's threads; *total = the sum.  part: GM_CAND_WAVES ints of LDS; two barriers
-__device__ __forceinline__ int block_scan(int v, int* part, int* total) {
-    const int lane = (int)threadIdx.x & (GM_WAVE - 1), wave = (int)threadIdx.x / GM_WAVE;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < GM_WAVE; o <<= 1) { const int t = __shfl_up(inc, o, GM_WAVE); if (lane >= o) inc += t; }
-    __syncthreads();                                                            // (the previous use of part is over)
-    if (lane == GM_WAVE - 1) part[wave] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < GM_CAND_WAVES; ++w) { const int p = part[w]; tot += p; if (w < wave) base += p; }
-    *total = tot;
-    return base + inc;
 }
 
 // FILL = false: total[r] = |C(nodes[r])|.  FILL = true: pairs[2 (off[r] + j)] = (nodes[r], j-th candidate, ascending).  The bitmap is zero on entry
@@ -117,7 +99,7 @@ k_cand_walk(cand_graph Gr, const int32_t* __restrict__ nodes, int32_t m, uint32_
         int c = 0;
         for (int w = w0; w < w1; ++w) c += __popc(wld<G>(&bm[w]));
         int tot;
-        const int inc = block_scan(c, part, &tot);
+        const int inc = gm_cand_scan(c, part, &tot);
         if (!FILL) {
             if (tid == 0) total[r] = tot;
             for (int w = w0; w < w1; ++w) wst<G>(&bm[w], 0u);
@@ -139,7 +121,7 @@ k_cand_walk(cand_graph Gr, const int32_t* __restrict__ nodes, int32_t m, uint32_
 }
 
 __device__ __forceinline__ unsigned long long cand_key(const int32_t* __restrict__ pairs, const float* __restrict__ scores, int col, int64_t i) {
-    return ((unsigned long long)__float_as_uint(scores[GM_CAND_COLS * i + col]) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)pairs[2 * i + 1]);
+    return gm_cand_key(__float_as_uint(scores[GM_CAND_COLS * i + col]), pairs[2 * i + 1]);
 }
 
 // block r: the segment [off[r], off[r + 1]) of the round's pairs -> row r0 + r of the result
@@ -168,7 +150,7 @@ k_cand_select(const int32_t* __restrict__ pairs, const float* __restrict__ score
             // thread t looks at digit 255 - t: the inclusive prefix counts the keys of this digit and above
             const int h = hist[255 - tid];
             int tot;
-            const int inc = block_scan(h, part, &tot);
+            const int inc = gm_cand_scan(h, part, &tot);
             if (inc - h < kk && kk <= inc) {                                    // exactly one thread: the digit that holds the kk-th largest
                 s_prefix = prefix | ((unsigned long long)(255 - tid) << shift);
                 s_k = kk - (inc - h);
@@ -190,27 +172,7 @@ k_cand_select(const int32_t* __restrict__ pairs, const float* __restrict__ score
     }
     __syncthreads();
     const int cnt = min(s_cnt, GM_CAND_MAX_K);                                  // = min(k, e - b)
-    int S = 1;
-    while (S < cnt) S <<= 1;
-    for (int i = cnt + tid; i < S; i += GM_CAND_THREADS) sk[i] = 0ull;          // below every key: a candidate's score bits are positive
-    __syncthreads();
-    for (int size = 2; size <= S; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < (S >> 1); t += GM_CAND_THREADS) {
-                const int i = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), j = i + stride;
-                const unsigned long long x = sk[i], y = sk[j];
-                const bool desc = (i & size) == 0;
-                if (desc ? x < y : x > y) { sk[i] = y; sk[j] = x; }
-            }
-            __syncthreads();
-        }
-    }
-    const int64_t o = (r0 + blockIdx.x) * (int64_t)k;
-    for (int j = tid; j < k; j += GM_CAND_THREADS) {
-        const unsigned long long key = j < cnt ? sk[j] : 0ull;
-        out_nodes[o + j] = j < cnt ? (int32_t)(0xFFFFFFFFu - (uint32_t)key) : -1;
-        out_scores[o + j] = j < cnt ? __uint_as_float((uint32_t)(key >> 32)) : 0.f;
-    }
+    gm_cand_sort_write(sk, cnt, k, (r0 + blockIdx.x) * (int64_t)k, out_nodes, out_scores);
 }
 
 template <bool FILL>

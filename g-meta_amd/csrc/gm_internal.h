@@ -274,6 +274,60 @@ void gm_nbr_release(const gm_store* s);                                         
 int gm_pair_lanes(const gm_store* s, int32_t g, const char* what, int* lpp);              // GM_EINVAL for a pair_lanes knob that is no instantiation; *lpp (optional; needs the index) = the lanes per pair in force
 int gm_pair_scores_launch(const gm_store* s, int32_t g, int lpp, const int32_t* d_pairs, int64_t n, int mask, float* d_out, hipStream_t st);      // k_pair_scores<lpp> over n pairs of graph g
 
+// ---- the ranking of candidate partners, device side, for the two translation units that select them (candidates.hip: gm_store_pair_candidates;
+// pagerank_candidates.hip: gm_store_pagerank_candidates): the key of include/gmeta_hip.h, the workgroup scan of the radix select, and the sort of the
+// survivors with the padding behind them.  Workgroups of GM_CAND_THREADS threads.
+#define GM_CAND_THREADS 256
+#define GM_CAND_WAVES (GM_CAND_THREADS / GM_WAVE)
+#define GM_CAND_MAX_K 1024
+
+// (uint64(score bits) << 32) | (0xFFFFFFFF - w): descending key = descending score, equal scores by ascending node id
+__device__ __forceinline__ unsigned long long gm_cand_key(uint32_t score_bits, int32_t w) {
+    return ((unsigned long long)score_bits << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)w);
+}
+
+// inclusive prefix of v over the workgroup's threads; *total = the sum.  part: GM_CAND_WAVES ints of LDS; two barriers
+__device__ __forceinline__ int gm_cand_scan(int v, int* part, int* total) {
+    const int lane = (int)threadIdx.x & (GM_WAVE - 1), wave = (int)threadIdx.x / GM_WAVE;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < GM_WAVE; o <<= 1) { const int t = __shfl_up(inc, o, GM_WAVE); if (lane >= o) inc += t; }
+    __syncthreads();                                                            // (the previous use of part is over)
+    if (lane == GM_WAVE - 1) part[wave] = inc;
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < GM_CAND_WAVES; ++w) { const int p = part[w]; tot += p; if (w < wave) base += p; }
+    *total = tot;
+    return base + inc;
+}
+
+// sk[0 .. cnt) in LDS (sk: GM_CAND_MAX_K keys; cnt <= GM_CAND_MAX_K, complete behind a barrier of the caller's): the unique keys of a source's survivors in
+// any order -> the result row at out_*[o .. o + k): the keys descending, -1 / 0.0f behind the last
+__device__ __forceinline__ void gm_cand_sort_write(unsigned long long* sk, int cnt, int k, int64_t o, int32_t* __restrict__ out_nodes, float* __restrict__ out_scores) {
+    const int tid = (int)threadIdx.x;
+    int S = 1;
+    while (S < cnt) S <<= 1;
+    for (int i = cnt + tid; i < S; i += GM_CAND_THREADS) sk[i] = 0ull;          // below every key: a candidate's score bits are positive
+    __syncthreads();
+    for (int size = 2; size <= S; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < (S >> 1); t += GM_CAND_THREADS) {
+                const int i = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), j = i + stride;
+                const unsigned long long x = sk[i], y = sk[j];
+                const bool desc = (i & size) == 0;
+                if (desc ? x < y : x > y) { sk[i] = y; sk[j] = x; }
+            }
+            __syncthreads();
+        }
+    }
+    for (int j = tid; j < k; j += GM_CAND_THREADS) {
+        const unsigned long long key = j < cnt ? sk[j] : 0ull;
+        out_nodes[o + j] = j < cnt ? (int32_t)(0xFFFFFFFFu - (uint32_t)key) : -1;
+        out_scores[o + j] = j < cnt ? __uint_as_float((uint32_t)(key >> 32)) : 0.f;
+    }
+}
+
 // What every store-level link-prediction call checks first: the store, the graph and -- with cnt_name, the count's name in the call's signature -- the count
 // 0 .. INT32_MAX and the flag bits.  (gm_store_has_edges and gm_store_negative_pairs have count bounds of their own and pass no name.)
 static inline int gm_store_call_check(const char* what, const gm_store* s, int32_t g, const char* cnt_name = nullptr, int64_t n = 0, int32_t flags = 0) {
@@ -353,6 +407,20 @@ struct gm_scratch {
         return sg.upload(*d, v);
     }
 };
+
+// ---- the selection of gm_store_pagerank_candidates (pagerank_candidates.hip), run by the export in pair_pagerank.hip on every round of its walk
+struct gm_nbr_graph;
+struct gm_pprc {                         // one call's selection scratch, sized for its widest round
+    int32_t k = 0, wgs_max = 0; hipStream_t st = nullptr;
+    void* cols = nullptr;                // [Bmax] per-column state of the radix select
+    int32_t *hist = nullptr, *cnt = nullptr, *total = nullptr, *ties = nullptr;      // [256, Bmax] bins; [Bmax] survivors; [Bmax] |R|; [ranges, Bmax] threshold entries per row range
+    unsigned long long* surv = nullptr;  // [Bmax, GM_CAND_MAX_K] the survivors' keys
+};
+int gm_pprc_prepare(gm_pprc* w, gm_scratch& sc, int32_t Bmax, int32_t k, hipStream_t st);
+// P[N, Br]: the round's state (overwritten: the exclusions), d_src[Br]: its columns' sources (-1: none); the `rows` output rows d_row[.] take the columns d_col[.] - c0
+// (d_col < 0: a source outside the graph).  tm: the phase laps walk / exclusion / select, the stream synchronised behind each (NULL: none)
+int gm_pprc_round(const gm_pprc& w, const gm_nbr_graph& G, float* P, int32_t Br, const int32_t* d_src, const int32_t* d_row, const int32_t* d_col, int64_t c0, int64_t rows,
+                  int32_t* d_out_nodes, float* d_out_scores, int32_t* d_out_total, gm_phase_timer* tm);
 
 // ---- layout helpers
 struct gm_layout {

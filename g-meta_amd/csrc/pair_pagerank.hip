@@ -13,7 +13,8 @@
 //   hub rows    a row of more than C entries (gm_set_tuning("ppr_chunk")) is cut into segments of C: k_ppr_parts sums each segment into a partial buffer
 //               (a wave per segment and slab), k_ppr_hubs adds the partials in ascending segment order and finishes the row.  Plain vector stores.
 //   results     gm_store_rooted_pagerank: k_ppr_rows_out transposes p[N, B] into the rows of d_out through a 64 x 64 LDS tile (a column serves every duplicate
-//               of its source); gm_store_pair_pagerank: k_ppr_entries_out gathers the two wanted entries of every pair.
+//               of its source); gm_store_pair_pagerank: k_ppr_entries_out gathers the two wanted entries of every pair; gm_store_pagerank_candidates:
+//               the top k of every column, selected on p[N, B] where it lies (gm_pprc_round, pagerank_candidates.hip), so that only [m, k] is written.
 // No float atomics, nothing depends on arrival order: a column's bits are a function of (graph, s, x, alpha, iters, C) alone.  Everything runs on the caller's
 // stream; scratch comes from the stream-ordered pool.
 #include <math.h>
@@ -230,7 +231,8 @@ static void ppr_iterate(const ppr_call& c, const ppr_cols& K, const ppr_hubs& H,
 }
 
 // The walk of the columns (cs[k], cx[k]), ascending, in rounds of at most B: after a round's last iteration emit(c0, Br, P) reads P[N, Br] = p of the
-// columns c0 .. c0 + Br on the call's stream (Br == 0, P == NULL: a call without a single column).  h_ptr: the graph's row pointers on the host.
+// columns c0 .. c0 + Br on the call's stream (Br == 0, P == NULL: a call without a single column); P is the round's scratch, dead behind the emit, which may
+// write to it.  h_ptr: the graph's row pointers on the host.
 template <class Emit>
 static int ppr_rounds(const char* what, const ppr_call& c, const int64_t* h_ptr, std::vector<int32_t> cs, std::vector<int32_t> cx, gm_stager& sg, Emit emit) {
     const gm_nbr_graph& G = c.G;
@@ -265,7 +267,7 @@ static int ppr_rounds(const char* what, const ppr_call& c, const int64_t* h_ptr,
     }
     for (int64_t c0 = 0; c0 == 0 || c0 < ncp; c0 += c.B) {
         const int32_t Br = (int32_t)(ncp - c0 < c.B ? ncp - c0 : c.B);
-        const float* P = nullptr;
+        float* P = nullptr;                                                        // (scratch: an emit may overwrite it)
         if (Br) {
             const ppr_cols K = {d_cs + c0, d_cx + c0, Br};
             bool mask = false;
@@ -403,5 +405,48 @@ extern "C" int32_t gm_store_pair_pagerank(const gm_store_t* s, int32_t g, const 
                            (const int64_t*)d_dst + lo, (const int32_t*)d_node + lo, (const int32_t*)d_col + lo, hi - lo, d_out);
         GM_HIP(hipGetLastError());
         return (int)GM_OK;
+    });
+}
+
+// The top k of every source's row, selected on the round's state while it is in scratch (pagerank_candidates.hip): the rows, columns and rounds are those of
+// gm_store_rooted_pagerank, so the scores are its bits
+extern "C" int32_t gm_store_pagerank_candidates(const gm_store_t* s, int32_t g, const int32_t* d_nodes, int64_t m, int32_t k, float alpha, int32_t iters, int32_t* d_out_nodes,
+                                                float* d_out_scores, int32_t* d_out_total, void* stream) {
+    const char* what = "gm_store_pagerank_candidates";
+    ppr_call c;
+    GM_TRY(ppr_begin(what, "m", s, g, m, 0, alpha, iters, d_nodes, d_out_nodes, stream, &c));
+    GM_REQUIRE(k >= 1 && k <= GM_CAND_MAX_K, GM_EINVAL, "%s: k = %d; 1 .. %d", what, k, GM_CAND_MAX_K);
+    if (!c.B) return GM_OK;
+    GM_REQUIRE(d_out_scores && d_out_total, GM_EINVAL, "%s: NULL argument", what);
+    const int64_t N = c.G.N;                                                // (node ids are int32 in the keys: ppr_rounds holds N below 2^31)
+    gm_phase_timer tm("pagerank candidates");
+    const bool timed = gm_knob().timing != 0;
+    gm_stager sg(c.st);
+    const int32_t* h_src = sg.download(d_nodes, (size_t)m);
+    const int64_t* h_ptr = sg.download(c.G.ptr, (size_t)(N + 1));
+    GM_REQUIRE(h_src && h_ptr, GM_ENOMEM, "%s: pinned staging allocation failed", what);
+    GM_HIP(hipStreamSynchronize(c.st));
+    // one entry per output row: the whole-graph column of its source
+    std::vector<int64_t> want((size_t)m, -1);
+    for (int64_t r = 0; r < m; ++r)
+        if (h_src[r] >= 0 && h_src[r] < N) want[(size_t)r] = ppr_key(h_src[r], -1);
+    ppr_plan pl;
+    GM_TRY(ppr_plan_of(what, want, &pl));
+    const std::vector<int32_t>& col = pl.col;
+    const std::vector<int32_t> row(pl.order.begin(), pl.order.end());      // (m <= INT32_MAX output rows)
+    const int64_t ncp = ((int64_t)pl.cs.size() + GM_WAVE - 1) / GM_WAVE * GM_WAVE;
+    std::vector<int32_t> src(pl.cs);
+    src.resize((size_t)ncp, -1);                                           // (as ppr_rounds pads its columns)
+    gm_scratch sc(c.st);
+    int32_t *d_row = nullptr, *d_col = nullptr, *d_src = nullptr;
+    GM_TRY(sc.put(&d_row, row, sg)); GM_TRY(sc.put(&d_col, col, sg)); GM_TRY(sc.put(&d_src, src, sg));
+    gm_pprc sel;
+    GM_TRY(gm_pprc_prepare(&sel, sc, (int32_t)(ncp < c.B ? ncp : c.B), k, c.st));
+    if (timed) { GM_HIP(hipStreamSynchronize(c.st)); tm.lap("plan"); }
+    return ppr_rounds(what, c, h_ptr, pl.cs, pl.cx, sg, [&](int64_t c0, int32_t Br, float* P) {
+        int64_t lo, hi;
+        ppr_span(col, c0, Br, &lo, &hi);
+        return gm_pprc_round(sel, c.G, P, Br, (const int32_t*)d_src + c0, (const int32_t*)d_row + lo, (const int32_t*)d_col + lo, c0, hi - lo, d_out_nodes, d_out_scores,
+                             d_out_total, timed ? &tm : nullptr);
     });
 }

@@ -240,6 +240,29 @@ class GraphStore:
                                                            _lib.stream_ptr()), 'gm_store_pair_candidates')
         return part.cpu().numpy().astype(np.int64), sc.cpu().numpy(), tot.cpu().numpy().astype(np.int64)
 
+    def pagerank_candidates(self, g, nodes, k=10, alpha=0.15, iters=20):
+        """Candidate partners of the `nodes` of graph `g` by the global score: per node the non-adjacent nodes with positive rooted-PageRank mass seen from
+        it (rooted_pagerank's row, bit for bit; the node itself and its neighbours aside), ranked descending, equal scores by ascending node id, the best `k`
+        (1..1024) kept -- walked and selected on the device, so that only [m, k] comes back (gm_store_pagerank_candidates; the definition is in
+        include/gmeta_hip.h, tests/pagerank_candidate_ref.py restates it).  Unlike link_candidates it reaches every node within `iters` steps.
+        -> (partners int64 [m, k], scores float32 [m, k], totals int64 [m]), laid out as link_candidates lays them out: gmeta_amd.candidate_names takes the
+        partners.  The score is one-directional; pair_pagerank rescores a shortlist symmetrically."""
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError('pagerank_candidates: k = %d; 1 .. 1024' % k)
+        alpha, iters = self._walk_of(alpha, iters, 'pagerank_candidates')
+        import torch
+        g, a = self._nodes_of(g, nodes, 'pagerank_candidates')
+        m = len(a)
+        part = torch.empty((m, k), dtype=torch.int32, device='cuda')
+        sc = torch.empty((m, k), dtype=torch.float32, device='cuda')
+        tot = torch.empty(m, dtype=torch.int32, device='cuda')
+        if m:
+            d_a = torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
+            _lib.check(_lib.lib().gm_store_pagerank_candidates(self.handle, g, _lib.ptr(d_a), m, k, alpha, iters, _lib.ptr(part), _lib.ptr(sc), _lib.ptr(tot),
+                                                               _lib.stream_ptr()), 'gm_store_pagerank_candidates')
+        return part.cpu().numpy().astype(np.int64), sc.cpu().numpy(), tot.cpu().numpy().astype(np.int64)
+
     def close(self):
         if getattr(self, 'handle', None):
             _lib.lib().gm_store_destroy(self.handle)

@@ -97,7 +97,7 @@ def link_pagerank_auc(store, names, labels, mask_target=False, alpha=0.15, iters
 
 
 def candidate_names(g, nodes, partners):
-    """The partners GraphStore.link_candidates found for the `nodes` of graph `g`, as pair names: one list of 'g_a_w' per node, in ranking order, the -1
+    """The partners GraphStore.link_candidates (or pagerank_candidates) found for the `nodes` of graph `g`, as pair names: one list of 'g_a_w' per node, in ranking order, the -1
     padding skipped -- the shape Subgraphs.query_batch takes (one set per source), whose batch Adapted.predict scores."""
     a = np.asarray(nodes, np.int64).reshape(-1)
     p = np.asarray(partners, np.int64)

@@ -250,6 +250,30 @@ int32_t gm_store_rooted_pagerank(const gm_store_t* s, int32_t g, const int32_t* 
 int32_t gm_store_pair_pagerank(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, float alpha, int32_t iters, float* d_out,
                                void* stream);
 
+/* ---- CANDIDATE PARTNERS BY ROOTED PAGERANK (beyond the reference): for m source nodes of one parent graph the k non-adjacent nodes that hold the most
+ * rooted-PageRank mass seen from the source -- the global generator beside gm_store_pair_candidates, selected on the device from the walk's state while it is
+ * still in scratch: only [m, k] leaves it.  This comment is THE definition; tests/pagerank_candidate_ref.py restates it.  Per parent graph g with N nodes:
+ *   neighbourhood  G(x), deg and the walk are those of gm_store_rooted_pagerank.
+ *   score          of w for the source a: pi_(a,-1)[w], the entry of gm_store_rooted_pagerank's row for a, BITWISE, under the ppr_chunk in force.  The score is
+ *                  one-directional; the symmetric pi_a(w) + pi_w(a) would need a column per candidate: a caller who wants it rescores the shortlist with
+ *                  gm_store_pair_pagerank.
+ *   candidate set  R(a) = { w : w != a, w not in G(a), pi_(a,-1)[w] > 0 }, decided on the fp32 bits: an entry that underflowed to zero is no candidate.
+ *                  Unlike C(a) of gm_store_pair_candidates, R(a) reaches every node within `iters` steps of a.  An isolated source and a source outside
+ *                  [0, N) have R = {}.
+ *   ranking        descending score, among equal fp32 scores ascending node id w: the descending order of the integer key
+ *                  (uint64(score bits) << 32) | (0xFFFFFFFF - w), the key of gm_store_pair_candidates.  Selection is integer work and the result is unique.
+ *   result         for k in 1..1024: d_out_nodes device int32 [m, k], d_out_scores device fp32 [m, k], d_out_total device int32 [m] = |R(a)|.  Row r holds
+ *                  the first min(k, total[r]) candidates of the ranking, in ranking order, then -1 in d_out_nodes and 0.0f in d_out_scores.  Nothing beyond
+ *                  row m - 1 is written.  Duplicate sources are allowed and give identical rows.
+ *   exactness      a row is a function of (graph, its own source, k, alpha, iters, ppr_chunk) alone: not of the other rows, of ppr_cols, of the stream or
+ *                  of arrival order.  No float atomics; integer atomics only where their order cannot change the result (histogram counts, list slots
+ *                  ahead of a sort of unique keys).
+ * The call reads the neighbour index, runs on `stream`, takes its scratch -- the walk's, a 256-bin histogram and at most 1,024 keys per column of a round --
+ * from the stream-ordered pool, reads the sources (and the graph's row lengths) back once, and is complete in stream order.  m == 0 is a no-op.
+ * GM_EINVAL (the message names the value): as gm_store_rooted_pagerank, and k outside 1..1024. */
+int32_t gm_store_pagerank_candidates(const gm_store_t* s, int32_t g, const int32_t* d_nodes, int64_t m, int32_t k, float alpha, int32_t iters,
+                                     int32_t* d_out_nodes, float* d_out_scores, int32_t* d_out_total, void* stream);
+
 /* ---- Extraction: replaces Subgraphs.generate_subgraph / generate_subgraph_link_pred
  * (sdp.py:295-346: h-hop in-neighbour expansion, node sampling, G.subgraph) and dgl.batch
  * (sdp.py:399-406) for n_sets sets at once.  seeds/set_offsets are host arrays; set s owns seeds
