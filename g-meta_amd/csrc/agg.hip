@@ -29,7 +29,7 @@ struct AggK {
     const float* e_w; const int32_t* x_idx;     // per-edge source scale / source row of x (see gm_agg_args)
     int skip_lo, skip_hi;                       // rows with skip_lo <= degree <= skip_hi are left to the fused aggregate+GEMM kernel (empty range: none)
     const int32_t* rowlist; int64_t n_list;     // optional: the windows walk this (ascending) row list instead of rows 0 .. rows
-    int keep_signed;                            // s_out's sign bit = nobody reads this row of `out`: computed, not stored; the scale is the magnitude.  Never read without the flag
+    int keep_signed;                            // s_out's sign bit = nobody reads this row of `out`: not stored (and without relu_bits not computed either: agg_unobservable); the scale is the magnitude.  Never read without the flag
 };
 // XCD-aware block mapping: hardware block b runs on XCD b % 8; each XCD gets a contiguous range of the nb logical blocks, so that one
 // subgraph's rows (and their gathers) stay in one L2.  First logical block of XCD x (x = GM_NXCD: nb) / logical block of hardware block b
@@ -43,6 +43,12 @@ __device__ __forceinline__ int agg_logical_block(const int nb, const int b) { re
 __device__ __forceinline__ float agg_out_scale(const AggK& a, const float raw, bool& keep) {
     keep = !(a.keep_signed && (__float_as_uint(raw) >> 31));
     return a.keep_signed ? fabsf(raw) : raw;
+}
+// ... and whether anything of the row can be observed in this launch: a row that is not stored is still owed its relu' bits where the launch writes them
+// (tests/test_hip_agg_numerics.py); where it writes none, nothing the row computes has a reader, and it issues no edge-table load, no gather and no mask
+// load and skips its epilogue.  One predicate for the windows (descriptor phase and row loop), the hub rows and k_agg; never true without keep_signed
+__device__ __forceinline__ bool agg_unobservable(const AggK& a, const float raw) {
+    return a.keep_signed && !a.relu_bits && (__float_as_uint(raw) >> 31);
 }
 // set of a row: which bias row it takes (few sets: short binary search)
 __device__ __forceinline__ int agg_bias_set(const AggK& a, const int64_t row) {
@@ -86,7 +92,9 @@ __global__ __launch_bounds__(AGG_BLOCK) void k_agg(AggK a) {
     if (row >= a.rows) return;
     const int e0 = a.indptr[row], e1 = a.indptr[row + 1];
     bool keep;
-    const float so = agg_out_scale(a, a.s_out ? a.s_out[row] : 1.f, keep);
+    const float raw = a.s_out ? a.s_out[row] : 1.f;
+    if (agg_unobservable(a, raw)) return;
+    const float so = agg_out_scale(a, raw, keep);
     const int set = agg_bias_set(a, row);
     for (int c0 = l * VEC; c0 < a.width; c0 += LPR * VEC) {
         V acc0, acc1; vzero(acc0); vzero(acc1);
@@ -195,6 +203,11 @@ __device__ __forceinline__ void agg_heavy_row(const AggK& a, const int g, float*
     int h = g, p = 0, P = 1;
     if (a.hub) { h = a.hub[a.n_heavy + 1 + g]; p = g - a.hub[h]; P = a.hub[h + 1] - a.hub[h]; }
     const int row = a.heavy[h];
+    // A hub row nobody can observe leaves here, ahead of every gather and every barrier.  The exit depends on the row alone, so the P parts of a split row all
+    // take it: none publishes a partial row and none takes a ticket, and the row's arrival counter stays at the 0 its last full round of P arrivals put back
+    // (agg_hub_arrive) -- as a launch that keeps the row expects to find it.  A counter only ever sees all P arrivals of a launch or none.
+    const float so = a.s_out ? a.s_out[row] : 1.f;
+    if (agg_unobservable(a, so)) return;
     int e0 = a.indptr[row], e1 = a.indptr[row + 1];
     if (P > 1) { e0 += p * a.hub_part; if (p < P - 1) e1 = e0 + a.hub_part; }      // the last part takes the remainder (up to 1.5 parts)
     const float* xl = a.x + l * 4;
@@ -236,7 +249,7 @@ __device__ __forceinline__ void agg_heavy_row(const AggK& a, const int g, float*
             }
         }
     }
-    if (gi == 0) agg_store_row<LPR, NCH>(a, row, a.s_out ? a.s_out[row] : 1.f, l, s4, false);      // (hub rows: plain stores)
+    if (gi == 0) agg_store_row<LPR, NCH>(a, row, so, l, s4, false);      // (hub rows: plain stores)
 }
 template <int LPR, int NCH>
 __global__ __launch_bounds__(AGG_HEAVY_BLOCK) void k_agg_heavy(AggK a) {
@@ -284,12 +297,19 @@ __global__ __launch_bounds__(AGG_BLOCK) void k_agg_win(AggK a) {
         p0 = a.indptr[myrow]; dg = a.indptr[myrow + 1] - p0;
         if (a.s_out) so = a.s_out[myrow];
         if (dg >= a.skip_lo && dg <= a.skip_hi) dg = -2;                   // not this launch's row
+        // ... and neither is a row nobody can observe: no edge-table load here (the dependent load behind indptr), and the row loop passes over it like a
+        // skipped row -- the broadcasts below stay where the wave is convergent, the lane groups of a side-by-side set diverge only behind them
+        if (agg_unobservable(a, so)) dg = -2;
         if (dg >= 1) agg_edge(a, p0, u0, w0);
         if (dg >= 2) agg_edge(a, p0 + 1, u1, w1);
     }
     const int nwin = (int)min((int64_t)a.win, nrows_w - R0);
     const float* xl = a.x + l * 4;
+    // the window's rows that are this launch's, one bit per row (the same in every lane): a step of the loop whose G * UNR rows are all passed over
+    // broadcasts nothing -- the whole wave leaves it together, ahead of the shuffles
+    const unsigned long long live = __ballot(mine && dg >= 0);
     for (int t0 = 0; t0 < nwin; t0 += G * UNR) {
+        if (!((live >> t0) & ((1ull << (G * UNR)) - 1))) continue;
         float4 acc[UNR][NCH];
         int rdg[UNR], rp0[UNR], rrow[UNR]; float rso[UNR];
 #pragma unroll

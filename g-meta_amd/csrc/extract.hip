@@ -780,6 +780,30 @@ int64_t gm_batch_e1_rows(const gm_batch* b, hipStream_t s) {
     if (hipMemcpyAsync(&h, b->d_n_e1_rows, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return fallback; }
     return b->n_e1_rows = h;
 }
+// by-source edges of the rows d_norm_e1 keeps (what the keep_signed aggregate walks): counted at first use, like gm_batch_unfused_sources
+__global__ void k_e1_kept_edges(const int32_t* indptr_t, const float* norm_e1, int64_t rows, unsigned long long* out) {
+    unsigned long long c = 0;
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x)
+        if (!(__float_as_uint(norm_e1[r]) >> 31)) c += (unsigned long long)(indptr_t[r + 1] - indptr_t[r]);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) c += __shfl_down(c, off, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
+}
+int64_t gm_batch_e1_edges(const gm_batch* b, hipStream_t s) {
+    if (b->n_e1_edges >= 0) return b->n_e1_edges;
+    const int64_t fallback = b->edges;
+    if (!b->d_norm_e1 || !b->d_indptr_t || b->rows <= 0) return fallback;
+    unsigned long long* cnt = nullptr; unsigned long long h = 0;
+    if (gm_alloc(&cnt, 1, s) != GM_OK) return fallback;
+    bool ok = hipMemsetAsync(cnt, 0, 8, s) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_e1_kept_edges, dim3((int)std::min<int64_t>(512, (b->rows + 255) / 256)), dim3(256), 0, s, b->d_indptr_t, b->d_norm_e1, (int64_t)b->rows, cnt);
+        ok = hipMemcpyAsync(&h, cnt, 8, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    }
+    if (!ok) (void)hipGetLastError();
+    gm_dev_free(cnt, s);
+    return ok ? (b->n_e1_edges = (int64_t)h) : fallback;
+}
 __global__ void k_copy_add(int32_t* dst, const int32_t* src, int64_t n, int32_t add) {
     for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) dst[k] = src[k] + add;
 }

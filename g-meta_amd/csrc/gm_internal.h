@@ -205,6 +205,7 @@ struct gm_batch {
                                        //        launch, gm_wgrad_args::g_keep of the weight gradient below it)
     int32_t* d_n_e1_rows = nullptr;    // [1]    rows with the bit clear, counted on the device (gm_batch_e1_rows reads it at first use)
     mutable int64_t n_e1_rows = -1;
+    mutable int64_t n_e1_edges = -1;   //        by-source edges of those rows (profiling only: counted on first use, gm_batch_e1_edges)
     float* d_e1_norm = nullptr;        // [n_e1] norm[source row]
     float* d_e1_coef = nullptr;        // [n_e1] weighted batches only: edge weight x norm[source row] (the transposed aggregate's coefficient; d_e1_norm stays the row scale)
     int32_t* d_c_tiles = nullptr; int32_t n_c_tiles = 0;          // GEMM tiles over centre rows (per set)
@@ -454,7 +455,7 @@ struct gm_agg_args {
     int64_t ldx;
     const float* s_in;         // optional per-source scale
     const float* s_out;        // optional per-destination scale
-    int keep_signed;           // s_out carries "nobody reads this row of `out`" in its sign bit (gm_batch::d_norm_e1): the scale is the magnitude, a flagged row is computed and not stored
+    int keep_signed;           // s_out carries "nobody reads this row of `out`" in its sign bit (gm_batch::d_norm_e1): the scale is the magnitude, a flagged row is not stored -- computed only where the launch writes relu_bits, left at its descriptor otherwise
     const float* mask_h;       // optional [rows, width]: zero the output where mask_h <= 0 (relu')
     const uint8_t* mask_b;     // same mask, packed: byte (row*width + col)/4 holds the relu' bits of 4 consecutive columns
     uint8_t* relu_bits;        // optional output: packed relu' bits of `out` (written with relu; width % 4 == 0)
@@ -684,6 +685,8 @@ bool gm_prof_enabled();
 int64_t gm_batch_unfused_sources(const gm_batch* b, hipStream_t s);
 // distinct source rows of the centres' in-edges (the rows gm_batch::d_norm_e1 keeps): read back at first use (synchronises the stream) -- the launch accounting and the tests ask for it
 int64_t gm_batch_e1_rows(const gm_batch* b, hipStream_t s);
+// by-source edges of those rows: counted on the device at first use (synchronises the stream) -- only the launch accounting asks for it; gm_batch::edges where it cannot be had
+int64_t gm_batch_e1_edges(const gm_batch* b, hipStream_t s);
 void gm_prof_note(int cat, int64_t work);      // adds work to a category without timing events
 static inline void gm_prof_agg_begin(hipStream_t s, int64_t bytes) { gm_prof_begin(GM_PROF_AGG, s, bytes); }
 static inline void gm_prof_agg_end(hipStream_t s) { gm_prof_end(GM_PROF_AGG, s); }

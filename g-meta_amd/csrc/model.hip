@@ -1155,15 +1155,16 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
                 int64_t by = gm_aggregate_bytes(b, fi);
                 if (t_centre && l == Lg - 1) {
                     a.x_idx = b->d_ect;
-                    int64_t n_out = b->rows;
+                    int64_t n_out = b->rows, e_out = b->edges;      // the rows the launch works on (every other row leaves behind its descriptor), and their edges
                     if (dq_e1) {
                         a.s_out = b->d_norm_e1; a.keep_signed = 1;
-                        // (the exact count when the launch accounting is on: read back once per batch; its bound otherwise -- nobody reads it then)
+                        // (the exact counts when the launch accounting is on: read back / counted once per batch; their bounds otherwise -- nobody reads them then)
                         n_out = gm_prof_enabled() ? gm_batch_e1_rows(b, st) : std::min<int64_t>(b->n_e1, b->rows);
+                        e_out = gm_prof_enabled() ? gm_batch_e1_edges(b, st) : b->edges;
                     }
-                    // SURVEY 8(d)'s B_agg on what this launch touches: every indptr entry, the edge table, the row scales, the relu' bits of every row,
-                    // T_L's centre rows read once, the rows it stores written once
-                    by = 4 * (b->rows + 1) + 4 * b->edges + 4 * b->rows + (maskbits ? b->rows * (int64_t)fi / 4 : 0) + 4 * ((int64_t)b->n_c + n_out) * (int64_t)fi;
+                    // SURVEY 8(d)'s B_agg on what this launch touches: every indptr entry and every row scale; of the rows it works on the edge-table entries
+                    // and the relu' bits; T_L's centre rows read once, the rows it stores written once
+                    by = 4 * (b->rows + 1) + 4 * b->rows + 4 * e_out + (maskbits ? n_out * (int64_t)fi / 4 : 0) + 4 * ((int64_t)b->n_c + n_out) * (int64_t)fi;
                 }
                 GM_TRY(launch_agg(a, by, by, st));
             }

@@ -467,7 +467,8 @@ int gm_dense_gemm(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, c
  *   CSR only); 3 X = x read through GM_F_EDGE_CENTRE_T (transposed only; x holds rows + 1 rows, the last one zero).  1 and 2 need width == the feature width.
  * scale_src: 0 w_e = 1 (weighted batches: the edge's weight); 1 w_e = s_in[src_e], gathered per source (refused on weighted batches, as gm_aggregate does);
  *   2 w_e from the batch's per-edge table of GM_F_NORM[src_e] (weighted batches: weight x norm).  s_in is given with scale_src == 1 only.
- * s_out (or NULL): row scale; keep_signed: its sign bit marks rows that are computed and not stored, the scale is the magnitude.  bias_t = bias + t * bias_stride
+ * s_out (or NULL): row scale; keep_signed: its sign bit marks rows that are not stored (computed where relu_bits are written -- the bits of every row are --,
+ *   left alone otherwise), the scale is the magnitude.  bias_t = bias + t * bias_stride
  *   (stride 0: one bias for every set) or NULL;  relu: max(v, 0), NaN kept;  relu_bits (or NULL, with relu): packed relu' bits of the stored value, byte
  *   (v * width + c) / 4, bit c % 4;  mask_h [rows, width] (or NULL): zero where mask_h <= 0;  mask_b (or NULL): the same as packed bits.
  * hubs: 0 no hub handling (every row by the row kernels); 1 the batch's hub-row list without a schedule (a separate hub launch); 2 its block schedule and hub parts.
@@ -500,7 +501,8 @@ int gm_dense_wgrad_centre(const gm_batch_t* b, const float* x, int32_t Kx, const
 /* One level down (GM_DEAD_ROWS=2), exported for tests: the last layer's transposed aggregate  out[u, :] = mask[u, :] ? norm[u] * sum over the out-edges
  * (u -> v) of w_uv T[v, :] : 0  as the dense backward launches it.  keep != 0: T is read through GM_F_EDGE_CENTRE_T -- its centre rows and one zero row
  * behind it (T holds rows + 1 rows of `width` floats; the call zeroes the last one, the others outside the centre rows may hold anything) -- and only the
- * rows GM_F_NORM_E1 keeps are stored, the other rows of `out` are left untouched; keep == 0: the plain launch over every row of T.  mask_b: packed relu'
+ * rows GM_F_NORM_E1 keeps are worked on and stored: a row it flags has no reader in this launch and stops at its descriptor (no edge-table entry, no row
+ * of T and no mask byte is loaded for it), its row of `out` is left untouched; keep == 0: the plain launch over every row of T.  mask_b: packed relu'
  * bits, byte (row * width + col) / 4, or NULL.  gm_dense_wgrad_e1 is gm_dense_wgrad_centre with GM_F_NORM_E1 as the flag. */
 int gm_dense_agg_centre_t(const gm_batch_t* b, float* T, int32_t width, const uint8_t* mask_b, float* out, int32_t keep, void* stream);
 int gm_dense_wgrad_e1(const gm_batch_t* b, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
