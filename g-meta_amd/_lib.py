@@ -82,6 +82,8 @@ PROTOTYPES = {
     'gm_dense_wgrad': (C.c_int, [vp, vp, i64, i32, vp, i64, i32, vp, vp, i64, vp, i64, vp, i64, i32, vp, vp, i64, C.c_float, vp, vp, vp, vp]),
     'gm_proto_loss_spt': (C.c_int, [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     'gm_proto_loss_qry': (C.c_int, [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+    'gm_dense_head_loss': (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i64, i64, i64, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp, vp,
+                                     vp, vp, i64, C.c_float, vp, i32, vp, vp]),
     'gm_set_ragged_classes': (None, [i32]),
     'gm_get_ragged_classes': (i32, []),
     'gm_set_readout': (None, [i32]),

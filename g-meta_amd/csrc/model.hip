@@ -827,6 +827,12 @@ extern "C" int64_t gm_gcn_ws_bytes(const gm_batch_t* b, const gm_model_t* m) {
     return cv.used + 256;
 }
 
+// > 0: every set of the batch holds this many subgraphs (HeadK::subs_per_set)
+static int head_subs_per_set(const gm_batch* b) {
+    int n = b->sets > 0 ? b->subs / b->sets : 0;
+    for (int t = 0; t <= b->sets && n; ++t) if (b->h_set_sub_off[t] != t * n) n = 0;
+    return n;
+}
 static HeadK make_head(const GcnCtx& c, const float* params, int64_t pstride) {
     const gm_layout& L = c.L; const gm_batch* b = c.b;
     HeadK k{};
@@ -836,8 +842,7 @@ static HeadK make_head(const GcnCtx& c, const float* params, int64_t pstride) {
     k.hc = L.hc; k.C = L.n_out; k.subs = b->subs; k.compact = c.cone ? 1 : 0;
     if (mean_readout(c)) { k.H = c.Pool; k.compact = 1; k.nc = 1; }      // the pooled rows, one per subgraph (pairs too): hc = Hd
     k.dq_amax = (c.np == 2 && c.am_pass >= 0) ? c.amdQ() : nullptr;
-    k.subs_per_set = b->sets > 0 ? b->subs / b->sets : 0;
-    for (int t = 0; t <= b->sets && k.subs_per_set; ++t) if (b->h_set_sub_off[t] != t * k.subs_per_set) k.subs_per_set = 0;
+    k.subs_per_set = head_subs_per_set(b);
     return k;
 }
 static int launch_head_fwd(const GcnCtx& c, const float* params, int64_t pstride, float* logits, hipStream_t st) {
@@ -1537,12 +1542,15 @@ static unsigned long long* const g_head_dbg = nullptr;      // the product libra
 // One k_head_loss launch: everything but the instantiation
 struct HeadLossLaunch {
     int sets; size_t lds; HeadK hk; float* logits; ProtoK pk; int bwd; float* dparams; int64_t dstride; float* dQ; float* Gc; SgdK sg; int stage_h, proto_floats;
+    int copy_out;             // 1 (gm_dense_head_loss only): a staged launch also writes its logits / dlogits to the global arrays
+    int32_t* launched;        // tests, or NULL: receives {workgroup size, staged, ragged instantiation} of the kernel that was launched
 };
 template <int NT, bool RGK>
 static int launch_head_loss_t(const HeadLossLaunch& a, hipStream_t st, bool again = false) {      // again: the probe's repeat of a launch just made -- the launch alone
     const auto k_head_loss_nt = k_head_loss<NT, RGK>;
     if (!again) GM_TRY(gm_func_full_lds((const void*)k_head_loss_nt));
-    hipLaunchKernelGGL(k_head_loss_nt, dim3(a.sets), dim3(NT), a.lds, st, a.hk, a.logits, a.pk, a.bwd, a.dparams, a.dstride, a.dQ, a.Gc, a.sg, a.stage_h, a.proto_floats, 0, g_head_dbg);
+    hipLaunchKernelGGL(k_head_loss_nt, dim3(a.sets), dim3(NT), a.lds, st, a.hk, a.logits, a.pk, a.bwd, a.dparams, a.dstride, a.dQ, a.Gc, a.sg, a.stage_h, a.proto_floats, a.copy_out, g_head_dbg);
+    if (a.launched) { a.launched[0] = NT; a.launched[1] = a.stage_h; a.launched[2] = RGK ? 1 : 0; }
     return GM_OK;
 }
 template <bool RGK>
@@ -1550,6 +1558,35 @@ static int launch_head_loss(int nt, const HeadLossLaunch& a, hipStream_t st) {
     return nt == 256 ? launch_head_loss_t<256, RGK>(a, st) : nt == 512 ? launch_head_loss_t<512, RGK>(a, st) : launch_head_loss_t<1024, RGK>(a, st);
 }
 static int launch_head_loss_ragged(int nt, const HeadLossLaunch& a, hipStream_t st);
+// The k_head_loss launch of a head (hk) and a loss (pk): the LDS of a set, staged or not, the workgroup size, the launcher.  Everything is decided from the launch's own
+// arguments, so that gm_dense_head_loss (tests) runs these very decisions.  copy_out / launched: see HeadLossLaunch.
+static int head_loss_launch(const gm_batch* b, const HeadK& hk, float* logits, const ProtoK& pk, int bwd, float* dparams, int64_t dstride, float* dQ, float* Gc,
+                            const SgdK& sg, bool ragged, int copy_out, int32_t* launched, hipStream_t st) {
+    const size_t proto_bytes = (proto_lds(pk.Ct, pk.n, pk.D, HL_THREADS) + 15) / 16 * 16;
+    int max_subs = 0;
+    for (int t = 0; t < b->sets; ++t) max_subs = std::max(max_subs, b->h_set_sub_off[t + 1] - b->h_set_sub_off[t]);
+    const size_t hs_bytes = sizeof(float) * ((size_t)max_subs * hk.nc * hk.Hd + (size_t)hk.C * (hk.hc + 1) + 2 * (size_t)max_subs * hk.C +
+                                             (size_t)max_subs * hk.nc + (size_t)pk.Ct * pk.n + (ragged ? (size_t)pk.Ct + 1 : 0)) + 16;      // + the centre-row scratch + the class rows (a ragged set's follow its class starts)
+    const int stage_on = gm_knob().head_stage;
+    const int stage_h = stage_on && proto_bytes + hs_bytes <= 150 * 1024;
+    const size_t lds = proto_bytes + (stage_h ? hs_bytes : 0);
+    // Workgroup size (GM_HEAD_THREADS, default 1024): one workgroup per task.  Measured: 256 threads -- which could start on a CU that a persistent
+    // GEMM workgroup of the other stream fills -- lose more inside the kernel than they gain at its start (FirstMM shape 1.62 -> 1.89 ms per
+    // meta-step, 4-task arxiv shard 4.59 -> 4.86; 512: 1.71 / 4.67).
+    int nt = gm_knob().head_threads;
+    if (nt != 256 && nt != 512) nt = 1024;
+    const HeadLossLaunch hl{b->sets, lds, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, bwd ? sg : SgdK{nullptr, 0, nullptr, 0, 0.f}, stage_h, (int)(proto_bytes / sizeof(float)),
+                            copy_out, launched};
+    if (!ragged) GM_TRY(launch_head_loss<false>(nt, hl, st));      // (first: the kernels every launch without ragged sets runs stay where they were in the code object)
+    else GM_TRY(launch_head_loss_ragged(nt, hl, st));
+#ifdef GM_PROBES
+    // tools/head_loss_probe.py: the same launch again -- it is idempotent -- to see what a warm instruction cache / warm L2 is worth
+    static const int twice = getenv("GM_HEAD_TWICE") ? atoi(getenv("GM_HEAD_TWICE")) : 0;
+    if (twice && nt == 1024 && !ragged) (void)launch_head_loss_t<1024, false>(hl, st, true);
+#endif
+    GM_HIP(hipGetLastError());
+    return GM_OK;
+}
 // Head forward + loss (+ head backward) in one launch (k_head_loss) after a gcn_forward(..., skip_head = 1).  With
 // bwd != 0 the matching gcn_backward(..., skip_head = 1) continues from dQ_L / the compact G2 written here; c.sgd (if
 // set) makes the head's own parameters take their SGD step in the same launch.
@@ -1567,31 +1604,9 @@ static int head_loss(GcnCtx& c, const float* params, int64_t pstride, float* log
             if (c.dq == GcnCtx::DQ_MEMSET) GM_HIP(hipMemsetAsync(dQ, 0, sizeof(float) * b->rows * L.dims[L.n_gcn], st));      // (DQ_CENTRE: nobody reads the rows this launch does not assign)
         }
     }
-    HeadK hk = make_head(c, params, pstride);
-    const size_t proto_bytes = (proto_lds(pk.Ct, pk.n, pk.D, HL_THREADS) + 15) / 16 * 16;
-    int max_subs = 0;
-    for (int t = 0; t < b->sets; ++t) max_subs = std::max(max_subs, b->h_set_sub_off[t + 1] - b->h_set_sub_off[t]);
-    const int nc = mean ? 1 : b->centres;
-    const size_t hs_bytes = sizeof(float) * ((size_t)max_subs * nc * L.dims[L.n_gcn] + (size_t)L.n_out * (L.hc + 1) + 2 * (size_t)max_subs * L.n_out +
-                                             (size_t)max_subs * nc + (size_t)pk.Ct * pk.n + (ragged ? (size_t)pk.Ct + 1 : 0)) + 16;      // + the centre-row scratch + the class rows (a ragged set's follow its class starts)
-    const int stage_on = gm_knob().head_stage;
-    const int stage_h = stage_on && proto_bytes + hs_bytes <= 150 * 1024;
-    const size_t lds = proto_bytes + (stage_h ? hs_bytes : 0);
-    // Workgroup size (GM_HEAD_THREADS, default 1024): one workgroup per task.  Measured: 256 threads -- which could start on a CU that a persistent
-    // GEMM workgroup of the other stream fills -- lose more inside the kernel than they gain at its start (FirstMM shape 1.62 -> 1.89 ms per
-    // meta-step, 4-task arxiv shard 4.59 -> 4.86; 512: 1.71 / 4.67).
-    int nt = gm_knob().head_threads;
-    if (nt != 256 && nt != 512) nt = 1024;
-    const HeadLossLaunch hl{b->sets, lds, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, bwd ? c.sgd : SgdK{nullptr, 0, nullptr, 0, 0.f}, stage_h, (int)(proto_bytes / sizeof(float))};
+    const HeadK hk = make_head(c, params, pstride);
     gm_prof_begin(GM_PROF_HEAD, st, b->subs);
-    if (!ragged) GM_TRY(launch_head_loss<false>(nt, hl, st));      // (first: the kernels every launch without ragged sets runs stay where they were in the code object)
-    else GM_TRY(launch_head_loss_ragged(nt, hl, st));
-#ifdef GM_PROBES
-    // tools/head_loss_probe.py: the same launch again -- it is idempotent -- to see what a warm instruction cache / warm L2 is worth
-    static const int twice = getenv("GM_HEAD_TWICE") ? atoi(getenv("GM_HEAD_TWICE")) : 0;
-    if (twice && nt == 1024 && !ragged) (void)launch_head_loss_t<1024, false>(hl, st, true);
-#endif
-    GM_HIP(hipGetLastError());
+    GM_TRY(head_loss_launch(b, hk, logits, pk, bwd, dparams, dstride, dQ, Gc, c.sgd, ragged, 0, nullptr, st));
     gm_prof_end(GM_PROF_HEAD, st);
     if (bwd && dQ && hk.dq_amax) c.dqv = true;
     if (bwd && mean) GM_TRY(readout_bwd(c, st));
@@ -2436,4 +2451,80 @@ static int readout_bwd(const GcnCtx& c, hipStream_t st) {
     gm_prof_end(GM_PROF_READOUT_BWD, st);
     GM_HIP(hipGetLastError());
     return GM_OK;
+}
+
+// ================================================================================ head + loss, exported for numerics tests
+// One head-and-loss launch on the caller's own H, parameters, labels and prototypes (include/gmeta_hip.h).  path 0: k_head_loss through head_loss_launch, the
+// code head_loss() runs; path 1: k_head_fwd, k_proto, k_head_bwd as gm_gcn_forward / gm_proto_loss_* / gm_gcn_backward issue them.  Host code only.
+extern "C" int gm_dense_head_loss(const gm_batch_t* b, const float* H, int32_t Hd, int32_t nc, int32_t compact, int32_t C, const float* params,
+                                  int64_t param_stride, int64_t wl_off, int64_t bl_off, const int32_t* centre_local, const int32_t* y, int32_t mode,
+                                  int32_t n_support, const float* protos, int32_t c_task, const int32_t* spt_labels, const int32_t* spt_counts, float* logits,
+                                  float* dlogits, float* dprotos, float* protos_out, float* loss, float* acc, int32_t bwd, float* dparams,
+                                  int64_t dparam_stride, float* dQ, float* Gc, const float* sgd_cur, float* sgd_next, int64_t sgd_stride, float sgd_lr,
+                                  uint32_t* dq_amax, int32_t path, int32_t* launched, void* stream) {
+    GM_REQUIRE(b && H && params && y && logits && loss && acc, GM_EINVAL, "dense_head_loss: NULL argument");
+    GM_REQUIRE(Hd >= 1 && Hd <= 2048 && C >= 1 && C <= 64 && (nc == 1 || nc == 2), GM_ERANGE, "dense_head_loss: Hd=%d C=%d nc=%d out of range", Hd, C, nc);
+    GM_REQUIRE(path == 0 || path == 1, GM_EINVAL, "dense_head_loss: path is 0 (fused) or 1 (unfused)");
+    GM_REQUIRE(compact ? (nc == b->centres || nc == 1) : nc == b->centres, GM_EINVAL, "dense_head_loss: nc=%d on a batch of %d centre(s) per subgraph", nc, b->centres);
+    GM_REQUIRE(!compact || !centre_local, GM_EINVAL, "dense_head_loss: a compact H has no centre table to override");
+    const int hc = nc * Hd;
+    GM_REQUIRE(wl_off >= 0 && bl_off >= 0 && (bl_off >= wl_off + (int64_t)C * hc || wl_off >= bl_off + C), GM_EINVAL, "dense_head_loss: Wl and bl overlap");
+    const int64_t p_end = std::max(wl_off + (int64_t)C * hc, bl_off + C);
+    GM_REQUIRE(param_stride == 0 || param_stride >= p_end, GM_EINVAL, "dense_head_loss: param_stride %lld < %lld", (long long)param_stride, (long long)p_end);
+    GM_REQUIRE(mode == 0 || mode == 1, GM_EINVAL, "dense_head_loss: mode is 0 (support) or 1 (query)");
+    if (mode == 0) GM_REQUIRE(n_support >= 1 && !protos && !dprotos, GM_EINVAL, "dense_head_loss: mode 0 takes n_support >= 1 and neither protos nor dprotos");
+    else GM_REQUIRE(protos && c_task >= 1 && !protos_out, GM_EINVAL, "dense_head_loss: mode 1 takes protos and c_task >= 1, and has no protos_out");
+    GM_REQUIRE(!spt_labels == !spt_counts && (!spt_labels || (mode == 1 && g_ragged)), GM_EINVAL, "dense_head_loss: support classes go with mode 1 in ragged-task mode");
+    GM_REQUIRE(!dprotos || dlogits, GM_EINVAL, "dense_head_loss: dprotos is written with dlogits");
+    GM_REQUIRE(!(dQ && Gc), GM_EINVAL, "dense_head_loss: dQ together with Gc");
+    if (bwd) GM_REQUIRE(dlogits && dparams && (dQ || Gc) && (b->sets == 1 || dparam_stride >= p_end), GM_EINVAL,
+                        "dense_head_loss: the backward needs dlogits, dparams, one of dQ and Gc, and dparam_stride >= %lld", (long long)p_end);
+    else GM_REQUIRE(!dQ && !Gc && !sgd_next && !dq_amax, GM_EINVAL, "dense_head_loss: dQ, Gc, the SGD step and dq_amax are outputs of the backward");
+    GM_REQUIRE(!sgd_next || (sgd_cur && path == 0 && (b->sets == 1 || sgd_stride >= p_end)), GM_EINVAL, "dense_head_loss: the SGD step needs cur, the fused launch and a stride >= %lld", (long long)p_end);
+    GM_REQUIRE(!dq_amax || dQ, GM_EINVAL, "dense_head_loss: dq_amax goes with dQ");
+    hipStream_t st = (hipStream_t)stream;
+    ClassTables ct, cs;
+    if (spt_labels) {      // the support side's classes of every set (all class_tables_ragged reads of it)
+        cs.tab.assign((size_t)b->sets * 3, 0);
+        for (int t = 0; t < b->sets; ++t) {
+            GM_REQUIRE(spt_counts[t] >= 1 && spt_counts[t] <= c_task, GM_EINVAL, "dense_head_loss: set %d has %d support classes, c_task = %d", t, spt_counts[t], c_task);
+            cs.tab[t * 3 + 1] = spt_counts[t];
+            cs.labels.insert(cs.labels.end(), spt_labels + cs.labels.size(), spt_labels + cs.labels.size() + spt_counts[t]);
+        }
+    }
+    GM_TRY(class_tables(b, y, mode == 0 ? n_support : 0, ct, spt_labels ? &cs : nullptr));
+    if (mode == 1) {      // as gm_proto_loss_qry
+        for (int t = 0; t < b->sets; ++t)
+            GM_REQUIRE(g_ragged ? ct.tab[t * 3 + 1] <= c_task : ct.tab[t * 3 + 1] == c_task, GM_EINVAL,
+                       "dense_head_loss: set %d has %d query classes but the prototypes hold %d per set", t, ct.tab[t * 3 + 1], c_task);
+        GM_REQUIRE(c_task <= 256 && (int64_t)c_task * ct.n <= 16384, GM_ERANGE, "dense_head_loss: c_task=%d with %d rows per class is outside the kernel's range", c_task, ct.n);
+    }
+    const int Ct = mode == 1 ? c_task : ct.Ct;
+    const bool ragged = ct.qmax != 0;
+    int32_t* d_rows = nullptr;
+    GM_TRY(upload_tables(ct, &d_rows, st));
+    HeadK hk{};
+    hk.H = H; hk.ldh = Hd; hk.Hd = Hd;
+    hk.sub_off = b->d_sub_off; hk.centre = centre_local ? centre_local : b->d_centre; hk.nc = nc; hk.sub_set = b->d_sub_set; hk.set_sub_off = b->d_set_sub_off;
+    hk.params = params; hk.pstride = param_stride; hk.wl_off = wl_off; hk.bl_off = bl_off; hk.hc = hc; hk.C = C; hk.subs = b->subs; hk.compact = compact ? 1 : 0;
+    hk.dq_amax = dq_amax; hk.subs_per_set = head_subs_per_set(b);
+    int rc = GM_OK;
+    if (path == 0) {
+        const ProtoK pk{logits, C, d_rows, Ct, ct.n, mode, protos, protos_out, loss, acc, 1, 0, dlogits, dprotos, 0, d_rows + ct.rows.size(), (ct.uniform && ct.Ct == Ct) ? 1 : 0};
+        rc = head_loss_launch(b, hk, logits, pk, bwd ? 1 : 0, dparams, dparam_stride, dQ, Gc, SgdK{sgd_cur, sgd_stride, sgd_next, sgd_stride, sgd_lr}, ragged, 1, launched, st);
+    } else {
+        hipLaunchKernelGGL(k_head_fwd, dim3((b->subs + 3) / 4), dim3(256), 0, st, hk, logits);
+        if (dlogits && hipMemsetAsync(dlogits, 0, sizeof(float) * b->subs * C, st) != hipSuccess) { gm_set_error("dense_head_loss: memset failed"); rc = GM_EHIP; }
+        if (rc == GM_OK) {
+            const ProtoK pk{logits, C, d_rows, Ct, ct.n, mode, protos, protos_out, loss, acc, 1, 0, dlogits, dprotos, 0, d_rows + ct.rows.size()};
+            rc = launch_proto(b, pk, ragged, st);
+        }
+        if (rc == GM_OK && bwd) hipLaunchKernelGGL(k_head_bwd, dim3(b->sets), dim3(256), 0, st, hk, (const float*)dlogits, dparams, dparam_stride, dQ, Gc);
+        if (rc == GM_OK && hipGetLastError() != hipSuccess) { gm_set_error("dense_head_loss: launch failed"); rc = GM_EHIP; }
+        if (launched) { launched[0] = 256; launched[1] = 0; launched[2] = ragged ? 1 : 0; }
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && rc == GM_OK) { gm_set_error("dense_head_loss: kernel failed"); rc = GM_EHIP; }
+    gm_dev_free(d_rows, st);
+    gm_batch_mark_use(b, st);
+    return rc;
 }

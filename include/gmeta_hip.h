@@ -549,6 +549,32 @@ int gm_proto_loss_qry(const gm_batch_t* b, const float* logits, int32_t n_out, c
                       int32_t c_task, float* loss, float* acc, float* dlogits, float* dprotos, void* stream);
 void gm_set_ragged_classes(int32_t on);     /* 1 / 0: ragged-task mode of the calling thread (above); workspace sizes depend on it */
 int32_t gm_get_ragged_classes(void);
+/* One launch of the classifier head with the prototypical loss (and the head's backward) as gm_meta_step issues it after the last GCN layer, exported for
+ * numerics tests of k_head_loss and of the unfused k_head_fwd / k_proto / k_head_bwd.  The LDS sizing, the staging decision (GM_HEAD_STAGE, and unstaged
+ * by itself above 150 KB of LDS per set), the workgroup size (GM_HEAD_THREADS) and the choice of the ragged instantiations are the library's own code.
+ *   H: device fp32 [rows, Hd], the post-relu output of the last layer; compact != 0: [subs * nc, Hd], the centre rows only, in centre order.
+ *   nc: centres per subgraph, the batch's own; with a compact H also 1 on a pair batch (pooled rows).  The head reads hc = nc * Hd columns, C = classes (<= 64).
+ *   params + t * param_stride (0: one vector for every set): Wl [C, hc] at wl_off, bl [C] at bl_off.  centre_local: as gm_gcn_forward, or NULL.
+ *   y: HOST int32 [subs].  mode 0: support loss over the first n_support rows of every class (protos_out [sets, classes, C] or NULL);  mode 1: query loss
+ *   against protos [sets, c_task, C] (dprotos likewise, or NULL).  Class tables by the rules of gm_proto_loss_spt / _qry, ragged-task mode included; in that
+ *   mode and mode 1, spt_labels / spt_counts (HOST; or both NULL) give every set's sorted support classes (concatenated; counts [sets], each <= c_task): the
+ *   query rows are then filed under them as gm_meta_step does, and a class may have no rows.
+ *   logits [subs, C], loss [sets], acc [sets]: always written.  dlogits [subs, C] (or NULL: no gradient): the loss's gradient, zero for subgraphs outside
+ *   the class tables.  bwd != 0 (needs dlogits, dparams): dparams + t * dparam_stride receives dWl / dbl at wl_off / bl_off and nothing else; dQ [rows, Hd]
+ *   receives relu'(H) * (dlogits @ Wl) at the centre rows -- NO other row is written, the call does no memset --, or Gc [subs * nc, Hd] the same rows in
+ *   centre order (over either form of H): exactly one of the two with bwd, neither without.  sgd_next (or NULL; fused launch only): sgd_next_t = sgd_cur_t - sgd_lr * (dWl, dbl) at the same
+ *   offsets, vectors sgd_stride apart.  dq_amax (or NULL; with dQ): uint32 slots t * 64, zeroed by the caller, receive the fp32 bits of max |dQ| written for set t.
+ *   path 0: the fused k_head_loss; 1: k_head_fwd, k_proto, k_head_bwd as gm_gcn_forward / gm_proto_loss_* / gm_gcn_backward launch them (no SGD step).
+ *   launched (HOST int32 [3], or NULL): {workgroup size, staged (LDS) 1 / 0, ragged instantiation 1 / 0} of the kernel that ran (path 1: 256, 0, k_proto's).
+ * The call synchronises the stream.  GM_EINVAL: dQ together with Gc; mode 1 without protos; mode 0 with protos / dprotos; bwd without dlogits / dparams; an
+ * output of the backward without bwd; the SGD step on path 1; dq_amax without dQ; nc that does not fit the batch; overlapping or too short strides; the
+ * refusals of gm_proto_loss_*. */
+int gm_dense_head_loss(const gm_batch_t* b, const float* H, int32_t Hd, int32_t nc, int32_t compact, int32_t C, const float* params,
+                       int64_t param_stride, int64_t wl_off, int64_t bl_off, const int32_t* centre_local, const int32_t* y, int32_t mode,
+                       int32_t n_support, const float* protos, int32_t c_task, const int32_t* spt_labels, const int32_t* spt_counts, float* logits,
+                       float* dlogits, float* dprotos, float* protos_out, float* loss, float* acc, int32_t bwd, float* dparams,
+                       int64_t dparam_stride, float* dQ, float* Gc, const float* sgd_cur, float* sgd_next, int64_t sgd_stride, float sgd_lr,
+                       uint32_t* dq_amax, int32_t path, int32_t* launched, void* stream);
 
 /* READOUT, gm_set_readout(mode): GM_READOUT_CENTRE (0, default: the head reads the centre row(s) of every subgraph, learner.py:159-170) or
  * GM_READOUT_MEAN (1: the alternative the reference left commented out, `#h = dgl.mean_nodes(g, 'h')`, learner.py:160); per calling thread, like
