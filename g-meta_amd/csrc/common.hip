@@ -372,6 +372,8 @@ const gm_knobs& gm_knob() {
         k.walk_lanes = env("GM_WALK_LANES", 0);
         k.ppr_chunk = env("GM_PPR_CHUNK", 0);
         k.ppr_cols = env("GM_PPR_COLS", 0);
+        k.dist_chunk = env("GM_DIST_CHUNK", 0);
+        k.dist_cols = env("GM_DIST_COLS", 0);
     });
     return k;
 }
@@ -396,6 +398,8 @@ static int gm_knobs::* gm_find_knob(const char* name) {
         {"walk_lanes", &gm_knobs::walk_lanes}, {"GM_WALK_LANES", &gm_knobs::walk_lanes},
         {"ppr_chunk", &gm_knobs::ppr_chunk}, {"GM_PPR_CHUNK", &gm_knobs::ppr_chunk},
         {"ppr_cols", &gm_knobs::ppr_cols}, {"GM_PPR_COLS", &gm_knobs::ppr_cols},
+        {"dist_chunk", &gm_knobs::dist_chunk}, {"GM_DIST_CHUNK", &gm_knobs::dist_chunk},
+        {"dist_cols", &gm_knobs::dist_cols}, {"GM_DIST_COLS", &gm_knobs::dist_cols},
     };
     for (const auto& e : tab)
         if (!strcmp(name, e.name)) return e.field;

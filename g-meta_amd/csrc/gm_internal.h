@@ -264,6 +264,8 @@ struct gm_knobs {
     int walk_lanes;                // GM_WALK_LANES, gm_set_tuning("walk_lanes"): lanes per work item of gm_store_pair_walks: 32 or 64; 0 (default) = by the graph's mean distinct degree and the length of the pair list.  The result does not depend on it
     int ppr_chunk;                 // GM_PPR_CHUNK, gm_set_tuning("ppr_chunk"): entries per segment of a hub row of gm_store_rooted_pagerank / gm_store_pair_pagerank (pair_pagerank.hip); 0 (default) = the library's choice.  The order of a row sum, hence the low bits of the result, belongs to it
     int ppr_cols;                  // GM_PPR_COLS, gm_set_tuning("ppr_cols"): columns per round of those two calls, a multiple of 64; 0 (default) = the library's choice.  The result does not depend on it
+    int dist_chunk;                // GM_DIST_CHUNK, gm_set_tuning("dist_chunk"): entries per segment of a hub row of gm_store_node_distances / gm_store_pair_distance (pair_distance.hip); 0 (default) = the library's choice.  The result does not depend on it
+    int dist_cols;                 // GM_DIST_COLS, gm_set_tuning("dist_cols"): columns per round of those two calls, a multiple of 64 up to 4096; 0 (default) = the library's choice.  The result does not depend on it
     int cand_bitmap;               // GM_CAND_BITMAP, gm_set_tuning("cand_bitmap"): home of that call's membership bitmap: 1 LDS, 2 a per-workgroup slab in HBM; 0 (default) = LDS wherever the graph fits.  The result does not depend on it
 };
 const gm_knobs& gm_knob();

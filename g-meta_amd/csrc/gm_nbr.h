@@ -1,6 +1,6 @@
 // The neighbour index (nbr_index.hip; gm_store in gm_internal.h) as the kernels see it: one graph's view, the search of a row, the adjacency test, the
 // canonical form of a pair and the intersection of two rows.  Included by the translation units that read the index (pair_scores.hip, candidates.hip,
-// pair_walks.hip, pair_pagerank.hip).  Every meaning bits depend on -- the tie rule, the symmetric rows -- is stated here once.
+// pair_walks.hip, pair_pagerank.hip, pair_distance.hip).  Every meaning bits depend on -- the tie rule, the symmetric rows -- is stated here once.
 #pragma once
 #include "gm_internal.h"
 

@@ -1,4 +1,4 @@
-// The neighbour index of a store: what the link-prediction calls read (pair_scores.hip, candidates.hip, pair_walks.hip, pair_pagerank.hip; the kernels' side
+// The neighbour index of a store: what the link-prediction calls read (pair_scores.hip, candidates.hip, pair_walks.hip, pair_pagerank.hip, pair_distance.hip; the kernels' side
 // of it is gm_nbr.h) and gm_store_neighbour_degrees shows the degrees of.  The DEFINITION is in include/gmeta_hip.h.
 //   the index   per node the ascending DISTINCT row of its in- and out-neighbours without itself (int64 row pointers over all graphs, int32 graph-local
 //               ids) and deg, 1 / ln(deg), 1 / deg.  Built on the host at the first call that needs it: the in-rows of the store keep the caller's edge

@@ -18,6 +18,7 @@
 // No float atomics, nothing depends on arrival order: a column's bits are a function of (graph, s, x, alpha, iters, C) alone.  Everything runs on the caller's
 // stream; scratch comes from the stream-ordered pool.
 #include <math.h>
+#include "gm_columns.h"
 #include "gm_nbr.h"
 
 #define GM_PPR_THREADS 256
@@ -287,39 +288,6 @@ static int ppr_rounds(const char* what, const ppr_call& c, const int64_t* h_ptr,
     return GM_OK;
 }
 
-// [lo, hi) of the ascending column numbers `col` that a round starting at column c0 serves: its own columns, and in the first round the -1s (no column)
-static void ppr_span(const std::vector<int32_t>& col, int64_t c0, int64_t Br, int64_t* lo, int64_t* hi) {
-    *lo = c0 == 0 ? 0 : std::lower_bound(col.begin(), col.end(), c0) - col.begin();
-    *hi = std::lower_bound(col.begin(), col.end(), c0 + Br) - col.begin();
-}
-
-// The columns a call walks and the order its output entries leave in.  want[e]: the column (source, excluded node) of output entry e as ppr_key packs it, -1:
-// no column (a node outside the graph).  -> cs / cx: the distinct columns in ascending (source, excluded) order; order: the entries stably by column number,
-// those without a column first; col[i]: the column number of entry order[i] (-1: none)
-struct ppr_plan {
-    std::vector<int32_t> cs, cx, col;
-    std::vector<int64_t> order;
-};
-static int64_t ppr_key(int32_t src, int32_t x) { return ((int64_t)src << 32) | (uint32_t)(x + 1); }
-static int ppr_plan_of(const char* what, const std::vector<int64_t>& want, ppr_plan* P) {
-    std::vector<int64_t> keys;
-    for (const int64_t w : want)
-        if (w >= 0) keys.push_back(w);
-    std::sort(keys.begin(), keys.end());
-    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-    GM_REQUIRE(keys.size() <= (size_t)INT32_MAX, GM_ERANGE, "%s: %lld distinct columns", what, (long long)keys.size());
-    P->cs.resize(keys.size()); P->cx.resize(keys.size());
-    for (size_t k = 0; k < keys.size(); ++k) { P->cs[k] = (int32_t)(keys[k] >> 32); P->cx[k] = (int32_t)(uint32_t)keys[k] - 1; }
-    std::vector<int32_t> ecol(want.size());
-    for (size_t e = 0; e < want.size(); ++e) ecol[e] = want[e] < 0 ? -1 : (int32_t)(std::lower_bound(keys.begin(), keys.end(), want[e]) - keys.begin());
-    P->order.resize(want.size());
-    for (size_t e = 0; e < want.size(); ++e) P->order[e] = (int64_t)e;
-    std::stable_sort(P->order.begin(), P->order.end(), [&](int64_t p, int64_t q) { return ecol[(size_t)p] < ecol[(size_t)q]; });
-    P->col.resize(want.size());
-    for (size_t e = 0; e < want.size(); ++e) P->col[e] = ecol[(size_t)P->order[e]];
-    return GM_OK;
-}
-
 extern "C" int32_t gm_store_rooted_pagerank(const gm_store_t* s, int32_t g, const int32_t* d_sources, int64_t m, float alpha, int32_t iters, float* d_out, void* stream) {
     const char* what = "gm_store_rooted_pagerank";
     ppr_call c;
@@ -334,9 +302,9 @@ extern "C" int32_t gm_store_rooted_pagerank(const gm_store_t* s, int32_t g, cons
     // one entry per output row: the whole-graph column of its source
     std::vector<int64_t> want((size_t)m, -1);
     for (int64_t r = 0; r < m; ++r)
-        if (h_src[r] >= 0 && h_src[r] < N) want[(size_t)r] = ppr_key(h_src[r], -1);
-    ppr_plan pl;
-    GM_TRY(ppr_plan_of(what, want, &pl));
+        if (h_src[r] >= 0 && h_src[r] < N) want[(size_t)r] = gm_col_key(h_src[r], -1);
+    gm_col_plan pl;
+    GM_TRY(gm_col_plan_of(what, want, &pl));
     const std::vector<int32_t>& col = pl.col;
     const std::vector<int32_t> row(pl.order.begin(), pl.order.end());      // (m <= INT32_MAX output rows)
     gm_scratch sc(c.st);
@@ -345,7 +313,7 @@ extern "C" int32_t gm_store_rooted_pagerank(const gm_store_t* s, int32_t g, cons
     const int64_t v_tiles = (N + GM_PPR_TILE - 1) / GM_PPR_TILE;
     return ppr_rounds(what, c, h_ptr, pl.cs, pl.cx, sg, [&](int64_t c0, int32_t Br, const float* P) {
         int64_t lo, hi;
-        ppr_span(col, c0, Br, &lo, &hi);
+        gm_col_span(col, c0, Br, true, &lo, &hi);
         if (hi == lo) return (int)GM_OK;
         const int64_t blocks = v_tiles * ((hi - lo + GM_PPR_TILE - 1) / GM_PPR_TILE);
         GM_REQUIRE(blocks <= (int64_t)INT32_MAX, GM_ERANGE, "%s: %lld output tiles in one round", what, (long long)blocks);
@@ -385,11 +353,11 @@ extern "C" int32_t gm_store_pair_pagerank(const gm_store_t* s, int32_t g, const 
         if (p < 0 || p >= N || q < 0 || q >= N) continue;
         const int32_t u = p < q ? p : q, v = p < q ? q : p;
         const bool cut = mask && h_adj[k];
-        want[(size_t)(2 * k)] = ppr_key(u, cut ? v : -1); node[(size_t)(2 * k)] = v;
-        want[(size_t)(2 * k + 1)] = ppr_key(v, cut ? u : -1); node[(size_t)(2 * k + 1)] = u;
+        want[(size_t)(2 * k)] = gm_col_key(u, cut ? v : -1); node[(size_t)(2 * k)] = v;
+        want[(size_t)(2 * k + 1)] = gm_col_key(v, cut ? u : -1); node[(size_t)(2 * k + 1)] = u;
     }
-    ppr_plan pl;
-    GM_TRY(ppr_plan_of(what, want, &pl));
+    gm_col_plan pl;
+    GM_TRY(gm_col_plan_of(what, want, &pl));
     const std::vector<int32_t>& col = pl.col;
     const std::vector<int64_t>& dst = pl.order;
     std::vector<int32_t> nd((size_t)(2 * n));
@@ -399,7 +367,7 @@ extern "C" int32_t gm_store_pair_pagerank(const gm_store_t* s, int32_t g, const 
     GM_TRY(sc.put(&d_dst, dst, sg)); GM_TRY(sc.put(&d_node, nd, sg)); GM_TRY(sc.put(&d_col, col, sg));
     return ppr_rounds(what, c, h_ptr, pl.cs, pl.cx, sg, [&](int64_t c0, int32_t Br, const float* P) {
         int64_t lo, hi;
-        ppr_span(col, c0, Br, &lo, &hi);
+        gm_col_span(col, c0, Br, true, &lo, &hi);
         if (hi == lo) return (int)GM_OK;
         hipLaunchKernelGGL(k_ppr_entries_out, dim3((unsigned)((hi - lo + GM_PPR_THREADS - 1) / GM_PPR_THREADS)), dim3(GM_PPR_THREADS), 0, c.st, P, Br, c0,
                            (const int64_t*)d_dst + lo, (const int32_t*)d_node + lo, (const int32_t*)d_col + lo, hi - lo, d_out);
@@ -429,9 +397,9 @@ extern "C" int32_t gm_store_pagerank_candidates(const gm_store_t* s, int32_t g, 
     // one entry per output row: the whole-graph column of its source
     std::vector<int64_t> want((size_t)m, -1);
     for (int64_t r = 0; r < m; ++r)
-        if (h_src[r] >= 0 && h_src[r] < N) want[(size_t)r] = ppr_key(h_src[r], -1);
-    ppr_plan pl;
-    GM_TRY(ppr_plan_of(what, want, &pl));
+        if (h_src[r] >= 0 && h_src[r] < N) want[(size_t)r] = gm_col_key(h_src[r], -1);
+    gm_col_plan pl;
+    GM_TRY(gm_col_plan_of(what, want, &pl));
     const std::vector<int32_t>& col = pl.col;
     const std::vector<int32_t> row(pl.order.begin(), pl.order.end());      // (m <= INT32_MAX output rows)
     const int64_t ncp = ((int64_t)pl.cs.size() + GM_WAVE - 1) / GM_WAVE * GM_WAVE;
@@ -445,7 +413,7 @@ extern "C" int32_t gm_store_pagerank_candidates(const gm_store_t* s, int32_t g, 
     if (timed) { GM_HIP(hipStreamSynchronize(c.st)); tm.lap("plan"); }
     return ppr_rounds(what, c, h_ptr, pl.cs, pl.cx, sg, [&](int64_t c0, int32_t Br, float* P) {
         int64_t lo, hi;
-        ppr_span(col, c0, Br, &lo, &hi);
+        gm_col_span(col, c0, Br, true, &lo, &hi);
         return gm_pprc_round(sel, c.G, P, Br, (const int32_t*)d_src + c0, (const int32_t*)d_row + lo, (const int32_t*)d_col + lo, c0, hi - lo, d_out_nodes, d_out_scores,
                              d_out_total, timed ? &tm : nullptr);
     });

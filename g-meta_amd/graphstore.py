@@ -207,6 +207,38 @@ class GraphStore:
         g, p = self._pairs_of(g, pairs, 'pair_pagerank')
         return self._pair_call('gm_store_pair_pagerank', g, p, (len(p), 2), torch.float32, _lib.PAIR_MASK_TARGET if mask_target else 0, alpha, iters)
 
+    @staticmethod
+    def _max_dist_of(max_dist, what):
+        max_dist = int(max_dist)
+        if not 1 <= max_dist <= 254:
+            raise ValueError('%s: max_dist = %d; 1 .. 254' % (what, max_dist))
+        return max_dist
+
+    def node_distances(self, g, sources, max_dist=8):
+        """uint8 [m, N]: row r holds the shortest-path distance (edges) from sources[r] to every node of graph `g` in the distinct-neighbour graph of
+        pair_scores, searched on the device one bit per (node, source) (gm_store_node_distances; the definition is in include/gmeta_hip.h,
+        tests/distance_ref.py restates it).  A node that no path of at most `max_dist` (1..254) edges reaches holds gmeta_amd.DIST_UNREACHED (255).  Duplicate
+        sources are allowed."""
+        import torch
+        max_dist = self._max_dist_of(max_dist, 'node_distances')
+        g, a = self._nodes_of(g, sources, 'node_distances')
+        out = torch.empty((len(a), self.n_nodes[g]), dtype=torch.uint8, device='cuda')
+        if len(a):
+            d_a = torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
+            _lib.check(_lib.lib().gm_store_node_distances(self.handle, g, _lib.ptr(d_a), len(a), max_dist, _lib.ptr(out), _lib.stream_ptr()),
+                       'gm_store_node_distances')
+        return out.cpu().numpy()
+
+    def pair_distance(self, g, pairs, mask_target=False, max_dist=8):
+        """uint8 [m]: the shortest-path distance between the two nodes of each of the [m, 2] `pairs` of graph `g` (node_distances' entries), searched on
+        the device (gm_store_pair_distance); gmeta_amd.DIST_UNREACHED (255) beyond `max_dist` (1..254) edges.  mask_target=True measures an adjacent pair in
+        the graph without its own edge: the length of the detour, 255 when the edge is a bridge (or the detour is longer than max_dist).
+        gmeta_amd.graph_distance_index turns the bytes into the score."""
+        import torch
+        max_dist = self._max_dist_of(max_dist, 'pair_distance')
+        g, p = self._pairs_of(g, pairs, 'pair_distance')
+        return self._pair_call('gm_store_pair_distance', g, p, len(p), torch.uint8, _lib.PAIR_MASK_TARGET if mask_target else 0, max_dist)
+
     def neighbour_degrees(self, g):
         """int32 [N]: the number of distinct neighbours (either direction, itself aside) of every node of graph `g` -- the degrees the pair scores use."""
         import torch

@@ -2,14 +2,16 @@
 include/gmeta_hip.h) turned into the ROC AUC a learned link predictor is held against.  The scores come from the device; the AUC is host work over
 one number per pair.  The path scores one step further -- the local path index and the truncated Katz index -- are formed here, in float64, from the exact walk
 counts of GraphStore.pair_walks (gm_store_pair_walks).  The one global score, rooted PageRank, is the float64 sum of the two columns of
-GraphStore.pair_pagerank (gm_store_pair_pagerank)."""
+GraphStore.pair_pagerank (gm_store_pair_pagerank).  Graph distance is the negated byte of GraphStore.pair_distance (gm_store_pair_distance)."""
 import numpy as np
 
+from ._lib import DIST_UNREACHED
 from .negatives import _pair
 
 PAIR_SCORES = ('cn', 'jaccard', 'adamic_adar', 'resource_allocation', 'pref_attachment')      # the columns of GraphStore.pair_scores, in order
 PATH_SCORES = ('local_path', 'katz')                                                          # the scores made of GraphStore.pair_walks' three columns
 PAGERANK_SCORES = ('rooted_pagerank',)                                                        # the score made of GraphStore.pair_pagerank's two columns
+DISTANCE_SCORES = ('graph_distance',)                                                        # the score made of GraphStore.pair_distance's byte
 
 
 def link_auc(scores, labels):
@@ -94,6 +96,24 @@ def link_pagerank_auc(store, names, labels, mask_target=False, alpha=0.15, iters
     """{'rooted_pagerank': ROC AUC} (PAGERANK_SCORES) over the pairs `names` ('g_i_j') with the 0 / 1 `labels` of a link table, all graphs together;
     mask_target as in link_heuristic_auc."""
     return {'rooted_pagerank': link_auc(rooted_pagerank_index(link_pagerank_scores(store, names, mask_target, alpha, iters)), labels)}
+
+
+def graph_distance_index(dist, max_dist):
+    """float64 [m]: -d of the uint8 [m] distances of GraphStore.pair_distance, an unreached pair (DIST_UNREACHED) at -(max_dist + 1): a closer pair ranks
+    higher and an unreached one below everything reached."""
+    d = np.asarray(dist, np.uint8).reshape(-1)
+    return -np.where(d == DIST_UNREACHED, int(max_dist) + 1, d).astype(np.float64)
+
+
+def link_distance_scores(store, names, mask_target=False, max_dist=8):
+    """uint8 [len(names)]: GraphStore.pair_distance of the pairs named 'g_i_j', one call per graph, in the order of `names`."""
+    return _per_graph(store, names, 1, np.uint8, lambda g, p: store.pair_distance(g, p, mask_target=mask_target, max_dist=max_dist).reshape(-1, 1)).reshape(-1)
+
+
+def link_distance_auc(store, names, labels, mask_target=False, max_dist=8):
+    """{'graph_distance': ROC AUC} (DISTANCE_SCORES) over the pairs `names` ('g_i_j') with the 0 / 1 `labels` of a link table, all graphs together; the many
+    pairs at one distance tie and count one half each (link_auc).  mask_target as in link_heuristic_auc."""
+    return {'graph_distance': link_auc(graph_distance_index(link_distance_scores(store, names, mask_target, max_dist), max_dist), labels)}
 
 
 def candidate_names(g, nodes, partners):

@@ -274,6 +274,37 @@ int32_t gm_store_pair_pagerank(const gm_store_t* s, int32_t g, const int32_t* d_
 int32_t gm_store_pagerank_candidates(const gm_store_t* s, int32_t g, const int32_t* d_nodes, int64_t m, int32_t k, float alpha, int32_t iters,
                                      int32_t* d_out_nodes, float* d_out_scores, int32_t* d_out_total, void* stream);
 
+/* ---- SHORTEST-PATH DISTANCES of sources and node pairs (beyond the reference): graph distance, the first of the classical link-prediction baselines, and the
+ * answer to "which nodes lie within d hops" and "is this edge a bridge, and if not how long is the detour" -- a bit-parallel breadth-first search of many
+ * columns at once, on the device.  This comment is THE definition; tests/distance_ref.py restates it with a plain breadth-first search.  Per parent graph g of
+ * a store, with N nodes:
+ *   neighbourhood  G(x) is that of gm_store_pair_scores: DISTINCT nodes joined in either direction, self loops never count, parallel copies count once,
+ *                  weights are ignored.
+ *   column         a pair (s, x), exactly as for gm_store_rooted_pagerank: s the source, x = -1 or a node whose edge {s, x} is removed.  The column's graph G'
+ *                  is G when x = -1, x == s or x not in G(s); otherwise G without that one edge.
+ *   distance       d_(s,x)[v] = the number of edges on a shortest path from s to v in G'; 0 for v == s; UNREACHED when there is no path or the shortest one
+ *                  is longer than max_dist.  max_dist in 1 .. 254; unreached is the byte 255 (GM_DIST_UNREACHED) in both results.
+ *   gm_store_node_distances   d_sources: device int32 [m]; d_out: device uint8 [m, N], row r = d_(sources[r], -1).  Duplicates are allowed, every row is
+ *                  written on its own; a source outside [0, N) gives a row of 255.  Nothing behind row m - 1 is written.
+ *   gm_store_pair_distance    d_pairs: device int32 [n, 2], any orientation, a == b allowed; a pair is canonicalised to (u, v) = (min, max).  d_out: device
+ *                  uint8 [n].  Without a flag the entry is d_(u,-1)[v].  With GM_PAIR_MASK_TARGET (1) in `flags` it is d_(u,v)[v]: the distance in the graph
+ *                  without the pair's own edge, as the other pair calls mask it (G' is symmetric, so d_(v,u)[u] is the same number: one column per pair);
+ *                  a non-adjacent pair gives the unflagged byte.  a == b gives 0; a node outside the graph gives 255.
+ *   exactness      the results are integers and unique.  A row or entry is a function of (graph, its own source or pair, flags, max_dist) alone: not of the
+ *                  other rows of the call, their order or their duplicates, not of how many columns a round holds (gm_set_tuning("dist_cols", B), a multiple
+ *                  of 64 up to 4096, 0 = the library's choice), not of where a long row is cut (gm_set_tuning("dist_chunk", C): entries per segment of a
+ *                  row of more than C, C >= 0, 0 = the library's choice), not of the stream or of arrival order.  gm_store_pair_distance without the flag
+ *                  gives the entries of gm_store_node_distances' rows.
+ * Both calls read the neighbour index (built at first use, as for gm_store_pair_scores), run on `stream`, take their scratch -- three bit matrices of
+ * N x B / 8 bytes each, B = the columns of a round, and 8 bytes per hub segment and 64 columns -- from the stream-ordered pool, and read the sources or pairs
+ * (and the graph's row lengths) back once to form the distinct columns; a call with max_dist above 16 also reads one flag back every 16 levels to stop early.
+ * The result is complete in stream order.  n == 0 / m == 0 is a no-op.
+ * GM_EINVAL (the message names the value): a bad graph index, n / m negative or above INT32_MAX, unknown flag bits, max_dist outside 1 .. 254, a NULL argument
+ * with work to do, a negative dist_chunk, a dist_cols that is no multiple of 64 or above 4096. */
+#define GM_DIST_UNREACHED 255
+int32_t gm_store_node_distances(const gm_store_t* s, int32_t g, const int32_t* d_sources, int64_t m, int32_t max_dist, uint8_t* d_out, void* stream);
+int32_t gm_store_pair_distance(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, int32_t max_dist, uint8_t* d_out, void* stream);
+
 /* ---- Extraction: replaces Subgraphs.generate_subgraph / generate_subgraph_link_pred
  * (sdp.py:295-346: h-hop in-neighbour expansion, node sampling, G.subgraph) and dgl.batch
  * (sdp.py:399-406) for n_sets sets at once.  seeds/set_offsets are host arrays; set s owns seeds

@@ -74,6 +74,10 @@ def parse(argv=None):
     ap.add_argument('--pagerank', type=int, default=0, choices=[0, 1],
                     help='1 (--link_pred_mode True): after the test evaluation and the --heuristics lines, print the ROC AUC of the rooted PageRank score (the one global '
                          'baseline: GraphStore.pair_pagerank, alpha 0.15, 20 iterations) over the pairs of the test table; follows --mask_target, independent of --heuristics')
+    ap.add_argument('--distance', type=int, default=0,
+                    help='D in 1..254 (--link_pred_mode True): after the test evaluation and the --heuristics / --pagerank lines, print the ROC AUC of graph distance (the '
+                         'shortest path of at most D edges, closer ranks higher: GraphStore.pair_distance) over the pairs of the test table; follows --mask_target, '
+                         'independent of --heuristics and --pagerank; 0 = off')
     ap.add_argument('--readout', default='centre', choices=['centre', 'mean'],
                     help="what the head reads of every subgraph: 'centre' = the centre row (both endpoints' rows of a pair), as the reference; 'mean' = the mean "
                          "over all of its rows (the dgl.mean_nodes line the reference left commented out), one pooled vector for pairs too")
@@ -91,6 +95,10 @@ def parse(argv=None):
         raise SystemExit('--heuristics 2 scores node PAIRS: it needs --link_pred_mode True')
     if a.pagerank and a.link_pred_mode != 'True':
         raise SystemExit('--pagerank 1 scores node PAIRS: it needs --link_pred_mode True')
+    if not 0 <= a.distance <= 254:
+        raise SystemExit('--distance %d: 1 .. 254 (the longest path searched), 0 = off' % a.distance)
+    if a.distance and a.link_pred_mode != 'True':
+        raise SystemExit('--distance %d scores node PAIRS: it needs --link_pred_mode True' % a.distance)
     return a
 
 
@@ -216,6 +224,12 @@ def main(args):
         res['pagerank_auc'] = gmeta_amd.link_pagerank_auc(store, names, labels, mask_target=bool(args.mask_target))
         if rank == 0:
             print('PageRank test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['pagerank_auc'].items()))
+    if args.distance:
+        from gmeta_amd.negatives import read_link_tables
+        names, labels = (tables if tables is not None else read_link_tables(root))['test']
+        res['distance_auc'] = gmeta_amd.link_distance_auc(store, names, labels, mask_target=bool(args.mask_target), max_dist=args.distance)
+        if rank == 0:
+            print('Distance test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['distance_auc'].items()))
     return res
 
 
