@@ -3,7 +3,8 @@
 // over the neighbour index (nbr_index.hip; gm_nbr.h):
 //   columns     a column is a pair (s, x): the search from s in the graph without the edge {s, x} (x = -1: the whole graph).  The host reads the sources or pairs
 //               back once, forms the DISTINCT columns in ascending (s, x) order (gm_columns.h) and runs them in rounds of at most B
-//               (gm_set_tuning("dist_cols")); with the mask flag only adjacent pairs get a column of their own (adjacency: k_dist_adjacent, before the read-back).
+//               (gm_set_tuning("dist_cols")); with the mask flag only adjacent pairs get a column of their own.  The call's frame -- knob checks, read-back
+//               and plan, adjacency, hub cut -- is gm_columns.h.
 //   the state   ONE BIT per (node, column): three bit matrices [N, W] of 64-bit words, W = B / 64 -- seen, frontier, next.  A level is a pull over the symmetric
 //               rows: next[v] = (OR over z in G(v) of frontier[z]) & ~seen[v], seen[v] |= next[v]; frontier and next swap.  Every word of the three is written by
 //               exactly one lane with a plain vector store (seen[v] is read by the lane that owns it alone); there are no atomics.
@@ -32,7 +33,6 @@
 //               and the lists of the columns, hub segments and output entries (4 .. 16 bytes each), from the stream-ordered pool.
 // A result is a function of (graph, source or pair, flags, max_dist) alone.  Everything runs on the caller's stream.
 #include "gm_columns.h"
-#include "gm_nbr.h"
 
 #define GM_DIST_THREADS 256
 #define GM_DIST_UNROLL 8                  // row reads of the frontier in flight per lane
@@ -203,13 +203,6 @@ __global__ void __launch_bounds__(GM_DIST_THREADS) k_dist_rows_out(const uint64_
     }
 }
 
-// adj[k] = 1 where the two nodes of pair k are distinct, inside the graph and neighbours (the pairs whose masked column differs from the unmasked one)
-__global__ void __launch_bounds__(GM_DIST_THREADS) k_dist_adjacent(gm_nbr_graph G, const int32_t* __restrict__ pairs, int64_t n, uint8_t* __restrict__ adj) {
-    const int64_t k = (int64_t)blockIdx.x * GM_DIST_THREADS + threadIdx.x;
-    if (k >= n) return;
-    adj[k] = gm_nbr_adjacent(G, pairs[2 * k], pairs[2 * k + 1]) ? 1 : 0;
-}
-
 // Columns per round and entries per hub segment, from the sweep at the arxiv shape (profiles/pair_distance.txt).  The widest round wins wherever there are
 // columns to fill it -- a level costs its launches and the longest row's tail once per round (4,096 sources: 22.7 / 9.1 / 6.0 / 5.5 ms at 64 / 256 / 1,024 /
 // 4,096 columns) --, so the library takes the bound; a round is never wider than the call's columns.  The cut: segments of 64 .. 256 lie within a few percent of
@@ -220,39 +213,21 @@ static int32_t dist_chunk_for() { return 128; }
 
 static unsigned dist_grid(int64_t threads) { return (unsigned)((threads + GM_DIST_THREADS - 1) / GM_DIST_THREADS); }
 
-struct dist_call {
-    int32_t max_dist; hipStream_t st;
-    int B; int32_t C;             // the knobs in force
-    gm_nbr_graph G;
-};
+struct dist_call : gm_col_call { int32_t max_dist; };
 
 // the checks both exports share; n == 0 leaves c->B == 0 (nothing to do)
 static int dist_begin(const char* what, const char* cnt_name, const gm_store* s, int32_t g, int64_t n, int32_t flags, int32_t max_dist, const void* d_in, const void* d_out,
                       void* stream, dist_call* c) {
     GM_TRY(gm_store_call_check(what, s, g, cnt_name, n, flags));
     GM_REQUIRE(max_dist >= 1 && max_dist <= 254, GM_EINVAL, "%s: max_dist = %d; 1 .. 254", what, max_dist);
-    const int cols = gm_knob().dist_cols, chunk = gm_knob().dist_chunk;
-    GM_REQUIRE(cols >= 0 && cols % GM_WAVE == 0 && cols <= GM_DIST_MAX_COLS, GM_EINVAL, "%s: dist_cols = %d; a multiple of 64 up to %d (0: the library's choice)", what, cols,
-               GM_DIST_MAX_COLS);
-    GM_REQUIRE(chunk >= 0, GM_EINVAL, "%s: dist_chunk = %d", what, chunk);
-    c->B = 0;
-    if (n == 0) return GM_OK;
-    GM_REQUIRE(d_in && d_out, GM_EINVAL, "%s: NULL argument", what);
-    GM_TRY(gm_nbr_index(s));
-    *c = {max_dist, (hipStream_t)stream, cols ? cols : dist_cols_for(), chunk ? chunk : dist_chunk_for(), gm_nbr_graph_of(s, g)};
-    return GM_OK;
+    c->max_dist = max_dist;
+    return gm_col_setup(what, {gm_knob().dist_cols, "dist_cols", gm_knob().dist_chunk, "dist_chunk", GM_DIST_MAX_COLS, dist_cols_for(), dist_chunk_for()}, s, g, n, d_in, d_out, stream,
+                        c);
 }
-
-// the hub rows of the cut and their segments, on the device
-struct dist_hubs {
-    int64_t n_hubs = 0, n_items = 0;
-    int32_t *row = nullptr, *first = nullptr, *it_row = nullptr, *it_seg = nullptr;
-    uint64_t* part = nullptr;
-};
 
 // one level of a round, F -> next: the rows up to C entries, then the hub rows' segments and the hub rows.  flag: changed + (level - 1)
 template <int L>
-static void dist_level(const dist_call& c, int32_t W, const dist_hubs& H, int32_t* flag, const uint64_t* F, uint64_t* next, uint64_t* seen) {
+static void dist_level(const dist_call& c, int32_t W, const gm_col_hubs<uint64_t>& H, int32_t* flag, const uint64_t* F, uint64_t* next, uint64_t* seen) {
     const dim3 block(GM_DIST_THREADS);
     hipLaunchKernelGGL(k_dist_rows<L>, dim3(dist_grid(c.G.N * L)), block, 0, c.st, c.G, W, c.C, flag, F, next, seen);
     if (!H.n_hubs) return;
@@ -260,34 +235,26 @@ static void dist_level(const dist_call& c, int32_t W, const dist_hubs& H, int32_
                        (const uint64_t*)seen, H.part);
     hipLaunchKernelGGL(k_dist_hubs<L>, dim3(dist_grid(H.n_hubs * L)), block, 0, c.st, W, flag, (const int32_t*)H.row, (const int32_t*)H.first, H.n_hubs, (const uint64_t*)H.part, next, seen);
 }
-typedef void (*dist_level_fn)(const dist_call&, int32_t, const dist_hubs&, int32_t*, const uint64_t*, uint64_t*, uint64_t*);
+typedef void (*dist_level_fn)(const dist_call&, int32_t, const gm_col_hubs<uint64_t>&, int32_t*, const uint64_t*, uint64_t*, uint64_t*);
 // the instantiation whose group of lanes holds the W words of a row
 static dist_level_fn dist_level_for(int32_t W) {
     return W <= 1 ? dist_level<1> : W <= 2 ? dist_level<2> : W <= 4 ? dist_level<4> : W <= 8 ? dist_level<8> : W <= 16 ? dist_level<16> : W <= 32 ? dist_level<32> : dist_level<64>;
 }
 
-// The search of the columns (cs[k], cx[k]), ascending, in rounds of at most B: behind every level t = 0 .. max_dist of a round emit(t, c0, Br, next, flag) reads
-// the level's new bits next[N, Br / 64] of the columns c0 .. c0 + Br on the call's stream; flag[0] == 0 on the device says that the level found none.
-// h_ptr: the graph's row pointers on the host.
+// The search of the plan's columns (cs[k], cx[k]), ascending, in rounds of at most B: behind every level t = 0 .. max_dist of a round emit(t, c0, Br, next, flag)
+// reads the level's new bits next[N, Br / 64] of the columns c0 .. c0 + Br on the call's stream; flag[0] == 0 on the device says that the level found none.
 template <class Emit>
-static int dist_rounds(const char* what, const dist_call& c, const int64_t* h_ptr, const std::vector<int32_t>& cs, const std::vector<int32_t>& cx, gm_stager& sg, Emit emit) {
+static int dist_rounds(const char* what, const dist_call& c, const gm_col_plan& pl, gm_stager& sg, Emit emit) {
     const gm_nbr_graph& G = c.G;
+    const std::vector<int32_t>& cs = pl.cs;
+    const std::vector<int32_t>& cx = pl.cx;
     const int64_t N = G.N, ncols = (int64_t)cs.size(), ncp = (ncols + GM_WAVE - 1) / GM_WAVE * GM_WAVE;
     if (!ncols) return GM_OK;
     const int64_t Bmax = ncp < c.B ? ncp : c.B, Wmax = Bmax / GM_WAVE;
     GM_REQUIRE(N * GM_WAVE / GM_DIST_THREADS < (int64_t)INT32_MAX, GM_ERANGE, "%s: %lld nodes pass the launch's 2^31 workgroups", what, (long long)N);
-    // the hub rows of the cut and their segments
-    std::vector<int32_t> hub_row, hub_first, it_row, it_seg;
-    for (int64_t v = 0; v < N; ++v) {
-        const int64_t deg = h_ptr[v + 1] - h_ptr[v];
-        if (deg <= c.C) continue;
-        hub_row.push_back((int32_t)v); hub_first.push_back((int32_t)it_row.size());
-        for (int64_t seg = 0; seg * c.C < deg; ++seg) { it_row.push_back((int32_t)v); it_seg.push_back((int32_t)seg); }
-        GM_REQUIRE(it_row.size() <= (size_t)(INT32_MAX / GM_WAVE), GM_ERANGE, "%s: more than 2^25 hub segments at dist_chunk = %d", what, (int)c.C);
-    }
-    hub_first.push_back((int32_t)it_row.size());
-    dist_hubs H;
-    H.n_hubs = (int64_t)hub_row.size(); H.n_items = (int64_t)it_row.size();
+    gm_col_hub_lists hl;
+    GM_TRY(gm_col_hub_cut(what, pl.h_ptr, N, c.C, 25, "dist_chunk", &hl));     // (INT32_MAX / GM_WAVE segments)
+    gm_col_hubs<uint64_t> H;
     // the (word, bits) items k_dist_unmask clears behind level 1, round by round: one item per distinct (excluded node, word)
     std::vector<int64_t> un_at, un_first;
     std::vector<uint64_t> un_bits;
@@ -313,11 +280,7 @@ static int dist_rounds(const char* what, const dist_call& c, const int64_t* h_pt
     GM_TRY(sc.take(&changed, (size_t)(c.max_dist + 1)));
     GM_TRY(sc.put(&d_cs, cs, sg));
     GM_TRY(sc.put(&d_un_at, un_at, sg)); GM_TRY(sc.put(&d_un_bits, un_bits, sg));
-    if (H.n_hubs) {
-        GM_TRY(sc.take(&H.part, (size_t)(H.n_items * Wmax)));
-        GM_TRY(sc.put(&H.row, hub_row, sg)); GM_TRY(sc.put(&H.first, hub_first, sg));
-        GM_TRY(sc.put(&H.it_row, it_row, sg)); GM_TRY(sc.put(&H.it_seg, it_seg, sg));
-    }
+    GM_TRY(gm_col_hubs_put(&H, hl, Wmax, sc, sg));
     const dim3 block(GM_DIST_THREADS);
     int64_t round = 0;
     for (int64_t c0 = 0; c0 < ncp; c0 += c.B, ++round) {
@@ -357,26 +320,15 @@ extern "C" int32_t gm_store_node_distances(const gm_store_t* s, int32_t g, const
     if (!c.B) return GM_OK;
     const int64_t N = c.G.N;
     gm_stager sg(c.st);
-    const int32_t* h_src = sg.download(d_sources, (size_t)m);
-    const int64_t* h_ptr = sg.download(c.G.ptr, (size_t)(N + 1));
-    GM_REQUIRE(h_src && h_ptr, GM_ENOMEM, "%s: pinned staging allocation failed", what);
-    GM_HIP(hipMemsetAsync(d_out, GM_DIST_UNREACHED, (size_t)m * (size_t)N, c.st));
-    GM_HIP(hipStreamSynchronize(c.st));
-    // one entry per output row: the whole-graph column of its source
-    std::vector<int64_t> want((size_t)m, -1);
-    for (int64_t r = 0; r < m; ++r)
-        if (h_src[r] >= 0 && h_src[r] < N) want[(size_t)r] = gm_col_key(h_src[r], -1);
-    gm_col_plan pl;
-    GM_TRY(gm_col_plan_of(what, want, &pl));
-    const std::vector<int32_t>& col = pl.col;
-    const std::vector<int32_t> row(pl.order.begin(), pl.order.end());      // (m <= INT32_MAX output rows)
     gm_scratch sc(c.st);
+    gm_col_plan pl;
     int32_t *d_row = nullptr, *d_col = nullptr;
-    GM_TRY(sc.put(&d_row, row, sg)); GM_TRY(sc.put(&d_col, col, sg));
+    GM_HIP(hipMemsetAsync(d_out, GM_DIST_UNREACHED, (size_t)m * (size_t)N, c.st));      // (ahead of the plan's synchronisation)
+    GM_TRY(gm_col_sources(what, c, d_sources, m, sg, sc, &pl, &d_row, &d_col));
     const int64_t v_tiles = (N + GM_WAVE - 1) / GM_WAVE;
-    return dist_rounds(what, c, h_ptr, pl.cs, pl.cx, sg, [&](int32_t t, int64_t c0, int32_t Br, const uint64_t* next, const int32_t* flag) {
+    return dist_rounds(what, c, pl, sg, [&](int32_t t, int64_t c0, int32_t Br, const uint64_t* next, const int32_t* flag) {
         int64_t lo, hi;
-        gm_col_span(col, c0, Br, false, &lo, &hi);
+        gm_col_span(pl.col, c0, Br, false, &lo, &hi);
         if (hi == lo) return (int)GM_OK;
         const int64_t blocks = v_tiles * (Br / GM_WAVE);
         GM_REQUIRE(blocks <= (int64_t)INT32_MAX, GM_ERANGE, "%s: %lld output tiles in one round", what, (long long)blocks);
@@ -392,44 +344,16 @@ extern "C" int32_t gm_store_pair_distance(const gm_store_t* s, int32_t g, const 
     dist_call c;
     GM_TRY(dist_begin(what, "n", s, g, n, flags, max_dist, d_pairs, d_out, stream, &c));
     if (!c.B) return GM_OK;
-    const int64_t N = c.G.N;
-    const bool mask = (flags & GM_PAIR_MASK_TARGET) != 0;
     gm_scratch sc(c.st);
     gm_stager sg(c.st);
-    uint8_t* d_adj = nullptr;
-    const uint8_t* h_adj = nullptr;
-    if (mask) {
-        GM_TRY(sc.take(&d_adj, (size_t)n));
-        hipLaunchKernelGGL(k_dist_adjacent, dim3(dist_grid(n)), dim3(GM_DIST_THREADS), 0, c.st, c.G, d_pairs, n, d_adj);
-        GM_HIP(hipGetLastError());
-        h_adj = sg.download((const uint8_t*)d_adj, (size_t)n);
-    }
-    const int32_t* h_pairs = sg.download(d_pairs, (size_t)(2 * n));
-    const int64_t* h_ptr = sg.download(c.G.ptr, (size_t)(N + 1));
-    GM_REQUIRE(h_pairs && h_ptr && (!mask || h_adj), GM_ENOMEM, "%s: pinned staging allocation failed", what);
-    GM_HIP(hipMemsetAsync(d_out, GM_DIST_UNREACHED, (size_t)n, c.st));
-    GM_HIP(hipStreamSynchronize(c.st));
-    // one entry per pair: the bit of v in the column (u, x); x = v for a masked adjacent pair, else -1
-    std::vector<int64_t> want((size_t)n, -1);
-    std::vector<int32_t> node((size_t)n, 0);
-    for (int64_t k = 0; k < n; ++k) {
-        const int32_t p = h_pairs[2 * k], q = h_pairs[2 * k + 1];
-        if (p < 0 || p >= N || q < 0 || q >= N) continue;
-        const int32_t u = p < q ? p : q, v = p < q ? q : p;
-        want[(size_t)k] = gm_col_key(u, mask && h_adj[k] ? v : -1); node[(size_t)k] = v;
-    }
-    gm_col_plan pl;
-    GM_TRY(gm_col_plan_of(what, want, &pl));
-    const std::vector<int32_t>& col = pl.col;
-    const std::vector<int64_t>& dst = pl.order;
-    std::vector<int32_t> nd((size_t)n);
-    for (size_t e = 0; e < dst.size(); ++e) nd[e] = node[(size_t)dst[e]];
+    gm_col_plan pl;                                                        // one entry per pair: the bit of v in the column of u
     int64_t* d_dst = nullptr;
     int32_t *d_node = nullptr, *d_col = nullptr;
-    GM_TRY(sc.put(&d_dst, dst, sg)); GM_TRY(sc.put(&d_node, nd, sg)); GM_TRY(sc.put(&d_col, col, sg));
-    return dist_rounds(what, c, h_ptr, pl.cs, pl.cx, sg, [&](int32_t t, int64_t c0, int32_t Br, const uint64_t* next, const int32_t* flag) {
+    GM_HIP(hipMemsetAsync(d_out, GM_DIST_UNREACHED, (size_t)n, c.st));     // (ahead of the plan's synchronisation)
+    GM_TRY(gm_col_pairs(what, c, d_pairs, n, (flags & GM_PAIR_MASK_TARGET) != 0, false, sg, sc, &pl, &d_dst, &d_node, &d_col));
+    return dist_rounds(what, c, pl, sg, [&](int32_t t, int64_t c0, int32_t Br, const uint64_t* next, const int32_t* flag) {
         int64_t lo, hi;
-        gm_col_span(col, c0, Br, false, &lo, &hi);
+        gm_col_span(pl.col, c0, Br, false, &lo, &hi);
         if (hi == lo) return (int)GM_OK;
         hipLaunchKernelGGL(k_dist_probe, dim3(dist_grid(hi - lo)), dim3(GM_DIST_THREADS), 0, c.st, next, Br / GM_WAVE, c0, flag, (const int64_t*)d_dst + lo, (const int32_t*)d_node + lo,
                            (const int32_t*)d_col + lo, hi - lo, t, d_out);

@@ -3,7 +3,7 @@
 // (nbr_index.hip; gm_nbr.h):
 //   columns     a column is a pair (s, x): the walk from s in the graph without the edge {s, x} (x = -1: the whole graph).  The host reads the sources or pairs
 //               back once, forms the DISTINCT columns in ascending (s, x) order and runs them in rounds of at most B (gm_set_tuning("ppr_cols")); with the mask
-//               flag only adjacent pairs get a column of their own (adjacency: k_ppr_adjacent, before the read-back).
+//               flag only adjacent pairs get a column of their own.  The call's frame -- knob checks, read-back and plan, adjacency, hub cut -- is gm_columns.h.
 //   the state   Q[N, B] fp32, row-major: p_t[z] / deg' z, pre-scaled per column (a row without neighbours keeps p_t[z] itself), so that a step of the walk is
 //               one load and one add per neighbour.  Two buffers swap between iterations; the last iteration stores p itself.
 //   one row     a wave takes a row v and a slab of 64 columns: lanes are columns, the neighbour id is wave-uniform (scalar loads), and every neighbour costs one
@@ -19,7 +19,6 @@
 // stream; scratch comes from the stream-ordered pool.
 #include <math.h>
 #include "gm_columns.h"
-#include "gm_nbr.h"
 
 #define GM_PPR_THREADS 256
 #define GM_PPR_WAVES (GM_PPR_THREADS / GM_WAVE)
@@ -171,13 +170,6 @@ __global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_entries_out(const float*
     out[dst[e]] = c >= 0 ? P[(int64_t)node[e] * B + (c - c0)] : 0.f;
 }
 
-// adj[k] = 1 where the two nodes of pair k are distinct, inside the graph and neighbours (the pairs whose masked columns differ from the unmasked ones)
-__global__ void __launch_bounds__(GM_PPR_THREADS) k_ppr_adjacent(gm_nbr_graph G, const int32_t* __restrict__ pairs, int64_t n, uint8_t* __restrict__ adj) {
-    const int64_t k = (int64_t)blockIdx.x * GM_PPR_THREADS + threadIdx.x;
-    if (k >= n) return;
-    adj[k] = gm_nbr_adjacent(G, pairs[2 * k], pairs[2 * k + 1]) ? 1 : 0;
-}
-
 // Columns per round and entries per hub segment, from the sweep at the arxiv shape (profiles/pair_pagerank.txt).  Wider rounds are faster as long as there are
 // columns to fill them (1,024 sources: 37.4 / 33.0 / 31.3 ms at 64 / 128 / 256 columns); a round is never wider than the call's columns.  The cut has to be ONE
 // value, whatever the round holds: the order of a row sum, hence the bits, belong to it.  Segments of 64 and 256 level everywhere; a round of one slab gains most
@@ -188,40 +180,21 @@ static int32_t ppr_chunk_for() { return 256; }
 
 static unsigned ppr_grid(int64_t waves) { return (unsigned)((waves + GM_PPR_WAVES - 1) / GM_PPR_WAVES); }
 
-struct ppr_call {
-    float alpha; int32_t iters; hipStream_t st;
-    int B; int32_t C;             // the knobs in force
-    gm_nbr_graph G;
-};
+struct ppr_call : gm_col_call { float alpha; int32_t iters; };
 
-// the checks both exports share; n == 0 leaves c->B == 0 (nothing to do)
+// the checks the exports share; n == 0 leaves c->B == 0 (nothing to do)
 static int ppr_begin(const char* what, const char* cnt_name, const gm_store* s, int32_t g, int64_t n, int32_t flags, float alpha, int32_t iters, const void* d_in, const void* d_out,
                      void* stream, ppr_call* c) {
     GM_TRY(gm_store_call_check(what, s, g, cnt_name, n, flags));
     GM_REQUIRE(isfinite(alpha) && alpha > 0.f && alpha < 1.f, GM_EINVAL, "%s: alpha = %g; 0 < alpha < 1", what, (double)alpha);
     GM_REQUIRE(iters >= 1 && iters <= 255, GM_EINVAL, "%s: iters = %d; 1 .. 255", what, iters);
-    const int cols = gm_knob().ppr_cols, chunk = gm_knob().ppr_chunk;
-    GM_REQUIRE(cols >= 0 && cols % GM_WAVE == 0 && cols <= GM_PPR_MAX_COLS, GM_EINVAL, "%s: ppr_cols = %d; a multiple of 64 up to %d (0: the library's choice)", what, cols,
-               GM_PPR_MAX_COLS);
-    GM_REQUIRE(chunk >= 0, GM_EINVAL, "%s: ppr_chunk = %d", what, chunk);
-    c->B = 0;
-    if (n == 0) return GM_OK;
-    GM_REQUIRE(d_in && d_out, GM_EINVAL, "%s: NULL argument", what);
-    GM_TRY(gm_nbr_index(s));
-    *c = {alpha, iters, (hipStream_t)stream, cols ? cols : ppr_cols_for(), chunk ? chunk : ppr_chunk_for(), gm_nbr_graph_of(s, g)};
-    return GM_OK;
+    c->alpha = alpha; c->iters = iters;
+    return gm_col_setup(what, {gm_knob().ppr_cols, "ppr_cols", gm_knob().ppr_chunk, "ppr_chunk", GM_PPR_MAX_COLS, ppr_cols_for(), ppr_chunk_for()}, s, g, n, d_in, d_out, stream, c);
 }
-
-// the hub rows of the cut and their segments, on the device
-struct ppr_hubs {
-    int64_t n_hubs = 0, n_items = 0;
-    int32_t *row = nullptr, *first = nullptr, *it_row = nullptr, *it_seg = nullptr;
-    float* part = nullptr;
-};
 
 // one iteration of a round's walk, src -> dst: the rows up to C entries, then the hub rows' segments and the hub rows
 template <bool MASK>
-static void ppr_iterate(const ppr_call& c, const ppr_cols& K, const ppr_hubs& H, int last, const float* src, float* dst) {
+static void ppr_iterate(const ppr_call& c, const ppr_cols& K, const gm_col_hubs<float>& H, int last, const float* src, float* dst) {
     const int32_t slabs = K.B / GM_WAVE;
     const float a = c.alpha, b = 1.0f - a;
     const dim3 block(GM_PPR_THREADS), rows(ppr_grid(c.G.N * slabs)), parts(ppr_grid(H.n_items * slabs)), hubs(ppr_grid(H.n_hubs * slabs));
@@ -231,28 +204,20 @@ static void ppr_iterate(const ppr_call& c, const ppr_cols& K, const ppr_hubs& H,
     hipLaunchKernelGGL(k_ppr_hubs<MASK>, hubs, block, 0, c.st, c.G, K, slabs, (const int32_t*)H.row, (const int32_t*)H.first, H.n_hubs, a, b, last, (const float*)H.part, src, dst);
 }
 
-// The walk of the columns (cs[k], cx[k]), ascending, in rounds of at most B: after a round's last iteration emit(c0, Br, P) reads P[N, Br] = p of the
+// The walk of the plan's columns (cs[k], cx[k]), ascending, in rounds of at most B: after a round's last iteration emit(c0, Br, P) reads P[N, Br] = p of the
 // columns c0 .. c0 + Br on the call's stream (Br == 0, P == NULL: a call without a single column); P is the round's scratch, dead behind the emit, which may
-// write to it.  h_ptr: the graph's row pointers on the host.
+// write to it.
 template <class Emit>
-static int ppr_rounds(const char* what, const ppr_call& c, const int64_t* h_ptr, std::vector<int32_t> cs, std::vector<int32_t> cx, gm_stager& sg, Emit emit) {
+static int ppr_rounds(const char* what, const ppr_call& c, const gm_col_plan& pl, gm_stager& sg, Emit emit) {
     const gm_nbr_graph& G = c.G;
+    std::vector<int32_t> cs(pl.cs), cx(pl.cx);
     const int64_t N = G.N, ncols = (int64_t)cs.size(), ncp = (ncols + GM_WAVE - 1) / GM_WAVE * GM_WAVE;
     cs.resize((size_t)ncp, -1); cx.resize((size_t)ncp, -1);
     const int64_t Bmax = ncp < c.B ? ncp : c.B;
     GM_REQUIRE(N * (Bmax / GM_WAVE + 1) <= (int64_t)INT32_MAX, GM_ERANGE, "%s: %lld nodes x %lld columns per round pass the launch's 2^31 waves", what, (long long)N, (long long)Bmax);
-    // the hub rows of the cut and their segments
-    std::vector<int32_t> hub_row, hub_first, it_row, it_seg;
-    for (int64_t v = 0; v < N; ++v) {
-        const int64_t deg = h_ptr[v + 1] - h_ptr[v];
-        if (deg <= c.C) continue;
-        hub_row.push_back((int32_t)v); hub_first.push_back((int32_t)it_row.size());
-        for (int64_t seg = 0; seg * c.C < deg; ++seg) { it_row.push_back((int32_t)v); it_seg.push_back((int32_t)seg); }
-        GM_REQUIRE(it_row.size() <= (size_t)(INT32_MAX / 2), GM_ERANGE, "%s: more than 2^30 hub segments at ppr_chunk = %d", what, (int)c.C);
-    }
-    hub_first.push_back((int32_t)it_row.size());
-    ppr_hubs H;
-    H.n_hubs = (int64_t)hub_row.size(); H.n_items = (int64_t)it_row.size();
+    gm_col_hub_lists hl;
+    GM_TRY(gm_col_hub_cut(what, pl.h_ptr, N, c.C, 30, "ppr_chunk", &hl));      // (INT32_MAX / 2 segments)
+    gm_col_hubs<float> H;
 
     gm_scratch sc(c.st);
     float *Qa = nullptr, *Qb = nullptr;
@@ -260,11 +225,7 @@ static int ppr_rounds(const char* what, const ppr_call& c, const int64_t* h_ptr,
     if (ncols) {
         GM_TRY(sc.take(&Qa, (size_t)(N * Bmax))); GM_TRY(sc.take(&Qb, (size_t)(N * Bmax)));
         GM_TRY(sc.put(&d_cs, cs, sg)); GM_TRY(sc.put(&d_cx, cx, sg));
-        if (H.n_hubs) {
-            GM_TRY(sc.take(&H.part, (size_t)(H.n_items * Bmax)));
-            GM_TRY(sc.put(&H.row, hub_row, sg)); GM_TRY(sc.put(&H.first, hub_first, sg));
-            GM_TRY(sc.put(&H.it_row, it_row, sg)); GM_TRY(sc.put(&H.it_seg, it_seg, sg));
-        }
+        GM_TRY(gm_col_hubs_put(&H, hl, Bmax, sc, sg));
     }
     for (int64_t c0 = 0; c0 == 0 || c0 < ncp; c0 += c.B) {
         const int32_t Br = (int32_t)(ncp - c0 < c.B ? ncp - c0 : c.B);
@@ -295,25 +256,14 @@ extern "C" int32_t gm_store_rooted_pagerank(const gm_store_t* s, int32_t g, cons
     if (!c.B) return GM_OK;
     const int64_t N = c.G.N;
     gm_stager sg(c.st);
-    const int32_t* h_src = sg.download(d_sources, (size_t)m);
-    const int64_t* h_ptr = sg.download(c.G.ptr, (size_t)(N + 1));
-    GM_REQUIRE(h_src && h_ptr, GM_ENOMEM, "%s: pinned staging allocation failed", what);
-    GM_HIP(hipStreamSynchronize(c.st));
-    // one entry per output row: the whole-graph column of its source
-    std::vector<int64_t> want((size_t)m, -1);
-    for (int64_t r = 0; r < m; ++r)
-        if (h_src[r] >= 0 && h_src[r] < N) want[(size_t)r] = gm_col_key(h_src[r], -1);
-    gm_col_plan pl;
-    GM_TRY(gm_col_plan_of(what, want, &pl));
-    const std::vector<int32_t>& col = pl.col;
-    const std::vector<int32_t> row(pl.order.begin(), pl.order.end());      // (m <= INT32_MAX output rows)
     gm_scratch sc(c.st);
+    gm_col_plan pl;
     int32_t *d_row = nullptr, *d_col = nullptr;
-    GM_TRY(sc.put(&d_row, row, sg)); GM_TRY(sc.put(&d_col, col, sg));
+    GM_TRY(gm_col_sources(what, c, d_sources, m, sg, sc, &pl, &d_row, &d_col));
     const int64_t v_tiles = (N + GM_PPR_TILE - 1) / GM_PPR_TILE;
-    return ppr_rounds(what, c, h_ptr, pl.cs, pl.cx, sg, [&](int64_t c0, int32_t Br, const float* P) {
+    return ppr_rounds(what, c, pl, sg, [&](int64_t c0, int32_t Br, const float* P) {
         int64_t lo, hi;
-        gm_col_span(col, c0, Br, true, &lo, &hi);
+        gm_col_span(pl.col, c0, Br, true, &lo, &hi);
         if (hi == lo) return (int)GM_OK;
         const int64_t blocks = v_tiles * ((hi - lo + GM_PPR_TILE - 1) / GM_PPR_TILE);
         GM_REQUIRE(blocks <= (int64_t)INT32_MAX, GM_ERANGE, "%s: %lld output tiles in one round", what, (long long)blocks);
@@ -329,45 +279,15 @@ extern "C" int32_t gm_store_pair_pagerank(const gm_store_t* s, int32_t g, const 
     ppr_call c;
     GM_TRY(ppr_begin(what, "n", s, g, n, flags, alpha, iters, d_pairs, d_out, stream, &c));
     if (!c.B) return GM_OK;
-    const int64_t N = c.G.N;
-    const bool mask = (flags & GM_PAIR_MASK_TARGET) != 0;
     gm_scratch sc(c.st);
     gm_stager sg(c.st);
-    uint8_t* d_adj = nullptr;
-    const uint8_t* h_adj = nullptr;
-    if (mask) {
-        GM_TRY(sc.take(&d_adj, (size_t)n));
-        hipLaunchKernelGGL(k_ppr_adjacent, dim3((unsigned)((n + GM_PPR_THREADS - 1) / GM_PPR_THREADS)), dim3(GM_PPR_THREADS), 0, c.st, c.G, d_pairs, n, d_adj);
-        GM_HIP(hipGetLastError());
-        h_adj = sg.download((const uint8_t*)d_adj, (size_t)n);
-    }
-    const int32_t* h_pairs = sg.download(d_pairs, (size_t)(2 * n));
-    const int64_t* h_ptr = sg.download(c.G.ptr, (size_t)(N + 1));
-    GM_REQUIRE(h_pairs && h_ptr && (!mask || h_adj), GM_ENOMEM, "%s: pinned staging allocation failed", what);
-    GM_HIP(hipStreamSynchronize(c.st));
-    // entry 2k: pi of the column (u, x)[v]; entry 2k + 1: pi of the column (v, x')[u]; x, x' = the other endpoint for a masked adjacent pair, else -1
-    std::vector<int64_t> want((size_t)(2 * n), -1);
-    std::vector<int32_t> node((size_t)(2 * n), 0);
-    for (int64_t k = 0; k < n; ++k) {
-        const int32_t p = h_pairs[2 * k], q = h_pairs[2 * k + 1];
-        if (p < 0 || p >= N || q < 0 || q >= N) continue;
-        const int32_t u = p < q ? p : q, v = p < q ? q : p;
-        const bool cut = mask && h_adj[k];
-        want[(size_t)(2 * k)] = gm_col_key(u, cut ? v : -1); node[(size_t)(2 * k)] = v;
-        want[(size_t)(2 * k + 1)] = gm_col_key(v, cut ? u : -1); node[(size_t)(2 * k + 1)] = u;
-    }
-    gm_col_plan pl;
-    GM_TRY(gm_col_plan_of(what, want, &pl));
-    const std::vector<int32_t>& col = pl.col;
-    const std::vector<int64_t>& dst = pl.order;
-    std::vector<int32_t> nd((size_t)(2 * n));
-    for (size_t e = 0; e < dst.size(); ++e) nd[e] = node[(size_t)dst[e]];
+    gm_col_plan pl;                                                        // two entries per pair: pi of v from u, pi of u from v
     int64_t* d_dst = nullptr;
     int32_t *d_node = nullptr, *d_col = nullptr;
-    GM_TRY(sc.put(&d_dst, dst, sg)); GM_TRY(sc.put(&d_node, nd, sg)); GM_TRY(sc.put(&d_col, col, sg));
-    return ppr_rounds(what, c, h_ptr, pl.cs, pl.cx, sg, [&](int64_t c0, int32_t Br, const float* P) {
+    GM_TRY(gm_col_pairs(what, c, d_pairs, n, (flags & GM_PAIR_MASK_TARGET) != 0, true, sg, sc, &pl, &d_dst, &d_node, &d_col));
+    return ppr_rounds(what, c, pl, sg, [&](int64_t c0, int32_t Br, const float* P) {
         int64_t lo, hi;
-        gm_col_span(col, c0, Br, true, &lo, &hi);
+        gm_col_span(pl.col, c0, Br, true, &lo, &hi);
         if (hi == lo) return (int)GM_OK;
         hipLaunchKernelGGL(k_ppr_entries_out, dim3((unsigned)((hi - lo + GM_PPR_THREADS - 1) / GM_PPR_THREADS)), dim3(GM_PPR_THREADS), 0, c.st, P, Br, c0,
                            (const int64_t*)d_dst + lo, (const int32_t*)d_node + lo, (const int32_t*)d_col + lo, hi - lo, d_out);
@@ -386,34 +306,23 @@ extern "C" int32_t gm_store_pagerank_candidates(const gm_store_t* s, int32_t g, 
     GM_REQUIRE(k >= 1 && k <= GM_CAND_MAX_K, GM_EINVAL, "%s: k = %d; 1 .. %d", what, k, GM_CAND_MAX_K);
     if (!c.B) return GM_OK;
     GM_REQUIRE(d_out_scores && d_out_total, GM_EINVAL, "%s: NULL argument", what);
-    const int64_t N = c.G.N;                                                // (node ids are int32 in the keys: ppr_rounds holds N below 2^31)
     gm_phase_timer tm("pagerank candidates");
     const bool timed = gm_knob().timing != 0;
     gm_stager sg(c.st);
-    const int32_t* h_src = sg.download(d_nodes, (size_t)m);
-    const int64_t* h_ptr = sg.download(c.G.ptr, (size_t)(N + 1));
-    GM_REQUIRE(h_src && h_ptr, GM_ENOMEM, "%s: pinned staging allocation failed", what);
-    GM_HIP(hipStreamSynchronize(c.st));
-    // one entry per output row: the whole-graph column of its source
-    std::vector<int64_t> want((size_t)m, -1);
-    for (int64_t r = 0; r < m; ++r)
-        if (h_src[r] >= 0 && h_src[r] < N) want[(size_t)r] = gm_col_key(h_src[r], -1);
-    gm_col_plan pl;
-    GM_TRY(gm_col_plan_of(what, want, &pl));
-    const std::vector<int32_t>& col = pl.col;
-    const std::vector<int32_t> row(pl.order.begin(), pl.order.end());      // (m <= INT32_MAX output rows)
+    gm_scratch sc(c.st);
+    gm_col_plan pl;                                                        // (node ids are int32 in the keys: ppr_rounds holds N below 2^31)
+    int32_t *d_row = nullptr, *d_col = nullptr, *d_src = nullptr;
+    GM_TRY(gm_col_sources(what, c, d_nodes, m, sg, sc, &pl, &d_row, &d_col));
     const int64_t ncp = ((int64_t)pl.cs.size() + GM_WAVE - 1) / GM_WAVE * GM_WAVE;
     std::vector<int32_t> src(pl.cs);
     src.resize((size_t)ncp, -1);                                           // (as ppr_rounds pads its columns)
-    gm_scratch sc(c.st);
-    int32_t *d_row = nullptr, *d_col = nullptr, *d_src = nullptr;
-    GM_TRY(sc.put(&d_row, row, sg)); GM_TRY(sc.put(&d_col, col, sg)); GM_TRY(sc.put(&d_src, src, sg));
+    GM_TRY(sc.put(&d_src, src, sg));
     gm_pprc sel;
     GM_TRY(gm_pprc_prepare(&sel, sc, (int32_t)(ncp < c.B ? ncp : c.B), k, c.st));
     if (timed) { GM_HIP(hipStreamSynchronize(c.st)); tm.lap("plan"); }
-    return ppr_rounds(what, c, h_ptr, pl.cs, pl.cx, sg, [&](int64_t c0, int32_t Br, float* P) {
+    return ppr_rounds(what, c, pl, sg, [&](int64_t c0, int32_t Br, float* P) {
         int64_t lo, hi;
-        gm_col_span(col, c0, Br, true, &lo, &hi);
+        gm_col_span(pl.col, c0, Br, true, &lo, &hi);
         return gm_pprc_round(sel, c.G, P, Br, (const int32_t*)d_src + c0, (const int32_t*)d_row + lo, (const int32_t*)d_col + lo, c0, hi - lo, d_out_nodes, d_out_scores,
                              d_out_total, timed ? &tm : nullptr);
     });

@@ -126,6 +126,36 @@ class GraphStore:
             _lib.check(getattr(_lib.lib(), name)(self.handle, g, _lib.ptr(d_p), len(p), *tail, _lib.ptr(out), _lib.stream_ptr()), name)
         return out.cpu().numpy()
 
+    def _source_call(self, name, g, a, dtype, *tail):
+        """The export `name` over the m sources `a` of graph `g`: the sources as int32 on the device, the [m, N] result of `dtype` allocated there, the call
+        (store, graph, sources, m, *tail, result, stream; skipped for m == 0), the result brought back as a numpy array."""
+        import torch
+        out = torch.empty((len(a), self.n_nodes[g]), dtype=dtype, device='cuda')
+        if len(a):
+            d_a = torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
+            _lib.check(getattr(_lib.lib(), name)(self.handle, g, _lib.ptr(d_a), len(a), *tail, _lib.ptr(out), _lib.stream_ptr()), name)
+        return out.cpu().numpy()
+
+    @staticmethod
+    def _k_of(k, what):
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError('%s: k = %d; 1 .. 1024' % (what, k))
+        return k
+
+    def _topk_call(self, name, g, a, k, *tail):
+        """The export `name` over the m nodes `a` of graph `g`: the call (store, graph, nodes, m, k, *tail, partners, scores, totals, stream; skipped for
+        m == 0) -> (partners int64 [m, k], scores float32 [m, k], totals int64 [m])."""
+        import torch
+        m = len(a)
+        part = torch.empty((m, k), dtype=torch.int32, device='cuda')
+        sc = torch.empty((m, k), dtype=torch.float32, device='cuda')
+        tot = torch.empty(m, dtype=torch.int32, device='cuda')
+        if m:
+            d_a = torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
+            _lib.check(getattr(_lib.lib(), name)(self.handle, g, _lib.ptr(d_a), m, k, *tail, _lib.ptr(part), _lib.ptr(sc), _lib.ptr(tot), _lib.stream_ptr()), name)
+        return part.cpu().numpy().astype(np.int64), sc.cpu().numpy(), tot.cpu().numpy().astype(np.int64)
+
     def negative_pairs(self, g, n, seed=222, mode='uniform', exclude=None):
         """`n` distinct node pairs (u < v) of graph `g` with no edge between them in either direction, drawn on the device: int64 [n, 2], in the order
         include/gmeta_hip.h defines (gm_store_negative_pairs: a function of the graph, seed, mode, exclusion list and n alone; tests/negative_ref.py
@@ -191,12 +221,7 @@ class GraphStore:
         import torch
         alpha, iters = self._walk_of(alpha, iters, 'rooted_pagerank')
         g, a = self._nodes_of(g, sources, 'rooted_pagerank')
-        out = torch.empty((len(a), self.n_nodes[g]), dtype=torch.float32, device='cuda')
-        if len(a):
-            d_a = torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
-            _lib.check(_lib.lib().gm_store_rooted_pagerank(self.handle, g, _lib.ptr(d_a), len(a), alpha, iters, _lib.ptr(out), _lib.stream_ptr()),
-                       'gm_store_rooted_pagerank')
-        return out.cpu().numpy()
+        return self._source_call('gm_store_rooted_pagerank', g, a, torch.float32, alpha, iters)
 
     def pair_pagerank(self, g, pairs, mask_target=False, alpha=0.15, iters=20):
         """float32 [m, 2]: for each of the [m, 2] node `pairs` of graph `g`, canonicalised to (u, v) = (min, max), the rooted PageRank of v seen from u and of
@@ -222,12 +247,7 @@ class GraphStore:
         import torch
         max_dist = self._max_dist_of(max_dist, 'node_distances')
         g, a = self._nodes_of(g, sources, 'node_distances')
-        out = torch.empty((len(a), self.n_nodes[g]), dtype=torch.uint8, device='cuda')
-        if len(a):
-            d_a = torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
-            _lib.check(_lib.lib().gm_store_node_distances(self.handle, g, _lib.ptr(d_a), len(a), max_dist, _lib.ptr(out), _lib.stream_ptr()),
-                       'gm_store_node_distances')
-        return out.cpu().numpy()
+        return self._source_call('gm_store_node_distances', g, a, torch.uint8, max_dist)
 
     def pair_distance(self, g, pairs, mask_target=False, max_dist=8):
         """uint8 [m]: the shortest-path distance between the two nodes of each of the [m, 2] `pairs` of graph `g` (node_distances' entries), searched on
@@ -257,20 +277,9 @@ class GraphStore:
         from .heuristics import PAIR_SCORES
         if score not in PAIR_SCORES:
             raise ValueError('link_candidates: score must be one of %s, not %r' % (', '.join(PAIR_SCORES), score))
-        k = int(k)
-        if not 1 <= k <= 1024:
-            raise ValueError('link_candidates: k = %d; 1 .. 1024' % k)
-        import torch
+        k = self._k_of(k, 'link_candidates')
         g, a = self._nodes_of(g, nodes, 'link_candidates')
-        m = len(a)
-        part = torch.empty((m, k), dtype=torch.int32, device='cuda')
-        sc = torch.empty((m, k), dtype=torch.float32, device='cuda')
-        tot = torch.empty(m, dtype=torch.int32, device='cuda')
-        if m:
-            d_a = torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
-            _lib.check(_lib.lib().gm_store_pair_candidates(self.handle, g, _lib.ptr(d_a), m, k, PAIR_SCORES.index(score), _lib.ptr(part), _lib.ptr(sc), _lib.ptr(tot),
-                                                           _lib.stream_ptr()), 'gm_store_pair_candidates')
-        return part.cpu().numpy().astype(np.int64), sc.cpu().numpy(), tot.cpu().numpy().astype(np.int64)
+        return self._topk_call('gm_store_pair_candidates', g, a, k, PAIR_SCORES.index(score))
 
     def pagerank_candidates(self, g, nodes, k=10, alpha=0.15, iters=20):
         """Candidate partners of the `nodes` of graph `g` by the global score: per node the non-adjacent nodes with positive rooted-PageRank mass seen from
@@ -279,21 +288,10 @@ class GraphStore:
         include/gmeta_hip.h, tests/pagerank_candidate_ref.py restates it).  Unlike link_candidates it reaches every node within `iters` steps.
         -> (partners int64 [m, k], scores float32 [m, k], totals int64 [m]), laid out as link_candidates lays them out: gmeta_amd.candidate_names takes the
         partners.  The score is one-directional; pair_pagerank rescores a shortlist symmetrically."""
-        k = int(k)
-        if not 1 <= k <= 1024:
-            raise ValueError('pagerank_candidates: k = %d; 1 .. 1024' % k)
+        k = self._k_of(k, 'pagerank_candidates')
         alpha, iters = self._walk_of(alpha, iters, 'pagerank_candidates')
-        import torch
         g, a = self._nodes_of(g, nodes, 'pagerank_candidates')
-        m = len(a)
-        part = torch.empty((m, k), dtype=torch.int32, device='cuda')
-        sc = torch.empty((m, k), dtype=torch.float32, device='cuda')
-        tot = torch.empty(m, dtype=torch.int32, device='cuda')
-        if m:
-            d_a = torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
-            _lib.check(_lib.lib().gm_store_pagerank_candidates(self.handle, g, _lib.ptr(d_a), m, k, alpha, iters, _lib.ptr(part), _lib.ptr(sc), _lib.ptr(tot),
-                                                               _lib.stream_ptr()), 'gm_store_pagerank_candidates')
-        return part.cpu().numpy().astype(np.int64), sc.cpu().numpy(), tot.cpu().numpy().astype(np.int64)
+        return self._topk_call('gm_store_pagerank_candidates', g, a, k, alpha, iters)
 
     def close(self):
         if getattr(self, 'handle', None):
