@@ -11,7 +11,7 @@ GM_MAX_GCN = 4
 LINK_SYMMETRIC = 2      # GM_LINK_SYMMETRIC: the link_pred mode of gm_extract / gm_extract_pair with h hops around both endpoints
 LINK_MASK_TARGET = 4    # GM_LINK_MASK_TARGET: flag OR-ed onto a pair mode -- the subgraph of (i, j) is built without the i-j edges themselves
 NEG_MODES = {'uniform': 0, 'two_hop': 1}      # GM_NEG_UNIFORM / GM_NEG_TWO_HOP (gm_store_negative_pairs)
-PAIR_MASK_TARGET = 1    # GM_PAIR_MASK_TARGET: flag of gm_store_pair_scores / gm_store_pair_walks / gm_store_pair_pagerank / gm_store_pair_distance -- the pair is scored as if no edge joined its two nodes
+PAIR_MASK_TARGET = 1    # GM_PAIR_MASK_TARGET: flag of gm_store_pair_scores / gm_store_pair_walks / gm_store_pair_pagerank / gm_store_pair_distance / gm_store_pair_distance_profile -- the pair is scored as if no edge joined its two nodes
 DIST_UNREACHED = 255    # GM_DIST_UNREACHED: the byte of gm_store_node_distances / gm_store_pair_distance for a node no path of at most max_dist edges reaches
 
 
@@ -46,6 +46,7 @@ PROTOTYPES = {
     'gm_store_pagerank_candidates': (i32, [vp, i32, vp, i64, i32, C.c_float, i32, vp, vp, vp, vp]),
     'gm_store_node_distances': (i32, [vp, i32, vp, i64, i32, vp, vp]),
     'gm_store_pair_distance': (i32, [vp, i32, vp, i64, i32, i32, vp, vp]),
+    'gm_store_pair_distance_profile': (i32, [vp, i32, vp, i64, i32, i32, vp, vp]),
     'gm_store_neighbour_degrees': (i32, [vp, i32, vp, vp]),
     'gm_store_pair_candidates': (i32, [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp]),
     'gm_extract': (C.c_int, [vp, vp, i32, vp, i32, i32, i32, u64, i32, vp, vp]),

@@ -11,7 +11,7 @@ OUT = os.path.join(HERE, 'libgmeta_hip.so')
 SOURCES = ['common.hip', 'store.hip', 'batch.hip', 'extract.hip', 'agg.hip', 'agg_stream.hip', 'gemm.hip', 'model.hip', 'cone.hip', 'dense_exports.hip', 'negatives.hip', 'nbr_index.hip', 'pair_scores.hip']
 SOURCES += ['candidates.hip']      # reads the neighbour index (nbr_index.hip, gm_nbr.h) and launches the score kernel of pair_scores.hip (gm_internal.h)
 SOURCES += ['pair_pagerank.hip', 'pagerank_candidates.hip']   # rooted PageRank of sources and node pairs over the same neighbour index; the top-k selection on a round's state
-SOURCES += ['pair_distance.hip']   # shortest-path distances of sources and node pairs over the same neighbour index: one bit per (node, column)
+SOURCES += ['pair_distance.hip', 'distance_profile.hip']   # shortest-path distances of sources and node pairs over the same neighbour index: one bit per (node, column); the joint hop-distance tables of pairs on that state
 SOURCES += ['pair_walks.hip']      # walk counts of node pairs over the same neighbour index
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result']
 

@@ -374,6 +374,7 @@ const gm_knobs& gm_knob() {
         k.ppr_cols = env("GM_PPR_COLS", 0);
         k.dist_chunk = env("GM_DIST_CHUNK", 0);
         k.dist_cols = env("GM_DIST_COLS", 0);
+        k.dist_plane_kib = env("GM_DIST_PLANE_KIB", 0);
     });
     return k;
 }
@@ -400,6 +401,7 @@ static int gm_knobs::* gm_find_knob(const char* name) {
         {"ppr_cols", &gm_knobs::ppr_cols}, {"GM_PPR_COLS", &gm_knobs::ppr_cols},
         {"dist_chunk", &gm_knobs::dist_chunk}, {"GM_DIST_CHUNK", &gm_knobs::dist_chunk},
         {"dist_cols", &gm_knobs::dist_cols}, {"GM_DIST_COLS", &gm_knobs::dist_cols},
+        {"dist_plane_kib", &gm_knobs::dist_plane_kib}, {"GM_DIST_PLANE_KIB", &gm_knobs::dist_plane_kib},
     };
     for (const auto& e : tab)
         if (!strcmp(name, e.name)) return e.field;

@@ -3,11 +3,14 @@
 //   the call    gm_col_call: stream, graph and the two knobs in force (columns per round B, entries per hub segment C); gm_col_setup checks the knobs and fills it.
 //   plans       gm_col_plan_of forms the DISTINCT columns of a call's output entries and the order the entries leave in; gm_col_sources (an entry per source)
 //               and gm_col_pairs (one or two entries per pair) read a call's input back, plan it and upload the plan; gm_col_span: the entries of one round.
+//   groups      gm_col_pair_groups cuts a call's pairs (gm_col_pairs_read) into groups of a bounded number of distinct columns, a plan each, for a result
+//               that reads both columns of a pair in one round.
 //   hub cut     gm_col_hub_cut lists the rows of more than C entries and their segments of C; gm_col_hubs_put uploads the lists with a partial buffer.
 //   adjacency   k_col_adjacent: the pairs that get a column of their own under the mask flag.
 // The walks, their rounds and what a round emits stay with the two files.
 #pragma once
 #include <algorithm>
+#include <unordered_set>
 #include <vector>
 #include "gm_nbr.h"
 
@@ -98,24 +101,35 @@ static inline int gm_col_sources(const char* what, const gm_col_call& c, const i
     return sc.put(d_col, P->col, sg);
 }
 
+// A call's n pairs, with `mask` their adjacency bytes (k_col_adjacent; else NULL), and the graph's row pointers, read back into pinned memory of the call's
+// stager behind ONE synchronisation of the stream, as gm_col_sources reads
+struct gm_col_pairs_host { const int32_t* pairs = nullptr; const uint8_t* adj = nullptr; const int64_t* ptr = nullptr; };
+static inline int gm_col_pairs_read(const char* what, const gm_col_call& c, const int32_t* d_pairs, int64_t n, bool mask, gm_stager& sg, gm_scratch& sc, gm_col_pairs_host* R) {
+    uint8_t* d_adj = nullptr;
+    if (mask) {
+        GM_TRY(sc.take(&d_adj, (size_t)n));
+        hipLaunchKernelGGL(k_col_adjacent, dim3((unsigned)((n + GM_COL_THREADS - 1) / GM_COL_THREADS)), dim3(GM_COL_THREADS), 0, c.st, c.G, d_pairs, n, d_adj);
+        GM_HIP(hipGetLastError());
+        R->adj = sg.download((const uint8_t*)d_adj, (size_t)n);
+    }
+    R->pairs = sg.download(d_pairs, (size_t)2 * (size_t)n);
+    R->ptr = sg.download(c.G.ptr, (size_t)(c.G.N + 1));
+    GM_REQUIRE(R->pairs && R->ptr && (!mask || R->adj), GM_ENOMEM, "%s: pinned staging allocation failed", what);
+    GM_HIP(hipStreamSynchronize(c.st));
+    return GM_OK;
+}
+
 // The plan of n pairs, canonicalised to (u, v) = (min, max); x = the other endpoint for an adjacent pair under `mask`, else -1.  With `both`, entry 2k is
 // (u, x)[v] and entry 2k + 1 is (v, x')[u]; without, entry k is (u, x)[v]; a pair with a node outside the graph has no column.  Reads back as gm_col_sources
 // does, the adjacency bytes (k_col_adjacent) first -> d_dst = P->order: where entry i goes, d_node[i]: the node it reads in its column, d_col = P->col
 static inline int gm_col_pairs(const char* what, const gm_col_call& c, const int32_t* d_pairs, int64_t n, bool mask, bool both, gm_stager& sg, gm_scratch& sc, gm_col_plan* P,
                                int64_t** d_dst, int32_t** d_node, int32_t** d_col) {
     const int64_t N = c.G.N;
-    uint8_t* d_adj = nullptr;
-    const uint8_t* h_adj = nullptr;
-    if (mask) {
-        GM_TRY(sc.take(&d_adj, (size_t)n));
-        hipLaunchKernelGGL(k_col_adjacent, dim3((unsigned)((n + GM_COL_THREADS - 1) / GM_COL_THREADS)), dim3(GM_COL_THREADS), 0, c.st, c.G, d_pairs, n, d_adj);
-        GM_HIP(hipGetLastError());
-        h_adj = sg.download((const uint8_t*)d_adj, (size_t)n);
-    }
-    const int32_t* h_pairs = sg.download(d_pairs, (size_t)2 * (size_t)n);
-    P->h_ptr = sg.download(c.G.ptr, (size_t)(N + 1));
-    GM_REQUIRE(h_pairs && P->h_ptr && (!mask || h_adj), GM_ENOMEM, "%s: pinned staging allocation failed", what);
-    GM_HIP(hipStreamSynchronize(c.st));
+    gm_col_pairs_host R;
+    GM_TRY(gm_col_pairs_read(what, c, d_pairs, n, mask, sg, sc, &R));
+    const int32_t* h_pairs = R.pairs;
+    const uint8_t* h_adj = R.adj;
+    P->h_ptr = R.ptr;
     const size_t per = both ? 2 : 1;
     std::vector<int64_t> want(per * (size_t)n, -1);
     std::vector<int32_t> node(per * (size_t)n, 0);
@@ -133,6 +147,55 @@ static inline int gm_col_pairs(const char* what, const gm_col_call& c, const int
     for (size_t e = 0; e < nd.size(); ++e) nd[e] = node[(size_t)P->order[e]];
     GM_TRY(sc.put(d_dst, P->order, sg)); GM_TRY(sc.put(d_node, nd, sg));
     return sc.put(d_col, P->col, sg);
+}
+
+// The pairs of a call whose result needs BOTH columns of a pair, (u, x) and (v, x'), alive in the same round: the canonical pairs sorted by (u, v) and cut
+// greedily into groups of at most B DISTINCT columns each (a pair brings at most two, so any B >= 2 holds every pair).  A group is a plan of its own
+// (plan: its columns, ascending) and the entries [first, first + cnt) of the lists: pair dst[i] of the call reads the columns cu[i], cv[i] of its group's plan.
+// A pair with a node outside the graph is in no group.
+struct gm_col_group { gm_col_plan plan; int64_t first = 0, cnt = 0; };
+struct gm_col_groups {
+    std::vector<gm_col_group> groups;
+    std::vector<int64_t> dst;
+    std::vector<int32_t> cu, cv;
+};
+static inline int gm_col_pair_groups(const char* what, int64_t N, const gm_col_pairs_host& R, int64_t n, bool mask, int64_t B, gm_col_groups* G) {
+    struct item { int32_t u, v; int64_t k; };
+    std::vector<item> items;
+    for (int64_t k = 0; k < n; ++k) {
+        const int32_t p = R.pairs[2 * k], q = R.pairs[2 * k + 1];
+        if (p < 0 || p >= N || q < 0 || q >= N) continue;
+        items.push_back({p < q ? p : q, p < q ? q : p, k});
+    }
+    std::stable_sort(items.begin(), items.end(), [](const item& a, const item& b) { return a.u != b.u ? a.u < b.u : a.v < b.v; });
+    G->dst.resize(items.size()); G->cu.resize(items.size()); G->cv.resize(items.size());
+    std::unordered_set<int64_t> held;                                          // the distinct columns of the open group
+    std::vector<int64_t> want;                                                 // ... and its entries: two per pair
+    size_t first = 0;
+    const auto close = [&](size_t end) -> int {
+        if (end == first) return GM_OK;
+        G->groups.emplace_back();
+        gm_col_group& g = G->groups.back();
+        g.first = (int64_t)first; g.cnt = (int64_t)(end - first); g.plan.h_ptr = R.ptr;
+        GM_TRY(gm_col_plan_of(what, want, &g.plan));
+        for (size_t e = 0; e < want.size(); ++e) {                             // entry order[e] = 2 i (the u side) or 2 i + 1 (the v side) of the group's pair i
+            const size_t at = first + (size_t)(g.plan.order[e] >> 1);
+            (g.plan.order[e] & 1 ? G->cv : G->cu)[at] = g.plan.col[e];
+        }
+        held.clear(); want.clear(); first = end;
+        return GM_OK;
+    };
+    for (size_t i = 0; i < items.size(); ++i) {
+        const item& it = items[i];
+        const bool cut = mask && R.adj[it.k];
+        const int64_t ku = gm_col_key(it.u, cut ? it.v : -1), kv = gm_col_key(it.v, cut ? it.u : -1);
+        const int64_t fresh = (held.count(ku) ? 0 : 1) + (kv != ku && !held.count(kv) ? 1 : 0);
+        if ((int64_t)held.size() + fresh > B) GM_TRY(close(i));
+        held.insert(ku); held.insert(kv);
+        want.push_back(ku); want.push_back(kv);
+        G->dst[i] = it.k;
+    }
+    return close(items.size());
 }
 
 // The hub rows of the cut at C entries and their segments.  Host: row[h] the h-th hub row, first[h] its first item (first[n_hubs]: the number of items),

@@ -266,6 +266,7 @@ struct gm_knobs {
     int ppr_cols;                  // GM_PPR_COLS, gm_set_tuning("ppr_cols"): columns per round of those two calls, a multiple of 64; 0 (default) = the library's choice.  The result does not depend on it
     int dist_chunk;                // GM_DIST_CHUNK, gm_set_tuning("dist_chunk"): entries per segment of a hub row of gm_store_node_distances / gm_store_pair_distance (pair_distance.hip); 0 (default) = the library's choice.  The result does not depend on it
     int dist_cols;                 // GM_DIST_COLS, gm_set_tuning("dist_cols"): columns per round of those two calls, a multiple of 64 up to 4096; 0 (default) = the library's choice.  The result does not depend on it
+    int dist_plane_kib;            // GM_DIST_PLANE_KIB, gm_set_tuning("dist_plane_kib"): KiB of level planes gm_store_pair_distance_profile may hold at a time (pair_distance.hip), which bounds the columns of a group; 0 (default) = the library's choice, 1 GiB.  The result does not depend on it
     int cand_bitmap;               // GM_CAND_BITMAP, gm_set_tuning("cand_bitmap"): home of that call's membership bitmap: 1 LDS, 2 a per-workgroup slab in HBM; 0 (default) = LDS wherever the graph fits.  The result does not depend on it
 };
 const gm_knobs& gm_knob();
@@ -424,6 +425,13 @@ int gm_pprc_prepare(gm_pprc* w, gm_scratch& sc, int32_t Bmax, int32_t k, hipStre
 // (d_col < 0: a source outside the graph).  tm: the phase laps walk / exclusion / select, the stream synchronised behind each (NULL: none)
 int gm_pprc_round(const gm_pprc& w, const gm_nbr_graph& G, float* P, int32_t Br, const int32_t* d_src, const int32_t* d_row, const int32_t* d_col, int64_t c0, int64_t rows,
                   int32_t* d_out_nodes, float* d_out_scores, int32_t* d_out_total, gm_phase_timer* tm);
+
+// ---- the planes and the count of gm_store_pair_distance_profile (distance_profile.hip), run by the export in pair_distance.hip on every level of its search
+// next[N, W]: a level's new bits, one word per (node, 64 columns); flag[0] == 0 on the device: the level found none -> plane[64 W, ceil(N / 64)]: one word per
+// (column, 64 nodes), written where a bit is set (the caller zeroed it)
+int gm_prof_transpose(hipStream_t st, const uint64_t* next, int32_t W, int64_t N, const int32_t* flag, uint64_t* plane);
+// T[D + 1, B, ceil(N / 64)]: the planes of the levels 0 .. D of B columns; entry e = the pair of the columns cu[e], cv[e] -> out[dst[e], D + 2, D + 2]
+int gm_prof_count(hipStream_t st, const uint64_t* T, int32_t D, int64_t B, int64_t N, const int32_t* cu, const int32_t* cv, const int64_t* dst, int64_t cnt, int32_t* out);
 
 // ---- layout helpers
 struct gm_layout {

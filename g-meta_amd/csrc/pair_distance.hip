@@ -31,6 +31,11 @@
 //               LDS (the word IS the transposed tile).  A column serves every duplicate of its source.
 //   scratch     3 N W 8 bytes of state (W = min(B, columns rounded up to 64) / 64: 3 N B / 8), 8 W bytes per hub segment, 4 (max_dist + 1) bytes of flags
 //               and the lists of the columns, hub segments and output entries (4 .. 16 bytes each), from the stream-ordered pool.
+//   profiles    gm_store_pair_distance_profile (at the end of the file) counts, per pair, the nodes a hops from one endpoint and b hops from the other: a third
+//               emit on dist_rounds.  Both columns of a pair must be alive in one round, so the pairs are cut into groups of at most Bp distinct columns
+//               (gm_columns.h: gm_col_pair_groups) and every group is a plan and a single round of its own.  Behind each level the new bits are transposed
+//               into node-major planes, behind the last a wave per pair counts on them (distance_profile.hip); only [n, D + 2, D + 2] integers leave the
+//               device.  Scratch beside the search's: (D + 1) Bp ceil(N / 64) 8 bytes of planes (gm_set_tuning("dist_plane_kib") bounds Bp) and 16 bytes per pair.
 // A result is a function of (graph, source or pair, flags, max_dist) alone.  Everything runs on the caller's stream.
 #include "gm_columns.h"
 
@@ -360,4 +365,78 @@ extern "C" int32_t gm_store_pair_distance(const gm_store_t* s, int32_t g, const 
         GM_HIP(hipGetLastError());
         return (int)GM_OK;
     });
+}
+
+// ---- gm_store_pair_distance_profile: the third emit on dist_rounds (the planes and the count are distance_profile.hip)
+#define GM_DIST_PROFILE_MAX 7             // max_dist of a profile: the range of gm_set_hop_labels, a table of at most 81 entries
+#define GM_DIST_PLANE_KIB (1 << 20)       // the library's budget of level planes: 1 GiB
+
+// GM_TIMING: the three phases of a call, the stream synchronised behind each (tools/distance_profile_bench.py reads the line)
+struct dist_laps {
+    bool on; hipStream_t st; double us[3] = {0, 0, 0};
+    std::chrono::steady_clock::time_point t;
+    explicit dist_laps(hipStream_t s) : on(gm_knob().timing != 0), st(s) { if (on) { (void)hipStreamSynchronize(st); t = std::chrono::steady_clock::now(); } }
+    void lap(int phase) {
+        if (!on) return;
+        (void)hipStreamSynchronize(st);
+        const auto n = std::chrono::steady_clock::now();
+        us[phase] += std::chrono::duration<double, std::micro>(n - t).count();
+        t = n;
+    }
+};
+
+extern "C" int32_t gm_store_pair_distance_profile(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, int32_t max_dist, int32_t* d_out, void* stream) {
+    const char* what = "gm_store_pair_distance_profile";
+    GM_TRY(gm_store_call_check(what, s, g, "n", n, flags));
+    GM_REQUIRE(max_dist >= 1 && max_dist <= GM_DIST_PROFILE_MAX, GM_EINVAL, "%s: max_dist = %d; 1 .. %d", what, max_dist, GM_DIST_PROFILE_MAX);
+    const int kib = gm_knob().dist_plane_kib;
+    GM_REQUIRE(kib >= 0, GM_EINVAL, "%s: dist_plane_kib = %d", what, kib);
+    dist_call c;
+    GM_TRY(dist_begin(what, "n", s, g, n, flags, max_dist, d_pairs, d_out, stream, &c));
+    if (!c.B) return GM_OK;
+    const int64_t N = c.G.N, NW = (N + GM_WAVE - 1) / GM_WAVE, L = max_dist + 1, E = (L + 1) * (L + 1);
+    // the columns of a group: what the search holds in a round, and what the budget holds of planes
+    const int64_t budget = (int64_t)(kib ? kib : GM_DIST_PLANE_KIB) * 1024, per_word = L * GM_WAVE * NW * (int64_t)sizeof(uint64_t);
+    GM_REQUIRE(budget >= per_word, GM_ERANGE, "%s: the level planes of 64 columns take %lld bytes at N = %lld, max_dist = %d; dist_plane_kib = %d holds %lld", what,
+               (long long)per_word, (long long)N, max_dist, kib ? kib : GM_DIST_PLANE_KIB, (long long)budget);
+    const int64_t fit = budget / per_word * GM_WAVE, Bp = fit < c.B ? fit : c.B;
+    gm_scratch sc(c.st);
+    gm_stager sg(c.st);
+    GM_HIP(hipMemsetAsync(d_out, 0, (size_t)n * (size_t)E * sizeof(int32_t), c.st));      // a pair with a node outside the graph (ahead of the read-back's synchronisation)
+    gm_col_pairs_host R;
+    GM_TRY(gm_col_pairs_read(what, c, d_pairs, n, (flags & GM_PAIR_MASK_TARGET) != 0, sg, sc, &R));
+    gm_col_groups G;
+    GM_TRY(gm_col_pair_groups(what, N, R, n, (flags & GM_PAIR_MASK_TARGET) != 0, Bp, &G));
+    if (G.groups.empty()) return GM_OK;
+    int64_t Bmax = 0;                                                          // the widest group, in whole words of columns
+    for (const gm_col_group& gr : G.groups) {
+        const int64_t b = ((int64_t)gr.plan.cs.size() + GM_WAVE - 1) / GM_WAVE * GM_WAVE;
+        Bmax = b > Bmax ? b : Bmax;
+    }
+    uint64_t* T = nullptr;
+    int64_t* d_dst = nullptr;
+    int32_t *d_cu = nullptr, *d_cv = nullptr;
+    GM_TRY(sc.take(&T, (size_t)(L * Bmax * NW)));
+    GM_TRY(sc.put(&d_dst, G.dst, sg)); GM_TRY(sc.put(&d_cu, G.cu, sg)); GM_TRY(sc.put(&d_cv, G.cv, sg));
+    dist_laps laps(c.st);
+    int64_t cols_run = 0;                                                      // the columns searched, padding included: a column may serve pairs of several groups
+    for (const gm_col_group& gr : G.groups) {
+        const int64_t Bg = ((int64_t)gr.plan.cs.size() + GM_WAVE - 1) / GM_WAVE * GM_WAVE;      // one round: Bg <= Bp <= c.B
+        GM_HIP(hipMemsetAsync(T, 0, (size_t)(L * Bg * NW) * sizeof(uint64_t), c.st));
+        cols_run += Bg;
+        GM_TRY(dist_rounds(what, c, gr.plan, sg, [&](int32_t t, int64_t c0, int32_t Br, const uint64_t* next, const int32_t* flag) {
+            GM_REQUIRE(c0 == 0 && Br == Bg, GM_ERANGE, "%s: a group of %lld columns in more than one round", what, (long long)gr.plan.cs.size());
+            laps.lap(0);
+            GM_TRY(gm_prof_transpose(c.st, next, Br / GM_WAVE, N, flag, T + (int64_t)t * Bg * NW));
+            laps.lap(1);
+            return (int)GM_OK;
+        }));
+        laps.lap(0);
+        GM_TRY(gm_prof_count(c.st, T, max_dist, Bg, N, (const int32_t*)d_cu + gr.first, (const int32_t*)d_cv + gr.first, (const int64_t*)d_dst + gr.first, gr.cnt, d_out));
+        laps.lap(2);
+    }
+    if (laps.on)
+        fprintf(stderr, "[gm timing] %s groups %lld columns %lld search %.1f us transpose %.1f us count %.1f us\n", what, (long long)G.groups.size(), (long long)cols_run, laps.us[0],
+                laps.us[1], laps.us[2]);
+    return GM_OK;
 }

@@ -259,6 +259,25 @@ class GraphStore:
         g, p = self._pairs_of(g, pairs, 'pair_distance')
         return self._pair_call('gm_store_pair_distance', g, p, len(p), torch.uint8, _lib.PAIR_MASK_TARGET if mask_target else 0, max_dist)
 
+    @staticmethod
+    def _profile_dist_of(max_dist, what):
+        max_dist = int(max_dist)
+        if not 1 <= max_dist <= 7:
+            raise ValueError('%s: max_dist = %d; 1 .. 7' % (what, max_dist))
+        return max_dist
+
+    def pair_distance_profile(self, g, pairs, mask_target=False, max_dist=3):
+        """int32 [m, D + 2, D + 2], D = `max_dist` (1..7): for each of the [m, 2] node `pairs` of graph `g`, canonicalised to (u, v) = (min, max), entry [a][b]
+        counts the nodes a hops from u and b hops from v (node_distances' distances); index D + 1 gathers everything farther and the unreached.  Counted on
+        the device from the search's state, only the tables come back (gm_store_pair_distance_profile; the definition is in include/gmeta_hip.h,
+        tests/distance_profile_ref.py restates it).  Both orientations of a pair give the same table; gmeta_amd.link_distance_profiles orients it by the
+        pair's name.  mask_target=True searches an adjacent pair's two columns in the graph without its own edge."""
+        import torch
+        max_dist = self._profile_dist_of(max_dist, 'pair_distance_profile')
+        g, p = self._pairs_of(g, pairs, 'pair_distance_profile')
+        return self._pair_call('gm_store_pair_distance_profile', g, p, (len(p), max_dist + 2, max_dist + 2), torch.int32, _lib.PAIR_MASK_TARGET if mask_target else 0,
+                               max_dist)
+
     def neighbour_degrees(self, g):
         """int32 [N]: the number of distinct neighbours (either direction, itself aside) of every node of graph `g` -- the degrees the pair scores use."""
         import torch

@@ -2,7 +2,9 @@
 include/gmeta_hip.h) turned into the ROC AUC a learned link predictor is held against.  The scores come from the device; the AUC is host work over
 one number per pair.  The path scores one step further -- the local path index and the truncated Katz index -- are formed here, in float64, from the exact walk
 counts of GraphStore.pair_walks (gm_store_pair_walks).  The one global score, rooted PageRank, is the float64 sum of the two columns of
-GraphStore.pair_pagerank (gm_store_pair_pagerank).  Graph distance is the negated byte of GraphStore.pair_distance (gm_store_pair_distance)."""
+GraphStore.pair_pagerank (gm_store_pair_pagerank).  Graph distance is the negated byte of GraphStore.pair_distance (gm_store_pair_distance).
+The joint hop-distance tables of GraphStore.pair_distance_profile (gm_store_pair_distance_profile) are no score: link_distance_profiles orients them by the
+pair's name and distance_profile_features turns them into input features."""
 import numpy as np
 
 from ._lib import DIST_UNREACHED
@@ -114,6 +116,31 @@ def link_distance_auc(store, names, labels, mask_target=False, max_dist=8):
     """{'graph_distance': ROC AUC} (DISTANCE_SCORES) over the pairs `names` ('g_i_j') with the 0 / 1 `labels` of a link table, all graphs together; the many
     pairs at one distance tie and count one half each (link_auc).  mask_target as in link_heuristic_auc."""
     return {'graph_distance': link_auc(graph_distance_index(link_distance_scores(store, names, mask_target, max_dist), max_dist), labels)}
+
+
+def link_distance_profiles(store, names, mask_target=False, max_dist=3):
+    """int32 [len(names), D + 2, D + 2], D = max_dist: GraphStore.pair_distance_profile of the pairs named 'g_i_j', one call per graph, rows in the order of
+    `names`, each table in the orientation of its name: entry [a][b] counts the nodes a hops from i and b hops from j (the store's table is that of
+    (min, max): a name with i > j gets the transpose)."""
+    side = int(max_dist) + 2
+    flat = _per_graph(store, names, side * side, np.int32,
+                      lambda g, p: np.asarray(store.pair_distance_profile(g, p, mask_target=mask_target, max_dist=max_dist), np.int32).reshape(len(p), side * side))
+    out = flat.reshape(-1, side, side)
+    trip = np.asarray([_pair(nm) for nm in names], np.int64).reshape(-1, 3)
+    swap = trip[:, 1] > trip[:, 2]
+    out[swap] = out[swap].transpose(0, 2, 1)
+    return out
+
+
+def distance_profile_features(profiles, symmetric=True):
+    """float64 [m, (D + 2)^2]: the [m, D + 2, D + 2] tables of link_distance_profiles as input features of a learned link predictor: log1p of the counts,
+    row-major.  symmetric=True (default) takes log1p(P + P^T), which does not depend on the orientation of the pair; False log1p(P)."""
+    p = np.asarray(profiles, np.int64)
+    if p.ndim != 3 or p.shape[1] != p.shape[2]:
+        raise ValueError('distance_profile_features: tables of shape %s; [m, D + 2, D + 2]' % (p.shape,))
+    if symmetric:
+        p = p + p.transpose(0, 2, 1)
+    return np.log1p(p.astype(np.float64)).reshape(len(p), p.shape[1] * p.shape[2])
 
 
 def candidate_names(g, nodes, partners):

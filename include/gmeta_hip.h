@@ -305,6 +305,38 @@ int32_t gm_store_pagerank_candidates(const gm_store_t* s, int32_t g, const int32
 int32_t gm_store_node_distances(const gm_store_t* s, int32_t g, const int32_t* d_sources, int64_t m, int32_t max_dist, uint8_t* d_out, void* stream);
 int32_t gm_store_pair_distance(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, int32_t max_dist, uint8_t* d_out, void* stream);
 
+/* ---- JOINT HOP-DISTANCE PROFILES of node pairs (beyond the reference): for a pair (u, v) the number of nodes lying a hops from u and b hops from v, for all
+ * small a, b -- the table behind SEAL's double-radius labels and the structure features of ELPH / BUDDY, exact, counted on the device from the state of the
+ * search above so that only [n, D + 2, D + 2] integers leave it.  This comment is THE definition; tests/distance_profile_ref.py restates it.  Per parent graph g
+ * of a store, with N nodes:
+ *   columns        neighbourhoods, columns (s, x) and d_(s,x)[z] are exactly those of gm_store_node_distances / gm_store_pair_distance.
+ *   D, cap         D = max_dist, in 1 .. 7 (the range of gm_set_hop_labels; a table has (D + 2)^2 <= 81 entries).  cap(d) = d if d <= D, else D + 1: the farther
+ *                  nodes and the unreached ones (byte 255) alike.
+ *   pair           d_pairs: device int32 [n, 2], any orientation, p == q allowed; a pair is canonicalised to (u, v) = (min, max).  xu = v and xv = u when
+ *                  GM_PAIR_MASK_TARGET (1) is in `flags`, u != v and v in G(u); otherwise xu = xv = -1.
+ *   table          P[a][b] = |{ z in [0, N) : cap(d_(u,xu)[z]) == a and cap(d_(v,xv)[z]) == b }|,   a, b in 0 .. D + 1
+ *   result         d_out: device int32 [n, D + 2, D + 2], row-major [a][b] of the CANONICAL pair: both orientations of a pair give the same bits (the table of
+ *                  (v, u) is the transpose; g-meta_amd/heuristics.py orients it by the pair's name).  A pair with a node outside the graph gives all zeros.
+ *                  Nothing behind entry n - 1 is written.  Duplicates are allowed, every entry is written on its own.
+ *   identities     that follow from the definition (tests hold the device to them):
+ *                    sum of P = N;
+ *                    row 0 and column 0 hold a single 1 each, at cap(gm_store_pair_distance(pair, flags)); u == v: P[0][0] = 1 and P is diagonal;
+ *                    u != v: P[1][1] = cn of gm_store_pair_scores, flagged or not (the pair's own edge never joins a common neighbour);
+ *                    sum over b of P[a][b] = |{ z : cap(d_(u,xu)[z]) == a }|, and the column sums likewise for v;
+ *                    a non-adjacent pair under the flag gives the unflagged bits.
+ *   exactness      the results are integers and unique.  A table is a function of (graph, its own pair, flags, max_dist) alone: not of the other pairs of the
+ *                  call, their order or their duplicates, not of dist_cols or dist_chunk (above), not of gm_set_tuning("dist_plane_kib", K) (below), not of
+ *                  the stream.  No atomics.
+ * The call reads the neighbour index, runs on `stream`, reads the pairs (with the flag their adjacency bytes, and the graph's row lengths) back once, sorts the
+ * canonical pairs by (u, v) and cuts them into groups of at most Bp DISTINCT columns, so that both columns of a pair are alive in one round of the search; each
+ * group is searched on its own.  Scratch from the stream-ordered pool: the search's (above, B = the widest group's columns), the level planes -- one bit per
+ * (level 0 .. D, column, node): (D + 1) x Bp x ceil(N / 64) x 8 bytes -- and 16 bytes per pair.  Bp = min(dist_cols in force, the largest multiple of 64 whose
+ * planes fit the budget); the budget is gm_set_tuning("dist_plane_kib", K) / GM_DIST_PLANE_KIB in KiB, 0 = the library's choice, 1 GiB.  GM_ERANGE (the message
+ * names N, max_dist and the budget) when the planes of even 64 columns do not fit.  The result is complete in stream order.  n == 0 is a no-op, with NULL
+ * pointers too.
+ * GM_EINVAL (the message names the value): as gm_store_pair_distance, with max_dist outside 1 .. 7, and a negative dist_plane_kib. */
+int32_t gm_store_pair_distance_profile(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, int32_t max_dist, int32_t* d_out, void* stream);
+
 /* ---- Extraction: replaces Subgraphs.generate_subgraph / generate_subgraph_link_pred
  * (sdp.py:295-346: h-hop in-neighbour expansion, node sampling, G.subgraph) and dgl.batch
  * (sdp.py:399-406) for n_sets sets at once.  seeds/set_offsets are host arrays; set s owns seeds
