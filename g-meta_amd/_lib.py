@@ -47,6 +47,11 @@ PROTOTYPES = {
     'gm_store_node_distances': (i32, [vp, i32, vp, i64, i32, vp, vp]),
     'gm_store_pair_distance': (i32, [vp, i32, vp, i64, i32, i32, vp, vp]),
     'gm_store_pair_distance_profile': (i32, [vp, i32, vp, i64, i32, i32, vp, vp]),
+    'gm_store_sketch_build': (i32, [vp, i32, i32, i32, i32, u64, vp, vp]),
+    'gm_sketch_dims': (i32, [vp, vp, vp, vp, vp, vp]),
+    'gm_sketch_registers': (i32, [vp, i32, vp, i64, vp, vp, vp]),
+    'gm_sketch_pair_counts': (i32, [vp, vp, i64, vp, vp, vp]),
+    'gm_sketch_destroy': (None, [vp]),
     'gm_store_neighbour_degrees': (i32, [vp, i32, vp, vp]),
     'gm_store_pair_candidates': (i32, [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp]),
     'gm_extract': (C.c_int, [vp, vp, i32, vp, i32, i32, i32, u64, i32, vp, vp]),

@@ -12,6 +12,7 @@ SOURCES = ['common.hip', 'store.hip', 'batch.hip', 'extract.hip', 'agg.hip', 'ag
 SOURCES += ['candidates.hip']      # reads the neighbour index (nbr_index.hip, gm_nbr.h) and launches the score kernel of pair_scores.hip (gm_internal.h)
 SOURCES += ['pair_pagerank.hip', 'pagerank_candidates.hip']   # rooted PageRank of sources and node pairs over the same neighbour index; the top-k selection on a round's state
 SOURCES += ['pair_distance.hip', 'distance_profile.hip']   # shortest-path distances of sources and node pairs over the same neighbour index: one bit per (node, column); the joint hop-distance tables of pairs on that state
+SOURCES += ['node_sketches.hip']   # ELPH / BUDDY neighbourhood sketches of all nodes over the same neighbour index: HyperLogLog + MinHash records per level, and the pair counts on them
 SOURCES += ['pair_walks.hip']      # walk counts of node pairs over the same neighbour index
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result']
 

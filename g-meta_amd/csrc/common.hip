@@ -375,6 +375,8 @@ const gm_knobs& gm_knob() {
         k.dist_chunk = env("GM_DIST_CHUNK", 0);
         k.dist_cols = env("GM_DIST_COLS", 0);
         k.dist_plane_kib = env("GM_DIST_PLANE_KIB", 0);
+        k.sketch_chunk = env("GM_SKETCH_CHUNK", 0);
+        k.sketch_mib = env("GM_SKETCH_MIB", 0);
     });
     return k;
 }
@@ -402,6 +404,8 @@ static int gm_knobs::* gm_find_knob(const char* name) {
         {"dist_chunk", &gm_knobs::dist_chunk}, {"GM_DIST_CHUNK", &gm_knobs::dist_chunk},
         {"dist_cols", &gm_knobs::dist_cols}, {"GM_DIST_COLS", &gm_knobs::dist_cols},
         {"dist_plane_kib", &gm_knobs::dist_plane_kib}, {"GM_DIST_PLANE_KIB", &gm_knobs::dist_plane_kib},
+        {"sketch_chunk", &gm_knobs::sketch_chunk}, {"GM_SKETCH_CHUNK", &gm_knobs::sketch_chunk},
+        {"sketch_mib", &gm_knobs::sketch_mib}, {"GM_SKETCH_MIB", &gm_knobs::sketch_mib},
     };
     for (const auto& e : tab)
         if (!strcmp(name, e.name)) return e.field;

@@ -268,6 +268,8 @@ struct gm_knobs {
     int dist_cols;                 // GM_DIST_COLS, gm_set_tuning("dist_cols"): columns per round of those two calls, a multiple of 64 up to 4096; 0 (default) = the library's choice.  The result does not depend on it
     int dist_plane_kib;            // GM_DIST_PLANE_KIB, gm_set_tuning("dist_plane_kib"): KiB of level planes gm_store_pair_distance_profile may hold at a time (pair_distance.hip), which bounds the columns of a group; 0 (default) = the library's choice, 1 GiB.  The result does not depend on it
     int cand_bitmap;               // GM_CAND_BITMAP, gm_set_tuning("cand_bitmap"): home of that call's membership bitmap: 1 LDS, 2 a per-workgroup slab in HBM; 0 (default) = LDS wherever the graph fits.  The result does not depend on it
+    int sketch_chunk;              // GM_SKETCH_CHUNK, gm_set_tuning("sketch_chunk"): entries per segment of a hub row of gm_store_sketch_build (node_sketches.hip); 0 (default) = the library's choice.  The result does not depend on it
+    int sketch_mib;                // GM_SKETCH_MIB, gm_set_tuning("sketch_mib"): MiB one gm_store_sketch_build may allocate; 0 (default) = the library's choice, 8 GiB.  The result does not depend on it
 };
 const gm_knobs& gm_knob();
 

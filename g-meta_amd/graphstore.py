@@ -278,6 +278,15 @@ class GraphStore:
         return self._pair_call('gm_store_pair_distance_profile', g, p, (len(p), max_dist + 2, max_dist + 2), torch.int32, _lib.PAIR_MASK_TARGET if mask_target else 0,
                                max_dist)
 
+    def sketches(self, g, hops=2, p=8, k=128, seed=222):
+        """gmeta_amd.NodeSketches of graph `g`: per node and level 0 .. `hops` (1..4) a HyperLogLog sketch of 2^`p` registers (p in 4..10) and a MinHash
+        sketch of `k` words (a multiple of 32 in 32..512) of its ball, built once on the device (gm_store_sketch_build; the definition is in
+        include/gmeta_hip.h, tests/sketch_ref.py restates it).  Its pair_counts + gmeta_amd.sketch_distance_profile estimate the table of
+        pair_distance_profile for any pair without a search.  No mask_target: the sketches describe the whole graph; pair_distance_profile(mask_target=True)
+        gives the exact, masked table of a shortlist."""
+        from .sketches import NodeSketches
+        return NodeSketches(self, g, hops, p, k, seed)
+
     def neighbour_degrees(self, g):
         """int32 [N]: the number of distinct neighbours (either direction, itself aside) of every node of graph `g` -- the degrees the pair scores use."""
         import torch

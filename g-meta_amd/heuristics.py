@@ -4,7 +4,9 @@ one number per pair.  The path scores one step further -- the local path index a
 counts of GraphStore.pair_walks (gm_store_pair_walks).  The one global score, rooted PageRank, is the float64 sum of the two columns of
 GraphStore.pair_pagerank (gm_store_pair_pagerank).  Graph distance is the negated byte of GraphStore.pair_distance (gm_store_pair_distance).
 The joint hop-distance tables of GraphStore.pair_distance_profile (gm_store_pair_distance_profile) are no score: link_distance_profiles orients them by the
-pair's name and distance_profile_features turns them into input features."""
+pair's name and distance_profile_features turns them into input features.  Their ESTIMATES for every pair come from the node sketches of GraphStore.sketches
+(gm_store_sketch_build / gm_sketch_pair_counts): hll_cardinality, sketch_intersections and sketch_distance_profile form them in float64 from the integers,
+link_sketch_profiles orients them by the pair's name and sketch_profile_features gives the same feature shape."""
 import numpy as np
 
 from ._lib import DIST_UNREACHED
@@ -141,6 +143,87 @@ def distance_profile_features(profiles, symmetric=True):
     if symmetric:
         p = p + p.transpose(0, 2, 1)
     return np.log1p(p.astype(np.float64)).reshape(len(p), p.shape[1] * p.shape[2])
+
+
+def hll_cardinality(zeros, zsum, p):
+    """float64, the shape of `zeros`: the HyperLogLog estimate of a set's size from its m = 2^p registers' two integers -- `zeros` registers equal to 0 and
+    `zsum` = the sum of 2^(32 - register), as NodeSketches.pair_counts returns them.  E = alpha_m m^2 / (zsum / 2^32); where E <= 2.5 m and zeros > 0 the
+    linear count m ln(m / zeros) takes its place.  alpha = 0.673, 0.697, 0.709 at m = 16, 32, 64, else 0.7213 / (1 + 1.079 / m).  No large-range correction:
+    a ball holds fewer than 2^31 nodes.  An all-zero record (zsum == 0: the C call's answer for a node outside the graph) gives 0."""
+    p = int(p)
+    if not 4 <= p <= 10:
+        raise ValueError('hll_cardinality: p = %d; 4 .. 10' % p)
+    m = float(1 << p)
+    alpha = {16: 0.673, 32: 0.697, 64: 0.709}.get(1 << p, 0.7213 / (1.0 + 1.079 / m))
+    z = np.asarray(zeros, np.int64).astype(np.float64)
+    s = np.asarray(zsum, np.int64).astype(np.float64) / 4294967296.0
+    with np.errstate(divide='ignore', invalid='ignore'):
+        est = np.where(s > 0, alpha * m * m / s, 0.0)
+        lin = m * np.log(m / np.where(z > 0, z, 1.0))
+    return np.where((s > 0) & (est <= 2.5 * m) & (z > 0), lin, est)
+
+
+def sketch_intersections(counts, p, k):
+    """float64 [m, H + 1, H + 1]: the estimate of |B_a(u) & B_b(v)| from the int64 [m, H + 1, H + 1, 3] counts of NodeSketches.pair_counts: the MinHash
+    Jaccard match / k times the HyperLogLog cardinality of the union."""
+    c = np.asarray(counts, np.int64)
+    if c.ndim != 4 or c.shape[1] != c.shape[2] or c.shape[3] != 3:
+        raise ValueError('sketch_intersections: counts of shape %s; [m, H + 1, H + 1, 3]' % (c.shape,))
+    return c[..., 0].astype(np.float64) / float(int(k)) * hll_cardinality(c[..., 1], c[..., 2], p)
+
+
+def sketch_distance_profile(counts, balls, n_nodes, p, k):
+    """float64 [m, H + 2, H + 2]: the estimate of GraphStore.pair_distance_profile(max_dist=H), unmasked, in its layout, from the two results of
+    NodeSketches.pair_counts.  With C = sketch_intersections (cumulative: nodes within a of u AND within b of v), the inner cells are the 2-D difference
+    C[a][b] - C[a-1][b] - C[a][b-1] + C[a-1][b-1] (C[-1][.] = C[.][-1] = 0); row and column H + 1 are the differences of the ball sizes (hll_cardinality of
+    `balls`) minus the inner row / column sums; the corner is n_nodes minus everything else, so every table sums to n_nodes.  Estimates are NOT clipped: a
+    cell may come out slightly negative (sketch_profile_features clips)."""
+    c = sketch_intersections(counts, p, k)
+    b = np.asarray(balls, np.int64)
+    m, L = c.shape[0], c.shape[1]
+    if b.shape != (m, 2, L, 2):
+        raise ValueError('sketch_distance_profile: balls of shape %s for counts of shape %s; [m, 2, H + 1, 2]' % (b.shape, np.shape(counts)))
+    size = hll_cardinality(b[..., 0], b[..., 1], p)                            # [m, 2, L]: |B_a(u)|, |B_a(v)|
+    ring = np.diff(size, axis=2, prepend=0.0)
+    inner = np.diff(np.diff(c, axis=1, prepend=0.0), axis=2, prepend=0.0)
+    out = np.zeros((m, L + 1, L + 1), np.float64)
+    out[:, :L, :L] = inner
+    out[:, :L, L] = ring[:, 0] - inner.sum(2)
+    out[:, L, :L] = ring[:, 1] - inner.sum(1)
+    out[:, L, L] = float(n_nodes) - out.reshape(m, -1).sum(1)
+    return out
+
+
+def link_sketch_profiles(sketches_by_graph, names):
+    """float64 [len(names), H + 2, H + 2]: sketch_distance_profile of the pairs named 'g_i_j' from sketches_by_graph[g] (a dict or a sequence of
+    NodeSketches with one `hops`), one pair_counts call per graph, rows in the order of `names`, each table in the orientation of its name as
+    link_distance_profiles orients the exact ones (a name with i > j gets the transpose)."""
+    trip = np.asarray([_pair(nm) for nm in names], np.int64).reshape(-1, 3)
+    graphs = np.unique(trip[:, 0]).tolist()
+    hops = {int(sketches_by_graph[g].hops) for g in graphs}
+    if len(hops) > 1:
+        raise ValueError('link_sketch_profiles: sketches of different hops %s' % sorted(hops))
+    side = (hops.pop() if hops else 0) + 2
+    out = np.zeros((len(trip), side, side), np.float64)
+    for g in graphs:
+        sk = sketches_by_graph[g]
+        at = np.nonzero(trip[:, 0] == g)[0]
+        counts, balls = sk.pair_counts(trip[at, 1:])
+        out[at] = sketch_distance_profile(counts, balls, sk.n_nodes, sk.p, sk.k)
+    swap = trip[:, 1] > trip[:, 2]
+    out[swap] = out[swap].transpose(0, 2, 1)
+    return out
+
+
+def sketch_profile_features(tables, symmetric=True):
+    """float64 [m, (H + 2)^2]: the estimated tables of link_sketch_profiles as input features, in the shape distance_profile_features gives for the exact
+    ones (either feeds the same predictor): log1p(max(P, 0)) row-major, P + P^T in place of P when symmetric (default)."""
+    t = np.asarray(tables, np.float64)
+    if t.ndim != 3 or t.shape[1] != t.shape[2]:
+        raise ValueError('sketch_profile_features: tables of shape %s; [m, H + 2, H + 2]' % (t.shape,))
+    if symmetric:
+        t = t + t.transpose(0, 2, 1)
+    return np.log1p(np.maximum(t, 0.0)).reshape(len(t), t.shape[1] * t.shape[2])
 
 
 def candidate_names(g, nodes, partners):

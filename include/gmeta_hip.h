@@ -337,6 +337,59 @@ int32_t gm_store_pair_distance(const gm_store_t* s, int32_t g, const int32_t* d_
  * GM_EINVAL (the message names the value): as gm_store_pair_distance, with max_dist outside 1 .. 7, and a negative dist_plane_kib. */
 int32_t gm_store_pair_distance_profile(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, int32_t flags, int32_t max_dist, int32_t* d_out, void* stream);
 
+/* ---- NEIGHBOURHOOD SKETCHES of all nodes (beyond the reference): the ELPH / BUDDY route to the table above for EVERY training pair.  The exact profile costs a
+ * search of two columns per pair; here each node carries a HyperLogLog and a MinHash sketch of its d-hop ball for d = 0 .. H, built once by H rounds of
+ * element-wise max / min over the neighbour lists, and the joint table of any pair is estimated from 2 (H + 1) small records with no search.  This comment is
+ * THE definition; tests/sketch_ref.py restates it.  Per parent graph g of a store, with N nodes:
+ *   neighbourhood  G(x) is that of gm_store_pair_scores: DISTINCT nodes joined in either direction, self loops never count, parallel copies count once,
+ *                  weights are ignored.
+ *   parameters     hops H in 1 .. 4; HLL precision p in 4 .. 10, m = 2^p registers of one byte; MinHash width K, a multiple of 32 in 32 .. 512, uint32
+ *                  values; seed, u64.
+ *   hashes         lowbias32 and sample_salt are those of the node sampling (gm_extract).  s_h = sample_salt(seed, g, 0x534B4831, 0),
+ *                  s_m = sample_salt(seed, g, 0x534B4D31, 0).
+ *                  HLL insert of node z:  h = lowbias32((uint32) z ^ s_h); register j = h >> (32 - p); w = h << p (mod 2^32); rho = clz32(w) + 1 when
+ *                  w != 0, else 33 - p.
+ *                  MinHash of node z:  q = lowbias32((uint32) z ^ s_m); mh_k(z) = lowbias32(q + (k + 1) * 0x9E3779B9) in wrap-around arithmetic, k = 0 .. K - 1.
+ *                  Every step is a bijection of uint32, so for a fixed k distinct nodes never share a value of mh_k: two of the identities below rest on it.
+ *   balls          B_0(x) = {x};  B_d(x) = B_{d-1}(x) united with B_{d-1}(z) over z in G(x)  =  { z : gm_store_node_distances(x)[z] <= d }.
+ *   sketches       R_d(x)[j] = max rho(z) over the z in B_d(x) with register j(z) = j, 0 if there is none;  M_d(x)[k] = min over z in B_d(x) of mh_k(z).
+ *                  Both are functions of a set and therefore unique; the recurrence computes them as the element-wise max / min over x's own level d - 1
+ *                  record and those of G(x).
+ *   pair counts    d_pairs: device int32 [n, 2], any orientation, a == b allowed; a pair is canonicalised to (u, v) = (min, max).  For a, b in 0 .. H, with
+ *                  U = max(R_a(u), R_b(v)) element-wise:
+ *                    match[a][b] = |{ k : M_a(u)[k] == M_b(v)[k] }|
+ *                    zeros[a][b] = |{ j : U[j] == 0 }|
+ *                    zsum[a][b]  = sum over j of 2^(32 - U[j]), exact; below 2^43
+ *                  d_out: device int64 [n, H + 1, H + 1, 3] = (match, zeros, zsum);  d_out_balls: device int64 [n, 2, H + 1, 2] = (zeros, zsum) of R_a(u) and
+ *                  then of R_a(v) alone.  A node id outside [0, N) gives zeros in both.  Nothing behind entry n - 1 is written.  Duplicates are written
+ *                  each on their own.  The estimators (HyperLogLog cardinality, MinHash Jaccard, the table in the layout of gm_store_pair_distance_profile)
+ *                  are float64 host work over these integers: g-meta_amd/heuristics.py.
+ *   identities     that follow from the definition (tests hold the device to them): match[a][b] == K whenever B_a(u) == B_b(v); match[a][b] == 0 whenever the
+ *                  two balls are disjoint (mh_k is a bijection); B_a(u) inside B_b(v) makes (zeros, zsum)[a][b] v's ball entry b; zeros and zsum do not
+ *                  increase in a or in b; both orientations of a pair give the same bits.
+ *   no mask flag   the sketches describe the WHOLE graph: a pair's own edge cannot be taken out of them (ELPH has the same limit).  The exact, masked table of
+ *                  a shortlist is gm_store_pair_distance_profile with GM_PAIR_MASK_TARGET.
+ *   exactness      every output is an integer and a function of (graph, seed, H, p, K, and for the counts the pair) alone: not of where a long row is cut
+ *                  (gm_set_tuning("sketch_chunk", C): entries per segment of a row of more than C, 0 = the library's choice -- max and min are idempotent
+ *                  and commutative), not of the stream, of arrival order or of the other pairs of the call.  No atomics, no floats.
+ *   memory         a sketch owns N (H + 1) (2^p + 4 K) bytes of device memory (0.52 GB at N = 169,343, H = 3, p = 8, K = 128), laid out level-major, then
+ *                  node-major, a node's record = its 2^p register bytes then its K words; level 0 is STORED, not recomputed.  gm_set_tuning("sketch_mib", M) /
+ *                  GM_SKETCH_MIB is the budget of one build in MiB, 0 = the library's choice, 8 GiB: GM_ERANGE (the message names N, H, p, K and the budget)
+ *                  when the formula exceeds it.  The sketch does not reference the store afterwards: destroying the store first is legal.
+ * gm_store_sketch_build reads the neighbour index (built at first use, as for gm_store_pair_scores), runs on `stream`, reads the graph's row lengths back once
+ * to cut the hub rows, takes the hub segments' partial records from the stream-ordered pool, and returns after the stream has produced the sketch: any stream
+ * may read it afterwards.  gm_sketch_registers returns the raw records of m nodes at one level, d_hll: device uint8 [m, 2^p], d_minhash: device uint32 [m, K]; a
+ * node outside [0, N) gives zeros.  Both readers run on `stream` and are complete in stream order; n == 0 / m == 0 is a no-op, with NULL pointers too.
+ * gm_sketch_dims fills whichever of its outputs is not NULL (bytes: the formula above).  gm_sketch_destroy waits for the device and frees the records.
+ * GM_EINVAL (the message names the value): a bad graph index, hops / p / k outside the ranges above, a level outside 0 .. H, n or m negative or above
+ * INT32_MAX, a NULL argument with work to do, a negative sketch_chunk or sketch_mib. */
+typedef struct gm_sketch gm_sketch_t;
+int32_t gm_store_sketch_build(const gm_store_t* s, int32_t g, int32_t hops, int32_t p, int32_t k, uint64_t seed, void* stream, gm_sketch_t** out);
+int32_t gm_sketch_dims(const gm_sketch_t* sk, int64_t* n_nodes, int32_t* hops, int32_t* p, int32_t* k, int64_t* bytes);
+int32_t gm_sketch_registers(const gm_sketch_t* sk, int32_t level, const int32_t* d_nodes, int64_t m, uint8_t* d_hll, uint32_t* d_minhash, void* stream);
+int32_t gm_sketch_pair_counts(const gm_sketch_t* sk, const int32_t* d_pairs, int64_t n, int64_t* d_out, int64_t* d_out_balls, void* stream);
+void gm_sketch_destroy(gm_sketch_t* sk);
+
 /* ---- Extraction: replaces Subgraphs.generate_subgraph / generate_subgraph_link_pred
  * (sdp.py:295-346: h-hop in-neighbour expansion, node sampling, G.subgraph) and dgl.batch
  * (sdp.py:399-406) for n_sets sets at once.  seeds/set_offsets are host arrays; set s owns seeds
