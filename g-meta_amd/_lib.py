@@ -12,6 +12,8 @@ LINK_SYMMETRIC = 2      # GM_LINK_SYMMETRIC: the link_pred mode of gm_extract / 
 LINK_MASK_TARGET = 4    # GM_LINK_MASK_TARGET: flag OR-ed onto a pair mode -- the subgraph of (i, j) is built without the i-j edges themselves
 NEG_MODES = {'uniform': 0, 'two_hop': 1}      # GM_NEG_UNIFORM / GM_NEG_TWO_HOP (gm_store_negative_pairs)
 PAIR_MASK_TARGET = 1    # GM_PAIR_MASK_TARGET: flag of gm_store_pair_scores / gm_store_pair_walks / gm_store_pair_pagerank / gm_store_pair_distance / gm_store_pair_distance_profile -- the pair is scored as if no edge joined its two nodes
+PROP_SELF_LOOPS = 1     # GM_PROP_SELF_LOOPS: flag of gm_store_propagate_build -- one extra entry (v, 1.0) in front of every row: the A + I of GCN / SIGN / BUDDY
+PROP_OPS = {'hadamard': 0, 'abs_diff': 1}      # GM_PROP_HADAMARD / GM_PROP_ABS_DIFF: how gm_prop_pair_features combines the two nodes' rows of a level
 DIST_UNREACHED = 255    # GM_DIST_UNREACHED: the byte of gm_store_node_distances / gm_store_pair_distance for a node no path of at most max_dist edges reaches
 
 
@@ -52,6 +54,11 @@ PROTOTYPES = {
     'gm_sketch_registers': (i32, [vp, i32, vp, i64, vp, vp, vp]),
     'gm_sketch_pair_counts': (i32, [vp, vp, i64, vp, vp, vp]),
     'gm_sketch_destroy': (None, [vp]),
+    'gm_store_propagate_build': (i32, [vp, i32, i32, i32, vp, vp]),
+    'gm_prop_dims': (i32, [vp, vp, vp, vp, vp, vp]),
+    'gm_prop_rows': (i32, [vp, i32, vp, i64, vp, vp]),
+    'gm_prop_pair_features': (i32, [vp, vp, i64, i32, vp, vp]),
+    'gm_prop_destroy': (None, [vp]),
     'gm_store_neighbour_degrees': (i32, [vp, i32, vp, vp]),
     'gm_store_pair_candidates': (i32, [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp]),
     'gm_extract': (C.c_int, [vp, vp, i32, vp, i32, i32, i32, u64, i32, vp, vp]),

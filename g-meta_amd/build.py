@@ -13,6 +13,7 @@ SOURCES += ['candidates.hip']      # reads the neighbour index (nbr_index.hip, g
 SOURCES += ['pair_pagerank.hip', 'pagerank_candidates.hip']   # rooted PageRank of sources and node pairs over the same neighbour index; the top-k selection on a round's state
 SOURCES += ['pair_distance.hip', 'distance_profile.hip']   # shortest-path distances of sources and node pairs over the same neighbour index: one bit per (node, column); the joint hop-distance tables of pairs on that state
 SOURCES += ['node_sketches.hip']   # ELPH / BUDDY neighbourhood sketches of all nodes over the same neighbour index: HyperLogLog + MinHash records per level, and the pair counts on them
+SOURCES += ['propagate.hip']       # BUDDY / SIGN hop-propagated node features of a whole parent graph over the store's in-edge CSR: norms, levels, and the row and pair readers on them
 SOURCES += ['pair_walks.hip']      # walk counts of node pairs over the same neighbour index
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result']
 

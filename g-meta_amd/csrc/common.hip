@@ -377,6 +377,8 @@ const gm_knobs& gm_knob() {
         k.dist_plane_kib = env("GM_DIST_PLANE_KIB", 0);
         k.sketch_chunk = env("GM_SKETCH_CHUNK", 0);
         k.sketch_mib = env("GM_SKETCH_MIB", 0);
+        k.prop_chunk = env("GM_PROP_CHUNK", 0);
+        k.prop_mib = env("GM_PROP_MIB", 0);
     });
     return k;
 }
@@ -406,6 +408,8 @@ static int gm_knobs::* gm_find_knob(const char* name) {
         {"dist_plane_kib", &gm_knobs::dist_plane_kib}, {"GM_DIST_PLANE_KIB", &gm_knobs::dist_plane_kib},
         {"sketch_chunk", &gm_knobs::sketch_chunk}, {"GM_SKETCH_CHUNK", &gm_knobs::sketch_chunk},
         {"sketch_mib", &gm_knobs::sketch_mib}, {"GM_SKETCH_MIB", &gm_knobs::sketch_mib},
+        {"prop_chunk", &gm_knobs::prop_chunk}, {"GM_PROP_CHUNK", &gm_knobs::prop_chunk},
+        {"prop_mib", &gm_knobs::prop_mib}, {"GM_PROP_MIB", &gm_knobs::prop_mib},
     };
     for (const auto& e : tab)
         if (!strcmp(name, e.name)) return e.field;

@@ -270,6 +270,8 @@ struct gm_knobs {
     int cand_bitmap;               // GM_CAND_BITMAP, gm_set_tuning("cand_bitmap"): home of that call's membership bitmap: 1 LDS, 2 a per-workgroup slab in HBM; 0 (default) = LDS wherever the graph fits.  The result does not depend on it
     int sketch_chunk;              // GM_SKETCH_CHUNK, gm_set_tuning("sketch_chunk"): entries per segment of a hub row of gm_store_sketch_build (node_sketches.hip); 0 (default) = the library's choice.  The result does not depend on it
     int sketch_mib;                // GM_SKETCH_MIB, gm_set_tuning("sketch_mib"): MiB one gm_store_sketch_build may allocate; 0 (default) = the library's choice, 8 GiB.  The result does not depend on it
+    int prop_chunk;                // GM_PROP_CHUNK, gm_set_tuning("prop_chunk"): entries per segment of a hub row of gm_store_propagate_build (propagate.hip); 0 (default) = the library's choice.  The order of a row's fp32 sum, hence its low bits, belongs to it
+    int prop_mib;                  // GM_PROP_MIB, gm_set_tuning("prop_mib"): MiB one gm_store_propagate_build may allocate; 0 (default) = the library's choice, 8 GiB.  The result does not depend on it
 };
 const gm_knobs& gm_knob();
 

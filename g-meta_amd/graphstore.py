@@ -287,6 +287,15 @@ class GraphStore:
         from .sketches import NodeSketches
         return NodeSketches(self, g, hops, p, k, seed)
 
+    def propagated_features(self, g, hops=2, self_loops=True):
+        """gmeta_amd.PropagatedFeatures of graph `g`: the SIGN / BUDDY levels x_0 = X, x_{t+1} = A^ x_t for t < `hops` (1..8) of the store's feature table, A^ the
+        GraphConv normalisation over the WHOLE graph's in-edge CSR (parallel edges, self loops, directions and weights kept) with one self loop in front of every
+        row under `self_loops`, built once on the device (gm_store_propagate_build; the definition is in include/gmeta_hip.h, tests/hop_feature_ref.py restates
+        it).  Its pair_features gives the x_t[u] * x_t[v] inputs of a BUDDY predictor; the structural counts come from sketches.  No mask_target: the levels
+        describe the whole graph, as the sketches do."""
+        from .propagate import PropagatedFeatures
+        return PropagatedFeatures(self, g, hops, self_loops)
+
     def neighbour_degrees(self, g):
         """int32 [N]: the number of distinct neighbours (either direction, itself aside) of every node of graph `g` -- the degrees the pair scores use."""
         import torch

@@ -6,7 +6,8 @@ GraphStore.pair_pagerank (gm_store_pair_pagerank).  Graph distance is the negate
 The joint hop-distance tables of GraphStore.pair_distance_profile (gm_store_pair_distance_profile) are no score: link_distance_profiles orients them by the
 pair's name and distance_profile_features turns them into input features.  Their ESTIMATES for every pair come from the node sketches of GraphStore.sketches
 (gm_store_sketch_build / gm_sketch_pair_counts): hll_cardinality, sketch_intersections and sketch_distance_profile form them in float64 from the integers,
-link_sketch_profiles orients them by the pair's name and sketch_profile_features gives the same feature shape."""
+link_sketch_profiles orients them by the pair's name and sketch_profile_features gives the same feature shape.  link_propagated_features is their twin for the
+hop-propagated node features of GraphStore.propagated_features (gm_store_propagate_build / gm_prop_pair_features): the other input of a BUDDY predictor."""
 import numpy as np
 
 from ._lib import DIST_UNREACHED
@@ -224,6 +225,27 @@ def sketch_profile_features(tables, symmetric=True):
     if symmetric:
         t = t + t.transpose(0, 2, 1)
     return np.log1p(np.maximum(t, 0.0)).reshape(len(t), t.shape[1] * t.shape[2])
+
+
+def link_propagated_features(props_by_graph, names, op='hadamard'):
+    """float32 [len(names), hops + 1, F]: PropagatedFeatures.pair_features of the pairs named 'g_i_j' from props_by_graph[g] (a dict or a sequence of
+    PropagatedFeatures with one `hops` and one `feat_dim`), one call per graph, rows in the order of `names` -- the twin of link_sketch_profiles: the two together
+    are the precomputed inputs of a BUDDY predictor.  Both operations ('hadamard', 'abs_diff') are symmetric in the pair: the orientation of a name drops out."""
+    from .propagate import check_op
+    check_op(op, 'link_propagated_features')
+    trip = np.asarray([_pair(nm) for nm in names], np.int64).reshape(-1, 3)
+    graphs = np.unique(trip[:, 0]).tolist()
+    hops = {int(props_by_graph[g].hops) for g in graphs}
+    if len(hops) > 1:
+        raise ValueError('link_propagated_features: propagated features of different hops %s' % sorted(hops))
+    width = {int(props_by_graph[g].feat_dim) for g in graphs}
+    if len(width) > 1:
+        raise ValueError('link_propagated_features: propagated features of different feat_dim %s' % sorted(width))
+    out = np.zeros((len(trip), (hops.pop() if hops else 0) + 1, width.pop() if width else 0), np.float32)
+    for g in graphs:
+        at = np.nonzero(trip[:, 0] == g)[0]
+        out[at] = props_by_graph[g].pair_features(trip[at, 1:], op)
+    return out
 
 
 def candidate_names(g, nodes, partners):

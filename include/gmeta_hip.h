@@ -390,6 +390,52 @@ int32_t gm_sketch_registers(const gm_sketch_t* sk, int32_t level, const int32_t*
 int32_t gm_sketch_pair_counts(const gm_sketch_t* sk, const int32_t* d_pairs, int64_t n, int64_t* d_out, int64_t* d_out_balls, void* stream);
 void gm_sketch_destroy(gm_sketch_t* sk);
 
+/* ---- HOP-PROPAGATED NODE FEATURES of a whole parent graph (beyond the reference): the second precomputed input of a BUDDY predictor beside the structural counts
+ * of the sketches above -- the SIGN-style levels X, A^ X, A^2 X, ..., which the predictor combines per pair as x_t[u] (.) x_t[v].  This comment is THE definition;
+ * tests/hop_feature_ref.py restates it.  Per parent graph g of a store, with N nodes and feature width F = feat_dim:
+ *   operator     the project's own GraphConv normalisation (the weighted-store comment above: norm(v) * sum w_uv * norm(u) * x[u]) over the WHOLE graph's in-edge
+ *                CSR as the store holds it -- NOT the neighbour index: parallel edges count with their multiplicity, self loops count, directions are kept,
+ *                weights are used on weighted stores.
+ *   row of v     its in-CSR entries (u, w_uv) in stored order; w = 1.0f on unweighted stores.  Under GM_PROP_SELF_LOOPS (flag bit 1) one extra entry (v, 1.0f)
+ *                stands in FRONT of every row: the A^ = D~^-1/2 (A + I) D~^-1/2 of GCN / SIGN / BUDDY.
+ *   degree       d(v) = the fp32 sum of the row's weights in row order;  norm(v) = 1 / sqrtf(d(v) > 0 ? d(v) : 1).
+ *   levels       x_0 = the store's feature rows.  For t = 0 .. hops - 1, in fp32:
+ *                  x_{t+1}[v][f] = norm(v) * S,  S = the sum over the row's entries, in row order, of (w_uv * norm(u)) * x_t[u][f]
+ *                where the coefficient c = w_uv * norm(u) is one fp32 product and S is accumulated from +0 as S = fmaf(c, x_t[u][f], S).  A row without entries
+ *                gives zeros, as GraphConv does.  hops in 1 .. 8.
+ *   hub rows     a row of more than C entries is summed in segments of C entries, each from +0, and the partial sums are added in ascending order (the first
+ *                plus the second, plus the third, ...); its degree sum goes the same way.  C = gm_set_tuning("prop_chunk", C) / GM_PROP_CHUNK, 0 = the
+ *                library's choice (256); the self-loop entry counts as an entry of its row.  The ORDER of a row sum, hence its low bits, belongs to C, as it
+ *                does for ppr_chunk.  No float atomics, nothing depends on arrival order.
+ *   exactness    for one value of prop_chunk the result is bit for bit a function of (graph, features, hops, flags) alone: not of the stream, not of how columns
+ *                are tiled over lanes or workgroups, not of the zero padding of the store's row stride.  Column f of every level depends on column f of the
+ *                features alone.  A weighted store with all weights 1.0 gives the unweighted bits.  Level 0 is STORED, equal to the store's features bitwise:
+ *                the handle holds no pointer into the store, and destroying the store first is legal.
+ *   pair rows    gm_prop_pair_features: d_pairs device int32 [n, 2], any orientation, a == b allowed;  d_out[k, t, f] = x_t[a][f] * x_t[b][f] (GM_PROP_HADAMARD) or
+ *                fabsf(x_t[a][f] - x_t[b][f]) (GM_PROP_ABS_DIFF) for t = 0 .. hops: ONE fp32 operation on the rows gm_prop_rows returns, hence the same bits as
+ *                that operation in numpy float32, and the same for both orientations.  A pair with a node outside [0, N) gives zeros.
+ *   no mask flag the levels describe the WHOLE graph, as the sketches do: a pair's own edge cannot be taken out of them.
+ *   memory       a handle owns (hops + 1) * N * ld * 4 bytes in one allocation, ld = the store's feature row stride (F where F is a multiple of 4, else F padded
+ *                with zero columns to 32 or to a multiple of 64), laid out level-major, then node-major.  gm_set_tuning("prop_mib", M) / GM_PROP_MIB is the budget of one build in MiB, 0 = the library's
+ *                choice, 8 GiB: GM_ERANGE (the message names N, hops, F, the bytes and the budget) when the formula exceeds it.
+ * gm_store_propagate_build runs on `stream`, reads the graph's row lengths back once to cut the hub rows, takes the norms, the per-entry coefficients and the hub
+ * segments' partial rows from the stream-ordered pool, and returns after the stream has produced every level: any stream may read them afterwards.
+ * gm_prop_rows returns the rows of m nodes at one level, d_out: device float [m, F], dense (the padding columns never leave); duplicates are allowed, a node outside
+ * [0, N) gives a row of zeros, nothing behind row m - 1 is written.  Both readers run on `stream` and are complete in stream order; m == 0 / n == 0 is a no-op, with
+ * NULL pointers too.  gm_prop_dims fills whichever of its outputs is not NULL (bytes: the formula above).  gm_prop_destroy waits for the device and frees the levels.
+ * GM_EINVAL (the message names the value): a bad graph index, hops outside 1 .. 8, unknown flag bits, an unknown op, a level outside 0 .. hops, m or n negative or
+ * above INT32_MAX, a NULL argument with work to do, a negative prop_chunk or prop_mib.  GM_ERANGE: a build beyond prop_mib, a prop_chunk that cuts more than
+ * 2^25 segments, a call whose launch would pass 2^31 workgroups. */
+#define GM_PROP_SELF_LOOPS 1
+#define GM_PROP_HADAMARD 0
+#define GM_PROP_ABS_DIFF 1
+typedef struct gm_prop gm_prop_t;
+int32_t gm_store_propagate_build(const gm_store_t* s, int32_t g, int32_t hops, int32_t flags, void* stream, gm_prop_t** out);
+int32_t gm_prop_dims(const gm_prop_t* p, int64_t* n_nodes, int32_t* hops, int32_t* feat_dim, int32_t* flags, int64_t* bytes);
+int32_t gm_prop_rows(const gm_prop_t* p, int32_t level, const int32_t* d_nodes, int64_t m, float* d_out /* [m, F] */, void* stream);
+int32_t gm_prop_pair_features(const gm_prop_t* p, const int32_t* d_pairs, int64_t n, int32_t op, float* d_out /* [n, hops + 1, F] */, void* stream);
+void gm_prop_destroy(gm_prop_t* p);
+
 /* ---- Extraction: replaces Subgraphs.generate_subgraph / generate_subgraph_link_pred
  * (sdp.py:295-346: h-hop in-neighbour expansion, node sampling, G.subgraph) and dgl.batch
  * (sdp.py:399-406) for n_sets sets at once.  seeds/set_offsets are host arrays; set s owns seeds
