@@ -88,8 +88,11 @@ PROTOTYPES = {
     'gm_gcn_backward': (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp]),
     'gm_dense_update': (C.c_int, [vp, vp, i32, vp, i64, i32, vp, i32, vp]),
     'gm_dense_gemm': (C.c_int, [vp, vp, i64, i32, vp, i64, i32, i32, vp, i64, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i32, vp, vp]),
+    'gm_dense_fused_gemm': (C.c_int, [vp, i32, vp, i64, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, vp, vp, i64, i32, vp, vp, vp, i32, vp, vp]),
+    'gm_dense_wgrad_fused': (C.c_int, [vp, i32, vp, i64, i32, vp, i64, vp, i64, i32, vp, vp, vp, i64, vp, i64, i32, vp]),
     'gm_dense_aggregate': (C.c_int, [vp, i32, i32, vp, i64, i32, i32, vp, vp, i32, vp, i64, i32, vp, vp, vp, i32, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp]),
     'gm_dense_agg_info': (C.c_int, [vp, i32, vp]),
+    'gm_dense_fuse_counts': (C.c_int, [vp, vp]),
     'gm_dense_agg_table': (C.c_int, [vp, i32, i32, vp, i64, vp]),
     'gm_dense_dz_centre': (C.c_int, [vp, vp, i32, vp, i64, i32, vp, vp]),
     'gm_dense_wgrad_centre': (C.c_int, [vp, vp, i32, vp, i32, vp, i64, vp, i64, vp]),

@@ -98,6 +98,52 @@ extern "C" int gm_dense_gemm(const gm_batch_t* b, const float* x, int64_t ldx, i
     return rc;
 }
 
+// The fused aggregate + GEMM as gcn_forward's `fuse` branch launches it: gm_dense_gemm with gm_gemm_args::fuse2 set.  The table is always the batch's own
+// (table 0: d_fuse2 over the caller's x; 1: d_fuse2_feat over the batch's feature table), so the kernel reads no row outside its operands
+extern "C" int gm_dense_fused_gemm(const gm_batch_t* b, int32_t table, const float* x, int64_t ldx, int32_t K, const float* zside, int64_t ldz,
+                                   const float* zfull, int64_t ldzf, const float* W, int64_t w_stride, int32_t N, float* out, int64_t ldc, const float* s,
+                                   const float* s_keep, const float* bias, int64_t bias_stride, int32_t relu, uint8_t* relu_bits, float* zero_out,
+                                   uint32_t* amax_out, int32_t mode, int32_t* launched, void* stream) {
+    GM_REQUIRE(b && W && out && zside && K >= 1 && N >= 1 && ldz >= K && ldc >= N && (mode == 1 || mode == 2) && (table == 0 || table == 1), GM_EINVAL,
+               "dense_fused_gemm: bad arguments");
+    GM_REQUIRE(b->d_fuse2 && b->d_fuse2_feat, GM_EINVAL, "dense_fused_gemm: the batch carries no source tables");
+    GM_REQUIRE(table == 1 || (x && ldx >= K), GM_EINVAL, "dense_fused_gemm: table 0 needs x and ldx >= K");
+    GM_REQUIRE(table == 0 || (b->feat && (K == b->feat_dim || K == b->feat_ld)), GM_EINVAL, "dense_fused_gemm: table 1 needs K == feat_dim (%d)", b->feat_dim);
+    GM_REQUIRE(!amax_out || mode == 2, GM_EINVAL, "dense_fused_gemm: amax_out is an output of the two-piece kernels (mode 2)");
+    GM_REQUIRE(mode != 2 || (zfull && ldzf >= K), GM_EINVAL, "dense_fused_gemm: mode 2 takes its A bounds over a fully aggregated Z (zfull)");
+    GM_REQUIRE((N == 256 || N == 128) && K % 16 == 0 && K >= 32, GM_EINVAL, "dense_fused_gemm: the split kernels need N = 128 or 256 and K a multiple of 16 (>= 32)");
+    hipStream_t st = (hipStream_t)stream;
+    const int sets = b->sets, wsets = w_stride ? sets : 1;
+    gm_gemm_args g{};
+    g.B = W; g.b_stride = w_stride; g.C = out; g.ldc = ldc; g.K = K; g.N = N;
+    g.row_scale = s; g.row_scale_keep = s_keep; g.n_keep = b->rows; g.bias = bias; g.bias_stride = bias_stride; g.relu = relu ? 1 : 0;
+    g.relu_bits = relu_bits; g.zero_out = zero_out;
+    g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows; g.launched = launched;
+    g.zside = zside; g.ldz = ldz;
+    if (table == 1) { g.A = b->feat; g.lda = b->feat_ld; g.fuse2 = b->d_fuse2_feat; }
+    else { g.A = x; g.lda = ldx; g.fuse2 = b->d_fuse2; }
+    uint16_t* planes = nullptr; unsigned* slots = nullptr;
+    int rc = gm_alloc(&planes, (size_t)wsets * 3 * K * N, st);
+    gm_bound wb = gm_no_bound();
+    if (rc == GM_OK && mode == 2) {
+        // per-set bounds of the rows the kernel forms (slots [0, sets)), taken over the caller's fully aggregated Z -- never over zside, whose rows of one or
+        // two sources nobody wrote --, and one per weight matrix (slots [sets, sets + wsets)): gm_dense_gemm's over a stored Z
+        rc = gm_alloc(&slots, (size_t)(sets + wsets) * GM_BOUND_PAD, st);
+        if (rc == GM_OK && hipMemsetAsync(slots, 0, sizeof(unsigned) * (sets + wsets) * GM_BOUND_PAD, st) != hipSuccess) { gm_set_error("dense_fused_gemm: memset failed"); rc = GM_EHIP; }
+        if (rc == GM_OK) rc = set_row_amax(b, zfull, ldzf, K, slots, st);
+        if (rc == GM_OK) rc = gm_amax(W, w_stride, 0, (int64_t)K * N, wsets, slots + (int64_t)sets * GM_BOUND_PAD, GM_BOUND_PAD, st);
+        wb.amax = slots + (int64_t)sets * GM_BOUND_PAD; wb.stride = w_stride ? GM_BOUND_PAD : 0;
+        g.np = 2; g.a_bound = gm_no_bound(); g.a_bound.amax = slots; g.a_bound.stride = GM_BOUND_PAD; g.b_bound = wb; g.amax_out = amax_out;
+    }
+    if (rc == GM_OK) rc = gm_split_weights(W, w_stride, 0, K, N, 0, wsets, planes, st, mode == 2 ? 2 : 3, wb);
+    g.Bsplit = planes; g.bsplit_stride = w_stride ? (int64_t)3 * K * N : 0;
+    if (rc == GM_OK) rc = gm_launch_gemm_nn(g, st);
+    if (planes) gm_dev_free(planes, st);
+    if (slots) gm_dev_free(slots, st);
+    gm_batch_mark_use(b, st);
+    return rc;
+}
+
 // The dZ product of the last layer over a dQ that holds its centre rows only, as gcn_backward launches it under GM_DEAD_ROWS (tests)
 extern "C" int gm_dense_dz_centre(const gm_batch_t* b, const float* dQ, int32_t K, const float* W, int64_t w_stride, int32_t N, float* T, void* stream) {
     GM_REQUIRE(b && dQ && W && T && b->d_dq_tab, GM_EINVAL, "dense_dz_centre: bad arguments");
@@ -213,6 +259,45 @@ extern "C" int gm_dense_wgrad(const gm_batch_t* b, const float* x, int64_t ldx, 
     return rc;
 }
 
+// The weight gradient over a Z whose forward ran fused, as gcn_backward's `zfused` branch launches it: A holds the rows the table flags GM_FUSE_SELF, every other
+// row is formed from gx through the batch's own table (table 0: d_fuse2 over the caller's gx; 1: d_fuse2_feat over the batch's feature table)
+extern "C" int gm_dense_wgrad_fused(const gm_batch_t* b, int32_t table, const float* A, int64_t lda, int32_t K, const float* gx, int64_t ldgx, const float* g,
+                                    int64_t ldg, int32_t N, const float* s, const float* g_keep, float* dW, int64_t dw_stride, float* db, int64_t db_stride,
+                                    int32_t mode, void* stream) {
+    GM_REQUIRE(b && A && g && dW && db && K >= 1 && N >= 1 && lda >= K && ldg >= N && mode >= 0 && mode <= 2 && (table == 0 || table == 1), GM_EINVAL,
+               "dense_wgrad_fused: bad arguments");
+    GM_REQUIRE(K <= 2048 && N <= 2048, GM_ERANGE, "dense_wgrad_fused: K=%d N=%d: at most 2048 columns per operand", K, N);
+    GM_REQUIRE(b->d_fuse2 && b->d_fuse2_feat, GM_EINVAL, "dense_wgrad_fused: the batch carries no source tables");
+    GM_REQUIRE(table == 1 || (gx && ldgx >= K), GM_EINVAL, "dense_wgrad_fused: table 0 needs gx and ldgx >= K");
+    GM_REQUIRE(table == 0 || (b->feat && (K == b->feat_dim || K == b->feat_ld)), GM_EINVAL, "dense_wgrad_fused: table 1 needs K == feat_dim (%d)", b->feat_dim);
+    const int sets = b->sets;
+    const int64_t KN = (int64_t)K * N;
+    GM_REQUIRE(sets == 1 || (dw_stride >= KN && db_stride >= N), GM_EINVAL, "dense_wgrad_fused: per-set outputs overlap");
+    hipStream_t st = (hipStream_t)stream;
+    gm_wgrad_args w{};
+    w.A = A; w.lda = lda; w.K = K; w.G = g; w.ldg = ldg; w.N = N; w.a_scale = s; w.g_keep = g_keep;
+    w.chunks = b->d_chunks; w.n_chunks = b->n_chunks; w.set_chunk_off = b->d_set_chunk_off; w.sets = sets; w.rows = b->rows;
+    w.dW = dW; w.dw_stride = dw_stride; w.db = db; w.db_stride = db_stride;
+    w.fuse2 = table == 1 ? b->d_fuse2_feat : b->d_fuse2;
+    w.gx = table == 1 ? b->feat : gx; w.ldgx = table == 1 ? b->feat_ld : ldgx;
+    w.pick = mode == 0 ? GM_WGRAD_PICK_EXACT : GM_WGRAD_PICK_SPLIT;
+    unsigned* slots = nullptr;
+    int rc = gm_alloc(&w.partial, (size_t)std::max(1, b->n_chunks) * (size_t)(KN + N), st);
+    if (rc == GM_OK && mode == 2) {
+        // two-piece operands as gm_dense_wgrad marks them (the launcher refuses them with a table before any bound is read: the slots stay zero)
+        rc = gm_alloc(&slots, (size_t)(2 * sets + 1) * GM_BOUND_PAD, st);
+        if (rc == GM_OK && hipMemsetAsync(slots, 0, sizeof(unsigned) * (2 * sets + 1) * GM_BOUND_PAD, st) != hipSuccess) { gm_set_error("dense_wgrad_fused: memset failed"); rc = GM_EHIP; }
+        w.np = 2;
+        w.a_bound = gm_no_bound(); w.a_bound.amax = slots; w.a_bound.stride = GM_BOUND_PAD;
+        w.g_bound = gm_no_bound(); w.g_bound.amax = slots + (int64_t)sets * GM_BOUND_PAD; w.g_bound.stride = GM_BOUND_PAD;
+    }
+    if (rc == GM_OK) rc = gm_launch_wgrad(w, st);
+    if (w.partial) gm_dev_free(w.partial, st);
+    if (slots) gm_dev_free(slots, st);
+    gm_batch_mark_use(b, st);
+    return rc;
+}
+
 // ================================================================================ aggregate, exported for numerics tests
 // One launch of gm_launch_aggregate over one orientation of the batch with every field the production callers (gm_aggregate, batch_agg / gcn_forward,
 // gcn_backward) set, and the instantiation that ran (include/gmeta_hip.h)
@@ -282,7 +367,8 @@ extern "C" int gm_dense_aggregate(const gm_batch_t* b, int32_t transposed, int32
 
 // What the tests of gm_dense_aggregate need to know about orientation o of a batch: info[16] = {hub threshold, hub rows, rows per scheduled window, edges
 // per hub part (0: unsplit), hub parts, scheduled (0 / 1), rows of the batch's window-row list, its window, list schedule (0 / 1), stream row segments (0 until the
-// orientation's first stream-eligible launch), stream workgroups, hub workgroups among them, weighted, feat_dim, feat_ld, 0}
+// orientation's first stream-eligible launch), stream workgroups, hub workgroups among them, weighted, feat_dim, feat_ld, 0}.  (Sixteen entries for good: callers
+// hold exactly that many.)
 extern "C" int gm_dense_agg_info(const gm_batch_t* b, int32_t transposed, int64_t* info) {
     GM_REQUIRE(b && info, GM_EINVAL, "dense_agg_info: bad arguments");
     const int o = transposed ? 1 : 0;
@@ -291,15 +377,24 @@ extern "C" int gm_dense_agg_info(const gm_batch_t* b, int32_t transposed, int64_
     std::copy(v, v + 16, info);
     return GM_OK;
 }
+// ... and the tests of the fused kernels: counts[2] = {rows of more than GM_FUSE_MAXDEG sources (gm_batch::unfused_rows: the rows a fused pass still aggregates by
+// the ordinary kernel), their in-edges (unfused_edges)}
+extern "C" int gm_dense_fuse_counts(const gm_batch_t* b, int64_t* counts) {
+    GM_REQUIRE(b && counts, GM_EINVAL, "dense_fuse_counts: bad arguments");
+    counts[0] = b->unfused_rows; counts[1] = b->unfused_edges;
+    return GM_OK;
+}
 // Device copies of the batch's derived tables (which: 0 per-edge source norm of orientation o [edges] float, 1 per-edge feature row [edges] int32, 2 window-row
-// list [info[6]] int32, 3 hub rows of orientation o [info[1]] int32): n elements -> dst (device)
+// list [info[6]] int32, 3 hub rows of orientation o [info[1]] int32; 4 / 5 / 6 the per-row source tables gm_batch::d_fuse2 / d_fuse2_feat / d_dq_tab, [rows] entries
+// of four int32 {u0, u1, w0, w1}): n entries -> dst (device)
 extern "C" int gm_dense_agg_table(const gm_batch_t* b, int32_t which, int32_t transposed, void* dst, int64_t n, void* stream) {
-    GM_REQUIRE(b && dst && n >= 0 && which >= 0 && which <= 3, GM_EINVAL, "dense_agg_table: bad arguments");
+    GM_REQUIRE(b && dst && n >= 0 && which >= 0 && which <= 6, GM_EINVAL, "dense_agg_table: bad arguments");
     const int o = transposed ? 1 : 0;
-    const void* src = which == 0 ? (const void*)b->d_enorm[o] : which == 1 ? (const void*)b->d_efeat : which == 2 ? (const void*)b->d_mid : (const void*)b->d_heavy[o];
-    const int64_t have = which <= 1 ? b->edges : which == 2 ? b->n_mid : b->n_heavy[o];
+    const void* src = which == 0 ? (const void*)b->d_enorm[o] : which == 1 ? (const void*)b->d_efeat : which == 2 ? (const void*)b->d_mid : which == 3 ? (const void*)b->d_heavy[o]
+                    : which == 4 ? (const void*)b->d_fuse2 : which == 5 ? (const void*)b->d_fuse2_feat : (const void*)b->d_dq_tab;
+    const int64_t have = which <= 1 ? b->edges : which == 2 ? b->n_mid : which == 3 ? b->n_heavy[o] : b->rows;
     GM_REQUIRE(src && n <= have, GM_EINVAL, "dense_agg_table: table %d holds %lld entries", which, (long long)(src ? have : 0));
-    if (n) GM_HIP(hipMemcpyAsync(dst, src, 4 * (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (n) GM_HIP(hipMemcpyAsync(dst, src, (which >= 4 ? 16 : 4) * (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     gm_batch_mark_use(b, (hipStream_t)stream);
     return GM_OK;
 }

@@ -622,6 +622,17 @@ int gm_dense_gemm(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, c
                   float* out, int64_t ldc, const float* s, const float* s_keep, const float* bias, int64_t bias_stride, int32_t relu,
                   uint8_t* relu_bits, const float* mask_h, const uint8_t* mask_b, float* zero_out, uint32_t* amax_out, int32_t mode,
                   int32_t* launched, void* stream);
+/* The fused aggregate + GEMM of a forward pass, exported for numerics tests: gm_dense_gemm's split kernels with the A operand formed in the loader,
+ *   Z[r] = w0 * X[u0] + w1 * X[u1]  from the batch's per-row source table {u0, u1, w0, w1} (gm_dense_agg_table 4 / 5),  out = epi(s (Z @ W_t) + bias_t).
+ * table 0: X = x [rows, ldx], sources are batch rows;  table 1: X = the batch's feature table (x, ldx ignored; K = its feature width, or its row stride).
+ * The table is always the batch's own.  zside [rows, ldz]: the finished aggregate of the rows of more than two sources (the only rows of it that are read;
+ * 16-byte aligned, ldz a multiple of 4).  mode 1: three pieces;  2: two pieces, with the per-set bounds of A taken over zfull [rows, ldzf], a fully
+ * aggregated Z (never over zside).  The other parameters are gm_dense_gemm's; launched receives the id of k_gemm_split_p<true, ...> (40, 41, 44, 45).
+ * GM_EINVAL (nothing launched, no output touched): K below 64, a misaligned zside, ldz not a multiple of 4, and gm_dense_gemm's refusals. */
+int gm_dense_fused_gemm(const gm_batch_t* b, int32_t table, const float* x, int64_t ldx, int32_t K, const float* zside, int64_t ldz, const float* zfull,
+                        int64_t ldzf, const float* W, int64_t w_stride, int32_t N, float* out, int64_t ldc, const float* s, const float* s_keep,
+                        const float* bias, int64_t bias_stride, int32_t relu, uint8_t* relu_bits, float* zero_out, uint32_t* amax_out, int32_t mode,
+                        int32_t* launched, void* stream);
 /* One aggregate launch over one orientation of the batch (0: the in-edge CSR, transposed: the by-source CSR) with every option the library's own callers
  * set, exported for numerics tests of every aggregate kernel (agg.hip, agg_stream.hip):
  *   out[v, :width] = epi(|s_out[v]| * sum over the edges e of row v of w_e * X[src_e, :] + bias_t)      for the rows v of set t.
@@ -648,9 +659,15 @@ int gm_dense_aggregate(const gm_batch_t* b, int32_t transposed, int32_t x_src, c
                        void* stream);
 /* What those tests need to know about one orientation of a batch: info[16] = {hub threshold, hub rows, rows per scheduled window, edges per hub part (0: unsplit),
  * hub parts, scheduled, rows of the batch's window-row list, its window, list schedule present, stream row segments (0 before the orientation's first
- * stream-eligible launch), stream workgroups, hub workgroups among them, weighted, feature width, feature row stride, 0};  gm_dense_agg_table copies n entries of
- * a derived table to dst (device): which 0 per-edge source norm (float), 1 per-edge feature row, 2 window-row list, 3 hub rows (int32). */
+ * stream-eligible launch), stream workgroups, hub workgroups among them, weighted, feature width, feature row stride, 0};  gm_dense_fuse_counts: counts[2] = {rows
+ * of more than two sources in the in-edge CSR (the rows a fused pass still aggregates by the ordinary kernel), their in-edges};  gm_dense_agg_table copies n entries of
+ * a derived table to dst (device): which 0 per-edge source norm (float), 1 per-edge feature row, 2 window-row list, 3 hub rows (int32); 4 / 5 / 6 the per-row
+ * source tables of the fused kernels, [rows] entries of four int32 {u0, u1, w0, w1} (w: fp32 bits): 4 sources as batch rows, 5 as rows of the feature table,
+ * 6 the last layer's dQ table.  A source flagged 0x40000000 is the row's own finished row, 0x20000000 an all-zero row:
+ *   no source {ZERO, ZERO, 1, 0};  one {u0, u0, w0, 0};  two {u0, u1, w0, w1};  more {row | SELF, row | SELF, 1, 0};  w = norm[u] (x the edge's weight);
+ *   dQ table: a centre row {row | SELF, ZERO, 1, 0}, any other {ZERO, ZERO, 0, 0}. */
 int gm_dense_agg_info(const gm_batch_t* b, int32_t transposed, int64_t* info);
+int gm_dense_fuse_counts(const gm_batch_t* b, int64_t* counts);
 int gm_dense_agg_table(const gm_batch_t* b, int32_t which, int32_t transposed, void* dst, int64_t n, void* stream);
 /* The last layer's dZ product and weight gradient where dQ holds its CENTRE rows only (GM_DEAD_ROWS: gm_meta_step no longer zero-fills the others;
  * their bytes may be anything), exported for tests:  T[r, :N] = norm[r] * (dQ0[r, :K] @ W_t^T)  with W_t stored [N, K] and dQ0 = dQ on the batch's
@@ -682,6 +699,15 @@ int gm_dense_wgrad_e1(const gm_batch_t* b, const float* x, int32_t Kx, const flo
 int gm_dense_wgrad(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, const float* g, int64_t ldg, int32_t N, const float* s,
                    const float* gb, int64_t ldgb, float* dW, int64_t dw_stride, float* db, int64_t db_stride, int32_t mode,
                    const float* cur, float* next, int64_t p_stride, float lr, float* wt, uint16_t* pl_fwd, uint16_t* pl_dz, void* stream);
+/* The same gradient over a Z whose forward ran fused, exported for numerics tests:  dW_t = sum_r (|s[r]| Z[r, :])^T g0[r, :],  db_t = sum_r g0[r, :],  with
+ * Z[r] formed from gx through the batch's own per-row source table as in gm_dense_fused_gemm (table 0: gx [rows, ldgx];  1: the batch's feature table) and
+ * read from A [rows, lda] only on the rows of more than two sources.  s: row scale or NULL;  g_keep (or NULL): the row scale again with the sign bit set on
+ * the rows of g that nobody wrote -- they enter as zeros whatever their bytes hold (g0; without g_keep g0 = g), and |g_keep| scales Z in place of s.
+ * mode 1: the three-piece split kernel (K, N in {128, 256}).  Modes 0 (exact kernels) and 2 (two-piece operands) cannot take a table: GM_EINVAL, no
+ * output touched. */
+int gm_dense_wgrad_fused(const gm_batch_t* b, int32_t table, const float* A, int64_t lda, int32_t K, const float* gx, int64_t ldgx, const float* g,
+                         int64_t ldg, int32_t N, const float* s, const float* g_keep, float* dW, int64_t dw_stride, float* db, int64_t db_stride,
+                         int32_t mode, void* stream);
 
 /* ---- Prototypical losses (meta.py:28-54 proto_loss_spt, 56-79 proto_loss_qry), per set.
  * y: HOST int32 [subs] labels.  Outputs (device): loss[sets], acc[sets], protos[sets, c_task, n_out]

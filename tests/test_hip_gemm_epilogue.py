@@ -44,7 +44,7 @@ SHORT_SETS = [1, 15, 16, 17, 31, 33, 127, 128, 129, 255, 257, 1000]
 CAPPED_PATTERN = [100, 129, 256, 37, 200, 1, 128]        # 10 tiles
 
 # the instantiations gm_dense_gemm can reach, by GM_GEMM_ID_* (gm_internal.h).  The fused feeders k_gemm_split_p<true, ...> (ids 40 .. 45)
-# need the batch's aggregate tables and are tested bitwise against this pass elsewhere.
+# need the batch's aggregate tables: test_hip_fused_numerics.py launches them (gm_dense_fused_gemm) against fp64 and bitwise against this pass.
 KERNELS = {1: 'glds<4>', 2: 'glds<2>', 3: 'glds<1>', 4: 'glds_small'}
 for _wi, _wc in enumerate((1, 2, 4)):
     for _vec in (0, 1):
