@@ -7,7 +7,7 @@ LIB_PATH = os.environ.get('GMETA_HIP_LIB') or os.path.join(HERE, 'libgmeta_hip.s
 
 GM_MAX_GCN = 4
 (F_SUB_OFF, F_SET_SUB_OFF, F_PARENT, F_GRAPH, F_INDPTR, F_INDICES, F_INDPTR_T, F_INDICES_T, F_CENTRE, F_NORM,
- F_FEAT_ROW, F_NORM_SRC, F_NORM_CENTRE, F_EDGE_W, F_EDGE_W_T, F_HOP, F_NORM_E1, F_EDGE_CENTRE_T) = range(18)
+ F_FEAT_ROW, F_NORM_SRC, F_NORM_CENTRE, F_EDGE_W, F_EDGE_W_T, F_HOP, F_NORM_E1, F_EDGE_CENTRE_T, F_OBS_CENTRE, F_OBS_E1) = range(20)
 LINK_SYMMETRIC = 2      # GM_LINK_SYMMETRIC: the link_pred mode of gm_extract / gm_extract_pair with h hops around both endpoints
 LINK_MASK_TARGET = 4    # GM_LINK_MASK_TARGET: flag OR-ed onto a pair mode -- the subgraph of (i, j) is built without the i-j edges themselves
 NEG_MODES = {'uniform': 0, 'two_hop': 1}      # GM_NEG_UNIFORM / GM_NEG_TWO_HOP (gm_store_negative_pairs)

@@ -134,6 +134,8 @@ static int field_ptr(const gm_batch_t* b, int32_t field, void** p, int64_t* byte
         case GM_F_NORM_CENTRE: *p = b->d_norm_c; *bytes = 4ll * b->rows; break;
         case GM_F_NORM_E1: *p = b->d_norm_e1; *bytes = 4ll * b->rows; break;
         case GM_F_EDGE_CENTRE_T: *p = b->d_ect; *bytes = 4ll * b->edges; break;
+        case GM_F_OBS_CENTRE: *p = b->d_obs[0]; *bytes = 4ll * b->rows; break;
+        case GM_F_OBS_E1: *p = b->d_obs[1]; *bytes = 4ll * b->rows; break;
         case GM_F_EDGE_W: case GM_F_EDGE_W_T:
             GM_REQUIRE(b->weighted, GM_EINVAL, "batch field %s: the batch is unweighted (its store was created without edge weights)", field == GM_F_EDGE_W ? "GM_F_EDGE_W" : "GM_F_EDGE_W_T");
             *p = b->d_ew[field == GM_F_EDGE_W ? 0 : 1]; *bytes = 4ll * b->edges; break;

@@ -386,12 +386,14 @@ extern "C" int gm_dense_fuse_counts(const gm_batch_t* b, int64_t* counts) {
 }
 // Device copies of the batch's derived tables (which: 0 per-edge source norm of orientation o [edges] float, 1 per-edge feature row [edges] int32, 2 window-row
 // list [info[6]] int32, 3 hub rows of orientation o [info[1]] int32; 4 / 5 / 6 the per-row source tables gm_batch::d_fuse2 / d_fuse2_feat / d_dq_tab, [rows] entries
-// of four int32 {u0, u1, w0, w1}): n entries -> dst (device)
+// of four int32 {u0, u1, w0, w1}; 7 / 8 / 9 the forward-only passes' tables of GM_DEAD_ROWS=3 in the same layout: the last layer's (gm_batch::d_fwd_tab[0]), the layer
+// below it over batch rows (d_fwd_tab[1]) and over the feature table (d_fwd_tab_feat)): n entries -> dst (device)
 extern "C" int gm_dense_agg_table(const gm_batch_t* b, int32_t which, int32_t transposed, void* dst, int64_t n, void* stream) {
-    GM_REQUIRE(b && dst && n >= 0 && which >= 0 && which <= 6, GM_EINVAL, "dense_agg_table: bad arguments");
+    GM_REQUIRE(b && dst && n >= 0 && which >= 0 && which <= 9, GM_EINVAL, "dense_agg_table: bad arguments");
     const int o = transposed ? 1 : 0;
     const void* src = which == 0 ? (const void*)b->d_enorm[o] : which == 1 ? (const void*)b->d_efeat : which == 2 ? (const void*)b->d_mid : which == 3 ? (const void*)b->d_heavy[o]
-                    : which == 4 ? (const void*)b->d_fuse2 : which == 5 ? (const void*)b->d_fuse2_feat : (const void*)b->d_dq_tab;
+                    : which == 4 ? (const void*)b->d_fuse2 : which == 5 ? (const void*)b->d_fuse2_feat : which == 6 ? (const void*)b->d_dq_tab
+                    : which == 7 ? (const void*)b->d_fwd_tab[0] : which == 8 ? (const void*)b->d_fwd_tab[1] : (const void*)b->d_fwd_tab_feat;
     const int64_t have = which <= 1 ? b->edges : which == 2 ? b->n_mid : which == 3 ? b->n_heavy[o] : b->rows;
     GM_REQUIRE(src && n <= have, GM_EINVAL, "dense_agg_table: table %d holds %lld entries", which, (long long)(src ? have : 0));
     if (n) GM_HIP(hipMemcpyAsync(dst, src, (which >= 4 ? 16 : 4) * (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream));

@@ -804,6 +804,57 @@ int64_t gm_batch_e1_edges(const gm_batch* b, hipStream_t s) {
     gm_dev_free(cnt, s);
     return ok ? (b->n_e1_edges = (int64_t)h) : fallback;
 }
+// GM_DEAD_ROWS=3 tables (gm_batch::d_fwd_tab / d_fwd_tab_feat / d_obs), after k_e1_rows: the source tables and the keep flags of the passes nobody differentiates.
+// A row is observable in the last layer where it is a centre (sign bit of norm_c clear), in the layer below where it is the source of an in-edge of a centre
+// (sign bit of norm_e1 clear): there it keeps d_fuse2's (d_fuse2_feat's) entry and the flag +1, everywhere else it reads the zero row and carries -1
+__global__ void k_fwd_tables(const int4* f2, const int4* f2_feat, const float* norm_c, const float* norm_e1, int64_t rows, int4* tab_c, int4* tab_e1, int4* tab_e1_feat,
+                             float* obs_c, float* obs_e1) {
+    auto pick = [](const bool on, const int4 t) { return make_int4(on ? t.x : GM_FUSE_ZERO, on ? t.y : GM_FUSE_ZERO, on ? t.z : 0, on ? t.w : 0); };
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
+        const bool c = !(__float_as_uint(norm_c[r]) >> 31), e = !(__float_as_uint(norm_e1[r]) >> 31);
+        const int4 t = f2[r], tf = f2_feat[r];
+        tab_c[r] = pick(c, t); tab_e1[r] = pick(e, t); tab_e1_feat[r] = pick(e, tf);
+        obs_c[r] = c ? 1.f : -1.f; obs_e1[r] = e ? 1.f : -1.f;
+    }
+}
+// what the partial aggregate launch over flag vector `obs` touches: rows of more than maxdeg in-edges with a positive flag and their in-edges (out[0], out[1]); their
+// sources marked in `bits` (k_count_bits counts them)
+__global__ void k_fwd_count(const int32_t* indptr, const int32_t* indices, const float* obs, int64_t rows, int maxdeg, uint32_t* bits, unsigned long long* out) {
+    unsigned long long nr = 0, ne = 0;
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
+        const int p = indptr[r], d = indptr[r + 1] - p;
+        if (d <= maxdeg || (__float_as_uint(obs[r]) >> 31)) continue;
+        ++nr; ne += (unsigned long long)d;
+        for (int e = p; e < p + d; ++e) { const int u = indices[e]; atomicOr(&bits[u >> 5], 1u << (u & 31)); }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { nr += __shfl_down(nr, off, 64); ne += __shfl_down(ne, off, 64); }
+    if ((threadIdx.x & 63) == 0 && nr) { atomicAdd(out, nr); atomicAdd(out + 1, ne); }
+}
+int gm_batch_fwd_counts(const gm_batch* b, int which, hipStream_t s, int64_t* out) {
+    GM_REQUIRE(b && out && (which == 0 || which == 1), GM_EINVAL, "batch_fwd_counts: bad arguments");
+    int64_t* have = b->fwd_cnt[which];
+    if (have[0] < 0) {
+        GM_REQUIRE(b->d_obs[which] && b->rows > 0, GM_EINVAL, "batch_fwd_counts: the batch carries no forward-only tables");
+        const int64_t words = (b->rows + 31) / 32;
+        uint32_t* bits = nullptr; unsigned long long* cnt = nullptr; unsigned long long h[3] = {0, 0, 0};
+        int rc = gm_alloc(&bits, (size_t)words, s);
+        if (rc == GM_OK) rc = gm_alloc(&cnt, 3, s);
+        bool ok = rc == GM_OK && hipMemsetAsync(bits, 0, 4 * (size_t)words, s) == hipSuccess && hipMemsetAsync(cnt, 0, 24, s) == hipSuccess;
+        if (ok) {
+            hipLaunchKernelGGL(k_fwd_count, dim3((int)std::min<int64_t>(2048, (b->rows + 255) / 256)), dim3(256), 0, s, b->d_indptr, b->d_indices, b->d_obs[which], (int64_t)b->rows,
+                               GM_FUSE_MAXDEG, bits, cnt);
+            hipLaunchKernelGGL(k_count_bits, dim3((int)std::min<int64_t>(512, (words + 255) / 256)), dim3(256), 0, s, bits, words, cnt + 2);
+            ok = hipMemcpyAsync(h, cnt, 24, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        }
+        if (bits) gm_dev_free(bits, s);
+        if (cnt) gm_dev_free(cnt, s);
+        if (!ok) { (void)hipGetLastError(); gm_set_error("batch_fwd_counts: counting failed"); return GM_EHIP; }
+        have[1] = (int64_t)h[1]; have[2] = (int64_t)h[2]; have[0] = (int64_t)h[0];
+    }
+    out[0] = have[0]; out[1] = have[1]; out[2] = have[2];
+    return GM_OK;
+}
 __global__ void k_copy_add(int32_t* dst, const int32_t* src, int64_t n, int32_t add) {
     for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) dst[k] = src[k] + add;
 }
@@ -1137,6 +1188,15 @@ static int finalize_finish(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
         hipLaunchKernelGGL(k_e1_tables, dim3(grid_for(std::max<int64_t>(b->edges, b->rows), 4096)), dim3(256), 0, s, b->d_indices_t, (int64_t)b->edges, b->d_norm, b->d_norm_c, (int64_t)b->rows, b->d_ect, b->d_norm_e1, b->d_n_e1_rows);
         if (b->n_e1 > 0) hipLaunchKernelGGL(k_e1_rows, dim3((b->n_e1 + 255) / 256), dim3(256), 0, s, b->d_e1_row, b->n_e1, b->d_norm_e1, b->d_n_e1_rows);
         GM_HIP(hipGetLastError());
+        if (b->d_fuse2 && b->d_fuse2_feat) {      // GM_DEAD_ROWS=3: the forward-only passes' source tables and keep flags over the same two row sets
+            int4 *tc = nullptr, *te = nullptr, *tf = nullptr;
+            GM_TRY(gm_balloc(b, &tc, (size_t)b->rows, s)); GM_TRY(gm_balloc(b, &te, (size_t)b->rows, s)); GM_TRY(gm_balloc(b, &tf, (size_t)b->rows, s));
+            GM_TRY(gm_balloc(b, &b->d_obs[0], (size_t)b->rows, s)); GM_TRY(gm_balloc(b, &b->d_obs[1], (size_t)b->rows, s));
+            hipLaunchKernelGGL(k_fwd_tables, dim3(grid_for(b->rows, 4096)), dim3(256), 0, s, (const int4*)b->d_fuse2, (const int4*)b->d_fuse2_feat, b->d_norm_c, b->d_norm_e1, (int64_t)b->rows,
+                               tc, te, tf, b->d_obs[0], b->d_obs[1]);
+            GM_HIP(hipGetLastError());
+            b->d_fwd_tab[0] = tc; b->d_fwd_tab[1] = te; b->d_fwd_tab_feat = tf;
+        }
     }
     std::vector<int32_t> ccoff, ecoff, c_set_off(b->sets + 1), e_set_off(b->sets + 1);      // per set: its centres, and the in-edges of its centres
     for (int t = 0; t <= b->sets; ++t) { c_set_off[t] = b->h_set_sub_off[t] * nc; e_set_off[t] = eoff[b->h_set_sub_off[t] * nc]; }

@@ -206,6 +206,12 @@ struct gm_batch {
     int32_t* d_n_e1_rows = nullptr;    // [1]    rows with the bit clear, counted on the device (gm_batch_e1_rows reads it at first use)
     mutable int64_t n_e1_rows = -1;
     mutable int64_t n_e1_edges = -1;   //        by-source edges of those rows (profiling only: counted on first use, gm_batch_e1_edges)
+    // GM_DEAD_ROWS=3 (k_fwd_tables, after k_e1_rows): the same two row sets for the passes nobody differentiates, whose only observable values are the centre rows
+    // of H_L.  [0]: the last layer (observable rows = the centre rows), [1]: the layer below it (the sources of the centres' in-edges)
+    void* d_fwd_tab[2] = {nullptr, nullptr};   // [rows] int4: d_fuse2's entry on the observable rows, {GM_FUSE_ZERO, GM_FUSE_ZERO, 0, 0} on every other row (gm_gemm_args::fuse2)
+    void* d_fwd_tab_feat = nullptr;            // [rows] int4: d_fuse2_feat's entry on the [1] rows -- where the layer below the last gathers from the feature table
+    float* d_obs[2] = {nullptr, nullptr};      // [rows] +1 on the observable rows, -1 on every other row: gm_agg_args::s_out + keep_signed of the partial aggregate launches (a scale of exactly 1)
+    mutable int64_t fwd_cnt[2][3] = {{-1, -1, -1}, {-1, -1, -1}};      // observable rows of more than GM_FUSE_MAXDEG sources, their in-edges, their distinct sources (profiling only: counted on first use, gm_batch_fwd_counts)
     float* d_e1_norm = nullptr;        // [n_e1] norm[source row]
     float* d_e1_coef = nullptr;        // [n_e1] weighted batches only: edge weight x norm[source row] (the transposed aggregate's coefficient; d_e1_norm stays the row scale)
     int32_t* d_c_tiles = nullptr; int32_t n_c_tiles = 0;          // GEMM tiles over centre rows (per set)
@@ -245,7 +251,8 @@ struct gm_knobs {
     int gemm_split_min_tiles;      // -1: a quarter of the current device's CUs
     int centre_store;              // GM_CENTRE_STORE: the last layer's update stores only the centre rows of its activation -- in every pass (2, default), in the forward-only passes (1) -- or every row (0)
     int dead_rows;                 // GM_DEAD_ROWS: rows no later kernel reads are computed and not stored / not zero-filled (off with GM_CENTRE_STORE=0 too): H_l below the last layer at rows without an out-edge, dQ_L outside the centre rows (1);
-                                   // and, one level down the dense backward, T_L outside the centre rows and dQ_{L-1} outside the sources of the centres' in-edges (2, default)
+                                   // and, one level down the dense backward, T_L outside the centre rows and dQ_{L-1} outside the sources of the centres' in-edges (2);
+                                   // and, one level down the passes nobody differentiates, Z_L outside the centre rows, H_{L-1} and Z_{L-1} outside the sources of the centres' in-edges (3, default)
     int fuse_agg, head_stage;
     int fuse_diff;                 // GM_FUSE_DIFF: the differentiated passes of the dense schedule take the fused aggregate + GEMM too, their weight gradients form Z's rows from the source table: 2 (default) everywhere except a support batch whose full launches take the stream aggregate, 1 everywhere, 0 never
     int agg_mid_win;               // GM_AGG_MID_WIN: rows per wave window over that list (0 = by its length)
@@ -699,6 +706,9 @@ bool gm_prof_enabled();
 int64_t gm_batch_unfused_sources(const gm_batch* b, hipStream_t s);
 // distinct source rows of the centres' in-edges (the rows gm_batch::d_norm_e1 keeps): read back at first use (synchronises the stream) -- the launch accounting and the tests ask for it
 int64_t gm_batch_e1_rows(const gm_batch* b, hipStream_t s);
+// what a forward-only partial aggregate launch touches at GM_DEAD_ROWS=3 (which: 0 the last layer, 1 the layer below): out[3] = {rows it writes (more than GM_FUSE_MAXDEG sources
+// and gm_batch::d_obs[which] positive), their in-edges, their distinct sources}.  Counted at first use (synchronises the stream): the launch accounting and the tests ask for it
+int gm_batch_fwd_counts(const gm_batch* b, int which, hipStream_t s, int64_t* out);
 // by-source edges of those rows: counted on the device at first use (synchronises the stream) -- only the launch accounting asks for it; gm_batch::edges where it cannot be had
 int64_t gm_batch_e1_edges(const gm_batch* b, hipStream_t s);
 void gm_prof_note(int cat, int64_t work);      // adds work to a category without timing events

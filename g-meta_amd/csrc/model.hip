@@ -933,9 +933,45 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
         for (int l = 0; l < GM_MAX_GCN; ++l) c.hv[l] = c.tv[l] = false;
         c.dqv = false;
     }
+    // an aggregate-first layer's update runs on the split kernel ...
+    auto layer_split_ok = [&](int l) {
+        return c.Wsplit && gm_gemm_split_ok(b->n_tiles, L.dims[l], L.dims[l + 1]) && ((uintptr_t)(params + L.b_off[l]) & 15) == 0 && pstride % 4 == 0;
+    };
+    // ... and takes the fused aggregate + GEMM: the passes nobody differentiates (fwd_only == 1) ...
+    auto layer_fuse = [&](int l) {
+        const int fi = L.dims[l], fo = L.dims[l + 1];
+        const bool gather = (l == 0 && !c.x0_user);
+        // ... and, round 6, the passes that ARE differentiated by the dense backward (fwd_only == 2: the support passes, the last query pass): their only
+        // other reader of Z_l is the weight gradient, whose split kernel forms the same rows from the same table (gm_wgrad_gather_ok; three-piece
+        // arithmetic only) -- the differentiated passes no longer write and re-read Z_l either (GM_FUSE_DIFF=0: as before)
+        // GM_FUSE_DIFF=2: ... except where the pass's full launches would take the stream aggregate (a support batch with stream tables, agg_stream.hip):
+        // that kernel runs INSIDE the CUs the query stream's GEMM occupies, a partial window launch competes with it for them
+        const bool keeps_stream = gm_knob().fuse_diff == 2 && c.is_support && gm_knob().agg_stream && gm_stream_batch_ok(b, 0);
+        const bool diff_ok = fwd_only == 2 && gm_knob().fuse_diff && !keeps_stream && c.np != 2 && !c.cone && gm_wgrad_gather_ok(b->n_chunks, fi, fo);
+        return (fwd_only == 1 || diff_ok) && gm_get_fuse_agg() && layer_split_ok(l) && !(l == 0 && reuse_z1) && fi >= 64 && fi % 4 == 0 && b->d_fuse2 && b->d_enorm[0] &&
+               (!gather || (b->feat_ld % 4 == 0 && b->feat_ld >= fi)) &&
+               // worth it only where a good part of the rows has one or two sources: on dense batches (Tissue shape: ~30 in-edges per
+               // row) nearly every row still goes through the ordinary aggregate and the gather feeders only cost (3.30 -> 3.21 ms)
+               2 * b->unfused_rows <= b->rows;
+    };
+    // GM_DEAD_ROWS=3: the same rule one level down the passes nobody differentiates (fwd_only == 1).  All anyone reads of such a pass is H_L at the centre rows, so
+    // Z_L is observable at the centre rows only, and H_{L-1} and Z_{L-1} only at the sources of the centres' in-edges (the rows gm_batch::d_norm_e1 keeps).  Every tile
+    // and every MFMA is still issued, no product and no sum that reaches a stored value is dropped or reordered:
+    //  * the fused loaders read Z_l / H_{l-1} through gm_batch::d_fwd_tab (d_fwd_tab_feat), which sends every unobservable row to the zero row: they never touch a
+    //    row this pass did not write;
+    //  * the partial aggregate launches form the observable rows only (s_out = gm_batch::d_obs: +-1, keep_signed -- the scale is exactly the 1 the launch applies
+    //    without it; flagged rows stop at their descriptor, agg.hip: agg_unobservable);
+    //  * the update below the last stores the rows d_norm_e1 keeps instead of every row with an out-edge (d_norm_src).
+    // Under level 2's preconditions (centre readout, three pieces, the batch's own centres and tables) and where the last layer runs fused on the split kernel
+    const int Lg = L.n_gcn;
+    const bool fwd3_last = fwd_only == 1 && gm_knob().dead_rows >= 3 && dead_rows && gm_knob().centre_store >= 1 && !mean && c.np != 2 && b->d_norm_c && b->d_norm_e1 &&
+                           b->d_fwd_tab[0] && b->d_obs[0] && L.dims[Lg - 1] <= L.dims[Lg] && layer_fuse(Lg - 1) &&
+                           (Lg >= 2 || c.x0_user);      // (a last layer that gathers from the feature table has no table of its own: one-layer models stay as they are)
+    const bool fwd3_below = fwd3_last && Lg >= 2 && L.dims[Lg - 2] <= L.dims[Lg - 1] && layer_split_ok(Lg - 2) && b->d_fwd_tab[1] && b->d_fwd_tab_feat && b->d_obs[1];
     for (int l = 0; l < L.n_gcn; ++l) {
         const int fi = L.dims[l], fo = L.dims[l + 1];
         const bool gather = (l == 0 && !c.x0_user);
+        const int obs = (fwd3_last && l == Lg - 1) ? 0 : (fwd3_below && l == Lg - 2) ? 1 : -1;      // GM_DEAD_ROWS=3: the layer's observable row set (gm_batch::d_obs), or none
         if (fi > fo) {                      // learner.py:34-40: multiply first, then aggregate
             const float* A = xin; int64_t lda = fi;
             if (gather) { GM_TRY(gm_gather_rows(b, b->d_feat_row, b->rows, fi, c.X0, st)); A = c.X0; }
@@ -948,19 +984,8 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
             a.out = c.H[l]; a.width = fo; a.relu_bits = c.M[l];
             GM_TRY(launch_agg(a, gm_aggregate_bytes(b, fo), gm_aggregate_bytes(b, fo), st));
         } else {                            // learner.py:41-47: aggregate first, then multiply
-            const bool split_ok = c.Wsplit && gm_gemm_split_ok(b->n_tiles, fi, fo) && ((uintptr_t)(params + L.b_off[l]) & 15) == 0 && pstride % 4 == 0;
-            // ... and, round 6, the passes that ARE differentiated by the dense backward (fwd_only == 2: the support passes, the last query pass): their only
-            // other reader of Z_l is the weight gradient, whose split kernel forms the same rows from the same table (gm_wgrad_gather_ok; three-piece
-            // arithmetic only) -- the differentiated passes no longer write and re-read Z_l either (GM_FUSE_DIFF=0: as before)
-            // GM_FUSE_DIFF=2: ... except where the pass's full launches would take the stream aggregate (a support batch with stream tables, agg_stream.hip):
-            // that kernel runs INSIDE the CUs the query stream's GEMM occupies, a partial window launch competes with it for them
-            const bool keeps_stream = gm_knob().fuse_diff == 2 && c.is_support && gm_knob().agg_stream && gm_stream_batch_ok(b, 0);
-            const bool diff_ok = fwd_only == 2 && gm_knob().fuse_diff && !keeps_stream && c.np != 2 && !c.cone && gm_wgrad_gather_ok(b->n_chunks, fi, fo);
-            const bool fuse = (fwd_only == 1 || diff_ok) && gm_get_fuse_agg() && split_ok && !(l == 0 && reuse_z1) && fi >= 64 && fi % 4 == 0 && b->d_fuse2 && b->d_enorm[0] &&
-                              (!gather || (b->feat_ld % 4 == 0 && b->feat_ld >= fi)) &&
-                              // worth it only where a good part of the rows has one or two sources: on dense batches (Tissue shape: ~30 in-edges per
-                              // row) nearly every row still goes through the ordinary aggregate and the gather feeders only cost (3.30 -> 3.21 ms)
-                              2 * b->unfused_rows <= b->rows;
+            const bool split_ok = layer_split_ok(l);
+            const bool fuse = layer_fuse(l);
             c.zfused[l] = fuse && fwd_only == 2;
             if (!(l == 0 && reuse_z1 && c.z1_valid)) {
                 gm_agg_args a; GM_TRY(batch_agg(c, 0, st, a));
@@ -978,13 +1003,25 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
                     }
                     // SURVEY 8(d)'s B_agg restricted to what this launch touches: every indptr entry, the indices / norms of the rows it writes,
                     // those rows (written once) and their sources (read once: the high-degree rows of a subgraph reach ~all of its rows)
-                    const int64_t pb0 = 4 * (b->rows + 1) + 4 * b->unfused_edges + 4 * b->unfused_rows + 4 * b->unfused_rows * (int64_t)fi;
+                    int64_t pb0 = 4 * (b->rows + 1) + 4 * b->unfused_edges + 4 * b->unfused_rows + 4 * b->unfused_rows * (int64_t)fi;
                     // (their DISTINCT sources when the launch accounting is on: counted once per batch; the bound min(edges, rows) otherwise -- nobody reads it then)
-                    const int64_t src = gm_prof_enabled() ? gm_batch_unfused_sources(b, st) : std::min<int64_t>(b->unfused_edges, b->rows);
+                    int64_t src, src_bound = std::min<int64_t>(b->unfused_edges, b->rows);
+                    if (obs >= 0) {
+                        // GM_DEAD_ROWS=3: of those rows only the observable ones are formed; the others stop at their descriptor (list entry, row bounds, flag)
+                        a.s_out = b->d_obs[obs]; a.keep_signed = 1;
+                        // {rows written, their in-edges, their distinct sources}: counted once per batch when the launch accounting is on, their bounds otherwise
+                        int64_t w[3] = {std::min<int64_t>(b->unfused_rows, obs == 0 ? b->n_c : b->n_e1), b->unfused_edges, 0};
+                        w[2] = std::min<int64_t>(w[1], b->rows);
+                        if (gm_prof_enabled()) GM_TRY(gm_batch_fwd_counts(b, obs, st, w));
+                        // every indptr entry; the list entry and the flag of every row of more than GM_FUSE_MAXDEG sources; the edge-table entries of the rows written,
+                        // those rows (written once) and their sources (read once)
+                        pb0 = 4 * (b->rows + 1) + 8 * b->unfused_rows + 4 * w[1] + 4 * w[0] * (int64_t)fi;
+                        src = w[2]; src_bound = std::min<int64_t>(w[1], b->rows);
+                    } else src = gm_prof_enabled() ? gm_batch_unfused_sources(b, st) : src_bound;
                     const int64_t pb = pb0 + 4 * src * (int64_t)fi;
                     // strict HBM pricing as for the full launches: a gather launch reads at most the whole (cache-resident) feature table
                     const int64_t pbs = pb0 + 4 * (gather ? std::min<int64_t>(src, b->feat_rows) : src) * (int64_t)fi;
-                    gm_prof_note(GM_PROF_AGG_BOUND, pb0 + 4 * std::min<int64_t>(b->unfused_edges, b->rows) * (int64_t)fi - pb);      // (difference to the exact count)
+                    gm_prof_note(GM_PROF_AGG_BOUND, pb0 + 4 * src_bound * (int64_t)fi - pb);      // (difference to the exact count)
                     GM_TRY(launch_agg(a, pb, pbs, st));
                 } else {
                     if (a.e_w) GM_TRY(gm_agg_stream_args(a, b, 0, gather, st));      // full launches may take the LDS-DMA stream kernel (agg_stream.hip)
@@ -1006,6 +1043,9 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
             if (dead_rows && split_ok && l < L.n_gcn - 1 && (fwd_only == 1 || (fwd_only == 2 && c.M[l])) && L.dims[l + 1] <= L.dims[l + 2] && b->d_norm_src) {
                 g.row_scale_keep = b->d_norm_src; g.n_keep = b->n_src;
             }
+            // GM_DEAD_ROWS=3: ... and in a pass nobody differentiates only a source of a centre's in-edge is the source of an edge anyone walks (a subset of the rows
+            // above; the kept-row count is read back only when the launch accounting is on, its bound otherwise -- nobody reads it then)
+            if (obs == 1) { g.row_scale_keep = b->d_norm_e1; g.n_keep = gm_prof_enabled() ? gm_batch_e1_rows(b, st) : std::min<int64_t>(b->n_e1, b->rows); }
             if (split_ok) {
                 gm_bound ab = gm_no_bound(), bb;
                 const bool want16 = in_bound(c, l, ab);
@@ -1026,8 +1066,8 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
             }
             if (fuse) {
                 g.zside = c.Z[l]; g.ldz = fi;
-                if (gather) { g.A = b->feat; g.lda = b->feat_ld; g.fuse2 = b->d_fuse2_feat; }
-                else { g.A = xin; g.lda = fi; g.fuse2 = b->d_fuse2; }
+                if (gather) { g.A = b->feat; g.lda = b->feat_ld; g.fuse2 = obs == 1 ? b->d_fwd_tab_feat : b->d_fuse2_feat; }
+                else { g.A = xin; g.lda = fi; g.fuse2 = obs >= 0 ? b->d_fwd_tab[obs] : b->d_fuse2; }
             }
             GM_TRY(gm_launch_gemm_nn(g, st));
         }

@@ -554,8 +554,12 @@ enum gm_field {
     GM_F_HOP = 15,      /* int8[rows*centres] hop-distance label of every row per centre, row-major [rows, centres] (hop-labelled batches only: GM_EINVAL otherwise) */
     GM_F_NORM_E1 = 16,  /* float[rows]    GM_F_NORM with the sign bit set on every row that is not the source of an in-edge of a centre: the last
                                           layer's backward leaves the gradient of the layer below zero there (GM_DEAD_ROWS=2)     */
-    GM_F_EDGE_CENTRE_T = 17 /* int32[edges] per edge of GM_F_INDICES_T: the destination row where it is a centre, else `rows` -- the zero row the
+    GM_F_EDGE_CENTRE_T = 17,/* int32[edges] per edge of GM_F_INDICES_T: the destination row where it is a centre, else `rows` -- the zero row the
                                           dense backward keeps behind its [rows, width] product T (GM_DEAD_ROWS=2)                 */
+    GM_F_OBS_CENTRE = 18, /* float[rows]  +1 on the centre rows, -1 on every other row: the keep flag (a scale of exactly 1) of the last layer's partial
+                                          aggregate in a pass nobody differentiates (GM_DEAD_ROWS=3)                               */
+    GM_F_OBS_E1 = 19    /* float[rows]    +1 on the sources of the centres' in-edges (the rows GM_F_NORM_E1 keeps), -1 on every other row: the same
+                                          flag for the layer below the last (GM_DEAD_ROWS=3)                                       */
 };
 int32_t gm_batch_weighted(const gm_batch_t* b);
 /* Copies a field to host memory (synchronises `stream` internally). */
@@ -665,7 +669,9 @@ int gm_dense_aggregate(const gm_batch_t* b, int32_t transposed, int32_t x_src, c
  * source tables of the fused kernels, [rows] entries of four int32 {u0, u1, w0, w1} (w: fp32 bits): 4 sources as batch rows, 5 as rows of the feature table,
  * 6 the last layer's dQ table.  A source flagged 0x40000000 is the row's own finished row, 0x20000000 an all-zero row:
  *   no source {ZERO, ZERO, 1, 0};  one {u0, u0, w0, 0};  two {u0, u1, w0, w1};  more {row | SELF, row | SELF, 1, 0};  w = norm[u] (x the edge's weight);
- *   dQ table: a centre row {row | SELF, ZERO, 1, 0}, any other {ZERO, ZERO, 0, 0}. */
+ *   dQ table: a centre row {row | SELF, ZERO, 1, 0}, any other {ZERO, ZERO, 0, 0}.
+ * 7 / 8 / 9 (GM_DEAD_ROWS=3) the tables of the passes nobody differentiates, same layout: 7 table 4's entry on the centre rows, 8 table 4's and 9 table 5's
+ * entry on the sources of the centres' in-edges (the rows GM_F_OBS_E1 keeps); every other row {ZERO, ZERO, 0, 0}. */
 int gm_dense_agg_info(const gm_batch_t* b, int32_t transposed, int64_t* info);
 int gm_dense_fuse_counts(const gm_batch_t* b, int64_t* counts);
 int gm_dense_agg_table(const gm_batch_t* b, int32_t which, int32_t transposed, void* dst, int64_t n, void* stream);
