@@ -350,7 +350,7 @@ const gm_knobs& gm_knob() {
         k.gemm_mode = (gm && (!strcmp(gm, "split") || !strcmp(gm, "1"))) ? 1 : (gm && (!strcmp(gm, "f32") || !strcmp(gm, "0"))) ? 0 : -1;
         k.gemm_split_min_tiles = env("GM_GEMM_SPLIT_MIN_TILES", -1);
         k.centre_store = env("GM_CENTRE_STORE", 2);
-        k.dead_rows = env("GM_DEAD_ROWS", 3);
+        k.dead_rows = env("GM_DEAD_ROWS", 4);
         k.fuse_agg = env("GM_FUSE_AGG", 1);
         k.fuse_diff = env("GM_FUSE_DIFF", 2);
         k.extract_pref16 = env("GM_EXTRACT_PREF16", 1);

@@ -1303,7 +1303,7 @@ int gm_launch_wgrad(const gm_wgrad_args& a, hipStream_t s) {
                "wgrad: the split kernel needs K, N in {128, 256}, no Gb / row indirection and 16-byte aligned operands (K=%d N=%d)", a.K, a.N);
     const int cat = split ? (wgrad_np(a) == 2 ? GM_PROF_WGRAD_SPLIT16 : GM_PROF_WGRAD_SPLIT) : GM_PROF_WGRAD;
     gm_prof_begin(cat, s, 2 * a.rows * a.K * a.N);
-    gm_prof_note(GM_PROF_WGRAD_BYTES, 4 * a.rows * ((int64_t)a.K + a.N));
+    gm_prof_note(GM_PROF_WGRAD_BYTES, 4 * ((a.fuse2 && a.a_rows > 0 ? std::min(a.a_rows, a.rows) : a.rows) * (int64_t)a.K + a.rows * (int64_t)a.N));
     const int rc = launch_wgrad(a, s);
     gm_prof_end(cat, s);
     return rc;

@@ -252,7 +252,8 @@ struct gm_knobs {
     int centre_store;              // GM_CENTRE_STORE: the last layer's update stores only the centre rows of its activation -- in every pass (2, default), in the forward-only passes (1) -- or every row (0)
     int dead_rows;                 // GM_DEAD_ROWS: rows no later kernel reads are computed and not stored / not zero-filled (off with GM_CENTRE_STORE=0 too): H_l below the last layer at rows without an out-edge, dQ_L outside the centre rows (1);
                                    // and, one level down the dense backward, T_L outside the centre rows and dQ_{L-1} outside the sources of the centres' in-edges (2);
-                                   // and, one level down the passes nobody differentiates, Z_L outside the centre rows, H_{L-1} and Z_{L-1} outside the sources of the centres' in-edges (3, default)
+                                   // and, one level down the passes nobody differentiates, Z_L outside the centre rows, H_{L-1} and Z_{L-1} outside the sources of the centres' in-edges (3);
+                                   // and the same rows of the passes the dense backward differentiates, whose weight gradients read Z_l through the same tables (4, default)
     int fuse_agg, head_stage;
     int fuse_diff;                 // GM_FUSE_DIFF: the differentiated passes of the dense schedule take the fused aggregate + GEMM too, their weight gradients form Z's rows from the source table: 2 (default) everywhere except a support batch whose full launches take the stream aggregate, 1 everywhere, 0 never
     int agg_mid_win;               // GM_AGG_MID_WIN: rows per wave window over that list (0 = by its length)
@@ -633,6 +634,7 @@ struct gm_wgrad_args {
     // from gx (row stride ldgx) through the per-row table fuse2 (gm_batch::d_fuse2 / d_fuse2_feat) in the aggregate's fma order, rows the table flags
     // GM_FUSE_SELF are read from A (the partial aggregate launch wrote them), GM_FUSE_ZERO rows are zero
     const void* fuse2; const float* gx; int64_t ldgx;
+    int64_t a_rows;                     // launch accounting only (GM_PROF_WGRAD_BYTES): rows of A the launch fetches, where the table sends the others to the zero row (0 = every row)
     // optional (three-piece split kernel only, GM_EINVAL elsewhere): the row scale again, |value| = a_scale, with the SIGN BIT SET on rows of G that were never
     // written (dQ_L outside the centre rows: gm_batch::d_norm_c) -- such a row enters dW and db as zeros, whatever its bytes hold
     const float* g_keep;

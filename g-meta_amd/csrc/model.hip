@@ -694,6 +694,10 @@ struct GcnCtx {
     bool t_zero = false;         // GM_DEAD_ROWS=2: this call zeroed the block behind T_L (t_zero_fill), the last layer's backward may read T_L through gm_batch::d_ect
     bool zfused[GM_MAX_GCN] = {};    // the last forward left Z[l] written at the rows of three or more sources only (fused aggregate + GEMM in a pass that IS
                                      // differentiated): the backward's weight gradient forms the other rows from the per-row source table (gm_wgrad_args::fuse2)
+    // GM_DEAD_ROWS=4: the last forward was a differentiated pass that formed and stored layer l on its observable rows only -- Z[l] / H[l] hold the centre rows
+    // (ZOBS_CENTRE: gm_batch::d_obs[0], d_fwd_tab[0]) or the sources of the centres' in-edges (ZOBS_E1: d_obs[1], d_fwd_tab[1] / d_fwd_tab_feat), every other row is
+    // unwritten.  Decided once in gcn_forward; EVERY backward over this pass reads the layer through those tables, whoever calls it
+    enum Zobs { ZOBS_NONE = 0, ZOBS_CENTRE, ZOBS_E1 } zobs[GM_MAX_GCN] = {};
     float* Z[GM_MAX_GCN]; float* H[GM_MAX_GCN]; float* X0; float* bufA; float* bufB; float* partial;
     float* partial_l[GM_MAX_GCN];    // dense backward: own partials for the layers above the first, whose reductions are held back and run
     gm_wgrad_hold hold;              // together with the first layer's (one launch less per layer and backward pass)
@@ -968,10 +972,29 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
                            b->d_fwd_tab[0] && b->d_obs[0] && L.dims[Lg - 1] <= L.dims[Lg] && layer_fuse(Lg - 1) &&
                            (Lg >= 2 || c.x0_user);      // (a last layer that gathers from the feature table has no table of its own: one-layer models stay as they are)
     const bool fwd3_below = fwd3_last && Lg >= 2 && L.dims[Lg - 2] <= L.dims[Lg - 1] && layer_split_ok(Lg - 2) && b->d_fwd_tab[1] && b->d_fwd_tab_feat && b->d_obs[1];
+    // GM_DEAD_ROWS=4: the same restriction in the passes the dense backward differentiates (fwd_only == 2).  A gradient reaches Z_L at the centre rows only (dQ_L is
+    // zero everywhere else) and Z_{L-1} / H_{L-1} only at the sources of the centres' in-edges (dQ_{L-1} likewise), so the forward forms, fetches and stores exactly
+    // what level 3 does, and the weight gradients read Z_l through the same tables (GcnCtx::zobs; gcn_backward).  Decided HERE, once, and recorded per layer: it holds
+    // under level 3's preconditions plus what level 2 needs of this pass -- dQ_L left to its centre rows (the DQ_CENTRE predicate below, evaluated up front), the zero
+    // block behind T_L (t_zero), every pass's centre-row store (GM_CENTRE_STORE=2) -- and, below the last layer, gcn_backward's dq_e1 conditions (two GraphConv layers,
+    // aggregate-first, the table-fed weight gradient, relu' bits).  Not with a hoisted Z_1 (reuse_z1), which stays a flagged extra.
+    // The relu' bits M[l] of a restricted layer are the every-row pass's on the observable rows; on every other row they come from a zero operand row (relu'(b_l): deterministic,
+    // not the every-row pass's).  Their readers: (a) the transposed aggregate behind support_bwd / the query backward (skip_head = 1, dq_e1): keep_signed over d_norm_e1, it
+    // forms -- and selects by the bits of -- the observable rows only; (b) the transposed aggregate of a backward that fills dQ_L itself (skip_head = 0: the meta-gradient
+    // through the last support pass) runs over every row, and on an unobservable row selects between +0 and (+0 aggregate) x norm = +0: the same +0 either way.
+    const bool dq_centre_fwd = fwd_only == 2 && !mean && dead_rows && layer_split_ok(Lg - 1) && c.np != 2 && b->d_norm_c && (Lg == 1 || dz_centre_ok(c, Lg - 1)) &&
+                               gm_wgrad_gather_ok(b->n_chunks, L.dims[Lg - 1], L.dims[Lg]);
+    const bool diff4_last = dq_centre_fwd && gm_knob().dead_rows >= 4 && gm_knob().centre_store >= 2 && c.t_zero && !reuse_z1 && Lg >= 2 && b->d_norm_e1 &&
+                            b->d_fwd_tab[0] && b->d_obs[0] && L.dims[Lg - 1] <= L.dims[Lg] && layer_fuse(Lg - 1);
+    const bool diff4_below = diff4_last && Lg == 2 && L.dims[0] <= L.dims[1] && layer_fuse(0) && gm_wgrad_gather_ok(b->n_chunks, L.dims[0], L.dims[1]) && c.M[0] &&
+                             b->d_fwd_tab[1] && b->d_fwd_tab_feat && b->d_obs[1];
+    for (int l = 0; l < GM_MAX_GCN; ++l) c.zobs[l] = GcnCtx::ZOBS_NONE;
     for (int l = 0; l < L.n_gcn; ++l) {
         const int fi = L.dims[l], fo = L.dims[l + 1];
         const bool gather = (l == 0 && !c.x0_user);
-        const int obs = (fwd3_last && l == Lg - 1) ? 0 : (fwd3_below && l == Lg - 2) ? 1 : -1;      // GM_DEAD_ROWS=3: the layer's observable row set (gm_batch::d_obs), or none
+        // GM_DEAD_ROWS=3 / 4: the layer's observable row set (gm_batch::d_obs), or none
+        const int obs = ((fwd3_last || diff4_last) && l == Lg - 1) ? 0 : ((fwd3_below || diff4_below) && l == Lg - 2) ? 1 : -1;
+        if (fwd_only == 2) c.zobs[l] = obs == 0 ? GcnCtx::ZOBS_CENTRE : obs == 1 ? GcnCtx::ZOBS_E1 : GcnCtx::ZOBS_NONE;
         if (fi > fo) {                      // learner.py:34-40: multiply first, then aggregate
             const float* A = xin; int64_t lda = fi;
             if (gather) { GM_TRY(gm_gather_rows(b, b->d_feat_row, b->rows, fi, c.X0, st)); A = c.X0; }
@@ -1064,6 +1087,7 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
                 if (dead_rows && split_ok && g.np != 2 && c.np != 2 && b->d_norm_c && dz_ok && gm_wgrad_gather_ok(b->n_chunks, fi, fo)) c.dq = GcnCtx::DQ_CENTRE;
                 else { g.zero_out = c.bufA; c.dq = GcnCtx::DQ_ZEROED; }
             }
+            GM_REQUIRE(!(fwd_only == 2 && obs == 0) || c.dq == GcnCtx::DQ_CENTRE, GM_EINVAL, "forward: a restricted differentiated pass must leave dQ to its centre rows");
             if (fuse) {
                 g.zside = c.Z[l]; g.ldz = fi;
                 if (gather) { g.A = b->feat; g.lda = b->feat_ld; g.fuse2 = obs == 1 ? b->d_fwd_tab_feat : b->d_fuse2_feat; }
@@ -1101,6 +1125,7 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
     //    layer's weight gradient selects zeros for the others (g_keep).  Deeper models keep dQ_{L-1} whole: it is the A operand of a plain-loader dZ GEMM.
     const bool t_centre = dq_centre && c.t_zero && gm_knob().dead_rows >= 2;
     const bool dq_e1 = t_centre && Lg == 2 && L.dims[0] <= L.dims[1] && c.np != 2 && gm_wgrad_gather_ok(b->n_chunks, L.dims[0], L.dims[1]);
+    const bool dq_filled = !skip_head && !mean_readout(c);      // this call zero-fills dQ_L whole (below) before the head writes its centre rows
     if (!skip_head && mean_readout(c)) {      // G = dlogits Wl on the pooled rows, then every row of dQ_L from it
         GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, nullptr, c.Gpool, st));
         GM_TRY(readout_bwd(c, st));
@@ -1144,7 +1169,24 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
             if (c.zfused[l]) {                 // the forward ran fused: Z[l] holds the rows of three or more sources, the table forms the others
                 const bool gather = l == 0 && !c.x0_user;
                 w.fuse2 = gather ? b->d_fuse2_feat : b->d_fuse2;
+                // GM_DEAD_ROWS=4: ... and of a restricted pass (GcnCtx::zobs) through the forward's own table: an unobservable row of A is the zero row -- the forward
+                // wrote neither its Z_l row nor (one layer down) the H_{l-1} rows the full table would gather for it
+                if (c.zobs[l] == GcnCtx::ZOBS_CENTRE) w.fuse2 = b->d_fwd_tab[0];
+                if (c.zobs[l] == GcnCtx::ZOBS_E1) w.fuse2 = gather ? b->d_fwd_tab_feat : b->d_fwd_tab[1];
                 w.gx = gather ? b->feat : (l > 0 ? c.H[l - 1] : c.x0_user); w.ldgx = gather ? b->feat_ld : fi;
+            }
+            if (c.zobs[l] != GcnCtx::ZOBS_NONE) {
+                // The zero rows of A stand in for finite rows the every-row pass multiplies by zero rows of G: those rows of G must BE zeros here too -- selected (g_keep:
+                // the backward behind head_loss, whose dQ holds the observable rows only), or true zeros because this very call filled dQ_L before the head
+                // wrote its centre rows (skip_head = 0: the meta-gradient through the last support pass, which runs over the Z / H / M that pass's restricted
+                // forward left).  Bitwise the every-row pass in both: a +-0 product added to a chain that started at +0 leaves the chain unchanged (bsum and the MFMA
+                // accumulators start at +0; a zero A row makes the same +-0 products as a finite one); in the second, dQ_L's other rows are the memset's +0, T_L's are
+                // +0 x norm, the transposed aggregate's +0-started chains over them stay +0, and the relu' select yields +0 whichever way the bit reads
+                GM_REQUIRE(c.zfused[l] && w.fuse2, GM_EINVAL, "backward: layer %d was formed on its observable rows only, its weight gradient needs the source table", l);
+                GM_REQUIRE(w.g_keep || dq_filled, GM_EINVAL,
+                           "backward: layer %d was formed on its observable rows only, but its weight gradient got neither flagged rows of G (g_keep) nor a dQ this call zero-filled", l);
+                // launch accounting: A is fetched on the observable rows only (every other row reads the cache-resident zero row)
+                if (gm_prof_enabled()) w.a_rows = c.zobs[l] == GcnCtx::ZOBS_CENTRE ? std::min<int64_t>(b->n_c, b->rows) : gm_batch_e1_rows(b, st);
             }
             if (l > 0) {
                 gm_gemm_args g{}; g.A = dQ; g.lda = fo; g.C = T; g.ldc = fi; g.K = fo; g.N = fi;

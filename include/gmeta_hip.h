@@ -557,9 +557,9 @@ enum gm_field {
     GM_F_EDGE_CENTRE_T = 17,/* int32[edges] per edge of GM_F_INDICES_T: the destination row where it is a centre, else `rows` -- the zero row the
                                           dense backward keeps behind its [rows, width] product T (GM_DEAD_ROWS=2)                 */
     GM_F_OBS_CENTRE = 18, /* float[rows]  +1 on the centre rows, -1 on every other row: the keep flag (a scale of exactly 1) of the last layer's partial
-                                          aggregate in a pass nobody differentiates (GM_DEAD_ROWS=3)                               */
+                                          aggregate in a pass nobody differentiates (GM_DEAD_ROWS=3) and in a differentiated pass (4) */
     GM_F_OBS_E1 = 19    /* float[rows]    +1 on the sources of the centres' in-edges (the rows GM_F_NORM_E1 keeps), -1 on every other row: the same
-                                          flag for the layer below the last (GM_DEAD_ROWS=3)                                       */
+                                          flag for the layer below the last (GM_DEAD_ROWS=3, 4)                                    */
 };
 int32_t gm_batch_weighted(const gm_batch_t* b);
 /* Copies a field to host memory (synchronises `stream` internally). */
@@ -670,7 +670,7 @@ int gm_dense_aggregate(const gm_batch_t* b, int32_t transposed, int32_t x_src, c
  * 6 the last layer's dQ table.  A source flagged 0x40000000 is the row's own finished row, 0x20000000 an all-zero row:
  *   no source {ZERO, ZERO, 1, 0};  one {u0, u0, w0, 0};  two {u0, u1, w0, w1};  more {row | SELF, row | SELF, 1, 0};  w = norm[u] (x the edge's weight);
  *   dQ table: a centre row {row | SELF, ZERO, 1, 0}, any other {ZERO, ZERO, 0, 0}.
- * 7 / 8 / 9 (GM_DEAD_ROWS=3) the tables of the passes nobody differentiates, same layout: 7 table 4's entry on the centre rows, 8 table 4's and 9 table 5's
+ * 7 / 8 / 9 (GM_DEAD_ROWS=3; at 4 also of the differentiated passes and their weight gradients) the tables of the passes nobody differentiates, same layout: 7 table 4's entry on the centre rows, 8 table 4's and 9 table 5's
  * entry on the sources of the centres' in-edges (the rows GM_F_OBS_E1 keeps); every other row {ZERO, ZERO, 0, 0}. */
 int gm_dense_agg_info(const gm_batch_t* b, int32_t transposed, int64_t* info);
 int gm_dense_fuse_counts(const gm_batch_t* b, int64_t* counts);
