@@ -259,7 +259,7 @@ extern "C" int gm_dense_wgrad(const gm_batch_t* b, const float* x, int64_t ldx, 
     return rc;
 }
 
-// The weight gradient over a Z whose forward ran fused, as gcn_backward's `zfused` branch launches it: A holds the rows the table flags GM_FUSE_SELF, every other
+// The weight gradient over a Z whose forward ran fused, as gcn_backward launches it for a fused layer (LayerPlan::fuse): A holds the rows the table flags GM_FUSE_SELF, every other
 // row is formed from gx through the batch's own table (table 0: d_fuse2 over the caller's gx; 1: d_fuse2_feat over the batch's feature table)
 extern "C" int gm_dense_wgrad_fused(const gm_batch_t* b, int32_t table, const float* A, int64_t lda, int32_t K, const float* gx, int64_t ldgx, const float* g,
                                     int64_t ldg, int32_t N, const float* s, const float* g_keep, float* dW, int64_t dw_stride, float* db, int64_t db_stride,

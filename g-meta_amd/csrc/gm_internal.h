@@ -249,13 +249,11 @@ struct gm_knobs {
     int extract_pref16;            // GM_EXTRACT_PREF16: 16-bit per-word prefix counts in the extraction kernels' LDS (1, default): four resident workgroups per CU instead of three at the arxiv parent size
     int gemm_mode;                 // 0 exact fp32, 1 split-bf16, -1 not set (library default)
     int gemm_split_min_tiles;      // -1: a quarter of the current device's CUs
-    int centre_store;              // GM_CENTRE_STORE: the last layer's update stores only the centre rows of its activation -- in every pass (2, default), in the forward-only passes (1) -- or every row (0)
-    int dead_rows;                 // GM_DEAD_ROWS: rows no later kernel reads are computed and not stored / not zero-filled (off with GM_CENTRE_STORE=0 too): H_l below the last layer at rows without an out-edge, dQ_L outside the centre rows (1);
-                                   // and, one level down the dense backward, T_L outside the centre rows and dQ_{L-1} outside the sources of the centres' in-edges (2);
-                                   // and, one level down the passes nobody differentiates, Z_L outside the centre rows, H_{L-1} and Z_{L-1} outside the sources of the centres' in-edges (3);
-                                   // and the same rows of the passes the dense backward differentiates, whose weight gradients read Z_l through the same tables (4, default)
+    // GM_CENTRE_STORE (0..2, default 2), GM_DEAD_ROWS (0..4, default 4), GM_FUSE_DIFF (0..2, default 2): which rows a pass of the dense schedule forms, stores and
+    // zero-fills, and which of its layers run fused.  What each value means and how the three combine: the table in DESIGN.md section 4.3; read by plan_pass (model.hip) alone
+    int centre_store, dead_rows;
     int fuse_agg, head_stage;
-    int fuse_diff;                 // GM_FUSE_DIFF: the differentiated passes of the dense schedule take the fused aggregate + GEMM too, their weight gradients form Z's rows from the source table: 2 (default) everywhere except a support batch whose full launches take the stream aggregate, 1 everywhere, 0 never
+    int fuse_diff;
     int agg_mid_win;               // GM_AGG_MID_WIN: rows per wave window over that list (0 = by its length)
     int agg_mid_list;              // GM_AGG_MID_LIST: the partial aggregate launch of a fused pass walks a compact list of its window rows (1, default) or every row (0)
     int query_streams;             // GM_QUERY_STREAMS: 2 = the query evaluations of gm_meta_step alternate between two streams; anything else (default 0) = one stream

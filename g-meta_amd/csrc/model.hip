@@ -683,21 +683,49 @@ struct PlaneDir {
     }
 };
 
+// ---- The row plan of one pass of the dense schedule (DESIGN.md section 4.3 has the table of knobs x pass kind).  plan_pass decides it, once, when gcn_forward
+// starts; gcn_forward executes it and leaves it in GcnCtx::plan, where head_loss and EVERY gcn_backward over the pass read it, whoever calls them and however much
+// later (the second backward of the last support pass runs long after its forward: the plan is never derived again)
+// PASS_PLAIN: a stand-alone pass (gm_gcn_forward, the passes the sparse backward differentiates): every row formed, nothing fused.  PASS_FWD_ONLY: nobody differentiates
+// it (the query evaluations of the inner steps, finetuning's query passes, gm_proto_predict): all anyone reads is H_L at the centre rows.  PASS_DIFF: the dense backward
+// differentiates it (the support passes, the last query evaluation): head + loss + gcn_backward follow
+enum PassKind { PASS_PLAIN = 0, PASS_FWD_ONLY = 1, PASS_DIFF = 2 };
+// A row set of a batch, as its tables carry it (row_view): every row; the rows with an out-edge inside the batch (the only rows of H_l below the last layer that an
+// edge reads); the sources of the centres' in-edges; the centre rows
+enum RowSet { ROWS_ALL, ROWS_SRC, ROWS_E1, ROWS_CENTRE };
+// How the pass leaves bufA (= dQ_L) for the head/loss launch and the gcn_backward(skip_head = 1) that follow.  DQ_MEMSET: untouched, head_loss zero-fills it with a
+// memset launch; DQ_ZEROED: the last forward GEMM zero-fills it on its way out; DQ_CENTRE (GM_DEAD_ROWS): left alone -- the head/loss launch assigns its centre rows
+// and the two readers of dQ_L in the backward take every other row as zeros (dZ GEMM: gm_batch::d_dq_tab; weight gradient: gm_wgrad_args::g_keep)
+enum DqFill { DQ_MEMSET, DQ_ZEROED, DQ_CENTRE };
+// One aggregate-first layer of a pass (a multiply-first layer forms and stores every row and only ever sets relu_bits).
+//  split: the update runs on the split-bf16 kernel.
+//  fuse: ... and takes the fused aggregate + GEMM: the aggregate of a row with one or two sources is formed in the GEMM's A feeders (same fma order), only rows of other
+//    degrees go through a partial aggregate launch and HBM; Z_l of the other rows is never written -- where the pass is differentiated, the weight gradient forms them from
+//    the same per-row source table (gm_wgrad_args::fuse2).  Same floats as the unfused pass, bit for bit.
+//  formed (GM_DEAD_ROWS=3 / 4): the rows of Z_l this pass forms and the fused loader fetches -- the observable ones; Z[l] is unwritten everywhere else.  Every tile and
+//    every MFMA is still issued, no product and no sum that reaches a stored value is dropped or reordered:
+//     * the fused loaders read Z_l / H_{l-1} through gm_batch::d_fwd_tab (d_fwd_tab_feat), which sends every unobservable row to the zero row: they never touch a
+//       row this pass did not write;
+//     * the partial aggregate launches form the observable rows only (s_out = gm_batch::d_obs: +-1, keep_signed -- the scale is exactly the 1 the launch applies
+//       without it; flagged rows stop at their descriptor, agg.hip: agg_unobservable).
+//    Always ROWS_ALL without `fuse` (plan_check).  In a differentiated pass (GM_DEAD_ROWS=4) EVERY backward reads Z_l through the same table.
+//  stored: the rows of H_l the update stores; every row is computed.  ROWS_CENTRE, last layer: only the head reads H_L, and only its centre rows (h[to_fetch]; the backward
+//    takes relu' from the bits and the weight gradient from Z_L).  ROWS_SRC, below the last: H_l is read through the edges only (the next layer's aggregate, the fused
+//    loaders, the table-formed weight gradient; the backward takes relu' from the bits) -- a row without an out-edge is nobody's source.  ROWS_E1, below a restricted
+//    last layer: only a source of a centre's in-edge is the source of an edge anyone walks (a subset of ROWS_SRC).
+//  relu_bits: the layer writes its relu' bits M[l] (where the context has them): every pass but the ones nobody differentiates
+struct LayerPlan { bool split, fuse; RowSet formed, stored; bool relu_bits; };
+// The pass: its kind, its layers, dQ_L, and what a gcn_backward(skip_head = 1) over it may do (GM_DEAD_ROWS=2; gcn_backward has the bitwise argument).  t_centre: dQ_L is
+// left to its centre rows and the zero block behind T_L is there -- the dZ GEMM stores T_L's centre rows only, the transposed aggregate reads T_L through gm_batch::d_ect.
+// dq_e1: ... and the layer below is the first, aggregate-first, with a table-fed three-piece weight gradient: that aggregate stores only the rows of dQ_{L-1} that can be non-zero
+struct PassPlan { PassKind kind; LayerPlan layer[GM_MAX_GCN]; DqFill dq; bool t_centre, dq_e1; };
+
 struct GcnCtx {
     const gm_batch* b; gm_layout L;
     PlaneDir* pd;                // non-NULL inside gm_meta_step
     bool is_support = false;     // gm_meta_step's support-chain context (the serial dependency of the step; the query contexts carry the bulk work)
-    // How the last forward left bufA (= dQ) for the head/loss launch and the gcn_backward(skip_head = 1) that follow.  DQ_MEMSET: untouched, head_loss zero-fills
-    // it with a memset launch; DQ_ZEROED: the last forward GEMM zero-filled it on its way out; DQ_CENTRE (GM_DEAD_ROWS): left alone -- the head/loss launch assigns its
-    // centre rows and the two readers of dQ_L in the backward take every other row as zeros (dZ GEMM: gm_batch::d_dq_tab; weight gradient: gm_wgrad_args::g_keep)
-    enum DqFill { DQ_MEMSET, DQ_ZEROED, DQ_CENTRE } dq = DQ_MEMSET;
+    PassPlan plan = {};          // of the last gcn_forward over this context (all zeros before the first: PASS_PLAIN, every row, DQ_MEMSET)
     bool t_zero = false;         // GM_DEAD_ROWS=2: this call zeroed the block behind T_L (t_zero_fill), the last layer's backward may read T_L through gm_batch::d_ect
-    bool zfused[GM_MAX_GCN] = {};    // the last forward left Z[l] written at the rows of three or more sources only (fused aggregate + GEMM in a pass that IS
-                                     // differentiated): the backward's weight gradient forms the other rows from the per-row source table (gm_wgrad_args::fuse2)
-    // GM_DEAD_ROWS=4: the last forward was a differentiated pass that formed and stored layer l on its observable rows only -- Z[l] / H[l] hold the centre rows
-    // (ZOBS_CENTRE: gm_batch::d_obs[0], d_fwd_tab[0]) or the sources of the centres' in-edges (ZOBS_E1: d_obs[1], d_fwd_tab[1] / d_fwd_tab_feat), every other row is
-    // unwritten.  Decided once in gcn_forward; EVERY backward over this pass reads the layer through those tables, whoever calls it
-    enum Zobs { ZOBS_NONE = 0, ZOBS_CENTRE, ZOBS_E1 } zobs[GM_MAX_GCN] = {};
     float* Z[GM_MAX_GCN]; float* H[GM_MAX_GCN]; float* X0; float* bufA; float* bufB; float* partial;
     float* partial_l[GM_MAX_GCN];    // dense backward: own partials for the layers above the first, whose reductions are held back and run
     gm_wgrad_hold hold;              // together with the first layer's (one launch less per layer and backward pass)
@@ -746,21 +774,23 @@ static bool dq_bound(const GcnCtx& c, int l, gm_bound& bd) {
     bd.stride = GM_BOUND_PAD; bd.hgain = 1.f;
     return true;
 }
-// The weight planes of a split GEMM of layer l (o = 0: X @ W, 1: dQ @ W^T) and their bound: the planes a reduction left for `params`, else
-// split now into c.Wsplit.  want16: the launch has its A bound and would take two-piece planes.  *np = the pieces (2 / 3) of *pl.
-static int weight_planes(GcnCtx& c, const float* params, int64_t pstride, int l, int o, int K, int N, bool want16, hipStream_t st, const uint16_t** pl, gm_bound* bb, int* np) {
-    const gm_layout& L = c.L;
-    uint16_t* have = (c.pd && pstride) ? c.pd->lookup(params, l, o) : nullptr;
-    *bb = gm_no_bound();
+// The weight operand of a split GEMM of layer l (o = 0: X @ W, A bound in_bound; 1: dQ @ W^T, A bound dq_bound) and both bounds, into g: the planes a reduction left for
+// `params`, else split now into c.Wsplit.  Two pieces where the launch has its A bound and the weights theirs (such a launch records its output's maximum), else three
+static int weight_planes(GcnCtx& c, const float* params, int64_t pstride, int l, int o, hipStream_t st, gm_gemm_args& g) {
+    const int fi = c.L.dims[l], fo = c.L.dims[l + 1];
+    const bool want16 = o ? dq_bound(c, l, g.a_bound) : in_bound(c, l, g.a_bound);
+    uint16_t* have = (c.pd && pstride) ? c.pd->lookup(params, l, o) : nullptr;       // left by the reduction that wrote these weights
+    g.b_bound = gm_no_bound(); g.np = 3; g.bsplit_stride = pstride ? (int64_t)3 * fi * fo : 0;
     if (have && c.np == 2) {                                               // stored planes are two-piece in this context
-        if (want16 && c.pd->w_bound(params, l, *bb)) { *pl = have; *np = 2; return GM_OK; }
-        have = nullptr;
+        if (want16 && c.pd->w_bound(params, l, g.b_bound)) g.np = 2; else have = nullptr;
     }
-    if (have) { *pl = have; *np = 3; return GM_OK; }
-    const bool f16 = want16 && c.pd && c.pd->w_bound(params, l, *bb);
-    if (!f16) *bb = gm_no_bound();
-    GM_TRY(gm_split_weights(params, pstride, L.w_off[l], K, N, o, pstride ? c.b->sets : 1, c.Wsplit, st, f16 ? 2 : 3, *bb));
-    *pl = c.Wsplit; *np = f16 ? 2 : 3;
+    if (!have) {
+        if (want16 && c.pd && c.pd->w_bound(params, l, g.b_bound)) g.np = 2; else g.b_bound = gm_no_bound();
+        GM_TRY(gm_split_weights(params, pstride, c.L.w_off[l], o ? fo : fi, o ? fi : fo, o, pstride ? c.b->sets : 1, c.Wsplit, st, g.np, g.b_bound));
+        have = c.Wsplit;
+    }
+    g.Bsplit = have;
+    if (g.np == 2) { g.amax_out = o ? c.amT(l) : c.amH(l); (o ? c.tv : c.hv)[l] = true; }
     return GM_OK;
 }
 
@@ -885,10 +915,51 @@ static int batch_agg(const GcnCtx& c, int dir, hipStream_t st, gm_agg_args& a) {
     return GM_OK;
 }
 
+// A row set as the launches take it.  keep: the row scale with "not of the set" in its sign bit -- gm_gemm_args::row_scale_keep (rows a GEMM stores), gm_wgrad_args::g_keep
+// (rows of G that were written), gm_agg_args::s_out + keep_signed of a transposed aggregate (NULL: every row).  sign: +1 on the set, -1 off it -- s_out + keep_signed of a
+// forward partial aggregate, a scale of exactly 1 (NULL: every row).  tab: the per-row source table of a fused loader or a table-fed weight gradient over a Z_l formed on the
+// set -- the full table's entry on its rows, the zero row everywhere else (gather: the layer reads the feature table; a centre-restricted layer never does, plan_check).
+// obs: the set's index into the tables of gm_batch_fwd_counts, -1 where it has none.  n: its rows as the host knows them (ROWS_E1: a bound, see rows_kept)
+struct RowView { const float* keep; const float* sign; const void* tab; int obs; int64_t n; };
+static RowView row_view(const gm_batch* b, RowSet rs, bool gather) {
+    if (rs == ROWS_E1) return {b->d_norm_e1, b->d_obs[1], gather ? b->d_fwd_tab_feat : b->d_fwd_tab[1], 1, b->n_e1};
+    if (rs == ROWS_CENTRE) return {b->d_norm_c, b->d_obs[0], b->d_fwd_tab[0], 0, b->n_c};
+    return {rs == ROWS_SRC ? b->d_norm_src : nullptr, nullptr, gather ? b->d_fuse2_feat : b->d_fuse2, -1, rs == ROWS_SRC ? b->n_src : b->rows};
+}
+// Rows of a set, and the by-source edges of those rows, for the launch accounting: exact when it is on (ROWS_E1: read back / counted once per batch at first use, which
+// synchronises the stream), their bounds otherwise -- nobody reads them then
+static int64_t rows_kept(const gm_batch* b, RowSet rs, hipStream_t st) { return rs != ROWS_E1 ? row_view(b, rs, false).n : gm_prof_enabled() ? gm_batch_e1_rows(b, st) : std::min<int64_t>(b->n_e1, b->rows); }
+
+// What the partial aggregate launch of a fused layer moves (only the rows the fused kernel does not form itself: more than GM_FUSE_MAXDEG sources; of those, under
+// GM_DEAD_ROWS=3 / 4, the `formed` ones -- the others stop at their descriptor): *bytes as SURVEY 8(d) prices B_agg, *strict its compulsory HBM part
+static int partial_agg_bytes(const gm_batch* b, RowSet formed, int fi, bool gather, hipStream_t st, int64_t* bytes, int64_t* strict) {
+    // w = {rows written, their in-edges, their distinct sources}: read once and written once (the high-degree rows of a subgraph reach ~all of its rows).  Counted once
+    // per batch when the launch accounting is on, their bounds otherwise -- nobody reads them then
+    const bool all = formed == ROWS_ALL;
+    int64_t w[3] = {std::min<int64_t>(b->unfused_rows, row_view(b, formed, gather).n), b->unfused_edges, std::min<int64_t>(b->unfused_edges, b->rows)};
+    if (gm_prof_enabled() && all) w[2] = gm_batch_unfused_sources(b, st);
+    if (gm_prof_enabled() && !all) GM_TRY(gm_batch_fwd_counts(b, row_view(b, formed, gather).obs, st, w));
+    // every indptr entry; the norm of every row of more than GM_FUSE_MAXDEG sources (a restricted launch: its list entry and its flag); the edge-table entries of the
+    // rows written and those rows
+    const int64_t pb0 = 4 * (b->rows + 1) + (all ? 4 : 8) * b->unfused_rows + 4 * w[1] + 4 * w[0] * (int64_t)fi;
+    *bytes = pb0 + 4 * w[2] * (int64_t)fi;
+    // strict HBM pricing as for the full launches: a gather launch reads at most the whole (cache-resident) feature table
+    *strict = pb0 + 4 * (gather ? std::min<int64_t>(w[2], b->feat_rows) : w[2]) * (int64_t)fi;
+    gm_prof_note(GM_PROF_AGG_BOUND, pb0 + 4 * std::min<int64_t>(w[1], b->rows) * (int64_t)fi - *bytes);      // (difference of the sources' bound to their exact count)
+    return GM_OK;
+}
+// ... and the last layer's transposed aggregate of a t_centre backward (PassPlan), which works on n_out rows with e_out edges (every other row leaves behind its
+// descriptor): every indptr entry and every row scale; of the rows it works on the edge-table entries and the relu' bits; T_L's centre rows read once, the rows it
+// stores written once
+static int64_t t_centre_agg_bytes(const gm_batch* b, RowSet out, int fi, bool maskbits, hipStream_t st) {
+    const int64_t n_out = rows_kept(b, out, st), e_out = (out == ROWS_E1 && gm_prof_enabled()) ? gm_batch_e1_edges(b, st) : b->edges;
+    return 4 * (b->rows + 1) + 4 * b->rows + 4 * e_out + (maskbits ? n_out * (int64_t)fi / 4 : 0) + 4 * ((int64_t)b->n_c + n_out) * (int64_t)fi;
+}
+
 // The dZ GEMM of layer l >= 1 (dQ_l @ W_l^T: K = fo, N = fi) runs on the split kernels ...
 static bool dz_split_ok(const GcnCtx& c, int l) { return c.Wsplit && gm_gemm_split_ok(c.b->n_tiles, c.L.dims[l + 1], c.L.dims[l]); }
-// ... and on their fused loader, which reads a dQ_l that holds its centre rows only through the batch's table (DQ_CENTRE).  gcn_forward leaves dQ_L
-// unfilled, and gcn_backward reads it that way, by this one predicate
+// ... and on their fused loader, which reads a dQ_l that holds its centre rows only through the batch's table (DQ_CENTRE): plan_pass leaves dQ_L unfilled
+// only where this holds
 static bool dz_centre_ok(const GcnCtx& c, int l) { return dz_split_ok(c, l) && c.L.dims[l + 1] >= 64 && c.L.dims[l + 1] <= 4096 && c.b->d_dq_tab; }
 // GM_DEAD_ROWS=2: the zero block behind T_L = rows [rows, rows + GM_ZERO_ROWS) of bufB at T_L's width -- where gm_batch::d_ect sends every edge whose destination is
 // not a centre.  NULL where there is none: one GCN layer, the cone schedule, or a layer below the last whose T is wider than T_L and would run over the block.
@@ -900,9 +971,12 @@ static float* t_zero_rows(const GcnCtx& c) {
     for (int l = 0; l < Lg - 1; ++l) if (std::min(L.dims[l], L.dims[l + 1]) > L.dims[Lg - 1]) return nullptr;
     return c.bufB + c.b->rows * (int64_t)L.dims[Lg - 1];
 }
+// The GM_DEAD_ROWS level in force for this context: GM_CENTRE_STORE=0 ("every row stored") switches every level off, and so do user-supplied centres (the batch's
+// tables are built over its own)
+static int dead_row_level(const GcnCtx& c) { return (gm_knob().centre_store == 0 || c.centre) ? 0 : gm_knob().dead_rows; }
 static int t_zero_fill(GcnCtx& c, hipStream_t st) {
     float* z = t_zero_rows(c);
-    c.t_zero = z && gm_knob().dead_rows >= 2 && gm_knob().centre_store != 0 && dz_centre_ok(c, c.L.n_gcn - 1) && c.b->d_ect && c.b->d_norm_e1;
+    c.t_zero = z && dead_row_level(c) >= 2 && dz_centre_ok(c, c.L.n_gcn - 1) && c.b->d_ect && c.b->d_norm_e1;
     if (c.t_zero) GM_HIP(hipMemsetAsync(z, 0, sizeof(float) * GM_ZERO_ROWS * c.L.dims[c.L.n_gcn - 1], st));
     return GM_OK;
 }
@@ -912,89 +986,107 @@ static int cone_forward(GcnCtx& c, const float* params, int64_t pstride, float* 
 static int cone_backward(GcnCtx& c, const float* params, int64_t pstride, const float* dlogits, float* dparams, int64_t dstride, hipStream_t st, int skip_head);
 
 // skip_head: the head (centre gather + linear) is evaluated by the fused k_head_loss launch that follows
-// fwd_only: nobody differentiates this pass (query evaluations of the inner steps, finetunning's query passes): aggregate-first layers
-// whose update runs on the split-bf16 kernel take the FUSED aggregate + GEMM -- the aggregate of a row with one or two sources is formed
-// in the GEMM's A feeders (same fma order), only rows of other degrees go through the aggregate kernel and HBM; Z_l of the other
-// rows and the relu' bits are never written.  Same floats as the unfused pass, bit for bit.
+// kind: who reads the pass (PassKind); what follows from it is plan_pass's to decide.  gm_set_fuse_agg: the run-time switch of the fused aggregate + GEMM
 static std::atomic<int> g_fuse_agg_override{-1};
 extern "C" void gm_set_fuse_agg(int32_t on) { g_fuse_agg_override.store(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed); }
 extern "C" int32_t gm_get_fuse_agg(void) { const int o = g_fuse_agg_override.load(std::memory_order_relaxed); return o >= 0 ? o : gm_knob().fuse_agg; }
 
-static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* logits, hipStream_t st, int reuse_z1, int skip_head = 0, int fwd_only = 0) {
+// What the executors rely on without looking again
+static int plan_check(const GcnCtx& c, const PassPlan& p) {
+    for (int l = 0; l < c.L.n_gcn; ++l) {
+        GM_REQUIRE(p.layer[l].formed == ROWS_ALL || p.layer[l].fuse, GM_EINVAL, "plan: layer %d is formed on a row set but not fused: nothing reads it through the set's table", l);
+        GM_REQUIRE(p.layer[l].formed != ROWS_CENTRE || (l == c.L.n_gcn - 1 && p.layer[l].stored == ROWS_CENTRE && (l > 0 || c.x0_user)), GM_EINVAL, "plan: layer %d is formed on the centre rows, but is not a last layer that stores them alone and reads no feature table", l);
+    }
+    GM_REQUIRE(!(p.kind == PASS_DIFF && p.layer[c.L.n_gcn - 1].formed == ROWS_CENTRE) || p.dq == DQ_CENTRE, GM_EINVAL, "plan: a restricted differentiated pass must leave dQ to its centre rows");
+    GM_REQUIRE(!p.dq_e1 || p.t_centre, GM_EINVAL, "plan: dQ_{L-1} on the sources of the centres' in-edges needs T_L on its centre rows");
+    return GM_OK;
+}
+// The plan of one pass (PassPlan): reads the knobs, the layout, the batch's table pointers and the context; launches nothing.  The only place of the dense path that
+// reads GM_DEAD_ROWS / GM_CENTRE_STORE (through dead_row_level too), GM_FUSE_DIFF and gm_get_fuse_agg
+static int plan_check(const GcnCtx& c, const PassPlan& p);
+static int plan_pass(const GcnCtx& c, const float* params, int64_t pstride, PassKind kind, int reuse_z1, PassPlan* plan) {
+    const gm_layout& L = c.L; const gm_batch* b = c.b;
+    const int Lg = L.n_gcn, last = Lg - 1, level = dead_row_level(c), centre_store = gm_knob().centre_store;
+    const bool mean = mean_readout(c);      // every row of H_L is stored, dQ_L is written whole by the backward readout: no centre-row store, no dQ fill
+    auto agg_first = [&](int l) { return L.dims[l] <= L.dims[l + 1]; };      // learner.py:41-47 (else learner.py:34-40: multiply first, then aggregate)
+    auto wgrad_tabled = [&](int l) { return gm_wgrad_gather_ok(b->n_chunks, L.dims[l], L.dims[l + 1]); };      // the weight gradient's split kernel can form Z_l's rows from a table
+    PassPlan p{}; p.kind = kind; p.dq = DQ_MEMSET;
+    for (int l = 0; l < Lg; ++l) {
+        LayerPlan& lp = p.layer[l]; const int fi = L.dims[l];      // (formed = stored = ROWS_ALL)
+        lp.relu_bits = !agg_first(l) || kind != PASS_FWD_ONLY;
+        if (!agg_first(l)) continue;
+        lp.split = c.Wsplit && gm_gemm_split_ok(b->n_tiles, fi, L.dims[l + 1]) && ((uintptr_t)(params + L.b_off[l]) & 15) == 0 && pstride % 4 == 0;
+        const bool gather = (l == 0 && !c.x0_user);
+        // the fused aggregate + GEMM: in the passes nobody differentiates and, round 6, in the passes that ARE differentiated by the dense backward: their only
+        // other reader of Z_l is the weight gradient, whose split kernel forms the same rows from the same table (gm_wgrad_gather_ok; three-piece
+        // arithmetic only) -- the differentiated passes no longer write and re-read Z_l either (GM_FUSE_DIFF=0: as before)
+        // GM_FUSE_DIFF=2: ... except where the pass's full launches would take the stream aggregate (a support batch with stream tables, agg_stream.hip):
+        // that kernel runs INSIDE the CUs the query stream's GEMM occupies, a partial window launch competes with it for them
+        const bool keeps_stream = gm_knob().fuse_diff == 2 && c.is_support && gm_knob().agg_stream && gm_stream_batch_ok(b, 0);
+        const bool diff_ok = kind == PASS_DIFF && gm_knob().fuse_diff && !keeps_stream && c.np != 2 && !c.cone && wgrad_tabled(l);
+        lp.fuse = (kind == PASS_FWD_ONLY || diff_ok) && gm_get_fuse_agg() && lp.split && !(l == 0 && reuse_z1) && fi >= 64 && fi % 4 == 0 && b->d_fuse2 && b->d_enorm[0] &&
+                  (!gather || (b->feat_ld % 4 == 0 && b->feat_ld >= fi)) &&
+                  // worth it only where a good part of the rows has one or two sources: on dense batches (Tissue shape: ~30 in-edges per
+                  // row) nearly every row still goes through the ordinary aggregate and the gather feeders only cost (3.30 -> 3.21 ms)
+                  2 * b->unfused_rows <= b->rows;
+        // the stores of H_l (LayerPlan::stored).  GM_CENTRE_STORE: in every pass (2), in the forward-only passes (1); GM_DEAD_ROWS >= 1 below the last layer, where a
+        // differentiated pass has the relu' bits to write in the stores' place
+        if (l == last) { if (!mean && !c.centre && b->d_norm_c && (centre_store >= 2 || (centre_store == 1 && kind == PASS_FWD_ONLY))) lp.stored = ROWS_CENTRE; }
+        else if (level >= 1 && lp.split && (kind == PASS_FWD_ONLY || (kind == PASS_DIFF && c.M[l])) && L.dims[l + 1] <= L.dims[l + 2] && b->d_norm_src) lp.stored = ROWS_SRC;
+    }
+    // dQ_L, decided where the last layer is aggregate-first (a multiply-first one keeps DQ_MEMSET).  The head + loss + backward follow a PASS_DIFF (gm_meta_step): the
+    // last layer's GEMM zero-fills dQ on its way out instead of a memset launch.  GM_DEAD_ROWS >= 1: ... or no fill at all, where both readers of dQ_L can take the rows
+    // the head/loss launch does not assign as zeros: the dZ GEMM on the fused kernel through gm_batch::d_dq_tab, the weight gradient on the three-piece split kernel
+    // (gm_wgrad_args::g_keep; gcn_forward asserts that the forward launch got three pieces too)
+    if (kind == PASS_DIFF && agg_first(last) && !mean)
+        p.dq = (level >= 1 && p.layer[last].split && c.np != 2 && b->d_norm_c && (last == 0 || dz_centre_ok(c, last)) && wgrad_tabled(last)) ? DQ_CENTRE : DQ_ZEROED;
+    // GM_DEAD_ROWS=2 (PassPlan::t_centre, dq_e1).  Deeper models than two layers keep dQ_{L-1} whole: it is the A operand of a plain-loader dZ GEMM
+    p.t_centre = p.dq == DQ_CENTRE && c.t_zero && level >= 2;
+    p.dq_e1 = p.t_centre && Lg == 2 && agg_first(0) && c.np != 2 && wgrad_tabled(0);
+    // GM_DEAD_ROWS=3 / 4 (LayerPlan::formed): the last layer on the centre rows, the one below on the sources of the centres' in-edges.  What both levels need: the centre
+    // readout, three pieces, the batch's own centres and tables, the last layer fused on the split kernel ...
+    const bool last_ok = !mean && c.np != 2 && b->d_norm_c && b->d_norm_e1 && b->d_fwd_tab[0] && b->d_obs[0] && agg_first(last) && p.layer[last].fuse;
+    const bool below_ok = Lg >= 2 && agg_first(Lg - 2) && b->d_fwd_tab[1] && b->d_fwd_tab_feat && b->d_obs[1];
+    // Level 3: all anyone reads of a pass nobody differentiates is H_L at the centre rows, so Z_L is observable at the centre rows only, and H_{L-1} and Z_{L-1} only
+    // at the sources of the centres' in-edges.  (A last layer that gathers from the feature table has no table of its own: one-layer models stay as they are.)
+    const bool fwd3 = kind == PASS_FWD_ONLY && level >= 3 && centre_store >= 1 && last_ok && (Lg >= 2 || c.x0_user);
+    // Level 4: a gradient reaches Z_L at the centre rows only (dQ_L is zero everywhere else) and Z_{L-1} / H_{L-1} only at the sources of the centres' in-edges
+    // (dQ_{L-1} likewise), so the forward forms, fetches and stores exactly what level 3 does, and the weight gradients read Z_l through the same tables.
+    // Under level 3's preconditions plus what level 2 needs of this pass -- t_centre: dQ_L left to its centre rows and the zero block behind T_L; every pass's
+    // centre-row store (GM_CENTRE_STORE=2).  Not with a hoisted Z_1 (reuse_z1), which stays a flagged extra; one-layer models stay as they are.
+    // The relu' bits M[l] of a restricted layer are the every-row pass's on the observable rows; on every other row they come from a zero operand row (relu'(b_l):
+    // deterministic, not the every-row pass's).  Their readers: (a) the transposed aggregate behind support_bwd / the query backward (skip_head = 1, dq_e1):
+    // keep_signed over d_norm_e1, it forms -- and selects by the bits of -- the observable rows only; (b) the transposed aggregate of a backward that fills dQ_L
+    // itself (skip_head = 0: the meta-gradient through the last support pass) runs over every row, and on an unobservable row selects between +0 and
+    // (+0 aggregate) x norm = +0: the same +0 either way.
+    const bool diff4 = kind == PASS_DIFF && level >= 4 && centre_store >= 2 && p.t_centre && !reuse_z1 && Lg >= 2 && last_ok;
+    if (fwd3 || diff4) p.layer[last].formed = ROWS_CENTRE;
+    // The layer below.  Level 3: stored on ROWS_E1 wherever it runs on the split kernel, and formed on them where it is fused as well (not with a hoisted Z_1).  Level 4:
+    // under dq_e1 (two GraphConv layers, aggregate-first, the table-fed weight gradient), fused, with the relu' bits -- a three-layer model restricts its last layer only
+    if (below_ok && ((fwd3 && p.layer[Lg - 2].split) || (diff4 && p.dq_e1 && p.layer[0].fuse && c.M[0]))) {
+        p.layer[Lg - 2].stored = ROWS_E1; if (p.layer[Lg - 2].fuse) p.layer[Lg - 2].formed = ROWS_E1; }
+    *plan = p; return plan_check(c, p);
+}
+
+static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* logits, hipStream_t st, int reuse_z1, int skip_head = 0, PassKind kind = PASS_PLAIN) {
     if (c.cone) return cone_forward(c, params, pstride, logits, st, reuse_z1, skip_head);
     const gm_layout& L = c.L; const gm_batch* b = c.b;
     if (!c.x0_user) GM_TRY(gm_check_feat_dim(b, L.dims[0], "forward"));
     GM_REQUIRE((L.link != 0) == (b->centres == 2), GM_EINVAL, "forward: link_pred model needs a 2-centre batch and vice versa");
     const float* xin = c.x0_user;           // NULL = gather rows of the store through feat_row
-    c.dq = GcnCtx::DQ_MEMSET;
-    const bool mean = mean_readout(c);      // every row of H_L is stored, dQ_L is written whole by the backward readout: no centre-row store, no dQ fill
+    GM_TRY(plan_pass(c, params, pstride, kind, reuse_z1, &c.plan));
+    const PassPlan& plan = c.plan; const bool mean = mean_readout(c);
     if (mean) GM_TRY(readout_tables(b, st));
-    // GM_DEAD_ROWS: rows nobody reads are computed and not stored (GM_CENTRE_STORE=0, "every row stored", switches it off too)
-    const bool dead_rows = gm_knob().dead_rows && gm_knob().centre_store != 0 && !c.centre;
     if (c.np == 2) {                        // a new pass: its own bound slots
         ++c.am_pass;
         GM_REQUIRE(c.am_pass < c.am_passes, GM_EINVAL, "forward: more passes than bound slots (%d)", c.am_passes);
         for (int l = 0; l < GM_MAX_GCN; ++l) c.hv[l] = c.tv[l] = false;
         c.dqv = false;
     }
-    // an aggregate-first layer's update runs on the split kernel ...
-    auto layer_split_ok = [&](int l) {
-        return c.Wsplit && gm_gemm_split_ok(b->n_tiles, L.dims[l], L.dims[l + 1]) && ((uintptr_t)(params + L.b_off[l]) & 15) == 0 && pstride % 4 == 0;
-    };
-    // ... and takes the fused aggregate + GEMM: the passes nobody differentiates (fwd_only == 1) ...
-    auto layer_fuse = [&](int l) {
-        const int fi = L.dims[l], fo = L.dims[l + 1];
-        const bool gather = (l == 0 && !c.x0_user);
-        // ... and, round 6, the passes that ARE differentiated by the dense backward (fwd_only == 2: the support passes, the last query pass): their only
-        // other reader of Z_l is the weight gradient, whose split kernel forms the same rows from the same table (gm_wgrad_gather_ok; three-piece
-        // arithmetic only) -- the differentiated passes no longer write and re-read Z_l either (GM_FUSE_DIFF=0: as before)
-        // GM_FUSE_DIFF=2: ... except where the pass's full launches would take the stream aggregate (a support batch with stream tables, agg_stream.hip):
-        // that kernel runs INSIDE the CUs the query stream's GEMM occupies, a partial window launch competes with it for them
-        const bool keeps_stream = gm_knob().fuse_diff == 2 && c.is_support && gm_knob().agg_stream && gm_stream_batch_ok(b, 0);
-        const bool diff_ok = fwd_only == 2 && gm_knob().fuse_diff && !keeps_stream && c.np != 2 && !c.cone && gm_wgrad_gather_ok(b->n_chunks, fi, fo);
-        return (fwd_only == 1 || diff_ok) && gm_get_fuse_agg() && layer_split_ok(l) && !(l == 0 && reuse_z1) && fi >= 64 && fi % 4 == 0 && b->d_fuse2 && b->d_enorm[0] &&
-               (!gather || (b->feat_ld % 4 == 0 && b->feat_ld >= fi)) &&
-               // worth it only where a good part of the rows has one or two sources: on dense batches (Tissue shape: ~30 in-edges per
-               // row) nearly every row still goes through the ordinary aggregate and the gather feeders only cost (3.30 -> 3.21 ms)
-               2 * b->unfused_rows <= b->rows;
-    };
-    // GM_DEAD_ROWS=3: the same rule one level down the passes nobody differentiates (fwd_only == 1).  All anyone reads of such a pass is H_L at the centre rows, so
-    // Z_L is observable at the centre rows only, and H_{L-1} and Z_{L-1} only at the sources of the centres' in-edges (the rows gm_batch::d_norm_e1 keeps).  Every tile
-    // and every MFMA is still issued, no product and no sum that reaches a stored value is dropped or reordered:
-    //  * the fused loaders read Z_l / H_{l-1} through gm_batch::d_fwd_tab (d_fwd_tab_feat), which sends every unobservable row to the zero row: they never touch a
-    //    row this pass did not write;
-    //  * the partial aggregate launches form the observable rows only (s_out = gm_batch::d_obs: +-1, keep_signed -- the scale is exactly the 1 the launch applies
-    //    without it; flagged rows stop at their descriptor, agg.hip: agg_unobservable);
-    //  * the update below the last stores the rows d_norm_e1 keeps instead of every row with an out-edge (d_norm_src).
-    // Under level 2's preconditions (centre readout, three pieces, the batch's own centres and tables) and where the last layer runs fused on the split kernel
-    const int Lg = L.n_gcn;
-    const bool fwd3_last = fwd_only == 1 && gm_knob().dead_rows >= 3 && dead_rows && gm_knob().centre_store >= 1 && !mean && c.np != 2 && b->d_norm_c && b->d_norm_e1 &&
-                           b->d_fwd_tab[0] && b->d_obs[0] && L.dims[Lg - 1] <= L.dims[Lg] && layer_fuse(Lg - 1) &&
-                           (Lg >= 2 || c.x0_user);      // (a last layer that gathers from the feature table has no table of its own: one-layer models stay as they are)
-    const bool fwd3_below = fwd3_last && Lg >= 2 && L.dims[Lg - 2] <= L.dims[Lg - 1] && layer_split_ok(Lg - 2) && b->d_fwd_tab[1] && b->d_fwd_tab_feat && b->d_obs[1];
-    // GM_DEAD_ROWS=4: the same restriction in the passes the dense backward differentiates (fwd_only == 2).  A gradient reaches Z_L at the centre rows only (dQ_L is
-    // zero everywhere else) and Z_{L-1} / H_{L-1} only at the sources of the centres' in-edges (dQ_{L-1} likewise), so the forward forms, fetches and stores exactly
-    // what level 3 does, and the weight gradients read Z_l through the same tables (GcnCtx::zobs; gcn_backward).  Decided HERE, once, and recorded per layer: it holds
-    // under level 3's preconditions plus what level 2 needs of this pass -- dQ_L left to its centre rows (the DQ_CENTRE predicate below, evaluated up front), the zero
-    // block behind T_L (t_zero), every pass's centre-row store (GM_CENTRE_STORE=2) -- and, below the last layer, gcn_backward's dq_e1 conditions (two GraphConv layers,
-    // aggregate-first, the table-fed weight gradient, relu' bits).  Not with a hoisted Z_1 (reuse_z1), which stays a flagged extra.
-    // The relu' bits M[l] of a restricted layer are the every-row pass's on the observable rows; on every other row they come from a zero operand row (relu'(b_l): deterministic,
-    // not the every-row pass's).  Their readers: (a) the transposed aggregate behind support_bwd / the query backward (skip_head = 1, dq_e1): keep_signed over d_norm_e1, it
-    // forms -- and selects by the bits of -- the observable rows only; (b) the transposed aggregate of a backward that fills dQ_L itself (skip_head = 0: the meta-gradient
-    // through the last support pass) runs over every row, and on an unobservable row selects between +0 and (+0 aggregate) x norm = +0: the same +0 either way.
-    const bool dq_centre_fwd = fwd_only == 2 && !mean && dead_rows && layer_split_ok(Lg - 1) && c.np != 2 && b->d_norm_c && (Lg == 1 || dz_centre_ok(c, Lg - 1)) &&
-                               gm_wgrad_gather_ok(b->n_chunks, L.dims[Lg - 1], L.dims[Lg]);
-    const bool diff4_last = dq_centre_fwd && gm_knob().dead_rows >= 4 && gm_knob().centre_store >= 2 && c.t_zero && !reuse_z1 && Lg >= 2 && b->d_norm_e1 &&
-                            b->d_fwd_tab[0] && b->d_obs[0] && L.dims[Lg - 1] <= L.dims[Lg] && layer_fuse(Lg - 1);
-    const bool diff4_below = diff4_last && Lg == 2 && L.dims[0] <= L.dims[1] && layer_fuse(0) && gm_wgrad_gather_ok(b->n_chunks, L.dims[0], L.dims[1]) && c.M[0] &&
-                             b->d_fwd_tab[1] && b->d_fwd_tab_feat && b->d_obs[1];
-    for (int l = 0; l < GM_MAX_GCN; ++l) c.zobs[l] = GcnCtx::ZOBS_NONE;
     for (int l = 0; l < L.n_gcn; ++l) {
         const int fi = L.dims[l], fo = L.dims[l + 1];
         const bool gather = (l == 0 && !c.x0_user);
-        // GM_DEAD_ROWS=3 / 4: the layer's observable row set (gm_batch::d_obs), or none
-        const int obs = ((fwd3_last || diff4_last) && l == Lg - 1) ? 0 : ((fwd3_below || diff4_below) && l == Lg - 2) ? 1 : -1;
-        if (fwd_only == 2) c.zobs[l] = obs == 0 ? GcnCtx::ZOBS_CENTRE : obs == 1 ? GcnCtx::ZOBS_E1 : GcnCtx::ZOBS_NONE;
+        const LayerPlan& lp = plan.layer[l]; uint8_t* relu_bits = lp.relu_bits ? c.M[l] : nullptr;
         if (fi > fo) {                      // learner.py:34-40: multiply first, then aggregate
             const float* A = xin; int64_t lda = fi;
             if (gather) { GM_TRY(gm_gather_rows(b, b->d_feat_row, b->rows, fi, c.X0, st)); A = c.X0; }
@@ -1004,18 +1096,15 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
             gm_agg_args a; GM_TRY(batch_agg(c, 0, st, a));
             a.x = c.Z[l]; a.ldx = fo; a.s_out = b->d_norm;
             a.bias = params + L.b_off[l]; a.bias_stride = pstride; a.set_row_off = b->d_set_row_off; a.n_sets = b->sets; a.relu = 1;
-            a.out = c.H[l]; a.width = fo; a.relu_bits = c.M[l];
+            a.out = c.H[l]; a.width = fo; a.relu_bits = relu_bits;
             GM_TRY(launch_agg(a, gm_aggregate_bytes(b, fo), gm_aggregate_bytes(b, fo), st));
         } else {                            // learner.py:41-47: aggregate first, then multiply
-            const bool split_ok = layer_split_ok(l);
-            const bool fuse = layer_fuse(l);
-            c.zfused[l] = fuse && fwd_only == 2;
+            const float* x = gather ? b->feat : xin; const int64_t ldx = gather ? b->feat_ld : fi;      // the layer's input as the aggregate and the fused loader read it
             if (!(l == 0 && reuse_z1 && c.z1_valid)) {
                 gm_agg_args a; GM_TRY(batch_agg(c, 0, st, a));
                 a.s_in = b->d_norm; a.e_w = b->d_enorm[0]; a.out = c.Z[l]; a.width = fi;
-                if (gather) { a.x = b->feat; a.x_row = b->d_feat_row; a.x_idx = b->d_efeat; a.ldx = b->feat_ld; }
-                else { a.x = xin; a.ldx = fi; }
-                if (fuse) {
+                a.x = x; a.ldx = ldx; if (gather) { a.x_row = b->d_feat_row; a.x_idx = b->d_efeat; }
+                if (lp.fuse) {
                     // only the rows the fused kernel does not form itself (more than GM_FUSE_MAXDEG sources): a partial launch
                     a.skip_on = 1; a.skip_lo = 0; a.skip_hi = GM_FUSE_MAXDEG;
                     if (b->d_mid && c.hub_set == 0 && gm_knob().agg_mid_list && (b->n_heavy[0] == 0 || b->d_sched_mid)) {
@@ -1024,27 +1113,10 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
                         if (b->n_heavy[0] > 0) { a.sched = b->d_sched_mid; a.sched_len = b->sched_len_mid; a.sched_win = b->mid_win; }
                         else { a.sched = nullptr; a.sched_len = 0; }
                     }
-                    // SURVEY 8(d)'s B_agg restricted to what this launch touches: every indptr entry, the indices / norms of the rows it writes,
-                    // those rows (written once) and their sources (read once: the high-degree rows of a subgraph reach ~all of its rows)
-                    int64_t pb0 = 4 * (b->rows + 1) + 4 * b->unfused_edges + 4 * b->unfused_rows + 4 * b->unfused_rows * (int64_t)fi;
-                    // (their DISTINCT sources when the launch accounting is on: counted once per batch; the bound min(edges, rows) otherwise -- nobody reads it then)
-                    int64_t src, src_bound = std::min<int64_t>(b->unfused_edges, b->rows);
-                    if (obs >= 0) {
-                        // GM_DEAD_ROWS=3: of those rows only the observable ones are formed; the others stop at their descriptor (list entry, row bounds, flag)
-                        a.s_out = b->d_obs[obs]; a.keep_signed = 1;
-                        // {rows written, their in-edges, their distinct sources}: counted once per batch when the launch accounting is on, their bounds otherwise
-                        int64_t w[3] = {std::min<int64_t>(b->unfused_rows, obs == 0 ? b->n_c : b->n_e1), b->unfused_edges, 0};
-                        w[2] = std::min<int64_t>(w[1], b->rows);
-                        if (gm_prof_enabled()) GM_TRY(gm_batch_fwd_counts(b, obs, st, w));
-                        // every indptr entry; the list entry and the flag of every row of more than GM_FUSE_MAXDEG sources; the edge-table entries of the rows written,
-                        // those rows (written once) and their sources (read once)
-                        pb0 = 4 * (b->rows + 1) + 8 * b->unfused_rows + 4 * w[1] + 4 * w[0] * (int64_t)fi;
-                        src = w[2]; src_bound = std::min<int64_t>(w[1], b->rows);
-                    } else src = gm_prof_enabled() ? gm_batch_unfused_sources(b, st) : src_bound;
-                    const int64_t pb = pb0 + 4 * src * (int64_t)fi;
-                    // strict HBM pricing as for the full launches: a gather launch reads at most the whole (cache-resident) feature table
-                    const int64_t pbs = pb0 + 4 * (gather ? std::min<int64_t>(src, b->feat_rows) : src) * (int64_t)fi;
-                    gm_prof_note(GM_PROF_AGG_BOUND, pb0 + 4 * src_bound * (int64_t)fi - pb);      // (difference to the exact count)
+                    // ... and of those only the rows the plan forms; the others stop at their descriptor (list entry, row bounds, flag)
+                    if (lp.formed != ROWS_ALL) { a.s_out = row_view(b, lp.formed, gather).sign; a.keep_signed = 1; }
+                    int64_t pb, pbs;
+                    GM_TRY(partial_agg_bytes(b, lp.formed, fi, gather, st, &pb, &pbs));
                     GM_TRY(launch_agg(a, pb, pbs, st));
                 } else {
                     if (a.e_w) GM_TRY(gm_agg_stream_args(a, b, 0, gather, st));      // full launches may take the LDS-DMA stream kernel (agg_stream.hip)
@@ -1057,42 +1129,15 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
             }
             gm_gemm_args g{}; g.A = c.Z[l]; g.lda = fi; g.B = params + L.w_off[l]; g.b_stride = pstride; g.C = c.H[l]; g.ldc = fo; g.K = fi; g.N = fo;
             g.row_scale = b->d_norm; g.bias = params + L.b_off[l]; g.bias_stride = pstride; g.relu = 1; g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows;
-            g.relu_bits = fwd_only == 1 ? nullptr : c.M[l];
-            // last layer: only the head reads H_L, and only its centre rows (h[to_fetch]; the backward pass takes relu' from the bits and the
-            // weight gradient from Z_L): the other rows are computed, their relu' bits written, their values not stored
-            if (l == L.n_gcn - 1 && !mean && !c.centre && b->d_norm_c && (gm_knob().centre_store >= 2 || (gm_knob().centre_store == 1 && fwd_only == 1))) { g.row_scale_keep = b->d_norm_c; g.n_keep = b->n_c; }
-            // a layer below the last: H_l is read through the edges only (the next layer's aggregate, the fused loaders, the table-formed weight gradient; the
-            // backward takes relu' from the bits) -- a row without an out-edge is nobody's source: computed, its relu' bits written, its value not stored
-            if (dead_rows && split_ok && l < L.n_gcn - 1 && (fwd_only == 1 || (fwd_only == 2 && c.M[l])) && L.dims[l + 1] <= L.dims[l + 2] && b->d_norm_src) {
-                g.row_scale_keep = b->d_norm_src; g.n_keep = b->n_src;
+            g.relu_bits = relu_bits;
+            // the other rows are computed, their relu' bits written, their values not stored (the kept-row count is for the launch accounting)
+            if (lp.stored != ROWS_ALL) { g.row_scale_keep = row_view(b, lp.stored, false).keep; g.n_keep = rows_kept(b, lp.stored, st); }
+            if (lp.split) {
+                GM_TRY(weight_planes(c, params, pstride, l, 0, st, g));
+                GM_REQUIRE(!(l == L.n_gcn - 1 && plan.dq == DQ_CENTRE) || g.np == 3, GM_EINVAL, "forward: dQ is left to its centre rows, which needs the three-piece kernels");
             }
-            // GM_DEAD_ROWS=3: ... and in a pass nobody differentiates only a source of a centre's in-edge is the source of an edge anyone walks (a subset of the rows
-            // above; the kept-row count is read back only when the launch accounting is on, its bound otherwise -- nobody reads it then)
-            if (obs == 1) { g.row_scale_keep = b->d_norm_e1; g.n_keep = gm_prof_enabled() ? gm_batch_e1_rows(b, st) : std::min<int64_t>(b->n_e1, b->rows); }
-            if (split_ok) {
-                gm_bound ab = gm_no_bound(), bb;
-                const bool want16 = in_bound(c, l, ab);
-                const uint16_t* pl = nullptr;                                                 // left by the reduction that wrote these weights, else split now
-                int np = 3;
-                GM_TRY(weight_planes(c, params, pstride, l, 0, fi, fo, want16, st, &pl, &bb, &np));
-                g.Bsplit = pl; g.bsplit_stride = pstride ? (int64_t)3 * fi * fo : 0;
-                g.np = np; g.a_bound = ab; g.b_bound = bb;
-                if (np == 2) { g.amax_out = c.amH(l); c.hv[l] = true; }        // (the two-piece kernels record it)
-            }
-            // fwd_only == 2: the head + loss + backward follow (gm_meta_step): the last layer's GEMM zero-fills dQ on its way out instead of a memset launch
-            // GM_DEAD_ROWS: ... or no fill at all, where both readers of dQ_L can take the rows the head/loss launch does not assign as zeros: the dZ GEMM on the
-            // fused kernel through gm_batch::d_dq_tab, the weight gradient on the three-piece split kernel (gm_wgrad_args::g_keep)
-            if (fwd_only == 2 && l == L.n_gcn - 1 && fo == L.dims[L.n_gcn] && !mean) {
-                const bool dz_ok = l == 0 || dz_centre_ok(c, l);
-                if (dead_rows && split_ok && g.np != 2 && c.np != 2 && b->d_norm_c && dz_ok && gm_wgrad_gather_ok(b->n_chunks, fi, fo)) c.dq = GcnCtx::DQ_CENTRE;
-                else { g.zero_out = c.bufA; c.dq = GcnCtx::DQ_ZEROED; }
-            }
-            GM_REQUIRE(!(fwd_only == 2 && obs == 0) || c.dq == GcnCtx::DQ_CENTRE, GM_EINVAL, "forward: a restricted differentiated pass must leave dQ to its centre rows");
-            if (fuse) {
-                g.zside = c.Z[l]; g.ldz = fi;
-                if (gather) { g.A = b->feat; g.lda = b->feat_ld; g.fuse2 = obs == 1 ? b->d_fwd_tab_feat : b->d_fuse2_feat; }
-                else { g.A = xin; g.lda = fi; g.fuse2 = obs >= 0 ? b->d_fwd_tab[obs] : b->d_fuse2; }
-            }
+            if (l == L.n_gcn - 1 && plan.dq == DQ_ZEROED) g.zero_out = c.bufA;
+            if (lp.fuse) { g.A = x; g.lda = ldx; g.zside = c.Z[l]; g.ldz = fi; g.fuse2 = row_view(b, lp.formed, gather).tab; }
             GM_TRY(gm_launch_gemm_nn(g, st));
         }
         xin = c.H[l];
@@ -1109,11 +1154,11 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
                         int skip_head = 0) {
     if (c.cone) return cone_backward(c, params, pstride, dlogits, dparams, dstride, st, skip_head);
     if (sparse && sparse_bwd_ok(c.L)) return gcn_backward_sparse(c, params, pstride, dlogits, dparams, dstride, st, skip_head);
-    const gm_layout& L = c.L; const gm_batch* b = c.b;
-    const int Lg = L.n_gcn;
+    const gm_layout& L = c.L; const gm_batch* b = c.b; const int Lg = L.n_gcn;
     float* dQ = c.bufA; float* T = c.bufB;
     c.hold.n = 0;
-    const bool dq_centre = skip_head && c.dq == GcnCtx::DQ_CENTRE;      // dQ_L holds its centre rows only (head_loss); without skip_head it is filled right here
+    const PassPlan& plan = c.plan;      // as the forward stored it: never derived again (gm_set_fuse_agg may have changed since)
+    const bool dq_centre = skip_head && plan.dq == DQ_CENTRE;      // dQ_L holds its centre rows only (head_loss); without skip_head it is filled right here
     // GM_DEAD_ROWS=2: the same rule one level down.  Every row of T_L = norm (dQ_L W_L^T) outside the centre rows is an exact zero, and so is every row of dQ_{L-1} =
     // relu' norm A^T T_L that is not the source of an in-edge of a centre.  Every row is still computed, no product and no sum is dropped:
     //  * the dZ GEMM stores T_L's centre rows only (row_scale_keep = d_norm_c);
@@ -1123,8 +1168,7 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
     //    NaN and not these: the forward over the same weights then gave a NaN loss, and the NaN guard discards the step -- DESIGN 4.3);
     //  * where the layer below is the first, that aggregate stores only the rows of dQ_{L-1} that can be non-zero (s_out = d_norm_e1, keep_signed), and the first
     //    layer's weight gradient selects zeros for the others (g_keep).  Deeper models keep dQ_{L-1} whole: it is the A operand of a plain-loader dZ GEMM.
-    const bool t_centre = dq_centre && c.t_zero && gm_knob().dead_rows >= 2;
-    const bool dq_e1 = t_centre && Lg == 2 && L.dims[0] <= L.dims[1] && c.np != 2 && gm_wgrad_gather_ok(b->n_chunks, L.dims[0], L.dims[1]);
+    const bool t_centre = dq_centre && plan.t_centre, dq_e1 = t_centre && plan.dq_e1;
     const bool dq_filled = !skip_head && !mean_readout(c);      // this call zero-fills dQ_L whole (below) before the head writes its centre rows
     if (!skip_head && mean_readout(c)) {      // G = dlogits Wl on the pooled rows, then every row of dQ_L from it
         GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, nullptr, c.Gpool, st));
@@ -1164,29 +1208,27 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
             // Order: dZ GEMM (reads dQ and the CURRENT weights) -> weight gradient (reads dQ; its reduction writes the updated
             // weights and, for the next step's dZ GEMM, their transpose) -> transposed aggregate (overwrites dQ).
             w.A = c.Z[l]; w.lda = fi; w.G = dQ; w.ldg = fo;
-            if (dq_centre && l == Lg - 1) w.g_keep = b->d_norm_c;
-            if (dq_e1 && l == Lg - 2) w.g_keep = b->d_norm_e1;      // dQ_{L-1} holds the sources of the centres' in-edges only; the other rows' bytes may be anything
-            if (c.zfused[l]) {                 // the forward ran fused: Z[l] holds the rows of three or more sources, the table forms the others
+            // the rows of dQ_l that were written: dQ_L its centre rows, dQ_{L-1} the sources of the centres' in-edges; the other rows' bytes may be anything
+            const RowSet g_rows = (dq_centre && l == Lg - 1) ? ROWS_CENTRE : (dq_e1 && l == Lg - 2) ? ROWS_E1 : ROWS_ALL;
+            w.g_keep = row_view(b, g_rows, false).keep;
+            const RowSet z_rows = plan.layer[l].formed;
+            if (plan.layer[l].fuse) {            // the forward ran fused: Z[l] holds the rows of three or more sources, the table forms the others
                 const bool gather = l == 0 && !c.x0_user;
-                w.fuse2 = gather ? b->d_fuse2_feat : b->d_fuse2;
-                // GM_DEAD_ROWS=4: ... and of a restricted pass (GcnCtx::zobs) through the forward's own table: an unobservable row of A is the zero row -- the forward
+                // GM_DEAD_ROWS=4: ... and of a restricted pass through the forward's own table: an unobservable row of A is the zero row -- the forward
                 // wrote neither its Z_l row nor (one layer down) the H_{l-1} rows the full table would gather for it
-                if (c.zobs[l] == GcnCtx::ZOBS_CENTRE) w.fuse2 = b->d_fwd_tab[0];
-                if (c.zobs[l] == GcnCtx::ZOBS_E1) w.fuse2 = gather ? b->d_fwd_tab_feat : b->d_fwd_tab[1];
+                w.fuse2 = row_view(b, z_rows, gather).tab;
                 w.gx = gather ? b->feat : (l > 0 ? c.H[l - 1] : c.x0_user); w.ldgx = gather ? b->feat_ld : fi;
             }
-            if (c.zobs[l] != GcnCtx::ZOBS_NONE) {
+            if (z_rows != ROWS_ALL) {          // (always tabled: plan_check)
                 // The zero rows of A stand in for finite rows the every-row pass multiplies by zero rows of G: those rows of G must BE zeros here too -- selected (g_keep:
                 // the backward behind head_loss, whose dQ holds the observable rows only), or true zeros because this very call filled dQ_L before the head
                 // wrote its centre rows (skip_head = 0: the meta-gradient through the last support pass, which runs over the Z / H / M that pass's restricted
                 // forward left).  Bitwise the every-row pass in both: a +-0 product added to a chain that started at +0 leaves the chain unchanged (bsum and the MFMA
                 // accumulators start at +0; a zero A row makes the same +-0 products as a finite one); in the second, dQ_L's other rows are the memset's +0, T_L's are
                 // +0 x norm, the transposed aggregate's +0-started chains over them stay +0, and the relu' select yields +0 whichever way the bit reads
-                GM_REQUIRE(c.zfused[l] && w.fuse2, GM_EINVAL, "backward: layer %d was formed on its observable rows only, its weight gradient needs the source table", l);
-                GM_REQUIRE(w.g_keep || dq_filled, GM_EINVAL,
-                           "backward: layer %d was formed on its observable rows only, but its weight gradient got neither flagged rows of G (g_keep) nor a dQ this call zero-filled", l);
+                GM_REQUIRE(w.g_keep || dq_filled, GM_EINVAL, "backward: layer %d was formed on its observable rows only, but its weight gradient got neither flagged rows of G (g_keep) nor a dQ this call zero-filled", l);
                 // launch accounting: A is fetched on the observable rows only (every other row reads the cache-resident zero row)
-                if (gm_prof_enabled()) w.a_rows = c.zobs[l] == GcnCtx::ZOBS_CENTRE ? std::min<int64_t>(b->n_c, b->rows) : gm_batch_e1_rows(b, st);
+                if (gm_prof_enabled()) w.a_rows = rows_kept(b, z_rows, st);
             }
             if (l > 0) {
                 gm_gemm_args g{}; g.A = dQ; g.lda = fo; g.C = T; g.ldc = fi; g.K = fo; g.N = fi;
@@ -1195,19 +1237,13 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
                 const bool use_wt = !use_split && c.WTl[l] && fi % 64 == 0 && fo % 16 == 0;
                 if (use_split) {
                     // B = W^T with W stored [fi][fo]: the planes are W's own rows (no transpose), K = fo, N = fi
-                    gm_bound ab = gm_no_bound(), bb;
-                    const bool want16 = dq_bound(c, l, ab);
-                    const uint16_t* pl = nullptr; int np = 3;
-                    GM_TRY(weight_planes(c, params, pstride, l, 1, fo, fi, want16, st, &pl, &bb, &np));
-                    g.Bsplit = pl; g.bsplit_stride = pstride ? (int64_t)3 * fi * fo : 0;
-                    g.np = np; g.a_bound = ab; g.b_bound = bb;
-                    if (np == 2) { g.amax_out = c.amT(l); c.tv[l] = true; }
+                    GM_TRY(weight_planes(c, params, pstride, l, 1, st, g));
                     g.B = params + L.w_off[l]; g.b_stride = pstride; g.transB = 1;
                     // dQ_L with its centre rows only: the fused kernel's loader reads them through the batch's table (fma(0, 0, fma(x, 1, 0)) = x) and zeros for
-                    // every other row -- the same tile, bit for bit, as the plain launch over a zero-filled dQ.  (dz_centre_ok is what gcn_forward chose
-                    // DQ_CENTRE by, so it holds here whenever dq_centre does: the two ends of one contract, and the GM_REQUIRE below is its guard)
-                    if (dq_centre && l == Lg - 1 && dz_centre_ok(c, l)) { g.fuse2 = b->d_dq_tab; g.zside = dQ; g.ldz = fo; }
-                    if (t_centre && l == Lg - 1) { g.row_scale_keep = b->d_norm_c; g.n_keep = b->n_c; }
+                    // every other row -- the same tile, bit for bit, as the plain launch over a zero-filled dQ.  (plan_pass chose DQ_CENTRE under dz_centre_ok, which
+                    // holds for a context or not at all: a dQ_L left to its centre rows always comes this way)
+                    if (dq_centre && l == Lg - 1) { g.fuse2 = b->d_dq_tab; g.zside = dQ; g.ldz = fo; }
+                    if (t_centre && l == Lg - 1) { g.row_scale_keep = row_view(b, ROWS_CENTRE, false).keep; g.n_keep = rows_kept(b, ROWS_CENTRE, st); }
                 } else if (use_wt) {
                     // dZ = dQ @ W^T through the direct-to-LDS kernel on transposed weights: left there by the previous step's
                     // weight-gradient reduction (which wrote these very weights), else transposed now (T x 256 KB)
@@ -1219,7 +1255,6 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
                     }
                     g.B = c.WTl[l]; g.b_stride = pstride ? (int64_t)fi * fo : 0; g.transB = 0;
                 } else { g.B = params + L.w_off[l]; g.b_stride = pstride; g.transB = 1; }
-                GM_REQUIRE(!(dq_centre && l == Lg - 1) || g.fuse2, GM_EINVAL, "backward: dQ was left unfilled for a dZ GEMM that cannot read it through the table");
                 GM_TRY(gm_launch_gemm_nn(g, st));
                 if (use_wt && c.sgd.next) { w.wt_next = c.WTl[l]; }
             }
@@ -1242,16 +1277,9 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
                 int64_t by = gm_aggregate_bytes(b, fi);
                 if (t_centre && l == Lg - 1) {
                     a.x_idx = b->d_ect;
-                    int64_t n_out = b->rows, e_out = b->edges;      // the rows the launch works on (every other row leaves behind its descriptor), and their edges
-                    if (dq_e1) {
-                        a.s_out = b->d_norm_e1; a.keep_signed = 1;
-                        // (the exact counts when the launch accounting is on: read back / counted once per batch; their bounds otherwise -- nobody reads them then)
-                        n_out = gm_prof_enabled() ? gm_batch_e1_rows(b, st) : std::min<int64_t>(b->n_e1, b->rows);
-                        e_out = gm_prof_enabled() ? gm_batch_e1_edges(b, st) : b->edges;
-                    }
-                    // SURVEY 8(d)'s B_agg on what this launch touches: every indptr entry and every row scale; of the rows it works on the edge-table entries
-                    // and the relu' bits; T_L's centre rows read once, the rows it stores written once
-                    by = 4 * (b->rows + 1) + 4 * b->rows + 4 * e_out + (maskbits ? n_out * (int64_t)fi / 4 : 0) + 4 * ((int64_t)b->n_c + n_out) * (int64_t)fi;
+                    const RowSet out = dq_e1 ? ROWS_E1 : ROWS_ALL;      // the rows the launch works on (every other row leaves behind its descriptor)
+                    if (dq_e1) { a.s_out = row_view(b, out, false).keep; a.keep_signed = 1; }
+                    by = t_centre_agg_bytes(b, out, fi, maskbits != nullptr, st);
                 }
                 GM_TRY(launch_agg(a, by, by, st));
             }
@@ -1683,7 +1711,7 @@ static int head_loss(GcnCtx& c, const float* params, int64_t pstride, float* log
         else if (sparse && sparse_bwd_ok(L)) Gc = c.cG2;
         else {
             dQ = c.bufA;
-            if (c.dq == GcnCtx::DQ_MEMSET) GM_HIP(hipMemsetAsync(dQ, 0, sizeof(float) * b->rows * L.dims[L.n_gcn], st));      // (DQ_CENTRE: nobody reads the rows this launch does not assign)
+            if (c.plan.dq == DQ_MEMSET) GM_HIP(hipMemsetAsync(dQ, 0, sizeof(float) * b->rows * L.dims[L.n_gcn], st));      // (DQ_CENTRE: nobody reads the rows this launch does not assign)
         }
     }
     const HeadK hk = make_head(c, params, pstride);
@@ -1895,7 +1923,7 @@ static int pad_theta(const SupportPlan& p, const float** theta, int64_t P, int64
 // w_next == NULL: the forward and the prototypes only, no support_bwd follows (gm_meta_adapt with K = 0).
 static int support_head(SupportPlan& p, const gm_hparams_t* hp, int k, const float* w, int64_t wstride, float* w_next, float* protos, hipStream_t st) {
     const int bwd = w_next ? 1 : 0, sparse = hp->sparse_bwd;
-    GM_TRY(gcn_forward(p.S, w, wstride, p.logit_s, st, hp->hoist_z1, 1, (sparse && sparse_bwd_ok(p.L)) ? 0 : 2));
+    GM_TRY(gcn_forward(p.S, w, wstride, p.logit_s, st, hp->hoist_z1, 1, (sparse && sparse_bwd_ok(p.L)) ? PASS_PLAIN : PASS_DIFF));
     if (bwd) p.S.sgd = SgdK{w, wstride, w_next, p.Pp, hp->update_lr};
     ProtoK pk{p.logit_s, p.L.n_out, p.rows_s, p.Ct, p.ns, 0, nullptr, protos, p.ls, p.as_, p.K + 1, k, bwd ? p.dlog_s : nullptr, nullptr, 0, p.tab_s, p.uni_s};
     return head_loss(p.S, w, wstride, p.logit_s, pk, bwd, p.g, p.Pp, sparse, st, p.qmax_s != 0);
@@ -2098,10 +2126,10 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
     auto q_ctx = [&](int j) -> GcnCtx& { return (two_q && (j & 1)) ? p.Q2 : p.Q; };
     auto q_str = [&](int j) -> hipStream_t { return (two_q && (j & 1)) ? sq2 : sq; };
     auto q_log = [&](int j) -> float* { return (two_q && (j & 1)) ? p.logit_q2 : p.logit_q; };
-    auto qry_fwd = [&](int j, const float* w, int64_t wstride, int fwd_only) -> int {
+    auto qry_fwd = [&](int j, const float* w, int64_t wstride, PassKind kind) -> int {
         GcnCtx& c = q_ctx(j);
         if (c.np == 2) c.am_pass = j - 1;                  // (gcn_forward advances it: evaluation j records its bounds in pass j, whichever context runs it)
-        return gcn_forward(c, w, wstride, q_log(j), q_str(j), hoist, 1, fwd_only);
+        return gcn_forward(c, w, wstride, q_log(j), q_str(j), hoist, 1, kind);
     };
     auto qry_loss = [&](int j, const float* w, int64_t wstride, int col, int kproto, bool grad) -> int {
         ProtoK pk{q_log(j), C, p.rows_q, Ct, nq, 1, protos(kproto), nullptr, p.lq, p.aq, K1, col, grad ? p.dlog_q : nullptr, grad ? p.dprotos : nullptr, 0, p.tab_q, p.uni_q};
@@ -2112,16 +2140,16 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
     // of the longer chain on small shards, so it goes out first -- behind the support step's ~17 launches it started ~110 us late.
     // (Where the support chain is the longer one -- small query batches: the FirstMM shape lost 2.5 % -- its launches keep the lead.)
     const bool query_first = qry->rows >= 100000;
-    if (query_first) GM_TRY(qry_fwd(0, theta, 0, 1));
+    if (query_first) GM_TRY(qry_fwd(0, theta, 0, PASS_FWD_ONLY));
     GM_TRY(support_head(p, hp, 0, theta, 0, p.fw_k(1), protos(0), st));
     hipEvent_t e_proto0 = signal(st);
-    if (!query_first) GM_TRY(qry_fwd(0, theta, 0, 1));
+    if (!query_first) GM_TRY(qry_fwd(0, theta, 0, PASS_FWD_ONLY));
     wait(q_str(0), e_proto0);
     GM_TRY(qry_loss(0, theta, 0, 0, 0, false));
     GM_TRY(support_bwd(p, hp, theta, 0, st));
     hipEvent_t e_fw = signal(st);                          // fw_1 ready (and, being later on st, the prototypes of step 0)
     wait(q_str(1), e_fw);
-    GM_TRY(qry_fwd(1, p.fw_k(1), Pp, 1));
+    GM_TRY(qry_fwd(1, p.fw_k(1), Pp, PASS_FWD_ONLY));
     GM_TRY(qry_loss(1, p.fw_k(1), Pp, 1, 0, false));
     bool have_grad = false;
     for (int k = 1; k < K; ++k) {            // meta.py:143-157
@@ -2131,7 +2159,7 @@ extern "C" int gm_meta_step(const gm_batch_t* spt, const gm_batch_t* qry, const 
         const int j = k + 1;
         wait(q_str(j), e_fw);
         const bool last = hp->need_meta_grad && k == K - 1;
-        GM_TRY(qry_fwd(j, p.fw_k(k + 1), Pp, last ? ((sparse && sparse_bwd_ok(p.L)) ? 0 : 2) : 1));       // only the last evaluation is differentiated
+        GM_TRY(qry_fwd(j, p.fw_k(k + 1), Pp, !last ? PASS_FWD_ONLY : (sparse && sparse_bwd_ok(p.L)) ? PASS_PLAIN : PASS_DIFF));       // only the last evaluation is differentiated
         GM_TRY(qry_loss(j, p.fw_k(k + 1), Pp, k + 1, k, last));
         if (last) {
             // first-order meta-gradient (no create_graph anywhere, meta.py:125,149): d L_q / d fw_K through the
@@ -2287,8 +2315,8 @@ extern "C" int gm_proto_predict(const gm_batch_t* qry, const gm_model_t* m, cons
         GM_TRY(stage_to_device(p.n_cls, 4 * (size_t)T, st, [&](void* h) { memcpy(h, n_classes, 4 * (size_t)T); }));
     }
     if (qry->subs > 0) {
-        // gm_meta_step's query evaluation nobody differentiates (fwd_only = 1: the fused aggregate + GEMM where eligible), then the scoring kernel
-        GM_TRY(gcn_forward(p.Q, p.params_p, p.Pp, logits, st, hp->hoist_z1, 1, 1));
+        // gm_meta_step's query evaluation nobody differentiates (PASS_FWD_ONLY: the fused aggregate + GEMM where eligible), then the scoring kernel
+        GM_TRY(gcn_forward(p.Q, p.params_p, p.Pp, logits, st, hp->hoist_z1, 1, PASS_FWD_ONLY));
         HeadK hk = make_head(p.Q, p.params_p, p.Pp);
         if (lds > 64 * 1024) GM_TRY(gm_func_full_lds((const void*)k_head_predict));
         hipLaunchKernelGGL(k_head_predict, dim3((qry->subs + 3) / 4), dim3(256), lds, st, hk, protos, (int)c_task, p.n_cls, logits, logp_out, pred_out);
