@@ -30,6 +30,7 @@ struct AggK {
     int skip_lo, skip_hi;                       // rows with skip_lo <= degree <= skip_hi are left to the fused aggregate+GEMM kernel (empty range: none)
     const int32_t* rowlist; int64_t n_list;     // optional: the windows walk this (ascending) row list instead of rows 0 .. rows
     int keep_signed;                            // s_out's sign bit = nobody reads this row of `out`: not stored (and without relu_bits not computed either: agg_unobservable); the scale is the magnitude.  Never read without the flag
+    const int32_t* n_list_dev;                  // optional, with rowlist: the list's length as the device counted it (<= n_list, the host's bound that sized the grid): one scalar load
 };
 // XCD-aware block mapping: hardware block b runs on XCD b % 8; each XCD gets a contiguous range of the nb logical blocks, so that one
 // subgraph's rows (and their gathers) stay in one L2.  First logical block of XCD x (x = GM_NXCD: nb) / logical block of hardware block b
@@ -286,7 +287,7 @@ __global__ __launch_bounds__(AGG_BLOCK) void k_agg_win(AggK a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane / LPR, l = lane % LPR;
     const int64_t R0 = ((int64_t)lb * (AGG_BLOCK / GM_WAVE) + wave) * a.win;
-    const int64_t nrows_w = a.rowlist ? a.n_list : a.rows;          // rows the windows walk: the list's, or all
+    const int64_t nrows_w = a.rowlist ? (a.n_list_dev ? (int64_t)*a.n_list_dev : a.n_list) : a.rows;          // rows the windows walk: the list's, or all
     if (R0 >= nrows_w) return;
     // ---- per-lane row descriptor (coalesced)
     const bool mine = lane < a.win && R0 + lane < nrows_w;
@@ -362,7 +363,7 @@ int gm_agg_window(int64_t rows, int64_t edges) {
 }
 
 int gm_agg_schedule_flat(gm_batch* b, int64_t rows, int win, const int32_t* pos, int n_heavy, const std::vector<int32_t>& tab, int32_t** d_sched, int32_t* len_out,
-                         hipStream_t s, gm_stager* sg) {
+                         hipStream_t s, gm_stager* sg, const uint8_t* keep) {
     const bool split = !tab.empty();
     const int RPB = win * (AGG_BLOCK / GM_WAVE);
     const int nwb = std::max(1, (int)((rows + RPB - 1) / RPB));
@@ -370,7 +371,7 @@ int gm_agg_schedule_flat(gm_batch* b, int64_t rows, int win, const int32_t* pos,
     // orientation of the 1.14 M-row batch): the hub blocks of every XCD's window range are counted first, which gives the common list length,
     // then the flat [8][len] array is written in place -- runs of window blocks with the hub entries spliced in behind their block.
     auto x_start = [&](int x) { return agg_xcd_first(nwb, x); };      // XCD x owns window blocks [x_start(x), x_start(x + 1))
-    auto n_entries = [&](int k) { return split ? tab[k + 1] - tab[k] : 1; };
+    auto n_entries = [&](int k) { return (keep && !keep[k]) ? 0 : split ? tab[k + 1] - tab[k] : 1; };      // (keep: only these hub rows get blocks -- the others have no work in the launch)
     int extra[GM_NXCD] = {}; int first[GM_NXCD + 1];
     {
         int hk = 0;
@@ -392,6 +393,7 @@ int gm_agg_schedule_flat(gm_batch* b, int64_t rows, int win, const int32_t* pos,
         int32_t* o = flat.data() + x * len; int32_t* const o_end = o + len;
         int wb = x_start(x); const int end = x_start(x + 1);
         for (int hk = first[x]; hk < first[x + 1]; ++hk) {
+            if (keep && !keep[hk]) continue;
             const int hb = pos[hk] / RPB;
             while (wb <= hb) *o++ = wb++;                                  // window blocks up to and including the hub row's
             if (split) for (int g = tab[hk]; g < tab[hk + 1]; ++g) *o++ = -g - 2;
@@ -492,7 +494,7 @@ int gm_launch_aggregate(const gm_agg_args& g, hipStream_t s) {
     a.hub = g.sched ? g.hub : nullptr; a.hub_scratch = g.sched ? g.hub_scratch : nullptr; a.hub_part = g.hub_part; a.hub_ld = GM_AGG_HUB_LD;
     a.e_w = g.e_w; a.x_idx = g.x_idx;
     a.skip_lo = g.skip_on ? g.skip_lo : 1; a.skip_hi = g.skip_on ? g.skip_hi : 0;
-    a.rowlist = g.rowlist; a.n_list = g.n_list;
+    a.rowlist = g.rowlist; a.n_list = g.n_list; a.n_list_dev = g.rowlist ? g.n_list_dev : nullptr;
     a.keep_signed = (g.keep_signed && g.s_out) ? 1 : 0;
     const bool vec4 = (g.width % 4 == 0) && (g.ldx % 4 == 0) && (((uintptr_t)g.x & 15) == 0) && (((uintptr_t)g.out & 15) == 0);
     const bool bias_ok = !g.bias || ((((uintptr_t)g.bias & 15) == 0) && (g.bias_stride % 4 == 0));

@@ -358,6 +358,15 @@ extern "C" int gm_dense_aggregate(const gm_batch_t* b, int32_t transposed, int32
                        "dense_aggregate: the list schedule goes with the batch's own list (%d rows, windows of %d) and its hub tables", b->n_mid, b->mid_win);
             a.sched = b->d_sched_mid; a.sched_len = b->sched_len_mid; a.sched_win = b->mid_win;
         } else { a.sched = nullptr; a.sched_len = 0; }
+    } else if (list_sched >= 2 && list_sched <= 4) {
+        // one of the batch's own lists of observable rows (gm_batch::obs[list_sched - 2]) as gcn_forward / gcn_backward launch over it: the list at its bound, its
+        // window, the length the device counted and, where the orientation has hub rows, the list's own schedule.  Built or not taken by the batch: both allowed here
+        const gm_batch::obs_list& ol = b->obs[list_sched - 2];
+        GM_REQUIRE(ol.rows && (list_sched == 4) == (transposed != 0), GM_EINVAL, "dense_aggregate: the batch holds no list %d of this orientation", list_sched - 2);
+        GM_REQUIRE(ol.cap >= 1 || ol.sched, GM_EINVAL, "dense_aggregate: list %d is empty and the orientation has no hub rows: nothing to launch", list_sched - 2);
+        GM_REQUIRE(b->n_heavy[o] == 0 || (hubs == 2 && ol.sched), GM_EINVAL, "dense_aggregate: list %d has no schedule for the orientation's hub rows", list_sched - 2);
+        a.rowlist = ol.rows; a.n_list = ol.cap; a.n_list_dev = ol.len; a.list_win = ol.win;
+        a.sched = ol.sched; a.sched_len = ol.sched ? ol.sched_len : 0; a.sched_win = ol.win;
     } else GM_REQUIRE(!list_sched, GM_EINVAL, "dense_aggregate: a list schedule without a row list");
     if (stream_ok && a.e_w && a.e_w == b->d_enorm[o]) GM_TRY(gm_agg_stream_args(a, b, o, gather, st));
     const int rc = gm_launch_aggregate(a, st);
@@ -377,6 +386,30 @@ extern "C" int gm_dense_agg_info(const gm_batch_t* b, int32_t transposed, int64_
     std::copy(v, v + 16, info);
     return GM_OK;
 }
+// The batch's lists of observable rows (gm_batch::obs; GM_AGG_OBS_LIST), four entries per list k = 0, 1, 2: info[4 k ..] = {length (read back from the device at first
+// use, which synchronises the stream; 0 where the list was not built), bound it was allocated and scheduled for, rows per window, how the batch takes it (0 today's
+// launch, 1 the list, 2 nothing to launch) + 4 where it carries a block schedule}; info[12 .. 15] = {gm_batch_fwd_counts(0)[0], gm_batch_fwd_counts(1)[0] (the observable rows
+// of more than GM_FUSE_MAXDEG sources, hub rows included; -1 without the forward-only tables), gm_batch_e1_rows, 0}: what the lengths are checked against
+extern "C" int gm_dense_obs_lists(const gm_batch_t* b, int64_t* info, void* stream) {
+    GM_REQUIRE(b && info, GM_EINVAL, "dense_obs_lists: bad arguments");
+    for (int k = 0; k < 3; ++k) {
+        const gm_batch::obs_list& ol = b->obs[k];
+        if (ol.n < 0) {
+            int32_t h = 0;
+            if (ol.rows && ol.len) { GM_HIP(hipMemcpyAsync(&h, ol.len, 4, hipMemcpyDeviceToHost, (hipStream_t)stream)); GM_HIP(hipStreamSynchronize((hipStream_t)stream)); }
+            ol.n = h;
+        }
+        info[4 * k] = ol.n; info[4 * k + 1] = ol.cap; info[4 * k + 2] = ol.win; info[4 * k + 3] = ol.take + (ol.sched ? 4 : 0);
+    }
+    for (int k = 0; k < 2; ++k) {
+        int64_t w[3] = {-1, -1, -1};
+        if (b->d_obs[k] && b->rows > 0) GM_TRY(gm_batch_fwd_counts(b, k, (hipStream_t)stream, w));
+        info[12 + k] = w[0];
+    }
+    info[14] = gm_batch_e1_rows(b, (hipStream_t)stream); info[15] = 0;
+    gm_batch_mark_use(b, (hipStream_t)stream);
+    return GM_OK;
+}
 // ... and the tests of the fused kernels: counts[2] = {rows of more than GM_FUSE_MAXDEG sources (gm_batch::unfused_rows: the rows a fused pass still aggregates by
 // the ordinary kernel), their in-edges (unfused_edges)}
 extern "C" int gm_dense_fuse_counts(const gm_batch_t* b, int64_t* counts) {
@@ -387,9 +420,16 @@ extern "C" int gm_dense_fuse_counts(const gm_batch_t* b, int64_t* counts) {
 // Device copies of the batch's derived tables (which: 0 per-edge source norm of orientation o [edges] float, 1 per-edge feature row [edges] int32, 2 window-row
 // list [info[6]] int32, 3 hub rows of orientation o [info[1]] int32; 4 / 5 / 6 the per-row source tables gm_batch::d_fuse2 / d_fuse2_feat / d_dq_tab, [rows] entries
 // of four int32 {u0, u1, w0, w1}; 7 / 8 / 9 the forward-only passes' tables of GM_DEAD_ROWS=3 in the same layout: the last layer's (gm_batch::d_fwd_tab[0]), the layer
-// below it over batch rows (d_fwd_tab[1]) and over the feature table (d_fwd_tab_feat)): n entries -> dst (device)
+// below it over batch rows (d_fwd_tab[1]) and over the feature table (d_fwd_tab_feat); 10 / 11 / 12 the lists of observable rows gm_batch::obs[0 .. 2], int32): n entries -> dst (device)
 extern "C" int gm_dense_agg_table(const gm_batch_t* b, int32_t which, int32_t transposed, void* dst, int64_t n, void* stream) {
-    GM_REQUIRE(b && dst && n >= 0 && which >= 0 && which <= 9, GM_EINVAL, "dense_agg_table: bad arguments");
+    GM_REQUIRE(b && dst && n >= 0 && which >= 0 && which <= 12, GM_EINVAL, "dense_agg_table: bad arguments");
+    if (which >= 10) {      // 10 / 11 / 12: the lists of observable rows (gm_dense_obs_lists), up to their bound
+        const gm_batch::obs_list& ol = b->obs[which - 10];
+        GM_REQUIRE(ol.rows && n <= ol.cap, GM_EINVAL, "dense_agg_table: table %d holds %lld entries", which, (long long)(ol.rows ? ol.cap : 0));
+        if (n) GM_HIP(hipMemcpyAsync(dst, ol.rows, 4 * (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        gm_batch_mark_use(b, (hipStream_t)stream);
+        return GM_OK;
+    }
     const int o = transposed ? 1 : 0;
     const void* src = which == 0 ? (const void*)b->d_enorm[o] : which == 1 ? (const void*)b->d_efeat : which == 2 ? (const void*)b->d_mid : which == 3 ? (const void*)b->d_heavy[o]
                     : which == 4 ? (const void*)b->d_fuse2 : which == 5 ? (const void*)b->d_fuse2_feat : which == 6 ? (const void*)b->d_dq_tab

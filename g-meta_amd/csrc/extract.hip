@@ -690,23 +690,24 @@ int64_t gm_batch_unfused_sources(const gm_batch* b, hipStream_t s) {
     gm_dev_free(bits, s); gm_dev_free(cnt, s);
     return ok ? (b->unfused_src = (int64_t)h) : fallback;
 }
-// Ordered compaction of the rows with lo <= in-degree <= hi (the window rows of a partial aggregate launch): per-block counts, a one-block scan
-// of the counts, then every block writes its rows at its offset (ballot ranks: ascending row ids).
+// Ordered compaction of the rows with lo <= in-degree <= hi (the window rows of a partial aggregate launch) and, with `flag`, its sign bit clear (the observable ones
+// among them: gm_batch::obs): per-block counts, a one-block scan of the counts, then every block writes its rows at its offset (ballot ranks: ascending row ids).
+// total (with cap): the scan leaves the list's length there, for the launches that learn it on the device (never above the cap the list was allocated for).
 #define MID_BLOCK 1024
-__device__ __forceinline__ bool mid_row(const int32_t* indptr, int64_t r, int64_t rows, int lo, int hi) {
+__device__ __forceinline__ bool mid_row(const int32_t* indptr, const float* flag, int64_t r, int64_t rows, int lo, int hi) {
     if (r >= rows) return false;
     const int d = indptr[r + 1] - indptr[r];
-    return d >= lo && d <= hi;
+    return d >= lo && d <= hi && !(flag && (__float_as_uint(flag[r]) >> 31));
 }
-__global__ __launch_bounds__(MID_BLOCK) void k_mid_count(const int32_t* indptr, int64_t rows, int lo, int hi, int32_t* bcnt) {
+__global__ __launch_bounds__(MID_BLOCK) void k_mid_count(const int32_t* indptr, const float* flag, int64_t rows, int lo, int hi, int32_t* bcnt) {
     __shared__ int wsum[MID_BLOCK / 64];
     const int64_t r = (int64_t)blockIdx.x * MID_BLOCK + threadIdx.x;
-    const unsigned long long m = __ballot(mid_row(indptr, r, rows, lo, hi));
+    const unsigned long long m = __ballot(mid_row(indptr, flag, r, rows, lo, hi));
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(m);
     __syncthreads();
     if (threadIdx.x == 0) { int t = 0; for (int k = 0; k < MID_BLOCK / 64; ++k) t += wsum[k]; bcnt[blockIdx.x] = t; }
 }
-__global__ __launch_bounds__(1024) void k_mid_scan(int32_t* bcnt, int nb) {      // exclusive scan in place, one block
+__global__ __launch_bounds__(1024) void k_mid_scan(int32_t* bcnt, int nb, int32_t* total, int cap) {      // exclusive scan in place, one block
     __shared__ int part[1024];
     const int per = (nb + 1023) / 1024, a = threadIdx.x * per, b = min(nb, a + per);
     int t = 0;
@@ -717,11 +718,12 @@ __global__ __launch_bounds__(1024) void k_mid_scan(int32_t* bcnt, int nb) {     
     __syncthreads();
     int run = part[threadIdx.x];
     for (int k = a; k < b; ++k) { const int v = bcnt[k]; bcnt[k] = run; run += v; }
+    if (total && threadIdx.x == 1023) *total = min(run, cap);      // (the last thread's run ends at the sum of every count)
 }
-__global__ __launch_bounds__(MID_BLOCK) void k_mid_scatter(const int32_t* indptr, int64_t rows, int lo, int hi, const int32_t* boff, int32_t* list, int cap) {
+__global__ __launch_bounds__(MID_BLOCK) void k_mid_scatter(const int32_t* indptr, const float* flag, int64_t rows, int lo, int hi, const int32_t* boff, int32_t* list, int cap) {
     __shared__ int wsum[MID_BLOCK / 64];
     const int64_t r = (int64_t)blockIdx.x * MID_BLOCK + threadIdx.x;
-    const bool f = mid_row(indptr, r, rows, lo, hi);
+    const bool f = mid_row(indptr, flag, r, rows, lo, hi);
     const unsigned long long m = __ballot(f);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) wsum[wv] = __popcll(m);
@@ -1112,7 +1114,8 @@ static int finalize_finish(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
     }
     b->h_centre.assign(h_centre, h_centre + b->n_c);
     b->sched_win = gm_agg_window(b->rows, b->edges);
-    std::vector<int32_t> heavy0, tab0;                       // forward orientation: sorted hub rows and their part table (for the list schedule below)
+    std::vector<int32_t> heavy_h[2], tab_h[2];               // per orientation: sorted hub rows and their part table (for the list schedules below)
+    std::vector<int32_t>&heavy0 = heavy_h[0], &tab0 = tab_h[0];
     for (int o = 0; o < 2; ++o) {
         b->n_heavy[o] = std::min(h_cnt[o], cap);
         if (b->n_heavy[o] > 0) {         // deterministic order (atomic append order is not)
@@ -1131,7 +1134,7 @@ static int finalize_finish(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
             gm_agg_sched sc;
             GM_TRY(gm_agg_schedule(b, b->rows, b->sched_win, h.data(), hd.data(), b->n_heavy[o], &sc, s, &sg));
             tm.lap("schedule");
-            if (o == 0) { heavy0 = h; tab0 = sc.tab; }
+            heavy_h[o] = h; tab_h[o] = sc.tab;
             {   // stream tables: at first use (gm_agg_stream_args), from these host copies
                 gm_batch::stream_pending& sp = b->spend[o];
                 sp.pending = true; sp.has_tab = sc.d_hub != nullptr; sp.n_parts = sc.d_hub ? sc.parts : (int)nh;
@@ -1142,30 +1145,34 @@ static int finalize_finish(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
     }
     // ---- the window rows of the fused passes' partial aggregate launch as a compact ascending list + its block schedule (no host wait: the
     // list's length follows from counts the round trip above already brought: rows with more than GM_FUSE_MAXDEG in-edges minus the hub rows)
+    // (the one compaction: rows of orientation indptr with lo <= degree <= hi and, with flag, its sign bit clear -> list[0 .. cap), ascending; total: see k_mid_scan)
+    auto compact = [&](const int32_t* indptr, const float* flag, int lo, int hi, int32_t* list, int64_t n_cap, int32_t* total) {
+        const int nb = (int)((b->rows + MID_BLOCK - 1) / MID_BLOCK);
+        int32_t* d_bcnt = nullptr;
+        GM_TRY(gm_alloc(&d_bcnt, (size_t)nb, s));
+        hipLaunchKernelGGL(k_mid_count, dim3(nb), dim3(MID_BLOCK), 0, s, indptr, flag, (int64_t)b->rows, lo, hi, d_bcnt);
+        hipLaunchKernelGGL(k_mid_scan, dim3(1), dim3(1024), 0, s, d_bcnt, nb, total, (int)n_cap);
+        hipLaunchKernelGGL(k_mid_scatter, dim3(nb), dim3(MID_BLOCK), 0, s, indptr, flag, (int64_t)b->rows, lo, hi, d_bcnt, list, (int)n_cap);
+        GM_HIP(hipGetLastError());
+        gm_dev_free(d_bcnt, s);
+        return (int)GM_OK;
+    };
+    // window size over a list of n rows: enough waves to fill the chip, at least two rows per wave (two rows in flight per lane group)
+    auto list_window = [](int64_t n) { int win = 64; while (win > 2 && n / win < 16384) win >>= 1; return gm_knob().agg_mid_win > 0 ? gm_knob().agg_mid_win : win; };
+    // hub parts of orientation o ride in a list's launch: placed after the list block nearest to the hub row's position (row id scaled to the list's n rows)
+    auto list_schedule = [&](int o, int64_t n, int win, int32_t** d_sched, int32_t* len, const uint8_t* keep = nullptr) {
+        std::vector<int32_t> pos(heavy_h[o].size());
+        for (size_t k = 0; k < pos.size(); ++k) pos[k] = (int32_t)std::min<int64_t>(std::max<int64_t>(n, 1) - 1, (int64_t)heavy_h[o][k] * n / b->rows);
+        return gm_agg_schedule_flat(b, n, win, pos.data(), (int)pos.size(), tab_h[o], d_sched, len, s, &sg, keep);
+    };
     if (b->d_fuse2 && gm_knob().agg_mid_list) {
         const int64_t n_mid = b->unfused_rows - (int64_t)b->n_heavy[0];
         if (n_mid > 0 && n_mid < b->rows && h_cnt[0] <= cap) {
-            const int nb = (int)((b->rows + MID_BLOCK - 1) / MID_BLOCK);
-            int32_t* d_bcnt = nullptr;
-            GM_TRY(gm_alloc(&d_bcnt, (size_t)nb, s));
             GM_TRY(gm_balloc(b, &b->d_mid, (size_t)n_mid, s));
-            hipLaunchKernelGGL(k_mid_count, dim3(nb), dim3(MID_BLOCK), 0, s, b->d_indptr, (int64_t)b->rows, GM_FUSE_MAXDEG + 1, b->heavy_deg, d_bcnt);
-            hipLaunchKernelGGL(k_mid_scan, dim3(1), dim3(1024), 0, s, d_bcnt, nb);
-            hipLaunchKernelGGL(k_mid_scatter, dim3(nb), dim3(MID_BLOCK), 0, s, b->d_indptr, (int64_t)b->rows, GM_FUSE_MAXDEG + 1, b->heavy_deg, d_bcnt, b->d_mid, (int)n_mid);
-            GM_HIP(hipGetLastError());
-            gm_dev_free(d_bcnt, s);
+            GM_TRY(compact(b->d_indptr, nullptr, GM_FUSE_MAXDEG + 1, b->heavy_deg, b->d_mid, n_mid, nullptr));
             b->n_mid = (int32_t)n_mid;
-            // window size over the list: enough waves to fill the chip, at least two rows per wave (two rows in flight per lane group)
-            int win = 64;
-            while (win > 2 && n_mid / win < 16384) win >>= 1;
-            if (gm_knob().agg_mid_win > 0) win = gm_knob().agg_mid_win;
-            b->mid_win = win;
-            if (b->n_heavy[0] > 0 && b->d_sched[0]) {
-                // hub parts ride in the same launch: placed after the list block nearest to the hub row's position (row id scaled to the list)
-                std::vector<int32_t> pos(heavy0.size());
-                for (size_t k = 0; k < heavy0.size(); ++k) pos[k] = (int32_t)std::min<int64_t>(n_mid - 1, (int64_t)heavy0[k] * n_mid / b->rows);
-                GM_TRY(gm_agg_schedule_flat(b, n_mid, win, pos.data(), (int)heavy0.size(), tab0, &b->d_sched_mid, &b->sched_len_mid, s, &sg));
-            }
+            b->mid_win = list_window(n_mid);
+            if (b->n_heavy[0] > 0 && b->d_sched[0]) GM_TRY(list_schedule(0, n_mid, b->mid_win, &b->d_sched_mid, &b->sched_len_mid));
         }
     }
     tm.lap("mid-list");
@@ -1197,7 +1204,66 @@ static int finalize_finish(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
             GM_HIP(hipGetLastError());
             b->d_fwd_tab[0] = tc; b->d_fwd_tab[1] = te; b->d_fwd_tab_feat = tf;
         }
+        // ---- the observable rows of the restricted aggregate launches as compact lists (gm_batch::obs), each with its window and, where its orientation has hub rows,
+        // its block schedule.  No host wait: [0] follows from the centres' rows and in-degrees the round trip brought; [1] / [2] are sized by their bounds, and the
+        // launches read their lengths on the device.  A list is taken where its bound is below half the rows today's launch walks (d_mid's, or every row)
+        if (gm_knob().agg_mid_list && h_cnt[0] <= cap && h_cnt[1] <= cap) {
+            const int64_t walked_fwd = b->d_mid ? b->n_mid : b->rows;
+            // list k over orientation o, n rows (exact or bound): window, schedule, taken or not.  hub_keep: the orientation's hub rows that can have work in the launch,
+            // where the host knows them (list 0: the hub rows that are centres) -- the others get no block; NULL: every hub row keeps its blocks, the flagged ones leave at once
+            auto finish = [&](int k, int o, int64_t n, int64_t walked, const uint8_t* hub_keep) {
+                gm_batch::obs_list& ol = b->obs[k];
+                ol.cap = (int32_t)n; ol.win = list_window(n);
+                if (2 * n > walked || (b->n_heavy[o] > 0 && !b->d_sched[o])) return (int)GM_OK;
+                if (b->n_heavy[o] > 0) GM_TRY(list_schedule(o, n, ol.win, &ol.sched, &ol.sched_len, hub_keep));
+                ol.take = 1;
+                return (int)GM_OK;
+            };
+            if (b->d_obs[0]) {
+                // [0]: the centre rows of GM_FUSE_MAXDEG+1 .. heavy_deg in-edges (two centres may share a row); a centre that is a hub row has its work in the hub blocks
+                std::vector<int32_t> lst, hubs_c;
+                for (int k = 0; k < b->n_c; ++k) {
+                    const int32_t row = b->h_sub_off[k / nc] + h_centre[k];
+                    if (h_cdeg[k] > b->heavy_deg) hubs_c.push_back(row); else if (h_cdeg[k] > GM_FUSE_MAXDEG) lst.push_back(row);
+                }
+                std::sort(lst.begin(), lst.end()); lst.erase(std::unique(lst.begin(), lst.end()), lst.end());
+                std::sort(hubs_c.begin(), hubs_c.end());
+                const bool hub_centre = !hubs_c.empty();
+                std::vector<uint8_t> hub_keep(heavy_h[0].size());
+                for (size_t k = 0; k < hub_keep.size(); ++k) hub_keep[k] = std::binary_search(hubs_c.begin(), hubs_c.end(), heavy_h[0][k]) ? 1 : 0;
+                gm_batch::obs_list& ol = b->obs[0];
+                ol.n = (int64_t)lst.size();
+                if (lst.empty() && !hub_centre) ol.take = 2;
+                else {      // (hub centres alone: an empty list whose schedule carries the hub blocks)
+                    GM_TRY(gm_balloc(b, &ol.rows, lst.size(), s));
+                    if (!lst.empty()) GM_TRY(sg.upload(ol.rows, lst));
+                    GM_TRY(finish(0, 0, (int64_t)lst.size(), walked_fwd, hub_keep.data()));
+                }
+            }
+            GM_TRY(gm_balloc(b, &b->obs[1].len, 2, s)); b->obs[2].len = b->obs[1].len + 1;
+            GM_HIP(hipMemsetAsync(b->obs[1].len, 0, 8, s));
+            if (b->d_obs[1]) {
+                // [1]: at most one row per in-edge of a centre, and no more than the rows of that degree range
+                const int64_t n_range = b->unfused_rows - (int64_t)b->n_heavy[0], bound = std::min<int64_t>(b->n_e1, n_range);
+                if (b->n_e1 == 0 || b->unfused_rows == 0) { b->obs[1].take = 2; b->obs[1].n = 0; }
+                else {      // (bound 0: hub rows alone, as above; the length word stays at its 0)
+                    GM_TRY(gm_balloc(b, &b->obs[1].rows, (size_t)bound, s));
+                    if (bound > 0) GM_TRY(compact(b->d_indptr, b->d_obs[1], GM_FUSE_MAXDEG + 1, b->heavy_deg, b->obs[1].rows, bound, b->obs[1].len));
+                    GM_TRY(finish(1, 0, bound, walked_fwd, nullptr));
+                }
+            }
+            {   // [2]: at most one row per in-edge of a centre, of any out-degree
+                const int64_t bound = std::min<int64_t>(b->n_e1, b->rows);
+                if (b->n_e1 == 0) { b->obs[2].take = 2; b->obs[2].n = 0; }
+                else {
+                    GM_TRY(gm_balloc(b, &b->obs[2].rows, (size_t)bound, s));
+                    GM_TRY(compact(b->d_indptr_t, b->d_norm_e1, 0, INT32_MAX, b->obs[2].rows, bound, b->obs[2].len));
+                    GM_TRY(finish(2, 1, bound, b->rows, nullptr));
+                }
+            }
+        }
     }
+    tm.lap("obs-lists");
     std::vector<int32_t> ccoff, ecoff, c_set_off(b->sets + 1), e_set_off(b->sets + 1);      // per set: its centres, and the in-edges of its centres
     for (int t = 0; t <= b->sets; ++t) { c_set_off[t] = b->h_set_sub_off[t] * nc; e_set_off[t] = eoff[b->h_set_sub_off[t] * nc]; }
     const std::vector<int32_t> ct = set_spans(c_set_off, GM_GEMM_BM), cc = set_spans(c_set_off, gm_wgrad_chunk_rows(c_set_off), &ccoff), ec = set_spans(e_set_off, gm_wgrad_chunk_rows(e_set_off), &ecoff);

@@ -211,6 +211,14 @@ struct gm_batch {
     void* d_fwd_tab[2] = {nullptr, nullptr};   // [rows] int4: d_fuse2's entry on the observable rows, {GM_FUSE_ZERO, GM_FUSE_ZERO, 0, 0} on every other row (gm_gemm_args::fuse2)
     void* d_fwd_tab_feat = nullptr;            // [rows] int4: d_fuse2_feat's entry on the [1] rows -- where the layer below the last gathers from the feature table
     float* d_obs[2] = {nullptr, nullptr};      // [rows] +1 on the observable rows, -1 on every other row: gm_agg_args::s_out + keep_signed of the partial aggregate launches (a scale of exactly 1)
+    // The observable rows of the restricted aggregate launches as compact ascending lists (finalize_finish, next to d_mid; GM_AGG_OBS_LIST).  [0]: rows of GM_FUSE_MAXDEG+1 ..
+    // heavy_deg in-edges with d_obs[0] positive (the last layer's partial aggregate), [1]: the same with d_obs[1] (the layer below), [2]: rows with the sign of d_norm_e1
+    // clear (the last layer's transposed aggregate; its hub rows stay listed, the windows pass over them).  [0] is built on the host from the centres' in-degrees (length
+    // exact, len == NULL); [1] / [2] by the d_mid compaction with the flag as a second condition: cap is the host's bound (min(n_e1, rows walked today)), it sizes list,
+    // grid and schedule, and the launch reads the true length from *len (gm_agg_args::n_list_dev).  take: 0 today's launch (no list: bound not below half the rows walked
+    // today, hub tables missing), 1 the list, 2 nothing to launch (known on the host: no row of the set has work).  sched: block schedule over the list where the orientation has hub rows
+    struct obs_list { int32_t* rows = nullptr; int32_t* len = nullptr; int32_t cap = 0, win = 0, take = 0; int32_t* sched = nullptr; int32_t sched_len = 0; mutable int64_t n = -1; };
+    obs_list obs[3];
     mutable int64_t fwd_cnt[2][3] = {{-1, -1, -1}, {-1, -1, -1}};      // observable rows of more than GM_FUSE_MAXDEG sources, their in-edges, their distinct sources (profiling only: counted on first use, gm_batch_fwd_counts)
     float* d_e1_norm = nullptr;        // [n_e1] norm[source row]
     float* d_e1_coef = nullptr;        // [n_e1] weighted batches only: edge weight x norm[source row] (the transposed aggregate's coefficient; d_e1_norm stays the row scale)
@@ -255,6 +263,7 @@ struct gm_knobs {
     int fuse_agg, head_stage;
     int fuse_diff;
     int agg_mid_win;               // GM_AGG_MID_WIN: rows per wave window over that list (0 = by its length)
+    int agg_obs_list;              // GM_AGG_OBS_LIST: the aggregate launches restricted to the observable rows walk the batch's compact lists of them (1, default; gm_batch::obs) or every row's descriptor (0).  Read at launch time (plan_pass): the lists are built either way
     int agg_mid_list;              // GM_AGG_MID_LIST: the partial aggregate launch of a fused pass walks a compact list of its window rows (1, default) or every row (0)
     int query_streams;             // GM_QUERY_STREAMS: 2 = the query evaluations of gm_meta_step alternate between two streams; anything else (default 0) = one stream
     int head_threads;              // GM_HEAD_THREADS: workgroup size of k_head_loss: 256 or 512; anything else (default 0) = 1024
@@ -494,6 +503,7 @@ struct gm_agg_args {
     int sched_len, sched_win;
     const int32_t* hub; float* hub_scratch; int hub_part;     // with sched: hub rows split over several blocks (gm_agg_sched)
     const int32_t* rowlist; int64_t n_list; int list_win;      // window kernel only: the wave windows walk rowlist[0 .. n_list) instead of every row (sched / sched_len then index list blocks)
+    const int32_t* n_list_dev; // optional, with rowlist: the list's true length on the device (<= n_list, which then is the host's bound: it sizes grid and schedule; the windows past the length leave at once)
     // optional: the batch / orientation whose stream tables this launch may use (gm_agg_stream_args): eligible launches take the LDS-DMA stream kernel (agg_stream.hip)
     const gm_batch* stream; int stream_o; int stream_feat; int64_t stream_xrows;
     int* launched;             // optional: receives the GM_AGG_ID_* of the instantiation launched (host side; tests)
@@ -540,7 +550,9 @@ int gm_agg_window(int64_t rows, int64_t edges);
 struct gm_stager;
 // Only the flat block schedule, for hub rows at (virtual, ascending) positions pos[] among `rows` window rows, over the part table `tab` of an earlier
 // gm_agg_schedule call (empty: one block per hub row)
-int gm_agg_schedule_flat(gm_batch* b, int64_t rows, int win, const int32_t* pos, int n_heavy, const std::vector<int32_t>& tab, int32_t** d_sched, int32_t* len, hipStream_t s, gm_stager* sg);
+// keep (or NULL: all): one byte per hub row, 0 = the row gets no block in this schedule (a launch in which the host knows it to have no work)
+int gm_agg_schedule_flat(gm_batch* b, int64_t rows, int win, const int32_t* pos, int n_heavy, const std::vector<int32_t>& tab, int32_t** d_sched, int32_t* len, hipStream_t s, gm_stager* sg,
+                         const uint8_t* keep = nullptr);
 int gm_agg_schedule(gm_batch* b, int64_t rows, int win, const int32_t* heavy_host, const int32_t* heavy_deg_host, int n_heavy, gm_agg_sched* out, hipStream_t s, gm_stager* sg);
 int gm_heavy_deg();   // rows with more edges than this are aggregated by a whole workgroup (64; a batch's own threshold is by density, see gm_heavy_deg_for)
 int gm_heavy_deg_for(int64_t rows, int64_t edges);

@@ -714,11 +714,14 @@ enum DqFill { DQ_MEMSET, DQ_ZEROED, DQ_CENTRE };
 //    loaders, the table-formed weight gradient; the backward takes relu' from the bits) -- a row without an out-edge is nobody's source.  ROWS_E1, below a restricted
 //    last layer: only a source of a centre's in-edge is the source of an edge anyone walks (a subset of ROWS_SRC).
 //  relu_bits: the layer writes its relu' bits M[l] (where the context has them): every pass but the ones nobody differentiates
-struct LayerPlan { bool split, fuse; RowSet formed, stored; bool relu_bits; };
+//  list (GM_AGG_OBS_LIST): the partial aggregate launch of a restricted fused layer walks the batch's compact list of its observable rows (gm_batch::obs; take == 2:
+//    nothing to launch) instead of every listed row's descriptor; NULL: today's launch
+struct LayerPlan { bool split, fuse; RowSet formed, stored; bool relu_bits; const gm_batch::obs_list* list; };
 // The pass: its kind, its layers, dQ_L, and what a gcn_backward(skip_head = 1) over it may do (GM_DEAD_ROWS=2; gcn_backward has the bitwise argument).  t_centre: dQ_L is
 // left to its centre rows and the zero block behind T_L is there -- the dZ GEMM stores T_L's centre rows only, the transposed aggregate reads T_L through gm_batch::d_ect.
 // dq_e1: ... and the layer below is the first, aggregate-first, with a table-fed three-piece weight gradient: that aggregate stores only the rows of dQ_{L-1} that can be non-zero
-struct PassPlan { PassKind kind; LayerPlan layer[GM_MAX_GCN]; DqFill dq; bool t_centre, dq_e1; };
+// t_list: ... and walks the compact list of those rows (gm_batch::obs[2]), as LayerPlan::list
+struct PassPlan { PassKind kind; LayerPlan layer[GM_MAX_GCN]; DqFill dq; bool t_centre, dq_e1; const gm_batch::obs_list* t_list; };
 
 struct GcnCtx {
     const gm_batch* b; gm_layout L;
@@ -941,6 +944,8 @@ static int partial_agg_bytes(const gm_batch* b, RowSet formed, int fi, bool gath
     if (gm_prof_enabled() && !all) GM_TRY(gm_batch_fwd_counts(b, row_view(b, formed, gather).obs, st, w));
     // every indptr entry; the norm of every row of more than GM_FUSE_MAXDEG sources (a restricted launch: its list entry and its flag); the edge-table entries of the
     // rows written and those rows
+    // (GM_AGG_OBS_LIST: a launch over the set's own list is priced like the descriptor walk it replaces -- an upper bound on its index traffic; the row, edge and
+    // source terms, which carry the width, are the same either way)
     const int64_t pb0 = 4 * (b->rows + 1) + (all ? 4 : 8) * b->unfused_rows + 4 * w[1] + 4 * w[0] * (int64_t)fi;
     *bytes = pb0 + 4 * w[2] * (int64_t)fi;
     // strict HBM pricing as for the full launches: a gather launch reads at most the whole (cache-resident) feature table
@@ -951,6 +956,7 @@ static int partial_agg_bytes(const gm_batch* b, RowSet formed, int fi, bool gath
 // ... and the last layer's transposed aggregate of a t_centre backward (PassPlan), which works on n_out rows with e_out edges (every other row leaves behind its
 // descriptor): every indptr entry and every row scale; of the rows it works on the edge-table entries and the relu' bits; T_L's centre rows read once, the rows it
 // stores written once
+// (GM_AGG_OBS_LIST: priced the same over the rows' own list, as partial_agg_bytes)
 static int64_t t_centre_agg_bytes(const gm_batch* b, RowSet out, int fi, bool maskbits, hipStream_t st) {
     const int64_t n_out = rows_kept(b, out, st), e_out = (out == ROWS_E1 && gm_prof_enabled()) ? gm_batch_e1_edges(b, st) : b->edges;
     return 4 * (b->rows + 1) + 4 * b->rows + 4 * e_out + (maskbits ? n_out * (int64_t)fi / 4 : 0) + 4 * ((int64_t)b->n_c + n_out) * (int64_t)fi;
@@ -1065,7 +1071,21 @@ static int plan_pass(const GcnCtx& c, const float* params, int64_t pstride, Pass
     // under dq_e1 (two GraphConv layers, aggregate-first, the table-fed weight gradient), fused, with the relu' bits -- a three-layer model restricts its last layer only
     if (below_ok && ((fwd3 && p.layer[Lg - 2].split) || (diff4 && p.dq_e1 && p.layer[0].fuse && c.M[0]))) {
         p.layer[Lg - 2].stored = ROWS_E1; if (p.layer[Lg - 2].fuse) p.layer[Lg - 2].formed = ROWS_E1; }
+    // GM_AGG_OBS_LIST: the launches restricted above walk the batch's lists of their rows where it built and took them (finalize_finish: bound below half the rows
+    // walked today, a schedule where the orientation has hub rows).  The first hub set only, as the d_mid list; the lists are over the batch's own centres, like the
+    // restricted sets themselves (dead_row_level)
+    if (gm_knob().agg_obs_list && c.hub_set == 0) {
+        auto taken = [&](int k) { return b->obs[k].take ? &b->obs[k] : nullptr; };
+        for (int l = 0; l < Lg; ++l)
+            if (p.layer[l].fuse && p.layer[l].formed != ROWS_ALL) p.layer[l].list = taken(p.layer[l].formed == ROWS_CENTRE ? 0 : 1);
+        if (p.dq_e1) p.t_list = taken(2);
+    }
     *plan = p; return plan_check(c, p);
+}
+// a restricted launch over the plan's list: the list in the windows' place, its own schedule (or none), the length the device counted
+static void agg_take_list(gm_agg_args& a, const gm_batch::obs_list& ol) {
+    a.rowlist = ol.rows; a.n_list = ol.cap; a.n_list_dev = ol.len; a.list_win = ol.win;
+    a.sched = ol.sched; a.sched_len = ol.sched ? ol.sched_len : 0; a.sched_win = ol.win;
 }
 
 static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* logits, hipStream_t st, int reuse_z1, int skip_head = 0, PassKind kind = PASS_PLAIN) {
@@ -1115,9 +1135,13 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
                     }
                     // ... and of those only the rows the plan forms; the others stop at their descriptor (list entry, row bounds, flag)
                     if (lp.formed != ROWS_ALL) { a.s_out = row_view(b, lp.formed, gather).sign; a.keep_signed = 1; }
-                    int64_t pb, pbs;
-                    GM_TRY(partial_agg_bytes(b, lp.formed, fi, gather, st, &pb, &pbs));
-                    GM_TRY(launch_agg(a, pb, pbs, st));
+                    // ... walking the compact list of THOSE rows where the plan took it (no launch where the host knows it empty)
+                    if (lp.list && lp.list->take == 1) agg_take_list(a, *lp.list);
+                    if (!(lp.list && lp.list->take == 2)) {
+                        int64_t pb, pbs;
+                        GM_TRY(partial_agg_bytes(b, lp.formed, fi, gather, st, &pb, &pbs));
+                        GM_TRY(launch_agg(a, pb, pbs, st));
+                    }
                 } else {
                     if (a.e_w) GM_TRY(gm_agg_stream_args(a, b, 0, gather, st));      // full launches may take the LDS-DMA stream kernel (agg_stream.hip)
                     // compulsory HBM bytes: a gather launch reads rows of the (cache-resident) feature table, at most all of it
@@ -1279,9 +1303,10 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
                     a.x_idx = b->d_ect;
                     const RowSet out = dq_e1 ? ROWS_E1 : ROWS_ALL;      // the rows the launch works on (every other row leaves behind its descriptor)
                     if (dq_e1) { a.s_out = row_view(b, out, false).keep; a.keep_signed = 1; }
+                    if (dq_e1 && plan.t_list && plan.t_list->take == 1) agg_take_list(a, *plan.t_list);
                     by = t_centre_agg_bytes(b, out, fi, maskbits != nullptr, st);
                 }
-                GM_TRY(launch_agg(a, by, by, st));
+                if (!(t_centre && l == Lg - 1 && dq_e1 && plan.t_list && plan.t_list->take == 2)) GM_TRY(launch_agg(a, by, by, st));
             }
         }
     }

@@ -650,7 +650,9 @@ int gm_dense_fused_gemm(const gm_batch_t* b, int32_t table, const float* x, int6
  *   (v * width + c) / 4, bit c % 4;  mask_h [rows, width] (or NULL): zero where mask_h <= 0;  mask_b (or NULL): the same as packed bits.
  * hubs: 0 no hub handling (every row by the row kernels); 1 the batch's hub-row list without a schedule (a separate hub launch); 2 its block schedule and hub parts.
  * rowlist (device, ascending, n_list entries; or NULL): the windows walk these rows in windows of list_win rows (2, 4, .. 64); list_sched: with the batch's own
- *   schedule over its list of window rows (the list must be that list).  skip_lo <= skip_hi: rows of those degrees are left unwritten (window kernel only).
+ *   schedule over its list of window rows (the list must be that list); list_sched 2 / 3 / 4 with rowlist NULL: the launch walks the batch's own list 0 / 1 / 2 of
+ *   observable rows (gm_dense_obs_lists; 4 goes with transposed) as the model's launches do: sized by the list's bound, with its window and its own block schedule,
+ *   the length read on the device.  skip_lo <= skip_hi: rows of those degrees are left unwritten (window kernel only).
  * stream_ok: the launch may take the stream kernel where the library's own callers could (hubs == 2, scale_src == 2, no epilogue option).
  * launched (or NULL) receives the id of the kernel instantiation that ran (GM_AGG_ID_* in the library's internal header).
  * GM_EINVAL: mask_h together with mask_b; a row list together with stream_ok, off the window kernel, not ascending or out of range; a gather of another width
@@ -671,7 +673,13 @@ int gm_dense_aggregate(const gm_batch_t* b, int32_t transposed, int32_t x_src, c
  *   no source {ZERO, ZERO, 1, 0};  one {u0, u0, w0, 0};  two {u0, u1, w0, w1};  more {row | SELF, row | SELF, 1, 0};  w = norm[u] (x the edge's weight);
  *   dQ table: a centre row {row | SELF, ZERO, 1, 0}, any other {ZERO, ZERO, 0, 0}.
  * 7 / 8 / 9 (GM_DEAD_ROWS=3; at 4 also of the differentiated passes and their weight gradients) the tables of the passes nobody differentiates, same layout: 7 table 4's entry on the centre rows, 8 table 4's and 9 table 5's
- * entry on the sources of the centres' in-edges (the rows GM_F_OBS_E1 keeps); every other row {ZERO, ZERO, 0, 0}. */
+ * entry on the sources of the centres' in-edges (the rows GM_F_OBS_E1 keeps); every other row {ZERO, ZERO, 0, 0}.
+ * 10 / 11 / 12 (int32, up to the list's bound) the ascending lists of observable rows that the restricted aggregate launches walk (GM_AGG_OBS_LIST): rows of 3 ..
+ *   hub-threshold sources that GM_F_OBS_CENTRE keeps, the same that GM_F_OBS_E1 keeps, and every row GM_F_NORM_E1 keeps.  gm_dense_obs_lists: info[16], per list
+ *   {length (read back at first use: synchronises the stream), the bound it is allocated and scheduled for, rows per window, 0 not taken / 1 taken / 2 nothing to
+ *   launch, + 4 with a block schedule of its own}, then {observable rows of more than two sources (hub rows included) of the centre set, of the set GM_F_OBS_E1
+ *   keeps (-1 without the tables), rows GM_F_NORM_E1 keeps, 0}. */
+int gm_dense_obs_lists(const gm_batch_t* b, int64_t* info, void* stream);
 int gm_dense_agg_info(const gm_batch_t* b, int32_t transposed, int64_t* info);
 int gm_dense_fuse_counts(const gm_batch_t* b, int64_t* counts);
 int gm_dense_agg_table(const gm_batch_t* b, int32_t which, int32_t transposed, void* dst, int64_t n, void* stream);
