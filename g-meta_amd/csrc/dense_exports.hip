@@ -100,10 +100,12 @@ extern "C" int gm_dense_gemm(const gm_batch_t* b, const float* x, int64_t ldx, i
 
 // The fused aggregate + GEMM as gcn_forward's `fuse` branch launches it: gm_dense_gemm with gm_gemm_args::fuse2 set.  The table is always the batch's own
 // (table 0: d_fuse2 over the caller's x; 1: d_fuse2_feat over the batch's feature table), so the kernel reads no row outside its operands
-extern "C" int gm_dense_fused_gemm(const gm_batch_t* b, int32_t table, const float* x, int64_t ldx, int32_t K, const float* zside, int64_t ldz,
-                                   const float* zfull, int64_t ldzf, const float* W, int64_t w_stride, int32_t N, float* out, int64_t ldc, const float* s,
-                                   const float* s_keep, const float* bias, int64_t bias_stride, int32_t relu, uint8_t* relu_bits, float* zero_out,
-                                   uint32_t* amax_out, int32_t mode, int32_t* launched, void* stream) {
+// rowset -1: the batch's full tables (gm_dense_fused_gemm).  0 / 1 (gm_dense_fused_gemm_rows): the tables of the centre rows / of the sources of their in-edges, with
+// live_on the set's tile flags (gm_batch::d_tile_live), grid workgroups (0: the production rule)
+static int dense_fused_gemm(const gm_batch_t* b, int32_t rowset, int32_t live_on, int32_t grid, int32_t table, const float* x, int64_t ldx, int32_t K, const float* zside, int64_t ldz,
+                            const float* zfull, int64_t ldzf, const float* W, int64_t w_stride, int32_t N, float* out, int64_t ldc, const float* s,
+                            const float* s_keep, const float* bias, int64_t bias_stride, int32_t relu, uint8_t* relu_bits, float* zero_out,
+                            uint32_t* amax_out, int32_t mode, int32_t* launched, void* stream) {
     GM_REQUIRE(b && W && out && zside && K >= 1 && N >= 1 && ldz >= K && ldc >= N && (mode == 1 || mode == 2) && (table == 0 || table == 1), GM_EINVAL,
                "dense_fused_gemm: bad arguments");
     GM_REQUIRE(b->d_fuse2 && b->d_fuse2_feat, GM_EINVAL, "dense_fused_gemm: the batch carries no source tables");
@@ -122,6 +124,13 @@ extern "C" int gm_dense_fused_gemm(const gm_batch_t* b, int32_t table, const flo
     g.zside = zside; g.ldz = ldz;
     if (table == 1) { g.A = b->feat; g.lda = b->feat_ld; g.fuse2 = b->d_fuse2_feat; }
     else { g.A = x; g.lda = ldx; g.fuse2 = b->d_fuse2; }
+    if (rowset >= 0) {
+        GM_REQUIRE(rowset <= 1 && !(rowset == 0 && table == 1) && grid >= 0, GM_EINVAL, "dense_fused_gemm_rows: bad row set");
+        GM_REQUIRE(b->d_fwd_tab[0] && b->d_fwd_tab[1] && b->d_fwd_tab_feat && b->d_tile_live[0] && b->d_tile_live[1], GM_EINVAL, "dense_fused_gemm_rows: the batch carries no row-set tables");
+        g.fuse2 = rowset == 0 ? b->d_fwd_tab[0] : table == 1 ? b->d_fwd_tab_feat : b->d_fwd_tab[1];
+        if (live_on) g.tile_live = b->d_tile_live[rowset];
+        g.grid_test = grid;
+    }
     uint16_t* planes = nullptr; unsigned* slots = nullptr;
     int rc = gm_alloc(&planes, (size_t)wsets * 3 * K * N, st);
     gm_bound wb = gm_no_bound();
@@ -142,6 +151,25 @@ extern "C" int gm_dense_fused_gemm(const gm_batch_t* b, int32_t table, const flo
     if (slots) gm_dev_free(slots, st);
     gm_batch_mark_use(b, st);
     return rc;
+}
+
+extern "C" int gm_dense_fused_gemm(const gm_batch_t* b, int32_t table, const float* x, int64_t ldx, int32_t K, const float* zside, int64_t ldz,
+                                   const float* zfull, int64_t ldzf, const float* W, int64_t w_stride, int32_t N, float* out, int64_t ldc, const float* s,
+                                   const float* s_keep, const float* bias, int64_t bias_stride, int32_t relu, uint8_t* relu_bits, float* zero_out,
+                                   uint32_t* amax_out, int32_t mode, int32_t* launched, void* stream) {
+    return dense_fused_gemm(b, -1, 0, 0, table, x, ldx, K, zside, ldz, zfull, ldzf, W, w_stride, N, out, ldc, s, s_keep, bias, bias_stride, relu, relu_bits, zero_out, amax_out,
+                            mode, launched, stream);
+}
+// ... over the table of a row set, as the restricted forward-only layers launch it (GM_DEAD_ROWS=3, GM_DEAD_TILES; tests): rowset 0 the centre rows (gm_batch::d_fwd_tab[0],
+// keep vector d_norm_c), 1 the sources of their in-edges (d_fwd_tab[1] / d_fwd_tab_feat, d_norm_e1).  keep: the set's keep vector is the launch's row_scale_keep (0: the
+// batch's norm scales and every row is stored).  live_on: the launch gets the set's tile flags.  grid: workgroups (0: the production rule)
+extern "C" int gm_dense_fused_gemm_rows(const gm_batch_t* b, int32_t rowset, int32_t keep, int32_t live_on, int32_t grid, int32_t table, const float* x, int64_t ldx, int32_t K,
+                                        const float* zside, int64_t ldz, const float* zfull, int64_t ldzf, const float* W, int64_t w_stride, int32_t N, float* out, int64_t ldc,
+                                        const float* bias, int64_t bias_stride, int32_t relu, uint8_t* relu_bits, float* zero_out, uint32_t* amax_out, int32_t mode,
+                                        int32_t* launched, void* stream) {
+    GM_REQUIRE(b && (rowset == 0 || rowset == 1) && b->d_norm_c && b->d_norm_e1, GM_EINVAL, "dense_fused_gemm_rows: bad arguments");
+    return dense_fused_gemm(b, rowset, live_on, grid, table, x, ldx, K, zside, ldz, zfull, ldzf, W, w_stride, N, out, ldc, b->d_norm, keep ? (rowset == 0 ? b->d_norm_c : b->d_norm_e1) : nullptr,
+                            bias, bias_stride, relu, relu_bits, zero_out, amax_out, mode, launched, stream);
 }
 
 // The dZ product of the last layer over a dQ that holds its centre rows only, as gcn_backward launches it under GM_DEAD_ROWS (tests)
@@ -420,9 +448,17 @@ extern "C" int gm_dense_fuse_counts(const gm_batch_t* b, int64_t* counts) {
 // Device copies of the batch's derived tables (which: 0 per-edge source norm of orientation o [edges] float, 1 per-edge feature row [edges] int32, 2 window-row
 // list [info[6]] int32, 3 hub rows of orientation o [info[1]] int32; 4 / 5 / 6 the per-row source tables gm_batch::d_fuse2 / d_fuse2_feat / d_dq_tab, [rows] entries
 // of four int32 {u0, u1, w0, w1}; 7 / 8 / 9 the forward-only passes' tables of GM_DEAD_ROWS=3 in the same layout: the last layer's (gm_batch::d_fwd_tab[0]), the layer
-// below it over batch rows (d_fwd_tab[1]) and over the feature table (d_fwd_tab_feat); 10 / 11 / 12 the lists of observable rows gm_batch::obs[0 .. 2], int32): n entries -> dst (device)
+// below it over batch rows (d_fwd_tab[1]) and over the feature table (d_fwd_tab_feat); 10 / 11 / 12 the lists of observable rows gm_batch::obs[0 .. 2], int32; 13 / 14 the tile flags
+// gm_batch::d_tile_live[0 / 1], one int32 per GEMM row tile): n entries -> dst (device)
 extern "C" int gm_dense_agg_table(const gm_batch_t* b, int32_t which, int32_t transposed, void* dst, int64_t n, void* stream) {
-    GM_REQUIRE(b && dst && n >= 0 && which >= 0 && which <= 12, GM_EINVAL, "dense_agg_table: bad arguments");
+    GM_REQUIRE(b && dst && n >= 0 && which >= 0 && which <= 14, GM_EINVAL, "dense_agg_table: bad arguments");
+    if (which >= 13) {      // 13 / 14: the tile flags of the centre rows / of the sources of their in-edges (gm_batch::d_tile_live), one int32 per GEMM row tile
+        const int32_t* fl = b->d_tile_live[which - 13];
+        GM_REQUIRE(fl && n <= b->n_tiles, GM_EINVAL, "dense_agg_table: table %d holds %lld entries", which, (long long)(fl ? b->n_tiles : 0));
+        if (n) GM_HIP(hipMemcpyAsync(dst, fl, 4 * (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        gm_batch_mark_use(b, (hipStream_t)stream);
+        return GM_OK;
+    }
     if (which >= 10) {      // 10 / 11 / 12: the lists of observable rows (gm_dense_obs_lists), up to their bound
         const gm_batch::obs_list& ol = b->obs[which - 10];
         GM_REQUIRE(ol.rows && n <= ol.cap, GM_EINVAL, "dense_agg_table: table %d holds %lld entries", which, (long long)(ol.rows ? ol.cap : 0));

@@ -819,6 +819,17 @@ __global__ void k_fwd_tables(const int4* f2, const int4* f2_feat, const float* n
         obs_c[r] = c ? 1.f : -1.f; obs_e1[r] = e ? 1.f : -1.f;
     }
 }
+// GM_DEAD_TILES flags (gm_batch::d_tile_live): one block per GEMM row tile {set, row0, nrows <= GM_GEMM_BM}; live_c / live_e1[tile] = 1 where some row of the tile has
+// the sign bit of norm_c / norm_e1 clear, else 0
+__global__ __launch_bounds__(GM_GEMM_BM) void k_tile_live(const int32_t* tiles, int n_tiles, const float* norm_c, const float* norm_e1, int32_t* live_c, int32_t* live_e1) {
+    const int t = blockIdx.x;
+    if (t >= n_tiles) return;
+    const int row0 = tiles[3 * t + 1], nrows = tiles[3 * t + 2], r = threadIdx.x;
+    const bool in = r < nrows;
+    const int c = in && !(__float_as_uint(norm_c[(int64_t)row0 + r]) >> 31), e = in && !(__float_as_uint(norm_e1[(int64_t)row0 + r]) >> 31);
+    const int any_c = __syncthreads_or(c), any_e = __syncthreads_or(e);
+    if (r == 0) { live_c[t] = any_c ? 1 : 0; live_e1[t] = any_e ? 1 : 0; }
+}
 // what the partial aggregate launch over flag vector `obs` touches: rows of more than maxdeg in-edges with a positive flag and their in-edges (out[0], out[1]); their
 // sources marked in `bits` (k_count_bits counts them)
 __global__ void k_fwd_count(const int32_t* indptr, const int32_t* indices, const float* obs, int64_t rows, int maxdeg, uint32_t* bits, unsigned long long* out) {
@@ -1203,6 +1214,11 @@ static int finalize_finish(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
                                tc, te, tf, b->d_obs[0], b->d_obs[1]);
             GM_HIP(hipGetLastError());
             b->d_fwd_tab[0] = tc; b->d_fwd_tab[1] = te; b->d_fwd_tab_feat = tf;
+        }
+        if (b->d_tiles && b->n_tiles > 0) {      // GM_DEAD_TILES: which GEMM row tiles hold a row of either set
+            GM_TRY(gm_balloc(b, &b->d_tile_live[0], (size_t)b->n_tiles, s)); GM_TRY(gm_balloc(b, &b->d_tile_live[1], (size_t)b->n_tiles, s));
+            hipLaunchKernelGGL(k_tile_live, dim3(b->n_tiles), dim3(GM_GEMM_BM), 0, s, b->d_tiles, b->n_tiles, b->d_norm_c, b->d_norm_e1, b->d_tile_live[0], b->d_tile_live[1]);
+            GM_HIP(hipGetLastError());
         }
         // ---- the observable rows of the restricted aggregate launches as compact lists (gm_batch::obs), each with its window and, where its orientation has hub rows,
         // its block schedule.  No host wait: [0] follows from the centres' rows and in-degrees the round trip brought; [1] / [2] are sized by their bounds, and the

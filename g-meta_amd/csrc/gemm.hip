@@ -521,7 +521,9 @@ static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
             // With the two-piece kernels (shorter tiles) the optimum moved from 4 to 3, and to 2 for the launches of 16 and more tiles per CU:
             // 4-task shard 4.36 -> 4.25 ms, task_num 32 24.86 -> 24.50 (three runs each, same box).
             const int mult_f = a.n_tiles >= 16 * grid_cap ? 2 : 3;
-            const int grid = std::min(a.n_tiles, mult_f * grid_cap);
+            const int grid = std::min(a.n_tiles, a.grid_test > 0 ? a.grid_test : mult_f * grid_cap);
+            // dead tiles: only where the kernel's epilogue has nothing to leave for a row that is not kept (keep_signed, no relu' bits, no zero fill), three pieces
+            if (a.tile_live && a.row_scale_keep && !a.relu_bits && !a.zero_out && !f16) k.tile_live = a.tile_live;
             GM_TRY(f16 ? (launch_gemm_split<true, 2>(a, k, grid, false, s)) : (launch_gemm_split<true, 3>(a, k, grid, false, s)));
         } else {
             const int grid = std::min(a.n_tiles, grid_cap);

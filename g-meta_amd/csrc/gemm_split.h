@@ -62,7 +62,10 @@ struct SplitGemmK {
     const float* row_scale; const float* bias; int64_t bias_stride; const float* mask_h; int relu;
     const uint8_t* mask_b; uint8_t* relu_bits;
     const int32_t* tiles; int n_tiles; int n_col_tiles; int nt_store;
-    unsigned long long* dbg;                   // unused; kept so the split kernels' argument layout stays as it is
+    // k_gemm_split_p<true, ., ., 3> with keep_signed and neither relu_bits nor zero_out: one word per tile of `tiles`, 0 = no row of the tile is kept (a DEAD
+    // tile: its MFMAs are issued on zero registers -- no table fetch, no operand load, no LDS traffic, no barrier, no epilogue).  NULL: every tile is walked.
+    // (it took the place of an unused pointer: the split kernels' argument layout stays as it is)
+    const int32_t* tile_live;
     int dephase;                               // unused; kept so the split kernels' argument layout stays as it is
     // k_gemm_split_p<true> (fused aggregate + GEMM): A / lda address the aggregate's INPUT rows, f2 is the per-row source table, rows
     // flagged GM_SPLIT_FUSE_SELF read their finished aggregate from zside (row stride ldz), rows without a source read zeros
@@ -257,7 +260,11 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
     constexpr int A_PER = (BM * BK / 4) / 256;                                        // float4 per A-feeder lane and chunk: MI (four feeder waves)
     constexpr int B_PPW = (NP * 2 * (BN / 64)) / 4;                                   // DMA pieces per B-feeder wave and chunk: 6 (N = 256) / 3
     constexpr int OFF_MAX = OFF_BIAS + 2 * BN * 4;                                    // {max bits, arrivals} of the compute waves' amax_out flush
-    __shared__ __attribute__((aligned(16))) char smem[OFF_MAX + 16];
+    // SplitGemmK::tile_live: the ordinals of this workgroup's live tiles, ascending, and their count (LIVE_CAP + 1 words behind the flush pair)
+    constexpr bool LIVE = GATHER && NP == 3;
+    constexpr int LIVE_CAP = LIVE ? 1024 : 0, OFF_LIVE = OFF_MAX + 16;
+    static_assert(!LIVE || SPLIT == 1, "one flag per tile of `tiles`");
+    __shared__ __attribute__((aligned(16))) char smem[OFF_LIVE + (LIVE ? (LIVE_CAP + 4) * 4 : 0)];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nchunks = g.K / BK;
     const int G = gridDim.x, b = blockIdx.x;
@@ -279,11 +286,79 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
         if constexpr (NP == 3) return 1.f;
         else return gs_bound_scale(g.b_bound, set);
     };
-    const int total = ntb * nchunks;                                                  // flattened chunk count
+    // Dead tiles (SplitGemmK::tile_live).  Wave 0 compacts the ordinals of the workgroup's live tiles into LDS; every role then runs its flattened (tile, chunk)
+    // sequence over that list -- nt tiles, the i-th of them tile ord(i) of the workgroup -- so every role executes the same 1 + nt * nchunks barriers, and
+    // whatever was keyed on the tile ordinal's parity (scales / biasl, the A stage, the B stage) is keyed on i.  The compute waves issue the MFMAs of the dead tiles
+    // in front of each live one (and behind the last) on zero registers, without a barrier.  A workgroup of more tiles than the list holds walks all of them.
+    int nt = ntb; bool listed = false;
+    const int* live_idx = reinterpret_cast<const int*>(smem + OFF_LIVE);
+    if constexpr (LIVE) {
+        if (g.tile_live && g.keep_signed && !g.relu_bits && !g.zero_out && ntb > 0 && ntb <= LIVE_CAP) {
+            int* lw = reinterpret_cast<int*>(smem + OFF_LIVE);
+            if (wave == 0) {
+                int n = 0;
+                for (int t0 = 0; t0 < ntb; t0 += 64) {
+                    const int ti = t0 + lane;
+                    const bool lv = ti < ntb && g.tile_live[logical(b + ti * G)] != 0;
+                    const unsigned long long m = __ballot(lv);
+                    if (lv) lw[n + __popcll(m & ((1ull << lane) - 1ull))] = ti;
+                    n += __popcll(m);
+                }
+                if (lane == 0) lw[LIVE_CAP] = n;
+            }
+            __syncthreads();
+            nt = __builtin_amdgcn_readfirstlane(live_idx[LIVE_CAP]); listed = true;
+        }
+    }
+    auto ord = [&](int i) -> int {                                                    // i-th tile this workgroup walks -> its ordinal among the workgroup's tiles
+        if constexpr (LIVE) { if (listed) return __builtin_amdgcn_readfirstlane(live_idx[i]); }
+        return i;
+    };
+    // n chunks of a dead tile on a compute wave: the chunk's MFMAs in the six-product order over the wave's 2 MI accumulator blocks, operands and accumulators zero
+    // registers nobody reads (asm volatile: the compiler would delete builtins without a reader).  s_nop: the hazard recogniser does not look into the asm.
+    auto dead_chunks = [&](int n) {
+        if constexpr (LIVE) {
+            if (n <= 0) return;
+            gm_f32x16 d[MI][2];
+#pragma unroll
+            for (int i = 0; i < MI; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) d[i][j][e] = 0.f;
+            gm_bf16x8 za, zb;
+            {                                                                         // (opaque zeros, like the zero quad of the epilogue)
+                typedef unsigned u4 __attribute__((ext_vector_type(4)));
+                u4 ua, ub;
+                asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0\n\tv_mov_b32 %2, 0\n\tv_mov_b32 %3, 0" : "=v"(ua.x), "=v"(ua.y), "=v"(ua.z), "=v"(ua.w));
+                asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0\n\tv_mov_b32 %2, 0\n\tv_mov_b32 %3, 0" : "=v"(ub.x), "=v"(ub.y), "=v"(ub.z), "=v"(ub.w));
+                za = __builtin_bit_cast(gm_bf16x8, ua); zb = __builtin_bit_cast(gm_bf16x8, ub);
+            }
+            asm volatile("s_nop 7" ::: "memory");
+#define GS_M(D) "v_mfma_f32_32x32x16_bf16 " D ", %[a], %[b], " D "\n\t"
+            for (; n > 0; --n) {                                                      // (s_nop: the compiler may place the zero fills right in front of the block)
+                if constexpr (MI == 2) {
+#define GS_P GS_M("%[d0]") GS_M("%[d1]") GS_M("%[d2]") GS_M("%[d3]")
+                    asm volatile("s_nop 1\n\t" GS_P GS_P GS_P GS_P GS_P GS_P : [d0] "+v"(d[0][0]), [d1] "+v"(d[0][1]), [d2] "+v"(d[MI - 1][0]), [d3] "+v"(d[MI - 1][1]) : [a] "v"(za), [b] "v"(zb));
+#undef GS_P
+                } else {
+#define GS_P GS_M("%[d0]") GS_M("%[d1]")
+                    asm volatile("s_nop 1\n\t" GS_P GS_P GS_P GS_P GS_P GS_P : [d0] "+v"(d[0][0]), [d1] "+v"(d[0][1]) : [a] "v"(za), [b] "v"(zb));
+#undef GS_P
+                }
+            }
+#undef GS_M
+            asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+        }
+    };
+    const int total = nt * nchunks;                                                   // flattened chunk count
     const unsigned lds_base = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
     float* scales = reinterpret_cast<float*>(smem + OFF_SC);                          // [2][128] by tile parity
     float* biasl = reinterpret_cast<float*>(smem + OFF_BIAS);                         // [2][256]
-    if (total == 0) return;
+    if (total == 0) {                                                                 // (no live tile: no barrier in any role)
+        if (listed && wave < 8) dead_chunks(ntb * nchunks);
+        return;
+    }
     if (NP == 2 && tid < 2) reinterpret_cast<unsigned*>(smem + OFF_MAX)[tid] = 0u;     // (visible to the compute waves after their first barrier)
     if (wave >= 12) {
         // ================= B feeder
@@ -299,10 +374,10 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
         const int64_t b_chunk_bytes = (int64_t)BK * g.N * 2;
         // chunks are issued in order: (tile, chunk) counters instead of a division per chunk, the tile's set looked up once per tile
         int ib_c = 0, ib_ti = 0;
-        uint64_t ib_base = (uint64_t)(uintptr_t)(g.Bt + (int64_t)tile_of(b).set * g.bt_stride);
+        uint64_t ib_base = (uint64_t)(uintptr_t)(g.Bt + (int64_t)tile_of(b + ord(0) * G).set * g.bt_stride);
         int ib_st = 0;                                                                // B stage of the next chunk to issue (gc % NB)
         auto issue_b = [&](int gc) {                                                  // global chunk gc (= the next in order) -> B stage gc % NB
-            if (ib_c == nchunks) { ib_c = 0; ++ib_ti; ib_base = (uint64_t)(uintptr_t)(g.Bt + (int64_t)tile_of(b + ib_ti * G).set * g.bt_stride); }
+            if (ib_c == nchunks) { ib_c = 0; ++ib_ti; ib_base = (uint64_t)(uintptr_t)(g.Bt + (int64_t)tile_of(b + ord(ib_ti) * G).set * g.bt_stride); }
             const uint64_t base = ib_base + (uint64_t)(ib_c * b_chunk_bytes);
             ++ib_c;
             const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)base), bhi = __builtin_amdgcn_readfirstlane((unsigned)(base >> 32));
@@ -360,8 +435,8 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
         float rc_sc = 1.f, rc_b = 0.f;
         float as_next = 1.f, as_cur = 1.f, inv_next = 1.f, inv_cur = 1.f;             // NP == 2: A scale of the tile being loaded / stored; 1 / (s_a s_b) for the epilogue
         auto fq_prefetch = [&](int ti) {                                              // table entries of tile ti (if any) -> fq, counted loads
-            if (ti >= ntb) return;
-            const GsTile t = tile_of(b + ti * G);
+            if (ti >= nt) return;
+            const GsTile t = tile_of(b + ord(ti) * G);
 #pragma unroll
             for (int p = 0; p < A_PER; ++p) {
                 const int4* q = g.f2 + t.row0 + min(rr[p], t.nrows - 1);
@@ -369,7 +444,7 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
             }
         };
         auto la_tile = [&](int ti, bool consts) {
-            const GsTile t = tile_of(b + ti * G);
+            const GsTile t = tile_of(b + ord(ti) * G);
             if constexpr (NP == 2) { as_next = a_scale_of(t.set); inv_next = (1.f / as_next) * (1.f / b_scale_of(t.set)); }
             if constexpr (GATHER) {
                 if constexpr (A_PER == 2) asm volatile("" : "+v"(fq[0]), "+v"(fq[A_PER - 1]) :: "memory");   // fetched a tile ago; every wait since then covered them
@@ -423,7 +498,7 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
                 as_cur = as_next; inv_cur = inv_next;
                 // the loads run PF_DA - 1 chunks ahead: with fewer chunks per tile than that (K = 32), la_tile has already moved as_next to a
                 // LATER tile, whose set may have another A bound -- take this tile's own (the short-K path reads its constants per tile anyway)
-                if constexpr (NP == 2) { if (!fast_consts) as_cur = a_scale_of(tile_of(b + sa_ti * G).set); }
+                if constexpr (NP == 2) { if (!fast_consts) as_cur = a_scale_of(tile_of(b + ord(sa_ti) * G).set); }
                 if constexpr (GATHER) {                                                // the loads of this tile were issued with w_next's table entries
 #pragma unroll
                     for (int p = 0; p < A_PER; ++p) { w_cur[p][0] = w_next[p][0]; w_cur[p][1] = w_next[p][1]; }
@@ -460,7 +535,7 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
         };
         // row scales + bias of tile ti -> LDS (parity ti & 1); ordinary loads, completed with the vmcnt(0) below
         auto stage_tile_consts = [&](int ti) {
-            const GsTile t = tile_of(b + ti * G);
+            const GsTile t = tile_of(b + ord(ti) * G);
             const int set = t.set, row0 = t.row0, nrows = t.nrows;
             float sc = 1.f;
             if (g.row_scale) sc = g.row_scale[row0 + min(ft & (BM - 1), nrows - 1)];
@@ -547,7 +622,9 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
             for (int o = 32; o >= 1; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o));
             if (lane == 0) vmax_note(__float_as_uint(vmax));
         };
-        for (int ti = 0; ti < ntb; ++ti) {
+        int walked = 0;                                                               // tiles of the workgroup behind us, dead ones included
+        for (int ti = 0; ti < nt; ++ti) {
+            if constexpr (LIVE) { if (listed) { const int o = ord(ti); dead_chunks((o - walked) * nchunks); walked = o + 1; } }
             gm_f32x16 acc[MI][2];
 #pragma unroll
             for (int i = 0; i < MI; ++i)
@@ -595,7 +672,7 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
             // ---- epilogue of tile ti: stores only (no global load, no barrier, no LDS staging).  The accumulators are transposed inside the
             // quads of lanes (gs_quad_transpose) so that a lane stores 16 bytes of ONE row and eight lanes cover 128 contiguous bytes of it; the
             // LDS round trips of the staged epilogue (8.6 k of a tile's 47 k cycles with the matrix pipe idle) are gone.
-            const GsTile tl = tile_of(b + ti * G);                // scalar (SMEM) loads: lgkmcnt, not vmcnt
+            const GsTile tl = tile_of(b + ord(ti) * G);                // scalar (SMEM) loads: lgkmcnt, not vmcnt
             const int row0 = tl.row0, nrows = tl.nrows;
             const float* sc_t = scales + (ti & 1) * GS_BM;
             const int t4 = li & 3, q4 = li >> 2;
@@ -648,6 +725,7 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
                 }
             }
         }
+        if constexpr (LIVE) { if (listed) dead_chunks((ntb - walked) * nchunks); }        // the dead tiles behind the last live one
         if constexpr (NP == 2) { if (g.amax_out && vmax_set >= 0) vmax_flush_last(); }     // (bit patterns of non-negative floats order as integers)
     }
 }

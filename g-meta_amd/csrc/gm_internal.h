@@ -211,6 +211,9 @@ struct gm_batch {
     void* d_fwd_tab[2] = {nullptr, nullptr};   // [rows] int4: d_fuse2's entry on the observable rows, {GM_FUSE_ZERO, GM_FUSE_ZERO, 0, 0} on every other row (gm_gemm_args::fuse2)
     void* d_fwd_tab_feat = nullptr;            // [rows] int4: d_fuse2_feat's entry on the [1] rows -- where the layer below the last gathers from the feature table
     float* d_obs[2] = {nullptr, nullptr};      // [rows] +1 on the observable rows, -1 on every other row: gm_agg_args::s_out + keep_signed of the partial aggregate launches (a scale of exactly 1)
+    // GM_DEAD_TILES (k_tile_live, next to k_fwd_tables): one word per tile of d_tiles, non-zero where some row of the tile has the sign bit of d_norm_c ([0]) / d_norm_e1 ([1])
+    // clear.  A split GEMM that stores those rows only issues a zero tile's MFMAs and nothing else of it (gm_gemm_args::tile_live)
+    int32_t* d_tile_live[2] = {nullptr, nullptr};
     // The observable rows of the restricted aggregate launches as compact ascending lists (finalize_finish, next to d_mid; GM_AGG_OBS_LIST).  [0]: rows of GM_FUSE_MAXDEG+1 ..
     // heavy_deg in-edges with d_obs[0] positive (the last layer's partial aggregate), [1]: the same with d_obs[1] (the layer below), [2]: rows with the sign of d_norm_e1
     // clear (the last layer's transposed aggregate; its hub rows stay listed, the windows pass over them).  [0] is built on the host from the centres' in-degrees (length
@@ -264,6 +267,7 @@ struct gm_knobs {
     int fuse_diff;
     int agg_mid_win;               // GM_AGG_MID_WIN: rows per wave window over that list (0 = by its length)
     int agg_obs_list;              // GM_AGG_OBS_LIST: the aggregate launches restricted to the observable rows walk the batch's compact lists of them (1, default; gm_batch::obs) or every row's descriptor (0).  Read at launch time (plan_pass): the lists are built either way
+    int dead_tiles;                // GM_DEAD_TILES: a fused three-piece split GEMM that stores the rows of a keep vector only takes the batch's tile flags (1, default; gm_batch::d_tile_live): a tile without a kept row issues its MFMAs on zero registers and nothing else.  0: every tile is fed.  Read by plan_pass alone; the flags are built either way
     int agg_mid_list;              // GM_AGG_MID_LIST: the partial aggregate launch of a fused pass walks a compact list of its window rows (1, default) or every row (0)
     int query_streams;             // GM_QUERY_STREAMS: 2 = the query evaluations of gm_meta_step alternate between two streams; anything else (default 0) = one stream
     int head_threads;              // GM_HEAD_THREADS: workgroup size of k_head_loss: 256 or 512; anything else (default 0) = 1024
@@ -585,6 +589,9 @@ struct gm_gemm_args {
     const int32_t* tiles;               // device [n_tiles*3]: set, row0, nrows  (nrows <= BM)
     int n_tiles;
     int64_t rows;                       // total rows covered by the tiles (profiling: flops = 2*rows*K*N)
+    const int32_t* tile_live;           // optional, with row_scale_keep: one word per tile, 0 = the tile holds no kept row (gm_batch::d_tile_live).  Taken by the fused three-piece split kernels
+                                        //   where the launch writes neither relu_bits nor zero_out (gemm_split.h: SplitGemmK::tile_live); every other launch ignores it
+    int grid_test;                      // tests only (gm_dense_fused_gemm_rows): workgroups of a fused split launch; 0 = the production rule
     int* launched;                      // optional: receives the GM_GEMM_ID_* of the instantiation launched (host side).  Set only by the
                                         // numerics-test export gm_dense_gemm; the product path leaves it NULL
 };

@@ -716,12 +716,15 @@ enum DqFill { DQ_MEMSET, DQ_ZEROED, DQ_CENTRE };
 //  relu_bits: the layer writes its relu' bits M[l] (where the context has them): every pass but the ones nobody differentiates
 //  list (GM_AGG_OBS_LIST): the partial aggregate launch of a restricted fused layer walks the batch's compact list of its observable rows (gm_batch::obs; take == 2:
 //    nothing to launch) instead of every listed row's descriptor; NULL: today's launch
-struct LayerPlan { bool split, fuse; RowSet formed, stored; bool relu_bits; const gm_batch::obs_list* list; };
+//  dead_tiles (GM_DEAD_TILES): the update of a forward-only fused layer that stores the centre rows or the sources of their in-edges takes the batch's tile flags of that
+//    set: a tile without a stored row issues its MFMAs on zero registers -- no table fetch, no operand load, no LDS traffic, no barrier, no epilogue (gemm_split.h)
+struct LayerPlan { bool split, fuse; RowSet formed, stored; bool relu_bits; const gm_batch::obs_list* list; bool dead_tiles; };
 // The pass: its kind, its layers, dQ_L, and what a gcn_backward(skip_head = 1) over it may do (GM_DEAD_ROWS=2; gcn_backward has the bitwise argument).  t_centre: dQ_L is
 // left to its centre rows and the zero block behind T_L is there -- the dZ GEMM stores T_L's centre rows only, the transposed aggregate reads T_L through gm_batch::d_ect.
 // dq_e1: ... and the layer below is the first, aggregate-first, with a table-fed three-piece weight gradient: that aggregate stores only the rows of dQ_{L-1} that can be non-zero
 // t_list: ... and walks the compact list of those rows (gm_batch::obs[2]), as LayerPlan::list
-struct PassPlan { PassKind kind; LayerPlan layer[GM_MAX_GCN]; DqFill dq; bool t_centre, dq_e1; const gm_batch::obs_list* t_list; };
+// t_dead_tiles (GM_DEAD_TILES): the table-read dZ launch under t_centre takes the centre rows' tile flags, as LayerPlan::dead_tiles
+struct PassPlan { PassKind kind; LayerPlan layer[GM_MAX_GCN]; DqFill dq; bool t_centre, dq_e1; const gm_batch::obs_list* t_list; bool t_dead_tiles; };
 
 struct GcnCtx {
     const gm_batch* b; gm_layout L;
@@ -923,11 +926,12 @@ static int batch_agg(const GcnCtx& c, int dir, hipStream_t st, gm_agg_args& a) {
 // forward partial aggregate, a scale of exactly 1 (NULL: every row).  tab: the per-row source table of a fused loader or a table-fed weight gradient over a Z_l formed on the
 // set -- the full table's entry on its rows, the zero row everywhere else (gather: the layer reads the feature table; a centre-restricted layer never does, plan_check).
 // obs: the set's index into the tables of gm_batch_fwd_counts, -1 where it has none.  n: its rows as the host knows them (ROWS_E1: a bound, see rows_kept)
-struct RowView { const float* keep; const float* sign; const void* tab; int obs; int64_t n; };
+// live: one word per GEMM row tile, 0 = no row of the set in it (gm_batch::d_tile_live; NULL: every row / no flags)
+struct RowView { const float* keep; const float* sign; const void* tab; int obs; int64_t n; const int32_t* live; };
 static RowView row_view(const gm_batch* b, RowSet rs, bool gather) {
-    if (rs == ROWS_E1) return {b->d_norm_e1, b->d_obs[1], gather ? b->d_fwd_tab_feat : b->d_fwd_tab[1], 1, b->n_e1};
-    if (rs == ROWS_CENTRE) return {b->d_norm_c, b->d_obs[0], b->d_fwd_tab[0], 0, b->n_c};
-    return {rs == ROWS_SRC ? b->d_norm_src : nullptr, nullptr, gather ? b->d_fuse2_feat : b->d_fuse2, -1, rs == ROWS_SRC ? b->n_src : b->rows};
+    if (rs == ROWS_E1) return {b->d_norm_e1, b->d_obs[1], gather ? b->d_fwd_tab_feat : b->d_fwd_tab[1], 1, b->n_e1, b->d_tile_live[1]};
+    if (rs == ROWS_CENTRE) return {b->d_norm_c, b->d_obs[0], b->d_fwd_tab[0], 0, b->n_c, b->d_tile_live[0]};
+    return {rs == ROWS_SRC ? b->d_norm_src : nullptr, nullptr, gather ? b->d_fuse2_feat : b->d_fuse2, -1, rs == ROWS_SRC ? b->n_src : b->rows, nullptr};
 }
 // Rows of a set, and the by-source edges of those rows, for the launch accounting: exact when it is on (ROWS_E1: read back / counted once per batch at first use, which
 // synchronises the stream), their bounds otherwise -- nobody reads them then
@@ -1080,6 +1084,17 @@ static int plan_pass(const GcnCtx& c, const float* params, int64_t pstride, Pass
             if (p.layer[l].fuse && p.layer[l].formed != ROWS_ALL) p.layer[l].list = taken(p.layer[l].formed == ROWS_CENTRE ? 0 : 1);
         if (p.dq_e1) p.t_list = taken(2);
     }
+    // GM_DEAD_TILES: the fused three-piece launches that store a flagged row set and leave nothing else behind for the other rows -- a forward-only layer stored on
+    // the centre rows or on the sources of their in-edges (no relu' bits, no dQ fill), and the table-read dZ launch that stores T_L's centre rows.  The last layer
+    // of a PASS_DIFF writes relu' bits for every row and stays as it is
+    if (gm_knob().dead_tiles) {
+        for (int l = 0; l < Lg; ++l) {
+            const LayerPlan& lp = p.layer[l];
+            p.layer[l].dead_tiles = kind == PASS_FWD_ONLY && lp.fuse && !lp.relu_bits && c.np != 2 && (lp.stored == ROWS_CENTRE || lp.stored == ROWS_E1) &&
+                                    row_view(b, lp.stored, false).live != nullptr;
+        }
+        p.t_dead_tiles = p.t_centre && c.np != 2 && b->d_tile_live[0] != nullptr;
+    }
     *plan = p; return plan_check(c, p);
 }
 // a restricted launch over the plan's list: the list in the windows' place, its own schedule (or none), the length the device counted
@@ -1156,6 +1171,7 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
             g.relu_bits = relu_bits;
             // the other rows are computed, their relu' bits written, their values not stored (the kept-row count is for the launch accounting)
             if (lp.stored != ROWS_ALL) { g.row_scale_keep = row_view(b, lp.stored, false).keep; g.n_keep = rows_kept(b, lp.stored, st); }
+            if (lp.dead_tiles) g.tile_live = row_view(b, lp.stored, false).live;
             if (lp.split) {
                 GM_TRY(weight_planes(c, params, pstride, l, 0, st, g));
                 GM_REQUIRE(!(l == L.n_gcn - 1 && plan.dq == DQ_CENTRE) || g.np == 3, GM_EINVAL, "forward: dQ is left to its centre rows, which needs the three-piece kernels");
@@ -1268,6 +1284,7 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
                     // holds for a context or not at all: a dQ_L left to its centre rows always comes this way)
                     if (dq_centre && l == Lg - 1) { g.fuse2 = b->d_dq_tab; g.zside = dQ; g.ldz = fo; }
                     if (t_centre && l == Lg - 1) { g.row_scale_keep = row_view(b, ROWS_CENTRE, false).keep; g.n_keep = rows_kept(b, ROWS_CENTRE, st); }
+                    if (t_centre && l == Lg - 1 && plan.t_dead_tiles) g.tile_live = row_view(b, ROWS_CENTRE, false).live;
                 } else if (use_wt) {
                     // dZ = dQ @ W^T through the direct-to-LDS kernel on transposed weights: left there by the previous step's
                     // weight-gradient reduction (which wrote these very weights), else transposed now (T x 256 KB)

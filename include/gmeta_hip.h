@@ -637,6 +637,15 @@ int gm_dense_fused_gemm(const gm_batch_t* b, int32_t table, const float* x, int6
                         int64_t ldzf, const float* W, int64_t w_stride, int32_t N, float* out, int64_t ldc, const float* s, const float* s_keep,
                         const float* bias, int64_t bias_stride, int32_t relu, uint8_t* relu_bits, float* zero_out, uint32_t* amax_out, int32_t mode,
                         int32_t* launched, void* stream);
+/* The same launch over the table of a row set, as the restricted forward-only layers run it (tests): rowset 0 the centre rows (table 7 of gm_dense_agg_table, keep
+ * vector GM_F_NORM_CENTRE; table must be 0), 1 the sources of the centres' in-edges (table 8, or 9 with table == 1; GM_F_NORM_E1).  s = GM_F_NORM.  keep != 0: the
+ * set's keep vector is the launch's s_keep (only its rows are stored); 0: every row is stored.  live_on != 0: the launch gets the set's tile flags (GM_DEAD_TILES;
+ * gm_dense_agg_table 13 / 14): a tile without a kept row issues its MFMAs and nothing else -- taken by the three-piece kernel where keep is on and neither relu_bits
+ * nor zero_out is given, ignored otherwise.  grid: workgroups of the launch (0: the library's rule; a small batch otherwise gets one tile per workgroup). */
+int gm_dense_fused_gemm_rows(const gm_batch_t* b, int32_t rowset, int32_t keep, int32_t live_on, int32_t grid, int32_t table, const float* x, int64_t ldx, int32_t K,
+                             const float* zside, int64_t ldz, const float* zfull, int64_t ldzf, const float* W, int64_t w_stride, int32_t N, float* out, int64_t ldc,
+                             const float* bias, int64_t bias_stride, int32_t relu, uint8_t* relu_bits, float* zero_out, uint32_t* amax_out, int32_t mode,
+                             int32_t* launched, void* stream);
 /* One aggregate launch over one orientation of the batch (0: the in-edge CSR, transposed: the by-source CSR) with every option the library's own callers
  * set, exported for numerics tests of every aggregate kernel (agg.hip, agg_stream.hip):
  *   out[v, :width] = epi(|s_out[v]| * sum over the edges e of row v of w_e * X[src_e, :] + bias_t)      for the rows v of set t.
@@ -678,7 +687,9 @@ int gm_dense_aggregate(const gm_batch_t* b, int32_t transposed, int32_t x_src, c
  *   hub-threshold sources that GM_F_OBS_CENTRE keeps, the same that GM_F_OBS_E1 keeps, and every row GM_F_NORM_E1 keeps.  gm_dense_obs_lists: info[16], per list
  *   {length (read back at first use: synchronises the stream), the bound it is allocated and scheduled for, rows per window, 0 not taken / 1 taken / 2 nothing to
  *   launch, + 4 with a block schedule of its own}, then {observable rows of more than two sources (hub rows included) of the centre set, of the set GM_F_OBS_E1
- *   keeps (-1 without the tables), rows GM_F_NORM_E1 keeps, 0}. */
+ *   keeps (-1 without the tables), rows GM_F_NORM_E1 keeps, 0}.
+ * 13 / 14 (int32, one per GEMM row tile of 128 rows inside a set, gm_batch_info's tile count) the tile flags of GM_DEAD_TILES: 1 where some row of the tile is kept
+ *   by GM_F_NORM_CENTRE / GM_F_NORM_E1, else 0. */
 int gm_dense_obs_lists(const gm_batch_t* b, int64_t* info, void* stream);
 int gm_dense_agg_info(const gm_batch_t* b, int32_t transposed, int64_t* info);
 int gm_dense_fuse_counts(const gm_batch_t* b, int64_t* counts);
