@@ -22,6 +22,7 @@ from .heuristics import (DISTANCE_SCORES, DIST_UNREACHED, PAGERANK_SCORES, PAIR_
                          link_path_scores, link_propagated_features, local_path_index, rooted_pagerank_index, sketch_distance_profile, sketch_intersections, sketch_profile_features)
 from .sketches import NodeSketches  # noqa: F401
 from .propagate import PropagatedFeatures  # noqa: F401
+from .predictor import PairPredictor  # noqa: F401
 
 __all__ = ['GraphStore', 'Subgraphs', 'SubgraphBatch', 'collate', 'Classifier', 'Meta', 'hop_label_width', 'hop_labels_switch', 'link_tables_with_negatives',
            'PAIR_SCORES', 'link_auc', 'link_heuristic_auc', 'candidate_names', 'PATH_SCORES', 'local_path_index', 'katz_index', 'link_path_scores',
@@ -29,4 +30,4 @@ __all__ = ['GraphStore', 'Subgraphs', 'SubgraphBatch', 'collate', 'Classifier', 
            'DISTANCE_SCORES', 'DIST_UNREACHED', 'graph_distance_index', 'link_distance_scores', 'link_distance_auc',
            'link_distance_profiles', 'distance_profile_features',
            'NodeSketches', 'hll_cardinality', 'sketch_intersections', 'sketch_distance_profile', 'link_sketch_profiles', 'sketch_profile_features',
-           'PropagatedFeatures', 'link_propagated_features']
+           'PropagatedFeatures', 'link_propagated_features', 'PairPredictor']

@@ -59,6 +59,10 @@ PROTOTYPES = {
     'gm_prop_rows': (i32, [vp, i32, vp, i64, vp, vp]),
     'gm_prop_pair_features': (i32, [vp, vp, i64, i32, vp, vp]),
     'gm_prop_destroy': (None, [vp]),
+    'gm_prop_pair_mlp_dims': (i32, [vp, i32, i32, vp, vp]),
+    'gm_prop_pair_mlp_tile': (i32, []),
+    'gm_prop_pair_mlp_forward': (i32, [vp, vp, i64, i32, vp, i32, vp, i32, vp, vp]),
+    'gm_prop_pair_mlp_step': (i32, [vp, vp, i64, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]),
     'gm_store_neighbour_degrees': (i32, [vp, i32, vp, vp]),
     'gm_store_pair_candidates': (i32, [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp]),
     'gm_extract': (C.c_int, [vp, vp, i32, vp, i32, i32, i32, u64, i32, vp, vp]),

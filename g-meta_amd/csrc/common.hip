@@ -381,6 +381,7 @@ const gm_knobs& gm_knob() {
         k.sketch_mib = env("GM_SKETCH_MIB", 0);
         k.prop_chunk = env("GM_PROP_CHUNK", 0);
         k.prop_mib = env("GM_PROP_MIB", 0);
+        k.pair_mlp_rows = env("GM_PAIR_MLP_ROWS", 0);
     });
     return k;
 }
@@ -412,6 +413,7 @@ static int gm_knobs::* gm_find_knob(const char* name) {
         {"sketch_mib", &gm_knobs::sketch_mib}, {"GM_SKETCH_MIB", &gm_knobs::sketch_mib},
         {"prop_chunk", &gm_knobs::prop_chunk}, {"GM_PROP_CHUNK", &gm_knobs::prop_chunk},
         {"prop_mib", &gm_knobs::prop_mib}, {"GM_PROP_MIB", &gm_knobs::prop_mib},
+        {"pair_mlp_rows", &gm_knobs::pair_mlp_rows}, {"GM_PAIR_MLP_ROWS", &gm_knobs::pair_mlp_rows},
     };
     for (const auto& e : tab)
         if (!strcmp(name, e.name)) return e.field;

@@ -291,8 +291,16 @@ struct gm_knobs {
     int sketch_mib;                // GM_SKETCH_MIB, gm_set_tuning("sketch_mib"): MiB one gm_store_sketch_build may allocate; 0 (default) = the library's choice, 8 GiB.  The result does not depend on it
     int prop_chunk;                // GM_PROP_CHUNK, gm_set_tuning("prop_chunk"): entries per segment of a hub row of gm_store_propagate_build (propagate.hip); 0 (default) = the library's choice.  The order of a row's fp32 sum, hence its low bits, belongs to it
     int prop_mib;                  // GM_PROP_MIB, gm_set_tuning("prop_mib"): MiB one gm_store_propagate_build may allocate; 0 (default) = the library's choice, 8 GiB.  The result does not depend on it
+    int pair_mlp_rows;             // GM_PAIR_MLP_ROWS, gm_set_tuning("pair_mlp_rows"): pairs per chunk of gm_prop_pair_mlp_step (pair_mlp.hip), which bounds its dh scratch; 0 (default) = the library's choice.  The logits do not depend on it; the summation order of the loss and the gradients, hence their low bits, belongs to it
 };
 const gm_knobs& gm_knob();
+
+// ---- the hop-propagated features of one graph (propagate.hip builds and reads them; pair_mlp.hip gathers their rows into its GEMMs)
+struct gm_prop {
+    int64_t N = 0, bytes = 0;
+    int32_t hops = 0, F = 0, ld = 0, flags = 0;
+    float* d = nullptr;                   // [hops + 1][N][ld]
+};
 
 // ---- the neighbour index (nbr_index.hip; the device side is gm_nbr.h) and the pair-score launch (pair_scores.hip), for the translation units that read the one
 // and score pairs of their own through the other (candidates.hip)

@@ -26,12 +26,7 @@
 #define GM_PR_MIB 8192                    // the library's prop_mib: 8 GiB per build
 #define GM_PR_MAX_HOPS 8
 
-struct gm_prop {
-    int64_t N = 0, bytes = 0;
-    int32_t hops = 0, F = 0, ld = 0, flags = 0;
-    float* d = nullptr;                   // [hops + 1][N][ld]
-};
-
+// (struct gm_prop, the handle, is in gm_internal.h: pair_mlp.hip reads the levels too)
 // the in-edge CSR of one graph: ptr = its rows of the store's pointers (GLOBAL edge offsets), idx / w based at the store's edge 0, sources LOCAL to the graph;
 // e0 = ptr[0]: coef[e - e0] is the coefficient of edge e
 struct pr_graph { const int64_t* ptr; const int32_t* idx; const float* w; int64_t N, e0; int32_t self; };

@@ -436,6 +436,40 @@ int32_t gm_prop_rows(const gm_prop_t* p, int32_t level, const int32_t* d_nodes, 
 int32_t gm_prop_pair_features(const gm_prop_t* p, const int32_t* d_pairs, int64_t n, int32_t op, float* d_out /* [n, hops + 1, F] */, void* stream);
 void gm_prop_destroy(gm_prop_t* p);
 
+/* ---- THE BUDDY PAIR PREDICTOR on those levels (beyond the reference): one hidden layer over the concatenation of a pair's level products and S caller-supplied
+ * structure columns, scored and differentiated on the device without the [n, K] input matrix ever standing in memory.  This comment is THE definition;
+ * tests/pair_mlp_ref.py restates it in float64.  For a handle p (levels x_0 .. x_hops, width F), a pair k = (a, b), op = GM_PROP_HADAMARD / GM_PROP_ABS_DIFF and
+ * the columns s_k of d_extra (device float [n, S], dense, S >= 0; NULL where S == 0):
+ *   z_k   = [ op(x_0[a], x_0[b]) | ... | op(x_hops[a], x_hops[b]) | s_k ]          K = (hops + 1) F + S;  op is the ONE fp32 operation of gm_prop_pair_features
+ *   h_k   = relu(z_k W1 + b1)                                                      W1 [K, Hd], in x out, row-major (the GraphConv convention)
+ *   l_k   = h_k . w2 + b2                                                          the logit
+ *   loss  = (1/n) sum_k  max(l_k, 0) - l_k y_k + log1p(exp(-|l_k|))                y_k in [0, 1]: d_labels, device float [n]
+ *   dl_k  = (sigmoid(l_k) - y_k) / n
+ *   dw2 = sum dl_k h_k,  db2 = sum dl_k,  dh_k = dl_k w2 [h_k > 0],  dW1 = sum z_k (x) dh_k,  db1 = sum dh_k
+ *   params       d_params and d_grad are ONE flat fp32 device buffer each, [W1 row-major | b1 | w2 | b2], n_params = K Hd + 2 Hd + 1 floats.
+ *   limits       1 <= Hd <= 256, 0 <= S <= 256, any F / hops the handle holds, 0 <= n <= INT32_MAX.  Sizes that are no multiple of a tile are padded inside the
+ *                kernels, never by the caller.  No gradient flows to the levels or to the structure columns: they are precomputed.
+ *   nodes        a pair with a node outside [0, N) has zeros for its level columns, as in gm_prop_pair_features (its structure columns still count).
+ *   arithmetic   every product carries both operands' full 24-bit significands (v_mfma_f32_32x32x2_f32: an fmaf chain per output); the sums are fp32.
+ *   exactness    l_k is bit for bit a function of (levels, a, b, op, s_k, params) alone, with (a, b) and (b, a) equal: not of n, of the pair's place in the call,
+ *                of the other pairs, of the stream, of pair_mlp_rows, and the same from gm_prop_pair_mlp_forward and gm_prop_pair_mlp_step -- a row's K order is
+ *                fixed by the tile code.  The loss and the gradients are sums over pairs without float atomics: partial sums of fixed row ranges added in
+ *                ascending order, the same bits for the same inputs and the same pair_mlp_rows.  gm_set_tuning("pair_mlp_rows", R) / GM_PAIR_MLP_ROWS: pairs
+ *                per chunk of a step (0 = the library's choice, 65536), which bounds the dh scratch (R rows of Hd padded to 64 floats) and is the ONLY thing
+ *                that may change the order of those sums, the role prop_chunk plays for the levels.
+ * gm_prop_pair_mlp_dims fills K and n_params (either may be NULL); gm_prop_pair_mlp_tile returns the pair tile T of the kernels (a workgroup scores T pairs).
+ * gm_prop_pair_mlp_forward stores the n logits.  gm_prop_pair_mlp_step stores the loss ([1]), the gradient ([n_params], OVERWRITTEN, never accumulated) and,
+ * where d_logits is not NULL, the logits; with n == 0 it stores loss 0 and a zero gradient.  Both run on `stream`, take their scratch from the stream-ordered pool
+ * and are complete in stream order; nothing outside [n] / [1] / [n_params] is written.
+ * GM_EINVAL (the message names the value) before any launch: a NULL handle, Hd outside 1 .. 256, S outside 0 .. 256, an unknown op, n negative or above INT32_MAX,
+ * a NULL argument with work to do (d_extra only where S > 0; d_logits of a step may be NULL), a negative pair_mlp_rows. */
+int32_t gm_prop_pair_mlp_dims(const gm_prop_t* p, int32_t S, int32_t Hd, int32_t* K, int64_t* n_params);
+int32_t gm_prop_pair_mlp_tile(void);
+int32_t gm_prop_pair_mlp_forward(const gm_prop_t* p, const int32_t* d_pairs, int64_t n, int32_t op, const float* d_extra /* [n, S] */, int32_t S, const float* d_params,
+                                 int32_t Hd, float* d_logits /* [n] */, void* stream);
+int32_t gm_prop_pair_mlp_step(const gm_prop_t* p, const int32_t* d_pairs, int64_t n, int32_t op, const float* d_extra /* [n, S] */, int32_t S, const float* d_labels /* [n] */,
+                              const float* d_params, int32_t Hd, float* d_logits /* [n], may be NULL */, float* d_loss /* [1] */, float* d_grad /* [n_params] */, void* stream);
+
 /* ---- Extraction: replaces Subgraphs.generate_subgraph / generate_subgraph_link_pred
  * (sdp.py:295-346: h-hop in-neighbour expansion, node sampling, G.subgraph) and dgl.batch
  * (sdp.py:399-406) for n_sets sets at once.  seeds/set_offsets are host arrays; set s owns seeds

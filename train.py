@@ -78,6 +78,10 @@ def parse(argv=None):
                     help='D in 1..254 (--link_pred_mode True): after the test evaluation and the --heuristics / --pagerank lines, print the ROC AUC of graph distance (the '
                          'shortest path of at most D edges, closer ranks higher: GraphStore.pair_distance) over the pairs of the test table; follows --mask_target, '
                          'independent of --heuristics and --pagerank; 0 = off')
+    ap.add_argument('--buddy', type=int, default=0,
+                    help='EPOCHS (--link_pred_mode True): after the test evaluation and the baseline lines, build the hop-propagated features (hops 2) and the '
+                         'neighbourhood sketches of every graph, fit a BUDDY pair predictor (gmeta_amd.PairPredictor: level products + sketch profile columns) on the '
+                         'pairs of the training table for EPOCHS epochs and print its ROC AUC over the pairs of the test table; 0 = off')
     ap.add_argument('--readout', default='centre', choices=['centre', 'mean'],
                     help="what the head reads of every subgraph: 'centre' = the centre row (both endpoints' rows of a pair), as the reference; 'mean' = the mean "
                          "over all of its rows (the dgl.mean_nodes line the reference left commented out), one pooled vector for pairs too")
@@ -99,6 +103,10 @@ def parse(argv=None):
         raise SystemExit('--distance %d: 1 .. 254 (the longest path searched), 0 = off' % a.distance)
     if a.distance and a.link_pred_mode != 'True':
         raise SystemExit('--distance %d scores node PAIRS: it needs --link_pred_mode True' % a.distance)
+    if a.buddy < 0:
+        raise SystemExit('--buddy %d: epochs of the pair predictor, 0 = off' % a.buddy)
+    if a.buddy and a.link_pred_mode != 'True':
+        raise SystemExit('--buddy %d trains a predictor of node PAIRS: it needs --link_pred_mode True' % a.buddy)
     return a
 
 
@@ -230,7 +238,31 @@ def main(args):
         res['distance_auc'] = gmeta_amd.link_distance_auc(store, names, labels, mask_target=bool(args.mask_target), max_dist=args.distance)
         if rank == 0:
             print('Distance test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['distance_auc'].items()))
+    if args.buddy:
+        from gmeta_amd.negatives import read_link_tables
+        both = tables if tables is not None else read_link_tables(root)
+        res['buddy_auc'] = buddy_auc(store, both['train'], both['test'], args.buddy)
+        if rank == 0:
+            print('BUDDY test AUC: %.4f' % res['buddy_auc'])
     return res
+
+
+def buddy_auc(store, train, test, epochs, hops=2):
+    """The two precomputed inputs of a BUDDY predictor for every graph (the levels of GraphStore.propagated_features and the sketches of GraphStore.sketches, both
+    at `hops`), a gmeta_amd.PairPredictor fitted on the (names, labels) of `train`, and its ROC AUC over those of `test`.  No mask_target: both inputs describe the
+    whole graph."""
+    graphs = range(store.n_graphs)
+    props = [store.propagated_features(g, hops=hops) for g in graphs]
+    sketches = [store.sketches(g, hops=hops) for g in graphs]
+    try:
+        columns = lambda names: gmeta_amd.sketch_profile_features(gmeta_amd.link_sketch_profiles(sketches, names))      # noqa: E731
+        x_train, x_test = columns(train[0]), columns(test[0])
+        model = gmeta_amd.PairPredictor(store.feat_dim, hops, extra_dim=x_train.shape[1], seed=222)
+        model.fit(props, train[0], train[1], extra=x_train, epochs=epochs)
+        return model.auc(props, test[0], test[1], extra=x_test)
+    finally:
+        for o in props + sketches:
+            o.close()
 
 
 def write_predictions(path, model, db, info):
