@@ -1,4 +1,5 @@
-// Single launches of the update GEMM, the dZ product and the weight gradient as gcn_forward / gcn_backward (model.hip) issue them.  Host code only.
+// Single launches of the update GEMM, the dZ product, the weight gradient and the aggregates as the step functions of gcn_forward / gcn_backward (model.hip) issue them: the
+// field groups those launches share come from model.hip's own builders (gm_internal.h), not from a restatement here.  Host code only.
 #include <algorithm>
 #include "gm_internal.h"
 
@@ -17,40 +18,48 @@ static int set_row_amax(const gm_batch* b, const float* x, int64_t ldx, int cols
     return rc;
 }
 
-// ================================================================================ dense update, exported for numerics tests
-extern "C" int gm_dense_update(const gm_batch_t* b, const float* x, int32_t K, const float* W, int64_t w_stride, int32_t N, float* out, int32_t mode,
-                               void* stream) {
-    GM_REQUIRE(b && x && W && out && K >= 1 && N >= 1, GM_EINVAL, "dense_update: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    gm_gemm_args g{};
-    g.A = x; g.lda = K; g.B = W; g.b_stride = w_stride; g.C = out; g.ldc = N; g.K = K; g.N = N;
-    g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows;
+// The scaffolding of the GEMM exports.  split: W (trans: stored [N, K] -- the planes are its own rows, as the dZ product's) as planes for the split kernels; np == 2: two
+// fp16 pieces per operand under bounds taken here -- of A over ax (per_set: one per set, over each set's rows as gm_dense_wgrad does, slots [0, sets); else one for all
+// of it, slot 0), then one per weight matrix.  The launch, the frees
+static int launch_gemm(const gm_batch* b, gm_gemm_args& g, bool split, const float* W, int64_t w_stride, int trans, int np, const float* ax, int64_t ldax, bool per_set,
+                       const char* who, hipStream_t st) {
     uint16_t* planes = nullptr; unsigned* slots = nullptr;
-    const bool split = mode == 1 || mode == 2 || (mode < 0 && gm_gemm_split_ok(b->n_tiles, K, N));
+    int rc = GM_OK;
     if (split) {
-        GM_REQUIRE((N == 256 || N == 128) && K % 16 == 0 && K >= 32, GM_EINVAL, "dense_update: the split kernels need N = 128 or 256 and K a multiple of 16 (>= 32)");
-        const int sets = w_stride ? b->sets : 1;
-        GM_TRY(gm_alloc(&planes, (size_t)sets * 3 * K * N, st));
-        int rc = GM_OK;
+        const int K = g.K, N = g.N, wsets = w_stride ? b->sets : 1, na = per_set ? b->sets : 1;
+        rc = gm_alloc(&planes, (size_t)wsets * 3 * K * N, st);
         gm_bound wb = gm_no_bound();
-        if (mode == 2) {
-            // two fp16 pieces per operand: bounds taken here -- one for all of x (slot 0), one per weight matrix (slots 1..)
-            rc = gm_alloc(&slots, (size_t)(sets + 1) * GM_BOUND_PAD, st);
-            if (rc == GM_OK && hipMemsetAsync(slots, 0, sizeof(unsigned) * (sets + 1) * GM_BOUND_PAD, st) != hipSuccess) { gm_set_error("dense_update: memset failed"); rc = GM_EHIP; }
-            if (rc == GM_OK) rc = gm_amax(x, 0, 0, (int64_t)b->rows * K, 1, slots, 0, st);
-            if (rc == GM_OK) rc = gm_amax(W, w_stride, 0, (int64_t)K * N, sets, slots + GM_BOUND_PAD, GM_BOUND_PAD, st);
-            wb.amax = slots + GM_BOUND_PAD; wb.stride = w_stride ? GM_BOUND_PAD : 0;
-            g.np = 2; g.a_bound = gm_no_bound(); g.a_bound.amax = slots; g.b_bound = wb;
+        if (rc == GM_OK && np == 2) {
+            rc = gm_alloc(&slots, (size_t)(na + wsets) * GM_BOUND_PAD, st);
+            if (rc == GM_OK && hipMemsetAsync(slots, 0, sizeof(unsigned) * (na + wsets) * GM_BOUND_PAD, st) != hipSuccess) { gm_set_error("%s: memset failed", who); rc = GM_EHIP; }
+            if (rc == GM_OK) rc = per_set ? set_row_amax(b, ax, ldax, K, slots, st) : gm_amax(ax, 0, 0, (int64_t)b->rows * K, 1, slots, 0, st);
+            if (rc == GM_OK) rc = gm_amax(W, w_stride, 0, (int64_t)K * N, wsets, slots + (int64_t)na * GM_BOUND_PAD, GM_BOUND_PAD, st);
+            wb.amax = slots + (int64_t)na * GM_BOUND_PAD; wb.stride = w_stride ? GM_BOUND_PAD : 0;
+            g.np = 2; g.a_bound = gm_no_bound(); g.a_bound.amax = slots; g.a_bound.stride = per_set ? GM_BOUND_PAD : 0; g.b_bound = wb;
         }
-        if (rc == GM_OK) rc = gm_split_weights(W, w_stride, 0, K, N, 0, sets, planes, st, mode == 2 ? 2 : 3, wb);
-        if (rc != GM_OK) { gm_dev_free(planes, st); if (slots) gm_dev_free(slots, st); return rc; }
+        if (rc == GM_OK) rc = gm_split_weights(W, w_stride, 0, K, N, trans, wsets, planes, st, np, wb);
         g.Bsplit = planes; g.bsplit_stride = w_stride ? (int64_t)3 * K * N : 0;
     }
-    const int rc = gm_launch_gemm_nn(g, st);
+    if (rc == GM_OK) rc = gm_launch_gemm_nn(g, st);
     if (planes) gm_dev_free(planes, st);
     if (slots) gm_dev_free(slots, st);
     gm_batch_mark_use(b, st);
     return rc;
+}
+// the batch's rows under the export's own row scale
+static LevelView scaled_level(const gm_batch* b, const float* s) { LevelView v = batch_level(b); v.norm = s; return v; }
+
+// ================================================================================ dense update, exported for numerics tests
+extern "C" int gm_dense_update(const gm_batch_t* b, const float* x, int32_t K, const float* W, int64_t w_stride, int32_t N, float* out, int32_t mode,
+                               void* stream) {
+    GM_REQUIRE(b && x && W && out && K >= 1 && N >= 1, GM_EINVAL, "dense_update: bad arguments");
+    gm_gemm_args g{};
+    g.A = x; g.lda = K; g.B = W; g.b_stride = w_stride; g.C = out; g.ldc = N; g.K = K; g.N = N;
+    gemm_rows(g, scaled_level(b, nullptr));
+    const bool split = mode == 1 || mode == 2 || (mode < 0 && gm_gemm_split_ok(b->n_tiles, K, N));
+    if (split) GM_REQUIRE((N == 256 || N == 128) && K % 16 == 0 && K >= 32, GM_EINVAL, "dense_update: the split kernels need N = 128 or 256 and K a multiple of 16 (>= 32)");
+    // mode 2: one bound for all of x, one per weight matrix
+    return launch_gemm(b, g, split, W, w_stride, 0, mode == 2 ? 2 : 3, x, K, false, "dense_update", (hipStream_t)stream);
 }
 
 // The same product with every field of gm_gemm_args that the forward and dZ GEMMs set: the epilogue options, a transposed W, strides, the
@@ -62,47 +71,25 @@ extern "C" int gm_dense_gemm(const gm_batch_t* b, const float* x, int64_t ldx, i
     GM_REQUIRE(b && x && W && out && K >= 1 && N >= 1 && ldx >= K && ldc >= N && mode >= -1 && mode <= 2 && !(mask_h && mask_b), GM_EINVAL,
                "dense_gemm: bad arguments");
     GM_REQUIRE(!amax_out || mode == 2, GM_EINVAL, "dense_gemm: amax_out is an output of the two-piece kernels (mode 2)");
-    hipStream_t st = (hipStream_t)stream;
-    const int sets = b->sets;
     gm_gemm_args g{};
     g.A = x; g.lda = ldx; g.B = W; g.b_stride = w_stride; g.transB = trans_w ? 1 : 0; g.C = out; g.ldc = ldc; g.K = K; g.N = N;
-    g.row_scale = s; g.row_scale_keep = s_keep; g.n_keep = b->rows; g.bias = bias; g.bias_stride = bias_stride; g.relu = relu ? 1 : 0;
-    g.relu_bits = relu_bits; g.mask_h = mask_h; g.mask_b = mask_b; g.zero_out = zero_out;
-    g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows; g.launched = launched;
-    uint16_t* planes = nullptr; unsigned* slots = nullptr;
-    int rc = GM_OK;
-    if (mode == 1 || mode == 2 || (mode < 0 && gm_gemm_split_ok(b->n_tiles, K, N))) {
+    gemm_rows(g, scaled_level(b, s));
+    gemm_keep_rows(g, RowView{s_keep}, s_keep != nullptr, false, b->rows);      // the caller's own keep vector
+    g.bias = bias; g.bias_stride = bias_stride; g.relu = relu ? 1 : 0;
+    g.relu_bits = relu_bits; g.mask_h = mask_h; g.mask_b = mask_b; g.zero_out = zero_out; g.amax_out = amax_out; g.launched = launched;
+    const bool split = mode == 1 || mode == 2 || (mode < 0 && gm_gemm_split_ok(b->n_tiles, K, N));
+    if (split) {
         GM_REQUIRE(!mask_h && !mask_b, GM_EINVAL, "dense_gemm: the split kernels take no relu' mask");
         GM_REQUIRE((N == 256 || N == 128) && K % 16 == 0 && K >= 32, GM_EINVAL, "dense_gemm: the split kernels need N = 128 or 256 and K a multiple of 16 (>= 32)");
-        const int wsets = w_stride ? sets : 1;
-        rc = gm_alloc(&planes, (size_t)wsets * 3 * K * N, st);
-        gm_bound wb = gm_no_bound();
-        if (rc == GM_OK && mode == 2) {
-            // two fp16 pieces per operand: per-set bounds of x (slots [0, sets)), taken over each set's rows as gm_dense_wgrad does, and one per
-            // weight matrix (slots [sets, sets + wsets))
-            rc = gm_alloc(&slots, (size_t)(sets + wsets) * GM_BOUND_PAD, st);
-            if (rc == GM_OK && hipMemsetAsync(slots, 0, sizeof(unsigned) * (sets + wsets) * GM_BOUND_PAD, st) != hipSuccess) { gm_set_error("dense_gemm: memset failed"); rc = GM_EHIP; }
-            if (rc == GM_OK) rc = set_row_amax(b, x, ldx, K, slots, st);
-            if (rc == GM_OK) rc = gm_amax(W, w_stride, 0, (int64_t)K * N, wsets, slots + (int64_t)sets * GM_BOUND_PAD, GM_BOUND_PAD, st);
-            wb.amax = slots + (int64_t)sets * GM_BOUND_PAD; wb.stride = w_stride ? GM_BOUND_PAD : 0;
-            g.np = 2; g.a_bound = gm_no_bound(); g.a_bound.amax = slots; g.a_bound.stride = GM_BOUND_PAD; g.b_bound = wb; g.amax_out = amax_out;
-        }
-        // trans_w: W stored [N, K] -- the planes are its own rows (as the dZ product's)
-        if (rc == GM_OK) rc = gm_split_weights(W, w_stride, 0, K, N, trans_w ? 1 : 0, wsets, planes, st, mode == 2 ? 2 : 3, wb);
-        g.Bsplit = planes; g.bsplit_stride = w_stride ? (int64_t)3 * K * N : 0;
     }
-    if (rc == GM_OK) rc = gm_launch_gemm_nn(g, st);
-    if (planes) gm_dev_free(planes, st);
-    if (slots) gm_dev_free(slots, st);
-    gm_batch_mark_use(b, st);
-    return rc;
+    return launch_gemm(b, g, split, W, w_stride, trans_w ? 1 : 0, mode == 2 ? 2 : 3, x, ldx, true, "dense_gemm", (hipStream_t)stream);
 }
 
-// The fused aggregate + GEMM as gcn_forward's `fuse` branch launches it: gm_dense_gemm with gm_gemm_args::fuse2 set.  The table is always the batch's own
+// The fused aggregate + GEMM as fwd_update (model.hip) launches a fused layer: gm_dense_gemm with gm_gemm_args::fuse2 set.  The table is always the batch's own
 // (table 0: d_fuse2 over the caller's x; 1: d_fuse2_feat over the batch's feature table), so the kernel reads no row outside its operands
-// rowset -1: the batch's full tables (gm_dense_fused_gemm).  0 / 1 (gm_dense_fused_gemm_rows): the tables of the centre rows / of the sources of their in-edges, with
-// live_on the set's tile flags (gm_batch::d_tile_live), grid workgroups (0: the production rule)
-static int dense_fused_gemm(const gm_batch_t* b, int32_t rowset, int32_t live_on, int32_t grid, int32_t table, const float* x, int64_t ldx, int32_t K, const float* zside, int64_t ldz,
+// rowset -1: the batch's full tables (gm_dense_fused_gemm; s_keep: the caller's keep vector).  0 / 1 (gm_dense_fused_gemm_rows): the tables of the centre rows / of the
+// sources of their in-edges through row_view, keep: the set's keep vector, live_on: its tile flags, grid workgroups (0: the production rule)
+static int dense_fused_gemm(const gm_batch_t* b, int32_t rowset, int32_t keep, int32_t live_on, int32_t grid, int32_t table, const float* x, int64_t ldx, int32_t K, const float* zside, int64_t ldz,
                             const float* zfull, int64_t ldzf, const float* W, int64_t w_stride, int32_t N, float* out, int64_t ldc, const float* s,
                             const float* s_keep, const float* bias, int64_t bias_stride, int32_t relu, uint8_t* relu_bits, float* zero_out,
                             uint32_t* amax_out, int32_t mode, int32_t* launched, void* stream) {
@@ -114,50 +101,33 @@ static int dense_fused_gemm(const gm_batch_t* b, int32_t rowset, int32_t live_on
     GM_REQUIRE(!amax_out || mode == 2, GM_EINVAL, "dense_fused_gemm: amax_out is an output of the two-piece kernels (mode 2)");
     GM_REQUIRE(mode != 2 || (zfull && ldzf >= K), GM_EINVAL, "dense_fused_gemm: mode 2 takes its A bounds over a fully aggregated Z (zfull)");
     GM_REQUIRE((N == 256 || N == 128) && K % 16 == 0 && K >= 32, GM_EINVAL, "dense_fused_gemm: the split kernels need N = 128 or 256 and K a multiple of 16 (>= 32)");
-    hipStream_t st = (hipStream_t)stream;
-    const int sets = b->sets, wsets = w_stride ? sets : 1;
     gm_gemm_args g{};
     g.B = W; g.b_stride = w_stride; g.C = out; g.ldc = ldc; g.K = K; g.N = N;
-    g.row_scale = s; g.row_scale_keep = s_keep; g.n_keep = b->rows; g.bias = bias; g.bias_stride = bias_stride; g.relu = relu ? 1 : 0;
-    g.relu_bits = relu_bits; g.zero_out = zero_out;
-    g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows; g.launched = launched;
+    gemm_rows(g, scaled_level(b, s));
+    gemm_keep_rows(g, RowView{s_keep}, s_keep != nullptr, false, b->rows);      // the caller's own keep vector
+    g.bias = bias; g.bias_stride = bias_stride; g.relu = relu ? 1 : 0;
+    g.relu_bits = relu_bits; g.zero_out = zero_out; g.amax_out = amax_out; g.launched = launched;
     g.zside = zside; g.ldz = ldz;
-    if (table == 1) { g.A = b->feat; g.lda = b->feat_ld; g.fuse2 = b->d_fuse2_feat; }
-    else { g.A = x; g.lda = ldx; g.fuse2 = b->d_fuse2; }
+    if (table == 1) { g.A = b->feat; g.lda = b->feat_ld; } else { g.A = x; g.lda = ldx; }
+    RowSet rs = ROWS_ALL;
     if (rowset >= 0) {
         GM_REQUIRE(rowset <= 1 && !(rowset == 0 && table == 1) && grid >= 0, GM_EINVAL, "dense_fused_gemm_rows: bad row set");
         GM_REQUIRE(b->d_fwd_tab[0] && b->d_fwd_tab[1] && b->d_fwd_tab_feat && b->d_tile_live[0] && b->d_tile_live[1], GM_EINVAL, "dense_fused_gemm_rows: the batch carries no row-set tables");
-        g.fuse2 = rowset == 0 ? b->d_fwd_tab[0] : table == 1 ? b->d_fwd_tab_feat : b->d_fwd_tab[1];
-        if (live_on) g.tile_live = b->d_tile_live[rowset];
+        rs = rowset == 0 ? ROWS_CENTRE : ROWS_E1;
+        gemm_keep_rows(g, row_view(b, rs, false), keep != 0, live_on != 0, b->rows);
         g.grid_test = grid;
     }
-    uint16_t* planes = nullptr; unsigned* slots = nullptr;
-    int rc = gm_alloc(&planes, (size_t)wsets * 3 * K * N, st);
-    gm_bound wb = gm_no_bound();
-    if (rc == GM_OK && mode == 2) {
-        // per-set bounds of the rows the kernel forms (slots [0, sets)), taken over the caller's fully aggregated Z -- never over zside, whose rows of one or
-        // two sources nobody wrote --, and one per weight matrix (slots [sets, sets + wsets)): gm_dense_gemm's over a stored Z
-        rc = gm_alloc(&slots, (size_t)(sets + wsets) * GM_BOUND_PAD, st);
-        if (rc == GM_OK && hipMemsetAsync(slots, 0, sizeof(unsigned) * (sets + wsets) * GM_BOUND_PAD, st) != hipSuccess) { gm_set_error("dense_fused_gemm: memset failed"); rc = GM_EHIP; }
-        if (rc == GM_OK) rc = set_row_amax(b, zfull, ldzf, K, slots, st);
-        if (rc == GM_OK) rc = gm_amax(W, w_stride, 0, (int64_t)K * N, wsets, slots + (int64_t)sets * GM_BOUND_PAD, GM_BOUND_PAD, st);
-        wb.amax = slots + (int64_t)sets * GM_BOUND_PAD; wb.stride = w_stride ? GM_BOUND_PAD : 0;
-        g.np = 2; g.a_bound = gm_no_bound(); g.a_bound.amax = slots; g.a_bound.stride = GM_BOUND_PAD; g.b_bound = wb; g.amax_out = amax_out;
-    }
-    if (rc == GM_OK) rc = gm_split_weights(W, w_stride, 0, K, N, 0, wsets, planes, st, mode == 2 ? 2 : 3, wb);
-    g.Bsplit = planes; g.bsplit_stride = w_stride ? (int64_t)3 * K * N : 0;
-    if (rc == GM_OK) rc = gm_launch_gemm_nn(g, st);
-    if (planes) gm_dev_free(planes, st);
-    if (slots) gm_dev_free(slots, st);
-    gm_batch_mark_use(b, st);
-    return rc;
+    g.fuse2 = row_view(b, rs, table == 1).tab;
+    // mode 2: per-set bounds of the rows the kernel forms, taken over the caller's fully aggregated Z -- never over zside, whose rows of one or two sources nobody
+    // wrote --, and one per weight matrix: gm_dense_gemm's over a stored Z
+    return launch_gemm(b, g, true, W, w_stride, 0, mode == 2 ? 2 : 3, zfull, ldzf, true, "dense_fused_gemm", (hipStream_t)stream);
 }
 
 extern "C" int gm_dense_fused_gemm(const gm_batch_t* b, int32_t table, const float* x, int64_t ldx, int32_t K, const float* zside, int64_t ldz,
                                    const float* zfull, int64_t ldzf, const float* W, int64_t w_stride, int32_t N, float* out, int64_t ldc, const float* s,
                                    const float* s_keep, const float* bias, int64_t bias_stride, int32_t relu, uint8_t* relu_bits, float* zero_out,
                                    uint32_t* amax_out, int32_t mode, int32_t* launched, void* stream) {
-    return dense_fused_gemm(b, -1, 0, 0, table, x, ldx, K, zside, ldz, zfull, ldzf, W, w_stride, N, out, ldc, s, s_keep, bias, bias_stride, relu, relu_bits, zero_out, amax_out,
+    return dense_fused_gemm(b, -1, 0, 0, 0, table, x, ldx, K, zside, ldz, zfull, ldzf, W, w_stride, N, out, ldc, s, s_keep, bias, bias_stride, relu, relu_bits, zero_out, amax_out,
                             mode, launched, stream);
 }
 // ... over the table of a row set, as the restricted forward-only layers launch it (GM_DEAD_ROWS=3, GM_DEAD_TILES; tests): rowset 0 the centre rows (gm_batch::d_fwd_tab[0],
@@ -168,80 +138,68 @@ extern "C" int gm_dense_fused_gemm_rows(const gm_batch_t* b, int32_t rowset, int
                                         const float* bias, int64_t bias_stride, int32_t relu, uint8_t* relu_bits, float* zero_out, uint32_t* amax_out, int32_t mode,
                                         int32_t* launched, void* stream) {
     GM_REQUIRE(b && (rowset == 0 || rowset == 1) && b->d_norm_c && b->d_norm_e1, GM_EINVAL, "dense_fused_gemm_rows: bad arguments");
-    return dense_fused_gemm(b, rowset, live_on, grid, table, x, ldx, K, zside, ldz, zfull, ldzf, W, w_stride, N, out, ldc, b->d_norm, keep ? (rowset == 0 ? b->d_norm_c : b->d_norm_e1) : nullptr,
+    return dense_fused_gemm(b, rowset, keep, live_on, grid, table, x, ldx, K, zside, ldz, zfull, ldzf, W, w_stride, N, out, ldc, b->d_norm, nullptr,
                             bias, bias_stride, relu, relu_bits, zero_out, amax_out, mode, launched, stream);
 }
 
-// The dZ product of the last layer over a dQ that holds its centre rows only, as gcn_backward launches it under GM_DEAD_ROWS (tests)
+// The dZ product of the last layer over a dQ that holds its centre rows only, as bwd_dz (model.hip) launches it under GM_DEAD_ROWS (tests)
 extern "C" int gm_dense_dz_centre(const gm_batch_t* b, const float* dQ, int32_t K, const float* W, int64_t w_stride, int32_t N, float* T, void* stream) {
     GM_REQUIRE(b && dQ && W && T && b->d_dq_tab, GM_EINVAL, "dense_dz_centre: bad arguments");
     GM_REQUIRE((N == 256 || N == 128) && K % 16 == 0 && K >= 64, GM_EINVAL, "dense_dz_centre: the fused split kernel needs N = 128 or 256 and K a multiple of 16 (>= 64)");
-    hipStream_t st = (hipStream_t)stream;
-    const int wsets = w_stride ? b->sets : 1;
-    uint16_t* planes = nullptr;
-    GM_TRY(gm_alloc(&planes, (size_t)wsets * 3 * K * N, st));
     gm_gemm_args g{};
-    g.A = dQ; g.lda = K; g.B = W; g.b_stride = w_stride; g.transB = 1; g.C = T; g.ldc = N; g.K = K; g.N = N;
-    g.row_scale = b->d_norm; g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows;
-    g.fuse2 = b->d_dq_tab; g.zside = dQ; g.ldz = K;
-    int rc = gm_split_weights(W, w_stride, 0, K, N, 1, wsets, planes, st, 3, gm_no_bound());
-    g.Bsplit = planes; g.bsplit_stride = w_stride ? (int64_t)3 * K * N : 0; g.np = 3;
-    if (rc == GM_OK) rc = gm_launch_gemm_nn(g, st);
-    gm_dev_free(planes, st);
-    gm_batch_mark_use(b, st);
-    return rc;
-}
-// ... and its weight gradient (keep: the flagged row scale that says which rows of dQ were written)
-static int dense_wgrad_keep(const gm_batch_t* b, const float* keep, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
-                            int64_t db_stride, void* stream) {
-    GM_REQUIRE(b && x && dQ && dW && db && keep, GM_EINVAL, "dense_wgrad_centre / _e1: bad arguments");
-    const int64_t KN = (int64_t)Kx * N;
-    GM_REQUIRE(b->sets == 1 || (dw_stride >= KN && db_stride >= N), GM_EINVAL, "dense_wgrad_centre / _e1: per-set outputs overlap");
-    hipStream_t st = (hipStream_t)stream;
-    gm_wgrad_args w{};
-    w.A = x; w.lda = Kx; w.K = Kx; w.G = dQ; w.ldg = N; w.N = N; w.a_scale = b->d_norm; w.g_keep = keep;
-    w.chunks = b->d_chunks; w.n_chunks = b->n_chunks; w.set_chunk_off = b->d_set_chunk_off; w.sets = b->sets; w.rows = b->rows;
-    w.dW = dW; w.dw_stride = dw_stride; w.db = db; w.db_stride = db_stride; w.pick = GM_WGRAD_PICK_SPLIT;
-    int rc = gm_alloc(&w.partial, (size_t)std::max(1, b->n_chunks) * (size_t)(KN + N), st);
-    if (rc == GM_OK) rc = gm_launch_wgrad(w, st);
-    if (w.partial) gm_dev_free(w.partial, st);
-    gm_batch_mark_use(b, st);
-    return rc;
-}
-extern "C" int gm_dense_wgrad_centre(const gm_batch_t* b, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
-                                     int64_t db_stride, void* stream) {
-    return dense_wgrad_keep(b, b ? b->d_norm_c : nullptr, x, Kx, dQ, N, dW, dw_stride, db, db_stride, stream);
+    g.A = dQ; g.lda = K; g.B = W; g.b_stride = w_stride; g.transB = 1; g.C = T; g.ldc = N; g.K = K; g.N = N; g.np = 3;
+    gemm_rows(g, batch_level(b)); gemm_dq_table(g, b, dQ, K);
+    return launch_gemm(b, g, true, W, w_stride, 1, 3, nullptr, 0, false, "dense_dz_centre", (hipStream_t)stream);
 }
 
-// GM_DEAD_ROWS=2 (tests): the last layer's transposed aggregate dQ_prev = relu' norm A^T T as gcn_backward launches it.  keep != 0: T read through the batch's
+// GM_DEAD_ROWS=2 (tests): the last layer's transposed aggregate dQ_prev = relu' norm A^T T as bwd_agg_t (model.hip) launches it.  keep != 0: T read through the batch's
 // per-edge table (gm_batch::d_ect; T holds rows + 1 rows, the last one zeroed HERE) and only the rows gm_batch::d_norm_e1 keeps stored; keep == 0: the plain
 // launch, every row of T read and every row of `out` stored.  mask_b: packed relu' bits [rows * width / 4], or NULL
 extern "C" int gm_dense_agg_centre_t(const gm_batch_t* b, float* T, int32_t width, const uint8_t* mask_b, float* out, int32_t keep, void* stream) {
     GM_REQUIRE(b && T && out && width >= 4 && width % 4 == 0, GM_EINVAL, "dense_agg_centre_t: bad arguments");
     GM_REQUIRE(!keep || (b->d_ect && b->d_norm_e1), GM_EINVAL, "dense_agg_centre_t: the batch carries no centre-edge tables");
     hipStream_t st = (hipStream_t)stream;
-    gm_agg_args a{};
-    a.indptr = b->d_indptr_t; a.indices = b->d_indices_t;
-    a.heavy = b->d_heavy[1]; a.n_heavy = b->n_heavy[1]; a.heavy_deg = b->heavy_deg;
-    a.sched = b->d_sched[1]; a.sched_len = b->sched_len[1]; a.sched_win = b->sched_win;
-    GM_TRY(gm_agg_hub(a, b, 1, st));
-    if (b->weighted) a.e_w = b->d_ew[1];
-    a.rows = b->rows; a.x = T; a.ldx = width; a.s_out = b->d_norm; a.mask_b = mask_b; a.out = out; a.width = width;
+    gm_agg_args a; GM_TRY(batch_agg(b, 1, 0, st, a));
+    a.x = T; a.ldx = width; a.s_out = b->d_norm; a.mask_b = mask_b; a.out = out; a.width = width;
     if (keep) {
         GM_HIP(hipMemsetAsync(T + b->rows * (int64_t)width, 0, sizeof(float) * GM_ZERO_ROWS * width, st));
-        a.x_idx = b->d_ect; a.s_out = b->d_norm_e1; a.keep_signed = 1;
+        agg_centre_t(a, b, ROWS_E1);
     }
     const int rc = gm_launch_aggregate(a, st);
     gm_batch_mark_use(b, st);
     return rc;
 }
-// ... and the weight gradient of the layer below over that dQ_prev: rows gm_batch::d_norm_e1 flags enter as zeros, whatever their bytes hold
-extern "C" int gm_dense_wgrad_e1(const gm_batch_t* b, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
-                                 int64_t db_stride, void* stream) {
-    return dense_wgrad_keep(b, b ? b->d_norm_e1 : nullptr, x, Kx, dQ, N, dW, dw_stride, db, db_stride, stream);
-}
 
 // ================================================================================ weight gradient, exported for numerics tests
+// The scaffolding of the weight-gradient exports over rows v (the batch's; the export's own row scale): the partials; np == 2: two fp16 pieces per operand, marked by
+// per-set bound slots of A (slots [0, sets)) and of G (slots [sets, 2 sets)) -- bounds: taken here over each set's rows (with the padding between them), and ONE bound
+// of |a_scale| over all rows (slot 2 sets) as the gain of A's: |s x| <= max_t |x| * max |s|; else left zero (the launcher refuses two pieces with a table before any bound
+// is read).  The launch, the frees
+static int launch_wgrad(const gm_batch* b, gm_wgrad_args& w, const LevelView& v, int np, bool bounds, const char* who, hipStream_t st) {
+    const int sets = b->sets;
+    wgrad_rows(w, v);
+    unsigned* slots = nullptr;
+    int rc = gm_alloc(&w.partial, (size_t)std::max(1, b->n_chunks) * (size_t)((int64_t)w.K * w.N + w.N), st);
+    if (rc == GM_OK && np == 2) {
+        unsigned* sg = nullptr; unsigned* ss = nullptr;
+        rc = gm_alloc(&slots, (size_t)(2 * sets + 1) * GM_BOUND_PAD, st);
+        if (rc == GM_OK) { sg = slots + (int64_t)sets * GM_BOUND_PAD; ss = slots + (int64_t)2 * sets * GM_BOUND_PAD; }
+        if (rc == GM_OK && hipMemsetAsync(slots, 0, sizeof(unsigned) * (2 * sets + 1) * GM_BOUND_PAD, st) != hipSuccess) { gm_set_error("%s: memset failed", who); rc = GM_EHIP; }
+        if (rc == GM_OK && bounds) rc = set_row_amax(b, w.A, w.lda, w.K, slots, st);
+        if (rc == GM_OK && bounds) rc = set_row_amax(b, w.G, w.ldg, w.N, sg, st);
+        if (rc == GM_OK && bounds && w.a_scale) rc = gm_amax(w.a_scale, 0, 0, b->rows, 1, ss, 0, st);
+        w.np = 2;
+        w.a_bound = gm_no_bound(); w.a_bound.amax = slots; w.a_bound.stride = GM_BOUND_PAD;
+        if (bounds && w.a_scale) w.a_bound.gain = reinterpret_cast<const float*>(ss);     // (an amax slot holds fp32 bits)
+        w.g_bound = gm_no_bound(); w.g_bound.amax = sg; w.g_bound.stride = GM_BOUND_PAD;
+    }
+    if (rc == GM_OK) rc = gm_launch_wgrad(w, st);
+    if (w.partial) gm_dev_free(w.partial, st);
+    if (slots) gm_dev_free(slots, st);
+    gm_batch_mark_use(b, st);
+    return rc;
+}
+
 extern "C" int gm_dense_wgrad(const gm_batch_t* b, const float* x, int64_t ldx, int32_t K, const float* g, int64_t ldg, int32_t N, const float* s,
                               const float* gb, int64_t ldgb, float* dW, int64_t dw_stride, float* db, int64_t db_stride, int32_t mode,
                               const float* cur, float* next, int64_t p_stride, float lr, float* wt, uint16_t* pl_fwd, uint16_t* pl_dz, void* stream) {
@@ -255,40 +213,19 @@ extern "C" int gm_dense_wgrad(const gm_batch_t* b, const float* x, int64_t ldx, 
     GM_REQUIRE(!next || (cur && db && (sets == 1 || p_stride >= KN + N)), GM_EINVAL, "dense_wgrad: the SGD step needs cur, db and a stride of at least (K+1)*N");
     GM_REQUIRE((!wt && !pl_fwd && !pl_dz) || next, GM_EINVAL, "dense_wgrad: wt and the planes are outputs of the SGD step");
     GM_REQUIRE((!pl_fwd && !pl_dz) || (K % 32 == 0 && N % 32 == 0), GM_EINVAL, "dense_wgrad: weight planes need K and N multiples of 32");
-    hipStream_t st = (hipStream_t)stream;
     gm_wgrad_args w{};
-    w.A = x; w.lda = ldx; w.K = K; w.G = g; w.ldg = ldg; w.N = N; w.Gb = gb; w.ldgb = ldgb; w.a_scale = s;
-    w.chunks = b->d_chunks; w.n_chunks = b->n_chunks; w.set_chunk_off = b->d_set_chunk_off; w.sets = sets; w.rows = b->rows;
+    w.A = x; w.lda = ldx; w.K = K; w.G = g; w.ldg = ldg; w.N = N; w.Gb = gb; w.ldgb = ldgb;
     w.dW = dW; w.dw_stride = dw_stride; w.db = db; w.db_stride = db_stride;
     if (next) {
         w.sgd_cur = cur; w.sgd_cur_stride = p_stride; w.sgd_next = next; w.sgd_next_stride = p_stride; w.sgd_lr = lr; w.w_off = 0; w.b_off = KN;
         w.wt_next = wt; w.pl_fwd = pl_fwd; w.pl_dz = pl_dz;
     }
     w.pick = mode == 0 ? GM_WGRAD_PICK_EXACT : mode > 0 ? GM_WGRAD_PICK_SPLIT : 0;
-    unsigned* slots = nullptr;
-    int rc = gm_alloc(&w.partial, (size_t)std::max(1, b->n_chunks) * (size_t)(KN + N), st);
-    if (rc == GM_OK && mode == 2) {
-        // two fp16 pieces per operand: per-set bounds of x (slots [0, sets)) and of g (slots [sets, 2 sets)), taken over each set's rows (with
-        // the padding between them), and ONE bound of |s| over all rows (slot 2 sets) as the gain of x's: |s x| <= max_t |x| * max |s|
-        rc = gm_alloc(&slots, (size_t)(2 * sets + 1) * GM_BOUND_PAD, st);
-        if (rc == GM_OK && hipMemsetAsync(slots, 0, sizeof(unsigned) * (2 * sets + 1) * GM_BOUND_PAD, st) != hipSuccess) { gm_set_error("dense_wgrad: memset failed"); rc = GM_EHIP; }
-        if (rc == GM_OK) rc = set_row_amax(b, x, ldx, K, slots, st);
-        if (rc == GM_OK) rc = set_row_amax(b, g, ldg, N, slots + (int64_t)sets * GM_BOUND_PAD, st);
-        if (rc == GM_OK && s) rc = gm_amax(s, 0, 0, b->rows, 1, slots + (int64_t)2 * sets * GM_BOUND_PAD, 0, st);
-        w.np = 2;
-        w.a_bound = gm_no_bound(); w.a_bound.amax = slots; w.a_bound.stride = GM_BOUND_PAD;
-        if (s) w.a_bound.gain = reinterpret_cast<const float*>(slots + (int64_t)2 * sets * GM_BOUND_PAD);     // (an amax slot holds fp32 bits)
-        w.g_bound = gm_no_bound(); w.g_bound.amax = slots + (int64_t)sets * GM_BOUND_PAD; w.g_bound.stride = GM_BOUND_PAD;
-    }
-    if (rc == GM_OK) rc = gm_launch_wgrad(w, st);
-    if (w.partial) gm_dev_free(w.partial, st);
-    if (slots) gm_dev_free(slots, st);
-    gm_batch_mark_use(b, st);
-    return rc;
+    return launch_wgrad(b, w, scaled_level(b, s), mode == 2 ? 2 : 3, true, "dense_wgrad", (hipStream_t)stream);
 }
 
-// The weight gradient over a Z whose forward ran fused, as gcn_backward launches it for a fused layer (LayerPlan::fuse): A holds the rows the table flags GM_FUSE_SELF, every other
-// row is formed from gx through the batch's own table (table 0: d_fuse2 over the caller's gx; 1: d_fuse2_feat over the batch's feature table)
+// The weight gradient over a Z whose forward ran fused, as bwd_wgrad_operands (model.hip) sets it up for a fused layer (LayerPlan::fuse): A holds the rows the table flags
+// GM_FUSE_SELF, every other row is formed from gx through the batch's own table (table 0: d_fuse2 over the caller's gx; 1: d_fuse2_feat over the batch's feature table)
 extern "C" int gm_dense_wgrad_fused(const gm_batch_t* b, int32_t table, const float* A, int64_t lda, int32_t K, const float* gx, int64_t ldgx, const float* g,
                                     int64_t ldg, int32_t N, const float* s, const float* g_keep, float* dW, int64_t dw_stride, float* db, int64_t db_stride,
                                     int32_t mode, void* stream) {
@@ -298,37 +235,39 @@ extern "C" int gm_dense_wgrad_fused(const gm_batch_t* b, int32_t table, const fl
     GM_REQUIRE(b->d_fuse2 && b->d_fuse2_feat, GM_EINVAL, "dense_wgrad_fused: the batch carries no source tables");
     GM_REQUIRE(table == 1 || (gx && ldgx >= K), GM_EINVAL, "dense_wgrad_fused: table 0 needs gx and ldgx >= K");
     GM_REQUIRE(table == 0 || (b->feat && (K == b->feat_dim || K == b->feat_ld)), GM_EINVAL, "dense_wgrad_fused: table 1 needs K == feat_dim (%d)", b->feat_dim);
-    const int sets = b->sets;
-    const int64_t KN = (int64_t)K * N;
-    GM_REQUIRE(sets == 1 || (dw_stride >= KN && db_stride >= N), GM_EINVAL, "dense_wgrad_fused: per-set outputs overlap");
-    hipStream_t st = (hipStream_t)stream;
+    GM_REQUIRE(b->sets == 1 || (dw_stride >= (int64_t)K * N && db_stride >= N), GM_EINVAL, "dense_wgrad_fused: per-set outputs overlap");
     gm_wgrad_args w{};
-    w.A = A; w.lda = lda; w.K = K; w.G = g; w.ldg = ldg; w.N = N; w.a_scale = s; w.g_keep = g_keep;
-    w.chunks = b->d_chunks; w.n_chunks = b->n_chunks; w.set_chunk_off = b->d_set_chunk_off; w.sets = sets; w.rows = b->rows;
+    w.A = A; w.lda = lda; w.K = K; w.G = g; w.ldg = ldg; w.N = N; w.g_keep = g_keep;
     w.dW = dW; w.dw_stride = dw_stride; w.db = db; w.db_stride = db_stride;
-    w.fuse2 = table == 1 ? b->d_fuse2_feat : b->d_fuse2;
+    w.fuse2 = row_view(b, ROWS_ALL, table == 1).tab;
     w.gx = table == 1 ? b->feat : gx; w.ldgx = table == 1 ? b->feat_ld : ldgx;
     w.pick = mode == 0 ? GM_WGRAD_PICK_EXACT : GM_WGRAD_PICK_SPLIT;
-    unsigned* slots = nullptr;
-    int rc = gm_alloc(&w.partial, (size_t)std::max(1, b->n_chunks) * (size_t)(KN + N), st);
-    if (rc == GM_OK && mode == 2) {
-        // two-piece operands as gm_dense_wgrad marks them (the launcher refuses them with a table before any bound is read: the slots stay zero)
-        rc = gm_alloc(&slots, (size_t)(2 * sets + 1) * GM_BOUND_PAD, st);
-        if (rc == GM_OK && hipMemsetAsync(slots, 0, sizeof(unsigned) * (2 * sets + 1) * GM_BOUND_PAD, st) != hipSuccess) { gm_set_error("dense_wgrad_fused: memset failed"); rc = GM_EHIP; }
-        w.np = 2;
-        w.a_bound = gm_no_bound(); w.a_bound.amax = slots; w.a_bound.stride = GM_BOUND_PAD;
-        w.g_bound = gm_no_bound(); w.g_bound.amax = slots + (int64_t)sets * GM_BOUND_PAD; w.g_bound.stride = GM_BOUND_PAD;
-    }
-    if (rc == GM_OK) rc = gm_launch_wgrad(w, st);
-    if (w.partial) gm_dev_free(w.partial, st);
-    if (slots) gm_dev_free(slots, st);
-    gm_batch_mark_use(b, st);
-    return rc;
+    return launch_wgrad(b, w, scaled_level(b, s), mode == 2 ? 2 : 3, false, "dense_wgrad_fused", (hipStream_t)stream);
+}
+
+// The weight gradients of a restricted backward (GM_DEAD_ROWS; tests): G = a dQ of which only the rows of a set were written -- the set's keep vector flags the others,
+// which enter as zeros whatever their bytes hold.  _centre: dQ_L on its centre rows; _e1: dQ_{L-1} on the sources of the centres' in-edges
+static int dense_wgrad_keep(const gm_batch_t* b, RowSet rs, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
+                            int64_t db_stride, void* stream) {
+    GM_REQUIRE(b && x && dQ && dW && db && row_view(b, rs, false).keep, GM_EINVAL, "dense_wgrad_centre / _e1: bad arguments");
+    GM_REQUIRE(b->sets == 1 || (dw_stride >= (int64_t)Kx * N && db_stride >= N), GM_EINVAL, "dense_wgrad_centre / _e1: per-set outputs overlap");
+    gm_wgrad_args w{};
+    w.A = x; w.lda = Kx; w.K = Kx; w.G = dQ; w.ldg = N; w.N = N; w.g_keep = row_view(b, rs, false).keep;
+    w.dW = dW; w.dw_stride = dw_stride; w.db = db; w.db_stride = db_stride; w.pick = GM_WGRAD_PICK_SPLIT;
+    return launch_wgrad(b, w, batch_level(b), 3, false, "dense_wgrad_centre / _e1", (hipStream_t)stream);
+}
+extern "C" int gm_dense_wgrad_centre(const gm_batch_t* b, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
+                                     int64_t db_stride, void* stream) {
+    return dense_wgrad_keep(b, ROWS_CENTRE, x, Kx, dQ, N, dW, dw_stride, db, db_stride, stream);
+}
+extern "C" int gm_dense_wgrad_e1(const gm_batch_t* b, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
+                                 int64_t db_stride, void* stream) {
+    return dense_wgrad_keep(b, ROWS_E1, x, Kx, dQ, N, dW, dw_stride, db, db_stride, stream);
 }
 
 // ================================================================================ aggregate, exported for numerics tests
-// One launch of gm_launch_aggregate over one orientation of the batch with every field the production callers (gm_aggregate, batch_agg / gcn_forward,
-// gcn_backward) set, and the instantiation that ran (include/gmeta_hip.h)
+// One launch of gm_launch_aggregate over one orientation of the batch with every field the production callers (gm_aggregate; fwd_mul_first, fwd_aggregate, bwd_mul_first,
+// bwd_agg_t of model.hip) set, and the instantiation that ran (include/gmeta_hip.h)
 extern "C" int gm_dense_aggregate(const gm_batch_t* b, int32_t transposed, int32_t x_src, const float* x, int64_t ldx, int32_t width, int32_t scale_src,
                                   const float* s_in, const float* s_out, int32_t keep_signed, const float* bias, int64_t bias_stride, int32_t relu,
                                   uint8_t* relu_bits, const float* mask_h, const uint8_t* mask_b, int32_t hubs, const int32_t* rowlist, int64_t n_list,
@@ -349,27 +288,24 @@ extern "C" int gm_dense_aggregate(const gm_batch_t* b, int32_t transposed, int32
     GM_REQUIRE(!bias || !bias_stride || b->d_set_row_off, GM_EINVAL, "dense_aggregate: per-set bias without set row offsets");
     GM_REQUIRE(!keep_signed || s_out, GM_EINVAL, "dense_aggregate: keep_signed needs s_out");
     GM_REQUIRE(!relu_bits || relu, GM_EINVAL, "dense_aggregate: relu_bits are written with relu");
+    // weighted batches, as gm_aggregate: only the per-edge tables have a slot for the edges' weights
+    GM_REQUIRE(!b->weighted || scale_src != 1, GM_EINVAL, "dense_aggregate: on a weighted batch the source scale is none or the batch's own table (the per-source gather has no edge-weight slot)");
+    // ... and a feature gather meets the weights only through the per-edge row table (gm_aggregate always takes it; the by-source CSR has none)
+    GM_REQUIRE(!b->weighted || x_src != 1, GM_EINVAL, "dense_aggregate: on a weighted batch the feature gather goes through the per-edge row table (x_src 2; the per-source gather has no edge-weight slot)");
     hipStream_t st = (hipStream_t)stream;
-    gm_agg_args a{};
-    a.indptr = transposed ? b->d_indptr_t : b->d_indptr;
-    a.indices = transposed ? b->d_indices_t : b->d_indices;
-    a.rows = b->rows; a.width = width; a.out = out; a.launched = launched;
+    // the orientation as production's launches take it (agg_graph: an aggregate without a source scale carries a weighted batch's edge weights), hubs == 2: with its
+    // block schedule and hub set (batch_agg); 1: the hub-row list alone; 0: not even that
+    gm_agg_args a;
+    if (hubs == 2) GM_TRY(batch_agg(b, o, 0, st, a)); else agg_graph(b, o, a);
+    if (!hubs) { a.heavy = nullptr; a.n_heavy = 0; a.heavy_deg = 0; }
+    a.width = width; a.out = out; a.launched = launched;
     if (gather) { a.x = b->feat; a.ldx = b->feat_ld; a.x_row = b->d_feat_row; if (x_src == 2) a.x_idx = b->d_efeat; }
-    else { a.x = x; a.ldx = ldx; if (x_src == 3) a.x_idx = b->d_ect; }
-    if (b->weighted) {
-        // as gm_aggregate: only the per-edge tables have a slot for the edges' weights
-        GM_REQUIRE(scale_src != 1, GM_EINVAL, "dense_aggregate: on a weighted batch the source scale is none or the batch's own table (the per-source gather has no edge-weight slot)");
-        // ... and a feature gather meets the weights only through the per-edge row table (gm_aggregate always takes it; the by-source CSR has none)
-        GM_REQUIRE(x_src != 1, GM_EINVAL, "dense_aggregate: on a weighted batch the feature gather goes through the per-edge row table (x_src 2; the per-source gather has no edge-weight slot)");
-        if (scale_src == 0) a.e_w = b->d_ew[o];
-    }
+    else { a.x = x; a.ldx = ldx; if (x_src == 3) agg_centre_t(a, b, ROWS_ALL); }
     if (scale_src == 1) a.s_in = s_in;
     if (scale_src == 2) { a.s_in = b->d_norm; a.e_w = b->d_enorm[o]; }
     a.s_out = s_out; a.keep_signed = keep_signed ? 1 : 0;
     a.bias = bias; a.bias_stride = bias_stride; a.set_row_off = b->d_set_row_off; a.n_sets = b->sets;
     a.relu = relu ? 1 : 0; a.relu_bits = relu_bits; a.mask_h = mask_h; a.mask_b = mask_b;
-    if (hubs) { a.heavy = b->d_heavy[o]; a.n_heavy = b->n_heavy[o]; a.heavy_deg = b->heavy_deg; }
-    if (hubs == 2) { a.sched = b->d_sched[o]; a.sched_len = b->sched_len[o]; a.sched_win = b->sched_win; GM_TRY(gm_agg_hub(a, b, o, st)); }
     if (skip_lo <= skip_hi) { a.skip_on = 1; a.skip_lo = skip_lo; a.skip_hi = skip_hi; }
     if (rowlist) {
         GM_REQUIRE(n_list >= 1 && n_list <= b->rows && list_win >= 2 && list_win <= 64 && (list_win & (list_win - 1)) == 0, GM_EINVAL,
@@ -381,20 +317,19 @@ extern "C" int gm_dense_aggregate(const gm_batch_t* b, int32_t transposed, int32
             GM_REQUIRE(h[k] >= 0 && h[k] < b->rows && (k == 0 || h[k] > h[k - 1]), GM_EINVAL, "dense_aggregate: the row list is not ascending / out of range at entry %lld", (long long)k);
         a.rowlist = rowlist; a.n_list = n_list; a.list_win = list_win;
         if (list_sched) {
-            // the batch's block schedule over its own list of window rows (gcn_forward's partial launch of a fused pass)
+            // the batch's block schedule over its own list of window rows (fwd_aggregate's partial launch of a fused layer)
             GM_REQUIRE(hubs == 2 && !transposed && b->d_sched_mid && n_list == b->n_mid && list_win == b->mid_win, GM_EINVAL,
                        "dense_aggregate: the list schedule goes with the batch's own list (%d rows, windows of %d) and its hub tables", b->n_mid, b->mid_win);
             a.sched = b->d_sched_mid; a.sched_len = b->sched_len_mid; a.sched_win = b->mid_win;
         } else { a.sched = nullptr; a.sched_len = 0; }
     } else if (list_sched >= 2 && list_sched <= 4) {
-        // one of the batch's own lists of observable rows (gm_batch::obs[list_sched - 2]) as gcn_forward / gcn_backward launch over it: the list at its bound, its
+        // one of the batch's own lists of observable rows (gm_batch::obs[list_sched - 2]) as fwd_aggregate / bwd_agg_t (model.hip) launch over it (agg_take_list): the list at its bound, its
         // window, the length the device counted and, where the orientation has hub rows, the list's own schedule.  Built or not taken by the batch: both allowed here
         const gm_batch::obs_list& ol = b->obs[list_sched - 2];
         GM_REQUIRE(ol.rows && (list_sched == 4) == (transposed != 0), GM_EINVAL, "dense_aggregate: the batch holds no list %d of this orientation", list_sched - 2);
         GM_REQUIRE(ol.cap >= 1 || ol.sched, GM_EINVAL, "dense_aggregate: list %d is empty and the orientation has no hub rows: nothing to launch", list_sched - 2);
         GM_REQUIRE(b->n_heavy[o] == 0 || (hubs == 2 && ol.sched), GM_EINVAL, "dense_aggregate: list %d has no schedule for the orientation's hub rows", list_sched - 2);
-        a.rowlist = ol.rows; a.n_list = ol.cap; a.n_list_dev = ol.len; a.list_win = ol.win;
-        a.sched = ol.sched; a.sched_len = ol.sched ? ol.sched_len : 0; a.sched_win = ol.win;
+        agg_take_list(a, ol);
     } else GM_REQUIRE(!list_sched, GM_EINVAL, "dense_aggregate: a list schedule without a row list");
     if (stream_ok && a.e_w && a.e_w == b->d_enorm[o]) GM_TRY(gm_agg_stream_args(a, b, o, gather, st));
     const int rc = gm_launch_aggregate(a, st);

@@ -675,6 +675,41 @@ struct gm_wgrad_args {
 int gm_launch_wgrad(const gm_wgrad_args& a, hipStream_t s);
 bool gm_wgrad_gather_ok(int n_chunks, int K, int N);
 
+// ---- The launches of the model's schedules, named once.  Defined in model.hip; the dense schedule (gcn_forward / gcn_backward and their step functions), the cone
+// schedule, the row-sparse backward and the gm_dense_* exports (dense_exports.hip: what the fp64 numerics and the dead-row suites drive) all fill these field groups
+// through these builders and nowhere else, so a field a production launch gains is a field of the launch the tests check
+// A row set of a batch, as its tables carry it (row_view): every row; the rows with an out-edge inside the batch (the only rows of H_l below the last layer that an
+// edge reads); the sources of the centres' in-edges; the centre rows
+enum RowSet { ROWS_ALL, ROWS_SRC, ROWS_E1, ROWS_CENTRE };
+// A row set as the launches take it.  keep: the row scale with "not of the set" in its sign bit -- gm_gemm_args::row_scale_keep (rows a GEMM stores), gm_wgrad_args::g_keep
+// (rows of G that were written), gm_agg_args::s_out + keep_signed of a transposed aggregate (NULL: every row).  sign: +1 on the set, -1 off it -- s_out + keep_signed of a
+// forward partial aggregate, a scale of exactly 1 (NULL: every row).  tab: the per-row source table of a fused loader or a table-fed weight gradient over a Z_l formed on the
+// set -- the full table's entry on its rows, the zero row everywhere else (gather: the layer reads the feature table; a centre-restricted layer never does, plan_check).
+// obs: the set's index into the tables of gm_batch_fwd_counts, -1 where it has none.  n: its rows as the host knows them (ROWS_E1: a bound, see rows_kept in model.hip)
+// live: one word per GEMM row tile, 0 = no row of the set in it (gm_batch::d_tile_live; NULL: every row / no flags)
+struct RowView { const float* keep; const float* sign; const void* tab; int obs; int64_t n; const int32_t* live; };
+RowView row_view(const gm_batch* b, RowSet rs, bool gather);
+// The rows a GEMM or a weight gradient runs over: their norm, GEMM row tiles, weight-gradient chunks and count.  The batch is one such level (batch_level); the cone
+// schedule has one per layer boundary and the row-sparse backward two compact ones (model.hip)
+struct LevelView { const float* norm; const int32_t* tiles; int n_tiles; const int32_t* chunks; const int32_t* set_chunk_off; int n_chunks; int64_t rows; int sets; };
+LevelView batch_level(const gm_batch* b);
+void gemm_rows(gm_gemm_args& g, const LevelView& v);       // row_scale, tiles, n_tiles, rows
+void wgrad_rows(gm_wgrad_args& w, const LevelView& v);     // a_scale, chunks, n_chunks, set_chunk_off, sets, rows
+// a GEMM that stores the rows of a set only (keep: row_scale_keep + the kept-row count of the launch accounting) and / or takes the set's tile flags (live)
+void gemm_keep_rows(gm_gemm_args& g, const RowView& v, bool keep, bool live, int64_t n_keep);
+// the dZ GEMM over a dQ_L that holds its centre rows only: the fused loader reads them through gm_batch::d_dq_tab and zeros for every other row
+void gemm_dq_table(gm_gemm_args& g, const gm_batch* b, const float* dQ, int64_t ld);
+// orientation dir of the batch (0: A, the in-edges; 1: A^T) as an aggregate walks it -- CSR, rows, hub-row list, the edges' weights of a weighted batch (agg_graph) -- and
+// with the orientation's block schedule and hub set hub_set on top: the batch-wide aggregate of the dense schedule (batch_agg)
+void agg_graph(const gm_batch* b, int dir, gm_agg_args& a);
+int batch_agg(const gm_batch* b, int dir, int hub_set, hipStream_t st, gm_agg_args& a);
+// a restricted launch over one of the batch's lists of observable rows: the list in the windows' place, its own schedule (or none), the length the device counted
+void agg_take_list(gm_agg_args& a, const gm_batch::obs_list& ol);
+// the last layer's transposed aggregate over a T_L that holds its centre rows only: T_L read through gm_batch::d_ect; out != ROWS_ALL: only that set's rows of dQ_{L-1}
+// stored (s_out = the set's keep vector, keep_signed)
+void agg_centre_t(gm_agg_args& a, const gm_batch* b, RowSet out);
+int gm_gather_rows(const gm_batch* b, const int32_t* feat_row, int64_t n, int F, float* out, hipStream_t st);      // extract.hip: out[i, :F] = feature row feat_row[i] of the store
+
 // Rows per weight-gradient chunk for sets of the given sizes.  One workgroup (one CU: 128 accumulator VGPRs x 16 waves)
 // takes one chunk and writes a (K+1)xN partial, so the chunk count should sit just under a multiple of the CU count (256) --
 // 280 chunks cost two rounds for the work of 1.1 -- and be small: every chunk adds a partial to write and re-read.

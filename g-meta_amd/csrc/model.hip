@@ -690,9 +690,6 @@ struct PlaneDir {
 // it (the query evaluations of the inner steps, finetuning's query passes, gm_proto_predict): all anyone reads is H_L at the centre rows.  PASS_DIFF: the dense backward
 // differentiates it (the support passes, the last query evaluation): head + loss + gcn_backward follow
 enum PassKind { PASS_PLAIN = 0, PASS_FWD_ONLY = 1, PASS_DIFF = 2 };
-// A row set of a batch, as its tables carry it (row_view): every row; the rows with an out-edge inside the batch (the only rows of H_l below the last layer that an
-// edge reads); the sources of the centres' in-edges; the centre rows
-enum RowSet { ROWS_ALL, ROWS_SRC, ROWS_E1, ROWS_CENTRE };
 // How the pass leaves bufA (= dQ_L) for the head/loss launch and the gcn_backward(skip_head = 1) that follow.  DQ_MEMSET: untouched, head_loss zero-fills it with a
 // memset launch; DQ_ZEROED: the last forward GEMM zero-fills it on its way out; DQ_CENTRE (GM_DEAD_ROWS): left alone -- the head/loss launch assigns its centre rows
 // and the two readers of dQ_L in the backward take every other row as zeros (dZ GEMM: gm_batch::d_dq_tab; weight gradient: gm_wgrad_args::g_keep)
@@ -719,7 +716,7 @@ enum DqFill { DQ_MEMSET, DQ_ZEROED, DQ_CENTRE };
 //  dead_tiles (GM_DEAD_TILES): the update of a forward-only fused layer that stores the centre rows or the sources of their in-edges takes the batch's tile flags of that
 //    set: a tile without a stored row issues its MFMAs on zero registers -- no table fetch, no operand load, no LDS traffic, no barrier, no epilogue (gemm_split.h)
 struct LayerPlan { bool split, fuse; RowSet formed, stored; bool relu_bits; const gm_batch::obs_list* list; bool dead_tiles; };
-// The pass: its kind, its layers, dQ_L, and what a gcn_backward(skip_head = 1) over it may do (GM_DEAD_ROWS=2; gcn_backward has the bitwise argument).  t_centre: dQ_L is
+// The pass: its kind, its layers, dQ_L, and what a gcn_backward(skip_head = 1) over it may do (GM_DEAD_ROWS=2; plan_backward, which resolves these against skip_head, has the bitwise argument).  t_centre: dQ_L is
 // left to its centre rows and the zero block behind T_L is there -- the dZ GEMM stores T_L's centre rows only, the transposed aggregate reads T_L through gm_batch::d_ect.
 // dq_e1: ... and the layer below is the first, aggregate-first, with a table-fed three-piece weight gradient: that aggregate stores only the rows of dQ_{L-1} that can be non-zero
 // t_list: ... and walks the compact list of those rows (gm_batch::obs[2]), as LayerPlan::list
@@ -807,7 +804,10 @@ static int readout_tables(const gm_batch* b, hipStream_t s);
 static int readout_fwd(const GcnCtx& c, hipStream_t st);
 static int readout_bwd(const GcnCtx& c, hipStream_t st);
 
-static void wgrad_sgd(gm_wgrad_args& w, const GcnCtx& c, int l) {
+// What layer l's weight gradient writes, in every schedule: its shape, the partials, dW_l / db_l inside `dparams`, and the context's fused SGD step
+static void wgrad_out(gm_wgrad_args& w, const GcnCtx& c, int l, float* partial, float* dparams, int64_t dstride) {
+    w.K = c.L.dims[l]; w.N = c.L.dims[l + 1]; w.partial = partial;
+    w.dW = dparams + c.L.w_off[l]; w.dw_stride = dstride; w.db = dparams + c.L.b_off[l]; w.db_stride = dstride;
     w.sgd_cur = c.sgd.cur; w.sgd_cur_stride = c.sgd.cur_stride; w.sgd_next = c.sgd.next; w.sgd_next_stride = c.sgd.next_stride; w.sgd_lr = c.sgd.lr;
     w.w_off = c.L.w_off[l]; w.b_off = c.L.b_off[l];
 }
@@ -906,29 +906,41 @@ static int launch_agg(const gm_agg_args& a, int64_t bytes, int64_t strict_bytes,
     gm_prof_agg_end(st);
     return rc;
 }
-// The batch-wide aggregate of the dense schedule over orientation dir (0: A, the in-edges; 1: A^T): graph, hub rows, block schedule and the context's hub set
-static int batch_agg(const GcnCtx& c, int dir, hipStream_t st, gm_agg_args& a) {
-    const gm_batch* b = c.b;
+// ---- The launch builders (declared, with what each is for, in gm_internal.h): every schedule below and every gm_dense_* export of dense_exports.hip fills these field
+// groups through them and nowhere else
+void agg_graph(const gm_batch* b, int dir, gm_agg_args& a) {
     a = gm_agg_args{};
     if (dir == 0) { a.indptr = b->d_indptr; a.indices = b->d_indices; } else { a.indptr = b->d_indptr_t; a.indices = b->d_indices_t; }
     a.heavy = b->d_heavy[dir]; a.n_heavy = b->n_heavy[dir]; a.heavy_deg = b->heavy_deg;
-    a.sched = b->d_sched[dir]; a.sched_len = b->sched_len[dir]; a.sched_win = b->sched_win;
-    GM_TRY(gm_agg_hub(a, b, dir, st, c.hub_set));
     a.rows = b->rows;
     // weighted batches: an aggregate without a source scale still carries the edges' weights (the callers that scale by the source's norm replace this
     // with d_enorm, which holds weight x norm).  A pointer choice only: the kernels read e_w as they do on unweighted batches
     if (b->weighted) a.e_w = b->d_ew[dir];
-    return GM_OK;
 }
-
-// A row set as the launches take it.  keep: the row scale with "not of the set" in its sign bit -- gm_gemm_args::row_scale_keep (rows a GEMM stores), gm_wgrad_args::g_keep
-// (rows of G that were written), gm_agg_args::s_out + keep_signed of a transposed aggregate (NULL: every row).  sign: +1 on the set, -1 off it -- s_out + keep_signed of a
-// forward partial aggregate, a scale of exactly 1 (NULL: every row).  tab: the per-row source table of a fused loader or a table-fed weight gradient over a Z_l formed on the
-// set -- the full table's entry on its rows, the zero row everywhere else (gather: the layer reads the feature table; a centre-restricted layer never does, plan_check).
-// obs: the set's index into the tables of gm_batch_fwd_counts, -1 where it has none.  n: its rows as the host knows them (ROWS_E1: a bound, see rows_kept)
-// live: one word per GEMM row tile, 0 = no row of the set in it (gm_batch::d_tile_live; NULL: every row / no flags)
-struct RowView { const float* keep; const float* sign; const void* tab; int obs; int64_t n; const int32_t* live; };
-static RowView row_view(const gm_batch* b, RowSet rs, bool gather) {
+int batch_agg(const gm_batch* b, int dir, int hub_set, hipStream_t st, gm_agg_args& a) {
+    agg_graph(b, dir, a);
+    a.sched = b->d_sched[dir]; a.sched_len = b->sched_len[dir]; a.sched_win = b->sched_win;
+    return gm_agg_hub(a, b, dir, st, hub_set);
+}
+void agg_take_list(gm_agg_args& a, const gm_batch::obs_list& ol) {
+    a.rowlist = ol.rows; a.n_list = ol.cap; a.n_list_dev = ol.len; a.list_win = ol.win;
+    a.sched = ol.sched; a.sched_len = ol.sched ? ol.sched_len : 0; a.sched_win = ol.win;
+}
+void agg_centre_t(gm_agg_args& a, const gm_batch* b, RowSet out) {
+    a.x_idx = b->d_ect;
+    if (out != ROWS_ALL) { a.s_out = row_view(b, out, false).keep; a.keep_signed = 1; }
+}
+LevelView batch_level(const gm_batch* b) { return {b->d_norm, b->d_tiles, b->n_tiles, b->d_chunks, b->d_set_chunk_off, b->n_chunks, b->rows, b->sets}; }
+void gemm_rows(gm_gemm_args& g, const LevelView& v) { g.row_scale = v.norm; g.tiles = v.tiles; g.n_tiles = v.n_tiles; g.rows = v.rows; }
+void wgrad_rows(gm_wgrad_args& w, const LevelView& v) {
+    w.a_scale = v.norm; w.chunks = v.chunks; w.n_chunks = v.n_chunks; w.set_chunk_off = v.set_chunk_off; w.sets = v.sets; w.rows = v.rows;
+}
+void gemm_keep_rows(gm_gemm_args& g, const RowView& v, bool keep, bool live, int64_t n_keep) {
+    if (keep) { g.row_scale_keep = v.keep; g.n_keep = n_keep; }
+    if (live) g.tile_live = v.live;
+}
+void gemm_dq_table(gm_gemm_args& g, const gm_batch* b, const float* dQ, int64_t ld) { g.fuse2 = b->d_dq_tab; g.zside = dQ; g.ldz = ld; }
+RowView row_view(const gm_batch* b, RowSet rs, bool gather) {
     if (rs == ROWS_E1) return {b->d_norm_e1, b->d_obs[1], gather ? b->d_fwd_tab_feat : b->d_fwd_tab[1], 1, b->n_e1, b->d_tile_live[1]};
     if (rs == ROWS_CENTRE) return {b->d_norm_c, b->d_obs[0], b->d_fwd_tab[0], 0, b->n_c, b->d_tile_live[0]};
     return {rs == ROWS_SRC ? b->d_norm_src : nullptr, nullptr, gather ? b->d_fuse2_feat : b->d_fuse2, -1, rs == ROWS_SRC ? b->n_src : b->rows, nullptr};
@@ -991,12 +1003,147 @@ static int t_zero_fill(GcnCtx& c, hipStream_t st) {
     return GM_OK;
 }
 
-int gm_gather_rows(const gm_batch* b, const int32_t* feat_row, int64_t n, int F, float* out, hipStream_t st);
-static int cone_forward(GcnCtx& c, const float* params, int64_t pstride, float* logits, hipStream_t st, int reuse_z1, int skip_head);
-static int cone_backward(GcnCtx& c, const float* params, int64_t pstride, const float* dlogits, float* dparams, int64_t dstride, hipStream_t st, int skip_head);
+// ================================================================================ row-sparse backward
+static bool sparse_bwd_ok(const gm_layout& L) {
+    if (L.n_gcn > 2 || L.readout == GM_READOUT_MEAN) return false;      // (mean readout: dQ_L is dense, every row reaches the head)
+    for (int l = 0; l < L.n_gcn; ++l) if (L.dims[l] > L.dims[l + 1]) return false;      // aggregate-first layers only
+    return true;
+}
+// dW_l = sum_k norm[r_k] Z_l[r_k]^T G[k] ; db_l = sum_k G[k] over the compact rows k of level v, whose batch rows are a_row (a set without any gets zeros: empty chunk range)
+static int sparse_wgrad(GcnCtx& c, int l, const LevelView& v, const int32_t* a_row, const float* G, float* dparams, int64_t dstride, hipStream_t st) {
+    gm_wgrad_args w{}; wgrad_out(w, c, l, c.partial_c, dparams, dstride); wgrad_rows(w, v);
+    w.A = c.Z[l]; w.lda = w.K; w.a_row = a_row; w.G = G; w.ldg = w.N;
+    return gm_launch_wgrad(w, st);
+}
+// Exact row-sparse backward (see gm_hparams_t.sparse_bwd).  The head is the only consumer of the last GCN layer, so
+// dQ_L lives on the centre rows; one transposed-aggregate step spreads it along the in-edges of the centres.  Every
+// product below is the dense backward's product with the structurally-zero terms removed.
+static int gcn_backward_sparse(GcnCtx& c, const float* params, int64_t pstride, const float* dlogits, float* dparams, int64_t dstride, hipStream_t st, int skip_head) {
+    const gm_layout& L = c.L; const gm_batch* b = c.b;
+    const int Lg = L.n_gcn, fiL = L.dims[Lg - 1], foL = L.dims[Lg];
+    // the two compact levels: the centre rows k (batch row c_k), and the centres' in-edges e (source u_e), which no GEMM runs over
+    const LevelView lc = {b->d_cnorm, b->d_c_tiles, b->n_c_tiles, b->d_c_chunks, b->d_c_set_chunk_off, b->n_c_chunks, b->n_c, b->sets};
+    const LevelView le = {b->d_e1_norm, nullptr, 0, b->d_e1_chunks, b->d_e1_set_chunk_off, b->n_e1_chunks, b->n_e1, b->sets};
+    if (!skip_head) GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, nullptr, c.cG2, st));
+    GM_TRY(sparse_wgrad(c, Lg - 1, lc, b->d_crow, c.cG2, dparams, dstride, st));
+    if (Lg == 1) return GM_OK;
+    // T2[k] = norm[c_k] * (G2[k] W_L^T)
+    gm_gemm_args g{}; g.A = c.cG2; g.lda = foL; g.B = params + L.w_off[Lg - 1]; g.b_stride = pstride; g.transB = 1; g.C = c.cT2; g.ldc = fiL; g.K = foL; g.N = fiL;
+    gemm_rows(g, lc);
+    GM_TRY(gm_launch_gemm_nn(g, st));
+    if (b->n_e1 > 0) {
+        const int64_t tot = (int64_t)b->n_e1 * fiL;
+        hipLaunchKernelGGL(k_expand_edges, dim3((int)std::min<int64_t>(2048, (tot + 255) / 256)), dim3(256), 0, st, c.cT2, c.H[0], fiL, b->d_e1_row, b->d_e1_par,
+                           b->weighted ? b->d_e1_coef : b->d_e1_norm, b->n_e1, c.cG1);      // (weighted batches: the edge's weight rides in the coefficient)
+        GM_HIP(hipGetLastError());
+    }
+    return sparse_wgrad(c, 0, le, b->d_e1_row, c.cG1, dparams, dstride, st);
+}
 
-// skip_head: the head (centre gather + linear) is evaluated by the fused k_head_loss launch that follows
-// kind: who reads the pass (PassKind); what follows from it is plan_pass's to decide.  gm_set_fuse_agg: the run-time switch of the fused aggregate + GEMM
+// ================================================================================ receptive-field ("cone") schedule
+// The same layer formulas as gcn_forward/gcn_backward, evaluated only on the rows that can reach a centre
+// (cone.hip): layer l maps level l (sources) to level l+1 (destinations); all matrices are compact.
+
+// SURVEY 8(d)'s B_agg on the rows a level-to-level aggregate actually touches: the destination level's row bounds + norms, the edges between the
+// two levels, every source-level row read once (by construction each of them is the source of at least one of those edges), every
+// destination row written once
+static int64_t cone_agg_bytes(int64_t n_dst, int64_t n_src, int64_t nnz, int width) {
+    return 4 * (n_dst + 1) + 4 * nnz + 4 * n_dst + 4 * (n_src + n_dst) * (int64_t)width;
+}
+static int cone_launch_agg(const gm_agg_args& a, int64_t n_src, int64_t nnz, hipStream_t st) {
+    const int64_t by = cone_agg_bytes(a.rows, n_src, nnz, a.width);
+    return launch_agg(a, by, by, st);
+}
+static gm_agg_args cone_agg(const gm_cone* cn, const gm_cone_level& up, int transposed) {
+    gm_agg_args a{};
+    a.indptr = transposed ? up.d_indptr_t : up.d_indptr; a.indices = transposed ? up.d_indices_t : up.d_indices;
+    a.heavy = up.d_heavy[transposed]; a.n_heavy = up.n_heavy[transposed]; a.heavy_deg = cn->heavy_deg;
+    a.e_w = transposed ? up.d_ew_t : up.d_ew;      // weighted batches (NULL otherwise): the edges' weights; launches that scale by the source's norm take d_enorm / d_enorm_t instead
+    return a;
+}
+// a level of the cone as the GEMMs and weight gradients over its rows take it
+static LevelView cone_level(const gm_cone_level& v, int sets) { return {v.d_norm, v.d_tiles, v.n_tiles, v.d_chunks, v.d_set_chunk_off, v.n_chunks, v.n, sets}; }
+
+static int cone_forward(GcnCtx& c, const float* params, int64_t pstride, float* logits, hipStream_t st, int reuse_z1, int skip_head) {
+    const gm_layout& L = c.L; const gm_batch* b = c.b; const gm_cone* cn = c.cone;
+    GM_TRY(gm_check_feat_dim(b, L.dims[0], "forward"));
+    GM_REQUIRE((L.link != 0) == (b->centres == 2), GM_EINVAL, "forward: link_pred model needs a 2-centre batch and vice versa");
+    GM_REQUIRE(!c.x0_user && !c.centre, GM_EINVAL, "forward: the cone schedule reads features and centres from the batch");
+    const float* xin = nullptr;
+    for (int l = 0; l < L.n_gcn; ++l) {
+        const gm_cone_level& lo = cn->lv[l]; const gm_cone_level& up = cn->lv[l + 1];
+        const int fi = L.dims[l], fo = L.dims[l + 1];
+        if (fi > fo) {                      // multiply on the source level, then aggregate into the destination level
+            const float* A = xin;
+            if (l == 0) { GM_TRY(gm_gather_rows(b, lo.d_feat_row, lo.n, fi, c.X0, st)); A = c.X0; }
+            gm_gemm_args g{}; g.A = A; g.lda = fi; g.B = params + L.w_off[l]; g.b_stride = pstride; g.C = c.Z[l]; g.ldc = fo; g.K = fi; g.N = fo;
+            gemm_rows(g, cone_level(lo, b->sets));
+            GM_TRY(gm_launch_gemm_nn(g, st));
+            gm_agg_args a = cone_agg(cn, up, 0);
+            a.x = c.Z[l]; a.ldx = fo; a.s_out = up.d_norm; a.bias = params + L.b_off[l]; a.bias_stride = pstride; a.set_row_off = up.d_set_off; a.n_sets = b->sets;
+            a.relu = 1; a.out = c.H[l]; a.rows = up.n; a.width = fo;
+            GM_TRY(cone_launch_agg(a, lo.n, up.nnz, st));
+        } else {
+            if (!(l == 0 && reuse_z1 && c.z1_valid)) {
+                gm_agg_args a = cone_agg(cn, up, 0);
+                a.s_in = lo.d_norm; a.e_w = up.d_enorm; a.out = c.Z[l]; a.rows = up.n; a.width = fi; a.ldx = fi;
+                if (l == 0) { a.x = b->feat; a.x_row = lo.d_feat_row; a.x_idx = up.d_efeat; a.ldx = b->feat_ld; } else a.x = xin;
+                GM_TRY(cone_launch_agg(a, lo.n, up.nnz, st));
+                if (l == 0) c.z1_valid = 1;
+            }
+            gm_gemm_args g{}; g.A = c.Z[l]; g.lda = fi; g.B = params + L.w_off[l]; g.b_stride = pstride; g.C = c.H[l]; g.ldc = fo; g.K = fi; g.N = fo;
+            g.bias = params + L.b_off[l]; g.bias_stride = pstride; g.relu = 1; gemm_rows(g, cone_level(up, b->sets));
+            GM_TRY(gm_launch_gemm_nn(g, st));
+        }
+        xin = c.H[l];
+    }
+    return skip_head ? GM_OK : launch_head_fwd(c, params, pstride, logits, st);
+}
+
+static int cone_backward(GcnCtx& c, const float* params, int64_t pstride, const float* dlogits, float* dparams, int64_t dstride, hipStream_t st, int skip_head) {
+    const gm_layout& L = c.L; const gm_batch* b = c.b; const gm_cone* cn = c.cone;
+    const int Lg = L.n_gcn;
+    float* dQ = c.bufA; float* T = c.bufB;
+    if (!skip_head) GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, nullptr, dQ, st));   // dQ_L on the centre rows
+    for (int l = Lg - 1; l >= 0; --l) {
+        const gm_cone_level& lo = cn->lv[l]; const gm_cone_level& up = cn->lv[l + 1];
+        const int fi = L.dims[l], fo = L.dims[l + 1];
+        const float* maskprev = l > 0 ? c.H[l - 1] : nullptr;
+        gm_wgrad_args w{}; wgrad_out(w, c, l, c.partial, dparams, dstride);
+        if (fi > fo) {
+            // dY = A^T (norm * dQ) on the source level ; dW = (norm*X)^T dY ; db = colsum(dQ) ; dQ_prev = relu'(H_prev) * norm * (dY W^T)
+            gm_agg_args a = cone_agg(cn, up, 1);
+            a.x = dQ; a.ldx = fo; a.s_in = up.d_norm; a.e_w = up.d_enorm_t; a.out = T; a.rows = lo.n; a.width = fo;
+            GM_TRY(cone_launch_agg(a, up.n, up.nnz, st));
+            w.A = l > 0 ? c.H[l - 1] : c.X0; w.lda = fi; w.G = T; w.ldg = fo; w.db = nullptr; wgrad_rows(w, cone_level(lo, b->sets));
+            GM_TRY(gm_launch_wgrad(w, st));
+            hipLaunchKernelGGL(k_colsum_rows, dim3(b->sets), dim3(256), 0, st, dQ, (int64_t)fo, fo, up.d_set_off, dparams + L.b_off[l], dstride, c.sgd, L.b_off[l]);
+            GM_HIP(hipGetLastError());
+            if (l > 0) {
+                gm_gemm_args g{}; g.A = T; g.lda = fo; g.B = params + L.w_off[l]; g.b_stride = pstride; g.transB = 1; g.C = dQ; g.ldc = fi; g.K = fo; g.N = fi;
+                g.mask_h = maskprev; gemm_rows(g, cone_level(lo, b->sets));
+                GM_TRY(gm_launch_gemm_nn(g, st));
+            }
+        } else {
+            // dW = (norm*Z)^T dQ ; db = colsum(dQ) ; dZ = norm * (dQ W^T) ; dQ_prev = relu'(H_prev) * norm * A^T dZ
+            w.A = c.Z[l]; w.lda = fi; w.G = dQ; w.ldg = fo; wgrad_rows(w, cone_level(up, b->sets));
+            GM_TRY(gm_launch_wgrad(w, st));
+            if (l > 0) {
+                gm_gemm_args g{}; g.A = dQ; g.lda = fo; g.B = params + L.w_off[l]; g.b_stride = pstride; g.transB = 1; g.C = T; g.ldc = fi; g.K = fo; g.N = fi;
+                gemm_rows(g, cone_level(up, b->sets));
+                GM_TRY(gm_launch_gemm_nn(g, st));
+                gm_agg_args a = cone_agg(cn, up, 1);
+                a.x = T; a.ldx = fi; a.s_out = lo.d_norm; a.mask_h = maskprev; a.out = dQ; a.rows = lo.n; a.width = fi;
+                GM_TRY(cone_launch_agg(a, up.n, up.nnz, st));
+            }
+        }
+    }
+    return GM_OK;
+}
+
+
+// ================================================================================ dense schedule
+// gm_set_fuse_agg: the run-time switch of the fused aggregate + GEMM
 static std::atomic<int> g_fuse_agg_override{-1};
 extern "C" void gm_set_fuse_agg(int32_t on) { g_fuse_agg_override.store(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed); }
 extern "C" int32_t gm_get_fuse_agg(void) { const int o = g_fuse_agg_override.load(std::memory_order_relaxed); return o >= 0 ? o : gm_knob().fuse_agg; }
@@ -1013,7 +1160,6 @@ static int plan_check(const GcnCtx& c, const PassPlan& p) {
 }
 // The plan of one pass (PassPlan): reads the knobs, the layout, the batch's table pointers and the context; launches nothing.  The only place of the dense path that
 // reads GM_DEAD_ROWS / GM_CENTRE_STORE (through dead_row_level too), GM_FUSE_DIFF and gm_get_fuse_agg
-static int plan_check(const GcnCtx& c, const PassPlan& p);
 static int plan_pass(const GcnCtx& c, const float* params, int64_t pstride, PassKind kind, int reuse_z1, PassPlan* plan) {
     const gm_layout& L = c.L; const gm_batch* b = c.b;
     const int Lg = L.n_gcn, last = Lg - 1, level = dead_row_level(c), centre_store = gm_knob().centre_store;
@@ -1097,12 +1243,71 @@ static int plan_pass(const GcnCtx& c, const float* params, int64_t pstride, Pass
     }
     *plan = p; return plan_check(c, p);
 }
-// a restricted launch over the plan's list: the list in the windows' place, its own schedule (or none), the length the device counted
-static void agg_take_list(gm_agg_args& a, const gm_batch::obs_list& ol) {
-    a.rowlist = ol.rows; a.n_list = ol.cap; a.n_list_dev = ol.len; a.list_win = ol.win;
-    a.sched = ol.sched; a.sched_len = ol.sched ? ol.sched_len : 0; a.sched_win = ol.win;
-}
 
+// ---- gcn_forward executes the pass's plan; one step function per launch group of a layer
+// learner.py:34-40: multiply first, then aggregate (every row formed and stored; of the plan such a layer takes its relu' bits only)
+static int fwd_mul_first(GcnCtx& c, int l, const float* params, int64_t pstride, const float* xin, hipStream_t st) {
+    const gm_layout& L = c.L; const gm_batch* b = c.b; const int fi = L.dims[l], fo = L.dims[l + 1];
+    if (l == 0 && !c.x0_user) { GM_TRY(gm_gather_rows(b, b->d_feat_row, b->rows, fi, c.X0, st)); xin = c.X0; }
+    gm_gemm_args g{}; g.A = xin; g.lda = fi; g.B = params + L.w_off[l]; g.b_stride = pstride; g.C = c.Z[l]; g.ldc = fo; g.K = fi; g.N = fo;
+    gemm_rows(g, batch_level(b));
+    GM_TRY(gm_launch_gemm_nn(g, st));
+    gm_agg_args a; GM_TRY(batch_agg(b, 0, c.hub_set, st, a));
+    a.x = c.Z[l]; a.ldx = fo; a.s_out = b->d_norm;
+    a.bias = params + L.b_off[l]; a.bias_stride = pstride; a.set_row_off = b->d_set_row_off; a.n_sets = b->sets; a.relu = 1;
+    a.out = c.H[l]; a.width = fo; a.relu_bits = c.plan.layer[l].relu_bits ? c.M[l] : nullptr;
+    return launch_agg(a, gm_aggregate_bytes(b, fo), gm_aggregate_bytes(b, fo), st);
+}
+// learner.py:41-47, aggregate first: Z_l = A (norm x), over x / ldx, the layer's input as the aggregate and the fused loader read it (gather: the feature table)
+static int fwd_aggregate(GcnCtx& c, int l, const float* x, int64_t ldx, bool gather, hipStream_t st) {
+    const gm_batch* b = c.b; const int fi = c.L.dims[l]; const LayerPlan& lp = c.plan.layer[l];
+    gm_agg_args a; GM_TRY(batch_agg(b, 0, c.hub_set, st, a));
+    a.s_in = b->d_norm; a.e_w = b->d_enorm[0]; a.out = c.Z[l]; a.width = fi;
+    a.x = x; a.ldx = ldx; if (gather) { a.x_row = b->d_feat_row; a.x_idx = b->d_efeat; }
+    if (!lp.fuse) {
+        if (a.e_w) GM_TRY(gm_agg_stream_args(a, b, 0, gather, st));      // full launches may take the LDS-DMA stream kernel (agg_stream.hip)
+        // compulsory HBM bytes: a gather launch reads rows of the (cache-resident) feature table, at most all of it
+        int64_t strict = gm_aggregate_bytes(b, fi);
+        if (gather) strict += 4 * b->rows - 4 * b->rows * (int64_t)fi + std::min<int64_t>(4 * b->rows * (int64_t)fi, 4 * b->feat_rows * (int64_t)fi);
+        GM_TRY(launch_agg(a, gm_aggregate_bytes(b, fi), strict, st));
+        if (l == 0) c.z1_valid = 1;
+        return GM_OK;
+    }
+    // only the rows the fused kernel does not form itself (more than GM_FUSE_MAXDEG sources): a partial launch
+    a.skip_on = 1; a.skip_lo = 0; a.skip_hi = GM_FUSE_MAXDEG;
+    if (b->d_mid && c.hub_set == 0 && gm_knob().agg_mid_list && (b->n_heavy[0] == 0 || b->d_sched_mid)) {
+        // ... walking the compact list of those rows (hub rows keep their blocks; the schedule is the list's)
+        a.rowlist = b->d_mid; a.n_list = b->n_mid; a.list_win = b->mid_win;
+        if (b->n_heavy[0] > 0) { a.sched = b->d_sched_mid; a.sched_len = b->sched_len_mid; a.sched_win = b->mid_win; }
+        else { a.sched = nullptr; a.sched_len = 0; }
+    }
+    // ... and of those only the rows the plan forms; the others stop at their descriptor (list entry, row bounds, flag)
+    if (lp.formed != ROWS_ALL) { a.s_out = row_view(b, lp.formed, gather).sign; a.keep_signed = 1; }
+    // ... walking the compact list of THOSE rows where the plan took it (no launch where the host knows it empty)
+    if (lp.list && lp.list->take == 2) return GM_OK;
+    if (lp.list && lp.list->take == 1) agg_take_list(a, *lp.list);
+    int64_t pb, pbs;
+    GM_TRY(partial_agg_bytes(b, lp.formed, fi, gather, st, &pb, &pbs));
+    return launch_agg(a, pb, pbs, st);
+}
+// ... then H_l = relu(norm Z_l W_l + b_l), on the kernel, through the loader and with the stores its plan says
+static int fwd_update(GcnCtx& c, int l, const float* params, int64_t pstride, const float* x, int64_t ldx, bool gather, hipStream_t st) {
+    const gm_layout& L = c.L; const gm_batch* b = c.b; const int fi = L.dims[l], fo = L.dims[l + 1];
+    const LayerPlan& lp = c.plan.layer[l]; const bool last = l == L.n_gcn - 1;
+    gm_gemm_args g{}; g.A = c.Z[l]; g.lda = fi; g.B = params + L.w_off[l]; g.b_stride = pstride; g.C = c.H[l]; g.ldc = fo; g.K = fi; g.N = fo;
+    gemm_rows(g, batch_level(b)); g.bias = params + L.b_off[l]; g.bias_stride = pstride; g.relu = 1; g.relu_bits = lp.relu_bits ? c.M[l] : nullptr;
+    // the other rows are computed, their relu' bits written, their values not stored (the kept-row count is for the launch accounting)
+    if (lp.stored != ROWS_ALL) gemm_keep_rows(g, row_view(b, lp.stored, false), true, lp.dead_tiles, rows_kept(b, lp.stored, st));
+    if (lp.split) {
+        GM_TRY(weight_planes(c, params, pstride, l, 0, st, g));
+        GM_REQUIRE(!(last && c.plan.dq == DQ_CENTRE) || g.np == 3, GM_EINVAL, "forward: dQ is left to its centre rows, which needs the three-piece kernels");
+    }
+    if (last && c.plan.dq == DQ_ZEROED) g.zero_out = c.bufA;
+    if (lp.fuse) { g.A = x; g.lda = ldx; g.zside = c.Z[l]; g.ldz = fi; g.fuse2 = row_view(b, lp.formed, gather).tab; }
+    return gm_launch_gemm_nn(g, st);
+}
+// skip_head: the head (centre gather + linear) is evaluated by the fused k_head_loss launch that follows
+// kind: who reads the pass (PassKind); what follows from it is plan_pass's to decide
 static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* logits, hipStream_t st, int reuse_z1, int skip_head = 0, PassKind kind = PASS_PLAIN) {
     if (c.cone) return cone_forward(c, params, pstride, logits, st, reuse_z1, skip_head);
     const gm_layout& L = c.L; const gm_batch* b = c.b;
@@ -1110,7 +1315,7 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
     GM_REQUIRE((L.link != 0) == (b->centres == 2), GM_EINVAL, "forward: link_pred model needs a 2-centre batch and vice versa");
     const float* xin = c.x0_user;           // NULL = gather rows of the store through feat_row
     GM_TRY(plan_pass(c, params, pstride, kind, reuse_z1, &c.plan));
-    const PassPlan& plan = c.plan; const bool mean = mean_readout(c);
+    const bool mean = mean_readout(c);
     if (mean) GM_TRY(readout_tables(b, st));
     if (c.np == 2) {                        // a new pass: its own bound slots
         ++c.am_pass;
@@ -1119,66 +1324,13 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
         c.dqv = false;
     }
     for (int l = 0; l < L.n_gcn; ++l) {
-        const int fi = L.dims[l], fo = L.dims[l + 1];
-        const bool gather = (l == 0 && !c.x0_user);
-        const LayerPlan& lp = plan.layer[l]; uint8_t* relu_bits = lp.relu_bits ? c.M[l] : nullptr;
-        if (fi > fo) {                      // learner.py:34-40: multiply first, then aggregate
-            const float* A = xin; int64_t lda = fi;
-            if (gather) { GM_TRY(gm_gather_rows(b, b->d_feat_row, b->rows, fi, c.X0, st)); A = c.X0; }
-            gm_gemm_args g{}; g.A = A; g.lda = lda; g.B = params + L.w_off[l]; g.b_stride = pstride; g.C = c.Z[l]; g.ldc = fo; g.K = fi; g.N = fo;
-            g.row_scale = b->d_norm; g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows;
-            GM_TRY(gm_launch_gemm_nn(g, st));
-            gm_agg_args a; GM_TRY(batch_agg(c, 0, st, a));
-            a.x = c.Z[l]; a.ldx = fo; a.s_out = b->d_norm;
-            a.bias = params + L.b_off[l]; a.bias_stride = pstride; a.set_row_off = b->d_set_row_off; a.n_sets = b->sets; a.relu = 1;
-            a.out = c.H[l]; a.width = fo; a.relu_bits = relu_bits;
-            GM_TRY(launch_agg(a, gm_aggregate_bytes(b, fo), gm_aggregate_bytes(b, fo), st));
-        } else {                            // learner.py:41-47: aggregate first, then multiply
-            const float* x = gather ? b->feat : xin; const int64_t ldx = gather ? b->feat_ld : fi;      // the layer's input as the aggregate and the fused loader read it
-            if (!(l == 0 && reuse_z1 && c.z1_valid)) {
-                gm_agg_args a; GM_TRY(batch_agg(c, 0, st, a));
-                a.s_in = b->d_norm; a.e_w = b->d_enorm[0]; a.out = c.Z[l]; a.width = fi;
-                a.x = x; a.ldx = ldx; if (gather) { a.x_row = b->d_feat_row; a.x_idx = b->d_efeat; }
-                if (lp.fuse) {
-                    // only the rows the fused kernel does not form itself (more than GM_FUSE_MAXDEG sources): a partial launch
-                    a.skip_on = 1; a.skip_lo = 0; a.skip_hi = GM_FUSE_MAXDEG;
-                    if (b->d_mid && c.hub_set == 0 && gm_knob().agg_mid_list && (b->n_heavy[0] == 0 || b->d_sched_mid)) {
-                        // ... walking the compact list of those rows (hub rows keep their blocks; the schedule is the list's)
-                        a.rowlist = b->d_mid; a.n_list = b->n_mid; a.list_win = b->mid_win;
-                        if (b->n_heavy[0] > 0) { a.sched = b->d_sched_mid; a.sched_len = b->sched_len_mid; a.sched_win = b->mid_win; }
-                        else { a.sched = nullptr; a.sched_len = 0; }
-                    }
-                    // ... and of those only the rows the plan forms; the others stop at their descriptor (list entry, row bounds, flag)
-                    if (lp.formed != ROWS_ALL) { a.s_out = row_view(b, lp.formed, gather).sign; a.keep_signed = 1; }
-                    // ... walking the compact list of THOSE rows where the plan took it (no launch where the host knows it empty)
-                    if (lp.list && lp.list->take == 1) agg_take_list(a, *lp.list);
-                    if (!(lp.list && lp.list->take == 2)) {
-                        int64_t pb, pbs;
-                        GM_TRY(partial_agg_bytes(b, lp.formed, fi, gather, st, &pb, &pbs));
-                        GM_TRY(launch_agg(a, pb, pbs, st));
-                    }
-                } else {
-                    if (a.e_w) GM_TRY(gm_agg_stream_args(a, b, 0, gather, st));      // full launches may take the LDS-DMA stream kernel (agg_stream.hip)
-                    // compulsory HBM bytes: a gather launch reads rows of the (cache-resident) feature table, at most all of it
-                    int64_t strict = gm_aggregate_bytes(b, fi);
-                    if (gather) strict += 4 * b->rows - 4 * b->rows * (int64_t)fi + std::min<int64_t>(4 * b->rows * (int64_t)fi, 4 * b->feat_rows * (int64_t)fi);
-                    GM_TRY(launch_agg(a, gm_aggregate_bytes(b, fi), strict, st));
-                    if (l == 0) c.z1_valid = 1;
-                }
-            }
-            gm_gemm_args g{}; g.A = c.Z[l]; g.lda = fi; g.B = params + L.w_off[l]; g.b_stride = pstride; g.C = c.H[l]; g.ldc = fo; g.K = fi; g.N = fo;
-            g.row_scale = b->d_norm; g.bias = params + L.b_off[l]; g.bias_stride = pstride; g.relu = 1; g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows;
-            g.relu_bits = relu_bits;
-            // the other rows are computed, their relu' bits written, their values not stored (the kept-row count is for the launch accounting)
-            if (lp.stored != ROWS_ALL) { g.row_scale_keep = row_view(b, lp.stored, false).keep; g.n_keep = rows_kept(b, lp.stored, st); }
-            if (lp.dead_tiles) g.tile_live = row_view(b, lp.stored, false).live;
-            if (lp.split) {
-                GM_TRY(weight_planes(c, params, pstride, l, 0, st, g));
-                GM_REQUIRE(!(l == L.n_gcn - 1 && plan.dq == DQ_CENTRE) || g.np == 3, GM_EINVAL, "forward: dQ is left to its centre rows, which needs the three-piece kernels");
-            }
-            if (l == L.n_gcn - 1 && plan.dq == DQ_ZEROED) g.zero_out = c.bufA;
-            if (lp.fuse) { g.A = x; g.lda = ldx; g.zside = c.Z[l]; g.ldz = fi; g.fuse2 = row_view(b, lp.formed, gather).tab; }
-            GM_TRY(gm_launch_gemm_nn(g, st));
+        const int fi = L.dims[l];
+        if (fi > L.dims[l + 1]) GM_TRY(fwd_mul_first(c, l, params, pstride, xin, st));
+        else {
+            const bool gather = (l == 0 && !c.x0_user);
+            const float* x = gather ? b->feat : xin; const int64_t ldx = gather ? b->feat_ld : fi;
+            if (!(l == 0 && reuse_z1 && c.z1_valid)) GM_TRY(fwd_aggregate(c, l, x, ldx, gather, st));
+            GM_TRY(fwd_update(c, l, params, pstride, x, ldx, gather, st));
         }
         xin = c.H[l];
     }
@@ -1186,19 +1338,23 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
     return skip_head ? GM_OK : launch_head_fwd(c, params, pstride, logits, st);
 }
 
-static int gcn_backward_sparse(GcnCtx& c, const float* params, int64_t pstride, const float* dlogits, float* dparams, int64_t dstride, hipStream_t st, int skip_head);
-static bool sparse_bwd_ok(const gm_layout& L);
-
-// skip_head: dQ_L / the compact G2 and the head's own gradients were already produced by k_head_loss (head_loss below)
-static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const float* dlogits, float* dparams, int64_t dstride, hipStream_t st, int sparse = 0,
-                        int skip_head = 0) {
-    if (c.cone) return cone_backward(c, params, pstride, dlogits, dparams, dstride, st, skip_head);
-    if (sparse && sparse_bwd_ok(c.L)) return gcn_backward_sparse(c, params, pstride, dlogits, dparams, dstride, st, skip_head);
-    const gm_layout& L = c.L; const gm_batch* b = c.b; const int Lg = L.n_gcn;
-    float* dQ = c.bufA; float* T = c.bufB;
-    c.hold.n = 0;
-    const PassPlan& plan = c.plan;      // as the forward stored it: never derived again (gm_set_fuse_agg may have changed since)
-    const bool dq_centre = skip_head && plan.dq == DQ_CENTRE;      // dQ_L holds its centre rows only (head_loss); without skip_head it is filled right here
+// ---- The plan of one gcn_backward over a pass: what the forward's plan (GcnCtx::plan, as the forward stored it: never derived again -- gm_set_fuse_agg may have changed
+// since) permits, resolved against skip_head -- the one place that is done.  plan_backward decides it when gcn_backward starts; gcn_backward and its step functions execute it.
+// Per aggregate-first layer l (a multiply-first one has every row of everything and no choice of kernel):
+//  g_rows: the rows of dQ_l that were written -- dQ_L its centre rows, dQ_{L-1} the sources of the centres' in-edges; the other rows' bytes may be anything.  The weight
+//    gradient selects zeros for them (gm_wgrad_args::g_keep)
+//  dz: the kernel family of the dZ GEMM T_l = norm (dQ_l W_l^T) (DZ_NONE: the first layer has none), dz_tab: its loader reads dQ_l through gm_batch::d_dq_tab
+//  t_rows: the rows of T_l that GEMM stores, t_live: ... and it takes their tile flags (GM_DEAD_TILES)
+//  agg / t_ect / dq_rows / list: the transposed aggregate dQ_{l-1} = relu' norm A^T T_l launches at all (not below the first layer, not where the host knows its list
+//    empty: obs_list::take == 2); reads T_l through gm_batch::d_ect; stores these rows of dQ_{l-1} (= g_rows of the layer below); walks this list of them (NULL: every row's descriptor)
+// Per call, fill_dq: this call zero-fills dQ_L whole before the head writes its centre rows (neither behind head_loss nor under the mean readout, whose backward writes every row)
+enum DzKind { DZ_NONE, DZ_SPLIT, DZ_WT, DZ_PLAIN };
+struct BwdLayer { RowSet g_rows; DzKind dz; bool dz_tab; RowSet t_rows; bool t_live, agg, t_ect; RowSet dq_rows; const gm_batch::obs_list* list; };
+struct BwdPlan { bool fill_dq; BwdLayer layer[GM_MAX_GCN]; };
+static int plan_backward(const GcnCtx& c, int skip_head, BwdPlan* out) {
+    const gm_layout& L = c.L; const PassPlan& plan = c.plan; const int last = L.n_gcn - 1;
+    BwdPlan p{}; p.fill_dq = !skip_head && !mean_readout(c);
+    const bool dq_centre = skip_head && plan.dq == DQ_CENTRE;      // dQ_L holds its centre rows only (head_loss); without skip_head it is filled in this call
     // GM_DEAD_ROWS=2: the same rule one level down.  Every row of T_L = norm (dQ_L W_L^T) outside the centre rows is an exact zero, and so is every row of dQ_{L-1} =
     // relu' norm A^T T_L that is not the source of an in-edge of a centre.  Every row is still computed, no product and no sum is dropped:
     //  * the dZ GEMM stores T_L's centre rows only (row_scale_keep = d_norm_c);
@@ -1209,267 +1365,148 @@ static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const f
     //  * where the layer below is the first, that aggregate stores only the rows of dQ_{L-1} that can be non-zero (s_out = d_norm_e1, keep_signed), and the first
     //    layer's weight gradient selects zeros for the others (g_keep).  Deeper models keep dQ_{L-1} whole: it is the A operand of a plain-loader dZ GEMM.
     const bool t_centre = dq_centre && plan.t_centre, dq_e1 = t_centre && plan.dq_e1;
-    const bool dq_filled = !skip_head && !mean_readout(c);      // this call zero-fills dQ_L whole (below) before the head writes its centre rows
-    if (!skip_head && mean_readout(c)) {      // G = dlogits Wl on the pooled rows, then every row of dQ_L from it
-        GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, nullptr, c.Gpool, st));
-        GM_TRY(readout_bwd(c, st));
-    } else if (!skip_head) {
-        GM_HIP(hipMemsetAsync(dQ, 0, sizeof(float) * b->rows * L.dims[Lg], st));
-        GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, dQ, nullptr, st));
-    }
-    for (int l = Lg - 1; l >= 0; --l) {
+    for (int l = last; l >= 0; --l) {
         const int fi = L.dims[l], fo = L.dims[l + 1];
-        const float* Xprev = l > 0 ? c.H[l - 1] : (c.x0_user ? c.x0_user : c.X0);
-        const float* maskprev = l > 0 ? c.H[l - 1] : nullptr;
-        const uint8_t* maskbits = l > 0 ? c.M[l - 1] : nullptr;           // packed relu'(H_{l-1}): 1/16 of the bytes of H_{l-1}
-        if (maskbits) maskprev = nullptr;
-        gm_wgrad_args w{}; w.chunks = b->d_chunks; w.n_chunks = b->n_chunks; w.set_chunk_off = b->d_set_chunk_off; w.sets = b->sets; w.rows = b->rows;
-        w.partial = c.partial; w.dW = dparams + L.w_off[l]; w.dw_stride = dstride; w.db = dparams + L.b_off[l]; w.db_stride = dstride;
-        w.a_scale = b->d_norm; w.K = fi; w.N = fo;
-        wgrad_sgd(w, c, l);
-        // the reduction (+ SGD step, weight planes) of a layer above the first is held back and launched with the first layer's: the new
-        // W_l has no reader before the next forward
-        w.hold = &c.hold; w.hold_this = l > 0 ? 1 : 0;
-        if (l > 0) w.partial = c.partial_l[l];
-        if (fi > fo) {
-            // dY = A^T (norm * dQ) ; dW = (norm*X)^T dY ; db = colsum(dQ) ; dQ_prev = relu'(H_prev) * norm * (dY W^T)
-            gm_agg_args a; GM_TRY(batch_agg(c, 1, st, a));
-            a.x = dQ; a.ldx = fo; a.s_in = b->d_norm; a.e_w = b->d_enorm[1]; a.out = T; a.width = fo;
-            GM_TRY(launch_agg(a, gm_aggregate_bytes(b, fo), gm_aggregate_bytes(b, fo), st));
-            w.A = Xprev; w.lda = fi; w.G = T; w.ldg = fo; w.Gb = dQ; w.ldgb = fo;
-            GM_TRY(gm_launch_wgrad(w, st));
-            if (l > 0) {
-                gm_gemm_args g{}; g.A = T; g.lda = fo; g.B = params + L.w_off[l]; g.b_stride = pstride; g.transB = 1; g.C = dQ; g.ldc = fi; g.K = fo; g.N = fi;
-                g.row_scale = b->d_norm; g.mask_h = maskprev; g.mask_b = maskbits; g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows;
-                GM_TRY(gm_launch_gemm_nn(g, st));
-            }
-        } else {
-            // dW = (norm*Z)^T dQ ; db = colsum(dQ) ; dZ = norm * (dQ W^T) ; dQ_prev = relu'(H_prev) * norm * A^T dZ
-            // Order: dZ GEMM (reads dQ and the CURRENT weights) -> weight gradient (reads dQ; its reduction writes the updated
-            // weights and, for the next step's dZ GEMM, their transpose) -> transposed aggregate (overwrites dQ).
-            w.A = c.Z[l]; w.lda = fi; w.G = dQ; w.ldg = fo;
-            // the rows of dQ_l that were written: dQ_L its centre rows, dQ_{L-1} the sources of the centres' in-edges; the other rows' bytes may be anything
-            const RowSet g_rows = (dq_centre && l == Lg - 1) ? ROWS_CENTRE : (dq_e1 && l == Lg - 2) ? ROWS_E1 : ROWS_ALL;
-            w.g_keep = row_view(b, g_rows, false).keep;
-            const RowSet z_rows = plan.layer[l].formed;
-            if (plan.layer[l].fuse) {            // the forward ran fused: Z[l] holds the rows of three or more sources, the table forms the others
-                const bool gather = l == 0 && !c.x0_user;
-                // GM_DEAD_ROWS=4: ... and of a restricted pass through the forward's own table: an unobservable row of A is the zero row -- the forward
-                // wrote neither its Z_l row nor (one layer down) the H_{l-1} rows the full table would gather for it
-                w.fuse2 = row_view(b, z_rows, gather).tab;
-                w.gx = gather ? b->feat : (l > 0 ? c.H[l - 1] : c.x0_user); w.ldgx = gather ? b->feat_ld : fi;
-            }
-            if (z_rows != ROWS_ALL) {          // (always tabled: plan_check)
-                // The zero rows of A stand in for finite rows the every-row pass multiplies by zero rows of G: those rows of G must BE zeros here too -- selected (g_keep:
-                // the backward behind head_loss, whose dQ holds the observable rows only), or true zeros because this very call filled dQ_L before the head
-                // wrote its centre rows (skip_head = 0: the meta-gradient through the last support pass, which runs over the Z / H / M that pass's restricted
-                // forward left).  Bitwise the every-row pass in both: a +-0 product added to a chain that started at +0 leaves the chain unchanged (bsum and the MFMA
-                // accumulators start at +0; a zero A row makes the same +-0 products as a finite one); in the second, dQ_L's other rows are the memset's +0, T_L's are
-                // +0 x norm, the transposed aggregate's +0-started chains over them stay +0, and the relu' select yields +0 whichever way the bit reads
-                GM_REQUIRE(w.g_keep || dq_filled, GM_EINVAL, "backward: layer %d was formed on its observable rows only, but its weight gradient got neither flagged rows of G (g_keep) nor a dQ this call zero-filled", l);
-                // launch accounting: A is fetched on the observable rows only (every other row reads the cache-resident zero row)
-                if (gm_prof_enabled()) w.a_rows = rows_kept(b, z_rows, st);
-            }
-            if (l > 0) {
-                gm_gemm_args g{}; g.A = dQ; g.lda = fo; g.C = T; g.ldc = fi; g.K = fo; g.N = fi;
-                g.row_scale = b->d_norm; g.tiles = b->d_tiles; g.n_tiles = b->n_tiles; g.rows = b->rows;
-                const bool use_split = dz_split_ok(c, l);
-                const bool use_wt = !use_split && c.WTl[l] && fi % 64 == 0 && fo % 16 == 0;
-                if (use_split) {
-                    // B = W^T with W stored [fi][fo]: the planes are W's own rows (no transpose), K = fo, N = fi
-                    GM_TRY(weight_planes(c, params, pstride, l, 1, st, g));
-                    g.B = params + L.w_off[l]; g.b_stride = pstride; g.transB = 1;
-                    // dQ_L with its centre rows only: the fused kernel's loader reads them through the batch's table (fma(0, 0, fma(x, 1, 0)) = x) and zeros for
-                    // every other row -- the same tile, bit for bit, as the plain launch over a zero-filled dQ.  (plan_pass chose DQ_CENTRE under dz_centre_ok, which
-                    // holds for a context or not at all: a dQ_L left to its centre rows always comes this way)
-                    if (dq_centre && l == Lg - 1) { g.fuse2 = b->d_dq_tab; g.zside = dQ; g.ldz = fo; }
-                    if (t_centre && l == Lg - 1) { g.row_scale_keep = row_view(b, ROWS_CENTRE, false).keep; g.n_keep = rows_kept(b, ROWS_CENTRE, st); }
-                    if (t_centre && l == Lg - 1 && plan.t_dead_tiles) g.tile_live = row_view(b, ROWS_CENTRE, false).live;
-                } else if (use_wt) {
-                    // dZ = dQ @ W^T through the direct-to-LDS kernel on transposed weights: left there by the previous step's
-                    // weight-gradient reduction (which wrote these very weights), else transposed now (T x 256 KB)
-                    if (!(c.wt_of[l] == params && c.wt_stride[l] == pstride)) {
-                        const int nt = pstride ? b->sets : 1;         // shared theta (step 0): one transpose serves every task
-                        hipLaunchKernelGGL(k_transpose_w, dim3((fo + 31) / 32, (fi + 31) / 32, nt), dim3(256), 0, st, params, pstride, L.w_off[l], fi, fo, c.WTl[l]);
-                        GM_HIP(hipGetLastError());
-                        c.wt_of[l] = params; c.wt_stride[l] = pstride;
-                    }
-                    g.B = c.WTl[l]; g.b_stride = pstride ? (int64_t)fi * fo : 0; g.transB = 0;
-                } else { g.B = params + L.w_off[l]; g.b_stride = pstride; g.transB = 1; }
-                GM_TRY(gm_launch_gemm_nn(g, st));
-                if (use_wt && c.sgd.next) { w.wt_next = c.WTl[l]; }
-            }
-            int kn = 0;
-            if (c.pd && c.sgd.next && (kn = c.pd->index_of(c.sgd.next)) != 0) { w.pl_fwd = c.pd->slot(kn, l, 0); w.pl_dz = c.pd->slot(kn, l, 1); }
-            if (c.np == 2) {
-                gm_bound ab, gb;
-                if (in_bound(c, l, ab) && dq_bound(c, l, gb)) { w.np = 2; w.a_bound = ab; w.g_bound = gb; }
-                if (kn) {                                                  // two-piece planes of the updated weights, under the step's weight bound
-                    if (c.pd->w_bound(c.sgd.next, l, w.pl_bound)) w.pl_np = 2; else { w.pl_fwd = nullptr; w.pl_dz = nullptr; }
-                }
-            }
-            GM_TRY(gm_launch_wgrad(w, st));
-            if (kn) { c.pd->valid[kn][l][0] = w.pl_fwd != nullptr; c.pd->valid[kn][l][1] = w.pl_dz != nullptr; }
-            if (w.wt_next) { c.wt_of[l] = c.sgd.next; c.wt_stride[l] = c.sgd.next_stride; }
-            if (l > 0) {
-                gm_agg_args a; GM_TRY(batch_agg(c, 1, st, a));
-                a.x = T; a.ldx = fi; a.s_out = b->d_norm; a.mask_h = maskprev; a.mask_b = maskbits;
-                a.out = dQ; a.width = fi;
-                int64_t by = gm_aggregate_bytes(b, fi);
-                if (t_centre && l == Lg - 1) {
-                    a.x_idx = b->d_ect;
-                    const RowSet out = dq_e1 ? ROWS_E1 : ROWS_ALL;      // the rows the launch works on (every other row leaves behind its descriptor)
-                    if (dq_e1) { a.s_out = row_view(b, out, false).keep; a.keep_signed = 1; }
-                    if (dq_e1 && plan.t_list && plan.t_list->take == 1) agg_take_list(a, *plan.t_list);
-                    by = t_centre_agg_bytes(b, out, fi, maskbits != nullptr, st);
-                }
-                if (!(t_centre && l == Lg - 1 && dq_e1 && plan.t_list && plan.t_list->take == 2)) GM_TRY(launch_agg(a, by, by, st));
-            }
+        BwdLayer& bl = p.layer[l];
+        if (fi > fo) continue;
+        bl.g_rows = l == last ? (dq_centre ? ROWS_CENTRE : ROWS_ALL) : p.layer[l + 1].dq_rows;
+        // The zero rows of A of a layer formed on its observable rows only (GM_DEAD_ROWS=4; always tabled: plan_check) stand in for finite rows the every-row pass multiplies
+        // by zero rows of G: those rows of G must BE zeros here too -- selected (g_keep: the backward behind head_loss, whose dQ holds the observable rows only), or true
+        // zeros because this very call filled dQ_L before the head wrote its centre rows (skip_head = 0: the meta-gradient through the last support pass, which runs over the
+        // Z / H / M that pass's restricted forward left).  Bitwise the every-row pass in both: a +-0 product added to a chain that started at +0 leaves the chain unchanged
+        // (bsum and the MFMA accumulators start at +0; a zero A row makes the same +-0 products as a finite one); in the second, dQ_L's other rows are the memset's +0, T_L's
+        // are +0 x norm, the transposed aggregate's +0-started chains over them stay +0, and the relu' select yields +0 whichever way the bit reads
+        GM_REQUIRE(plan.layer[l].formed == ROWS_ALL || row_view(c.b, bl.g_rows, false).keep || p.fill_dq, GM_EINVAL, "backward: layer %d was formed on its observable rows only, but its weight gradient got neither flagged rows of G (g_keep) nor a dQ this call zero-filled", l);
+        if (l == 0) continue;
+        bl.dz = dz_split_ok(c, l) ? DZ_SPLIT : (c.WTl[l] && fi % 64 == 0 && fo % 16 == 0) ? DZ_WT : DZ_PLAIN;
+        // dQ_L with its centre rows only: the fused kernel's loader reads them through the batch's table (fma(0, 0, fma(x, 1, 0)) = x) and zeros for every other row -- the
+        // same tile, bit for bit, as the plain launch over a zero-filled dQ.  (plan_pass chose DQ_CENTRE under dz_centre_ok, which holds for a context or not at all: a
+        // dQ_L left to its centre rows always comes this way)
+        bl.dz_tab = bl.dz == DZ_SPLIT && dq_centre && l == last;
+        bl.t_rows = (bl.dz == DZ_SPLIT && t_centre && l == last) ? ROWS_CENTRE : ROWS_ALL;
+        bl.t_live = bl.t_rows == ROWS_CENTRE && plan.t_dead_tiles;
+        bl.t_ect = t_centre && l == last;
+        bl.dq_rows = (bl.t_ect && dq_e1) ? ROWS_E1 : ROWS_ALL;      // the rows that launch works on (every other row leaves behind its descriptor)
+        const gm_batch::obs_list* tl = bl.dq_rows == ROWS_E1 ? plan.t_list : nullptr;
+        bl.list = (tl && tl->take == 1) ? tl : nullptr;
+        bl.agg = !(tl && tl->take == 2);
+    }
+    *out = p; return GM_OK;
+}
+
+// ---- gcn_backward executes it; one step function per launch group of a layer.  w arrives with the batch's rows, the layer's outputs and its hold slot
+// relu'(H_{l-1}) as layer l's backward reads it: the packed bits where the context has them (1/16 of the bytes of H_{l-1}), else H_{l-1} itself; nothing below the first layer
+struct ReluMask { const float* h; const uint8_t* bits; };
+static ReluMask relu_mask(const GcnCtx& c, int l) { const uint8_t* m = l > 0 ? c.M[l - 1] : nullptr; return {(l > 0 && !m) ? c.H[l - 1] : nullptr, m}; }
+// multiply-first: dY = A^T (norm * dQ) ; dW = (norm*X)^T dY ; db = colsum(dQ) ; dQ_prev = relu'(H_prev) * norm * (dY W^T)
+static int bwd_mul_first(GcnCtx& c, int l, gm_wgrad_args& w, const float* params, int64_t pstride, hipStream_t st) {
+    const gm_layout& L = c.L; const gm_batch* b = c.b; const int fi = L.dims[l], fo = L.dims[l + 1];
+    float* dQ = c.bufA; float* T = c.bufB;
+    gm_agg_args a; GM_TRY(batch_agg(b, 1, c.hub_set, st, a));
+    a.x = dQ; a.ldx = fo; a.s_in = b->d_norm; a.e_w = b->d_enorm[1]; a.out = T; a.width = fo;
+    GM_TRY(launch_agg(a, gm_aggregate_bytes(b, fo), gm_aggregate_bytes(b, fo), st));
+    w.A = l > 0 ? c.H[l - 1] : (c.x0_user ? c.x0_user : c.X0); w.lda = fi; w.G = T; w.ldg = fo; w.Gb = dQ; w.ldgb = fo;
+    GM_TRY(gm_launch_wgrad(w, st));
+    if (l == 0) return GM_OK;
+    gm_gemm_args g{}; g.A = T; g.lda = fo; g.B = params + L.w_off[l]; g.b_stride = pstride; g.transB = 1; g.C = dQ; g.ldc = fi; g.K = fo; g.N = fi;
+    const ReluMask m = relu_mask(c, l);
+    gemm_rows(g, batch_level(b)); g.mask_h = m.h; g.mask_b = m.bits;
+    return gm_launch_gemm_nn(g, st);
+}
+// aggregate-first: dW = (norm*Z)^T dQ ; db = colsum(dQ) ; dZ = norm * (dQ W^T) ; dQ_prev = relu'(H_prev) * norm * A^T dZ
+// Order: dZ GEMM (reads dQ and the CURRENT weights) -> weight gradient (reads dQ; its reduction writes the updated
+// weights and, for the next step's dZ GEMM, their transpose) -> transposed aggregate (overwrites dQ).
+// The weight gradient's operands: G = dQ_l on the rows that were written, A = Z_l as the forward left it
+static void bwd_wgrad_operands(const GcnCtx& c, int l, const BwdLayer& bl, gm_wgrad_args& w, hipStream_t st) {
+    const gm_batch* b = c.b; const int fi = c.L.dims[l]; const LayerPlan& lp = c.plan.layer[l];
+    w.A = c.Z[l]; w.lda = fi; w.G = c.bufA; w.ldg = c.L.dims[l + 1];
+    w.g_keep = row_view(b, bl.g_rows, false).keep;
+    if (lp.fuse) {            // the forward ran fused: Z[l] holds the rows of three or more sources, the table forms the others
+        const bool gather = l == 0 && !c.x0_user;
+        // GM_DEAD_ROWS=4: ... and of a restricted pass through the forward's own table: an unobservable row of A is the zero row -- the forward
+        // wrote neither its Z_l row nor (one layer down) the H_{l-1} rows the full table would gather for it
+        w.fuse2 = row_view(b, lp.formed, gather).tab;
+        w.gx = gather ? b->feat : (l > 0 ? c.H[l - 1] : c.x0_user); w.ldgx = gather ? b->feat_ld : fi;
+    }
+    // launch accounting: A is fetched on the observable rows only (every other row reads the cache-resident zero row)
+    if (lp.formed != ROWS_ALL && gm_prof_enabled()) w.a_rows = rows_kept(b, lp.formed, st);
+}
+// T_l = norm (dQ_l W_l^T), K = fo, N = fi, on the plan's kernel family
+static int bwd_dz(GcnCtx& c, int l, const BwdLayer& bl, gm_wgrad_args& w, const float* params, int64_t pstride, hipStream_t st) {
+    const gm_layout& L = c.L; const gm_batch* b = c.b; const int fi = L.dims[l], fo = L.dims[l + 1];
+    gm_gemm_args g{}; g.A = c.bufA; g.lda = fo; g.C = c.bufB; g.ldc = fi; g.K = fo; g.N = fi;
+    gemm_rows(g, batch_level(b));
+    g.B = params + L.w_off[l]; g.b_stride = pstride; g.transB = 1;
+    if (bl.dz == DZ_SPLIT) {
+        // B = W^T with W stored [fi][fo]: the planes are W's own rows (no transpose)
+        GM_TRY(weight_planes(c, params, pstride, l, 1, st, g));
+        if (bl.dz_tab) gemm_dq_table(g, b, c.bufA, fo);
+        if (bl.t_rows != ROWS_ALL) gemm_keep_rows(g, row_view(b, bl.t_rows, false), true, bl.t_live, rows_kept(b, bl.t_rows, st));
+    } else if (bl.dz == DZ_WT) {
+        // dZ = dQ @ W^T through the direct-to-LDS kernel on transposed weights: left there by the previous step's
+        // weight-gradient reduction (which wrote these very weights), else transposed now (T x 256 KB)
+        if (!(c.wt_of[l] == params && c.wt_stride[l] == pstride)) {
+            const int nt = pstride ? b->sets : 1;         // shared theta (step 0): one transpose serves every task
+            hipLaunchKernelGGL(k_transpose_w, dim3((fo + 31) / 32, (fi + 31) / 32, nt), dim3(256), 0, st, params, pstride, L.w_off[l], fi, fo, c.WTl[l]);
+            GM_HIP(hipGetLastError());
+            c.wt_of[l] = params; c.wt_stride[l] = pstride;
+        }
+        g.B = c.WTl[l]; g.b_stride = pstride ? (int64_t)fi * fo : 0; g.transB = 0;
+        if (c.sgd.next) w.wt_next = c.WTl[l];
+    }
+    return gm_launch_gemm_nn(g, st);
+}
+// ... the weight gradient: planes of the updated weights for the next step's GEMMs, two-piece bounds, the launch, and what it left behind
+static int bwd_wgrad(GcnCtx& c, int l, gm_wgrad_args& w, hipStream_t st) {
+    int kn = 0;
+    if (c.pd && c.sgd.next && (kn = c.pd->index_of(c.sgd.next)) != 0) { w.pl_fwd = c.pd->slot(kn, l, 0); w.pl_dz = c.pd->slot(kn, l, 1); }
+    if (c.np == 2) {
+        gm_bound ab, gb;
+        if (in_bound(c, l, ab) && dq_bound(c, l, gb)) { w.np = 2; w.a_bound = ab; w.g_bound = gb; }
+        if (kn) {                                                  // two-piece planes of the updated weights, under the step's weight bound
+            if (c.pd->w_bound(c.sgd.next, l, w.pl_bound)) w.pl_np = 2; else { w.pl_fwd = nullptr; w.pl_dz = nullptr; }
         }
     }
-    return GM_OK;
-}
-
-static bool sparse_bwd_ok(const gm_layout& L) {
-    if (L.n_gcn > 2 || L.readout == GM_READOUT_MEAN) return false;      // (mean readout: dQ_L is dense, every row reaches the head)
-    for (int l = 0; l < L.n_gcn; ++l) if (L.dims[l] > L.dims[l + 1]) return false;      // aggregate-first layers only
-    return true;
-}
-
-// Exact row-sparse backward (see gm_hparams_t.sparse_bwd).  The head is the only consumer of the last GCN layer, so
-// dQ_L lives on the centre rows; one transposed-aggregate step spreads it along the in-edges of the centres.  Every
-// product below is the dense backward's product with the structurally-zero terms removed.
-static int gcn_backward_sparse(GcnCtx& c, const float* params, int64_t pstride, const float* dlogits, float* dparams, int64_t dstride, hipStream_t st, int skip_head) {
-    const gm_layout& L = c.L; const gm_batch* b = c.b;
-    const int Lg = L.n_gcn, fiL = L.dims[Lg - 1], foL = L.dims[Lg];
-    if (!skip_head) GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, nullptr, c.cG2, st));
-    // dW_L = sum_k norm[c_k] Z_L[c_k]^T G2[k] ; db_L = sum_k G2[k]
-    gm_wgrad_args w{}; w.A = c.Z[Lg - 1]; w.lda = fiL; w.K = fiL; w.a_row = b->d_crow; w.a_scale = b->d_cnorm; w.G = c.cG2; w.ldg = foL; w.N = foL;
-    w.rows = b->n_c; w.chunks = b->d_c_chunks; w.n_chunks = b->n_c_chunks; w.set_chunk_off = b->d_c_set_chunk_off; w.sets = b->sets; w.partial = c.partial_c;
-    w.dW = dparams + L.w_off[Lg - 1]; w.dw_stride = dstride; w.db = dparams + L.b_off[Lg - 1]; w.db_stride = dstride;
-    wgrad_sgd(w, c, Lg - 1);
     GM_TRY(gm_launch_wgrad(w, st));
-    if (Lg == 1) return GM_OK;
-    // T2[k] = norm[c_k] * (G2[k] W_L^T)
-    gm_gemm_args g{}; g.A = c.cG2; g.lda = foL; g.B = params + L.w_off[Lg - 1]; g.b_stride = pstride; g.transB = 1; g.C = c.cT2; g.ldc = fiL; g.K = foL; g.N = fiL;
-    g.row_scale = b->d_cnorm; g.tiles = b->d_c_tiles; g.n_tiles = b->n_c_tiles; g.rows = b->n_c;
-    GM_TRY(gm_launch_gemm_nn(g, st));
-    if (b->n_e1 > 0) {
-        const int64_t tot = (int64_t)b->n_e1 * fiL;
-        hipLaunchKernelGGL(k_expand_edges, dim3((int)std::min<int64_t>(2048, (tot + 255) / 256)), dim3(256), 0, st, c.cT2, c.H[0], fiL, b->d_e1_row, b->d_e1_par,
-                           b->weighted ? b->d_e1_coef : b->d_e1_norm, b->n_e1, c.cG1);      // (weighted batches: the edge's weight rides in the coefficient)
-        GM_HIP(hipGetLastError());
-    }
-    // dW_1 = sum_e norm[u_e] Z_1[u_e]^T G1[e] ; db_1 = sum_e G1[e]   (a set without any centre in-edge gets zeros: empty chunk range)
-    const int f0 = L.dims[0];
-    gm_wgrad_args w1{}; w1.A = c.Z[0]; w1.lda = f0; w1.K = f0; w1.a_row = b->d_e1_row; w1.a_scale = b->d_e1_norm; w1.G = c.cG1; w1.ldg = fiL; w1.N = fiL;
-    w1.rows = b->n_e1; w1.chunks = b->d_e1_chunks; w1.n_chunks = b->n_e1_chunks; w1.set_chunk_off = b->d_e1_set_chunk_off; w1.sets = b->sets; w1.partial = c.partial_c;
-    w1.dW = dparams + L.w_off[0]; w1.dw_stride = dstride; w1.db = dparams + L.b_off[0]; w1.db_stride = dstride;
-    wgrad_sgd(w1, c, 0);
-    GM_TRY(gm_launch_wgrad(w1, st));
+    if (kn) { c.pd->valid[kn][l][0] = w.pl_fwd != nullptr; c.pd->valid[kn][l][1] = w.pl_dz != nullptr; }
+    if (w.wt_next) { c.wt_of[l] = c.sgd.next; c.wt_stride[l] = c.sgd.next_stride; }
     return GM_OK;
 }
-
-
-// ================================================================================ receptive-field ("cone") schedule
-// The same layer formulas as gcn_forward/gcn_backward, evaluated only on the rows that can reach a centre
-// (cone.hip): layer l maps level l (sources) to level l+1 (destinations); all matrices are compact.
-
-// SURVEY 8(d)'s B_agg on the rows a level-to-level aggregate actually touches: the destination level's row bounds + norms, the edges between the
-// two levels, every source-level row read once (by construction each of them is the source of at least one of those edges), every
-// destination row written once
-static int64_t cone_agg_bytes(int64_t n_dst, int64_t n_src, int64_t nnz, int width) {
-    return 4 * (n_dst + 1) + 4 * nnz + 4 * n_dst + 4 * (n_src + n_dst) * (int64_t)width;
-}
-static int cone_launch_agg(const gm_agg_args& a, int64_t n_src, int64_t nnz, hipStream_t st) {
-    const int64_t by = cone_agg_bytes(a.rows, n_src, nnz, a.width);
+// ... dQ_{l-1} = relu'(H_{l-1}) norm A^T T_l, overwriting dQ
+static int bwd_agg_t(GcnCtx& c, int l, const BwdLayer& bl, hipStream_t st) {
+    const gm_batch* b = c.b; const int fi = c.L.dims[l]; const ReluMask m = relu_mask(c, l);
+    gm_agg_args a; GM_TRY(batch_agg(b, 1, c.hub_set, st, a));
+    a.x = c.bufB; a.ldx = fi; a.s_out = b->d_norm; a.mask_h = m.h; a.mask_b = m.bits;
+    a.out = c.bufA; a.width = fi;
+    if (bl.t_ect) agg_centre_t(a, b, bl.dq_rows);
+    if (bl.list) agg_take_list(a, *bl.list);
+    const int64_t by = bl.t_ect ? t_centre_agg_bytes(b, bl.dq_rows, fi, m.bits != nullptr, st) : gm_aggregate_bytes(b, fi);
     return launch_agg(a, by, by, st);
 }
-static gm_agg_args cone_agg(const gm_cone* cn, const gm_cone_level& up, int transposed) {
-    gm_agg_args a{};
-    a.indptr = transposed ? up.d_indptr_t : up.d_indptr; a.indices = transposed ? up.d_indices_t : up.d_indices;
-    a.heavy = up.d_heavy[transposed]; a.n_heavy = up.n_heavy[transposed]; a.heavy_deg = cn->heavy_deg;
-    a.e_w = transposed ? up.d_ew_t : up.d_ew;      // weighted batches (NULL otherwise): the edges' weights; launches that scale by the source's norm take d_enorm / d_enorm_t instead
-    return a;
-}
-
-static int cone_forward(GcnCtx& c, const float* params, int64_t pstride, float* logits, hipStream_t st, int reuse_z1, int skip_head) {
-    const gm_layout& L = c.L; const gm_batch* b = c.b; const gm_cone* cn = c.cone;
-    GM_TRY(gm_check_feat_dim(b, L.dims[0], "forward"));
-    GM_REQUIRE((L.link != 0) == (b->centres == 2), GM_EINVAL, "forward: link_pred model needs a 2-centre batch and vice versa");
-    GM_REQUIRE(!c.x0_user && !c.centre, GM_EINVAL, "forward: the cone schedule reads features and centres from the batch");
-    const float* xin = nullptr;
-    for (int l = 0; l < L.n_gcn; ++l) {
-        const gm_cone_level& lo = cn->lv[l]; const gm_cone_level& up = cn->lv[l + 1];
-        const int fi = L.dims[l], fo = L.dims[l + 1];
-        if (fi > fo) {                      // multiply on the source level, then aggregate into the destination level
-            const float* A = xin;
-            if (l == 0) { GM_TRY(gm_gather_rows(b, lo.d_feat_row, lo.n, fi, c.X0, st)); A = c.X0; }
-            gm_gemm_args g{}; g.A = A; g.lda = fi; g.B = params + L.w_off[l]; g.b_stride = pstride; g.C = c.Z[l]; g.ldc = fo; g.K = fi; g.N = fo;
-            g.row_scale = lo.d_norm; g.tiles = lo.d_tiles; g.n_tiles = lo.n_tiles; g.rows = lo.n;
-            GM_TRY(gm_launch_gemm_nn(g, st));
-            gm_agg_args a = cone_agg(cn, up, 0);
-            a.x = c.Z[l]; a.ldx = fo; a.s_out = up.d_norm; a.bias = params + L.b_off[l]; a.bias_stride = pstride; a.set_row_off = up.d_set_off; a.n_sets = b->sets;
-            a.relu = 1; a.out = c.H[l]; a.rows = up.n; a.width = fo;
-            GM_TRY(cone_launch_agg(a, lo.n, up.nnz, st));
-        } else {
-            if (!(l == 0 && reuse_z1 && c.z1_valid)) {
-                gm_agg_args a = cone_agg(cn, up, 0);
-                a.s_in = lo.d_norm; a.e_w = up.d_enorm; a.out = c.Z[l]; a.rows = up.n; a.width = fi; a.ldx = fi;
-                if (l == 0) { a.x = b->feat; a.x_row = lo.d_feat_row; a.x_idx = up.d_efeat; a.ldx = b->feat_ld; } else a.x = xin;
-                GM_TRY(cone_launch_agg(a, lo.n, up.nnz, st));
-                if (l == 0) c.z1_valid = 1;
-            }
-            gm_gemm_args g{}; g.A = c.Z[l]; g.lda = fi; g.B = params + L.w_off[l]; g.b_stride = pstride; g.C = c.H[l]; g.ldc = fo; g.K = fi; g.N = fo;
-            g.row_scale = up.d_norm; g.bias = params + L.b_off[l]; g.bias_stride = pstride; g.relu = 1; g.tiles = up.d_tiles; g.n_tiles = up.n_tiles; g.rows = up.n;
-            GM_TRY(gm_launch_gemm_nn(g, st));
-        }
-        xin = c.H[l];
+// skip_head: dQ_L / the compact G2 and the head's own gradients were already produced by k_head_loss (head_loss below)
+static int gcn_backward(GcnCtx& c, const float* params, int64_t pstride, const float* dlogits, float* dparams, int64_t dstride, hipStream_t st, int sparse = 0,
+                        int skip_head = 0) {
+    if (c.cone) return cone_backward(c, params, pstride, dlogits, dparams, dstride, st, skip_head);
+    if (sparse && sparse_bwd_ok(c.L)) return gcn_backward_sparse(c, params, pstride, dlogits, dparams, dstride, st, skip_head);
+    const gm_layout& L = c.L; const gm_batch* b = c.b;
+    BwdPlan bp; GM_TRY(plan_backward(c, skip_head, &bp));
+    c.hold.n = 0;
+    if (!skip_head) {      // dQ_L from the head: zero-filled and its centre rows written, or -- mean readout -- G = dlogits Wl on the pooled rows, then every row from it
+        if (bp.fill_dq) GM_HIP(hipMemsetAsync(c.bufA, 0, sizeof(float) * b->rows * L.dims[L.n_gcn], st));
+        GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, bp.fill_dq ? c.bufA : nullptr, bp.fill_dq ? nullptr : c.Gpool, st));
+        if (!bp.fill_dq) GM_TRY(readout_bwd(c, st));
     }
-    return skip_head ? GM_OK : launch_head_fwd(c, params, pstride, logits, st);
-}
-
-static int cone_backward(GcnCtx& c, const float* params, int64_t pstride, const float* dlogits, float* dparams, int64_t dstride, hipStream_t st, int skip_head) {
-    const gm_layout& L = c.L; const gm_batch* b = c.b; const gm_cone* cn = c.cone;
-    const int Lg = L.n_gcn;
-    float* dQ = c.bufA; float* T = c.bufB;
-    if (!skip_head) GM_TRY(launch_head_bwd(c, params, pstride, dlogits, dparams, dstride, nullptr, dQ, st));   // dQ_L on the centre rows
-    for (int l = Lg - 1; l >= 0; --l) {
-        const gm_cone_level& lo = cn->lv[l]; const gm_cone_level& up = cn->lv[l + 1];
-        const int fi = L.dims[l], fo = L.dims[l + 1];
-        const float* maskprev = l > 0 ? c.H[l - 1] : nullptr;
-        gm_wgrad_args w{}; w.sets = b->sets; w.partial = c.partial; w.K = fi; w.N = fo;
-        w.dW = dparams + L.w_off[l]; w.dw_stride = dstride; w.db = dparams + L.b_off[l]; w.db_stride = dstride;
-        wgrad_sgd(w, c, l);
-        if (fi > fo) {
-            // dY = A^T (norm * dQ) on the source level ; dW = (norm*X)^T dY ; db = colsum(dQ) ; dQ_prev = relu'(H_prev) * norm * (dY W^T)
-            gm_agg_args a = cone_agg(cn, up, 1);
-            a.x = dQ; a.ldx = fo; a.s_in = up.d_norm; a.e_w = up.d_enorm_t; a.out = T; a.rows = lo.n; a.width = fo;
-            GM_TRY(cone_launch_agg(a, up.n, up.nnz, st));
-            w.A = l > 0 ? c.H[l - 1] : c.X0; w.lda = fi; w.a_scale = lo.d_norm; w.G = T; w.ldg = fo; w.db = nullptr;
-            w.rows = lo.n; w.chunks = lo.d_chunks; w.n_chunks = lo.n_chunks; w.set_chunk_off = lo.d_set_chunk_off;
-            GM_TRY(gm_launch_wgrad(w, st));
-            hipLaunchKernelGGL(k_colsum_rows, dim3(b->sets), dim3(256), 0, st, dQ, (int64_t)fo, fo, up.d_set_off, dparams + L.b_off[l], dstride, c.sgd, L.b_off[l]);
-            GM_HIP(hipGetLastError());
-            if (l > 0) {
-                gm_gemm_args g{}; g.A = T; g.lda = fo; g.B = params + L.w_off[l]; g.b_stride = pstride; g.transB = 1; g.C = dQ; g.ldc = fi; g.K = fo; g.N = fi;
-                g.row_scale = lo.d_norm; g.mask_h = maskprev; g.tiles = lo.d_tiles; g.n_tiles = lo.n_tiles; g.rows = lo.n;
-                GM_TRY(gm_launch_gemm_nn(g, st));
-            }
-        } else {
-            // dW = (norm*Z)^T dQ ; db = colsum(dQ) ; dZ = norm * (dQ W^T) ; dQ_prev = relu'(H_prev) * norm * A^T dZ
-            w.A = c.Z[l]; w.lda = fi; w.a_scale = up.d_norm; w.G = dQ; w.ldg = fo;
-            w.rows = up.n; w.chunks = up.d_chunks; w.n_chunks = up.n_chunks; w.set_chunk_off = up.d_set_chunk_off;
-            GM_TRY(gm_launch_wgrad(w, st));
-            if (l > 0) {
-                gm_gemm_args g{}; g.A = dQ; g.lda = fo; g.B = params + L.w_off[l]; g.b_stride = pstride; g.transB = 1; g.C = T; g.ldc = fi; g.K = fo; g.N = fi;
-                g.row_scale = up.d_norm; g.tiles = up.d_tiles; g.n_tiles = up.n_tiles; g.rows = up.n;
-                GM_TRY(gm_launch_gemm_nn(g, st));
-                gm_agg_args a = cone_agg(cn, up, 1);
-                a.x = T; a.ldx = fi; a.s_out = lo.d_norm; a.mask_h = maskprev; a.out = dQ; a.rows = lo.n; a.width = fi;
-                GM_TRY(cone_launch_agg(a, up.n, up.nnz, st));
-            }
-        }
+    for (int l = L.n_gcn - 1; l >= 0; --l) {
+        const BwdLayer& bl = bp.layer[l];
+        // the reduction (+ SGD step, weight planes) of a layer above the first is held back and launched with the first layer's: the new
+        // W_l has no reader before the next forward
+        gm_wgrad_args w{}; wgrad_out(w, c, l, l > 0 ? c.partial_l[l] : c.partial, dparams, dstride); wgrad_rows(w, batch_level(b));
+        w.hold = &c.hold; w.hold_this = l > 0 ? 1 : 0;
+        if (L.dims[l] > L.dims[l + 1]) { GM_TRY(bwd_mul_first(c, l, w, params, pstride, st)); continue; }
+        bwd_wgrad_operands(c, l, bl, w, st);
+        if (bl.dz != DZ_NONE) GM_TRY(bwd_dz(c, l, bl, w, params, pstride, st));
+        GM_TRY(bwd_wgrad(c, l, w, st));
+        if (bl.agg) GM_TRY(bwd_agg_t(c, l, bl, st));
     }
     return GM_OK;
 }

@@ -11,8 +11,8 @@ Worlds and helpers: those of tests/test_hip_dead_rows_fwd.py (20,000-node prefer
 sample_nodes 160, every edge stored both ways; the same graph stored low id -> high id with the forced-split knobs), plus one
 link-prediction world (two centres per subgraph) cut from synth's FirstMM-shaped config.
 
-Not here: the GM_REQUIRE of gcn_backward that refuses a restricted layer whose weight gradient gets neither flagged rows of G nor a dQ the call filled.  It
-guards gcn_backward's own bookkeeping; the test exports gm_dense_wgrad_fused / gm_dense_fused_gemm launch the kernels below it and cannot reach it."""
+Not here: the GM_REQUIRE of plan_backward (csrc/model.hip) that refuses a restricted layer whose weight gradient gets neither flagged rows of G nor a dQ the call
+filled.  It guards the backward plan's own consistency; the test exports gm_dense_wgrad_fused / gm_dense_fused_gemm launch the kernels below it and cannot reach it."""
 import argparse
 import ctypes as C
 import random

@@ -209,6 +209,24 @@ def test_two_piece_launch_ignores_the_flags():
     assert (on['out'][~e.keep[0]] == SENTINEL).all() and (on['out'][e.keep[0]] != SENTINEL).all()
 
 
+def test_keep_launch_is_priced_on_the_kept_row_count_it_was_given():
+    """launch accounting, category 13 (A rows read once + the C rows the launch stores): a launch with a keep vector prices the kept-row count that comes with the
+    vector (gemm_keep_rows of csrc/model.hip sets both).  Through this export that count is every row of the batch, so the launch is priced exactly as the one
+    without a keep vector: 4 rows (K + N) bytes -- a count that went missing would price 4 rows K."""
+    L = _L()
+    e = env('sparse')
+    K, N = 128, 256
+    for keep in (1, 0):
+        ms, n, work = C.c_double(), C.c_int64(), C.c_int64()
+        L.lib().gm_profile_enable(1)
+        try:
+            launch('sparse', 0, K, N, True, 0, keep=keep)
+            L.lib().gm_profile_read(13, C.byref(ms), C.byref(n), C.byref(work))
+        finally:
+            L.lib().gm_profile_enable(0)
+        assert work.value == 4 * e.rows * (K + N), (keep, work.value, 4 * e.rows * (K + N))
+
+
 # ---------------------------------------------------------------------------------------------------- the step
 def test_meta_step_is_bitwise_the_step_without_the_flags():
     """one two-layer arxiv-shaped Meta.forward (the world of tests/test_hip_pass_plan.py, split kernels forced) at GM_DEAD_TILES 0 and 1: accuracies, query losses,
