@@ -1,4 +1,9 @@
-"""TEST INFRASTRUCTURE ONLY -- CPU restatement (numpy, float32) of G-Meta's inner-loop hot path.
+"""TEST INFRASTRUCTURE ONLY -- CPU restatement (numpy, float32 by default) of G-Meta's inner-loop hot path.
+
+The step functions (classifier_forward / classifier_backward, agg / agg_t, the proto_loss* functions, protos_to_dlogits, task_inner_loop, meta_step)
+take a `dtype`.  At the default, float32, they are what they always were, bit for bit (tests/test_oracle_golden.py).  At float64 the same statements
+run on the widened fp32 inputs and are the reference the end-to-end numerics tests hold the device to (tests/test_step_ref.py,
+tests/test_hip_step_numerics.py); update_lr enters as float(np.float32(update_lr)), the value the kernels receive, in both precisions.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module,
 and only as the checker / reported baseline.  The product (g-meta_amd/) never imports it.
@@ -192,8 +197,29 @@ def _load_c():
     return _clib
 
 
-def agg(indptr, indices, x):
-    """update_all(copy_src, sum) (learner.py:38-39,44-45): out[v] = sum_{u in row v} x[u]."""
+def _kw(dtype):
+    """Keyword arguments that hand `dtype` on to another step function: none at float32, so that at the default every internal call is the call it always was
+    (tests/ragged_ref.py, readout_ref.py and edge_weight_ref.py stand their own float32 versions of some of these functions in)."""
+    return {} if dtype == f32 else {'dtype': dtype}
+
+
+def _agg_reduceat(indptr, indices, x):
+    """Row sums of x[indices] over the CSR rows with np.add.reduceat over the starts of the non-empty rows (an empty row has no element between two
+    starts, so leaving its start out keeps every other segment right); empty rows stay zero.  Each row is summed in edge order."""
+    indptr = np.asarray(indptr, np.int64)
+    out = np.zeros((len(indptr) - 1, x.shape[1]), x.dtype)
+    nz = np.diff(indptr) > 0
+    if nz.any():
+        out[nz] = np.add.reduceat(x[np.asarray(indices, np.int64)], indptr[:-1][nz], axis=0)
+    return out
+
+
+def agg(indptr, indices, x, dtype=f32):
+    """update_all(copy_src, sum) (learner.py:38-39,44-45): out[v] = sum_{u in row v} x[u].
+    float32: the C helper (or np.add.at without it).  Any other dtype: np.add.reduceat over the CSR with the empty rows fixed up (_agg_reduceat) --
+    np.add.at over rows x width elements takes minutes at 15k rows x 256."""
+    if dtype != f32:
+        return _agg_reduceat(indptr, indices, np.asarray(x, dtype))
     lib = _load_c()
     x = np.ascontiguousarray(x, f32)
     n = len(indptr) - 1
@@ -220,8 +246,11 @@ def _by_source(batch):
     return c
 
 
-def agg_t(batch, g):
-    """autograd backward of update_all: grad_x[u] = sum_{(u->v)} g[v] (transposed pass)."""
+def agg_t(batch, g, dtype=f32):
+    """autograd backward of update_all: grad_x[u] = sum_{(u->v)} g[v] (transposed pass).  Other than float32: np.add.reduceat over the by-source CSR."""
+    if dtype != f32:
+        ptr, idx = _by_source(batch)
+        return _agg_reduceat(ptr, idx, np.asarray(g, dtype))
     lib = _load_c()
     if lib and hasattr(lib, 'oracle_agg_t_f32'):
         ptr, idx = _by_source(batch)
@@ -236,6 +265,42 @@ def agg_t(batch, g):
 
 
 # =========================================================================== model (a6, a7)
+_SEQUENTIAL = False
+
+
+class sequential_products:
+    """Inside this context every float32 matrix product of the step functions is an fmaf chain over its contraction index, acc = fma(a[:, k], b[k, :], acc)
+    for k = 0, 1, ..: the arithmetic of k_gemm_nn and k_wgrad (csrc/gemm.hip: v_mfma_f32_32x32x2_f32, "bit-for-bit an fmaf chain"; k_wgrad over the rows
+    of a chunk), where numpy's BLAS adds blocked partial sums.  The fma is formed in float64 -- the product of two fp32 numbers is exact there, the sum is
+    rounded to 53 bits and then to 24, which differs from a true fmaf only on rare double-rounding ties.  Both orders are honest fp32 products;
+    tests/test_hip_gemm_numerics.py, test_hip_gemm_epilogue.py and test_hip_wgrad_numerics.py hold those kernels to the K * 2^-24 bound of such a chain.  The
+    end-to-end numerics tests take the larger error of the two orders as their yardstick on the small worlds those kernels serve (tests/step_bar.py).
+    Other dtypes: the same chain with a plain multiply and add.  Default: off, numpy's own product."""
+
+    def __enter__(self):
+        global _SEQUENTIAL
+        self.was, _SEQUENTIAL = _SEQUENTIAL, True
+
+    def __exit__(self, *exc):
+        global _SEQUENTIAL
+        _SEQUENTIAL = self.was
+        return False
+
+
+def _mm(a, b):
+    if not _SEQUENTIAL:
+        return a @ b
+    if a.dtype == f32 and b.dtype == f32:
+        acc = np.zeros((a.shape[0], b.shape[1]), f32)
+        a64, b64 = a.astype(np.float64), b.astype(np.float64)
+        for k in range(a.shape[1]):
+            acc = (a64[:, k:k + 1] * b64[k:k + 1, :] + acc).astype(f32)
+        return acc
+    acc = np.zeros((a.shape[0], b.shape[1]), np.result_type(a, b))
+    for k in range(a.shape[1]):
+        acc += a[:, k:k + 1] * b[k:k + 1, :]
+    return acc
+
 def parse_config(config):
     """train.py:67-75 config list -> (gcn dims, linear dims, link_pred)."""
     gcn = [tuple(p) for n, p in config if n == 'GraphConv']
@@ -244,23 +309,23 @@ def parse_config(config):
     return gcn, lin, link
 
 
-def classifier_forward(batch, x0, vars_, config):
+def classifier_forward(batch, x0, vars_, config, dtype=f32):
     """Classifier.forward (learner.py:134-175) with GraphConv.forward (learner.py:25-56).
     Returns logits [S,C] and a cache for the backward."""
     gcn, lin, link = parse_config(config)
     norm = batch.norm[:, None]
-    h = np.asarray(x0, f32)
+    h = np.asarray(x0, dtype)
     cache = []
     for l, (fi, fo) in enumerate(gcn):
         W, b = vars_[2 * l], vars_[2 * l + 1]
         xs = h * norm                                       # learner.py:32
         if fi > fo:                                         # learner.py:34-40 matmul first
-            y = xs @ W
-            z = agg(batch.indptr, batch.indices, y)
+            y = _mm(xs, W)
+            z = agg(batch.indptr, batch.indices, y, **_kw(dtype))
             pre = z
         else:                                               # learner.py:41-47 aggregate first
-            z = agg(batch.indptr, batch.indices, xs)
-            pre = z @ W
+            z = agg(batch.indptr, batch.indices, xs, **_kw(dtype))
+            pre = _mm(z, W)
         q = pre * norm + b                                  # learner.py:49-51
         hn = np.maximum(q, 0)                               # relu on every GCN layer (learner.py:97)
         cache.append((xs, z, hn, fi > fo))
@@ -268,22 +333,26 @@ def classifier_forward(batch, x0, vars_, config):
     rows = batch.centre_rows
     hc = h[rows[:, 0]] if rows.shape[1] == 1 else np.concatenate([h[rows[:, 0]], h[rows[:, 1]]], 1)  # learner.py:165-170
     Wl, bl = vars_[2 * len(gcn)], vars_[2 * len(gcn) + 1]
-    logits = hc @ Wl.T + bl                                 # F.linear (learner.py:174)
-    return logits.astype(f32), (cache, hc, h.shape)
+    logits = _mm(hc, Wl.T) + bl                                 # F.linear (learner.py:174)
+    return logits.astype(dtype), (cache, hc, h.shape)
 
 
-def classifier_backward(batch, vars_, config, fcache, dlogits):
-    """Manual reverse pass of classifier_forward; returns grads in `vars` order."""
+def classifier_backward(batch, vars_, config, fcache, dlogits, dtype=f32, bias_abs=None):
+    """Manual reverse pass of classifier_forward; returns grads in `vars` order.
+    `bias_abs`, a dict, receives per bias tensor (its index in `vars`) the size of what its gradient sums: the largest column sum of |dq| over the rows for a
+    GraphConv bias, the sum of |dlogits| for the head bias."""
     gcn, lin, link = parse_config(config)
     cache, hc, hshape = fcache
     L = len(gcn)
     grads = [None] * len(vars_)
     Wl = vars_[2 * L]
-    dlogits = np.asarray(dlogits, f32)
-    grads[2 * L] = dlogits.T @ hc
+    dlogits = np.asarray(dlogits, dtype)
+    grads[2 * L] = _mm(dlogits.T, hc)
     grads[2 * L + 1] = dlogits.sum(0)
-    dhc = dlogits @ Wl
-    dh = np.zeros(hshape, f32)
+    if bias_abs is not None:
+        bias_abs[2 * L + 1] = float(np.abs(dlogits).sum())
+    dhc = _mm(dlogits, Wl)
+    dh = np.zeros(hshape, dtype)
     rows = batch.centre_rows
     H = hshape[1]
     np.add.at(dh, rows[:, 0], dhc[:, :H])
@@ -295,16 +364,18 @@ def classifier_backward(batch, vars_, config, fcache, dlogits):
         xs, z, hn, mm_first = cache[l]
         dq = dh * (hn > 0)
         grads[2 * l + 1] = dq.sum(0)
+        if bias_abs is not None:
+            bias_abs[2 * l + 1] = float(np.abs(dq).sum(0).max())
         dpre = dq * norm
         if mm_first:
-            dy = agg_t(batch, dpre)
-            grads[2 * l] = xs.T @ dy
-            dxs = dy @ W.T if l > 0 else None
+            dy = agg_t(batch, dpre, **_kw(dtype))
+            grads[2 * l] = _mm(xs.T, dy)
+            dxs = _mm(dy, W.T) if l > 0 else None
         else:
-            grads[2 * l] = z.T @ dpre
-            dxs = agg_t(batch, dpre @ W.T) if l > 0 else None
+            grads[2 * l] = _mm(z.T, dpre)
+            dxs = agg_t(batch, _mm(dpre, W.T), **_kw(dtype)) if l > 0 else None
         dh = dxs * norm if l > 0 else None
-    return [g.astype(f32) for g in grads]
+    return [g.astype(dtype) for g in grads]
 
 
 # =========================================================================== losses (a8, a9)
@@ -325,7 +396,7 @@ def _class_rows(y, limit=None):
     return classes, np.stack(rows)                          # [C_task, n]
 
 
-def proto_loss(logits, rows, protos):
+def proto_loss(logits, rows, protos, dtype=f32):
     """Shared tail of meta.py:44-53 / 68-78.  rows [C_task,n]; returns loss, acc, G=dL/d(-dist)."""
     C, n = rows.shape
     q = logits[rows.reshape(-1)]                            # grouped by class
@@ -335,16 +406,16 @@ def proto_loss(logits, rows, protos):
     logp = _log_softmax(-d)
     tgt = np.repeat(np.arange(C), n)
     loss = -logp[np.arange(C * n), tgt].mean()
-    acc = (logp.argmax(1) == tgt).astype(f32).mean()
-    G = np.exp(logp); G[np.arange(C * n), tgt] -= 1; G /= f32(C * n)   # dL/da, a = -d
-    return f32(loss), f32(acc), G.astype(f32), q, tgt
+    acc = (logp.argmax(1) == tgt).astype(dtype).mean()
+    G = np.exp(logp); G[np.arange(C * n), tgt] -= 1; G /= dtype(C * n)   # dL/da, a = -d
+    return dtype(loss), dtype(acc), G.astype(dtype), q, tgt
 
 
-def proto_loss_spt(logits, y, n_support, need_grad=True):
+def proto_loss_spt(logits, y, n_support, need_grad=True, dtype=f32):
     """meta.py:28-54.  Returns loss, acc, prototypes, dlogits (both roles summed)."""
     classes, rows = _class_rows(y, n_support)
-    protos = np.stack([logits[r].mean(0) for r in rows]).astype(f32)
-    loss, acc, G, q, tgt = proto_loss(logits, rows, protos)
+    protos = np.stack([logits[r].mean(0) for r in rows]).astype(dtype)
+    loss, acc, G, q, tgt = proto_loss(logits, rows, protos, **_kw(dtype))
     dl = None
     if need_grad:
         dl = np.zeros_like(logits)
@@ -353,67 +424,83 @@ def proto_loss_spt(logits, y, n_support, need_grad=True):
         dp = (G[:, :, None] * (2 * diff)).sum(0)            # prototype role [C,D]
         np.add.at(dl, rows.reshape(-1), dq)
         for c in range(len(classes)):
-            dl[rows[c]] += dp[c] / f32(rows.shape[1])
+            dl[rows[c]] += dp[c] / dtype(rows.shape[1])
     return loss, acc, protos, dl
 
 
-def proto_loss_qry(logits, y, protos, need_grad=False):
+def proto_loss_qry(logits, y, protos, need_grad=False, dtype=f32):
     """meta.py:56-79.  Returns loss, acc, (dlogits, dprotos) if need_grad."""
     classes, rows = _class_rows(y)
-    loss, acc, G, q, tgt = proto_loss(logits, rows, protos)
+    loss, acc, G, q, tgt = proto_loss(logits, rows, protos, **_kw(dtype))
     if not need_grad:
         return loss, acc, None, None
     diff = q[:, None, :] - protos[None, :, :]
     dl = np.zeros_like(logits)
     np.add.at(dl, rows.reshape(-1), (G[:, :, None] * (-2 * diff)).sum(1))
     dp = (G[:, :, None] * (2 * diff)).sum(0)
-    return loss, acc, dl.astype(f32), dp.astype(f32)
+    return loss, acc, dl.astype(dtype), dp.astype(dtype)
 
 
-def protos_to_dlogits(y, n_support, dprotos, shape):
+def protos_to_dlogits(y, n_support, dprotos, shape, dtype=f32):
     """Prototype path back into the support logits: prototype_c = mean of first n_support rows."""
     classes, rows = _class_rows(y, n_support)
-    dl = np.zeros(shape, f32)
+    dl = np.zeros(shape, dtype)
     for c in range(len(classes)):
-        dl[rows[c]] += dprotos[c] / f32(rows.shape[1])
+        dl[rows[c]] += dprotos[c] / dtype(rows.shape[1])
     return dl
 
 
 # =========================================================================== ProtoMAML (a10, a11)
-def task_inner_loop(spt, qry, x_spt, x_qry, y_spt, y_qry, theta, config, k_spt, update_lr, K, need_meta_grad, trace=None):
+def task_inner_loop(spt, qry, x_spt, x_qry, y_spt, y_qry, theta, config, k_spt, update_lr, K, need_meta_grad, trace=None, dtype=f32, detail=None):
     """One task of forward_ProtoMAML (meta.py:118-157) / finetunning_ProtoMAML (meta.py:197-229).
     Returns losses_q[K+1], accs_q[K+1], meta-grad list (first-order: query path at fw_K plus
-    prototype path through the support forward at fw_{K-1})."""
+    prototype path through the support forward at fw_{K-1}).
+    `detail`, a dict, receives what the device path can show of the task: 'fw' (the fast weights fw_0 .. fw_K), 'protos' (the support prototypes of steps
+    0 .. K-1), 'scored' (per k the query logits and the prototypes losses_q[k] scored them against; the last entry holds the last pass's logits), 'g_q' /
+    'g_p' (the two parts of the meta-gradient), 'bias_abs' (classifier_backward's, summed over the two backward passes that form them), 'dl_abs' (the sum of |dlogits| over both backward passes that form them) and 'dls_abs' (the sum of |dlogits| of
+    each inner step's support backward)."""
     if K < 2 and need_meta_grad:
         raise ValueError('update_step must be >= 2 (meta.py:129-141 are no_grad)')
-    lq, aq = np.zeros(K + 1, f32), np.zeros(K + 1, f32)
-    fw = [v.copy() for v in theta]
+    lr = dtype(float(f32(update_lr)))                       # the float the kernels receive, in either precision
+    lq, aq = np.zeros(K + 1, dtype), np.zeros(K + 1, dtype)
+    fw = [v.copy() if dtype == f32 else np.array(v, dtype) for v in theta]
     log = (lambda t, v: trace.append((t, v))) if trace is not None else (lambda t, v: None)
+    det = detail if detail is not None else {}
+    det.update(fw=[fw], protos=[], scored=[], g_q=None, g_p=None, dl_abs=None, bias_abs=None, dls_abs=[])
     # step 0 (meta.py:122-126)
-    logit_s, cs = classifier_forward(spt, x_spt, fw, config); log('logits', logit_s)
-    loss_s, _, protos, dls = proto_loss_spt(logit_s, y_spt, k_spt); log('loss_s', loss_s)
-    g = classifier_backward(spt, fw, config, cs, dls)
-    fw1 = [w - f32(update_lr) * gg for w, gg in zip(fw, g)]
+    logit_s, cs = classifier_forward(spt, x_spt, fw, config, **_kw(dtype)); log('logits', logit_s)
+    loss_s, _, protos, dls = proto_loss_spt(logit_s, y_spt, k_spt, **_kw(dtype)); log('loss_s', loss_s)
+    det['dls_abs'].append(float(np.abs(dls).sum()))
+    g = classifier_backward(spt, fw, config, cs, dls, **_kw(dtype))
+    fw1 = [w - lr * gg for w, gg in zip(fw, g)]
+    det['fw'].append(fw1); det['protos'].append(protos)
     # query before / after first update (meta.py:129-141), both against step-0 prototypes
     for k, w in ((0, fw), (1, fw1)):
-        logit_q, _ = classifier_forward(qry, x_qry, w, config); log('logits', logit_q)
-        lq[k], aq[k], _, _ = proto_loss_qry(logit_q, y_qry, protos); log('loss_q', lq[k])
+        logit_q, _ = classifier_forward(qry, x_qry, w, config, **_kw(dtype)); log('logits', logit_q)
+        lq[k], aq[k], _, _ = proto_loss_qry(logit_q, y_qry, protos, **_kw(dtype)); log('loss_q', lq[k])
+        det['scored'].append((logit_q, protos))
     fw_prev, fw = fw, fw1
     mg = None
     for k in range(1, K):                                   # meta.py:143-157
-        logit_s, cs = classifier_forward(spt, x_spt, fw, config); log('logits', logit_s)
-        loss_s, _, protos, dls = proto_loss_spt(logit_s, y_spt, k_spt); log('loss_s', loss_s)
-        g = classifier_backward(spt, fw, config, cs, dls)
-        fw_next = [w - f32(update_lr) * gg for w, gg in zip(fw, g)]
-        logit_q, cq = classifier_forward(qry, x_qry, fw_next, config); log('logits', logit_q)
+        logit_s, cs = classifier_forward(spt, x_spt, fw, config, **_kw(dtype)); log('logits', logit_s)
+        loss_s, _, protos, dls = proto_loss_spt(logit_s, y_spt, k_spt, **_kw(dtype)); log('loss_s', loss_s)
+        det['dls_abs'].append(float(np.abs(dls).sum()))
+        g = classifier_backward(spt, fw, config, cs, dls, **_kw(dtype))
+        fw_next = [w - lr * gg for w, gg in zip(fw, g)]
+        det['fw'].append(fw_next); det['protos'].append(protos)
+        logit_q, cq = classifier_forward(qry, x_qry, fw_next, config, **_kw(dtype)); log('logits', logit_q)
         last = need_meta_grad and k == K - 1
-        lq[k + 1], aq[k + 1], dlq, dpr = proto_loss_qry(logit_q, y_qry, protos, need_grad=last)
+        lq[k + 1], aq[k + 1], dlq, dpr = proto_loss_qry(logit_q, y_qry, protos, need_grad=last, **_kw(dtype))
         log('loss_q', lq[k + 1])
+        det['scored'].append((logit_q, protos))
         if last:
-            g_q = classifier_backward(qry, fw_next, config, cq, dlq)                    # d L_q / d fw_K
-            dls_p = protos_to_dlogits(y_spt, k_spt, dpr, logit_s.shape)
-            g_p = classifier_backward(spt, fw, config, cs, dls_p)                        # d L_q / d fw_{K-1}
+            ba_q, ba_p = {}, {}
+            ba = (lambda d: {'bias_abs': d}) if detail is not None else (lambda d: {})
+            g_q = classifier_backward(qry, fw_next, config, cq, dlq, **_kw(dtype), **ba(ba_q))            # d L_q / d fw_K
+            dls_p = protos_to_dlogits(y_spt, k_spt, dpr, logit_s.shape, **_kw(dtype))
+            g_p = classifier_backward(spt, fw, config, cs, dls_p, **_kw(dtype), **ba(ba_p))                # d L_q / d fw_{K-1}
             mg = [a + b for a, b in zip(g_q, g_p)]
+            det.update(g_q=g_q, g_p=g_p, dl_abs=float(np.abs(dlq).sum() + np.abs(dls_p).sum()), bias_abs={i: ba_q[i] + ba_p[i] for i in ba_q})
         fw = fw_next
     return lq, aq, mg
 
@@ -433,18 +520,23 @@ def adam_step(theta, grad, state, lr, b1=0.9, b2=0.999, eps=1e-8):
 
 
 def meta_step(graphs, feats, spt_batches, qry_batches, y_spt, y_qry, theta, config, k_spt,
-              update_lr, meta_lr, K, adam_state=None, trace=None):
-    """Meta.forward_ProtoMAML (meta.py:101-173) over T tasks.  Returns accs[K+1], grad, theta'."""
+              update_lr, meta_lr, K, adam_state=None, trace=None, dtype=f32, detail=None):
+    """Meta.forward_ProtoMAML (meta.py:101-173) over T tasks.  Returns accs[K+1], grad, theta', losses_q[K+1].
+    `detail`, a list, receives one dict per task (task_inner_loop) with that task's 'losses_q' and 'accs_q' added."""
     T = len(spt_batches)
     lq_sum, aq_sum = np.zeros(K + 1, np.float64), np.zeros(K + 1, np.float64)
-    gsum = [np.zeros_like(v) for v in theta]
+    gsum = [np.zeros_like(v, dtype=dtype) for v in theta]
     for t in range(T):
         xs, xq = spt_batches[t].features(feats), qry_batches[t].features(feats)
+        det = {} if detail is not None else None
         lq, aq, mg = task_inner_loop(spt_batches[t], qry_batches[t], xs, xq, y_spt[t], y_qry[t], theta, config,
-                                     k_spt, update_lr, K, True, trace)
+                                     k_spt, update_lr, K, True, trace, **_kw(dtype), **({'detail': det} if detail is not None else {}))
+        if detail is not None:
+            det.update(losses_q=lq, accs_q=aq)
+            detail.append(det)
         lq_sum += lq; aq_sum += aq
         gsum = [a + b for a, b in zip(gsum, mg)]
-    grad = [(g / f32(T)).astype(f32) for g in gsum]
+    grad = [(g / dtype(T)).astype(dtype) for g in gsum]
     loss_q = lq_sum[-1] / T
     new_theta = theta
     if not np.isnan(loss_q):                               # meta.py:163-169 NaN guard
