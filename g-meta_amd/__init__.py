@@ -17,7 +17,7 @@ from .learner import Classifier  # noqa: F401
 from .meta import Meta  # noqa: F401
 from .negatives import link_tables_with_negatives  # noqa: F401
 from .heuristics import (DISTANCE_SCORES, DIST_UNREACHED, PAGERANK_SCORES, PAIR_SCORES, PATH_SCORES, candidate_names, distance_profile_features,  # noqa: F401
-                         graph_distance_index, hll_cardinality, katz_index, link_distance_profiles, link_sketch_profiles,
+                         graph_distance_index, hll_cardinality, katz_index, link_distance_profiles, link_sketch_features, link_sketch_profiles,
                          link_auc, link_distance_auc, link_distance_scores, link_heuristic_auc, link_pagerank_auc, link_pagerank_scores, link_path_auc,
                          link_path_scores, link_propagated_features, local_path_index, rooted_pagerank_index, sketch_distance_profile, sketch_intersections, sketch_profile_features)
 from .sketches import NodeSketches  # noqa: F401
@@ -29,5 +29,5 @@ __all__ = ['GraphStore', 'Subgraphs', 'SubgraphBatch', 'collate', 'Classifier', 
            'link_path_auc', 'PAGERANK_SCORES', 'rooted_pagerank_index', 'link_pagerank_scores', 'link_pagerank_auc',
            'DISTANCE_SCORES', 'DIST_UNREACHED', 'graph_distance_index', 'link_distance_scores', 'link_distance_auc',
            'link_distance_profiles', 'distance_profile_features',
-           'NodeSketches', 'hll_cardinality', 'sketch_intersections', 'sketch_distance_profile', 'link_sketch_profiles', 'sketch_profile_features',
+           'NodeSketches', 'hll_cardinality', 'sketch_intersections', 'sketch_distance_profile', 'link_sketch_profiles', 'sketch_profile_features', 'link_sketch_features',
            'PropagatedFeatures', 'link_propagated_features', 'PairPredictor']

@@ -53,6 +53,7 @@ PROTOTYPES = {
     'gm_sketch_dims': (i32, [vp, vp, vp, vp, vp, vp]),
     'gm_sketch_registers': (i32, [vp, i32, vp, i64, vp, vp, vp]),
     'gm_sketch_pair_counts': (i32, [vp, vp, i64, vp, vp, vp]),
+    'gm_sketch_pair_features': (i32, [vp, vp, i64, i32, vp, i64, vp]),
     'gm_sketch_destroy': (None, [vp]),
     'gm_store_propagate_build': (i32, [vp, i32, i32, i32, vp, vp]),
     'gm_prop_dims': (i32, [vp, vp, vp, vp, vp, vp]),

@@ -12,6 +12,8 @@
 //   pairs       k_sketch_pairs<H + 1>: a wave per pair reads the 2 (H + 1) records once, chunk by chunk, and forms the (H + 1)^2 combinations: the matches as
 //               popcounts of ballots, the zero registers and the sum of 2^(32 - register) of the element-wise max in ONE 64-bit integer per lane (sk_term)
 //               reduced by shuffles; the finished entries go through LDS to plain vector stores of consecutive int64.  No atomics, no floats.
+//   features    k_sketch_pair_features<H + 1>: the same counting body (sk_pair_tab, ONE copy for both kernels), then the estimators of the header in fp64 in the
+//               same wave -- a lane per entry, a lane per cell, the cells through LDS -- and (H + 2)^2 consecutive float32 stores per pair.  No atomics.
 // A build runs on the caller's stream and is complete on the device when it returns; the sketch is read-only afterwards and holds no pointer into the store.
 #include "gm_columns.h"
 #include "gm_devutil.h"
@@ -155,22 +157,22 @@ __device__ __forceinline__ uint64_t sk_wave_sum(uint64_t x) {
     return x;
 }
 
-// out[e, L1, L1, 3] = (match, zeros, zsum) of the canonical pair's records at the levels (a, b); balls[e, 2, L1, 2] = (zeros, zsum) of u's, then v's, own records
+// one wave's LDS hand-over between its lanes: the wave's LDS operations issue in order, so nothing waits; the fences and the barrier keep the compiler from
+// moving an LDS access across the point
+__device__ __forceinline__ void sk_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// tab[0 .. E) = [L1, L1, 3] (match, zeros, zsum) of the canonical pair's records at the levels (a, b); tab[E .. E + EB) = [2, L1, 2] (zeros, zsum) of u's, then v's,
+// own records; all zeros for a node outside the graph.  The whole wave calls it (pa, pb wave-uniform); the entries are in the wave's LDS row when it returns
 template <int L1>
-__global__ void __launch_bounds__(GM_SK_THREADS) k_sketch_pairs(const uint32_t* __restrict__ sk, int64_t N, sk_shape sh, const int32_t* __restrict__ pairs, int64_t n,
-                                                                int64_t* __restrict__ out, int64_t* __restrict__ balls) {
+__device__ __forceinline__ void sk_pair_tab(const uint32_t* __restrict__ sk, int64_t N, const sk_shape& sh, int32_t pa, int32_t pb, int32_t lane, int64_t* tab) {
     constexpr int E = L1 * L1 * 3, EB = 2 * L1 * 2;
-    __shared__ int64_t tab[GM_SK_WAVES][E + EB];
-    const int32_t lane = (int32_t)threadIdx.x & (GM_WAVE - 1);
-    const int32_t wave = __builtin_amdgcn_readfirstlane((int32_t)threadIdx.x / GM_WAVE);
-    const int64_t e = (int64_t)blockIdx.x * GM_SK_WAVES + wave;
-    if (e >= n) return;                                                        // (a whole wave; no barrier below)
-    int64_t* o = out + e * E;
-    int64_t* ob = balls + e * EB;
-    const int32_t pa = pairs[2 * e], pb = pairs[2 * e + 1];
     if (pa < 0 || pa >= N || pb < 0 || pb >= N) {                              // (wave-uniform)
-        for (int i = lane; i < E; i += GM_WAVE) o[i] = 0;
-        for (int i = lane; i < EB; i += GM_WAVE) ob[i] = 0;
+        for (int i = lane; i < E + EB; i += GM_WAVE) tab[i] = 0;
+        sk_wave_sync();
         return;
     }
     const int64_t u = pa < pb ? pa : pb, v = pa < pb ? pb : pa;
@@ -214,19 +216,94 @@ __global__ void __launch_bounds__(GM_SK_THREADS) k_sketch_pairs(const uint32_t* 
         for (int b = 0; b < L1; ++b) {
             const uint64_t s = sk_wave_sum(zs[a][b]);
             if (lane == 0) {
-                tab[wave][(a * L1 + b) * 3] = match[a][b];
-                tab[wave][(a * L1 + b) * 3 + 1] = (int64_t)(s >> GM_SK_ZERO_SHIFT); tab[wave][(a * L1 + b) * 3 + 2] = (int64_t)(s & ((1ull << GM_SK_ZERO_SHIFT) - 1));
+                tab[(a * L1 + b) * 3] = match[a][b];
+                tab[(a * L1 + b) * 3 + 1] = (int64_t)(s >> GM_SK_ZERO_SHIFT); tab[(a * L1 + b) * 3 + 2] = (int64_t)(s & ((1ull << GM_SK_ZERO_SHIFT) - 1));
             }
         }
 #pragma unroll
         for (int side = 0; side < 2; ++side) {
             const uint64_t s = sk_wave_sum(bs[side][a]);
-            if (lane == 0) { tab[wave][E + (side * L1 + a) * 2] = (int64_t)(s >> GM_SK_ZERO_SHIFT); tab[wave][E + (side * L1 + a) * 2 + 1] = (int64_t)(s & ((1ull << GM_SK_ZERO_SHIFT) - 1)); }
+            if (lane == 0) { tab[E + (side * L1 + a) * 2] = (int64_t)(s >> GM_SK_ZERO_SHIFT); tab[E + (side * L1 + a) * 2 + 1] = (int64_t)(s & ((1ull << GM_SK_ZERO_SHIFT) - 1)); }
         }
     }
-    __builtin_amdgcn_wave_barrier();                                           // (lane 0's LDS stores are ordered ahead of the wave's loads: one wave, in order)
+    sk_wave_sync();                                                            // (lane 0's entries ahead of the wave's loads)
+}
+
+// out[e, L1, L1, 3], balls[e, 2, L1, 2] = the pair's entries as sk_pair_tab leaves them
+template <int L1>
+__global__ void __launch_bounds__(GM_SK_THREADS) k_sketch_pairs(const uint32_t* __restrict__ sk, int64_t N, sk_shape sh, const int32_t* __restrict__ pairs, int64_t n,
+                                                                int64_t* __restrict__ out, int64_t* __restrict__ balls) {
+    constexpr int E = L1 * L1 * 3, EB = 2 * L1 * 2;
+    __shared__ int64_t tab[GM_SK_WAVES][E + EB];
+    const int32_t lane = (int32_t)threadIdx.x & (GM_WAVE - 1);
+    const int32_t wave = __builtin_amdgcn_readfirstlane((int32_t)threadIdx.x / GM_WAVE);
+    const int64_t e = (int64_t)blockIdx.x * GM_SK_WAVES + wave;
+    if (e >= n) return;                                                        // (a whole wave; no barrier below)
+    int64_t* o = out + e * E;
+    int64_t* ob = balls + e * EB;
+    sk_pair_tab<L1>(sk, N, sh, pairs[2 * e], pairs[2 * e + 1], lane, tab[wave]);
     for (int i = lane; i < E; i += GM_WAVE) o[i] = tab[wave][i];
     for (int i = lane; i < EB; i += GM_WAVE) ob[i] = tab[wave][E + i];
+}
+
+// the HyperLogLog estimate of (zeros, zsum) at m = 2^p registers (include/gmeta_hip.h: card); every operation rounded once, in the header's order
+__device__ __forceinline__ double sk_card(int64_t zeros, int64_t zsum, double m, double alpha) {
+#pragma clang fp contract(off)
+    const double z = (double)zeros, s = (double)zsum / 4294967296.0;
+    if (!(s > 0.0)) return 0.0;
+    const double est = alpha * m * m / s;
+    return (est <= 2.5 * m && z > 0.0) ? m * log(m / z) : est;
+}
+
+// out[e * ld + 0 .. S) = the S = (L1 + 1)^2 structure columns of pair e (include/gmeta_hip.h: gm_sketch_pair_features), fp64 up to the final cast.  After the
+// counts a lane per entry forms the L1^2 intersections and the 2 L1 ball sizes, a lane per cell the table -- inner cells, then the last row and column, then
+// the corner, each phase reading the one before from the wave's LDS row -- and a lane per cell T and its column
+template <int L1>
+__global__ void __launch_bounds__(GM_SK_THREADS) k_sketch_pair_features(const uint32_t* __restrict__ sk, int64_t N, sk_shape sh, const int32_t* __restrict__ pairs, int64_t n,
+                                                                        int32_t symmetric, double m, double alpha, float* __restrict__ out, int64_t ld) {
+#pragma clang fp contract(off)
+    constexpr int E = L1 * L1 * 3, EB = 2 * L1 * 2, NC = L1 * L1, NB = 2 * L1, W = L1 + 1, S = W * W;
+    static_assert(NC + NB <= GM_WAVE && S <= GM_WAVE, "a lane per entry and per cell");
+    __shared__ int64_t tab[GM_SK_WAVES][E + EB];
+    __shared__ double est[GM_SK_WAVES][NC + NB];                               // C[a][b], then |B_a(u)|, then |B_a(v)|
+    __shared__ double cell[GM_SK_WAVES][S];
+    const int32_t lane = (int32_t)threadIdx.x & (GM_WAVE - 1);
+    const int32_t wave = __builtin_amdgcn_readfirstlane((int32_t)threadIdx.x / GM_WAVE);
+    const int64_t e = (int64_t)blockIdx.x * GM_SK_WAVES + wave;
+    if (e >= n) return;                                                        // (a whole wave; no barrier below)
+    const int32_t pa = pairs[2 * e], pb = pairs[2 * e + 1];
+    sk_pair_tab<L1>(sk, N, sh, pa, pb, lane, tab[wave]);
+    const int64_t* t = tab[wave];
+    double* C = est[wave];
+    double* P = cell[wave];
+    if (lane < NC) C[lane] = (double)t[lane * 3] / (double)sh.K * sk_card(t[lane * 3 + 1], t[lane * 3 + 2], m, alpha);
+    else if (lane < NC + NB) C[lane] = sk_card(t[E + (lane - NC) * 2], t[E + (lane - NC) * 2 + 1], m, alpha);
+    sk_wave_sync();
+    const int32_t a = lane / W, b = lane % W;                                  // the lane's cell
+    if (lane < S && a < L1 && b < L1) {                                        // the 2-D difference, along a first
+        const double up = a ? C[(a - 1) * L1 + b] : 0.0, left = b ? C[a * L1 + b - 1] : 0.0, diag = a && b ? C[(a - 1) * L1 + b - 1] : 0.0;
+        P[lane] = (C[a * L1 + b] - up) - (left - diag);
+    }
+    sk_wave_sync();
+    if (lane < S && (a == L1) != (b == L1)) {                                  // the ring of the ball minus the inner row / column
+        const int32_t side = a == L1, i = side ? b : a;
+        const double ring = C[NC + side * L1 + i] - (i ? C[NC + side * L1 + i - 1] : 0.0);
+        double sum = 0.0;
+        for (int j = 0; j < L1; ++j) sum = sum + (side ? P[j * W + i] : P[i * W + j]);
+        P[lane] = ring - sum;
+    }
+    sk_wave_sync();
+    if (lane == S - 1) {                                                       // the corner: every table sums to N
+        double sum = 0.0;
+        for (int j = 0; j < S - 1; ++j) sum = sum + P[j];
+        P[lane] = (double)N - sum;
+    }
+    sk_wave_sync();
+    if (lane < S) {
+        const double own = P[lane], other = P[b * W + a];
+        const double T = symmetric ? own + other : (pa <= pb ? own : other);
+        out[e * ld + lane] = (float)log1p(T > 0.0 ? T : 0.0);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------- host
@@ -343,6 +420,35 @@ extern "C" int32_t gm_sketch_pair_counts(const gm_sketch_t* sk, const int32_t* d
         case 2: sk_pairs<3>(st, sk, sh, d_pairs, n, d_out, d_out_balls); break;
         case 3: sk_pairs<4>(st, sk, sh, d_pairs, n, d_out, d_out_balls); break;
         default: sk_pairs<5>(st, sk, sh, d_pairs, n, d_out, d_out_balls); break;
+    }
+    GM_HIP(hipGetLastError());
+    return GM_OK;
+}
+
+template <int L1>
+static void sk_pair_features(hipStream_t st, const gm_sketch* sk, const sk_shape& sh, const int32_t* d_pairs, int64_t n, int32_t symmetric, double m, double alpha,
+                             float* d_out, int64_t ld) {
+    hipLaunchKernelGGL(k_sketch_pair_features<L1>, dim3(sk_grid(n)), dim3(GM_SK_THREADS), 0, st, (const uint32_t*)sk->d, sk->N, sh, d_pairs, n, symmetric, m, alpha, d_out, ld);
+}
+
+extern "C" int32_t gm_sketch_pair_features(const gm_sketch_t* sk, const int32_t* d_pairs, int64_t n, int32_t symmetric, float* d_out, int64_t ld, void* stream) {
+    const char* what = "gm_sketch_pair_features";
+    GM_REQUIRE(sk, GM_EINVAL, "%s: sketch is NULL", what);
+    GM_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX, GM_EINVAL, "%s: n = %lld", what, (long long)n);
+    const int32_t S = (sk->hops + 2) * (sk->hops + 2);
+    GM_REQUIRE(ld >= S, GM_EINVAL, "%s: ld = %lld; at least (hops + 2)^2 = %d", what, (long long)ld, S);
+    if (n == 0) return GM_OK;
+    GM_REQUIRE(d_pairs && d_out, GM_EINVAL, "%s: NULL argument", what);
+    const sk_shape sh = sk_shape_of(sk->p, sk->k);
+    const hipStream_t st = (hipStream_t)stream;
+    const int32_t regs = 1 << sk->p;
+    const double m = (double)regs;                                             // alpha as gmeta_amd.hll_cardinality forms it
+    const double alpha = regs == 16 ? 0.673 : regs == 32 ? 0.697 : regs == 64 ? 0.709 : 0.7213 / (1.0 + 1.079 / m);
+    switch (sk->hops) {
+        case 1: sk_pair_features<2>(st, sk, sh, d_pairs, n, symmetric, m, alpha, d_out, ld); break;
+        case 2: sk_pair_features<3>(st, sk, sh, d_pairs, n, symmetric, m, alpha, d_out, ld); break;
+        case 3: sk_pair_features<4>(st, sk, sh, d_pairs, n, symmetric, m, alpha, d_out, ld); break;
+        default: sk_pair_features<5>(st, sk, sh, d_pairs, n, symmetric, m, alpha, d_out, ld); break;
     }
     GM_HIP(hipGetLastError());
     return GM_OK;

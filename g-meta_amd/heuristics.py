@@ -6,7 +6,8 @@ GraphStore.pair_pagerank (gm_store_pair_pagerank).  Graph distance is the negate
 The joint hop-distance tables of GraphStore.pair_distance_profile (gm_store_pair_distance_profile) are no score: link_distance_profiles orients them by the
 pair's name and distance_profile_features turns them into input features.  Their ESTIMATES for every pair come from the node sketches of GraphStore.sketches
 (gm_store_sketch_build / gm_sketch_pair_counts): hll_cardinality, sketch_intersections and sketch_distance_profile form them in float64 from the integers,
-link_sketch_profiles orients them by the pair's name and sketch_profile_features gives the same feature shape.  link_propagated_features is their twin for the
+link_sketch_profiles orients them by the pair's name and sketch_profile_features gives the same feature shape; link_sketch_features is that chain in one call
+on the device (gm_sketch_pair_features).  link_propagated_features is their twin for the
 hop-propagated node features of GraphStore.propagated_features (gm_store_propagate_build / gm_prop_pair_features): the other input of a BUDDY predictor."""
 import numpy as np
 
@@ -225,6 +226,23 @@ def sketch_profile_features(tables, symmetric=True):
     if symmetric:
         t = t + t.transpose(0, 2, 1)
     return np.log1p(np.maximum(t, 0.0)).reshape(len(t), t.shape[1] * t.shape[2])
+
+
+def link_sketch_features(sketches_by_graph, names, symmetric=True):
+    """float32 [len(names), (H + 2)^2]: NodeSketches.pair_features of the pairs named 'g_i_j' from sketches_by_graph[g] (a dict or a sequence of NodeSketches
+    with one `hops`), one call per graph, rows in the order of `names` -- the one-call twin of sketch_profile_features(link_sketch_profiles(...), symmetric),
+    formed on the device (gm_sketch_pair_features) and equal to it to float32 rounding.  A pair is passed in its name's order: symmetric=False orients the
+    table by the name."""
+    trip = np.asarray([_pair(nm) for nm in names], np.int64).reshape(-1, 3)
+    graphs = np.unique(trip[:, 0]).tolist()
+    hops = {int(sketches_by_graph[g].hops) for g in graphs}
+    if len(hops) > 1:
+        raise ValueError('link_sketch_features: sketches of different hops %s' % sorted(hops))
+    out = np.zeros((len(trip), ((hops.pop() if hops else 0) + 2) ** 2), np.float32)
+    for g in graphs:
+        at = np.nonzero(trip[:, 0] == g)[0]
+        out[at] = sketches_by_graph[g].pair_features(trip[at, 1:], symmetric=symmetric)
+    return out
 
 
 def link_propagated_features(props_by_graph, names, op='hadamard'):

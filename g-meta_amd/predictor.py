@@ -70,56 +70,78 @@ class PairPredictor:
     def parameters(self):
         return [self.params]
 
-    def _inputs(self, props, pairs, extra, what):
-        """-> device int32 pairs [m, 2] (or None), device float32 extra [m, S] (or None), m"""
+    def _inputs(self, props, pairs, extra, what, sketches=None):
+        """-> device int32 pairs [m, 2] (or None), device float32 structure columns [m, extra_dim] (or None), m.  With `sketches` the columns are
+        [sketch columns | extra], built on the device: the sketch kernel writes into the [m, extra_dim] tensor with ld = extra_dim, extra is copied behind."""
         import torch
         if not getattr(props, 'handle', None):
             raise ValueError('%s: the propagated features are closed' % what)
         if props.feat_dim != self.feat_dim or props.hops != self.hops:
             raise ValueError('%s: propagated features of feat_dim = %d, hops = %d; the predictor has feat_dim = %d, hops = %d'
                              % (what, props.feat_dim, props.hops, self.feat_dim, self.hops))
+        own = 0                                                                  # the columns the sketches fill
+        if sketches is not None:
+            if not getattr(sketches, 'handle', None):
+                raise ValueError('%s: the sketches are closed' % what)
+            if sketches.n_nodes != props.n_nodes:
+                raise ValueError('%s: sketches of a graph with %d nodes; the propagated features have %d' % (what, sketches.n_nodes, props.n_nodes))
+            own = sketches.n_columns
+            given = 0 if extra is None else (int(extra.shape[1]) if getattr(extra, 'ndim', 0) == 2 else -1)
+            if given < 0 or own + given != self.extra_dim:
+                raise ValueError('%s: the sketches give %d columns and extra %s; the predictor has extra_dim = %d'
+                                 % (what, own, 'none' if extra is None else 'shape %s' % (tuple(extra.shape),), self.extra_dim))
+        width = self.extra_dim - own
         p = props._ids(pairs, what, (-1, 2))
         m = len(p)
         d_e = None
         if extra is None:
-            if self.extra_dim:
+            if width:
                 raise ValueError('%s: extra is None; the predictor has extra_dim = %d' % (what, self.extra_dim))
         elif isinstance(extra, torch.Tensor):
             if extra.dtype != torch.float32 or not extra.is_cuda:
                 raise ValueError('%s: extra is a %s tensor on %s; a CUDA float32 tensor or a numpy array' % (what, extra.dtype, extra.device))
-            if tuple(extra.shape) != (m, self.extra_dim):
-                raise ValueError('%s: extra of shape %s; [%d, %d]' % (what, tuple(extra.shape), m, self.extra_dim))
+            if tuple(extra.shape) != (m, width):
+                raise ValueError('%s: extra of shape %s; [%d, %d]' % (what, tuple(extra.shape), m, width))
             d_e = extra.contiguous()
         else:
             e = np.asarray(extra)
             if e.dtype not in (np.float32, np.float64):
                 raise ValueError('%s: extra of dtype %s; float32 or float64' % (what, e.dtype))
-            if e.shape != (m, self.extra_dim):
-                raise ValueError('%s: extra of shape %s; [%d, %d]' % (what, e.shape, m, self.extra_dim))
+            if e.shape != (m, width):
+                raise ValueError('%s: extra of shape %s; [%d, %d]' % (what, e.shape, m, width))
             d_e = torch.from_numpy(np.ascontiguousarray(e, np.float32)).cuda()       # float64 is cast to float32 ONCE, here
-        if self.extra_dim == 0:
+        if width == 0:
             d_e = None
         d_p = torch.from_numpy(np.ascontiguousarray(p, np.int32)).cuda() if m else None
+        if own:
+            cols = torch.empty((m, self.extra_dim), dtype=torch.float32, device='cuda')
+            if m:
+                sketches._features_into(d_p, m, True, cols)
+                if d_e is not None:
+                    cols[:, own:] = d_e
+            d_e = cols
         return d_p, d_e, m
 
-    def scores(self, props, pairs, extra=None, as_torch=False):
+    def scores(self, props, pairs, extra=None, as_torch=False, sketches=None):
         """float32 [m]: the logits of the [m, 2] node `pairs` of the graph of `props` (gm_prop_pair_mlp_forward).  A pair's logit is the same bits alone or in
         any batch, and for both of its orientations.  `extra`: the [m, extra_dim] structure columns, numpy (float64 is cast to float32 once) or a CUDA
-        float32 tensor -- sketch_profile_features and distance_profile_features give them.  as_torch=True leaves the result on the device."""
+        float32 tensor -- sketch_profile_features and distance_profile_features give them.  as_torch=True leaves the result on the device.
+        `sketches`: the NodeSketches of the same graph; the structure columns are then [its pair_features (symmetric) | extra], built on the device with no
+        read-back, and extra_dim must equal sketches.n_columns + the width of extra."""
         import torch
-        d_p, d_e, m = self._inputs(props, pairs, extra, 'scores')
+        d_p, d_e, m = self._inputs(props, pairs, extra, 'scores', sketches)
         out = torch.empty((m,), dtype=torch.float32, device='cuda')
         if m:
             _lib.check(_lib.lib().gm_prop_pair_mlp_forward(props.handle, _lib.ptr(d_p), m, self.op_code, _lib.ptr(d_e), self.extra_dim, _lib.ptr(self.params.data),
                                                            self.hidden, _lib.ptr(out), _lib.stream_ptr()), 'gm_prop_pair_mlp_forward')
         return out if as_torch else out.cpu().numpy()
 
-    def step(self, props, pairs, labels, extra=None):
+    def step(self, props, pairs, labels, extra=None, sketches=None):
         """The mean binary cross-entropy of the logits against `labels` (numbers in [0, 1], or the tables' strings) as a float, and its gradient in
         .params.grad (OVERWRITTEN, as after zero_grad + backward) -- forward, loss and all gradients in one call (gm_prop_pair_mlp_step); any torch optimiser
-        over .parameters() then steps."""
+        over .parameters() then steps.  `extra`, `sketches` as in .scores."""
         import torch
-        d_p, d_e, m = self._inputs(props, pairs, extra, 'step')
+        d_p, d_e, m = self._inputs(props, pairs, extra, 'step', sketches)
         y = np.asarray(labels).reshape(-1).astype(np.float32)
         if len(y) != m:
             raise ValueError('step: %d labels, %d pairs' % (len(y), m))
@@ -138,19 +160,22 @@ class PairPredictor:
         from .heuristics import _pair
         return np.asarray([_pair(nm) for nm in names], np.int64).reshape(-1, 3)
 
-    def link_scores(self, props_by_graph, names, extra=None):
-        """float32 [len(names)]: .scores of the pairs named 'g_i_j' from props_by_graph[g], one call per graph, rows in the order of `names`."""
+    def link_scores(self, props_by_graph, names, extra=None, sketches=None):
+        """float32 [len(names)]: .scores of the pairs named 'g_i_j' from props_by_graph[g], one call per graph, rows in the order of `names`.  `sketches`: a dict or a
+        sequence of NodeSketches by graph; the structure columns are then built on the device per call (.scores)."""
         trip = self._names(names)
         out = np.zeros(len(trip), np.float32)
         for g in np.unique(trip[:, 0]).tolist():
             at = np.nonzero(trip[:, 0] == g)[0]
-            out[at] = self.scores(props_by_graph[g], trip[at, 1:], None if extra is None else extra[at])
+            out[at] = self.scores(props_by_graph[g], trip[at, 1:], None if extra is None else extra[at], sketches=None if sketches is None else sketches[g])
         return out
 
-    def fit(self, props_by_graph, names, labels, extra=None, epochs=10, batch=4096, lr=0.01):
+    def fit(self, props_by_graph, names, labels, extra=None, epochs=10, batch=4096, lr=0.01, sketches=None):
         """Trains with Adam on the pairs named 'g_i_j' (props_by_graph[g]: a dict or a sequence of PropagatedFeatures) and their 0 / 1 `labels`: per epoch the
         pairs of every graph, in ascending graph order, are shuffled by the predictor's seeded generator and walked in minibatches of `batch`, one .step per
         graph and minibatch -- the twin of link_propagated_features, without its [m, hops + 1, F] array.  `extra` (numpy [len(names), extra_dim]) rides along.
+        `sketches` (a dict or a sequence of NodeSketches by graph): the sketch columns are built on the device per minibatch, in front of extra's, so that at most
+        batch * extra_dim floats of them exist at a time and nothing per pair crosses to the host but the ids, the labels and the loss.
         -> the list of per-epoch losses (the mean of the minibatch losses, each weighted by its size)."""
         import torch
         trip = self._names(names)
@@ -172,13 +197,13 @@ class PairPredictor:
                 at = at[torch.randperm(len(at), generator=self.generator).numpy()]
                 for i in range(0, len(at), batch):
                     b = at[i:i + batch]
-                    loss = self.step(props_by_graph[g], trip[b, 1:], y[b], None if extra is None else extra[b])
+                    loss = self.step(props_by_graph[g], trip[b, 1:], y[b], None if extra is None else extra[b], sketches=None if sketches is None else sketches[g])
                     opt.step()
                     total += loss * len(b); seen += len(b)
             curve.append(total / max(seen, 1))
         return curve
 
-    def auc(self, props_by_graph, names, labels, extra=None):
+    def auc(self, props_by_graph, names, labels, extra=None, sketches=None):
         """link_auc of .link_scores against the 0 / 1 `labels`."""
         from .heuristics import link_auc
-        return link_auc(self.link_scores(props_by_graph, names, extra), labels)
+        return link_auc(self.link_scores(props_by_graph, names, extra, sketches), labels)

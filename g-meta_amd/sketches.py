@@ -1,7 +1,8 @@
 """ELPH / BUDDY neighbourhood sketches of every node of a parent graph (gm_store_sketch_build, gm_sketch_*; the definition is in include/gmeta_hip.h,
 tests/sketch_ref.py restates it): per node and level d = 0 .. hops a HyperLogLog record of 2^p byte registers and a MinHash record of k words of its d-hop
 ball, built once on the device; afterwards the integers behind the joint hop-distance table of ANY pair come from 2 (hops + 1) small records, with no search.
-The estimators over those integers are float64 host work: gmeta_amd.hll_cardinality, sketch_intersections, sketch_distance_profile.
+The estimators over those integers exist twice: in float64 on the host (gmeta_amd.hll_cardinality, sketch_intersections, sketch_distance_profile), and on the
+device in NodeSketches.pair_features (gm_sketch_pair_features), which hands a predictor its structure columns without a read-back.
 
 There is no mask_target: the sketches describe the whole graph and a pair's own edge cannot be taken out of them (ELPH has the same limit).  The exact,
 masked table of a shortlist is GraphStore.pair_distance_profile(mask_target=True)."""
@@ -63,6 +64,42 @@ class NodeSketches:
             d_p = torch.from_numpy(np.ascontiguousarray(p, np.int32)).cuda()
             _lib.check(_lib.lib().gm_sketch_pair_counts(self.handle, _lib.ptr(d_p), len(p), _lib.ptr(out), _lib.ptr(balls), _lib.stream_ptr()), 'gm_sketch_pair_counts')
         return out.cpu().numpy(), balls.cpu().numpy()
+
+    @property
+    def n_columns(self):
+        """(hops + 2)^2: the structure columns pair_features gives per pair"""
+        return (self.hops + 2) ** 2
+
+    def pair_features(self, pairs, symmetric=True, as_torch=False, out=None):
+        """float32 [m, (hops + 2)^2]: the structure columns of a BUDDY predictor for the [m, 2] node `pairs`, formed on the device from the integers of
+        pair_counts (gm_sketch_pair_features): log1p(max(T, 0)) row-major of the estimated joint hop-distance table, T = P + P^T when symmetric (default; both
+        orientations of a pair give the same bits), else P in the orientation the pair is passed in -- to float32 rounding what
+        sketch_profile_features(sketch_distance_profile(*pair_counts(pairs), ...), symmetric) gives on the host.  numpy, or with as_torch=True a CUDA tensor
+        that never left the device.  `out`: a CUDA float32 tensor [m, W >= (hops + 2)^2] with contiguous rows; its first (hops + 2)^2 columns are filled in
+        place, the others are not touched, and it is what is returned (as_torch) or copied back."""
+        import torch
+        p = self._ids(pairs, 'pair_features', (-1, 2))
+        S = self.n_columns
+        if out is None:
+            out = torch.empty((len(p), S), dtype=torch.float32, device='cuda')
+        else:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda:
+                raise ValueError('pair_features: out must be a CUDA float32 tensor')
+            if out.dim() != 2 or out.shape[0] != len(p) or out.shape[1] < S:
+                raise ValueError('pair_features: out of shape %s; [%d, at least %d]' % (tuple(out.shape), len(p), S))
+            if out.shape[1] and out.stride(1) != 1 or len(p) > 1 and out.stride(0) != out.shape[1]:
+                raise ValueError('pair_features: out of strides %s; contiguous rows' % (tuple(out.stride()),))
+        if len(p):
+            self._features_into(torch.from_numpy(np.ascontiguousarray(p, np.int32)).cuda(), len(p), symmetric, out)
+        return out if as_torch else out[:, :S].cpu().numpy()
+
+    def _features_into(self, d_pairs, m, symmetric, out):
+        """gm_sketch_pair_features of the device int32 [m, 2] `d_pairs` (ids already checked) into the first n_columns columns of the CUDA float32 [m, W]
+        `out`, ld = W"""
+        if not self.handle:
+            raise ValueError('pair_features: the sketches are closed')
+        _lib.check(_lib.lib().gm_sketch_pair_features(self.handle, _lib.ptr(d_pairs), m, 1 if symmetric else 0, _lib.ptr(out), out.shape[1], _lib.stream_ptr()),
+                   'gm_sketch_pair_features')
 
     def registers(self, nodes, level):
         """(uint8 [m, 2^p], uint32 [m, k]): the HyperLogLog registers and the MinHash words of the `nodes` at `level` (0 .. hops), as stored

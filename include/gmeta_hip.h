@@ -363,7 +363,29 @@ int32_t gm_store_pair_distance_profile(const gm_store_t* s, int32_t g, const int
  *                  d_out: device int64 [n, H + 1, H + 1, 3] = (match, zeros, zsum);  d_out_balls: device int64 [n, 2, H + 1, 2] = (zeros, zsum) of R_a(u) and
  *                  then of R_a(v) alone.  A node id outside [0, N) gives zeros in both.  Nothing behind entry n - 1 is written.  Duplicates are written
  *                  each on their own.  The estimators (HyperLogLog cardinality, MinHash Jaccard, the table in the layout of gm_store_pair_distance_profile)
- *                  are float64 host work over these integers: g-meta_amd/heuristics.py.
+ *                  over these integers are written twice: in float64 on the host (g-meta_amd/heuristics.py), and on the device in gm_sketch_pair_features.
+ *   pair features  gm_sketch_pair_features: the S = (H + 2)^2 structure columns a BUDDY predictor reads, formed from the integers above without leaving the
+ *                  device.  d_pairs as above; d_out: device float32 with row stride ld >= S; row e, columns 0 .. S - 1 get the features of pair e and NOTHING
+ *                  else is written: not the columns S .. ld - 1, not anything behind row n - 1.  The chain below is evaluated in fp64 (IEEE double), each
+ *                  operation as written and rounded once -- no fused multiply-add -- and tests/sketch_feature_ref.py restates it:
+ *                    integers  (match, zeros, zsum)[a][b] and the ball entries of the canonical (u, v) = (min, max), exactly as pair counts gives them; a
+ *                              node id outside [0, N) gives the chain's value on all-zero integers.
+ *                    card(zeros, zsum), with m = 2^p:  s = zsum / 2^32;  est = ((alpha * m) * m) / s, or 0 where zsum == 0;  where zsum != 0 and
+ *                              est <= 2.5 * m and zeros > 0 the value is m * log(m / zeros), else est.  alpha = 0.673, 0.697, 0.709 at m = 16, 32, 64, else
+ *                              0.7213 / (1.0 + 1.079 / m).  (gmeta_amd.hll_cardinality, in its operation order.)
+ *                    C[a][b] = (match[a][b] / K) * card(zeros[a][b], zsum[a][b]);  su[a] = card(u's ball entry a), sv[b] = card(v's ball entry b).
+ *                    P, (H + 2) x (H + 2), with C[-1][.] = C[.][-1] = 0, su[-1] = sv[-1] = 0 (gmeta_amd.sketch_distance_profile):
+ *                              P[a][b] = (C[a][b] - C[a-1][b]) - (C[a][b-1] - C[a-1][b-1])                      a, b in 0 .. H
+ *                              P[a][H+1] = (su[a] - su[a-1]) - sum over b = 0 .. H of P[a][b]
+ *                              P[H+1][b] = (sv[b] - sv[b-1]) - sum over a = 0 .. H of P[a][b]
+ *                              P[H+1][H+1] = N - sum of all other cells
+ *                              every sum runs from 0.0 over its cells in ascending index order (the last one row-major), one addition per cell.
+ *                    T         symmetric != 0: T[a][b] = P[a][b] + P[b][a].  symmetric == 0: T = P for d_pairs[e] = (x, y) with x <= y, its transpose
+ *                              otherwise -- entry [a][b] then speaks of the nodes a hops from x and b hops from y (gmeta_amd.link_sketch_profiles).
+ *                    out[e][a * (H + 2) + b] = (float) log1p(max(T[a][b], 0)).
+ *                  fp64 keeps the cancellation of the differences far below fp32 resolution and is the host definition's format; log and log1p are the
+ *                  device library's (a few ulp), so the host chain agrees to fp32 rounding, not in every bit.  A pair's row is the same bits alone or in any
+ *                  batch, on any stream, and for both orientations when symmetric.  No atomics.
  *   identities     that follow from the definition (tests hold the device to them): match[a][b] == K whenever B_a(u) == B_b(v); match[a][b] == 0 whenever the
  *                  two balls are disjoint (mh_k is a bijection); B_a(u) inside B_b(v) makes (zeros, zsum)[a][b] v's ball entry b; zeros and zsum do not
  *                  increase in a or in b; both orientations of a pair give the same bits.
@@ -382,12 +404,13 @@ int32_t gm_store_pair_distance_profile(const gm_store_t* s, int32_t g, const int
  * node outside [0, N) gives zeros.  Both readers run on `stream` and are complete in stream order; n == 0 / m == 0 is a no-op, with NULL pointers too.
  * gm_sketch_dims fills whichever of its outputs is not NULL (bytes: the formula above).  gm_sketch_destroy waits for the device and frees the records.
  * GM_EINVAL (the message names the value): a bad graph index, hops / p / k outside the ranges above, a level outside 0 .. H, n or m negative or above
- * INT32_MAX, a NULL argument with work to do, a negative sketch_chunk or sketch_mib. */
+ * INT32_MAX, a NULL argument with work to do, a negative sketch_chunk or sketch_mib, ld < (H + 2)^2. */
 typedef struct gm_sketch gm_sketch_t;
 int32_t gm_store_sketch_build(const gm_store_t* s, int32_t g, int32_t hops, int32_t p, int32_t k, uint64_t seed, void* stream, gm_sketch_t** out);
 int32_t gm_sketch_dims(const gm_sketch_t* sk, int64_t* n_nodes, int32_t* hops, int32_t* p, int32_t* k, int64_t* bytes);
 int32_t gm_sketch_registers(const gm_sketch_t* sk, int32_t level, const int32_t* d_nodes, int64_t m, uint8_t* d_hll, uint32_t* d_minhash, void* stream);
 int32_t gm_sketch_pair_counts(const gm_sketch_t* sk, const int32_t* d_pairs, int64_t n, int64_t* d_out, int64_t* d_out_balls, void* stream);
+int32_t gm_sketch_pair_features(const gm_sketch_t* sk, const int32_t* d_pairs, int64_t n, int32_t symmetric, float* d_out, int64_t ld, void* stream);
 void gm_sketch_destroy(gm_sketch_t* sk);
 
 /* ---- HOP-PROPAGATED NODE FEATURES of a whole parent graph (beyond the reference): the second precomputed input of a BUDDY predictor beside the structural counts

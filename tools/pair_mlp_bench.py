@@ -2,7 +2,7 @@
 with no target.  Case: the arxiv-shaped synthetic graph of the other pair benchmarks (synth.CONFIGS['arxiv'], 128 feature columns), hops 2, hidden 256, 16
 structure columns (the width sketch_profile_features gives at hops 2; their values do not matter to the time: random here).
 
-    python tools/pair_mlp_bench.py [--reps 5] [--warmup 2] [--out profiles/pair_mlp.txt]
+    python tools/pair_mlp_bench.py [--reps 5] [--warmup 2] [--section all|kernels|fit] [--out profiles/pair_mlp.txt]
 
 batches        10,000 pairs, 262,144 pairs (half edges, half negatives from GraphStore.negative_pairs), and all directed edges plus as many negatives.
 fused          forward (scoring) and step (forward, loss, all gradients): HIP events around the C call, median (min - max) of --reps after --warmup.
@@ -13,11 +13,15 @@ memory         unfused: torch's peak allocation above the resident inputs; fused
                partials of one chunk of pair_mlp_rows), and the drop of free device memory across the first call (the stream-ordered pool keeps what it took).
 rates          2 n K Hd FLOP for a forward, 4 n K Hd for a step (the weight gradient; the hidden layer's input needs no gradient), over the time: fp32-equivalent
                TFLOP/s, beside torch's fp32 GEMM [262144, K] @ [K, 256] and the HBM copy rate (bench.py's box_calibration), both measured in this process.
+fit            (--section fit, or all) one PairPredictor.fit epoch over 262,144 pairs (batch 4,096) with REAL structure columns, host clock: the columns built up
+               front on the host (sketch_profile_features(link_sketch_profiles(...)): pair_counts, read-back, float64 numpy) and passed as extra=, against the same
+               epoch with sketches=, which builds them per minibatch on the device (gm_sketch_pair_features).  Both start from the same seed; their losses are printed.
 One JSON line per measurement; --out appends a plain-text table."""
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -42,11 +46,52 @@ def fused_scratch_bytes(n, K, Hd):
     return 4 * (pad * HP + tiles * (2 * HP + 4) + ranges * K * Hd)
 
 
+def fit_section(store, N, src, dst, F, a, lines):
+    """one fit epoch over CHUNK pairs: host-built columns as extra= against sketches="""
+    rng = np.random.default_rng(7)
+    edges = np.stack([src, dst], 1).astype(np.int64)
+    pos = edges[rng.choice(len(edges), CHUNK // 2, replace=False)]
+    pairs = np.concatenate([pos, store.negative_pairs(0, CHUNK - len(pos), seed=222)]).astype(np.int64)
+    labels = np.concatenate([np.ones(len(pos), np.float32), np.zeros(CHUNK - len(pos), np.float32)])
+    names = ['0_%d_%d' % (x, y) for x, y in pairs.tolist()]
+
+    def clock(call):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = call()
+        torch.cuda.synchronize()
+        return r, (time.perf_counter() - t0) * 1e3
+
+    with store.propagated_features(0, hops=HOPS) as props, store.sketches(0, hops=HOPS) as sk:
+        res = {}
+        for k in range(a.warmup + a.reps):
+            x, t_cols = clock(lambda: gmeta_amd.sketch_profile_features(gmeta_amd.link_sketch_profiles([sk], names)))
+            model = gmeta_amd.PairPredictor(F, HOPS, hidden=HD, extra_dim=S, seed=0)
+            curve_h, t_host = clock(lambda: model.fit([props], names, labels, extra=x, epochs=1))
+            model = gmeta_amd.PairPredictor(F, HOPS, hidden=HD, extra_dim=S, seed=0)
+            curve_d, t_dev = clock(lambda: model.fit([props], names, labels, epochs=1, sketches=[sk]))
+            if k >= a.warmup:
+                for key, v in (('columns', t_cols), ('fit_extra', t_host), ('fit_sketches', t_dev)):
+                    res.setdefault(key, []).append(v)
+    stat = {key: (float(np.median(v)), float(min(v)), float(max(v))) for key, v in res.items()}
+    host_total = stat['columns'][0] + stat['fit_extra'][0]
+    rec = {'what': 'fit epoch', 'n': CHUNK, 'batch': 4096, 'host_columns_ms': [round(t, 1) for t in stat['columns']], 'fit_extra_ms': [round(t, 1) for t in stat['fit_extra']],
+           'fit_sketches_ms': [round(t, 1) for t in stat['fit_sketches']], 'host_total_over_device': round(host_total / stat['fit_sketches'][0], 2), 'loss_extra': curve_h[0],
+           'loss_sketches': curve_d[0]}
+    print(json.dumps(rec), flush=True)
+    lines.append('fit, one epoch over %d pairs in minibatches of 4096, %d structure columns from the sketches (hops %d, p 8, K 128), host clock, median (min - max) of %d after %d:'
+                 % (CHUNK, S, HOPS, a.reps, a.warmup))
+    lines.append('  host-built extra=:  columns up front %9.1f ms (%.1f - %.1f)  +  epoch %8.1f ms (%.1f - %.1f)  =  %9.1f ms      sketches=:  epoch %8.1f ms (%.1f - %.1f)      '
+                 'host route / device route %.2f      loss %.7f vs %.7f' % (stat['columns'] + stat['fit_extra'] + (host_total,) + stat['fit_sketches'] + (host_total / stat['fit_sketches'][0],
+                                                                                                                                                    curve_h[0], curve_d[0])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--section', default='all', choices=['all', 'kernels', 'fit'])
     a = ap.parse_args()
     torch.cuda.set_device(0)
     torch.manual_seed(0)
@@ -75,7 +120,7 @@ def main():
              'box: HBM copy rate %.0f GB/s (1 GiB device copy, read + written), torch fp32 GEMM [%d, %d] @ [%d, %d] %.1f TFLOP/s; HIP events around the call, median (min - max) of %d '
              'after %d warm-up(s)' % (copy_gbps, CHUNK, K, K, HD, gemm_tf, a.reps, a.warmup),
              'unfused = pair_features(as_torch=True) -> cat -> addmm / relu / BCE-with-logits -> backward for the weights, chunks of %d pairs; memory: MB above the resident inputs' % CHUNK]
-    for n in (10000, CHUNK, 2 * len(edges)):
+    for n in (10000, CHUNK, 2 * len(edges)) if a.section != 'fit' else ():
         pos = edges if n == 2 * len(edges) else edges[rng.choice(len(edges), n // 2, replace=False)]
         pairs = np.concatenate([pos, store.negative_pairs(0, n - len(pos), seed=222)]).astype(np.int64)
         labels = np.concatenate([np.ones(len(pos), np.float32), np.zeros(n - len(pos), np.float32)])
@@ -148,6 +193,8 @@ def main():
         print(json.dumps({'what': 'agreement', 'n': n, 'max_logit_diff': dl, 'max_grad_diff': dg, 'max_grad': gs, 'loss': float(loss.item()), 'loss_unfused': float(total)}), flush=True)
         del d_p, d_y, d_e, logits, grad, ref_logits, w
     props.close()
+    if a.section != 'kernels':
+        fit_section(store, N, src, dst, F, a, lines)
     print('\n'.join(lines))
     if a.out:
         with open(a.out, 'a') as f:

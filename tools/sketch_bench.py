@@ -1,7 +1,7 @@
 """Time and accuracy of the node sketches on the device (gm_store_sketch_build, gm_sketch_pair_counts), reported with no target.  Case: the arxiv-shaped
 synthetic graph of the other pair benchmarks (synth.CONFIGS['arxiv']).
 
-    python tools/sketch_bench.py [--reps 5] [--warmup 2] [--out profiles/sketches.txt]
+    python tools/sketch_bench.py [--reps 5] [--warmup 2] [--section all|sketches|features] [--out profiles/sketches.txt]
 
 build        (p, K) = (8, 128) and (6, 64) at H = 2 and 3: HIP events around the C call (the allocation and the final synchronisation included), median (min -
              max) of --reps after --warmup; per level one more build under GM_TIMING, where the library synchronises the stream behind every level (host
@@ -12,6 +12,10 @@ pair_counts  10,000 pairs (half edges, half negatives) and all |E| edges as pair
              measured in the same run.
 accuracy     the estimated table (gmeta_amd.sketch_distance_profile) against the exact one over those 10,000 pairs: per cell the mean absolute error and its
              quantiles.
+features     (--section features, or all) gm_sketch_pair_features at (p 8, K 128), H = 2 and 3, over the 10,000 pairs and over all edges, the result left on the
+             device; gm_sketch_pair_counts alone on the same pairs in the same run; and the full host route to the same columns: NodeSketches.pair_counts (kernel
+             + read-back) -> sketch_distance_profile -> sketch_profile_features -> float32 -> upload, on the host clock.  The records' bytes per second against the
+             copy rate as in the pair_counts rows.
 One JSON line per measurement; --out appends a plain-text table."""
 import argparse
 import ctypes as C
@@ -20,6 +24,7 @@ import os
 import re
 import sys
 import tempfile
+import time
 
 import numpy as np
 import torch
@@ -61,11 +66,65 @@ def level_ms(store, H, p, K):
     return ms
 
 
+def host_clock(call, reps, warmup):
+    """ms on the host clock, the device idle before and after: median, min, max"""
+    ms = []
+    for k in range(warmup + reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call()
+        torch.cuda.synchronize()
+        if k >= warmup:
+            ms.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ms)), float(min(ms)), float(max(ms))
+
+
+def features_section(store, N, batches, copy_gbps, a, lines):
+    """gm_sketch_pair_features beside gm_sketch_pair_counts and beside the host route to the same columns"""
+    lib = _lib.lib()
+    lines.append('pair_features (p 8 K 128; the columns left on the device) against pair_counts alone on the same pairs, and against the host route to the same columns '
+                 '(pair_counts + read-back + hll_cardinality / sketch_intersections / sketch_distance_profile / sketch_profile_features in float64 numpy + cast + upload; host clock):')
+    for H in HOPS:
+        L, S = H + 1, (H + 2) ** 2
+        with store.sketches(0, hops=H, p=8, k=128, seed=222) as sk:
+            for what, pp in batches:
+                n = len(pp)
+                d_p = torch.from_numpy(np.ascontiguousarray(pp, np.int32)).cuda()
+                out = torch.empty((n, L, L, 3), dtype=torch.int64, device='cuda')
+                balls = torch.empty((n, 2, L, 2), dtype=torch.int64, device='cuda')
+                cols = torch.empty((n, S), dtype=torch.float32, device='cuda')
+                counts_call = lambda: _lib.check(lib.gm_sketch_pair_counts(sk.handle, _lib.ptr(d_p), n, _lib.ptr(out), _lib.ptr(balls), _lib.stream_ptr()), 'gm_sketch_pair_counts')      # noqa: E731
+                feat_call = lambda: _lib.check(lib.gm_sketch_pair_features(sk.handle, _lib.ptr(d_p), n, 1, _lib.ptr(cols), S, _lib.stream_ptr()), 'gm_sketch_pair_features')      # noqa: E731
+                c_med, c_lo, c_hi = timed(counts_call, a.reps, a.warmup)
+                f_med, f_lo, f_hi = timed(feat_call, a.reps, a.warmup)
+
+                def host_route():
+                    counts, bl = sk.pair_counts(pp)
+                    x = gmeta_amd.sketch_profile_features(gmeta_amd.sketch_distance_profile(counts, bl, N, sk.p, sk.k))
+                    return torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda()
+
+                h_reps, h_warm = (a.reps, 1) if n <= 100000 else (1, 0)
+                h_med, h_lo, h_hi = host_clock(host_route, h_reps, h_warm)
+                diff = float((host_route() - cols).abs().max())
+                read = 2.0 * L * (256 + 512) * n
+                rec = {'what': 'pair_features ' + what, 'hops': H, 'n': n, 'ms': round(f_med, 3), 'min_ms': round(f_lo, 3), 'max_ms': round(f_hi, 3), 'pair_counts_ms': round(c_med, 3),
+                       'pair_counts_min_ms': round(c_lo, 3), 'pair_counts_max_ms': round(c_hi, 3), 'record_GBps': round(read / (f_med * 1e-3) / 1e9, 1),
+                       'stored_bytes_per_pair': 4 * S, 'pair_counts_stored_bytes_per_pair': 8 * (3 * L * L + 4 * L), 'host_route_ms': round(h_med, 1), 'host_route_min_ms': round(h_lo, 1),
+                       'host_route_max_ms': round(h_hi, 1), 'host_route_reps': h_reps, 'max_abs_diff_to_host': diff}
+                print(json.dumps(rec), flush=True)
+                lines.append('  H %d  %-18s pair_features %9.3f ms (%.3f - %.3f)   pair_counts %9.3f ms (%.3f - %.3f)   features / counts %.3f   stores %d vs %d B per pair   '
+                             'records read %7.1f GB/s = %.3f of the copy rate   host route %10.1f ms (%.1f - %.1f, %d run(s)): %.0f x   largest |device - host| %.3g'
+                             % (H, what, f_med, f_lo, f_hi, c_med, c_lo, c_hi, f_med / c_med, 4 * S, rec['pair_counts_stored_bytes_per_pair'], rec['record_GBps'],
+                                rec['record_GBps'] / copy_gbps, h_med, h_lo, h_hi, h_reps, h_med / f_med, diff))
+                del d_p, out, balls, cols
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--section', default='all', choices=['all', 'sketches', 'features'])
     a = ap.parse_args()
     torch.cuda.set_device(0)
     import bench
@@ -83,7 +142,28 @@ def main():
              'box: HBM copy rate %.0f GB/s (1 GiB device copy, bytes read + written per second); end to end: HIP events around the C call, median (min - max) of %d after %d warm-up(s);'
              % (copy_gbps, a.reps, a.warmup),
              'levels: one build under GM_TIMING, the stream synchronised behind every level (host clock); gathered bytes of a level = index entries x record bytes',
-             'build (allocation and final synchronisation included):']
+             ]
+    rng = np.random.default_rng(5)
+    half = len(src) // 2
+    n = 10000
+    pos = np.stack([src[:half], dst[:half]], 1)[rng.choice(half, n // 2, replace=False)]
+    pairs = np.concatenate([pos, store.negative_pairs(0, n - n // 2, seed=222)]).astype(np.int64)
+    every = np.stack([src, dst], 1).astype(np.int64)
+    if a.section != 'features':
+        sketch_sections(store, N, src, deg, nnz, pairs, every, copy_gbps, a, lines)
+    if a.section != 'sketches':
+        features_section(store, N, (('10,000 pairs', pairs), ('all %d edges' % len(every), every)), copy_gbps, a, lines)
+    print('\n'.join(lines))
+    if a.out:
+        with open(a.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
+def sketch_sections(store, N, src, deg, nnz, pairs, every, copy_gbps, a, lines):
+    """the build, sketch_chunk, pair_counts and accuracy sections"""
+    lib = _lib.lib()
+    n = len(pairs)
+    lines.append('build (allocation and final synchronisation included):')
     for p, K in SHAPES:
         rec_bytes = (1 << p) + 4 * K
         for H in HOPS:
@@ -113,12 +193,6 @@ def main():
         print(json.dumps(rec), flush=True)
         lines.append('  sketch_chunk %10d  %5d hub rows in %6d segments  %9.3f ms (%.3f - %.3f)   levels %s ms'
                      % (chunk, rec['hub_rows'], rec['segments'], med, lo, hi, ' / '.join('%.3f' % t for t in lv[1:])))
-    rng = np.random.default_rng(5)
-    half = len(src) // 2
-    n = 10000
-    pos = np.stack([src[:half], dst[:half]], 1)[rng.choice(half, n // 2, replace=False)]
-    pairs = np.concatenate([pos, store.negative_pairs(0, n - n // 2, seed=222)]).astype(np.int64)
-    every = np.stack([src, dst], 1).astype(np.int64)
     lines.append('pair_counts (p 8 K 128) against gm_store_pair_distance_profile on the same 10,000 pairs, unmasked, max_dist = H, in the same run:')
     errs = []
     for H in HOPS:
@@ -159,10 +233,6 @@ def main():
                 print(json.dumps({'what': 'error', 'hops': H, 'cell': [i, j], 'mean': round(float(e.mean()), 3), 'q50': round(float(q[0]), 3), 'q90': round(float(q[1]), 3),
                                   'q99': round(float(q[2]), 3), 'max': round(float(e.max()), 3), 'mean_exact': round(float(exact[:, i, j].mean()), 3)}), flush=True)
                 lines.append('  H %d [%d][%d]  %10.3f / %10.3f / %10.3f / %10.3f / %10.3f   (%.3f)' % (H, i, j, e.mean(), q[0], q[1], q[2], e.max(), exact[:, i, j].mean()))
-    print('\n'.join(lines))
-    if a.out:
-        with open(a.out, 'a') as f:
-            f.write('\n'.join(lines) + '\n')
 
 
 if __name__ == '__main__':

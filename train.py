@@ -82,6 +82,10 @@ def parse(argv=None):
                     help='EPOCHS (--link_pred_mode True): after the test evaluation and the baseline lines, build the hop-propagated features (hops 2) and the '
                          'neighbourhood sketches of every graph, fit a BUDDY pair predictor (gmeta_amd.PairPredictor: level products + sketch profile columns) on the '
                          'pairs of the training table for EPOCHS epochs and print its ROC AUC over the pairs of the test table; 0 = off')
+    ap.add_argument('--buddy_columns', default='host', choices=['host', 'device'],
+                    help="where the sketch profile columns of --buddy are formed: 'host' = read the integers back and run the float64 estimators in numpy for every pair of "
+                         "the train and test tables before the first step; 'device' = the predictor builds them per minibatch from the sketches "
+                         "(NodeSketches.pair_features), nothing per pair is read back; needs --buddy > 0")
     ap.add_argument('--readout', default='centre', choices=['centre', 'mean'],
                     help="what the head reads of every subgraph: 'centre' = the centre row (both endpoints' rows of a pair), as the reference; 'mean' = the mean "
                          "over all of its rows (the dgl.mean_nodes line the reference left commented out), one pooled vector for pairs too")
@@ -107,6 +111,8 @@ def parse(argv=None):
         raise SystemExit('--buddy %d: epochs of the pair predictor, 0 = off' % a.buddy)
     if a.buddy and a.link_pred_mode != 'True':
         raise SystemExit('--buddy %d trains a predictor of node PAIRS: it needs --link_pred_mode True' % a.buddy)
+    if a.buddy_columns != 'host' and not a.buddy:
+        raise SystemExit('--buddy_columns %s chooses where the columns of the --buddy predictor are formed: it needs --buddy > 0' % a.buddy_columns)
     return a
 
 
@@ -241,20 +247,25 @@ def main(args):
     if args.buddy:
         from gmeta_amd.negatives import read_link_tables
         both = tables if tables is not None else read_link_tables(root)
-        res['buddy_auc'] = buddy_auc(store, both['train'], both['test'], args.buddy)
+        res['buddy_auc'] = buddy_auc(store, both['train'], both['test'], args.buddy, columns=args.buddy_columns)
         if rank == 0:
             print('BUDDY test AUC: %.4f' % res['buddy_auc'])
     return res
 
 
-def buddy_auc(store, train, test, epochs, hops=2):
+def buddy_auc(store, train, test, epochs, hops=2, columns='host'):
     """The two precomputed inputs of a BUDDY predictor for every graph (the levels of GraphStore.propagated_features and the sketches of GraphStore.sketches, both
     at `hops`), a gmeta_amd.PairPredictor fitted on the (names, labels) of `train`, and its ROC AUC over those of `test`.  No mask_target: both inputs describe the
-    whole graph."""
+    whole graph.  columns='host': the sketch profile columns of every pair of both tables are formed up front by the float64 host estimators;
+    'device': the predictor forms them per minibatch on the device from the sketches (PairPredictor.fit / .auc with sketches=)."""
     graphs = range(store.n_graphs)
     props = [store.propagated_features(g, hops=hops) for g in graphs]
     sketches = [store.sketches(g, hops=hops) for g in graphs]
     try:
+        if columns == 'device':
+            model = gmeta_amd.PairPredictor(store.feat_dim, hops, extra_dim=(hops + 2) ** 2, seed=222)
+            model.fit(props, train[0], train[1], epochs=epochs, sketches=sketches)
+            return model.auc(props, test[0], test[1], sketches=sketches)
         columns = lambda names: gmeta_amd.sketch_profile_features(gmeta_amd.link_sketch_profiles(sketches, names))      # noqa: E731
         x_train, x_test = columns(train[0]), columns(test[0])
         model = gmeta_amd.PairPredictor(store.feat_dim, hops, extra_dim=x_train.shape[1], seed=222)
