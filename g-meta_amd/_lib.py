@@ -95,6 +95,7 @@ PROTOTYPES = {
     'gm_dense_gemm': (C.c_int, [vp, vp, i64, i32, vp, i64, i32, i32, vp, i64, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i32, vp, vp]),
     'gm_dense_fused_gemm': (C.c_int, [vp, i32, vp, i64, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, vp, vp, i64, i32, vp, vp, vp, i32, vp, vp]),
     'gm_dense_fused_gemm_rows': (C.c_int, [vp, i32, i32, i32, i32, i32, vp, i64, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp, vp, vp, i32, vp, vp]),
+    'gm_dense_fused_gemm_packed': (C.c_int, [vp, i32, i32, i32, vp, i64, i32, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp, vp]),
     'gm_dense_wgrad_fused': (C.c_int, [vp, i32, vp, i64, i32, vp, i64, vp, i64, i32, vp, vp, vp, i64, vp, i64, i32, vp]),
     'gm_dense_aggregate': (C.c_int, [vp, i32, i32, vp, i64, i32, i32, vp, vp, i32, vp, i64, i32, vp, vp, vp, i32, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp]),
     'gm_dense_agg_info': (C.c_int, [vp, i32, vp]),
@@ -102,6 +103,7 @@ PROTOTYPES = {
     'gm_dense_fuse_counts': (C.c_int, [vp, vp]),
     'gm_dense_agg_table': (C.c_int, [vp, i32, i32, vp, i64, vp]),
     'gm_dense_dz_centre': (C.c_int, [vp, vp, i32, vp, i64, i32, vp, vp]),
+    'gm_dense_dz_centre_rows': (C.c_int, [vp, vp, i32, vp, i64, i32, vp, i32, i32, vp]),
     'gm_dense_wgrad_centre': (C.c_int, [vp, vp, i32, vp, i32, vp, i64, vp, i64, vp]),
     'gm_dense_agg_centre_t': (C.c_int, [vp, vp, i32, vp, vp, i32, vp]),
     'gm_dense_wgrad_e1': (C.c_int, [vp, vp, i32, vp, i32, vp, i64, vp, i64, vp]),
@@ -146,7 +148,7 @@ PROBE_PROTOTYPES = {
 
 # test-only exports of PROTOTYPES younger than the rest: a library given through GMETA_HIP_LIB may be an older build without them (the A/B measurements run
 # the parent commit's library in this checkout) and still loads; the package's own library must export every one (tests/test_cabi_and_host.py)
-LATER_EXPORTS = {'gm_dense_obs_lists', 'gm_dense_fused_gemm_rows'}
+LATER_EXPORTS = {'gm_dense_obs_lists', 'gm_dense_fused_gemm_rows', 'gm_dense_fused_gemm_packed', 'gm_dense_dz_centre_rows'}
 
 _lib = None
 

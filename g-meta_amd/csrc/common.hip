@@ -361,6 +361,7 @@ const gm_knobs& gm_knob() {
         k.agg_mid_win = env("GM_AGG_MID_WIN", 0);
         k.agg_obs_list = env("GM_AGG_OBS_LIST", 1);
         k.dead_tiles = env("GM_DEAD_TILES", 1);
+        k.pack_rows = env("GM_PACK_ROWS", 1);
         k.split_pieces = env("GM_SPLIT_PIECES", 3);                   // 3: every operand carries its full 24 significand bits (the reference multiplies in fp32, learner.py:36,47); 2 = opt-in fast mode
         k.split16_min_rows = env("GM_SPLIT16_MIN_ROWS", 65536);
         k.wgrad_split_min_chunks = env("GM_WGRAD_SPLIT_MIN_CHUNKS", -1);
@@ -395,7 +396,7 @@ static int gm_knobs::* gm_find_knob(const char* name) {
     (void)gm_knob();
     static const struct { const char* name; int gm_knobs::*field; } tab[] = {
         {"GM_GEMM_SPLIT_MIN_TILES", &gm_knobs::gemm_split_min_tiles}, {"GM_CENTRE_STORE", &gm_knobs::centre_store}, {"GM_DEAD_ROWS", &gm_knobs::dead_rows},
-        {"GM_HEAD_STAGE", &gm_knobs::head_stage}, {"GM_HEAD_THREADS", &gm_knobs::head_threads}, {"GM_QUERY_STREAMS", &gm_knobs::query_streams}, {"GM_AGG_MID_LIST", &gm_knobs::agg_mid_list}, {"GM_AGG_MID_WIN", &gm_knobs::agg_mid_win}, {"GM_AGG_OBS_LIST", &gm_knobs::agg_obs_list}, {"GM_DEAD_TILES", &gm_knobs::dead_tiles}, {"GM_AGG_STREAM", &gm_knobs::agg_stream}, {"GM_AGG_STREAM_MIN_ROWS", &gm_knobs::agg_stream_min_rows},
+        {"GM_HEAD_STAGE", &gm_knobs::head_stage}, {"GM_HEAD_THREADS", &gm_knobs::head_threads}, {"GM_QUERY_STREAMS", &gm_knobs::query_streams}, {"GM_AGG_MID_LIST", &gm_knobs::agg_mid_list}, {"GM_AGG_MID_WIN", &gm_knobs::agg_mid_win}, {"GM_AGG_OBS_LIST", &gm_knobs::agg_obs_list}, {"GM_DEAD_TILES", &gm_knobs::dead_tiles}, {"GM_PACK_ROWS", &gm_knobs::pack_rows}, {"GM_AGG_STREAM", &gm_knobs::agg_stream}, {"GM_AGG_STREAM_MIN_ROWS", &gm_knobs::agg_stream_min_rows},
         {"GM_SPLIT16_MIN_ROWS", &gm_knobs::split16_min_rows}, {"GM_WGRAD_SPLIT_MIN_CHUNKS", &gm_knobs::wgrad_split_min_chunks}, {"GM_TIMING", &gm_knobs::timing},
         {"GM_FUSE_DIFF", &gm_knobs::fuse_diff}, {"GM_EXTRACT_PREF16", &gm_knobs::extract_pref16},
         {"neg_round", &gm_knobs::neg_round}, {"GM_NEG_ROUND", &gm_knobs::neg_round},

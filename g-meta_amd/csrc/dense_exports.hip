@@ -88,7 +88,7 @@ extern "C" int gm_dense_gemm(const gm_batch_t* b, const float* x, int64_t ldx, i
 // The fused aggregate + GEMM as fwd_update (model.hip) launches a fused layer: gm_dense_gemm with gm_gemm_args::fuse2 set.  The table is always the batch's own
 // (table 0: d_fuse2 over the caller's x; 1: d_fuse2_feat over the batch's feature table), so the kernel reads no row outside its operands
 // rowset -1: the batch's full tables (gm_dense_fused_gemm; s_keep: the caller's keep vector).  0 / 1 (gm_dense_fused_gemm_rows): the tables of the centre rows / of the
-// sources of their in-edges through row_view, keep: the set's keep vector, live_on: its tile flags, grid workgroups (0: the production rule)
+// sources of their in-edges through row_view, keep: the set's keep vector, live_on: its tile flags (2: and its packed tiles, GM_PACK_ROWS), grid workgroups (0: the production rule)
 static int dense_fused_gemm(const gm_batch_t* b, int32_t rowset, int32_t keep, int32_t live_on, int32_t grid, int32_t table, const float* x, int64_t ldx, int32_t K, const float* zside, int64_t ldz,
                             const float* zfull, int64_t ldzf, const float* W, int64_t w_stride, int32_t N, float* out, int64_t ldc, const float* s,
                             const float* s_keep, const float* bias, int64_t bias_stride, int32_t relu, uint8_t* relu_bits, float* zero_out,
@@ -114,7 +114,8 @@ static int dense_fused_gemm(const gm_batch_t* b, int32_t rowset, int32_t keep, i
         GM_REQUIRE(rowset <= 1 && !(rowset == 0 && table == 1) && grid >= 0, GM_EINVAL, "dense_fused_gemm_rows: bad row set");
         GM_REQUIRE(b->d_fwd_tab[0] && b->d_fwd_tab[1] && b->d_fwd_tab_feat && b->d_tile_live[0] && b->d_tile_live[1], GM_EINVAL, "dense_fused_gemm_rows: the batch carries no row-set tables");
         rs = rowset == 0 ? ROWS_CENTRE : ROWS_E1;
-        gemm_keep_rows(g, row_view(b, rs, false), keep != 0, live_on != 0, b->rows);
+        GM_REQUIRE(live_on != 2 || row_view(b, rs, false).pack, GM_EINVAL, "dense_fused_gemm_packed: the batch carries no packed row sets");
+        gemm_keep_rows(g, row_view(b, rs, false), keep != 0, live_on != 0, b->rows, live_on == 2);
         g.grid_test = grid;
     }
     g.fuse2 = row_view(b, rs, table == 1).tab;
@@ -142,6 +143,16 @@ extern "C" int gm_dense_fused_gemm_rows(const gm_batch_t* b, int32_t rowset, int
                             bias, bias_stride, relu, relu_bits, zero_out, amax_out, mode, launched, stream);
 }
 
+// ... over the row set's PACKED tiles, as the same layers launch it under GM_PACK_ROWS (tests): the set's keep vector, its tile flags and its packed tables
+// (gm_batch::pack), three-piece kernel, grid workgroups (0: the production rule)
+extern "C" int gm_dense_fused_gemm_packed(const gm_batch_t* b, int32_t rowset, int32_t grid, int32_t table, const float* x, int64_t ldx, int32_t K, const float* zside, int64_t ldz,
+                                          const float* W, int64_t w_stride, int32_t N, float* out, int64_t ldc, const float* bias, int64_t bias_stride, int32_t relu,
+                                          int32_t* launched, void* stream) {
+    GM_REQUIRE(b && (rowset == 0 || rowset == 1) && b->d_norm_c && b->d_norm_e1, GM_EINVAL, "dense_fused_gemm_packed: bad arguments");
+    return dense_fused_gemm(b, rowset, 1, 2, grid, table, x, ldx, K, zside, ldz, nullptr, 0, W, w_stride, N, out, ldc, b->d_norm, nullptr,
+                            bias, bias_stride, relu, nullptr, nullptr, nullptr, 1, launched, stream);
+}
+
 // The dZ product of the last layer over a dQ that holds its centre rows only, as bwd_dz (model.hip) launches it under GM_DEAD_ROWS (tests)
 extern "C" int gm_dense_dz_centre(const gm_batch_t* b, const float* dQ, int32_t K, const float* W, int64_t w_stride, int32_t N, float* T, void* stream) {
     GM_REQUIRE(b && dQ && W && T && b->d_dq_tab, GM_EINVAL, "dense_dz_centre: bad arguments");
@@ -150,6 +161,21 @@ extern "C" int gm_dense_dz_centre(const gm_batch_t* b, const float* dQ, int32_t 
     g.A = dQ; g.lda = K; g.B = W; g.b_stride = w_stride; g.transB = 1; g.C = T; g.ldc = N; g.K = K; g.N = N; g.np = 3;
     gemm_rows(g, batch_level(b)); gemm_dq_table(g, b, dQ, K);
     return launch_gemm(b, g, true, W, w_stride, 1, 3, nullptr, 0, false, "dense_dz_centre", (hipStream_t)stream);
+}
+
+// ... storing T's centre rows only, as bwd_dz launches it under GM_DEAD_ROWS=2 and up with the centres' tile flags (GM_DEAD_TILES); pack != 0: over the centres' packed
+// tiles (GM_PACK_ROWS).  grid workgroups (0: the production rule)
+extern "C" int gm_dense_dz_centre_rows(const gm_batch_t* b, const float* dQ, int32_t K, const float* W, int64_t w_stride, int32_t N, float* T, int32_t pack, int32_t grid, void* stream) {
+    GM_REQUIRE(b && dQ && W && T && b->d_dq_tab && b->d_norm_c && b->d_tile_live[0] && grid >= 0, GM_EINVAL, "dense_dz_centre_rows: bad arguments");
+    GM_REQUIRE((N == 256 || N == 128) && K % 16 == 0 && K >= 64, GM_EINVAL, "dense_dz_centre_rows: the fused split kernel needs N = 128 or 256 and K a multiple of 16 (>= 64)");
+    const RowView v = row_view(b, ROWS_CENTRE, false);
+    GM_REQUIRE(!pack || v.pack, GM_EINVAL, "dense_dz_centre_rows: the batch carries no packed row sets");
+    gm_gemm_args g{};
+    g.A = dQ; g.lda = K; g.B = W; g.b_stride = w_stride; g.transB = 1; g.C = T; g.ldc = N; g.K = K; g.N = N; g.np = 3;
+    gemm_rows(g, batch_level(b)); gemm_dq_table(g, b, dQ, K);
+    gemm_keep_rows(g, v, true, true, b->n_c, pack != 0);
+    g.grid_test = grid;
+    return launch_gemm(b, g, true, W, w_stride, 1, 3, nullptr, 0, false, "dense_dz_centre_rows", (hipStream_t)stream);
 }
 
 // GM_DEAD_ROWS=2 (tests): the last layer's transposed aggregate dQ_prev = relu' norm A^T T as bwd_agg_t (model.hip) launches it.  keep != 0: T read through the batch's
@@ -384,9 +410,21 @@ extern "C" int gm_dense_fuse_counts(const gm_batch_t* b, int64_t* counts) {
 // list [info[6]] int32, 3 hub rows of orientation o [info[1]] int32; 4 / 5 / 6 the per-row source tables gm_batch::d_fuse2 / d_fuse2_feat / d_dq_tab, [rows] entries
 // of four int32 {u0, u1, w0, w1}; 7 / 8 / 9 the forward-only passes' tables of GM_DEAD_ROWS=3 in the same layout: the last layer's (gm_batch::d_fwd_tab[0]), the layer
 // below it over batch rows (d_fwd_tab[1]) and over the feature table (d_fwd_tab_feat); 10 / 11 / 12 the lists of observable rows gm_batch::obs[0 .. 2], int32; 13 / 14 the tile flags
-// gm_batch::d_tile_live[0 / 1], one int32 per GEMM row tile): n entries -> dst (device)
+// gm_batch::d_tile_live[0 / 1], one int32 per GEMM row tile; 15 / 16 the packed row ids of the centre rows / of the sources of their in-edges (gm_batch::pack[0 / 1].rowid,
+// up to the host's bound), 17 / 18 their packed tile tables ({set, offset, nrows}: n counts int32 words, up to three per tile of the bound), 19 / 20 their tile counts
+// (one int32)): n entries -> dst (device)
 extern "C" int gm_dense_agg_table(const gm_batch_t* b, int32_t which, int32_t transposed, void* dst, int64_t n, void* stream) {
-    GM_REQUIRE(b && dst && n >= 0 && which >= 0 && which <= 14, GM_EINVAL, "dense_agg_table: bad arguments");
+    GM_REQUIRE(b && dst && n >= 0 && which >= 0 && which <= 20, GM_EINVAL, "dense_agg_table: bad arguments");
+    if (which >= 15) {      // 15 .. 20: the packed row sets (gm_batch::pack)
+        const gm_batch::pack_set& pk = b->pack[(which - 15) & 1];
+        const int kind = (which - 15) >> 1;
+        const int32_t* src = kind == 0 ? pk.rowid : kind == 1 ? pk.tiles : pk.count;
+        const int64_t have = !pk.tiles ? 0 : kind == 0 ? pk.cap_rows : kind == 1 ? 3 * (int64_t)pk.cap_tiles : 1;
+        GM_REQUIRE(pk.tiles && src && n <= have, GM_EINVAL, "dense_agg_table: table %d holds %lld entries", which, (long long)have);
+        if (n) GM_HIP(hipMemcpyAsync(dst, src, 4 * (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        gm_batch_mark_use(b, (hipStream_t)stream);
+        return GM_OK;
+    }
     if (which >= 13) {      // 13 / 14: the tile flags of the centre rows / of the sources of their in-edges (gm_batch::d_tile_live), one int32 per GEMM row tile
         const int32_t* fl = b->d_tile_live[which - 13];
         GM_REQUIRE(fl && n <= b->n_tiles, GM_EINVAL, "dense_agg_table: table %d holds %lld entries", which, (long long)(fl ? b->n_tiles : 0));

@@ -830,6 +830,51 @@ __global__ __launch_bounds__(GM_GEMM_BM) void k_tile_live(const int32_t* tiles, 
     const int any_c = __syncthreads_or(c), any_e = __syncthreads_or(e);
     if (r == 0) { live_c[t] = any_c ? 1 : 0; live_e1[t] = any_e ? 1 : 0; }
 }
+// GM_PACK_ROWS tables (gm_batch::pack): one block per set walks the set's rows in ascending order and appends every row with the sign bit of `keep` clear to the set's
+// region [base[t], base[t + 1]) of the packed arrays: its row id, |keep|, and its entries of up to two per-row tables.  cnt[t]: the rows appended (never more than the
+// region holds: base comes from the host's bounds of the same counts)
+#define PACK_BLOCK 1024
+__global__ __launch_bounds__(PACK_BLOCK) void k_pack_rows(const int32_t* set_row_off, const int32_t* base, const float* keep, const int4* src0, const int4* src1,
+                                                          int32_t* rowid, float* scale, int4* dst0, int4* dst1, int32_t* cnt) {
+    __shared__ int wsum[PACK_BLOCK / 64];
+    const int t = blockIdx.x, r0 = set_row_off[t], r1 = set_row_off[t + 1], o0 = base[t], room = base[t + 1] - o0;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int done = 0;
+    for (int rb = r0; rb < r1; rb += PACK_BLOCK) {
+        const int r = rb + threadIdx.x;
+        const float kv = r < r1 ? keep[r] : -1.f;
+        const bool on = r < r1 && !(__float_as_uint(kv) >> 31);
+        const unsigned long long m = __ballot(on);
+        if (lane == 0) wsum[w] = __popcll(m);
+        __syncthreads();
+        int before = 0, all = 0;
+        for (int k = 0; k < PACK_BLOCK / 64; ++k) { const int c = wsum[k]; before += k < w ? c : 0; all += c; }
+        const int at = done + before + __popcll(m & ((1ull << lane) - 1ull));
+        if (on && at < room) {
+            rowid[o0 + at] = r; scale[o0 + at] = kv;
+            if (src0) dst0[o0 + at] = src0[r];
+            if (src1) dst1[o0 + at] = src1[r];
+        }
+        done += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) cnt[t] = done < room ? done : room;
+}
+// ... and the packed tile table {set, offset, nrows <= GM_GEMM_BM} over those counts, sets in order, with the number of tiles in *count (one block)
+__global__ __launch_bounds__(64) void k_pack_tiles(const int32_t* cnt, const int32_t* base, int sets, int cap_tiles, int32_t* tiles, int32_t* count) {
+    __shared__ int first;
+    if (threadIdx.x == 0) first = 0;
+    __syncthreads();
+    for (int t = 0; t < sets; ++t) {
+        const int n = cnt[t], nt = (n + GM_GEMM_BM - 1) / GM_GEMM_BM, f = first;
+        for (int j = threadIdx.x; j < nt; j += blockDim.x)
+            if (f + j < cap_tiles) { int32_t* q = tiles + 3 * (int64_t)(f + j); q[0] = t; q[1] = base[t] + j * GM_GEMM_BM; q[2] = min(GM_GEMM_BM, n - j * GM_GEMM_BM); }
+        __syncthreads();
+        if (threadIdx.x == 0) first = min(cap_tiles, f + nt);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *count = first;
+}
 // what the partial aggregate launch over flag vector `obs` touches: rows of more than maxdeg in-edges with a positive flag and their in-edges (out[0], out[1]); their
 // sources marked in `bits` (k_count_bits counts them)
 __global__ void k_fwd_count(const int32_t* indptr, const int32_t* indices, const float* obs, int64_t rows, int maxdeg, uint32_t* bits, unsigned long long* out) {
@@ -1285,6 +1330,39 @@ static int finalize_finish(gm_batch* b, hipStream_t s, gm_stager& sg, FinalizeCt
     const std::vector<int32_t> ct = set_spans(c_set_off, GM_GEMM_BM), cc = set_spans(c_set_off, gm_wgrad_chunk_rows(c_set_off), &ccoff), ec = set_spans(e_set_off, gm_wgrad_chunk_rows(e_set_off), &ecoff);
     b->n_c_tiles = (int32_t)(ct.size() / 3); b->n_c_chunks = (int32_t)(cc.size() / 3); b->n_e1_chunks = (int32_t)(ec.size() / 3);
     GM_TRY(upload_tables(b, sg, s, {{&b->d_c_tiles, &ct}, {&b->d_c_chunks, &cc}, {&b->d_c_set_chunk_off, &ccoff}, {&b->d_e1_chunks, &ec}, {&b->d_e1_set_chunk_off, &ecoff}}));
+    // ---- GM_PACK_ROWS: the centre rows and the sources of their in-edges packed per set (gm_batch::pack).  No host wait: the regions and the tile tables are sized by
+    // the host's bounds -- per set its centres / the in-edges of its centres, capped by its rows -- and the launches read the tile count on the device
+    if (b->rows > 0 && b->d_norm_c && b->d_norm_e1 && b->d_tiles && b->n_tiles > 0 && b->sets > 0) {
+        const float* keep[2] = {b->d_norm_c, b->d_norm_e1};
+        const void* src[2][2] = {{b->d_fwd_tab[0], b->d_dq_tab}, {b->d_fwd_tab[1], b->d_fwd_tab_feat}};
+        for (int k = 0; k < 2; ++k) {
+            gm_batch::pack_set& pk = b->pack[k];
+            const std::vector<int32_t>& off = k == 0 ? c_set_off : e_set_off;
+            std::vector<int32_t> base(b->sets + 1, 0);
+            int32_t cap_tiles = 0;
+            for (int t = 0; t < b->sets; ++t) {
+                const int32_t bound = std::min<int32_t>(off[t + 1] - off[t], b->h_set_row_off[t + 1] - b->h_set_row_off[t]);
+                base[t + 1] = base[t] + bound; cap_tiles += (bound + GM_GEMM_BM - 1) / GM_GEMM_BM;
+            }
+            int32_t* d_base = nullptr;
+            GM_TRY(upload_tables(b, sg, s, {{&d_base, &base}}));
+            pk.cap_rows = base[b->sets]; pk.cap_tiles = cap_tiles; pk.keep = keep[k];
+            GM_TRY(gm_balloc(b, &pk.rowid, (size_t)pk.cap_rows, s)); GM_TRY(gm_balloc(b, &pk.scale, (size_t)pk.cap_rows, s));
+            GM_TRY(gm_balloc(b, &pk.set_cnt, (size_t)b->sets, s)); GM_TRY(gm_balloc(b, &pk.count, 1, s));
+            int32_t* tl = nullptr;
+            GM_TRY(gm_balloc(b, &tl, (size_t)3 * std::max(cap_tiles, 1), s));
+            for (int j = 0; j < 2; ++j) {
+                pk.src_tab[j] = src[k][j];
+                if (src[k][j]) { int4* d = nullptr; GM_TRY(gm_balloc(b, &d, (size_t)pk.cap_rows, s)); pk.tab[j] = d; }
+            }
+            hipLaunchKernelGGL(k_pack_rows, dim3(b->sets), dim3(PACK_BLOCK), 0, s, b->d_set_row_off, d_base, keep[k], (const int4*)pk.src_tab[0], (const int4*)pk.src_tab[1],
+                               pk.rowid, pk.scale, (int4*)pk.tab[0], (int4*)pk.tab[1], pk.set_cnt);
+            hipLaunchKernelGGL(k_pack_tiles, dim3(1), dim3(64), 0, s, pk.set_cnt, d_base, b->sets, cap_tiles, tl, pk.count);
+            GM_HIP(hipGetLastError());
+            pk.tiles = tl;
+        }
+    }
+    tm.lap("pack-rows");
     gm_dev_free(d_eoff, s);
     return GM_OK;
 }

@@ -524,6 +524,16 @@ static int launch_gemm_nn(const gm_gemm_args& a, hipStream_t s) {
             const int grid = std::min(a.n_tiles, a.grid_test > 0 ? a.grid_test : mult_f * grid_cap);
             // dead tiles: only where the kernel's epilogue has nothing to leave for a row that is not kept (keep_signed, no relu' bits, no zero fill), three pieces
             if (a.tile_live && a.row_scale_keep && !a.relu_bits && !a.zero_out && !f16) k.tile_live = a.tile_live;
+            // packed rows, in the flags' place: the set's kept rows as full tiles with the launch's own table and scales in packed order; every other tile is a dead one
+            if (k.tile_live && a.pack && a.pack->tiles && a.row_scale_keep == a.pack->keep) {
+                const gm_batch::pack_set& pk = *a.pack;
+                for (int t = 0; t < 2; ++t)
+                    if (pk.src_tab[t] && pk.tab[t] && a.fuse2 == pk.src_tab[t]) {
+                        k.f2 = reinterpret_cast<const int4*>(pk.tab[t]); k.row_scale = pk.scale; k.tile_live = nullptr;
+                        k.pk_tiles = pk.tiles; k.pk_rowid = pk.rowid; k.pk_count = pk.count;
+                        break;
+                    }
+            }
             GM_TRY(f16 ? (launch_gemm_split<true, 2>(a, k, grid, false, s)) : (launch_gemm_split<true, 3>(a, k, grid, false, s)));
         } else {
             const int grid = std::min(a.n_tiles, grid_cap);

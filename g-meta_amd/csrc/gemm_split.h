@@ -76,6 +76,11 @@ struct SplitGemmK {
     // (atomicMax on the bit pattern) -- the bound of whoever consumes C
     gm_bound a_bound, b_bound; unsigned* amax_out;
     int keep_signed;                           // row_scale carries "nobody reads this row" in its sign bit: such rows are computed and not stored
+    // k_gemm_split_p<true, ., ., 3>, where tile_live would apply: the kept rows of the launch PACKED into the fewest tiles (gm_batch::pack).  pk_tiles: {set, offset into the
+    // packed arrays, nrows} per packed tile, *pk_count of them; f2 and row_scale then are the packed copies (entry offset + r belongs to row pk_rowid[offset + r] of C, every
+    // scale has its sign bit clear).  The launch still walks n_tiles tiles per workgroup ownership: the packed ones are dealt out round robin and fed, every other tile
+    // is a dead one.  NULL: rows are the tiles' own
+    const int32_t* pk_tiles; const int32_t* pk_rowid; const int32_t* pk_count;
 };
 #define GM_SPLIT_FUSE_SELF 0x40000000
 #define GM_SPLIT_FUSE_ZERO 0x20000000
@@ -290,10 +295,16 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
     // sequence over that list -- nt tiles, the i-th of them tile ord(i) of the workgroup -- so every role executes the same 1 + nt * nchunks barriers, and
     // whatever was keyed on the tile ordinal's parity (scales / biasl, the A stage, the B stage) is keyed on i.  The compute waves issue the MFMAs of the dead tiles
     // in front of each live one (and behind the last) on zero registers, without a barrier.  A workgroup of more tiles than the list holds walks all of them.
-    int nt = ntb; bool listed = false;
+    // Packed rows (SplitGemmK::pk_tiles).  The workgroup feeds packed tiles b, b + G, ... (at most ceil(count / G) of them, whatever logical() does with the others) and
+    // issues the MFMAs of the remaining ntb - nt tiles of its share as dead chunks behind them.  The count comes through the scalar cache.  The list's LDS words hold the
+    // row ids of the tile instead ([2][128] by tile parity, staged by the A feeders beside `scales`).
+    int nt = ntb; bool listed = false, packed = false;
     const int* live_idx = reinterpret_cast<const int*>(smem + OFF_LIVE);
     if constexpr (LIVE) {
-        if (g.tile_live && g.keep_signed && !g.relu_bits && !g.zero_out && ntb > 0 && ntb <= LIVE_CAP) {
+        if (g.pk_tiles && g.keep_signed && !g.relu_bits && !g.zero_out && ntb > 0) {
+            const int npk = min((int)gs_sload(g.pk_count), nb);
+            nt = b < npk ? min(ntb, (npk - b + G - 1) / G) : 0; listed = true; packed = true;
+        } else if (g.tile_live && g.keep_signed && !g.relu_bits && !g.zero_out && ntb > 0 && ntb <= LIVE_CAP) {
             int* lw = reinterpret_cast<int*>(smem + OFF_LIVE);
             if (wave == 0) {
                 int n = 0;
@@ -313,6 +324,10 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
     auto ord = [&](int i) -> int {                                                    // i-th tile this workgroup walks -> its ordinal among the workgroup's tiles
         if constexpr (LIVE) { if (listed) return __builtin_amdgcn_readfirstlane(live_idx[i]); }
         return i;
+    };
+    auto wtile = [&](int i) -> GsTile {                                               // i-th tile this workgroup walks -> {set, row0 (packed: offset), nrows}
+        if constexpr (LIVE) { if (packed) return gs_tile(g.pk_tiles, b + i * G); }
+        return tile_of(b + ord(i) * G);
     };
     // n chunks of a dead tile on a compute wave: the chunk's MFMAs in the six-product order over the wave's 2 MI accumulator blocks, operands and accumulators zero
     // registers nobody reads (asm volatile: the compiler would delete builtins without a reader).  s_nop: the hazard recogniser does not look into the asm.
@@ -374,10 +389,10 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
         const int64_t b_chunk_bytes = (int64_t)BK * g.N * 2;
         // chunks are issued in order: (tile, chunk) counters instead of a division per chunk, the tile's set looked up once per tile
         int ib_c = 0, ib_ti = 0;
-        uint64_t ib_base = (uint64_t)(uintptr_t)(g.Bt + (int64_t)tile_of(b + ord(0) * G).set * g.bt_stride);
+        uint64_t ib_base = (uint64_t)(uintptr_t)(g.Bt + (int64_t)wtile(0).set * g.bt_stride);
         int ib_st = 0;                                                                // B stage of the next chunk to issue (gc % NB)
         auto issue_b = [&](int gc) {                                                  // global chunk gc (= the next in order) -> B stage gc % NB
-            if (ib_c == nchunks) { ib_c = 0; ++ib_ti; ib_base = (uint64_t)(uintptr_t)(g.Bt + (int64_t)tile_of(b + ord(ib_ti) * G).set * g.bt_stride); }
+            if (ib_c == nchunks) { ib_c = 0; ++ib_ti; ib_base = (uint64_t)(uintptr_t)(g.Bt + (int64_t)wtile(ib_ti).set * g.bt_stride); }
             const uint64_t base = ib_base + (uint64_t)(ib_c * b_chunk_bytes);
             ++ib_c;
             const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)base), bhi = __builtin_amdgcn_readfirstlane((unsigned)(base >> 32));
@@ -436,7 +451,7 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
         float as_next = 1.f, as_cur = 1.f, inv_next = 1.f, inv_cur = 1.f;             // NP == 2: A scale of the tile being loaded / stored; 1 / (s_a s_b) for the epilogue
         auto fq_prefetch = [&](int ti) {                                              // table entries of tile ti (if any) -> fq, counted loads
             if (ti >= nt) return;
-            const GsTile t = tile_of(b + ord(ti) * G);
+            const GsTile t = wtile(ti);
 #pragma unroll
             for (int p = 0; p < A_PER; ++p) {
                 const int4* q = g.f2 + t.row0 + min(rr[p], t.nrows - 1);
@@ -444,7 +459,7 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
             }
         };
         auto la_tile = [&](int ti, bool consts) {
-            const GsTile t = tile_of(b + ord(ti) * G);
+            const GsTile t = wtile(ti);
             if constexpr (NP == 2) { as_next = a_scale_of(t.set); inv_next = (1.f / as_next) * (1.f / b_scale_of(t.set)); }
             if constexpr (GATHER) {
                 if constexpr (A_PER == 2) asm volatile("" : "+v"(fq[0]), "+v"(fq[A_PER - 1]) :: "memory");   // fetched a tile ago; every wait since then covered them
@@ -465,7 +480,12 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
                 for (int p = 0; p < A_PER; ++p) la_src[p][0] = g.A + (int64_t)(t.row0 + min(rr[p], t.nrows - 1)) * g.lda + c4;
             }
             if (consts) {
-                if (g.row_scale) { const float* q = g.row_scale + t.row0 + min(ft & (BM - 1), t.nrows - 1); asm volatile("global_load_dword %0, %1, off" : "=v"(rc_sc) : "v"(q) : "memory"); }
+                if (g.row_scale) {
+                    const float* q = g.row_scale + t.row0 + min(ft & (BM - 1), t.nrows - 1);
+                    // packed rows: only lanes ft < BM carry a scale -- the other BM lanes of the same counted load fetch the tile's row ids (no further load, no further register)
+                    if constexpr (LIVE) { if (packed && ft >= BM) q = reinterpret_cast<const float*>(g.pk_rowid + t.row0 + min(ft & (BM - 1), t.nrows - 1)); }
+                    asm volatile("global_load_dword %0, %1, off" : "=v"(rc_sc) : "v"(q) : "memory");
+                }
                 if (g.bias) { const float* q = g.bias + (int64_t)t.set * g.bias_stride + min(ft, BN - 1); asm volatile("global_load_dword %0, %1, off" : "=v"(rc_b) : "v"(q) : "memory"); }
             }
         };
@@ -498,7 +518,7 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
                 as_cur = as_next; inv_cur = inv_next;
                 // the loads run PF_DA - 1 chunks ahead: with fewer chunks per tile than that (K = 32), la_tile has already moved as_next to a
                 // LATER tile, whose set may have another A bound -- take this tile's own (the short-K path reads its constants per tile anyway)
-                if constexpr (NP == 2) { if (!fast_consts) as_cur = a_scale_of(tile_of(b + ord(sa_ti) * G).set); }
+                if constexpr (NP == 2) { if (!fast_consts) as_cur = a_scale_of(wtile(sa_ti).set); }
                 if constexpr (GATHER) {                                                // the loads of this tile were issued with w_next's table entries
 #pragma unroll
                     for (int p = 0; p < A_PER; ++p) { w_cur[p][0] = w_next[p][0]; w_cur[p][1] = w_next[p][1]; }
@@ -506,8 +526,18 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
             }
             if (sa_c == 0 && sa_ti > 0 && fast_consts) {                               // first chunk of a later tile: its consts arrived with (before) this chunk's loads
                 asm volatile("" : "+v"(rc_sc), "+v"(rc_b) :: "memory");
-                if (ft < BM) scales[(sa_ti & 1) * GS_BM + ft] = rc_sc * inv_cur;
-                if (ft < BN) biasl[(sa_ti & 1) * BN + ft] = rc_b;
+                if constexpr (LIVE) {
+                    // the three LDS offsets as opaque SCALARS (the region's offset lies beyond a ds_write's immediate): left to itself the compiler keeps one
+                    // address VGPR per region for the whole kernel, and the row ids' brought the kernel above its 120 VGPRs
+                    int o_sc = OFF_SC + (sa_ti & 1) * GS_BM * 4, o_b = OFF_BIAS + (sa_ti & 1) * BN * 4, o_id = OFF_LIVE + (sa_ti & 1) * GS_BM * 4;
+                    asm volatile("" : "+s"(o_sc), "+s"(o_b), "+s"(o_id));
+                    if (ft < BM) *reinterpret_cast<float*>(smem + o_sc + ft * 4) = rc_sc * inv_cur;
+                    if (ft < BN) *reinterpret_cast<float*>(smem + o_b + ft * 4) = rc_b;
+                    if (packed && ft >= BM) *reinterpret_cast<int*>(smem + o_id + (ft - BM) * 4) = __float_as_int(rc_sc);      // lanes BM .. 2 BM - 1 hold the row ids
+                } else {
+                    if (ft < BM) scales[(sa_ti & 1) * GS_BM + ft] = rc_sc * inv_cur;
+                    if (ft < BN) biasl[(sa_ti & 1) * BN + ft] = rc_b;
+                }
             }
             ++sa_c;
             char* As = smem + (gc & 1) * A_ST;
@@ -535,15 +565,23 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
         };
         // row scales + bias of tile ti -> LDS (parity ti & 1); ordinary loads, completed with the vmcnt(0) below
         auto stage_tile_consts = [&](int ti) {
-            const GsTile t = tile_of(b + ord(ti) * G);
+            const GsTile t = wtile(ti);
             const int set = t.set, row0 = t.row0, nrows = t.nrows;
             float sc = 1.f;
             if (g.row_scale) sc = g.row_scale[row0 + min(ft & (BM - 1), nrows - 1)];
             float b0 = 0.f;
             if (g.bias) b0 = (g.bias + (int64_t)set * g.bias_stride)[min(ft, BN - 1)];
             if constexpr (NP == 2) sc *= (1.f / a_scale_of(set)) * (1.f / b_scale_of(set));
-            if (ft < BM) scales[(ti & 1) * GS_BM + ft] = sc;
-            if (ft < BN) biasl[(ti & 1) * BN + ft] = b0;
+            if constexpr (LIVE) {                                                      // (opaque scalar offsets: see store_a)
+                int o_sc = OFF_SC + (ti & 1) * GS_BM * 4, o_b = OFF_BIAS + (ti & 1) * BN * 4, o_id = OFF_LIVE + (ti & 1) * GS_BM * 4;
+                asm volatile("" : "+s"(o_sc), "+s"(o_b), "+s"(o_id));
+                if (ft < BM) *reinterpret_cast<float*>(smem + o_sc + ft * 4) = sc;
+                if (ft < BN) *reinterpret_cast<float*>(smem + o_b + ft * 4) = b0;
+                if (packed && ft < BM) *reinterpret_cast<int*>(smem + o_id + ft * 4) = g.pk_rowid[row0 + min(ft, nrows - 1)];
+            } else {
+                if (ft < BM) scales[(ti & 1) * GS_BM + ft] = sc;
+                if (ft < BN) biasl[(ti & 1) * BN + ft] = b0;
+            }
         };
         static_assert((A_PER == 1 || A_PER == 2) && PF_DA >= 2 && PF_DA <= 8, "wait macro is written for 1 or 2 rows per lane and chunk");
 #define PF_WAIT_SLOT(NEWER, SLOT)                                                                                                              \
@@ -624,7 +662,7 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
         };
         int walked = 0;                                                               // tiles of the workgroup behind us, dead ones included
         for (int ti = 0; ti < nt; ++ti) {
-            if constexpr (LIVE) { if (listed) { const int o = ord(ti); dead_chunks((o - walked) * nchunks); walked = o + 1; } }
+            if constexpr (LIVE) { if (listed && !packed) { const int o = ord(ti); dead_chunks((o - walked) * nchunks); walked = o + 1; } }
             gm_f32x16 acc[MI][2];
 #pragma unroll
             for (int i = 0; i < MI; ++i)
@@ -672,7 +710,7 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
             // ---- epilogue of tile ti: stores only (no global load, no barrier, no LDS staging).  The accumulators are transposed inside the
             // quads of lanes (gs_quad_transpose) so that a lane stores 16 bytes of ONE row and eight lanes cover 128 contiguous bytes of it; the
             // LDS round trips of the staged epilogue (8.6 k of a tile's 47 k cycles with the matrix pipe idle) are gone.
-            const GsTile tl = tile_of(b + ord(ti) * G);                // scalar (SMEM) loads: lgkmcnt, not vmcnt
+            const GsTile tl = wtile(ti);                // scalar (SMEM) loads: lgkmcnt, not vmcnt
             const int row0 = tl.row0, nrows = tl.nrows;
             const float* sc_t = scales + (ti & 1) * GS_BM;
             const int t4 = li & 3, q4 = li >> 2;
@@ -695,7 +733,10 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
                     const bool keep = !g.keep_signed || !(__float_as_uint(sc_raw) >> 31);
                     if (keep_only && __ballot(keep) == 0ull) continue;
                     const float sc = fabsf(sc_raw);
-                    const int64_t row = row0 + rl;
+                    int64_t row = row0 + rl;
+                    // (every packed row is kept: its scale's sign is clear.  volatile: read here, one at a time -- eight of them hoisted above the stores cost the kernel
+                    // its 120 VGPRs)
+                    if constexpr (LIVE) { if (packed) row = reinterpret_cast<const volatile int*>(smem + OFF_LIVE)[(ti & 1) * GS_BM + rl]; }
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
                         float a0 = acc[i][j][gq * 4 + 0], a1 = acc[i][j][gq * 4 + 1], a2 = acc[i][j][gq * 4 + 2], a3 = acc[i][j][gq * 4 + 3];
@@ -725,7 +766,7 @@ __global__ __launch_bounds__(1024) void k_gemm_split_p(SplitGemmK g) {
                 }
             }
         }
-        if constexpr (LIVE) { if (listed) dead_chunks((ntb - walked) * nchunks); }        // the dead tiles behind the last live one
+        if constexpr (LIVE) { if (packed) walked = nt; if (listed) dead_chunks((ntb - walked) * nchunks); }        // the dead tiles behind the last live one (packed: all of them)
         if constexpr (NP == 2) { if (g.amax_out && vmax_set >= 0) vmax_flush_last(); }     // (bit patterns of non-negative floats order as integers)
     }
 }

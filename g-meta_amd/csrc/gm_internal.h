@@ -214,6 +214,15 @@ struct gm_batch {
     // GM_DEAD_TILES (k_tile_live, next to k_fwd_tables): one word per tile of d_tiles, non-zero where some row of the tile has the sign bit of d_norm_c ([0]) / d_norm_e1 ([1])
     // clear.  A split GEMM that stores those rows only issues a zero tile's MFMAs and nothing else of it (gm_gemm_args::tile_live)
     int32_t* d_tile_live[2] = {nullptr, nullptr};
+    // GM_PACK_ROWS (k_pack_rows / k_pack_tiles, at the end of the finalisation): the same two row sets PACKED per set (task), ascending by row, into the fewest tiles --
+    // [0] the rows with the sign of d_norm_c clear, [1] those of d_norm_e1.  Set t owns entries [base_t, base_t + kept_t) of the packed arrays, base_t the prefix of the
+    // host's bounds (the set's centres / the in-edges of its centres, capped by its rows).  rowid: batch row of every packed entry; scale: |keep vector| of that row;
+    // tab[k]: src_tab[k]'s entry of that row (centres: d_fwd_tab[0], d_dq_tab; e1: d_fwd_tab[1], d_fwd_tab_feat); tiles: {set, offset, nrows <= GM_GEMM_BM} in d_tiles'
+    // format, *count of them (a set without a kept row has none; never more than cap_tiles, and never more than the set's own tiles of d_tiles).
+    // A split GEMM that would take d_tile_live feeds these tiles instead and stores row r of a tile at rowid[offset + r] (gm_gemm_args::pack)
+    struct pack_set { int32_t* rowid = nullptr; int32_t* tiles = nullptr; int32_t* count = nullptr; float* scale = nullptr; const float* keep = nullptr;
+                      const void* src_tab[2] = {nullptr, nullptr}; void* tab[2] = {nullptr, nullptr}; int32_t* set_cnt = nullptr; int32_t cap_rows = 0, cap_tiles = 0; };
+    pack_set pack[2];
     // The observable rows of the restricted aggregate launches as compact ascending lists (finalize_finish, next to d_mid; GM_AGG_OBS_LIST).  [0]: rows of GM_FUSE_MAXDEG+1 ..
     // heavy_deg in-edges with d_obs[0] positive (the last layer's partial aggregate), [1]: the same with d_obs[1] (the layer below), [2]: rows with the sign of d_norm_e1
     // clear (the last layer's transposed aggregate; its hub rows stay listed, the windows pass over them).  [0] is built on the host from the centres' in-degrees (length
@@ -268,6 +277,7 @@ struct gm_knobs {
     int agg_mid_win;               // GM_AGG_MID_WIN: rows per wave window over that list (0 = by its length)
     int agg_obs_list;              // GM_AGG_OBS_LIST: the aggregate launches restricted to the observable rows walk the batch's compact lists of them (1, default; gm_batch::obs) or every row's descriptor (0).  Read at launch time (plan_pass): the lists are built either way
     int dead_tiles;                // GM_DEAD_TILES: a fused three-piece split GEMM that stores the rows of a keep vector only takes the batch's tile flags (1, default; gm_batch::d_tile_live): a tile without a kept row issues its MFMAs on zero registers and nothing else.  0: every tile is fed.  Read by plan_pass alone; the flags are built either way
+    int pack_rows;                 // GM_PACK_ROWS: a launch that takes the tile flags takes the row set's packed tiles instead (1, default; gm_batch::pack): the kept rows fill the fewest tiles, every other tile is a dead one.  0: the tile flags.  Read by plan_pass alone; the tables are built either way
     int agg_mid_list;              // GM_AGG_MID_LIST: the partial aggregate launch of a fused pass walks a compact list of its window rows (1, default) or every row (0)
     int query_streams;             // GM_QUERY_STREAMS: 2 = the query evaluations of gm_meta_step alternate between two streams; anything else (default 0) = one stream
     int head_threads;              // GM_HEAD_THREADS: workgroup size of k_head_loss: 256 or 512; anything else (default 0) = 1024
@@ -599,6 +609,8 @@ struct gm_gemm_args {
     int64_t rows;                       // total rows covered by the tiles (profiling: flops = 2*rows*K*N)
     const int32_t* tile_live;           // optional, with row_scale_keep: one word per tile, 0 = the tile holds no kept row (gm_batch::d_tile_live).  Taken by the fused three-piece split kernels
                                         //   where the launch writes neither relu_bits nor zero_out (gemm_split.h: SplitGemmK::tile_live); every other launch ignores it
+    const gm_batch::pack_set* pack;     // optional, in tile_live's place (same conditions): the row set's packed tiles (gm_batch::pack).  Taken where row_scale_keep is the set's keep vector and
+                                        //   fuse2 one of the tables it carries in packed order; every other launch ignores it
     int grid_test;                      // tests only (gm_dense_fused_gemm_rows): workgroups of a fused split launch; 0 = the production rule
     int* launched;                      // optional: receives the GM_GEMM_ID_* of the instantiation launched (host side).  Set only by the
                                         // numerics-test export gm_dense_gemm; the product path leaves it NULL
@@ -687,7 +699,8 @@ enum RowSet { ROWS_ALL, ROWS_SRC, ROWS_E1, ROWS_CENTRE };
 // set -- the full table's entry on its rows, the zero row everywhere else (gather: the layer reads the feature table; a centre-restricted layer never does, plan_check).
 // obs: the set's index into the tables of gm_batch_fwd_counts, -1 where it has none.  n: its rows as the host knows them (ROWS_E1: a bound, see rows_kept in model.hip)
 // live: one word per GEMM row tile, 0 = no row of the set in it (gm_batch::d_tile_live; NULL: every row / no flags)
-struct RowView { const float* keep; const float* sign; const void* tab; int obs; int64_t n; const int32_t* live; };
+// pack: the set's packed tiles (gm_batch::pack; NULL: every row / the batch carries none)
+struct RowView { const float* keep; const float* sign; const void* tab; int obs; int64_t n; const int32_t* live; const gm_batch::pack_set* pack; };
 RowView row_view(const gm_batch* b, RowSet rs, bool gather);
 // The rows a GEMM or a weight gradient runs over: their norm, GEMM row tiles, weight-gradient chunks and count.  The batch is one such level (batch_level); the cone
 // schedule has one per layer boundary and the row-sparse backward two compact ones (model.hip)
@@ -695,8 +708,9 @@ struct LevelView { const float* norm; const int32_t* tiles; int n_tiles; const i
 LevelView batch_level(const gm_batch* b);
 void gemm_rows(gm_gemm_args& g, const LevelView& v);       // row_scale, tiles, n_tiles, rows
 void wgrad_rows(gm_wgrad_args& w, const LevelView& v);     // a_scale, chunks, n_chunks, set_chunk_off, sets, rows
-// a GEMM that stores the rows of a set only (keep: row_scale_keep + the kept-row count of the launch accounting) and / or takes the set's tile flags (live)
-void gemm_keep_rows(gm_gemm_args& g, const RowView& v, bool keep, bool live, int64_t n_keep);
+// a GEMM that stores the rows of a set only (keep: row_scale_keep + the kept-row count of the launch accounting) and / or takes the set's tile flags (live) and, with
+// them, the set's packed tiles (pack: GM_PACK_ROWS)
+void gemm_keep_rows(gm_gemm_args& g, const RowView& v, bool keep, bool live, int64_t n_keep, bool pack = false);
 // the dZ GEMM over a dQ_L that holds its centre rows only: the fused loader reads them through gm_batch::d_dq_tab and zeros for every other row
 void gemm_dq_table(gm_gemm_args& g, const gm_batch* b, const float* dQ, int64_t ld);
 // orientation dir of the batch (0: A, the in-edges; 1: A^T) as an aggregate walks it -- CSR, rows, hub-row list, the edges' weights of a weighted batch (agg_graph) -- and

@@ -715,13 +715,13 @@ enum DqFill { DQ_MEMSET, DQ_ZEROED, DQ_CENTRE };
 //    nothing to launch) instead of every listed row's descriptor; NULL: today's launch
 //  dead_tiles (GM_DEAD_TILES): the update of a forward-only fused layer that stores the centre rows or the sources of their in-edges takes the batch's tile flags of that
 //    set: a tile without a stored row issues its MFMAs on zero registers -- no table fetch, no operand load, no LDS traffic, no barrier, no epilogue (gemm_split.h)
-struct LayerPlan { bool split, fuse; RowSet formed, stored; bool relu_bits; const gm_batch::obs_list* list; bool dead_tiles; };
+struct LayerPlan { bool split, fuse; RowSet formed, stored; bool relu_bits; const gm_batch::obs_list* list; bool dead_tiles, pack_rows; };      // pack_rows (GM_PACK_ROWS): with dead_tiles, the set's packed tiles in the flags' place
 // The pass: its kind, its layers, dQ_L, and what a gcn_backward(skip_head = 1) over it may do (GM_DEAD_ROWS=2; plan_backward, which resolves these against skip_head, has the bitwise argument).  t_centre: dQ_L is
 // left to its centre rows and the zero block behind T_L is there -- the dZ GEMM stores T_L's centre rows only, the transposed aggregate reads T_L through gm_batch::d_ect.
 // dq_e1: ... and the layer below is the first, aggregate-first, with a table-fed three-piece weight gradient: that aggregate stores only the rows of dQ_{L-1} that can be non-zero
 // t_list: ... and walks the compact list of those rows (gm_batch::obs[2]), as LayerPlan::list
 // t_dead_tiles (GM_DEAD_TILES): the table-read dZ launch under t_centre takes the centre rows' tile flags, as LayerPlan::dead_tiles
-struct PassPlan { PassKind kind; LayerPlan layer[GM_MAX_GCN]; DqFill dq; bool t_centre, dq_e1; const gm_batch::obs_list* t_list; bool t_dead_tiles; };
+struct PassPlan { PassKind kind; LayerPlan layer[GM_MAX_GCN]; DqFill dq; bool t_centre, dq_e1; const gm_batch::obs_list* t_list; bool t_dead_tiles, t_pack_rows; };      // t_pack_rows: as LayerPlan::pack_rows, for the dZ launch
 
 struct GcnCtx {
     const gm_batch* b; gm_layout L;
@@ -935,15 +935,16 @@ void gemm_rows(gm_gemm_args& g, const LevelView& v) { g.row_scale = v.norm; g.ti
 void wgrad_rows(gm_wgrad_args& w, const LevelView& v) {
     w.a_scale = v.norm; w.chunks = v.chunks; w.n_chunks = v.n_chunks; w.set_chunk_off = v.set_chunk_off; w.sets = v.sets; w.rows = v.rows;
 }
-void gemm_keep_rows(gm_gemm_args& g, const RowView& v, bool keep, bool live, int64_t n_keep) {
+void gemm_keep_rows(gm_gemm_args& g, const RowView& v, bool keep, bool live, int64_t n_keep, bool pack) {
     if (keep) { g.row_scale_keep = v.keep; g.n_keep = n_keep; }
     if (live) g.tile_live = v.live;
+    if (live && pack) g.pack = v.pack;
 }
 void gemm_dq_table(gm_gemm_args& g, const gm_batch* b, const float* dQ, int64_t ld) { g.fuse2 = b->d_dq_tab; g.zside = dQ; g.ldz = ld; }
 RowView row_view(const gm_batch* b, RowSet rs, bool gather) {
-    if (rs == ROWS_E1) return {b->d_norm_e1, b->d_obs[1], gather ? b->d_fwd_tab_feat : b->d_fwd_tab[1], 1, b->n_e1, b->d_tile_live[1]};
-    if (rs == ROWS_CENTRE) return {b->d_norm_c, b->d_obs[0], b->d_fwd_tab[0], 0, b->n_c, b->d_tile_live[0]};
-    return {rs == ROWS_SRC ? b->d_norm_src : nullptr, nullptr, gather ? b->d_fuse2_feat : b->d_fuse2, -1, rs == ROWS_SRC ? b->n_src : b->rows, nullptr};
+    if (rs == ROWS_E1) return {b->d_norm_e1, b->d_obs[1], gather ? b->d_fwd_tab_feat : b->d_fwd_tab[1], 1, b->n_e1, b->d_tile_live[1], b->pack[1].tiles ? &b->pack[1] : nullptr};
+    if (rs == ROWS_CENTRE) return {b->d_norm_c, b->d_obs[0], b->d_fwd_tab[0], 0, b->n_c, b->d_tile_live[0], b->pack[0].tiles ? &b->pack[0] : nullptr};
+    return {rs == ROWS_SRC ? b->d_norm_src : nullptr, nullptr, gather ? b->d_fuse2_feat : b->d_fuse2, -1, rs == ROWS_SRC ? b->n_src : b->rows, nullptr, nullptr};
 }
 // Rows of a set, and the by-source edges of those rows, for the launch accounting: exact when it is on (ROWS_E1: read back / counted once per batch at first use, which
 // synchronises the stream), their bounds otherwise -- nobody reads them then
@@ -1240,6 +1241,11 @@ static int plan_pass(const GcnCtx& c, const float* params, int64_t pstride, Pass
                                     row_view(b, lp.stored, false).live != nullptr;
         }
         p.t_dead_tiles = p.t_centre && c.np != 2 && b->d_tile_live[0] != nullptr;
+        // GM_PACK_ROWS: the same launches take the set's packed tiles where the batch carries them
+        if (gm_knob().pack_rows) {
+            for (int l = 0; l < Lg; ++l) p.layer[l].pack_rows = p.layer[l].dead_tiles && row_view(b, p.layer[l].stored, false).pack != nullptr;
+            p.t_pack_rows = p.t_dead_tiles && row_view(b, ROWS_CENTRE, false).pack != nullptr;
+        }
     }
     *plan = p; return plan_check(c, p);
 }
@@ -1297,7 +1303,7 @@ static int fwd_update(GcnCtx& c, int l, const float* params, int64_t pstride, co
     gm_gemm_args g{}; g.A = c.Z[l]; g.lda = fi; g.B = params + L.w_off[l]; g.b_stride = pstride; g.C = c.H[l]; g.ldc = fo; g.K = fi; g.N = fo;
     gemm_rows(g, batch_level(b)); g.bias = params + L.b_off[l]; g.bias_stride = pstride; g.relu = 1; g.relu_bits = lp.relu_bits ? c.M[l] : nullptr;
     // the other rows are computed, their relu' bits written, their values not stored (the kept-row count is for the launch accounting)
-    if (lp.stored != ROWS_ALL) gemm_keep_rows(g, row_view(b, lp.stored, false), true, lp.dead_tiles, rows_kept(b, lp.stored, st));
+    if (lp.stored != ROWS_ALL) gemm_keep_rows(g, row_view(b, lp.stored, false), true, lp.dead_tiles, rows_kept(b, lp.stored, st), lp.pack_rows);
     if (lp.split) {
         GM_TRY(weight_planes(c, params, pstride, l, 0, st, g));
         GM_REQUIRE(!(last && c.plan.dq == DQ_CENTRE) || g.np == 3, GM_EINVAL, "forward: dQ is left to its centre rows, which needs the three-piece kernels");
@@ -1349,7 +1355,7 @@ static int gcn_forward(GcnCtx& c, const float* params, int64_t pstride, float* l
 //    empty: obs_list::take == 2); reads T_l through gm_batch::d_ect; stores these rows of dQ_{l-1} (= g_rows of the layer below); walks this list of them (NULL: every row's descriptor)
 // Per call, fill_dq: this call zero-fills dQ_L whole before the head writes its centre rows (neither behind head_loss nor under the mean readout, whose backward writes every row)
 enum DzKind { DZ_NONE, DZ_SPLIT, DZ_WT, DZ_PLAIN };
-struct BwdLayer { RowSet g_rows; DzKind dz; bool dz_tab; RowSet t_rows; bool t_live, agg, t_ect; RowSet dq_rows; const gm_batch::obs_list* list; };
+struct BwdLayer { RowSet g_rows; DzKind dz; bool dz_tab; RowSet t_rows; bool t_live, agg, t_ect; RowSet dq_rows; const gm_batch::obs_list* list; bool t_pack; };
 struct BwdPlan { bool fill_dq; BwdLayer layer[GM_MAX_GCN]; };
 static int plan_backward(const GcnCtx& c, int skip_head, BwdPlan* out) {
     const gm_layout& L = c.L; const PassPlan& plan = c.plan; const int last = L.n_gcn - 1;
@@ -1384,7 +1390,7 @@ static int plan_backward(const GcnCtx& c, int skip_head, BwdPlan* out) {
         // dQ_L left to its centre rows always comes this way)
         bl.dz_tab = bl.dz == DZ_SPLIT && dq_centre && l == last;
         bl.t_rows = (bl.dz == DZ_SPLIT && t_centre && l == last) ? ROWS_CENTRE : ROWS_ALL;
-        bl.t_live = bl.t_rows == ROWS_CENTRE && plan.t_dead_tiles;
+        bl.t_live = bl.t_rows == ROWS_CENTRE && plan.t_dead_tiles; bl.t_pack = bl.t_live && plan.t_pack_rows;
         bl.t_ect = t_centre && l == last;
         bl.dq_rows = (bl.t_ect && dq_e1) ? ROWS_E1 : ROWS_ALL;      // the rows that launch works on (every other row leaves behind its descriptor)
         const gm_batch::obs_list* tl = bl.dq_rows == ROWS_E1 ? plan.t_list : nullptr;
@@ -1441,7 +1447,7 @@ static int bwd_dz(GcnCtx& c, int l, const BwdLayer& bl, gm_wgrad_args& w, const 
         // B = W^T with W stored [fi][fo]: the planes are W's own rows (no transpose)
         GM_TRY(weight_planes(c, params, pstride, l, 1, st, g));
         if (bl.dz_tab) gemm_dq_table(g, b, c.bufA, fo);
-        if (bl.t_rows != ROWS_ALL) gemm_keep_rows(g, row_view(b, bl.t_rows, false), true, bl.t_live, rows_kept(b, bl.t_rows, st));
+        if (bl.t_rows != ROWS_ALL) gemm_keep_rows(g, row_view(b, bl.t_rows, false), true, bl.t_live, rows_kept(b, bl.t_rows, st), bl.t_pack);
     } else if (bl.dz == DZ_WT) {
         // dZ = dQ @ W^T through the direct-to-LDS kernel on transposed weights: left there by the previous step's
         // weight-gradient reduction (which wrote these very weights), else transposed now (T x 256 KB)

@@ -703,6 +703,12 @@ int gm_dense_fused_gemm_rows(const gm_batch_t* b, int32_t rowset, int32_t keep, 
                              const float* zside, int64_t ldz, const float* zfull, int64_t ldzf, const float* W, int64_t w_stride, int32_t N, float* out, int64_t ldc,
                              const float* bias, int64_t bias_stride, int32_t relu, uint8_t* relu_bits, float* zero_out, uint32_t* amax_out, int32_t mode,
                              int32_t* launched, void* stream);
+/* ... over the row set's PACKED tiles (GM_PACK_ROWS; tests): keep and the tile flags on, three pieces, and the set's kept rows packed per set into the fewest tiles
+ * (gm_dense_agg_table 15 .. 20).  The launch walks the same tiles per workgroup as gm_dense_fused_gemm_rows; the packed ones are fed and stored at their own rows,
+ * every other tile issues its MFMAs alone.  The bytes of `out` are those of gm_dense_fused_gemm_rows with keep on, whatever live_on and grid. */
+int gm_dense_fused_gemm_packed(const gm_batch_t* b, int32_t rowset, int32_t grid, int32_t table, const float* x, int64_t ldx, int32_t K, const float* zside, int64_t ldz,
+                               const float* W, int64_t w_stride, int32_t N, float* out, int64_t ldc, const float* bias, int64_t bias_stride, int32_t relu,
+                               int32_t* launched, void* stream);
 /* One aggregate launch over one orientation of the batch (0: the in-edge CSR, transposed: the by-source CSR) with every option the library's own callers
  * set, exported for numerics tests of every aggregate kernel (agg.hip, agg_stream.hip):
  *   out[v, :width] = epi(|s_out[v]| * sum over the edges e of row v of w_e * X[src_e, :] + bias_t)      for the rows v of set t.
@@ -746,7 +752,10 @@ int gm_dense_aggregate(const gm_batch_t* b, int32_t transposed, int32_t x_src, c
  *   launch, + 4 with a block schedule of its own}, then {observable rows of more than two sources (hub rows included) of the centre set, of the set GM_F_OBS_E1
  *   keeps (-1 without the tables), rows GM_F_NORM_E1 keeps, 0}.
  * 13 / 14 (int32, one per GEMM row tile of 128 rows inside a set, gm_batch_info's tile count) the tile flags of GM_DEAD_TILES: 1 where some row of the tile is kept
- *   by GM_F_NORM_CENTRE / GM_F_NORM_E1, else 0. */
+ *   by GM_F_NORM_CENTRE / GM_F_NORM_E1, else 0.
+ * 15 .. 20 (int32; GM_PACK_ROWS) the same two row sets packed per set, ascending by row: 15 / 16 the packed row ids (up to the host's bound: per set its centres / the
+ *   in-edges of its centres, capped by its rows; set t's entries start at the prefix of those bounds), 17 / 18 the packed tile tables, three words {set, offset into
+ *   the packed arrays, rows <= 128} per tile (n counts words), 19 / 20 the number of packed tiles (one word): the sum over the sets of ceil(kept rows / 128). */
 int gm_dense_obs_lists(const gm_batch_t* b, int64_t* info, void* stream);
 int gm_dense_agg_info(const gm_batch_t* b, int32_t transposed, int64_t* info);
 int gm_dense_fuse_counts(const gm_batch_t* b, int64_t* counts);
@@ -757,6 +766,9 @@ int gm_dense_agg_table(const gm_batch_t* b, int32_t which, int32_t transposed, v
  * db_t[N] = sum_r dQ0[r, :N] -- through the split weight-gradient kernel's flagged-row variant.  Three pieces; dims as for modes 1 of gm_dense_gemm /
  * gm_dense_wgrad (K >= 64 here), GM_EINVAL otherwise. */
 int gm_dense_dz_centre(const gm_batch_t* b, const float* dQ, int32_t K, const float* W, int64_t w_stride, int32_t N, float* T, void* stream);
+/* gm_dense_dz_centre storing the centre rows of T only, with the centres' tile flags (GM_DEAD_TILES) and, pack != 0, over their packed tiles (GM_PACK_ROWS); grid:
+ * workgroups (0: the library's rule).  The other rows of T are left as they are. */
+int gm_dense_dz_centre_rows(const gm_batch_t* b, const float* dQ, int32_t K, const float* W, int64_t w_stride, int32_t N, float* T, int32_t pack, int32_t grid, void* stream);
 int gm_dense_wgrad_centre(const gm_batch_t* b, const float* x, int32_t Kx, const float* dQ, int32_t N, float* dW, int64_t dw_stride, float* db,
                           int64_t db_stride, void* stream);
 /* One level down (GM_DEAD_ROWS=2), exported for tests: the last layer's transposed aggregate  out[u, :] = mask[u, :] ? norm[u] * sum over the out-edges
