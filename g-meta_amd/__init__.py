@@ -23,6 +23,7 @@ from .heuristics import (DISTANCE_SCORES, DIST_UNREACHED, PAGERANK_SCORES, PAIR_
 from .sketches import NodeSketches  # noqa: F401
 from .propagate import PropagatedFeatures  # noqa: F401
 from .predictor import PairPredictor  # noqa: F401
+from .ranking import link_ranking, rank_counts, rank_metrics  # noqa: F401
 
 __all__ = ['GraphStore', 'Subgraphs', 'SubgraphBatch', 'collate', 'Classifier', 'Meta', 'hop_label_width', 'hop_labels_switch', 'link_tables_with_negatives',
            'PAIR_SCORES', 'link_auc', 'link_heuristic_auc', 'candidate_names', 'PATH_SCORES', 'local_path_index', 'katz_index', 'link_path_scores',
@@ -30,4 +31,4 @@ __all__ = ['GraphStore', 'Subgraphs', 'SubgraphBatch', 'collate', 'Classifier', 
            'DISTANCE_SCORES', 'DIST_UNREACHED', 'graph_distance_index', 'link_distance_scores', 'link_distance_auc',
            'link_distance_profiles', 'distance_profile_features',
            'NodeSketches', 'hll_cardinality', 'sketch_intersections', 'sketch_distance_profile', 'link_sketch_profiles', 'sketch_profile_features', 'link_sketch_features',
-           'PropagatedFeatures', 'link_propagated_features', 'PairPredictor']
+           'PropagatedFeatures', 'link_propagated_features', 'PairPredictor', 'rank_counts', 'rank_metrics', 'link_ranking']

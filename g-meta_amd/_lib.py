@@ -30,6 +30,13 @@ class HParams(C.Structure):
                 ('hoist_z1', C.c_int32), ('serialize', C.c_int32), ('sparse_bwd', C.c_int32), ('cone', C.c_int32)]
 
 
+RANK_MAX_K = 8          # GM_RANK_MAX_K: the K values one gm_rank_summary call takes
+
+
+class RankSummary(C.Structure):
+    _fields_ = [('n_pos', C.c_int64), ('n_pairs', C.c_int64), ('auc2', C.c_int64), ('rr_sum', C.c_double), ('hits', C.c_int64 * RANK_MAX_K)]
+
+
 vp, i32, i64, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
 PROTOTYPES = {
     'gm_last_error': (C.c_char_p, []),
@@ -64,6 +71,8 @@ PROTOTYPES = {
     'gm_prop_pair_mlp_tile': (i32, []),
     'gm_prop_pair_mlp_forward': (i32, [vp, vp, i64, i32, vp, i32, vp, i32, vp, vp]),
     'gm_prop_pair_mlp_step': (i32, [vp, vp, i64, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]),
+    'gm_rank_counts': (i32, [vp, i64, vp, i64, vp, vp, vp]),
+    'gm_rank_summary': (i32, [vp, i64, vp, i64, vp, vp, i32, vp, vp, vp]),
     'gm_store_neighbour_degrees': (i32, [vp, i32, vp, vp]),
     'gm_store_pair_candidates': (i32, [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp]),
     'gm_extract': (C.c_int, [vp, vp, i32, vp, i32, i32, i32, u64, i32, vp, vp]),

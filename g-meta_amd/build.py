@@ -15,6 +15,7 @@ SOURCES += ['pair_distance.hip', 'distance_profile.hip']   # shortest-path dista
 SOURCES += ['node_sketches.hip']   # ELPH / BUDDY neighbourhood sketches of all nodes over the same neighbour index: HyperLogLog + MinHash records per level, and the pair counts on them
 SOURCES += ['propagate.hip']       # BUDDY / SIGN hop-propagated node features of a whole parent graph over the store's in-edge CSR: norms, levels, and the row and pair readers on them
 SOURCES += ['pair_mlp.hip']        # the BUDDY pair predictor on those levels: the fused gather + fp32 MFMA forward, its loss, and the weight gradient that re-forms its input
+SOURCES += ['ranking.hip']         # rank counts of positive scores against negative scores, shared or per-positive ranges, and their reduction to Hits@K / MRR / AUC
 SOURCES += ['pair_walks.hip']      # walk counts of node pairs over the same neighbour index
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result']
 

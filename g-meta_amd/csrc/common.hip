@@ -383,6 +383,7 @@ const gm_knobs& gm_knob() {
         k.prop_chunk = env("GM_PROP_CHUNK", 0);
         k.prop_mib = env("GM_PROP_MIB", 0);
         k.pair_mlp_rows = env("GM_PAIR_MLP_ROWS", 0);
+        k.rank_sort_min = env("GM_RANK_SORT_MIN", 0);
     });
     return k;
 }
@@ -415,6 +416,7 @@ static int gm_knobs::* gm_find_knob(const char* name) {
         {"prop_chunk", &gm_knobs::prop_chunk}, {"GM_PROP_CHUNK", &gm_knobs::prop_chunk},
         {"prop_mib", &gm_knobs::prop_mib}, {"GM_PROP_MIB", &gm_knobs::prop_mib},
         {"pair_mlp_rows", &gm_knobs::pair_mlp_rows}, {"GM_PAIR_MLP_ROWS", &gm_knobs::pair_mlp_rows},
+        {"rank_sort_min", &gm_knobs::rank_sort_min}, {"GM_RANK_SORT_MIN", &gm_knobs::rank_sort_min},
     };
     for (const auto& e : tab)
         if (!strcmp(name, e.name)) return e.field;

@@ -302,6 +302,7 @@ struct gm_knobs {
     int prop_chunk;                // GM_PROP_CHUNK, gm_set_tuning("prop_chunk"): entries per segment of a hub row of gm_store_propagate_build (propagate.hip); 0 (default) = the library's choice.  The order of a row's fp32 sum, hence its low bits, belongs to it
     int prop_mib;                  // GM_PROP_MIB, gm_set_tuning("prop_mib"): MiB one gm_store_propagate_build may allocate; 0 (default) = the library's choice, 8 GiB.  The result does not depend on it
     int pair_mlp_rows;             // GM_PAIR_MLP_ROWS, gm_set_tuning("pair_mlp_rows"): pairs per chunk of gm_prop_pair_mlp_step (pair_mlp.hip), which bounds its dh scratch; 0 (default) = the library's choice.  The logits do not depend on it; the summation order of the loss and the gradients, hence their low bits, belongs to it
+    int rank_sort_min;             // GM_RANK_SORT_MIN, gm_set_tuning("rank_sort_min"): the N at or above which the shared mode of gm_rank_counts / gm_rank_summary (ranking.hip) sorts the negatives instead of sweeping them; 0 (default) = the library's choice, 1 = always, INT32_MAX = never.  The result does not depend on it
 };
 const gm_knobs& gm_knob();
 

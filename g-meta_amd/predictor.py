@@ -160,10 +160,19 @@ class PairPredictor:
         from .heuristics import _pair
         return np.asarray([_pair(nm) for nm in names], np.int64).reshape(-1, 3)
 
-    def link_scores(self, props_by_graph, names, extra=None, sketches=None):
+    def link_scores(self, props_by_graph, names, extra=None, sketches=None, as_torch=False):
         """float32 [len(names)]: .scores of the pairs named 'g_i_j' from props_by_graph[g], one call per graph, rows in the order of `names`.  `sketches`: a dict or a
-        sequence of NodeSketches by graph; the structure columns are then built on the device per call (.scores)."""
+        sequence of NodeSketches by graph; the structure columns are then built on the device per call (.scores).  as_torch=True: the logits of every graph stay
+        on the device and come back as one CUDA tensor (the same bits)."""
         trip = self._names(names)
+        if as_torch:
+            import torch
+            out = torch.zeros(len(trip), dtype=torch.float32, device='cuda')
+            for g in np.unique(trip[:, 0]).tolist():
+                at = np.nonzero(trip[:, 0] == g)[0]
+                out[torch.from_numpy(at).cuda()] = self.scores(props_by_graph[g], trip[at, 1:], None if extra is None else extra[at], as_torch=True,
+                                                               sketches=None if sketches is None else sketches[g])
+            return out
         out = np.zeros(len(trip), np.float32)
         for g in np.unique(trip[:, 0]).tolist():
             at = np.nonzero(trip[:, 0] == g)[0]
@@ -207,3 +216,9 @@ class PairPredictor:
         """link_auc of .link_scores against the 0 / 1 `labels`."""
         from .heuristics import link_auc
         return link_auc(self.link_scores(props_by_graph, names, extra, sketches), labels)
+
+    def ranking(self, props_by_graph, names, labels, ks=(20, 50, 100), extra=None, sketches=None, groups=None):
+        """link_ranking (Hits@K, MRR, AUC from rank counts) of .link_scores against the 0 / 1 `labels`: the logits of every graph stay on the device,
+        concatenated, and are ranked there -- nothing per pair is read back.  `groups` as in link_ranking."""
+        from .ranking import link_ranking
+        return link_ranking(self.link_scores(props_by_graph, names, extra, sketches, as_torch=True), labels, ks=ks, groups=groups)

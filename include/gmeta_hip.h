@@ -493,6 +493,41 @@ int32_t gm_prop_pair_mlp_forward(const gm_prop_t* p, const int32_t* d_pairs, int
 int32_t gm_prop_pair_mlp_step(const gm_prop_t* p, const int32_t* d_pairs, int64_t n, int32_t op, const float* d_extra /* [n, S] */, int32_t S, const float* d_labels /* [n] */,
                               const float* d_params, int32_t Hd, float* d_logits /* [n], may be NULL */, float* d_loss /* [1] */, float* d_grad /* [n_params] */, void* stream);
 
+/* ---- RANK COUNTS AND RANKING METRICS of device-resident scores (beyond the reference): the last stage of link prediction -- Hits@K, MRR and AUC of P positive
+ * scores against negative scores, from exact integer counts formed on the device; a few integers and one double leave it.  This comment is THE definition;
+ * tests/ranking_ref.py restates it by direct comparison.  d_pos: device float [P], d_neg: device float [N], d_neg_range: device int64 [P, 2] or NULL.
+ *   order        scores are compared as IEEE fp32 VALUES: -0.0 == +0.0, denormals are distinct values and never flushed, +-inf are ordinary values.  The
+ *                comparison runs on order-preserving integer keys, so the denormal mode of the device cannot matter: with u the bits of a score,
+ *                u = 0 where u == 0x80000000 (-0.0 -> +0.0), then key = u ^ (u >> 31 ? 0xFFFFFFFF : 0x80000000); a < b as floats iff key(a) < key(b) as uint32.
+ *   ranges       positive i is ranked against all N negatives where d_neg_range == NULL (the SHARED mode: the Hits@K protocol of ogbl-collab / -ppa / -ddi), else
+ *                against d_neg[b_i .. e_i) with (b_i, e_i) = d_neg_range[i] (the MRR protocol of ogbl-citation2).  Ranges may be empty, overlap and repeat.
+ *                N_i = the length of i's range (N in the shared mode).
+ *   counts       d_counts[i] = (gt_i, eq_i): the negatives of the range strictly greater than d_pos[i], and those equal to it.  Exact integers, a function of
+ *                d_pos[i] and the multiset of negatives in the range alone: not of P, of the other positives, of the order of the negatives, of the stream, or
+ *                of any tuning value.
+ *   summary      n_pos = P;  n_pairs = sum_i N_i;
+ *                hits[j] = the number of positives with gt_i + eq_i < h_ks[j]  (OGB's pos > k-th largest negative; a positive with N_i < K is a hit);
+ *                rr_sum  = sum_i 1 / (1 + gt_i + eq_i / 2) in fp64: the reciprocal of the mean of the optimistic and the pessimistic rank, exact in fp64, one
+ *                          IEEE division per positive.  Summed without float atomics: partial sums over fixed ranges of i, added in a fixed ascending order that
+ *                          belongs to P alone -- the same inputs give the same bits;
+ *                auc2    = sum_i (2 (N_i - gt_i - eq_i) + eq_i): twice the Mann-Whitney U, an exact integer.
+ *                The metrics are formed by the caller: hits@K = hits[j] / P,  mrr = rr_sum / P,  auc = (auc2 / 2.0) / (double)n_pairs.
+ *   paths        the shared mode either sweeps the negatives per positive or sorts their keys once and searches them; gm_set_tuning("rank_sort_min", v) /
+ *                GM_RANK_SORT_MIN: the N at or above which it sorts, 0 = the library's choice, 1 = always, INT32_MAX = never.  The integers are the same.
+ * gm_rank_counts stores the [P, 2] counts.  gm_rank_summary reduces them on the device into *h_out (host) for the n_k values of h_ks (host); where d_counts is
+ * not NULL it stores the counts too.  Both run on `stream`, take their scratch from the stream-ordered pool, write nothing outside [P, 2] and *h_out, read one
+ * record back and return after the stream has produced the result.  P == 0: GM_OK, a zero summary, nothing else is looked at.
+ * GM_EINVAL (the message names the value), before any launch: P or N negative or above INT32_MAX, n_k outside 0 .. GM_RANK_MAX_K, an h_ks[j] < 1, a NULL argument
+ * with work to do (d_neg may be NULL where N == 0; d_counts of the summary may be NULL), a negative rank_sort_min.  Found on the device, in the pass that forms
+ * the keys, and returned after the one read-back: a range with b < 0, e < b or e > N (no kernel walks a range of such a call), a NaN in either array.  On an
+ * error the contents of d_counts are unspecified and *h_out is untouched.  GM_ERANGE: P * N above 2^61 (n_pairs could pass it). */
+#define GM_RANK_MAX_K 8
+typedef struct gm_rank_summary { int64_t n_pos, n_pairs, auc2; double rr_sum; int64_t hits[GM_RANK_MAX_K]; } gm_rank_summary_t;
+int32_t gm_rank_counts(const float* d_pos, int64_t P, const float* d_neg, int64_t N, const int64_t* d_neg_range /* [P, 2] or NULL */, int64_t* d_counts /* [P, 2] */,
+                       void* stream);
+int32_t gm_rank_summary(const float* d_pos, int64_t P, const float* d_neg, int64_t N, const int64_t* d_neg_range /* [P, 2] or NULL */, const int64_t* h_ks, int32_t n_k,
+                        int64_t* d_counts /* [P, 2], may be NULL */, gm_rank_summary_t* h_out, void* stream);
+
 /* ---- Extraction: replaces Subgraphs.generate_subgraph / generate_subgraph_link_pred
  * (sdp.py:295-346: h-hop in-neighbour expansion, node sampling, G.subgraph) and dgl.batch
  * (sdp.py:399-406) for n_sets sets at once.  seeds/set_offsets are host arrays; set s owns seeds

@@ -86,6 +86,10 @@ def parse(argv=None):
                     help="where the sketch profile columns of --buddy are formed: 'host' = read the integers back and run the float64 estimators in numpy for every pair of "
                          "the train and test tables before the first step; 'device' = the predictor builds them per minibatch from the sketches "
                          "(NodeSketches.pair_features), nothing per pair is read back; needs --buddy > 0")
+    ap.add_argument('--rank_k', default='',
+                    help="K,K,... (up to 8 values, e.g. 20,50,100): after the ROC AUC line of every family the run scores (--heuristics, --pagerank, --distance, --buddy) "
+                         "print one more line with its Hits@K and MRR over the pairs of the test table -- every positive against all negatives, all graphs "
+                         "together, from rank counts formed on the device (gmeta_amd.link_ranking); '' = off")
     ap.add_argument('--readout', default='centre', choices=['centre', 'mean'],
                     help="what the head reads of every subgraph: 'centre' = the centre row (both endpoints' rows of a pair), as the reference; 'mean' = the mean "
                          "over all of its rows (the dgl.mean_nodes line the reference left commented out), one pooled vector for pairs too")
@@ -113,7 +117,28 @@ def parse(argv=None):
         raise SystemExit('--buddy %d trains a predictor of node PAIRS: it needs --link_pred_mode True' % a.buddy)
     if a.buddy_columns != 'host' and not a.buddy:
         raise SystemExit('--buddy_columns %s chooses where the columns of the --buddy predictor are formed: it needs --buddy > 0' % a.buddy_columns)
+    a.rank_ks = []
+    if a.rank_k:
+        try:
+            a.rank_ks = [int(k) for k in a.rank_k.split(',')]
+        except ValueError:
+            raise SystemExit('--rank_k %s: comma-separated integers, e.g. 20,50,100' % a.rank_k)
+        if not 1 <= len(a.rank_ks) <= 8 or min(a.rank_ks) < 1:
+            raise SystemExit('--rank_k %s: one to eight values of K, each at least 1' % a.rank_k)
+        if not (a.heuristics or a.pagerank or a.distance or a.buddy):
+            raise SystemExit('--rank_k %s ranks the scores of a family: it needs --heuristics, --pagerank, --distance or --buddy' % a.rank_k)
     return a
+
+
+def ranking_line(args, res, family, title, scores, labels):
+    """--rank_k: res['<family>_ranking'] = {score name: gmeta_amd.link_ranking} of the family's scores over the test table, and the line behind its AUC line."""
+    if not getattr(args, 'rank_ks', None):
+        return
+    res[family + '_ranking'] = {nm: gmeta_amd.link_ranking(sc, labels, ks=args.rank_ks) for nm, sc in scores.items()}
+    if int(os.environ.get('RANK', 0)) == 0:
+        fmt = lambda m: ' '.join(['Hits@%d %.4f' % (k, m['hits@%d' % k]) for k in args.rank_ks] + ['MRR %.4f' % m['mrr']])      # noqa: E731
+        one = len(scores) == 1
+        print('%s test' % title, '  '.join(fmt(m) if one else '%s %s' % (nm, fmt(m)) for nm, m in res[family + '_ranking'].items()))
 
 
 def main(args):
@@ -228,36 +253,53 @@ def main(args):
         res['heuristic_auc'] = gmeta_amd.link_heuristic_auc(store, names, labels, mask_target=bool(args.mask_target))
         if rank == 0:
             print('Heuristic test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['heuristic_auc'].items()))
+        if getattr(args, 'rank_ks', None):
+            from gmeta_amd.heuristics import link_heuristic_scores
+            sc = link_heuristic_scores(store, names, bool(args.mask_target))
+            ranking_line(args, res, 'heuristic', 'Heuristic', {nm: sc[:, k] for k, nm in enumerate(gmeta_amd.PAIR_SCORES)}, labels)
         if args.heuristics == 2:
             res['path_auc'] = gmeta_amd.link_path_auc(store, names, labels, mask_target=bool(args.mask_target))
             if rank == 0:
                 print('Path test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['path_auc'].items()))
+            if getattr(args, 'rank_ks', None):
+                w = gmeta_amd.link_path_scores(store, names, bool(args.mask_target))
+                ranking_line(args, res, 'path', 'Path', {'local_path': gmeta_amd.local_path_index(w), 'katz': gmeta_amd.katz_index(w)}, labels)
     if args.pagerank:
         from gmeta_amd.negatives import read_link_tables
         names, labels = (tables if tables is not None else read_link_tables(root))['test']
         res['pagerank_auc'] = gmeta_amd.link_pagerank_auc(store, names, labels, mask_target=bool(args.mask_target))
         if rank == 0:
             print('PageRank test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['pagerank_auc'].items()))
+        if getattr(args, 'rank_ks', None):
+            cols = gmeta_amd.link_pagerank_scores(store, names, bool(args.mask_target))
+            ranking_line(args, res, 'pagerank', 'PageRank', {'rooted_pagerank': gmeta_amd.rooted_pagerank_index(cols)}, labels)
     if args.distance:
         from gmeta_amd.negatives import read_link_tables
         names, labels = (tables if tables is not None else read_link_tables(root))['test']
         res['distance_auc'] = gmeta_amd.link_distance_auc(store, names, labels, mask_target=bool(args.mask_target), max_dist=args.distance)
         if rank == 0:
             print('Distance test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['distance_auc'].items()))
+        if getattr(args, 'rank_ks', None):
+            d = gmeta_amd.link_distance_scores(store, names, bool(args.mask_target), args.distance)
+            ranking_line(args, res, 'distance', 'Distance', {'graph_distance': gmeta_amd.graph_distance_index(d, args.distance)}, labels)
     if args.buddy:
         from gmeta_amd.negatives import read_link_tables
         both = tables if tables is not None else read_link_tables(root)
-        res['buddy_auc'] = buddy_auc(store, both['train'], both['test'], args.buddy, columns=args.buddy_columns)
+        logits = [] if getattr(args, 'rank_ks', None) else None
+        res['buddy_auc'] = buddy_auc(store, both['train'], both['test'], args.buddy, columns=args.buddy_columns, logits=logits)
         if rank == 0:
             print('BUDDY test AUC: %.4f' % res['buddy_auc'])
+        if getattr(args, 'rank_ks', None):
+            ranking_line(args, res, 'buddy', 'BUDDY', {'buddy': logits[0]}, both['test'][1])      # the fitted predictor's logits, still on the device
     return res
 
 
-def buddy_auc(store, train, test, epochs, hops=2, columns='host'):
+def buddy_auc(store, train, test, epochs, hops=2, columns='host', logits=None):
     """The two precomputed inputs of a BUDDY predictor for every graph (the levels of GraphStore.propagated_features and the sketches of GraphStore.sketches, both
     at `hops`), a gmeta_amd.PairPredictor fitted on the (names, labels) of `train`, and its ROC AUC over those of `test`.  No mask_target: both inputs describe the
     whole graph.  columns='host': the sketch profile columns of every pair of both tables are formed up front by the float64 host estimators;
-    'device': the predictor forms them per minibatch on the device from the sketches (PairPredictor.fit / .auc with sketches=)."""
+    'device': the predictor forms them per minibatch on the device from the sketches (PairPredictor.fit / .auc with sketches=).  `logits`: a list that
+    receives the fitted predictor's logits of `test` as one CUDA tensor (PairPredictor.link_scores(..., as_torch=True)), for --rank_k."""
     graphs = range(store.n_graphs)
     props = [store.propagated_features(g, hops=hops) for g in graphs]
     sketches = [store.sketches(g, hops=hops) for g in graphs]
@@ -265,11 +307,15 @@ def buddy_auc(store, train, test, epochs, hops=2, columns='host'):
         if columns == 'device':
             model = gmeta_amd.PairPredictor(store.feat_dim, hops, extra_dim=(hops + 2) ** 2, seed=222)
             model.fit(props, train[0], train[1], epochs=epochs, sketches=sketches)
+            if logits is not None:
+                logits.append(model.link_scores(props, test[0], sketches=sketches, as_torch=True))
             return model.auc(props, test[0], test[1], sketches=sketches)
         columns = lambda names: gmeta_amd.sketch_profile_features(gmeta_amd.link_sketch_profiles(sketches, names))      # noqa: E731
         x_train, x_test = columns(train[0]), columns(test[0])
         model = gmeta_amd.PairPredictor(store.feat_dim, hops, extra_dim=x_train.shape[1], seed=222)
         model.fit(props, train[0], train[1], extra=x_train, epochs=epochs)
+        if logits is not None:
+            logits.append(model.link_scores(props, test[0], extra=x_test, as_torch=True))
         return model.auc(props, test[0], test[1], extra=x_test)
     finally:
         for o in props + sketches:
