@@ -15,7 +15,7 @@ from .graphstore import GraphStore  # noqa: F401
 from .subgraphs import Subgraphs, SubgraphBatch, collate, hop_label_width, hop_labels_switch  # noqa: F401
 from .learner import Classifier  # noqa: F401
 from .meta import Meta  # noqa: F401
-from .negatives import link_tables_with_negatives  # noqa: F401
+from .negatives import link_holdout, link_tables_with_negatives  # noqa: F401
 from .heuristics import (DISTANCE_SCORES, DIST_UNREACHED, PAGERANK_SCORES, PAIR_SCORES, PATH_SCORES, candidate_names, distance_profile_features,  # noqa: F401
                          graph_distance_index, hll_cardinality, katz_index, link_distance_profiles, link_sketch_features, link_sketch_profiles,
                          link_auc, link_distance_auc, link_distance_scores, link_heuristic_auc, link_pagerank_auc, link_pagerank_scores, link_path_auc,
@@ -25,7 +25,7 @@ from .propagate import PropagatedFeatures  # noqa: F401
 from .predictor import PairPredictor  # noqa: F401
 from .ranking import link_ranking, rank_counts, rank_metrics  # noqa: F401
 
-__all__ = ['GraphStore', 'Subgraphs', 'SubgraphBatch', 'collate', 'Classifier', 'Meta', 'hop_label_width', 'hop_labels_switch', 'link_tables_with_negatives',
+__all__ = ['GraphStore', 'Subgraphs', 'SubgraphBatch', 'collate', 'Classifier', 'Meta', 'hop_label_width', 'hop_labels_switch', 'link_tables_with_negatives', 'link_holdout',
            'PAIR_SCORES', 'link_auc', 'link_heuristic_auc', 'candidate_names', 'PATH_SCORES', 'local_path_index', 'katz_index', 'link_path_scores',
            'link_path_auc', 'PAGERANK_SCORES', 'rooted_pagerank_index', 'link_pagerank_scores', 'link_pagerank_auc',
            'DISTANCE_SCORES', 'DIST_UNREACHED', 'graph_distance_index', 'link_distance_scores', 'link_distance_auc',

@@ -48,6 +48,10 @@ PROTOTYPES = {
     'gm_store_destroy': (None, [vp]),
     'gm_store_negative_pairs': (i32, [vp, i32, i64, u64, i32, vp, i64, vp, vp, vp]),
     'gm_store_has_edges': (i32, [vp, i32, vp, i64, vp, vp]),
+    'gm_store_without_edges': (i32, [vp, vp, vp, vp, vp]),
+    'gm_store_split_edges': (i32, [vp, i32, u64, u64, u64, vp, vp, i64, vp, vp]),
+    'gm_store_dims': (i32, [vp, i32, vp, vp, vp]),
+    'gm_store_read_csr': (i32, [vp, i32, i32, vp, vp, vp]),
     'gm_store_pair_scores': (i32, [vp, i32, vp, i64, i32, vp, vp]),
     'gm_store_pair_walks': (i32, [vp, i32, vp, i64, i32, vp, vp]),
     'gm_store_rooted_pagerank': (i32, [vp, i32, vp, i64, C.c_float, i32, vp, vp]),

@@ -16,6 +16,7 @@ SOURCES += ['node_sketches.hip']   # ELPH / BUDDY neighbourhood sketches of all 
 SOURCES += ['propagate.hip']       # BUDDY / SIGN hop-propagated node features of a whole parent graph over the store's in-edge CSR: norms, levels, and the row and pair readers on them
 SOURCES += ['pair_mlp.hip']        # the BUDDY pair predictor on those levels: the fused gather + fp32 MFMA forward, its loss, and the weight gradient that re-forms its input
 SOURCES += ['ranking.hip']         # rank counts of positive scores against negative scores, shared or per-positive ranges, and their reduction to Hits@K / MRR / AUC
+SOURCES += ['holdout.hip']         # a store derived on the device with a set of node pairs removed, and the hashed edge split that names such a set
 SOURCES += ['pair_walks.hip']      # walk counts of node pairs over the same neighbour index
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result']
 

@@ -1,5 +1,5 @@
 // Small device helpers that more than one translation unit needs bit for bit: the hash and salt behind every random word of the library (extract.hip's node
-// sampling, negatives.hip's candidate stream) and the word access of a membership bitmap that lives in LDS or in HBM (extract.hip, candidates.hip).
+// sampling, negatives.hip's candidate stream), the search of a sorted list of pair keys (negatives.hip, holdout.hip) and the word access of a membership bitmap that lives in LDS or in HBM (extract.hip, candidates.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,6 +18,18 @@ __host__ __device__ __forceinline__ uint32_t sample_salt(uint64_t seed, int g, i
     s = lowbias32(s ^ (uint32_t)i);
     s = lowbias32(s + (uint32_t)(j + 1) * 0xC2B2AE35u);
     return s;
+}
+
+// key in the ascending list keys[0 .. n) of canonical pair keys u * N + v (int64): the exclusion list of negatives.hip, the removal lists of holdout.hip
+__device__ __forceinline__ bool gm_key_listed(const int64_t* keys, int64_t n, int64_t key) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        const int64_t x = keys[mid];
+        if (x == key) return true;
+        if (x < key) lo = mid + 1; else hi = mid;
+    }
+    return false;
 }
 
 // Bitmap words live in LDS (G = false) or, for parent graphs too large for it, in a per-workgroup slab of global memory

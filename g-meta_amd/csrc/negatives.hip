@@ -12,7 +12,7 @@
 //   output is a function of the definition alone: not of R, not of the schedule.  The host reads one counter per round and stops at n or at the budget.
 // Everything runs on the caller's stream; the table and the scratch come from the stream-ordered pool and go back to it on that stream.
 #include "gm_internal.h"
-#include "gm_devutil.h"      // lowbias32, sample_salt: extract.hip's hash and salt (oracle.lowbias32 / oracle.sample_salt)
+#include "gm_devutil.h"      // lowbias32, sample_salt: extract.hip's hash and salt (oracle.lowbias32 / oracle.sample_salt); gm_key_listed: the search of the exclusion keys
 
 #define GM_NEG_SALT_TAG 0x6E454721      // the `i` of sample_salt(seed, g, i, mode) for this stream of random words
 #define GM_NEG_THREADS 256
@@ -45,17 +45,6 @@ __device__ __forceinline__ bool row_has(const neg_graph& G, int32_t u, int32_t v
 // an edge u -> v or v -> u, at any multiplicity
 __device__ __forceinline__ bool adjacent(const neg_graph& G, int32_t u, int32_t v) { return row_has(G, u, v) || (u != v && row_has(G, v, u)); }
 
-__device__ __forceinline__ bool key_listed(const int64_t* keys, int64_t n, int64_t key) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        const int64_t x = keys[mid];
-        if (x == key) return true;
-        if (x < key) lo = mid + 1; else hi = mid;
-    }
-    return false;
-}
-
 // candidate k in canonical form; false where the definition calls it invalid before any look at the pair (a dead end of the walk, u == v)
 __device__ __forceinline__ bool candidate(const neg_graph& G, uint32_t salt, int mode, uint32_t k, int32_t& u, int32_t& v) {
     const uint32_t w0 = salt + 4u * k;
@@ -86,7 +75,7 @@ k_neg_mark(neg_graph G, uint32_t salt, int mode, const int64_t* excl, int64_t n_
     int32_t u = -1, v = -1;
     bool ok = candidate(G, salt, mode, k, u, v);
     const int64_t key = (int64_t)u * G.N + v;
-    ok = ok && !adjacent(G, u, v) && !key_listed(excl, n_excl, key);
+    ok = ok && !adjacent(G, u, v) && !gm_key_listed(excl, n_excl, key);
     cand[i] = ok ? make_int2(u, v) : make_int2(-1, -1);
     if (!ok) return;
     // the table holds more than twice the keys a call can insert (the host sizes it): a free slot always ends the probe; the bound is a second fence

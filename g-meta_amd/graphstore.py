@@ -86,8 +86,52 @@ class GraphStore:
         self.handle = h
         self.n_graphs, self.n_nodes, self.feat_dim = G, ns, F0
         self.n_edges = [int(p[-1]) for p in ptrs]
-        self.host_csr = list(zip(ptrs, idxs))      # host copy of the in-edge CSR (Subgraphs(sample_mode='reference') walks it like sdp.py:301)
-        self.host_weights = wts if self.weighted else None      # per graph: the edge weights aligned with host_csr's indices
+        self._host_csr = list(zip(ptrs, idxs))      # host copy of the in-edge CSR (Subgraphs(sample_mode='reference') walks it like sdp.py:301)
+        self._host_weights = wts if self.weighted else None      # per graph: the edge weights aligned with host_csr's indices
+
+    @property
+    def host_csr(self):
+        """Per graph (indptr int64 [N + 1], indices int32 [E]): the host copy of the in-edge CSR.  A derived store (without_edges) reads it back from the
+        device at the first access (gm_store_read_csr), not at construction."""
+        if self._host_csr is None:
+            self._read_back()
+        return self._host_csr
+
+    @host_csr.setter
+    def host_csr(self, v):
+        self._host_csr = v
+
+    @property
+    def host_weights(self):
+        """Per graph the edge weights aligned with host_csr's indices (None for a store without weights); read back like host_csr on a derived store."""
+        if self.weighted and self._host_weights is None:
+            self._read_back()
+        return self._host_weights
+
+    @host_weights.setter
+    def host_weights(self, v):
+        self._host_weights = v
+
+    def read_csr(self, g, orientation=0):
+        """(indptr int64 [N + 1], indices int32 [E], weights float32 [E] or None) of graph `g` as the device holds it (gm_store_read_csr): orientation 0 = by
+        destination (the in-edge CSR, entries = sources), 1 = by source (entries = destinations)."""
+        g, _ = self._pairs_of(g, [], 'read_csr')
+        ptr = np.empty(self.n_nodes[g] + 1, np.int64)
+        idx = np.empty(self.n_edges[g], np.int32)
+        w = np.empty(self.n_edges[g], np.float32) if self.weighted else None
+        _lib.check(_lib.lib().gm_store_read_csr(self.handle, g, int(orientation), _lib.ptr(ptr), _lib.ptr(idx), _lib.ptr(w)), 'gm_store_read_csr')
+        return ptr, idx, w
+
+    def _read_back(self):
+        got = [self.read_csr(g) for g in range(self.n_graphs)]
+        self._host_csr = [(p, i) for p, i, _ in got]
+        self._host_weights = [w for _, _, w in got] if self.weighted else None
+
+    def dims(self, g):
+        """(nodes, stored edges, symmetric flag) of graph `g` as the library holds them (gm_store_dims); the flag is the store's, GM_EXTRACT_NO_SYM included."""
+        n, e, sym = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        _lib.check(_lib.lib().gm_store_dims(self.handle, int(g), C.byref(n), C.byref(e), C.byref(sym)), 'gm_store_dims')
+        return n.value, e.value, bool(sym.value)
 
     def symmetric(self):
         """True when every out-edge list equals the in-edge list element for element (undirected graphs stored in both directions with
@@ -167,7 +211,7 @@ class GraphStore:
             raise ValueError("mode must be 'uniform' or 'two_hop', not %r" % (mode,))
         n = int(n)
         g, ex = self._pairs_of(g, [] if exclude is None else exclude, 'negative_pairs(exclude=)')
-        keys = np.unique(np.minimum(ex[:, 0], ex[:, 1]) * self.n_nodes[g] + np.maximum(ex[:, 0], ex[:, 1]))      # canonical, keyed, sorted, unique
+        keys = self.pair_keys(g, ex)
         d_keys = torch.from_numpy(keys).cuda() if len(keys) else None
         out = torch.empty((max(n, 1), 2), dtype=torch.int32, device='cuda')
         found = C.c_int64(0)
@@ -177,6 +221,64 @@ class GraphStore:
             raise ValueError('negative_pairs: graph %d holds only %d distinct non-adjacent %s pair(s) within the draw budget of %d candidates; %d asked for'
                              % (g, found.value, mode, 64 * n + 4096, n))
         return out[:n].cpu().numpy().astype(np.int64)
+
+    def pair_keys(self, g, pairs):
+        """int64 [k]: the canonical keys min(a, b) * N + max(a, b) of the [m, 2] node `pairs` of graph `g`, sorted and unique -- the list format of
+        negative_pairs' exclusions and of without_edges.  Pairs may come in any orientation and may repeat; a pair (a, a) names the self loops of a."""
+        g, p = self._pairs_of(g, pairs, 'pair_keys')
+        return np.unique(np.minimum(p[:, 0], p[:, 1]) * self.n_nodes[g] + np.maximum(p[:, 0], p[:, 1]))      # canonical, keyed, sorted, unique
+
+    def without_edges(self, removed):
+        """A new GraphStore with the same nodes and features and every edge except those between the node pairs in `removed`, derived on the device
+        (gm_store_without_edges; the definition is in include/gmeta_hip.h, tests/holdout_ref.py restates it).  `removed`: {g: pairs [m, 2]} or a list with one entry
+        per graph (None: nothing); pairs in any orientation, duplicates allowed.  Removal is per pair: both directions and every parallel copy go, pairs that
+        name no edge are ignored, weights travel with their edges.  The result equals the store the constructor builds from the filtered edges, bit for bit,
+        and is independent of this one (either may be closed first): evaluate link prediction on it so that no structural input sees a held-out link."""
+        import torch
+        if isinstance(removed, dict):
+            bad = [g for g in removed if not (isinstance(g, (int, np.integer)) and 0 <= g < self.n_graphs)]
+            if bad:
+                raise ValueError('without_edges: graph %r of a store with %d graph(s)' % (bad[0], self.n_graphs))
+            removed = [removed.get(g) for g in range(self.n_graphs)]
+        elif len(removed) != self.n_graphs:
+            raise ValueError('without_edges: %d entries for a store with %d graph(s)' % (len(removed), self.n_graphs))
+        keys = [self.pair_keys(g, [] if r is None else r) for g, r in enumerate(removed)]
+        off = np.zeros(self.n_graphs + 1, np.int64)
+        off[1:] = np.cumsum([len(k) for k in keys])
+        d_keys = torch.from_numpy(np.concatenate(keys)).cuda() if off[-1] else None
+        h = C.c_void_p()
+        _lib.check(_lib.lib().gm_store_without_edges(self.handle, _lib.ptr(d_keys), _lib.ptr(off), C.byref(h), _lib.stream_ptr()), 'gm_store_without_edges')
+        new = object.__new__(GraphStore)
+        new.handle = h
+        new.n_graphs, new.feat_dim = self.n_graphs, self.feat_dim
+        new.weighted = bool(_lib.lib().gm_store_weighted(h))
+        d = [new.dims(g) for g in range(new.n_graphs)]
+        new.n_nodes, new.n_edges = [n for n, _, _ in d], [e for _, e, _ in d]
+        new._host_csr = new._host_weights = None      # read back at first access
+        return new
+
+    def split_edges(self, g, val=0.05, test=0.10, seed=222):
+        """(val_pairs int64 [n_v, 2], test_pairs int64 [n_t, 2]): a deterministic random split of the links of graph `g` -- the distinct node pairs u < v joined by an
+        edge in either direction, self loops aside -- decided per pair by a hash on the device (gm_store_split_edges; the definition is in include/gmeta_hip.h):
+        a link is test with probability `test`, validation with probability `val`, else it stays.  Each array ascends by u * N + v.  A function of the graph,
+        the seed and the fractions alone; without_edges({g: both}) takes the pairs out."""
+        import torch
+        from fractions import Fraction
+        g, _ = self._pairs_of(g, [], 'split_edges')
+        fv, ft = Fraction(val), Fraction(test)
+        if not (0 <= fv <= 1 and 0 <= ft <= 1 and fv + ft <= 1):
+            raise ValueError('split_edges: val = %r, test = %r; fractions in [0, 1] with val + test <= 1' % (val, test))
+        t_test, t_val = int(ft * 2 ** 32), int((ft + fv) * 2 ** 32)      # floor(fraction * 2^32) in exact arithmetic: no float reaches the ABI
+        cnt = (C.c_int64 * 3)()
+        call = lambda pairs, cls, cap: _lib.check(_lib.lib().gm_store_split_edges(self.handle, g, int(seed) & 0xFFFFFFFFFFFFFFFF, t_test, t_val, _lib.ptr(pairs),      # noqa: E731
+                                                                                   _lib.ptr(cls), cap, cnt, _lib.stream_ptr()), 'gm_store_split_edges')
+        call(None, None, 0)
+        n = int(cnt[1] + cnt[2])
+        pairs = torch.empty((max(n, 1), 2), dtype=torch.int32, device='cuda')
+        cls = torch.empty(max(n, 1), dtype=torch.uint8, device='cuda')
+        call(pairs, cls, n)
+        pairs, cls = pairs[:n].cpu().numpy().astype(np.int64), cls[:n].cpu().numpy()
+        return pairs[cls == 1], pairs[cls == 2]
 
     def has_edges(self, g, pairs):
         """bool [m]: whether graph `g` holds an edge between the two nodes of each of the [m, 2] `pairs`, in either direction (gm_store_has_edges: the

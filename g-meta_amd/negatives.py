@@ -78,3 +78,23 @@ def link_tables_with_negatives(store, tables, info, mode='uniform', seed=222):
             if parts:
                 out[s] = ([nm for names, _ in parts for nm in names], [l for _, labels in parts for l in labels])
     return out, info
+
+
+def link_holdout(store, tables, splits=('val', 'test')):
+    """The store without the positive pairs of the named `splits`: from a `tables=` dictionary (read_link_tables / link_tables_with_negatives: key ->
+    (names 'g_i_j', labels)) the pairs labelled 1 in each split's plain table -- or, where that is absent, in its _spt / _qry parts -- are collected per graph
+    and taken out with store.without_edges (gm_store_without_edges).  Score the validation and test pairs on the result: no structural input computed from
+    it -- neighbourhoods, walks, distances, sketches, propagated features -- holds a link that is being predicted.  Negative pairs name no edge and are
+    skipped.  The caller closes the returned store."""
+    removed = {}
+    for s in splits:
+        if s not in SPLITS:
+            raise ValueError('link_holdout: split %r; one of %s' % (s, ', '.join(SPLITS)))
+        keys = [s] if s in tables else [s + p for p in PARTS if s + p in tables]
+        for key in keys:
+            names, labels = tables[key]
+            for nm, lab in zip(names, labels):
+                if int(lab) == 1:
+                    g, i, j = _pair(nm)
+                    removed.setdefault(g, []).append((i, j))
+    return store.without_edges({g: np.asarray(p, np.int64).reshape(-1, 2) for g, p in removed.items()})

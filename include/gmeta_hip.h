@@ -129,6 +129,44 @@ int32_t gm_store_negative_pairs(const gm_store_t* s, int32_t g, int64_t n, uint6
                                 int64_t n_exclude, int32_t* d_out_pairs, int64_t* h_found, void* stream);
 int32_t gm_store_has_edges(const gm_store_t* s, int32_t g, const int32_t* d_pairs, int64_t n, uint8_t* d_out, void* stream);
 
+/* ---- HELD-OUT EDGES (beyond the reference): a store derived on the device from a resident one with a set of node pairs removed, and the deterministic
+ * random split of a graph's links that produces such a set -- the evaluation protocol of link prediction, where the graph the structural inputs are
+ * computed from holds none of the links being predicted.  This comment is THE definition; tests/holdout_ref.py restates it and the device result
+ * equals it bit for bit.
+ * gm_store_without_edges(s, d_keys, h_key_off, out, stream)
+ *   input    per graph g of the store (N_g nodes) a sorted, strictly ascending list of canonical keys u * N_g + v (int64), u <= v -- the format of
+ *            gm_store_negative_pairs' exclusion list; u == v names self loops.  The lists are concatenated over the graphs in d_keys (device);
+ *            h_key_off (host, [n_graphs + 1], h_key_off[0] = 0) gives their offsets.  Any list may be empty (d_keys may be NULL when all are).
+ *   effect   *out is a new, independent store (gm_store_destroy, in any order relative to s) with the nodes and features of s and every stored edge
+ *            a -> b of s except those whose canonical pair (min(a, b), max(a, b)) is listed for its graph: both directions and every parallel copy
+ *            go; keys that name no edge are ignored; edge weights travel with their edges.
+ *   contract the new store equals, bit for bit, the store gm_store_create / gm_store_create_weighted builds from the FILTERED in-CSR -- the rows of s
+ *            with the removed entries deleted and the stored order otherwise kept: both CSR orientations and their weights, the node and edge
+ *            offsets, the symmetric flag (decided on the device from the new arrays; env GM_EXTRACT_NO_SYM and a store without edges give false,
+ *            and a non-symmetric parent can become symmetric), the feature table, its stride, bound and host statistics (copied device to device).
+ *            The neighbour index is not copied: the new store builds its own at first use.
+ *   errors   GM_EINVAL for a NULL argument, offsets that are not monotone, a key outside [0, N_g^2) or a list that is not strictly ascending (checked
+ *            on the device in the same pass).  The call runs on `stream`, takes scratch from the stream-ordered pool and returns when the new
+ *            store is complete.
+ * gm_store_split_edges(s, g, seed, t_test, t_val, d_out_pairs, d_out_class, capacity, h_counts, stream): a Bernoulli split of the links of graph g,
+ * decided per pair by a hash: a function of (graph, seed, thresholds) alone.
+ *   links    the pairs (u, v), u < v, with v in the neighbour-index row of u (the distinct neighbours in either direction, as gm_store_pair_scores
+ *            defines them): distinct, self loops never count.
+ *   hash     s0 = sample_salt(seed, g, 0x53504C54, 0);  h(u, v) = lowbias32(lowbias32(s0 + (uint32)u) + (uint32)v) in 32-bit wrap-around arithmetic.
+ *   class    2 (test) if h < t_test; 1 (validation) if t_test <= h < t_val; 0 (train) otherwise.  0 <= t_test <= t_val <= 2^32 (GM_EINVAL otherwise); a
+ *            caller forms the thresholds as floor(fraction * 2^32) in integers.
+ *   output   h_counts (host, [3]) = {links, validation, test}.  With d_out_pairs == NULL only the counts are produced; otherwise the held-out pairs
+ *            (class 1 or 2) are written in ascending order of u * N + v to d_out_pairs (device int32 [n, 2]) and their classes to d_out_class (device
+ *            uint8 [n]; may be NULL).  GM_ERANGE if `capacity` (rows of d_out_pairs) is below the held-out count.
+ * gm_store_dims: nodes and stored edges of graph g, and the store's symmetric flag (any of the three may be NULL).  gm_store_read_csr: the CSR of graph
+ * g as the store holds it, orientation 0 = by destination (entries = sources), 1 = by source (entries = destinations): h_ptr (host int64 [N + 1],
+ * graph-local offsets), h_idx (host int32 [edges], graph-local ids), h_w (host fp32 [edges], weighted stores only; may be NULL).  Plain read-backs. */
+int32_t gm_store_without_edges(const gm_store_t* s, const int64_t* d_keys, const int64_t* h_key_off /* host [n_graphs + 1] */, gm_store_t** out, void* stream);
+int32_t gm_store_split_edges(const gm_store_t* s, int32_t g, uint64_t seed, uint64_t t_test, uint64_t t_val, int32_t* d_out_pairs, uint8_t* d_out_class,
+                             int64_t capacity, int64_t* h_counts /* host [3] */, void* stream);
+int32_t gm_store_dims(const gm_store_t* s, int32_t g, int64_t* n_nodes, int64_t* n_edges, int32_t* symmetric);
+int32_t gm_store_read_csr(const gm_store_t* s, int32_t g, int32_t orientation, int64_t* h_ptr, int32_t* h_idx, float* h_w);
+
 /* ---- NEIGHBOURHOOD HEURISTIC SCORES of node pairs (beyond the reference): the numbers a learned link predictor is held against -- common neighbours,
  * Jaccard, Adamic-Adar, resource allocation, preferential attachment -- for n pairs of one parent graph, on the device.  This comment is THE definition;
  * tests/pair_score_ref.py restates it with Python sets and fp64 sums.  Per parent graph g of a store, with N nodes:

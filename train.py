@@ -90,6 +90,11 @@ def parse(argv=None):
                     help="K,K,... (up to 8 values, e.g. 20,50,100): after the ROC AUC line of every family the run scores (--heuristics, --pagerank, --distance, --buddy) "
                          "print one more line with its Hits@K and MRR over the pairs of the test table -- every positive against all negatives, all graphs "
                          "together, from rank counts formed on the device (gmeta_amd.link_ranking); '' = off")
+    ap.add_argument('--holdout', type=int, default=0, choices=[0, 1],
+                    help='1 (--link_pred_mode True, with --heuristics, --pagerank, --distance or --buddy): score those families on the graphs WITHOUT the positive pairs of '
+                         'the validation and test tables (gmeta_amd.link_holdout: a store derived on the device), the protocol of the OGB link tasks -- no neighbourhood, '
+                         'walk, distance, sketch or propagated feature sees a link that is being predicted; their lines end in "(held out)".  The meta-learning path '
+                         'keeps the full graphs and --mask_target')
     ap.add_argument('--readout', default='centre', choices=['centre', 'mean'],
                     help="what the head reads of every subgraph: 'centre' = the centre row (both endpoints' rows of a pair), as the reference; 'mean' = the mean "
                          "over all of its rows (the dgl.mean_nodes line the reference left commented out), one pooled vector for pairs too")
@@ -117,6 +122,10 @@ def parse(argv=None):
         raise SystemExit('--buddy %d trains a predictor of node PAIRS: it needs --link_pred_mode True' % a.buddy)
     if a.buddy_columns != 'host' and not a.buddy:
         raise SystemExit('--buddy_columns %s chooses where the columns of the --buddy predictor are formed: it needs --buddy > 0' % a.buddy_columns)
+    if a.holdout and a.link_pred_mode != 'True':
+        raise SystemExit('--holdout 1 takes held-out node PAIRS out of the graphs: it needs --link_pred_mode True')
+    if a.holdout and not (a.heuristics or a.pagerank or a.distance or a.buddy):
+        raise SystemExit('--holdout 1 chooses the graphs a family is scored on: it needs --heuristics, --pagerank, --distance or --buddy')
     a.rank_ks = []
     if a.rank_k:
         try:
@@ -130,15 +139,17 @@ def parse(argv=None):
     return a
 
 
-def ranking_line(args, res, family, title, scores, labels):
-    """--rank_k: res['<family>_ranking'] = {score name: gmeta_amd.link_ranking} of the family's scores over the test table, and the line behind its AUC line."""
+def ranking_line(args, res, family, title, scores, labels, key='', tail=()):
+    """--rank_k: res['<family>_ranking'] = {score name: gmeta_amd.link_ranking} of the family's scores over the test table, and the line behind its AUC line.
+    --holdout: `key` behind the name in res, `tail` behind the line."""
     if not getattr(args, 'rank_ks', None):
         return
-    res[family + '_ranking'] = {nm: gmeta_amd.link_ranking(sc, labels, ks=args.rank_ks) for nm, sc in scores.items()}
+    family += '_ranking' + key
+    res[family] = {nm: gmeta_amd.link_ranking(sc, labels, ks=args.rank_ks) for nm, sc in scores.items()}
     if int(os.environ.get('RANK', 0)) == 0:
         fmt = lambda m: ' '.join(['Hits@%d %.4f' % (k, m['hits@%d' % k]) for k in args.rank_ks] + ['MRR %.4f' % m['mrr']])      # noqa: E731
         one = len(scores) == 1
-        print('%s test' % title, '  '.join(fmt(m) if one else '%s %s' % (nm, fmt(m)) for nm, m in res[family + '_ranking'].items()))
+        print('%s test' % title, '  '.join(fmt(m) if one else '%s %s' % (nm, fmt(m)) for nm, m in res[family].items()), *tail)
 
 
 def main(args):
@@ -246,58 +257,73 @@ def main(args):
     if args.predict_out and rank == 0:
         write_predictions(args.predict_out, model_max, db_test, info)
     res = {'test_acc': float(accs[-1]), 'early_stopped_test_acc': float(accs_max[-1]), 'val_best': float(max_acc)}
+    full, key, tail = store, '', ()
+    if getattr(args, 'holdout', 0):
+        # the families below score the test pairs in the graphs without the validation and test positives; Subgraphs / Meta above kept the full store
+        from gmeta_amd.negatives import read_link_tables
+        store, key, tail = gmeta_amd.link_holdout(full, tables if tables is not None else read_link_tables(root)), '_holdout', ('(held out)',)
+    try:
+        family_lines(args, res, store, tables, root, rank, key, tail)
+    finally:
+        if store is not full:
+            store.close()
+    return res
+
+
+def family_lines(args, res, store, tables, root, rank, key, tail):
+    """The baseline families of --heuristics / --pagerank / --distance / --buddy over the test table, scored on `store`: their entries of `res` (names end in
+    `key`) and their lines (end in `tail`)."""
     if args.heuristics:
         # the test table as the run used it: completed by --negatives where that drew the negative pairs, else the CSV's own
         from gmeta_amd.negatives import read_link_tables
         names, labels = (tables if tables is not None else read_link_tables(root))['test']
-        res['heuristic_auc'] = gmeta_amd.link_heuristic_auc(store, names, labels, mask_target=bool(args.mask_target))
+        res['heuristic_auc' + key] = gmeta_amd.link_heuristic_auc(store, names, labels, mask_target=bool(args.mask_target))
         if rank == 0:
-            print('Heuristic test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['heuristic_auc'].items()))
+            print('Heuristic test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['heuristic_auc' + key].items()), *tail)
         if getattr(args, 'rank_ks', None):
             from gmeta_amd.heuristics import link_heuristic_scores
             sc = link_heuristic_scores(store, names, bool(args.mask_target))
-            ranking_line(args, res, 'heuristic', 'Heuristic', {nm: sc[:, k] for k, nm in enumerate(gmeta_amd.PAIR_SCORES)}, labels)
+            ranking_line(args, res, 'heuristic', 'Heuristic', {nm: sc[:, k] for k, nm in enumerate(gmeta_amd.PAIR_SCORES)}, labels, key, tail)
         if args.heuristics == 2:
-            res['path_auc'] = gmeta_amd.link_path_auc(store, names, labels, mask_target=bool(args.mask_target))
+            res['path_auc' + key] = gmeta_amd.link_path_auc(store, names, labels, mask_target=bool(args.mask_target))
             if rank == 0:
-                print('Path test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['path_auc'].items()))
+                print('Path test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['path_auc' + key].items()), *tail)
             if getattr(args, 'rank_ks', None):
                 w = gmeta_amd.link_path_scores(store, names, bool(args.mask_target))
-                ranking_line(args, res, 'path', 'Path', {'local_path': gmeta_amd.local_path_index(w), 'katz': gmeta_amd.katz_index(w)}, labels)
+                ranking_line(args, res, 'path', 'Path', {'local_path': gmeta_amd.local_path_index(w), 'katz': gmeta_amd.katz_index(w)}, labels, key, tail)
     if args.pagerank:
         from gmeta_amd.negatives import read_link_tables
         names, labels = (tables if tables is not None else read_link_tables(root))['test']
-        res['pagerank_auc'] = gmeta_amd.link_pagerank_auc(store, names, labels, mask_target=bool(args.mask_target))
+        res['pagerank_auc' + key] = gmeta_amd.link_pagerank_auc(store, names, labels, mask_target=bool(args.mask_target))
         if rank == 0:
-            print('PageRank test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['pagerank_auc'].items()))
+            print('PageRank test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['pagerank_auc' + key].items()), *tail)
         if getattr(args, 'rank_ks', None):
             cols = gmeta_amd.link_pagerank_scores(store, names, bool(args.mask_target))
-            ranking_line(args, res, 'pagerank', 'PageRank', {'rooted_pagerank': gmeta_amd.rooted_pagerank_index(cols)}, labels)
+            ranking_line(args, res, 'pagerank', 'PageRank', {'rooted_pagerank': gmeta_amd.rooted_pagerank_index(cols)}, labels, key, tail)
     if args.distance:
         from gmeta_amd.negatives import read_link_tables
         names, labels = (tables if tables is not None else read_link_tables(root))['test']
-        res['distance_auc'] = gmeta_amd.link_distance_auc(store, names, labels, mask_target=bool(args.mask_target), max_dist=args.distance)
+        res['distance_auc' + key] = gmeta_amd.link_distance_auc(store, names, labels, mask_target=bool(args.mask_target), max_dist=args.distance)
         if rank == 0:
-            print('Distance test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['distance_auc'].items()))
+            print('Distance test AUC:', '  '.join('%s %.4f' % (k, v) for k, v in res['distance_auc' + key].items()), *tail)
         if getattr(args, 'rank_ks', None):
             d = gmeta_amd.link_distance_scores(store, names, bool(args.mask_target), args.distance)
-            ranking_line(args, res, 'distance', 'Distance', {'graph_distance': gmeta_amd.graph_distance_index(d, args.distance)}, labels)
+            ranking_line(args, res, 'distance', 'Distance', {'graph_distance': gmeta_amd.graph_distance_index(d, args.distance)}, labels, key, tail)
     if args.buddy:
         from gmeta_amd.negatives import read_link_tables
         both = tables if tables is not None else read_link_tables(root)
         logits = [] if getattr(args, 'rank_ks', None) else None
-        res['buddy_auc'] = buddy_auc(store, both['train'], both['test'], args.buddy, columns=args.buddy_columns, logits=logits)
+        res['buddy_auc' + key] = buddy_auc(store, both['train'], both['test'], args.buddy, columns=args.buddy_columns, logits=logits)
         if rank == 0:
-            print('BUDDY test AUC: %.4f' % res['buddy_auc'])
+            print('BUDDY test AUC: %.4f' % res['buddy_auc' + key], *tail)
         if getattr(args, 'rank_ks', None):
-            ranking_line(args, res, 'buddy', 'BUDDY', {'buddy': logits[0]}, both['test'][1])      # the fitted predictor's logits, still on the device
-    return res
+            ranking_line(args, res, 'buddy', 'BUDDY', {'buddy': logits[0]}, both['test'][1], key, tail)      # the fitted predictor's logits, still on the device
 
 
 def buddy_auc(store, train, test, epochs, hops=2, columns='host', logits=None):
     """The two precomputed inputs of a BUDDY predictor for every graph (the levels of GraphStore.propagated_features and the sketches of GraphStore.sketches, both
     at `hops`), a gmeta_amd.PairPredictor fitted on the (names, labels) of `train`, and its ROC AUC over those of `test`.  No mask_target: both inputs describe the
-    whole graph.  columns='host': the sketch profile columns of every pair of both tables are formed up front by the float64 host estimators;
+    whole graph of `store` -- pass gmeta_amd.link_holdout(store, tables) (train.py --holdout 1) so that neither holds a pair of `test` as an edge.  columns='host': the sketch profile columns of every pair of both tables are formed up front by the float64 host estimators;
     'device': the predictor forms them per minibatch on the device from the sketches (PairPredictor.fit / .auc with sketches=).  `logits`: a list that
     receives the fitted predictor's logits of `test` as one CUDA tensor (PairPredictor.link_scores(..., as_torch=True)), for --rank_k."""
     graphs = range(store.n_graphs)
