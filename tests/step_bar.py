@@ -292,7 +292,7 @@ def run_device(m, batch, K, feat=None):
         accs = np.asarray(m(xs, ys, xq, yq, None, None, None, None, None, None, feat)).copy()
         torch.cuda.synchronize()
         ms, n, wk = C.c_double(), C.c_int64(), C.c_int64()
-        for cat in (0, 1, 2, 4, 5, 6, 7):
+        for cat in (0, 1, 2, 4, 5, 6, 7, 14):      # (14: the weight gradients' accounted bytes, the A and G rows they read)
             lib.gm_profile_read(cat, C.byref(ms), C.byref(n), C.byref(wk))
             launches[cat], work[cat] = int(n.value), int(wk.value)
     finally:

@@ -44,6 +44,26 @@ SCHEDULE CLASSES, one representative each (variants that other tests prove bitwi
   undirected, T = 1                         the first task alone on the forced split kernels
   three layers / multiply-first layer       [128, 256, 256, 256] and [128, 256, 128] on the undirected world
   link prediction                           two centres per subgraph (the world of test_hip_dead_rows_diff.py)
+The flagged schedules at world size (section 5 of this file; multi-tile, multi-chunk launches).  Each path first shows from the launch accounting, against the
+dense run of the same model and batch, that the flag's own chain ran -- sparse_bwd_ok and make_ctx fall back to the dense schedule without a word -- and which
+kernel families served it (categories of gm_profile_read: 1 / 2 exact-fp32 GEMM / weight gradient, 4 / 5 split-bf16 GEMM / weight gradient).  The counts of one
+step and the byte ratios below are a RECORD of the run behind profiles/step_fp64.txt, printed again by every run (_hold_flagged) and not asserted: what is asserted
+is the inequality or the family named beside them, and a scheduling change may move the figures without failing anything:
+  undirected / directed, hoist_z1           Z_1 of a batch from one full aggregate launch, layer 1 on the ungathered split GEMM: 11 aggregate launches for the
+                                            default's 14; split GEMMs (14) and split weight gradients (8)
+  ... hoist_z1, GM_AGG_STREAM 1 (MIN_ROWS 0) the same on batches with stream tables: the hoisted Z_1 from k_agg_stream (stream segments asserted)
+  ... sparse_bwd                            gcn_backward_sparse behind PASS_PLAIN forwards: k_expand_edges, sparse_wgrad with a_row on k_wgrad (8), the transB GEMM
+                                            over the centre tiles on the exact-fp32 kernel (4), split GEMMs forward (10); 10 aggregate launches, the weight
+                                            gradients' accounted bytes about 1/34 (undirected) and 1/9 (directed) of the default's
+  ... cone, cone + hoist_z1                 cone_forward / cone_backward on the level tables of cone.hip (gm_batch_cone_dims ok = 1 on both batches, asserted before
+                                            the run): every GEMM exact-fp32 (14, none split), aggregate bytes priced on level rows; weight gradients on k_wgrad
+                                            (undirected, 8) or the split kernel (directed, whose fixture forces it, and undirected with
+                                            GM_WGRAD_SPLIT_MIN_CHUNKS = 0: 8); with the hoist 11 aggregate launches for cone's 14
+  undirected, T = 1, cone                   a level's set_off / set_chunk_off with nothing to cancel a per-set mix-up
+  three layers / multiply-first, cone       four levels (23 GEMMs, 12 weight gradients); [128, 256, 128]: k_colsum_rows, the source-level GEMM and the aggregate
+                                            behind it.  sparse_bwd = 1 on these two models falls back to the dense backward: pinned bitwise (results and launch
+                                            accounting) to the default run, not a class
+  link prediction, sparse_bwd / cone / cone + hoist_z1   two centres per subgraph, ok = 1 on both batches; under cone both weight-gradient families (4 + 4)
 Three-piece kernels only: the opt-in two-piece fp16 path has its own bound machinery.
 
 WHAT THE SEQUENTIAL ORDER IS FOR.  With numpy's blocked products alone in the yardstick, g7_wide_h2 (hidden 128, K = 3) exceeded the bar: task 0's prototypes of step
@@ -61,7 +81,7 @@ import torch
 import step_bar as sb
 from golden_util import CASES, NAN_CASES, Fixture
 from test_hip_dead_rows_diff import link_world      # noqa: F401  (a module fixture: the link-prediction world)
-from test_hip_dead_rows_fwd import _meta, _need_split, _world, tuning
+from test_hip_dead_rows_fwd import _bits, _meta, _need_split, _world, tuning
 
 pytestmark = pytest.mark.gpu
 FINITE = [c for c in CASES if c not in NAN_CASES]
@@ -81,6 +101,10 @@ HEADER = """# The whole meta-step against fp64 (tests/test_hip_step_numerics.py)
 # Ill-conditioned, not a measure of anything: g1_sampled_h2 grad/3 (and what it feeds).  Its layer-2 bias gradient is zero in exact arithmetic and the sign of
 # its rounding noise decides a relu' in the next inner step (DESIGN.md section 3), so the fp32 implementations themselves miss fp64 by ~4 % of the tensor there.
 # g8_wide_scales (feature scales 2^-20 .. 2^4) has yardsticks of 40 - 180 u.
+# Flagged schedules on the worlds ('... hoist_z1', '... sparse_bwd', '... cone', '... cone+hoist_z1', 'link ...'): against the reference of the dense paths (the
+# oracle has no schedule); each of these runs showed from its launch accounting that the flag's own chain ran.  Under cone every GEMM is on the exact-fp32 kernels.
+# 'directed agg_stream1' and 'directed hoist_z1 agg_stream1' equal 'directed default' and 'directed hoist_z1' digit for digit: those batches have stream tables, but
+# no row sum of theirs comes out in another association -- only the undirected blocks measure the stream kernel's order.
 """
 
 
@@ -238,6 +262,19 @@ def _stream_segments(w):
     return n
 
 
+def _default_dev(w, theta, config=None, name='default', batch_key='batch'):
+    """The dense schedule's run of one model on one batch of a world at default knobs, made once and kept: what a flagged run's launch accounting is compared
+    with, and what a flag that must fall back to the dense schedule has to reproduce bit for bit.  `name` names `config` (callers pass the pair _variant
+    returns, or the world's own model as 'default').  The kept result is shared between tests and is read only: nobody writes into its arrays or dicts."""
+    devs = w.setdefault('dev_default', {})
+    key = (name, batch_key)
+    if key not in devs:
+        devs[key] = _world_run(w, theta, config, batch_key)
+        if key == ('default', 'batch'):
+            w['acct_default'] = (devs[key]['launches'][0], devs[key]['work'][0])
+    return devs[key]
+
+
 PATHS = {
     'default': dict(),
     'fuse_diff0': dict(knobs=dict(GM_FUSE_DIFF=0)),
@@ -271,9 +308,7 @@ def test_world_step_at_every_launch_path(world, path, request):
             assert 0 < B.edges <= 8 * B.rows, (B.edges, B.rows)       # stream-eligible (gm_stream_batch_ok): a world that is not does not cover this class
         with tuning(GM_AGG_STREAM=1, GM_AGG_STREAM_MIN_ROWS=0):
             run_on = _fresh_stream_world(world, name)
-    if 'acct_default' not in world:
-        d0 = _world_run(world, theta, None)
-        world['acct_default'] = (d0['launches'][0], d0['work'][0])
+    _default_dev(world, theta)
     dev = _world_run(run_on, theta, None, **PATHS[path])
     n = dev['launches']
     assert n[6] == 0 and n[7] == 0                                    # never the two-piece kernels
@@ -314,16 +349,23 @@ def test_world_first_task_alone(undirected):
     _finish(rep)
 
 
-@pytest.mark.parametrize('dims', [[128, 256, 256, 256], [128, 256, 128]])
+VARIANTS = [[128, 256, 256, 256], [128, 256, 128]]
+
+
+def _variant(w, dims):
+    assert dims[0] == w['cfg']['F0']
+    config = [('GraphConv', [dims[l], dims[l + 1]]) for l in range(len(dims) - 1)] + [('Linear', [dims[-1], w['cfg']['n_way']])]
+    return 'x'.join(str(d) for d in dims), config
+
+
+@pytest.mark.parametrize('dims', VARIANTS)
 def test_model_variants(undirected, dims):
     """Three GraphConv layers, and a multiply-first last layer (in > out), at default knobs."""
     w = undirected
     _need_split(w, w['S'], w['Q'])
-    assert dims[0] == w['cfg']['F0']
-    config = [('GraphConv', [dims[l], dims[l + 1]]) for l in range(len(dims) - 1)] + [('Linear', [dims[-1], w['cfg']['n_way']])]
-    name = 'x'.join(str(d) for d in dims)
+    name, config = _variant(w, dims)
     theta, ref = _reference(w, name, config)
-    dev = _world_run(w, theta, config)
+    dev = _default_dev(w, theta, config, name)
     assert dev['launches'][4] > 0 and dev['launches'][5] > 0
     rep = sb.Report()
     sb.hold_all(rep, 'undirected %s' % name, ref, theta, dev)
@@ -334,8 +376,164 @@ def test_link_prediction(link_world):      # noqa: F811
     w = link_world
     assert w['S'].centres == 2 and w['Q'].centres == 2
     theta, ref = _reference(w, 'default', w['config'])
-    dev = _world_run(w, theta, w['config'])
+    dev = _default_dev(w, theta, w['config'])
     assert dev['launches'][4] > 0 and dev['launches'][5] > 0
     rep = sb.Report()
     sb.hold_all(rep, 'link default', ref, theta, dev)
     _finish(rep)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 5. the flagged schedules at world size
+# hoist_z1, sparse_bwd and cone run host chains and kernels of their own (cone_forward / cone_backward, gcn_backward_sparse, the hoisted full aggregate launch), and
+# each of them can fall back to the dense schedule without a word: sparse_bwd_ok refuses three layers and a multiply-first layer, make_ctx drops cone when
+# gm_batch_cone reports ok = 0, and the step drops it for both batches when either dropped it.  So no path below passes on numbers alone: each first shows from
+# the launch accounting (launches / algorithmic bytes per category, against the dense run of the same model, batch and knobs' defaults) that the flag changed what ran.
+FLAGGED = {
+    'hoist_z1': dict(hoist_z1=1),
+    'sparse_bwd': dict(sparse_bwd=1),
+    'cone': dict(cone=1),
+    'cone_hoist_z1': dict(cone=1, hoist_z1=1),
+}
+WGRAD_BYTES = 14      # launch-accounting category (test_hip_dead_rows_diff.py): the A and G rows of every weight-gradient launch
+
+
+def _n_gcn(w, config):
+    return sum(1 for kind, _ in (config or _default_config(w)) if kind == 'GraphConv')
+
+
+def _assert_cone_tables(w, config, batch_key):
+    """gm_batch_cone's verdict on both batches, before the run: with ok = 0 on either (a self pair among the centres) the step runs the dense schedule."""
+    from gmeta_amd import _lib
+    lib = _lib.lib()
+    L = _n_gcn(w, config)
+    b = w[batch_key]
+    for B in (b[0][0].view_of, b[2][0].view_of):
+        _lib.check(lib.gm_batch_prepare_cone(B.handle, L, None), 'prepare_cone')
+        ok = C.c_int32(); nrows = (C.c_int64 * (L + 1))(); nedges = (C.c_int64 * (L + 1))()
+        _lib.check(lib.gm_batch_cone_dims(B.handle, L, C.byref(ok), nrows, nedges), 'cone_dims')
+        assert ok.value == 1, 'no cone tables on this batch: cone = 1 would run the dense schedule'
+        assert nrows[L] == B.subs * B.centres and 0 < nrows[0] <= B.rows, (list(nrows), B.rows)
+
+
+def _flag_dev(w, theta, config, name, batch_key, flag):
+    """A flagged run at default knobs, kept (cone + hoist_z1 is compared with cone alone); read only, like _default_dev's."""
+    devs = w.setdefault('dev_flagged', {})
+    key = (name, batch_key, flag)
+    if key not in devs:
+        devs[key] = _world_run(w, theta, config, batch_key, **FLAGGED[flag])
+    return devs[key]
+
+
+def _hold_flagged(w, label, flag, theta, ref, config=None, name='default', batch_key='batch', knobs=None, run_on=None, dense=None):
+    """One flagged schedule of one model on one batch: the launch accounting shows that the flag's own chain ran, then every tensor is held to the bar.
+    dense: the run without the flag that the accounting is compared with, where that is not the default-knob run (a run under the same `knobs`)."""
+    on = run_on or w
+    cone = 'cone' in FLAGGED[flag]
+    if cone:
+        _assert_cone_tables(on, config, batch_key)
+    dev0 = dense or _default_dev(w, theta, config, name, batch_key)
+    dev = _world_run(on, theta, config, batch_key, knobs=knobs, **FLAGGED[flag]) if (knobs or run_on) else _flag_dev(w, theta, config, name, batch_key, flag)
+    n, wk, n0, wk0 = dev['launches'], dev['work'], dev0['launches'], dev0['work']
+    print('%s: launches %s bytes(0) %d bytes(14) %d; dense: launches %s bytes(0) %d bytes(14) %d' % (label, n, wk[0], wk[WGRAD_BYTES], n0, wk0[0], wk0[WGRAD_BYTES]))
+    assert n[6] == 0 and n[7] == 0                                                # never the two-piece kernels
+    assert n[0] > 0 and n[2] + n[5] > 0
+    if cone:
+        assert 0 < wk[0] < wk0[0], (wk[0], wk0[0])                                # priced on level rows (cone_agg_bytes)
+        assert n[4] == 0 and n[1] > 0, n                                          # no split weights under cone: every GEMM on the exact-fp32 kernels
+    if flag == 'cone_hoist_z1':
+        alone = _flag_dev(w, theta, config, name, batch_key, 'cone')['launches']
+        assert n[0] < alone[0], (n[0], alone[0])                                  # Z_1 of a batch formed once, not once per pass
+    if flag == 'sparse_bwd':
+        assert 0 < wk[WGRAD_BYTES] < wk0[WGRAD_BYTES], (wk[WGRAD_BYTES], wk0[WGRAD_BYTES])      # the weight gradients read the centre level and the centre-in-edge level alone
+        assert n[0] != n0[0] and wk[0] != wk0[0], (n[0], wk[0], n0[0], wk0[0])    # the differentiated passes planned PASS_PLAIN, no transposed aggregates behind them
+    if flag == 'hoist_z1':
+        assert n[0] < n0[0] and wk[0] != wk0[0], (n[0], wk[0], n0[0], wk0[0])     # fewer layer-1 aggregate launches
+    rep = sb.Report()
+    sb.hold_all(rep, label, ref, theta, dev)
+    _finish(rep)
+    return dev
+
+
+@pytest.mark.parametrize('flag', list(FLAGGED))
+def test_world_step_at_every_flagged_schedule(world, flag, request):
+    """undirected / directed at default knobs under hoist_z1, sparse_bwd, cone and cone + hoist_z1, against the reference of the dense paths (the oracle has no
+    schedule)."""
+    _need_split(world, world['S'], world['Q'])
+    name = request.node.callspec.params['world']
+    theta, ref = _reference(world, 'default', None)
+    _hold_flagged(world, '%s %s' % (name, flag.replace('cone_', 'cone+')), flag, theta, ref)
+
+
+def test_world_cone_on_the_split_weight_gradient(undirected):
+    """cone with GM_WGRAD_SPLIT_MIN_CHUNKS=0: the level chunk tables on the split-bf16 weight gradient (at default thresholds a cone level of the undirected world
+    stays on k_wgrad; the directed world forces the knob already)."""
+    w = undirected
+    theta, ref = _reference(w, 'default', None)
+    dev = _hold_flagged(w, 'undirected cone wgrad_split', 'cone', theta, ref, knobs=dict(GM_WGRAD_SPLIT_MIN_CHUNKS=0))
+    assert dev['launches'][5] > 0, dev['launches']
+
+
+def test_world_hoist_z1_with_the_stream_aggregate(world, request):
+    """hoist_z1 on batches with stream tables: the one place where the hoisted Z_1, a full aggregate launch, comes from k_agg_stream (another association inside
+    a hub row's sum than the window kernel's).  The accounting is compared with the dense run under the same stream knobs on the same batches, so that the
+    difference is the flag's alone.  On the undirected world the numbers move with the stream kernel; on the directed world the block is digit for digit the
+    'directed hoist_z1' block (as 'directed agg_stream1' is 'directed default'): its batches get stream tables (asserted) but no result moves by a digit,
+    so the directed case shows that this chain runs and holds, and adds no other order of summation."""
+    _need_split(world, world['S'], world['Q'])
+    name = request.node.callspec.params['world']
+    theta, ref = _reference(world, 'default', None)
+    for B in (world['S'], world['Q']):
+        assert 0 < B.edges <= 8 * B.rows, (B.edges, B.rows)       # stream-eligible (gm_stream_batch_ok)
+    knobs = dict(GM_AGG_STREAM=1, GM_AGG_STREAM_MIN_ROWS=0)
+    with tuning(**knobs):
+        run_on = _fresh_stream_world(world, name)
+    dense = _world_run(run_on, theta, None, knobs=knobs)
+    _hold_flagged(world, '%s hoist_z1 agg_stream1' % name, 'hoist_z1', theta, ref, knobs=knobs, run_on=run_on, dense=dense)
+    assert _stream_segments(run_on) > 0
+
+
+def test_world_first_task_alone_under_cone(undirected):
+    """T = 1 under cone: a per-set mix-up in a level's set_off / set_chunk_off cannot cancel in the task mean."""
+    w = undirected
+    theta, ref = _reference(w, 'default', None, 'one')
+    assert ref['T'] == 1
+    _hold_flagged(w, 'undirected T=1 cone', 'cone', theta, ref, batch_key='one')
+
+
+@pytest.mark.parametrize('dims', VARIANTS)
+def test_model_variants_under_cone(undirected, dims):
+    """Three GraphConv layers (four cone levels) and the multiply-first last layer under cone.  [128, 256, 128] is the path of k_colsum_rows (the bias gradient
+    of a multiply-first layer, summed over a set's centre rows), of the GEMM on the source level with the aggregate after it (cone_forward, fi > fo), and in the
+    backward of the transposed aggregate of dQ, the weight gradient over the source level's chunk table and the transB + mask_h GEMM on it."""
+    w = undirected
+    name, config = _variant(w, dims)
+    theta, ref = _reference(w, name, config)
+    _hold_flagged(w, 'undirected %s cone' % name, 'cone', theta, ref, config, name)
+
+
+@pytest.mark.parametrize('dims', VARIANTS)
+def test_model_variants_pin_the_sparse_bwd_fallback(undirected, dims):
+    """sparse_bwd_ok refuses more than two GCN layers and a multiply-first layer: sparse_bwd = 1 then runs the dense backward behind PASS_DIFF forwards.  Not a
+    schedule class: everything is bitwise the default run's, and the launch accounting is the same."""
+    w = undirected
+    name, config = _variant(w, dims)
+    theta, _ = _reference(w, name, config)
+    dev0 = _default_dev(w, theta, config, name)
+    dev = _world_run(w, theta, config, sparse_bwd=1)
+    for k in ('grad', 'losses', 'fw', 'protos', 'accs_task'):
+        assert dev[k].dtype == dev0[k].dtype and dev[k].shape == dev0[k].shape and np.array_equal(_bits(dev[k]), _bits(dev0[k])), k
+    assert len(dev['logits']) == len(dev0['logits']) == len(w['batch'][0])
+    for t, (a, b) in enumerate(zip(dev['logits'], dev0['logits'])):
+        a, b = np.asarray(a), np.asarray(b)
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(_bits(a), _bits(b)), t
+        assert np.array_equal(np.asarray(dev['pred'][t]), np.asarray(dev0['pred'][t])), t
+    assert dev['launches'] == dev0['launches'] and dev['work'] == dev0['work'], (dev['launches'], dev0['launches'], dev['work'], dev0['work'])
+
+
+@pytest.mark.parametrize('flag', ['sparse_bwd', 'cone', 'cone_hoist_z1'])
+def test_link_prediction_at_flagged_schedules(link_world, flag):      # noqa: F811
+    """Two centres per subgraph: the head with compact = 1 over pairs of centre rows, the centre level of twice the subgraphs."""
+    w = link_world
+    assert w['S'].centres == 2 and w['Q'].centres == 2
+    theta, ref = _reference(w, 'default', w['config'])
+    _hold_flagged(w, 'link %s' % flag.replace('cone_', 'cone+'), flag, theta, ref, w['config'])
